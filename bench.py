@@ -1,10 +1,21 @@
 #!/usr/bin/env python3
 """Forward-attention benchmark of the gfx950 FlashAttention-2 path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--no-cpu-baseline]
-                    [--steady-launches S] [--collectives] [--backend nccl|gloo] [--same-device]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+                    [--no-cpu-baseline] [--steady-launches S] [--collectives] [--backend nccl|gloo] [--same-device]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what `value` needs and nothing else: inputs -> one untimed call -> settle -> W warm-up -> K timed steps
+-> (--dump-outputs) -> the JSON line.  `--full` adds everything else the benchmark measures or checks, in the order of
+`sequence` below: the parity gate, the cold region, per-launch events, the steady and sustained re-timings, the determinism
+and dense-attention checks, the informational backward, the CPU baseline and, with N > 1 and no --workload, the c2
+weak-scaling figure.  Keys that only a --full run carries:
+cold, launch_ms, check, steady, sustained, backward, cpu_baseline, cpu_port, weak_c2.
+`--dump-outputs DIR` (rank 0) writes what the last timed step returned to the caller, the attention output o, as DIR/o.npy in
+float32: the whole [B,H,N,D] tensor when it fits in DUMP_BYTES, else a fixed, seeded sample of whole (batch, head) slices,
+[n,N,D] in ascending b*H+h order.  The inputs depend only on the workload and the rank (seeded on the device), so two builds
+given the same arguments can be compared output for output.
 
 A "step" is ONE forward call FlashAttentionFunction.apply(q, k, v, None, causal) — the same call the
 reference harness times (bench_with_sdpa.py:99, :136) — on synthetic torch.rand U[0,1) inputs
@@ -26,18 +37,18 @@ rule): scatter_batch of q/k/v and gather_batch of o (rocwmma_fattn/shard.py).
 refuses duplicate devices): the dry run the 1-GPU test suite uses; its numbers are not a scaling claim.
 
 Default workload: c2 with one rank; with N > 1 ranks and no --workload the run measures c5 — BASELINE.json's multi-GPU
-configuration (B = 64 split over the ranks, strong scaling) — as `value`, and then the c2 weak-scaling figure (every rank its own
-B2 shard) under the separate key `weak_c2`.
+configuration (B = 64 split over the ranks, strong scaling) — as `value`, and then (--full) the c2 weak-scaling figure (every rank
+its own B2 shard) under the separate key `weak_c2`.
 
 Rank 0 prints ONE JSON line.
   value        whole-job TFLOPS: all ranks' FLOPs / max-over-ranks wall time of the K steps, bracketed
                by barrier + synchronize (contract).  Measured AFTER the settle phase (below); `warmup` is the W of the command line,
-               `warmup_effective` every launch of the operator that preceded the timed region (gate + cold region + settle + W).
+               `warmup_effective` every launch of the operator that preceded the timed region (first call + settle + W; --full: gate + cold region + settle + W).
   cold         the same W warm-up + K timed steps run straight after the parity gate, BEFORE any settling — the protocol of rounds 1-3
                (and of a harness that only knows W): {"value", "ms_per_step", "kernel_ms"}; compare rounds on this key or on `steady`.
-  sequence     what the process does, in order (also in the JSON line): parity gate -> settle -> W warm-up + K
-               timed steps (the contract) -> K launches with per-launch events -> steady re-timing ->
-               informational backward -> CPU baseline.  The timed region carries no event between launches (one costs
+  sequence     what the process does, in order (also in the JSON line): (one untimed call; --full: parity gate -> cold region) -> settle -> W
+               warm-up + K timed steps (the contract) (--full: -> K launches with per-launch events -> steady re-timing ->
+               informational backward -> CPU baseline).  The timed region carries no event between launches (one costs
                1.6 %, tools/event_overhead.py).
   settle       before the warm-up the same call is launched in chunks of 25 for at least 150 ms and until six consecutive
                chunks agree within 1 % (at most `--settle N` launches, default 2000; checked bit-identical to the gate's output): after idle
@@ -66,6 +77,7 @@ import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -76,6 +88,7 @@ ROOT = os.path.dirname(os.path.realpath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
 
 MFMA_PEAK_TFLOPS = 2500.0  # dense fp16/bf16, MI355X_MICROARCH.md "Peak BF16/FP16 MFMA"
+DUMP_BYTES = 48 << 20      # --dump-outputs: float32 bytes of o written at most (the whole dump stays under 64 MB)
 
 WORKLOADS = {
     #       B   H   N     D    dtype            causal  scaling
@@ -157,6 +170,19 @@ def dense_head_check(q, k, v, o, causal, b, h):
     return float((o[b, h].float() - ref).abs().max())
 
 
+def dump_outputs(out_dir, o, seed):
+    """out_dir/o.npy: o in float32, whole when it fits in DUMP_BYTES, else the (batch, head) slices of a fixed seeded sample
+    (numpy default_rng(seed), ascending b*H+h) as [n, N, D]."""
+    import numpy as np
+    B, H, N, D = o.shape
+    head_bytes = N * D * 4
+    if B * H * head_bytes > DUMP_BYTES:
+        pick = np.sort(np.random.default_rng(seed).choice(B * H, size=DUMP_BYTES // head_bytes, replace=False))
+        o = o.reshape(B * H, N, D)[torch.from_numpy(pick).to(o.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "o.npy"), o.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -164,6 +190,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)   # past the DVFS ramp-up after idle
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None,
                     help="default: c2 with one rank; c5 (+ the c2 weak-scaling figure under `weak_c2`) with --gpus > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond `value` (gate, cold region, per-launch events, steady, sustained, "
+                         "checks, backward, CPU baseline, weak_c2); the options below that name one of them act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/o.npy (float32; a seeded sample of heads when larger than DUMP_BYTES)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--steady-launches", type=int, default=400, help="launches of the post-region steady re-timing (0 = skip)")
     ap.add_argument("--sustain-seconds", type=float, default=5.0,
@@ -185,7 +216,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` with no launcher around it: become the launcher.  One rank per GPU under
-        # torch.distributed.run on a free loopback port; rank 0 of the children prints the JSON line, this process is replaced.
+        # torch.distributed.run on a free loopback port in a child process; rank 0 of the children prints the JSON line, this
+        # process exits with the launcher's status.
         if not args.same_device:
             have = torch.cuda.device_count()
             if have < args.gpus:
@@ -198,7 +230,7 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.realpath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
     if world != args.gpus:
         args.gpus = world
     if not torch.cuda.is_available():
@@ -259,7 +291,8 @@ def main():
         return time.perf_counter() - t0, ev0.elapsed_time(ev1) / args.steps, o
 
     def measure(workload, extras):
-        """gate -> cold region -> settle -> contractual region (-> per-launch events, steady: `extras`) of one workload on this rank's shard."""
+        """(--full: gate -> cold region ->) settle -> contractual region (--full: -> checks, -> per-launch events, steady: `extras`) of one
+        workload on this rank's shard."""
         B, H, N, D, dtype, causal, scaling = WORKLOADS[workload]
         if scaling == "strong":
             lo, hi = shard_bounds(B, world, rank)
@@ -273,21 +306,29 @@ def main():
         r = {"workload": workload, "B": B, "H": H, "N": N, "D": D, "dtype": dtype, "causal": causal, "scaling": scaling,
              "B_local": B_local, "B_global": B_global, "cfg_idx": cfg_idx, "q": q, "k": k, "v": v}
 
-        # ---- parity gate BEFORE anything is timed: every (batch, head) of one forward call (a strided sample of 64 when there are
-        #      more) against dense fp32 attention on the GPU.
-        check_tol = 2e-3 if dtype == torch.float16 else 1.6e-2
-        o = attn(q, k, v, None, causal)
-        n_heads = B_local * H
-        picks = list(range(n_heads)) if n_heads <= 64 else [int(i * n_heads / 64) for i in range(64)]
-        gate_err = max(dense_head_check(q, k, v, o, causal, i // H, i % H) for i in picks)
-        assert gate_err <= check_tol, "output differs from dense fp32 attention before timing: %g" % gate_err
-        o_gate = o
-        launches = 1
+        launches = 0
+        o_gate = None
+        if args.full:
+            # ---- parity gate BEFORE anything is timed: every (batch, head) of one forward call (a strided sample of 64 when there are
+            #      more) against dense fp32 attention on the GPU.
+            check_tol = 2e-3 if dtype == torch.float16 else 1.6e-2
+            o = attn(q, k, v, None, causal)
+            n_heads = B_local * H
+            picks = list(range(n_heads)) if n_heads <= 64 else [int(i * n_heads / 64) for i in range(64)]
+            gate_err = max(dense_head_check(q, k, v, o, causal, i // H, i % H) for i in picks)
+            assert gate_err <= check_tol, "output differs from dense fp32 attention before timing: %g" % gate_err
+            o_gate = o
+            launches = 1
 
-        # ---- cold region: the contract's W + K straight after the gate, nothing settled — what rounds 1-3 reported as `value`, and what a harness
-        #      that only knows W warm-up launches sees.  Reported under `cold`; it also is the first stretch of load the settling below builds on.
-        cold_elapsed, cold_kernel_ms, _ = timed_region(q, k, v, causal)
-        launches += args.warmup + args.steps
+            # ---- cold region: the contract's W + K straight after the gate, nothing settled — what rounds 1-3 reported as `value`, and what a harness
+            #      that only knows W warm-up launches sees.  Reported under `cold`; it also is the first stretch of load the settling below builds on.
+            cold_elapsed, cold_kernel_ms, _ = timed_region(q, k, v, causal)
+            launches += args.warmup + args.steps
+        else:
+            # the first call loads the kernel's code object (milliseconds of idle GPU): kept out of the settle phase's 150 ms of load, as the gate does
+            attn(q, k, v, None, causal)
+            torch.cuda.synchronize()
+            launches = 1
 
         # ---- settling, stated plainly: after idle the chip boosts, overshoots its power budget, throttles and needs ~100 launches (25 ms) of THIS load to
         #      find its steady clock (profiles/r03_clock_settling.txt: the first 30 launches of a process run 15 % slower than the 100th; on other boxes
@@ -327,9 +368,11 @@ def main():
         # ---- contractual region: W untimed warm-up steps, then exactly K timed steps between barrier + synchronize
         elapsed, kernel_ms, o = timed_region(q, k, v, causal)
         launches += args.warmup
-        r.update({"elapsed": elapsed, "kernel_ms": kernel_ms, "cold_elapsed": cold_elapsed, "cold_kernel_ms": cold_kernel_ms,
-                  "settle": settle_info, "warmup_effective": launches, "gate_err": gate_err, "n_picks": len(picks), "n_heads": n_heads,
-                  "check_tol": check_tol})
+        r.update({"elapsed": elapsed, "kernel_ms": kernel_ms, "settle": settle_info, "warmup_effective": launches, "o": o})
+        if not args.full:
+            return r
+        r.update({"cold_elapsed": cold_elapsed, "cold_kernel_ms": cold_kernel_ms,
+                  "gate_err": gate_err, "n_picks": len(picks), "n_heads": n_heads, "check_tol": check_tol})
         assert torch.equal(o_gate, o), "the operator is not deterministic run to run (gate vs timed output)"
         if o_settled is not None:
             assert torch.equal(o_settled, o), "the operator is not deterministic run to run (settling phase)"
@@ -390,8 +433,7 @@ def main():
     B, H, N, D, dtype, causal, scaling = (m[x] for x in ("B", "H", "N", "D", "dtype", "causal", "scaling"))
     B_local, B_global, cfg_idx = m["B_local"], m["B_global"], m["cfg_idx"]
     q, k, v = m["q"], m["k"], m["v"]
-    elapsed, kernel_ms, per_launch, steady, settle_info = m["elapsed"], m["kernel_ms"], m["per_launch"], m["steady"], m["settle"]
-    check_err, check_tol, gate_err = m["check_err"], m["check_tol"], m["gate_err"]
+    elapsed, kernel_ms, settle_info = m["elapsed"], m["kernel_ms"], m["settle"]
 
     # ---- edge transfers (SURVEY §8e timing rule): reported separately, never part of `value`
     coll = None
@@ -422,7 +464,7 @@ def main():
 
     # ---- informational backward (reference harness style, bench_with_sdpa.py:78-88), outside the timed region
     bwd = None
-    if world == 1 and not args.no_backward:
+    if args.full and world == 1 and not args.no_backward:
         qg, kg, vg = (t.detach().requires_grad_(True) for t in (q, k, v))
         do = torch.rand_like(q)
         og = attn(qg, kg, vg, None, causal)
@@ -453,10 +495,13 @@ def main():
                "note": "bwd FLOPs = 2.5 x fwd (bench_with_sdpa.py:35-41); two deterministic passes (dQ: S, dP, dQ; dK/dV: S, dP, dV, dK) "
                        "recompute S and dP, so 7 GEMM-equivalents execute; time = wall of 30 autograd backward calls / 30 (HIP events)"}
 
-    elapsed, kernel_ms, cold_elapsed, cold_kernel_ms = max_over_ranks([elapsed, kernel_ms, m["cold_elapsed"], m["cold_kernel_ms"]])
+    if args.full:
+        elapsed, kernel_ms, cold_elapsed, cold_kernel_ms = max_over_ranks([elapsed, kernel_ms, m["cold_elapsed"], m["cold_kernel_ms"]])
+    else:
+        elapsed, kernel_ms = max_over_ranks([elapsed, kernel_ms])
     # ---- N > 1 with no --workload: the c2 weak-scaling figure (every rank its own B2 H16 N4096 D128 shard) next to the c5 line
     weak = None
-    if default_multi:
+    if default_multi and args.full:
         del q, k, v
         m.pop("q"), m.pop("k"), m.pop("v")
         torch.cuda.empty_cache()
@@ -478,6 +523,8 @@ def main():
         rank_info = {"backend": args.backend, "world_size": dist.get_world_size(), "ranks": gathered}
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, m["o"], 1234 + cfg_idx)
         flops_global = attention_flops(B_global, H, N, N, D, causal)
         flops_local = attention_flops(B_local, H, N, N, D, causal)
         value = flops_global * args.steps / elapsed / 1e12
@@ -497,27 +544,31 @@ def main():
             "metric": "fwd attention TFLOPS (and % MFMA roofline) at B2 H16 N4096 D128 fp16",
             "value": round(value, 2), "unit": "TFLOPS", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "warmup_effective": m["warmup_effective"],
-            "cold": {"value": round(flops_global * args.steps / cold_elapsed / 1e12, 2), "ms_per_step": round(cold_elapsed / args.steps * 1e3, 5),
-                     "kernel_ms": round(cold_kernel_ms, 5), "frac": round(flops_local / (cold_kernel_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                     "note": "the same W + K region straight after the parity gate, before the settle phase: the protocol of rounds 1-3"},
             "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": scaling,
             "vs_baseline": None, "dtype": "f16" if dtype == torch.float16 else "bf16", "data": "synthetic",
             "config": {"workload": "%s: B%d H%d N%d D%d %s causal=%s per GPU, BHND, torch.rand U[0,1)"
                                    % (args.workload, B_local, H, N, D, str(dtype)[6:], causal),
                        "global_batch": B_global, "parallelism": "batch-shard x%d (no data-path collective)" % world},
             "roofline": roof,
-            "sequence": ["parity_gate", "cold_warmup", "cold_timed", "settle", "warmup", "timed", "per_launch_events", "steady", "sustained", "backward_info", "cpu_baseline"],
+            "sequence": ["first_call", "settle", "warmup", "timed"],
             "settle": settle_info,
             "pct_of_mfma_roofline": round(100.0 * value / (MFMA_PEAK_TFLOPS * world), 2),
-            "launch_ms": {"min": round(min(per_launch), 5), "median": round(statistics.median(per_launch), 5),
-                          "max": round(max(per_launch), 5), "first": round(per_launch[0], 5), "last": round(per_launch[-1], 5)},
-            "check": {"max_abs_err_vs_dense_fp32": round(check_err, 6), "tol": check_tol, "head": [B_local - 1, H - 1],
-                      "gate_before_timing": {"heads_checked": m["n_picks"], "of": m["n_heads"], "max_abs_err": round(gate_err, 6)}},
         }
-        if steady is not None:
-            line["steady"] = steady
-        if m.get("sustained") is not None:
-            line["sustained"] = m["sustained"]
+        if args.full:
+            per_launch = m["per_launch"]
+            line["cold"] = {"value": round(flops_global * args.steps / cold_elapsed / 1e12, 2), "ms_per_step": round(cold_elapsed / args.steps * 1e3, 5),
+                            "kernel_ms": round(cold_kernel_ms, 5), "frac": round(flops_local / (cold_kernel_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                            "note": "the same W + K region straight after the parity gate, before the settle phase: the protocol of rounds 1-3"}
+            line["sequence"] = ["parity_gate", "cold_warmup", "cold_timed", "settle", "warmup", "timed", "per_launch_events", "steady", "sustained",
+                                "backward_info", "cpu_baseline"]
+            line["launch_ms"] = {"min": round(min(per_launch), 5), "median": round(statistics.median(per_launch), 5),
+                                 "max": round(max(per_launch), 5), "first": round(per_launch[0], 5), "last": round(per_launch[-1], 5)}
+            line["check"] = {"max_abs_err_vs_dense_fp32": round(m["check_err"], 6), "tol": m["check_tol"], "head": [B_local - 1, H - 1],
+                             "gate_before_timing": {"heads_checked": m["n_picks"], "of": m["n_heads"], "max_abs_err": round(m["gate_err"], 6)}}
+            if m["steady"] is not None:
+                line["steady"] = m["steady"]
+            if m["sustained"] is not None:
+                line["sustained"] = m["sustained"]
         if weak is not None:
             line["weak_c2"] = weak
         if rank_info is not None:
@@ -531,7 +582,7 @@ def main():
             line["collectives"] = coll
         if bwd is not None:
             line["backward"] = bwd
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], line["cpu_port"] = cpu_baseline(B * H, N, D, causal, dtype, 1234 + cfg_idx)
         print(json.dumps(line), flush=True)
     if use_dist:

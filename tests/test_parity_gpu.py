@@ -813,7 +813,7 @@ def test_bench_two_ranks_on_one_gpu_dry_run():
     for workload in ("c5",):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-               "--workload", workload, "--backend", "gloo", "--same-device", "--steady-launches", "0", "--collectives"]
+               "--workload", workload, "--backend", "gloo", "--same-device", "--steady-launches", "0", "--collectives", "--full"]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
         assert res.returncode == 0, res.stderr[-2000:]
         lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -839,7 +839,7 @@ def test_bench_self_launches_its_ranks():
     root = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--backend", "gloo", "--same-device", "--steady-launches", "0"]
+           "--backend", "gloo", "--same-device", "--steady-launches", "0", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -867,13 +867,53 @@ def test_bench_runs_the_rccl_path_with_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c2",
-           "--force-dist", "--collectives", "--steady-launches", "0", "--no-cpu-baseline", "--no-backward"]
+           "--force-dist", "--collectives", "--steady-launches", "0", "--no-cpu-baseline", "--no-backward", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     rec = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
     assert rec["n_gpus"] == 1 and rec["dist"]["backend"] == "nccl" and "dry_run" not in rec
     assert rec["collectives"]["backend"] == "nccl" and rec["collectives"]["world"] == 1
     assert rec["collectives"]["scatter_qkv_ms"] > 0 and rec["collectives"]["gather_o_ms"] > 0
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and prints the headline keys and none of the --full ones; --dump-outputs
+    writes the output of the last timed step — a seeded sample of whole heads of c2 here — and a second run with the same arguments writes the
+    same bytes (the inputs are fixed by the arguments).  The sampled heads are checked against dense attention of the same inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, res.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 7 and rec["warmup"] == 2 and rec["unit"] == "TFLOPS" and rec["higher_is_better"] is True and rec["dtype"] == "f16"
+        assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["metric"].startswith("fwd attention TFLOPS")
+        assert abs(rec["value"] - 4.0 * 2 * 16 * 4096 * 4096 * 128 / (rec["ms_per_step"] * 1e-3) / 1e12) <= 0.01 * rec["value"]
+        assert rec["warmup_effective"] == 1 + rec["settle"]["launches"] + 2
+        assert not set(rec) & {"cold", "launch_ms", "check", "steady", "sustained", "backward", "cpu_baseline", "cpu_port", "weak_c2"}
+        assert sorted(os.listdir(out)) == ["o.npy"]
+        dumps.append(np.load(out / "o.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.ndim == 3 and a.shape[1:] == (4096, 128) and 1 <= a.shape[0] < 32 and a.nbytes <= 64 << 20
+    assert np.array_equal(a, b)
+    # the same inputs and the same head sample as bench.py builds them (c2 = configuration 1 of the sorted workloads)
+    dev = _dev()
+    g = torch.Generator(device=dev).manual_seed(1234 + 1)
+    q, k, v = (torch.rand((2, 16, 4096, 128), generator=g, device=dev, dtype=torch.float32).half() for _ in range(3))
+    pick = np.sort(np.random.default_rng(1234 + 1).choice(32, size=a.shape[0], replace=False))
+    for i in (0, a.shape[0] - 1):
+        b_, h = divmod(int(pick[i]), 16)
+        s = (q[b_, h].float() @ k[b_, h].float().t()) * (128 ** -0.5)
+        ref = (torch.softmax(s, -1) @ v[b_, h].float()).cpu().numpy()
+        assert np.abs(a[i] - ref).max() <= 2e-3
 
 
 @pytest.mark.parametrize("shape", [(2, 10, 4096, 64), (2, 17, 4096, 64), (1, 24, 4096, 128), (3, 7, 2816, 128), (1, 20, 3500, 80)])

@@ -71,8 +71,8 @@ def test_two_rank_scatter_compute_gather(B):
 
 def test_bench_refuses_more_ranks_than_gpus_and_becomes_its_own_launcher(monkeypatch, capsys):
     """bench.py --gpus N without a launcher: (a) asks for N visible GPUs (none here -> a clear refusal, not a hang); (b) with
-    --same-device it replaces itself by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
-    --master-port <free> bench.py <same arguments>` (os.execv intercepted here)."""
+    --same-device it starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
+    --master-port <free> bench.py <same arguments>` as a child process and exits with its status (subprocess.call intercepted here)."""
     import importlib.util
     import sys
     root = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
@@ -88,14 +88,15 @@ def test_bench_refuses_more_ranks_than_gpus_and_becomes_its_own_launcher(monkeyp
         assert "only" in str(e.value) and "--gpus 8" in str(e.value)
     seen = {}
 
-    def fake_execv(exe, argv):
-        seen["exe"], seen["argv"] = exe, list(argv)
-        raise SystemExit(0)
+    def fake_call(argv):
+        seen["exe"], seen["argv"] = argv[0], list(argv)
+        return 3
 
-    monkeypatch.setattr(os, "execv", fake_execv)
+    monkeypatch.setattr(bench.subprocess, "call", fake_call)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--same-device"])
-    with pytest.raises(SystemExit):
+    with pytest.raises(SystemExit) as e:
         bench.main()
+    assert e.value.code == 3            # the launcher's exit status is the process's
     a = seen["argv"]
     assert seen["exe"] == sys.executable and a[1:3] == ["-m", "torch.distributed.run"]
     assert a[a.index("--nproc-per-node") + 1] == "2" and a[a.index("--master-addr") + 1] == "127.0.0.1"
