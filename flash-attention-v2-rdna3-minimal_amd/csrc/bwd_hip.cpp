@@ -25,12 +25,15 @@ namespace {
 
 constexpr bool kBF16 = FA2_TU_BF16 != 0;
 
+// (batch, K / V head) owners of the dK / dV passes: B * H / kv_group (grouped-query attention: one owner per K / V head)
+int64_t kv_owners(const fa2::BwdParams& p) { return (int64_t)p.B * (p.H / p.kv_group); }
+
 template <int HD, bool CAUSAL, int KSN, int DTN>
 int launch_bwd_pair(const fa2::BwdParams& p, hipStream_t stream) {
     constexpr int lds = 2 * (4 * fa2::Geo<HD, 8>::TILEB + 512) + 4 * 4096;
     constexpr auto kern = fa2::bwd_dkv_pair_kernel<HD, kBF16, CAUSAL, KSN, DTN>;
     if (int rc = fa2::set_lds<kern>(lds)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)p.B * p.H * p.nblk)), dim3(512), lds, stream, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(kv_owners(p) * p.nblk)), dim3(512), lds, stream, p);
     return (int)hipGetLastError();
 }
 
@@ -40,7 +43,8 @@ int launch_merge(const fa2::BwdParams& p, int which, hipStream_t stream) {
     if constexpr (HD <= 128) {
         fa2::BwdMergeParams m;
         m.ws = p.ws;
-        m.H = p.H; m.nbh = p.B * p.H; m.nblk = p.nblk; m.D = p.D;
+        m.H = which == 1 ? p.H : p.H / p.kv_group;      // the dK / dV tiles belong to K / V heads
+        m.nbh = p.B * m.H; m.nblk = p.nblk; m.D = p.D;
         m.full_items = p.full_items; m.split_items = p.split_items; m.nsplit = p.nsplit;
         if (which == 1) {
             m.out[0] = p.dq; m.out[1] = nullptr; m.mul[0] = p.scale; m.mul[1] = 0.f; m.nrows = p.Nq;
@@ -116,7 +120,7 @@ int launch_bwd_t(fa2::BwdParams p, int parts, hipStream_t stream) {
     if constexpr (HD == 128) {
         // D in 65..128: dK and dV in one sweep by wave pairs (bwd_dkv_pair_kernel): 128 KV rows per workgroup, S and P formed once
         p.nblk = (p.Nkv + 127) / 128;
-        if ((int64_t)p.B * p.H * p.nblk > 0x7fffffffLL) return FA2_ERR_GRID;
+        if (kv_owners(p) * p.nblk > 0x7fffffffLL) return FA2_ERR_GRID;
         return launch_bwd_pair<HD, CAUSAL, KSN, DTN>(p, stream);
     } else if constexpr (HD <= 64) {
         // D <= 64: both accumulators fit one wave, one sweep forms S and P once for dK and dV
@@ -124,7 +128,7 @@ int launch_bwd_t(fa2::BwdParams p, int parts, hipStream_t stream) {
         constexpr int lds = kStages * (4 * TILEB + 512);
         constexpr auto kern = fa2::bwd_dkv_kernel<HD, kBF16, CAUSAL, true, NW, true, HD, 0, KSN, DTN>;
         if ((rc = fa2::set_lds<kern>(lds))) return rc;
-        int64_t grid = (int64_t)p.B * p.H * p.nblk;
+        int64_t grid = kv_owners(p) * p.nblk;
         if constexpr (!CAUSAL) {
             if (sp_dkv.nsplit > 1) {
                 p.full_items = sp_dkv.full_items; p.split_items = sp_dkv.split_items; p.nsplit = sp_dkv.nsplit;
@@ -146,7 +150,7 @@ int launch_bwd_t(fa2::BwdParams p, int parts, hipStream_t stream) {
             static_assert(lds <= 160 * 1024, "LDS budget");
             constexpr auto kern = fa2::bwd_dkv_kernel<HD, kBF16, CAUSAL, true, NW, true, HD, 0, KSN, DTN>;
             if ((rc = fa2::set_lds<kern>(lds))) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)p.B * p.H * p.nblk)), dim3(NW * 64), lds, stream, p);
+            hipLaunchKernelGGL(kern, dim3((unsigned)(kv_owners(p) * p.nblk)), dim3(NW * 64), lds, stream, p);
             return (int)hipGetLastError();
         }
 #endif
@@ -154,14 +158,14 @@ int launch_bwd_t(fa2::BwdParams p, int parts, hipStream_t stream) {
             constexpr int lds = kStages * (2 * TILEB + 512);
             constexpr auto kern = fa2::bwd_dkv_kernel<HD, kBF16, CAUSAL, false, NW, false, HD, 0, KSN, DTN>;
             if ((rc = fa2::set_lds<kern>(lds))) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)p.B * p.H * p.nblk)), dim3(NW * 64), lds, stream, p);
+            hipLaunchKernelGGL(kern, dim3((unsigned)(kv_owners(p) * p.nblk)), dim3(NW * 64), lds, stream, p);
             if ((rc = (int)hipGetLastError())) return rc;
         }
         {
             constexpr int lds = kStages * (3 * TILEB + 512);
             constexpr auto kern = fa2::bwd_dkv_kernel<HD, kBF16, CAUSAL, true, NW, false, HD, 0, KSN, DTN>;
             if ((rc = fa2::set_lds<kern>(lds))) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)p.B * p.H * p.nblk)), dim3(NW * 64), lds, stream, p);
+            hipLaunchKernelGGL(kern, dim3((unsigned)(kv_owners(p) * p.nblk)), dim3(NW * 64), lds, stream, p);
             if ((rc = (int)hipGetLastError())) return rc;
         }
         return 0;
@@ -191,14 +195,14 @@ int launch_bwd_512(fa2::BwdParams p, int parts, hipStream_t stream) {
         constexpr int lds = TILEB + TILEBV + 512;
         constexpr auto kern = fa2::bwd_dkv_kernel<HD, kBF16, CAUSAL, false, NW, false, HDV, 0, KSN, HDV / 32>;
         if ((rc = fa2::set_lds<kern>(lds))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)p.B * p.H * p.nblk), (p.D + HDV - 1) / HDV), dim3(NW * 64), lds, stream, p);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(kv_owners(p) * p.nblk), (p.D + HDV - 1) / HDV), dim3(NW * 64), lds, stream, p);
         if ((rc = (int)hipGetLastError())) return rc;
     }
     {
         constexpr int lds = 2 * TILEB + TILEBV + 512;
         constexpr auto kern = fa2::bwd_dkv_kernel<HD, kBF16, CAUSAL, true, NW, false, HDV, 0, KSN, HDV / 32>;
         if ((rc = fa2::set_lds<kern>(lds))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)p.B * p.H * p.nblk), (p.D + HDV - 1) / HDV), dim3(NW * 64), lds, stream, p);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(kv_owners(p) * p.nblk), (p.D + HDV - 1) / HDV), dim3(NW * 64), lds, stream, p);
         if ((rc = (int)hipGetLastError())) return rc;
     }
     return 0;

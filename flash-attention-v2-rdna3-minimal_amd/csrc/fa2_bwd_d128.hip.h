@@ -124,8 +124,8 @@ __global__ __launch_bounds__(256, 1) void bwd_dq_d128_kernel(const BwdParams p) 
     const uint64_t gbase = (uint64_t)((const uint16_t*)p.dout + b * p.dos[0] + h * p.dos[1]);
     const uint64_t obase = (uint64_t)((const uint16_t*)p.o + b * p.os[0] + h * p.os[1]);
     const uint64_t lbase = (uint64_t)(p.lse + b * p.ls[0] + h * p.ls[1]);
-    const uint64_t ka = (uint64_t)((const uint16_t*)p.k + b * p.ks[0] + h * p.ks[1]);
-    const uint64_t va = (uint64_t)((const uint16_t*)p.v + b * p.vs[0] + h * p.vs[1]);
+    const uint64_t ka = (uint64_t)((const uint16_t*)p.k + b * p.ks[0] + (h / p.kv_group) * p.ks[1]);
+    const uint64_t va = (uint64_t)((const uint16_t*)p.v + b * p.vs[0] + (h / p.kv_group) * p.vs[1]);
     const bwd_u32x4s krs = {(uint32_t)ka, (uint32_t)(ka >> 32) & 0xffffu, p.k_bytes, 0x00020000u};
     const bwd_u32x4s vrs = {(uint32_t)va, (uint32_t)(va >> 32) & 0xffffu, p.v_bytes, 0x00020000u};
     const uint32_t k_tile = kBwdTile * k_rowb, v_tile = kBwdTile * v_rowb, k_row4 = 4 * k_rowb - 1024, v_row4 = 4 * v_rowb - 1024;

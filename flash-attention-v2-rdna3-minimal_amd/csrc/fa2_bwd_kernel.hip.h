@@ -57,6 +57,9 @@ struct BwdParams {
     int full_items, split_items, nsplit;
     float* ws;            // [split_items * nsplit] tiles of 256 x HD floats (the fused dK / dV pass: all dK tiles, then as many dV tiles)
     size_t ws_bytes;      // what the caller handed over
+    // grouped-query attention (fa2_bwd_gqa): Q head h reads K / V head h / kv_group; the dK / dV passes own the H / kv_group K / V heads and sum
+    // the gradients of their kv_group member Q heads in-kernel (1: one K / V head per Q head)
+    int kv_group = 1;
 };
 
 // f32 partial accumulator tile of a part -> workspace.  Layout of a tile: float (((dt*4 + g) * 256 + row) * 8 + 4*hi + e) for
@@ -341,8 +344,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
         if (hi == 0 && qrow < p.Nq && vcol0 == 0 && part <= 0) p.delta[b * p.ls[0] + h * p.ls[1] + qrow] = Dq;
     }
 
-    const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + h * p.ks[1];
-    const uint16_t* vbase = (const uint16_t*)p.v + b * p.vs[0] + h * p.vs[1];
+    const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + (h / p.kv_group) * p.ks[1];      // (grouped: the member's K / V head)
+    const uint16_t* vbase = (const uint16_t*)p.v + b * p.vs[0] + (h / p.kv_group) * p.vs[1];
     const auto krs = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, p.k_bytes, 0x00020000);
     const auto vrs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, p.v_bytes, 0x00020000);
     const uint32_t k_rowb = (uint32_t)p.ks[2] * 2u, v_rowb = (uint32_t)p.vs[2] * 2u;
@@ -573,8 +576,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // block -> (head, kv block); causal: the FIRST kv block sweeps the most Q tiles -> ascending kv block, across heads
-    const int nbh = p.B * p.H;
+    // block -> (head, kv block); causal: the FIRST kv block sweeps the most Q tiles -> ascending kv block, across heads.
+    // Grouped-query attention: the workgroup owns rows of K / V head h of the H / G ones and sweeps the Q tiles of its G member heads in turn
+    const int G = p.kv_group, Hkv = p.H / G;
+    const int nbh = p.B * Hkv;
     int bid = blockIdx.x;
     int part = -1, sidx = 0;               // split last round (fused pass only): see bwd_dq_kernel
     if constexpr (!CAUSAL && NW == 8 && BOTH) {
@@ -592,7 +597,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
         else { bh = (bid & 7) + 8 * (slot / p.nblk); kblk = slot % p.nblk; }
     } else if (CAUSAL) { bh = bid % nbh; kblk = bid / nbh; }
     else { bh = bid / p.nblk; kblk = bid % p.nblk; }
-    const int b = bh / p.H, h = bh % p.H;
+    const int b = bh / Hkv, h = bh % Hkv;     // K / V head (G = 1: also the Q head — the masked passes are never grouped)
     const int kv0 = kblk * kRows, kvw0 = kv0 + 32 * wave, kvrow = kvw0 + l31;   // this lane's KV row
     const int kr = kvrow < p.Nkv ? kvrow : p.Nkv - 1;
 
@@ -611,18 +616,23 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
             if constexpr (WANT_DK) vf[ks] = in ? *(const u32x4*)(vp + 16 * ks + 8 * hi) : (u32x4){0u, 0u, 0u, 0u};
         }
     }
-    const uint16_t* qbase = (const uint16_t*)p.q + b * p.qs[0] + h * p.qs[1];
-    const uint16_t* gbase = (const uint16_t*)p.dout + b * p.dos[0] + h * p.dos[1];
-    const auto qrs = __builtin_amdgcn_make_buffer_rsrc((void*)qbase, 0, p.q_bytes, 0x00020000);
-    const auto grs = __builtin_amdgcn_make_buffer_rsrc((void*)gbase, 0, p.do_bytes, 0x00020000);
-    const auto lrs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.lse + b * p.ls[0] + h * p.ls[1]), 0, p.l_bytes, 0x00020000);
-    const auto drs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.delta + b * p.ls[0] + h * p.ls[1]), 0, p.l_bytes, 0x00020000);
+    // Q / dO / L / delta descriptors of the member head being staged (rebuilt when the sweep crosses into the next member head)
+    auto q_rsrc = [&](int hq) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.q + b * p.qs[0] + hq * p.qs[1]), 0, p.q_bytes, 0x00020000); };
+    auto g_rsrc = [&](int hq) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.dout + b * p.dos[0] + hq * p.dos[1]), 0, p.do_bytes, 0x00020000); };
+    auto l_rsrc = [&](const float* base, int hq) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(base + b * p.ls[0] + hq * p.ls[1]), 0, p.l_bytes, 0x00020000); };
+    auto qrs = q_rsrc(h * G), grs = g_rsrc(h * G), lrs = l_rsrc(p.lse, h * G), drs = l_rsrc(p.delta, h * G);
     const uint32_t q_rowb = (uint32_t)p.qs[2] * 2u, g_rowb = (uint32_t)p.dos[2] * 2u;
 
-    // Q tiles that can touch this workgroup's KV rows: causal keeps only q >= kv (top-left aligned)
-    int ntiles = (p.Nq + kKvTile - 1) / kKvTile;
-    int tile0 = CAUSAL ? kv0 / kKvTile : 0;
-    if (part >= 0) { tile0 = part * ntiles / p.nsplit; ntiles = (part + 1) * ntiles / p.nsplit; }   // a part sweeps its share of the Q tiles
+    // Q tiles that can touch this workgroup's KV rows: causal keeps only q >= kv (top-left aligned).  The sweep is virtual: G member heads of
+    // `per` tiles each, every member restarting at tile0; vt in [vt0, vnt) is tile tile0 + vt % per of member vt / per
+    const int ntiles = (p.Nq + kKvTile - 1) / kKvTile;
+    const int tile0 = CAUSAL ? kv0 / kKvTile : 0;
+    const int per = ntiles > tile0 ? ntiles - tile0 : 0;
+    int vt0 = 0, vnt = G * per;
+    if (part >= 0) { vt0 = part * vnt / p.nsplit; vnt = (part + 1) * vnt / p.nsplit; }   // a part sweeps its share of the virtual sweep
     const int tile0_w = CAUSAL ? kvw0 / kKvTile : 0;     // this wave's first useful tile
 
     // per-lane source offsets of the staging loads within a tile (loop-invariant); the tile's own byte offset rides in soffset
@@ -847,14 +857,29 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
     // A wave whose 32 KV rows all lie past Nkv (cross-attention on a text prompt: 77 keys in a 256-row workgroup — five of eight waves) stages and
     // syncs, nothing else: its accumulators stay zero (a whole item never stores them, a part stores the zeros).  Round 6: that pass is issue-bound
     const bool wave_live = kvw0 < p.Nkv;
-    if (tile0 < ntiles) stage_load(tile0, 0);
+    // (member, tile) of the tile being computed and of the next one to stage.  Staging tile t + 1 may cross into the next member head, whose
+    // descriptors are rebuilt before its first load (the tile body reads LDS only and never needs them)
+    const int m0 = per ? vt0 / per : 0;
+    int tile = tile0 + (per ? vt0 % per : 0), stile = tile, sm = m0, smem_m = m0;
+    if (m0 != 0) { const int hq = h * G + m0; qrs = q_rsrc(hq); grs = g_rsrc(hq); lrs = l_rsrc(p.lse, hq); drs = l_rsrc(p.delta, hq); }
+    auto stage_next = [&](int stage) __attribute__((always_inline)) {
+        if (sm != smem_m) {
+            smem_m = sm;
+            const int hq = h * G + sm;
+            qrs = q_rsrc(hq); grs = g_rsrc(hq); lrs = l_rsrc(p.lse, hq); drs = l_rsrc(p.delta, hq);
+        }
+        stage_load(stile, stage);
+        if (++stile == ntiles) { stile = tile0; ++sm; }
+    };
+    if (vt0 < vnt) stage_next(0);
     __syncthreads();
-    for (int tile = tile0; tile < ntiles; ++tile) {
-        const int st = DBUF ? (tile - tile0) & 1 : 0;
-        if (DBUF && tile + 1 < ntiles) stage_load(tile + 1, st ^ 1);
+    for (int vt = vt0; vt < vnt; ++vt) {
+        const int st = DBUF ? (vt - vt0) & 1 : 0;
+        if (DBUF && vt + 1 < vnt) stage_next(st ^ 1);
         if ((!CAUSAL || tile >= tile0_w) && wave_live) tile_body(tile, st, CAUSAL && tile < first_plain);
         __syncthreads();
-        if (!DBUF && tile + 1 < ntiles) { stage_load(tile + 1, 0); __syncthreads(); }
+        if (!DBUF && vt + 1 < vnt) { stage_next(0); __syncthreads(); }
+        if (++tile == ntiles) tile = tile0;
     }
     if constexpr (!CAUSAL && NW == 8 && BOTH) {
         if (part >= 0) {                   // unscaled f32 partial dK and dV tiles
@@ -908,7 +933,9 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
     const bool ds_side = wave >= 4;
     const lds_char_ptr xch = smem + 2 * STAGEB + grp * XCHB + lane * 16;
 
-    const int nbh = p.B * p.H, bid = blockIdx.x;
+    // grouped-query attention: K / V head h of the H / G ones, the Q tiles of its G member heads swept in turn (see bwd_dkv_kernel)
+    const int G = p.kv_group, Hkv = p.H / G;
+    const int nbh = p.B * Hkv, bid = blockIdx.x;
     int bh, kblk;
     if ((nbh & 7) == 0) {
         const int slot = bid >> 3, hpx = nbh >> 3;
@@ -916,7 +943,7 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
         else { bh = (bid & 7) + 8 * (slot / p.nblk); kblk = slot % p.nblk; }
     } else if (CAUSAL) { bh = bid % nbh; kblk = bid / nbh; }
     else { bh = bid / p.nblk; kblk = bid % p.nblk; }
-    const int b = bh / p.H, h = bh % p.H;
+    const int b = bh / Hkv, h = bh % Hkv;
     const int kv0 = kblk * kRows, kvw0 = kv0 + 32 * grp, kvrow = kvw0 + l31;
     const int kr = kvrow < p.Nkv ? kvrow : p.Nkv - 1;
 
@@ -930,16 +957,19 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
         for (int ks = 0; ks < KS; ++ks)
             bf[ks] = 16 * ks + 8 * hi < p.D ? *(const u32x4*)(rp + 16 * ks + 8 * hi) : (u32x4){0u, 0u, 0u, 0u};
     }
-    const uint16_t* qbase = (const uint16_t*)p.q + b * p.qs[0] + h * p.qs[1];
-    const uint16_t* gbase = (const uint16_t*)p.dout + b * p.dos[0] + h * p.dos[1];
-    const auto qrs = __builtin_amdgcn_make_buffer_rsrc((void*)qbase, 0, p.q_bytes, 0x00020000);
-    const auto grs = __builtin_amdgcn_make_buffer_rsrc((void*)gbase, 0, p.do_bytes, 0x00020000);
-    const auto lrs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.lse + b * p.ls[0] + h * p.ls[1]), 0, p.l_bytes, 0x00020000);
-    const auto drs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.delta + b * p.ls[0] + h * p.ls[1]), 0, p.l_bytes, 0x00020000);
+    // Q / dO / L / delta descriptors of the member head being staged (rebuilt when the sweep crosses into the next member head)
+    auto q_rsrc = [&](int hq) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.q + b * p.qs[0] + hq * p.qs[1]), 0, p.q_bytes, 0x00020000); };
+    auto g_rsrc = [&](int hq) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((const uint16_t*)p.dout + b * p.dos[0] + hq * p.dos[1]), 0, p.do_bytes, 0x00020000); };
+    auto l_rsrc = [&](const float* base, int hq) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(base + b * p.ls[0] + hq * p.ls[1]), 0, p.l_bytes, 0x00020000); };
+    auto qrs = q_rsrc(h * G), grs = g_rsrc(h * G), lrs = l_rsrc(p.lse, h * G), drs = l_rsrc(p.delta, h * G);
     const uint32_t q_rowb = (uint32_t)p.qs[2] * 2u, g_rowb = (uint32_t)p.dos[2] * 2u;
 
     const int ntiles = (p.Nq + kKvTile - 1) / kKvTile;
     const int tile0 = CAUSAL ? kv0 / kKvTile : 0;
+    const int vnt = G * (ntiles > tile0 ? ntiles - tile0 : 0);      // the virtual sweep: G member heads, each from tile0
     const int first_plain = CAUSAL ? (kvw0 + 31 + kKvTile - 1) / kKvTile : 0;
 
     // per-lane source offsets of the staging loads within a tile (loop-invariant); the tile's own byte offset rides in soffset
@@ -993,12 +1023,23 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
     // accumulator registers at the join in every iteration.  Both loops hold the same two barriers per tile.
     // (A pair whose rows all lie above a tile's q range — the first tile of groups 2, 3 under a causal mask — runs the tile like
     //  any other: every P is masked to zero, so it contributes nothing.)
-    if (tile0 < ntiles) stage_load(tile0, 0);
+    int stile = tile0, sm = 0, smem_m = 0;        // the next tile to stage, its member head, the member the descriptors describe
+    auto stage_next = [&](int stage) __attribute__((always_inline)) {
+        if (sm != smem_m) {
+            smem_m = sm;
+            const int hq = h * G + sm;
+            qrs = q_rsrc(hq); grs = g_rsrc(hq); lrs = l_rsrc(p.lse, hq); drs = l_rsrc(p.delta, hq);
+        }
+        stage_load(stile, stage);
+        if (++stile == ntiles) { stile = tile0; ++sm; }
+    };
+    if (vnt > 0) stage_next(0);
     __syncthreads();
+    int tile = tile0;
     if (!ds_side) {
-        for (int tile = tile0; tile < ntiles; ++tile) {
-            const int st = (tile - tile0) & 1;
-            if (tile + 1 < ntiles) stage_load(tile + 1, st ^ 1);
+        for (int vt = 0; vt < vnt; ++vt, tile = tile + 1 == ntiles ? tile0 : tile + 1) {
+            const int st = vt & 1;
+            if (vt + 1 < vnt) stage_next(st ^ 1);
             const lds_char_ptr qR = smem + st * STAGEB;
             const lds_char_ptr lt = qR + NT * TILEB;
             f32x16 s0, s1;
@@ -1046,9 +1087,9 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
             __syncthreads();
         }
     } else {
-        for (int tile = tile0; tile < ntiles; ++tile) {
-            const int st = (tile - tile0) & 1;
-            if (tile + 1 < ntiles) stage_load(tile + 1, st ^ 1);
+        for (int vt = 0; vt < vnt; ++vt, tile = tile + 1 == ntiles ? tile0 : tile + 1) {
+            const int st = vt & 1;
+            if (vt + 1 < vnt) stage_next(st ^ 1);
             const lds_char_ptr qR = smem + st * STAGEB;
             const lds_char_ptr lt = qR + NT * TILEB;
             const lds_char_ptr gR = qR + TILEB;

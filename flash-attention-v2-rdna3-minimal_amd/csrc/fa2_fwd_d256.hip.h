@@ -63,8 +63,8 @@ __global__ __launch_bounds__(256, 1) void fwd_asm_d256_kernel(const FwdParams p)
     const uint32_t q_off = n16 * q_rowb + 16u * g4, o_off = n16 * o_rowb + 8u * g4;
 
     const uint64_t qa = (uint64_t)((const uint16_t*)p.q + b * p.qs[0] + h * p.qs[1]);
-    const uint64_t ka = (uint64_t)((const uint16_t*)p.k + b * p.ks[0] + h * p.ks[1]);
-    const uint64_t va = (uint64_t)((const uint16_t*)p.v + b * p.vs[0] + h * p.vs[1]);
+    const uint64_t ka = (uint64_t)((const uint16_t*)p.k + b * p.ks[0] + (h / p.kv_group) * p.ks[1]);
+    const uint64_t va = (uint64_t)((const uint16_t*)p.v + b * p.vs[0] + (h / p.kv_group) * p.vs[1]);
     const uint64_t oa = (uint64_t)((uint16_t*)p.o + b * p.os[0] + h * p.os[1]);
     const d256_u32x4s qrs = {(uint32_t)qa, (uint32_t)(qa >> 32) & 0xffffu, (uint32_t)(p.Nq - 1) * q_rowb + 2u * (uint32_t)p.D, 0x00020000u};
     const d256_u32x4s krs = {(uint32_t)ka, (uint32_t)(ka >> 32) & 0xffffu, p.k_bytes, 0x00020000u};

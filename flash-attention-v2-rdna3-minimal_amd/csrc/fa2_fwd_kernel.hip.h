@@ -118,6 +118,7 @@ struct FwdParams {
     int blk0;                            // added to blockIdx.x (a launch that covers only the parts: blk0 = full_items)
     int item_cap;                        // hand-scheduled kernels: the launch covers the list entries [0, item_cap): whole items, then parts (0 = all whole items)
     float* ws;                           // [split_items * nsplit] partial O tiles of kSplitRows x HD floats, then as many LSE rows of kSplitRows
+    int kv_group = 1;                    // grouped-query attention: Q head h reads K / V head h / kv_group (1: one K / V head per Q head)
 };
 
 constexpr int kSplitRows = 256;          // rows of a split item (the 8-wave workgroup shape)
@@ -338,8 +339,8 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 
     // ---- K/V staging: buffer descriptors of this head's matrices (out-of-range rows read 0)
     const uint32_t k_rowb = (uint32_t)p.ks[2] * 2u, v_rowb = (uint32_t)p.vs[2] * 2u;
-    const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + h * p.ks[1] + (int64_t)kv_first * p.ks[2];
-    const uint16_t* vbase = (const uint16_t*)p.v + b * p.vs[0] + h * p.vs[1] + (int64_t)kv_first * p.vs[2];
+    const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + (h / p.kv_group) * p.ks[1] + (int64_t)kv_first * p.ks[2];
+    const uint16_t* vbase = (const uint16_t*)p.v + b * p.vs[0] + (h / p.kv_group) * p.vs[1] + (int64_t)kv_first * p.vs[2];
     const auto krs = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, p.k_bytes - (uint32_t)kv_first * k_rowb, 0x00020000);
     const auto vrs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, p.v_bytes - (uint32_t)kv_first * v_rowb, 0x00020000);
     uint32_t kg_off[NPASS], vg_off[VNPASS];  // per-lane byte offsets into the head matrix, tile 0

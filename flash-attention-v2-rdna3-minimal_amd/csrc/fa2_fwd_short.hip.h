@@ -60,8 +60,8 @@ __global__ __launch_bounds__(256, (HD <= 64 ? 3 : 2)) void fwd_short_kernel(cons
     // rows >= Nkv are outside the descriptors and arrive as zeros
     {
         const uint32_t k_rowb = (uint32_t)p.ks[2] * 2u, v_rowb = (uint32_t)p.vs[2] * 2u;
-        const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + h * p.ks[1];
-        const uint16_t* vbase_p = (const uint16_t*)p.v + b * p.vs[0] + h * p.vs[1];
+        const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + (h / p.kv_group) * p.ks[1];
+        const uint16_t* vbase_p = (const uint16_t*)p.v + b * p.vs[0] + (h / p.kv_group) * p.vs[1];
         const auto krs = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, p.k_bytes, 0x00020000);
         const auto vrs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase_p, 0, p.v_bytes, 0x00020000);
 #pragma unroll

@@ -154,7 +154,10 @@ inline int64_t plan_bwd_split(int HD, const BwdParams& p, bool causal, SplitPlan
     if (p.bias_kind == 0 && HD == 128 && p.D == 128 && (options().asm_mask.load(std::memory_order_relaxed) & 2)) return 0;
     const int64_t cus = device_cus(), bh = (int64_t)p.B * p.H, tile_bytes = (int64_t)kSplitRows * HD * 4;
     *dq = plan_tail_split(bh * ((p.Nq + 255) / 256), (p.Nkv + kKvTile - 1) / kKvTile, 1.35 * HD / 64.0, 10.0, tile_bytes, cus, FA2_BWD_DQ_UNDERFILLED != 0);
-    if (HD <= 64) *dkv = plan_tail_split(bh * ((p.Nkv + 255) / 256), (p.Nq + kKvTile - 1) / kKvTile, 1.8 * HD / 64.0, 10.0, 2 * tile_bytes, cus, true);
+    // (grouped-query attention: B * H / kv_group KV owners, each sweeping the Q tiles of its kv_group member heads — the parts divide that virtual sweep)
+    if (HD <= 64)
+        *dkv = plan_tail_split((bh / p.kv_group) * ((p.Nkv + 255) / 256), p.kv_group * ((p.Nq + kKvTile - 1) / kKvTile), 1.8 * HD / 64.0, 10.0, 2 * tile_bytes,
+                               cus, true);
     return dq->bytes > dkv->bytes ? dq->bytes : dkv->bytes;
 }
 // HIP backward (bwd_hip.cpp): parts bit 0 = dQ pass (+ delta workspace), bit 1 = dK / dV pass(es)

@@ -28,20 +28,25 @@ at::Tensor kernel_ready(const at::Tensor& t) { return strides_ok(t) ? t : t.cont
 // Workspace sizes are a function of (dtype, shape, device, options): asked once per shape and option epoch instead of on every call
 // (an SDXL UNet step makes 140 attention calls over 6 shapes).  Per thread: no lock on the call path.
 struct WsKey {
-    int which, dtype, dev; int64_t b, h, n, nkv, d;
-    bool operator==(const WsKey& o) const { return which == o.which && dtype == o.dtype && dev == o.dev && b == o.b && h == o.h && n == o.n && nkv == o.nkv && d == o.d; }
+    int which, dtype, dev; int64_t b, h, n, nkv, d, hkv;
+    bool operator==(const WsKey& o) const {
+        return which == o.which && dtype == o.dtype && dev == o.dev && b == o.b && h == o.h && n == o.n && nkv == o.nkv && d == o.d && hkv == o.hkv;
+    }
 };
-size_t cached_ws_bytes(int which, int dtype, int dev, int64_t b, int64_t h, int64_t n, int64_t nkv, int64_t d) {
+// hkv: K / V heads of a grouped-query call (fa2_*_gqa_workspace_bytes), 0 for the MHA calls
+size_t cached_ws_bytes(int which, int dtype, int dev, int64_t b, int64_t h, int64_t n, int64_t nkv, int64_t d, int64_t hkv = 0) {
     struct Entry { WsKey key; size_t bytes; };
     thread_local std::vector<Entry> cache;
     thread_local int epoch = -1;
     const int now = fa2_get_option("epoch");
     if (now != epoch) { cache.clear(); epoch = now; }
-    const WsKey key{which, dtype, dev, b, h, n, nkv, d};
+    const WsKey key{which, dtype, dev, b, h, n, nkv, d, hkv};
     for (const Entry& e : cache)
         if (e.key == key) return e.bytes;
-    const size_t bytes = which == 0 ? fa2_fwd_workspace_bytes(dtype, (int)b, (int)h, (int)n, (int)nkv, (int)d, 0)
-                                    : fa2_bwd_workspace_bytes(dtype, (int)b, (int)h, (int)n, (int)nkv, (int)d, 0);
+    const size_t bytes = hkv ? (which == 0 ? fa2_fwd_gqa_workspace_bytes(dtype, (int)b, (int)h, (int)hkv, (int)n, (int)nkv, (int)d, 0)
+                                           : fa2_bwd_gqa_workspace_bytes(dtype, (int)b, (int)h, (int)hkv, (int)n, (int)nkv, (int)d, 0))
+                             : which == 0 ? fa2_fwd_workspace_bytes(dtype, (int)b, (int)h, (int)n, (int)nkv, (int)d, 0)
+                                          : fa2_bwd_workspace_bytes(dtype, (int)b, (int)h, (int)n, (int)nkv, (int)d, 0);
     if (cache.size() >= 64) cache.clear();
     cache.push_back({key, bytes});
     return bytes;
@@ -124,8 +129,10 @@ std::vector<at::Tensor> forward(at::Tensor q, at::Tensor k, at::Tensor v, int64_
         }
     }
     const int n_ax = permute_NH ? 1 : 2, h_ax = permute_NH ? 2 : 1;
-    const int64_t b = q.size(0), h = q.size(h_ax), n = q.size(n_ax), d = q.size(3), n_kv = k.size(n_ax);
-    TORCH_CHECK(k.size(0) == b && k.size(h_ax) == h && k.size(3) == d && v.sizes() == k.sizes(), "fa2: inconsistent q/k/v shapes");
+    const int64_t b = q.size(0), h = q.size(h_ax), n = q.size(n_ax), d = q.size(3), n_kv = k.size(n_ax), hkv = k.size(h_ax);
+    TORCH_CHECK(k.size(0) == b && k.size(3) == d && v.sizes() == k.sizes(), "fa2: inconsistent q/k/v shapes");
+    // grouped-query attention: k and v share a head count that divides q's (Q head i attends K / V head i / (h / hkv))
+    TORCH_CHECK(hkv >= 1 && h % hkv == 0, "fa2: the head count of k / v (", hkv, ") must divide the head count of q (", h, ")");
     TORCH_CHECK(fa2_padded_head_dim((int)(d + ((8 - d % 8) % 8))) > 0, "fa2: head dim ", d, " is larger than the largest gfx950 kernel");
     const int64_t d_pad = (8 - d % 8) % 8, d_kernel = d + d_pad;
     at::Tensor qp = q, kp = k, vp = v;
@@ -166,12 +173,15 @@ std::vector<at::Tensor> forward(at::Tensor q, at::Tensor k, at::Tensor v, int64_
     const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream();
     // scratch for the KV-split of a partly filled last round of workgroups (fa2_fwd_ws): the per-stream block above
     at::Tensor ws;
-    const size_t ws_bytes = causal ? 0 : cached_ws_bytes(0, dtype_code, q.device().index(), b, h, n, n_kv, d_kernel);
+    const size_t ws_bytes = causal ? 0 : cached_ws_bytes(0, dtype_code, q.device().index(), b, h, n, n_kv, d_kernel, hkv == h ? 0 : hkv);
     if (ws_bytes) ws = workspace(ws_bytes, q, stream);
     else workspace_unused(q.device().index(), stream);
-    const int rc = fa2_fwd_ws(dtype_code, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), O.data_ptr(), L.data_ptr<float>(), (int)b, (int)h,
-                              (int)n, (int)n_kv, (int)d_kernel, qs, ks, vs, os, ls, (float)scale, (int)(flags & 3),
-                              ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, (void*)stream);
+    const int rc = hkv == h ? fa2_fwd_ws(dtype_code, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), O.data_ptr(), L.data_ptr<float>(), (int)b, (int)h,
+                                         (int)n, (int)n_kv, (int)d_kernel, qs, ks, vs, os, ls, (float)scale, (int)(flags & 3),
+                                         ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, (void*)stream)
+                            : fa2_fwd_gqa(dtype_code, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), O.data_ptr(), L.data_ptr<float>(), (int)b, (int)h,
+                                          (int)hkv, (int)n, (int)n_kv, (int)d_kernel, qs, ks, vs, os, ls, (float)scale, (int)(flags & 3),
+                                          ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, (void*)stream);
     TORCH_CHECK(rc == 0, "fa2 call failed (", rc, "): ", fa2_error_string(rc));
     at::Tensor O_fwd = O;
     if (nq_pad) O_fwd = O_fwd.narrow(n_ax, 0, n);
@@ -188,7 +198,17 @@ std::vector<at::Tensor> backward(at::Tensor Q, at::Tensor K, at::Tensor V, at::T
     (void)Bc;
     TORCH_CHECK(Q.is_cuda() && dO.is_cuda(), "fa2: tensors must be on a ROCm device (no CPU path in this operator)");
     const int n_ax = permute_NH ? 1 : 2, h_ax = permute_NH ? 2 : 1;
-    const int64_t b = Q.size(0), h = Q.size(h_ax), dk = Q.size(3);
+    const int64_t b = Q.size(0), h = Q.size(h_ax), dk = Q.size(3), hkv = K.size(h_ax);
+    TORCH_CHECK(hkv >= 1 && h % hkv == 0 && V.size(h_ax) == hkv, "fa2: the head count of k / v (", hkv, ") must divide the head count of q (", h, ")");
+    if (hkv != h) {
+        // grouped-query attention (rocwmma_fattn/FlashAttn.py::_grouped_backward, the same steps): K / V expanded to q's head count, the MHA backward,
+        // dK / dV summed over each group in f32 and rounded once.  fa2_bwd_gqa's in-kernel sum runs a grid g times smaller and lost to this on every
+        // shape measured
+        const int64_t g = h / hkv;
+        std::vector<at::Tensor> r = backward(Q, K.repeat_interleave(g, h_ax), V.repeat_interleave(g, h_ax), O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal,
+                                             scale, permute_NH);
+        return {r[0], r[1].unflatten(h_ax, {hkv, g}).sum(h_ax + 1), r[2].unflatten(h_ax, {hkv, g}).sum(h_ax + 1)};
+    }
     const int dtype_code = Q.scalar_type() == at::kHalf ? FA2_DTYPE_F16 : FA2_DTYPE_BF16;
     if (dO.scalar_type() != Q.scalar_type()) dO = dO.to(Q.scalar_type());          // host.cpp:47-58 dispatches on dO's dtype; Q's wins here
     if (dO.size(3) != dk) dO = at::constant_pad_nd(dO, {0, dk - dO.size(3)});        // kernel_fp16.cu:900-905

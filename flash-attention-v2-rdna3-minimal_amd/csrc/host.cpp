@@ -359,6 +359,9 @@ int launch_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal, hipStrea
     if (!asm_pitch_ok(p.ks[2], 128) || !asm_pitch_ok(p.vs[2], 128)) asm_parts &= ~1;
     if (!asm_pitch_ok(p.qs[2], 128) || !asm_pitch_ok(p.dos[2], 128)) asm_parts &= ~2;
     if (p.Nq % 32 != 0) asm_parts &= ~2;              // the hand-scheduled dK/dV pass sweeps whole 32-row Q tiles
+    // grouped-query attention: the hand-scheduled dK/dV body owns one Q head's sweep; the compiler-scheduled wave-pair pass sums the group in-kernel
+    // (the hand-scheduled dQ pass then writes +delta, which that pass reads)
+    if (p.kv_group > 1) asm_parts &= ~2;
     // the sign delta crosses the workspace with: the hand-scheduled dK/dV pass takes -delta (C operand of its dP product); a dQ pass
     // that is not the hand-scheduled one writes +delta, so the two only go together
     if ((asm_parts & 2) && !(asm_parts & 1)) asm_parts = 0;
@@ -474,7 +477,7 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
                     int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
                     const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
                     float scale, int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
-                    void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, fa2_fwd_plan_t* plan_out = nullptr) {
+                    void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, fa2_fwd_plan_t* plan_out = nullptr, int Hkv = 0) {
     // `causal` carries the call's flags: bit 0 = causal mask, bit 1 = FA2_FLAG_EXACT_SCALE (this call scales the f32 product whatever option "fold" says)
     // Until round 5 any non-zero value meant "causal"; a caller that still passes another truthy int would silently get a non-causal forward: refuse it
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
@@ -495,6 +498,8 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
     }
     if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
     if (B < 1 || H < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
+    if (Hkv == 0) Hkv = H;                       // (the MHA entry points)
+    if (Hkv < 1 || Hkv > H || H % Hkv != 0 || (Hkv != H && bias_kind != FA2_BIAS_NONE)) return FA2_ERR_BAD_SHAPE;
     const int HD = fa2_padded_head_dim(D);       // kernel head dim; columns [D, HD) are masked in-kernel
     if (HD < 0 || (D & 7)) return FA2_ERR_HEAD_DIM;
     if (!std::isfinite(scale)) return FA2_ERR_SCALE;
@@ -528,6 +533,7 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
     p.ws = nullptr;
     p.k_bytes = (uint32_t)k_bytes;
     p.v_bytes = (uint32_t)v_bytes;
+    p.kv_group = H / Hkv;
     p.bias = bias;
     p.bias_kind = bias_kind;
     for (int i = 0; i < 3; ++i) p.bs[i] = bias_kind != FA2_BIAS_NONE ? bias_strides[i] : 0;
@@ -665,7 +671,7 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
             const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
             const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
             int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
-            void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr) {
+            void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, int Hkv = 0) {
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;      // (as in fwd_impl: no value but the documented flag bits)
     causal &= 1;          // (bit 1, FA2_FLAG_EXACT_SCALE, is what the backward does anyway unless option "kfold" is set)
     if (ws_need) *ws_need = 0;
@@ -681,6 +687,8 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
         return FA2_ERR_NULL_POINTER;
     if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
     if (B < 1 || H < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
+    if (Hkv == 0) Hkv = H;                              // (the MHA entry points)
+    if (Hkv < 1 || Hkv > H || H % Hkv != 0 || (Hkv != H && bias_kind != FA2_BIAS_NONE)) return FA2_ERR_BAD_SHAPE;
     const int HD = fa2_padded_head_dim(D);              // columns [D, HD) are masked in-kernel
     if (HD < 0 || HD > kMaxBwdHeadDim || (D & 7)) return FA2_ERR_HEAD_DIM;
     if (!std::isfinite(scale)) return FA2_ERR_SCALE;
@@ -729,6 +737,7 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
     p.full_items = p.split_items = p.nsplit = 0;
     p.ws = (float*)ws;
     p.ws_bytes = ws_bytes;
+    p.kv_group = H / Hkv;
     if (ws_need) {      // fa2_bwd_workspace_bytes: validate and plan only
         fa2::SplitPlan a, b2;
         *ws_need = (size_t)fa2::plan_bwd_split(HD, p, causal != 0, &a, &b2);
@@ -805,6 +814,55 @@ int fa2_bwd_bias(int dtype, const void* q, const void* k, const void* v, const v
                  int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream) {
     return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
                     do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, bias, bias_kind, bias_strides, hip_stream);
+}
+
+// ---- grouped-query / multi-query attention: K and V (and dK, dV) have Hkv heads, Q head h reads K / V head h / (H / Hkv)
+int fa2_fwd_gqa(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
+                int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
+                float scale, int causal, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (Hkv < 1) return FA2_ERR_BAD_SHAPE;
+    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
+                    scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, workspace, workspace_bytes, nullptr, nullptr, Hkv);
+}
+
+size_t fa2_fwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int causal) {
+    // the forward's plan does not depend on the K / V head count (the grouped call runs the MHA call's kernels): fa2_fwd_workspace_bytes, validated
+    if (B < 1 || H < 1 || Hkv < 1 || Hkv > H || H % Hkv != 0) return 0;
+    return fa2_fwd_workspace_bytes(dtype, B, H, Nq, Nkv, D, causal);
+}
+
+int fa2_fwd_gqa_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                     float scale, int causal, size_t workspace_bytes, fa2_fwd_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
+    const ContigStrides cs(H, Nq, Nkv, D), ck(Hkv, Nq, Nkv, D);
+    char* d = g_plan_dummy;
+    return fwd_impl(dtype, d, d, d, d, (float*)d, B, H, Nq, Nkv, D, q_strides ? q_strides : cs.q, k_strides ? k_strides : ck.k, k_strides ? k_strides : ck.k,
+                    q_strides ? q_strides : cs.q, cs.ls, scale, causal, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, workspace_bytes, nullptr, plan, Hkv);
+}
+
+int fa2_bwd_gqa(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Hkv, int Nq, int Nkv, int D,
+                const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
+                int causal, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (Hkv < 1) return FA2_ERR_BAD_SHAPE;
+    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
+                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream,
+                    workspace, workspace_bytes, nullptr, Hkv);
+}
+
+size_t fa2_bwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int causal) {
+    static const int64_t one[3] = {8, 8, 8};
+    alignas(16) static char dummy[16];
+    const int64_t ls[2] = {0, 0};
+    size_t need = 0;
+    if (Hkv < 1 || bwd_impl(dtype, dummy, dummy, dummy, dummy, dummy, (const float*)dummy, dummy, dummy, dummy, (float*)dummy, B, H, Nq, Nkv, D, one, one, one,
+                            one, one, one, one, one, ls, 1.0f, causal, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need, Hkv) != FA2_OK)
+        return 0;
+    return need;
 }
 
 #define FA2_BWD_ARGS                                                                                                    \

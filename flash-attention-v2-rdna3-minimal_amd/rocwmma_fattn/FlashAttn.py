@@ -83,9 +83,10 @@ class _FlashAttnWmma:
         n_ax, h_ax = (1, 2) if permute_NH else (2, 1)
         qsh, ksh = q.shape, k.shape
         b, h, n, d = qsh[0], qsh[h_ax], qsh[n_ax], qsh[3]
-        n_kv = ksh[n_ax]
-        if ksh[0] != b or ksh[h_ax] != h or ksh[3] != d or v.shape != ksh:
+        n_kv, h_kv = ksh[n_ax], ksh[h_ax]
+        if ksh[0] != b or ksh[3] != d or v.shape != ksh:
             raise RuntimeError("fa2: inconsistent q/k/v shapes %s %s %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+        _check_groups(h, h_kv)
         if d > _MAX_HEAD_DIM:
             raise RuntimeError("fa2: head dim %d is larger than the largest gfx950 kernel" % d)
         d_pad = -d % 8
@@ -127,10 +128,16 @@ class _FlashAttnWmma:
                 _fa2_lib.strides2(h * (n + nq_pad), n + nq_pad), float(scale), flags)
         fn = lib.fa2_fwd
         if bias is not None:
+            if h_kv != h:
+                raise RuntimeError("fa2: the masked forward has no grouped-query form (flash_attention(mask=...) expands k / v for it)")
             bias_t, kind, bstr = _prepare_bias(bias, b, h, n, n_kv, q_pad.dtype, q.device)
             args += (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
             fn = lib.fa2_fwd_bias
-        if dev != _current_device():
+        if h_kv != h:          # grouped-query attention: fa2_fwd_gqa (the MHA call's kernels, K / V addressed through the group)
+            args = args[:8] + (h_kv,) + args[8:]
+            with torch.cuda.device(dev):
+                rc = _launch_fwd_gqa(lib, args, dev, q.device, not causal)
+        elif dev != _current_device():
             with torch.cuda.device(dev):
                 rc = _launch_fwd(lib, fn, args, dev, q.device, bias is None and not causal)
         else:
@@ -165,6 +172,12 @@ class _FlashAttnWmma:
             raise RuntimeError("fa2: tensors must be on a ROCm device (no CPU path in this operator)")
         n_ax, h_ax = (1, 2) if permute_NH else (2, 1)
         b, h, dk = Q.size(0), Q.size(h_ax), Q.size(3)
+        h_kv = K.size(h_ax)
+        _check_groups(h, h_kv)
+        if h_kv != h:
+            if bias is not None:
+                raise RuntimeError("fa2: the masked backward has no grouped-query form (flash_attention(mask=...) expands k / v for it)")
+            return _grouped_backward(_FlashAttnWmma.backward_py, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH)
         act_n, act_nkv, act_d = int(act_n), int(act_nkv), int(act_d)
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
         if dO.dtype != Q.dtype:
@@ -280,6 +293,36 @@ def _launch_fwd(lib, fn, args, dev, device, may_split):
     if _WS_POOL:
         _workspace_unused(dev, stream)
     return fn(*args, stream)
+
+
+def _launch_fwd_gqa(lib, args, dev, device, may_split):
+    """fa2_fwd_gqa on torch's current stream (args: fa2_fwd's with the K / V head count after H), with the KV-split's scratch where the library
+    can use it for this shape (fa2_fwd_gqa_workspace_bytes: the MHA call's answer)."""
+    stream = _raw_stream(dev)
+    need = lib.fa2_fwd_gqa_workspace_bytes(args[0], *args[6:12], 0) if may_split else 0
+    if need:
+        ws = _workspace(need, device, dev, stream)
+        return lib.fa2_fwd_gqa(*args, ws.data_ptr(), need, stream)
+    if _WS_POOL:
+        _workspace_unused(dev, stream)
+    return lib.fa2_fwd_gqa(*args, None, 0, stream)
+
+
+def _grouped_backward(mha_backward, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH):
+    """The operator's backward of a grouped-query call: K / V expanded to q's head count, the MHA backward, dK / dV summed over each group (f32
+    accumulation, one rounding).  The C-ABI's fa2_bwd_gqa sums the groups in-kernel without the expanded tensors, but its dK / dV pass runs
+    B * Hkv KV owners — a grid g times smaller — and lost to this path on every shape measured (profiles/r28_gqa_bench.txt)."""
+    h_ax = 2 if permute_NH else 1
+    g = Q.size(h_ax) // K.size(h_ax)
+    dQ, dKe, dVe = mha_backward(Q, K.repeat_interleave(g, dim=h_ax), V.repeat_interleave(g, dim=h_ax), O, dO, L, act_n, act_nkv, act_d, Br, Bc,
+                                causal, scale, permute_NH)
+    return [dQ, dKe.unflatten(h_ax, (K.size(h_ax), g)).sum(h_ax + 1), dVe.unflatten(h_ax, (V.size(h_ax), g)).sum(h_ax + 1)]
+
+
+def _check_groups(h, h_kv):
+    """Grouped-query attention: k and v share a head count that divides q's (Q head i attends K / V head i // (h // h_kv))."""
+    if h_kv < 1 or h % h_kv:
+        raise RuntimeError("fa2: the head count of k / v (%d) must divide the head count of q (%d)" % (h_kv, h))
 
 
 _FRONTEND = [False]      # False = not looked for yet, None = absent
@@ -418,6 +461,9 @@ _autograd_apply = FlashAttentionFunction.apply
 
 
 def _apply(q, k, v, mask=None, causal=None, scale=None, BNHD_fmt=False, *args, **kwargs):
+    h_ax = 2 if BNHD_fmt else 1
+    if q.dim() == 4 and k.dim() == 4 and k.shape[h_ax] != q.shape[h_ax]:
+        _check_groups(q.shape[h_ax], k.shape[h_ax])      # (grouped-query attention: refused before any device work when the counts do not divide)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         fe = _frontend()
         if fe is not None and q.requires_grad and not args and not kwargs and hasattr(fe, "attention"):
@@ -470,6 +516,15 @@ def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False
     position is masked return zeros.  Differentiable in q, k, v (C-ABI fa2_bwd_bias; head dims up to 256); the mask gets no gradient."""
     if mask is None:
         return FlashAttentionFunction.apply(q, k, v, None, causal, scale, BNHD_fmt)
+    h_ax = 2 if BNHD_fmt else 1
+    if q.dim() == 4 and k.dim() == 4 and v.dim() == 4 and k.shape[h_ax] != q.shape[h_ax]:
+        # grouped-query attention under a mask: the masked kernels have no grouped form, so K / V are expanded to q's head count here and autograd
+        # sums dK / dV over each group (correct, not a hot path: the expanded K / V cross memory g times)
+        _check_groups(q.shape[h_ax], k.shape[h_ax])
+        if v.shape[h_ax] != k.shape[h_ax]:
+            raise RuntimeError("fa2: inconsistent q/k/v shapes %s %s %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+        g = q.shape[h_ax] // k.shape[h_ax]
+        k, v = k.repeat_interleave(g, dim=h_ax), v.repeat_interleave(g, dim=h_ax)
     D = q.shape[3]
     if scale is None:
         scale = D ** -0.5

@@ -68,6 +68,12 @@ SYMBOLS = {
     "fa2_tile_rows": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "fa2_fwd_prescales_q": (ctypes.c_int, [ctypes.c_int, ctypes.c_float]),
     "fa2_fwd_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [_i64p, _i64p, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(FwdPlan)]),
+    # grouped-query / multi-query attention: the MHA argument lists with Hkv after H (fa2_fwd_gqa: fa2_fwd_ws's, fa2_bwd_gqa: fa2_bwd_ws's)
+    "fa2_fwd_gqa": (ctypes.c_int, [ctypes.c_int] + _FWD_ARGTYPES[:7] + [ctypes.c_int] + _FWD_ARGTYPES[7:-1] + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fa2_fwd_gqa_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
+    "fa2_fwd_gqa_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p, _i64p, ctypes.c_float, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(FwdPlan)]),
+    "fa2_bwd_gqa": (ctypes.c_int, [ctypes.c_int] + _BWD_ARGTYPES[:12] + [ctypes.c_int] + _BWD_ARGTYPES[12:-1] + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fa2_bwd_gqa_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
     "fa2_set_option": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "fa2_get_option": (ctypes.c_int, [ctypes.c_char_p]),
     "fa2_error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -174,6 +180,17 @@ def fwd_plan(q, k, causal, scale=None, bias_kind=FA2_BIAS_NONE, workspace_bytes=
     check(load().fa2_fwd_plan(dt, B, H, Nq, k.shape[2], D, strides3(q.stride(0), q.stride(1), q.stride(2)),
                               strides3(k.stride(0), k.stride(1), k.stride(2)), float(D ** -0.5 if scale is None else scale),
                               call_flags(causal), int(bias_kind), int(workspace_bytes), ctypes.byref(plan)))
+    return plan
+
+
+def gqa_plan(q, k, causal, scale=None, workspace_bytes=0):
+    """fa2_fwd_gqa_plan for the call fa2_fwd_gqa(q, k, ...) would be (k: [B, Hkv, Nkv, D])."""
+    B, H, Nq, D = q.shape
+    dt = FA2_DTYPE_F16 if q.dtype == torch.float16 else FA2_DTYPE_BF16
+    plan = FwdPlan()
+    check(load().fa2_fwd_gqa_plan(dt, B, H, k.shape[1], Nq, k.shape[2], D, strides3(q.stride(0), q.stride(1), q.stride(2)),
+                                  strides3(k.stride(0), k.stride(1), k.stride(2)), float(D ** -0.5 if scale is None else scale),
+                                  call_flags(causal), int(workspace_bytes), ctypes.byref(plan)))
     return plan
 
 

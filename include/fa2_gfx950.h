@@ -254,6 +254,44 @@ int fa2_bwd_bias_ws(int dtype, const void* q, const void* k, const void* v, cons
                     void* workspace, size_t workspace_bytes, void* hip_stream);
 size_t fa2_bwd_bias_workspace_bytes(int dtype, int B, int H, int Nq, int Nkv, int D, int causal);
 
+/*
+ * Grouped-query attention (GQA) and multi-query attention (MQA, Hkv = 1): K and V have Hkv heads that serve the H query heads, the semantics of
+ * torch's scaled_dot_product_attention(..., enable_gqa=True).
+ * Layout contract
+ *   q, o, dout, dq : [B, H,   Nq,  D]  as in fa2_fwd / fa2_bwd
+ *   k, v, dk, dv   : [B, Hkv, Nkv, D]  element (b,hk,j,c) at k + b*k_strides[0] + hk*k_strides[1] + j*k_strides[2] + c (likewise v, dk, dv)
+ *   lse, delta_ws  : [B, H, Nq] (indexed by the Q head, lse_strides)
+ *   Hkv >= 1 must divide H (FA2_ERR_BAD_SHAPE otherwise); g = H / Hkv; Q head h attends K / V head h / g.
+ *   dK / dV of K / V head hk are the SUM of the gradients of the Q heads hk*g .. hk*g + g-1 — formed in-kernel: one workgroup owns a K / V head's
+ *   rows and sweeps the Q tiles of its g member heads in turn, accumulating in f32 registers and rounding once (no atomics, deterministic).
+ * Kernels.  The forward runs the kernels the MHA call of the same shape runs (fa2_fwd_gqa_plan reports the same plan), with K / V addressed through
+ * the group; the workspace acts as in fa2_fwd_ws (NULL / too small: the call is fa2_fwd's).  The backward's dQ pass is the MHA call's, hand-scheduled
+ * one at head dim 128 included; the dK / dV passes are the compiler-scheduled ones at every head dim (head dim 128: the wave-pair pass, not the
+ * hand-scheduled body), and fa2_bwd_gqa's workspace splits their B * Hkv owners over the virtual sweep of g x (Q tiles) as in fa2_bwd_ws.
+ * A call with Hkv == H is exactly the corresponding fa2_fwd_ws / fa2_bwd_ws call.  Masked (bias) calls have no grouped form.
+ * When to call which.  fa2_fwd_gqa is the fast choice for every grouped forward (0.94 .. 1.00x the MHA call on pre-expanded K / V, which also
+ * needs the expansion).  fa2_bwd_gqa is the MEMORY-lean backward: no expanded K / V, no [B, H, Nkv, D] dK / dV buffers.  It is not the fast one on
+ * the shapes measured: its dK / dV passes run B * Hkv * ceil(Nkv / rows) workgroups, a grid g times smaller than the MHA
+ * call's, and at head dim 128 without the hand-scheduled body — 1.05 .. 1.5x the time of expanding K / V, fa2_bwd_ws and summing dK / dV over
+ * each group at g = 4 .. 8, 5.8x for MQA at B1 N4096.  A caller with the memory to spare takes that route; the Python operator does.
+ */
+int fa2_fwd_gqa(int dtype,
+                const void* q, const void* k, const void* v, void* o, float* lse,
+                int B, int H, int Hkv, int Nq, int Nkv, int D,
+                const int64_t q_strides[3], const int64_t k_strides[3],
+                const int64_t v_strides[3], const int64_t o_strides[3],
+                const int64_t lse_strides[2],
+                float scale, int causal, void* workspace, size_t workspace_bytes, void* hip_stream);
+size_t fa2_fwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int causal);
+int fa2_bwd_gqa(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                void* dq, void* dk, void* dv, float* delta_ws,
+                int B, int H, int Hkv, int Nq, int Nkv, int D,
+                const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2],
+                float scale, int causal, void* workspace, size_t workspace_bytes, void* hip_stream);
+size_t fa2_bwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int causal);
+
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
  * that is not a multiple of 8 has to be zero-padded by the caller (to the next multiple of 8). */
@@ -313,6 +351,10 @@ typedef struct fa2_fwd_plan_t {
 int fa2_fwd_plan(int dtype, int B, int H, int Nq, int Nkv, int D,
                  const int64_t q_strides[3], const int64_t k_strides[3],
                  float scale, int causal, int bias_kind, size_t workspace_bytes, fa2_fwd_plan_t* plan);
+/* The plan of fa2_fwd_gqa (k_strides: those of the [B, Hkv, Nkv, D] K, or NULL for a contiguous one): the MHA call's plan for the same shape. */
+int fa2_fwd_gqa_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D,
+                     const int64_t q_strides[3], const int64_t k_strides[3],
+                     float scale, int causal, size_t workspace_bytes, fa2_fwd_plan_t* plan);
 
 /* Coarse form of the above (kept for callers of version 0.8): 1 if launches of this head dim MAY fold the scale into Q (head dims exactly 64
  * and 128, 0 < scale*log2(e) <= 1, option "fold" >= 1: the fp16 launches the hand-scheduled bodies take), 0 if none does, -1: D not supported.
