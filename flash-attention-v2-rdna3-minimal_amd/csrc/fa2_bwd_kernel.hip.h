@@ -275,6 +275,12 @@ __device__ __forceinline__ void store_acc_t(const f32x16 (&acc)[DT], uint16_t* r
 // and DTN = ceil(D / 32) column blocks of the accumulators.  Defaults = the full kernel.
 template <int HD, bool BF16, bool CAUSAL, int NW = 8, int HDV = HD, int BIAS = 0, int KSN = HD / 16, int DTN = HDV / 32>
 __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_dq_kernel(const BwdParams p) {
+#if FA2_WIN
+    // FA2_WIN (fa2_bwd_window; window_hip.cpp, CAUSAL = false, BIAS = 0): the sweep covers the KV tiles of the workgroup's window only (fa2_window.h), a
+    // wave computes the tiles of its own rows' range, tiles cut by an edge of the band are masked on both sides.
+    static_assert(!CAUSAL && !BIAS, "the windowed passes carry the causal edge in the window and take no bias");
+    const Window win = get_window(p);      // (the window travels in the bias stride fields: fa2_fwd_kernel.hip.h)
+#endif
     using L_ = BwdLane<HD, NW>;
     using LV_ = BwdLane<HDV, NW>;             // geometry of the transposed-read image (the slab)
     constexpr int kRows = NW * 32;            // rows per workgroup (p.nblk = ceil(N / kRows))
@@ -294,7 +300,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
     int bid = blockIdx.x;
     // split last round: blocks [full_items, ...) are parts, part-major (fa2_fwd_kernel.hip.h has the forward's twin)
     int part = -1, sidx = 0;
+#if FA2_WIN
+    if constexpr (false) {
+#else
     if constexpr (!CAUSAL && NW == 8 && HDV == HD) {
+#endif
         if (p.nsplit > 1 && bid >= p.full_items) {
             const int j = bid - p.full_items;
             part = j / p.split_items;
@@ -358,6 +368,24 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
     }
     int ntiles_w = ntiles;
     if (CAUSAL) { const int nt_w = (qw0 + 31) / kKvTile + 1; ntiles_w = nt_w < ntiles ? nt_w : ntiles; }
+#if FA2_WIN
+    // the workgroup's tiles [t_first, ntiles), this wave's [tf_w, ntiles_w), the wave's unmasked tiles [plain0, n_plain) and the lane's limits
+    int t_first, tf_w, plain0, lim_lo, lim_hi;
+    {
+        int first, n;
+        window_tile_range(p.Nq, p.Nkv, win.left, win.right, win.off, q0, kRows, kKvTile, &first, &n);
+        t_first = first;
+        ntiles = first + n;
+        window_tile_range(p.Nq, p.Nkv, win.left, win.right, win.off, qw0, 32, kKvTile, &first, &n);
+        tf_w = first;
+        ntiles_w = first + n;
+        const int pos0 = qw0 + win.off, pos = qrow + win.off;
+        const int w_lo_full = win.left < 0 ? 0 : pos0 + 31 - win.left;
+        plain0 = w_lo_full > 0 ? (w_lo_full + kKvTile - 1) / kKvTile : 0;
+        lim_lo = win.left < 0 ? 0 : pos - win.left;
+        lim_hi = win.right < 0 || pos + win.right > p.Nkv - 1 ? p.Nkv - 1 : pos + win.right;
+    }
+#endif
     asm volatile("" : "+s"(ntiles_w));   // opaque: stops the non-causal build from peeling the tail tile into a register-hungry shape
 
     // per-lane source offsets of the staging loads within a tile (loop-invariant); the tile's own byte offset rides in soffset
@@ -409,6 +437,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
     // tiles [0, n_plain) need no mask for this wave: fully inside Nkv and fully below the wave's diagonal
     int n_plain = p.Nkv / kKvTile;
     if (CAUSAL) { const int nc = (qw0 + 1) / kKvTile; n_plain = nc < n_plain ? nc : n_plain; }
+#if FA2_WIN
+    {
+        const int pos0 = qw0 + win.off;
+        const int w_hi_full = win.right < 0 || pos0 + win.right > p.Nkv - 1 ? p.Nkv - 1 : pos0 + win.right;     // every row of the wave sees up to here
+        const int nr = (w_hi_full + 1) / kKvTile;
+        n_plain = nr < n_plain ? nr : n_plain;
+    }
+#endif
     n_plain = n_plain < ntiles_w ? n_plain : ntiles_w;
 
     // ONE tile body: two bodies (masked / plain) joined by a branch made the register allocator copy the 64 accumulator registers
@@ -436,7 +472,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
             }
             const int kv0 = tile * kKvTile;
             const int lim_c = CAUSAL ? qrow : 0x7fffffff;
+#if FA2_WIN
+            const int lim = lim_hi;                                  // kv index must be in [lim_lo, lim] (MASKED tiles only)
+            (void)lim_c;
+#else
             const int lim = lim_c < p.Nkv - 1 ? lim_c : p.Nkv - 1;   // kv index must be <= lim (MASKED tiles only)
+#endif
             // P^T = 2^(S^T c - L); masked entries -> 0
             constexpr bool tiled = BIAS == 2;       // (BIAS = 1: one load per score; the two forms are separate instantiations — together
                                                     //  they spilled hundreds of bytes per lane)
@@ -487,8 +528,13 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int kvi = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+#if FA2_WIN
+                    if (kvi > lim || kvi < lim_lo) s0[r] = 0.f;
+                    if (kvi + 32 > lim || kvi + 32 < lim_lo) s1[r] = 0.f;
+#else
                     if (kvi > lim) s0[r] = 0.f;
                     if (kvi + 32 > lim) s1[r] = 0.f;
+#endif
                 }
             }
             f32x16 d0, d1;
@@ -525,18 +571,30 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
         }
     };
 
+#if FA2_WIN
+    int t_begin = t_first;
+#else
     int t_begin = 0;                       // a part sweeps its share of the whole KV tiles
+#endif
     if (part >= 0) { t_begin = part * ntiles / p.nsplit; ntiles = (part + 1) * ntiles / p.nsplit; }
     stage_load(t_begin, 0);
     __syncthreads();
     for (int tile = t_begin; tile < ntiles; ++tile) {
         const int st = DBUF ? (tile - t_begin) & 1 : 0;
         if (DBUF && tile + 1 < ntiles) stage_load(tile + 1, st ^ 1);   // destination stage was last read before the previous barrier
+#if FA2_WIN
+        if (tile >= tf_w && tile < ntiles_w) tile_body(tile, st, tile >= n_plain || tile < plain0);   // (a wave outside its range only keeps the barriers)
+#else
         if (!CAUSAL || tile < ntiles_w) tile_body(tile, st, tile >= n_plain);   // (causal: a wave past its diagonal only keeps the barriers)
+#endif
         __syncthreads();
         if (!DBUF && tile + 1 < ntiles) { stage_load(tile + 1, 0); __syncthreads(); }
     }
+#if FA2_WIN
+    if constexpr (false) {
+#else
     if constexpr (!CAUSAL && NW == 8 && HDV == HD) {
+#endif
         if (part >= 0) {                   // unscaled f32 partial dQ tile; bwd_merge_kernel sums the parts, scales and rounds once
             store_partial_t<DT>(acc, p.ws + (int64_t)(sidx * p.nsplit + part) * kSplitRows * HD, 32 * wave + l31, hi);
             return;
@@ -557,6 +615,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
 // dim, only the transposed-read image and the accumulator are slab-sized (see bwd_dq_kernel).
 template <int HD, bool BF16, bool CAUSAL, bool WANT_DK, int NW = 8, bool BOTH = false, int HDV = HD, int BIAS = 0, int KSN = HD / 16, int DTN = HDV / 32>
 __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParams p) {
+#if FA2_WIN
+    // FA2_WIN (fa2_bwd_window; kv_group = 1): the workgroup sweeps the Q tiles of the transposed band only (fa2_window.h: window_row_range), masked on
+    // both sides.
+    static_assert(!CAUSAL && !BIAS, "the windowed passes carry the causal edge in the window and take no bias");
+    const Window win = get_window(p);
+#endif
     static_assert(!BOTH || WANT_DK, "the fused pass is the dK pass plus a dV accumulator");
     static_assert(!BOTH || HDV == HD, "slabs exist for the separate passes only");
     using L_ = BwdLane<HD, NW>;
@@ -582,7 +646,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
     const int nbh = p.B * Hkv;
     int bid = blockIdx.x;
     int part = -1, sidx = 0;               // split last round (fused pass only): see bwd_dq_kernel
+#if FA2_WIN
+    if constexpr (false) {
+#else
     if constexpr (!CAUSAL && NW == 8 && BOTH) {
+#endif
         if (p.nsplit > 1 && bid >= p.full_items) {
             const int j = bid - p.full_items;
             part = j / p.split_items;
@@ -628,12 +696,37 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
 
     // Q tiles that can touch this workgroup's KV rows: causal keeps only q >= kv (top-left aligned).  The sweep is virtual: G member heads of
     // `per` tiles each, every member restarting at tile0; vt in [vt0, vnt) is tile tile0 + vt % per of member vt / per
+#if FA2_WIN
+    // the workgroup's Q tiles [tile0, ntiles), this wave's [tile0_w, tend_w), the wave's unmasked tiles [first_plain, last_plain) and the lane's first /
+    // last Q row (key j is seen by the rows j - q_offset - window_right ... j - q_offset + window_left)
+    int ntiles, tile0, tile0_w, tend_w, first_plain, last_plain, q_lo, q_hi;
+    {
+        int first, n;
+        window_row_range(p.Nq, p.Nkv, win.left, win.right, win.off, kv0, kRows, kKvTile, &first, &n);
+        tile0 = first;
+        ntiles = first + n;
+        window_row_range(p.Nq, p.Nkv, win.left, win.right, win.off, kvw0, 32, kKvTile, &first, &n);
+        tile0_w = first;
+        tend_w = first + n;
+        q_lo = win.right < 0 ? 0 : kvrow - win.off - win.right;
+        q_hi = win.left < 0 ? 0x7fffffff : kvrow - win.off + win.left;
+        const int lo_full = win.right < 0 ? 0 : kvw0 + 31 - win.off - win.right;       // every key of the wave is seen from this row on ...
+        first_plain = lo_full > 0 ? (lo_full + kKvTile - 1) / kKvTile : 0;
+        const int hi_full = win.left < 0 ? 0x7ffffff0 : kvw0 - win.off + win.left;     // ... up to this one
+        last_plain = hi_full < -1 ? 0 : (hi_full + 1) / kKvTile;
+    }
+    const int per = ntiles > tile0 ? ntiles - tile0 : 0;
+#else
     const int ntiles = (p.Nq + kKvTile - 1) / kKvTile;
     const int tile0 = CAUSAL ? kv0 / kKvTile : 0;
     const int per = ntiles > tile0 ? ntiles - tile0 : 0;
+#endif
     int vt0 = 0, vnt = G * per;
     if (part >= 0) { vt0 = part * vnt / p.nsplit; vnt = (part + 1) * vnt / p.nsplit; }   // a part sweeps its share of the virtual sweep
+#if FA2_WIN
+#else
     const int tile0_w = CAUSAL ? kvw0 / kKvTile : 0;     // this wave's first useful tile
+#endif
 
     // per-lane source offsets of the staging loads within a tile (loop-invariant); the tile's own byte offset rides in soffset
     // (kept for the 8-wave kernels only: the 4-wave ones have 8 passes per tile and no registers to spare)
@@ -697,7 +790,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
     const float c = p.c, scale = p.scale;
 
     // Q tiles from first_plain on lie entirely at or below this wave's KV rows' diagonal (q >= kv for every pair)
+#if FA2_WIN
+#else
     const int first_plain = CAUSAL ? (kvw0 + 31 + kKvTile - 1) / kKvTile : 0;
+#endif
 
     // element form of a bias broadcast over the Q rows (row stride 0: a [B, 1, 1, Nkv] key-padding mask, the mask of SD cross-attention): the
     // score's bias depends on the lane's KV row only — ONE load before the sweep instead of 32 per tile and lane
@@ -798,6 +894,16 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
                     if (kvrow > qi + 32) s1[r] = 0.f;
                 }
             }
+#if FA2_WIN
+            if (masked) {                         // window: rows outside [q_lo, q_hi] do not see this lane's key (wave-uniform branch)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qi = q0t + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    if (qi < q_lo || qi > q_hi) s0[r] = 0.f;
+                    if (qi + 32 < q_lo || qi + 32 > q_hi) s1[r] = 0.f;
+                }
+            }
+#endif
             if constexpr (WANT_DK) {
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
@@ -876,12 +982,20 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
     for (int vt = vt0; vt < vnt; ++vt) {
         const int st = DBUF ? (vt - vt0) & 1 : 0;
         if (DBUF && vt + 1 < vnt) stage_next(st ^ 1);
+#if FA2_WIN
+        if (tile >= tile0_w && tile < tend_w && wave_live) tile_body(tile, st, tile < first_plain || tile >= last_plain);
+#else
         if ((!CAUSAL || tile >= tile0_w) && wave_live) tile_body(tile, st, CAUSAL && tile < first_plain);
+#endif
         __syncthreads();
         if (!DBUF && vt + 1 < vnt) { stage_next(0); __syncthreads(); }
         if (++tile == ntiles) tile = tile0;
     }
+#if FA2_WIN
+    if constexpr (false) {
+#else
     if constexpr (!CAUSAL && NW == 8 && BOTH) {
+#endif
         if (part >= 0) {                   // unscaled f32 partial dK and dV tiles
             const int64_t slot = sidx * p.nsplit + part, ntile = (int64_t)p.split_items * p.nsplit;
             store_partial_t<DT>(acc, p.ws + slot * kSplitRows * HD, 32 * wave + l31, hi);
@@ -920,6 +1034,11 @@ __device__ __forceinline__ void pair_mid_barrier() {
 // of a pair runs beside the MFMAs of the other.  Stage: Q row | dO row | Q tr | dO tr | L | D, two stages (129 KiB) + 16 KiB of slots.
 template <int HD, bool BF16, bool CAUSAL, int KSN = HD / 16, int DTN = HD / 32>
 __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p) {
+#if FA2_WIN
+    // FA2_WIN (fa2_bwd_window; kv_group = 1): the Q tiles of the transposed band only, masked on both sides (see bwd_dkv_kernel).
+    static_assert(!CAUSAL, "the windowed passes carry the causal edge in the window");
+    const Window win = get_window(p);
+#endif
     constexpr int NW = 8;
     using L_ = BwdLane<HD, NW>;
     constexpr int kRows = 128;
@@ -967,10 +1086,27 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
     auto qrs = q_rsrc(h * G), grs = g_rsrc(h * G), lrs = l_rsrc(p.lse, h * G), drs = l_rsrc(p.delta, h * G);
     const uint32_t q_rowb = (uint32_t)p.qs[2] * 2u, g_rowb = (uint32_t)p.dos[2] * 2u;
 
+#if FA2_WIN
+    int ntiles, tile0, first_plain, last_plain, q_lo, q_hi;
+    {
+        int first, n;
+        window_row_range(p.Nq, p.Nkv, win.left, win.right, win.off, kv0, kRows, kKvTile, &first, &n);
+        tile0 = first;
+        ntiles = first + n;
+        q_lo = win.right < 0 ? 0 : kvrow - win.off - win.right;
+        q_hi = win.left < 0 ? 0x7fffffff : kvrow - win.off + win.left;
+        const int lo_full = win.right < 0 ? 0 : kvw0 + 31 - win.off - win.right;
+        first_plain = lo_full > 0 ? (lo_full + kKvTile - 1) / kKvTile : 0;
+        const int hi_full = win.left < 0 ? 0x7ffffff0 : kvw0 - win.off + win.left;
+        last_plain = hi_full < -1 ? 0 : (hi_full + 1) / kKvTile;
+    }
+    const int vnt = G * (ntiles > tile0 ? ntiles - tile0 : 0);      // the virtual sweep (G = 1 here)
+#else
     const int ntiles = (p.Nq + kKvTile - 1) / kKvTile;
     const int tile0 = CAUSAL ? kv0 / kKvTile : 0;
     const int vnt = G * (ntiles > tile0 ? ntiles - tile0 : 0);      // the virtual sweep: G member heads, each from tile0
     const int first_plain = CAUSAL ? (kvw0 + 31 + kKvTile - 1) / kKvTile : 0;
+#endif
 
     // per-lane source offsets of the staging loads within a tile (loop-invariant); the tile's own byte offset rides in soffset
     uint32_t qr_src[NPASS], qt_src[NPASS], gr_src[NPASS], gt_src[NPASS];
@@ -1072,6 +1208,17 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
                     if (kvrow > qi + 32) s1[r] = 0.f;
                 }
             }
+#if FA2_WIN
+            if (tile < first_plain || tile >= last_plain) {           // window: rows outside [q_lo, q_hi] do not see this lane's key
+                const int q0t = tile * kKvTile;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int qi = q0t + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    if (qi < q_lo || qi > q_hi) s0[r] = 0.f;
+                    if (qi + 32 < q_lo || qi + 32 > q_hi) s1[r] = 0.f;
+                }
+            }
+#endif
             u32x4 xf[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {

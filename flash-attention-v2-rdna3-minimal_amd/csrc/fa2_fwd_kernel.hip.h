@@ -36,6 +36,14 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "fa2_window.h"
+
+// FA2_WIN = 1 (window_hip.cpp only, which also gives the kernels names of their own): the sliding-window forms of the kernels below.  The additions are
+// preprocessor blocks, not template parameters, so that every other translation unit compiles exactly the text it compiled before they existed.
+#ifndef FA2_WIN
+#define FA2_WIN 0
+#endif
+
 // ---- tuning knobs (A/B-tested on MI355X with tools/kbench.py; numbers at B2 H16 N4096 D128 fp16) ----
 #ifndef FA2_DEFER_THR        // skip the O rescale while the row max grew by <= this (log2 units); <0: always rescale.
 #define FA2_DEFER_THR 8.0f   // 0 = exact FA2 (rescale whenever any row's max grows); 8 keeps P <= 2^8 (fp16/bf16 safe): +5 %
@@ -120,6 +128,17 @@ struct FwdParams {
     float* ws;                           // [split_items * nsplit] partial O tiles of kSplitRows x HD floats, then as many LSE rows of kSplitRows
     int kv_group = 1;                    // grouped-query attention: Q head h reads K / V head h / kv_group (1: one K / V head per Q head)
 };
+
+// Sliding window (FA2_WIN kernels; fa2_fwd_window / fa2_bwd_window, fa2_window.h).  A windowed call has no bias, so its three integers travel in the bias
+// stride fields of FwdParams / BwdParams: the parameter blocks keep their layout, and every other kernel its kernarg segment.
+template <typename P>
+__host__ __device__ inline void set_window(P& p, const Window& w) { p.bs[0] = w.left; p.bs[1] = w.right; p.bs[2] = w.off; }
+template <typename P>
+__host__ __device__ inline Window get_window(const P& p) {
+    Window w;
+    w.left = (int)p.bs[0]; w.right = (int)p.bs[1]; w.off = (int)p.bs[2];
+    return w;
+}
 
 constexpr int kSplitRows = 256;          // rows of a split item (the 8-wave workgroup shape)
 constexpr int kMaxSplit = 8;
@@ -271,6 +290,11 @@ constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && 
 // workgroup-uniform run-time bound.  Defaults = the full kernel.  KV-split parts keep the workspace layout of HD (the merge kernel never
 // reads columns >= D).  Reference counterpart: the host-side zero padding of D to a
 // multiple of 32 (kernel_fp16.cu:763-779) — it multiplies the zeros.
+//
+// FA2_WIN (fa2_fwd_window; window_hip.cpp: CAUSAL = false, BIAS = 0, QB = 1): sliding-window attention.  The workgroup sweeps the KV tiles
+// [first, first + n) that hold a key one of its rows sees (fa2_window.h: window_tile_range — kv_first / nkv below, as for a KV-split part), a wave
+// computes only the tiles of its own 32 rows' range [tf_w, ntiles_w), tiles cut by the band's left or right edge are masked per lane (lim_lo, lim_hi)
+// and the tiles in between run the unmasked steady-state loop.  A row that sees no key ends with O = 0, lse = -inf (the BIAS kernels' convention).
 template <int HD, int HDV, bool BF16, bool CAUSAL, int NW, int QB, int BIAS = 0, int KSQ = HD / 16, int DTN = HDV / 32, bool RTD = false>
 __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams p) {
     constexpr int kRowsPerBlock = NW * QB * 32;   // Q rows per workgroup (p.nqblk = ceil(Nq / kRowsPerBlock))
@@ -296,7 +320,15 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     // multiple of 8 a part lands on the XCD (block index % 8) its item's head is mapped to
     int bid = blockIdx.x + p.blk0;
     int part = -1, sidx = 0;
+#if FA2_WIN
+    static_assert(!CAUSAL && !BIAS && QB == 1, "the windowed kernels carry the causal edge in the window, no bias, one q block per wave");
+    const Window win = get_window(p);
+#endif
+#if FA2_WIN
+    if constexpr (false) {
+#else
     if constexpr (!CAUSAL && !BIAS && HD == HDV && NW * QB * 32 == kSplitRows) {
+#endif
         if (p.nsplit > 1 && bid >= p.full_items) {
             const int j = bid - p.full_items;
             part = j / p.split_items;
@@ -316,6 +348,14 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         kv_first = t0 * kKvTile;
         nkv = (t1 * kKvTile < p.Nkv ? t1 * kKvTile : p.Nkv) - kv_first;
     }
+#if FA2_WIN
+    {                           // the tiles that hold a key this workgroup's rows see; none: nkv = 0, every score of the prologue's tile is masked
+        int first, n;
+        window_tile_range(p.Nq, p.Nkv, win.left, win.right, win.off, q0, kRowsPerBlock, kKvTile, &first, &n);
+        kv_first = first * kKvTile;
+        nkv = n ? ((first + n) * kKvTile < p.Nkv ? (first + n) * kKvTile : p.Nkv) - kv_first : 0;
+    }
+#endif
     const int qw0 = q0 + wave * kRowsPerWave;   // first Q row of this wave
     int qrow[QB];                               // this lane's Q row in each of its blocks (may be >= Nq)
 #pragma unroll
@@ -385,6 +425,22 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         const int nt_w = (qw0 + kRowsPerWave - 1) / kKvTile + 1;
         ntiles_w = nt_w < ntiles ? nt_w : ntiles;
     }
+#if FA2_WIN
+    // this wave's own tile range [tf_w, ntiles_w) (tile indices count from kv_first), the absolute key range [w_lo_full, w_hi_full] every one of
+    // its rows sees (tiles inside it need no mask), and this lane's row's first / last visible key
+    int tf_w, w_lo_full, w_hi_full, lim_lo, lim_hi;
+    {
+        int first, n;
+        window_tile_range(p.Nq, p.Nkv, win.left, win.right, win.off, qw0, kRowsPerWave, kKvTile, &first, &n);
+        tf_w = n ? first - kv_first / kKvTile : 0;
+        ntiles_w = n ? tf_w + n : 0;
+        const int pos0 = qw0 + win.off, pos = qrow[0] + win.off;
+        w_lo_full = win.left < 0 ? 0 : pos0 + kRowsPerWave - 1 - win.left;
+        w_hi_full = win.right < 0 || pos0 + win.right > p.Nkv - 1 ? p.Nkv - 1 : pos0 + win.right;
+        lim_lo = win.left < 0 ? 0 : pos - win.left;
+        lim_hi = win.right < 0 || pos + win.right > p.Nkv - 1 ? p.Nkv - 1 : pos + win.right;
+    }
+#endif
 
     f32x16 acc[QB][DT];
     float m_run[QB], l_run[QB];  // running reference max (raw score units) / row sum (this lane's kv half)
@@ -761,7 +817,26 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         for (int qb = 0; qb < QB; ++qb) {
             f32x16& s0 = s[qb][0];
             f32x16& s1 = s[qb][1];
+#if FA2_WIN
             if constexpr (decltype(masked)::value) {
+                const int kv0 = kv_first + tile * kKvTile;       // (absolute key index: the limits are absolute)
+                if (kv0 < w_lo_full || kv0 + kKvTile - 1 > w_hi_full) {
+                    int lo = lim_lo, hi_k = lim_hi, kvb = kv0 + 4 * hi;
+                    asm volatile("" : "+v"(lo), "+v"(hi_k), "+v"(kvb));      // (opaque: keeps LICM from hoisting 32 lane masks, see below)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int kvi = kvb + (r & 3) + 8 * (r >> 2);
+                        if (kvi > hi_k || kvi < lo) s0[r] = -INFINITY;
+                        if (kvi + 32 > hi_k || kvi + 32 < lo) s1[r] = -INFINITY;
+                    }
+                }
+            }
+#endif
+#if FA2_WIN
+            if constexpr (false) {
+#else
+            if constexpr (decltype(masked)::value) {
+#endif
                 const int kv0 = tile * kKvTile;
                 const bool need_causal = CAUSAL && (kv0 + kKvTile - 1 > qw0 + 32 * qb);
                 const bool need_tail = kv0 + kKvTile > nkv;
@@ -797,6 +872,9 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
                 const float m_new = __builtin_fmaxf(m_run[qb], mx[qb]);
                 float alpha = __builtin_amdgcn_exp2f((m_run[qb] - m_new) * c);
                 if constexpr (BIAS) alpha = m_new == -INFINITY ? 1.0f : alpha;   // row fully masked so far: nothing accumulated
+#if FA2_WIN
+                alpha = m_new == -INFINITY ? 1.0f : alpha;                       // (a window leaves rows fully masked so far, too)
+#endif
                 m_run[qb] = m_new;
                 l_run[qb] *= alpha;
 #pragma unroll
@@ -814,7 +892,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         for (int qb = 0; qb < QB; ++qb) {
             f32x16& s0 = s[qb][0];
             f32x16& s1 = s[qb][1];
+#if FA2_WIN
+            const float mc = m_run[qb] == -INFINITY ? 0.f : m_run[qb] * c;             // fully masked so far: P = 2^(-inf - 0) = 0
+#else
             const float mc = (BIAS && m_run[qb] == -INFINITY) ? 0.f : m_run[qb] * c;   // fully masked so far: P = 2^(-inf - 0) = 0
+#endif
             float rs0 = 0.f, rs1 = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -867,7 +949,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         constexpr int MODE = decltype(mode)::value;
         constexpr bool FAST = MODE != 0;
         const bool more1 = FAST || tile + 1 < ntiles, more2 = FAST || tile + 2 < ntiles;
+#if FA2_WIN
+        const bool next_w = FAST || (tile + 1 < ntiles_w && tile + 1 >= tf_w), cur_w = FAST || (tile < ntiles_w && tile >= tf_w);
+#else
         const bool next_w = FAST || tile + 1 < ntiles_w, cur_w = FAST || tile < ntiles_w;
+#endif
 #if FA2_IGLP >= 0
         if constexpr (FAST) __builtin_amdgcn_iglp_opt(FA2_IGLP);   // scheduler hint for the steady-state block
 #endif
@@ -908,13 +994,35 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         const int unmasked_c = CAUSAL ? (qw0 + 1) / kKvTile : 0x7fffffff;  // tiles fully below the diagonal
         const int unmasked = unmasked_kv < unmasked_c ? unmasked_kv : unmasked_c;
         n_fast = n_fast < unmasked - 1 ? n_fast : unmasked - 1;            // tile+1 <= unmasked-1
+#if FA2_WIN
+        {                                                                  // tiles fully at or below every row's right edge (and inside Nkv)
+            const int unmasked_r = w_hi_full + 1 >= kv_first ? (w_hi_full + 1 - kv_first) / kKvTile : 0;
+            n_fast = n_fast < unmasked_r - 1 ? n_fast : unmasked_r - 1;
+        }
+#endif
         n_fast = n_fast < 0 ? 0 : n_fast & ~1;
     }
+#if FA2_WIN
+    // the steady state starts at f0: tile f0 is one of this wave's, tile f0 + 1 lies fully right of every row's left edge
+    int f0;
+    {
+        const int plain0 = w_lo_full > kv_first ? (w_lo_full - kv_first + kKvTile - 1) / kKvTile : 0;     // first tile without a left edge
+        f0 = tf_w > plain0 - 1 ? tf_w : plain0 - 1;
+        f0 = (f0 + 1) & ~1;
+        f0 = f0 < n_fast ? f0 : n_fast;
+    }
+#endif
     constexpr std::integral_constant<int, 0> P0{};
     constexpr std::integral_constant<int, 1> P1{};
     constexpr std::integral_constant<int, 0> GENERIC{};
     constexpr std::integral_constant<int, 1> STEADY{};
     int tile = 0;
+#if FA2_WIN
+    for (; tile < f0; tile += 2) {                // (f0 <= n_fast <= ntiles - 2: both tiles exist)
+        step(tile, P0, GENERIC, sa, sb);
+        step(tile + 1, P1, GENERIC, sb, sa);
+    }
+#endif
     for (; tile < n_fast; tile += 2) {
         step(tile, P0, STEADY, sa, sb);
         step(tile + 1, P1, STEADY, sb, sa);
@@ -932,7 +1040,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     // row-major, so that every global store instruction writes whole contiguous rows (64 lanes x 16 B = 4 rows of
     // 256 B) instead of 32 B of each of 32 rows.  The K/V buffers are free by now; rows are padded by 16 B so both the
     // column-wise writes and the row-wise reads are bank-conflict free.
+#if FA2_WIN
+    if constexpr (false) {
+#else
     if constexpr (!CAUSAL && !BIAS && HD == HDV && NW * QB * 32 == kSplitRows) {
+#endif
         if (part >= 0) {
             // a part: normalised f32 partial tile + partial LSE -> workspace.  Layout of a tile: float (((dt*4 + g) * 256 + row) * 8 + 4*hi + e)
             // for d = 32dt + 8g + 4hi + e — one store instruction of the wave writes 1 KiB of consecutive bytes.
@@ -962,7 +1074,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         __syncthreads();                                         // every wave is done reading the K / V buffers
         char* img = smem + wave * (32 * EROW);
         const float l_tot = half_swap_sum(l_run[0]);
+#if FA2_WIN
+        const float inv_l = !(l_tot > 0.f) ? 0.f : 1.0f / l_tot;             // row that sees no key: O = 0 (lse = -inf)
+#else
         const float inv_l = (BIAS && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;   // fully masked row: O = 0 (lse = -inf)
+#endif
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
@@ -994,7 +1110,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
         const float l_tot = half_swap_sum(l_run[qb]);
+#if FA2_WIN
+        const float inv_l = !(l_tot > 0.f) ? 0.f : 1.0f / l_tot;
+#else
         const float inv_l = (BIAS && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;
+#endif
         if (qrow[qb] < p.Nq) {
             uint16_t* op = (uint16_t*)p.o + b * p.os[0] + h * p.os[1] + (int64_t)qrow[qb] * p.os[2] + vcol0;
 #pragma unroll

@@ -175,6 +175,12 @@ FA2_HIDDEN int launch_bwd_merge_bf16(int HD, const BwdParams& p, int which, hipS
 // HIP backward through a biased / masked forward (bwd_bias_hip.cpp): dQ, dV, dK; head dims up to 256
 FA2_HIDDEN int launch_bwd_bias_hip_f16(int HD, const BwdParams& p, bool causal, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_bias_hip_bf16(int HD, const BwdParams& p, bool causal, hipStream_t stream);
+// sliding-window attention (window_hip.cpp): the WIN forms of the compiler-scheduled forward (rows = 128 | 256 per workgroup) and backward passes;
+// the window, causal flag already folded in, travels in p.bs (set_window / get_window, fa2_fwd_kernel.hip.h)
+FA2_HIDDEN int launch_fwd_window_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_fwd_window_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_window_f16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_window_bf16(int HD, const BwdParams& p, hipStream_t stream);
 // hand-scheduled backward, head dim exactly 128 (bwd_asm.cpp); same `parts`
 // neg_delta: the dQ pass writes -delta (the hand-scheduled dK/dV pass reads it as such; the HIP dK/dV passes read +delta)
 // kfold: the dK / dV body whose P side folds scale * log2(e) into its K fragments (option "fold"; host.cpp: bwd_folds)

@@ -108,8 +108,18 @@ at::Tensor workspace(size_t bytes, const at::Tensor& like, hipStream_t stream) {
     return pool.back().ws;
 }
 
-std::vector<at::Tensor> forward(at::Tensor q, at::Tensor k, at::Tensor v, int64_t Br, int64_t Bc, int64_t flags, double scale,
-                                bool permute_NH) {
+// sliding window (flash_attention(window=..., q_offset=...)): (window_left, window_right, q_offset), -1 = unbounded; the words of
+// rocwmma_fattn/_fa2_lib.py::WINDOW_MESSAGE, so that both front ends refuse bad values alike
+struct Win { int64_t left, right, off; };
+void check_window(const Win& w) {
+    TORCH_CHECK_VALUE(w.left >= -1 && w.right >= -1 && w.off >= 0 && w.left < (int64_t(1) << 31) && w.right < (int64_t(1) << 31) && w.off < (int64_t(1) << 31),
+                      "fa2: window is None, an int W (= (W, W)) or (left, right), each -1 / None (unbounded) or >= 0, and q_offset is an int >= 0, got window=(",
+                      w.left, ", ", w.right, ") q_offset=", w.off);
+}
+
+std::vector<at::Tensor> forward_impl(at::Tensor q, at::Tensor k, at::Tensor v, int64_t Br, int64_t Bc, int64_t flags, double scale,
+                                     bool permute_NH, const Win* win) {
+    if (win) check_window(*win);
     // flags: the reference's `causal` (0 / 1; a Python bool converts), or the C-ABI's call flags FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE
     const bool causal = (flags & FA2_FLAG_CAUSAL) != 0;
     (void)Bc;
@@ -173,10 +183,13 @@ std::vector<at::Tensor> forward(at::Tensor q, at::Tensor k, at::Tensor v, int64_
     const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream();
     // scratch for the KV-split of a partly filled last round of workgroups (fa2_fwd_ws): the per-stream block above
     at::Tensor ws;
-    const size_t ws_bytes = causal ? 0 : cached_ws_bytes(0, dtype_code, q.device().index(), b, h, n, n_kv, d_kernel, hkv == h ? 0 : hkv);
+    const size_t ws_bytes = (causal || win) ? 0 : cached_ws_bytes(0, dtype_code, q.device().index(), b, h, n, n_kv, d_kernel, hkv == h ? 0 : hkv);
     if (ws_bytes) ws = workspace(ws_bytes, q, stream);
     else workspace_unused(q.device().index(), stream);
-    const int rc = hkv == h ? fa2_fwd_ws(dtype_code, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), O.data_ptr(), L.data_ptr<float>(), (int)b, (int)h,
+    const int rc = win ? fa2_fwd_window(dtype_code, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), O.data_ptr(), L.data_ptr<float>(), (int)b, (int)h,
+                                        (int)hkv, (int)n, (int)n_kv, (int)d_kernel, qs, ks, vs, os, ls, (float)scale, (int)(flags & 3),
+                                        (int)win->left, (int)win->right, (int)win->off, (void*)stream)
+                 : hkv == h ? fa2_fwd_ws(dtype_code, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), O.data_ptr(), L.data_ptr<float>(), (int)b, (int)h,
                                          (int)n, (int)n_kv, (int)d_kernel, qs, ks, vs, os, ls, (float)scale, (int)(flags & 3),
                                          ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, (void*)stream)
                             : fa2_fwd_gqa(dtype_code, qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), O.data_ptr(), L.data_ptr<float>(), (int)b, (int)h,
@@ -189,13 +202,24 @@ std::vector<at::Tensor> forward(at::Tensor q, at::Tensor k, at::Tensor v, int64_
     return {O_fwd, qp, kp, vp, O, L};
 }
 
+std::vector<at::Tensor> forward(at::Tensor q, at::Tensor k, at::Tensor v, int64_t Br, int64_t Bc, int64_t flags, double scale, bool permute_NH) {
+    return forward_impl(q, k, v, Br, Bc, flags, scale, permute_NH, nullptr);
+}
+
+std::vector<at::Tensor> forward_window(at::Tensor q, at::Tensor k, at::Tensor v, int64_t Br, int64_t Bc, int64_t flags, double scale, bool permute_NH,
+                                       int64_t window_left, int64_t window_right, int64_t q_offset) {
+    const Win w{window_left, window_right, q_offset};
+    return forward_impl(q, k, v, Br, Bc, flags, scale, permute_NH, &w);
+}
+
 // backward(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH) -> [dQ, dK, dV] of the reference's module
 // (rocwmma_fattn/host.cpp:47-58, kernel_fp16.cu:878-1028), what _FlashAttnWmma.backward does in Python for unmasked calls: outputs and the delta
 // workspace from torch's allocator, the split's scratch when fa2_bwd_workspace_bytes asks for it, results sliced to the actual sizes.
-std::vector<at::Tensor> backward(at::Tensor Q, at::Tensor K, at::Tensor V, at::Tensor O, at::Tensor dO, at::Tensor L, int64_t act_n, int64_t act_nkv,
-                                 int64_t act_d, int64_t Br, int64_t Bc, bool causal, double scale, bool permute_NH) {
+std::vector<at::Tensor> backward_impl(at::Tensor Q, at::Tensor K, at::Tensor V, at::Tensor O, at::Tensor dO, at::Tensor L, int64_t act_n, int64_t act_nkv,
+                                      int64_t act_d, int64_t Br, int64_t Bc, bool causal, double scale, bool permute_NH, const Win* win) {
     (void)Br;
     (void)Bc;
+    if (win) check_window(*win);
     TORCH_CHECK(Q.is_cuda() && dO.is_cuda(), "fa2: tensors must be on a ROCm device (no CPU path in this operator)");
     const int n_ax = permute_NH ? 1 : 2, h_ax = permute_NH ? 2 : 1;
     const int64_t b = Q.size(0), h = Q.size(h_ax), dk = Q.size(3), hkv = K.size(h_ax);
@@ -205,8 +229,8 @@ std::vector<at::Tensor> backward(at::Tensor Q, at::Tensor K, at::Tensor V, at::T
         // dK / dV summed over each group in f32 and rounded once.  fa2_bwd_gqa's in-kernel sum runs a grid g times smaller and lost to this on every
         // shape measured
         const int64_t g = h / hkv;
-        std::vector<at::Tensor> r = backward(Q, K.repeat_interleave(g, h_ax), V.repeat_interleave(g, h_ax), O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal,
-                                             scale, permute_NH);
+        std::vector<at::Tensor> r = backward_impl(Q, K.repeat_interleave(g, h_ax), V.repeat_interleave(g, h_ax), O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal,
+                                                  scale, permute_NH, win);
         return {r[0], r[1].unflatten(h_ax, {hkv, g}).sum(h_ax + 1), r[2].unflatten(h_ax, {hkv, g}).sum(h_ax + 1)};
     }
     const int dtype_code = Q.scalar_type() == at::kHalf ? FA2_DTYPE_F16 : FA2_DTYPE_BF16;
@@ -226,14 +250,29 @@ std::vector<at::Tensor> backward(at::Tensor Q, at::Tensor K, at::Tensor V, at::T
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
     const hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Q.device().index()).stream();
     at::Tensor ws;
-    const size_t ws_bytes = causal ? 0 : cached_ws_bytes(1, dtype_code, Q.device().index(), b, h, act_n, act_nkv, dk);
+    const size_t ws_bytes = (causal || win) ? 0 : cached_ws_bytes(1, dtype_code, Q.device().index(), b, h, act_n, act_nkv, dk);
     if (ws_bytes) ws = workspace(ws_bytes, Q, stream);
     else workspace_unused(Q.device().index(), stream);
-    const int rc = fa2_bwd_ws(dtype_code, Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr<float>(), dQ.data_ptr(),
+    const int rc = win ? fa2_bwd_window(dtype_code, Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr<float>(), dQ.data_ptr(),
+                                        dK.data_ptr(), dV.data_ptr(), delta.data_ptr<float>(), (int)b, (int)h, (int)act_n, (int)act_nkv, (int)dk, qs, ks, vs, os,
+                                        gs, dqs, dks, dvs, ls, (float)scale, causal ? 1 : 0, (int)win->left, (int)win->right, (int)win->off, (void*)stream)
+                       : fa2_bwd_ws(dtype_code, Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr<float>(), dQ.data_ptr(),
                               dK.data_ptr(), dV.data_ptr(), delta.data_ptr<float>(), (int)b, (int)h, (int)act_n, (int)act_nkv, (int)dk, qs, ks, vs, os, gs,
                               dqs, dks, dvs, ls, (float)scale, causal ? 1 : 0, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, (void*)stream);
     TORCH_CHECK(rc == 0, "fa2 call failed (", rc, "): ", fa2_error_string(rc));
     return {dQ.narrow(n_ax, 0, act_n).narrow(3, 0, act_d), dK.narrow(n_ax, 0, act_nkv).narrow(3, 0, act_d), dV.narrow(n_ax, 0, act_nkv).narrow(3, 0, act_d)};
+}
+
+std::vector<at::Tensor> backward(at::Tensor Q, at::Tensor K, at::Tensor V, at::Tensor O, at::Tensor dO, at::Tensor L, int64_t act_n, int64_t act_nkv,
+                                 int64_t act_d, int64_t Br, int64_t Bc, bool causal, double scale, bool permute_NH) {
+    return backward_impl(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, nullptr);
+}
+
+std::vector<at::Tensor> backward_window(at::Tensor Q, at::Tensor K, at::Tensor V, at::Tensor O, at::Tensor dO, at::Tensor L, int64_t act_n, int64_t act_nkv,
+                                        int64_t act_d, int64_t Br, int64_t Bc, bool causal, double scale, bool permute_NH, int64_t window_left,
+                                        int64_t window_right, int64_t q_offset) {
+    const Win w{window_left, window_right, q_offset};
+    return backward_impl(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, &w);
 }
 
 // The autograd node of FlashAttentionFunction (rocwmma_fattn/FlashAttn.py:45-92 of the reference: forward saves q_pad, k_pad, v_pad, O, L; backward
@@ -278,5 +317,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("forward", &forward, "forward(q, k, v, Br, Bc, causal (bool, or the C-ABI's call flags), scale, permute_NH) -> [O_fwd, q_pad, k_pad, v_pad, O, L]");
     m.def("attention", &attention, "attention(q, k, v, causal, scale, permute_NH) -> O, differentiable (the C++ autograd node of FlashAttentionFunction)");
     m.def("workspace_pool_bytes", &workspace_pool_bytes, "bytes the per-stream scratch blocks of the split hold right now");
+    m.def("forward_window", &forward_window, "forward(...) under a sliding window: ..., window_left, window_right, q_offset (C-ABI fa2_fwd_window)");
+    m.def("backward_window", &backward_window, "backward(...) of forward_window: ..., window_left, window_right, q_offset (C-ABI fa2_bwd_window)");
     m.def("backward", &backward, "backward(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH) -> [dQ, dK, dV]");
 }

@@ -390,6 +390,20 @@ int launch_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal, hipStrea
     return 0;
 }
 
+// A windowed call as the kernels see it: the causal flag folded into the window (right = 0), and the calls whose window masks nothing for their
+// lengths told apart — those ARE plain calls (kind 0) or today's top-left causal call (kind 1) and run exactly what fa2_fwd_gqa / fa2_bwd run.
+struct WindowCall { int kind; fa2::Window w; };     // kind: 0 plain, 1 plain causal, 2 windowed, -1 bad arguments
+WindowCall reduce_window(int Nq, int Nkv, int left, int right, int off, bool causal) {
+    WindowCall c;
+    c.kind = -1;
+    if (Nq < 1 || Nkv < 1 || !fa2::window_args_ok(Nq, Nkv, left, right, off)) return c;
+    c.w.left = left; c.w.right = fa2::window_normalize_right(right, causal); c.w.off = off;
+    if (fa2::window_is_full(Nq, Nkv, c.w.left, c.w.right, off)) c.kind = 0;
+    else if (c.w.right == 0 && off == 0 && fa2::window_is_full(Nq, Nkv, c.w.left, -1, 0)) c.kind = 1;
+    else c.kind = 2;
+    return c;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool strides_ok(const int64_t* s) { return s[0] % 8 == 0 && s[1] % 8 == 0 && s[2] % 8 == 0 && s[2] > 0; }
 
@@ -458,7 +472,7 @@ const char* fa2_error_string(int code) {
     switch (code) {
         case FA2_OK: return "ok";
         case FA2_ERR_NULL_POINTER: return "fa2: null pointer argument";
-        case FA2_ERR_BAD_SHAPE: return "fa2: B, H, Nq, Nkv, D must be >= 1 and one head's matrix must span < 2 GiB";
+        case FA2_ERR_BAD_SHAPE: return "fa2: B, H, Nq, Nkv, D must be >= 1 and one head's matrix must span < 2 GiB; window_left / window_right are -1 or >= 0, q_offset >= 0";
         case FA2_ERR_HEAD_DIM: return "fa2: head dim not supported (pad D to fa2_padded_head_dim(D))";
         case FA2_ERR_ALIGNMENT: return "fa2: pointers must be 16-byte aligned, strides multiples of 8 elements, last dim contiguous";
         case FA2_ERR_DTYPE: return "fa2: dtype must be FA2_DTYPE_F16 or FA2_DTYPE_BF16";
@@ -477,7 +491,8 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
                     int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
                     const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
                     float scale, int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
-                    void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, fa2_fwd_plan_t* plan_out = nullptr, int Hkv = 0) {
+                    void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, fa2_fwd_plan_t* plan_out = nullptr, int Hkv = 0,
+                    const fa2::Window* win = nullptr) {
     // `causal` carries the call's flags: bit 0 = causal mask, bit 1 = FA2_FLAG_EXACT_SCALE (this call scales the f32 product whatever option "fold" says)
     // Until round 5 any non-zero value meant "causal"; a caller that still passes another truthy int would silently get a non-causal forward: refuse it
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
@@ -562,6 +577,19 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
 
     hipStream_t stream = (hipStream_t)hip_stream;
     const bool bf16 = dtype == FA2_DTYPE_BF16;
+    if (win) {          // fa2_fwd_window with a window that masks something (reduce_window kind 2): the WIN kernels, contract 0
+        if ((int64_t)B * H * ((Nq + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
+        fa2::set_window(p, *win);
+        const int rows = HD > 256 ? 128 : pick_rows(p);
+        if (plan_out) {
+            std::memset(plan_out, 0, sizeof(*plan_out));
+            plan_out->kernel = FA2_KERNEL_HIP_WINDOW;
+            plan_out->rows = rows;
+            plan_out->heads_main = B * H;
+        }
+        if (plan_only) return FA2_OK;
+        return bf16 ? fa2::launch_fwd_window_bf16(HD, p, rows, stream) : fa2::launch_fwd_window_f16(HD, p, rows, stream);
+    }
     if (bias_kind != FA2_BIAS_NONE) {
         if ((int64_t)B * H * ((Nq + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
         if (plan_out) {
@@ -671,7 +699,7 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
             const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
             const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
             int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
-            void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, int Hkv = 0) {
+            void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, int Hkv = 0, const fa2::Window* win = nullptr) {
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;      // (as in fwd_impl: no value but the documented flag bits)
     causal &= 1;          // (bit 1, FA2_FLAG_EXACT_SCALE, is what the backward does anyway unless option "kfold" is set)
     if (ws_need) *ws_need = 0;
@@ -745,6 +773,10 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
     }
     hipStream_t stream = (hipStream_t)hip_stream;
     const bool bf16 = dtype == FA2_DTYPE_BF16;
+    if (win) {          // fa2_bwd_window with a window that masks something: the WIN passes
+        fa2::set_window(p, *win);
+        return bf16 ? fa2::launch_bwd_window_bf16(HD, p, stream) : fa2::launch_bwd_window_f16(HD, p, stream);
+    }
     if (bias_kind != FA2_BIAS_NONE)
         return bf16 ? fa2::launch_bwd_bias_hip_bf16(HD, p, causal != 0, stream) : fa2::launch_bwd_bias_hip_f16(HD, p, causal != 0, stream);
     return launch_bwd(HD, bf16, p, causal != 0, stream);
@@ -863,6 +895,68 @@ size_t fa2_bwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int
                             one, one, one, one, one, ls, 1.0f, causal, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need, Hkv) != FA2_OK)
         return 0;
     return need;
+}
+
+// ---- sliding-window attention: include/fa2_gfx950.h has the contract, fa2_window.h the arithmetic, window_hip.cpp the kernels
+int fa2_fwd_window(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
+                   int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
+                   float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream) {
+    if (Hkv < 1 || (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE))) return FA2_ERR_BAD_SHAPE;
+    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
+    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
+    const int f = (flags & FA2_FLAG_EXACT_SCALE) | (c.kind == 1 ? FA2_FLAG_CAUSAL : 0);
+    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
+                    scale, f, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, c.kind == 2 ? &c.w : nullptr);
+}
+
+int fa2_fwd_window_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                        float scale, int flags, int window_left, int window_right, int q_offset, size_t workspace_bytes, fa2_fwd_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || Nkv < 1 || D < 1 || (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE))) return FA2_ERR_BAD_SHAPE;
+    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
+    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
+    const int f = (flags & FA2_FLAG_EXACT_SCALE) | (c.kind == 1 ? FA2_FLAG_CAUSAL : 0);
+    const ContigStrides cs(H, Nq, Nkv, D), ck(Hkv, Nq, Nkv, D);
+    char* d = g_plan_dummy;
+    return fwd_impl(dtype, d, d, d, d, (float*)d, B, H, Nq, Nkv, D, q_strides ? q_strides : cs.q, k_strides ? k_strides : ck.k, k_strides ? k_strides : ck.k,
+                    q_strides ? q_strides : cs.q, cs.ls, scale, f, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, workspace_bytes, nullptr, plan, Hkv,
+                    c.kind == 2 ? &c.w : nullptr);
+}
+
+int fa2_bwd_window(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                   void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
+                   const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                   const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                   const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
+                   int flags, int window_left, int window_right, int q_offset, void* hip_stream) {
+    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
+    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
+    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
+    const int f = (flags & FA2_FLAG_EXACT_SCALE) | (c.kind == 1 ? FA2_FLAG_CAUSAL : 0);
+    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
+                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, f, nullptr, FA2_BIAS_NONE, nullptr, hip_stream,
+                    nullptr, 0, nullptr, 0, c.kind == 2 ? &c.w : nullptr);
+}
+
+int fa2_window_tile_range(int Nq, int Nkv, int window_left, int window_right, int q_offset, int causal, int row0, int rows, int tile,
+                          int* first_tile, int* ntiles) {
+    if (!first_tile || !ntiles) return FA2_ERR_NULL_POINTER;
+    if (Nq < 1 || Nkv < 1 || row0 < 0 || rows < 1 || tile < 1 || rows > (1 << 24) || row0 > 0x7fffffff - (1 << 24) ||
+        !fa2::window_args_ok(Nq, Nkv, window_left, window_right, q_offset))
+        return FA2_ERR_BAD_SHAPE;
+    fa2::window_tile_range(Nq, Nkv, window_left, fa2::window_normalize_right(window_right, causal), q_offset, row0, rows, tile, first_tile, ntiles);
+    return FA2_OK;
+}
+
+int fa2_window_row_range(int Nq, int Nkv, int window_left, int window_right, int q_offset, int causal, int key0, int keys, int tile,
+                         int* first_tile, int* ntiles) {
+    if (!first_tile || !ntiles) return FA2_ERR_NULL_POINTER;
+    if (Nq < 1 || Nkv < 1 || key0 < 0 || keys < 1 || tile < 1 || keys > (1 << 24) || key0 > 0x7fffffff - (1 << 24) ||
+        !fa2::window_args_ok(Nq, Nkv, window_left, window_right, q_offset))
+        return FA2_ERR_BAD_SHAPE;
+    fa2::window_row_range(Nq, Nkv, window_left, fa2::window_normalize_right(window_right, causal), q_offset, key0, keys, tile, first_tile, ntiles);
+    return FA2_OK;
 }
 
 #define FA2_BWD_ARGS                                                                                                    \

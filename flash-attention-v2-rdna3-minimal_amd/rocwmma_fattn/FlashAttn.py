@@ -52,7 +52,25 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=bias)
 
     @staticmethod
-    def forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=None):
+    def forward_window(q, k, v, Br, Bc, causal, scale, permute_NH, window):
+        """forward() under a sliding window (extension: C-ABI fa2_fwd_window).  window = (window_left, window_right, q_offset), -1 = unbounded;
+        `causal`: a bool or the C-ABI's call flags.  Same 6-tensor return; grouped k / v run without expansion."""
+        fe = _frontend()
+        if fe is not None and hasattr(fe, "forward_window"):
+            return fe.forward_window(q, k, v, int(Br), int(Bc), _fa2_lib.call_flags(causal), float(scale), bool(permute_NH), *(int(x) for x in window))
+        return _FlashAttnWmma.forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, window=window)
+
+    @staticmethod
+    def backward_window(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, window):
+        """backward() of forward_window (C-ABI fa2_bwd_window; grouped K / V: expanded, dK / dV summed per group in f32)."""
+        fe = _frontend()
+        if fe is not None and hasattr(fe, "backward_window"):
+            return fe.backward_window(Q, K, V, O, dO, L, int(act_n), int(act_nkv), int(act_d), int(Br), int(Bc), bool(causal), float(scale), bool(permute_NH),
+                                      *(int(x) for x in window))
+        return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, window=window)
+
+    @staticmethod
+    def forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=None, window=None):
         """Returns [O_fwd, q_pad, k_pad, v_pad, O, L] like forward_fp16/forward_bf16 (kernel_fp16.cu:744-876).
         O and L keep the reference's shapes — rows padded to a multiple of Br with a zero tail, O_fwd a view into
         O (kernel_fp16.cu:761, :793-796, :865-875) — but nothing is COPIED to get there: the gfx950 kernels mask
@@ -61,6 +79,8 @@ class _FlashAttnWmma:
         kernel_fp16.cu:767-779).  Only a D that is not a multiple of 8 is zero-padded, to the next multiple of 8.
         Br sizes the N padding of O and L; Bc is accepted for signature compatibility.  `causal`: the reference's bool, or the C-ABI's call flags
         (_fa2_lib.FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE: the operator marks the forward of calls that will be differentiated)."""
+        if window is not None:
+            window = _fa2_lib.parse_window((window[0], window[1]), window[2])
         lib = _fa2_lib.load()
         flags = _fa2_lib.call_flags(causal)
         causal = bool(flags & _fa2_lib.FA2_FLAG_CAUSAL)
@@ -133,7 +153,10 @@ class _FlashAttnWmma:
             bias_t, kind, bstr = _prepare_bias(bias, b, h, n, n_kv, q_pad.dtype, q.device)
             args += (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
             fn = lib.fa2_fwd_bias
-        if h_kv != h:          # grouped-query attention: fa2_fwd_gqa (the MHA call's kernels, K / V addressed through the group)
+        if window is not None:     # sliding window: fa2_fwd_window (grouped or not: K / V addressed through the group)
+            with torch.cuda.device(dev):
+                rc = lib.fa2_fwd_window(*(args[:8] + (h_kv,) + args[8:]), *window, _raw_stream(dev))
+        elif h_kv != h:        # grouped-query attention: fa2_fwd_gqa (the MHA call's kernels, K / V addressed through the group)
             args = args[:8] + (h_kv,) + args[8:]
             with torch.cuda.device(dev):
                 rc = _launch_fwd_gqa(lib, args, dev, q.device, not causal)
@@ -165,8 +188,10 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias)
 
     @staticmethod
-    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None):
-        """backward() in Python (masked calls; every call when the compiled front end is absent)."""
+    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None, window=None):
+        """backward() in Python (masked calls; every call when the compiled front end is absent).  window: as forward_window's."""
+        if window is not None:
+            window = _fa2_lib.parse_window((window[0], window[1]), window[2])
         lib = _fa2_lib.load()
         if not (Q.is_cuda and dO.is_cuda):
             raise RuntimeError("fa2: tensors must be on a ROCm device (no CPU path in this operator)")
@@ -177,7 +202,8 @@ class _FlashAttnWmma:
         if h_kv != h:
             if bias is not None:
                 raise RuntimeError("fa2: the masked backward has no grouped-query form (flash_attention(mask=...) expands k / v for it)")
-            return _grouped_backward(_FlashAttnWmma.backward_py, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH)
+            mha = _FlashAttnWmma.backward_py if window is None else (lambda *a: _FlashAttnWmma.backward_py(*a, window=window))
+            return _grouped_backward(mha, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH)
         act_n, act_nkv, act_d = int(act_n), int(act_nkv), int(act_d)
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
         if dO.dtype != Q.dtype:
@@ -206,7 +232,10 @@ class _FlashAttnWmma:
             bias_t, kind, bstr = _prepare_bias(bias, b, h, act_n, act_nkv, Q.dtype, Q.device)
             args += (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
             fn = lib.fa2_bwd_bias
-        if not causal:
+        if window is not None:
+            args += tuple(window)
+            fn = lib.fa2_bwd_window
+        elif not causal:
             # scratch for the split of a partly filled last round of workgroups (fa2_bwd_ws / fa2_bwd_bias_ws, the backward's twins of fa2_fwd_ws)
             need = (lib.fa2_bwd_workspace_bytes if bias is None else lib.fa2_bwd_bias_workspace_bytes)(dtype_code, b, h, act_n, act_nkv, dk, 0)
             if need:
@@ -507,13 +536,78 @@ class _MaskedAttentionFunction(torch.autograd.Function):
         return dQ, dK, dV, None, None, None, None
 
 
-def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False):
+class _WindowAttentionFunction(torch.autograd.Function):
+    """autograd node of flash_attention(window=..., q_offset=...): forward = fa2_fwd_window, backward = fa2_bwd_window; saves the three integers."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, q, k, v, causal, scale, BNHD_fmt, window):
+        D = q.shape[3]
+        Br = 32 if D > 384 else 64                      # FlashAttn.py:56-67
+        flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | _fa2_lib.FA2_FLAG_EXACT_SCALE
+        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_window(q, k, v, Br, 128, flags, scale, BNHD_fmt, window)
+        n_ax = 1 if BNHD_fmt else 2
+        ctx.args = (causal, scale, q.shape[n_ax], k.shape[n_ax], D, BNHD_fmt, window)
+        ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L)
+        return o
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, do):
+        causal, scale, N, Nkv, D, BNHD_fmt, window = ctx.args
+        q, k, v, o, L = ctx.saved_tensors
+        dQ, dK, dV = flash_attn_wmma.backward_window(q, k, v, o, do, L, N, Nkv, D, 128, 128, causal, scale, BNHD_fmt, window)
+        return dQ, dK, dV, None, None, None, None
+
+
+def _band_mask(nq, nkv, window, causal, device):
+    """The window as a boolean keep-mask [Nq, Nkv] (True = attend): what flash_attention folds into `mask` when both are given."""
+    left, right, off = window
+    if causal:
+        right = 0
+    pos = torch.arange(nq, device=device).unsqueeze(1) + off
+    j = torch.arange(nkv, device=device).unsqueeze(0)
+    keep = torch.ones((nq, nkv), dtype=torch.bool, device=device)
+    if left >= 0:
+        keep &= j >= pos - left
+    if right >= 0:
+        keep &= j <= pos + right
+    return keep
+
+
+def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False, window=None, q_offset=0):
     """Forward attention that HONOURS `mask` — the extension the reference lists as to do (README.md:45; its
     FlashAttentionFunction accepts the argument and ignores it, FlashAttn.py:49, :74, and `FlashAttentionFunction.apply` here
     keeps doing exactly that so that existing call sites see no change).  `mask` follows
     torch.nn.functional.scaled_dot_product_attention(attn_mask=...): broadcastable to [B, H, Nq, Nkv]; bool = True where
     attention is allowed, float = added to the scaled scores.  mask=None is FlashAttentionFunction.apply.  Rows whose every
-    position is masked return zeros.  Differentiable in q, k, v (C-ABI fa2_bwd_bias; head dims up to 256); the mask gets no gradient."""
+    position is masked return zeros.  Differentiable in q, k, v (C-ABI fa2_bwd_bias; head dims up to 256); the mask gets no gradient.
+
+    `window` / `q_offset`: sliding-window (local) attention.  window is None, an int W (= (W, W)) or (left, right) with -1 / None = unbounded;
+    query row i sits at key position i + q_offset and attends the keys [i + q_offset - left, i + q_offset + right]; `causal` then means right = 0
+    (causal=True, window=(W - 1, 0): W keys ending at the query's own; q_offset = Nkv - Nq: new queries against a longer KV cache).  The kernels
+    sweep only the tiles of the band (C-ABI fa2_fwd_window / fa2_bwd_window: no [Nq, Nkv] mask in memory, grouped k / v without expansion); rows
+    that see no key return zeros.  With a `mask` as well the band is folded into it and the masked path runs.  window=None, q_offset=0: as before."""
+    if window is not None or q_offset != 0:
+        win = _fa2_lib.parse_window(window, q_offset)
+        if mask is not None:
+            n_ax = 1 if BNHD_fmt else 2
+            band = _band_mask(q.shape[n_ax], k.shape[n_ax], win, causal, q.device)
+            if mask.dtype == torch.bool:
+                mask = mask & band
+            else:
+                mask = (mask + torch.zeros_like(band, dtype=mask.dtype)).masked_fill(~band, float("-inf"))      # (broadcast to [..., Nq, Nkv] first)
+            return flash_attention(q, k, v, mask, False, scale, BNHD_fmt)
+        h_ax = 2 if BNHD_fmt else 1
+        if q.dim() == 4 and k.dim() == 4 and k.shape[h_ax] != q.shape[h_ax]:
+            _check_groups(q.shape[h_ax], k.shape[h_ax])
+        D = q.shape[3]
+        if scale is None:
+            scale = D ** -0.5
+        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+            return _WindowAttentionFunction.apply(q, k, v, bool(causal), scale, BNHD_fmt, win)
+        Br = 32 if D > 384 else 64                      # FlashAttn.py:56-67
+        return flash_attn_wmma.forward_window(q, k, v, Br, 128, bool(causal), scale, BNHD_fmt, win)[0]
     if mask is None:
         return FlashAttentionFunction.apply(q, k, v, None, causal, scale, BNHD_fmt)
     h_ax = 2 if BNHD_fmt else 1

@@ -22,6 +22,7 @@ FA2_DTYPE_BF16 = 1
 FA2_BIAS_NONE, FA2_BIAS_IO_DTYPE, FA2_BIAS_F32, FA2_BIAS_BOOL = 0, 1, 2, 3     # bias_kind of fa2_fwd_bias
 
 FA2_KERNEL_HIP_256, FA2_KERNEL_HIP_128, FA2_KERNEL_ASM, FA2_KERNEL_HIP_BIAS = 1, 2, 3, 4              # fa2_fwd_plan_t.kernel
+FA2_KERNEL_HIP_WINDOW = 5                                                                               # ... of fa2_fwd_window_plan (an enumerator in the header)
 FA2_CONTRACT_PRESCALE_Q, FA2_CONTRACT_LSUM_P16 = 1, 2                                                   # fa2_fwd_plan_t.contract bits
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -74,6 +75,12 @@ SYMBOLS = {
     "fa2_fwd_gqa_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p, _i64p, ctypes.c_float, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(FwdPlan)]),
     "fa2_bwd_gqa": (ctypes.c_int, [ctypes.c_int] + _BWD_ARGTYPES[:12] + [ctypes.c_int] + _BWD_ARGTYPES[12:-1] + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "fa2_bwd_gqa_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
+    # sliding-window attention: fa2_fwd_gqa's / fa2_bwd's argument lists with (window_left, window_right, q_offset) in place of the workspace / before the stream
+    "fa2_fwd_window": (ctypes.c_int, [ctypes.c_int] + _FWD_ARGTYPES[:7] + [ctypes.c_int] + _FWD_ARGTYPES[7:-1] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "fa2_bwd_window": (ctypes.c_int, [ctypes.c_int] + _BWD_ARGTYPES[:-1] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "fa2_fwd_window_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p, _i64p, ctypes.c_float] + [ctypes.c_int] * 4 + [ctypes.c_size_t, ctypes.POINTER(FwdPlan)]),
+    "fa2_window_tile_range": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "fa2_window_row_range": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_set_option": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "fa2_get_option": (ctypes.c_int, [ctypes.c_char_p]),
     "fa2_error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -192,6 +199,53 @@ def gqa_plan(q, k, causal, scale=None, workspace_bytes=0):
                                   strides3(k.stride(0), k.stride(1), k.stride(2)), float(D ** -0.5 if scale is None else scale),
                                   call_flags(causal), int(workspace_bytes), ctypes.byref(plan)))
     return plan
+
+
+WINDOW_MESSAGE = "fa2: window is None, an int W (= (W, W)) or (left, right), each -1 / None (unbounded) or >= 0, and q_offset is an int >= 0"
+
+
+def parse_window(window, q_offset=0):
+    """The operator's `window` / `q_offset` arguments -> (window_left, window_right, q_offset) of the C-ABI, -1 = unbounded.  Bad values raise
+    ValueError(WINDOW_MESSAGE) — the compiled front end refuses them with the same text."""
+    def one(x):
+        if x is None:
+            return -1
+        if isinstance(x, bool) or not isinstance(x, int) or x < -1 or x >= 2 ** 31:
+            raise ValueError(WINDOW_MESSAGE + ", got window=%r q_offset=%r" % (window, q_offset))
+        return x
+    if window is None:
+        left = right = -1
+    elif isinstance(window, (tuple, list)):
+        if len(window) != 2:
+            raise ValueError(WINDOW_MESSAGE + ", got window=%r q_offset=%r" % (window, q_offset))
+        left, right = one(window[0]), one(window[1])
+    else:
+        left = right = one(window)
+        if left < 0:                                  # (-1 is spelled None or (-1, -1))
+            raise ValueError(WINDOW_MESSAGE + ", got window=%r q_offset=%r" % (window, q_offset))
+    if isinstance(q_offset, bool) or not isinstance(q_offset, int) or q_offset < 0 or q_offset >= 2 ** 31:
+        raise ValueError(WINDOW_MESSAGE + ", got window=%r q_offset=%r" % (window, q_offset))
+    return left, right, q_offset
+
+
+def window_plan(q, k, causal, window_left, window_right, q_offset, scale=None, workspace_bytes=0):
+    """fa2_fwd_window_plan for the call fa2_fwd_window(q, k, ...) would be (k: [B, Hkv, Nkv, D])."""
+    B, H, Nq, D = q.shape
+    dt = FA2_DTYPE_F16 if q.dtype == torch.float16 else FA2_DTYPE_BF16
+    plan = FwdPlan()
+    check(load().fa2_fwd_window_plan(dt, B, H, k.shape[1], Nq, k.shape[2], D, strides3(q.stride(0), q.stride(1), q.stride(2)),
+                                     strides3(k.stride(0), k.stride(1), k.stride(2)), float(D ** -0.5 if scale is None else scale),
+                                     call_flags(causal), int(window_left), int(window_right), int(q_offset), int(workspace_bytes), ctypes.byref(plan)))
+    return plan
+
+
+def window_tile_range(Nq, Nkv, window_left, window_right, q_offset, causal, row0, rows, tile=64, transpose=False):
+    """fa2_window_tile_range (transpose: fa2_window_row_range, row0 / rows then name a block of keys) -> (first_tile, ntiles)."""
+    first, n = ctypes.c_int(), ctypes.c_int()
+    fn = load().fa2_window_row_range if transpose else load().fa2_window_tile_range
+    check(fn(int(Nq), int(Nkv), int(window_left), int(window_right), int(q_offset), int(bool(causal)), int(row0), int(rows), int(tile),
+             ctypes.byref(first), ctypes.byref(n)))
+    return first.value, n.value
 
 
 def strides3(a, b, c):

@@ -292,6 +292,55 @@ int fa2_bwd_gqa(int dtype, const void* q, const void* k, const void* v, const vo
                 float scale, int causal, void* workspace, size_t workspace_bytes, void* hip_stream);
 size_t fa2_bwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int causal);
 
+/*
+ * Sliding-window (local) attention with an offset between query and key positions.
+ * Three integers per call:
+ *   window_left  >= 0, or -1 = unbounded
+ *   window_right >= 0, or -1 = unbounded
+ *   q_offset     >= 0: the position of query row 0 on the key axis (0: top-left alignment, this library's causal convention; Nkv - Nq: the
+ *                bottom-right alignment of other libraries — a chunk of new queries against a longer KV cache, decode with Nq = 1)
+ * Query row i attends key j iff
+ *   (window_left < 0 or j >= i + q_offset - window_left) and (window_right < 0 or j <= i + q_offset + window_right) and 0 <= j < Nkv.
+ * FA2_FLAG_CAUSAL in `flags` (the `causal` argument of the other entry points: FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE) means window_right = 0 under
+ * the same q_offset: causal with q_offset = 0 is the causal call of the other entry points, causal with window_left = W - 1 a window of W keys that
+ * ends at the query's own position.  window_left = window_right = -1, q_offset = 0 is plain attention.
+ * Rows that see no key (possible when Nq + q_offset > Nkv + window_left) return O = 0 and lse = -inf and contribute zero gradients; dK / dV of a
+ * key no row sees are zero, and every element of dq / dk / dv is written (no zero-init needed).
+ * Negative values other than -1, a negative q_offset, or values whose sums with Nq / Nkv leave 32-bit position arithmetic: FA2_ERR_BAD_SHAPE.
+ * Layout as the grouped entry points: q, o [B, H, Nq, D]; k, v [B, Hkv, Nkv, D], Hkv divides H (the forward addresses K / V through the group, no
+ * expansion).  The backward is the multi-head one (k, v, dk, dv have H heads): a caller with grouped K / V expands them and sums dK / dV per group.
+ * Numerical contract 0 (f32 scale of the product, row sums of the f32 P); lse in log2 units.
+ * Kernels.  The workgroup of a block of query rows sweeps only the KV tiles that hold a key one of its rows sees (the dK / dV passes: the Q tiles
+ * of the transposed band), masks the tiles the band's edges cut and runs the unmasked steady-state loop in between: compiler-scheduled kernels at
+ * every head dim (FA2_KERNEL_HIP_WINDOW; option "rows" picks 128- or 256-row forward workgroups as elsewhere).  No KV-split, no hand-scheduled
+ * bodies.  A call whose window masks nothing for its Nq / Nkv — both -1 with q_offset 0, the causal flag alone with q_offset 0, or bounds at least
+ * as long as the sequences — IS the fa2_fwd_gqa / fa2_bwd call of the same arguments (same plan, same kernels, bit-identical results).
+ * The plan query reports this; its strides may be NULL for contiguous tensors, as in the other plan queries.
+ */
+int fa2_fwd_window(int dtype,
+                   const void* q, const void* k, const void* v, void* o, float* lse,
+                   int B, int H, int Hkv, int Nq, int Nkv, int D,
+                   const int64_t q_strides[3], const int64_t k_strides[3],
+                   const int64_t v_strides[3], const int64_t o_strides[3],
+                   const int64_t lse_strides[2],
+                   float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream);
+int fa2_bwd_window(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                   void* dq, void* dk, void* dv, float* delta_ws,
+                   int B, int H, int Nq, int Nkv, int D,
+                   const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                   const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                   const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2],
+                   float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream);
+/* The tile-range arithmetic the windowed kernels and their launchers use (pure host arithmetic, no GPU needed; csrc/fa2_window.h).
+ * fa2_window_tile_range: the KV tiles of `tile` keys that the block of `rows` query rows starting at `row0` has to sweep are
+ * [*first_tile, *first_tile + *ntiles); both ends hold a visible (row, key) pair, ntiles = 0 when the block sees no key.
+ * fa2_window_row_range: its transpose — the tiles of `tile` query rows that see at least one of the `keys` keys starting at `key0`.
+ * `causal` != 0 means window_right = 0.  Returns FA2_OK, FA2_ERR_NULL_POINTER, or FA2_ERR_BAD_SHAPE for bad windows / offsets / lengths / blocks. */
+int fa2_window_tile_range(int Nq, int Nkv, int window_left, int window_right, int q_offset, int causal,
+                          int row0, int rows, int tile, int* first_tile, int* ntiles);
+int fa2_window_row_range(int Nq, int Nkv, int window_left, int window_right, int q_offset, int causal,
+                         int key0, int keys, int tile, int* first_tile, int* ntiles);
+
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
  * that is not a multiple of 8 has to be zero-padded by the caller (to the next multiple of 8). */
@@ -355,6 +404,14 @@ int fa2_fwd_plan(int dtype, int B, int H, int Nq, int Nkv, int D,
 int fa2_fwd_gqa_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D,
                      const int64_t q_strides[3], const int64_t k_strides[3],
                      float scale, int causal, size_t workspace_bytes, fa2_fwd_plan_t* plan);
+
+/* The plan of the windowed forward above.  kernel = FA2_KERNEL_HIP_WINDOW, contract 0, rows as launched — or, for a window that masks nothing, exactly the grouped plan query's answer.
+ * (An enumerator, not a #define: the macro list above is the closed set tests/test_boundary.py pins for the other entry points' plans.) */
+enum { FA2_KERNEL_HIP_WINDOW = 5 };
+int fa2_fwd_window_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D,
+                        const int64_t q_strides[3], const int64_t k_strides[3],
+                        float scale, int flags, int window_left, int window_right, int q_offset,
+                        size_t workspace_bytes, fa2_fwd_plan_t* plan);
 
 /* Coarse form of the above (kept for callers of version 0.8): 1 if launches of this head dim MAY fold the scale into Q (head dims exactly 64
  * and 128, 0 < scale*log2(e) <= 1, option "fold" >= 1: the fp16 launches the hand-scheduled bodies take), 0 if none does, -1: D not supported.
