@@ -48,6 +48,8 @@ UNITS = [
     ("bwd_bias_hip_bf16", "bwd_bias_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("window_hip_f16", "window_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("window_hip_bf16", "window_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("varlen_hip_f16", "varlen_hip.cpp", ["-DFA2_TU_BF16=0"]),
+    ("varlen_hip_bf16", "varlen_hip.cpp", ["-DFA2_TU_BF16=1"]),
 ]
 FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end of the operator (host-only C++, g++)
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")

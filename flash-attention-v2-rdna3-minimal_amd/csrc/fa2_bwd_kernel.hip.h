@@ -62,6 +62,34 @@ struct BwdParams {
     int kv_group = 1;
 };
 
+#if FA2_VARLEN
+// Packed (variable-length) backward (fa2_bwd_varlen): the backward's twin of the forward's varlen_enter (fa2_fwd_kernel.hip.h) — cu_seqlens_q in `bias`,
+// cu_seqlens_k in `ws`.  by_keys: the workgroup owns a block of KEY rows (the dK / dV passes) and leaves when that block lies beyond the sequence's keys;
+// otherwise a block of query rows (the dQ pass).  Every descriptor the passes build (K, V; Q, dO, L, delta) ends at the sequence's own last row.
+__device__ __forceinline__ bool varlen_enter(BwdParams& p, Window& win, int s, int row0, bool by_keys) {
+    const VarlenSeq v = varlen_seq(p, s);
+    if (row0 >= (by_keys ? v.Nkv : v.Nq)) return true;
+    p.Nq = v.Nq; p.Nkv = v.Nkv;
+    win.off = win.off ? v.Nkv - v.Nq : 0;
+    p.q = (const uint16_t*)p.q + (int64_t)v.q_base * p.qs[2];
+    p.o = (const uint16_t*)p.o + (int64_t)v.q_base * p.os[2];
+    p.dout = (const uint16_t*)p.dout + (int64_t)v.q_base * p.dos[2];
+    p.dq = (uint16_t*)p.dq + (int64_t)v.q_base * p.dqs[2];
+    p.lse += v.q_base;
+    p.delta += v.q_base;
+    p.k = (const uint16_t*)p.k + (int64_t)v.k_base * p.ks[2];
+    p.v = (const uint16_t*)p.v + (int64_t)v.k_base * p.vs[2];
+    p.dk = (uint16_t*)p.dk + (int64_t)v.k_base * p.dks[2];
+    p.dv = (uint16_t*)p.dv + (int64_t)v.k_base * p.dvs[2];
+    p.q_bytes = varlen_bytes(v.Nq, p.qs[2], p.D);
+    p.do_bytes = varlen_bytes(v.Nq, p.dos[2], p.D);
+    p.l_bytes = v.Nq > 0 ? (uint32_t)v.Nq * 4u : 0u;
+    p.k_bytes = varlen_bytes(v.Nkv, p.ks[2], p.D);
+    p.v_bytes = varlen_bytes(v.Nkv, p.vs[2], p.D);
+    return false;
+}
+#endif
+
 // f32 partial accumulator tile of a part -> workspace.  Layout of a tile: float (((dt*4 + g) * 256 + row) * 8 + 4*hi + e) for
 // d = 32dt + 8g + 4hi + e (the forward's partial O tiles: a wave's store instruction writes 1 KiB of consecutive bytes).
 template <int DT>
@@ -274,12 +302,19 @@ __device__ __forceinline__ void store_acc_t(const f32x16 (&acc)[DT], uint16_t* r
 // images and staging (columns >= D are never fetched) but runs only KSN = ceil(D / 16) k-steps of the products contracted over the head dim
 // and DTN = ceil(D / 32) column blocks of the accumulators.  Defaults = the full kernel.
 template <int HD, bool BF16, bool CAUSAL, int NW = 8, int HDV = HD, int BIAS = 0, int KSN = HD / 16, int DTN = HDV / 32>
-__global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_dq_kernel(const BwdParams p) {
+__global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_dq_kernel(const BwdParams FA2_KP) {
+#if FA2_VARLEN
+    BwdParams p = pk;         // (adjusted to the workgroup's sequence below: varlen_enter)
+#endif
 #if FA2_WIN
     // FA2_WIN (fa2_bwd_window; window_hip.cpp, CAUSAL = false, BIAS = 0): the sweep covers the KV tiles of the workgroup's window only (fa2_window.h), a
     // wave computes the tiles of its own rows' range, tiles cut by an edge of the band are masked on both sides.
     static_assert(!CAUSAL && !BIAS, "the windowed passes carry the causal edge in the window and take no bias");
+#if FA2_VARLEN
+    Window win = get_window(p);
+#else
     const Window win = get_window(p);      // (the window travels in the bias stride fields: fa2_fwd_kernel.hip.h)
+#endif
 #endif
     using L_ = BwdLane<HD, NW>;
     using LV_ = BwdLane<HDV, NW>;             // geometry of the transposed-read image (the slab)
@@ -321,6 +356,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
     else { bh = bid / p.nblk; qblk = bid % p.nblk; }
     const int b = bh / p.H, h = bh % p.H;
     const int q0 = qblk * kRows, qw0 = q0 + 32 * wave, qrow = qw0 + l31;
+#if FA2_VARLEN
+    if (varlen_enter(p, win, b, q0, false)) return;      // b is the sequence (the batch strides are 0); from here on p describes that sequence alone
+#endif
     const int qr = qrow < p.Nq ? qrow : p.Nq - 1;
 
     L_ ln;
@@ -614,12 +652,19 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
 // HDV < HD (HD = 512): the workgroup produces the HDV-column slab blockIdx.y of dK / dV; S (and dP) are contracted over the whole head
 // dim, only the transposed-read image and the accumulator are slab-sized (see bwd_dq_kernel).
 template <int HD, bool BF16, bool CAUSAL, bool WANT_DK, int NW = 8, bool BOTH = false, int HDV = HD, int BIAS = 0, int KSN = HD / 16, int DTN = HDV / 32>
-__global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParams p) {
+__global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParams FA2_KP) {
+#if FA2_VARLEN
+    BwdParams p = pk;
+#endif
 #if FA2_WIN
     // FA2_WIN (fa2_bwd_window; kv_group = 1): the workgroup sweeps the Q tiles of the transposed band only (fa2_window.h: window_row_range), masked on
     // both sides.
     static_assert(!CAUSAL && !BIAS, "the windowed passes carry the causal edge in the window and take no bias");
+#if FA2_VARLEN
+    Window win = get_window(p);
+#else
     const Window win = get_window(p);
+#endif
 #endif
     static_assert(!BOTH || WANT_DK, "the fused pass is the dK pass plus a dV accumulator");
     static_assert(!BOTH || HDV == HD, "slabs exist for the separate passes only");
@@ -667,6 +712,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
     else { bh = bid / p.nblk; kblk = bid % p.nblk; }
     const int b = bh / Hkv, h = bh % Hkv;     // K / V head (G = 1: also the Q head — the masked passes are never grouped)
     const int kv0 = kblk * kRows, kvw0 = kv0 + 32 * wave, kvrow = kvw0 + l31;   // this lane's KV row
+#if FA2_VARLEN
+    if (varlen_enter(p, win, b, kv0, true)) return;      // (a live block whose transposed range is empty sweeps nothing and stores zeros)
+#endif
     const int kr = kvrow < p.Nkv ? kvrow : p.Nkv - 1;
 
     L_ ln;
@@ -1033,11 +1081,18 @@ __device__ __forceinline__ void pair_mid_barrier() {
 // Each tile has two phases separated by a barrier: {S, exp | dP} and {dV | dS, dK}; the transcendental / VALU stretch of one wave
 // of a pair runs beside the MFMAs of the other.  Stage: Q row | dO row | Q tr | dO tr | L | D, two stages (129 KiB) + 16 KiB of slots.
 template <int HD, bool BF16, bool CAUSAL, int KSN = HD / 16, int DTN = HD / 32>
-__global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p) {
+__global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA2_KP) {
+#if FA2_VARLEN
+    BwdParams p = pk;
+#endif
 #if FA2_WIN
     // FA2_WIN (fa2_bwd_window; kv_group = 1): the Q tiles of the transposed band only, masked on both sides (see bwd_dkv_kernel).
     static_assert(!CAUSAL, "the windowed passes carry the causal edge in the window");
+#if FA2_VARLEN
+    Window win = get_window(p);
+#else
     const Window win = get_window(p);
+#endif
 #endif
     constexpr int NW = 8;
     using L_ = BwdLane<HD, NW>;
@@ -1064,6 +1119,9 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams p)
     else { bh = bid / p.nblk; kblk = bid % p.nblk; }
     const int b = bh / Hkv, h = bh % Hkv;
     const int kv0 = kblk * kRows, kvw0 = kv0 + 32 * grp, kvrow = kvw0 + l31;
+#if FA2_VARLEN
+    if (varlen_enter(p, win, b, kv0, true)) return;
+#endif
     const int kr = kvrow < p.Nkv ? kvrow : p.Nkv - 1;
 
     L_ ln;

@@ -43,6 +43,20 @@
 #ifndef FA2_WIN
 #define FA2_WIN 0
 #endif
+// FA2_VARLEN = 1 (varlen_hip.cpp only, on top of FA2_WIN = 1): the packed, variable-length forms — the windowed kernels with the lengths, the base rows and
+// the band's offset taken per sequence from cu_seqlens instead of per launch (varlen_enter below).  The kernel's parameter block is then a copy the
+// workgroup adjusts (FA2_KP names the kernarg itself); everywhere else FA2_KP is the plain `p` it always was.
+#ifndef FA2_VARLEN
+#define FA2_VARLEN 0
+#endif
+#if FA2_VARLEN && !FA2_WIN
+#error "FA2_VARLEN builds on the FA2_WIN blocks"
+#endif
+#if FA2_VARLEN
+#define FA2_KP pk
+#else
+#define FA2_KP p
+#endif
 
 // ---- tuning knobs (A/B-tested on MI355X with tools/kbench.py; numbers at B2 H16 N4096 D128 fp16) ----
 #ifndef FA2_DEFER_THR        // skip the O rescale while the row max grew by <= this (log2 units); <0: always rescale.
@@ -139,6 +153,41 @@ __host__ __device__ inline Window get_window(const P& p) {
     w.left = (int)p.bs[0]; w.right = (int)p.bs[1]; w.off = (int)p.bs[2];
     return w;
 }
+
+#if FA2_VARLEN
+// Packed (variable-length) attention (fa2_fwd_varlen / fa2_bwd_varlen; include/fa2_gfx950.h has the contract).  A varlen call has neither bias nor split
+// workspace: cu_seqlens_q travels in `bias`, cu_seqlens_k in `ws`, and the bottom-right flag where the window's offset would be.  The host passes batch
+// strides of 0, Nq / Nkv = the stated maxima (they size the grid) and B = the number of sequences; the workgroup of sequence s then turns its copy of the
+// parameter block into the windowed call on that sequence alone: base pointers moved to the sequence's first row, Nq / Nkv and the band's offset its own,
+// and every buffer descriptor ending at the last row OF THE SEQUENCE, so that rows past it read zeros and a neighbour's rows are never fetched.
+struct VarlenSeq { int q_base, k_base, Nq, Nkv; };
+template <typename P>
+__device__ __forceinline__ VarlenSeq varlen_seq(const P& p, int s) {       // (s is workgroup-uniform: four scalar loads)
+    const int* cq = (const int*)p.bias;
+    const int* ck = (const int*)p.ws;
+    VarlenSeq v;
+    v.q_base = cq[s]; v.k_base = ck[s];
+    v.Nq = cq[s + 1] - v.q_base; v.Nkv = ck[s + 1] - v.k_base;
+    return v;
+}
+// addressable bytes of n rows of `pitch` elements, D of them used (0 rows: nothing is addressable)
+__device__ __forceinline__ uint32_t varlen_bytes(int n, int64_t pitch, int D) { return n > 0 ? (uint32_t)(((int64_t)(n - 1) * pitch + D) * 2) : 0u; }
+// true: the block of rows from row0 on lies beyond the sequence's queries — the workgroup has nothing to do (uniform; before any barrier or LDS-DMA)
+__device__ __forceinline__ bool varlen_enter(FwdParams& p, Window& win, int s, int row0) {
+    const VarlenSeq v = varlen_seq(p, s);
+    if (row0 >= v.Nq) return true;
+    p.Nq = v.Nq; p.Nkv = v.Nkv;
+    win.off = win.off ? v.Nkv - v.Nq : 0;                                  // FA2_FLAG_BOTTOM_RIGHT : the library's top-left convention
+    p.q = (const uint16_t*)p.q + (int64_t)v.q_base * p.qs[2];
+    p.k = (const uint16_t*)p.k + (int64_t)v.k_base * p.ks[2];
+    p.v = (const uint16_t*)p.v + (int64_t)v.k_base * p.vs[2];
+    p.o = (uint16_t*)p.o + (int64_t)v.q_base * p.os[2];
+    p.lse += v.q_base;
+    p.k_bytes = varlen_bytes(v.Nkv, p.ks[2], p.D);
+    p.v_bytes = varlen_bytes(v.Nkv, p.vs[2], p.D);
+    return false;
+}
+#endif
 
 constexpr int kSplitRows = 256;          // rows of a split item (the 8-wave workgroup shape)
 constexpr int kMaxSplit = 8;
@@ -296,7 +345,10 @@ constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && 
 // computes only the tiles of its own 32 rows' range [tf_w, ntiles_w), tiles cut by the band's left or right edge are masked per lane (lim_lo, lim_hi)
 // and the tiles in between run the unmasked steady-state loop.  A row that sees no key ends with O = 0, lse = -inf (the BIAS kernels' convention).
 template <int HD, int HDV, bool BF16, bool CAUSAL, int NW, int QB, int BIAS = 0, int KSQ = HD / 16, int DTN = HDV / 32, bool RTD = false>
-__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams p) {
+__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP) {
+#if FA2_VARLEN
+    FwdParams p = pk;         // (adjusted to the workgroup's sequence below: varlen_enter)
+#endif
     constexpr int kRowsPerBlock = NW * QB * 32;   // Q rows per workgroup (p.nqblk = ceil(Nq / kRowsPerBlock))
     using G_ = Geo<HD, NW>;    // K tile image
     using GV_ = Geo<HDV, NW>;  // V tile image
@@ -322,7 +374,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     int part = -1, sidx = 0;
 #if FA2_WIN
     static_assert(!CAUSAL && !BIAS && QB == 1, "the windowed kernels carry the causal edge in the window, no bias, one q block per wave");
+#if FA2_VARLEN
+    Window win = get_window(p);
+#else
     const Window win = get_window(p);
+#endif
 #endif
 #if FA2_WIN
     if constexpr (false) {
@@ -340,6 +396,9 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     block_to_head_qblock<CAUSAL>(p, bid, bh, qblk);
     const int b = bh / p.H, h = bh % p.H;
     const int q0 = qblk * kRowsPerBlock;
+#if FA2_VARLEN
+    if (varlen_enter(p, win, b, q0)) return;      // b is the sequence (the batch strides are 0); from here on p describes that sequence alone
+#endif
     // this workgroup's KV range [kv_first, kv_first + nkv): everything, or a part's whole tiles
     int kv_first = 0, nkv = p.Nkv;
     if (part >= 0) {

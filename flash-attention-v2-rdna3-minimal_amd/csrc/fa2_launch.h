@@ -181,6 +181,12 @@ FA2_HIDDEN int launch_fwd_window_f16(int HD, const FwdParams& p, int rows, hipSt
 FA2_HIDDEN int launch_fwd_window_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_window_f16(int HD, const BwdParams& p, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_window_bf16(int HD, const BwdParams& p, hipStream_t stream);
+// packed, variable-length attention (varlen_hip.cpp): the same launchers over the VARLEN forms; p.Nq / p.Nkv = the stated maximum lengths, p.B = the number
+// of sequences, batch strides 0, cu_seqlens_q / cu_seqlens_k in p.bias / p.ws, the window's offset field = the bottom-right flag
+FA2_HIDDEN int launch_fwd_varlen_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_fwd_varlen_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_varlen_f16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_varlen_bf16(int HD, const BwdParams& p, hipStream_t stream);
 // hand-scheduled backward, head dim exactly 128 (bwd_asm.cpp); same `parts`
 // neg_delta: the dQ pass writes -delta (the hand-scheduled dK/dV pass reads it as such; the HIP dK/dV passes read +delta)
 // kfold: the dK / dV body whose P side folds scale * log2(e) into its K fragments (option "fold"; host.cpp: bwd_folds)

@@ -1,12 +1,18 @@
 // fa2_window.h — the range arithmetic of sliding-window (local) attention, shared by the kernels, the launchers and the C-ABI queries
 // fa2_window_tile_range / fa2_window_row_range (include/fa2_gfx950.h), so that it can be tested on the CPU against brute force.
 //
-// Positions.  Query row i sits at key position i + off (off = q_offset >= 0); it attends key j iff
+// Positions.  Query row i sits at key position i + off (off = q_offset >= 0 on the windowed entry points); it attends key j iff
 //     (left  < 0 or j >= i + off - left) and (right < 0 or j <= i + off + right) and 0 <= j < Nkv
 // (-1 = unbounded).  The causal flag of a windowed call means right = 0 (window_normalize_right): the kernels only ever see (left, right, off).
 // Both bounds of a row grow by one per row, so the live rows of a block (rows that see a key at all) are contiguous, and so is the union of
 // their key intervals: a block's visible keys are [lo of its first live row, hi of its last live row].  The same holds for the transpose.
-// The host validates Nq + off + max(left, right) and Nkv + off + max(left, right) against 32-bit overflow (window_args_ok): plain int arithmetic here.
+// The host validates Nq + |off| + max(left, right) and Nkv + |off| + max(left, right) against 32-bit overflow (window_args_ok): plain int arithmetic here.
+//
+// Negative offsets (packed attention, fa2_fwd_varlen: off = Nkv_s - Nq_s of a sequence with fewer keys than queries, bottom-right aligned).  The span
+// arithmetic below holds for them unchanged; what changes is that the live rows of a block are no longer a prefix of it: rows with i + off + right < 0
+// are dead at the TOP (their whole interval lies left of key 0).  They are still contiguous, and the first live row's interval starts at key 0, so
+// [max(0, lo of the block's first row), hi of its last live row] is still tight.  The windowed entry points keep refusing off < 0 (window_args_ok's
+// default); lengths of 0 (an empty sequence on either side) give empty spans.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -24,12 +30,13 @@ struct Window {
 // `causal` on a windowed call: nothing to the right of the query's own position
 FA2_WIN_HD inline int window_normalize_right(int right, int causal) { return causal ? 0 : right; }
 
-// -1 (unbounded) or >= 0, off >= 0, and every position sum used below stays inside int
-FA2_WIN_HD inline bool window_args_ok(int Nq, int Nkv, int left, int right, int off) {
-    if (left < -1 || right < -1 || off < 0) return false;
+// -1 (unbounded) or >= 0, off >= 0 (negative_off: any sign — the packed entry points), and every position sum used below stays inside int
+FA2_WIN_HD inline bool window_args_ok(int Nq, int Nkv, int left, int right, int off, bool negative_off = false) {
+    if (left < -1 || right < -1 || (off < 0 && !negative_off)) return false;
     const long long m = (left > right ? left : right) > 0 ? (left > right ? left : right) : 0;
     const long long n = Nq > Nkv ? Nq : Nkv;
-    return n + off + m + 1024 <= 0x7fffffffLL;
+    const long long a = off < 0 ? -(long long)off : (long long)off;
+    return n + a + m + 1024 <= 0x7fffffffLL;
 }
 
 // does the window mask nothing at all for these lengths?  (then the call is a plain one)

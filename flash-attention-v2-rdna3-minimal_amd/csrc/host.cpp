@@ -404,6 +404,10 @@ WindowCall reduce_window(int Nq, int Nkv, int left, int right, int off, bool cau
     return c;
 }
 
+// A packed (variable-length) call on its way through fwd_impl / bwd_impl: the cu_seqlens arrays (device memory) next to the window, whose offset field
+// carries the bottom-right flag.  Nq / Nkv of such a call are the stated maximum lengths, B the number of sequences, the batch strides 0.
+struct VarlenCall { const int* cu_q; const int* cu_k; };
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool strides_ok(const int64_t* s) { return s[0] % 8 == 0 && s[1] % 8 == 0 && s[2] % 8 == 0 && s[2] > 0; }
 
@@ -492,7 +496,7 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
                     const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
                     float scale, int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
                     void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, fa2_fwd_plan_t* plan_out = nullptr, int Hkv = 0,
-                    const fa2::Window* win = nullptr) {
+                    const fa2::Window* win = nullptr, const VarlenCall* vl = nullptr) {
     // `causal` carries the call's flags: bit 0 = causal mask, bit 1 = FA2_FLAG_EXACT_SCALE (this call scales the f32 product whatever option "fold" says)
     // Until round 5 any non-zero value meant "causal"; a caller that still passes another truthy int would silently get a non-causal forward: refuse it
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
@@ -580,14 +584,16 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
     if (win) {          // fa2_fwd_window with a window that masks something (reduce_window kind 2): the WIN kernels, contract 0
         if ((int64_t)B * H * ((Nq + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
         fa2::set_window(p, *win);
-        const int rows = HD > 256 ? 128 : pick_rows(p);
+        if (vl) { p.bias = vl->cu_q; p.ws = (float*)const_cast<int*>(vl->cu_k); }      // (fa2_fwd_kernel.hip.h: varlen_seq)
+        const int rows = HD > 256 ? 128 : pick_rows(p);      // (varlen: the grid of the stated maximum lengths)
         if (plan_out) {
             std::memset(plan_out, 0, sizeof(*plan_out));
-            plan_out->kernel = FA2_KERNEL_HIP_WINDOW;
+            plan_out->kernel = vl ? FA2_KERNEL_HIP_VARLEN : FA2_KERNEL_HIP_WINDOW;
             plan_out->rows = rows;
             plan_out->heads_main = B * H;
         }
         if (plan_only) return FA2_OK;
+        if (vl) return bf16 ? fa2::launch_fwd_varlen_bf16(HD, p, rows, stream) : fa2::launch_fwd_varlen_f16(HD, p, rows, stream);
         return bf16 ? fa2::launch_fwd_window_bf16(HD, p, rows, stream) : fa2::launch_fwd_window_f16(HD, p, rows, stream);
     }
     if (bias_kind != FA2_BIAS_NONE) {
@@ -699,7 +705,8 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
             const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
             const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
             int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
-            void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, int Hkv = 0, const fa2::Window* win = nullptr) {
+            void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, int Hkv = 0, const fa2::Window* win = nullptr,
+            const VarlenCall* vl = nullptr) {
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;      // (as in fwd_impl: no value but the documented flag bits)
     causal &= 1;          // (bit 1, FA2_FLAG_EXACT_SCALE, is what the backward does anyway unless option "kfold" is set)
     if (ws_need) *ws_need = 0;
@@ -775,6 +782,10 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
     const bool bf16 = dtype == FA2_DTYPE_BF16;
     if (win) {          // fa2_bwd_window with a window that masks something: the WIN passes
         fa2::set_window(p, *win);
+        if (vl) {
+            p.bias = vl->cu_q; p.ws = (float*)const_cast<int*>(vl->cu_k);
+            return bf16 ? fa2::launch_bwd_varlen_bf16(HD, p, stream) : fa2::launch_bwd_varlen_f16(HD, p, stream);
+        }
         return bf16 ? fa2::launch_bwd_window_bf16(HD, p, stream) : fa2::launch_bwd_window_f16(HD, p, stream);
     }
     if (bias_kind != FA2_BIAS_NONE)
@@ -957,6 +968,109 @@ int fa2_window_row_range(int Nq, int Nkv, int window_left, int window_right, int
         return FA2_ERR_BAD_SHAPE;
     fa2::window_row_range(Nq, Nkv, window_left, fa2::window_normalize_right(window_right, causal), q_offset, key0, keys, tile, first_tile, ntiles);
     return FA2_OK;
+}
+
+// ---- packed, variable-length attention: include/fa2_gfx950.h has the contract, varlen_hip.cpp the kernels
+namespace {
+
+// What the host can check of a packed call (the contents of cu_seqlens live on the device).  On success: the window as the kernels take it — the causal flag
+// folded in, the offset field carrying the bottom-right flag.
+int varlen_check(int B, int H, int Hkv, int max_q, int max_k, int D, int flags, int left, int right, fa2::Window* w) {
+    if (B < 1 || H < 1 || Hkv < 1 || max_q < 1 || max_k < 1 || D < 1 || Hkv > H || H % Hkv != 0) return FA2_ERR_BAD_SHAPE;
+    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE | FA2_FLAG_BOTTOM_RIGHT)) return FA2_ERR_BAD_SHAPE;
+    const bool br = (flags & FA2_FLAG_BOTTOM_RIGHT) != 0;
+    const int n = max_q > max_k ? max_q : max_k;          // a sequence's offset Nkv_s - Nq_s lies in [-max_q, max_k]
+    if (!fa2::window_args_ok(max_q, max_k, left, right, br ? -n : 0, true)) return FA2_ERR_BAD_SHAPE;
+    w->left = left;
+    w->right = fa2::window_normalize_right(right, (flags & FA2_FLAG_CAUSAL) != 0);
+    w->off = br ? 1 : 0;
+    return FA2_OK;
+}
+
+// [total, heads, D] strides {head, row} as the kernels' {batch, head, row} with a batch stride of 0: the sequence's first row is added in-kernel
+struct PackedStrides {
+    int64_t s[3];
+    explicit PackedStrides(const int64_t* two) { s[0] = 0; s[1] = two[0]; s[2] = two[1]; }
+};
+
+}  // namespace
+
+int fa2_fwd_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
+                   int max_seqlen_q, int max_seqlen_k, int D, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                   const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                   int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream) {
+    fa2::Window w;
+    if (int rc = varlen_check(B, H, Hkv, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
+    if (!q_strides || !k_strides || !v_strides || !o_strides) return FA2_ERR_NULL_POINTER;
+    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides);
+    const int64_t ls[2] = {0, lse_stride};
+    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
+    // (the tensors may still be null: a plan-only pass validates everything else first, so that a bad argument is reported as what it is)
+    char* d = g_plan_dummy;
+    fa2_fwd_plan_t plan;
+    if (int rc = fwd_impl(dtype, d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE,
+                          nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, nullptr, &plan, Hkv, &w, &vl))
+        return rc;
+    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
+    return fwd_impl(dtype, q, k, v, o, lse, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE,
+                    nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, &w, &vl);
+}
+
+int fa2_fwd_varlen_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D, const int64_t q_strides[2], const int64_t k_strides[2],
+                        float scale, int flags, int window_left, int window_right, fa2_fwd_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    fa2::Window w;
+    if (int rc = varlen_check(B, H, Hkv, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
+    const int64_t cq[2] = {D, (int64_t)H * D}, ck[2] = {D, (int64_t)Hkv * D};          // a contiguous [total, heads, D]
+    const PackedStrides qs(q_strides ? q_strides : cq), ks(k_strides ? k_strides : ck);
+    const int64_t ls[2] = {0, 0};
+    const VarlenCall vl = {nullptr, nullptr};
+    char* d = g_plan_dummy;
+    return fwd_impl(dtype, d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, ks.s, qs.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE,
+                    nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, nullptr, plan, Hkv, &w, &vl);
+}
+
+int fa2_bwd_varlen(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                   void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                   const int* cu_seqlens_q, const int* cu_seqlens_k,
+                   const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                   const int64_t do_strides[2], const int64_t dq_strides[2], const int64_t dk_strides[2], const int64_t dv_strides[2],
+                   int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream) {
+    fa2::Window w;
+    if (int rc = varlen_check(B, H, H, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
+    if (!q_strides || !k_strides || !v_strides || !o_strides || !do_strides || !dq_strides || !dk_strides || !dv_strides) return FA2_ERR_NULL_POINTER;
+    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides), gs(do_strides), dqs(dq_strides), dks(dk_strides), dvs(dv_strides);
+    const int64_t ls[2] = {0, lse_stride};
+    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
+    // (as in fa2_fwd_varlen: everything but the tensors first — the workspace query is the validation-only pass of bwd_impl)
+    char* d = g_plan_dummy;
+    size_t need = 0;
+    if (int rc = bwd_impl(dtype, d, d, d, d, d, (const float*)d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s,
+                          dks.s, dvs.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need, 0, &w, &vl))
+        return rc;
+    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
+    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s, dks.s, dvs.s,
+                    ls, scale, flags & FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, 0, &w, &vl);
+}
+
+static int varlen_range(bool transpose, int Nq_s, int Nkv_s, int left, int right, int flags, int row0, int rows, int tile, int* first_tile, int* ntiles) {
+    if (!first_tile || !ntiles) return FA2_ERR_NULL_POINTER;
+    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE | FA2_FLAG_BOTTOM_RIGHT)) return FA2_ERR_BAD_SHAPE;
+    if (Nq_s < 0 || Nkv_s < 0 || row0 < 0 || rows < 1 || tile < 1 || rows > (1 << 24) || row0 > 0x7fffffff - (1 << 24)) return FA2_ERR_BAD_SHAPE;
+    const int off = (flags & FA2_FLAG_BOTTOM_RIGHT) ? Nkv_s - Nq_s : 0;             // (|off| <= max(Nq_s, Nkv_s): no overflow)
+    if (!fa2::window_args_ok(Nq_s, Nkv_s, left, right, off, true)) return FA2_ERR_BAD_SHAPE;
+    right = fa2::window_normalize_right(right, (flags & FA2_FLAG_CAUSAL) != 0);
+    if (transpose) fa2::window_row_range(Nq_s, Nkv_s, left, right, off, row0, rows, tile, first_tile, ntiles);
+    else fa2::window_tile_range(Nq_s, Nkv_s, left, right, off, row0, rows, tile, first_tile, ntiles);
+    return FA2_OK;
+}
+
+int fa2_varlen_tile_range(int Nq_s, int Nkv_s, int window_left, int window_right, int flags, int row0, int rows, int tile, int* first_tile, int* ntiles) {
+    return varlen_range(false, Nq_s, Nkv_s, window_left, window_right, flags, row0, rows, tile, first_tile, ntiles);
+}
+
+int fa2_varlen_row_range(int Nq_s, int Nkv_s, int window_left, int window_right, int flags, int key0, int keys, int tile, int* first_tile, int* ntiles) {
+    return varlen_range(true, Nq_s, Nkv_s, window_left, window_right, flags, key0, keys, tile, first_tile, ntiles);
 }
 
 #define FA2_BWD_ARGS                                                                                                    \

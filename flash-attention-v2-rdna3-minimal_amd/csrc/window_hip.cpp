@@ -5,11 +5,16 @@
 // No trimmed instantiations, no KV-split, no hand-scheduled bodies: every head dim runs the full kernel of its padded head dim.
 // The kernel headers compile their sliding-window blocks under FA2_WIN (preprocessor blocks: every other translation unit sees the text it always
 // saw, so its code cannot change), and the kernels get names of their own here so that they never collide with the plain instantiations.
+// varlen_hip.cpp includes this file under FA2_VARLEN with kernel and launcher names of its own: the packed forms are launched exactly like these (the
+// host passes the stated maximum lengths as Nq / Nkv, which size the grids).
+#ifndef FA2_VARLEN
 #define FA2_WIN 1
 #define fwd_kernel fwd_window_kernel
 #define bwd_dq_kernel bwd_window_dq_kernel
 #define bwd_dkv_kernel bwd_window_dkv_kernel
 #define bwd_dkv_pair_kernel bwd_window_dkv_pair_kernel
+#define FA2_WIN_LAUNCH(pass, dt) launch_##pass##_window_##dt
+#endif
 #include "fa2_launch.h"
 
 #include "fa2_gfx950.h"
@@ -133,9 +138,9 @@ int launch_bwd_hd(fa2::BwdParams p, hipStream_t stream) {
 namespace fa2 {
 
 #if FA2_TU_BF16
-int launch_fwd_window_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream) {
+int FA2_WIN_LAUNCH(fwd, bf16)(int HD, const FwdParams& p, int rows, hipStream_t stream) {
 #else
-int launch_fwd_window_f16(int HD, const FwdParams& p, int rows, hipStream_t stream) {
+int FA2_WIN_LAUNCH(fwd, f16)(int HD, const FwdParams& p, int rows, hipStream_t stream) {
 #endif
     switch (HD) {
         case 64: return launch_fwd_hd<64>(p, rows, stream);
@@ -147,9 +152,9 @@ int launch_fwd_window_f16(int HD, const FwdParams& p, int rows, hipStream_t stre
 }
 
 #if FA2_TU_BF16
-int launch_bwd_window_bf16(int HD, const BwdParams& p, hipStream_t stream) {
+int FA2_WIN_LAUNCH(bwd, bf16)(int HD, const BwdParams& p, hipStream_t stream) {
 #else
-int launch_bwd_window_f16(int HD, const BwdParams& p, hipStream_t stream) {
+int FA2_WIN_LAUNCH(bwd, f16)(int HD, const BwdParams& p, hipStream_t stream) {
 #endif
     switch (HD) {
         case 64: return launch_bwd_hd<64>(p, stream);

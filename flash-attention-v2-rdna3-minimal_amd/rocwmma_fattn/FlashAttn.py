@@ -70,6 +70,80 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, window=window)
 
     @staticmethod
+    def forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, flags, scale, window):
+        """Packed, variable-length forward (extension: C-ABI fa2_fwd_varlen).  q [total_q, H, D], k / v [total_k, Hkv, D] (grouped K / V are addressed
+        through the group), cu_seqlens_* int32 [B + 1] on q's device, the maxima host ints; flags = FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE |
+        FA2_FLAG_BOTTOM_RIGHT; window = (window_left, window_right), -1 = unbounded.  Returns [O_fwd, q, k, v, O, L] like forward(): the tensors the
+        backward wants (D padded to a multiple of 8 if need be; O_fwd a view of O), L = f32 [H, total_q] in log2 units."""
+        lib = _fa2_lib.load()
+        h, h_kv, d = _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k)
+        if q.dtype == torch.float16:
+            dtype_code = _fa2_lib.FA2_DTYPE_F16
+            if k.dtype != q.dtype or v.dtype != q.dtype:
+                raise RuntimeError("fa2: q, k, v must share one dtype")
+        else:
+            dtype_code = _fa2_lib.FA2_DTYPE_BF16
+            if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+                q, k, v = q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16)
+        d_pad = -d % 8
+        if d_pad:
+            q, k, v = (torch.nn.functional.pad(t, (0, d_pad)) for t in (q, k, v))
+        q, k, v = (_packed_ready(t) for t in (q, k, v))
+        total_q = q.shape[0]
+        O = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        L = torch.empty((h, total_q), dtype=torch.float32, device=q.device)
+        if total_q and k.shape[0] == 0:            # no keys at all: every row is dead (and the library wants non-null pointers)
+            O.zero_()
+            L.fill_(float("-inf"))
+        elif total_q:
+            dev = q.device.index
+            with torch.cuda.device(dev):
+                rc = lib.fa2_fwd_varlen(dtype_code, q.data_ptr(), k.data_ptr(), v.data_ptr(), O.data_ptr(), L.data_ptr(), cu_seqlens_q.numel() - 1, h, h_kv,
+                                        max(int(max_seqlen_q), 1), max(int(max_seqlen_k), 1), d + d_pad, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
+                                        _s2(q), _s2(k), _s2(v), _s2(O), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]),
+                                        _raw_stream(dev))
+            if rc:
+                _fa2_lib.check(rc)
+        return [O[..., :d] if d_pad else O, q, k, v, O, L]
+
+    @staticmethod
+    def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window):
+        """backward() of forward_varlen (C-ABI fa2_bwd_varlen; grouped K / V: expanded, dK / dV summed per group in f32).  Returns [dQ, dK, dV]."""
+        lib = _fa2_lib.load()
+        if not (Q.is_cuda and dO.is_cuda):
+            raise RuntimeError("fa2: tensors must be on a ROCm device (no CPU path in this operator)")
+        h, h_kv, dk = Q.size(1), K.size(1), Q.size(2)
+        _check_groups(h, h_kv)
+        if h_kv != h:
+            def mha(Q4, K4, V4, O4, dO4, L_, *rest):
+                return [t.unsqueeze(0) for t in _FlashAttnWmma.backward_varlen(Q4[0], K4[0], V4[0], O4[0], dO4[0], L_, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+                                                                               max_seqlen_k, act_d, flags, scale, window)]
+            return [t[0] for t in _grouped_backward(mha, Q.unsqueeze(0), K.unsqueeze(0), V.unsqueeze(0), O.unsqueeze(0), dO.unsqueeze(0), L, 0, 0, act_d,
+                                                    128, 128, False, scale, True)]
+        dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+        if dO.dtype != Q.dtype:
+            dO = dO.to(Q.dtype)
+        if dO.size(2) != dk:
+            dO = torch.nn.functional.pad(dO, (0, dk - dO.size(2)))
+        dO = _packed_ready(dO)
+        dQ = torch.empty(Q.shape, dtype=Q.dtype, device=Q.device)       # every element is written by its owner
+        dK = torch.empty(K.shape, dtype=K.dtype, device=K.device)
+        dV = torch.empty(V.shape, dtype=V.dtype, device=V.device)
+        if Q.shape[0] == 0 or K.shape[0] == 0:         # no queries or no keys at all: no gradient anywhere
+            return [dQ.zero_()[..., :act_d], dK.zero_()[..., :act_d], dV.zero_()[..., :act_d]]
+        L = L.contiguous()
+        delta = torch.empty_like(L)
+        dev = Q.device.index
+        with torch.cuda.device(dev):
+            rc = lib.fa2_bwd_varlen(dtype_code, Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(), dQ.data_ptr(),
+                                    dK.data_ptr(), dV.data_ptr(), delta.data_ptr(), cu_seqlens_q.numel() - 1, h, max(int(max_seqlen_q), 1),
+                                    max(int(max_seqlen_k), 1), dk, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), _s2(Q), _s2(K), _s2(V), _s2(O), _s2(dO),
+                                    _s2(dQ), _s2(dK), _s2(dV), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]), _raw_stream(dev))
+        if rc:
+            _fa2_lib.check(rc)
+        return [dQ[..., :act_d], dK[..., :act_d], dV[..., :act_d]]
+
+    @staticmethod
     def forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=None, window=None):
         """Returns [O_fwd, q_pad, k_pad, v_pad, O, L] like forward_fp16/forward_bf16 (kernel_fp16.cu:744-876).
         O and L keep the reference's shapes — rows padded to a multiple of Br with a zero tail, O_fwd a view into
@@ -348,6 +422,43 @@ def _grouped_backward(mha_backward, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br
     return [dQ, dKe.unflatten(h_ax, (K.size(h_ax), g)).sum(h_ax + 1), dVe.unflatten(h_ax, (V.size(h_ax), g)).sum(h_ax + 1)]
 
 
+def _s2(t):
+    """{head, row} element strides of a packed [total, heads, D] tensor, as the varlen entry points take them."""
+    return _fa2_lib.strides2(t.stride(1), t.stride(0))
+
+
+def _packed_ready(t):
+    """A packed [total, heads, D] tensor the kernels can address: D contiguous, strides multiples of 8 elements, 16-byte aligned."""
+    s0, s1, s2 = t.stride()
+    return t if s2 == 1 and not ((s0 | s1) & 7) and not (t.data_ptr() & 15) else t.contiguous()
+
+
+def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k):
+    """The argument checks of the packed calls, before any device work -> (H, Hkv, D)."""
+    if not all(torch.is_tensor(t) for t in (q, k, v)) or q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise ValueError("fa2: q, k, v of a packed (varlen) call must be 3-D: [total_q, H, D] and [total_k, Hkv, D]")
+    if not torch.is_tensor(cu_seqlens_q) or not torch.is_tensor(cu_seqlens_k) or cu_seqlens_q.dim() != 1 or cu_seqlens_k.dim() != 1:
+        raise ValueError("fa2: cu_seqlens_q / cu_seqlens_k must be 1-D int32 tensors of B + 1 row offsets")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel() or cu_seqlens_q.numel() < 2:
+        raise ValueError("fa2: cu_seqlens_q and cu_seqlens_k must have the same length B + 1 >= 2, got %d and %d" % (cu_seqlens_q.numel(), cu_seqlens_k.numel()))
+    if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_k.dtype != torch.int32:
+        raise ValueError("fa2: cu_seqlens_q / cu_seqlens_k must be int32, got %s and %s" % (cu_seqlens_q.dtype, cu_seqlens_k.dtype))
+    if cu_seqlens_q.device != q.device or cu_seqlens_k.device != q.device:
+        raise ValueError("fa2: cu_seqlens_q / cu_seqlens_k must be on the device of q")
+    if k.shape[2] != q.shape[2] or v.shape != k.shape:
+        raise RuntimeError("fa2: inconsistent q/k/v shapes %s %s %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    _check_groups(q.shape[1], k.shape[1])
+    if q.shape[2] > _MAX_HEAD_DIM:
+        raise RuntimeError("fa2: head dim %d is larger than the largest gfx950 kernel" % q.shape[2])
+    if not q.is_cuda or not k.is_cuda or not v.is_cuda:
+        raise RuntimeError("fa2: q, k, v must be on a ROCm device (no CPU path in this operator)")
+    if k.device != q.device or v.device != q.device:
+        raise RuntimeError("fa2: q, k, v must be on the same device")
+    if not cu_seqlens_q.is_contiguous() or not cu_seqlens_k.is_contiguous():
+        raise ValueError("fa2: cu_seqlens_q / cu_seqlens_k must be contiguous")
+    return q.shape[1], k.shape[1], q.shape[2]
+
+
 def _check_groups(h, h_kv):
     """Grouped-query attention: k and v share a head count that divides q's (Q head i attends K / V head i // (h // h_kv))."""
     if h_kv < 1 or h % h_kv:
@@ -558,6 +669,52 @@ class _WindowAttentionFunction(torch.autograd.Function):
         q, k, v, o, L = ctx.saved_tensors
         dQ, dK, dV = flash_attn_wmma.backward_window(q, k, v, o, do, L, N, Nkv, D, 128, 128, causal, scale, BNHD_fmt, window)
         return dQ, dK, dV, None, None, None, None
+
+
+class _VarlenAttentionFunction(torch.autograd.Function):
+    """autograd node of flash_attention_varlen: forward = fa2_fwd_varlen (flagged FA2_FLAG_EXACT_SCALE), backward = fa2_bwd_varlen."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, flags, scale, window):
+        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_varlen(q, k, v, cu_q, cu_k, max_q, max_k, flags | _fa2_lib.FA2_FLAG_EXACT_SCALE, scale, window)
+        ctx.args = (max_q, max_k, q.shape[2], flags, scale, window)
+        ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L, cu_q, cu_k)
+        return o
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, do):
+        max_q, max_k, D, flags, scale, window = ctx.args
+        q, k, v, o, L, cu_q, cu_k = ctx.saved_tensors
+        dQ, dK, dV = flash_attn_wmma.backward_varlen(q, k, v, o, do, L, cu_q, cu_k, max_q, max_k, D, flags, scale, window)
+        return dQ, dK, dV, None, None, None, None, None, None, None
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=False, scale=None, window=None,
+                           bottom_right=False):
+    """Packed, variable-length attention: B sequences of individual lengths in one buffer (the flash_attn_varlen_func shape).
+    q [total_q, H, D], k / v [total_k, Hkv, D] (Hkv divides H: grouped K / V are not expanded); cu_seqlens_q / cu_seqlens_k: int32 [B + 1] on q's
+    device, non-decreasing — sequence s owns the rows [cu[s], cu[s+1]); zero-length sequences are fine.  Returns [total_q, H, D].
+    max_seqlen_q / max_seqlen_k: host ints >= every sequence's length; they size the grids.  None computes the maximum from the tensor, which is a
+    device-to-host SYNCHRONISATION — pass them in a hot loop.  A sequence longer than the stated maximum is the caller's error: its extra rows are
+    not computed.
+    causal / window: per sequence, as flash_attention's (window None, an int W or (left, right); causal means right = 0).  Row i of a sequence sits at
+    key position i (top-left, this library's convention) or, with bottom_right=True, at i + Nkv_s - Nq_s (other libraries' causal convention; a
+    sequence with fewer keys than queries then has leading rows that see nothing).  Rows that see no key return zeros.
+    Differentiable in q, k, v (C-ABI fa2_fwd_varlen / fa2_bwd_varlen): no atomics, deterministic gradients."""
+    left, right, _ = _fa2_lib.parse_window(window, 0)
+    h, h_kv, D = _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k)
+    if max_seqlen_q is None:
+        max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max())
+    if max_seqlen_k is None:
+        max_seqlen_k = int((cu_seqlens_k[1:] - cu_seqlens_k[:-1]).max())
+    if scale is None:
+        scale = D ** -0.5
+    flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | (_fa2_lib.FA2_FLAG_BOTTOM_RIGHT if bottom_right else 0)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return _VarlenAttentionFunction.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right))
+    return flash_attn_wmma.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right))[0]
 
 
 def _band_mask(nq, nkv, window, causal, device):

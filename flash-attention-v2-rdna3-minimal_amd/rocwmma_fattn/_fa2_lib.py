@@ -23,6 +23,7 @@ FA2_BIAS_NONE, FA2_BIAS_IO_DTYPE, FA2_BIAS_F32, FA2_BIAS_BOOL = 0, 1, 2, 3     #
 
 FA2_KERNEL_HIP_256, FA2_KERNEL_HIP_128, FA2_KERNEL_ASM, FA2_KERNEL_HIP_BIAS = 1, 2, 3, 4              # fa2_fwd_plan_t.kernel
 FA2_KERNEL_HIP_WINDOW = 5                                                                               # ... of fa2_fwd_window_plan (an enumerator in the header)
+FA2_KERNEL_HIP_VARLEN = 6                                                                               # ... of fa2_fwd_varlen_plan (an enumerator, too)
 FA2_CONTRACT_PRESCALE_Q, FA2_CONTRACT_LSUM_P16 = 1, 2                                                   # fa2_fwd_plan_t.contract bits
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -81,6 +82,14 @@ SYMBOLS = {
     "fa2_fwd_window_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p, _i64p, ctypes.c_float] + [ctypes.c_int] * 4 + [ctypes.c_size_t, ctypes.POINTER(FwdPlan)]),
     "fa2_window_tile_range": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_window_row_range": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    # packed (variable-length) attention: [total, heads, D] tensors with {head, row} strides, cu_seqlens in device memory, the stated maximum lengths
+    "fa2_fwd_varlen": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 2 + [_i64p] * 4 +
+                       [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "fa2_bwd_varlen": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [_i64p] * 8 +
+                       [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "fa2_fwd_varlen_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p, _i64p, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.POINTER(FwdPlan)]),
+    "fa2_varlen_tile_range": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "fa2_varlen_row_range": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_set_option": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "fa2_get_option": (ctypes.c_int, [ctypes.c_char_p]),
     "fa2_error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -165,6 +174,7 @@ class options:
 
 
 FA2_FLAG_CAUSAL, FA2_FLAG_EXACT_SCALE = 1, 2       # bits of the `causal` argument (include/fa2_gfx950.h)
+FA2_FLAG_BOTTOM_RIGHT = 4                          # ... of the packed (varlen) entry points' `flags` only
 
 
 def call_flags(causal):
@@ -245,6 +255,25 @@ def window_tile_range(Nq, Nkv, window_left, window_right, q_offset, causal, row0
     fn = load().fa2_window_row_range if transpose else load().fa2_window_tile_range
     check(fn(int(Nq), int(Nkv), int(window_left), int(window_right), int(q_offset), int(bool(causal)), int(row0), int(rows), int(tile),
              ctypes.byref(first), ctypes.byref(n)))
+    return first.value, n.value
+
+
+def varlen_plan(q, k, max_seqlen_q, max_seqlen_k, B, flags=0, window_left=-1, window_right=-1, scale=None):
+    """fa2_fwd_varlen_plan for the call fa2_fwd_varlen(q, k, ...) would be (q: [total_q, H, D], k: [total_k, Hkv, D], B sequences; flags: FA2_FLAG_*)."""
+    _, H, D = q.shape
+    dt = FA2_DTYPE_F16 if q.dtype == torch.float16 else FA2_DTYPE_BF16
+    plan = FwdPlan()
+    check(load().fa2_fwd_varlen_plan(dt, int(B), H, k.shape[1], int(max_seqlen_q), int(max_seqlen_k), D, strides2(q.stride(1), q.stride(0)),
+                                     strides2(k.stride(1), k.stride(0)), float(D ** -0.5 if scale is None else scale), int(flags),
+                                     int(window_left), int(window_right), ctypes.byref(plan)))
+    return plan
+
+
+def varlen_tile_range(Nq_s, Nkv_s, window_left, window_right, flags, row0, rows, tile=64, transpose=False):
+    """fa2_varlen_tile_range (transpose: fa2_varlen_row_range, row0 / rows then name a block of keys) -> (first_tile, ntiles)."""
+    first, n = ctypes.c_int(), ctypes.c_int()
+    fn = load().fa2_varlen_row_range if transpose else load().fa2_varlen_tile_range
+    check(fn(int(Nq_s), int(Nkv_s), int(window_left), int(window_right), int(flags), int(row0), int(rows), int(tile), ctypes.byref(first), ctypes.byref(n)))
     return first.value, n.value
 
 

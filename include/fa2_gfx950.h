@@ -57,6 +57,7 @@
 
 #define FA2_FLAG_CAUSAL      1
 #define FA2_FLAG_EXACT_SCALE 2
+#define FA2_FLAG_BOTTOM_RIGHT 4   /* the packed (varlen) entry points only: see fa2_fwd_varlen; every other entry point refuses this bit */
 
 #ifdef __cplusplus
 extern "C" {
@@ -341,6 +342,64 @@ int fa2_window_tile_range(int Nq, int Nkv, int window_left, int window_right, in
 int fa2_window_row_range(int Nq, int Nkv, int window_left, int window_right, int q_offset, int causal,
                          int key0, int keys, int tile, int* first_tile, int* ntiles);
 
+/*
+ * Packed, variable-length attention: B sequences of individual lengths in one buffer, the layout of other libraries' varlen calls.
+ * Layout
+ *   q, o, dout, dq : [total_q, H, D]; row t of head h at ptr + t*strides[1] + h*strides[0] — element strides {head, row}, D contiguous
+ *   k, v, dk, dv   : [total_k, Hkv, D], addressed the same way (the backward is the multi-head one: its k, v, dk, dv have H heads; a caller with
+ *                    grouped K / V expands them and sums dK / dV per group, as for fa2_bwd_window).  The forward addresses K / V through the
+ *                    group h / (H / Hkv); nothing is expanded.
+ *   Alignment as everywhere: 16-byte pointers, strides multiples of 8 elements.
+ *   cu_seqlens_q, cu_seqlens_k : int32[B + 1] in DEVICE memory, non-decreasing.  Sequence s owns the rows [cu[s], cu[s+1]): Nq_s queries, Nkv_s keys.
+ *                    Zero-length sequences are legal on either side.  Rows at or beyond cu[B] are neither read nor written.
+ *   max_seqlen_q, max_seqlen_k : host integers >= every Nq_s / Nkv_s.  They size the grids (B * H * ceil(max_seqlen / rows) workgroups), so the call
+ *                    needs no device-to-host synchronisation.  A sequence LONGER than the stated maximum is the caller's error and cannot be detected
+ *                    on the host: its query rows (in the dK / dV passes: its key rows) beyond the maximum are not computed, their outputs not written.
+ *   lse, delta_ws  : f32 [H, total_q]; element (h, t) at lse + h*lse_stride + t.  lse in log2 units, as everywhere.
+ * Masking, per sequence: the windowed contract above with a per-sequence offset off_s.  Row i of sequence s attends key j of the SAME sequence iff
+ *   (window_left < 0 or j >= i + off_s - window_left) and (window_right < 0 or j <= i + off_s + window_right) and 0 <= j < Nkv_s.
+ * FA2_FLAG_CAUSAL means window_right = 0.  off_s = 0 is this library's top-left convention and the default; FA2_FLAG_BOTTOM_RIGHT makes
+ * off_s = Nkv_s - Nq_s (the convention of other libraries' causal varlen calls).  That offset is negative for a sequence with fewer keys than
+ * queries: its first Nq_s - Nkv_s - window_right rows then see nothing.
+ * A row that sees no key (Nkv_s = 0, or a row outside the band) returns O = 0 and lse = -inf and contributes no gradient; dK / dV of keys nobody sees
+ * are zero (Nq_s = 0 included).  Every element of o, lse, dq, dk, dv below cu[B] is written — no zero-init needed — by exactly one owner: no atomics,
+ * deterministic results.  FA2_FLAG_EXACT_SCALE is accepted; the kernels are contract 0 (f32 scale, f32 row sums) either way.
+ * Validation (the existing codes; the contents of cu_seqlens are not validated, they live on the device): null pointers; B, H, Hkv, D or a maximum
+ * below 1; Hkv not dividing H; a bad window; flag bits other than the three named here; head dim; alignment; a stated maximum whose K / V span
+ * (max_seqlen * row pitch; in the backward also Q / dO) reaches 2 GiB; grids beyond 2^31 - 1.  Everything but the tensors and cu_seqlens is
+ * checked first, so a bad argument is reported as what it is even with null tensors.
+ * Kernels (FA2_KERNEL_HIP_VARLEN): the compiler-scheduled windowed kernels with the lengths, base rows and offset read per workgroup from cu_seqlens.
+ * A workgroup whose block starts at or beyond its sequence's length returns at once; the K / V (and Q / dO / lse) buffer descriptors of a workgroup end
+ * at the last row of its own sequence, so a neighbour's rows are never fetched.  A band that masks nothing runs the unmasked steady-state loop.
+ * Head dims: multiples of 8 up to 512.  Option "rows" picks 128- or 256-row forward workgroups as elsewhere, otherwise a heuristic on the grid of
+ * the stated maxima; the plan query reports it (rows as launched, heads_main = B*H; its strides may be NULL for contiguous tensors).
+ * The result for a sequence is bit-identical to fa2_fwd_window on that sequence alone (q_offset = off_s, same "rows") wherever that call runs
+ * FA2_KERNEL_HIP_WINDOW.
+ */
+int fa2_fwd_varlen(int dtype,
+                   const void* q, const void* k, const void* v, void* o, float* lse,
+                   int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D,
+                   const int* cu_seqlens_q, const int* cu_seqlens_k,
+                   const int64_t q_strides[2], const int64_t k_strides[2],
+                   const int64_t v_strides[2], const int64_t o_strides[2],
+                   int64_t lse_stride,
+                   float scale, int flags, int window_left, int window_right, void* hip_stream);
+int fa2_bwd_varlen(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                   void* dq, void* dk, void* dv, float* delta_ws,
+                   int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                   const int* cu_seqlens_q, const int* cu_seqlens_k,
+                   const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2],
+                   const int64_t o_strides[2], const int64_t do_strides[2], const int64_t dq_strides[2],
+                   const int64_t dk_strides[2], const int64_t dv_strides[2], int64_t lse_stride,
+                   float scale, int flags, int window_left, int window_right, void* hip_stream);
+/* The per-sequence range arithmetic of the packed kernels: fa2_window_tile_range / fa2_window_row_range for one sequence of Nq_s queries and Nkv_s
+ * keys (>= 0), the offset derived from `flags` (FA2_FLAG_BOTTOM_RIGHT: Nkv_s - Nq_s, which may be negative — the windowed queries above keep
+ * refusing negative offsets; FA2_FLAG_CAUSAL: window_right = 0).  Pure host arithmetic. */
+int fa2_varlen_tile_range(int Nq_s, int Nkv_s, int window_left, int window_right, int flags,
+                          int row0, int rows, int tile, int* first_tile, int* ntiles);
+int fa2_varlen_row_range(int Nq_s, int Nkv_s, int window_left, int window_right, int flags,
+                         int key0, int keys, int tile, int* first_tile, int* ntiles);
+
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
  * that is not a multiple of 8 has to be zero-padded by the caller (to the next multiple of 8). */
@@ -412,6 +471,12 @@ int fa2_fwd_window_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D
                         const int64_t q_strides[3], const int64_t k_strides[3],
                         float scale, int flags, int window_left, int window_right, int q_offset,
                         size_t workspace_bytes, fa2_fwd_plan_t* plan);
+
+/* The plan of the packed forward (fa2_fwd_varlen above): kernel = FA2_KERNEL_HIP_VARLEN, contract 0, rows as launched, heads_main = B*H. */
+enum { FA2_KERNEL_HIP_VARLEN = 6 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+int fa2_fwd_varlen_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D,
+                        const int64_t q_strides[2], const int64_t k_strides[2],
+                        float scale, int flags, int window_left, int window_right, fa2_fwd_plan_t* plan);
 
 /* Coarse form of the above (kept for callers of version 0.8): 1 if launches of this head dim MAY fold the scale into Q (head dims exactly 64
  * and 128, 0 < scale*log2(e) <= 1, option "fold" >= 1: the fp16 launches the hand-scheduled bodies take), 0 if none does, -1: D not supported.
