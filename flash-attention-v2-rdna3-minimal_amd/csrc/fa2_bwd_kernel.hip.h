@@ -471,6 +471,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
     const float c = p.c, scale = p.scale;
+#if FA2_DROP
+    // FA2_DROP (fa2_bwd_dropout; fa2_dropout.h): dP = keep o (dO V^T) / (1 - p_eff) — the lane layout is the forward's, and so are the Philox calls
+    const DropCtx drop = drop_ctx(p, b, h);
+#endif
 
     // tiles [0, n_plain) need no mask for this wave: fully inside Nkv and fully below the wave's diagonal
     int n_plain = p.Nkv / kKvTile;
@@ -583,6 +587,18 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
                 d0 = mfma16<BF16>(lds_load128(vR + ln.kr_off[ks]), gf[ks], d0);
                 d1 = mfma16<BF16>(lds_load128(vR + ln.kr_off[ks] + 32 * ROWB), gf[ks], d1);
             }
+#if FA2_DROP
+            {
+                uint32_t dw[4][4];
+                drop_rowlane_words(drop, (uint32_t)qrow, (uint32_t)kv0, (uint32_t)hi, dw);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const uint32_t w0 = dw[r >> 3][(r & 7) >> 1], w1 = dw[2 + (r >> 3)][(r & 7) >> 1];
+                    d0[r] = ((r & 1) ? drop_keep_hi(drop, w0) : drop_keep_lo(drop, w0)) ? d0[r] * drop.rs : 0.f;
+                    d1[r] = ((r & 1) ? drop_keep_hi(drop, w1) : drop_keep_lo(drop, w1)) ? d1[r] * drop.rs : 0.f;
+                }
+            }
+#endif
             // dS^T / scale = P^T * (dP^T - D); the factor `scale` is applied once, to the finished dQ
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -836,6 +852,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[dt][r] = 0.f; if constexpr (BOTH) accv[dt][r] = 0.f; }
     const float c = p.c, scale = p.scale;
+#if FA2_DROP
+    // FA2_DROP: lane = key — the keep bits of a tile come from drop_keylane_bits (fa2_dropout.h); dV = (keep o P)^T dO / (1 - p_eff), the factor applied
+    // once to the finished dV; dP = keep o (dO V^T) / (1 - p_eff).  (kv_group = 1: h is the query head)
+    const DropCtx drop = drop_ctx(p, b, h * G);
+#endif
 
     // Q tiles from first_plain on lie entirely at or below this wave's KV rows' diagonal (q >= kv for every pair)
 #if FA2_WIN
@@ -952,6 +973,16 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
                 }
             }
 #endif
+#if FA2_DROP
+            const uint32_t kbits = drop_keylane_bits(drop, (uint32_t)q0t, (uint32_t)kvw0, (uint32_t)l31, (uint32_t)hi);
+            if constexpr (WANT_DK) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    d0[r] = (kbits & (1u << r)) ? d0[r] * drop.rs : 0.f;
+                    d1[r] = (kbits & (1u << (16 + r))) ? d1[r] * drop.rs : 0.f;
+                }
+            }
+#endif
             if constexpr (WANT_DK) {
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
@@ -968,6 +999,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
                     }
                 }
             }
+#if FA2_DROP
+            if constexpr (!WANT_DK || BOTH) {          // the P the dV product sees
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if (!(kbits & (1u << r))) s0[r] = 0.f;
+                    if (!(kbits & (1u << (16 + r)))) s1[r] = 0.f;
+                }
+            }
+#endif
             u32x4 xf[4];   // P (dV) or dS (dK) as B fragments: contraction index = q
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1054,11 +1094,19 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
     if (kvrow < p.Nkv) {
         uint16_t* op = WANT_DK ? (uint16_t*)p.dk + b * p.dks[0] + h * p.dks[1] + (int64_t)kvrow * p.dks[2]
                                : (uint16_t*)p.dv + b * p.dvs[0] + h * p.dvs[1] + (int64_t)kvrow * p.dvs[2];
+#if FA2_DROP
+        store_acc_t<BF16, DT>(acc, op, hi, WANT_DK ? scale : drop.rs, p.D, vcol0);
+        if constexpr (BOTH) {
+            uint16_t* ov = (uint16_t*)p.dv + b * p.dvs[0] + h * p.dvs[1] + (int64_t)kvrow * p.dvs[2];
+            store_acc_t<BF16, DT>(accv, ov, hi, drop.rs, p.D);
+        }
+#else
         store_acc_t<BF16, DT>(acc, op, hi, WANT_DK ? scale : 1.0f, p.D, vcol0);
         if constexpr (BOTH) {
             uint16_t* ov = (uint16_t*)p.dv + b * p.dvs[0] + h * p.dvs[1] + (int64_t)kvrow * p.dvs[2];
             store_acc_t<BF16, DT>(accv, ov, hi, 1.0f, p.D);
         }
+#endif
     }
 }
 
@@ -1197,6 +1245,11 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
     const float c = p.c;
+#if FA2_DROP
+    // FA2_DROP: both waves of a pair form the tile's keep bits (drop_keylane_bits) — the P side masks the fragments of its dV product (the slot carries the
+    // undropped P, which dS needs), the dS side masks dP
+    const DropCtx drop = drop_ctx(p, b, h * G);
+#endif
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     typedef const __attribute__((address_space(3))) f32x4* lds_f32x4_cptr;
     typedef __attribute__((address_space(3))) u32x4* lds_u32x4_ptr;
@@ -1288,6 +1341,16 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
 #pragma unroll
             for (int i = 0; i < 4; ++i) *(lds_u32x4_ptr)(xch + 1024 * i) = xf[i];
             pair_mid_barrier();                                       // P is in the pair's slot
+#if FA2_DROP
+            {
+                const uint32_t kbits = drop_keylane_bits(drop, (uint32_t)(tile * kKvTile), (uint32_t)kvw0, (uint32_t)l31, (uint32_t)hi);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        xf[j][i] &= ((kbits & (1u << (8 * j + 2 * i))) ? 0xffffu : 0u) | ((kbits & (2u << (8 * j + 2 * i))) ? 0xffff0000u : 0u);
+            }
+#endif
             accumulate(qR + 3 * TILEB, xf);                           // dV^T += dO^T P
             __syncthreads();
         }
@@ -1306,6 +1369,16 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                 d0 = mfma16<BF16>(lds_load128(gR + ln.kr_off[ks]), bf[ks], d0);
                 d1 = mfma16<BF16>(lds_load128(gR + ln.kr_off[ks] + 32 * ROWB), bf[ks], d1);
             }
+#if FA2_DROP
+            {
+                const uint32_t kbits = drop_keylane_bits(drop, (uint32_t)(tile * kKvTile), (uint32_t)kvw0, (uint32_t)l31, (uint32_t)hi);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    d0[r] = (kbits & (1u << r)) ? d0[r] * drop.rs : 0.f;
+                    d1[r] = (kbits & (1u << (16 + r))) ? d1[r] * drop.rs : 0.f;
+                }
+            }
+#endif
             pair_mid_barrier();
             u32x4 xf[4];
 #pragma unroll
@@ -1352,7 +1425,11 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
     if (kvrow < p.Nkv) {
         uint16_t* op = ds_side ? (uint16_t*)p.dk + b * p.dks[0] + h * p.dks[1] + (int64_t)kvrow * p.dks[2]
                                : (uint16_t*)p.dv + b * p.dvs[0] + h * p.dvs[1] + (int64_t)kvrow * p.dvs[2];
+#if FA2_DROP
+        store_acc_t<BF16, DT>(acc, op, hi, ds_side ? p.scale : drop.rs, p.D);
+#else
         store_acc_t<BF16, DT>(acc, op, hi, ds_side ? p.scale : 1.0f, p.D);
+#endif
     }
 }
 

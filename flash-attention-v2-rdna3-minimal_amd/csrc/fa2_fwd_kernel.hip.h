@@ -57,6 +57,18 @@
 #else
 #define FA2_KP p
 #endif
+// FA2_DROP = 1 (dropout_hip.cpp / varlen_dropout_hip.cpp only, on top of FA2_WIN = 1): attention dropout.  The keep mask is fa2_dropout.h's, a pure function of
+// (seed, b * H + h, row, key); the softmax state (m, l, the LSE) is that of the undropped probabilities, the packed 16-bit P of a step is AND-ed with the mask
+// before the P.V product, and 1 / (1 - p_eff) is folded into the epilogue's inv_l.
+#ifndef FA2_DROP
+#define FA2_DROP 0
+#endif
+#if FA2_DROP && !FA2_WIN
+#error "FA2_DROP builds on the FA2_WIN blocks"
+#endif
+#if FA2_DROP
+#include "fa2_dropout.h"
+#endif
 
 // ---- tuning knobs (A/B-tested on MI355X with tools/kbench.py; numbers at B2 H16 N4096 D128 fp16) ----
 #ifndef FA2_DEFER_THR        // skip the O rescale while the row max grew by <= this (log2 units); <0: always rescale.
@@ -501,6 +513,10 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     }
 #endif
 
+#if FA2_DROP
+    const DropCtx drop = drop_ctx(p, b, h);      // (packed calls: b is the sequence, qrow and the keys count inside it)
+    int drop_kv0 = 0;                            // absolute first key of the tile whose P is being formed (set by step)
+#endif
     f32x16 acc[QB][DT];
     float m_run[QB], l_run[QB];  // running reference max (raw score units) / row sum (this lane's kv half)
 #pragma unroll
@@ -972,6 +988,17 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
                 pf[qb][2][i] = pack2<BF16>(s1[2 * i], s1[2 * i + 1]);
                 pf[qb][3][i] = pack2<BF16>(s1[8 + 2 * i], s1[8 + 2 * i + 1]);
             }
+#if FA2_DROP
+            {                                   // word w of call c masks the packed pair pf[c][w] (fa2_dropout.h: the counter mapping)
+#pragma unroll
+                for (int cI = 0; cI < 4; ++cI) {
+                    uint32_t dw[4];
+                    drop_rowlane_call(drop, (uint32_t)qrow[qb], (uint32_t)drop_kv0, (uint32_t)hi, cI, dw);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) pf[qb][cI][i] &= drop_pair_mask(drop, dw[i]);
+                }
+            }
+#endif
         }
     };
 
@@ -1023,6 +1050,9 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         if (next_w) qk(PAR ^ 1, sn);
         if (cur_w) {
             u32x4 pf[QB][4];
+#if FA2_DROP
+            drop_kv0 = kv_first + tile * kKvTile;
+#endif
             exp_scores(sc, pf);
             pv(PAR, pf);
         }
@@ -1133,7 +1163,9 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         __syncthreads();                                         // every wave is done reading the K / V buffers
         char* img = smem + wave * (32 * EROW);
         const float l_tot = half_swap_sum(l_run[0]);
-#if FA2_WIN
+#if FA2_DROP
+        const float inv_l = !(l_tot > 0.f) ? 0.f : drop.rs / l_tot;          // ... and the kept probabilities scaled by 1 / (1 - p_eff)
+#elif FA2_WIN
         const float inv_l = !(l_tot > 0.f) ? 0.f : 1.0f / l_tot;             // row that sees no key: O = 0 (lse = -inf)
 #else
         const float inv_l = (BIAS && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;   // fully masked row: O = 0 (lse = -inf)
@@ -1169,7 +1201,9 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
         const float l_tot = half_swap_sum(l_run[qb]);
-#if FA2_WIN
+#if FA2_DROP
+        const float inv_l = !(l_tot > 0.f) ? 0.f : drop.rs / l_tot;
+#elif FA2_WIN
         const float inv_l = !(l_tot > 0.f) ? 0.f : 1.0f / l_tot;
 #else
         const float inv_l = (BIAS && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;

@@ -187,6 +187,16 @@ FA2_HIDDEN int launch_fwd_varlen_f16(int HD, const FwdParams& p, int rows, hipSt
 FA2_HIDDEN int launch_fwd_varlen_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_varlen_f16(int HD, const BwdParams& p, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_varlen_bf16(int HD, const BwdParams& p, hipStream_t stream);
+// attention dropout (dropout_hip.cpp, varlen_dropout_hip.cpp): the same launchers over the DROP forms of the windowed and packed kernels; the seed and
+// the threshold travel in p.full_items / p.split_items / p.bias_kind (set_dropout, fa2_dropout.h)
+FA2_HIDDEN int launch_fwd_dropout_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_fwd_dropout_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_dropout_f16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_dropout_bf16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_HIDDEN int launch_fwd_varlen_dropout_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_fwd_varlen_dropout_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_varlen_dropout_f16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_HIDDEN int launch_bwd_varlen_dropout_bf16(int HD, const BwdParams& p, hipStream_t stream);
 // hand-scheduled backward, head dim exactly 128 (bwd_asm.cpp); same `parts`
 // neg_delta: the dQ pass writes -delta (the hand-scheduled dK/dV pass reads it as such; the HIP dK/dV passes read +delta)
 // kfold: the dK / dV body whose P side folds scale * log2(e) into its K fragments (option "fold"; host.cpp: bwd_folds)

@@ -12,6 +12,7 @@
 // launch is asynchronous on the caller's stream, and failures are returned, not printf'ed
 // (reference: kernel_fp16.cu:854-863).
 #include "fa2_launch.h"
+#include "fa2_dropout.h"
 
 #include <algorithm>
 #include <cmath>
@@ -408,6 +409,10 @@ WindowCall reduce_window(int Nq, int Nkv, int left, int right, int off, bool cau
 // carries the bottom-right flag.  Nq / Nkv of such a call are the stated maximum lengths, B the number of sequences, the batch strides 0.
 struct VarlenCall { const int* cu_q; const int* cu_k; };
 
+// A dropout call on its way through fwd_impl / bwd_impl (always with a window, which may mask nothing): the seed and the threshold of fa2_dropout.h
+struct DropCall { uint64_t seed; uint32_t t; };
+bool dropout_p_ok(float p) { return p >= 0.f && p < 1.f; }       // (NaN fails both comparisons)
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool strides_ok(const int64_t* s) { return s[0] % 8 == 0 && s[1] % 8 == 0 && s[2] % 8 == 0 && s[2] > 0; }
 
@@ -483,6 +488,7 @@ const char* fa2_error_string(int code) {
         case FA2_ERR_SCALE: return "fa2: scale must be finite";
         case FA2_ERR_GRID: return "fa2: B*H*ceil(Nq/256) exceeds the grid limit";
         case FA2_ERR_BIAS: return "fa2: bias_kind must be FA2_BIAS_{NONE,IO_DTYPE,F32,BOOL} and bias strides >= 0";
+        case FA2_ERR_DROPOUT: return "fa2: dropout_p must be in [0, 1)";
         default: break;
     }
     if (code > 0) return hipGetErrorString((hipError_t)code);
@@ -496,7 +502,7 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
                     const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
                     float scale, int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
                     void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, fa2_fwd_plan_t* plan_out = nullptr, int Hkv = 0,
-                    const fa2::Window* win = nullptr, const VarlenCall* vl = nullptr) {
+                    const fa2::Window* win = nullptr, const VarlenCall* vl = nullptr, const DropCall* drop = nullptr) {
     // `causal` carries the call's flags: bit 0 = causal mask, bit 1 = FA2_FLAG_EXACT_SCALE (this call scales the f32 product whatever option "fold" says)
     // Until round 5 any non-zero value meant "causal"; a caller that still passes another truthy int would silently get a non-causal forward: refuse it
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
@@ -593,6 +599,11 @@ static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void
             plan_out->heads_main = B * H;
         }
         if (plan_only) return FA2_OK;
+        if (drop) {       // fa2_fwd_dropout / fa2_fwd_varlen_dropout: the DROP forms of the same kernels
+            fa2::set_dropout(p, drop->seed, drop->t);
+            if (vl) return bf16 ? fa2::launch_fwd_varlen_dropout_bf16(HD, p, rows, stream) : fa2::launch_fwd_varlen_dropout_f16(HD, p, rows, stream);
+            return bf16 ? fa2::launch_fwd_dropout_bf16(HD, p, rows, stream) : fa2::launch_fwd_dropout_f16(HD, p, rows, stream);
+        }
         if (vl) return bf16 ? fa2::launch_fwd_varlen_bf16(HD, p, rows, stream) : fa2::launch_fwd_varlen_f16(HD, p, rows, stream);
         return bf16 ? fa2::launch_fwd_window_bf16(HD, p, rows, stream) : fa2::launch_fwd_window_f16(HD, p, rows, stream);
     }
@@ -706,7 +717,7 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
             const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
             int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
             void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, int Hkv = 0, const fa2::Window* win = nullptr,
-            const VarlenCall* vl = nullptr) {
+            const VarlenCall* vl = nullptr, const DropCall* drop = nullptr) {
     if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;      // (as in fwd_impl: no value but the documented flag bits)
     causal &= 1;          // (bit 1, FA2_FLAG_EXACT_SCALE, is what the backward does anyway unless option "kfold" is set)
     if (ws_need) *ws_need = 0;
@@ -782,6 +793,14 @@ static int bwd_impl(int dtype, const void* q, const void* k, const void* v, cons
     const bool bf16 = dtype == FA2_DTYPE_BF16;
     if (win) {          // fa2_bwd_window with a window that masks something: the WIN passes
         fa2::set_window(p, *win);
+        if (drop) {       // fa2_bwd_dropout / fa2_bwd_varlen_dropout
+            fa2::set_dropout(p, drop->seed, drop->t);
+            if (vl) {
+                p.bias = vl->cu_q; p.ws = (float*)const_cast<int*>(vl->cu_k);
+                return bf16 ? fa2::launch_bwd_varlen_dropout_bf16(HD, p, stream) : fa2::launch_bwd_varlen_dropout_f16(HD, p, stream);
+            }
+            return bf16 ? fa2::launch_bwd_dropout_bf16(HD, p, stream) : fa2::launch_bwd_dropout_f16(HD, p, stream);
+        }
         if (vl) {
             p.bias = vl->cu_q; p.ws = (float*)const_cast<int*>(vl->cu_k);
             return bf16 ? fa2::launch_bwd_varlen_bf16(HD, p, stream) : fa2::launch_bwd_varlen_f16(HD, p, stream);
@@ -1071,6 +1090,108 @@ int fa2_varlen_tile_range(int Nq_s, int Nkv_s, int window_left, int window_right
 
 int fa2_varlen_row_range(int Nq_s, int Nkv_s, int window_left, int window_right, int flags, int key0, int keys, int tile, int* first_tile, int* ntiles) {
     return varlen_range(true, Nq_s, Nkv_s, window_left, window_right, flags, key0, keys, tile, first_tile, ntiles);
+}
+
+// ---- attention dropout: include/fa2_gfx950.h has the contract, fa2_dropout.h the mask, dropout_hip.cpp / varlen_dropout_hip.cpp the kernels.
+// These calls always take the windowed (packed) kernel family, also when the window masks nothing: its DROP forms are the only kernels with the mask.
+int fa2_fwd_dropout(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
+                    int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                    const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
+                    float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream, float dropout_p, uint64_t seed) {
+    if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
+    if (Hkv < 1 || (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE))) return FA2_ERR_BAD_SHAPE;
+    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
+    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
+    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
+    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
+                    scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, &c.w, nullptr, &drop);
+}
+
+int fa2_bwd_dropout(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                    void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
+                    const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                    const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                    const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
+                    int flags, int window_left, int window_right, int q_offset, void* hip_stream, float dropout_p, uint64_t seed) {
+    if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
+    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
+    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
+    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
+    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
+    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
+                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream,
+                    nullptr, 0, nullptr, 0, &c.w, nullptr, &drop);
+}
+
+int fa2_fwd_varlen_dropout(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
+                           int max_seqlen_q, int max_seqlen_k, int D, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                           const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                           int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream, float dropout_p, uint64_t seed) {
+    if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
+    fa2::Window w;
+    if (int rc = varlen_check(B, H, Hkv, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
+    if (!q_strides || !k_strides || !v_strides || !o_strides) return FA2_ERR_NULL_POINTER;
+    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides);
+    const int64_t ls[2] = {0, lse_stride};
+    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
+    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
+    char* d = g_plan_dummy;          // (as fa2_fwd_varlen: everything but the tensors first)
+    fa2_fwd_plan_t plan;
+    if (int rc = fwd_impl(dtype, d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, FA2_FLAG_EXACT_SCALE,
+                          nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, nullptr, &plan, Hkv, &w, &vl, &drop))
+        return rc;
+    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
+    return fwd_impl(dtype, q, k, v, o, lse, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, FA2_FLAG_EXACT_SCALE,
+                    nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, &w, &vl, &drop);
+}
+
+int fa2_bwd_varlen_dropout(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                           void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                           const int* cu_seqlens_q, const int* cu_seqlens_k,
+                           const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                           const int64_t do_strides[2], const int64_t dq_strides[2], const int64_t dk_strides[2], const int64_t dv_strides[2],
+                           int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream, float dropout_p, uint64_t seed) {
+    if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
+    fa2::Window w;
+    if (int rc = varlen_check(B, H, H, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
+    if (!q_strides || !k_strides || !v_strides || !o_strides || !do_strides || !dq_strides || !dk_strides || !dv_strides) return FA2_ERR_NULL_POINTER;
+    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides), gs(do_strides), dqs(dq_strides), dks(dk_strides), dvs(dv_strides);
+    const int64_t ls[2] = {0, lse_stride};
+    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
+    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
+    char* d = g_plan_dummy;
+    size_t need = 0;
+    if (int rc = bwd_impl(dtype, d, d, d, d, d, (const float*)d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s,
+                          dks.s, dvs.s, ls, scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need, 0, &w, &vl, &drop))
+        return rc;
+    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
+    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s, dks.s, dvs.s,
+                    ls, scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, 0, &w, &vl, &drop);
+}
+
+int fa2_dropout_threshold(float dropout_p, float* p_eff) {
+    if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
+    return (int)fa2::dropout_threshold(dropout_p, p_eff);
+}
+
+int fa2_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    if (!ctr || !key || !out) return FA2_ERR_NULL_POINTER;
+    uint32_t o[4];
+    fa2::philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], o);
+    for (int i = 0; i < 4; ++i) out[i] = o[i];
+    return FA2_OK;
+}
+
+int fa2_dropout_keep_mask(uint64_t seed, float dropout_p, int H, int b, int h, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint8_t* mask) {
+    if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
+    if (!mask) return FA2_ERR_NULL_POINTER;
+    if (H < 1 || b < 0 || h < 0 || h >= H || i0 < 0 || j0 < 0 || i1 <= i0 || j1 <= j0 || i1 > 0x7fffffffLL || j1 > 0x7fffffffLL ||
+        (int64_t)b * H + h > 0xffffffffLL)
+        return FA2_ERR_BAD_SHAPE;
+    const uint32_t t = fa2::dropout_threshold(dropout_p, nullptr), bh = (uint32_t)((int64_t)b * H + h);
+    for (int64_t i = i0; i < i1; ++i)
+        for (int64_t j = j0; j < j1; ++j) mask[(i - i0) * (j1 - j0) + (j - j0)] = fa2::dropout_keep(seed, t, bh, (uint32_t)i, (uint32_t)j) ? 1 : 0;
+    return FA2_OK;
 }
 
 #define FA2_BWD_ARGS                                                                                                    \

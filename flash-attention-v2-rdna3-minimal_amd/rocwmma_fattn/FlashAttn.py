@@ -70,11 +70,12 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, window=window)
 
     @staticmethod
-    def forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, flags, scale, window):
+    def forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, flags, scale, window, dropout=None):
         """Packed, variable-length forward (extension: C-ABI fa2_fwd_varlen).  q [total_q, H, D], k / v [total_k, Hkv, D] (grouped K / V are addressed
         through the group), cu_seqlens_* int32 [B + 1] on q's device, the maxima host ints; flags = FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE |
         FA2_FLAG_BOTTOM_RIGHT; window = (window_left, window_right), -1 = unbounded.  Returns [O_fwd, q, k, v, O, L] like forward(): the tensors the
-        backward wants (D padded to a multiple of 8 if need be; O_fwd a view of O), L = f32 [H, total_q] in log2 units."""
+        backward wants (D padded to a multiple of 8 if need be; O_fwd a view of O), L = f32 [H, total_q] in log2 units.
+        dropout = (p, seed): attention dropout (C-ABI fa2_fwd_varlen_dropout)."""
         lib = _fa2_lib.load()
         h, h_kv, d = _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k)
         if q.dtype == torch.float16:
@@ -97,18 +98,19 @@ class _FlashAttnWmma:
             L.fill_(float("-inf"))
         elif total_q:
             dev = q.device.index
+            args = (dtype_code, q.data_ptr(), k.data_ptr(), v.data_ptr(), O.data_ptr(), L.data_ptr(), cu_seqlens_q.numel() - 1, h, h_kv,
+                    max(int(max_seqlen_q), 1), max(int(max_seqlen_k), 1), d + d_pad, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
+                    _s2(q), _s2(k), _s2(v), _s2(O), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]), _raw_stream(dev))
             with torch.cuda.device(dev):
-                rc = lib.fa2_fwd_varlen(dtype_code, q.data_ptr(), k.data_ptr(), v.data_ptr(), O.data_ptr(), L.data_ptr(), cu_seqlens_q.numel() - 1, h, h_kv,
-                                        max(int(max_seqlen_q), 1), max(int(max_seqlen_k), 1), d + d_pad, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
-                                        _s2(q), _s2(k), _s2(v), _s2(O), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]),
-                                        _raw_stream(dev))
+                rc = lib.fa2_fwd_varlen(*args) if dropout is None else lib.fa2_fwd_varlen_dropout(*args, float(dropout[0]), int(dropout[1]))
             if rc:
                 _fa2_lib.check(rc)
         return [O[..., :d] if d_pad else O, q, k, v, O, L]
 
     @staticmethod
-    def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window):
-        """backward() of forward_varlen (C-ABI fa2_bwd_varlen; grouped K / V: expanded, dK / dV summed per group in f32).  Returns [dQ, dK, dV]."""
+    def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window, dropout=None):
+        """backward() of forward_varlen (C-ABI fa2_bwd_varlen; grouped K / V: expanded, dK / dV summed per group in f32).  Returns [dQ, dK, dV].
+        dropout = (p, seed) of the forward: the mask is regenerated (fa2_bwd_varlen_dropout; it is keyed by the query head, so expansion changes nothing)."""
         lib = _fa2_lib.load()
         if not (Q.is_cuda and dO.is_cuda):
             raise RuntimeError("fa2: tensors must be on a ROCm device (no CPU path in this operator)")
@@ -117,7 +119,7 @@ class _FlashAttnWmma:
         if h_kv != h:
             def mha(Q4, K4, V4, O4, dO4, L_, *rest):
                 return [t.unsqueeze(0) for t in _FlashAttnWmma.backward_varlen(Q4[0], K4[0], V4[0], O4[0], dO4[0], L_, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
-                                                                               max_seqlen_k, act_d, flags, scale, window)]
+                                                                               max_seqlen_k, act_d, flags, scale, window, dropout)]
             return [t[0] for t in _grouped_backward(mha, Q.unsqueeze(0), K.unsqueeze(0), V.unsqueeze(0), O.unsqueeze(0), dO.unsqueeze(0), L, 0, 0, act_d,
                                                     128, 128, False, scale, True)]
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
@@ -134,17 +136,18 @@ class _FlashAttnWmma:
         L = L.contiguous()
         delta = torch.empty_like(L)
         dev = Q.device.index
+        args = (dtype_code, Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(), dQ.data_ptr(),
+                dK.data_ptr(), dV.data_ptr(), delta.data_ptr(), cu_seqlens_q.numel() - 1, h, max(int(max_seqlen_q), 1),
+                max(int(max_seqlen_k), 1), dk, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), _s2(Q), _s2(K), _s2(V), _s2(O), _s2(dO),
+                _s2(dQ), _s2(dK), _s2(dV), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]), _raw_stream(dev))
         with torch.cuda.device(dev):
-            rc = lib.fa2_bwd_varlen(dtype_code, Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(), dQ.data_ptr(),
-                                    dK.data_ptr(), dV.data_ptr(), delta.data_ptr(), cu_seqlens_q.numel() - 1, h, max(int(max_seqlen_q), 1),
-                                    max(int(max_seqlen_k), 1), dk, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), _s2(Q), _s2(K), _s2(V), _s2(O), _s2(dO),
-                                    _s2(dQ), _s2(dK), _s2(dV), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]), _raw_stream(dev))
+            rc = lib.fa2_bwd_varlen(*args) if dropout is None else lib.fa2_bwd_varlen_dropout(*args, float(dropout[0]), int(dropout[1]))
         if rc:
             _fa2_lib.check(rc)
         return [dQ[..., :act_d], dK[..., :act_d], dV[..., :act_d]]
 
     @staticmethod
-    def forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=None, window=None):
+    def forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None):
         """Returns [O_fwd, q_pad, k_pad, v_pad, O, L] like forward_fp16/forward_bf16 (kernel_fp16.cu:744-876).
         O and L keep the reference's shapes — rows padded to a multiple of Br with a zero tail, O_fwd a view into
         O (kernel_fp16.cu:761, :793-796, :865-875) — but nothing is COPIED to get there: the gfx950 kernels mask
@@ -152,7 +155,10 @@ class _FlashAttnWmma:
         themselves (made contiguous if their strides require it; the reference returns padded copies,
         kernel_fp16.cu:767-779).  Only a D that is not a multiple of 8 is zero-padded, to the next multiple of 8.
         Br sizes the N padding of O and L; Bc is accepted for signature compatibility.  `causal`: the reference's bool, or the C-ABI's call flags
-        (_fa2_lib.FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE: the operator marks the forward of calls that will be differentiated)."""
+        (_fa2_lib.FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE: the operator marks the forward of calls that will be differentiated).
+        dropout = (p, seed), with a window (which may be (-1, -1, 0)): attention dropout (C-ABI fa2_fwd_dropout)."""
+        if dropout is not None and (window is None or bias is not None):
+            raise RuntimeError("fa2: the dropout forward is the windowed one (pass window=(-1, -1, 0) for full attention) and takes no bias")
         if window is not None:
             window = _fa2_lib.parse_window((window[0], window[1]), window[2])
         lib = _fa2_lib.load()
@@ -227,7 +233,10 @@ class _FlashAttnWmma:
             bias_t, kind, bstr = _prepare_bias(bias, b, h, n, n_kv, q_pad.dtype, q.device)
             args += (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
             fn = lib.fa2_fwd_bias
-        if window is not None:     # sliding window: fa2_fwd_window (grouped or not: K / V addressed through the group)
+        if dropout is not None:    # attention dropout: fa2_fwd_dropout (the windowed call's arguments, then p and the seed)
+            with torch.cuda.device(dev):
+                rc = lib.fa2_fwd_dropout(*(args[:8] + (h_kv,) + args[8:]), *window, _raw_stream(dev), float(dropout[0]), int(dropout[1]))
+        elif window is not None:   # sliding window: fa2_fwd_window (grouped or not: K / V addressed through the group)
             with torch.cuda.device(dev):
                 rc = lib.fa2_fwd_window(*(args[:8] + (h_kv,) + args[8:]), *window, _raw_stream(dev))
         elif h_kv != h:        # grouped-query attention: fa2_fwd_gqa (the MHA call's kernels, K / V addressed through the group)
@@ -262,8 +271,11 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias)
 
     @staticmethod
-    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None, window=None):
-        """backward() in Python (masked calls; every call when the compiled front end is absent).  window: as forward_window's."""
+    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None):
+        """backward() in Python (masked calls; every call when the compiled front end is absent).  window: as forward_window's.
+        dropout = (p, seed) of the forward: the mask is regenerated (fa2_bwd_dropout; it is keyed by the query head, so expanding grouped K / V changes nothing)."""
+        if dropout is not None and (window is None or bias is not None):
+            raise RuntimeError("fa2: the dropout backward is the windowed one (pass window=(-1, -1, 0) for full attention) and takes no bias")
         if window is not None:
             window = _fa2_lib.parse_window((window[0], window[1]), window[2])
         lib = _fa2_lib.load()
@@ -276,7 +288,7 @@ class _FlashAttnWmma:
         if h_kv != h:
             if bias is not None:
                 raise RuntimeError("fa2: the masked backward has no grouped-query form (flash_attention(mask=...) expands k / v for it)")
-            mha = _FlashAttnWmma.backward_py if window is None else (lambda *a: _FlashAttnWmma.backward_py(*a, window=window))
+            mha = _FlashAttnWmma.backward_py if window is None else (lambda *a: _FlashAttnWmma.backward_py(*a, window=window, dropout=dropout))
             return _grouped_backward(mha, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH)
         act_n, act_nkv, act_d = int(act_n), int(act_nkv), int(act_d)
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
@@ -317,6 +329,9 @@ class _FlashAttnWmma:
                 args += (ws.data_ptr(), need)
                 fn = lib.fa2_bwd_ws if bias is None else lib.fa2_bwd_bias_ws
         args += (stream,)
+        if dropout is not None:
+            args += (float(dropout[0]), int(dropout[1]))
+            fn = lib.fa2_bwd_dropout
         if Q.device.index != _current_device():
             with torch.cuda.device(Q.device):
                 rc = fn(*args)
@@ -672,27 +687,91 @@ class _WindowAttentionFunction(torch.autograd.Function):
 
 
 class _VarlenAttentionFunction(torch.autograd.Function):
-    """autograd node of flash_attention_varlen: forward = fa2_fwd_varlen (flagged FA2_FLAG_EXACT_SCALE), backward = fa2_bwd_varlen."""
+    """autograd node of flash_attention_varlen: forward = fa2_fwd_varlen (flagged FA2_FLAG_EXACT_SCALE), backward = fa2_bwd_varlen.
+    dropout = None or (p, seed): the dropout twins of the two; the node saves the seed and the backward regenerates the mask."""
 
     @staticmethod
     @torch.no_grad()
-    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, flags, scale, window):
-        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_varlen(q, k, v, cu_q, cu_k, max_q, max_k, flags | _fa2_lib.FA2_FLAG_EXACT_SCALE, scale, window)
-        ctx.args = (max_q, max_k, q.shape[2], flags, scale, window)
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, flags, scale, window, dropout=None):
+        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_varlen(q, k, v, cu_q, cu_k, max_q, max_k, flags | _fa2_lib.FA2_FLAG_EXACT_SCALE, scale, window,
+                                                                          dropout)
+        ctx.args = (max_q, max_k, q.shape[2], flags, scale, window, dropout)
         ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L, cu_q, cu_k)
         return o
 
     @staticmethod
     @torch.no_grad()
     def backward(ctx, do):
-        max_q, max_k, D, flags, scale, window = ctx.args
+        max_q, max_k, D, flags, scale, window, dropout = ctx.args
         q, k, v, o, L, cu_q, cu_k = ctx.saved_tensors
-        dQ, dK, dV = flash_attn_wmma.backward_varlen(q, k, v, o, do, L, cu_q, cu_k, max_q, max_k, D, flags, scale, window)
-        return dQ, dK, dV, None, None, None, None, None, None, None
+        dQ, dK, dV = flash_attn_wmma.backward_varlen(q, k, v, o, do, L, cu_q, cu_k, max_q, max_k, D, flags, scale, window, dropout)
+        return dQ, dK, dV, None, None, None, None, None, None, None, None
+
+
+class _DropoutAttentionFunction(torch.autograd.Function):
+    """autograd node of flash_attention(dropout_p > 0): forward = fa2_fwd_dropout, backward = fa2_bwd_dropout; saves the window, p and the seed — the
+    backward regenerates the forward's mask."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, q, k, v, causal, scale, BNHD_fmt, window, dropout):
+        D = q.shape[3]
+        Br = 32 if D > 384 else 64                      # FlashAttn.py:56-67
+        flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | _fa2_lib.FA2_FLAG_EXACT_SCALE
+        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_py(q, k, v, Br, 128, flags, scale, BNHD_fmt, window=window, dropout=dropout)
+        n_ax = 1 if BNHD_fmt else 2
+        ctx.args = (causal, scale, q.shape[n_ax], k.shape[n_ax], D, BNHD_fmt, window, dropout)
+        ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L)
+        return o
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, do):
+        causal, scale, N, Nkv, D, BNHD_fmt, window, dropout = ctx.args
+        q, k, v, o, L = ctx.saved_tensors
+        dQ, dK, dV = flash_attn_wmma.backward_py(q, k, v, o, do, L, N, Nkv, D, 128, 128, causal, scale, BNHD_fmt, window=window, dropout=dropout)
+        return dQ, dK, dV, None, None, None, None, None
+
+
+DROPOUT_MESSAGE = "fa2: dropout_p must be a number in [0, 1)"
+
+
+def _parse_dropout(dropout_p, dropout_seed):
+    """The operator's dropout arguments -> None (dropout_p == 0) or (p, seed).  Raises ValueError before any device work.  dropout_seed=None draws a
+    63-bit seed from torch's CPU default generator, so torch.manual_seed reproduces a run."""
+    try:
+        p = float(dropout_p)
+    except (TypeError, ValueError):
+        raise ValueError(DROPOUT_MESSAGE + ", got %r" % (dropout_p,))
+    if isinstance(dropout_p, bool) or not (0.0 <= p < 1.0):           # (NaN fails the comparison)
+        raise ValueError(DROPOUT_MESSAGE + ", got %r" % (dropout_p,))
+    if p == 0.0:
+        return None
+    if dropout_seed is None:
+        dropout_seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, device="cpu").item())
+    if isinstance(dropout_seed, bool) or not isinstance(dropout_seed, int) or not (0 <= dropout_seed < 2 ** 64):
+        raise ValueError("fa2: dropout_seed must be None or an int in [0, 2**64), got %r" % (dropout_seed,))
+    return (p, dropout_seed)
+
+
+def dropout_keep_mask(seed, p, B, H, Nq, Nkv):
+    """The keep mask of a dropout call as a CPU bool tensor [B, H, Nq, Nkv] (True = kept), from the library's host function fa2_dropout_keep_mask — the
+    same inline functions the kernels call (csrc/fa2_dropout.h).  For a packed call B counts the sequences and Nq / Nkv are positions inside one.
+    No GPU needed."""
+    lib = _fa2_lib.load()
+    out = torch.empty((B, H, Nq, Nkv), dtype=torch.uint8)
+    for b in range(B):
+        for h in range(H):
+            rc = lib.fa2_dropout_keep_mask(int(seed), float(p), int(H), b, h, 0, int(Nq), 0, int(Nkv), out[b, h].data_ptr())
+            if rc:
+                if rc == -9:
+                    raise ValueError(DROPOUT_MESSAGE + ", got %r" % (p,))
+                _fa2_lib.check(rc)
+    return out.bool()
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=False, scale=None, window=None,
-                           bottom_right=False):
+                           bottom_right=False, dropout_p=0.0, dropout_seed=None):
     """Packed, variable-length attention: B sequences of individual lengths in one buffer (the flash_attn_varlen_func shape).
     q [total_q, H, D], k / v [total_k, Hkv, D] (Hkv divides H: grouped K / V are not expanded); cu_seqlens_q / cu_seqlens_k: int32 [B + 1] on q's
     device, non-decreasing — sequence s owns the rows [cu[s], cu[s+1]); zero-length sequences are fine.  Returns [total_q, H, D].
@@ -702,7 +781,9 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     causal / window: per sequence, as flash_attention's (window None, an int W or (left, right); causal means right = 0).  Row i of a sequence sits at
     key position i (top-left, this library's convention) or, with bottom_right=True, at i + Nkv_s - Nq_s (other libraries' causal convention; a
     sequence with fewer keys than queries then has leading rows that see nothing).  Rows that see no key return zeros.
-    Differentiable in q, k, v (C-ABI fa2_fwd_varlen / fa2_bwd_varlen): no atomics, deterministic gradients."""
+    Differentiable in q, k, v (C-ABI fa2_fwd_varlen / fa2_bwd_varlen): no atomics, deterministic gradients.
+    dropout_p / dropout_seed: attention dropout as flash_attention's; the mask is keyed by the sequence index and the positions inside the sequence."""
+    dropout = None if dropout_p.__class__ is float and dropout_p == 0.0 else _parse_dropout(dropout_p, dropout_seed)      # (the default: no work)
     left, right, _ = _fa2_lib.parse_window(window, 0)
     h, h_kv, D = _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k)
     if max_seqlen_q is None:
@@ -713,7 +794,11 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
         scale = D ** -0.5
     flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | (_fa2_lib.FA2_FLAG_BOTTOM_RIGHT if bottom_right else 0)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        if dropout is not None:
+            return _VarlenAttentionFunction.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right), dropout)
         return _VarlenAttentionFunction.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right))
+    if dropout is not None:
+        return flash_attn_wmma.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right), dropout)[0]
     return flash_attn_wmma.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right))[0]
 
 
@@ -732,7 +817,7 @@ def _band_mask(nq, nkv, window, causal, device):
     return keep
 
 
-def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False, window=None, q_offset=0):
+def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False, window=None, q_offset=0, dropout_p=0.0, dropout_seed=None):
     """Forward attention that HONOURS `mask` — the extension the reference lists as to do (README.md:45; its
     FlashAttentionFunction accepts the argument and ignores it, FlashAttn.py:49, :74, and `FlashAttentionFunction.apply` here
     keeps doing exactly that so that existing call sites see no change).  `mask` follows
@@ -744,7 +829,32 @@ def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False
     query row i sits at key position i + q_offset and attends the keys [i + q_offset - left, i + q_offset + right]; `causal` then means right = 0
     (causal=True, window=(W - 1, 0): W keys ending at the query's own; q_offset = Nkv - Nq: new queries against a longer KV cache).  The kernels
     sweep only the tiles of the band (C-ABI fa2_fwd_window / fa2_bwd_window: no [Nq, Nkv] mask in memory, grouped k / v without expansion); rows
-    that see no key return zeros.  With a `mask` as well the band is folded into it and the masked path runs.  window=None, q_offset=0: as before."""
+    that see no key return zeros.  With a `mask` as well the band is folded into it and the masked path runs.  window=None, q_offset=0: as before.
+
+    `dropout_p` / `dropout_seed`: attention dropout, the dropout_p of scaled_dot_product_attention.  Each probability is dropped after the softmax with
+    probability p_eff = round(p * 65536) / 65536 and the kept ones are scaled by 1 / (1 - p_eff); the mask is generated in-kernel (Philox4x32-10 keyed by
+    the seed: csrc/fa2_dropout.h has the contract, dropout_keep_mask() returns it on the CPU) and regenerated by the backward, so no [Nq, Nkv] tensor
+    exists.  It applies whenever dropout_p > 0, whatever the grad mode (as SDPA); dropout_p == 0 takes exactly the path it takes without the argument.
+    dropout_seed=None draws a seed from torch's CPU default generator (torch.manual_seed reproduces a run).  Works with causal, window, q_offset and
+    grouped k / v (C-ABI fa2_fwd_dropout / fa2_bwd_dropout, every head dim up to 512).  Limits: the seed is a host value, so a call captured in a
+    graph replays the same mask; `mask=` together with dropout_p > 0 is not supported (ValueError)."""
+    dropout = None if dropout_p.__class__ is float and dropout_p == 0.0 else _parse_dropout(dropout_p, dropout_seed)      # (the default: no work)
+    if dropout is not None:
+        if mask is not None:
+            raise ValueError("fa2: flash_attention(mask=..., dropout_p > 0) is not supported: dropout runs on the unmasked / windowed kernels only")
+        win = _fa2_lib.parse_window(window if window is not None else (-1, -1), q_offset)
+        if not (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)) or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+            raise RuntimeError("fa2: q, k, v must be 4-D ([B,H,N,D] or [B,N,H,D] with BNHD_fmt)")
+        if not q.is_cuda or not k.is_cuda or not v.is_cuda:
+            raise RuntimeError("fa2: q, k, v must be on a ROCm device (no CPU path in this operator)")
+        D = q.shape[3]
+        if scale is None:
+            scale = D ** -0.5
+        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+            return _DropoutAttentionFunction.apply(q, k, v, bool(causal), scale, BNHD_fmt, win, dropout)
+        Br = 32 if D > 384 else 64                      # FlashAttn.py:56-67
+        flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | _fa2_lib.FA2_FLAG_EXACT_SCALE
+        return flash_attn_wmma.forward_py(q, k, v, Br, 128, flags, scale, BNHD_fmt, window=win, dropout=dropout)[0]
     if window is not None or q_offset != 0:
         win = _fa2_lib.parse_window(window, q_offset)
         if mask is not None:

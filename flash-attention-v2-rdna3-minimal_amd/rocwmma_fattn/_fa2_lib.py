@@ -90,6 +90,17 @@ SYMBOLS = {
     "fa2_fwd_varlen_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p, _i64p, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.POINTER(FwdPlan)]),
     "fa2_varlen_tile_range": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_varlen_row_range": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    # attention dropout: the windowed / packed argument lists, then (float dropout_p, uint64_t seed); and the host side of the mask contract
+    "fa2_fwd_dropout": (ctypes.c_int, [ctypes.c_int] + _FWD_ARGTYPES[:7] + [ctypes.c_int] + _FWD_ARGTYPES[7:-1] + [ctypes.c_int] * 3 + [ctypes.c_void_p] +
+                        [ctypes.c_float, ctypes.c_uint64]),
+    "fa2_bwd_dropout": (ctypes.c_int, [ctypes.c_int] + _BWD_ARGTYPES[:-1] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_uint64]),
+    "fa2_fwd_varlen_dropout": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 2 + [_i64p] * 4 +
+                               [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_uint64]),
+    "fa2_bwd_varlen_dropout": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [_i64p] * 8 +
+                               [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_uint64]),
+    "fa2_dropout_keep_mask": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 4 + [ctypes.c_void_p]),
+    "fa2_dropout_threshold": (ctypes.c_int, [ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
+    "fa2_philox4x32_10": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)] * 3),
     "fa2_set_option": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "fa2_get_option": (ctypes.c_int, [ctypes.c_char_p]),
     "fa2_error_string": (ctypes.c_char_p, [ctypes.c_int]),

@@ -77,6 +77,7 @@ extern "C" {
 #define FA2_ERR_SCALE         -6   /* scale is NaN/inf */
 #define FA2_ERR_GRID          -7   /* B*H*ceil(Nq/256) exceeds the 2^31-1 grid limit */
 #define FA2_ERR_BIAS          -8   /* unknown bias_kind or a negative bias stride */
+#define FA2_ERR_DROPOUT       -9   /* dropout_p < 0, >= 1 or NaN (the dropout entry points) */
 
 /* bias_kind codes for fa2_fwd_bias */
 #define FA2_BIAS_NONE     0   /* no bias: the call is fa2_fwd */
@@ -399,6 +400,67 @@ int fa2_varlen_tile_range(int Nq_s, int Nkv_s, int window_left, int window_right
                           int row0, int rows, int tile, int* first_tile, int* ntiles);
 int fa2_varlen_row_range(int Nq_s, int Nkv_s, int window_left, int window_right, int flags,
                          int key0, int keys, int tile, int* first_tile, int* ntiles);
+
+/*
+ * Attention dropout: the windowed and the packed entry points with a dropout probability and a seed.
+ *   fa2_fwd_dropout / fa2_bwd_dropout               fa2_fwd_window's / fa2_bwd_window's argument lists, then float dropout_p, uint64_t seed
+ *   fa2_fwd_varlen_dropout / fa2_bwd_varlen_dropout  fa2_fwd_varlen's / fa2_bwd_varlen's argument lists, then the same two
+ * Everything those entry points document holds (window_left = window_right = -1, q_offset = 0 is full attention; grouped K / V in the forward, the
+ * multi-head backward; layouts; validation), except that these calls always run the dropout kernels (FA2_DROP forms of the compiler-scheduled windowed /
+ * packed kernels, every head dim up to 512), whatever the window masks.
+ * The mask (csrc/fa2_dropout.h has the contract in full).  Whether the probability at (b, h, i, j) — batch or sequence b, QUERY head h, row i, key j, the
+ * latter two counted inside the sequence — is kept is a pure function of (seed, b * H + h, i, j) and the threshold: Philox4x32-10 keyed by the seed,
+ * counter { call(j), i, b * H + h, 0 }, sixteen bits per element, dropped when they are < t = round(dropout_p * 65536) (clamped to 65535).  So
+ * p_eff = t / 65536 and the kept probabilities are scaled by 1 / (1 - p_eff).  It does not depend on tile sizes, option "rows", head dim, dtype, layout,
+ * grouped or expanded K / V, or the pass: the backward regenerates the forward's mask from the same seed.
+ * Numerics.  The softmax state is untouched: the row sum and the LSE are those of the undropped probabilities (the LSE of a dropout call is the LSE of the
+ * same call without dropout).  O = (sum_j keep P16 V) / l / (1 - p_eff); dV = (keep o P16)^T dO / (1 - p_eff); dP = keep o (dO V^T) / (1 - p_eff),
+ * dS = P o (dP - delta), delta = rowsum(dO o O).  Contract 0 (f32 scale of the product); a row that sees no key returns zeros.
+ * dropout_p == 0 keeps everything.  dropout_p < 0, >= 1 or NaN: FA2_ERR_DROPOUT, reported before anything else is looked at.
+ * The seed is a host value: a call captured in a graph replays the same mask.
+ */
+int fa2_fwd_dropout(int dtype,
+                    const void* q, const void* k, const void* v, void* o, float* lse,
+                    int B, int H, int Hkv, int Nq, int Nkv, int D,
+                    const int64_t q_strides[3], const int64_t k_strides[3],
+                    const int64_t v_strides[3], const int64_t o_strides[3],
+                    const int64_t lse_strides[2],
+                    float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream,
+                    float dropout_p, uint64_t seed);
+int fa2_bwd_dropout(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                    void* dq, void* dk, void* dv, float* delta_ws,
+                    int B, int H, int Nq, int Nkv, int D,
+                    const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                    const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                    const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2],
+                    float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream,
+                    float dropout_p, uint64_t seed);
+int fa2_fwd_varlen_dropout(int dtype,
+                           const void* q, const void* k, const void* v, void* o, float* lse,
+                           int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D,
+                           const int* cu_seqlens_q, const int* cu_seqlens_k,
+                           const int64_t q_strides[2], const int64_t k_strides[2],
+                           const int64_t v_strides[2], const int64_t o_strides[2],
+                           int64_t lse_stride,
+                           float scale, int flags, int window_left, int window_right, void* hip_stream,
+                           float dropout_p, uint64_t seed);
+int fa2_bwd_varlen_dropout(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                           void* dq, void* dk, void* dv, float* delta_ws,
+                           int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                           const int* cu_seqlens_q, const int* cu_seqlens_k,
+                           const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2],
+                           const int64_t o_strides[2], const int64_t do_strides[2], const int64_t dq_strides[2],
+                           const int64_t dk_strides[2], const int64_t dv_strides[2], int64_t lse_stride,
+                           float scale, int flags, int window_left, int window_right, void* hip_stream,
+                           float dropout_p, uint64_t seed);
+/* Host-only (no GPU needed).  fa2_dropout_keep_mask: mask[(i - i0) * (j1 - j0) + (j - j0)] = 1 where the element (b, h, i, j) is kept, 0 where it is
+ * dropped, for the rectangle [i0, i1) x [j0, j1) of one (b, h) of a call with H query heads.  FA2_ERR_NULL_POINTER, FA2_ERR_BAD_SHAPE (negative or
+ * empty ranges, b / h out of range), FA2_ERR_DROPOUT.
+ * fa2_dropout_threshold: t of dropout_p (the return value, or FA2_ERR_DROPOUT), and p_eff = t / 65536 (p_eff may be NULL).
+ * fa2_philox4x32_10: the generator itself, out = Philox4x32-10(ctr, key). */
+int fa2_dropout_keep_mask(uint64_t seed, float dropout_p, int H, int b, int h, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint8_t* mask);
+int fa2_dropout_threshold(float dropout_p, float* p_eff);
+int fa2_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
