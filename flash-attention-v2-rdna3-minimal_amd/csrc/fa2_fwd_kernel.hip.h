@@ -165,18 +165,24 @@ __host__ __device__ inline Window get_window(const P& p) {
     w.left = (int)p.bs[0]; w.right = (int)p.bs[1]; w.off = (int)p.bs[2];
     return w;
 }
+// Packed (variable-length) calls have neither bias nor split workspace: cu_seqlens_q travels in `bias`, cu_seqlens_k in `ws` (same reason, same rule:
+// host.cpp writes them with set_varlen, the FA2_VARLEN kernels read them with get_varlen, nobody else casts these fields)
+struct VarlenPtrs { const int* cu_q; const int* cu_k; };
+template <typename P>
+__host__ __device__ inline void set_varlen(P& p, const int* cu_q, const int* cu_k) { p.bias = cu_q; p.ws = (float*)const_cast<int*>(cu_k); }
+template <typename P>
+__host__ __device__ inline VarlenPtrs get_varlen(const P& p) { return {(const int*)p.bias, (const int*)p.ws}; }
 
 #if FA2_VARLEN
 // Packed (variable-length) attention (fa2_fwd_varlen / fa2_bwd_varlen; include/fa2_gfx950.h has the contract).  A varlen call has neither bias nor split
-// workspace: cu_seqlens_q travels in `bias`, cu_seqlens_k in `ws`, and the bottom-right flag where the window's offset would be.  The host passes batch
+// workspace: cu_seqlens_q / cu_seqlens_k travel in `bias` / `ws` (set_varlen above), and the bottom-right flag where the window's offset would be.  The host passes batch
 // strides of 0, Nq / Nkv = the stated maxima (they size the grid) and B = the number of sequences; the workgroup of sequence s then turns its copy of the
 // parameter block into the windowed call on that sequence alone: base pointers moved to the sequence's first row, Nq / Nkv and the band's offset its own,
 // and every buffer descriptor ending at the last row OF THE SEQUENCE, so that rows past it read zeros and a neighbour's rows are never fetched.
 struct VarlenSeq { int q_base, k_base, Nq, Nkv; };
 template <typename P>
 __device__ __forceinline__ VarlenSeq varlen_seq(const P& p, int s) {       // (s is workgroup-uniform: four scalar loads)
-    const int* cq = (const int*)p.bias;
-    const int* ck = (const int*)p.ws;
+    const int *cq = get_varlen(p).cu_q, *ck = get_varlen(p).cu_k;
     VarlenSeq v;
     v.q_base = cq[s]; v.k_base = ck[s];
     v.Nq = cq[s + 1] - v.q_base; v.Nkv = ck[s + 1] - v.k_base;

@@ -182,7 +182,7 @@ FA2_HIDDEN int launch_fwd_window_bf16(int HD, const FwdParams& p, int rows, hipS
 FA2_HIDDEN int launch_bwd_window_f16(int HD, const BwdParams& p, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_window_bf16(int HD, const BwdParams& p, hipStream_t stream);
 // packed, variable-length attention (varlen_hip.cpp): the same launchers over the VARLEN forms; p.Nq / p.Nkv = the stated maximum lengths, p.B = the number
-// of sequences, batch strides 0, cu_seqlens_q / cu_seqlens_k in p.bias / p.ws, the window's offset field = the bottom-right flag
+// of sequences, batch strides 0, cu_seqlens_q / cu_seqlens_k in p.bias / p.ws (set_varlen / get_varlen), the window's offset field = the bottom-right flag
 FA2_HIDDEN int launch_fwd_varlen_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
 FA2_HIDDEN int launch_fwd_varlen_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_varlen_f16(int HD, const BwdParams& p, hipStream_t stream);
@@ -204,6 +204,26 @@ FA2_HIDDEN int launch_bwd_varlen_dropout_bf16(int HD, const BwdParams& p, hipStr
 // dkv16: likewise the dK / dV pass (csrc/gen/bwd_dkv_m16_gen.py)
 FA2_HIDDEN int launch_bwd_d128(bool bf16, const BwdParams& p, bool causal, int parts, bool neg_delta, bool kfold, hipStream_t stream, bool dq16 = false,
                                bool dkv16 = false);
+
+// ---- the launcher of a family for a dtype known at run time (host.cpp; the windowed / packed / dropout families go through its table)
+inline int launch_fwd_hip(bool bf16, int HD, const FwdParams& p, bool causal, int rows, bool bias, hipStream_t stream) {
+    return bf16 ? launch_fwd_hip_bf16(HD, p, causal, rows, bias, stream) : launch_fwd_hip_f16(HD, p, causal, rows, bias, stream);
+}
+inline int launch_fwd_short(bool bf16, int HD, const FwdParams& p, hipStream_t stream) {
+    return bf16 ? launch_fwd_short_bf16(HD, p, stream) : launch_fwd_short_f16(HD, p, stream);
+}
+inline int launch_fwd_combine(bool bf16, int HD, const FwdParams& p, hipStream_t stream) {
+    return bf16 ? launch_fwd_combine_bf16(HD, p, stream) : launch_fwd_combine_f16(HD, p, stream);
+}
+inline int launch_bwd_hip(bool bf16, int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream) {
+    return bf16 ? launch_bwd_hip_bf16(HD, p, causal, parts, stream) : launch_bwd_hip_f16(HD, p, causal, parts, stream);
+}
+inline int launch_bwd_short_dq(bool bf16, int HD, const BwdParams& p, bool neg_delta, hipStream_t stream) {
+    return bf16 ? launch_bwd_short_dq_bf16(HD, p, neg_delta, stream) : launch_bwd_short_dq_f16(HD, p, neg_delta, stream);
+}
+inline int launch_bwd_bias_hip(bool bf16, int HD, const BwdParams& p, bool causal, hipStream_t stream) {
+    return bf16 ? launch_bwd_bias_hip_bf16(HD, p, causal, stream) : launch_bwd_bias_hip_f16(HD, p, causal, stream);
+}
 
 constexpr int kBwdAsmParts = 3;      // passes the hand-scheduled backward covers: bit 0 = dQ, bit 1 = dK / dV
 

@@ -1,6 +1,11 @@
 // host.cpp — C-ABI shim of the gfx950 FlashAttention-2 path (compiled with hipcc -x hip): argument validation, launch
 // heuristics and dispatch.  The kernels live in the other translation units of the library (fa2_launch.h).
 //
+// Layout of the file: the planner (which kernels serve a launch: plan_range, plan_split, plan_fwd) and the launch steps (launch_fwd, launch_bwd);
+// the call descriptions FwdCall / BwdCall, which every extern "C" entry point fills by field name; validation (a description -> FwdParams /
+// BwdParams + the kernel head dim, or an error code); fwd_run / bwd_run (validate, then answer the plan / size query or launch); the helpers the
+// entry points of one family share (dense_window, packed_call, run_query / workspace_query); the entry points.
+//
 // Counterpart of the reference's host layer:
 //   rocwmma_fattn/host.cpp:30-45        dtype switch forward()        -> fa2_fwd
 //   rocwmma_fattn/kernel_fp16.cu:744-876 forward_fp16 host launcher   -> fa2_fwd_f16
@@ -19,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "fa2_gfx950.h"
 
@@ -66,7 +72,9 @@ constexpr int kNumHeadDims = sizeof(kHeadDims) / sizeof(kHeadDims[0]);
 constexpr int kFwdRows = 256;         // Q rows per forward workgroup of the default shapes
 
 int forced_rows() { return fa2::options().rows.load(std::memory_order_relaxed); }
-bool asm_fwd() { return fa2::options().asm_mask.load(std::memory_order_relaxed) & 1; }
+int asm_mask() { return fa2::options().asm_mask.load(std::memory_order_relaxed); }
+int m16_mode() { return fa2::fwd_m16_mode(asm_mask()); }      // which 16x16x32 forward bodies option "asm" allows (fa2_launch.h)
+bool asm_fwd() { return asm_mask() & 1; }
 
 // A grid of 256-row workgroups that covers well under half of the CUs leaves the chip idle: 128-row workgroups double the
 // number of busy CUs at the price of staging every K/V tile for half as many rows.  Measured (tools/rows_probe.py, MI355X, 256 CUs):
@@ -134,7 +142,7 @@ bool asm_q_span_ok(const fa2::FwdParams& p, bool any_pitch = false) {
 // 0.96 0.89 1.07 (bf16 alike) — the hand-scheduled body from N = 1792 (profiles/r06_asm_kv_ab.txt).  Option "asm" bit 5 and option "rows" = 256 ignore this rule (A/B measurements, tests).
 bool asm_folds(bool bf16, const fa2::FwdParams& p);
 bool asm_kv_len_ok(int HD, bool bf16, const fa2::FwdParams& p, bool causal) {
-    if ((fa2::options().asm_mask.load(std::memory_order_relaxed) & 32) || forced_rows() == 256) return true;     // (option rows = 256 pins the
+    if ((asm_mask() & 32) || forced_rows() == 256) return true;     // (option rows = 256 pins the
     if (causal) return p.Nkv >= 1792;                                                                              //  hand-scheduled kernels: tests)
     // Round 5, re-measured with the 16x16x32 bodies (tools/asm_kv_ab.py, profiles/r18_asm_kv_ab.txt; HIP time / hand-scheduled time at Nkv = 256, 512,
     // 768, 1024, 1536): D = 128 fp16 0.90 1.01 1.07 1.11 1.16, bf16 0.91 1.01 1.05 1.07 1.09 -> from 512 on; D = 64 fp16 (folded) 0.82 0.92 0.99 1.03
@@ -164,14 +172,13 @@ bool short_kv_ok(int HD, const fa2::FwdParams& p, bool causal) {
 
 // A head dim below the body's that the 16x16x32 bodies take (see plan_range)
 bool asm_trimmed(int HD, bool bf16, const fa2::FwdParams& p, bool fold) {
-    const int m16_mode = fa2::fwd_m16_mode(fa2::options().asm_mask.load(std::memory_order_relaxed));
 #ifndef FA2_TRIM_MIN64       // (developer A/B: tools/kbench.py build NAME:-DFA2_TRIM_MIN64=32,-DFA2_TRIM_MIN128=80,only=host)
 #define FA2_TRIM_MIN64 40
 #endif
 #ifndef FA2_TRIM_MIN128
 #define FA2_TRIM_MIN128 88      // (B2 H16 N4096 fp16, same file: D = 72 +4 %, 80 +2 %, 88 +7 %, 96 +6 %; D = 24 / 32 on the 64 body: -1 %)
 #endif
-    return p.D < HD && p.D >= (HD == 64 ? FA2_TRIM_MIN64 : fold ? FA2_TRIM_MIN128 : 104) && fa2::fwd_asm_m16_kind(HD, bf16, p, fold, m16_mode) != fa2::kM16None;
+    return p.D < HD && p.D >= (HD == 64 ? FA2_TRIM_MIN64 : fold ? FA2_TRIM_MIN128 : 104) && fa2::fwd_asm_m16_kind(HD, bf16, p, fold, m16_mode()) != fa2::kM16None;
 }
 
 // Head dim exactly 256 (round 6): the hand-scheduled 128-row kernel (fa2_fwd_d256.hip.h; option "asm" bit 10).  It scales the f32 product and adds the
@@ -180,7 +187,7 @@ bool asm_trimmed(int HD, bool bf16, const fa2::FwdParams& p, bool fold) {
 // addressed with 32-bit offsets from the head base; short KV sweeps stay on the 8-wave kernels (two waves per SIMD hide each other's prologue).
 bool asm_d256_ok(bool bf16, const fa2::FwdParams& p, bool causal) {
     (void)bf16;
-    const int mask = fa2::options().asm_mask.load(std::memory_order_relaxed);
+    const int mask = asm_mask();
 #ifndef FA2_D256_TRIM_MIN      // (developer A/B: tools/kbench.py build NAME:-DFA2_D256_TRIM_MIN=144,only=host)
 #define FA2_D256_TRIM_MIN 136
 #endif
@@ -197,10 +204,9 @@ bool asm_d256_ok(bool bf16, const fa2::FwdParams& p, bool causal) {
     return (mask & 32) || p.Nkv >= (causal ? 1024 : 512);
 }
 
-RangePlan plan_range(int HD, bool bf16, const fa2::FwdParams& p, bool causal) {
-    if (HD == 256 && asm_d256_ok(bf16, p, causal)) return {FA2_KERNEL_ASM, FA2_CONTRACT_LSUM_P16, 128, false};
-    if (short_kv_ok(HD, p, causal)) return {FA2_KERNEL_HIP_128, 0, 128, false, true};
-    const int rows = pick_rows(p, causal);
+// Launches the hand-scheduled persistent kernels of head dims 128 and 64 can take, the workgroup shape aside (plan_range adds the rows checks): the
+// one eligibility predicate — plan_range asks it for the launch at hand, plan_split / plan_fwd for the non-causal rounds beside the parts of a split.
+bool asm_eligible(int HD, bool bf16, const fa2::FwdParams& p, bool causal) {
     // Head dim exactly 128 with a positive scale: the hand-scheduled 4-wave kernel (256-row workgroups).  Head dim 64 has its generated
     // body too (same generator, half the MFMAs per tile for the same softmax work, row sums on the matrix pipe), but a lone wave per SIMD
     // issues that VALU-bound mix no faster than the two waves of the compiler-scheduled 8-wave kernel: same box (tools/fwd_ab.py) B2 H16
@@ -209,8 +215,7 @@ RangePlan plan_range(int HD, bool bf16, const fa2::FwdParams& p, bool causal) {
     // (round 3) the body that folds the scale into Q beats the 8-wave kernel non-causal too (+9 %), so every launch that folds takes it.
     const bool fold = asm_folds(bf16, p);
     // (round 5: and every launch the f32-scale 16x16x32 body with the row sums on the matrix pipe takes: calls that are not flagged FA2_FLAG_EXACT_SCALE)
-    const bool d64_asm = HD == 64 && (causal || fold || (fa2::options().asm_mask.load(std::memory_order_relaxed) & 16) ||
-                                      fa2::fwd_asm_m16_kind(HD, bf16, p, fold, fa2::fwd_m16_mode(fa2::options().asm_mask.load(std::memory_order_relaxed))) == fa2::kM16F32Lm);
+    const bool d64_asm = HD == 64 && (causal || fold || (asm_mask() & 16) || fa2::fwd_asm_m16_kind(HD, bf16, p, fold, m16_mode()) == fa2::kM16F32Lm);
     // Head dims BELOW the body's (round 5; the 16x16x32 bodies only): the padded columns of the Q / K / V images are zero-filled by the LDS-DMA itself (a
     // granule the row does not have gets a source offset beyond the descriptor) and the piece offsets take their general form, so any row pitch goes.
     // The body runs at D / HD of its rate: it takes the head dims where that still beats the trimmed compiler-scheduled kernels
@@ -218,12 +223,22 @@ RangePlan plan_range(int HD, bool bf16, const fa2::FwdParams& p, bool causal) {
     // causal +5.8 %, D = 96 +6.5 %, D = 104 .. 120 +19 .. 20 %, D = 112 causal +13 %; bf16 (f32 scale) D = 112 +14 %, D = 96 causal -8.7 %: the folded
     // bodies from 40 / 88 on, the f32-scale ones from 104 on.
     const bool trimmed = asm_trimmed(HD, bf16, p, fold);
-    if ((HD == 128 || d64_asm) && (p.D == HD || trimmed) && !p.negate_q && asm_fwd() && rows == 256 && pick_rows(p) == 256 && asm_q_span_ok(p, trimmed) &&
-        (trimmed || asm_pitch_ok(p.ks[2], HD)) && asm_kv_len_ok(HD, bf16, p, causal)) {
-        // (the folded bodies built on v_mfma_f32_16x16x32 add the rounded P into the row sums — on the matrix pipe; csrc/gen/fwd_m16_gen.py, opt=lm)
-        const bool lsum16 = fa2::fwd_asm_lsum16(HD, bf16, p, fold, fa2::fwd_m16_mode(fa2::options().asm_mask.load(std::memory_order_relaxed)));
-        return {FA2_KERNEL_ASM, (fold ? FA2_CONTRACT_PRESCALE_Q : 0) | (lsum16 ? FA2_CONTRACT_LSUM_P16 : 0), 256, fold};
-    }
+    return (HD == 128 || d64_asm) && (p.D == HD || trimmed) && !p.negate_q && asm_fwd() && asm_q_span_ok(p, trimmed) &&
+           (trimmed || asm_pitch_ok(p.ks[2], HD)) && asm_kv_len_ok(HD, bf16, p, causal);
+}
+
+// the hand-scheduled body's plan: which contract a launch that folds / does not fold the scale runs under
+RangePlan asm_range(int HD, bool bf16, const fa2::FwdParams& p, bool fold) {
+    // (the folded bodies built on v_mfma_f32_16x16x32 add the rounded P into the row sums — on the matrix pipe; csrc/gen/fwd_m16_gen.py, opt=lm)
+    const bool lsum16 = fa2::fwd_asm_lsum16(HD, bf16, p, fold, m16_mode());
+    return {FA2_KERNEL_ASM, (fold ? FA2_CONTRACT_PRESCALE_Q : 0) | (lsum16 ? FA2_CONTRACT_LSUM_P16 : 0), 256, fold};
+}
+
+RangePlan plan_range(int HD, bool bf16, const fa2::FwdParams& p, bool causal) {
+    if (HD == 256 && asm_d256_ok(bf16, p, causal)) return {FA2_KERNEL_ASM, FA2_CONTRACT_LSUM_P16, 128, false};
+    if (short_kv_ok(HD, p, causal)) return {FA2_KERNEL_HIP_128, 0, 128, false, true};
+    const int rows = pick_rows(p, causal);
+    if (asm_eligible(HD, bf16, p, causal) && rows == 256 && pick_rows(p) == 256) return asm_range(HD, bf16, p, asm_folds(bf16, p));
     return {rows == 256 ? FA2_KERNEL_HIP_256 : FA2_KERNEL_HIP_128, 0, rows, false};
 }
 
@@ -232,19 +247,9 @@ int launch_range(int HD, bool bf16, const fa2::FwdParams& p, bool causal, hipStr
     // option "asm" bit 6 (default): head dim 128 launches of whole items take the bodies built on v_mfma_f32_16x16x32 (round 5; fwd_asm.cpp)
     if (r.kernel == FA2_KERNEL_ASM && HD == 256) return fa2::launch_fwd_asm_d256(bf16, p, causal, stream);
     if (r.kernel == FA2_KERNEL_ASM)
-        return fa2::launch_fwd_asm(HD, bf16, p, causal, r.fold, stream, fa2::fwd_m16_mode(fa2::options().asm_mask.load(std::memory_order_relaxed)));
-    if (r.short_kv) return bf16 ? fa2::launch_fwd_short_bf16(HD, p, stream) : fa2::launch_fwd_short_f16(HD, p, stream);
-    return bf16 ? fa2::launch_fwd_hip_bf16(HD, p, causal, r.rows, false, stream) : fa2::launch_fwd_hip_f16(HD, p, causal, r.rows, false, stream);
-}
-
-// non-causal launches the hand-scheduled persistent kernels take: head dim 128, and head dim 64 when the launch folds the scale (plan_range)
-bool asm_noncausal_ok(int HD, bool bf16, const fa2::FwdParams& p) {
-    const bool fold = asm_folds(bf16, p);
-    const bool d64 = HD == 64 && (fold || (fa2::options().asm_mask.load(std::memory_order_relaxed) & 16) ||
-                                  fa2::fwd_asm_m16_kind(HD, bf16, p, fold, fa2::fwd_m16_mode(fa2::options().asm_mask.load(std::memory_order_relaxed))) == fa2::kM16F32Lm);
-    const bool trimmed = asm_trimmed(HD, bf16, p, fold);
-    return (HD == 128 || d64) && (p.D == HD || trimmed) && !p.negate_q && asm_fwd() && asm_q_span_ok(p, trimmed) && (trimmed || asm_pitch_ok(p.ks[2], HD)) &&
-           asm_kv_len_ok(HD, bf16, p, false);
+        return fa2::launch_fwd_asm(HD, bf16, p, causal, r.fold, stream, m16_mode());
+    if (r.short_kv) return fa2::launch_fwd_short(bf16, HD, p, stream);
+    return fa2::launch_fwd_hip(bf16, HD, p, causal, r.rows, false, stream);
 }
 
 // KV-split tail (fa2_fwd_ws).  B*H*ceil(Nq/256) equal workgroups on the CUs take ceil(x / CUs) rounds however empty the last one is: SDXL's
@@ -264,7 +269,8 @@ fa2::SplitPlan plan_split(const fa2::FwdParams& p, int HD, bool bf16, bool causa
     const int64_t items = (int64_t)p.nbh * ((p.Nq + kFwdRows - 1) / kFwdRows);
     const int nt = (p.Nkv + fa2::kKvTile - 1) / fa2::kKvTile;
     // whole rounds on the hand-scheduled persistent kernel (head dim 128; head dim 64 in fp16): the parts need a launch of their own
-    const bool asm_rounds = asm_noncausal_ok(HD, bf16, p);
+    // (non-causal launches the hand-scheduled persistent kernels take: head dim 128, and head dim 64 when the launch folds the scale — asm_eligible)
+    const bool asm_rounds = asm_eligible(HD, bf16, p, false);
     // (round 6) ... and EVERY item of a grid that covers at most half of the CUs over a long sweep — a decode-sized call: B1 H32 Nq1 Nkv8192 is 32
     // workgroups streaming 134 MB of K / V, 147 us for 30 us of bytes (plan_tail_split, underfilled; the parts run on the 8-wave kernel: plan_fwd)
     return fa2::plan_tail_split(items, nt, 0.9 * HD / 64.0, asm_rounds ? 14.0 : 10.0, fa2::split_ws_bytes(1, 1, HD), fa2::device_cus(), true);
@@ -287,15 +293,12 @@ FwdPlan plan_fwd(int HD, bool bf16, const fa2::FwdParams& p0, bool causal, bool 
             fa2::FwdParams p = p0;
             p.rows_hint = 256;
             f.split = pl;
-            f.split_asm = asm_noncausal_ok(HD, bf16, p) && pick_rows(p, causal) == 256 &&
+            f.split_asm = asm_eligible(HD, bf16, p, false) && pick_rows(p, causal) == 256 &&
                           // (a grid of parts only — plan_split, underfilled: the persistent kernel where a part sweeps at least 24 tiles, else the 8-wave
                           //  kernel, whose prologue is shorter.  Same box, hand-scheduled / 8-wave parts: B1 H8 N4096 D128, 2 parts of 32 tiles, 67.6 / 78.5 us,
                           //  D40 44.5 / 48.3, bf16 D64 48.7 / 53.3; B1 H4 N2048 D128, 4 x 8 tiles, 29.2 / 27.5; B1 H32 Nq1 Nkv8192, 8 x 16, 48.4 / 44.9)
                           (pl.full_items > 0 || ((p.Nkv + fa2::kKvTile - 1) / fa2::kKvTile) / pl.nsplit >= 24);
-            const bool fold = f.split_asm && asm_folds(bf16, p);
-            const bool lsum16 = f.split_asm && fa2::fwd_asm_lsum16(HD, bf16, p, fold, fa2::fwd_m16_mode(fa2::options().asm_mask.load(std::memory_order_relaxed)));
-            f.main = f.split_asm ? RangePlan{FA2_KERNEL_ASM, (fold ? FA2_CONTRACT_PRESCALE_Q : 0) | (lsum16 ? FA2_CONTRACT_LSUM_P16 : 0), 256, fold}
-                                 : RangePlan{FA2_KERNEL_HIP_256, 0, 256, false};
+            f.main = f.split_asm ? asm_range(HD, bf16, p, asm_folds(bf16, p)) : RangePlan{FA2_KERNEL_HIP_256, 0, 256, false};
             return f;
         }
     }
@@ -330,12 +333,12 @@ int launch_fwd(int HD, bool bf16, const fa2::FwdParams& p0, bool causal, hipStre
             // the hand-scheduled persistent kernel: every workgroup works through its whole items, then its parts (the item seam hides a
             // part's load phase like any other item's; the block stores a part's f32 tile itself)
             p.item_cap = f.split.full_items + f.split.split_items * f.split.nsplit;
-            rc = fa2::launch_fwd_asm(HD, bf16, p, false, f.main.fold, stream, fa2::fwd_m16_mode(fa2::options().asm_mask.load(std::memory_order_relaxed)));
+            rc = fa2::launch_fwd_asm(HD, bf16, p, false, f.main.fold, stream, m16_mode());
         } else {
-            rc = bf16 ? fa2::launch_fwd_hip_bf16(HD, p, false, 256, false, stream) : fa2::launch_fwd_hip_f16(HD, p, false, 256, false, stream);
+            rc = fa2::launch_fwd_hip(bf16, HD, p, false, 256, false, stream);
         }
         if (rc) return rc;
-        return bf16 ? fa2::launch_fwd_combine_bf16(HD, p, stream) : fa2::launch_fwd_combine_f16(HD, p, stream);
+        return fa2::launch_fwd_combine(bf16, HD, p, stream);
     }
     if (f.main_heads < p0.nbh) {
         fa2::FwdParams p = p0;
@@ -352,7 +355,7 @@ int launch_fwd(int HD, bool bf16, const fa2::FwdParams& p0, bool causal, hipStre
 // Head dim exactly 128 runs the hand-scheduled backward kernels (fa2_bwd_d128.hip.h) unless option "asm" bit 1 is cleared; bits 2 / 3 of
 // the option take only the dQ pass / only the dK-dV pass off them (A/B measurements of one pass at a time).
 int launch_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal, hipStream_t stream) {
-    const int m = fa2::options().asm_mask.load(std::memory_order_relaxed);
+    const int m = asm_mask();
     const int want = fa2::options().bwd_parts.load(std::memory_order_relaxed);      // 3 unless a profiling run asked for one pass only
     int asm_parts = 0;
     if (HD == 128 && p.D == 128 && (m & 2)) asm_parts = 3 & ~((m >> 2) & 3) & fa2::kBwdAsmParts;
@@ -383,9 +386,9 @@ int launch_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal, hipStrea
         int rc;
         // (round 6) the dQ pass of a non-causal sweep of at most two KV tiles — cross-attention — is the short-sweep kernel's (fa2_bwd_short.hip.h;
         //  option "short"; option "rows" pins the streaming passes); it leaves delta in the sign the dK / dV pass that follows takes
-        if (part == 1 && short_dq) rc = bf16 ? fa2::launch_bwd_short_dq_bf16(HD, p, neg_delta, stream) : fa2::launch_bwd_short_dq_f16(HD, p, neg_delta, stream);
+        if (part == 1 && short_dq) rc = fa2::launch_bwd_short_dq(bf16, HD, p, neg_delta, stream);
         else if (asm_parts & part) rc = fa2::launch_bwd_d128(bf16, p, causal, part, neg_delta, kfold, stream, (m & 128) != 0, (m & 256) != 0);     // option "asm" bits 7 / 8: the 16x16x32 dQ / dK-dV pass
-        else rc = bf16 ? fa2::launch_bwd_hip_bf16(HD, p, causal, part, stream) : fa2::launch_bwd_hip_f16(HD, p, causal, part, stream);
+        else rc = fa2::launch_bwd_hip(bf16, HD, p, causal, part, stream);
         if (rc) return rc;
     }
     return 0;
@@ -405,16 +408,373 @@ WindowCall reduce_window(int Nq, int Nkv, int left, int right, int off, bool cau
     return c;
 }
 
-// A packed (variable-length) call on its way through fwd_impl / bwd_impl: the cu_seqlens arrays (device memory) next to the window, whose offset field
-// carries the bottom-right flag.  Nq / Nkv of such a call are the stated maximum lengths, B the number of sequences, the batch strides 0.
-struct VarlenCall { const int* cu_q; const int* cu_k; };
-
-// A dropout call on its way through fwd_impl / bwd_impl (always with a window, which may mask nothing): the seed and the threshold of fa2_dropout.h
-struct DropCall { uint64_t seed; uint32_t t; };
 bool dropout_p_ok(float p) { return p >= 0.f && p < 1.f; }       // (NaN fails both comparisons)
-
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool strides_ok(const int64_t* s) { return s[0] % 8 == 0 && s[1] % 8 == 0 && s[2] % 8 == 0 && s[2] > 0; }
+
+// ---- One call, described: every extern "C" entry point fills one of these by field name and hands it to fwd_run / bwd_run.
+enum class Ask { Launch, Plan, Size };      // what the caller wants: the kernels launched, fa2_fwd_*_plan's report, or a fa2_*_workspace_bytes answer
+struct BiasArg { const void* ptr = nullptr; int kind = FA2_BIAS_NONE; const int64_t* strides = nullptr; };
+struct Call {                                // what a forward and a backward call have in common
+    int dtype = 0, B = 0, H = 0, Hkv = 0, Nq = 0, Nkv = 0, D = 0;      // packed: B = the number of sequences, Nq / Nkv = the stated maximum lengths
+    float scale = 0.f;
+    int flags = 0;                           // FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE: the causal mask the kernels apply themselves (a window carries its own)
+    BiasArg bias;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    void* stream = nullptr;
+    bool windowed = false;                   // `window` masks something (reduce_window kind 2): the WIN kernels, contract 0
+    fa2::Window window = {};                 // the causal flag folded in (right = 0); packed: the offset field carries the bottom-right flag
+    bool packed = false;                     // [total, heads, D] tensors (batch strides 0) and the cu_seqlens arrays, which live in device memory
+    const int *cu_q = nullptr, *cu_k = nullptr;
+    bool dropout = false;                    // always with a window, which may mask nothing: the seed and the threshold of fa2_dropout.h
+    uint64_t seed = 0;
+    uint32_t drop_t = 0;
+    Ask ask = Ask::Launch;
+    size_t* ws_need = nullptr;               // Ask::Size
+};
+struct FwdCall : Call {
+    const void *q = nullptr, *k = nullptr, *v = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    const int64_t *qs = nullptr, *ks = nullptr, *vs = nullptr, *os = nullptr, *ls = nullptr;      // {batch, head, row}; ls: {batch, head}
+    fa2_fwd_plan_t* plan = nullptr;          // Ask::Plan
+};
+struct BwdCall : Call {
+    const void *q = nullptr, *k = nullptr, *v = nullptr, *o = nullptr, *dout = nullptr;
+    const float* lse = nullptr;
+    void *dq = nullptr, *dk = nullptr, *dv = nullptr;
+    float* delta_ws = nullptr;
+    const int64_t *qs = nullptr, *ks = nullptr, *vs = nullptr, *os = nullptr, *dos = nullptr, *dqs = nullptr, *dks = nullptr, *dvs = nullptr, *ls = nullptr;
+};
+
+// ---- validation: a call description -> FwdParams / BwdParams and the kernel head dim, or an error code.  The order of the checks is part of the
+// C-ABI's behaviour (tests/test_abi_golden.py pins which code a call with two defects gets).
+int bias_esize(int kind) { return kind == FA2_BIAS_F32 ? 4 : kind == FA2_BIAS_IO_DTYPE ? 2 : 1; }
+
+// (a launch needs the bias and its strides; a plan / size query describes neither: its strides read as 0)
+int check_bias(const Call& c) {
+    const BiasArg& b = c.bias;
+    if (b.kind == FA2_BIAS_NONE) return FA2_OK;
+    if (b.kind != FA2_BIAS_IO_DTYPE && b.kind != FA2_BIAS_F32 && b.kind != FA2_BIAS_BOOL) return FA2_ERR_BIAS;
+    if (c.ask == Ask::Launch && (!b.ptr || !b.strides)) return FA2_ERR_NULL_POINTER;
+    if (b.strides && (b.strides[0] < 0 || b.strides[1] < 0 || b.strides[2] < 0)) return FA2_ERR_BIAS;
+    if (reinterpret_cast<uintptr_t>(b.ptr) % (uintptr_t)bias_esize(b.kind)) return FA2_ERR_ALIGNMENT;
+    return FA2_OK;
+}
+
+// dtype, sizes, head grouping, head dim, scale — in this order, forward and backward alike.  *HD: the kernel head dim; columns [D, HD) are masked in-kernel.
+static_assert(kHeadDims[kNumHeadDims - 1] == kMaxBwdHeadDim, "the backward serves every head dim of the forward");
+int check_shape(const Call& c, int* HD) {
+    if (c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    if (c.B < 1 || c.H < 1 || c.Nq < 1 || c.Nkv < 1 || c.D < 1) return FA2_ERR_BAD_SHAPE;
+    if (c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0 || (c.Hkv != c.H && c.bias.kind != FA2_BIAS_NONE)) return FA2_ERR_BAD_SHAPE;
+    *HD = fa2_padded_head_dim(c.D);
+    if (*HD < 0 || (c.D & 7)) return FA2_ERR_HEAD_DIM;
+    if (!std::isfinite(c.scale)) return FA2_ERR_SCALE;
+    return FA2_OK;
+}
+
+// addressable bytes of n rows of a head's matrix, and whether they — plus one tile of rows past the end: masked lanes add fa2::kOobOffset to such an
+// offset, which relies on every in-range offset staying below 2 GiB — fit 31 bits
+int64_t span_bytes(int n, const int64_t* s, int D) { return ((int64_t)(n - 1) * s[2] + D) * 2; }
+bool span_ok(int n, const int64_t* s, int D) { return span_bytes(n, s, D) + 64 * s[2] * 2 <= 0x7fffffffLL; }
+
+// The tensors of a call: a null pointer (stride arrays included), then alignment.  Dense launches make the first check before everything but the flags
+// and the second beside the stride checks; packed launches make both last, so that a bad argument is reported as what it is; plan and size
+// queries have no tensors.
+bool any_null(std::initializer_list<const void*> ptrs) { return std::any_of(ptrs.begin(), ptrs.end(), [](const void* p) { return !p; }); }
+bool all_aligned16(std::initializer_list<const void*> ptrs) { return std::all_of(ptrs.begin(), ptrs.end(), aligned16); }
+bool tensors_null(const FwdCall& c) { return any_null({c.q, c.k, c.v, c.o, c.lse, c.qs, c.ks, c.vs, c.os, c.ls}); }
+bool tensors_null(const BwdCall& c) {
+    return any_null({c.q, c.k, c.v, c.o, c.dout, c.lse, c.dq, c.dk, c.dv, c.delta_ws, c.qs, c.ks, c.vs, c.os, c.dos, c.dqs, c.dks, c.dvs, c.ls});
+}
+bool tensors_aligned(const FwdCall& c) { return all_aligned16({c.q, c.k, c.v, c.o}); }
+bool tensors_aligned(const BwdCall& c) { return all_aligned16({c.q, c.k, c.v, c.o, c.dout, c.dq, c.dk, c.dv}); }
+template <typename C>
+int check_packed_tensors(const C& c) {
+    if (!c.cu_q || !c.cu_k || tensors_null(c)) return FA2_ERR_NULL_POINTER;
+    return tensors_aligned(c) ? FA2_OK : FA2_ERR_ALIGNMENT;
+}
+
+// what the windowed / packed / dropout kernels read from fields of the parameter block that such a call does not use otherwise
+template <typename P>
+void set_family(P& p, const Call& c) {
+    fa2::set_window(p, c.window);
+    if (c.packed) fa2::set_varlen(p, c.cu_q, c.cu_k);
+    if (c.dropout) fa2::set_dropout(p, c.seed, c.drop_t);
+}
+
+int fwd_validate(const FwdCall& c, fa2::FwdParams& p, int& HD) {
+    // Until round 5 any non-zero value of the flag word meant "causal"; a caller that still passes another truthy int would silently get a non-causal
+    // forward: refuse it
+    if (c.flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
+    const bool tensors = c.ask == Ask::Launch && !c.packed;
+    if (tensors && tensors_null(c)) return FA2_ERR_NULL_POINTER;
+    if (int rc = check_bias(c)) return rc;
+    if (int rc = check_shape(c, &HD)) return rc;
+    if ((tensors && !tensors_aligned(c)) || !strides_ok(c.qs) || !strides_ok(c.ks) || !strides_ok(c.vs) || !strides_ok(c.os)) return FA2_ERR_ALIGNMENT;
+    if (!span_ok(c.Nkv, c.ks, c.D) || !span_ok(c.Nkv, c.vs, c.D)) return FA2_ERR_BAD_SHAPE;
+
+    const int B = c.B, H = c.H, Nq = c.Nq, Nkv = c.Nkv, bias_kind = c.bias.kind;
+    p.q = c.q; p.k = c.k; p.v = c.v; p.o = c.o; p.lse = c.lse;
+    p.B = B; p.H = H; p.Nq = Nq; p.Nkv = Nkv; p.D = c.D;
+    for (int i = 0; i < 3; ++i) {
+        p.qs[i] = c.qs[i]; p.ks[i] = c.ks[i]; p.vs[i] = c.vs[i]; p.os[i] = c.os[i];
+    }
+    p.ls[0] = c.ls[0]; p.ls[1] = c.ls[1];
+    p.c = std::fabs(c.scale) * 1.4426950408889634f;  // fold log2(e): reference kernel_fp16.cu:827
+    // scale == 0 is the uniform softmax (O = mean of V, as the reference's arithmetic gives).  With c == 0 the first
+    // tile's (max - (-inf)) * c would be NaN; a factor too small to move any f32 score off zero gives the same result.
+    if (p.c < 1e-30f) p.c = 1e-30f;
+    p.negate_q = c.scale < 0.f;
+    p.nqblk = (Nq + kFwdRows - 1) / kFwdRows;
+    p.bh0 = 0;
+    p.nbh = B * H;
+    p.rows_hint = 0;
+    p.exact_scale = (c.flags & FA2_FLAG_EXACT_SCALE) ? 1 : 0;      // this call scales the f32 product whatever option "fold" says
+    p.persist = 1;
+    p.full_items = p.split_items = p.nsplit = p.blk0 = p.item_cap = 0;
+    p.ws = nullptr;
+    p.k_bytes = (uint32_t)span_bytes(Nkv, c.ks, c.D);
+    p.v_bytes = (uint32_t)span_bytes(Nkv, c.vs, c.D);
+    p.kv_group = H / c.Hkv;
+    p.bias = c.bias.ptr;
+    p.bias_kind = bias_kind;
+    for (int i = 0; i < 3; ++i) p.bs[i] = bias_kind != FA2_BIAS_NONE && c.bias.strides ? c.bias.strides[i] : 0;
+    p.bias_vec = 0;
+    if (bias_kind != FA2_BIAS_NONE) {      // groups of four consecutive kv can be fetched with one aligned load
+        const uintptr_t esize = bias_esize(bias_kind), at = reinterpret_cast<uintptr_t>(p.bias);
+        p.bias_vec = Nkv % 4 == 0 && at % (4 * esize) == 0 && p.bs[0] % 4 == 0 && p.bs[1] % 4 == 0 && p.bs[2] % 4 == 0;
+        // 2: a per-row bias whose geometry allows whole 16-byte granules: coalesced tile loads through LDS (a row-broadcast bias —
+        // bs[2] == 0, e.g. a key-padding mask — is one cache line for the whole wave already)
+        const int64_t gran = 16 / (int64_t)esize;
+        if (p.bias_vec && HD <= 256 && Nkv % gran == 0 && at % 16 == 0 && p.bs[0] % gran == 0 && p.bs[1] % gran == 0 && p.bs[2] % gran == 0 && p.bs[2] != 0)
+            p.bias_vec = 2;
+        // 3: the same geometry on a grid of more than 3/8 of the CUs' worth of 256-row workgroups, head dims <= 128, one (b, h) slice of the bias within
+        // 32-bit byte offsets: the 8-wave shape with the tile staged by LDS-DMA (no bias registers).  Measured (tools/mask_bench.py): dense fp16 bias
+        // shared by the heads, B2 H10 N4096 D64, 445 us as 4-wave workgroups; torch SDPA 339.
+        if (p.bias_vec == 2 && HD <= 128 && forced_rows() != 128 && (int64_t)B * H * ((Nq + 255) / 256) > fa2::device_cus() * 3 / 8 &&
+            ((int64_t)(Nq - 1) * p.bs[2] + Nkv + 64 * p.bs[2]) * (int64_t)esize < 0x7fffffffLL)
+            p.bias_vec = 3;
+        // 4: a bias broadcast over the Q rows (row stride 0 — the [B, 1, 1, Nkv] key-padding mask of padded token batches and of SD cross-attention),
+        // any alignment: a wave fetches the tile's 64 values once and spreads them through its LDS image (head dims <= 256: the image exists)
+        if (p.bs[2] == 0 && HD <= 256) p.bias_vec = 4;
+    }
+    if ((int64_t)B * H * p.nqblk > 0x7fffffffLL) return FA2_ERR_GRID;
+    // (the windowed and the BIAS kernels may run as 128-row workgroups)
+    if ((c.windowed || bias_kind != FA2_BIAS_NONE) && (int64_t)B * H * ((Nq + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
+    if (c.windowed) set_family(p, c);
+    return FA2_OK;
+}
+
+// ---- the windowed, packed and dropout kernel families share one launcher signature per direction: [packed][dropout][bf16]
+using FwdFamilyLaunch = int (*)(int HD, const fa2::FwdParams& p, int rows, hipStream_t stream);
+using BwdFamilyLaunch = int (*)(int HD, const fa2::BwdParams& p, hipStream_t stream);
+constexpr FwdFamilyLaunch kFwdFamily[2][2][2] = {
+    {{fa2::launch_fwd_window_f16, fa2::launch_fwd_window_bf16}, {fa2::launch_fwd_dropout_f16, fa2::launch_fwd_dropout_bf16}},
+    {{fa2::launch_fwd_varlen_f16, fa2::launch_fwd_varlen_bf16}, {fa2::launch_fwd_varlen_dropout_f16, fa2::launch_fwd_varlen_dropout_bf16}}};
+constexpr BwdFamilyLaunch kBwdFamily[2][2][2] = {
+    {{fa2::launch_bwd_window_f16, fa2::launch_bwd_window_bf16}, {fa2::launch_bwd_dropout_f16, fa2::launch_bwd_dropout_bf16}},
+    {{fa2::launch_bwd_varlen_f16, fa2::launch_bwd_varlen_bf16}, {fa2::launch_bwd_varlen_dropout_f16, fa2::launch_bwd_varlen_dropout_bf16}}};
+
+// fa2_fwd_workspace_bytes.  The size query has no scale argument, and the split plan depends on the scale at head dim 64 (a launch that folds the
+// scale — c <= 1 — runs the parts inside the hand-scheduled kernel: other fixed costs, possibly another S): the answer is the larger of the two plans,
+// so a workspace of this size serves the call whatever its scale (the callers' caches are keyed without the scale).
+// Likewise FA2_FLAG_EXACT_SCALE (the forward of a call that will be differentiated never folds: another kernel, other fixed costs, possibly
+// another S): both settings are planned, whatever the query's flag says — the callers' caches are keyed without it too.
+size_t fwd_workspace_need(const fa2::FwdParams& p, int HD, bool bf16, bool causal) {
+    size_t need = 0;
+    for (const float c_try : {0.5f, 2.0f})
+        for (const int exact_try : {0, 1}) {
+            fa2::FwdParams pt = p;
+            pt.c = c_try;
+            pt.exact_scale = exact_try;
+            const fa2::SplitPlan pl = plan_split(pt, HD, bf16, causal);
+            if (pl.nsplit > 1) need = std::max(need, (size_t)fa2::split_ws_bytes(pl.split_items, pl.nsplit, HD));
+        }
+    return need;
+}
+
+// fa2_fwd_*_plan: what a launch of this call would run, with a (16-byte aligned) workspace of c.ws_bytes bytes
+void fwd_report(const FwdCall& c, const fa2::FwdParams& p, int HD, int family_rows, fa2_fwd_plan_t* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->heads_main = c.B * c.H;
+    if (c.windowed) {
+        out->kernel = c.packed ? FA2_KERNEL_HIP_VARLEN : FA2_KERNEL_HIP_WINDOW;
+        out->rows = family_rows;
+    } else if (c.bias.kind != FA2_BIAS_NONE) {
+        out->kernel = FA2_KERNEL_HIP_BIAS;
+        out->rows = 0;       // unspecified: the load form (and with it 128- or 256-row workgroups) depends on the bias strides and alignment, which the query does not take
+    } else {
+        const FwdPlan f = plan_fwd(HD, c.dtype == FA2_DTYPE_BF16, p, (c.flags & FA2_FLAG_CAUSAL) != 0, c.ws_bytes > 0, c.ws_bytes);
+        out->kernel = f.main.kernel; out->contract = f.main.contract; out->rows = f.main.rows;
+        out->heads_main = f.main_heads;
+        out->kernel_tail = f.tail.kernel; out->contract_tail = f.tail.contract; out->rows_tail = f.tail.rows;
+        out->nsplit = f.split.nsplit > 1 ? f.split.nsplit : 0;
+        out->split_items = f.split.nsplit > 1 ? f.split.split_items : 0;
+    }
+}
+
+// The forward call: validate, then answer the query or launch.
+int fwd_run(const FwdCall& c) {
+    fa2::FwdParams p;
+    int HD = 0;
+    if (int rc = fwd_validate(c, p, HD)) return rc;
+    const bool bf16 = c.dtype == FA2_DTYPE_BF16, causal = (c.flags & FA2_FLAG_CAUSAL) != 0;
+    // rows per workgroup of the windowed / packed kernels (packed: the grid of the stated maximum lengths)
+    const int family_rows = !c.windowed ? 0 : HD > 256 ? 128 : pick_rows(p);
+    if (c.ask == Ask::Size) { *c.ws_need = fwd_workspace_need(p, HD, bf16, causal); return FA2_OK; }
+    if (c.ask == Ask::Plan) { fwd_report(c, p, HD, family_rows, c.plan); return FA2_OK; }
+    if (c.packed)
+        if (int rc = check_packed_tensors(c)) return rc;
+    hipStream_t stream = (hipStream_t)c.stream;
+    if (c.windowed) return kFwdFamily[c.packed][c.dropout][bf16](HD, p, family_rows, stream);
+    if (c.bias.kind != FA2_BIAS_NONE) return fa2::launch_fwd_hip(bf16, HD, p, causal, 128, true, stream);
+    return launch_fwd(HD, bf16, p, causal, stream, c.ws, c.ws_bytes);
+}
+
+int bwd_validate(const BwdCall& c, fa2::BwdParams& p, int& HD) {
+    if (c.flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;      // (as in fwd_validate: no value but the documented flag bits;
+    if (int rc = check_bias(c)) return rc;                                                    //  bit 1 is what the backward does anyway unless option "kfold" is set)
+    const bool tensors = c.ask == Ask::Launch && !c.packed;
+    if (tensors && tensors_null(c)) return FA2_ERR_NULL_POINTER;
+    if (int rc = check_shape(c, &HD)) return rc;
+    if (tensors && !tensors_aligned(c)) return FA2_ERR_ALIGNMENT;
+    for (const int64_t* s : {c.qs, c.ks, c.vs, c.os, c.dos, c.dqs, c.dks, c.dvs})
+        if (!strides_ok(s)) return FA2_ERR_ALIGNMENT;
+    const int B = c.B, H = c.H, Nq = c.Nq, Nkv = c.Nkv, D = c.D, bias_kind = c.bias.kind;
+    if (!span_ok(Nq, c.qs, D) || !span_ok(Nq, c.dos, D) || !span_ok(Nkv, c.ks, D) || !span_ok(Nkv, c.vs, D)) return FA2_ERR_BAD_SHAPE;
+    const int64_t blocks = (int64_t)B * H * (((Nq > Nkv ? Nq : Nkv) + fa2::kQBlock - 1) / fa2::kQBlock);
+    if (blocks > 0x7fffffffLL || (int64_t)B * H * Nq / 16 > 0x7fffffffLL) return FA2_ERR_GRID;
+
+    p.q = c.q; p.k = c.k; p.v = c.v; p.o = c.o; p.dout = c.dout; p.lse = c.lse; p.delta = c.delta_ws; p.dq = c.dq; p.dk = c.dk; p.dv = c.dv;
+    p.B = B; p.H = H; p.Nq = Nq; p.Nkv = Nkv; p.D = D;
+    for (int i = 0; i < 3; ++i) {
+        p.qs[i] = c.qs[i]; p.ks[i] = c.ks[i]; p.vs[i] = c.vs[i]; p.os[i] = c.os[i];
+        p.dos[i] = c.dos[i]; p.dqs[i] = c.dqs[i]; p.dks[i] = c.dks[i]; p.dvs[i] = c.dvs[i];
+    }
+    p.ls[0] = c.ls[0]; p.ls[1] = c.ls[1];
+    p.scale = c.scale;
+    p.c = c.scale * 1.4426950408889634f;
+    p.nblk = 0;
+    p.q_bytes = (uint32_t)span_bytes(Nq, c.qs, D); p.k_bytes = (uint32_t)span_bytes(Nkv, c.ks, D); p.v_bytes = (uint32_t)span_bytes(Nkv, c.vs, D);
+    p.do_bytes = (uint32_t)span_bytes(Nq, c.dos, D); p.l_bytes = (uint32_t)Nq * 4u;
+    p.bias = c.bias.ptr;
+    p.bias_kind = bias_kind;
+    for (int i = 0; i < 3; ++i) p.bs[i] = bias_kind != FA2_BIAS_NONE && c.bias.strides ? c.bias.strides[i] : 0;
+    // bias tiles by LDS-DMA (fa2_bwd_kernel.hip.h: bwd_bias_tile_*): a per-row bias whose pointer, strides and Nkv are multiples of 16 bytes, one
+    // (b, h) slice within 32-bit byte offsets; otherwise one guarded load per score
+    p.bias_tile = 0;
+    p.bias_img = 4096;
+    if (bias_kind != FA2_BIAS_NONE) {
+        const int64_t esize = bias_esize(bias_kind), gran = 16 / esize;
+        // the backward addresses one (b, h) slice of the bias with 32-bit byte offsets (bounds-checked buffer loads), like K and V
+        if (((int64_t)(Nq - 1) * p.bs[2] + Nkv + 64 * p.bs[2]) * esize >= 0x7fffffffLL) return FA2_ERR_BAD_SHAPE;
+        if (bias_kind == FA2_BIAS_F32) p.bias_img = 8192;
+        if (Nkv % gran == 0 && reinterpret_cast<uintptr_t>(p.bias) % 16 == 0 && p.bs[0] % gran == 0 && p.bs[1] % gran == 0 && p.bs[2] % gran == 0 &&
+            p.bs[2] != 0)
+            p.bias_tile = 1;
+    }
+    p.full_items = p.split_items = p.nsplit = 0;
+    p.ws = (float*)c.ws;
+    p.ws_bytes = c.ws_bytes;
+    p.kv_group = H / c.Hkv;
+    if (c.windowed) set_family(p, c);
+    return FA2_OK;
+}
+
+// The backward call: validate, then answer the size query (fa2_bwd_*_workspace_bytes) or launch.
+int bwd_run(const BwdCall& c) {
+    fa2::BwdParams p;
+    int HD = 0;
+    if (int rc = bwd_validate(c, p, HD)) return rc;
+    const bool bf16 = c.dtype == FA2_DTYPE_BF16, causal = (c.flags & FA2_FLAG_CAUSAL) != 0;
+    if (c.ask == Ask::Size) {
+        fa2::SplitPlan dq, dkv;
+        *c.ws_need = (size_t)fa2::plan_bwd_split(HD, p, causal, &dq, &dkv);
+        return FA2_OK;
+    }
+    if (c.packed)
+        if (int rc = check_packed_tensors(c)) return rc;
+    hipStream_t stream = (hipStream_t)c.stream;
+    if (c.windowed) return kBwdFamily[c.packed][c.dropout][bf16](HD, p, stream);
+    if (c.bias.kind != FA2_BIAS_NONE) return fa2::launch_bwd_bias_hip(bf16, HD, p, causal, stream);
+    return launch_bwd(HD, bf16, p, causal, stream);
+}
+
+// ---- what the entry points of one family share
+// The dense windowed and dropout entry points: the flag check, the window reduced for these lengths, and the flags and window the kernels then take —
+// a window that masks nothing IS a plain call (kind 0) or today's top-left causal call (kind 1) and runs exactly what fa2_fwd_gqa / fa2_bwd run, unless
+// the call drops: the DROP forms of the windowed kernels are the only ones with the mask, and they scale the f32 product.
+int dense_window(Call& c, int flags, int left, int right, int q_offset) {
+    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
+    const WindowCall w = reduce_window(c.Nq, c.Nkv, left, right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
+    if (w.kind < 0) return FA2_ERR_BAD_SHAPE;
+    c.window = w.w;
+    c.windowed = c.dropout || w.kind == 2;
+    c.flags = c.dropout ? FA2_FLAG_EXACT_SCALE : (flags & FA2_FLAG_EXACT_SCALE) | (w.kind == 1 ? FA2_FLAG_CAUSAL : 0);
+    return FA2_OK;
+}
+
+void set_dropout_args(Call& c, float dropout_p, uint64_t seed) {       // (after dropout_p_ok)
+    c.dropout = true;
+    c.seed = seed;
+    c.drop_t = fa2::dropout_threshold(dropout_p, nullptr);
+}
+
+// The packed entry points (c.B .. c.D by name already): what the host can check of such a call — the contents of cu_seqlens live on the device —, the window
+// as the kernels take it (the causal flag folded in, the offset field carrying the bottom-right flag), and the [total, heads, D] strides {head, row} as the
+// kernels' {batch, head, row} with a batch stride of 0: the sequence's first row is added in-kernel.  `two`: q, k, v, o (, do, dq, dk, dv).
+struct PackedStrides { int64_t s[8][3], ls[2]; };
+int packed_call(Call& c, PackedStrides& ps, std::initializer_list<const int64_t*> two, int64_t lse_stride, int flags, int left, int right) {
+    if (c.B < 1 || c.H < 1 || c.Hkv < 1 || c.Nq < 1 || c.Nkv < 1 || c.D < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return FA2_ERR_BAD_SHAPE;
+    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE | FA2_FLAG_BOTTOM_RIGHT)) return FA2_ERR_BAD_SHAPE;
+    const bool br = (flags & FA2_FLAG_BOTTOM_RIGHT) != 0;
+    const int n = c.Nq > c.Nkv ? c.Nq : c.Nkv;          // a sequence's offset Nkv_s - Nq_s lies in [-max_q, max_k]
+    if (!fa2::window_args_ok(c.Nq, c.Nkv, left, right, br ? -n : 0, true)) return FA2_ERR_BAD_SHAPE;
+    for (const int64_t* t : two)
+        if (!t) return FA2_ERR_NULL_POINTER;
+    c.window.left = left;
+    c.window.right = fa2::window_normalize_right(right, (flags & FA2_FLAG_CAUSAL) != 0);
+    c.window.off = br ? 1 : 0;
+    c.windowed = c.packed = true;
+    c.flags = c.dropout ? FA2_FLAG_EXACT_SCALE : flags & FA2_FLAG_EXACT_SCALE;
+    int i = 0;
+    for (const int64_t* t : two) { ps.s[i][0] = 0; ps.s[i][1] = t[0]; ps.s[i][2] = t[1]; ++i; }
+    ps.ls[0] = 0; ps.ls[1] = lse_stride;
+    return FA2_OK;
+}
+
+// Plan and size queries describe no tensors.  Forward: contiguous [B, H, N, D] ones unless the query passes strides (the plan looks at the row pitches of Q
+// and K: a contiguous tensor's are what the size query must assume — ADVICE r3: stand-in pitches of 8 elements made the query plan for the
+// compiler-scheduled kernels and the launch for the hand-scheduled ones).  V takes K's strides, O takes Q's.
+int run_query(FwdCall& c) {
+    if (c.B < 1 || c.H < 1 || c.Hkv < 1 || c.Nq < 1 || c.Nkv < 1 || c.D < 1) return FA2_ERR_BAD_SHAPE;
+    const int64_t d = c.D;
+    const int64_t q[3] = {(int64_t)c.H * c.Nq * d, (int64_t)c.Nq * d, d}, k[3] = {(int64_t)c.Hkv * c.Nkv * d, (int64_t)c.Nkv * d, d};
+    const int64_t ls[2] = {(int64_t)c.H * c.Nq, c.Nq};
+    if (!c.qs) c.qs = q;
+    if (!c.ks) c.ks = k;
+    c.vs = c.ks; c.os = c.qs;
+    if (!c.ls) c.ls = ls;
+    return fwd_run(c);
+}
+// Backward: the plan depends on the shape, the options and the device's CU count only — any valid strides will do.
+int run_query(BwdCall& c) {
+    static const int64_t one[3] = {8, 8, 8}, ls[2] = {0, 0};
+    c.qs = c.ks = c.vs = c.os = c.dos = c.dqs = c.dks = c.dvs = one;
+    c.ls = ls;
+    return bwd_run(c);
+}
+// fa2_*_workspace_bytes: the validation and planning half of the call; 0 for a call that would be refused
+template <typename C>
+size_t workspace_query(C& c) {
+    size_t need = 0;
+    c.ask = Ask::Size;
+    c.ws_need = &need;
+    return run_query(c) == FA2_OK ? need : 0;
+}
 
 }  // namespace
 
@@ -497,476 +857,166 @@ const char* fa2_error_string(int code) {
 
 const char* fa2_version(void) { return "fa2_gfx950 0.9 (D=128 forward (sum-check fast bodies) + backward and D=64 forward: hand-scheduled 4-wave asm bodies; other head dims up to 512: HIP kernels; mfma32x32x16, lds-dma; KV-split tail rounds; attention bias / mask, forward + backward)"; }
 
-static int fwd_impl(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H,
-                    int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                    const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                    float scale, int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
-                    void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, fa2_fwd_plan_t* plan_out = nullptr, int Hkv = 0,
-                    const fa2::Window* win = nullptr, const VarlenCall* vl = nullptr, const DropCall* drop = nullptr) {
-    // `causal` carries the call's flags: bit 0 = causal mask, bit 1 = FA2_FLAG_EXACT_SCALE (this call scales the f32 product whatever option "fold" says)
-    // Until round 5 any non-zero value meant "causal"; a caller that still passes another truthy int would silently get a non-causal forward: refuse it
-    if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
-    const bool exact_scale = (causal & FA2_FLAG_EXACT_SCALE) != 0;
-    causal &= 1;
-    // ws_need / plan_out: validate and plan only (fa2_fwd_workspace_bytes, fa2_fwd_plan) — the data pointers are stand-ins then
-    const bool plan_only = ws_need || plan_out;
-    if (ws_need) *ws_need = 0;
-    if (!q || !k || !v || !o || !lse || !q_strides || !k_strides || !v_strides || !o_strides || !lse_strides)
-        return FA2_ERR_NULL_POINTER;
-    if (bias_kind != FA2_BIAS_NONE) {
-        if (bias_kind != FA2_BIAS_IO_DTYPE && bias_kind != FA2_BIAS_F32 && bias_kind != FA2_BIAS_BOOL) return FA2_ERR_BIAS;
-        if (plan_only) { static const int64_t z3[3] = {0, 0, 0}; if (!bias) bias = q; if (!bias_strides) bias_strides = z3; }
-        if (!bias || !bias_strides) return FA2_ERR_NULL_POINTER;
-        if (bias_strides[0] < 0 || bias_strides[1] < 0 || bias_strides[2] < 0) return FA2_ERR_BIAS;
-        const uintptr_t esize = bias_kind == FA2_BIAS_F32 ? 4 : bias_kind == FA2_BIAS_IO_DTYPE ? 2 : 1;
-        if (reinterpret_cast<uintptr_t>(bias) % esize) return FA2_ERR_ALIGNMENT;
-    }
-    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
-    if (B < 1 || H < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
-    if (Hkv == 0) Hkv = H;                       // (the MHA entry points)
-    if (Hkv < 1 || Hkv > H || H % Hkv != 0 || (Hkv != H && bias_kind != FA2_BIAS_NONE)) return FA2_ERR_BAD_SHAPE;
-    const int HD = fa2_padded_head_dim(D);       // kernel head dim; columns [D, HD) are masked in-kernel
-    if (HD < 0 || (D & 7)) return FA2_ERR_HEAD_DIM;
-    if (!std::isfinite(scale)) return FA2_ERR_SCALE;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !strides_ok(q_strides) ||
-        !strides_ok(k_strides) || !strides_ok(v_strides) || !strides_ok(o_strides))
-        return FA2_ERR_ALIGNMENT;
-    const int64_t k_bytes = ((int64_t)(Nkv - 1) * k_strides[2] + D) * 2;
-    const int64_t v_bytes = ((int64_t)(Nkv - 1) * v_strides[2] + D) * 2;
-    // fa2::kOobOffset relies on every in-range offset, plus one tile of rows past the end, staying below 2 GiB
-    if (k_bytes + 64 * k_strides[2] * 2 > 0x7fffffffLL || v_bytes + 64 * v_strides[2] * 2 > 0x7fffffffLL) return FA2_ERR_BAD_SHAPE;
+// The parameters every dense forward / backward entry point takes, after `dtype` and up to the flag word (HKV: FA2_HKV where the entry point has an Hkv;
+// include/fa2_gfx950.h spells every list out), the same as arguments, and a call description filled from them by field name (the MHA entry points' Hkv is H).
+#define FA2_HKV int Hkv,
+#define FA2_FWD_ARGS(HKV)                                                                                                            \
+    const void *q, const void *k, const void *v, void *o, float *lse, int B, int H, HKV int Nq, int Nkv, int D, const int64_t q_strides[3], \
+        const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], float scale, int flags
+#define FA2_FWD_PASS q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides, scale, flags
+#define FA2_FWD_CALL(c)                                                                                                 \
+    FwdCall c;                                                                                                          \
+    c.dtype = dtype; c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.B = B; c.H = c.Hkv = H; c.Nq = Nq; c.Nkv = Nkv; c.D = D; \
+    c.qs = q_strides; c.ks = k_strides; c.vs = v_strides; c.os = o_strides; c.ls = lse_strides; c.scale = scale; c.flags = flags; c.stream = hip_stream
+#define FA2_BWD_ARGS(HKV)                                                                                               \
+    const void *q, const void *k, const void *v, const void *o, const void *dout, const float *lse, void *dq, void *dk, \
+        void *dv, float *delta_ws, int B, int H, HKV int Nq, int Nkv, int D, const int64_t q_strides[3],                \
+        const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],                             \
+        const int64_t do_strides[3], const int64_t dq_strides[3], const int64_t dk_strides[3],                          \
+        const int64_t dv_strides[3], const int64_t lse_strides[2], float scale, int flags
+#define FA2_BWD_PASS                                                                                                    \
+    q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,          \
+        do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, flags
+#define FA2_BWD_CALL(c)                                                                                                 \
+    BwdCall c;                                                                                                          \
+    c.dtype = dtype; c.q = q; c.k = k; c.v = v; c.o = o; c.dout = dout; c.lse = lse; c.dq = dq; c.dk = dk; c.dv = dv; c.delta_ws = delta_ws; \
+    c.B = B; c.H = c.Hkv = H; c.Nq = Nq; c.Nkv = Nkv; c.D = D; c.qs = q_strides; c.ks = k_strides; c.vs = v_strides; c.os = o_strides;         \
+    c.dos = do_strides; c.dqs = dq_strides; c.dks = dk_strides; c.dvs = dv_strides; c.ls = lse_strides;                \
+    c.scale = scale; c.flags = flags; c.stream = hip_stream
+// ... and every query: the shape (fa2_fwd_plan and the MHA size queries: Hkv = H)
+#define FA2_QUERY_CALL(Type, c, Hkv_) \
+    Type c;                           \
+    c.dtype = dtype; c.B = B; c.H = H; c.Hkv = Hkv_; c.Nq = Nq; c.Nkv = Nkv; c.D = D; c.flags = flags
 
-    fa2::FwdParams p;
-    p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
-    p.B = B; p.H = H; p.Nq = Nq; p.Nkv = Nkv; p.D = D;
-    for (int i = 0; i < 3; ++i) {
-        p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; p.os[i] = o_strides[i];
-    }
-    p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
-    p.c = std::fabs(scale) * 1.4426950408889634f;  // fold log2(e): reference kernel_fp16.cu:827
-    // scale == 0 is the uniform softmax (O = mean of V, as the reference's arithmetic gives).  With c == 0 the first
-    // tile's (max - (-inf)) * c would be NaN; a factor too small to move any f32 score off zero gives the same result.
-    if (p.c < 1e-30f) p.c = 1e-30f;
-    p.negate_q = scale < 0.f;
-    p.nqblk = (Nq + kFwdRows - 1) / kFwdRows;
-    p.bh0 = 0;
-    p.nbh = B * H;
-    p.rows_hint = 0;
-    p.exact_scale = exact_scale ? 1 : 0;
-    p.persist = 1;
-    p.full_items = p.split_items = p.nsplit = p.blk0 = p.item_cap = 0;
-    p.ws = nullptr;
-    p.k_bytes = (uint32_t)k_bytes;
-    p.v_bytes = (uint32_t)v_bytes;
-    p.kv_group = H / Hkv;
-    p.bias = bias;
-    p.bias_kind = bias_kind;
-    for (int i = 0; i < 3; ++i) p.bs[i] = bias_kind != FA2_BIAS_NONE ? bias_strides[i] : 0;
-    p.bias_vec = 0;
-    if (bias_kind != FA2_BIAS_NONE) {      // groups of four consecutive kv can be fetched with one aligned load
-        const uintptr_t esize = bias_kind == FA2_BIAS_F32 ? 4 : bias_kind == FA2_BIAS_IO_DTYPE ? 2 : 1;
-        p.bias_vec = Nkv % 4 == 0 && reinterpret_cast<uintptr_t>(bias) % (4 * esize) == 0 && p.bs[0] % 4 == 0 && p.bs[1] % 4 == 0 &&
-                     p.bs[2] % 4 == 0;
-        // 2: a per-row bias whose geometry allows whole 16-byte granules: coalesced tile loads through LDS (a row-broadcast bias —
-        // bs[2] == 0, e.g. a key-padding mask — is one cache line for the whole wave already)
-        const int64_t gran = 16 / (int64_t)esize;
-        if (p.bias_vec && HD <= 256 && Nkv % gran == 0 && reinterpret_cast<uintptr_t>(bias) % 16 == 0 && p.bs[0] % gran == 0 &&
-            p.bs[1] % gran == 0 && p.bs[2] % gran == 0 && p.bs[2] != 0)
-            p.bias_vec = 2;
-        // 3: the same geometry on a grid of more than 3/8 of the CUs' worth of 256-row workgroups, head dims <= 128, one (b, h) slice of the bias within
-        // 32-bit byte offsets: the 8-wave shape with the tile staged by LDS-DMA (no bias registers).  Measured (tools/mask_bench.py): dense fp16 bias
-        // shared by the heads, B2 H10 N4096 D64, 445 us as 4-wave workgroups; torch SDPA 339.
-        if (p.bias_vec == 2 && HD <= 128 && forced_rows() != 128 && (int64_t)B * H * ((Nq + 255) / 256) > fa2::device_cus() * 3 / 8 &&
-            ((int64_t)(Nq - 1) * p.bs[2] + Nkv + 64 * p.bs[2]) * (int64_t)esize < 0x7fffffffLL)
-            p.bias_vec = 3;
-        // 4: a bias broadcast over the Q rows (row stride 0 — the [B, 1, 1, Nkv] key-padding mask of padded token batches and of SD cross-attention),
-        // any alignment: a wave fetches the tile's 64 values once and spreads them through its LDS image (head dims <= 256: the image exists)
-        if (p.bs[2] == 0 && HD <= 256) p.bias_vec = 4;
-    }
-    if ((int64_t)B * H * p.nqblk > 0x7fffffffLL) return FA2_ERR_GRID;
-
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const bool bf16 = dtype == FA2_DTYPE_BF16;
-    if (win) {          // fa2_fwd_window with a window that masks something (reduce_window kind 2): the WIN kernels, contract 0
-        if ((int64_t)B * H * ((Nq + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
-        fa2::set_window(p, *win);
-        if (vl) { p.bias = vl->cu_q; p.ws = (float*)const_cast<int*>(vl->cu_k); }      // (fa2_fwd_kernel.hip.h: varlen_seq)
-        const int rows = HD > 256 ? 128 : pick_rows(p);      // (varlen: the grid of the stated maximum lengths)
-        if (plan_out) {
-            std::memset(plan_out, 0, sizeof(*plan_out));
-            plan_out->kernel = vl ? FA2_KERNEL_HIP_VARLEN : FA2_KERNEL_HIP_WINDOW;
-            plan_out->rows = rows;
-            plan_out->heads_main = B * H;
-        }
-        if (plan_only) return FA2_OK;
-        if (drop) {       // fa2_fwd_dropout / fa2_fwd_varlen_dropout: the DROP forms of the same kernels
-            fa2::set_dropout(p, drop->seed, drop->t);
-            if (vl) return bf16 ? fa2::launch_fwd_varlen_dropout_bf16(HD, p, rows, stream) : fa2::launch_fwd_varlen_dropout_f16(HD, p, rows, stream);
-            return bf16 ? fa2::launch_fwd_dropout_bf16(HD, p, rows, stream) : fa2::launch_fwd_dropout_f16(HD, p, rows, stream);
-        }
-        if (vl) return bf16 ? fa2::launch_fwd_varlen_bf16(HD, p, rows, stream) : fa2::launch_fwd_varlen_f16(HD, p, rows, stream);
-        return bf16 ? fa2::launch_fwd_window_bf16(HD, p, rows, stream) : fa2::launch_fwd_window_f16(HD, p, rows, stream);
-    }
-    if (bias_kind != FA2_BIAS_NONE) {
-        if ((int64_t)B * H * ((Nq + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
-        if (plan_out) {
-            std::memset(plan_out, 0, sizeof(*plan_out));
-            plan_out->kernel = FA2_KERNEL_HIP_BIAS;
-            plan_out->rows = 0;       // unspecified: the load form (and with it 128- or 256-row workgroups) depends on the bias strides and alignment, which the query does not take
-            plan_out->heads_main = B * H;
-        }
-        if (plan_only) return FA2_OK;
-        return bf16 ? fa2::launch_fwd_hip_bf16(HD, p, causal != 0, 128, true, stream) : fa2::launch_fwd_hip_f16(HD, p, causal != 0, 128, true, stream);
-    }
-    if (ws_need) {      // fa2_fwd_workspace_bytes
-        // The size query has no scale argument, and the split plan depends on the scale at head dim 64 (a launch that folds the scale — c <= 1 — runs
-        // the parts inside the hand-scheduled kernel: other fixed costs, possibly another S): the answer is the larger of the two plans, so a
-        // workspace of this size serves the call whatever its scale (the callers' caches are keyed without the scale).
-        // Likewise FA2_FLAG_EXACT_SCALE (the forward of a call that will be differentiated never folds: another kernel, other fixed costs, possibly
-        // another S): both settings are planned, whatever the query's flag says — the callers' caches are keyed without it too.
-        size_t need = 0;
-        for (const float c_try : {0.5f, 2.0f})
-            for (const int exact_try : {0, 1}) {
-                fa2::FwdParams pt = p;
-                pt.c = c_try;
-                pt.exact_scale = exact_try;
-                const fa2::SplitPlan pl = plan_split(pt, HD, dtype == FA2_DTYPE_BF16, causal != 0);
-                if (pl.nsplit > 1) need = std::max(need, (size_t)fa2::split_ws_bytes(pl.split_items, pl.nsplit, HD));
-            }
-        *ws_need = need;
-    }
-    if (plan_out) {     // fa2_fwd_plan: what launch_fwd would do with a (16-byte aligned) workspace of ws_bytes bytes
-        const FwdPlan f = plan_fwd(HD, bf16, p, causal != 0, ws_bytes > 0, ws_bytes);
-        std::memset(plan_out, 0, sizeof(*plan_out));
-        plan_out->kernel = f.main.kernel; plan_out->contract = f.main.contract; plan_out->rows = f.main.rows;
-        plan_out->heads_main = f.main_heads;
-        plan_out->kernel_tail = f.tail.kernel; plan_out->contract_tail = f.tail.contract; plan_out->rows_tail = f.tail.rows;
-        plan_out->nsplit = f.split.nsplit > 1 ? f.split.nsplit : 0;
-        plan_out->split_items = f.split.nsplit > 1 ? f.split.split_items : 0;
-    }
-    if (plan_only) return FA2_OK;
-    return launch_fwd(HD, bf16, p, causal != 0, stream, ws, ws_bytes);
+int fa2_fwd(int dtype, FA2_FWD_ARGS(), void* hip_stream) {
+    FA2_FWD_CALL(c);
+    return fwd_run(c);
 }
 
-int fa2_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H,
-            int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-            const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-            float scale, int causal, void* hip_stream) {
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
-                    scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream);
+int fa2_fwd_ws(int dtype, FA2_FWD_ARGS(), void* workspace, size_t workspace_bytes, void* hip_stream) {
+    FA2_FWD_CALL(c);
+    c.ws = workspace; c.ws_bytes = workspace_bytes;
+    return fwd_run(c);
 }
 
-int fa2_fwd_ws(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H,
-               int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-               const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-               float scale, int causal, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
-                    scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, workspace, workspace_bytes);
-}
-
-// Stand-in arguments of the plan-only calls: contiguous BHND tensors (the plan looks at the row pitches of Q and K: a contiguous tensor's are
-// what the size query must assume — ADVICE r3: stand-in pitches of 8 elements made the query plan for the compiler-scheduled kernels and
-// the launch for the hand-scheduled ones).
-struct ContigStrides {
-    int64_t q[3], k[3], ls[2];
-    ContigStrides(int H, int Nq, int Nkv, int D) {
-        const int64_t d = D > 0 ? D : 8;
-        q[2] = d; q[1] = (int64_t)Nq * d; q[0] = (int64_t)H * q[1];
-        k[2] = d; k[1] = (int64_t)Nkv * d; k[0] = (int64_t)H * k[1];
-        ls[1] = Nq; ls[0] = (int64_t)H * Nq;
-    }
-};
-alignas(16) static char g_plan_dummy[16];
-
-size_t fa2_fwd_workspace_bytes(int dtype, int B, int H, int Nq, int Nkv, int D, int causal) {
-    // the plan depends on the shape, the options and the device's CU count only: run the validation + planning half of the call on stand-in arguments
-    if (B < 1 || H < 1 || Nq < 1 || Nkv < 1 || D < 1) return 0;
-    const ContigStrides cs(H, Nq, Nkv, D);
-    size_t need = 0;
-    char* d = g_plan_dummy;
-    if (fwd_impl(dtype, d, d, d, d, (float*)d, B, H, Nq, Nkv, D, cs.q, cs.k, cs.k, cs.q, cs.ls, (float)(1.0 / std::sqrt((double)D)), causal, nullptr, FA2_BIAS_NONE,
-                 nullptr, nullptr, nullptr, 0, &need) != FA2_OK)
-        return 0;
-    return need;
+size_t fa2_fwd_workspace_bytes(int dtype, int B, int H, int Nq, int Nkv, int D, int flags) {
+    FA2_QUERY_CALL(FwdCall, c, H);
+    c.scale = (float)(1.0 / std::sqrt((double)D));
+    return workspace_query(c);
 }
 
 int fa2_fwd_plan(int dtype, int B, int H, int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                 float scale, int causal, int bias_kind, size_t workspace_bytes, fa2_fwd_plan_t* plan) {
+                 float scale, int flags, int bias_kind, size_t workspace_bytes, fa2_fwd_plan_t* plan) {
     if (!plan) return FA2_ERR_NULL_POINTER;
-    if (B < 1 || H < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
-    const ContigStrides cs(H, Nq, Nkv, D);
-    char* d = g_plan_dummy;
-    return fwd_impl(dtype, d, d, d, d, (float*)d, B, H, Nq, Nkv, D, q_strides ? q_strides : cs.q, k_strides ? k_strides : cs.k, k_strides ? k_strides : cs.k,
-                    q_strides ? q_strides : cs.q, cs.ls, scale, causal, nullptr, bias_kind, nullptr, nullptr, nullptr, workspace_bytes, nullptr, plan);
+    FA2_QUERY_CALL(FwdCall, c, H);
+    c.qs = q_strides; c.ks = k_strides; c.scale = scale; c.bias.kind = bias_kind; c.ws_bytes = workspace_bytes;
+    c.ask = Ask::Plan; c.plan = plan;
+    return run_query(c);
 }
 
-int fa2_fwd_bias(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H,
-                 int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                 const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                 float scale, int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream) {
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
-                    scale, causal, bias, bias_kind, bias_strides, hip_stream);
+int fa2_fwd_bias(int dtype, FA2_FWD_ARGS(), const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream) {
+    FA2_FWD_CALL(c);
+    c.bias.ptr = bias; c.bias.kind = bias_kind; c.bias.strides = bias_strides;
+    return fwd_run(c);
 }
 
-static const int64_t* ls3_zero() { static const int64_t z[3] = {0, 0, 0}; return z; }
-
-static int bwd_impl(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-            void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
-            const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-            const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-            const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-            int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream,
-            void* ws = nullptr, size_t ws_bytes = 0, size_t* ws_need = nullptr, int Hkv = 0, const fa2::Window* win = nullptr,
-            const VarlenCall* vl = nullptr, const DropCall* drop = nullptr) {
-    if (causal & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;      // (as in fwd_impl: no value but the documented flag bits)
-    causal &= 1;          // (bit 1, FA2_FLAG_EXACT_SCALE, is what the backward does anyway unless option "kfold" is set)
-    if (ws_need) *ws_need = 0;
-    if (bias_kind != FA2_BIAS_NONE) {
-        if (bias_kind != FA2_BIAS_IO_DTYPE && bias_kind != FA2_BIAS_F32 && bias_kind != FA2_BIAS_BOOL) return FA2_ERR_BIAS;
-        if (!bias || !bias_strides) return FA2_ERR_NULL_POINTER;
-        if (bias_strides[0] < 0 || bias_strides[1] < 0 || bias_strides[2] < 0) return FA2_ERR_BIAS;
-        const uintptr_t esize = bias_kind == FA2_BIAS_F32 ? 4 : bias_kind == FA2_BIAS_IO_DTYPE ? 2 : 1;
-        if (reinterpret_cast<uintptr_t>(bias) % esize) return FA2_ERR_ALIGNMENT;
-    }
-    if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !delta_ws || !q_strides || !k_strides ||
-        !v_strides || !o_strides || !do_strides || !dq_strides || !dk_strides || !dv_strides || !lse_strides)
-        return FA2_ERR_NULL_POINTER;
-    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
-    if (B < 1 || H < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
-    if (Hkv == 0) Hkv = H;                              // (the MHA entry points)
-    if (Hkv < 1 || Hkv > H || H % Hkv != 0 || (Hkv != H && bias_kind != FA2_BIAS_NONE)) return FA2_ERR_BAD_SHAPE;
-    const int HD = fa2_padded_head_dim(D);              // columns [D, HD) are masked in-kernel
-    if (HD < 0 || HD > kMaxBwdHeadDim || (D & 7)) return FA2_ERR_HEAD_DIM;
-    if (!std::isfinite(scale)) return FA2_ERR_SCALE;
-    const void* ptrs[] = {q, k, v, o, dout, dq, dk, dv};
-    const int64_t* strides[] = {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides};
-    for (int i = 0; i < 8; ++i)
-        if (!aligned16(ptrs[i]) || !strides_ok(strides[i])) return FA2_ERR_ALIGNMENT;
-    const int64_t q_bytes = ((int64_t)(Nq - 1) * q_strides[2] + D) * 2, do_bytes = ((int64_t)(Nq - 1) * do_strides[2] + D) * 2;
-    const int64_t k_bytes = ((int64_t)(Nkv - 1) * k_strides[2] + D) * 2, v_bytes = ((int64_t)(Nkv - 1) * v_strides[2] + D) * 2;
-    const int64_t lim = 0x7fffffffLL;   // + one tile of rows past the end: masked lanes add fa2::kOobOffset to such an offset
-    if (q_bytes + 64 * q_strides[2] * 2 > lim || do_bytes + 64 * do_strides[2] * 2 > lim || k_bytes + 64 * k_strides[2] * 2 > lim ||
-        v_bytes + 64 * v_strides[2] * 2 > lim)
-        return FA2_ERR_BAD_SHAPE;
-    const int64_t blocks = (int64_t)B * H * (((Nq > Nkv ? Nq : Nkv) + fa2::kQBlock - 1) / fa2::kQBlock);
-    if (blocks > 0x7fffffffLL || (int64_t)B * H * Nq / 16 > 0x7fffffffLL) return FA2_ERR_GRID;
-
-    fa2::BwdParams p;
-    p.q = q; p.k = k; p.v = v; p.o = o; p.dout = dout; p.lse = lse; p.delta = delta_ws; p.dq = dq; p.dk = dk; p.dv = dv;
-    p.B = B; p.H = H; p.Nq = Nq; p.Nkv = Nkv; p.D = D;
-    for (int i = 0; i < 3; ++i) {
-        p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; p.os[i] = o_strides[i];
-        p.dos[i] = do_strides[i]; p.dqs[i] = dq_strides[i]; p.dks[i] = dk_strides[i]; p.dvs[i] = dv_strides[i];
-    }
-    p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
-    p.scale = scale;
-    p.c = scale * 1.4426950408889634f;
-    p.nblk = 0;
-    p.q_bytes = (uint32_t)q_bytes; p.k_bytes = (uint32_t)k_bytes; p.v_bytes = (uint32_t)v_bytes;
-    p.do_bytes = (uint32_t)do_bytes; p.l_bytes = (uint32_t)Nq * 4u;
-    p.bias = bias;
-    p.bias_kind = bias_kind;
-    for (int i = 0; i < 3; ++i) p.bs[i] = bias_kind != FA2_BIAS_NONE ? bias_strides[i] : 0;
-    // bias tiles by LDS-DMA (fa2_bwd_kernel.hip.h: bwd_bias_tile_*): a per-row bias whose pointer, strides and Nkv are multiples of 16 bytes, one
-    // (b, h) slice within 32-bit byte offsets; otherwise one guarded load per score
-    p.bias_tile = 0;
-    p.bias_img = 4096;
-    if (bias_kind != FA2_BIAS_NONE) {
-        const int64_t esize = bias_kind == FA2_BIAS_F32 ? 4 : bias_kind == FA2_BIAS_IO_DTYPE ? 2 : 1, gran = 16 / esize;
-        // the backward addresses one (b, h) slice of the bias with 32-bit byte offsets (bounds-checked buffer loads), like K and V
-        if (((int64_t)(Nq - 1) * p.bs[2] + Nkv + 64 * p.bs[2]) * esize >= 0x7fffffffLL) return FA2_ERR_BAD_SHAPE;
-        if (bias_kind == FA2_BIAS_F32) p.bias_img = 8192;
-        if (Nkv % gran == 0 && reinterpret_cast<uintptr_t>(bias) % 16 == 0 && p.bs[0] % gran == 0 && p.bs[1] % gran == 0 && p.bs[2] % gran == 0 &&
-            p.bs[2] != 0)
-            p.bias_tile = 1;
-    }
-    p.full_items = p.split_items = p.nsplit = 0;
-    p.ws = (float*)ws;
-    p.ws_bytes = ws_bytes;
-    p.kv_group = H / Hkv;
-    if (ws_need) {      // fa2_bwd_workspace_bytes: validate and plan only
-        fa2::SplitPlan a, b2;
-        *ws_need = (size_t)fa2::plan_bwd_split(HD, p, causal != 0, &a, &b2);
-        return FA2_OK;
-    }
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const bool bf16 = dtype == FA2_DTYPE_BF16;
-    if (win) {          // fa2_bwd_window with a window that masks something: the WIN passes
-        fa2::set_window(p, *win);
-        if (drop) {       // fa2_bwd_dropout / fa2_bwd_varlen_dropout
-            fa2::set_dropout(p, drop->seed, drop->t);
-            if (vl) {
-                p.bias = vl->cu_q; p.ws = (float*)const_cast<int*>(vl->cu_k);
-                return bf16 ? fa2::launch_bwd_varlen_dropout_bf16(HD, p, stream) : fa2::launch_bwd_varlen_dropout_f16(HD, p, stream);
-            }
-            return bf16 ? fa2::launch_bwd_dropout_bf16(HD, p, stream) : fa2::launch_bwd_dropout_f16(HD, p, stream);
-        }
-        if (vl) {
-            p.bias = vl->cu_q; p.ws = (float*)const_cast<int*>(vl->cu_k);
-            return bf16 ? fa2::launch_bwd_varlen_bf16(HD, p, stream) : fa2::launch_bwd_varlen_f16(HD, p, stream);
-        }
-        return bf16 ? fa2::launch_bwd_window_bf16(HD, p, stream) : fa2::launch_bwd_window_f16(HD, p, stream);
-    }
-    if (bias_kind != FA2_BIAS_NONE)
-        return bf16 ? fa2::launch_bwd_bias_hip_bf16(HD, p, causal != 0, stream) : fa2::launch_bwd_bias_hip_f16(HD, p, causal != 0, stream);
-    return launch_bwd(HD, bf16, p, causal != 0, stream);
+int fa2_bwd(int dtype, FA2_BWD_ARGS(), void* hip_stream) {
+    FA2_BWD_CALL(c);
+    return bwd_run(c);
 }
 
-int fa2_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-            void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
-            const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-            const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-            const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-            int causal, void* hip_stream) {
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
-                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream);
+int fa2_bwd_ws(int dtype, FA2_BWD_ARGS(), void* workspace, size_t workspace_bytes, void* hip_stream) {
+    FA2_BWD_CALL(c);
+    c.ws = workspace; c.ws_bytes = workspace_bytes;
+    return bwd_run(c);
 }
 
-int fa2_bwd_ws(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-               void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
-               const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-               const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-               const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-               int causal, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
-                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream,
-                    workspace, workspace_bytes);
+size_t fa2_bwd_workspace_bytes(int dtype, int B, int H, int Nq, int Nkv, int D, int flags) {
+    FA2_QUERY_CALL(BwdCall, c, H);
+    c.scale = 1.0f;
+    return workspace_query(c);
 }
 
-size_t fa2_bwd_workspace_bytes(int dtype, int B, int H, int Nq, int Nkv, int D, int causal) {
-    static const int64_t one[3] = {8, 8, 8};
-    alignas(16) static char dummy[16];
-    const int64_t ls[2] = {0, 0};
-    size_t need = 0;
-    if (bwd_impl(dtype, dummy, dummy, dummy, dummy, dummy, (const float*)dummy, dummy, dummy, dummy, (float*)dummy, B, H, Nq, Nkv, D, one, one, one, one,
-                 one, one, one, one, ls, 1.0f, causal, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need) != FA2_OK)
-        return 0;
-    return need;
-}
-
-int fa2_bwd_bias_ws(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                    void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
-                    const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-                    const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-                    const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-                    int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* workspace, size_t workspace_bytes,
+int fa2_bwd_bias_ws(int dtype, FA2_BWD_ARGS(), const void* bias, int bias_kind, const int64_t bias_strides[3], void* workspace, size_t workspace_bytes,
                     void* hip_stream) {
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
-                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, bias, bias_kind, bias_strides, hip_stream,
-                    workspace, workspace_bytes);
+    FA2_BWD_CALL(c);
+    c.bias.ptr = bias; c.bias.kind = bias_kind; c.bias.strides = bias_strides;
+    c.ws = workspace; c.ws_bytes = workspace_bytes;
+    return bwd_run(c);
 }
 
-size_t fa2_bwd_bias_workspace_bytes(int dtype, int B, int H, int Nq, int Nkv, int D, int causal) {
-    static const int64_t one[3] = {8, 8, 8};
-    alignas(16) static char dummy[16];
-    const int64_t ls[2] = {0, 0};
-    size_t need = 0;
-    // (the plan does not depend on the bias' kind or strides: any valid description will do)
-    if (bwd_impl(dtype, dummy, dummy, dummy, dummy, dummy, (const float*)dummy, dummy, dummy, dummy, (float*)dummy, B, H, Nq, Nkv, D, one, one, one, one,
-                 one, one, one, one, ls, 1.0f, causal, dummy, FA2_BIAS_BOOL, ls3_zero(), nullptr, nullptr, 0, &need) != FA2_OK)
-        return 0;
-    return need;
+size_t fa2_bwd_bias_workspace_bytes(int dtype, int B, int H, int Nq, int Nkv, int D, int flags) {
+    FA2_QUERY_CALL(BwdCall, c, H);
+    c.scale = 1.0f;
+    c.bias.kind = FA2_BIAS_BOOL;       // (the plan does not depend on the bias' kind or strides: any valid kind will do)
+    return workspace_query(c);
 }
 
-int fa2_bwd_bias(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                 void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
-                 const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-                 const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-                 const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-                 int causal, const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream) {
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
-                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, bias, bias_kind, bias_strides, hip_stream);
+int fa2_bwd_bias(int dtype, FA2_BWD_ARGS(), const void* bias, int bias_kind, const int64_t bias_strides[3], void* hip_stream) {
+    FA2_BWD_CALL(c);
+    c.bias.ptr = bias; c.bias.kind = bias_kind; c.bias.strides = bias_strides;
+    return bwd_run(c);
 }
 
 // ---- grouped-query / multi-query attention: K and V (and dK, dV) have Hkv heads, Q head h reads K / V head h / (H / Hkv)
-int fa2_fwd_gqa(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
-                int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                float scale, int causal, void* workspace, size_t workspace_bytes, void* hip_stream) {
+int fa2_fwd_gqa(int dtype, FA2_FWD_ARGS(FA2_HKV), void* workspace, size_t workspace_bytes, void* hip_stream) {
     if (Hkv < 1) return FA2_ERR_BAD_SHAPE;
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
-                    scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, workspace, workspace_bytes, nullptr, nullptr, Hkv);
+    FA2_FWD_CALL(c);
+    c.Hkv = Hkv; c.ws = workspace; c.ws_bytes = workspace_bytes;
+    return fwd_run(c);
 }
 
-size_t fa2_fwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int causal) {
+size_t fa2_fwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int flags) {
     // the forward's plan does not depend on the K / V head count (the grouped call runs the MHA call's kernels): fa2_fwd_workspace_bytes, validated
     if (B < 1 || H < 1 || Hkv < 1 || Hkv > H || H % Hkv != 0) return 0;
-    return fa2_fwd_workspace_bytes(dtype, B, H, Nq, Nkv, D, causal);
+    return fa2_fwd_workspace_bytes(dtype, B, H, Nq, Nkv, D, flags);
 }
 
 int fa2_fwd_gqa_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                     float scale, int causal, size_t workspace_bytes, fa2_fwd_plan_t* plan) {
+                     float scale, int flags, size_t workspace_bytes, fa2_fwd_plan_t* plan) {
     if (!plan) return FA2_ERR_NULL_POINTER;
-    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
-    const ContigStrides cs(H, Nq, Nkv, D), ck(Hkv, Nq, Nkv, D);
-    char* d = g_plan_dummy;
-    return fwd_impl(dtype, d, d, d, d, (float*)d, B, H, Nq, Nkv, D, q_strides ? q_strides : cs.q, k_strides ? k_strides : ck.k, k_strides ? k_strides : ck.k,
-                    q_strides ? q_strides : cs.q, cs.ls, scale, causal, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, workspace_bytes, nullptr, plan, Hkv);
+    FA2_QUERY_CALL(FwdCall, c, Hkv);
+    c.qs = q_strides; c.ks = k_strides; c.scale = scale; c.ws_bytes = workspace_bytes;
+    c.ask = Ask::Plan; c.plan = plan;
+    return run_query(c);
 }
 
-int fa2_bwd_gqa(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Hkv, int Nq, int Nkv, int D,
-                const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-                const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-                const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-                int causal, void* workspace, size_t workspace_bytes, void* hip_stream) {
+int fa2_bwd_gqa(int dtype, FA2_BWD_ARGS(FA2_HKV), void* workspace, size_t workspace_bytes, void* hip_stream) {
     if (Hkv < 1) return FA2_ERR_BAD_SHAPE;
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
-                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, nullptr, FA2_BIAS_NONE, nullptr, hip_stream,
-                    workspace, workspace_bytes, nullptr, Hkv);
+    FA2_BWD_CALL(c);
+    c.Hkv = Hkv; c.ws = workspace; c.ws_bytes = workspace_bytes;
+    return bwd_run(c);
 }
 
-size_t fa2_bwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int causal) {
-    static const int64_t one[3] = {8, 8, 8};
-    alignas(16) static char dummy[16];
-    const int64_t ls[2] = {0, 0};
-    size_t need = 0;
-    if (Hkv < 1 || bwd_impl(dtype, dummy, dummy, dummy, dummy, dummy, (const float*)dummy, dummy, dummy, dummy, (float*)dummy, B, H, Nq, Nkv, D, one, one, one,
-                            one, one, one, one, one, ls, 1.0f, causal, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need, Hkv) != FA2_OK)
-        return 0;
-    return need;
+size_t fa2_bwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int flags) {
+    FA2_QUERY_CALL(BwdCall, c, Hkv);
+    c.scale = 1.0f;
+    return workspace_query(c);
 }
 
 // ---- sliding-window attention: include/fa2_gfx950.h has the contract, fa2_window.h the arithmetic, window_hip.cpp the kernels
-int fa2_fwd_window(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
-                   int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                   float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream) {
-    if (Hkv < 1 || (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE))) return FA2_ERR_BAD_SHAPE;
-    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
-    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
-    const int f = (flags & FA2_FLAG_EXACT_SCALE) | (c.kind == 1 ? FA2_FLAG_CAUSAL : 0);
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
-                    scale, f, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, c.kind == 2 ? &c.w : nullptr);
+int fa2_fwd_window(int dtype, FA2_FWD_ARGS(FA2_HKV), int window_left, int window_right, int q_offset, void* hip_stream) {
+    if (Hkv < 1) return FA2_ERR_BAD_SHAPE;
+    FA2_FWD_CALL(c);
+    c.Hkv = Hkv;
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    return fwd_run(c);
 }
 
 int fa2_fwd_window_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
                         float scale, int flags, int window_left, int window_right, int q_offset, size_t workspace_bytes, fa2_fwd_plan_t* plan) {
     if (!plan) return FA2_ERR_NULL_POINTER;
-    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || Nkv < 1 || D < 1 || (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE))) return FA2_ERR_BAD_SHAPE;
-    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
-    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
-    const int f = (flags & FA2_FLAG_EXACT_SCALE) | (c.kind == 1 ? FA2_FLAG_CAUSAL : 0);
-    const ContigStrides cs(H, Nq, Nkv, D), ck(Hkv, Nq, Nkv, D);
-    char* d = g_plan_dummy;
-    return fwd_impl(dtype, d, d, d, d, (float*)d, B, H, Nq, Nkv, D, q_strides ? q_strides : cs.q, k_strides ? k_strides : ck.k, k_strides ? k_strides : ck.k,
-                    q_strides ? q_strides : cs.q, cs.ls, scale, f, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, workspace_bytes, nullptr, plan, Hkv,
-                    c.kind == 2 ? &c.w : nullptr);
+    FA2_QUERY_CALL(FwdCall, c, Hkv);
+    c.qs = q_strides; c.ks = k_strides; c.scale = scale; c.ws_bytes = workspace_bytes;
+    c.ask = Ask::Plan; c.plan = plan;
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    return run_query(c);
 }
 
-int fa2_bwd_window(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                   void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
-                   const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-                   const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-                   const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-                   int flags, int window_left, int window_right, int q_offset, void* hip_stream) {
-    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
-    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
-    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
-    const int f = (flags & FA2_FLAG_EXACT_SCALE) | (c.kind == 1 ? FA2_FLAG_CAUSAL : 0);
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
-                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, f, nullptr, FA2_BIAS_NONE, nullptr, hip_stream,
-                    nullptr, 0, nullptr, 0, c.kind == 2 ? &c.w : nullptr);
+int fa2_bwd_window(int dtype, FA2_BWD_ARGS(), int window_left, int window_right, int q_offset, void* hip_stream) {
+    FA2_BWD_CALL(c);
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    return bwd_run(c);
 }
 
 int fa2_window_tile_range(int Nq, int Nkv, int window_left, int window_right, int q_offset, int causal, int row0, int rows, int tile,
@@ -990,63 +1040,41 @@ int fa2_window_row_range(int Nq, int Nkv, int window_left, int window_right, int
 }
 
 // ---- packed, variable-length attention: include/fa2_gfx950.h has the contract, varlen_hip.cpp the kernels
-namespace {
-
-// What the host can check of a packed call (the contents of cu_seqlens live on the device).  On success: the window as the kernels take it — the causal flag
-// folded in, the offset field carrying the bottom-right flag.
-int varlen_check(int B, int H, int Hkv, int max_q, int max_k, int D, int flags, int left, int right, fa2::Window* w) {
-    if (B < 1 || H < 1 || Hkv < 1 || max_q < 1 || max_k < 1 || D < 1 || Hkv > H || H % Hkv != 0) return FA2_ERR_BAD_SHAPE;
-    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE | FA2_FLAG_BOTTOM_RIGHT)) return FA2_ERR_BAD_SHAPE;
-    const bool br = (flags & FA2_FLAG_BOTTOM_RIGHT) != 0;
-    const int n = max_q > max_k ? max_q : max_k;          // a sequence's offset Nkv_s - Nq_s lies in [-max_q, max_k]
-    if (!fa2::window_args_ok(max_q, max_k, left, right, br ? -n : 0, true)) return FA2_ERR_BAD_SHAPE;
-    w->left = left;
-    w->right = fa2::window_normalize_right(right, (flags & FA2_FLAG_CAUSAL) != 0);
-    w->off = br ? 1 : 0;
-    return FA2_OK;
-}
-
-// [total, heads, D] strides {head, row} as the kernels' {batch, head, row} with a batch stride of 0: the sequence's first row is added in-kernel
-struct PackedStrides {
-    int64_t s[3];
-    explicit PackedStrides(const int64_t* two) { s[0] = 0; s[1] = two[0]; s[2] = two[1]; }
-};
-
-}  // namespace
+// The parameters the packed entry points take under these names (the strides go through packed_call)
+#define FA2_PACKED_FILL(c, Hkv_)                                                                                        \
+    c.dtype = dtype; c.B = B; c.H = H; c.Hkv = Hkv_; c.Nq = max_seqlen_q; c.Nkv = max_seqlen_k; c.D = D; c.scale = scale
+#define FA2_PACKED_FWD_FILL(c, ps)                                                                                      \
+    c.q = q; c.k = k; c.v = v; c.o = o; c.lse = lse; c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k;                     \
+    c.qs = ps.s[0]; c.ks = ps.s[1]; c.vs = ps.s[2]; c.os = ps.s[3]; c.ls = ps.ls; c.stream = hip_stream
+#define FA2_PACKED_BWD_FILL(c, ps)                                                                                      \
+    c.q = q; c.k = k; c.v = v; c.o = o; c.dout = dout; c.lse = lse; c.dq = dq; c.dk = dk; c.dv = dv; c.delta_ws = delta_ws; \
+    c.cu_q = cu_seqlens_q; c.cu_k = cu_seqlens_k; c.qs = ps.s[0]; c.ks = ps.s[1]; c.vs = ps.s[2]; c.os = ps.s[3];      \
+    c.dos = ps.s[4]; c.dqs = ps.s[5]; c.dks = ps.s[6]; c.dvs = ps.s[7]; c.ls = ps.ls; c.stream = hip_stream
 
 int fa2_fwd_varlen(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
                    int max_seqlen_q, int max_seqlen_k, int D, const int* cu_seqlens_q, const int* cu_seqlens_k,
                    const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
                    int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream) {
-    fa2::Window w;
-    if (int rc = varlen_check(B, H, Hkv, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
-    if (!q_strides || !k_strides || !v_strides || !o_strides) return FA2_ERR_NULL_POINTER;
-    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides);
-    const int64_t ls[2] = {0, lse_stride};
-    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
-    // (the tensors may still be null: a plan-only pass validates everything else first, so that a bad argument is reported as what it is)
-    char* d = g_plan_dummy;
-    fa2_fwd_plan_t plan;
-    if (int rc = fwd_impl(dtype, d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE,
-                          nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, nullptr, &plan, Hkv, &w, &vl))
-        return rc;
-    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE,
-                    nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, &w, &vl);
+    FwdCall c;
+    PackedStrides ps;
+    FA2_PACKED_FILL(c, Hkv);
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides}, lse_stride, flags, window_left, window_right)) return rc;
+    FA2_PACKED_FWD_FILL(c, ps);
+    return fwd_run(c);
 }
 
 int fa2_fwd_varlen_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D, const int64_t q_strides[2], const int64_t k_strides[2],
                         float scale, int flags, int window_left, int window_right, fa2_fwd_plan_t* plan) {
     if (!plan) return FA2_ERR_NULL_POINTER;
-    fa2::Window w;
-    if (int rc = varlen_check(B, H, Hkv, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
     const int64_t cq[2] = {D, (int64_t)H * D}, ck[2] = {D, (int64_t)Hkv * D};          // a contiguous [total, heads, D]
-    const PackedStrides qs(q_strides ? q_strides : cq), ks(k_strides ? k_strides : ck);
-    const int64_t ls[2] = {0, 0};
-    const VarlenCall vl = {nullptr, nullptr};
-    char* d = g_plan_dummy;
-    return fwd_impl(dtype, d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, ks.s, qs.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE,
-                    nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, nullptr, plan, Hkv, &w, &vl);
+    const int64_t *qs = q_strides ? q_strides : cq, *ks = k_strides ? k_strides : ck;
+    FwdCall c;
+    PackedStrides ps;
+    FA2_PACKED_FILL(c, Hkv);
+    if (int rc = packed_call(c, ps, {qs, ks, ks, qs}, 0, flags, window_left, window_right)) return rc;
+    c.qs = ps.s[0]; c.ks = ps.s[1]; c.vs = ps.s[2]; c.os = ps.s[3]; c.ls = ps.ls;
+    c.ask = Ask::Plan; c.plan = plan;
+    return fwd_run(c);
 }
 
 int fa2_bwd_varlen(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
@@ -1055,21 +1083,14 @@ int fa2_bwd_varlen(int dtype, const void* q, const void* k, const void* v, const
                    const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
                    const int64_t do_strides[2], const int64_t dq_strides[2], const int64_t dk_strides[2], const int64_t dv_strides[2],
                    int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream) {
-    fa2::Window w;
-    if (int rc = varlen_check(B, H, H, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
-    if (!q_strides || !k_strides || !v_strides || !o_strides || !do_strides || !dq_strides || !dk_strides || !dv_strides) return FA2_ERR_NULL_POINTER;
-    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides), gs(do_strides), dqs(dq_strides), dks(dk_strides), dvs(dv_strides);
-    const int64_t ls[2] = {0, lse_stride};
-    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
-    // (as in fa2_fwd_varlen: everything but the tensors first — the workspace query is the validation-only pass of bwd_impl)
-    char* d = g_plan_dummy;
-    size_t need = 0;
-    if (int rc = bwd_impl(dtype, d, d, d, d, d, (const float*)d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s,
-                          dks.s, dvs.s, ls, scale, flags & FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need, 0, &w, &vl))
+    BwdCall c;
+    PackedStrides ps;
+    FA2_PACKED_FILL(c, H);
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides}, lse_stride, flags,
+                             window_left, window_right))
         return rc;
-    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s, dks.s, dvs.s,
-                    ls, scale, flags & FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, 0, &w, &vl);
+    FA2_PACKED_BWD_FILL(c, ps);
+    return bwd_run(c);
 }
 
 static int varlen_range(bool transpose, int Nq_s, int Nkv_s, int left, int right, int flags, int row0, int rows, int tile, int* first_tile, int* ntiles) {
@@ -1094,33 +1115,22 @@ int fa2_varlen_row_range(int Nq_s, int Nkv_s, int window_left, int window_right,
 
 // ---- attention dropout: include/fa2_gfx950.h has the contract, fa2_dropout.h the mask, dropout_hip.cpp / varlen_dropout_hip.cpp the kernels.
 // These calls always take the windowed (packed) kernel family, also when the window masks nothing: its DROP forms are the only kernels with the mask.
-int fa2_fwd_dropout(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
-                    int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                    const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                    float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream, float dropout_p, uint64_t seed) {
+int fa2_fwd_dropout(int dtype, FA2_FWD_ARGS(FA2_HKV), int window_left, int window_right, int q_offset, void* hip_stream, float dropout_p, uint64_t seed) {
     if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
-    if (Hkv < 1 || (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE))) return FA2_ERR_BAD_SHAPE;
-    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
-    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
-    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides, lse_strides,
-                    scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, &c.w, nullptr, &drop);
+    if (Hkv < 1) return FA2_ERR_BAD_SHAPE;
+    FA2_FWD_CALL(c);
+    c.Hkv = Hkv;
+    set_dropout_args(c, dropout_p, seed);
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    return fwd_run(c);
 }
 
-int fa2_bwd_dropout(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                    void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
-                    const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-                    const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
-                    const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2], float scale,
-                    int flags, int window_left, int window_right, int q_offset, void* hip_stream, float dropout_p, uint64_t seed) {
+int fa2_bwd_dropout(int dtype, FA2_BWD_ARGS(), int window_left, int window_right, int q_offset, void* hip_stream, float dropout_p, uint64_t seed) {
     if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
-    if (flags & ~(FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE)) return FA2_ERR_BAD_SHAPE;
-    const WindowCall c = reduce_window(Nq, Nkv, window_left, window_right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
-    if (c.kind < 0) return FA2_ERR_BAD_SHAPE;
-    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,
-                    do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream,
-                    nullptr, 0, nullptr, 0, &c.w, nullptr, &drop);
+    FA2_BWD_CALL(c);
+    set_dropout_args(c, dropout_p, seed);
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    return bwd_run(c);
 }
 
 int fa2_fwd_varlen_dropout(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
@@ -1128,21 +1138,13 @@ int fa2_fwd_varlen_dropout(int dtype, const void* q, const void* k, const void* 
                            const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
                            int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream, float dropout_p, uint64_t seed) {
     if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
-    fa2::Window w;
-    if (int rc = varlen_check(B, H, Hkv, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
-    if (!q_strides || !k_strides || !v_strides || !o_strides) return FA2_ERR_NULL_POINTER;
-    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides);
-    const int64_t ls[2] = {0, lse_stride};
-    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
-    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
-    char* d = g_plan_dummy;          // (as fa2_fwd_varlen: everything but the tensors first)
-    fa2_fwd_plan_t plan;
-    if (int rc = fwd_impl(dtype, d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, FA2_FLAG_EXACT_SCALE,
-                          nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, nullptr, &plan, Hkv, &w, &vl, &drop))
-        return rc;
-    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
-    return fwd_impl(dtype, q, k, v, o, lse, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, ls, scale, FA2_FLAG_EXACT_SCALE,
-                    nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, Hkv, &w, &vl, &drop);
+    FwdCall c;
+    PackedStrides ps;
+    set_dropout_args(c, dropout_p, seed);
+    FA2_PACKED_FILL(c, Hkv);
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides}, lse_stride, flags, window_left, window_right)) return rc;
+    FA2_PACKED_FWD_FILL(c, ps);
+    return fwd_run(c);
 }
 
 int fa2_bwd_varlen_dropout(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
@@ -1152,21 +1154,15 @@ int fa2_bwd_varlen_dropout(int dtype, const void* q, const void* k, const void* 
                            const int64_t do_strides[2], const int64_t dq_strides[2], const int64_t dk_strides[2], const int64_t dv_strides[2],
                            int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream, float dropout_p, uint64_t seed) {
     if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
-    fa2::Window w;
-    if (int rc = varlen_check(B, H, H, max_seqlen_q, max_seqlen_k, D, flags, window_left, window_right, &w)) return rc;
-    if (!q_strides || !k_strides || !v_strides || !o_strides || !do_strides || !dq_strides || !dk_strides || !dv_strides) return FA2_ERR_NULL_POINTER;
-    const PackedStrides qs(q_strides), ks(k_strides), vs(v_strides), os(o_strides), gs(do_strides), dqs(dq_strides), dks(dk_strides), dvs(dv_strides);
-    const int64_t ls[2] = {0, lse_stride};
-    const VarlenCall vl = {cu_seqlens_q, cu_seqlens_k};
-    const DropCall drop = {seed, fa2::dropout_threshold(dropout_p, nullptr)};
-    char* d = g_plan_dummy;
-    size_t need = 0;
-    if (int rc = bwd_impl(dtype, d, d, d, d, d, (const float*)d, d, d, d, (float*)d, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s,
-                          dks.s, dvs.s, ls, scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, nullptr, nullptr, 0, &need, 0, &w, &vl, &drop))
+    BwdCall c;
+    PackedStrides ps;
+    set_dropout_args(c, dropout_p, seed);
+    FA2_PACKED_FILL(c, H);
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides}, lse_stride, flags,
+                             window_left, window_right))
         return rc;
-    if (!cu_seqlens_q || !cu_seqlens_k) return FA2_ERR_NULL_POINTER;
-    return bwd_impl(dtype, q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, max_seqlen_q, max_seqlen_k, D, qs.s, ks.s, vs.s, os.s, gs.s, dqs.s, dks.s, dvs.s,
-                    ls, scale, FA2_FLAG_EXACT_SCALE, nullptr, FA2_BIAS_NONE, nullptr, hip_stream, nullptr, 0, nullptr, 0, &w, &vl, &drop);
+    FA2_PACKED_BWD_FILL(c, ps);
+    return bwd_run(c);
 }
 
 int fa2_dropout_threshold(float dropout_p, float* p_eff) {
@@ -1194,33 +1190,9 @@ int fa2_dropout_keep_mask(uint64_t seed, float dropout_p, int H, int b, int h, i
     return FA2_OK;
 }
 
-#define FA2_BWD_ARGS                                                                                                    \
-    const void *q, const void *k, const void *v, const void *o, const void *dout, const float *lse, void *dq, void *dk, \
-        void *dv, float *delta_ws, int B, int H, int Nq, int Nkv, int D, const int64_t q_strides[3],                    \
-        const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],                             \
-        const int64_t do_strides[3], const int64_t dq_strides[3], const int64_t dk_strides[3],                          \
-        const int64_t dv_strides[3], const int64_t lse_strides[2], float scale, int causal, void *hip_stream
-#define FA2_BWD_PASS                                                                                                  \
-    q, k, v, o, dout, lse, dq, dk, dv, delta_ws, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides, o_strides,        \
-        do_strides, dq_strides, dk_strides, dv_strides, lse_strides, scale, causal, hip_stream
-
-int fa2_bwd_f16(FA2_BWD_ARGS) { return fa2_bwd(FA2_DTYPE_F16, FA2_BWD_PASS); }
-int fa2_bwd_bf16(FA2_BWD_ARGS) { return fa2_bwd(FA2_DTYPE_BF16, FA2_BWD_PASS); }
-
-int fa2_fwd_f16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq,
-                int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                float scale, int causal, void* hip_stream) {
-    return fa2_fwd(FA2_DTYPE_F16, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides,
-                   o_strides, lse_strides, scale, causal, hip_stream);
-}
-
-int fa2_fwd_bf16(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq,
-                 int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                 const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                 float scale, int causal, void* hip_stream) {
-    return fa2_fwd(FA2_DTYPE_BF16, q, k, v, o, lse, B, H, Nq, Nkv, D, q_strides, k_strides, v_strides,
-                   o_strides, lse_strides, scale, causal, hip_stream);
-}
+int fa2_fwd_f16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_F16, FA2_FWD_PASS, hip_stream); }
+int fa2_fwd_bf16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_BF16, FA2_FWD_PASS, hip_stream); }
+int fa2_bwd_f16(FA2_BWD_ARGS(), void* hip_stream) { return fa2_bwd(FA2_DTYPE_F16, FA2_BWD_PASS, hip_stream); }
+int fa2_bwd_bf16(FA2_BWD_ARGS(), void* hip_stream) { return fa2_bwd(FA2_DTYPE_BF16, FA2_BWD_PASS, hip_stream); }
 
 }  // extern "C"
