@@ -1,10 +1,12 @@
 """GPU tests of attention dropout (fa2_fwd_dropout / fa2_bwd_dropout and their packed twins, flash_attention(dropout_p=...)).
-The reference is dense float64 attention written here, with the keep mask taken from the library's host function (dropout_keep_mask): the oracle is
+The reference is dense float64 attention (tools/fuzz_features.py: ref64), with the keep mask taken from the library's host function (dropout_keep_mask): the oracle is
 not involved.  Bars, scaled by magnitude because 1 / (1 - p) enlarges O:
     max|O - O_true| <= max(2 * err_emu, FLOOR[dt] * max(1, max|O_true|)),   gradients likewise with GRAD_TOL[dt],
 err_emu = the error against float64 of a same-contract torch emulation (f32 scores and sums, P rounded to the I/O dtype, one final rounding).
 The LSE is that of the undropped probabilities: LSE_TOL against float64 and against the same call without dropout."""
+import importlib.util
 import math
+import os
 
 import numpy as np
 import pytest
@@ -34,69 +36,15 @@ def _rand(shape, dt, g, mul=1.0):
     return (torch.randn(shape, generator=g) * mul).to(dt)
 
 
-def _band(Nq, Nkv, left, right, off, causal):
-    if causal:
-        right = 0
-    pos = torch.arange(Nq).unsqueeze(1) + off
-    j = torch.arange(Nkv).unsqueeze(0)
-    keep = torch.ones(Nq, Nkv, dtype=torch.bool)
-    if left >= 0:
-        keep &= j >= pos - left
-    if right >= 0:
-        keep &= j <= pos + right
-    return keep
-
-
-def _p_eff(p):
-    return round(p * 65536) / 65536.0
-
-
-def _ref64(q, k, v, do, keep, band, scale, p):
-    """float64 truth for [H, Nq, D] q and [H, Nkv, D] k / v (already expanded): O, lse (log2 units), dQ, dK, dV."""
-    rs = 1.0 / (1.0 - _p_eff(p))
-    q, k, v = (t.double().clone().requires_grad_(True) for t in (q, k, v))
-    S = (q @ k.transpose(-1, -2)) * scale
-    S = S.masked_fill(~band, float("-inf"))
-    dead = ~band.any(-1)
-    m = S.max(-1, keepdim=True).values.detach()                  # (a shift: the softmax does not depend on it)
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    E = torch.exp(S - m)
-    l = E.sum(-1, keepdim=True)
-    P = E / torch.where(l > 0, l, torch.ones_like(l))
-    O = (P * keep * rs) @ v
-    lse = ((m + torch.log(l)) / LN2).squeeze(-1).detach()
-    lse[..., dead] = float("-inf")
-    O.backward(do.double())
-    return O.detach(), lse, q.grad, k.grad, v.grad
-
-
-def _emu(q, k, v, do, keep, band, scale, p, dt):
-    """The kernels' contract in torch on the CPU: f32 scores and sums, P rounded to the I/O dtype, outputs rounded once."""
-    rs = np.float32(1.0 / (1.0 - _p_eff(p)))
-    qf, kf, vf, gf = q.float(), k.float(), v.float(), do.float()
-    S = (qf @ kf.transpose(-1, -2)) * scale
-    S = S.masked_fill(~band, float("-inf"))
-    m = S.max(-1, keepdim=True).values
-    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
-    E = torch.exp(S - m)
-    l = E.sum(-1, keepdim=True)
-    l1 = torch.where(l > 0, l, torch.ones_like(l))
-    kf32 = keep.float()
-    O = (((E.to(dt).float() * kf32) @ vf) / l1 * rs).to(dt)
-    Pn = E / l1
-    Pn16 = Pn.to(dt).float()
-    dV = (((Pn16 * kf32).transpose(-1, -2) @ gf) * rs).to(dt)
-    dP = (gf @ vf.transpose(-1, -2)) * kf32 * rs
-    delta = (gf * O.float()).sum(-1, keepdim=True)
-    dS = (Pn * (dP - delta)).to(dt).float()
-    dQ = ((dS @ kf) * scale).to(dt)
-    dK = ((dS.transpose(-1, -2) @ qf) * scale).to(dt)
-    return O.double(), dQ.double(), dK.double(), dV.double()
+# the band, float64 truth, the same-contract emulation and the bar rule: one copy, in tools/fuzz_features.py (the randomised sweep uses them too)
+_spec = importlib.util.spec_from_file_location("_fuzz_features", os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(__file__))), "tools", "fuzz_features.py"))
+_ff = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_ff)
+_band, _ref64, _emu = _ff.band, _ff.ref64, _ff.emu
 
 
 def _check(name, got, true, emu, tol, tag):
-    err, err_emu = (got.double() - true).abs().max().item(), (emu - true).abs().max().item()
-    bar = max(2 * err_emu, tol * max(1.0, true.abs().max().item()))
+    err, err_emu, bar = _ff.error_and_bar(got, true, emu, tol)
     print("%s %s: err %.3g, emulation %.3g, bar %.3g (max |true| %.3g)" % (tag, name, err, err_emu, bar, true.abs().max().item()))
     assert err <= bar, (tag, name, err, bar)
 

@@ -5,6 +5,9 @@ against float64 attention on the device, held to the contract fa2_fwd_plan names
 hand-scheduled kernels once it drew grids wide enough for them; tools/fuzz_mask.py does the same for the bias / mask path.  One fixed seed of
 each runs here, plus forced draws of the two shape classes the random draw reaches rarely: grids of more 256-row workgroups than CUs (the
 persistent hand-scheduled kernels, the split of a partly filled last round) and long causal sequences (pair units through the item seam).
+tools/fuzz_features.py draws what those two never pass — window / q_offset, grouped k / v, dropout, option "rows", packed batches — against float64 with the
+keep mask from the host, and reads the mask each of the three dropout passes used back bit for bit; its slices here use the seeds whose draw
+tests/test_fuzz_features.py proves to reach every combination they are there for.
 The committed long sweeps live under profiles/*fuzz*.json."""
 import importlib.util
 import os
@@ -61,3 +64,28 @@ def test_randomised_mask_sweep_slice():
         if d["fails"]:
             bad.append(d)
     assert not bad, bad[:3]
+
+
+def _feature_slice(fx, seed, counts):
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    descs = fx.draw_sweep(seed, counts)
+    out = [fx.run_case(d, gen) for d in descs]
+    bad = [d for d in out if d["fails"]]
+    assert not bad, bad[:3]
+    missing = [name for name, n in fx.coverage(descs).items() if n < 1]
+    assert not missing, missing
+    return out
+
+
+def test_randomised_feature_sweep_slice():
+    fx = _tool("fuzz_features")
+    out = _feature_slice(fx, fx.SLICE_SEED, fx.SLICE_COUNTS)
+    assert len(out) == 112 and sum(d["bwd"] for d in out) == 56
+    print("worst err / bar: O %.3f, gradients %.3f; worst LSE err %.3g" % tuple(max(d[k] for d in out) for k in ("o_ratio", "grad_ratio", "lse_err")))
+
+
+def test_dropout_mask_readback_all_passes_slice():
+    fx = _tool("fuzz_features")
+    out = _feature_slice(fx, fx.READBACK_SEED, fx.READBACK_COUNTS)
+    assert len(out) == 24 and {(d["pass_"], d["packed"]) for d in out} == {(ps, pk) for ps in fx.READBACK_PASSES for pk in (False, True)}
+    print("mask bits read back: %d; largest distance of a decoded count from an integer %.4f" % (sum(d["bits"] for d in out), max(d["frac"] for d in out)))

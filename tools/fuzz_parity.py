@@ -25,6 +25,9 @@ from rocwmma_fattn.FlashAttn import FlashAttentionFunction, flash_attn_wmma  # n
 LOG2E = 1.4426950408889634
 FLOOR = {torch.float16: 1e-3, torch.bfloat16: 8e-3}
 GRAD_TOL = {torch.float16: 2e-3, torch.bfloat16: 1.6e-2}
+# the draw's head dims and edge lengths (tools/fuzz_features.py draws from the same lists)
+HEAD_DIMS = [8, 16, 24, 32, 40, 48, 64, 72, 80, 96, 104, 112, 120, 128, 128, 128, 136, 144, 160, 176, 192, 208, 224, 232, 256, 320, 328, 384, 448, 512]
+EDGE_LENGTHS = [1, 2, 31, 32, 33, 63, 64, 65, 77, 127, 128, 129, 255, 256, 257, 511, 512, 513]
 
 
 def dense64(q, k, v, causal, scale):
@@ -36,6 +39,42 @@ def dense64(q, k, v, causal, scale):
     lse = torch.logsumexp(s, dim=-1)
     p = torch.softmax(s, dim=-1)
     return torch.matmul(p, vf), lse * LOG2E
+
+
+def folded_heads(plan, B, H, device):
+    """The (batch, head) pairs whose launch folds scale * log2(e) into Q (FA2_CONTRACT_PRESCALE_Q), as the plan names them per head range: a bool [B, H]
+    tensor, or None when no launch of the call does."""
+    pre_main, pre_tail = plan.contract & _fa2_lib.FA2_CONTRACT_PRESCALE_Q, plan.contract_tail & _fa2_lib.FA2_CONTRACT_PRESCALE_Q
+    if not (pre_main or pre_tail):
+        return None
+    folded = torch.zeros(B * H, dtype=torch.bool, device=device)
+    if pre_main:
+        folded[:plan.heads_main] = True
+    if pre_tail:
+        folded[plan.heads_main:] = True
+    return folded.view(B, H)
+
+
+def prescaled_q(q, scale, dtype):
+    """Q as a FA2_CONTRACT_PRESCALE_Q launch sees it (scale * log2(e) folded in, rounded once to the I/O dtype) and the scale its scores then take."""
+    return (q.float() * (scale * LOG2E)).to(dtype), 1.0 / LOG2E
+
+
+def lse_limit(plan, q, k, D, scale, dtype):
+    """The bound on the log2 LSE against float64 under the contract the plan names."""
+    # the f32 logit itself carries ~2^-24 relative rounding per accumulate step: bound scales with the logit magnitude
+    smag = (q.float().abs().max() * k.float().abs().max() * D * abs(scale) * LOG2E).item()
+    lim = max(1e-3, 4e-6 * smag)
+    p16 = (plan.contract | plan.contract_tail) & _fa2_lib.FA2_CONTRACT_LSUM_P16
+    if (D == 64 or p16) and dtype == torch.bfloat16:
+        # launches whose row sums add the ROUNDED P (FA2_CONTRACT_LSUM_P16: the 16x16x32 bodies, on the matrix pipe; head dim 64's causal / wide
+        # launches did before): when one key dominates a row (large logits) the sum carries that single term's bf16 rounding, log2(1 + 2^-9) =
+        # 2.8e-3, on top of the f32 bound (tests hold it to LSE_TOL_P16_BF16 against the oracle under the same contract; against float64 truth,
+        # with logits scaled 3x: 4.4e-3 seen)
+        lim = max(lim, 2.8e-3 + lim, 6e-3)          # (a dominant key whose P sits just above a power of two: log2(1 + 2^-8) = 5.6e-3; tests/conftest.py LSE_TOL_P16_BF16)
+    elif p16:
+        lim = max(lim, 3.6e-4 + lim)          # fp16: log2(1 + 2^-12)
+    return lim
 
 
 def make(shape_bhnd, dtype, layout, rng, gen, dist):
@@ -61,12 +100,12 @@ def one_case(i, rng, gen, want_bwd, force=None):
     32-rows-per-wave kernel)."""
     dtype = rng.choice([torch.float16, torch.bfloat16])
     dmax = 512
-    D = rng.choice([8, 16, 24, 32, 40, 48, 64, 72, 80, 96, 104, 112, 120, 128, 128, 128, 136, 144, 160, 176, 192, 208, 224, 232, 256, 320, 328, 384, 448, 512])
+    D = rng.choice(HEAD_DIMS)
     while D > dmax:
         D = rng.choice([32, 40, 64, 80, 96, 128, 160, 192, 224, 256])
     big = rng.random() < 0.15
     nmax = 2300 if big and D <= 128 else 700 if D <= 256 else 300
-    pick_n = lambda: rng.choice([1, 2, 31, 32, 33, 63, 64, 65, 77, 127, 128, 129, 255, 256, 257, 511, 512, 513]) \
+    pick_n = lambda: rng.choice(EDGE_LENGTHS) \
         if rng.random() < 0.35 else rng.randint(1, nmax)  # noqa: E731
     Nq, Nkv = pick_n(), pick_n()
     if rng.random() < 0.4:
@@ -139,16 +178,10 @@ def one_case(i, rng, gen, want_bwd, force=None):
     ws = 0 if causal else _fa2_lib.load().fa2_fwd_workspace_bytes(0 if dtype == torch.float16 else 1, B, H, Nq, Nkv, qk.shape[3], 0)
     plan = _fa2_lib.fwd_plan(qk, kk, causal, scale, workspace_bytes=ws)
     desc["plan"] = [plan.kernel, plan.contract, plan.heads_main, plan.kernel_tail, plan.contract_tail, plan.nsplit]
-    pre_main, pre_tail = plan.contract & _fa2_lib.FA2_CONTRACT_PRESCALE_Q, plan.contract_tail & _fa2_lib.FA2_CONTRACT_PRESCALE_Q
-    if pre_main or pre_tail:
-        qs = (q.float() * (scale * LOG2E)).to(dtype)
-        o_alt, lse_alt = dense64(qs, k, v, causal, 1.0 / LOG2E)
-        folded = torch.zeros(B * H, dtype=torch.bool, device=q.device)
-        if pre_main:
-            folded[:plan.heads_main] = True
-        if pre_tail:
-            folded[plan.heads_main:] = True
-        folded = folded.view(B, H)
+    folded = folded_heads(plan, B, H, q.device)
+    if folded is not None:
+        qs, s_alt = prescaled_q(q, scale, dtype)
+        o_alt, lse_alt = dense64(qs, k, v, causal, s_alt)
         o_true = torch.where(folded[:, :, None, None], o_alt, o_true)
         lse_true = torch.where(folded[:, :, None], lse_alt, lse_true)
     fails = []
@@ -189,18 +222,7 @@ def one_case(i, rng, gen, want_bwd, force=None):
             fails.append("O err %.3e > %.3e" % (err, 2 * FLOOR[dtype] * vmax))
         desc["o_err"] = err
     if lse is not None:
-        # the f32 logit itself carries ~2^-24 relative rounding per accumulate step: bound scales with the logit magnitude
-        smag = (q.float().abs().max() * k.float().abs().max() * D * abs(scale) * LOG2E).item()
-        lim = max(1e-3, 4e-6 * smag)
-        p16 = (plan.contract | plan.contract_tail) & _fa2_lib.FA2_CONTRACT_LSUM_P16
-        if (D == 64 or p16) and dtype == torch.bfloat16:
-            # launches whose row sums add the ROUNDED P (FA2_CONTRACT_LSUM_P16: the 16x16x32 bodies, on the matrix pipe; head dim 64's causal / wide
-            # launches did before): when one key dominates a row (large logits) the sum carries that single term's bf16 rounding, log2(1 + 2^-9) =
-            # 2.8e-3, on top of the f32 bound (tests hold it to LSE_TOL_P16_BF16 against the oracle under the same contract; against float64 truth,
-            # with logits scaled 3x: 4.4e-3 seen)
-            lim = max(lim, 2.8e-3 + lim, 6e-3)          # (a dominant key whose P sits just above a power of two: log2(1 + 2^-8) = 5.6e-3; tests/conftest.py LSE_TOL_P16_BF16)
-        elif p16:
-            lim = max(lim, 3.6e-4 + lim)          # fp16: log2(1 + 2^-12)
+        lim = lse_limit(plan, q, k, D, scale, dtype)
         lerr = (lse.double() - lse_true).abs().max().item()
         if not lerr <= lim:
             fails.append("LSE err %.3e > %.3e" % (lerr, lim))
