@@ -199,7 +199,10 @@ bool asm_d256_ok(bool bf16, const fa2::FwdParams& p, bool causal) {
     // D == 256: the pieces of a wave's LDS-DMA share are derived from piece 0 by flipping offset bits — row pitches that are multiples of one 512-byte
     // tile row; below, the general form of the offsets: any pitch
     if (p.D == 256 && (p.ks[2] % 256 || p.vs[2] % 256)) return false;
-    if (((int64_t)(p.Nq + 32) * p.qs[2] + 256) * 2 >= ((int64_t)1 << 32) || ((int64_t)(p.Nq + 32) * p.os[2] + 256) * 2 >= ((int64_t)1 << 32)) return false;
+    // Q and O rows are addressed with 32-bit byte offsets from the head base, and every wave of the last workgroup forms them, also one wholly past Nq
+    // (its loads and stores fall outside the descriptor): rows up to Nq - 1 + 96 + 31, plus 504 bytes inside the row — 128 rows of slack, so that no
+    // offset wraps back into the descriptor's range
+    if (((int64_t)(p.Nq + 128) * p.qs[2] + 256) * 2 >= ((int64_t)1 << 32) || ((int64_t)(p.Nq + 128) * p.os[2] + 256) * 2 >= ((int64_t)1 << 32)) return false;
     if (forced_rows() == 256) return false;              // (option rows = 256 pins the 256-row kernels: tests, A/B)
     return (mask & 32) || p.Nkv >= (causal ? 1024 : 512);
 }
@@ -352,16 +355,26 @@ int launch_fwd(int HD, bool bf16, const fa2::FwdParams& p0, bool causal, hipStre
     return launch_range(HD, bf16, p0, causal, stream);
 }
 
+// addressable bytes of n rows of a head's matrix, and whether they — plus one tile of rows past the end: masked lanes add fa2::kOobOffset to such an
+// offset, which relies on every in-range offset staying below 2 GiB — fit 31 bits
+int64_t span_bytes(int n, const int64_t* s, int D) { return ((int64_t)(n - 1) * s[2] + D) * 2; }
+bool span_ok(int n, const int64_t* s, int D) { return span_bytes(n, s, D) + 64 * s[2] * 2 <= 0x7fffffffLL; }
+
 // Head dim exactly 128 runs the hand-scheduled backward kernels (fa2_bwd_d128.hip.h) unless option "asm" bit 1 is cleared; bits 2 / 3 of
 // the option take only the dQ pass / only the dK-dV pass off them (A/B measurements of one pass at a time).
-int launch_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal, hipStream_t stream) {
+struct BwdPlan { int asm_parts; bool neg_delta, kfold, short_dq; };      // the ONE place that decides it: launch_bwd executes the plan, fa2_bwd_plan reports it
+BwdPlan plan_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal) {
     const int m = asm_mask();
-    const int want = fa2::options().bwd_parts.load(std::memory_order_relaxed);      // 3 unless a profiling run asked for one pass only
     int asm_parts = 0;
     if (HD == 128 && p.D == 128 && (m & 2)) asm_parts = 3 & ~((m >> 2) & 3) & fa2::kBwdAsmParts;
     // row pitches the generated bodies' LDS-DMA offset arithmetic holds for (asm_pitch_ok): the dQ pass stages K and V, the dK / dV pass Q and dO
     if (!asm_pitch_ok(p.ks[2], 128) || !asm_pitch_ok(p.vs[2], 128)) asm_parts &= ~1;
     if (!asm_pitch_ok(p.qs[2], 128) || !asm_pitch_ok(p.dos[2], 128)) asm_parts &= ~2;
+    // the hand-scheduled dQ pass reads O's rows (delta = rowsum(dO * O)) at 32-bit byte offsets from the head's base, like Q's and dO's.  Validation bounds
+    // those two spans; O is the caller's tensor and may have a wider pitch: an O whose head spans 2 GiB or more runs the compiler-scheduled dQ pass, which
+    // forms O's row pointers in 64 bits (fa2_bwd_kernel.hip.h) — the call is served, not refused.  (The product would wrap at 4 GiB; the bound is Q's and
+    // dO's 2 GiB: O's loads are the instruction form of theirs and stay in the same range.)
+    if (!span_ok(p.Nq, p.os, p.D)) asm_parts &= ~1;
     if (p.Nq % 32 != 0) asm_parts &= ~2;              // the hand-scheduled dK/dV pass sweeps whole 32-row Q tiles
     // grouped-query attention: the hand-scheduled dK/dV body owns one Q head's sweep; the compiler-scheduled wave-pair pass sums the group in-kernel
     // (the hand-scheduled dQ pass then writes +delta, which that pass reads)
@@ -381,6 +394,15 @@ int launch_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal, hipStrea
     // (head dim 128 exactly keeps the hand-scheduled dQ pass where that one is available: B8 H16 N4096 x 77, whole backward, 236 us against 246)
     const bool short_dq = !causal && (HD <= 64 || (HD == 128 && !(asm_parts & 1))) && p.Nkv <= 2 * fa2::kKvTile && p.bias_kind == FA2_BIAS_NONE &&
                           forced_rows() == 0 && fa2::options().short_kv.load(std::memory_order_relaxed) != 0;
+    return {asm_parts, neg_delta, kfold, short_dq};
+}
+
+int launch_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal, hipStream_t stream) {
+    const int m = asm_mask();
+    const int want = fa2::options().bwd_parts.load(std::memory_order_relaxed);      // 3 unless a profiling run asked for one pass only
+    const BwdPlan pl = plan_bwd(HD, bf16, p, causal);
+    const int asm_parts = pl.asm_parts;
+    const bool neg_delta = pl.neg_delta, kfold = pl.kfold, short_dq = pl.short_dq;
     for (int part = 1; part <= 2; part <<= 1) {       // the dQ pass first: it fills the delta workspace the dK / dV pass reads
         if (!(want & part)) continue;
         int rc;
@@ -445,6 +467,7 @@ struct BwdCall : Call {
     const float* lse = nullptr;
     void *dq = nullptr, *dk = nullptr, *dv = nullptr;
     float* delta_ws = nullptr;
+    fa2_bwd_plan_t* plan = nullptr;          // Ask::Plan
     const int64_t *qs = nullptr, *ks = nullptr, *vs = nullptr, *os = nullptr, *dos = nullptr, *dqs = nullptr, *dks = nullptr, *dvs = nullptr, *ls = nullptr;
 };
 
@@ -463,6 +486,28 @@ int check_bias(const Call& c) {
     return FA2_OK;
 }
 
+// How the forward fetches the bias (FwdParams::bias_vec; fa2_fwd_bias_form reports it): 0 one guarded load per score, 1 ... 4 below.
+int bias_load_form(int bias_kind, uintptr_t at, const int64_t* bs, int B, int H, int Nq, int Nkv, int HD) {
+    // 1: groups of four consecutive kv can be fetched with one aligned load
+    const uintptr_t esize = bias_esize(bias_kind);
+    int form = Nkv % 4 == 0 && at % (4 * esize) == 0 && bs[0] % 4 == 0 && bs[1] % 4 == 0 && bs[2] % 4 == 0;
+    // 2: a per-row bias whose geometry allows whole 16-byte granules: coalesced tile loads through LDS (a row-broadcast bias —
+    // bs[2] == 0, e.g. a key-padding mask — is one cache line for the whole wave already)
+    const int64_t gran = 16 / (int64_t)esize;
+    if (form && HD <= 256 && Nkv % gran == 0 && at % 16 == 0 && bs[0] % gran == 0 && bs[1] % gran == 0 && bs[2] % gran == 0 && bs[2] != 0)
+        form = 2;
+    // 3: the same geometry on a grid of more than 3/8 of the CUs' worth of 256-row workgroups, head dims <= 128, one (b, h) slice of the bias within
+    // 32-bit byte offsets: the 8-wave shape with the tile staged by LDS-DMA (no bias registers).  Measured (tools/mask_bench.py): dense fp16 bias
+    // shared by the heads, B2 H10 N4096 D64, 445 us as 4-wave workgroups; torch SDPA 339.
+    if (form == 2 && HD <= 128 && forced_rows() != 128 && (int64_t)B * H * ((Nq + 255) / 256) > fa2::device_cus() * 3 / 8 &&
+        ((int64_t)(Nq - 1) * bs[2] + Nkv + 64 * bs[2]) * (int64_t)esize < 0x7fffffffLL)
+        form = 3;
+    // 4: a bias broadcast over the Q rows (row stride 0 — the [B, 1, 1, Nkv] key-padding mask of padded token batches and of SD cross-attention),
+    // any alignment: a wave fetches the tile's 64 values once and spreads them through its LDS image (head dims <= 256: the image exists)
+    if (bs[2] == 0 && HD <= 256) form = 4;
+    return form;
+}
+
 // dtype, sizes, head grouping, head dim, scale — in this order, forward and backward alike.  *HD: the kernel head dim; columns [D, HD) are masked in-kernel.
 static_assert(kHeadDims[kNumHeadDims - 1] == kMaxBwdHeadDim, "the backward serves every head dim of the forward");
 int check_shape(const Call& c, int* HD) {
@@ -474,11 +519,6 @@ int check_shape(const Call& c, int* HD) {
     if (!std::isfinite(c.scale)) return FA2_ERR_SCALE;
     return FA2_OK;
 }
-
-// addressable bytes of n rows of a head's matrix, and whether they — plus one tile of rows past the end: masked lanes add fa2::kOobOffset to such an
-// offset, which relies on every in-range offset staying below 2 GiB — fit 31 bits
-int64_t span_bytes(int n, const int64_t* s, int D) { return ((int64_t)(n - 1) * s[2] + D) * 2; }
-bool span_ok(int n, const int64_t* s, int D) { return span_bytes(n, s, D) + 64 * s[2] * 2 <= 0x7fffffffLL; }
 
 // The tensors of a call: a null pointer (stride arrays included), then alignment.  Dense launches make the first check before everything but the flags
 // and the second beside the stride checks; packed launches make both last, so that a bad argument is reported as what it is; plan and size
@@ -542,25 +582,7 @@ int fwd_validate(const FwdCall& c, fa2::FwdParams& p, int& HD) {
     p.bias = c.bias.ptr;
     p.bias_kind = bias_kind;
     for (int i = 0; i < 3; ++i) p.bs[i] = bias_kind != FA2_BIAS_NONE && c.bias.strides ? c.bias.strides[i] : 0;
-    p.bias_vec = 0;
-    if (bias_kind != FA2_BIAS_NONE) {      // groups of four consecutive kv can be fetched with one aligned load
-        const uintptr_t esize = bias_esize(bias_kind), at = reinterpret_cast<uintptr_t>(p.bias);
-        p.bias_vec = Nkv % 4 == 0 && at % (4 * esize) == 0 && p.bs[0] % 4 == 0 && p.bs[1] % 4 == 0 && p.bs[2] % 4 == 0;
-        // 2: a per-row bias whose geometry allows whole 16-byte granules: coalesced tile loads through LDS (a row-broadcast bias —
-        // bs[2] == 0, e.g. a key-padding mask — is one cache line for the whole wave already)
-        const int64_t gran = 16 / (int64_t)esize;
-        if (p.bias_vec && HD <= 256 && Nkv % gran == 0 && at % 16 == 0 && p.bs[0] % gran == 0 && p.bs[1] % gran == 0 && p.bs[2] % gran == 0 && p.bs[2] != 0)
-            p.bias_vec = 2;
-        // 3: the same geometry on a grid of more than 3/8 of the CUs' worth of 256-row workgroups, head dims <= 128, one (b, h) slice of the bias within
-        // 32-bit byte offsets: the 8-wave shape with the tile staged by LDS-DMA (no bias registers).  Measured (tools/mask_bench.py): dense fp16 bias
-        // shared by the heads, B2 H10 N4096 D64, 445 us as 4-wave workgroups; torch SDPA 339.
-        if (p.bias_vec == 2 && HD <= 128 && forced_rows() != 128 && (int64_t)B * H * ((Nq + 255) / 256) > fa2::device_cus() * 3 / 8 &&
-            ((int64_t)(Nq - 1) * p.bs[2] + Nkv + 64 * p.bs[2]) * (int64_t)esize < 0x7fffffffLL)
-            p.bias_vec = 3;
-        // 4: a bias broadcast over the Q rows (row stride 0 — the [B, 1, 1, Nkv] key-padding mask of padded token batches and of SD cross-attention),
-        // any alignment: a wave fetches the tile's 64 values once and spreads them through its LDS image (head dims <= 256: the image exists)
-        if (p.bs[2] == 0 && HD <= 256) p.bias_vec = 4;
-    }
+    p.bias_vec = bias_kind != FA2_BIAS_NONE ? bias_load_form(bias_kind, reinterpret_cast<uintptr_t>(p.bias), p.bs, B, H, Nq, Nkv, HD) : 0;
     if ((int64_t)B * H * p.nqblk > 0x7fffffffLL) return FA2_ERR_GRID;
     // (the windowed and the BIAS kernels may run as 128-row workgroups)
     if ((c.windowed || bias_kind != FA2_BIAS_NONE) && (int64_t)B * H * ((Nq + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
@@ -693,6 +715,13 @@ int bwd_run(const BwdCall& c) {
     if (c.ask == Ask::Size) {
         fa2::SplitPlan dq, dkv;
         *c.ws_need = (size_t)fa2::plan_bwd_split(HD, p, causal, &dq, &dkv);
+        return FA2_OK;
+    }
+    if (c.ask == Ask::Plan) {        // fa2_bwd_plan: the dense unmasked call's passes (the masked backward runs the BIAS forms of the compiler-scheduled passes)
+        BwdPlan pl = {0, false, false, false};
+        if (c.bias.kind == FA2_BIAS_NONE) pl = plan_bwd(HD, bf16, p, causal);
+        c.plan->dq_kernel = pl.short_dq ? FA2_BWD_KERNEL_SHORT : (pl.asm_parts & 1) ? FA2_BWD_KERNEL_ASM : FA2_BWD_KERNEL_HIP;
+        c.plan->dkv_kernel = (pl.asm_parts & 2) ? FA2_BWD_KERNEL_ASM : FA2_BWD_KERNEL_HIP;
         return FA2_OK;
     }
     if (c.packed)
@@ -841,7 +870,7 @@ const char* fa2_error_string(int code) {
     switch (code) {
         case FA2_OK: return "ok";
         case FA2_ERR_NULL_POINTER: return "fa2: null pointer argument";
-        case FA2_ERR_BAD_SHAPE: return "fa2: B, H, Nq, Nkv, D must be >= 1 and one head's matrix must span < 2 GiB; window_left / window_right are -1 or >= 0, q_offset >= 0";
+        case FA2_ERR_BAD_SHAPE: return "fa2: B, H, Nq, Nkv, D must be >= 1; one head's K / V (backward: also Q / dO; backward bias: one slice) must span < 2 GiB with 64 rows of slack; window_left / window_right are -1 or >= 0, q_offset >= 0";
         case FA2_ERR_HEAD_DIM: return "fa2: head dim not supported (pad D to fa2_padded_head_dim(D))";
         case FA2_ERR_ALIGNMENT: return "fa2: pointers must be 16-byte aligned, strides multiples of 8 elements, last dim contiguous";
         case FA2_ERR_DTYPE: return "fa2: dtype must be FA2_DTYPE_F16 or FA2_DTYPE_BF16";
@@ -986,6 +1015,32 @@ int fa2_bwd_gqa(int dtype, FA2_BWD_ARGS(FA2_HKV), void* workspace, size_t worksp
     FA2_BWD_CALL(c);
     c.Hkv = Hkv; c.ws = workspace; c.ws_bytes = workspace_bytes;
     return bwd_run(c);
+}
+
+int fa2_bwd_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                 const int64_t o_strides[3], const int64_t do_strides[3], float scale, int flags, int bias_kind, const int64_t bias_strides[3],
+                 fa2_bwd_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
+    // a stride array the query does not pass describes a contiguous [B, heads, N, D] tensor; dQ / dK / dV (64-bit stores in every pass) take Q's / K's / V's
+    const int64_t d = D, q[3] = {(int64_t)H * Nq * d, (int64_t)Nq * d, d}, k[3] = {(int64_t)Hkv * Nkv * d, (int64_t)Nkv * d, d};
+    static const int64_t ls[2] = {0, 0};
+    FA2_QUERY_CALL(BwdCall, c, Hkv);
+    c.scale = scale; c.bias.kind = bias_kind; c.bias.strides = bias_strides;
+    c.qs = c.dqs = q_strides ? q_strides : q; c.ks = c.dks = k_strides ? k_strides : k; c.vs = c.dvs = v_strides ? v_strides : k;
+    c.os = o_strides ? o_strides : q; c.dos = do_strides ? do_strides : q; c.ls = ls;
+    c.ask = Ask::Plan; c.plan = plan;
+    return bwd_run(c);
+}
+
+int fa2_fwd_bias_form(int bias_kind, int B, int H, int Nq, int Nkv, int D, const int64_t bias_strides[3]) {
+    if (!bias_strides) return FA2_ERR_NULL_POINTER;
+    if (bias_kind != FA2_BIAS_IO_DTYPE && bias_kind != FA2_BIAS_F32 && bias_kind != FA2_BIAS_BOOL) return FA2_ERR_BIAS;
+    if (bias_strides[0] < 0 || bias_strides[1] < 0 || bias_strides[2] < 0) return FA2_ERR_BIAS;
+    if (B < 1 || H < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
+    const int HD = fa2_padded_head_dim(D);
+    if (HD < 0 || (D & 7)) return FA2_ERR_HEAD_DIM;
+    return bias_load_form(bias_kind, 0, bias_strides, B, H, Nq, Nkv, HD);
 }
 
 size_t fa2_bwd_gqa_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, int flags) {

@@ -38,6 +38,15 @@ class FwdPlan(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BwdPlan(ctypes.Structure):
+    """fa2_bwd_plan_t (include/fa2_gfx950.h)."""
+    _fields_ = [("dq_kernel", ctypes.c_int), ("dkv_kernel", ctypes.c_int)]
+
+
+FA2_BWD_KERNEL_HIP, FA2_BWD_KERNEL_ASM, FA2_BWD_KERNEL_SHORT = 1, 2, 3                                   # fa2_bwd_plan_t.dq_kernel / .dkv_kernel
+FA2_BIAS_FORM_SCALAR, FA2_BIAS_FORM_VEC4, FA2_BIAS_FORM_TILE, FA2_BIAS_FORM_TILE_DMA, FA2_BIAS_FORM_ROW = 0, 1, 2, 3, 4     # fa2_fwd_bias_form
+
+
 _FWD_ARGTYPES = [
     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # q k v o lse
     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,                  # B H Nq Nkv D
@@ -70,6 +79,8 @@ SYMBOLS = {
     "fa2_tile_rows": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "fa2_fwd_prescales_q": (ctypes.c_int, [ctypes.c_int, ctypes.c_float]),
     "fa2_fwd_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [_i64p, _i64p, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(FwdPlan)]),
+    "fa2_bwd_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _i64p, ctypes.POINTER(BwdPlan)]),
+    "fa2_fwd_bias_form": (ctypes.c_int, [ctypes.c_int] * 6 + [_i64p]),
     # grouped-query / multi-query attention: the MHA argument lists with Hkv after H (fa2_fwd_gqa: fa2_fwd_ws's, fa2_bwd_gqa: fa2_bwd_ws's)
     "fa2_fwd_gqa": (ctypes.c_int, [ctypes.c_int] + _FWD_ARGTYPES[:7] + [ctypes.c_int] + _FWD_ARGTYPES[7:-1] + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "fa2_fwd_gqa_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),

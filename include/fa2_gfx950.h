@@ -32,7 +32,21 @@
  *   All base pointers must be 16-byte aligned and every stride a multiple of 8 elements.
  *   D is any multiple of 8 up to the largest kernel head dim (512, forward and backward): the call runs on the
  *   kernel of fa2_padded_head_dim(D) and columns >= D are masked in-kernel — read as zero, never stored — where
- *   the reference zero-pads D on the host (kernel_fp16.cu:763, :767-779).  One head's matrix must stay below 2 GiB.
+ *   the reference zero-pads D on the host (kernel_fp16.cu:763, :767-779).
+ *   Span rules ("addressing limits").  The span of one head's matrix of n rows is ((n - 1) * row stride + D) * 2 bytes.  Bounded, with 64
+ *   further rows of the same pitch as slack: span + 64 * row stride * 2 <= 2^31 - 1, else FA2_ERR_BAD_SHAPE —
+ *     forward : K and V (n = Nkv);            backward : K, V (n = Nkv), Q and dO (n = Nq);
+ *     packed  : the same tensors with n = the stated maximum length (a sequence's rows, not the packed tensor's);
+ *     bias    : one (b, h) slice, ((Nq - 1) * bias_strides[2] + Nkv + 64 * bias_strides[2]) * element size < 2^31 - 1, in the backward (the
+ *               forward accepts any bias slice and chooses the load form by it).
+ *   Not bounded: Q, O and LSE of the forward; O, dQ, dK, dV, LSE and delta_ws of the backward; every batch and head stride; the packed tensors
+ *   as a whole.  These are addressed with 64-bit pointers.  Where a hand-scheduled kernel would address one of them with 32-bit offsets the call
+ *   runs on the compiler-scheduled kernels instead, and the plan query says so:
+ *     Q of the forward's 256-row bodies: ((Nq + 64) * row stride + D) * 2 < 2^32 at the body's head dim (64, 128), < 2^31 at a head dim below it;
+ *     Q and O of the forward's 128-row kernel (head dims 136 .. 256): ((Nq + 128) * row stride + 256) * 2 < 2^32 — every wave of the last
+ *       workgroup forms its rows' offsets, up to 127 rows past Nq;
+ *     O of the backward's hand-scheduled dQ pass (fa2_bwd_plan): the K / V rule above, which keeps O's loads in the range of Q's and dO's.
+ *   The forward stages a bias by LDS-DMA (fa2_fwd_bias_form) only while one (b, h) slice obeys the backward's bias rule.
  *
  * Numerics contract (reference: kernel_fp16.cu:434-490, :510-543)
  *   S = (Q K^T) * scale * log2(e)   (f32 accumulate on MFMA)
@@ -525,6 +539,37 @@ int fa2_fwd_plan(int dtype, int B, int H, int Nq, int Nkv, int D,
 int fa2_fwd_gqa_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D,
                      const int64_t q_strides[3], const int64_t k_strides[3],
                      float scale, int causal, size_t workspace_bytes, fa2_fwd_plan_t* plan);
+
+/* The plan of fa2_bwd / fa2_bwd_ws / fa2_bwd_gqa (Hkv = H for the first two) and of fa2_bwd_bias: which kernel serves each of the two passes, for
+ * these strides.  The launch code executes the same plan.
+ *   FA2_BWD_KERNEL_HIP    the compiler-scheduled pass (every head dim, every layout the validation accepts: 64-bit row pointers for O, dQ, dK, dV)
+ *   FA2_BWD_KERNEL_ASM    the hand-scheduled pass of head dim exactly 128 (row pitches of the staged matrices multiples of 128 elements; dK / dV pass:
+ *                         Nq a multiple of 32, Hkv = H, and only beside the hand-scheduled dQ pass; dQ pass: O's span bounded like Q's — see the
+ *                         span rules above)
+ *   FA2_BWD_KERNEL_SHORT  (dQ pass) the single-pass kernel of non-causal sweeps of at most two KV tiles
+ * Any stride array may be NULL: a contiguous [B, heads, N, D] tensor (dO and O: Q's shape).  dQ / dK / dV are described with Q's / K's / V's strides: no
+ * pass looks at them.  bias_kind other than FA2_BIAS_NONE: fa2_bwd_bias (bias_strides as there, or NULL), both passes FA2_BWD_KERNEL_HIP.
+ * Returns FA2_OK or the validation code the call itself would return with non-null, aligned tensors.
+ * (Enumerators, like FA2_KERNEL_HIP_WINDOW below.) */
+enum { FA2_BWD_KERNEL_HIP = 1, FA2_BWD_KERNEL_ASM = 2, FA2_BWD_KERNEL_SHORT = 3 };
+typedef struct fa2_bwd_plan_t {
+    int dq_kernel, dkv_kernel;                  /* FA2_BWD_KERNEL_* of the dQ (+ delta) pass and of the dK / dV pass */
+} fa2_bwd_plan_t;
+int fa2_bwd_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D,
+                 const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                 const int64_t o_strides[3], const int64_t do_strides[3],
+                 float scale, int causal, int bias_kind, const int64_t bias_strides[3], fa2_bwd_plan_t* plan);
+
+/* How fa2_fwd_bias fetches a bias of these strides whose pointer is 16-byte aligned (the forward accepts every bias; the form follows its geometry):
+ *   FA2_BIAS_FORM_SCALAR    one guarded load per score
+ *   FA2_BIAS_FORM_VEC4      one aligned load per four consecutive keys (Nkv and the strides multiples of 4)
+ *   FA2_BIAS_FORM_TILE      coalesced tile loads through LDS from 64-bit row pointers (Nkv and the strides whole 16-byte granules, head dims <= 256)
+ *   FA2_BIAS_FORM_TILE_DMA  the tile staged by LDS-DMA with 32-bit byte offsets into one (b, h) slice: the TILE geometry on a grid of more than 3/8 of
+ *                           the CUs' worth of 256-row workgroups, head dims <= 128, the slice within the backward's bias span rule above
+ *   FA2_BIAS_FORM_ROW       a bias broadcast over the Q rows (bias_strides[2] == 0), head dims <= 256
+ * Returns the form (>= 0) or a validation code (< 0). */
+enum { FA2_BIAS_FORM_SCALAR = 0, FA2_BIAS_FORM_VEC4 = 1, FA2_BIAS_FORM_TILE = 2, FA2_BIAS_FORM_TILE_DMA = 3, FA2_BIAS_FORM_ROW = 4 };
+int fa2_fwd_bias_form(int bias_kind, int B, int H, int Nq, int Nkv, int D, const int64_t bias_strides[3]);
 
 /* The plan of the windowed forward above.  kernel = FA2_KERNEL_HIP_WINDOW, contract 0, rows as launched — or, for a window that masks nothing, exactly the grouped plan query's answer.
  * (An enumerator, not a #define: the macro list above is the closed set tests/test_boundary.py pins for the other entry points' plans.) */
