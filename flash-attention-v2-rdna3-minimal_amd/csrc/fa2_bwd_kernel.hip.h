@@ -302,7 +302,7 @@ __device__ __forceinline__ void store_acc_t(const f32x16 (&acc)[DT], uint16_t* r
 // images and staging (columns >= D are never fetched) but runs only KSN = ceil(D / 16) k-steps of the products contracted over the head dim
 // and DTN = ceil(D / 32) column blocks of the accumulators.  Defaults = the full kernel.
 template <int HD, bool BF16, bool CAUSAL, int NW = 8, int HDV = HD, int BIAS = 0, int KSN = HD / 16, int DTN = HDV / 32>
-__global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_dq_kernel(const BwdParams FA2_KP) {
+__global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_dq_kernel(const BwdParams FA2_KP FA2_SMOD_PARAM) {
 #if FA2_VARLEN
     BwdParams p = pk;         // (adjusted to the workgroup's sequence below: varlen_enter)
 #endif
@@ -471,6 +471,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
     const float c = p.c, scale = p.scale;
+#if FA2_SMOD
+    // FA2_SMOD (fa2_bwd_scoremod; fa2_scoremod.h): x, t and s are recomputed as in the forward (same lane layout), P = 2^(s log2e - L), and dS is multiplied
+    // by 1 - t^2 in f32 before it is rounded for the dS.K product.  P is formed together with dS once dP is there, so the factor needs no registers of
+    // its own; both modifiers are always computed (smod_score: no branch inside the tile body).
+    (void)c;
+    const float smod_slope = smod.slopes ? smod.slopes[(int64_t)b * smod.stride + h] : 0.f;
+    const int smod_pos = qrow + win.off;
+#endif
 #if FA2_DROP
     // FA2_DROP (fa2_bwd_dropout; fa2_dropout.h): dP = keep o (dO V^T) / (1 - p_eff) — the lane layout is the forward's, and so are the Philox calls
     const DropCtx drop = drop_ctx(p, b, h);
@@ -559,13 +567,16 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
                 }
                 // (kv >= Nkv: the image holds zeros or a neighbouring row's values, P stays finite; the MASKED block below zeroes those entries)
             } else {
+#if !FA2_SMOD
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float b0 = -Lq, b1 = -Lq;
                     s0[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[r], c, b0));
                     s1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[r], c, b1));
                 }
+#endif
             }
+#if !FA2_SMOD
             if (masked) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -579,6 +590,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
 #endif
                 }
             }
+#endif
             f32x16 d0, d1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { d0[r] = 0.f; d1[r] = 0.f; }
@@ -600,11 +612,34 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
             }
 #endif
             // dS^T / scale = P^T * (dP^T - D); the factor `scale` is applied once, to the finished dQ
+#if FA2_SMOD
+            {           // dX^T / scale = P^T * (dP^T - D) * (1 - t^2), P from the modified score; then the band's masks (zeros: the P of such an entry is 0)
+                const float dpos = (float)(smod_pos - (kv0 + 4 * hi));
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float dr = dpos - (float)((r & 3) + 8 * (r >> 2));
+                    float f0, f1;
+                    const float v0 = smod_score(s0[r] * scale, smod.softcap, smod.inv_softcap, smod_slope, __builtin_fabsf(dr), &f0);
+                    const float v1 = smod_score(s1[r] * scale, smod.softcap, smod.inv_softcap, smod_slope, __builtin_fabsf(dr - 32.0f), &f1);
+                    s0[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(v0, kSmodLog2e, -Lq)) * (d0[r] - Dq) * f0;
+                    s1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(v1, kSmodLog2e, -Lq)) * (d1[r] - Dq) * f1;
+                }
+                if (masked) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int kvi = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                        if (kvi > lim || kvi < lim_lo) s0[r] = 0.f;
+                        if (kvi + 32 > lim || kvi + 32 < lim_lo) s1[r] = 0.f;
+                    }
+                }
+            }
+#else
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 s0[r] = s0[r] * (d0[r] - Dq);
                 s1[r] = s1[r] * (d1[r] - Dq);
             }
+#endif
             u32x4 df[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -668,7 +703,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
 // HDV < HD (HD = 512): the workgroup produces the HDV-column slab blockIdx.y of dK / dV; S (and dP) are contracted over the whole head
 // dim, only the transposed-read image and the accumulator are slab-sized (see bwd_dq_kernel).
 template <int HD, bool BF16, bool CAUSAL, bool WANT_DK, int NW = 8, bool BOTH = false, int HDV = HD, int BIAS = 0, int KSN = HD / 16, int DTN = HDV / 32>
-__global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParams FA2_KP) {
+__global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParams FA2_KP FA2_SMOD_PARAM) {
 #if FA2_VARLEN
     BwdParams p = pk;
 #endif
@@ -774,9 +809,19 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
         tend_w = first + n;
         q_lo = win.right < 0 ? 0 : kvrow - win.off - win.right;
         q_hi = win.left < 0 ? 0x7fffffff : kvrow - win.off + win.left;
+#if FA2_SMOD
+        // rows >= Nq of a ragged last Q tile are masked here (the other forms leave them to Q = dO = 0 and P = 2^0 = 1; a modified score has no such
+        // bound: with a negative slope 2^(s log2e) of such a row can be +inf, and inf * 0 would be NaN)
+        q_hi = q_hi < p.Nq - 1 ? q_hi : p.Nq - 1;
+#endif
         const int lo_full = win.right < 0 ? 0 : kvw0 + 31 - win.off - win.right;       // every key of the wave is seen from this row on ...
         first_plain = lo_full > 0 ? (lo_full + kKvTile - 1) / kKvTile : 0;
+#if FA2_SMOD
+        const int hi_full_w = win.left < 0 ? 0x7ffffff0 : kvw0 - win.off + win.left;
+        const int hi_full = hi_full_w < p.Nq - 1 ? hi_full_w : p.Nq - 1;                  // (... and the tile that holds them is not a plain one)
+#else
         const int hi_full = win.left < 0 ? 0x7ffffff0 : kvw0 - win.off + win.left;     // ... up to this one
+#endif
         last_plain = hi_full < -1 ? 0 : (hi_full + 1) / kKvTile;
     }
     const int per = ntiles > tile0 ? ntiles - tile0 : 0;
@@ -852,6 +897,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[dt][r] = 0.f; if constexpr (BOTH) accv[dt][r] = 0.f; }
     const float c = p.c, scale = p.scale;
+#if FA2_SMOD
+    // FA2_SMOD: lane = key, the rows of a tile run along the registers — the same recomputation with |pos - j| = |q + off - kvrow|; where the pass forms
+    // dS (WANT_DK) the factor 1 - t^2 is folded into (dP - D) at once, in f32.  (kv_group = 1, like every windowed pass: h is the query head)
+    (void)c;
+    const float smod_slope = smod.slopes ? smod.slopes[(int64_t)b * smod.stride + h * G] : 0.f;
+#endif
 #if FA2_DROP
     // FA2_DROP: lane = key — the keep bits of a tile come from drop_keylane_bits (fa2_dropout.h); dV = (keep o P)^T dO / (1 - p_eff), the factor applied
     // once to the finished dV; dP = keep o (dO V^T) / (1 - p_eff).  (kv_group = 1: h is the query head)
@@ -921,6 +972,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const f32x4 L0 = *(const __attribute__((address_space(3))) f32x4*)(lt + (8 * g4 + 4 * hi) * 4);
                     const f32x4 L1 = *(const __attribute__((address_space(3))) f32x4*)(lt + (32 + 8 * g4 + 4 * hi) * 4);
+#if FA2_SMOD
+                    [[maybe_unused]] f32x4 Ds0 = {0.f, 0.f, 0.f, 0.f}, Ds1 = {0.f, 0.f, 0.f, 0.f};
+                    if constexpr (WANT_DK) {
+                        Ds0 = *(const __attribute__((address_space(3))) f32x4*)(lt + 256 + (8 * g4 + 4 * hi) * 4);
+                        Ds1 = *(const __attribute__((address_space(3))) f32x4*)(lt + 256 + (32 + 8 * g4 + 4 * hi) * 4);
+                    }
+                    const float dpos = (float)(q0t + 4 * hi + win.off - kvrow);
+#endif
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int r = 4 * g4 + e;
@@ -942,8 +1001,20 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
                             b0 = L0[e] == -__builtin_inff() ? -__builtin_inff() : b0 + t0;
                             b1 = L1[e] == -__builtin_inff() ? -__builtin_inff() : b1 + t1;
                         }
+#if FA2_SMOD
+                        {
+                            const float dr = dpos + (float)((r & 3) + 8 * (r >> 2));
+                            float f0, f1;
+                            const float v0 = smod_score(s0[r] * scale, smod.softcap, smod.inv_softcap, smod_slope, __builtin_fabsf(dr), &f0);
+                            const float v1 = smod_score(s1[r] * scale, smod.softcap, smod.inv_softcap, smod_slope, __builtin_fabsf(dr + 32.0f), &f1);
+                            s0[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(v0, kSmodLog2e, b0));
+                            s1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(v1, kSmodLog2e, b1));
+                            if constexpr (WANT_DK) { d0[r] = (d0[r] - Ds0[e]) * f0; d1[r] = (d1[r] - Ds1[e]) * f1; }      // (dP - D) (1 - t^2)
+                        }
+#else
                         s0[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[r], c, b0));
                         s1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[r], c, b1));
+#endif
                     }
                 }
             };
@@ -983,7 +1054,18 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
                 }
             }
 #endif
+#if FA2_SMOD
+            if constexpr (WANT_DK) {              // dX / scale = P (dP - D) (1 - t^2): the last two factors are in d0 / d1 already (p_loop); masked P are zeros
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if constexpr (BOTH) { d0[r] = s0[r] * d0[r]; d1[r] = s1[r] * d1[r]; }
+                    else { s0[r] = s0[r] * d0[r]; s1[r] = s1[r] * d1[r]; }
+                }
+            }
+            if constexpr (false) {
+#else
             if constexpr (WANT_DK) {
+#endif
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const f32x4 D0 = *(const __attribute__((address_space(3))) f32x4*)(lt + 256 + (8 * g4 + 4 * hi) * 4);
@@ -1129,7 +1211,7 @@ __device__ __forceinline__ void pair_mid_barrier() {
 // Each tile has two phases separated by a barrier: {S, exp | dP} and {dV | dS, dK}; the transcendental / VALU stretch of one wave
 // of a pair runs beside the MFMAs of the other.  Stage: Q row | dO row | Q tr | dO tr | L | D, two stages (129 KiB) + 16 KiB of slots.
 template <int HD, bool BF16, bool CAUSAL, int KSN = HD / 16, int DTN = HD / 32>
-__global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA2_KP) {
+__global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA2_KP FA2_SMOD_PARAM) {
 #if FA2_VARLEN
     BwdParams p = pk;
 #endif
@@ -1201,9 +1283,19 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
         ntiles = first + n;
         q_lo = win.right < 0 ? 0 : kvrow - win.off - win.right;
         q_hi = win.left < 0 ? 0x7fffffff : kvrow - win.off + win.left;
+#if FA2_SMOD
+        // rows >= Nq of a ragged last Q tile are masked here (the other forms leave them to Q = dO = 0 and P = 2^0 = 1; a modified score has no such
+        // bound: with a negative slope 2^(s log2e) of such a row can be +inf, and inf * 0 would be NaN)
+        q_hi = q_hi < p.Nq - 1 ? q_hi : p.Nq - 1;
+#endif
         const int lo_full = win.right < 0 ? 0 : kvw0 + 31 - win.off - win.right;
         first_plain = lo_full > 0 ? (lo_full + kKvTile - 1) / kKvTile : 0;
+#if FA2_SMOD
+        const int hi_full_w = win.left < 0 ? 0x7ffffff0 : kvw0 - win.off + win.left;
+        const int hi_full = hi_full_w < p.Nq - 1 ? hi_full_w : p.Nq - 1;                  // (... and the tile that holds them is not a plain one)
+#else
         const int hi_full = win.left < 0 ? 0x7ffffff0 : kvw0 - win.off + win.left;
+#endif
         last_plain = hi_full < -1 ? 0 : (hi_full + 1) / kKvTile;
     }
     const int vnt = G * (ntiles > tile0 ? ntiles - tile0 : 0);      // the virtual sweep (G = 1 here)
@@ -1245,6 +1337,12 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
     const float c = p.c;
+#if FA2_SMOD
+    // FA2_SMOD: only the P side holds S, so the factor travels with P — the pair's slot carries round16(P (1 - t^2)) while the P side keeps the plain
+    // round16(P) for its dV product; the dS side multiplies what it reads by (dP - D) as ever, which makes it dX / scale.  (kv_group = 1: h is the query head)
+    (void)c;
+    const float smod_slope = smod.slopes ? smod.slopes[(int64_t)b * smod.stride + h * G] : 0.f;
+#endif
 #if FA2_DROP
     // FA2_DROP: both waves of a pair form the tile's keep bits (drop_keylane_bits) — the P side masks the fragments of its dV product (the slot carries the
     // undropped P, which dS needs), the dS side masks dP
@@ -1299,6 +1397,38 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                 s1 = mfma16<BF16>(lds_load128(qR + ln.kr_off[ks] + 32 * ROWB), bf[ks], s1);
             }
             __builtin_amdgcn_s_setprio(0);
+#if FA2_SMOD
+            u32x4 xg[4];                                              // P (1 - t^2) as 16-bit fragments: what the slot carries
+            {
+                // the band's masks are applied here, to P and P (1 - t^2) alike, as limits relative to the tile's first row (a plain tile: none)
+                const bool edge = tile < first_plain || tile >= last_plain;
+                const int q0t = tile * kKvTile;
+                const int lo_rel = edge ? q_lo - q0t - 4 * hi : -0x40000000, hi_rel = edge ? q_hi - q0t - 4 * hi : 0x40000000;
+                const float dpos = (float)(q0t + 4 * hi + win.off - kvrow);
+                const float scale = p.scale;
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const f32x4 L0 = *(lds_f32x4_cptr)(lt + (8 * g4 + 4 * hi) * 4);
+                    const f32x4 L1 = *(lds_f32x4_cptr)(lt + (32 + 8 * g4 + 4 * hi) * 4);
+                    float pf0[4], pf1[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = 4 * g4 + e, qo = (r & 3) + 8 * (r >> 2);
+                        float f0, f1;
+                        const float v0 = smod_score(s0[r] * scale, smod.softcap, smod.inv_softcap, smod_slope, __builtin_fabsf(dpos + (float)qo), &f0);
+                        const float v1 = smod_score(s1[r] * scale, smod.softcap, smod.inv_softcap, smod_slope, __builtin_fabsf(dpos + (float)(qo + 32)), &f1);
+                        s0[r] = (qo < lo_rel || qo > hi_rel) ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(v0, kSmodLog2e, -L0[e]));
+                        s1[r] = (qo + 32 < lo_rel || qo + 32 > hi_rel) ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(v1, kSmodLog2e, -L1[e]));
+                        pf0[e] = s0[r] * f0;
+                        pf1[e] = s1[r] * f1;
+                    }
+                    xg[g4 >> 1][2 * (g4 & 1)] = pack2<BF16>(pf0[0], pf0[1]);
+                    xg[g4 >> 1][2 * (g4 & 1) + 1] = pack2<BF16>(pf0[2], pf0[3]);
+                    xg[2 + (g4 >> 1)][2 * (g4 & 1)] = pack2<BF16>(pf1[0], pf1[1]);
+                    xg[2 + (g4 >> 1)][2 * (g4 & 1) + 1] = pack2<BF16>(pf1[2], pf1[3]);
+                }
+            }
+#else
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 const f32x4 L0 = *(lds_f32x4_cptr)(lt + (8 * g4 + 4 * hi) * 4);
@@ -1310,6 +1440,7 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                     s1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[r], c, -L1[e]));
                 }
             }
+#endif
             if (CAUSAL && tile < first_plain) {                       // pairs with kv > q contribute nothing (wave-uniform branch)
                 const int q0t = tile * kKvTile;
 #pragma unroll
@@ -1319,7 +1450,7 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                     if (kvrow > qi + 32) s1[r] = 0.f;
                 }
             }
-#if FA2_WIN
+#if FA2_WIN && !FA2_SMOD
             if (tile < first_plain || tile >= last_plain) {           // window: rows outside [q_lo, q_hi] do not see this lane's key
                 const int q0t = tile * kKvTile;
 #pragma unroll
@@ -1339,7 +1470,11 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                 xf[3][i] = pack2<BF16>(s1[8 + 2 * i], s1[8 + 2 * i + 1]);
             }
 #pragma unroll
+#if FA2_SMOD
+            for (int i = 0; i < 4; ++i) *(lds_u32x4_ptr)(xch + 1024 * i) = xg[i];
+#else
             for (int i = 0; i < 4; ++i) *(lds_u32x4_ptr)(xch + 1024 * i) = xf[i];
+#endif
             pair_mid_barrier();                                       // P is in the pair's slot
 #if FA2_DROP
             {

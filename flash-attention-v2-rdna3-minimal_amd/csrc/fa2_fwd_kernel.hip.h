@@ -69,6 +69,22 @@
 #if FA2_DROP
 #include "fa2_dropout.h"
 #endif
+// FA2_SMOD = 1 (scoremod_hip.cpp / varlen_scoremod_hip.cpp only, on top of FA2_WIN = 1): the score modifiers of fa2_scoremod.h — logit soft-capping and
+// ALiBi slopes — applied to every tile's scores as they leave the MFMA, before the band's masks.  The scores are then already scaled, so the factor of
+// the exp step is log2(e).  softcap, the slope pointer and its stride travel in a further kernel argument (FA2_SMOD_PARAM): the parameter blocks keep
+// their layout.
+#ifndef FA2_SMOD
+#define FA2_SMOD 0
+#endif
+#if FA2_SMOD && (!FA2_WIN || FA2_DROP)
+#error "FA2_SMOD builds on the FA2_WIN blocks and does not combine with FA2_DROP"
+#endif
+#if FA2_SMOD
+#include "fa2_scoremod.h"
+#define FA2_SMOD_PARAM , const ScoreMod smod
+#else
+#define FA2_SMOD_PARAM
+#endif
 
 // ---- tuning knobs (A/B-tested on MI355X with tools/kbench.py; numbers at B2 H16 N4096 D128 fp16) ----
 #ifndef FA2_DEFER_THR        // skip the O rescale while the row max grew by <= this (log2 units); <0: always rescale.
@@ -363,7 +379,7 @@ constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && 
 // computes only the tiles of its own 32 rows' range [tf_w, ntiles_w), tiles cut by the band's left or right edge are masked per lane (lim_lo, lim_hi)
 // and the tiles in between run the unmasked steady-state loop.  A row that sees no key ends with O = 0, lse = -inf (the BIAS kernels' convention).
 template <int HD, int HDV, bool BF16, bool CAUSAL, int NW, int QB, int BIAS = 0, int KSQ = HD / 16, int DTN = HDV / 32, bool RTD = false>
-__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP) {
+__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP FA2_SMOD_PARAM) {
 #if FA2_VARLEN
     FwdParams p = pk;         // (adjusted to the workgroup's sequence below: varlen_enter)
 #endif
@@ -535,7 +551,14 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
             for (int r = 0; r < 16; ++r) acc[qb][dt][r] = 0.f;
     }
     const float cs = p.c;                // factor of the raw Q.K^T product
+#if FA2_SMOD
+    const float c = kSmodLog2e;          // (the modified scores are scaled already, in natural units)
+    // this workgroup's slope (one scalar load; packed calls: b is the sequence) and this lane's row's key position
+    const float smod_slope = smod.slopes ? smod.slopes[(int64_t)b * smod.stride + h] : 0.f;
+    const int smod_pos = qrow[0] + win.off;
+#else
     const float c = BIAS ? 1.0f : p.c;   // factor still to be applied to a finished score (BIAS: already in log2 units)
+#endif
 
     // ---- attention bias (BIAS kernels): the 32 values of this lane's row in one KV tile, as loaded (raw words), in the register
     // order of the two score accumulators: element i = 16*half + 4*g + e <-> kv = kv0 + 32*half + 8*g + 4*hi + e, i.e. eight groups
@@ -898,6 +921,31 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         for (int qb = 0; qb < QB; ++qb) {
             f32x16& s0 = s[qb][0];
             f32x16& s1 = s[qb][1];
+#if FA2_SMOD
+            // x = raw * scale, then the cap, then the ALiBi term — on every tile, the plain ones included; the masks below come last.  Both switches
+            // are wave-uniform branches around a loop over the 32 scores (a call with one modifier does not pay for the other).
+            if (smod.softcap > 0.f) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float t;
+                    s0[r] = smod_cap(s0[r] * smod.scale, smod.softcap, smod.inv_softcap, &t);
+                    s1[r] = smod_cap(s1[r] * smod.scale, smod.softcap, smod.inv_softcap, &t);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { s0[r] *= smod.scale; s1[r] *= smod.scale; }
+            }
+            if (smod.slopes) {
+                // pos - j of register r: d - (r & 3) - 8 (r >> 2) (- 32); |.| is a source modifier of the fma (free, whatever the band)
+                const float d = (float)(smod_pos - (kv_first + tile * kKvTile + 4 * hi));
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float dr = d - (float)((r & 3) + 8 * (r >> 2));
+                    s0[r] = smod_alibi(s0[r], smod_slope, __builtin_fabsf(dr));
+                    s1[r] = smod_alibi(s1[r], smod_slope, __builtin_fabsf(dr - 32.0f));
+                }
+            }
+#endif
 #if FA2_WIN
             if constexpr (decltype(masked)::value) {
                 const int kv0 = kv_first + tile * kKvTile;       // (absolute key index: the limits are absolute)

@@ -8,6 +8,7 @@
 
 #include <atomic>
 
+#include "fa2_scoremod.h"
 #include "fa2_bwd_kernel.hip.h"      // FwdParams / BwdParams (templates are only instantiated where a launcher names them)
 
 #define FA2_HIDDEN __attribute__((visibility("hidden")))
@@ -197,6 +198,16 @@ FA2_HIDDEN int launch_fwd_varlen_dropout_f16(int HD, const FwdParams& p, int row
 FA2_HIDDEN int launch_fwd_varlen_dropout_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_varlen_dropout_f16(int HD, const BwdParams& p, hipStream_t stream);
 FA2_HIDDEN int launch_bwd_varlen_dropout_bf16(int HD, const BwdParams& p, hipStream_t stream);
+// score modifiers (scoremod_hip.cpp, varlen_scoremod_hip.cpp): the same launchers over the SMOD forms of the windowed and packed kernels, with the
+// ScoreMod block (fa2_scoremod.h: softcap, the ALiBi slope pointer and its stride) as a further kernel argument
+FA2_HIDDEN int launch_fwd_scoremod_f16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
+FA2_HIDDEN int launch_fwd_scoremod_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
+FA2_HIDDEN int launch_bwd_scoremod_f16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
+FA2_HIDDEN int launch_bwd_scoremod_bf16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
+FA2_HIDDEN int launch_fwd_varlen_scoremod_f16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
+FA2_HIDDEN int launch_fwd_varlen_scoremod_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
+FA2_HIDDEN int launch_bwd_varlen_scoremod_f16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
+FA2_HIDDEN int launch_bwd_varlen_scoremod_bf16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
 // hand-scheduled backward, head dim exactly 128 (bwd_asm.cpp); same `parts`
 // neg_delta: the dQ pass writes -delta (the hand-scheduled dK/dV pass reads it as such; the HIP dK/dV passes read +delta)
 // kfold: the dK / dV body whose P side folds scale * log2(e) into its K fragments (option "fold"; host.cpp: bwd_folds)

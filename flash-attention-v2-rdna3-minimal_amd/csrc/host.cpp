@@ -452,6 +452,10 @@ struct Call {                                // what a forward and a backward ca
     bool dropout = false;                    // always with a window, which may mask nothing: the seed and the threshold of fa2_dropout.h
     uint64_t seed = 0;
     uint32_t drop_t = 0;
+    bool scoremod = false;                   // softcap > 0 or ALiBi slopes (fa2_scoremod.h): always with a window, which may mask nothing; never with dropout
+    float softcap = 0.f;
+    const float* slopes = nullptr;           // device memory, f32 [.., H]
+    int64_t slope_stride = 0;                // elements between two batches' / sequences' slope vectors
     Ask ask = Ask::Launch;
     size_t* ws_need = nullptr;               // Ask::Size
 };
@@ -600,6 +604,15 @@ constexpr BwdFamilyLaunch kBwdFamily[2][2][2] = {
     {{fa2::launch_bwd_window_f16, fa2::launch_bwd_window_bf16}, {fa2::launch_bwd_dropout_f16, fa2::launch_bwd_dropout_bf16}},
     {{fa2::launch_bwd_varlen_f16, fa2::launch_bwd_varlen_bf16}, {fa2::launch_bwd_varlen_dropout_f16, fa2::launch_bwd_varlen_dropout_bf16}}};
 
+// ... and the score-modifier forms of the windowed / packed kernels, which take the ScoreMod block as well: [packed][bf16]
+using FwdSmodLaunch = int (*)(int HD, const fa2::FwdParams& p, int rows, hipStream_t stream, const fa2::ScoreMod& sm);
+using BwdSmodLaunch = int (*)(int HD, const fa2::BwdParams& p, hipStream_t stream, const fa2::ScoreMod& sm);
+constexpr FwdSmodLaunch kFwdSmod[2][2] = {{fa2::launch_fwd_scoremod_f16, fa2::launch_fwd_scoremod_bf16},
+                                          {fa2::launch_fwd_varlen_scoremod_f16, fa2::launch_fwd_varlen_scoremod_bf16}};
+constexpr BwdSmodLaunch kBwdSmod[2][2] = {{fa2::launch_bwd_scoremod_f16, fa2::launch_bwd_scoremod_bf16},
+                                          {fa2::launch_bwd_varlen_scoremod_f16, fa2::launch_bwd_varlen_scoremod_bf16}};
+fa2::ScoreMod scoremod_of(const Call& c) { return fa2::make_scoremod(c.softcap, c.scale, c.slopes, c.slope_stride); }
+
 // fa2_fwd_workspace_bytes.  The size query has no scale argument, and the split plan depends on the scale at head dim 64 (a launch that folds the
 // scale — c <= 1 — runs the parts inside the hand-scheduled kernel: other fixed costs, possibly another S): the answer is the larger of the two plans,
 // so a workspace of this size serves the call whatever its scale (the callers' caches are keyed without the scale).
@@ -651,6 +664,7 @@ int fwd_run(const FwdCall& c) {
     if (c.packed)
         if (int rc = check_packed_tensors(c)) return rc;
     hipStream_t stream = (hipStream_t)c.stream;
+    if (c.scoremod) return kFwdSmod[c.packed][bf16](HD, p, family_rows, stream, scoremod_of(c));
     if (c.windowed) return kFwdFamily[c.packed][c.dropout][bf16](HD, p, family_rows, stream);
     if (c.bias.kind != FA2_BIAS_NONE) return fa2::launch_fwd_hip(bf16, HD, p, causal, 128, true, stream);
     return launch_fwd(HD, bf16, p, causal, stream, c.ws, c.ws_bytes);
@@ -727,6 +741,7 @@ int bwd_run(const BwdCall& c) {
     if (c.packed)
         if (int rc = check_packed_tensors(c)) return rc;
     hipStream_t stream = (hipStream_t)c.stream;
+    if (c.scoremod) return kBwdSmod[c.packed][bf16](HD, p, stream, scoremod_of(c));
     if (c.windowed) return kBwdFamily[c.packed][c.dropout][bf16](HD, p, stream);
     if (c.bias.kind != FA2_BIAS_NONE) return fa2::launch_bwd_bias_hip(bf16, HD, p, causal, stream);
     return launch_bwd(HD, bf16, p, causal, stream);
@@ -741,8 +756,8 @@ int dense_window(Call& c, int flags, int left, int right, int q_offset) {
     const WindowCall w = reduce_window(c.Nq, c.Nkv, left, right, q_offset, (flags & FA2_FLAG_CAUSAL) != 0);
     if (w.kind < 0) return FA2_ERR_BAD_SHAPE;
     c.window = w.w;
-    c.windowed = c.dropout || w.kind == 2;
-    c.flags = c.dropout ? FA2_FLAG_EXACT_SCALE : (flags & FA2_FLAG_EXACT_SCALE) | (w.kind == 1 ? FA2_FLAG_CAUSAL : 0);
+    c.windowed = c.dropout || c.scoremod || w.kind == 2;        // (the score-modifier calls likewise: the SMOD forms are the only kernels with the transform)
+    c.flags = c.dropout || c.scoremod ? FA2_FLAG_EXACT_SCALE : (flags & FA2_FLAG_EXACT_SCALE) | (w.kind == 1 ? FA2_FLAG_CAUSAL : 0);
     return FA2_OK;
 }
 
@@ -750,6 +765,17 @@ void set_dropout_args(Call& c, float dropout_p, uint64_t seed) {       // (after
     c.dropout = true;
     c.seed = seed;
     c.drop_t = fa2::dropout_threshold(dropout_p, nullptr);
+}
+
+// The score-modifier entry points' own three arguments, checked ahead of everything else, in this order: softcap (negative, NaN, inf), the stride of
+// the slopes (negative), the slope pointer's alignment.  softcap == 0 and no slopes: nothing is set and the call IS the windowed / packed call.
+int set_scoremod_args(Call& c, float softcap, const float* slopes, int64_t stride) {
+    if (!fa2::softcap_ok(softcap)) return FA2_ERR_SOFTCAP;
+    if (stride < 0) return FA2_ERR_BAD_SHAPE;
+    if (reinterpret_cast<uintptr_t>(slopes) & 3u) return FA2_ERR_ALIGNMENT;
+    c.scoremod = softcap > 0.f || slopes != nullptr;
+    c.softcap = softcap; c.slopes = slopes; c.slope_stride = stride;
+    return FA2_OK;
 }
 
 // The packed entry points (c.B .. c.D by name already): what the host can check of such a call — the contents of cu_seqlens live on the device —, the window
@@ -768,7 +794,7 @@ int packed_call(Call& c, PackedStrides& ps, std::initializer_list<const int64_t*
     c.window.right = fa2::window_normalize_right(right, (flags & FA2_FLAG_CAUSAL) != 0);
     c.window.off = br ? 1 : 0;
     c.windowed = c.packed = true;
-    c.flags = c.dropout ? FA2_FLAG_EXACT_SCALE : flags & FA2_FLAG_EXACT_SCALE;
+    c.flags = c.dropout || c.scoremod ? FA2_FLAG_EXACT_SCALE : flags & FA2_FLAG_EXACT_SCALE;
     int i = 0;
     for (const int64_t* t : two) { ps.s[i][0] = 0; ps.s[i][1] = t[0]; ps.s[i][2] = t[1]; ++i; }
     ps.ls[0] = 0; ps.ls[1] = lse_stride;
@@ -878,6 +904,7 @@ const char* fa2_error_string(int code) {
         case FA2_ERR_GRID: return "fa2: B*H*ceil(Nq/256) exceeds the grid limit";
         case FA2_ERR_BIAS: return "fa2: bias_kind must be FA2_BIAS_{NONE,IO_DTYPE,F32,BOOL} and bias strides >= 0";
         case FA2_ERR_DROPOUT: return "fa2: dropout_p must be in [0, 1)";
+        case FA2_ERR_SOFTCAP: return "fa2: softcap must be 0 (off) or a finite positive number (a normal float: >= 1.18e-38)";
         default: break;
     }
     if (code > 0) return hipGetErrorString((hipError_t)code);
@@ -1218,6 +1245,68 @@ int fa2_bwd_varlen_dropout(int dtype, const void* q, const void* k, const void* 
         return rc;
     FA2_PACKED_BWD_FILL(c, ps);
     return bwd_run(c);
+}
+
+// ---- score modifiers (logit soft-capping, ALiBi slopes): include/fa2_gfx950.h has the contract, fa2_scoremod.h the arithmetic, scoremod_hip.cpp /
+// varlen_scoremod_hip.cpp the kernels.  With softcap > 0 or slopes these calls always take the SMOD forms of the windowed (packed) kernels, whatever the
+// window masks; with neither they are fa2_fwd_window / fa2_bwd_window / fa2_fwd_varlen / fa2_bwd_varlen.
+int fa2_fwd_scoremod(int dtype, FA2_FWD_ARGS(FA2_HKV), int window_left, int window_right, int q_offset, void* hip_stream, float softcap,
+                     const float* alibi_slopes, int64_t alibi_batch_stride) {
+    FA2_FWD_CALL(c);
+    if (int rc = set_scoremod_args(c, softcap, alibi_slopes, alibi_batch_stride)) return rc;
+    if (Hkv < 1) return FA2_ERR_BAD_SHAPE;
+    c.Hkv = Hkv;
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    return fwd_run(c);
+}
+
+int fa2_bwd_scoremod(int dtype, FA2_BWD_ARGS(), int window_left, int window_right, int q_offset, void* hip_stream, float softcap,
+                     const float* alibi_slopes, int64_t alibi_batch_stride) {
+    FA2_BWD_CALL(c);
+    if (int rc = set_scoremod_args(c, softcap, alibi_slopes, alibi_batch_stride)) return rc;
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    return bwd_run(c);
+}
+
+int fa2_fwd_varlen_scoremod(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
+                            int max_seqlen_q, int max_seqlen_k, int D, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                            const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                            int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream, float softcap,
+                            const float* alibi_slopes, int64_t alibi_batch_stride) {
+    FwdCall c;
+    PackedStrides ps;
+    if (int rc = set_scoremod_args(c, softcap, alibi_slopes, alibi_batch_stride)) return rc;
+    FA2_PACKED_FILL(c, Hkv);
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides}, lse_stride, flags, window_left, window_right)) return rc;
+    FA2_PACKED_FWD_FILL(c, ps);
+    return fwd_run(c);
+}
+
+int fa2_bwd_varlen_scoremod(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                            void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k,
+                            const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                            const int64_t do_strides[2], const int64_t dq_strides[2], const int64_t dk_strides[2], const int64_t dv_strides[2],
+                            int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream, float softcap,
+                            const float* alibi_slopes, int64_t alibi_batch_stride) {
+    BwdCall c;
+    PackedStrides ps;
+    if (int rc = set_scoremod_args(c, softcap, alibi_slopes, alibi_batch_stride)) return rc;
+    FA2_PACKED_FILL(c, H);
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides}, lse_stride, flags,
+                             window_left, window_right))
+        return rc;
+    FA2_PACKED_BWD_FILL(c, ps);
+    return bwd_run(c);
+}
+
+int fa2_scoremod_eval(float x, float softcap, float slope, int pos, int j, float* s, float* dfactor) {
+    if (!fa2::softcap_ok(softcap)) return FA2_ERR_SOFTCAP;
+    if (!s || !dfactor) return FA2_ERR_NULL_POINTER;
+    const int64_t d = (int64_t)pos - (int64_t)j;
+    const fa2::ScoreMod m = fa2::make_scoremod(softcap, 1.0f, nullptr, 0);
+    *s = fa2::smod_score(x, m.softcap, m.inv_softcap, slope, (float)(d < 0 ? -d : d), dfactor);
+    return FA2_OK;
 }
 
 int fa2_dropout_threshold(float dropout_p, float* p_eff) {

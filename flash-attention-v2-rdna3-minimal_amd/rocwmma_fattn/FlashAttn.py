@@ -70,12 +70,15 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, window=window)
 
     @staticmethod
-    def forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, flags, scale, window, dropout=None):
+    def forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, flags, scale, window, dropout=None, scoremod=None):
         """Packed, variable-length forward (extension: C-ABI fa2_fwd_varlen).  q [total_q, H, D], k / v [total_k, Hkv, D] (grouped K / V are addressed
         through the group), cu_seqlens_* int32 [B + 1] on q's device, the maxima host ints; flags = FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE |
         FA2_FLAG_BOTTOM_RIGHT; window = (window_left, window_right), -1 = unbounded.  Returns [O_fwd, q, k, v, O, L] like forward(): the tensors the
         backward wants (D padded to a multiple of 8 if need be; O_fwd a view of O), L = f32 [H, total_q] in log2 units.
-        dropout = (p, seed): attention dropout (C-ABI fa2_fwd_varlen_dropout)."""
+        dropout = (p, seed): attention dropout (C-ABI fa2_fwd_varlen_dropout).
+        scoremod = (softcap, slopes): logit soft-capping / ALiBi slopes [H] or [num_sequences, H] (C-ABI fa2_fwd_varlen_scoremod); not with dropout."""
+        if dropout is not None and scoremod is not None:
+            raise RuntimeError("fa2: the score modifiers do not combine with dropout")
         lib = _fa2_lib.load()
         h, h_kv, d = _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k)
         if q.dtype == torch.float16:
@@ -102,15 +105,19 @@ class _FlashAttnWmma:
                     max(int(max_seqlen_q), 1), max(int(max_seqlen_k), 1), d + d_pad, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
                     _s2(q), _s2(k), _s2(v), _s2(O), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]), _raw_stream(dev))
             with torch.cuda.device(dev):
-                rc = lib.fa2_fwd_varlen(*args) if dropout is None else lib.fa2_fwd_varlen_dropout(*args, float(dropout[0]), int(dropout[1]))
+                if scoremod is not None:
+                    rc = lib.fa2_fwd_varlen_scoremod(*args, *_scoremod_args(scoremod))
+                else:
+                    rc = lib.fa2_fwd_varlen(*args) if dropout is None else lib.fa2_fwd_varlen_dropout(*args, float(dropout[0]), int(dropout[1]))
             if rc:
                 _fa2_lib.check(rc)
         return [O[..., :d] if d_pad else O, q, k, v, O, L]
 
     @staticmethod
-    def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window, dropout=None):
+    def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window, dropout=None, scoremod=None):
         """backward() of forward_varlen (C-ABI fa2_bwd_varlen; grouped K / V: expanded, dK / dV summed per group in f32).  Returns [dQ, dK, dV].
-        dropout = (p, seed) of the forward: the mask is regenerated (fa2_bwd_varlen_dropout; it is keyed by the query head, so expansion changes nothing)."""
+        dropout = (p, seed) of the forward: the mask is regenerated (fa2_bwd_varlen_dropout; it is keyed by the query head, so expansion changes nothing).
+        scoremod = (softcap, slopes) of the forward (fa2_bwd_varlen_scoremod; the slopes belong to the query heads, so expansion changes nothing either)."""
         lib = _fa2_lib.load()
         if not (Q.is_cuda and dO.is_cuda):
             raise RuntimeError("fa2: tensors must be on a ROCm device (no CPU path in this operator)")
@@ -119,7 +126,7 @@ class _FlashAttnWmma:
         if h_kv != h:
             def mha(Q4, K4, V4, O4, dO4, L_, *rest):
                 return [t.unsqueeze(0) for t in _FlashAttnWmma.backward_varlen(Q4[0], K4[0], V4[0], O4[0], dO4[0], L_, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
-                                                                               max_seqlen_k, act_d, flags, scale, window, dropout)]
+                                                                               max_seqlen_k, act_d, flags, scale, window, dropout, scoremod)]
             return [t[0] for t in _grouped_backward(mha, Q.unsqueeze(0), K.unsqueeze(0), V.unsqueeze(0), O.unsqueeze(0), dO.unsqueeze(0), L, 0, 0, act_d,
                                                     128, 128, False, scale, True)]
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
@@ -141,13 +148,16 @@ class _FlashAttnWmma:
                 max(int(max_seqlen_k), 1), dk, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), _s2(Q), _s2(K), _s2(V), _s2(O), _s2(dO),
                 _s2(dQ), _s2(dK), _s2(dV), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]), _raw_stream(dev))
         with torch.cuda.device(dev):
-            rc = lib.fa2_bwd_varlen(*args) if dropout is None else lib.fa2_bwd_varlen_dropout(*args, float(dropout[0]), int(dropout[1]))
+            if scoremod is not None:
+                rc = lib.fa2_bwd_varlen_scoremod(*args, *_scoremod_args(scoremod))
+            else:
+                rc = lib.fa2_bwd_varlen(*args) if dropout is None else lib.fa2_bwd_varlen_dropout(*args, float(dropout[0]), int(dropout[1]))
         if rc:
             _fa2_lib.check(rc)
         return [dQ[..., :act_d], dK[..., :act_d], dV[..., :act_d]]
 
     @staticmethod
-    def forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None):
+    def forward_py(q, k, v, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None, scoremod=None):
         """Returns [O_fwd, q_pad, k_pad, v_pad, O, L] like forward_fp16/forward_bf16 (kernel_fp16.cu:744-876).
         O and L keep the reference's shapes — rows padded to a multiple of Br with a zero tail, O_fwd a view into
         O (kernel_fp16.cu:761, :793-796, :865-875) — but nothing is COPIED to get there: the gfx950 kernels mask
@@ -156,9 +166,12 @@ class _FlashAttnWmma:
         kernel_fp16.cu:767-779).  Only a D that is not a multiple of 8 is zero-padded, to the next multiple of 8.
         Br sizes the N padding of O and L; Bc is accepted for signature compatibility.  `causal`: the reference's bool, or the C-ABI's call flags
         (_fa2_lib.FA2_FLAG_CAUSAL | FA2_FLAG_EXACT_SCALE: the operator marks the forward of calls that will be differentiated).
-        dropout = (p, seed), with a window (which may be (-1, -1, 0)): attention dropout (C-ABI fa2_fwd_dropout)."""
+        dropout = (p, seed), with a window (which may be (-1, -1, 0)): attention dropout (C-ABI fa2_fwd_dropout).
+        scoremod = (softcap, slopes), with a window likewise: logit soft-capping / ALiBi slopes [H] or [B, H] (C-ABI fa2_fwd_scoremod); not with dropout."""
         if dropout is not None and (window is None or bias is not None):
             raise RuntimeError("fa2: the dropout forward is the windowed one (pass window=(-1, -1, 0) for full attention) and takes no bias")
+        if scoremod is not None and (window is None or bias is not None or dropout is not None):
+            raise RuntimeError("fa2: the score-modifier forward is the windowed one (pass window=(-1, -1, 0) for full attention) and takes neither bias nor dropout")
         if window is not None:
             window = _fa2_lib.parse_window((window[0], window[1]), window[2])
         lib = _fa2_lib.load()
@@ -233,7 +246,10 @@ class _FlashAttnWmma:
             bias_t, kind, bstr = _prepare_bias(bias, b, h, n, n_kv, q_pad.dtype, q.device)
             args += (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
             fn = lib.fa2_fwd_bias
-        if dropout is not None:    # attention dropout: fa2_fwd_dropout (the windowed call's arguments, then p and the seed)
+        if scoremod is not None:   # logit soft-capping / ALiBi: fa2_fwd_scoremod (the windowed call's arguments, then softcap, the slopes and their stride)
+            with torch.cuda.device(dev):
+                rc = lib.fa2_fwd_scoremod(*(args[:8] + (h_kv,) + args[8:]), *window, _raw_stream(dev), *_scoremod_args(scoremod))
+        elif dropout is not None:  # attention dropout: fa2_fwd_dropout (the windowed call's arguments, then p and the seed)
             with torch.cuda.device(dev):
                 rc = lib.fa2_fwd_dropout(*(args[:8] + (h_kv,) + args[8:]), *window, _raw_stream(dev), float(dropout[0]), int(dropout[1]))
         elif window is not None:   # sliding window: fa2_fwd_window (grouped or not: K / V addressed through the group)
@@ -271,11 +287,14 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias)
 
     @staticmethod
-    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None):
+    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None, scoremod=None):
         """backward() in Python (masked calls; every call when the compiled front end is absent).  window: as forward_window's.
         dropout = (p, seed) of the forward: the mask is regenerated (fa2_bwd_dropout; it is keyed by the query head, so expanding grouped K / V changes nothing)."""
         if dropout is not None and (window is None or bias is not None):
             raise RuntimeError("fa2: the dropout backward is the windowed one (pass window=(-1, -1, 0) for full attention) and takes no bias")
+        # scoremod = (softcap, slopes) of the forward (fa2_bwd_scoremod; the slopes belong to the query heads, so expanding grouped K / V changes nothing)
+        if scoremod is not None and (window is None or bias is not None or dropout is not None):
+            raise RuntimeError("fa2: the score-modifier backward is the windowed one (pass window=(-1, -1, 0) for full attention) and takes neither bias nor dropout")
         if window is not None:
             window = _fa2_lib.parse_window((window[0], window[1]), window[2])
         lib = _fa2_lib.load()
@@ -288,7 +307,7 @@ class _FlashAttnWmma:
         if h_kv != h:
             if bias is not None:
                 raise RuntimeError("fa2: the masked backward has no grouped-query form (flash_attention(mask=...) expands k / v for it)")
-            mha = _FlashAttnWmma.backward_py if window is None else (lambda *a: _FlashAttnWmma.backward_py(*a, window=window, dropout=dropout))
+            mha = _FlashAttnWmma.backward_py if window is None else (lambda *a: _FlashAttnWmma.backward_py(*a, window=window, dropout=dropout, scoremod=scoremod))
             return _grouped_backward(mha, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH)
         act_n, act_nkv, act_d = int(act_n), int(act_nkv), int(act_d)
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
@@ -332,6 +351,9 @@ class _FlashAttnWmma:
         if dropout is not None:
             args += (float(dropout[0]), int(dropout[1]))
             fn = lib.fa2_bwd_dropout
+        if scoremod is not None:
+            args += _scoremod_args(scoremod)
+            fn = lib.fa2_bwd_scoremod
         if Q.device.index != _current_device():
             with torch.cuda.device(Q.device):
                 rc = fn(*args)
@@ -733,6 +755,90 @@ class _DropoutAttentionFunction(torch.autograd.Function):
         return dQ, dK, dV, None, None, None, None, None
 
 
+class _ScoreModAttentionFunction(torch.autograd.Function):
+    """autograd node of flash_attention(softcap > 0 or alibi_slopes): forward = fa2_fwd_scoremod, backward = fa2_bwd_scoremod; saves the window, softcap and
+    the slopes, which are constants of the call (no gradient, as in flash-attn)."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, q, k, v, slopes, causal, scale, BNHD_fmt, window, softcap):
+        D = q.shape[3]
+        Br = 32 if D > 384 else 64                      # FlashAttn.py:56-67
+        flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | _fa2_lib.FA2_FLAG_EXACT_SCALE
+        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_py(q, k, v, Br, 128, flags, scale, BNHD_fmt, window=window, scoremod=(softcap, slopes))
+        n_ax = 1 if BNHD_fmt else 2
+        ctx.args = (causal, scale, q.shape[n_ax], k.shape[n_ax], D, BNHD_fmt, window, softcap, slopes is not None)
+        ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L, *(() if slopes is None else (slopes,)))
+        return o
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, do):
+        causal, scale, N, Nkv, D, BNHD_fmt, window, softcap, has_slopes = ctx.args
+        q, k, v, o, L = ctx.saved_tensors[:5]
+        slopes = ctx.saved_tensors[5] if has_slopes else None
+        dQ, dK, dV = flash_attn_wmma.backward_py(q, k, v, o, do, L, N, Nkv, D, 128, 128, causal, scale, BNHD_fmt, window=window, scoremod=(softcap, slopes))
+        return dQ, dK, dV, None, None, None, None, None, None
+
+
+class _VarlenScoreModAttentionFunction(torch.autograd.Function):
+    """autograd node of flash_attention_varlen(softcap > 0 or alibi_slopes): forward = fa2_fwd_varlen_scoremod, backward = fa2_bwd_varlen_scoremod."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, q, k, v, slopes, cu_q, cu_k, max_q, max_k, flags, scale, window, softcap):
+        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_varlen(q, k, v, cu_q, cu_k, max_q, max_k, flags | _fa2_lib.FA2_FLAG_EXACT_SCALE, scale, window,
+                                                                          scoremod=(softcap, slopes))
+        ctx.args = (max_q, max_k, q.shape[2], flags, scale, window, softcap, slopes is not None)
+        ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L, cu_q, cu_k, *(() if slopes is None else (slopes,)))
+        return o
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, do):
+        max_q, max_k, D, flags, scale, window, softcap, has_slopes = ctx.args
+        q, k, v, o, L, cu_q, cu_k = ctx.saved_tensors[:7]
+        slopes = ctx.saved_tensors[7] if has_slopes else None
+        dQ, dK, dV = flash_attn_wmma.backward_varlen(q, k, v, o, do, L, cu_q, cu_k, max_q, max_k, D, flags, scale, window, scoremod=(softcap, slopes))
+        return dQ, dK, dV, None, None, None, None, None, None, None, None, None
+
+
+SOFTCAP_MESSAGE = "fa2: softcap must be 0 (off) or a finite positive number (a normal float32: >= 1.18e-38)"
+_SOFTCAP_MIN = 2.0 ** -126          # the smallest normal float32: below it 1 / softcap overflows (the library answers FA2_ERR_SOFTCAP)
+ALIBI_MESSAGE = "fa2: alibi_slopes must be a float32 tensor on q's device, shaped [H] or [B, H] (packed calls: [H] or [num_sequences, H])"
+
+
+def _parse_scoremod(softcap, alibi_slopes, q, h, nb):
+    """The operator's softcap / alibi_slopes arguments -> None (both off) or (softcap, slopes).  h: query heads, nb: batches (packed calls: sequences).
+    Raises ValueError before any device work."""
+    try:
+        cap = float(softcap)
+    except (TypeError, ValueError):
+        raise ValueError(SOFTCAP_MESSAGE + ", got %r" % (softcap,))
+    if isinstance(softcap, bool) or not (cap == 0.0 or _SOFTCAP_MIN <= cap <= 3.0e38):           # (NaN fails the comparisons)
+        raise ValueError(SOFTCAP_MESSAGE + ", got %r" % (softcap,))
+    if alibi_slopes is not None:
+        a = alibi_slopes
+        if not torch.is_tensor(a) or a.dtype != torch.float32 or a.device != q.device or tuple(a.shape) not in ((h,), (nb, h)):
+            got = "%s %s on %s" % (tuple(a.shape), a.dtype, a.device) if torch.is_tensor(a) else repr(a)
+            raise ValueError(ALIBI_MESSAGE + "; H = %d, B = %d, q on %s, got %s" % (h, nb, q.device, got))
+    if cap == 0.0 and alibi_slopes is None:
+        return None
+    if alibi_slopes is not None and not alibi_slopes.is_contiguous():
+        alibi_slopes = alibi_slopes.contiguous()       # once, here: this is the tensor the launches read and the autograd node saves for the backward
+    return (cap, alibi_slopes)
+
+
+def _scoremod_args(scoremod):
+    """(softcap, slopes) -> the three trailing arguments of the C-ABI's score-modifier entry points."""
+    cap, a = scoremod
+    if a is None:
+        return (float(cap), None, 0)
+    if not a.is_contiguous():      # (_parse_scoremod hands over a contiguous tensor; a temporary made here would be freed before the launch)
+        raise RuntimeError("fa2: the slope tensor of a score-modifier call must be contiguous")
+    return (float(cap), a.data_ptr(), a.stride(0) if a.dim() == 2 else 0)
+
+
 DROPOUT_MESSAGE = "fa2: dropout_p must be a number in [0, 1)"
 
 
@@ -771,7 +877,7 @@ def dropout_keep_mask(seed, p, B, H, Nq, Nkv):
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=False, scale=None, window=None,
-                           bottom_right=False, dropout_p=0.0, dropout_seed=None):
+                           bottom_right=False, dropout_p=0.0, dropout_seed=None, softcap=0.0, alibi_slopes=None):
     """Packed, variable-length attention: B sequences of individual lengths in one buffer (the flash_attn_varlen_func shape).
     q [total_q, H, D], k / v [total_k, Hkv, D] (Hkv divides H: grouped K / V are not expanded); cu_seqlens_q / cu_seqlens_k: int32 [B + 1] on q's
     device, non-decreasing — sequence s owns the rows [cu[s], cu[s+1]); zero-length sequences are fine.  Returns [total_q, H, D].
@@ -782,9 +888,18 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     key position i (top-left, this library's convention) or, with bottom_right=True, at i + Nkv_s - Nq_s (other libraries' causal convention; a
     sequence with fewer keys than queries then has leading rows that see nothing).  Rows that see no key return zeros.
     Differentiable in q, k, v (C-ABI fa2_fwd_varlen / fa2_bwd_varlen): no atomics, deterministic gradients.
-    dropout_p / dropout_seed: attention dropout as flash_attention's; the mask is keyed by the sequence index and the positions inside the sequence."""
+    dropout_p / dropout_seed: attention dropout as flash_attention's; the mask is keyed by the sequence index and the positions inside the sequence.
+    softcap / alibi_slopes: as flash_attention's; the slopes are [H] or [num_sequences, H], the positions count inside the sequence (row i at i, or at
+    i + Nkv_s - Nq_s with bottom_right=True).  Not together with dropout_p > 0 (ValueError)."""
     dropout = None if dropout_p.__class__ is float and dropout_p == 0.0 else _parse_dropout(dropout_p, dropout_seed)      # (the default: no work)
     left, right, _ = _fa2_lib.parse_window(window, 0)
+    smod = None
+    if not (softcap.__class__ is float and softcap == 0.0 and alibi_slopes is None):                                      # (the default: no work)
+        if not (torch.is_tensor(q) and q.dim() == 3 and torch.is_tensor(cu_seqlens_q) and cu_seqlens_q.dim() == 1):
+            raise RuntimeError("fa2: q must be [total_q, H, D] and cu_seqlens_q a 1-D tensor")
+        smod = _parse_scoremod(softcap, alibi_slopes, q, q.shape[1], cu_seqlens_q.numel() - 1)
+        if smod is not None and dropout is not None:
+            raise ValueError("fa2: flash_attention_varlen(softcap / alibi_slopes, dropout_p > 0) is not supported: the score modifiers do not combine with dropout")
     h, h_kv, D = _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k)
     if max_seqlen_q is None:
         max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max())
@@ -793,6 +908,12 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     if scale is None:
         scale = D ** -0.5
     flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | (_fa2_lib.FA2_FLAG_BOTTOM_RIGHT if bottom_right else 0)
+    if smod is not None:
+        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+            return _VarlenScoreModAttentionFunction.apply(q, k, v, smod[1], cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale,
+                                                          (left, right), smod[0])
+        return flash_attn_wmma.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags | _fa2_lib.FA2_FLAG_EXACT_SCALE,
+                                              scale, (left, right), scoremod=smod)[0]
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         if dropout is not None:
             return _VarlenAttentionFunction.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right), dropout)
@@ -817,7 +938,8 @@ def _band_mask(nq, nkv, window, causal, device):
     return keep
 
 
-def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False, window=None, q_offset=0, dropout_p=0.0, dropout_seed=None):
+def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False, window=None, q_offset=0, dropout_p=0.0, dropout_seed=None,
+                    softcap=0.0, alibi_slopes=None):
     """Forward attention that HONOURS `mask` — the extension the reference lists as to do (README.md:45; its
     FlashAttentionFunction accepts the argument and ignores it, FlashAttn.py:49, :74, and `FlashAttentionFunction.apply` here
     keeps doing exactly that so that existing call sites see no change).  `mask` follows
@@ -837,8 +959,35 @@ def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False
     exists.  It applies whenever dropout_p > 0, whatever the grad mode (as SDPA); dropout_p == 0 takes exactly the path it takes without the argument.
     dropout_seed=None draws a seed from torch's CPU default generator (torch.manual_seed reproduces a run).  Works with causal, window, q_offset and
     grouped k / v (C-ABI fa2_fwd_dropout / fa2_bwd_dropout, every head dim up to 512).  Limits: the seed is a host value, so a call captured in a
-    graph replays the same mask; `mask=` together with dropout_p > 0 is not supported (ValueError)."""
+    graph replays the same mask; `mask=` together with dropout_p > 0 is not supported (ValueError).
+
+    `softcap` / `alibi_slopes`: the two keywords of flash_attn_func that change the score itself, applied between Q.K^T and the softmax:
+    s = softcap * tanh(scale * q.k / softcap) when softcap > 0 (Gemma-2 / -3, Grok), then s -= slope[b, h] * |i + q_offset - j| when alibi_slopes is
+    given (BLOOM, MPT, Baichuan) — a float32 tensor on q's device, [H] or [B, H], one slope per QUERY head, no gradient —, then the causal / window
+    masks.  No [Nq, Nkv] tensor exists; works with causal, window, q_offset and grouped k / v, differentiable in q, k, v (C-ABI fa2_fwd_scoremod /
+    fa2_bwd_scoremod, every head dim up to 512).  softcap=0.0, alibi_slopes=None: exactly the path taken without the arguments.  Not together with
+    `mask=` or dropout_p > 0 (ValueError)."""
     dropout = None if dropout_p.__class__ is float and dropout_p == 0.0 else _parse_dropout(dropout_p, dropout_seed)      # (the default: no work)
+    if not (softcap.__class__ is float and softcap == 0.0 and alibi_slopes is None):                                      # (the default: no work)
+        if not (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)) or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+            raise RuntimeError("fa2: q, k, v must be 4-D ([B,H,N,D] or [B,N,H,D] with BNHD_fmt)")
+        smod = _parse_scoremod(softcap, alibi_slopes, q, q.shape[2 if BNHD_fmt else 1], q.shape[0])
+        if smod is not None:
+            if mask is not None:
+                raise ValueError("fa2: flash_attention(mask=..., softcap / alibi_slopes) is not supported: the score modifiers run on the unmasked / windowed kernels only")
+            if dropout is not None:
+                raise ValueError("fa2: flash_attention(softcap / alibi_slopes, dropout_p > 0) is not supported: the score modifiers do not combine with dropout")
+            win = _fa2_lib.parse_window(window if window is not None else (-1, -1), q_offset)
+            if not q.is_cuda or not k.is_cuda or not v.is_cuda:
+                raise RuntimeError("fa2: q, k, v must be on a ROCm device (no CPU path in this operator)")
+            D = q.shape[3]
+            if scale is None:
+                scale = D ** -0.5
+            if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+                return _ScoreModAttentionFunction.apply(q, k, v, smod[1], bool(causal), scale, BNHD_fmt, win, smod[0])
+            Br = 32 if D > 384 else 64                      # FlashAttn.py:56-67
+            flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | _fa2_lib.FA2_FLAG_EXACT_SCALE
+            return flash_attn_wmma.forward_py(q, k, v, Br, 128, flags, scale, BNHD_fmt, window=win, scoremod=smod)[0]
     if dropout is not None:
         if mask is not None:
             raise ValueError("fa2: flash_attention(mask=..., dropout_p > 0) is not supported: dropout runs on the unmasked / windowed kernels only")

@@ -109,6 +109,15 @@ SYMBOLS = {
                                [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_uint64]),
     "fa2_bwd_varlen_dropout": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [_i64p] * 8 +
                                [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_uint64]),
+    # score modifiers (logit soft-capping, ALiBi slopes): the windowed / packed argument lists, then (float softcap, const float* alibi_slopes, int64_t stride)
+    "fa2_fwd_scoremod": (ctypes.c_int, [ctypes.c_int] + _FWD_ARGTYPES[:7] + [ctypes.c_int] + _FWD_ARGTYPES[7:-1] + [ctypes.c_int] * 3 + [ctypes.c_void_p] +
+                         [ctypes.c_float, ctypes.c_void_p, ctypes.c_int64]),
+    "fa2_bwd_scoremod": (ctypes.c_int, [ctypes.c_int] + _BWD_ARGTYPES[:-1] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_void_p, ctypes.c_int64]),
+    "fa2_fwd_varlen_scoremod": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 2 + [_i64p] * 4 +
+                                [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_void_p, ctypes.c_int64]),
+    "fa2_bwd_varlen_scoremod": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [_i64p] * 8 +
+                                [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_void_p, ctypes.c_int64]),
+    "fa2_scoremod_eval": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 2),
     "fa2_dropout_keep_mask": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 4 + [ctypes.c_void_p]),
     "fa2_dropout_threshold": (ctypes.c_int, [ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
     "fa2_philox4x32_10": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32)] * 3),

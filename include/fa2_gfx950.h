@@ -92,6 +92,7 @@ extern "C" {
 #define FA2_ERR_GRID          -7   /* B*H*ceil(Nq/256) exceeds the 2^31-1 grid limit */
 #define FA2_ERR_BIAS          -8   /* unknown bias_kind or a negative bias stride */
 #define FA2_ERR_DROPOUT       -9   /* dropout_p < 0, >= 1 or NaN (the dropout entry points) */
+#define FA2_ERR_SOFTCAP       -10  /* softcap < 0, NaN or inf (the score-modifier entry points) */
 
 /* bias_kind codes for fa2_fwd_bias */
 #define FA2_BIAS_NONE     0   /* no bias: the call is fa2_fwd */
@@ -475,6 +476,73 @@ int fa2_bwd_varlen_dropout(int dtype, const void* q, const void* k, const void* 
 int fa2_dropout_keep_mask(uint64_t seed, float dropout_p, int H, int b, int h, int64_t i0, int64_t i1, int64_t j0, int64_t j1, uint8_t* mask);
 int fa2_dropout_threshold(float dropout_p, float* p_eff);
 int fa2_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+
+/*
+ * Score modifiers — logit soft-capping and ALiBi slopes: the windowed and the packed entry points with three further arguments.
+ *   fa2_fwd_scoremod / fa2_bwd_scoremod               fa2_fwd_window's / fa2_bwd_window's argument lists, then
+ *   fa2_fwd_varlen_scoremod / fa2_bwd_varlen_scoremod  fa2_fwd_varlen's / fa2_bwd_varlen's argument lists, then
+ *       float softcap, const float* alibi_slopes, int64_t alibi_batch_stride
+ * Everything those entry points document holds (window_left = window_right = -1, q_offset = 0 is full attention; grouped K / V in the forward, the
+ * multi-head backward; layouts; validation order).
+ * Contract (csrc/fa2_scoremod.h has the arithmetic).  For query row i at key position pos = i + q_offset (packed: i + the sequence's offset — 0, or
+ * Nkv_s - Nq_s under FA2_FLAG_BOTTOM_RIGHT) and key j:
+ *     x  = (q_i . k_j) * scale                          f32: the MFMA product scaled in f32 (contract 0)
+ *     s  = softcap > 0 ? softcap * tanh(x / softcap) : x
+ *     s += alibi_slopes ? -slope[b, h] * |pos - j| : 0  h = the QUERY head; b = the batch, or the sequence of a packed call;
+ *                                                       slope[b, h] = alibi_slopes[b * alibi_batch_stride + h]
+ *     s  = -inf outside the band (window / causal / Nkv): the masks come LAST (tanh(-inf) = -1: capping a masked score would un-mask it)
+ * The softmax state, the LSE (log2 units) and P are those of s.  Rows that see no key return zeros and lse = -inf.
+ * Backward, with t = tanh(x / softcap): P is recomputed from s and the saved LSE, dS = P o (dP - delta), dX = dS o (1 - t^2) (f32, then rounded to the
+ * I/O dtype for the dX.K and dX^T.Q products), dQ = scale dX K, dK = scale dX^T Q; dV is unchanged.  (The wave-pair dK / dV pass of head dims 65 .. 128
+ * hands round16(P o (1 - t^2)) from one wave to the other: there dX = round16(round16(P (1 - t^2)) o (dP - delta)).)  The slopes are constants of the
+ * call and get no gradient.
+ * softcap = 0 means off; softcap < 0, NaN, inf or a positive value below the smallest normal float (1.18e-38: its reciprocal overflows): FA2_ERR_SOFTCAP,
+ * reported before anything else is looked at.  Slopes of either sign are served.  alibi_slopes: f32 in device memory, one
+ * value per QUERY head, NULL = off; alibi_batch_stride = elements between the vectors of two batches / sequences, 0 = one [H] vector for all; a negative
+ * stride is FA2_ERR_BAD_SHAPE and a pointer that is not 4-byte aligned FA2_ERR_ALIGNMENT — these two come next, in this order, before the checks of
+ * the windowed / packed call.
+ * With softcap == 0 and alibi_slopes == NULL the call IS the windowed / packed call of the same arguments: same kernels, bit-identical results.
+ * Otherwise it always runs the score-modifier kernels (FA2_SMOD forms of the compiler-scheduled windowed / packed kernels, every head dim up to 512,
+ * contract 0), whatever the window masks.  Not combined with dropout or a bias.
+ */
+int fa2_fwd_scoremod(int dtype,
+                     const void* q, const void* k, const void* v, void* o, float* lse,
+                     int B, int H, int Hkv, int Nq, int Nkv, int D,
+                     const int64_t q_strides[3], const int64_t k_strides[3],
+                     const int64_t v_strides[3], const int64_t o_strides[3],
+                     const int64_t lse_strides[2],
+                     float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream,
+                     float softcap, const float* alibi_slopes, int64_t alibi_batch_stride);
+int fa2_bwd_scoremod(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                     void* dq, void* dk, void* dv, float* delta_ws,
+                     int B, int H, int Nq, int Nkv, int D,
+                     const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                     const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                     const int64_t dk_strides[3], const int64_t dv_strides[3], const int64_t lse_strides[2],
+                     float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream,
+                     float softcap, const float* alibi_slopes, int64_t alibi_batch_stride);
+int fa2_fwd_varlen_scoremod(int dtype,
+                            const void* q, const void* k, const void* v, void* o, float* lse,
+                            int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k,
+                            const int64_t q_strides[2], const int64_t k_strides[2],
+                            const int64_t v_strides[2], const int64_t o_strides[2],
+                            int64_t lse_stride,
+                            float scale, int flags, int window_left, int window_right, void* hip_stream,
+                            float softcap, const float* alibi_slopes, int64_t alibi_batch_stride);
+int fa2_bwd_varlen_scoremod(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                            void* dq, void* dk, void* dv, float* delta_ws,
+                            int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k,
+                            const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2],
+                            const int64_t o_strides[2], const int64_t do_strides[2], const int64_t dq_strides[2],
+                            const int64_t dk_strides[2], const int64_t dv_strides[2], int64_t lse_stride,
+                            float scale, int flags, int window_left, int window_right, void* hip_stream,
+                            float softcap, const float* alibi_slopes, int64_t alibi_batch_stride);
+/* Host-only (no GPU needed): the transform itself, through the inline functions the kernels call.  *s = the modified score of the scaled score x
+ * for key position pos and key j (slope 0: no ALiBi term), *dfactor = ds / dx = 1 - tanh^2(x / softcap) (1 when softcap == 0).
+ * FA2_ERR_SOFTCAP, FA2_ERR_NULL_POINTER. */
+int fa2_scoremod_eval(float x, float softcap, float slope, int pos, int j, float* s, float* dfactor);
 
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
