@@ -58,6 +58,7 @@ UNITS = [
     ("scoremod_hip_bf16", "scoremod_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("varlen_scoremod_hip_f16", "varlen_scoremod_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("varlen_scoremod_hip_bf16", "varlen_scoremod_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("merge_hip", "merge_hip.cpp", []),          # both dtypes in one unit
 ]
 FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end of the operator (host-only C++, g++)
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")

@@ -60,7 +60,19 @@ struct BwdParams {
     // grouped-query attention (fa2_bwd_gqa): Q head h reads K / V head h / kv_group; the dK / dV passes own the H / kv_group K / V heads and sum
     // the gradients of their kv_group member Q heads in-kernel (1: one K / V head per Q head)
     int kv_group = 1;
+    // gradient of the loss with respect to the forward's LSE (fa2_bwd_lse / fa2_bwd_window_lse / fa2_bwd_varlen_lse), f32 in log2 units like `lse`, with
+    // strides of its own (batch, head; rows contiguous).  Null = off.  d lse_i / d s_ij = P_ij, so dS = P (dP - delta + log2(e) dlse): the dQ passes
+    // subtract log2(e) * dlse from the row's delta once, in their prologue, before they use it and before they store it for the dK / dV passes.
+    const float* dlse = nullptr;
+    int64_t dls[2] = {0, 0};
 };
+
+// delta_i - log2(e) * dlse_i for the lane's row (the dQ passes' prologue).  A row that saw no key (saved lse == -inf) ignores its dlse, whatever it holds.
+__device__ __forceinline__ float delta_with_dlse(const BwdParams& p, float Dq, float lse_row, int b, int h, int row) {
+    if (p.dlse == nullptr) return Dq;
+    const float g = p.dlse[b * p.dls[0] + h * p.dls[1] + row];
+    return lse_row == -__builtin_inff() ? Dq : __builtin_fmaf(-1.4426950408889634f, g, Dq);
+}
 
 #if FA2_VARLEN
 // Packed (variable-length) backward (fa2_bwd_varlen): the backward's twin of the forward's varlen_enter (fa2_fwd_kernel.hip.h) — cu_seqlens_q in `bias`,
@@ -77,6 +89,7 @@ __device__ __forceinline__ bool varlen_enter(BwdParams& p, Window& win, int s, i
     p.dq = (uint16_t*)p.dq + (int64_t)v.q_base * p.dqs[2];
     p.lse += v.q_base;
     p.delta += v.q_base;
+    if (p.dlse != nullptr) p.dlse += v.q_base;
     p.k = (const uint16_t*)p.k + (int64_t)v.k_base * p.ks[2];
     p.v = (const uint16_t*)p.v + (int64_t)v.k_base * p.vs[2];
     p.dk = (uint16_t*)p.dk + (int64_t)v.k_base * p.dks[2];
@@ -377,6 +390,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
         }
     }
     float Lq = p.lse[b * p.ls[0] + h * p.ls[1] + qr];
+    const float Lq_saved = Lq;
     if (BIAS && Lq == -__builtin_inff()) Lq = __builtin_inff();        // fully masked row: every P below becomes 2^(-inf) = 0
     // D_i = sum_d dO[i,d] * O[i,d] (the reference's `Di`, kernel_fp16.cu:605-631) for the lane's own row, from the dO
     // fragments already in registers; stored to the delta workspace for the dK pass that follows on the stream.
@@ -388,7 +402,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || HD <= 128) ? 2 : 1) void bwd_d
         for (int ks = 0; ks < KS; ++ks) {
             if (16 * ks + 8 * hi < p.D) dsum += dot8<BF16>(*(const u32x4*)(orow + 16 * ks + 8 * hi), gf[ks]);
         }
-        Dq = half_swap_sum(dsum);
+        Dq = delta_with_dlse(p, half_swap_sum(dsum), Lq_saved, b, h, qr);
         if (hi == 0 && qrow < p.Nq && vcol0 == 0 && part <= 0) p.delta[b * p.ls[0] + h * p.ls[1] + qrow] = Dq;
     }
 

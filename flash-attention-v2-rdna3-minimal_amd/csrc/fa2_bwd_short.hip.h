@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256, (HD <= 64 ? 3 : 2)) void bwd_short_dq_kernel(c
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
             if (16 * ks + 8 * hi < p.D) dsum += dot8<BF16>(*(const u32x4*)(orow + 16 * ks + 8 * hi), gf[ks]);
-        Dq = half_swap_sum(dsum);
+        Dq = delta_with_dlse(p, half_swap_sum(dsum), Lq, b, h, qr);
         if (hi == 0 && qrow < p.Nq) p.delta[b * p.ls[0] + h * p.ls[1] + qrow] = neg_delta ? -Dq : Dq;
     }
     __syncthreads();

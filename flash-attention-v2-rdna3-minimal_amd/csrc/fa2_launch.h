@@ -236,6 +236,26 @@ inline int launch_bwd_bias_hip(bool bf16, int HD, const BwdParams& p, bool causa
     return bf16 ? launch_bwd_bias_hip_bf16(HD, p, causal, stream) : launch_bwd_bias_hip_f16(HD, p, causal, stream);
 }
 
+// merge of partial attention results (merge_hip.cpp; fa2_merge_fwd / fa2_merge_bwd): the kernels' argument block.  The parts' pointers travel BY VALUE
+// (host arrays copied in here: no device copy, graph-capturable); every part shares one stride set.  Element strides {batch, head, row} / {batch, head}.
+constexpr int kMergeMaxParts = 16;
+struct MergeParams {
+    const void* o_parts[kMergeMaxParts];
+    const float* lse_parts[kMergeMaxParts];
+    void* do_parts[kMergeMaxParts];          // backward: gradients of the parts
+    float* dlse_parts[kMergeMaxParts];
+    void* o;                                 // forward: the merged result
+    float* lse;                              // forward: written; backward: read
+    const void* dout;                        // backward
+    const float* dlse;                       // backward, may be null (= zeros)
+    int nparts, B, H, Nq, D, natural;        // natural: the LSEs are natural-log (FA2_MERGE_NATURAL_LSE), else log2
+    int64_t ps[3], pls[2], os[3], ls[2], dos[3], dls[2], dps[3], dpls[2];
+    int lanes, group;                        // launcher: D / 8 lanes own a row's granules, inside a group of the next power of two lanes
+    int64_t rows;                            // launcher: B * H * Nq
+};
+FA2_HIDDEN int launch_merge_fwd(bool bf16, MergeParams& p, hipStream_t stream);
+FA2_HIDDEN int launch_merge_bwd(bool bf16, MergeParams& p, hipStream_t stream);
+
 constexpr int kBwdAsmParts = 3;      // passes the hand-scheduled backward covers: bit 0 = dQ, bit 1 = dK / dV
 
 }  // namespace fa2

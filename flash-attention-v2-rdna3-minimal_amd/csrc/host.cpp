@@ -367,6 +367,9 @@ BwdPlan plan_bwd(int HD, bool bf16, const fa2::BwdParams& p, bool causal) {
     const int m = asm_mask();
     int asm_parts = 0;
     if (HD == 128 && p.D == 128 && (m & 2)) asm_parts = 3 & ~((m >> 2) & 3) & fa2::kBwdAsmParts;
+    // a call with a gradient for the LSE (fa2_bwd_lse): the generated dQ bodies form delta themselves and know no dlse, and the hand-scheduled dK / dV pass
+    // only goes with the hand-scheduled dQ pass — both passes are the compiler-scheduled ones (teaching the generators is the follow-up: DESIGN)
+    if (p.dlse) asm_parts = 0;
     // row pitches the generated bodies' LDS-DMA offset arithmetic holds for (asm_pitch_ok): the dQ pass stages K and V, the dK / dV pass Q and dO
     if (!asm_pitch_ok(p.ks[2], 128) || !asm_pitch_ok(p.vs[2], 128)) asm_parts &= ~1;
     if (!asm_pitch_ok(p.qs[2], 128) || !asm_pitch_ok(p.dos[2], 128)) asm_parts &= ~2;
@@ -472,6 +475,8 @@ struct BwdCall : Call {
     void *dq = nullptr, *dk = nullptr, *dv = nullptr;
     float* delta_ws = nullptr;
     fa2_bwd_plan_t* plan = nullptr;          // Ask::Plan
+    const float* dlse = nullptr;             // optional: the gradient of the LSE (the *_lse entry points; a plan query: any non-null value = "has one")
+    const int64_t* dlses = nullptr;          // ... and its strides {batch, head} (packed: {0, head}); checked last
     const int64_t *qs = nullptr, *ks = nullptr, *vs = nullptr, *os = nullptr, *dos = nullptr, *dqs = nullptr, *dks = nullptr, *dvs = nullptr, *ls = nullptr;
 };
 
@@ -717,6 +722,19 @@ int bwd_validate(const BwdCall& c, fa2::BwdParams& p, int& HD) {
     p.ws_bytes = c.ws_bytes;
     p.kv_group = H / c.Hkv;
     if (c.windowed) set_family(p, c);
+    p.dlse = c.dlse;
+    return FA2_OK;
+}
+
+// The dlse arguments of the *_lse entry points, checked after everything else: alignment of the pointer, then the strides.
+int check_dlse(const BwdCall& c, fa2::BwdParams& p) {
+    if (!c.dlse) return FA2_OK;
+    if (reinterpret_cast<uintptr_t>(c.dlse) & 3u) return FA2_ERR_ALIGNMENT;
+    if (c.ask == Ask::Launch && !c.dlses) return FA2_ERR_NULL_POINTER;
+    if (c.dlses) {
+        if (c.dlses[0] < 0 || c.dlses[1] < 0) return FA2_ERR_BAD_SHAPE;
+        p.dls[0] = c.dlses[0]; p.dls[1] = c.dlses[1];
+    }
     return FA2_OK;
 }
 
@@ -731,6 +749,8 @@ int bwd_run(const BwdCall& c) {
         *c.ws_need = (size_t)fa2::plan_bwd_split(HD, p, causal, &dq, &dkv);
         return FA2_OK;
     }
+    if (c.ask != Ask::Launch)
+        if (int rc = check_dlse(c, p)) return rc;
     if (c.ask == Ask::Plan) {        // fa2_bwd_plan: the dense unmasked call's passes (the masked backward runs the BIAS forms of the compiler-scheduled passes)
         BwdPlan pl = {0, false, false, false};
         if (c.bias.kind == FA2_BIAS_NONE) pl = plan_bwd(HD, bf16, p, causal);
@@ -740,6 +760,7 @@ int bwd_run(const BwdCall& c) {
     }
     if (c.packed)
         if (int rc = check_packed_tensors(c)) return rc;
+    if (int rc = check_dlse(c, p)) return rc;
     hipStream_t stream = (hipStream_t)c.stream;
     if (c.scoremod) return kBwdSmod[c.packed][bf16](HD, p, stream, scoremod_of(c));
     if (c.windowed) return kBwdFamily[c.packed][c.dropout][bf16](HD, p, stream);
@@ -1332,6 +1353,134 @@ int fa2_dropout_keep_mask(uint64_t seed, float dropout_p, int H, int b, int h, i
     for (int64_t i = i0; i < i1; ++i)
         for (int64_t j = j0; j < j1; ++j) mask[(i - i0) * (j1 - j0) + (j - j0)] = fa2::dropout_keep(seed, t, bh, (uint32_t)i, (uint32_t)j) ? 1 : 0;
     return FA2_OK;
+}
+
+// ---- a gradient for the LSE: include/fa2_gfx950.h has the contract.  Each entry point is a superset of a family — one more optional field of the call
+// description —, and with dlse == NULL it IS the existing call of the same arguments.
+int fa2_bwd_lse(int dtype, FA2_BWD_ARGS(), const void* bias, int bias_kind, const int64_t bias_strides[3], void* workspace, size_t workspace_bytes,
+                void* hip_stream, const float* dlse, const int64_t dlse_strides[2]) {
+    FA2_BWD_CALL(c);
+    c.bias.ptr = bias; c.bias.kind = bias_kind; c.bias.strides = bias_strides;
+    c.ws = workspace; c.ws_bytes = workspace_bytes;
+    c.dlse = dlse; c.dlses = dlse_strides;
+    return bwd_run(c);
+}
+
+int fa2_bwd_lse_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D, const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                     const int64_t o_strides[3], const int64_t do_strides[3], float scale, int flags, int bias_kind, const int64_t bias_strides[3],
+                     int has_dlse, fa2_bwd_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || Nkv < 1 || D < 1) return FA2_ERR_BAD_SHAPE;
+    const int64_t d = D, q[3] = {(int64_t)H * Nq * d, (int64_t)Nq * d, d}, k[3] = {(int64_t)Hkv * Nkv * d, (int64_t)Nkv * d, d};
+    static const int64_t ls[2] = {0, 0};
+    static const float some_dlse = 0.f;          // (a plan query reads no tensor: any non-null value says "this call has a dlse")
+    FA2_QUERY_CALL(BwdCall, c, Hkv);
+    c.scale = scale; c.bias.kind = bias_kind; c.bias.strides = bias_strides;
+    c.qs = c.dqs = q_strides ? q_strides : q; c.ks = c.dks = k_strides ? k_strides : k; c.vs = c.dvs = v_strides ? v_strides : k;
+    c.os = o_strides ? o_strides : q; c.dos = do_strides ? do_strides : q; c.ls = ls;
+    c.dlse = has_dlse ? &some_dlse : nullptr;
+    c.ask = Ask::Plan; c.plan = plan;
+    return bwd_run(c);
+}
+
+// dropout_p > 0: fa2_bwd_dropout; softcap > 0 or slopes: fa2_bwd_scoremod; neither: fa2_bwd_window.  Never both (the kernels have no such form).
+static int window_lse_family(Call& c, float dropout_p, uint64_t seed, float softcap, const float* alibi_slopes, int64_t alibi_batch_stride) {
+    if (!dropout_p_ok(dropout_p)) return FA2_ERR_DROPOUT;
+    if (int rc = set_scoremod_args(c, softcap, alibi_slopes, alibi_batch_stride)) return rc;
+    if (dropout_p > 0.f && c.scoremod) return FA2_ERR_DROPOUT;
+    if (dropout_p > 0.f) set_dropout_args(c, dropout_p, seed);
+    return FA2_OK;
+}
+
+int fa2_bwd_window_lse(int dtype, FA2_BWD_ARGS(), int window_left, int window_right, int q_offset, void* hip_stream, float dropout_p, uint64_t seed,
+                       float softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* dlse, const int64_t dlse_strides[2]) {
+    FA2_BWD_CALL(c);
+    if (int rc = window_lse_family(c, dropout_p, seed, softcap, alibi_slopes, alibi_batch_stride)) return rc;
+    if (int rc = dense_window(c, flags, window_left, window_right, q_offset)) return rc;
+    c.dlse = dlse; c.dlses = dlse_strides;
+    return bwd_run(c);
+}
+
+int fa2_bwd_varlen_lse(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                       void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                       const int* cu_seqlens_q, const int* cu_seqlens_k,
+                       const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                       const int64_t do_strides[2], const int64_t dq_strides[2], const int64_t dk_strides[2], const int64_t dv_strides[2],
+                       int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream, float dropout_p, uint64_t seed,
+                       float softcap, const float* alibi_slopes, int64_t alibi_batch_stride, const float* dlse, int64_t dlse_stride) {
+    BwdCall c;
+    PackedStrides ps;
+    if (int rc = window_lse_family(c, dropout_p, seed, softcap, alibi_slopes, alibi_batch_stride)) return rc;
+    FA2_PACKED_FILL(c, H);
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides}, lse_stride, flags,
+                             window_left, window_right))
+        return rc;
+    FA2_PACKED_BWD_FILL(c, ps);
+    const int64_t dls[2] = {0, dlse_stride};
+    c.dlse = dlse; c.dlses = dls;
+    return bwd_run(c);
+}
+
+// ---- merge of partial attention results: include/fa2_gfx950.h has the contract, merge_hip.cpp the kernels
+static bool strides3_ok(const int64_t* s) { return s[0] >= 0 && s[1] >= 0 && strides_ok(s); }
+static int merge_common(fa2::MergeParams& p, int dtype, int nparts, const void* const* o_parts, const float* const* lse_parts, int B, int H, int Nq, int D,
+                        const int64_t part_strides[3], const int64_t part_lse_strides[2], int flags) {
+    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    if (nparts < 1 || nparts > fa2::kMergeMaxParts || B < 1 || H < 1 || Nq < 1 || D < 1 || (flags & ~FA2_MERGE_NATURAL_LSE)) return FA2_ERR_BAD_SHAPE;
+    if ((D & 7) || D > kMaxBwdHeadDim) return FA2_ERR_HEAD_DIM;
+    if (!o_parts || !lse_parts || !part_strides || !part_lse_strides) return FA2_ERR_NULL_POINTER;
+    for (int k = 0; k < nparts; ++k) {
+        if (!o_parts[k] || !lse_parts[k]) return FA2_ERR_NULL_POINTER;
+        if (!aligned16(o_parts[k]) || (reinterpret_cast<uintptr_t>(lse_parts[k]) & 3u)) return FA2_ERR_ALIGNMENT;
+    }
+    if (!strides3_ok(part_strides)) return FA2_ERR_ALIGNMENT;
+    if (part_lse_strides[0] < 0 || part_lse_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
+    std::memset(&p, 0, sizeof(p));
+    for (int k = 0; k < nparts; ++k) { p.o_parts[k] = o_parts[k]; p.lse_parts[k] = lse_parts[k]; }
+    p.nparts = nparts; p.B = B; p.H = H; p.Nq = Nq; p.D = D; p.natural = (flags & FA2_MERGE_NATURAL_LSE) != 0;
+    for (int i = 0; i < 3; ++i) p.ps[i] = part_strides[i];
+    p.pls[0] = part_lse_strides[0]; p.pls[1] = part_lse_strides[1];
+    return FA2_OK;
+}
+
+int fa2_merge_fwd(int dtype, int nparts, const void* const* o_parts, const float* const* lse_parts, void* o, float* lse, int B, int H, int Nq, int D,
+                  const int64_t part_strides[3], const int64_t part_lse_strides[2], const int64_t o_strides[3], const int64_t lse_strides[2], int flags,
+                  void* hip_stream) {
+    fa2::MergeParams p;
+    if (int rc = merge_common(p, dtype, nparts, o_parts, lse_parts, B, H, Nq, D, part_strides, part_lse_strides, flags)) return rc;
+    if (!o || !lse || !o_strides || !lse_strides) return FA2_ERR_NULL_POINTER;
+    if (!aligned16(o) || (reinterpret_cast<uintptr_t>(lse) & 3u) || !strides3_ok(o_strides)) return FA2_ERR_ALIGNMENT;
+    if (lse_strides[0] < 0 || lse_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
+    p.o = o; p.lse = lse;
+    for (int i = 0; i < 3; ++i) p.os[i] = o_strides[i];
+    p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
+    return fa2::launch_merge_fwd(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
+}
+
+int fa2_merge_bwd(int dtype, int nparts, const void* const* o_parts, const float* const* lse_parts, const float* lse, const void* dout, const float* dlse,
+                  void* const* do_parts, float* const* dlse_parts, int B, int H, int Nq, int D, const int64_t part_strides[3],
+                  const int64_t part_lse_strides[2], const int64_t lse_strides[2], const int64_t do_strides[3], const int64_t dlse_strides[2],
+                  const int64_t dpart_strides[3], const int64_t dpart_lse_strides[2], int flags, void* hip_stream) {
+    fa2::MergeParams p;
+    if (int rc = merge_common(p, dtype, nparts, o_parts, lse_parts, B, H, Nq, D, part_strides, part_lse_strides, flags)) return rc;
+    if (!lse || !dout || !do_parts || !dlse_parts || !lse_strides || !do_strides || !dpart_strides || !dpart_lse_strides || (dlse && !dlse_strides))
+        return FA2_ERR_NULL_POINTER;
+    for (int k = 0; k < nparts; ++k) {
+        if (!do_parts[k] || !dlse_parts[k]) return FA2_ERR_NULL_POINTER;
+        if (!aligned16(do_parts[k]) || (reinterpret_cast<uintptr_t>(dlse_parts[k]) & 3u)) return FA2_ERR_ALIGNMENT;
+    }
+    if (!aligned16(dout) || ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(dlse)) & 3u) || !strides3_ok(do_strides) ||
+        !strides3_ok(dpart_strides))
+        return FA2_ERR_ALIGNMENT;
+    if (lse_strides[0] < 0 || lse_strides[1] < 0 || dpart_lse_strides[0] < 0 || dpart_lse_strides[1] < 0 || (dlse && (dlse_strides[0] < 0 || dlse_strides[1] < 0)))
+        return FA2_ERR_BAD_SHAPE;
+    for (int k = 0; k < nparts; ++k) { p.do_parts[k] = do_parts[k]; p.dlse_parts[k] = dlse_parts[k]; }
+    p.lse = const_cast<float*>(lse); p.dout = dout; p.dlse = dlse;
+    for (int i = 0; i < 3; ++i) { p.dos[i] = do_strides[i]; p.dps[i] = dpart_strides[i]; }
+    p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
+    p.dpls[0] = dpart_lse_strides[0]; p.dpls[1] = dpart_lse_strides[1];
+    if (dlse) { p.dls[0] = dlse_strides[0]; p.dls[1] = dlse_strides[1]; }
+    return fa2::launch_merge_bwd(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
 }
 
 int fa2_fwd_f16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_F16, FA2_FWD_PASS, hip_stream); }

@@ -16,13 +16,14 @@ Layers (reference counterpart in brackets):
 The host is PyTorch-ROCm for memory and streams only; the compute is the C-ABI library
 (include/fa2_gfx950.h).  There is no CPU path: tensors must live on a ROCm device.
 """
+import ctypes
 import os
 
 import torch
 
 from . import _fa2_lib
 
-__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention"]
+__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention"]
 
 
 class _FlashAttnWmma:
@@ -114,10 +115,12 @@ class _FlashAttnWmma:
         return [O[..., :d] if d_pad else O, q, k, v, O, L]
 
     @staticmethod
-    def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window, dropout=None, scoremod=None):
+    def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window, dropout=None, scoremod=None,
+                        dlse=None):
         """backward() of forward_varlen (C-ABI fa2_bwd_varlen; grouped K / V: expanded, dK / dV summed per group in f32).  Returns [dQ, dK, dV].
         dropout = (p, seed) of the forward: the mask is regenerated (fa2_bwd_varlen_dropout; it is keyed by the query head, so expansion changes nothing).
-        scoremod = (softcap, slopes) of the forward (fa2_bwd_varlen_scoremod; the slopes belong to the query heads, so expansion changes nothing either)."""
+        scoremod = (softcap, slopes) of the forward (fa2_bwd_varlen_scoremod; the slopes belong to the query heads, so expansion changes nothing either).
+        dlse: None, or the gradient of the natural-log LSE, f32 [H, total_q] (fa2_bwd_varlen_lse; it belongs to the query heads as well)."""
         lib = _fa2_lib.load()
         if not (Q.is_cuda and dO.is_cuda):
             raise RuntimeError("fa2: tensors must be on a ROCm device (no CPU path in this operator)")
@@ -126,7 +129,7 @@ class _FlashAttnWmma:
         if h_kv != h:
             def mha(Q4, K4, V4, O4, dO4, L_, *rest):
                 return [t.unsqueeze(0) for t in _FlashAttnWmma.backward_varlen(Q4[0], K4[0], V4[0], O4[0], dO4[0], L_, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
-                                                                               max_seqlen_k, act_d, flags, scale, window, dropout, scoremod)]
+                                                                               max_seqlen_k, act_d, flags, scale, window, dropout, scoremod, dlse)]
             return [t[0] for t in _grouped_backward(mha, Q.unsqueeze(0), K.unsqueeze(0), V.unsqueeze(0), O.unsqueeze(0), dO.unsqueeze(0), L, 0, 0, act_d,
                                                     128, 128, False, scale, True)]
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
@@ -148,7 +151,11 @@ class _FlashAttnWmma:
                 max(int(max_seqlen_k), 1), dk, cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), _s2(Q), _s2(K), _s2(V), _s2(O), _s2(dO),
                 _s2(dQ), _s2(dK), _s2(dV), L.stride(0), float(scale), int(flags), int(window[0]), int(window[1]), _raw_stream(dev))
         with torch.cuda.device(dev):
-            if scoremod is not None:
+            if dlse is not None:
+                g = _dlse_log2(dlse)
+                rc = lib.fa2_bwd_varlen_lse(*args, *((0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]))),
+                                            *((0.0, None, 0) if scoremod is None else _scoremod_args(scoremod)), g.data_ptr(), g.stride(0))
+            elif scoremod is not None:
                 rc = lib.fa2_bwd_varlen_scoremod(*args, *_scoremod_args(scoremod))
             else:
                 rc = lib.fa2_bwd_varlen(*args) if dropout is None else lib.fa2_bwd_varlen_dropout(*args, float(dropout[0]), int(dropout[1]))
@@ -287,8 +294,11 @@ class _FlashAttnWmma:
         return _FlashAttnWmma.backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias)
 
     @staticmethod
-    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None, scoremod=None):
+    def backward_py(Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH, bias=None, window=None, dropout=None, scoremod=None,
+                    dlse=None):
         """backward() in Python (masked calls; every call when the compiled front end is absent).  window: as forward_window's.
+        dlse: None, or the gradient of the natural-log LSE, f32 [B, H, Nq] with any strides: the family's *_lse entry point (fa2_bwd_lse without a window,
+        fa2_bwd_window_lse with one) instead of the call made without it.
         dropout = (p, seed) of the forward: the mask is regenerated (fa2_bwd_dropout; it is keyed by the query head, so expanding grouped K / V changes nothing)."""
         if dropout is not None and (window is None or bias is not None):
             raise RuntimeError("fa2: the dropout backward is the windowed one (pass window=(-1, -1, 0) for full attention) and takes no bias")
@@ -307,7 +317,8 @@ class _FlashAttnWmma:
         if h_kv != h:
             if bias is not None:
                 raise RuntimeError("fa2: the masked backward has no grouped-query form (flash_attention(mask=...) expands k / v for it)")
-            mha = _FlashAttnWmma.backward_py if window is None else (lambda *a: _FlashAttnWmma.backward_py(*a, window=window, dropout=dropout, scoremod=scoremod))
+            mha = _FlashAttnWmma.backward_py if window is None and dlse is None else (
+                lambda *a: _FlashAttnWmma.backward_py(*a, window=window, dropout=dropout, scoremod=scoremod, dlse=dlse))
             return _grouped_backward(mha, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br, Bc, causal, scale, permute_NH)
         act_n, act_nkv, act_d = int(act_n), int(act_nkv), int(act_d)
         dtype_code = _fa2_lib.FA2_DTYPE_F16 if Q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
@@ -333,6 +344,30 @@ class _FlashAttnWmma:
                 s3(Q), s3(K), s3(V), s3(O), s3(dO), s3(dQ), s3(dK), s3(dV),
                 _fa2_lib.strides2(L.stride(0), L.stride(1)), float(scale), 1 if causal else 0)
         fn = lib.fa2_bwd
+        if dlse is not None:         # a gradient for the LSE: the superset entry points take every family's arguments, then dlse (log2 units) and its strides
+            g = _dlse_log2(dlse)
+            if window is not None:
+                args += tuple(window) + (stream,) + ((0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1])))
+                args += (0.0, None, 0) if scoremod is None else _scoremod_args(scoremod)
+                fn = lib.fa2_bwd_window_lse
+            else:
+                if bias is not None:
+                    bias_t, kind, bstr = _prepare_bias(bias, b, h, act_n, act_nkv, Q.dtype, Q.device)
+                    args += (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
+                else:
+                    args += (None, _fa2_lib.FA2_BIAS_NONE, None)
+                need = 0 if causal else (lib.fa2_bwd_workspace_bytes if bias is None else lib.fa2_bwd_bias_workspace_bytes)(dtype_code, b, h, act_n, act_nkv, dk, 0)
+                ws = _workspace(need, Q.device, Q.device.index, stream) if need else None
+                args += (ws.data_ptr() if need else None, need, stream)
+                fn = lib.fa2_bwd_lse
+            args += (g.data_ptr(), _fa2_lib.strides2(g.stride(0), g.stride(1)))
+            with torch.cuda.device(Q.device):
+                rc = fn(*args)
+            if rc:
+                _fa2_lib.check(rc)
+            if permute_NH:
+                return [dQ[:, :act_n, :, :act_d], dK[:, :act_nkv, :, :act_d], dV[:, :act_nkv, :, :act_d]]
+            return [dQ[:, :, :act_n, :act_d], dK[:, :, :act_nkv, :act_d], dV[:, :, :act_nkv, :act_d]]
         if bias is not None:         # backward through forward_bias (extension, like the masked forward itself): same bias arguments
             bias_t, kind, bstr = _prepare_bias(bias, b, h, act_n, act_nkv, Q.dtype, Q.device)
             args += (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
@@ -803,6 +838,255 @@ class _VarlenScoreModAttentionFunction(torch.autograd.Function):
         return dQ, dK, dV, None, None, None, None, None, None, None, None, None
 
 
+_LN2 = 0.6931471805599453
+
+
+def _dlse_log2(dlse):
+    """The gradient of the natural-log LSE the operator returned -> the C-ABI's dlse: f32, in log2 units (g * ln 2), rows contiguous, strides >= 0."""
+    g = dlse.to(torch.float32) * _LN2          # (a fresh tensor: an expanded gradient, e.g. of lse.sum(), becomes a dense one here)
+    return g if g.stride(-1) == 1 or g.size(-1) <= 1 else g.contiguous()
+
+
+def _lse_forward(q, k, v, mask, slopes, causal, scale, BNHD_fmt, window, dropout, softcap):
+    """The forward of flash_attention(return_lse=True): the family's forward flagged FA2_FLAG_EXACT_SCALE -> the 6-tensor return and the natural-log LSE
+    [B, H, Nq], sliced out of the row-padded L.  window None: the plain / masked call; a triple: the windowed / dropout / score-modifier call."""
+    D = q.shape[3]
+    Br = 32 if D > 384 else 64                      # FlashAttn.py:56-67
+    flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | _fa2_lib.FA2_FLAG_EXACT_SCALE
+    smod = (softcap, slopes) if (softcap or slopes is not None) else None
+    if window is None:
+        ret = flash_attn_wmma.forward_py(q, k, v, Br, 128, flags, scale, BNHD_fmt, bias=mask)
+    elif dropout is None and smod is None:
+        ret = flash_attn_wmma.forward_window(q, k, v, Br, 128, flags, scale, BNHD_fmt, window)
+    else:
+        ret = flash_attn_wmma.forward_py(q, k, v, Br, 128, flags, scale, BNHD_fmt, window=window, dropout=dropout, scoremod=smod)
+    n = q.shape[1 if BNHD_fmt else 2]
+    return ret, ret[5][:, :, :n] * _LN2
+
+
+class _LseAttentionFunction(torch.autograd.Function):
+    """autograd node of flash_attention(return_lse=True), every route: outputs (out, lse), backward takes (dO, dLSE) — either may be None — and runs the
+    family's *_lse backward (fa2_bwd_lse / fa2_bwd_window_lse).  A missing dLSE passes no dlse: exactly the family's backward of today."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, q, k, v, mask, slopes, causal, scale, BNHD_fmt, window, dropout, softcap):
+        ctx.set_materialize_grads(False)
+        if mask is not None and q.shape[3] > _MAX_MASKED_BWD_HEAD_DIM:
+            raise RuntimeError("fa2: a masked attention call that needs gradients supports head dims up to %d (got %d): fa2_bwd_bias has no kernel above"
+                               % (_MAX_MASKED_BWD_HEAD_DIM, q.shape[3]))
+        (o, q_bwd, k_bwd, v_bwd, o_bwd, L), lse = _lse_forward(q, k, v, mask, slopes, causal, scale, BNHD_fmt, window, dropout, softcap)
+        n_ax = 1 if BNHD_fmt else 2
+        ctx.args = (causal, scale, q.shape[n_ax], k.shape[n_ax], q.shape[3], BNHD_fmt, window, dropout, softcap, mask is not None, slopes is not None)
+        ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L, *(t for t in (mask, slopes) if t is not None))
+        return o, lse
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, do, dlse):
+        causal, scale, N, Nkv, D, BNHD_fmt, window, dropout, softcap, has_mask, has_slopes = ctx.args
+        q, k, v, o, L = ctx.saved_tensors[:5]
+        mask = ctx.saved_tensors[5] if has_mask else None
+        slopes = ctx.saved_tensors[5 + has_mask] if has_slopes else None
+        if do is None:
+            do = torch.zeros_like(q)                # (the kernels read a dO; dLSE alone is the rare case)
+        smod = (softcap, slopes) if (softcap or slopes is not None) else None
+        dQ, dK, dV = flash_attn_wmma.backward_py(q, k, v, o, do, L, N, Nkv, D, 128, 128, causal, scale, BNHD_fmt, bias=mask, window=window, dropout=dropout,
+                                                 scoremod=smod, dlse=dlse)
+        return dQ, dK, dV, None, None, None, None, None, None, None, None
+
+
+class _VarlenLseAttentionFunction(torch.autograd.Function):
+    """autograd node of flash_attention_varlen(return_lse=True): outputs (out, lse [H, total_q]), backward = fa2_bwd_varlen_lse."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, q, k, v, slopes, cu_q, cu_k, max_q, max_k, flags, scale, window, dropout, softcap):
+        ctx.set_materialize_grads(False)
+        smod = (softcap, slopes) if (softcap or slopes is not None) else None
+        o, q_bwd, k_bwd, v_bwd, o_bwd, L = flash_attn_wmma.forward_varlen(q, k, v, cu_q, cu_k, max_q, max_k, flags | _fa2_lib.FA2_FLAG_EXACT_SCALE, scale, window,
+                                                                          dropout, smod)
+        ctx.args = (max_q, max_k, q.shape[2], flags, scale, window, dropout, softcap, slopes is not None)
+        ctx.save_for_backward(q_bwd, k_bwd, v_bwd, o_bwd, L, cu_q, cu_k, *(() if slopes is None else (slopes,)))
+        return o, L * _LN2
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, do, dlse):
+        max_q, max_k, D, flags, scale, window, dropout, softcap, has_slopes = ctx.args
+        q, k, v, o, L, cu_q, cu_k = ctx.saved_tensors[:7]
+        slopes = ctx.saved_tensors[7] if has_slopes else None
+        if do is None:
+            do = torch.zeros_like(q)
+        smod = (softcap, slopes) if (softcap or slopes is not None) else None
+        dQ, dK, dV = flash_attn_wmma.backward_varlen(q, k, v, o, do, L, cu_q, cu_k, max_q, max_k, D, flags, scale, window, dropout, smod, dlse=dlse)
+        return dQ, dK, dV, None, None, None, None, None, None, None, None, None, None
+
+
+def _flash_attention_lse(q, k, v, mask, causal, scale, BNHD_fmt, window, q_offset, dropout_p, dropout_seed, softcap, alibi_slopes):
+    """flash_attention(return_lse=True): the argument checks of every route, then ONE node (or, when nothing needs a gradient, the bare forward)."""
+    if not (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)) or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise RuntimeError("fa2: q, k, v must be 4-D ([B,H,N,D] or [B,N,H,D] with BNHD_fmt)")
+    if not q.is_cuda or not k.is_cuda or not v.is_cuda:
+        raise RuntimeError("fa2: q, k, v must be on a ROCm device (no CPU path in this operator)")
+    h_ax, n_ax = (2, 1) if BNHD_fmt else (1, 2)
+    dropout = _parse_dropout(dropout_p, dropout_seed)
+    smod = _parse_scoremod(softcap, alibi_slopes, q, q.shape[h_ax], q.shape[0])
+    if smod is not None and mask is not None:
+        raise ValueError("fa2: flash_attention(mask=..., softcap / alibi_slopes) is not supported: the score modifiers run on the unmasked / windowed kernels only")
+    if smod is not None and dropout is not None:
+        raise ValueError("fa2: flash_attention(softcap / alibi_slopes, dropout_p > 0) is not supported: the score modifiers do not combine with dropout")
+    if dropout is not None and mask is not None:
+        raise ValueError("fa2: flash_attention(mask=..., dropout_p > 0) is not supported: dropout runs on the unmasked / windowed kernels only")
+    _check_groups(q.shape[h_ax], k.shape[h_ax])
+    win = None
+    if smod is not None or dropout is not None or window is not None or q_offset != 0:
+        win = _fa2_lib.parse_window(window if window is not None else (-1, -1), q_offset)
+    if mask is not None:
+        if win is not None:                      # the band folded into the mask, as flash_attention does without return_lse
+            band = _band_mask(q.shape[n_ax], k.shape[n_ax], win, causal, q.device)
+            mask = mask & band if mask.dtype == torch.bool else (mask + torch.zeros_like(band, dtype=mask.dtype)).masked_fill(~band, float("-inf"))
+            causal, win = False, None
+        if k.shape[h_ax] != q.shape[h_ax]:       # the masked kernels have no grouped form: expanded here, autograd sums dK / dV per group
+            g = q.shape[h_ax] // k.shape[h_ax]
+            k, v = k.repeat_interleave(g, dim=h_ax), v.repeat_interleave(g, dim=h_ax)
+    if scale is None:
+        scale = q.shape[3] ** -0.5
+    cap, slopes = smod if smod is not None else (0.0, None)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return _LseAttentionFunction.apply(q, k, v, mask, slopes, bool(causal), scale, BNHD_fmt, win, dropout, cap)
+    ret, lse = _lse_forward(q, k, v, mask, slopes, bool(causal), scale, BNHD_fmt, win, dropout, cap)
+    return ret[0], lse
+
+
+class _MergeFunction(torch.autograd.Function):
+    """autograd node of merge_attention for up to 16 parts: forward = fa2_merge_fwd, backward = fa2_merge_bwd (natural-log LSEs)."""
+
+    @staticmethod
+    @torch.no_grad()
+    def forward(ctx, BNHD_fmt, n, *parts):
+        ctx.set_materialize_grads(False)
+        outs, lses = list(parts[:n]), list(parts[n:])
+        d = outs[0].shape[-1]
+        d_pad = -d % 8
+        if d_pad:
+            outs = [torch.nn.functional.pad(t, (0, d_pad)) for t in outs]
+        ready = _strides_ok if outs[0].dim() == 4 else (lambda t: _packed_ready(t) is t)
+        if any(t.stride() != outs[0].stride() or not ready(t) for t in outs):
+            outs = [t.contiguous() for t in outs]
+        lses = [t.to(torch.float32) for t in lses]
+        if any(t.stride() != lses[0].stride() or (t.stride(-1) != 1 and t.size(-1) > 1) for t in lses):
+            lses = [t.contiguous() for t in lses]
+        out = torch.empty(outs[0].shape, dtype=outs[0].dtype, device=outs[0].device)
+        lse = torch.empty(lses[0].shape, dtype=torch.float32, device=outs[0].device)
+        geo = _merge_geometry(outs[0], BNHD_fmt)
+        dev = out.device.index
+        with torch.cuda.device(dev):
+            rc = _fa2_lib.load().fa2_merge_fwd(geo[0], n, _ptr_array(outs), _ptr_array(lses), out.data_ptr(), lse.data_ptr(), *geo[1:],
+                                               _merge_s3(outs[0], BNHD_fmt), _merge_s2(lses[0]), _merge_s3(out, BNHD_fmt), _merge_s2(lse),
+                                               _fa2_lib.FA2_MERGE_NATURAL_LSE, _raw_stream(dev))
+        if rc:
+            _fa2_lib.check(rc)
+        ctx.args = (BNHD_fmt, n, d)
+        ctx.save_for_backward(lse, *outs, *lses)
+        return (out[..., :d] if d_pad else out), lse
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, dout, dlse):
+        BNHD_fmt, n, d = ctx.args
+        lse, outs, lses = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + n], ctx.saved_tensors[1 + n:]
+        if dout is None:
+            dout = torch.zeros_like(outs[0])
+        else:
+            if dout.dtype != outs[0].dtype:
+                dout = dout.to(outs[0].dtype)
+            if dout.shape[-1] != outs[0].shape[-1]:
+                dout = torch.nn.functional.pad(dout, (0, outs[0].shape[-1] - dout.shape[-1]))
+            if not (_strides_ok(dout) if dout.dim() == 4 else _packed_ready(dout) is dout):
+                dout = dout.contiguous()
+        if dlse is not None:
+            dlse = dlse.to(torch.float32)
+            if dlse.stride(-1) != 1 or min(dlse.stride()) < 0 or dlse.data_ptr() & 3:
+                dlse = dlse.contiguous()
+        douts = [torch.empty(outs[0].shape, dtype=outs[0].dtype, device=lse.device) for _ in range(n)]
+        dlses = [torch.empty(lse.shape, dtype=torch.float32, device=lse.device) for _ in range(n)]
+        geo = _merge_geometry(outs[0], BNHD_fmt)
+        dev = lse.device.index
+        with torch.cuda.device(dev):
+            rc = _fa2_lib.load().fa2_merge_bwd(geo[0], n, _ptr_array(outs), _ptr_array(lses), lse.data_ptr(), dout.data_ptr(),
+                                               None if dlse is None else dlse.data_ptr(), _ptr_array(douts), _ptr_array(dlses), *geo[1:],
+                                               _merge_s3(outs[0], BNHD_fmt), _merge_s2(lses[0]), _merge_s2(lse), _merge_s3(dout, BNHD_fmt),
+                                               None if dlse is None else _merge_s2(dlse), _merge_s3(douts[0], BNHD_fmt), _merge_s2(dlses[0]),
+                                               _fa2_lib.FA2_MERGE_NATURAL_LSE, _raw_stream(dev))
+        if rc:
+            _fa2_lib.check(rc)
+        if douts[0].shape[-1] != d:
+            douts = [t[..., :d] for t in douts]
+        return (None, None, *douts, *dlses)
+
+
+def _ptr_array(tensors):
+    """A host array of device pointers, as fa2_merge_* take them (copied into the kernel's argument block by the library)."""
+    return (ctypes.c_void_p * len(tensors))(*(t.data_ptr() for t in tensors))
+
+
+def _merge_geometry(o, BNHD_fmt):
+    """(dtype code, B, H, Nq, D) of a part: [B, H, N, D], [B, N, H, D] with BNHD_fmt, or the packed [total, H, D] (B = 1)."""
+    code = _fa2_lib.FA2_DTYPE_F16 if o.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+    if o.dim() == 3:
+        return code, 1, o.shape[1], o.shape[0], o.shape[2]
+    return (code, o.shape[0], o.shape[2], o.shape[1], o.shape[3]) if BNHD_fmt else (code, o.shape[0], o.shape[1], o.shape[2], o.shape[3])
+
+
+def _merge_s3(o, BNHD_fmt):
+    st = o.stride()
+    if o.dim() == 3:
+        return _fa2_lib.strides3(0, st[1], st[0])
+    return _fa2_lib.strides3(st[0], st[2], st[1]) if BNHD_fmt else _fa2_lib.strides3(st[0], st[1], st[2])
+
+
+def _merge_s2(lse):
+    st = lse.stride()
+    return _fa2_lib.strides2(0, st[0]) if lse.dim() == 2 else _fa2_lib.strides2(st[0], st[1])
+
+
+_MERGE_MAX_PARTS = 16
+
+
+def merge_attention(outs, lses, BNHD_fmt=False):
+    """Merge attention computed over disjoint pieces of the KV axis: `outs` / `lses` are sequences of equal-shaped tensors as
+    flash_attention(..., return_lse=True) returns them — out [B, H, Nq, D] ([B, Nq, H, D] with BNHD_fmt), lse [B, H, Nq] f32 natural-log — or the packed
+    forms of flash_attention_varlen ([total_q, H, D] and [H, total_q]).  Returns (out, lse) of the attention over the union of the pieces: per row
+    w_k = exp(lse_k - lse), out = sum_k w_k out_k (f32, rounded once), lse = logsumexp_k lse_k.  A row no piece saw (every lse_k = -inf) gives zeros and
+    -inf; a piece with lse_k = -inf has weight exactly 0.  One HIP kernel each way (C-ABI fa2_merge_fwd / fa2_merge_bwd, no atomics), differentiable in
+    every out and every lse, capturable in a graph.  More than 16 parts are folded in groups of 16 (the operation is associative; each fold rounds its
+    out once).  Parts whose strides differ are made contiguous first."""
+    outs, lses = list(outs), list(lses)
+    if not outs or len(outs) != len(lses):
+        raise ValueError("fa2: merge_attention takes as many lses as outs, at least one")
+    o0, l0 = outs[0], lses[0]
+    if not all(torch.is_tensor(t) for t in outs + lses) or o0.dim() not in (3, 4):
+        raise ValueError("fa2: merge_attention takes tensors: outs [B, H, Nq, D] or packed [total_q, H, D], lses [B, H, Nq] or [H, total_q]")
+    if not all(t.is_cuda for t in outs + lses):
+        raise RuntimeError("fa2: the parts must be on a ROCm device (no CPU path in this operator)")
+    if o0.dim() == 3:
+        lshape = (o0.shape[1], o0.shape[0])
+    else:
+        lshape = (o0.shape[0], o0.shape[2], o0.shape[1]) if BNHD_fmt else tuple(o0.shape[:3])
+    for o, l in zip(outs, lses):
+        if o.shape != o0.shape or o.dtype != o0.dtype or o.device != o0.device or tuple(l.shape) != lshape or l.device != o0.device:
+            raise ValueError("fa2: merge_attention: every out must be %s %s and every lse %s on %s" % (tuple(o0.shape), o0.dtype, lshape, o0.device))
+    if o0.dtype not in (torch.float16, torch.bfloat16) or o0.shape[-1] > _MAX_HEAD_DIM:
+        raise RuntimeError("fa2: merge_attention takes fp16 / bf16 outs of head dim <= %d" % _MAX_HEAD_DIM)
+    if o0.numel() == 0:
+        return torch.zeros_like(o0), torch.full(lshape, float("-inf"), dtype=torch.float32, device=o0.device)
+    while len(outs) > _MERGE_MAX_PARTS:
+        o, l = _MergeFunction.apply(BNHD_fmt, _MERGE_MAX_PARTS, *outs[:_MERGE_MAX_PARTS], *lses[:_MERGE_MAX_PARTS])
+        outs, lses = [o] + outs[_MERGE_MAX_PARTS:], [l] + lses[_MERGE_MAX_PARTS:]
+    return _MergeFunction.apply(BNHD_fmt, len(outs), *outs, *lses)
+
+
 SOFTCAP_MESSAGE = "fa2: softcap must be 0 (off) or a finite positive number (a normal float32: >= 1.18e-38)"
 _SOFTCAP_MIN = 2.0 ** -126          # the smallest normal float32: below it 1 / softcap overflows (the library answers FA2_ERR_SOFTCAP)
 ALIBI_MESSAGE = "fa2: alibi_slopes must be a float32 tensor on q's device, shaped [H] or [B, H] (packed calls: [H] or [num_sequences, H])"
@@ -877,7 +1161,7 @@ def dropout_keep_mask(seed, p, B, H, Nq, Nkv):
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, causal=False, scale=None, window=None,
-                           bottom_right=False, dropout_p=0.0, dropout_seed=None, softcap=0.0, alibi_slopes=None):
+                           bottom_right=False, dropout_p=0.0, dropout_seed=None, softcap=0.0, alibi_slopes=None, return_lse=False):
     """Packed, variable-length attention: B sequences of individual lengths in one buffer (the flash_attn_varlen_func shape).
     q [total_q, H, D], k / v [total_k, Hkv, D] (Hkv divides H: grouped K / V are not expanded); cu_seqlens_q / cu_seqlens_k: int32 [B + 1] on q's
     device, non-decreasing — sequence s owns the rows [cu[s], cu[s+1]); zero-length sequences are fine.  Returns [total_q, H, D].
@@ -890,7 +1174,9 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     Differentiable in q, k, v (C-ABI fa2_fwd_varlen / fa2_bwd_varlen): no atomics, deterministic gradients.
     dropout_p / dropout_seed: attention dropout as flash_attention's; the mask is keyed by the sequence index and the positions inside the sequence.
     softcap / alibi_slopes: as flash_attention's; the slopes are [H] or [num_sequences, H], the positions count inside the sequence (row i at i, or at
-    i + Nkv_s - Nq_s with bottom_right=True).  Not together with dropout_p > 0 (ValueError)."""
+    i + Nkv_s - Nq_s with bottom_right=True).  Not together with dropout_p > 0 (ValueError).
+    return_lse=True returns (out, lse), lse f32 [H, total_q] in natural-log units, -inf for rows that see no key, differentiable like out (see
+    flash_attention); merge_attention combines such pairs.  False takes exactly the path taken without the argument."""
     dropout = None if dropout_p.__class__ is float and dropout_p == 0.0 else _parse_dropout(dropout_p, dropout_seed)      # (the default: no work)
     left, right, _ = _fa2_lib.parse_window(window, 0)
     smod = None
@@ -908,6 +1194,14 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     if scale is None:
         scale = D ** -0.5
     flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | (_fa2_lib.FA2_FLAG_BOTTOM_RIGHT if bottom_right else 0)
+    if return_lse:
+        cap, slopes = smod if smod is not None else (0.0, None)
+        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+            return _VarlenLseAttentionFunction.apply(q, k, v, slopes, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale,
+                                                     (left, right), dropout, cap)
+        ret = flash_attn_wmma.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags | _fa2_lib.FA2_FLAG_EXACT_SCALE,
+                                             scale, (left, right), dropout, smod)
+        return ret[0], ret[5] * _LN2
     if smod is not None:
         if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
             return _VarlenScoreModAttentionFunction.apply(q, k, v, smod[1], cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale,
@@ -939,7 +1233,7 @@ def _band_mask(nq, nkv, window, causal, device):
 
 
 def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False, window=None, q_offset=0, dropout_p=0.0, dropout_seed=None,
-                    softcap=0.0, alibi_slopes=None):
+                    softcap=0.0, alibi_slopes=None, return_lse=False):
     """Forward attention that HONOURS `mask` — the extension the reference lists as to do (README.md:45; its
     FlashAttentionFunction accepts the argument and ignores it, FlashAttn.py:49, :74, and `FlashAttentionFunction.apply` here
     keeps doing exactly that so that existing call sites see no change).  `mask` follows
@@ -966,7 +1260,18 @@ def flash_attention(q, k, v, mask=None, causal=False, scale=None, BNHD_fmt=False
     given (BLOOM, MPT, Baichuan) — a float32 tensor on q's device, [H] or [B, H], one slope per QUERY head, no gradient —, then the causal / window
     masks.  No [Nq, Nkv] tensor exists; works with causal, window, q_offset and grouped k / v, differentiable in q, k, v (C-ABI fa2_fwd_scoremod /
     fa2_bwd_scoremod, every head dim up to 512).  softcap=0.0, alibi_slopes=None: exactly the path taken without the arguments.  Not together with
-    `mask=` or dropout_p > 0 (ValueError)."""
+    `mask=` or dropout_p > 0 (ValueError).
+
+    `return_lse`: True returns (out, lse) — flash_attn_func's return_attn_probs / return_lse.  lse is the row log-sum-exp of the (masked, modified)
+    scaled scores, f32 [B, H, Nq] whatever BNHD_fmt is, in NATURAL-log units, -inf for rows that see no key; under dropout it is that of the undropped
+    probabilities.  It works on every route above.  When q, k or v needs a gradient, lse is a differentiable output of the same autograd node as out
+    (C-ABI fa2_bwd_lse / fa2_bwd_window_lse: d lse_i / d s_ij = P_ij enters the dQ pass's row term), so attention over pieces of the KV axis can be
+    merged with merge_attention and differentiated — ring / sequence-parallel attention, chunked prefill, shared-prefix inference, a sink term added by
+    the caller.  Such a call ALWAYS scales the f32 scores (FA2_FLAG_EXACT_SCALE), also under no_grad: the LSE is a result the caller combines with the
+    LSEs of other calls, so it must be that of the f32-scaled scores, not of a kernel that folds the scale into a rounded Q.  With a gradient for lse
+    head dim 128 runs the compiler-scheduled backward passes (fa2_bwd_lse_plan).  False takes exactly the path taken without the argument."""
+    if return_lse:
+        return _flash_attention_lse(q, k, v, mask, causal, scale, BNHD_fmt, window, q_offset, dropout_p, dropout_seed, softcap, alibi_slopes)
     dropout = None if dropout_p.__class__ is float and dropout_p == 0.0 else _parse_dropout(dropout_p, dropout_seed)      # (the default: no work)
     if not (softcap.__class__ is float and softcap == 0.0 and alibi_slopes is None):                                      # (the default: no work)
         if not (torch.is_tensor(q) and torch.is_tensor(k) and torch.is_tensor(v)) or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:

@@ -27,6 +27,7 @@ FA2_KERNEL_HIP_VARLEN = 6                                                       
 FA2_CONTRACT_PRESCALE_Q, FA2_CONTRACT_LSUM_P16 = 1, 2                                                   # fa2_fwd_plan_t.contract bits
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_vpp = ctypes.POINTER(ctypes.c_void_p)      # a host array of device pointers (fa2_merge_*)
 
 
 class FwdPlan(ctypes.Structure):
@@ -117,6 +118,20 @@ SYMBOLS = {
                                 [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_void_p, ctypes.c_int64]),
     "fa2_bwd_varlen_scoremod": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [_i64p] * 8 +
                                 [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_float, ctypes.c_void_p, ctypes.c_int64]),
+    # a gradient for the LSE: a family's backward argument list, then (for the windowed / packed ones) dropout_p, seed, softcap, slopes, stride, then dlse and its strides
+    "fa2_bwd_lse": (ctypes.c_int, [ctypes.c_int] + _BWD_ARGTYPES[:-1] + [ctypes.c_void_p, ctypes.c_int, _i64p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p] +
+                    [ctypes.c_void_p, _i64p]),
+    "fa2_bwd_window_lse": (ctypes.c_int, [ctypes.c_int] + _BWD_ARGTYPES[:-1] + [ctypes.c_int] * 3 + [ctypes.c_void_p] +
+                           [ctypes.c_float, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _i64p]),
+    "fa2_bwd_varlen_lse": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [_i64p] * 8 +
+                           [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p] +
+                           [ctypes.c_float, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]),
+    "fa2_bwd_lse_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _i64p, ctypes.c_int, ctypes.POINTER(BwdPlan)]),
+    # merge of partial attention results: host arrays of device pointers, shared stride sets
+    "fa2_merge_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vpp, _vpp, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [_i64p] * 4 +
+                      [ctypes.c_int, ctypes.c_void_p]),
+    "fa2_merge_bwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vpp, _vpp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _vpp, _vpp] + [ctypes.c_int] * 4 +
+                      [_i64p] * 7 + [ctypes.c_int, ctypes.c_void_p]),
     "fa2_scoremod_eval": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 2),
     "fa2_dropout_keep_mask": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 4 + [ctypes.c_void_p]),
     "fa2_dropout_threshold": (ctypes.c_int, [ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
@@ -205,6 +220,7 @@ class options:
 
 
 FA2_FLAG_CAUSAL, FA2_FLAG_EXACT_SCALE = 1, 2       # bits of the `causal` argument (include/fa2_gfx950.h)
+FA2_MERGE_NATURAL_LSE = 1                          # `flags` of fa2_merge_fwd / fa2_merge_bwd (an enumerator in the header)
 FA2_FLAG_BOTTOM_RIGHT = 4                          # ... of the packed (varlen) entry points' `flags` only
 
 

@@ -544,6 +544,73 @@ int fa2_bwd_varlen_scoremod(int dtype, const void* q, const void* k, const void*
  * FA2_ERR_SOFTCAP, FA2_ERR_NULL_POINTER. */
 int fa2_scoremod_eval(float x, float softcap, float slope, int pos, int j, float* s, float* dfactor);
 
+/* ---- A gradient for the LSE.
+ * The forward's `lse` is a result a caller may consume (merging attention over pieces of the KV axis: fa2_merge_fwd below), so the backward accepts a
+ * gradient for it.  `dlse`: f32 in device memory, the gradient of the loss with respect to the `lse` the forward wrote — in ITS unit, log2 — addressed
+ * dlse[b * dlse_strides[0] + h * dlse_strides[1] + row] (packed: dlse[h * dlse_stride + t]); strides of its own, so a compact gradient needs no padded
+ * copy.  With natural-log lse_n = lse * ln 2, d lse_n[i] / d s[i][j] = P[i][j], hence dS = P (dP - delta + dlse_n): the dQ pass replaces the row term
+ * delta[i] by delta[i] - log2(e) * dlse[i] (a caller holding the natural-log gradient g passes g * ln 2) before it uses it and before it stores it to
+ * delta_ws, which therefore holds the modified value.  This holds under dropout (the LSE is that of the undropped P) and under soft-capping.  A row
+ * whose saved lse is -inf (it saw no key) ignores its dlse entirely: even a NaN there yields zero gradients.
+ * Each entry point is a superset of a family; with dlse == NULL it IS the existing call of the same arguments (same kernels, same plan, bit-identical
+ * results).  With a dlse, head dim 128 runs the compiler-scheduled passes (the hand-scheduled bodies form delta inside generated code):
+ * fa2_bwd_lse_plan reports it.
+ *   fa2_bwd_lse          fa2_bwd_bias_ws's arguments (bias_kind = FA2_BIAS_NONE: fa2_bwd_ws), then the dlse pair.
+ *   fa2_bwd_window_lse   fa2_bwd_window's arguments, then fa2_bwd_dropout's (dropout_p, seed) and fa2_bwd_scoremod's (softcap, alibi_slopes,
+ *                        alibi_batch_stride), then the dlse pair.  dropout_p > 0: the call is fa2_bwd_dropout; softcap > 0 or slopes: fa2_bwd_scoremod;
+ *                        neither: fa2_bwd_window.  Checked first, in this order: dropout_p (FA2_ERR_DROPOUT), the score-modifier arguments (their
+ *                        codes), both at once (FA2_ERR_DROPOUT: the kernels have no such form).
+ *   fa2_bwd_varlen_lse   the same for fa2_bwd_varlen; dlse_stride = elements between two heads' rows.
+ * The dlse arguments are checked LAST: a pointer that is not 4-byte aligned FA2_ERR_ALIGNMENT, a negative stride FA2_ERR_BAD_SHAPE. */
+int fa2_bwd_lse(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
+                const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                const int64_t do_strides[3], const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                const int64_t lse_strides[2], float scale, int causal,
+                const void* bias, int bias_kind, const int64_t bias_strides[3], void* workspace, size_t workspace_bytes, void* hip_stream,
+                const float* dlse, const int64_t dlse_strides[2]);
+int fa2_bwd_window_lse(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                       void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int Nq, int Nkv, int D,
+                       const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                       const int64_t do_strides[3], const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                       const int64_t lse_strides[2], float scale, int flags, int window_left, int window_right, int q_offset, void* hip_stream,
+                       float dropout_p, uint64_t seed, float softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                       const float* dlse, const int64_t dlse_strides[2]);
+int fa2_bwd_varlen_lse(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                       void* dq, void* dk, void* dv, float* delta_ws, int B, int H, int max_seqlen_q, int max_seqlen_k, int D,
+                       const int* cu_seqlens_q, const int* cu_seqlens_k,
+                       const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2],
+                       const int64_t o_strides[2], const int64_t do_strides[2], const int64_t dq_strides[2],
+                       const int64_t dk_strides[2], const int64_t dv_strides[2], int64_t lse_stride,
+                       float scale, int flags, int window_left, int window_right, void* hip_stream,
+                       float dropout_p, uint64_t seed, float softcap, const float* alibi_slopes, int64_t alibi_batch_stride,
+                       const float* dlse, int64_t dlse_stride);
+
+/* ---- Merge of partial attention results.
+ * nparts (1 .. 16) calls over disjoint pieces of the KV axis left (O_k, lse_k); per row
+ *     m = max_k lse_k,   w_k = 2^(lse_k - m) / sum_k 2^(lse_k - m),   O = sum_k w_k O_k (f32, rounded once),   lse = m + log2 sum_k 2^(lse_k - m)
+ * is the result over the union.  A row whose parts are all -inf gives O = 0, lse = -inf; a part of weight exactly 0 is not read (its O_k may hold
+ * anything).  o_parts / lse_parts (and do_parts / dlse_parts) are HOST arrays of device pointers, copied into the kernel's argument block: no device
+ * copy, and the call can be captured in a graph.  All parts share one stride set: part_strides {batch, head, row} in elements (D contiguous),
+ * part_lse_strides {batch, head} (rows contiguous) — the forward's O and padded L buffers can be passed as they are.  The packed layout [total, H, D] /
+ * [H, total] is the same call with B = 1, Nq = total and the matching strides.  D: a multiple of 8, up to 512.  flags: FA2_MERGE_NATURAL_LSE = every
+ * LSE (in and out, and their gradients) is natural-log; clear = log2, as fa2_fwd writes them.
+ * fa2_merge_bwd: dO_k = w_k dO (rounded to the I/O dtype), dlse_k = w_k (dlse + dO.(O_k - O)), with dO.O formed as sum_k w_k (dO.O_k) in f32 (the
+ * merged O is not read) and the dot term scaled by ln 2 when the LSEs are log2; `lse` is the merged LSE the forward wrote, dlse (may be NULL = zeros)
+ * its gradient with strides dlse_strides; dout has do_strides, the parts' gradients dpart_strides / dpart_lse_strides.  Dead rows and zero-weight
+ * parts get zeros.  No atomics: every output element has one owner.
+ * Errors: FA2_ERR_DTYPE; nparts outside 1 .. 16, a size < 1, an unknown flag bit or a negative stride FA2_ERR_BAD_SHAPE; FA2_ERR_HEAD_DIM;
+ * FA2_ERR_NULL_POINTER; tensors not 16-byte (LSEs: 4-byte) aligned or strides not multiples of 8 elements FA2_ERR_ALIGNMENT; FA2_ERR_GRID. */
+enum { FA2_MERGE_NATURAL_LSE = 1 };
+int fa2_merge_fwd(int dtype, int nparts, const void* const* o_parts, const float* const* lse_parts, void* o, float* lse,
+                  int B, int H, int Nq, int D, const int64_t part_strides[3], const int64_t part_lse_strides[2],
+                  const int64_t o_strides[3], const int64_t lse_strides[2], int flags, void* hip_stream);
+int fa2_merge_bwd(int dtype, int nparts, const void* const* o_parts, const float* const* lse_parts, const float* lse,
+                  const void* dout, const float* dlse, void* const* do_parts, float* const* dlse_parts,
+                  int B, int H, int Nq, int D, const int64_t part_strides[3], const int64_t part_lse_strides[2],
+                  const int64_t lse_strides[2], const int64_t do_strides[3], const int64_t dlse_strides[2],
+                  const int64_t dpart_strides[3], const int64_t dpart_lse_strides[2], int flags, void* hip_stream);
+
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
  * that is not a multiple of 8 has to be zero-padded by the caller (to the next multiple of 8). */
@@ -627,6 +694,11 @@ int fa2_bwd_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D,
                  const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
                  const int64_t o_strides[3], const int64_t do_strides[3],
                  float scale, int causal, int bias_kind, const int64_t bias_strides[3], fa2_bwd_plan_t* plan);
+/* ... of fa2_bwd_lse: has_dlse = 0 is fa2_bwd_plan's answer; has_dlse = 1: what the launch with a dlse executes (no FA2_BWD_KERNEL_ASM pass). */
+int fa2_bwd_lse_plan(int dtype, int B, int H, int Hkv, int Nq, int Nkv, int D,
+                     const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                     const int64_t o_strides[3], const int64_t do_strides[3],
+                     float scale, int causal, int bias_kind, const int64_t bias_strides[3], int has_dlse, fa2_bwd_plan_t* plan);
 
 /* How fa2_fwd_bias fetches a bias of these strides whose pointer is 16-byte aligned (the forward accepts every bias; the form follows its geometry):
  *   FA2_BIAS_FORM_SCALAR    one guarded load per score
