@@ -10,35 +10,20 @@ namespace {
 // parts: bit 0 = dQ pass, bit 1 = dK/dV pass.  neg_delta: the dQ pass leaves -delta in the workspace (the hand-scheduled dK/dV pass follows).
 template <bool BF16, bool CAUSAL, bool KFOLD, bool M16 = false>
 int launch_dkv(const fa2::BwdParams& p, hipStream_t stream) {
-    constexpr auto kern = fa2::bwd_dkv_d128_kernel<BF16, CAUSAL, KFOLD, M16>;
-    if (int rc = fa2::set_lds<kern>(fa2::kBwdKvLdsBytes)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)p.B * p.H * p.nblk)), dim3(256), fa2::kBwdKvLdsBytes, stream, p);
-    return (int)hipGetLastError();
+    return fa2::launch<fa2::bwd_dkv_d128_kernel<BF16, CAUSAL, KFOLD, M16>>(dim3((unsigned)((int64_t)p.B * p.H * p.nblk)), dim3(256), fa2::kBwdKvLdsBytes, stream, p);
+}
+
+template <bool BF16, bool CAUSAL, bool NEG_DELTA, bool M16 = false>
+int launch_dq(const fa2::BwdParams& p, hipStream_t stream) {
+    return fa2::launch<fa2::bwd_dq_d128_kernel<BF16, CAUSAL, NEG_DELTA, M16>>(dim3((unsigned)((int64_t)p.B * p.H * p.nblk)), dim3(256), fa2::kBwdDqLdsBytes, stream, p);
 }
 
 template <bool BF16, bool CAUSAL>
 int launch_t(fa2::BwdParams p, int parts, bool neg_delta, bool kfold, bool dq16, bool dkv16, hipStream_t stream) {
-    if (parts & 1) {        // dQ (+ delta): one workgroup per 256 Q rows
+    if (parts & 1) {        // dQ (+ delta): one workgroup per 256 Q rows; dq16: the body built on v_mfma_f32_16x16x32 (csrc/gen/bwd_dq_m16_gen.py)
         p.nblk = (p.Nq + 255) / 256;
-        const dim3 grid((unsigned)((int64_t)p.B * p.H * p.nblk));
-        if (dq16 && neg_delta) {        // the body built on v_mfma_f32_16x16x32 (csrc/gen/bwd_dq_m16_gen.py)
-            constexpr auto kern = fa2::bwd_dq_d128_kernel<BF16, CAUSAL, true, true>;
-            if (int rc = fa2::set_lds<kern>(fa2::kBwdDqLdsBytes)) return rc;
-            hipLaunchKernelGGL(kern, grid, dim3(256), fa2::kBwdDqLdsBytes, stream, p);
-        } else if (dq16) {
-            constexpr auto kern = fa2::bwd_dq_d128_kernel<BF16, CAUSAL, false, true>;
-            if (int rc = fa2::set_lds<kern>(fa2::kBwdDqLdsBytes)) return rc;
-            hipLaunchKernelGGL(kern, grid, dim3(256), fa2::kBwdDqLdsBytes, stream, p);
-        } else if (neg_delta) {
-            constexpr auto kern = fa2::bwd_dq_d128_kernel<BF16, CAUSAL, true>;
-            if (int rc = fa2::set_lds<kern>(fa2::kBwdDqLdsBytes)) return rc;
-            hipLaunchKernelGGL(kern, grid, dim3(256), fa2::kBwdDqLdsBytes, stream, p);
-        } else {
-            constexpr auto kern = fa2::bwd_dq_d128_kernel<BF16, CAUSAL, false>;
-            if (int rc = fa2::set_lds<kern>(fa2::kBwdDqLdsBytes)) return rc;
-            hipLaunchKernelGGL(kern, grid, dim3(256), fa2::kBwdDqLdsBytes, stream, p);
-        }
-        if (int rc = (int)hipGetLastError()) return rc;
+        if (int rc = dq16 ? (neg_delta ? launch_dq<BF16, CAUSAL, true, true>(p, stream) : launch_dq<BF16, CAUSAL, false, true>(p, stream))
+                          : (neg_delta ? launch_dq<BF16, CAUSAL, true>(p, stream) : launch_dq<BF16, CAUSAL, false>(p, stream))) return rc;
     }
     if (parts & 2) {        // dK / dV: one workgroup per 128 KV rows
         p.nblk = (p.Nkv + 127) / 128;

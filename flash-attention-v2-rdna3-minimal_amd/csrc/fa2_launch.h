@@ -3,6 +3,9 @@
 // The library is compiled as several translation units in parallel (build.py): host.cpp holds the C-ABI, the argument
 // validation and the launch heuristics; the others hold the kernel instantiations of one family each and export one
 // launcher per dtype.  Nothing here is part of the public boundary (include/fa2_gfx950.h): every symbol is hidden.
+// Here: the options, the split plans, the one kernel-launch helper (set_lds + launch) and one FA2_LAUNCHER line per exported launcher.
+// fa2_pass_launch.h has the passes of the compiler-scheduled kernels as launches (what the per-dtype units share), fa2_family_unit.h the body of
+// the six family units.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -93,19 +96,51 @@ int set_lds(int bytes) {
     return rc;
 }
 
+// One kernel launch: opt the kernel in (set_lds), launch it, return hipGetLastError().  A launcher whose LDS size varies per call (bwd_bias_hip.cpp: the
+// bias images) opts its kernels in once with the largest size and launches with the call's own: LdsBytes(launch, optin).
+struct LdsBytes {
+    int launch, optin;
+    LdsBytes(int bytes) : launch(bytes), optin(bytes) {}
+    LdsBytes(int launch_bytes, int optin_bytes) : launch(launch_bytes), optin(optin_bytes) {}
+};
+template <auto Kernel, class... Args>
+int launch(dim3 grid, dim3 block, LdsBytes lds, hipStream_t stream, const Args&... args) {
+    if (int rc = set_lds<Kernel>(lds.optin)) return rc;
+    hipLaunchKernelGGL(Kernel, grid, block, lds.launch, stream, args...);
+    return (int)hipGetLastError();
+}
+
+// The per-dtype units (build.py compiles them twice, -DFA2_TU_BF16=0 and =1) name their exported launchers FA2_DT(launch_x): launch_x_f16 / launch_x_bf16.
+#define FA2_PASTE_(a, b) a##b
+#define FA2_PASTE(a, b) FA2_PASTE_(a, b)
+#ifdef FA2_TU_BF16
+#if FA2_TU_BF16
+#define FA2_DT(name) FA2_PASTE(name, _bf16)
+#else
+#define FA2_DT(name) FA2_PASTE(name, _f16)
+#endif
+#endif
+// ... and FA2_LAUNCHER declares the pair and name(bool bf16, ...), which picks one of them for a dtype known at run time (host.cpp)
+#define FA2_UNPAREN(...) __VA_ARGS__
+#define FA2_LAUNCHER(name, params, args)                   \
+    FA2_HIDDEN int name##_f16 params;                      \
+    FA2_HIDDEN int name##_bf16 params;                     \
+    inline int name(bool bf16, FA2_UNPAREN params) { return bf16 ? name##_bf16 args : name##_f16 args; }
+#define FA2_FWD_FAMILY_LAUNCHER(name) FA2_LAUNCHER(name, (int HD, const FwdParams& p, int rows, hipStream_t stream), (HD, p, rows, stream))
+#define FA2_BWD_FAMILY_LAUNCHER(name) FA2_LAUNCHER(name, (int HD, const BwdParams& p, hipStream_t stream), (HD, p, stream))
+#define FA2_FWD_SMOD_LAUNCHER(name) \
+    FA2_LAUNCHER(name, (int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm), (HD, p, rows, stream, sm))
+#define FA2_BWD_SMOD_LAUNCHER(name) FA2_LAUNCHER(name, (int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm), (HD, p, stream, sm))
+
 // ---- one launcher per (family, dtype); `HD` is the kernel head dim (fa2_padded_head_dim)
 // generic HIP forward (fwd_hip.cpp): rows = 256 (8 waves) or 128 (4 waves) per workgroup; bias: the BIAS kernels (always 128 rows)
-FA2_HIDDEN int launch_fwd_hip_f16(int HD, const FwdParams& p, bool causal, int rows, bool bias, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_hip_bf16(int HD, const FwdParams& p, bool causal, int rows, bool bias, hipStream_t stream);
+FA2_LAUNCHER(launch_fwd_hip, (int HD, const FwdParams& p, bool causal, int rows, bool bias, hipStream_t stream), (HD, p, causal, rows, bias, stream))
 // KV sweeps of at most two tiles, non-causal, no bias, head dims <= 128 (fa2_fwd_short.hip.h; round 6): 128-row workgroups, one memory round trip
-FA2_HIDDEN int launch_fwd_short_f16(int HD, const FwdParams& p, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_short_bf16(int HD, const FwdParams& p, hipStream_t stream);
+FA2_LAUNCHER(launch_fwd_short, (int HD, const FwdParams& p, hipStream_t stream), (HD, p, stream))
 // trimmed instantiations of the same kernels for head dims well below HD (fwd_hip.cpp compiled with -DFA2_TU_TRIM=1); -1 = none for this p.D
-FA2_HIDDEN int launch_fwd_hip_trim_f16(int HD, const FwdParams& p, bool causal, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_hip_trim_bf16(int HD, const FwdParams& p, bool causal, int rows, hipStream_t stream);
+FA2_LAUNCHER(launch_fwd_hip_trim, (int HD, const FwdParams& p, bool causal, int rows, hipStream_t stream), (HD, p, causal, rows, stream))
 // merge of the KV-split parts a forward launch left in p.ws (fwd_hip.cpp)
-FA2_HIDDEN int launch_fwd_combine_f16(int HD, const FwdParams& p, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_combine_bf16(int HD, const FwdParams& p, hipStream_t stream);
+FA2_LAUNCHER(launch_fwd_combine, (int HD, const FwdParams& p, hipStream_t stream), (HD, p, stream))
 // hand-scheduled forward, head dim exactly 128 or 64 (fwd_asm.cpp)
 // fold: the body that folds scale * log2(e) into Q (FA2_CONTRACT_PRESCALE_Q) instead of scaling the f32 product
 // m16: the body built on v_mfma_f32_16x16x32 (head dim 128, f32 scale, whole items only; csrc/gen/fwd_m16_gen.py) where it applies
@@ -162,52 +197,35 @@ inline int64_t plan_bwd_split(int HD, const BwdParams& p, bool causal, SplitPlan
     return dq->bytes > dkv->bytes ? dq->bytes : dkv->bytes;
 }
 // HIP backward (bwd_hip.cpp): parts bit 0 = dQ pass (+ delta workspace), bit 1 = dK / dV pass(es)
-FA2_HIDDEN int launch_bwd_hip_f16(int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_hip_bf16(int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream);
+FA2_LAUNCHER(launch_bwd_hip, (int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream), (HD, p, causal, parts, stream))
 // dQ pass (+ delta, or -delta for the hand-scheduled dK / dV pass) of KV sweeps of at most two tiles, non-causal, no bias, head dims <= 128 (fa2_bwd_short.hip.h; round 6)
-FA2_HIDDEN int launch_bwd_short_dq_f16(int HD, const BwdParams& p, bool neg_delta, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_short_dq_bf16(int HD, const BwdParams& p, bool neg_delta, hipStream_t stream);
+FA2_LAUNCHER(launch_bwd_short_dq, (int HD, const BwdParams& p, bool neg_delta, hipStream_t stream), (HD, p, neg_delta, stream))
 // trimmed instantiations of the same passes for head dims well below HD (bwd_hip.cpp compiled with -DFA2_TU_TRIM=1); -1 = none for this p.D
-FA2_HIDDEN int launch_bwd_hip_trim_f16(int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_hip_trim_bf16(int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream);
+FA2_LAUNCHER(launch_bwd_hip_trim, (int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream), (HD, p, causal, parts, stream))
 // sum of the parts a split pass left in p.ws (bwd_merge_kernel, bwd_hip.cpp): which = 1: dQ, 2: dK and dV; head dims <= 128
-FA2_HIDDEN int launch_bwd_merge_f16(int HD, const BwdParams& p, int which, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_merge_bf16(int HD, const BwdParams& p, int which, hipStream_t stream);
+FA2_LAUNCHER(launch_bwd_merge, (int HD, const BwdParams& p, int which, hipStream_t stream), (HD, p, which, stream))
 // HIP backward through a biased / masked forward (bwd_bias_hip.cpp): dQ, dV, dK; head dims up to 256
-FA2_HIDDEN int launch_bwd_bias_hip_f16(int HD, const BwdParams& p, bool causal, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_bias_hip_bf16(int HD, const BwdParams& p, bool causal, hipStream_t stream);
+FA2_LAUNCHER(launch_bwd_bias_hip, (int HD, const BwdParams& p, bool causal, hipStream_t stream), (HD, p, causal, stream))
 // sliding-window attention (window_hip.cpp): the WIN forms of the compiler-scheduled forward (rows = 128 | 256 per workgroup) and backward passes;
 // the window, causal flag already folded in, travels in p.bs (set_window / get_window, fa2_fwd_kernel.hip.h)
-FA2_HIDDEN int launch_fwd_window_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_window_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_window_f16(int HD, const BwdParams& p, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_window_bf16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_FWD_FAMILY_LAUNCHER(launch_fwd_window)
+FA2_BWD_FAMILY_LAUNCHER(launch_bwd_window)
 // packed, variable-length attention (varlen_hip.cpp): the same launchers over the VARLEN forms; p.Nq / p.Nkv = the stated maximum lengths, p.B = the number
 // of sequences, batch strides 0, cu_seqlens_q / cu_seqlens_k in p.bias / p.ws (set_varlen / get_varlen), the window's offset field = the bottom-right flag
-FA2_HIDDEN int launch_fwd_varlen_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_varlen_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_varlen_f16(int HD, const BwdParams& p, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_varlen_bf16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_FWD_FAMILY_LAUNCHER(launch_fwd_varlen)
+FA2_BWD_FAMILY_LAUNCHER(launch_bwd_varlen)
 // attention dropout (dropout_hip.cpp, varlen_dropout_hip.cpp): the same launchers over the DROP forms of the windowed and packed kernels; the seed and
 // the threshold travel in p.full_items / p.split_items / p.bias_kind (set_dropout, fa2_dropout.h)
-FA2_HIDDEN int launch_fwd_dropout_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_dropout_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_dropout_f16(int HD, const BwdParams& p, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_dropout_bf16(int HD, const BwdParams& p, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_varlen_dropout_f16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_fwd_varlen_dropout_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_varlen_dropout_f16(int HD, const BwdParams& p, hipStream_t stream);
-FA2_HIDDEN int launch_bwd_varlen_dropout_bf16(int HD, const BwdParams& p, hipStream_t stream);
+FA2_FWD_FAMILY_LAUNCHER(launch_fwd_dropout)
+FA2_BWD_FAMILY_LAUNCHER(launch_bwd_dropout)
+FA2_FWD_FAMILY_LAUNCHER(launch_fwd_varlen_dropout)
+FA2_BWD_FAMILY_LAUNCHER(launch_bwd_varlen_dropout)
 // score modifiers (scoremod_hip.cpp, varlen_scoremod_hip.cpp): the same launchers over the SMOD forms of the windowed and packed kernels, with the
 // ScoreMod block (fa2_scoremod.h: softcap, the ALiBi slope pointer and its stride) as a further kernel argument
-FA2_HIDDEN int launch_fwd_scoremod_f16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
-FA2_HIDDEN int launch_fwd_scoremod_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
-FA2_HIDDEN int launch_bwd_scoremod_f16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
-FA2_HIDDEN int launch_bwd_scoremod_bf16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
-FA2_HIDDEN int launch_fwd_varlen_scoremod_f16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
-FA2_HIDDEN int launch_fwd_varlen_scoremod_bf16(int HD, const FwdParams& p, int rows, hipStream_t stream, const ScoreMod& sm);
-FA2_HIDDEN int launch_bwd_varlen_scoremod_f16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
-FA2_HIDDEN int launch_bwd_varlen_scoremod_bf16(int HD, const BwdParams& p, hipStream_t stream, const ScoreMod& sm);
+FA2_FWD_SMOD_LAUNCHER(launch_fwd_scoremod)
+FA2_BWD_SMOD_LAUNCHER(launch_bwd_scoremod)
+FA2_FWD_SMOD_LAUNCHER(launch_fwd_varlen_scoremod)
+FA2_BWD_SMOD_LAUNCHER(launch_bwd_varlen_scoremod)
 // hand-scheduled backward, head dim exactly 128 (bwd_asm.cpp); same `parts`
 // neg_delta: the dQ pass writes -delta (the hand-scheduled dK/dV pass reads it as such; the HIP dK/dV passes read +delta)
 // kfold: the dK / dV body whose P side folds scale * log2(e) into its K fragments (option "fold"; host.cpp: bwd_folds)
@@ -215,26 +233,6 @@ FA2_HIDDEN int launch_bwd_varlen_scoremod_bf16(int HD, const BwdParams& p, hipSt
 // dkv16: likewise the dK / dV pass (csrc/gen/bwd_dkv_m16_gen.py)
 FA2_HIDDEN int launch_bwd_d128(bool bf16, const BwdParams& p, bool causal, int parts, bool neg_delta, bool kfold, hipStream_t stream, bool dq16 = false,
                                bool dkv16 = false);
-
-// ---- the launcher of a family for a dtype known at run time (host.cpp; the windowed / packed / dropout families go through its table)
-inline int launch_fwd_hip(bool bf16, int HD, const FwdParams& p, bool causal, int rows, bool bias, hipStream_t stream) {
-    return bf16 ? launch_fwd_hip_bf16(HD, p, causal, rows, bias, stream) : launch_fwd_hip_f16(HD, p, causal, rows, bias, stream);
-}
-inline int launch_fwd_short(bool bf16, int HD, const FwdParams& p, hipStream_t stream) {
-    return bf16 ? launch_fwd_short_bf16(HD, p, stream) : launch_fwd_short_f16(HD, p, stream);
-}
-inline int launch_fwd_combine(bool bf16, int HD, const FwdParams& p, hipStream_t stream) {
-    return bf16 ? launch_fwd_combine_bf16(HD, p, stream) : launch_fwd_combine_f16(HD, p, stream);
-}
-inline int launch_bwd_hip(bool bf16, int HD, const BwdParams& p, bool causal, int parts, hipStream_t stream) {
-    return bf16 ? launch_bwd_hip_bf16(HD, p, causal, parts, stream) : launch_bwd_hip_f16(HD, p, causal, parts, stream);
-}
-inline int launch_bwd_short_dq(bool bf16, int HD, const BwdParams& p, bool neg_delta, hipStream_t stream) {
-    return bf16 ? launch_bwd_short_dq_bf16(HD, p, neg_delta, stream) : launch_bwd_short_dq_f16(HD, p, neg_delta, stream);
-}
-inline int launch_bwd_bias_hip(bool bf16, int HD, const BwdParams& p, bool causal, hipStream_t stream) {
-    return bf16 ? launch_bwd_bias_hip_bf16(HD, p, causal, stream) : launch_bwd_bias_hip_f16(HD, p, causal, stream);
-}
 
 // merge of partial attention results (merge_hip.cpp; fa2_merge_fwd / fa2_merge_bwd): the kernels' argument block.  The parts' pointers travel BY VALUE
 // (host arrays copied in here: no device copy, graph-capturable); every part shares one stride set.  Element strides {batch, head, row} / {batch, head}.

@@ -13,9 +13,6 @@ namespace {
 // (fa2_fwd_d128.hip.h).  Option "persist" = 0 launches one workgroup per item instead (A/B measurements, bit-identity tests).
 template <int HD, bool BF16, bool CAUSAL, bool FOLD, bool M16 = false, bool LM = false>
 int launch_asm_t(const fa2::FwdParams& p0, hipStream_t stream) {
-    constexpr auto kern = fa2::fwd_asm_kernel<HD, BF16, CAUSAL, FOLD, M16, LM>;
-    constexpr int lds = fa2::AsmGeo<HD>::LDS_BYTES;
-    if (int rc = fa2::set_lds<kern>(lds)) return rc;
     fa2::FwdParams p = p0;
     p.persist = fa2::options().persist.load(std::memory_order_relaxed) ? 1 : 0;
     const int pg = fa2::device_cus() & ~7;       // a multiple of 8: a unit stays on its head's XCD
@@ -38,21 +35,19 @@ int launch_asm_t(const fa2::FwdParams& p0, hipStream_t stream) {
     int64_t grid = (int64_t)p.nbh * per_head;
     if (!CAUSAL && p.item_cap > 0) grid = p.item_cap;
     if (p.persist && pg > 0 && grid > pg) grid = pg;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, p);
-    return (int)hipGetLastError();
+    return fa2::launch<fa2::fwd_asm_kernel<HD, BF16, CAUSAL, FOLD, M16, LM>>(dim3((unsigned)grid), dim3(256), fa2::AsmGeo<HD>::LDS_BYTES, stream, p);
 }
 
 // head dim 256 (round 6): 128-row workgroups, one item each (fa2_fwd_d256.hip.h)
 template <bool BF16, bool CAUSAL, bool TRIM, int KS = 8>
 int launch_d256_t(const fa2::FwdParams& p0, hipStream_t stream) {
     constexpr auto kern = fa2::fwd_asm_d256_kernel<BF16, CAUSAL, TRIM, KS>;
-    if (int rc = fa2::set_lds<kern>(fa2::kD256LdsBytes)) return rc;
+    if (int rc = fa2::set_lds<kern>(fa2::kD256LdsBytes)) return rc;      // (here, not only in launch: a failed opt-in is reported before FA2_ERR_GRID)
     fa2::FwdParams p = p0;
     p.nqblk = (p.Nq + fa2::kD256Rows - 1) / fa2::kD256Rows;
     const int64_t grid = (int64_t)p.nbh * p.nqblk;
     if (grid > 0x7fffffffLL) return FA2_ERR_GRID;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), fa2::kD256LdsBytes, stream, p);
-    return (int)hipGetLastError();
+    return fa2::launch<kern>(dim3((unsigned)grid), dim3(256), fa2::kD256LdsBytes, stream, p);
 }
 
 }  // namespace

@@ -599,23 +599,17 @@ int fwd_validate(const FwdCall& c, fa2::FwdParams& p, int& HD) {
     return FA2_OK;
 }
 
-// ---- the windowed, packed and dropout kernel families share one launcher signature per direction: [packed][dropout][bf16]
-using FwdFamilyLaunch = int (*)(int HD, const fa2::FwdParams& p, int rows, hipStream_t stream);
-using BwdFamilyLaunch = int (*)(int HD, const fa2::BwdParams& p, hipStream_t stream);
-constexpr FwdFamilyLaunch kFwdFamily[2][2][2] = {
-    {{fa2::launch_fwd_window_f16, fa2::launch_fwd_window_bf16}, {fa2::launch_fwd_dropout_f16, fa2::launch_fwd_dropout_bf16}},
-    {{fa2::launch_fwd_varlen_f16, fa2::launch_fwd_varlen_bf16}, {fa2::launch_fwd_varlen_dropout_f16, fa2::launch_fwd_varlen_dropout_bf16}}};
-constexpr BwdFamilyLaunch kBwdFamily[2][2][2] = {
-    {{fa2::launch_bwd_window_f16, fa2::launch_bwd_window_bf16}, {fa2::launch_bwd_dropout_f16, fa2::launch_bwd_dropout_bf16}},
-    {{fa2::launch_bwd_varlen_f16, fa2::launch_bwd_varlen_bf16}, {fa2::launch_bwd_varlen_dropout_f16, fa2::launch_bwd_varlen_dropout_bf16}}};
+// ---- the windowed, packed and dropout kernel families share one launcher signature per direction: [packed][dropout]
+using FwdFamilyLaunch = int (*)(bool bf16, int HD, const fa2::FwdParams& p, int rows, hipStream_t stream);
+using BwdFamilyLaunch = int (*)(bool bf16, int HD, const fa2::BwdParams& p, hipStream_t stream);
+constexpr FwdFamilyLaunch kFwdFamily[2][2] = {{fa2::launch_fwd_window, fa2::launch_fwd_dropout}, {fa2::launch_fwd_varlen, fa2::launch_fwd_varlen_dropout}};
+constexpr BwdFamilyLaunch kBwdFamily[2][2] = {{fa2::launch_bwd_window, fa2::launch_bwd_dropout}, {fa2::launch_bwd_varlen, fa2::launch_bwd_varlen_dropout}};
 
-// ... and the score-modifier forms of the windowed / packed kernels, which take the ScoreMod block as well: [packed][bf16]
-using FwdSmodLaunch = int (*)(int HD, const fa2::FwdParams& p, int rows, hipStream_t stream, const fa2::ScoreMod& sm);
-using BwdSmodLaunch = int (*)(int HD, const fa2::BwdParams& p, hipStream_t stream, const fa2::ScoreMod& sm);
-constexpr FwdSmodLaunch kFwdSmod[2][2] = {{fa2::launch_fwd_scoremod_f16, fa2::launch_fwd_scoremod_bf16},
-                                          {fa2::launch_fwd_varlen_scoremod_f16, fa2::launch_fwd_varlen_scoremod_bf16}};
-constexpr BwdSmodLaunch kBwdSmod[2][2] = {{fa2::launch_bwd_scoremod_f16, fa2::launch_bwd_scoremod_bf16},
-                                          {fa2::launch_bwd_varlen_scoremod_f16, fa2::launch_bwd_varlen_scoremod_bf16}};
+// ... and the score-modifier forms of the windowed / packed kernels, which take the ScoreMod block as well: [packed]
+using FwdSmodLaunch = int (*)(bool bf16, int HD, const fa2::FwdParams& p, int rows, hipStream_t stream, const fa2::ScoreMod& sm);
+using BwdSmodLaunch = int (*)(bool bf16, int HD, const fa2::BwdParams& p, hipStream_t stream, const fa2::ScoreMod& sm);
+constexpr FwdSmodLaunch kFwdSmod[2] = {fa2::launch_fwd_scoremod, fa2::launch_fwd_varlen_scoremod};
+constexpr BwdSmodLaunch kBwdSmod[2] = {fa2::launch_bwd_scoremod, fa2::launch_bwd_varlen_scoremod};
 fa2::ScoreMod scoremod_of(const Call& c) { return fa2::make_scoremod(c.softcap, c.scale, c.slopes, c.slope_stride); }
 
 // fa2_fwd_workspace_bytes.  The size query has no scale argument, and the split plan depends on the scale at head dim 64 (a launch that folds the
@@ -669,8 +663,8 @@ int fwd_run(const FwdCall& c) {
     if (c.packed)
         if (int rc = check_packed_tensors(c)) return rc;
     hipStream_t stream = (hipStream_t)c.stream;
-    if (c.scoremod) return kFwdSmod[c.packed][bf16](HD, p, family_rows, stream, scoremod_of(c));
-    if (c.windowed) return kFwdFamily[c.packed][c.dropout][bf16](HD, p, family_rows, stream);
+    if (c.scoremod) return kFwdSmod[c.packed](bf16, HD, p, family_rows, stream, scoremod_of(c));
+    if (c.windowed) return kFwdFamily[c.packed][c.dropout](bf16, HD, p, family_rows, stream);
     if (c.bias.kind != FA2_BIAS_NONE) return fa2::launch_fwd_hip(bf16, HD, p, causal, 128, true, stream);
     return launch_fwd(HD, bf16, p, causal, stream, c.ws, c.ws_bytes);
 }
@@ -762,8 +756,8 @@ int bwd_run(const BwdCall& c) {
         if (int rc = check_packed_tensors(c)) return rc;
     if (int rc = check_dlse(c, p)) return rc;
     hipStream_t stream = (hipStream_t)c.stream;
-    if (c.scoremod) return kBwdSmod[c.packed][bf16](HD, p, stream, scoremod_of(c));
-    if (c.windowed) return kBwdFamily[c.packed][c.dropout][bf16](HD, p, stream);
+    if (c.scoremod) return kBwdSmod[c.packed](bf16, HD, p, stream, scoremod_of(c));
+    if (c.windowed) return kBwdFamily[c.packed][c.dropout](bf16, HD, p, stream);
     if (c.bias.kind != FA2_BIAS_NONE) return fa2::launch_bwd_bias_hip(bf16, HD, p, causal, stream);
     return launch_bwd(HD, bf16, p, causal, stream);
 }

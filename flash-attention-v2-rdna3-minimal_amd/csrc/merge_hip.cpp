@@ -138,25 +138,24 @@ __global__ __launch_bounds__(kMergeThreads) void merge_bwd_kernel(const MergePar
         if (k < p.nparts) p.dlse_parts[k][dlo] = w[k] != 0.f ? w[k] * (gl + dot_unit * (d[k] - dot_o)) : 0.f;
 }
 
-template <typename K>
-int launch_merge(K kern, MergeParams& p, hipStream_t stream) {
+template <auto Kernel>
+int launch_merge(MergeParams& p, hipStream_t stream) {
     p.lanes = p.D / 8;
     p.group = 1;
     while (p.group < p.lanes) p.group <<= 1;
     p.rows = (int64_t)p.B * p.H * p.Nq;
     const int64_t per_block = kMergeThreads / p.group, blocks = (p.rows + per_block - 1) / per_block;
     if (blocks > 0x7fffffffLL) return FA2_ERR_GRID;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kMergeThreads), 0, stream, p);
-    return (int)hipGetLastError();
+    return launch<Kernel>(dim3((unsigned)blocks), dim3(kMergeThreads), 0, stream, p);
 }
 
 }  // namespace
 
 int launch_merge_fwd(bool bf16, MergeParams& p, hipStream_t stream) {
-    return bf16 ? launch_merge(merge_fwd_kernel<true>, p, stream) : launch_merge(merge_fwd_kernel<false>, p, stream);
+    return bf16 ? launch_merge<merge_fwd_kernel<true>>(p, stream) : launch_merge<merge_fwd_kernel<false>>(p, stream);
 }
 int launch_merge_bwd(bool bf16, MergeParams& p, hipStream_t stream) {
-    return bf16 ? launch_merge(merge_bwd_kernel<true>, p, stream) : launch_merge(merge_bwd_kernel<false>, p, stream);
+    return bf16 ? launch_merge<merge_bwd_kernel<true>>(p, stream) : launch_merge<merge_bwd_kernel<false>>(p, stream);
 }
 
 }  // namespace fa2
