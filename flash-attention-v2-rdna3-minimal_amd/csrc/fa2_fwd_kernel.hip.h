@@ -307,27 +307,30 @@ struct Geo {
 //               instead of 68 tile-steps at B2 H16 N4096).  FA2_CAUSAL_HPG > 0 restricts the interleave to that many
 //               heads at a time (interleaving all heads of an XCD cycles their K/V through one 4 MiB L2).
 template <bool CAUSAL>
-__device__ __forceinline__ void block_to_head_qblock(const FwdParams& p, int bid, int& bh, int& qblk) {
-    const int nbh = p.nbh;               // (a launch may cover a sub-range of the heads: host.cpp, tail split)
+__device__ __forceinline__ void block_to_head_qblock(int nbh, int nqblk, int bh0, int bid, int& bh, int& qblk) {      // (nbh: a launch may cover a sub-range of the heads: host.cpp, tail split)
     if ((nbh & 7) == 0) {
         const int slot = bid >> 3, hpx = nbh >> 3;   // hpx = heads per XCD
         if (CAUSAL) {
             const int hpg = (FA2_CAUSAL_HPG > 0 && hpx % FA2_CAUSAL_HPG == 0) ? FA2_CAUSAL_HPG : hpx;
-            const int per_group = hpg * p.nqblk, g = slot / per_group, r = slot % per_group;
+            const int per_group = hpg * nqblk, g = slot / per_group, r = slot % per_group;
             bh = (bid & 7) + 8 * (g * hpg + r % hpg);
-            qblk = p.nqblk - 1 - r / hpg;
+            qblk = nqblk - 1 - r / hpg;
         } else {
-            bh = (bid & 7) + 8 * (slot / p.nqblk);
-            qblk = slot % p.nqblk;
+            bh = (bid & 7) + 8 * (slot / nqblk);
+            qblk = slot % nqblk;
         }
     } else if (CAUSAL) {
         bh = bid % nbh;
-        qblk = p.nqblk - 1 - bid / nbh;
+        qblk = nqblk - 1 - bid / nbh;
     } else {
-        bh = bid / p.nqblk;
-        qblk = bid % p.nqblk;
+        bh = bid / nqblk;
+        qblk = bid % nqblk;
     }
-    bh += p.bh0;
+    bh += bh0;
+}
+template <bool CAUSAL>
+__device__ __forceinline__ void block_to_head_qblock(const FwdParams& p, int bid, int& bh, int& qblk) {
+    block_to_head_qblock<CAUSAL>(p.nbh, p.nqblk, p.bh0, bid, bh, qblk);
 }
 
 // NW waves per workgroup, each owning QB consecutive 32-row Q blocks (NW * QB * 32 == 256):

@@ -35,7 +35,18 @@ int launch_asm_t(const fa2::FwdParams& p0, hipStream_t stream) {
     int64_t grid = (int64_t)p.nbh * per_head;
     if (!CAUSAL && p.item_cap > 0) grid = p.item_cap;
     if (p.persist && pg > 0 && grid > pg) grid = pg;
-    return fa2::launch<fa2::fwd_asm_kernel<HD, BF16, CAUSAL, FOLD, M16, LM>>(dim3((unsigned)grid), dim3(256), fa2::AsmGeo<HD>::LDS_BYTES, stream, p);
+    // the loop's divisors travel with their reciprocals (fa2_fwd_d128.hip.h: div_by)
+    fa2::AsmFwdParams ap;
+    ap.p = p;
+    ap.m_H = fa2::div_magic(p.H);
+    ap.m_nqblk = fa2::div_magic(p.nqblk);
+    ap.m_units = fa2::div_magic((p.nqblk + 1) / 2);
+    ap.m_split_items = fa2::div_magic(p.split_items);
+    ap.m_kv_group = fa2::div_magic(p.kv_group);
+    const int nt = (p.Nkv + fa2::kKvTile - 1) / fa2::kKvTile, ns = p.nsplit > 1 ? (p.nsplit < fa2::kMaxSplit ? p.nsplit : fa2::kMaxSplit) : 1;
+    for (int i = 0; i <= fa2::kMaxSplit; ++i) ap.part_tile[i] = (int)((int64_t)(i < ns ? i : ns) * nt / ns);      // (fa2_fwd_kernel.hip.h: the same ranges)
+    ap.ws_lse = p.ws ? p.ws + (int64_t)p.split_items * p.nsplit * fa2::kSplitRows * HD : nullptr;
+    return fa2::launch<fa2::fwd_asm_kernel<HD, BF16, CAUSAL, FOLD, M16, LM>>(dim3((unsigned)grid), dim3(256), fa2::AsmGeo<HD>::LDS_BYTES, stream, ap);
 }
 
 // head dim 256 (round 6): 128-row workgroups, one item each (fa2_fwd_d256.hip.h)

@@ -1,7 +1,7 @@
 """Kernel-variant A/B harness (developer tool).
 
   build (CPU container):  python tools/kbench.py build NAME[:-DFOO=1,-DBAR=2] ...
-  run   (GPU box):        python tools/kbench.py run [--rounds R] [--iters I] [--cfg c2,c3,c4,b8] [NAME ...]
+  run   (GPU box):        python tools/kbench.py run [NAME ...] [--rounds R] [--iters I] [--cfg c2,c3,c4,b8] [--settle-ms MS]
 
 Variants are separate copies of libfa2_gfx950.so compiled with extra -D flags into tools/variants/
 (git-ignored, but they travel with gpurun).  `run` checks every variant against an fp32 torch
@@ -146,7 +146,7 @@ def ref_fp32(q, k, v, causal):
     return torch.matmul(torch.softmax(s, -1), v.float()), torch.logsumexp(s, -1) * 1.4426950408889634
 
 
-def run(names, rounds, iters, cfgs, fill="rand"):
+def run(names, rounds, iters, cfgs, fill="rand", settle_ms=0):
     import torch
     paths = sorted(glob.glob(os.path.join(VAR_DIR, "*.so")))
     if names:
@@ -186,6 +186,14 @@ def run(names, rounds, iters, cfgs, fill="rand"):
             for _ in range(5):
                 var.fwd(q, k, v, o, lse, causal, stream)
         torch.cuda.synchronize()
+        if settle_ms > 0:               # after idle the chip boosts, overshoots and throttles for tens of ms — time what comes after
+            import time
+            t_end = time.time() + settle_ms * 1e-3
+            while time.time() < t_end:
+                for var in variants:
+                    for _ in range(25):
+                        var.fwd(q, k, v, o, lse, causal, stream)
+                torch.cuda.synchronize()
         for _ in range(rounds):
             for var in variants:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -206,8 +214,9 @@ def run(names, rounds, iters, cfgs, fill="rand"):
                         var.name, bb, hh, [(float(x[w, 0]), float(x[w, 32])) for w in range(4)], [(float(x[-4 + w, 0]), float(x[-4 + w, 32])) for w in range(4)]))
         for name, ts in times.items():
             med, mn = statistics.median(ts), min(ts)
-            print("   %-16s median %8.1f us  %7.1f TF (%4.1f%%)   best %8.1f us  %7.1f TF"
-                  % (name, med * 1e3, flops / med / 1e9, flops / med / 1e9 / 25, mn * 1e3, flops / mn / 1e9))
+            print("   %-16s median %8.1f us  %7.1f TF (%4.1f%%)   best %8.1f us  %7.1f TF   spread (max - min of the rounds) %6.2f us"
+                  % (name, med * 1e3, flops / med / 1e9, flops / med / 1e9 / 25, mn * 1e3, flops / mn / 1e9, (max(ts) - mn) * 1e3))
+            print("   %-16s rounds (us): %s" % ("", " ".join("%.1f" % (t * 1e3) for t in ts)))
 
 
 if __name__ == "__main__":
@@ -218,7 +227,8 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--cfg", default="c2")
     ap.add_argument("--fill", default="rand", choices=["rand", "randn", "zeros"])
+    ap.add_argument("--settle-ms", type=int, default=0, help="run every variant for this long before the timed rounds of a config")
     a = ap.parse_args()
     if a.cmd == "build":
         sys.exit(0 if build(a.names) else 1)
-    run(a.names, a.rounds, a.iters, a.cfg.split(","), a.fill)
+    run(a.names, a.rounds, a.iters, a.cfg.split(","), a.fill, a.settle_ms)
