@@ -34,6 +34,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.realpath(__file__)))
+import gen_driver  # noqa: E402
 import sched  # noqa: E402
 from isa import A, S, V, Arg, Ins, Label, M0, Neg, Program, VCC, mk  # noqa: E402
 
@@ -65,6 +66,8 @@ def f_swz16(r):
 
 class BodyEmitter:
     """What the bodies of both backward kernels share: fillers placed into MFMA gaps, counted LDS waits, the end-of-body sync."""
+    # accepted names (gen_driver.py): KEYS are a generator's DEFAULTS; abl= builds timing-only bodies with wrong results
+    PROBE_KEYS, PROBE_OPTS = ("abl",), ()
 
     def check_running_state(self, body, bookkeeping, name):
         """Legality of a placed body.  The filler streams are written against the running state a body is ENTERED with — the tile counter, the source
@@ -196,8 +199,10 @@ class DQ:
 
 class GenDQ(BodyEmitter):
     DEFAULTS = {"valu": (1.0, 47.0), "rowread": (0.0, 15.0), "trread": (17.0, 47.0), "dma": (1.0, 14.0), "opt": (), "abl": ()}
+    KEYS, OPTS, STEM = tuple(DEFAULTS), ("uni", "nocheck"), "fa2dq"
 
     def __init__(self, bf16=False, **cfg):
+        assert not gen_driver.unknown(type(self), cfg), gen_driver.unknown(type(self), cfg)
         self.cfg = dict(self.DEFAULTS)
         self.cfg.update(cfg)
         self.opt = set(self.cfg["opt"])
@@ -604,8 +609,10 @@ class KV:
 
 class GenDKV(BodyEmitter):
     DEFAULTS = {"valu_p": (1.0, 31.0), "valu_s": (1.0, 31.0), "rowread": (0.0, 15.0), "trread": (16.0, 31.0), "dma": (1.0, 12.0), "lread": (20.0, 31.0), "lread_p": (1.0, 12.0), "opt": (), "abl": ()}
+    KEYS, OPTS, STEM = tuple(DEFAULTS), ("kfold", "qsplit", "nocheck"), "fa2dkv"
 
     def __init__(self, bf16=False, **cfg):
+        assert not gen_driver.unknown(type(self), cfg), gen_driver.unknown(type(self), cfg)
         self.cfg = dict(self.DEFAULTS)
         self.cfg.update(cfg)
         self.opt = set(self.cfg["opt"])
@@ -1027,72 +1034,15 @@ class GenDKV(BodyEmitter):
         return p
 
 
-def clobber_list(vbase, sregs):
-    regs = ["v%d" % i for i in range(vbase, 256)] + ["a%d" % i for i in range(256)] + ["s%d" % i for i in sregs]
-    return ", ".join('"%s"' % r for r in regs + ["vcc", "scc", "memory"])
-
-
-def render_inline(prog, stem):
-    saved = Label.text
-    Label.text = lambda self: ".L%s_%s_%%=" % (stem, self.name)
-    try:
-        return "\n".join('"%s\\n"' % t for t in prog.text_lines()) + "\n"
-    finally:
-        Label.text = saved
-
-
-def parse_opts(text):
-    cfg = {}
-    for item in filter(None, (text or "").split(",")):
-        k, _, v = item.partition("=")
-        if k in ("abl", "opt"):
-            cfg[k] = tuple(x for x in v.split("+") if x)
-        else:
-            a, _, b = v.partition(":")
-            cfg[k] = (float(a), float(b or 0))
-    return cfg
-
-
-def write_atomic(path, text):
-    tmp = "%s.tmp.%d" % (path, os.getpid())
-    with open(tmp, "w") as f:
-        f.write(text)
-    os.replace(tmp, path)
-
-
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
-    ap.add_argument("--opt", default="", help="schedule windows / options: 'dq:valu=1:47,dq:abl=dma' (prefix dq: or dkv:)")
-    ap.add_argument("--probe", action="store_true", help="allow timing-probe options (abl=...: bodies with wrong results; never for the product build)")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    per = {"dq": [], "dkv": []}
-    for item in filter(None, a.opt.split(",")):
-        k, _, rest = item.partition(":")
-        per[k].append(rest)
-    cfgs = {k: parse_opts(",".join(v)) for k, v in per.items()}
-    if any("abl" in c for c in cfgs.values()) and not a.probe:
-        sys.exit("bwd_d128_gen.py: %r contains timing-probe options; they need --probe and must not go into the product build" % a.opt)
-    for bf16 in (False, True):
-        dt = "bf16" if bf16 else "f16"
-        prog = GenDQ(bf16, **cfgs["dq"]).build()
-        write_atomic(os.path.join(a.out, "fa2_bwd_dq_d128_%s.inc" % dt),
-                     "// GENERATED by csrc/gen/bwd_d128_gen.py %s — do not edit.  %d instructions.\n" % (a.opt, len(prog.ins)) + render_inline(prog, "fa2dq"))
-        print("fa2_bwd_dq_d128_%s.inc" % dt, len(prog.ins), "instructions")
-        for fold in (False, True):      # two dK / dV bodies per dtype: scale applied to the f32 scores / folded into the K fragments ("kfold"; host: option "fold")
-            c = dict(cfgs["dkv"])
-            c["opt"] = tuple(o for o in c.get("opt", ()) if o != "kfold") + (("kfold",) if fold else ())
-            prog = GenDKV(bf16, **c).build()
-            fn = "fa2_bwd_dkv_d128_%s%s.inc" % (dt, "_fold" if fold else "")
-            write_atomic(os.path.join(a.out, fn),
-                         "// GENERATED by csrc/gen/bwd_d128_gen.py %s — do not edit.  %d instructions.\n" % (a.opt, len(prog.ins)) + render_inline(prog, "fa2dkv"))
-            print(fn, len(prog.ins), "instructions")
-    write_atomic(os.path.join(a.out, "fa2_bwd_dq_d128_clobbers.inc"),
-                 "// GENERATED by csrc/gen/bwd_d128_gen.py — do not edit.\n" + clobber_list(DQ.VBASE, DQ.CLOBBER_S) + "\n")
-    write_atomic(os.path.join(a.out, "fa2_bwd_dkv_d128_clobbers.inc"),
-                 "// GENERATED by csrc/gen/bwd_d128_gen.py — do not edit.\n" + clobber_list(KV.VBASE, KV.CLOBBER_S) + "\n")
+    variants = []
+    for dt in ("f16", "bf16"):
+        variants.append(("fa2_bwd_dq_d128_%s.inc" % dt, GenDQ, {"bf16": dt == "bf16"}, ()))
+        # two dK / dV bodies per dtype: scale applied to the f32 scores / folded into the K fragments ("kfold"; host: option "fold")
+        variants.append(("fa2_bwd_dkv_d128_%s.inc" % dt, GenDKV, {"bf16": dt == "bf16"}, ()))
+        variants.append(("fa2_bwd_dkv_d128_%s_fold.inc" % dt, GenDKV, {"bf16": dt == "bf16"}, ("kfold",)))
+    gen_driver.run("bwd_d128_gen.py", variants, managed=("kfold",), prefixes={GenDQ: "dq", GenDKV: "dkv"},
+                   clobbers=[("fa2_bwd_dq_d128_clobbers.inc", DQ.VBASE, DQ.CLOBBER_S), ("fa2_bwd_dkv_d128_clobbers.inc", KV.VBASE, KV.CLOBBER_S)])
 
 
 if __name__ == "__main__":

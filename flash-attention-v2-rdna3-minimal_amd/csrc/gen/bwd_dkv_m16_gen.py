@@ -22,6 +22,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.realpath(__file__)))
 import bwd_d128_gen as base  # noqa: E402
+import gen_driver  # noqa: E402
 import sched  # noqa: E402
 from bwd_d128_gen import KV  # noqa: E402
 from isa import A, V, Arg, Ins, Label, M0, Neg, VCC, mk  # noqa: E402
@@ -72,9 +73,10 @@ class GenDKV16(base.GenDKV):
     DEFAULTS = {"valu_p": (2.0, 62.0), "valu_s": (2.0, 62.0), "rowread": (0.0, 30.0), "trread": (32.0, 62.0), "dma": (2.0, 24.0), "lread": (40.0, 62.0),
                 "lread_p": (2.0, 24.0), "opt": (), "abl": ()}
 
+    OPTS, STEM = ("nocheck",), "fa2dkv16"       # (no kfold / qsplit bodies on this tile)
+
     def __init__(self, bf16=False, **cfg):
         super().__init__(bf16, **cfg)
-        assert not self.kfold and not self.qsplit, "the 16x16x32 dK / dV generator has no kfold / qsplit bodies"
         self.mfma = "v_mfma_f32_16x16x32_bf16" if bf16 else "v_mfma_f32_16x16x32_f16"
 
     # ------------------------------------------------------------------ MFMA lists
@@ -310,22 +312,7 @@ class GenDKV16(base.GenDKV):
 
 
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
-    ap.add_argument("--opt", default="", help="schedule windows / options (bwd_d128_gen.parse_opts)")
-    ap.add_argument("--probe", action="store_true")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    cfg = base.parse_opts(a.opt)
-    if "abl" in cfg and not a.probe:
-        sys.exit("bwd_dkv_m16_gen.py: %r contains timing-probe options; they need --probe" % a.opt)
-    for bf16 in (False, True):
-        prog = GenDKV16(bf16, **cfg).build()
-        fn = "fa2_bwd_dkv_m16_%s.inc" % ("bf16" if bf16 else "f16")
-        base.write_atomic(os.path.join(a.out, fn),
-                          "// GENERATED by csrc/gen/bwd_dkv_m16_gen.py %s — do not edit.  %d instructions.\n" % (a.opt, len(prog.ins)) + base.render_inline(prog, "fa2dkv16"))
-        print(fn, len(prog.ins), "instructions")
+    gen_driver.run("bwd_dkv_m16_gen.py", [("fa2_bwd_dkv_m16_%s.inc" % dt, GenDKV16, {"bf16": dt == "bf16"}, ()) for dt in ("f16", "bf16")])
 
 
 if __name__ == "__main__":

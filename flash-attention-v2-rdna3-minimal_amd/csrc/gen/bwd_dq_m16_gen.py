@@ -21,6 +21,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.realpath(__file__)))
 import bwd_d128_gen as base  # noqa: E402
+import gen_driver  # noqa: E402
 import sched  # noqa: E402
 from bwd_d128_gen import DQ  # noqa: E402
 from isa import A, V, Arg, Ins, Label, Neg, VCC, mk  # noqa: E402
@@ -76,9 +77,10 @@ def GF(qg, ks):
 class GenDQ16(base.GenDQ):
     DEFAULTS = {"valu": (2.0, 94.0), "rowread": (0.0, 30.0), "trread": (34.0, 94.0), "dma": (2.0, 28.0), "opt": (), "abl": ()}
 
+    OPTS, STEM = ("nocheck",), "fa2dq16"
+
     def __init__(self, bf16=False, **cfg):
         super().__init__(bf16, **cfg)
-        assert "uni" not in self.opt
         self.mfma = "v_mfma_f32_16x16x32_bf16" if bf16 else "v_mfma_f32_16x16x32_f16"
 
     # ------------------------------------------------------------------ MFMA lists
@@ -391,19 +393,7 @@ class GenDQ16(base.GenDQ):
 
 
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
-    ap.add_argument("--opt", default="")
-    ap.add_argument("--probe", action="store_true")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    cfg = base.parse_opts(a.opt) if hasattr(base, "parse_opts") else {}
-    for bf16 in (False, True):
-        prog = GenDQ16(bf16, **cfg).build()
-        path = os.path.join(a.out, "fa2_bwd_dq_m16_%s.inc" % ("bf16" if bf16 else "f16"))
-        base.write_atomic(path, "// GENERATED by csrc/gen/bwd_dq_m16_gen.py %s — do not edit.  %d instructions.\n" % (a.opt, len(prog.ins)) + base.render_inline(prog, "fa2dq16"))
-        print(path, len(prog.ins), "instructions")
+    gen_driver.run("bwd_dq_m16_gen.py", [("fa2_bwd_dq_m16_%s.inc" % dt, GenDQ16, {"bf16": dt == "bf16"}, ()) for dt in ("f16", "bf16")])
 
 
 if __name__ == "__main__":

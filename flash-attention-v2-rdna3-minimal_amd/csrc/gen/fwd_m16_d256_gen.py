@@ -30,6 +30,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.realpath(__file__)))
 import fwd_d128_gen as base  # noqa: E402
 import fwd_m16_gen as m16  # noqa: E402
+import gen_driver  # noqa: E402
 import sched  # noqa: E402
 from fwd_d128_gen import (A_C, A_KD0, A_KR0, A_KRS, A_KTILE, A_LDSW, A_LIM0, A_LIM1, A_LSE0, A_NTW, A_NTWG, A_VD0, A_VR0, A_VRS, A_VTILE,  # noqa: E402,F401
                           NEG_INF, S_D, S_FLAG, S_KOFF, S_NOVM, S_T, S_TMP, S_TMP2, S_VOFF, S_WAVE, SB)
@@ -80,6 +81,10 @@ def VF(dg, kvs):
 
 
 class Gen256(m16.Gen16):
+    WINDOWS = ("m", "mmask", "e", "vread", "kread_ct", "dma", "dmaf")       # (dma: the guarded bodies' staging window, dmaf: the main-loop bodies')
+    KEYS = ("abl", "opt") + WINDOWS
+    OPTS = ("lm", "trim")
+
     def __init__(self, bf16=False, nks=8, **cfg):
         """nks: 32-column k-steps of Q.K^T the body really runs (opt=trim: 5 .. 8 for head dims <= 160 / 192 / 224 / 256; the d groups of O follow: 2 nks).
         The images, rings and the LDS-DMA are the head-dim-256 ones whatever nks is; k-steps and d groups that hold no real column — their MFMAs, their
@@ -149,7 +154,7 @@ class Gen256(m16.Gen16):
             g0 = self.npv + 8 * (ks - 3) + 7
             for kg in range(4):
                 it = kr[4 * ks + kg]
-                load[g0] += base._weight(it)
+                load[g0] += sched.weight(it)
                 slots[g0].append((g0 + 0.5 + 0.1 * kg, 3, it))
 
     def stream_vread(self, par):
@@ -503,23 +508,9 @@ class Gen256(m16.Gen16):
 
 
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
-    ap.add_argument("--opt", default="")
-    ap.add_argument("--probe", action="store_true")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    cfg = base.parse_opts(a.opt)
-    if base.is_probe(cfg) and not a.probe:
-        sys.exit("fwd_m16_d256_gen.py: %r contains timing-probe options; they need --probe" % a.opt)
-    for bf16, trim, nks in ((b, t, n) for b in (False, True) for (t, n) in ((False, 8), (True, 8), (True, 7), (True, 6), (True, 5))):
-        c = dict(cfg)
-        c["opt"] = tuple(o for o in cfg.get("opt", ()) if o != "trim") + (("trim",) if trim else ())
-        prog = Gen256(bf16, nks=nks, **c).build()
-        path = os.path.join(a.out, "fa2_fwd_m16_d256_%s%s.inc" % ("bf16" if bf16 else "f16", ("_trim%d" % nks) if trim else ""))
-        base.write_atomic(path, "// GENERATED by csrc/gen/fwd_m16_d256_gen.py %s — do not edit.  %d instructions.\n" % (a.opt, len(prog.ins)) + base.render_inline(prog))
-        print(path, len(prog.ins), "instructions")
+    variants = [("fa2_fwd_m16_d256_%s%s.inc" % ("bf16" if bf16 else "f16", ("_trim%d" % nks) if trim else ""), Gen256, {"bf16": bf16, "nks": nks}, ("trim",) if trim else ())
+                for bf16 in (False, True) for (trim, nks) in ((False, 8), (True, 8), (True, 7), (True, 6), (True, 5))]
+    gen_driver.run("fwd_m16_d256_gen.py", variants, managed=("trim",))
 
 
 if __name__ == "__main__":

@@ -32,6 +32,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.realpath(__file__)))
 import fwd_d128_gen as base  # noqa: E402
+import gen_driver  # noqa: E402
+import sched  # noqa: E402
 from fwd_d128_gen import (A_C, A_EPI, A_FLAGS, A_WSB, A_KD0, A_KR0, A_KRS, A_KROW4, A_KTILE, A_LDSW, A_LIM0, A_LIM1, A_LSE0, A_NKRS, A_NQRS,  # noqa: E402,F401
                           A_NQW, A_NTW, A_NTWG, A_NVRS, A_QD0, A_QRS, A_QT16, A_QW, A_VD0, A_VR0, A_VROW4, A_VRS, A_VTILE, KD, NEG_INF,
                           PSUM_MAX, QD, SB, S_D, S_FLAG, S_FIX, S_KOFF, S_NFAST, S_NOVM, S_PF, S_QH, S_QM0, S_QSB, S_QSOFF, S_SUM, S_T, S_TMP,
@@ -113,9 +115,14 @@ class Gen16(base.Gen):
     DEFAULTS16_64 = {"m": (2.0, 12.0), "e": (12.0, 64.0), "vread": (34.0, 44.0), "kread": (0.0, 24.0), "dma": (2.0, 20.0), "mmask": (2.0, 24.0),
                      "se0": (0.0, 48.0), "se1": (8.0, 60.0), "sc0": (48.0, 58.0), "sc1": (60.0, 64.0)}
 
+    # accepted names (gen_driver.py): the base generator's windows and the link gaps of the lm bodies, each also as d64_<w> (head dim 64 only),
+    # lm_<w> (lm bodies, head dim 128) and d64_lm_<w>; no trace builds, no qpre
+    WINDOWS = base.Gen.WINDOWS + ("lk0", "lk1", "lk2", "lk3")
+    KEYS = ("abl", "opt") + tuple(pre + w for w in WINDOWS for pre in ("", "d64_", "lm_", "d64_lm_"))
+    OPTS = ("ct", "lm", "nolm", "maxfirst")
+    PROBE_KEYS = ("abl",)
+
     def __init__(self, bf16=False, hd=128, **cfg):
-        opt = tuple(cfg.get("opt", ()))
-        assert "lmfma" not in opt, "the 16x16x32 generator has no lmfma bodies"
         user = {(k[4:] if k.startswith("d64_") else k): v for k, v in cfg.items() if hd == 64 or not k.startswith("d64_")}
         super().__init__(bf16, hd=hd, **cfg)
         self.NKS16, self.NDG = hd // 32, hd // 16         # k-steps of Q.K^T (32 head-dim columns each), 16-column d groups of O
@@ -347,18 +354,6 @@ class Gen16(base.Gen):
             if 0 <= k - 1 < 16:
                 e = prs[k - 1]
                 E += [mk("v_exp_f32", b[e], b[e], tag="trans"), mk("v_exp_f32", b[e + 1], b[e + 1], tag="trans")]
-            if "pkadd" in self.opt:
-                # opt=pkadd: a pair (two consecutive registers of one row) enters its row's sums with ONE packed add — two partial sums per row (the four
-                # scratch registers of the q block).  An anti-lever beside the energy-bound 32 x 32 body (-6.4 %); this body is issue-bound.
-                if 0 <= k - 2 < 16:
-                    e = prs[k - 2]
-                    tp = V(TMP[4 * qb + 2 * (e // 16)].idx, 2)
-                    if e % 16 == 2:               # the row's second pair: both are through the exp stage now
-                        Ad.append(mk("v_pk_add_f32", tp, b.sub(e - 2, 2), b.sub(e, 2), tag="valu"))
-                    elif e % 16 != 0:
-                        Ad.append(mk("v_pk_add_f32", tp, tp, b.sub(e, 2), tag="valu"))
-                out += F + E + Ad
-                continue
             if 0 <= k - 2 < 16:
                 e = prs[k - 2]
                 t = tsum[e // 16]
@@ -371,11 +366,6 @@ class Gen16(base.Gen):
                 if e % 16 != 0:
                     Ad.append(mk("v_add_f32", tsum[e // 16], tsum[e // 16], b[e + 1], tag="valu"))
             out += F + E + Ad
-        if "pkadd" in self.opt:
-            # row h: partial sums in TMP[4 qb + 2 h], +1 -> ta / tb (the registers the check and the rare block know)
-            t0, t1, t2_, t3 = (TMP[4 * qb + i] for i in range(4))
-            out.append(mk("v_add_f32", t0, t0, t1, tag="valu"))      # ta = row 0
-            out.append(mk("v_add_f32", t1, t2_, t3, tag="valu"))     # tb = row 1
         out.append(mk("v_add_f32", LA[qb], LA[qb], ta, tag="valu"))
         out.append(mk("v_add_f32", LB[qb], LB[qb], tb, tag="valu"))
         out.append(mk("v_add_f32", ts, ta, tb, tag="valu"))
@@ -810,7 +800,7 @@ class Gen16(base.Gen):
             g0 = self.npv + 16 * (ks - 2) + 15
             for kg in range(4):
                 it = kr[4 * ks + kg]
-                load[g0] += base._weight(it)
+                load[g0] += sched.weight(it)
                 slots[g0].append((g0 + 0.5 + 0.1 * kg, 3, it))
 
     def rare_rescale(self, lab):
@@ -890,8 +880,6 @@ class Gen16(base.Gen):
         p = self.p
         g = self.g
         bf16_ = self.bf16
-        tr = int(self.cfg["trace"][0])
-        assert not tr, "the trace builds belong to the 32x32 generator"
         # ---- entry: addresses, the wave's Q through its LDS image, the first tiles
         p.emit("s_waitcnt", vmcnt=0, lgkmcnt=0)
         nks, ndg = self.NKS16, self.NDG
@@ -1198,32 +1186,19 @@ class Gen16(base.Gen):
         return p
 
 
-def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
-    ap.add_argument("--opt", default="", help="schedule tunables / options (fwd_d128_gen.parse_opts)")
-    ap.add_argument("--probe", action="store_true")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    cfg = base.parse_opts(a.opt)
-    if base.is_probe(cfg) and not a.probe:
-        sys.exit("fwd_m16_gen.py: %r contains timing-probe options; they need --probe" % a.opt)
+def variants(cfg):
     # per head dim and dtype: the f32-scale body with the sum check (calls flagged FA2_FLAG_EXACT_SCALE: the LSE a backward pass will consume adds the
     # f32 P), the f32-scale body with the row sums on the matrix pipe ("_lm"), the folded body (row sums on the matrix pipe; opt=nolm: with the sum check)
     # ... and, at head dim 128, the folded body with the sum check and its in-place repair ("_fold_nolm": option "asm" bit 9 clear — fp16 data whose
     # rows outgrow the reference of their first tiles by 16 octaves and more costs the lm bodies a second sweep per item, tools/growth_cliff.py)
-    for hd, bf16, kind in ((hd, bf16, kind) for hd in (128, 64) for bf16 in (False, True) for kind in ("", "_lm", "_fold", "_fold_nolm")):
-        if kind == "_fold_nolm" and hd == 64:
-            continue
-        c = dict(cfg)
-        c["opt"] = tuple(o for o in cfg.get("opt", ()) if o not in ("ct", "lm", "nolm")) + (("ct",) if kind.startswith("_fold") else ())
-        if kind == "_lm" or (kind == "_fold" and "nolm" not in cfg.get("opt", ())):
-            c["opt"] += ("lm",)
-        prog = Gen16(bf16, hd=hd, **c).build()
-        path = os.path.join(a.out, "fa2_fwd_m16_%s%s%s.inc" % ("d64_" if hd == 64 else "", "bf16" if bf16 else "f16", kind))
-        base.write_atomic(path, "// GENERATED by csrc/gen/fwd_m16_gen.py %s — do not edit.  %d instructions.\n" % (a.opt, len(prog.ins)) + base.render_inline(prog))
-        print(path, len(prog.ins), "instructions")
+    fold_lm = () if "nolm" in cfg.get("opt", ()) else ("lm",)
+    kinds = {"": (), "_lm": ("lm",), "_fold": ("ct",) + fold_lm, "_fold_nolm": ("ct",)}
+    return [("fa2_fwd_m16_%s%s%s.inc" % ("d64_" if hd == 64 else "", "bf16" if bf16 else "f16", kind), Gen16, {"bf16": bf16, "hd": hd}, add)
+            for hd in (128, 64) for bf16 in (False, True) for kind, add in kinds.items() if not (kind == "_fold_nolm" and hd == 64)]
+
+
+def main():
+    gen_driver.run("fwd_m16_gen.py", variants, managed=("ct", "lm", "nolm"))
 
 
 if __name__ == "__main__":

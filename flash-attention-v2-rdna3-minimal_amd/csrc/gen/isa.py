@@ -10,7 +10,8 @@ Operand objects
     Sym(name)                 'vcc', 'exec', 'm0', 'scc', 'off'
     Arg(n)                    compiler-assigned inline-asm operand %n (only in the entry/exit moves)
     int / float               immediates (floats are rendered as hex literals)
-    Label(name)               branch target
+    Label(name)               branch target; rendered bare, or through the `label` format string the renderer is given
+                              (the inline-asm statements need names that are unique per statement: gen_driver.render_inline)
 """
 import struct
 
@@ -98,8 +99,8 @@ class Label:
     def __init__(self, name):
         self.name = name
 
-    def text(self):
-        return self.name
+    def text(self, label="%s"):
+        return label % self.name
 
 
 def f32_bits(x):
@@ -127,14 +128,14 @@ class Ins:
     def __init__(self, op, ops=(), mods=None, tag=None, comment=None):
         self.op, self.ops, self.mods, self.tag, self.comment = op, tuple(ops), dict(mods or {}), tag, comment
 
-    def text(self):
+    def text(self, label="%s"):
         if self.op == "label":
-            return "%s:" % self.ops[0].text()
+            return "%s:" % self.ops[0].text(label)
         if self.op == "raw":
             return self.ops[0]
         parts = []
         for o in self.ops:
-            parts.append(o.text() if hasattr(o, "text") else _imm_text(o))
+            parts.append(o.text(label) if isinstance(o, Label) else o.text() if hasattr(o, "text") else _imm_text(o))
         s = self.op
         if self.op == "s_waitcnt":
             s += " " + " ".join("%s(%d)" % (k, v) for k, v in self.mods.items())
@@ -172,10 +173,11 @@ class Program:
         self._uniq += 1
         return "%s_%d" % (stem, self._uniq)
 
-    def text_lines(self):
+    def text_lines(self, label="%s"):
+        """one line per instruction; `label`: format string every label name goes through (default: the bare name)"""
         out = []
         for i in self.ins:
-            t = i.text()
+            t = i.text(label)
             if i.comment:
                 t += "   ; " + i.comment
             out.append(t)

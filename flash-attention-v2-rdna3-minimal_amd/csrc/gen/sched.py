@@ -17,10 +17,6 @@ def weight(item):
     return 0.0 if item.op == "label" else WEIGHT.get(item.tag, 1.0)
 
 
-def set_weights(trans, lds, dma, salu):
-    WEIGHT.update({"trans": trans, "lds": lds, "dma": dma, "salu": salu, "branch": salu})
-
-
 def place(load, slots, items, a, b, sid):
     """Put the ordered `items` of one stream into the MFMA gaps [a, b), filling the least loaded gaps first
     (water-filling on the weighted load) while keeping the stream's order."""

@@ -52,6 +52,11 @@ CFGS = {
 }
 
 
+# flag of a variant spec -> the generator (csrc/gen/) whose --opt it carries; the 16x16x32 backward passes are timed by tools/bwd_bench.py --libs
+GEN_FLAGS = {"gen=": "fwd_d128_gen.py", "bgen=": "bwd_d128_gen.py", "m16gen=": "fwd_m16_gen.py", "d256gen=": "fwd_m16_d256_gen.py",
+             "dq16gen=": "bwd_dq_m16_gen.py", "dkv16gen=": "bwd_dkv_m16_gen.py"}
+
+
 def build(specs):
     """NAME[:flag,flag,...]: flags are -D... compiler flags, gen=<options of csrc/gen/fwd_d128_gen.py> and bgen=<options of
     bwd_d128_gen.py> (';' between options, e.g. gen=e=10:64;abl=exp+dma).  Generator options go through --probe into a private
@@ -65,25 +70,13 @@ def build(specs):
     for s in specs:
         name, _, flags = s.partition(":")
         fl = [f for f in flags.split(",") if f]
-        extra = [f for f in fl if not f.startswith(("gen=", "bgen=", "m16gen=", "d256gen=", "dq16gen=", "dkv16gen=", "only=", "opts="))]
+        extra = [f for f in fl if not f.startswith(tuple(GEN_FLAGS) + ("only=", "opts="))]
         only = None if extra else ["fwd_asm", "bwd_asm"]          # generator-only variants: recompile just the units that include the bodies
         for f in fl:
             if f.startswith("only="):                            # only=fwd_asm+host: -D flags that matter to these units alone
                 only = f[5:].split("+")
-        opts = {}
-        for f in fl:
-            if f.startswith("gen="):
-                opts["fwd_d128_gen.py"] = f[4:].replace(";", ",")
-            if f.startswith("bgen="):
-                opts["bwd_d128_gen.py"] = f[5:].replace(";", ",")
-            if f.startswith("m16gen="):      # options of csrc/gen/fwd_m16_gen.py (the 16x16x32 body)
-                opts["fwd_m16_gen.py"] = f[7:].replace(";", ",")
-            if f.startswith("d256gen="):     # options of csrc/gen/fwd_m16_d256_gen.py (the head-dim-256 body)
-                opts["fwd_m16_d256_gen.py"] = f[8:].replace(";", ",")
-            if f.startswith("dq16gen="):     # ... of the 16x16x32 backward passes (csrc/gen/bwd_dq_m16_gen.py, bwd_dkv_m16_gen.py; timed by tools/bwd_bench.py --libs)
-                opts["bwd_dq_m16_gen.py"] = f[8:].replace(";", ",")
-            if f.startswith("dkv16gen="):
-                opts["bwd_dkv_m16_gen.py"] = f[9:].replace(";", ",")
+        # (an option a generator does not know — a mistyped window, a probe that has been removed — fails the generator run below)
+        opts = {gen: f[len(flag):].replace(";", ",") for f in fl for flag, gen in GEN_FLAGS.items() if f.startswith(flag)}
         gdir = os.path.join(VAR_DIR, name + "_gen")
         os.makedirs(gdir, exist_ok=True)
         b.generate(gdir, opts, probe=True)
