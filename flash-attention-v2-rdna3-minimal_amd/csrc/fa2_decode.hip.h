@@ -1,0 +1,373 @@
+// fa2_decode.hip.h — KV-cache decode attention (fa2_fwd_decode; include/fa2_gfx950.h has the contract, DESIGN.md section 20 the reasons).
+//
+// A few new query tokens per sequence against a preallocated cache whose valid length lives on the device.  One workgroup serves one item
+// (sequence b, K / V head hkv, part s): the Nq * G query rows of the group (G = H / Hkv) are the M rows of v_mfma_f32_16x16x32, in RT row tiles of
+// 16, so K and V are fetched once per group and not once per query head.  The part sweeps the key tiles decode_part_range gives it (the ONE place
+// that decides it, host and device); its four waves take those tiles in turn, each with a private online-softmax state, and are merged through LDS
+// at the end.
+//
+//   S^T[key, row] = K[key, :] . Q[row, :]      A = K fragment, loaded from global memory STRAIGHT into VGPRs (16 bytes per lane: the lane's key, 8 of
+//                                              its columns — the operand map itself), B = Q fragment (registers for the whole sweep)
+//   O^T[d, row]  += V^T[d, key] . P^T[key, row] A = V^T fragment, B = P: the S^T accumulator of a lane holds 4 keys of ONE row in each 16-key block,
+//                                              so the two blocks of a 32-key tile, rounded to the I/O dtype, ARE the B fragment (k slot j of lane
+//                                              group g = key 16 (j >> 2) + 4 g + (j & 3)); no lane movement for P.
+// K is used once per workgroup, so it never visits LDS.  V needs its keys along the MFMA k dimension, which a row-major 16-byte load cannot give: a
+// wave writes its V tile to a PRIVATE LDS slab as it came from memory (coalesced 256-byte rows) and reads it back with ds_read_b64_tr_b16 in exactly
+// the k order P has.  The slab is private to the wave, so the sweep has no workgroup barrier; the tiles of the next step are loaded into registers
+// before the current one is computed on.
+//
+// Safety (the lengths and the block table are device data nobody validated): len is clamped into [0, capacity_keys], every page id into
+// [0, num_pages), every key index a lane forms into [0, len - 1] before it becomes an address.  Keys at or beyond len contribute nothing whatever
+// the cache holds there: their scores are replaced by -inf (a select on the position, not arithmetic on the score) and their V rows by zero bits
+// before they reach LDS, since 0 * NaN is NaN.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#include "fa2_fwd_kernel.hip.h"      // the vector types, pack2
+#define FA2_DEC_HD __host__ __device__
+#else
+#define FA2_DEC_HD
+#endif
+
+namespace fa2 {
+
+constexpr int kDecodeTile = 32;        // keys per tile: divides 64, so a tile never straddles a page (page sizes are multiples of 64)
+constexpr int kDecodeMaxSplit = 16;    // parts per item
+constexpr int kDecodeMaxRows = 64;     // Nq * G query rows per K / V head: four row tiles of 16
+constexpr int kDecodeWaves = 4;
+
+FA2_DEC_HD inline int decode_clamp_len(int64_t len, int64_t capacity_keys) {
+    return (int)(len < 0 ? 0 : len > capacity_keys ? capacity_keys : len);
+}
+
+// The key tiles part `part` of `nsplit` sweeps for a sequence of `len` keys: [*first, *first + *n).  tiles = ceil(len / tile), per = ceil(tiles / nsplit),
+// part s takes [s * per, min((s + 1) * per, tiles)).  len is clamped into [0, capacity_keys] HERE.  (Nq does not shorten the sweep: the last query row
+// sits at position len - 1 and sees every valid key.)
+FA2_DEC_HD inline void decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, int nsplit, int part, int* first, int* n) {
+    (void)Nq;
+    const int l = decode_clamp_len(len, capacity_keys);
+    const int tiles = (int)(((int64_t)l + tile - 1) / tile);
+    const int per = (tiles + nsplit - 1) / nsplit;
+    const int64_t lo = (int64_t)part * per, hi = lo + per < tiles ? lo + per : tiles;
+    *first = lo < hi ? (int)lo : 0;
+    *n = lo < hi ? (int)(hi - lo) : 0;
+}
+
+struct DecodeParams {
+    const void *q, *k, *v;
+    void* o;
+    float* lse;
+    const int* lens;            // cache_seqlens [B], device
+    const int* bt;              // block_table (paged) or null
+    float* ws;                  // nsplit > 1: [item][part][row][HD] normalised f32 partial rows, then [item][part][row] log2 LSEs
+    int B, H, Hkv, Nq, G, rows; // rows = Nq * G live query rows per K / V head
+    int page_size, num_pages;   // page_size 0 = contiguous cache
+    int nsplit;
+    int64_t capacity_keys;      // Nmax, or max_pages * page_size
+    int64_t qs[3], ks[3], vs[3], os[3], ls[2], bts;      // element strides {batch | page, head, row}; lse {batch, head}; block-table row stride
+    float c;                    // scale * log2(e)
+};
+
+// workspace bytes of a split call (live rows only)
+FA2_DEC_HD inline int64_t decode_ws_bytes(int64_t items, int nsplit, int rows, int HD) { return nsplit > 1 ? items * nsplit * rows * (HD + 1) * 4 : 0; }
+
+#if defined(__HIPCC__)
+
+template <bool BF16>
+__device__ __forceinline__ f32x4 decode_mfma(u32x4 a, u32x4 b, f32x4 c) {
+    if constexpr (BF16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+// max / sum over the four 16-lane groups of a wave (the lanes that hold the same query row)
+__device__ __forceinline__ float decode_group_max(float x) {
+    x = __builtin_fmaxf(x, __shfl_xor(x, 16, 64));
+    return __builtin_fmaxf(x, __shfl_xor(x, 32, 64));
+}
+__device__ __forceinline__ float decode_group_sum(float x) {
+    x += __shfl_xor(x, 16, 64);
+    return x + __shfl_xor(x, 32, 64);
+}
+
+// memory operations of the wave's lanes on its private LDS slab stay on their side of this point (no instruction: a wave's DS operations run in order)
+__device__ __forceinline__ void decode_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int HD, bool BF16, int RT>
+__global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeParams p) {
+    constexpr int NW = kDecodeWaves, T = kDecodeTile, DC = HD / 32, DB = HD / 16, VL = T * HD * 2 / 16 / 64, GR = HD / 8;
+    constexpr int VROWB = HD * 2 + 16;                 // bytes of a V row in the slab
+    constexpr int SLAB = T * VROWB;                    // one wave's slab: its V tile, later its f32 accumulator tile [16 rows][HD + 4]
+    constexpr int XROW = HD + 4;
+    static_assert(16 * XROW * 4 <= SLAB, "the accumulator exchange reuses the V slab");
+    static_assert(VL * 64 * 16 == T * HD * 2 && T == 32, "tile geometry");
+    __shared__ __attribute__((aligned(16))) char lds[NW * SLAB + 2 * NW * kDecodeMaxRows * 4];
+    float* const sm = reinterpret_cast<float*>(lds + NW * SLAB);          // [NW][64] running maxima, then [NW][64] row sums
+    float* const sl = sm + NW * kDecodeMaxRows;
+    const float ninf = -__builtin_inff();
+
+    const int part = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, qi = lane & 15;
+    const int len = decode_clamp_len(p.lens[b], p.capacity_keys);
+    int first, nt;
+    decode_part_range(len, p.capacity_keys, p.Nq, T, p.nsplit, part, &first, &nt);
+    const int64_t item = (int64_t)b * p.Hkv + hkv;
+    float* const ws_o = p.ws + ((item * p.nsplit + part) * p.rows) * HD;
+    float* const ws_l = p.ws + (int64_t)p.B * p.Hkv * p.nsplit * p.rows * HD + (item * p.nsplit + part) * p.rows;
+
+    if (p.nsplit > 1 && nt == 0) {                     // an empty part: lse = -inf, no O (the combine never reads a part of weight 0)
+        if (tid < p.rows) ws_l[tid] = ninf;
+        return;
+    }
+
+    // the lane's query row in each row tile: packed row r = i * G + gq -> query i, head hkv * G + gq, at key position len - Nq + i
+    const uint16_t* const qbase = static_cast<const uint16_t*>(p.q) + b * p.qs[0];
+    u32x4 qf[RT][DC];
+    int pos[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int r = rt * 16 + qi;
+        const bool live = r < p.rows;
+        const int i = live ? r / p.G : 0, h = hkv * p.G + (live ? r % p.G : 0);
+        pos[rt] = live ? len - p.Nq + i : -1;
+        const uint16_t* row = qbase + h * p.qs[1] + i * p.qs[2] + 8 * g;
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) qf[rt][dc] = live ? *reinterpret_cast<const u32x4*>(row + dc * 32) : (u32x4){0u, 0u, 0u, 0u};
+    }
+
+    // one tile into registers: K as MFMA A fragments [16-key block][32-column chunk], V as it lies in memory (chunk c = i * 64 + lane of the tile's
+    // T * HD / 8 16-byte chunks; rows at or beyond len as zero bits)
+    auto load_tile = [&](int t, u32x4 (&kf)[2][DC], u32x4 (&vr)[VL]) {
+        const int key0 = t * T;
+        int64_t kofs, vofs;
+        int row0 = key0;
+        if (p.page_size) {
+            const int pg = key0 / p.page_size;
+            int pid = p.bt[b * p.bts + pg];
+            pid = pid < 0 ? 0 : pid >= p.num_pages ? p.num_pages - 1 : pid;
+            row0 = key0 - pg * p.page_size;
+            kofs = pid * p.ks[0] + hkv * p.ks[1];
+            vofs = pid * p.vs[0] + hkv * p.vs[1];
+        } else {
+            kofs = b * p.ks[0] + hkv * p.ks[1];
+            vofs = b * p.vs[0] + hkv * p.vs[1];
+        }
+        const int last = len - 1 - key0;               // >= 0: the tile holds a valid key; a lane's key index is clamped to it
+        const uint16_t* const kb = static_cast<const uint16_t*>(p.k) + kofs + 8 * g;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const int kk = blk * 16 + qi;
+            const uint16_t* row = kb + (int64_t)(row0 + (kk < last ? kk : last)) * p.ks[2];
+#pragma unroll
+            for (int dc = 0; dc < DC; ++dc) kf[blk][dc] = *reinterpret_cast<const u32x4*>(row + dc * 32);
+        }
+        const uint16_t* const vb = static_cast<const uint16_t*>(p.v) + vofs;
+#pragma unroll
+        for (int i = 0; i < VL; ++i) {
+            const int ch = i * 64 + lane, kk = ch / GR, col = ch % GR;
+            const u32x4 x = *reinterpret_cast<const u32x4*>(vb + (int64_t)(row0 + (kk < last ? kk : last)) * p.vs[2] + col * 8);
+            vr[i] = kk <= last ? x : (u32x4){0u, 0u, 0u, 0u};
+        }
+    };
+
+    float m[RT], l[RT];
+    f32x4 acc[RT][DB];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        m[rt] = ninf;
+        l[rt] = 0.f;
+#pragma unroll
+        for (int db = 0; db < DB; ++db) acc[rt][db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+
+    char* const slab = lds + w * SLAB;
+    char* const tr_addr = slab + (4 * g + (qi >> 2)) * VROWB + 8 * (qi & 3);      // ds_read_b64_tr_b16: lane 4 q + p of a group supplies row q, columns 4 p ..
+
+    const int tend = first + nt;
+    int t = first + w;
+    u32x4 kf[2][DC], vr[VL];
+    if (t < tend) load_tile(t, kf, vr);
+    while (t < tend) {
+        const int tn = t + NW;
+        u32x4 kfn[2][DC] = {}, vrn[VL] = {};
+        if (tn < tend) load_tile(tn, kfn, vrn);        // the next step's tiles are in flight while this one is computed on
+
+        // S^T = K Q^T, one 16 x 16 block per (row tile, 16-key block)
+        f32x4 s[RT][2];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk) {
+                s[rt][blk] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int dc = 0; dc < DC; ++dc) s[rt][blk] = decode_mfma<BF16>(kf[blk][dc], qf[rt][dc], s[rt][blk]);
+            }
+
+        // V tile -> the wave's slab, rows as they lie in memory
+        decode_wave_sync();                            // (the previous step's transposed reads come first)
+#pragma unroll
+        for (int i = 0; i < VL; ++i) {
+            const int ch = i * 64 + lane;
+            *reinterpret_cast<u32x4*>(slab + (ch / GR) * VROWB + (ch % GR) * 16) = vr[i];
+        }
+        decode_wave_sync();
+
+        // online softmax: scores scaled in f32, f32 maxima and row sums, P rounded to the I/O dtype for P . V
+        const int key0 = t * T;
+        u32x4 pf[RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            float x[8];
+            float mt = ninf;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int key = key0 + 16 * (j >> 2) + 4 * g + (j & 3);
+                x[j] = key <= pos[rt] ? s[rt][j >> 2][j & 3] * p.c : ninf;
+                mt = __builtin_fmaxf(mt, x[j]);
+            }
+            mt = decode_group_max(mt);
+            const float mn = __builtin_fmaxf(m[rt], mt), mu = mn == ninf ? 0.f : mn;
+            const float alpha = __builtin_amdgcn_exp2f(m[rt] - mu);
+            float sum = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                x[j] = __builtin_amdgcn_exp2f(x[j] - mu);
+                sum += x[j];
+            }
+            l[rt] = l[rt] * alpha + decode_group_sum(sum);
+            m[rt] = mn;
+            pf[rt] = (u32x4){pack2<BF16>(x[0], x[1]), pack2<BF16>(x[2], x[3]), pack2<BF16>(x[4], x[5]), pack2<BF16>(x[6], x[7])};
+#pragma unroll
+            for (int db = 0; db < DB; ++db) acc[rt][db] *= alpha;
+        }
+
+        // O^T += V^T P^T: the transposed reads deliver keys 4 g .. 4 g + 3 and the same 16 rows further down — P's k order
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+            const u32x2 lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tr_addr + db * 32)));
+            const u32x2 hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tr_addr + db * 32 + 16 * VROWB)));
+            const u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) acc[rt][db] = decode_mfma<BF16>(vf, pf[rt], acc[rt][db]);
+        }
+
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int dc = 0; dc < DC; ++dc) kf[blk][dc] = kfn[blk][dc];
+#pragma unroll
+        for (int i = 0; i < VL; ++i) vr[i] = vrn[i];
+        t = tn;
+    }
+
+    // merge the four waves' states: maxima and sums first, then one row tile of accumulators at a time through the slabs
+    if (g == 0) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            sm[w * kDecodeMaxRows + rt * 16 + qi] = m[rt];
+            sl[w * kDecodeMaxRows + rt * 16 + qi] = l[rt];
+        }
+    }
+    const int orow = tid / GR, ogr = tid % GR;          // the thread's (row of the tile, 8-column granule) in the output step
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        decode_wave_sync();
+        float* const xs = reinterpret_cast<float*>(slab) + qi * XROW + 4 * g;
+#pragma unroll
+        for (int db = 0; db < DB; ++db) *reinterpret_cast<f32x4*>(xs + db * 16) = acc[rt][db];      // acc[db][e] = O^T[d = 16 db + 4 g + e][row qi]
+        __syncthreads();
+        const int r = rt * 16 + orow;
+        if (orow < 16 && r < p.rows) {
+            float f[NW];
+            float M = ninf, L = 0.f;
+#pragma unroll
+            for (int k = 0; k < NW; ++k) M = __builtin_fmaxf(M, sm[k * kDecodeMaxRows + r]);
+            const float mu = M == ninf ? 0.f : M;
+#pragma unroll
+            for (int k = 0; k < NW; ++k) {
+                f[k] = __builtin_amdgcn_exp2f(sm[k * kDecodeMaxRows + r] - mu);
+                L = __builtin_fmaf(f[k], sl[k * kDecodeMaxRows + r], L);
+            }
+            float out[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < NW; ++k) {
+                const float* src = reinterpret_cast<const float*>(lds + k * SLAB) + orow * XROW + ogr * 8;
+                const f32x4 a = *reinterpret_cast<const f32x4*>(src), c = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    out[e] = __builtin_fmaf(f[k], a[e], out[e]);
+                    out[4 + e] = __builtin_fmaf(f[k], c[e], out[4 + e]);
+                }
+            }
+            const float inv = L > 0.f ? 1.0f / L : 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) out[e] *= inv;
+            const float lse2 = L > 0.f ? M + __builtin_amdgcn_logf(L) : ninf;
+            if (p.nsplit > 1) {
+                float* dst = ws_o + (int64_t)r * HD + ogr * 8;
+                *reinterpret_cast<f32x4*>(dst) = (f32x4){out[0], out[1], out[2], out[3]};
+                *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){out[4], out[5], out[6], out[7]};
+                if (ogr == 0) ws_l[r] = lse2;
+            } else {
+                const int i = r / p.G, h = hkv * p.G + r % p.G;
+                uint16_t* dst = static_cast<uint16_t*>(p.o) + b * p.os[0] + h * p.os[1] + i * p.os[2] + ogr * 8;
+                *reinterpret_cast<u32x4*>(dst) = (u32x4){pack2<BF16>(out[0], out[1]), pack2<BF16>(out[2], out[3]), pack2<BF16>(out[4], out[5]),
+                                                         pack2<BF16>(out[6], out[7])};
+                if (ogr == 0) p.lse[b * p.ls[0] + h * p.ls[1] + i] = lse2;
+            }
+        }
+        __syncthreads();                               // the slabs are rewritten for the next row tile
+    }
+}
+
+// merge of the parts a split launch left in p.ws: one thread per (item, live row, 8-column granule); weights 2^(lse_s - max), parts of weight 0 are
+// never read (an empty part wrote no O), one rounding.  Every part empty: zeros and -inf.
+template <int HD, bool BF16>
+__global__ __launch_bounds__(256) void decode_combine_kernel(const DecodeParams p) {
+    constexpr int GR = HD / 8;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, total = (int64_t)p.B * p.Hkv * p.rows * GR;
+    if (idx >= total) return;
+    const int gr = (int)(idx % GR), r = (int)((idx / GR) % p.rows);
+    const int64_t item = idx / GR / p.rows;
+    const int b = (int)(item / p.Hkv), hkv = (int)(item % p.Hkv);
+    const float ninf = -__builtin_inff();
+    const float* const ws_l = p.ws + (int64_t)p.B * p.Hkv * p.nsplit * p.rows * HD + item * p.nsplit * p.rows + r;
+    const float* const ws_o = p.ws + (item * p.nsplit * p.rows + r) * HD + gr * 8;
+    float M = ninf;
+    for (int s = 0; s < p.nsplit; ++s) M = __builtin_fmaxf(M, ws_l[(int64_t)s * p.rows]);
+    float out[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float L = 0.f;
+    if (M != ninf) {
+        for (int s = 0; s < p.nsplit; ++s) {
+            const float f = __builtin_amdgcn_exp2f(ws_l[(int64_t)s * p.rows] - M);
+            if (f != 0.f) {
+                const float* src = ws_o + (int64_t)s * p.rows * HD;
+                const f32x4 a = *reinterpret_cast<const f32x4*>(src), c = *reinterpret_cast<const f32x4*>(src + 4);
+                L += f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    out[e] = __builtin_fmaf(f, a[e], out[e]);
+                    out[4 + e] = __builtin_fmaf(f, c[e], out[4 + e]);
+                }
+            }
+        }
+        const float inv = 1.0f / L;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e] *= inv;
+    }
+    const int i = r / p.G, h = hkv * p.G + r % p.G;
+    uint16_t* dst = static_cast<uint16_t*>(p.o) + b * p.os[0] + h * p.os[1] + i * p.os[2] + gr * 8;
+    *reinterpret_cast<u32x4*>(dst) = (u32x4){pack2<BF16>(out[0], out[1]), pack2<BF16>(out[2], out[3]), pack2<BF16>(out[4], out[5]), pack2<BF16>(out[6], out[7])};
+    if (gr == 0) p.lse[b * p.ls[0] + h * p.ls[1] + i] = M != ninf ? M + __builtin_amdgcn_logf(L) : ninf;
+}
+
+#endif  // __HIPCC__
+
+}  // namespace fa2

@@ -13,6 +13,7 @@
 
 #include "fa2_scoremod.h"
 #include "fa2_bwd_kernel.hip.h"      // FwdParams / BwdParams (templates are only instantiated where a launcher names them)
+#include "fa2_decode.hip.h"          // DecodeParams, decode_part_range
 
 #define FA2_HIDDEN __attribute__((visibility("hidden")))
 
@@ -253,6 +254,10 @@ struct MergeParams {
 };
 FA2_HIDDEN int launch_merge_fwd(bool bf16, MergeParams& p, hipStream_t stream);
 FA2_HIDDEN int launch_merge_bwd(bool bf16, MergeParams& p, hipStream_t stream);
+
+// KV-cache decode attention (decode_hip.cpp; fa2_fwd_decode): the kernel of csrc/fa2_decode.hip.h with `row_tiles` (1, 2 or 4) row tiles of 16 query rows per
+// K / V head on a grid of (p.nsplit, Hkv, B) workgroups, then — p.nsplit > 1 — the combine of the parts left in p.ws
+FA2_LAUNCHER(launch_decode, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
 
 constexpr int kBwdAsmParts = 3;      // passes the hand-scheduled backward covers: bit 0 = dQ, bit 1 = dK / dV
 

@@ -1477,6 +1477,100 @@ int fa2_merge_bwd(int dtype, int nparts, const void* const* o_parts, const float
     return fa2::launch_merge_bwd(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
 }
 
+// ---- KV-cache decode attention: include/fa2_gfx950.h has the contract, csrc/fa2_decode.hip.h the kernel, decode_hip.cpp its launches
+// The sizes of a decode call, in the documented order (shape, then head dim); *row_tiles: the row tiles the kernel runs (1, 2 or 4).
+static int decode_check_shape(int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int* row_tiles) {
+    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || D < 1 || capacity < 1 || Hkv > H || H % Hkv != 0) return FA2_ERR_BAD_SHAPE;
+    const int64_t rows = (int64_t)Nq * (H / Hkv);
+    if (rows > fa2::kDecodeMaxRows || page_size < 0 || page_size % 64 != 0 || num_splits < 0 || num_splits > fa2::kDecodeMaxSplit) return FA2_ERR_BAD_SHAPE;
+    if (page_size > 0 && (int64_t)capacity * page_size > 0x7fffffffLL - 64) return FA2_ERR_BAD_SHAPE;      // key positions are ints
+    if (D != 64 && D != 128) return FA2_ERR_HEAD_DIM;
+    const int rt = (int)((rows + 15) / 16);
+    *row_tiles = rt == 3 ? 4 : rt;
+    return FA2_OK;
+}
+
+// The split: a pure function of the shape, the capacity and the CU count (the lengths live on the device).  One workgroup per (sequence, K / V head,
+// part) streams its share of K and V once; B * Hkv * row_tiles >= CUs: the chip is covered, no split.  Otherwise two workgroups per CU's worth of
+// parts (a workgroup is 4 waves and 36 KiB of LDS: two fit), at most 16, and no part shorter than 8 key tiles of the capacity (two per wave).
+static int decode_split(int B, int Hkv, int row_tiles, int capacity_tiles, int num_splits) {
+    if (num_splits > 0) return num_splits;
+    const int64_t work = (int64_t)B * Hkv * row_tiles, cus = fa2::device_cus();
+    if (work >= cus) return 1;
+    int64_t S = 2 * cus / work;
+    if (S > fa2::kDecodeMaxSplit) S = fa2::kDecodeMaxSplit;
+    if (S > capacity_tiles / 8) S = capacity_tiles / 8;
+    return S < 1 ? 1 : (int)S;
+}
+
+static int decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
+    int row_tiles = 0;
+    if (int rc = decode_check_shape(B, H, Hkv, Nq, D, capacity, page_size, num_splits, &row_tiles)) return rc;
+    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    const int64_t capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
+    plan->kernel = FA2_KERNEL_HIP_DECODE;
+    plan->row_tiles = row_tiles;
+    plan->key_tile = fa2::kDecodeTile;
+    plan->nsplit = decode_split(B, Hkv, row_tiles, (int)((capacity_keys + fa2::kDecodeTile - 1) / fa2::kDecodeTile), num_splits);
+    return FA2_OK;
+}
+
+int fa2_fwd_decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    std::memset(plan, 0, sizeof(*plan));
+    return decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, plan);
+}
+
+size_t fa2_fwd_decode_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits) {
+    fa2_decode_plan_t plan;
+    if (decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, &plan)) return 0;
+    return (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, Nq * (H / Hkv), D);
+}
+
+int fa2_decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, int nsplit, int part, int* first_tile, int* ntiles) {
+    if (!first_tile || !ntiles) return FA2_ERR_NULL_POINTER;
+    if (capacity_keys < 0 || capacity_keys > 0x7fffffffLL || Nq < 1 || tile < 1 || nsplit < 1 || nsplit > fa2::kDecodeMaxSplit || part < 0 || part >= nsplit)
+        return FA2_ERR_BAD_SHAPE;
+    fa2::decode_part_range(len, capacity_keys, Nq, tile, nsplit, part, first_tile, ntiles);
+    return FA2_OK;
+}
+
+int fa2_fwd_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table,
+                   int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3], const int64_t k_strides[3],
+                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale,
+                   int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (any_null({q, k_cache, v_cache, o, lse, cache_seqlens, q_strides, k_strides, v_strides, o_strides, lse_strides}) || (page_size > 0 && !block_table))
+        return FA2_ERR_NULL_POINTER;
+    int row_tiles = 0;
+    if (int rc = decode_check_shape(B, H, Hkv, Nq, D, capacity, page_size, num_splits, &row_tiles)) return rc;
+    if ((page_size > 0 && num_pages < 1) || lse_strides[0] < 0 || lse_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
+    if (!all_aligned16({q, k_cache, v_cache, o}) ||
+        ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(block_table)) & 3u) ||
+        !strides3_ok(q_strides) || !strides3_ok(k_strides) || !strides3_ok(v_strides) || !strides3_ok(o_strides) || block_table_stride < 0)
+        return FA2_ERR_ALIGNMENT;
+    fa2_decode_plan_t plan;
+    if (int rc = decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, &plan)) return rc;       // (the dtype: after the alignment)
+    if (!std::isfinite(scale)) return FA2_ERR_SCALE;
+    if (B > 65535 || Hkv > 65535) return FA2_ERR_GRID;
+    fa2::DecodeParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = q; p.k = k_cache; p.v = v_cache; p.o = o; p.lse = lse; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr;
+    p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.G = H / Hkv; p.rows = Nq * p.G;
+    p.page_size = page_size; p.num_pages = num_pages; p.nsplit = plan.nsplit;
+    p.capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
+    for (int i = 0; i < 3; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; p.os[i] = o_strides[i]; }
+    p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
+    p.bts = block_table_stride;
+    p.c = scale * 1.4426950408889634f;
+    if (plan.nsplit > 1) {
+        if (!workspace) return FA2_ERR_NULL_POINTER;
+        if (!aligned16(workspace)) return FA2_ERR_ALIGNMENT;
+        if (workspace_bytes < (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, p.rows, D)) return FA2_ERR_BAD_SHAPE;
+        p.ws = static_cast<float*>(workspace);
+    }
+    return fa2::launch_decode(dtype == FA2_DTYPE_BF16, D, p, plan.row_tiles, (hipStream_t)hip_stream);
+}
+
 int fa2_fwd_f16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_F16, FA2_FWD_PASS, hip_stream); }
 int fa2_fwd_bf16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_BF16, FA2_FWD_PASS, hip_stream); }
 int fa2_bwd_f16(FA2_BWD_ARGS(), void* hip_stream) { return fa2_bwd(FA2_DTYPE_F16, FA2_BWD_PASS, hip_stream); }

@@ -1087,6 +1087,103 @@ def merge_attention(outs, lses, BNHD_fmt=False):
     return _MergeFunction.apply(BNHD_fmt, len(outs), *outs, *lses)
 
 
+_DECODE_MAX_ROWS = 64       # Nq * (H / Hkv) query rows per K / V head (four MFMA row tiles)
+_DECODE_MAX_SPLITS = 16
+_DECODE_ROUTE = "flash_attention_varlen(..., causal=True, bottom_right=True) on packed tensors serves such calls"
+
+
+def _decode_strides_ok(t):
+    s0, s1, s2, s3 = t.stride()
+    return s3 == 1 and not ((s0 | s1 | s2) & 7) and s1 > 0 and not (t.data_ptr() & 15)
+
+
+def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None, scale=None, return_lse=False, num_splits=0):
+    """KV-cache decode attention (the flash_attn_with_kvcache shape): a few new query tokens per sequence against a preallocated cache.
+    q [B, Nq, H, D] fp16 / bf16.  Contiguous cache: k_cache / v_cache [B, Nmax, Hkv, D].  Paged cache: k_cache / v_cache [num_pages, page_size, Hkv, D]
+    with block_table int32 [B, max_pages] on q's device, page_size a multiple of 64.  Strided views are fine (D contiguous, strides multiples of 8
+    elements); a q that is not is copied, a cache that is not raises — copying the cache is what this call exists to avoid.
+    cache_seqlens: int32 [B] on q's device, the valid keys of each sequence INCLUDING the Nq new tokens (the caller has written their K / V).  The host
+    never reads it or the block table: no synchronisation, the call can be captured in a graph, and replaying the graph after either tensor changed in
+    place gives the result for the new contents.
+    Masking is bottom-right causal per sequence: query row i of sequence b sits at position len_b - Nq + i and sees the keys j <= that position (Nq = 1:
+    every valid key).  Rows at a negative position return zeros (lse -inf).  Keys at or beyond len_b and unused pages contribute nothing whatever
+    they hold; lengths and page ids are clamped into the cache in-kernel, so wrong ones give a wrong answer, never an out-of-bounds read.
+    Hkv divides H; D is 64 or 128; Nq * (H / Hkv) <= 64.  Anything else raises ValueError (longer chunks: flash_attention_varlen).
+    Returns o [B, Nq, H, D]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention combines such pairs).
+    num_splits: 0 = the library's plan, 1 .. 16 = that many parts per (sequence, K / V head).  Inference only: no backward.
+    C-ABI fa2_fwd_decode: K and V are read once per K / V head group (the group's rows are the M rows of the MFMA), no atomics."""
+    if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cache_seqlens)) or q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("fa2: flash_attention_decode takes q [B, Nq, H, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
+                         "with a block_table)")
+    if torch.is_grad_enabled() and (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad):
+        raise ValueError("fa2: flash_attention_decode is inference only (an input requires grad); " + _DECODE_ROUTE)
+    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise ValueError("fa2: flash_attention_decode takes fp16 or bf16 q, k_cache, v_cache of one dtype, got %s %s %s" % (q.dtype, k_cache.dtype, v_cache.dtype))
+    B, Nq, H, D = q.shape
+    Hkv = k_cache.shape[2]
+    if v_cache.shape != k_cache.shape or k_cache.shape[3] != D:
+        raise ValueError("fa2: inconsistent q / k_cache / v_cache shapes %s %s %s" % (tuple(q.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
+    if B < 1 or Nq < 1 or Hkv < 1 or H % Hkv:
+        raise ValueError("fa2: the head count of the cache (%d) must divide the head count of q (%d), and B, Nq >= 1; %s" % (Hkv, H, _DECODE_ROUTE))
+    if D not in (64, 128):
+        raise ValueError("fa2: flash_attention_decode serves head dims 64 and 128, got %d; %s" % (D, _DECODE_ROUTE))
+    if Nq * (H // Hkv) > _DECODE_MAX_ROWS:
+        raise ValueError("fa2: flash_attention_decode serves Nq * (H / Hkv) <= %d query rows per K / V head, got %d * %d; %s"
+                         % (_DECODE_MAX_ROWS, Nq, H // Hkv, _DECODE_ROUTE))
+    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous():
+        raise ValueError("fa2: cache_seqlens must be a contiguous int32 tensor of shape [B] = [%d], got %s %s" % (B, cache_seqlens.dtype, tuple(cache_seqlens.shape)))
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _DECODE_MAX_SPLITS:
+        raise ValueError("fa2: num_splits is 0 (the library chooses) or 1 .. %d, got %r" % (_DECODE_MAX_SPLITS, num_splits))
+    if block_table is None:
+        if k_cache.shape[0] != B:
+            raise ValueError("fa2: a contiguous cache is [B, Nmax, Hkv, D] with q's batch size %d, got %s (a paged cache needs its block_table)"
+                             % (B, tuple(k_cache.shape)))
+        capacity, page_size, num_pages = k_cache.shape[1], 0, 0
+    else:
+        if not torch.is_tensor(block_table) or block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != B or \
+                block_table.shape[1] < 1 or block_table.stride(1) != 1:
+            raise ValueError("fa2: block_table must be int32 [B, max_pages] with q's batch size %d and contiguous rows, got %s"
+                             % (B, "%s %s" % (block_table.dtype, tuple(block_table.shape)) if torch.is_tensor(block_table) else repr(block_table)))
+        capacity, page_size, num_pages = block_table.shape[1], k_cache.shape[1], k_cache.shape[0]
+        if page_size < 64 or page_size % 64:
+            raise ValueError("fa2: the page size of a paged cache (k_cache.shape[1]) must be a multiple of 64, got %d" % page_size)
+        if num_pages < 1:
+            raise ValueError("fa2: a paged cache needs at least one page")
+    if capacity < 1:
+        raise ValueError("fa2: the cache has no key slots")
+    aux = (cache_seqlens,) if block_table is None else (cache_seqlens, block_table)
+    if not all(t.is_cuda for t in (q, k_cache, v_cache) + aux):
+        raise RuntimeError("fa2: q, the caches, cache_seqlens and block_table must be on a ROCm device (no CPU path in this operator)")
+    if any(t.device != q.device for t in (k_cache, v_cache) + aux):
+        raise RuntimeError("fa2: q, the caches, cache_seqlens and block_table must be on the same device")
+    if not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
+        raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
+    if not _decode_strides_ok(q):
+        q = q.contiguous()
+    if scale is None:
+        scale = D ** -0.5
+    lib = _fa2_lib.load()
+    code = _fa2_lib.FA2_DTYPE_F16 if q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+    o = torch.empty((B, Nq, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    dev = q.device.index if q.device.index is not None else _current_device()
+    with torch.cuda.device(dev):
+        stream = _raw_stream(dev)
+        need = lib.fa2_fwd_decode_workspace_bytes(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits)
+        ws = _workspace(need, q.device, dev, stream) if need else None
+        if ws is None and _WS_POOL:
+            _workspace_unused(dev, stream)
+        s3 = _fa2_lib.strides3
+        rc = lib.fa2_fwd_decode(code, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), cache_seqlens.data_ptr(),
+                                None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page_size, num_pages,
+                                s3(q.stride(0), q.stride(2), q.stride(1)), s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)),
+                                s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)), s3(o.stride(0), o.stride(2), o.stride(1)),
+                                _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0), float(scale),
+                                num_splits, None if ws is None else ws.data_ptr(), need, stream)
+    _fa2_lib.check(rc)
+    return (o, lse * _LN2) if return_lse else o
+
+
 SOFTCAP_MESSAGE = "fa2: softcap must be 0 (off) or a finite positive number (a normal float32: >= 1.18e-38)"
 _SOFTCAP_MIN = 2.0 ** -126          # the smallest normal float32: below it 1 / softcap overflows (the library answers FA2_ERR_SOFTCAP)
 ALIBI_MESSAGE = "fa2: alibi_slopes must be a float32 tensor on q's device, shaped [H] or [B, H] (packed calls: [H] or [num_sequences, H])"

@@ -44,7 +44,16 @@ class BwdPlan(ctypes.Structure):
     _fields_ = [("dq_kernel", ctypes.c_int), ("dkv_kernel", ctypes.c_int)]
 
 
-FA2_BWD_KERNEL_HIP, FA2_BWD_KERNEL_ASM, FA2_BWD_KERNEL_SHORT = 1, 2, 3                                   # fa2_bwd_plan_t.dq_kernel / .dkv_kernel
+class DecodePlan(ctypes.Structure):
+    """fa2_decode_plan_t (include/fa2_gfx950.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kernel", "nsplit", "row_tiles", "key_tile")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+FA2_KERNEL_HIP_DECODE = 7                                                                               # fa2_decode_plan_t.kernel (an enumerator in the header)
+FA2_BWD_KERNEL_HIP, FA2_BWD_KERNEL_ASM, FA2_BWD_KERNEL_SHORT = 1, 2, 3                                  # fa2_bwd_plan_t.dq_kernel / .dkv_kernel
 FA2_BIAS_FORM_SCALAR, FA2_BIAS_FORM_VEC4, FA2_BIAS_FORM_TILE, FA2_BIAS_FORM_TILE_DMA, FA2_BIAS_FORM_ROW = 0, 1, 2, 3, 4     # fa2_fwd_bias_form
 
 
@@ -132,6 +141,13 @@ SYMBOLS = {
                       [ctypes.c_int, ctypes.c_void_p]),
     "fa2_merge_bwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vpp, _vpp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _vpp, _vpp] + [ctypes.c_int] * 4 +
                       [_i64p] * 7 + [ctypes.c_int, ctypes.c_void_p]),
+    # KV-cache decode attention: q k_cache v_cache o lse cache_seqlens block_table, B H Hkv Nq D capacity page_size num_pages, four stride triples, the lse
+    # pair, the block-table row stride, scale, num_splits, workspace, bytes, stream
+    "fa2_fwd_decode": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 8 + [_i64p] * 5 +
+                       [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fa2_fwd_decode_plan": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(DecodePlan)]),
+    "fa2_fwd_decode_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
+    "fa2_decode_part_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_scoremod_eval": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 2),
     "fa2_dropout_keep_mask": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 4 + [ctypes.c_void_p]),
     "fa2_dropout_threshold": (ctypes.c_int, [ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
@@ -321,6 +337,20 @@ def varlen_tile_range(Nq_s, Nkv_s, window_left, window_right, flags, row0, rows,
     first, n = ctypes.c_int(), ctypes.c_int()
     fn = load().fa2_varlen_row_range if transpose else load().fa2_varlen_tile_range
     check(fn(int(Nq_s), int(Nkv_s), int(window_left), int(window_right), int(flags), int(row0), int(rows), int(tile), ctypes.byref(first), ctypes.byref(n)))
+    return first.value, n.value
+
+
+def decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size=0, num_splits=0):
+    """fa2_fwd_decode_plan: the split, the row tiles per K / V head, the key tile and the kernel of a decode call (dtype: an FA2_DTYPE_* code)."""
+    plan = DecodePlan()
+    check(load().fa2_fwd_decode_plan(int(dtype), int(B), int(H), int(Hkv), int(Nq), int(D), int(capacity), int(page_size), int(num_splits), ctypes.byref(plan)))
+    return plan
+
+
+def decode_part_range(length, capacity_keys, Nq, tile, nsplit, part):
+    """fa2_decode_part_range -> (first_tile, ntiles): the key tiles part `part` of `nsplit` sweeps for a sequence of `length` keys."""
+    first, n = ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_decode_part_range(int(length), int(capacity_keys), int(Nq), int(tile), int(nsplit), int(part), ctypes.byref(first), ctypes.byref(n)))
     return first.value, n.value
 
 

@@ -611,6 +611,61 @@ int fa2_merge_bwd(int dtype, int nparts, const void* const* o_parts, const float
                   const int64_t lse_strides[2], const int64_t do_strides[3], const int64_t dlse_strides[2],
                   const int64_t dpart_strides[3], const int64_t dpart_lse_strides[2], int flags, void* hip_stream);
 
+/* ---- KV-cache decode attention: a few new query tokens per sequence against a preallocated cache whose valid length lives on the device.
+ * Layout (element strides {batch, head, row}, D contiguous, as everywhere; the call takes the [B, Nq, H, D] / [B, Nmax, Hkv, D] tensors of other
+ * libraries' kv-cache calls through their strides)
+ *   q, o          : B x H x Nq x D.
+ *   k_cache, v_cache, page_size == 0 : B x Hkv x capacity x D — a contiguous cache of `capacity` (Nmax) key slots per sequence.
+ *   k_cache, v_cache, page_size  > 0 : num_pages x Hkv x page_size x D (strides[0] = the page stride); key j of sequence b lies in page
+ *                   block_table[b * block_table_stride + j / page_size] at slot j % page_size; `capacity` = the block-table entries per sequence.
+ *                   page_size is a multiple of 64, so a key tile never straddles a page.
+ *   cache_seqlens : int32[B], DEVICE memory: the valid keys of each sequence, INCLUDING the Nq new tokens (their K / V are in the cache already).
+ *   block_table   : int32, DEVICE memory (paged calls only).
+ *   lse           : f32 B x H x Nq, lse_strides {batch, head}, log2 units as everywhere.
+ * The host reads neither cache_seqlens nor block_table: no synchronisation, the call can be captured in a graph, and a replay after they changed in
+ * place computes the result for the new contents.  The plan (below) depends on the shape, `capacity` and the CU count only, never on the lengths.
+ * Masking: bottom-right causal per sequence.  With len = clamp(cache_seqlens[b], 0, capacity_keys) (capacity_keys = capacity, paged: capacity *
+ * page_size), query row i sits at position len - Nq + i and sees the keys j <= that position.  Rows at a negative position (len < Nq) see no key:
+ * O = 0, lse = -inf.  Keys at or beyond len and pages beyond the used ones contribute nothing WHATEVER they hold, NaN and Inf in K and in V included.
+ * No content of cache_seqlens or block_table can make the kernel read outside the two cache allocations: len is clamped as above (fa2_decode_part_range),
+ * every page id into [0, num_pages).  A wrong length gives a wrong answer, not a fault.
+ * Shapes: Hkv divides H; D is 64 or 128 (FA2_ERR_HEAD_DIM otherwise); Nq * (H / Hkv) <= 64 query rows per K / V head — longer chunks are
+ * fa2_fwd_varlen's; num_splits 0 (the plan chooses) or 1 .. 16 (forced).  A bad row count, page_size, num_splits: FA2_ERR_BAD_SHAPE.
+ * Checked in this order: null pointers (block_table only when paged), sizes, head dim, alignment (16-byte tensors, 4-byte lse / cache_seqlens /
+ * block_table, strides multiples of 8 with a positive row stride, a non-negative block-table stride), dtype, scale, FA2_ERR_GRID (B or Hkv above
+ * 65535), and last the workspace: with a split above 1 it must be non-null (FA2_ERR_NULL_POINTER), 16-byte aligned (FA2_ERR_ALIGNMENT) and hold
+ * fa2_fwd_decode_workspace_bytes(...) bytes (FA2_ERR_BAD_SHAPE).  It is private to the call until the stream has passed it.
+ * Kernel (FA2_KERNEL_HIP_DECODE, csrc/fa2_decode.hip.h; contract 0: f32 scale of the product, f32 softmax state and row sums, P rounded RNE to the
+ * I/O dtype before P.V, f32 accumulator).  One workgroup per (sequence, K / V head, part): the Nq * G rows of the group are the M rows of
+ * v_mfma_f32_16x16x32 in `row_tiles` tiles of 16, so K and V are fetched once per group.  With a split of 1 the kernel writes o / lse itself;
+ * otherwise the parts leave normalised f32 rows and log2 LSEs of the live rows in the workspace (an empty part: lse = -inf, no O) and a second
+ * kernel merges them and rounds once (all parts empty: zeros and -inf).  No atomics.
+ * Not here: appending new K / V or rotary embedding inside the call, windows, soft-capping, ALiBi, a backward. */
+enum { FA2_KERNEL_HIP_DECODE = 7 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+typedef struct fa2_decode_plan_t {
+    int kernel;        /* FA2_KERNEL_HIP_DECODE */
+    int nsplit;        /* parts per (sequence, K / V head); 1: no workspace, no combine kernel */
+    int row_tiles;     /* row tiles of 16 query rows per K / V head the kernel runs (1, 2 or 4) */
+    int key_tile;      /* keys per tile: the `tile` of fa2_decode_part_range */
+} fa2_decode_plan_t;
+int fa2_fwd_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse,
+                   const int* cache_seqlens, const int* block_table,
+                   int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages,
+                   const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                   const int64_t lse_strides[2], int64_t block_table_stride,
+                   float scale, int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* The plan of that call (the launch executes the same one) and its workspace: pure host functions of the arguments and the device's CU count.
+ * Split rule: 1 when B * Hkv * row_tiles workgroups' worth of row tiles already cover the CUs, else floor(2 * CUs / (B * Hkv * row_tiles)), at most 16
+ * and at most one part per 8 key tiles of the capacity.  fa2_fwd_decode_workspace_bytes: B * Hkv * nsplit * Nq * (H / Hkv) * (D + 1) * 4, 0 for a
+ * split of 1; 0 as well for arguments the call would refuse. */
+int fa2_fwd_decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan);
+size_t fa2_fwd_decode_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits);
+/* The key tiles part `part` of `nsplit` sweeps for a sequence of `len` keys — the host side of the one function the kernel calls
+ * (csrc/fa2_decode.hip.h: decode_part_range).  len is clamped into [0, capacity_keys]; tiles = ceil(len / tile), per = ceil(tiles / nsplit), the
+ * part takes [part * per, min((part + 1) * per, tiles)): [*first_tile, *first_tile + *ntiles), ntiles = 0 for an empty part.
+ * FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for capacity_keys < 0, Nq < 1, tile < 1, nsplit outside 1 .. 16 or part outside [0, nsplit). */
+int fa2_decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, int nsplit, int part, int* first_tile, int* ntiles);
+
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
  * that is not a multiple of 8 has to be zero-padded by the caller (to the next multiple of 8). */

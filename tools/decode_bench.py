@@ -1,0 +1,175 @@
+"""KV-cache decode attention: flash_attention_decode against the routes the library had before it, same box, interleaved rounds, median of
+per-round event times with the spread of the rounds beside it (tools/gqa_bench.py practice).
+
+    python tools/decode_bench.py [--rounds R] [--iters I] [--rows uniform|ragged|all]
+
+Uniform rows (every sequence has the same length, so the older entry points can serve the call at all):
+    decode  flash_attention_decode(q, k_cache, v_cache, cache_seqlens) on a [B, Nmax, Hkv, D] cache with Nmax above the length
+    dense   flash_attention(q, k[:, :, :len], v[:, :, :len]) on [B, Hkv, Nmax, D] tensors, the layout that call prefers (Nq > 1: causal=True with
+            q_offset = len - Nq, the same bottom-right mask) — the BASELINE: what a caller had to run before
+Ragged rows (B sequences with lengths drawn from 256 .. 8192):
+    decode / paged64 / paged256   the contiguous cache, and the same data in pages of 64 / 256 keys in shuffled physical order
+    varlen        flash_attention_varlen(causal=True, bottom_right=True) on a packed copy of the valid keys made OUTSIDE the timed region
+    varlen+copy   ... with the packing (one torch.cat of the per-sequence slices per tensor) inside it: what serving a cache through it costs per step
+    padmask       flash_attention(mask = key padding [B, 1, 1, Nmax]) on the padded cache
+Every row prints the K + V bytes that are valid (what a perfect kernel has to read) and the time they take at 6.3 TB/s, the achievable HBM rate.
+Each row first checks the routes against each other on the timed inputs (fp16 1e-3 + 2e-3 |x|, bf16 8e-3 + 1.6e-2 |x|): faster and different is not faster.
+The same K / V are read in every iteration, so caches up to the 256 MB of Infinity Cache are served from it in every route alike.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
+
+import torch  # noqa: E402
+
+from rocwmma_fattn import _fa2_lib  # noqa: E402
+from rocwmma_fattn.FlashAttn import flash_attention, flash_attention_decode, flash_attention_varlen  # noqa: E402
+
+HBM_TBS = 6.3
+UNIFORM = [  # (label, B, H, Hkv, Nq, keys, D, dtype)
+    ("b1_hkv8", 1, 32, 8, 1, 8192, 128, torch.float16),
+    ("b1_hkv1_mqa", 1, 32, 1, 1, 8192, 128, torch.float16),
+    ("b1_hkv32_mha", 1, 32, 32, 1, 8192, 128, torch.float16),
+    ("b32_hkv8_bf16", 32, 32, 8, 1, 4096, 128, torch.bfloat16),
+    ("b4_h8_d64", 4, 8, 8, 1, 16384, 64, torch.float16),
+    ("b8_hkv8_nq4", 8, 32, 8, 4, 8192, 128, torch.float16),
+]
+RAGGED = ("ragged_b32", 32, 32, 8, 1, 256, 8192, 128, torch.float16)      # label, B, H, Hkv, Nq, shortest, longest, D, dtype
+
+
+def interleaved(fns, rounds, iters):
+    """{name: (median, min, max) ms per call} of the callables in `fns`, timed round-robin (one event pair per (round, callable))."""
+    for f in fns.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    times = {n: [] for n in fns}
+    for _ in range(rounds):
+        for n, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record()
+            torch.cuda.synchronize()
+            times[n].append(e0.elapsed_time(e1) / iters)
+    return {n: (statistics.median(t), min(t), max(t)) for n, t in times.items()}
+
+
+def close(a, b, dt, what):
+    atol, rtol = (1e-3, 2e-3) if dt == torch.float16 else (8e-3, 1.6e-2)
+    a, b = a.float(), b.float()
+    bad = (a - b).abs() > atol + rtol * b.abs()
+    if bad.any() or not torch.isfinite(a).all():
+        raise SystemExit("decode_bench: %s disagree (max |diff| %.3g)" % (what, float((a - b).abs().max())))
+
+
+def report(label, shape, t, valid_bytes, base):
+    floor_us = valid_bytes / (HBM_TBS * 1e12) * 1e6
+    print("%-14s %s  valid K+V %.1f MB = %.1f us at %.1f TB/s" % (label, shape, valid_bytes / 1e6, floor_us, HBM_TBS))
+    b_med, b_lo, b_hi = t[base]
+    for n, (med, lo, hi) in t.items():
+        rel = "" if n == base else "  %.2fx faster than %s" % (b_med / med, base) if med <= b_med else "  %.2fx SLOWER than %s" % (med / b_med, base)
+        print("    %-12s %9.1f us  (rounds %.1f .. %.1f, spread %.1f %%)  %5.2f TB/s of valid K+V%s"
+              % (n, med * 1e3, lo * 1e3, hi * 1e3, 100.0 * (hi - lo) / med, valid_bytes / (med * 1e-3) / 1e12, rel))
+    sys.stdout.flush()
+
+
+def uniform_row(label, B, H, Hkv, Nq, keys, D, dt, rounds, iters):
+    dev = torch.device("cuda", 0)
+    nmax = keys + 256                                        # a cache with room to grow, as in serving
+    q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
+    kc, vc = (torch.randn((B, nmax, Hkv, D), device=dev, dtype=dt) for _ in range(2))
+    lens = torch.full((B,), keys, dtype=torch.int32, device=dev)
+    qh = q.transpose(1, 2).contiguous()                      # the dense call's layout: [B, H, N, D] and a [B, Hkv, Nmax, D] cache
+    kh, vh = kc.transpose(1, 2).contiguous(), vc.transpose(1, 2).contiguous()
+    if Nq == 1:
+        dense = lambda: flash_attention(qh, kh[:, :, :keys], vh[:, :, :keys])  # noqa: E731
+    else:
+        dense = lambda: flash_attention(qh, kh[:, :, :keys], vh[:, :, :keys], causal=True, q_offset=keys - Nq)  # noqa: E731
+    fns = {"decode": lambda: flash_attention_decode(q, kc, vc, lens), "dense": dense}
+    with torch.no_grad():
+        close(fns["decode"]().transpose(1, 2), fns["dense"](), dt, label + ": decode and dense")
+        t = interleaved(fns, rounds, iters)
+    plan = _fa2_lib.decode_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, nmax)
+    shape = "B%d H%d Hkv%d Nq%d keys %d D%d %s (split %d, %d row tile%s)" % (B, H, Hkv, Nq, keys, D, "fp16" if dt == torch.float16 else "bf16", plan.nsplit,
+                                                                              plan.row_tiles, "" if plan.row_tiles == 1 else "s")
+    report(label, shape, t, 2 * B * Hkv * keys * D * 2, "dense")
+
+
+def paged(kc, vc, lens, page, g):
+    B, nmax = kc.shape[0], kc.shape[1]
+    used = [-(-n // page) for n in lens]
+    total = sum(used) + 4
+    order = torch.randperm(total, generator=g).tolist()
+    pk = torch.zeros((total, page) + tuple(kc.shape[2:]), device=kc.device, dtype=kc.dtype)
+    pv = torch.zeros_like(pk)
+    bt = torch.full((B, nmax // page), order[-1], dtype=torch.int32)
+    nxt = 0
+    for b in range(B):
+        for j in range(used[b]):
+            pk[order[nxt]] = kc[b, j * page:(j + 1) * page]
+            pv[order[nxt]] = vc[b, j * page:(j + 1) * page]
+            bt[b, j] = order[nxt]
+            nxt += 1
+    return pk, pv, bt.to(kc.device)
+
+
+def ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    lens_h = torch.randint(lo, hi + 1, (B,), generator=g).tolist()
+    nmax = hi
+    q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
+    kc, vc = (torch.randn((B, nmax, Hkv, D), device=dev, dtype=dt) for _ in range(2))
+    lens = torch.tensor(lens_h, dtype=torch.int32, device=dev)
+    cu_q = torch.arange(0, (B + 1) * Nq, Nq, dtype=torch.int32, device=dev)
+    cu_k = torch.tensor([0] + list(torch.tensor(lens_h).cumsum(0)), dtype=torch.int32, device=dev)
+    qp = q.reshape(B * Nq, H, D)
+    pack = lambda t: torch.cat([t[b, :n] for b, n in enumerate(lens_h)])  # noqa: E731
+    kp, vp = pack(kc), pack(vc)
+    qh, kh, vh = q.transpose(1, 2).contiguous(), kc.transpose(1, 2).contiguous(), vc.transpose(1, 2).contiguous()
+    keep = (torch.arange(nmax, device=dev)[None, :] < lens[:, None]).view(B, 1, 1, nmax)
+    p64, p256 = paged(kc, vc, lens_h, 64, g), paged(kc, vc, lens_h, 256, g)
+    fns = {
+        "decode": lambda: flash_attention_decode(q, kc, vc, lens),
+        "paged64": lambda: flash_attention_decode(q, p64[0], p64[1], lens, block_table=p64[2]),
+        "paged256": lambda: flash_attention_decode(q, p256[0], p256[1], lens, block_table=p256[2]),
+        "varlen": lambda: flash_attention_varlen(qp, kp, vp, cu_q, cu_k, Nq, hi, causal=True, bottom_right=True),
+        "varlen+copy": lambda: flash_attention_varlen(qp, pack(kc), pack(vc), cu_q, cu_k, Nq, hi, causal=True, bottom_right=True),
+        "padmask": lambda: flash_attention(qh, kh, vh, mask=keep),
+    }
+    with torch.no_grad():
+        want = fns["varlen"]().reshape(B, Nq, H, D)
+        for n in ("decode", "paged64", "paged256"):
+            close(fns[n](), want, dt, label + ": %s and varlen" % n)
+        close(fns["padmask"]().transpose(1, 2), want, dt, label + ": padmask and varlen")
+        t = interleaved(fns, rounds, max(1, iters // 2))
+    plan = _fa2_lib.decode_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, nmax)
+    shape = "B%d H%d Hkv%d Nq%d keys %d .. %d (mean %d) D%d %s (split %d)" % (B, H, Hkv, Nq, min(lens_h), max(lens_h), sum(lens_h) // B, D,
+                                                                             "fp16" if dt == torch.float16 else "bf16", plan.nsplit)
+    report(label, shape, t, 2 * Hkv * sum(lens_h) * D * 2, "varlen")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rows", default="all", choices=("uniform", "ragged", "all"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("decode_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
+    print(torch.cuda.get_device_name(0), "rounds", a.rounds, "iters", a.iters, "|", _fa2_lib.load().fa2_version().decode())
+    if a.rows in ("uniform", "all"):
+        for r in UNIFORM:
+            uniform_row(*r, a.rounds, a.iters)
+    if a.rows in ("ragged", "all"):
+        ragged_row(*RAGGED, a.rounds, a.iters)
+
+
+if __name__ == "__main__":
+    main()
