@@ -61,6 +61,8 @@ UNITS = [
     ("merge_hip", "merge_hip.cpp", []),          # both dtypes in one unit
     ("decode_hip_f16", "decode_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("decode_hip_bf16", "decode_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("decode_fp8_hip_f16", "decode_hip.cpp", ["-DFA2_TU_BF16=0", "-DFA2_TU_FP8=1"]),      # e4m3 caches, f16 / bf16 q and o
+    ("decode_fp8_hip_bf16", "decode_hip.cpp", ["-DFA2_TU_BF16=1", "-DFA2_TU_FP8=1"]),
 ]
 FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end of the operator (host-only C++, g++)
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")

@@ -20,8 +20,18 @@
 // [0, num_pages), every key index a lane forms into [0, len - 1] before it becomes an address.  Keys at or beyond len contribute nothing whatever
 // the cache holds there: their scores are replaced by -inf (a select on the position, not arithmetic on the score) and their V rows by zero bits
 // before they reach LDS, since 0 * NaN is NaN.
+//
+// FP8 caches (fa2_fwd_decode_fp8): the same body with the compile-time cache format FP8.  K and V are OCP e4m3 bytes, half the
+// bytes per key, and become the I/O dtype in registers (v_cvt_scalef32_pk_{f16,bf16}_fp8 at scale 1: exact, every finite e4m3 value is a f16 and a
+// bf16 value).  A lane still takes 16 bytes of its key per load — now 16 columns, which feed TWO k-steps of S^T = K Q^T; the contraction index may be
+// permuted freely, so Q's B fragments are loaded once in the same permutation (k-step dc of lane group g = columns 64 (dc >> 1) + 16 g + 8 (dc & 1) ..).
+// V is converted between the registers and the slab, whose format, transposed reads and P . V MFMAs are unchanged.  k_descale[b, hkv] is folded into
+// the f32 score scale, v_descale[b, hkv] multiplies the normalised f32 row before its one rounding (split calls: before the workspace, so the combine
+// kernel is the same).  The zero-bit select of V rows at or beyond len acts on the raw bytes (0x00 is +0), the -inf select of the scores on positions.
 #pragma once
 #include <stdint.h>
+
+#include <type_traits>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #include "fa2_fwd_kernel.hip.h"      // the vector types, pack2
@@ -67,6 +77,8 @@ struct DecodeParams {
     int64_t capacity_keys;      // Nmax, or max_pages * page_size
     int64_t qs[3], ks[3], vs[3], os[3], ls[2], bts;      // element strides {batch | page, head, row}; lse {batch, head}; block-table row stride
     float c;                    // scale * log2(e)
+    const float *kd, *vd;       // FP8 caches: k_descale / v_descale [B, Hkv], device, null = 1.0
+    int64_t ds[2];              // their element strides {batch, K / V head}
 };
 
 // workspace bytes of a split call (live rows only)
@@ -99,14 +111,36 @@ __device__ __forceinline__ void decode_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int HD, bool BF16, int RT>
+// two e4m3 bytes (the low or the high half of w) -> two I/O dtype values, exact
+template <bool BF16>
+__device__ __forceinline__ uint32_t decode_cvt2(uint32_t w, bool hi) {
+    if constexpr (BF16)
+        return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
+                  : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+    else
+        return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))
+                  : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
+}
+// eight e4m3 bytes -> eight I/O dtype values in memory order
+template <bool BF16>
+__device__ __forceinline__ u32x4 decode_cvt8(uint32_t lo, uint32_t hi) {
+    return (u32x4){decode_cvt2<BF16>(lo, false), decode_cvt2<BF16>(lo, true), decode_cvt2<BF16>(hi, false), decode_cvt2<BF16>(hi, true)};
+}
+
+// FP8: the caches hold OCP e4m3 bytes (KV = bytes per cache element); q, o and the arithmetic stay in the I/O dtype.
+template <int HD, bool BF16, int RT, bool FP8 = false>
 __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeParams p) {
-    constexpr int NW = kDecodeWaves, T = kDecodeTile, DC = HD / 32, DB = HD / 16, VL = T * HD * 2 / 16 / 64, GR = HD / 8;
+    constexpr int KV = FP8 ? 1 : 2;
+    using cache_t = typename std::conditional<FP8, uint8_t, uint16_t>::type;
+    constexpr int E16 = 16 / KV;                       // cache elements per 16-byte load
+    constexpr int NW = kDecodeWaves, T = kDecodeTile, DC = HD / 32, DB = HD / 16, VL = T * HD * KV / 16 / 64, GR = HD / 8;
+    constexpr int KC = DC * KV / 2;                    // 16-byte loads per key of a lane: 32 columns apart (16-bit), 64 (FP8: one load feeds two k-steps)
+    constexpr int VGR = HD * KV / 16;                  // 16-byte chunks of a V row in memory
     constexpr int VROWB = HD * 2 + 16;                 // bytes of a V row in the slab
     constexpr int SLAB = T * VROWB;                    // one wave's slab: its V tile, later its f32 accumulator tile [16 rows][HD + 4]
     constexpr int XROW = HD + 4;
     static_assert(16 * XROW * 4 <= SLAB, "the accumulator exchange reuses the V slab");
-    static_assert(VL * 64 * 16 == T * HD * 2 && T == 32, "tile geometry");
+    static_assert(VL * 64 * 16 == T * HD * KV && T == 32 && KC >= 1, "tile geometry");
     __shared__ __attribute__((aligned(16))) char lds[NW * SLAB + 2 * NW * kDecodeMaxRows * 4];
     float* const sm = reinterpret_cast<float*>(lds + NW * SLAB);          // [NW][64] running maxima, then [NW][64] row sums
     float* const sl = sm + NW * kDecodeMaxRows;
@@ -137,14 +171,22 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
         const bool live = r < p.rows;
         const int i = live ? r / p.G : 0, h = hkv * p.G + (live ? r % p.G : 0);
         pos[rt] = live ? len - p.Nq + i : -1;
-        const uint16_t* row = qbase + h * p.qs[1] + i * p.qs[2] + 8 * g;
+        const uint16_t* row = qbase + h * p.qs[1] + i * p.qs[2] + (FP8 ? 16 : 8) * g;
 #pragma unroll
-        for (int dc = 0; dc < DC; ++dc) qf[rt][dc] = live ? *reinterpret_cast<const u32x4*>(row + dc * 32) : (u32x4){0u, 0u, 0u, 0u};
+        for (int dc = 0; dc < DC; ++dc)                // FP8: the column order of K's 16-byte loads
+            qf[rt][dc] = live ? *reinterpret_cast<const u32x4*>(row + (FP8 ? 64 * (dc >> 1) + 8 * (dc & 1) : dc * 32)) : (u32x4){0u, 0u, 0u, 0u};
+    }
+    // the score scale and the output scale of the item (FP8: the descales are device data, like the lengths)
+    float c = p.c, vd = 1.f;
+    if constexpr (FP8) {
+        const int64_t di = b * p.ds[0] + hkv * p.ds[1];
+        if (p.kd) c *= p.kd[di];
+        if (p.vd) vd = p.vd[di];
     }
 
-    // one tile into registers: K as MFMA A fragments [16-key block][32-column chunk], V as it lies in memory (chunk c = i * 64 + lane of the tile's
-    // T * HD / 8 16-byte chunks; rows at or beyond len as zero bits)
-    auto load_tile = [&](int t, u32x4 (&kf)[2][DC], u32x4 (&vr)[VL]) {
+    // one tile into registers: K as MFMA A fragments [16-key block][32-column chunk] (FP8: the bytes of two chunks), V as it lies in memory (chunk
+    // c = i * 64 + lane of the tile's 16-byte chunks; rows at or beyond len as zero bits)
+    auto load_tile = [&](int t, u32x4 (&kf)[2][KC], u32x4 (&vr)[VL]) {
         const int key0 = t * T;
         int64_t kofs, vofs;
         int row0 = key0;
@@ -160,19 +202,19 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
             vofs = b * p.vs[0] + hkv * p.vs[1];
         }
         const int last = len - 1 - key0;               // >= 0: the tile holds a valid key; a lane's key index is clamped to it
-        const uint16_t* const kb = static_cast<const uint16_t*>(p.k) + kofs + 8 * g;
+        const cache_t* const kb = static_cast<const cache_t*>(p.k) + kofs + E16 * g;
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
             const int kk = blk * 16 + qi;
-            const uint16_t* row = kb + (int64_t)(row0 + (kk < last ? kk : last)) * p.ks[2];
+            const cache_t* row = kb + (int64_t)(row0 + (kk < last ? kk : last)) * p.ks[2];
 #pragma unroll
-            for (int dc = 0; dc < DC; ++dc) kf[blk][dc] = *reinterpret_cast<const u32x4*>(row + dc * 32);
+            for (int kc = 0; kc < KC; ++kc) kf[blk][kc] = *reinterpret_cast<const u32x4*>(row + kc * 4 * E16);
         }
-        const uint16_t* const vb = static_cast<const uint16_t*>(p.v) + vofs;
+        const cache_t* const vb = static_cast<const cache_t*>(p.v) + vofs;
 #pragma unroll
         for (int i = 0; i < VL; ++i) {
-            const int ch = i * 64 + lane, kk = ch / GR, col = ch % GR;
-            const u32x4 x = *reinterpret_cast<const u32x4*>(vb + (int64_t)(row0 + (kk < last ? kk : last)) * p.vs[2] + col * 8);
+            const int ch = i * 64 + lane, kk = ch / VGR, col = ch % VGR;
+            const u32x4 x = *reinterpret_cast<const u32x4*>(vb + (int64_t)(row0 + (kk < last ? kk : last)) * p.vs[2] + col * E16);
             vr[i] = kk <= last ? x : (u32x4){0u, 0u, 0u, 0u};
         }
     };
@@ -192,11 +234,11 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
 
     const int tend = first + nt;
     int t = first + w;
-    u32x4 kf[2][DC], vr[VL];
+    u32x4 kf[2][KC], vr[VL];
     if (t < tend) load_tile(t, kf, vr);
     while (t < tend) {
         const int tn = t + NW;
-        u32x4 kfn[2][DC] = {}, vrn[VL] = {};
+        u32x4 kfn[2][KC] = {}, vrn[VL] = {};
         if (tn < tend) load_tile(tn, kfn, vrn);        // the next step's tiles are in flight while this one is computed on
 
         // S^T = K Q^T, one 16 x 16 block per (row tile, 16-key block)
@@ -207,7 +249,12 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
             for (int blk = 0; blk < 2; ++blk) {
                 s[rt][blk] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int dc = 0; dc < DC; ++dc) s[rt][blk] = decode_mfma<BF16>(kf[blk][dc], qf[rt][dc], s[rt][blk]);
+                for (int dc = 0; dc < DC; ++dc) {
+                    u32x4 a;
+                    if constexpr (FP8) a = decode_cvt8<BF16>(kf[blk][dc >> 1][2 * (dc & 1)], kf[blk][dc >> 1][2 * (dc & 1) + 1]);
+                    else a = kf[blk][dc];
+                    s[rt][blk] = decode_mfma<BF16>(a, qf[rt][dc], s[rt][blk]);
+                }
             }
 
         // V tile -> the wave's slab, rows as they lie in memory
@@ -215,7 +262,13 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
 #pragma unroll
         for (int i = 0; i < VL; ++i) {
             const int ch = i * 64 + lane;
-            *reinterpret_cast<u32x4*>(slab + (ch / GR) * VROWB + (ch % GR) * 16) = vr[i];
+            if constexpr (FP8) {                       // 16 columns of a key: converted here, the slab holds the I/O dtype as ever
+                char* const dst = slab + (ch / VGR) * VROWB + (ch % VGR) * 32;
+                *reinterpret_cast<u32x4*>(dst) = decode_cvt8<BF16>(vr[i][0], vr[i][1]);
+                *reinterpret_cast<u32x4*>(dst + 16) = decode_cvt8<BF16>(vr[i][2], vr[i][3]);
+            } else {
+                *reinterpret_cast<u32x4*>(slab + (ch / GR) * VROWB + (ch % GR) * 16) = vr[i];
+            }
         }
         decode_wave_sync();
 
@@ -229,7 +282,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int key = key0 + 16 * (j >> 2) + 4 * g + (j & 3);
-                x[j] = key <= pos[rt] ? s[rt][j >> 2][j & 3] * p.c : ninf;
+                x[j] = key <= pos[rt] ? s[rt][j >> 2][j & 3] * c : ninf;
                 mt = __builtin_fmaxf(mt, x[j]);
             }
             mt = decode_group_max(mt);
@@ -261,7 +314,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
-            for (int dc = 0; dc < DC; ++dc) kf[blk][dc] = kfn[blk][dc];
+            for (int kc = 0; kc < KC; ++kc) kf[blk][kc] = kfn[blk][kc];
 #pragma unroll
         for (int i = 0; i < VL; ++i) vr[i] = vrn[i];
         t = tn;
@@ -309,6 +362,10 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
             const float inv = L > 0.f ? 1.0f / L : 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) out[e] *= inv;
+            if constexpr (FP8) {                       // v_descale: f32, on the normalised row, before its one rounding (or the workspace)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) out[e] *= vd;
+            }
             const float lse2 = L > 0.f ? M + __builtin_amdgcn_logf(L) : ninf;
             if (p.nsplit > 1) {
                 float* dst = ws_o + (int64_t)r * HD + ogr * 8;

@@ -258,6 +258,9 @@ FA2_HIDDEN int launch_merge_bwd(bool bf16, MergeParams& p, hipStream_t stream);
 // KV-cache decode attention (decode_hip.cpp; fa2_fwd_decode): the kernel of csrc/fa2_decode.hip.h with `row_tiles` (1, 2 or 4) row tiles of 16 query rows per
 // K / V head on a grid of (p.nsplit, Hkv, B) workgroups, then — p.nsplit > 1 — the combine of the parts left in p.ws
 FA2_LAUNCHER(launch_decode, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
+// ... the same kernel over e4m3 caches (fa2_fwd_decode_fp8; decode_hip.cpp compiled with -DFA2_TU_FP8=1), and the one combine both end with
+FA2_LAUNCHER(launch_decode_fp8, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
+FA2_LAUNCHER(launch_decode_combine, (int HD, const DecodeParams& p, hipStream_t stream), (HD, p, stream))
 
 constexpr int kBwdAsmParts = 3;      // passes the hand-scheduled backward covers: bit 0 = dQ, bit 1 = dK / dV
 

@@ -1535,18 +1535,26 @@ int fa2_decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, 
     return FA2_OK;
 }
 
-int fa2_fwd_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table,
-                   int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3], const int64_t k_strides[3],
-                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale,
-                   int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    if (any_null({q, k_cache, v_cache, o, lse, cache_seqlens, q_strides, k_strides, v_strides, o_strides, lse_strides}) || (page_size > 0 && !block_table))
+// One body for fa2_fwd_decode and fa2_fwd_decode_fp8 (fp8: e4m3 caches, whose element strides are bytes; the descales and their strides are the fp8
+// entry's alone).  The checks run in the documented order.
+static int decode_run(bool fp8, int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens,
+                      const int* block_table, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
+                      const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
+                      int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                      int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (any_null({q, k_cache, v_cache, o, lse, cache_seqlens, q_strides, k_strides, v_strides, o_strides, lse_strides}) || (page_size > 0 && !block_table) ||
+        ((k_descale || v_descale) && !descale_strides))
         return FA2_ERR_NULL_POINTER;
     int row_tiles = 0;
     if (int rc = decode_check_shape(B, H, Hkv, Nq, D, capacity, page_size, num_splits, &row_tiles)) return rc;
     if ((page_size > 0 && num_pages < 1) || lse_strides[0] < 0 || lse_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
+    if ((k_descale || v_descale) && (descale_strides[0] < 0 || descale_strides[1] < 0)) return FA2_ERR_BAD_SHAPE;
+    // a 16-byte load covers 8 columns of a 16-bit cache and 16 of an e4m3 one
+    const auto cache_strides_ok = [fp8](const int64_t* st) { return strides3_ok(st) && (!fp8 || ((st[0] | st[1] | st[2]) & 15) == 0); };
     if (!all_aligned16({q, k_cache, v_cache, o}) ||
-        ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(block_table)) & 3u) ||
-        !strides3_ok(q_strides) || !strides3_ok(k_strides) || !strides3_ok(v_strides) || !strides3_ok(o_strides) || block_table_stride < 0)
+        ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(block_table) |
+          reinterpret_cast<uintptr_t>(k_descale) | reinterpret_cast<uintptr_t>(v_descale)) & 3u) ||
+        !strides3_ok(q_strides) || !cache_strides_ok(k_strides) || !cache_strides_ok(v_strides) || !strides3_ok(o_strides) || block_table_stride < 0)
         return FA2_ERR_ALIGNMENT;
     fa2_decode_plan_t plan;
     if (int rc = decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, &plan)) return rc;       // (the dtype: after the alignment)
@@ -1562,13 +1570,44 @@ int fa2_fwd_decode(int dtype, const void* q, const void* k_cache, const void* v_
     p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
     p.bts = block_table_stride;
     p.c = scale * 1.4426950408889634f;
+    p.kd = k_descale; p.vd = v_descale;
+    if (k_descale || v_descale) { p.ds[0] = descale_strides[0]; p.ds[1] = descale_strides[1]; }
     if (plan.nsplit > 1) {
         if (!workspace) return FA2_ERR_NULL_POINTER;
         if (!aligned16(workspace)) return FA2_ERR_ALIGNMENT;
         if (workspace_bytes < (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, p.rows, D)) return FA2_ERR_BAD_SHAPE;
         p.ws = static_cast<float*>(workspace);
     }
-    return fa2::launch_decode(dtype == FA2_DTYPE_BF16, D, p, plan.row_tiles, (hipStream_t)hip_stream);
+    return fp8 ? fa2::launch_decode_fp8(dtype == FA2_DTYPE_BF16, D, p, plan.row_tiles, (hipStream_t)hip_stream)
+               : fa2::launch_decode(dtype == FA2_DTYPE_BF16, D, p, plan.row_tiles, (hipStream_t)hip_stream);
+}
+
+int fa2_fwd_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table,
+                   int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3], const int64_t k_strides[3],
+                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale,
+                   int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    return decode_run(false, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
+                      v_strides, o_strides, lse_strides, block_table_stride, scale, nullptr, nullptr, nullptr, num_splits, workspace, workspace_bytes, hip_stream);
+}
+
+// ---- ... on e4m3 caches with per (sequence, K / V head) descales.  The fp8 kernel sweeps the same 32-key tiles under the same split rule, so the plan
+// and the workspace are the 16-bit call's (the parts are f32 rows either way).
+int fa2_fwd_decode_fp8(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens,
+                       const int* block_table, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
+                       const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
+                       int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                       int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    return decode_run(true, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
+                      v_strides, o_strides, lse_strides, block_table_stride, scale, k_descale, v_descale, descale_strides, num_splits, workspace, workspace_bytes,
+                      hip_stream);
+}
+
+int fa2_fwd_decode_fp8_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
+    return fa2_fwd_decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, plan);
+}
+
+size_t fa2_fwd_decode_fp8_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits) {
+    return fa2_fwd_decode_workspace_bytes(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits);
 }
 
 int fa2_fwd_f16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_F16, FA2_FWD_PASS, hip_stream); }

@@ -1092,12 +1092,17 @@ _DECODE_MAX_SPLITS = 16
 _DECODE_ROUTE = "flash_attention_varlen(..., causal=True, bottom_right=True) on packed tensors serves such calls"
 
 
-def _decode_strides_ok(t):
+def _decode_strides_ok(t, mult=8):
     s0, s1, s2, s3 = t.stride()
-    return s3 == 1 and not ((s0 | s1 | s2) & 7) and s1 > 0 and not (t.data_ptr() & 15)
+    return s3 == 1 and not ((s0 | s1 | s2) & (mult - 1)) and s1 > 0 and not (t.data_ptr() & 15)
 
 
-def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None, scale=None, return_lse=False, num_splits=0):
+_FP8_CACHE = getattr(torch, "float8_e4m3fn", None)
+_FP8_OTHERS = tuple(d for d in (getattr(torch, n, None) for n in ("float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz")) if d is not None)
+
+
+def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None, scale=None, return_lse=False, num_splits=0, k_descale=None,
+                           v_descale=None):
     """KV-cache decode attention (the flash_attn_with_kvcache shape): a few new query tokens per sequence against a preallocated cache.
     q [B, Nq, H, D] fp16 / bf16.  Contiguous cache: k_cache / v_cache [B, Nmax, Hkv, D].  Paged cache: k_cache / v_cache [num_pages, page_size, Hkv, D]
     with block_table int32 [B, max_pages] on q's device, page_size a multiple of 64.  Strided views are fine (D contiguous, strides multiples of 8
@@ -1111,14 +1116,29 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     Hkv divides H; D is 64 or 128; Nq * (H / Hkv) <= 64.  Anything else raises ValueError (longer chunks: flash_attention_varlen).
     Returns o [B, Nq, H, D]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention combines such pairs).
     num_splits: 0 = the library's plan, 1 .. 16 = that many parts per (sequence, K / V head).  Inference only: no backward.
+    FP8 caches: k_cache and v_cache may both be torch.float8_e4m3fn (OCP e4m3, gfx950's FP8; not e5m2, not fnuz) in the same two layouts, q staying
+    fp16 / bf16.  k_descale / v_descale: float32 [B, Hkv] on q's device (any strides), each optional, None = 1.0; K = float(k_cache) * k_descale[b, hkv],
+    V = float(v_cache) * v_descale[b, hkv].  They are device data the host never reads, like cache_seqlens: a captured graph replays correctly after
+    they changed in place.  An fp8 cache needs a contiguous head dim, 16-byte aligned storage and strides that are multiples of 16 elements.  A descale
+    with a 16-bit cache raises ValueError.  C-ABI fa2_fwd_decode_fp8; o and lse as for a 16-bit cache.
     C-ABI fa2_fwd_decode: K and V are read once per K / V head group (the group's rows are the M rows of the MFMA), no atomics."""
     if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cache_seqlens)) or q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("fa2: flash_attention_decode takes q [B, Nq, H, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
                          "with a block_table)")
     if torch.is_grad_enabled() and (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad):
         raise ValueError("fa2: flash_attention_decode is inference only (an input requires grad); " + _DECODE_ROUTE)
-    if q.dtype not in (torch.float16, torch.bfloat16) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise ValueError("fa2: flash_attention_decode takes fp16 or bf16 q, k_cache, v_cache of one dtype, got %s %s %s" % (q.dtype, k_cache.dtype, v_cache.dtype))
+    if k_cache.dtype in _FP8_OTHERS or v_cache.dtype in _FP8_OTHERS:
+        raise ValueError("fa2: flash_attention_decode takes FP8 caches as torch.float8_e4m3fn (OCP e4m3) only: e5m2 and the fnuz formats are not "
+                         "served, got %s %s" % (k_cache.dtype, v_cache.dtype))
+    fp8 = _FP8_CACHE is not None and (k_cache.dtype == _FP8_CACHE or v_cache.dtype == _FP8_CACHE)
+    if fp8 and k_cache.dtype != v_cache.dtype:
+        raise ValueError("fa2: flash_attention_decode takes k_cache and v_cache of one dtype (both float8_e4m3fn, or both q's dtype), got %s %s"
+                         % (k_cache.dtype, v_cache.dtype))
+    if q.dtype not in (torch.float16, torch.bfloat16) or (not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype)):
+        raise ValueError("fa2: flash_attention_decode takes fp16 or bf16 q, k_cache, v_cache of one dtype (or float8_e4m3fn caches), got %s %s %s"
+                         % (q.dtype, k_cache.dtype, v_cache.dtype))
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise ValueError("fa2: k_descale / v_descale belong to float8_e4m3fn caches; this cache is %s" % k_cache.dtype)
     B, Nq, H, D = q.shape
     Hkv = k_cache.shape[2]
     if v_cache.shape != k_cache.shape or k_cache.shape[3] != D:
@@ -1151,12 +1171,23 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
             raise ValueError("fa2: a paged cache needs at least one page")
     if capacity < 1:
         raise ValueError("fa2: the cache has no key slots")
-    aux = (cache_seqlens,) if block_table is None else (cache_seqlens, block_table)
+    descales = tuple(d for d in (k_descale, v_descale) if d is not None)
+    for d in descales:
+        if not torch.is_tensor(d) or d.dtype != torch.float32 or tuple(d.shape) != (B, Hkv):
+            raise ValueError("fa2: k_descale / v_descale must be float32 tensors of shape [B, Hkv] = [%d, %d], got %s"
+                             % (B, Hkv, "%s %s" % (d.dtype, tuple(d.shape)) if torch.is_tensor(d) else repr(d)))
+    aux = ((cache_seqlens,) if block_table is None else (cache_seqlens, block_table)) + descales
     if not all(t.is_cuda for t in (q, k_cache, v_cache) + aux):
-        raise RuntimeError("fa2: q, the caches, cache_seqlens and block_table must be on a ROCm device (no CPU path in this operator)")
+        raise RuntimeError("fa2: q, the caches, cache_seqlens, block_table and the descales must be on a ROCm device (no CPU path in this operator)")
     if any(t.device != q.device for t in (k_cache, v_cache) + aux):
-        raise RuntimeError("fa2: q, the caches, cache_seqlens and block_table must be on the same device")
-    if not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
+        raise RuntimeError("fa2: q, the caches, cache_seqlens, block_table and the descales must be on the same device")
+    if fp8:
+        if not _decode_strides_ok(k_cache, 16) or not _decode_strides_ok(v_cache, 16):
+            raise ValueError("fa2: float8_e4m3fn k_cache / v_cache need a contiguous head dim, strides that are multiples of 16 elements and 16-byte "
+                             "aligned storage")
+        if len(descales) == 2 and k_descale.stride() != v_descale.stride():       # the C-ABI takes one stride pair: a device copy, nothing read back
+            k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
+    elif not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
         raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
     if not _decode_strides_ok(q):
         q = q.contiguous()
@@ -1169,17 +1200,23 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     dev = q.device.index if q.device.index is not None else _current_device()
     with torch.cuda.device(dev):
         stream = _raw_stream(dev)
-        need = lib.fa2_fwd_decode_workspace_bytes(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits)
+        need = (lib.fa2_fwd_decode_fp8_workspace_bytes if fp8 else lib.fa2_fwd_decode_workspace_bytes)(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits)
         ws = _workspace(need, q.device, dev, stream) if need else None
         if ws is None and _WS_POOL:
             _workspace_unused(dev, stream)
         s3 = _fa2_lib.strides3
-        rc = lib.fa2_fwd_decode(code, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), cache_seqlens.data_ptr(),
-                                None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page_size, num_pages,
-                                s3(q.stride(0), q.stride(2), q.stride(1)), s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)),
-                                s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)), s3(o.stride(0), o.stride(2), o.stride(1)),
-                                _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0), float(scale),
-                                num_splits, None if ws is None else ws.data_ptr(), need, stream)
+        head = (code, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), cache_seqlens.data_ptr(),
+                None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page_size, num_pages,
+                s3(q.stride(0), q.stride(2), q.stride(1)), s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)),
+                s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)), s3(o.stride(0), o.stride(2), o.stride(1)),
+                _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0), float(scale))
+        tail = (num_splits, None if ws is None else ws.data_ptr(), need, stream)
+        if fp8:
+            d0 = k_descale if k_descale is not None else v_descale
+            rc = lib.fa2_fwd_decode_fp8(*head, None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
+                                        None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), *tail)
+        else:
+            rc = lib.fa2_fwd_decode(*head, *tail)
     _fa2_lib.check(rc)
     return (o, lse * _LN2) if return_lse else o
 

@@ -148,6 +148,12 @@ SYMBOLS = {
     "fa2_fwd_decode_plan": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(DecodePlan)]),
     "fa2_fwd_decode_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
     "fa2_decode_part_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    # ... on e4m3 caches: the same list with k_descale v_descale descale_strides after scale
+    "fa2_fwd_decode_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 8 + [_i64p] * 5 +
+                           [ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, _i64p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                            ctypes.c_void_p]),
+    "fa2_fwd_decode_fp8_plan": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(DecodePlan)]),
+    "fa2_fwd_decode_fp8_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
     "fa2_scoremod_eval": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 2),
     "fa2_dropout_keep_mask": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 4 + [ctypes.c_void_p]),
     "fa2_dropout_threshold": (ctypes.c_int, [ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
@@ -344,6 +350,14 @@ def decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size=0, num_splits=0):
     """fa2_fwd_decode_plan: the split, the row tiles per K / V head, the key tile and the kernel of a decode call (dtype: an FA2_DTYPE_* code)."""
     plan = DecodePlan()
     check(load().fa2_fwd_decode_plan(int(dtype), int(B), int(H), int(Hkv), int(Nq), int(D), int(capacity), int(page_size), int(num_splits), ctypes.byref(plan)))
+    return plan
+
+
+def decode_fp8_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size=0, num_splits=0):
+    """fa2_fwd_decode_fp8_plan: the plan of the call on e4m3 caches (dtype: the FA2_DTYPE_* code of q and o)."""
+    plan = DecodePlan()
+    check(load().fa2_fwd_decode_fp8_plan(int(dtype), int(B), int(H), int(Hkv), int(Nq), int(D), int(capacity), int(page_size), int(num_splits),
+                                         ctypes.byref(plan)))
     return plan
 
 

@@ -666,6 +666,32 @@ size_t fa2_fwd_decode_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, 
  * FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for capacity_keys < 0, Nq < 1, tile < 1, nsplit outside 1 .. 16 or part outside [0, nsplit). */
 int fa2_decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, int nsplit, int part, int* first_tile, int* ntiles);
 
+/* ---- ... on FP8 caches: fa2_fwd_decode with k_cache / v_cache in OCP e4m3 (gfx950's FP8: torch.float8_e4m3fn, not MI300's fnuz; no e5m2) and one f32
+ * descale per (sequence, K / V head).  `dtype` stays the dtype of q and o (f16 or bf16); the cache strides are in elements, which here are bytes.
+ *   k_descale, v_descale : f32 B x Hkv, DEVICE memory, descale_strides {batch, K / V head}; either may be null = 1.0 (both null: descale_strides may be).
+ *                          Like cache_seqlens the host never reads them: a captured call replays correctly after they changed in place.
+ * Meaning: K = float(k_cache) * k_descale[b, hkv], V = float(v_cache) * v_descale[b, hkv]; everything else — layouts, paging, masking, dead rows, the
+ * clamps, num_splits, the workspace, lse — is fa2_fwd_decode's.  Every finite e4m3 value is a f16 and a bf16 value, so the in-register conversion
+ * rounds nothing; k_descale is folded into the f32 score scale (scale * log2(e) * k_descale), v_descale multiplies the normalised f32 row before its one
+ * rounding (a split call: before the row goes to the workspace), the LSE is that of the descaled scores.  Contract 0 otherwise.
+ * e4m3 has NaN codes (0x7f, 0xff) and no Inf: keys at or beyond len still contribute nothing whatever the bytes are.  A NaN descale poisons its own
+ * (sequence, K / V head) only.  No content of any device input can move an address.
+ * Checked in this order: null pointers (block_table only when paged; descale_strides when a descale is given), sizes (as fa2_fwd_decode; a negative
+ * descale stride), head dim, alignment (16-byte q / o / caches, CACHE strides multiples of 16 — one 16-byte load covers 16 columns —, q / o strides
+ * multiples of 8, positive row strides, 4-byte lse / cache_seqlens / block_table / descales, a non-negative block-table stride), dtype, scale,
+ * FA2_ERR_GRID, and last the workspace (null, alignment, size) as in fa2_fwd_decode.
+ * Plan and workspace: the fp8 kernel sweeps the same 32-key tiles under the same split rule, so both functions answer as the 16-bit pair does; they
+ * are pure host functions of shape, capacity and CU count.  plan.key_tile is the tile the fp8 kernel uses. */
+int fa2_fwd_decode_fp8(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse,
+                       const int* cache_seqlens, const int* block_table,
+                       int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages,
+                       const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                       const int64_t lse_strides[2], int64_t block_table_stride, float scale,
+                       const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                       int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fa2_fwd_decode_fp8_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan);
+size_t fa2_fwd_decode_fp8_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits);
+
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
  * that is not a multiple of 8 has to be zero-padded by the caller (to the next multiple of 8). */

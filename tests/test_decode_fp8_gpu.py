@@ -1,0 +1,384 @@
+"""Decode attention on FP8 (e4m3) KV caches on the GPU: fa2_fwd_decode_fp8 and flash_attention_decode(k_descale=, v_descale=).
+
+The batch is tests/test_decode_gpu.py's (nine sequences: a length of 0, lengths below Nq, both sides of the 32- and 64-key tile edges, a long one).
+Every cache BYTE at or beyond a sequence's length is 0x7f, an e4m3 NaN; outputs and the workspace are pre-filled with NaN.
+
+Reference under the same contract.  Cache values are clamp(randn / d, +-448) cast to e4m3 (clamped first: torch's cast does not saturate), the
+descales d per (sequence, K / V head) powers of two from {2^-5, 2^-6, 2^-7}, so the dequantised cache is unit-scale like the 16-bit tests' data.
+Every finite e4m3 value is a f16 and a bf16 value and a power of two commutes with every rounding, so the reference is the repository's oracle,
+unchanged: fa2_oracle.fwd_c per sequence on the cache upcast to q's dtype and multiplied by k_descale (exact), its O multiplied by v_descale
+(exact).  Bars: conftest's ATOL / RTOL / LSE_TOL against the oracle, 2 * FLOOR against float64 of the dequantised values (fwd_numpy).  Before
+anything runs on the GPU, _case checks on the CPU that the oracle's own result on these inputs is within FLOOR of float64.
+General (not power-of-two) descales are held to float64 only.  The references of a shape are computed once and shared.
+No test feeds an out-of-range length or page id to the GPU."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ATOL, FLOOR, LSE_TOL, RTOL
+from oracle import fa2_oracle as fo
+from rocwmma_fattn import _fa2_lib
+from rocwmma_fattn.FlashAttn import flash_attention_decode
+
+pytestmark = pytest.mark.gpu
+
+F16, BF16, E4M3 = torch.float16, torch.bfloat16, torch.float8_e4m3fn
+LENS = (1, 63, 64, 65, 127, 129, 1000, 0, 2)
+NMAX = 1024
+SPLITS = (0, 1, 3, 16)
+LOG2E = 1.4426950408889634
+NAN_BYTE = 0x7F
+# (H, Hkv, Nq, D, dtype): one row; 4 rows; 20 rows, a ragged second tile; 48 rows, the four-tile kernel; 64 rows
+SHAPES = [(8, 8, 1, 128, F16), (8, 2, 1, 64, BF16), (10, 2, 4, 128, BF16), (16, 1, 3, 64, F16), (16, 1, 4, 128, F16)]
+IDS = ["H%d_Hkv%d_Nq%d_D%d_%s" % (s[0], s[1], s[2], s[3], "f16" if s[4] == F16 else "bf16") for s in SHAPES]
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a ROCm GPU")
+    return torch.device("cuda", 0)
+
+
+def _code(dt):
+    return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+
+
+def _s3(t):
+    return _fa2_lib.strides3(t.stride(0), t.stride(2), t.stride(1))
+
+
+def _quant(x, d):
+    """x / d as e4m3, clamped into the format's range first (torch's cast does not saturate); d broadcasts against x."""
+    return (x / d).clamp(-448.0, 448.0).to(E4M3)
+
+
+def _decode_c(q, k, v, lens, num_splits, kd=None, vd=None, block_table=None, o=None, scale=None):
+    """fa2_fwd_decode_fp8 with NaN-filled outputs and a NaN-filled workspace: every element the contract names must be written, nothing unwritten read."""
+    lib = _fa2_lib.load()
+    B, Nq, H, D = q.shape
+    Hkv = k.shape[2]
+    o = torch.full((B, Nq, H, D), float("nan"), dtype=q.dtype, device=q.device) if o is None else o
+    lse = torch.full((B, H, Nq), float("nan"), dtype=torch.float32, device=q.device)
+    if block_table is None:
+        capacity, page, pages = k.shape[1], 0, 0
+    else:
+        capacity, page, pages = block_table.shape[1], k.shape[1], k.shape[0]
+    need = lib.fa2_fwd_decode_fp8_workspace_bytes(_code(q.dtype), B, H, Hkv, Nq, D, capacity, page, num_splits)
+    ws = torch.full((max(need, 16) // 4,), float("nan"), dtype=torch.float32, device=q.device)
+    d0 = kd if kd is not None else vd
+    assert kd is None or vd is None or kd.stride() == vd.stride()
+    _fa2_lib.check(lib.fa2_fwd_decode_fp8(_code(q.dtype), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), lens.data_ptr(),
+                                          None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page, pages, _s3(q), _s3(k),
+                                          _s3(v), _s3(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0),
+                                          D ** -0.5 if scale is None else scale, None if kd is None else kd.data_ptr(), None if vd is None else vd.data_ptr(),
+                                          None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), num_splits, ws.data_ptr() if need else None,
+                                          need, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    return o, lse
+
+
+def _poison(cache8):
+    """every byte at or beyond a sequence's length: 0x7f"""
+    raw = cache8.view(torch.uint8)
+    for b, n in enumerate(LENS):
+        raw[b, n:] = NAN_BYTE
+    return cache8
+
+
+def _seq_inputs(q, k8, v8, kd, vd, b, n, Nq, G):
+    """sequence b: q [1, H, Nq, D]; f32 K * k_descale and V (no descale), V * v_descale, [1, H, n, D], heads repeated; the causal band as a bias"""
+    keep = np.arange(n)[None, :] <= (n - Nq + np.arange(Nq))[:, None]
+    bias = np.where(keep, 0.0, -np.inf).astype(np.float32)
+    qs = q[b].transpose(0, 1).unsqueeze(0).contiguous()
+    rep = lambda t: t.transpose(0, 1).repeat_interleave(G, dim=0).unsqueeze(0).contiguous()
+    one = torch.ones(k8.shape[2])
+    ks = rep(k8[b, :n].float() * (one if kd is None else kd[b])[None, :, None])
+    vraw = rep(v8[b, :n].float())
+    vs = rep(v8[b, :n].float() * (one if vd is None else vd[b])[None, :, None])
+    return qs, ks, vraw, vs, keep, bias
+
+
+@functools.lru_cache(maxsize=None)
+def _case(H, Hkv, Nq, D, dt):
+    """CPU tensors of one shape and, per sequence, the oracle's and the float64 results.  Computed once; the oracle is checked against float64 here."""
+    g = torch.Generator(device="cpu").manual_seed(1000 * H + 100 * Hkv + 10 * Nq + D + 8)
+    B = len(LENS)
+    q = torch.randn((B, Nq, H, D), generator=g).to(dt)
+    kd, vd = (2.0 ** -torch.randint(5, 8, (B, Hkv), generator=g).float() for _ in range(2))
+    k8 = _poison(_quant(torch.randn((B, NMAX, Hkv, D), generator=g), kd[:, None, :, None]))
+    v8 = _poison(_quant(torch.randn((B, NMAX, Hkv, D), generator=g), vd[:, None, :, None]))
+    code, G = _code(dt), H // Hkv
+    refs = []
+    for b, n in enumerate(LENS):
+        if n == 0:
+            refs.append(None)
+            continue
+        qs, ks, vraw, vs, keep, bias = _seq_inputs(q, k8, v8, kd, vd, b, n, Nq, G)
+        assert torch.equal(ks.to(dt).float(), ks) and torch.equal(vraw.to(dt).float(), vraw), "the upcast, descaled cache is exact in q's dtype"
+        o_bits, lse_ref = fo.fwd_c(_bits(qs), _bits(ks.to(dt)), _bits(vraw.to(dt)), code, False, bias=bias)
+        vdh = vd[b].repeat_interleave(G).numpy()[None, :, None, None]
+        o_ref = fo.bits_to_f32(o_bits, code) * vdh                                        # a power of two: exact, commutes with the oracle's rounding
+        o_true, lse_true = fo.fwd_numpy(qs.float().numpy(), ks.numpy(), vs.numpy(), False, bias=bias)
+        live = keep.any(1)
+        assert np.abs(o_ref - o_true)[:, :, live].max() <= FLOOR[code], "the oracle itself against float64 (CPU, before any GPU run)"
+        assert np.abs(lse_ref[..., live] - lse_true[..., live]).max() <= LSE_TOL
+        refs.append((o_ref, lse_ref, o_true, lse_true, ~live))
+    return q, k8, v8, kd, vd, refs
+
+
+def _check(o, lse2, refs, dt, tag, oracle=True):
+    """o [B, Nq, H, D] and the log2 lse [B, H, Nq] (device) against the shared references; dead rows exactly 0 / -inf, every element written."""
+    code = _code(dt)
+    got_o, got_l = o.float().cpu(), lse2.cpu()
+    assert torch.isfinite(got_o).all(), (tag, "O not finite: an element was not written, or a NaN byte beyond a length leaked")
+    assert not torch.isnan(got_l).any(), (tag, "LSE not written")
+    for b, ref in enumerate(refs):
+        go = got_o[b].transpose(0, 1).unsqueeze(0).numpy()
+        gl = got_l[b].unsqueeze(0).numpy()
+        if ref is None:
+            assert np.all(go == 0.0) and np.all(np.isneginf(gl)), (tag, b, "a sequence without keys")
+            continue
+        o_ref, lse_ref, o_true, lse_true, dead = ref
+        assert np.all(go[:, :, dead] == 0.0) and np.all(np.isneginf(gl[:, :, dead])), (tag, b, "rows at a negative position")
+        err_t = np.abs(go - o_true)
+        print(tag, "len", LENS[b], "float64 O err %.3g" % err_t.max(), "" if not oracle else "oracle O err %.3g" % np.abs(go - o_ref).max())
+        if oracle:
+            err_o = np.abs(go - o_ref)
+            assert np.all(err_o <= ATOL[code] + RTOL[code] * np.abs(o_ref)), (tag, b, LENS[b], "oracle O", float(err_o.max()))
+        assert err_t.max() <= 2 * FLOOR[code], (tag, b, LENS[b], "float64 O", float(err_t.max()))
+        if (~dead).any():
+            if oracle:
+                assert np.abs(gl[..., ~dead] - lse_ref[..., ~dead]).max() <= LSE_TOL, (tag, b, LENS[b], "oracle LSE")
+            assert np.abs(gl[..., ~dead] - lse_true[..., ~dead]).max() <= LSE_TOL, (tag, b, LENS[b], "float64 LSE")
+
+
+def _same_lse(a, b):
+    fa, fb = torch.isfinite(a), torch.isfinite(b)
+    return torch.equal(fa, fb) and torch.equal(a[~fa], b[~fb]) and (not fa.any() or float((a[fa] - b[fb]).abs().max()) <= LSE_TOL)
+
+
+def _all_codes():
+    """[4, 64] bytes: all 256 e4m3 codes, the two NaN codes (0x7f, 0xff) replaced by 0"""
+    codes = torch.arange(256, dtype=torch.int16).to(torch.uint8)
+    codes[codes == 0x7F] = 0
+    codes[codes == 0xFF] = 0
+    return codes.reshape(4, 64)
+
+
+@pytest.mark.parametrize("dt", [F16, BF16], ids=["f16", "bf16"])
+def test_every_v_code_exactly(dt):
+    """B4 Hkv1 H1 D64, one key per sequence whose V row holds 64 of the 256 codes: a single key has weight exactly 1, so o is the V row converted —
+    torch's e4m3fn -> q.dtype conversion bit for bit, for every code.  (One code is expected as a different bit pattern than torch's: 0x80, -0.  The
+    f32 accumulator starts at +0 and +0 + 1 * (-0) is +0 under round-to-nearest, as in the 16-bit call on a V of -0; the value is the same.)"""
+    dev = _dev()
+    nmax = 64
+    v8 = torch.full((4, nmax, 1, 64), NAN_BYTE, dtype=torch.uint8)
+    v8[:, 0, 0] = _all_codes()
+    k8 = torch.full((4, nmax, 1, 64), NAN_BYTE, dtype=torch.uint8)
+    k8[:, 0] = 0x38                                                     # 1.0
+    v8, k8 = v8.view(E4M3), k8.view(E4M3)
+    q = torch.randn((4, 1, 1, 64), generator=torch.Generator(device="cpu").manual_seed(3)).to(dt)
+    lens = torch.ones(4, dtype=torch.int32)
+    o = flash_attention_decode(q.to(dev), k8.to(dev), v8.to(dev), lens.to(dev))
+    want = v8[:, :1].to(dt)                                             # [4, 1, 1, 64] = o's shape (H = Hkv = 1)
+    assert torch.isfinite(want.float()).all()
+    want_bits = want.view(torch.int16).clone()
+    want_bits[want_bits == -32768] = 0                                  # -0 -> +0 (see above)
+    assert int((want.view(torch.int16) == -32768).sum()) == 1
+    assert torch.equal(o.cpu().view(torch.int16), want_bits), (o.cpu().view(torch.int16) != want_bits).nonzero()[:8]
+
+
+@pytest.mark.parametrize("dt", [F16, BF16], ids=["f16", "bf16"])
+def test_every_k_code_exactly(dt):
+    """The same four rows as K, 64 query heads with q[h] = e_h and scale = 1: the one score of head h is k[h] exactly, so lse[b, h, 0] = float(k[b, 0, 0, h])
+    within three f32 roundings (scale * log2e, the product, the operator's ln 2): 3 * 2^-24 = 1.8e-7 < 1e-6 relative."""
+    dev = _dev()
+    nmax = 64
+    k8 = torch.full((4, nmax, 1, 64), NAN_BYTE, dtype=torch.uint8)
+    k8[:, 0, 0] = _all_codes()
+    v8 = torch.full((4, nmax, 1, 64), NAN_BYTE, dtype=torch.uint8)
+    v8[:, 0] = 0x38
+    v8, k8 = v8.view(E4M3), k8.view(E4M3)
+    q = torch.eye(64).to(dt).reshape(1, 1, 64, 64).expand(4, 1, 64, 64).contiguous()
+    lens = torch.ones(4, dtype=torch.int32)
+    o, lse = flash_attention_decode(q.to(dev), k8.to(dev), v8.to(dev), lens.to(dev), scale=1.0, return_lse=True)
+    want = k8[:, 0, 0].double()                                          # [4, 64] = lse[:, :, 0]
+    got = lse[:, :, 0].double().cpu()
+    assert torch.isfinite(got).all()
+    assert bool(((got - want).abs() <= 1e-6 * want.abs() + 1e-30).all()), float((got - want).abs().max())
+    assert torch.equal(o.float().cpu(), torch.ones(4, 1, 64, 64))
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+def test_lengths_shapes_and_splits(shape):
+    dev = _dev()
+    H, Hkv, Nq, D, dt = shape
+    q, k8, v8, kd, vd, refs = _case(*shape)
+    qd, kk, vv, kdd, vdd = (t.to(dev) for t in (q, k8, v8, kd, vd))
+    lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
+    lse1 = None
+    for ns in SPLITS:
+        o, lse = _decode_c(qd, kk, vv, lens, ns, kdd, vdd)
+        _check(o, lse, refs, dt, (shape[:4], "splits", ns))
+        if ns == 1:
+            lse1 = lse
+        elif ns > 1:
+            assert _same_lse(lse, lse1), (shape[:4], ns, "LSE of the split against split 1")
+    # the operator: natural-log LSE, the same O bits as the C call with the plan's split
+    po, pl = flash_attention_decode(qd, kk, vv, lens, return_lse=True, k_descale=kdd, v_descale=vdd)
+    o0, l0 = _decode_c(qd, kk, vv, lens, 0, kdd, vdd)
+    assert torch.equal(po.view(torch.int16), o0.view(torch.int16)) and _same_lse(pl * LOG2E, l0)
+
+
+@pytest.mark.parametrize("which", ["both", "k_only", "v_only", "neither"])
+def test_general_descales_against_float64(which):
+    """Descales amax / 448 per (sequence, head) — not powers of two, so no same-contract oracle: float64 of the dequantised values only, 2 * FLOOR and
+    LSE_TOL.  Where a descale is left out the cache is quantised at scale 1, so the dequantised values stay unit-scale and the absolute bar means
+    what it means elsewhere."""
+    dev = _dev()
+    H, Hkv, Nq, D, dt = 8, 2, 3, 64, BF16
+    G, B = H // Hkv, len(LENS)
+    g = torch.Generator(device="cpu").manual_seed(41)
+    q = torch.randn((B, Nq, H, D), generator=g).to(dt)
+    xk, xv = (torch.randn((B, NMAX, Hkv, D), generator=g) for _ in range(2))
+
+    def descale(x):
+        d = torch.ones(B, Hkv)
+        for b, n in enumerate(LENS):
+            if n:
+                d[b] = x[b, :n].abs().amax(dim=(0, 2)) / 448.0
+        return d
+
+    kd = descale(xk) if which in ("both", "k_only") else None
+    vd = descale(xv) if which in ("both", "v_only") else None
+    one = torch.ones(B, 1, Hkv, 1)
+    k8 = _poison(_quant(xk, one if kd is None else kd[:, None, :, None]))
+    v8 = _poison(_quant(xv, one if vd is None else vd[:, None, :, None]))
+    refs = []
+    for b, n in enumerate(LENS):
+        if n == 0:
+            refs.append(None)
+            continue
+        qs, ks, _, vs, keep, bias = _seq_inputs(q, k8, v8, kd, vd, b, n, Nq, G)
+        o_true, lse_true = fo.fwd_numpy(qs.float().numpy(), ks.numpy(), vs.numpy(), False, bias=bias)
+        refs.append((None, None, o_true, lse_true, ~keep.any(1)))
+    lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
+    for ns in (0, 3):
+        o, lse = flash_attention_decode(q.to(dev), k8.to(dev), v8.to(dev), lens, return_lse=True, num_splits=ns,
+                                        k_descale=None if kd is None else kd.to(dev), v_descale=None if vd is None else vd.to(dev))
+        _check(o, lse * LOG2E, refs, dt, (which, ns), oracle=False)
+
+
+def _paged(k, v, page, g, spare=3):
+    """The [B, NMAX, Hkv, D] caches scattered into pages in shuffled physical order; spare pages and the pages no sequence uses hold 0x7f bytes, and
+    block-table entries beyond a sequence's used pages point at such a page."""
+    B, per = k.shape[0], NMAX // page
+    used = [-(-n // page) for n in LENS]
+    total = sum(used) + spare
+    order = torch.randperm(total, generator=g).tolist()
+    pk = torch.full((total, page) + tuple(k.shape[2:]), NAN_BYTE, dtype=torch.uint8)
+    pv = torch.full_like(pk, NAN_BYTE)
+    bt = torch.full((B, per), order[-1], dtype=torch.int32)
+    nxt = 0
+    for b in range(B):
+        for j in range(used[b]):
+            pid = order[nxt]
+            nxt += 1
+            pk[pid] = k.view(torch.uint8)[b, j * page:(j + 1) * page]
+            pv[pid] = v.view(torch.uint8)[b, j * page:(j + 1) * page]
+            bt[b, j] = pid
+    return pk.view(E4M3), pv.view(E4M3), bt
+
+
+@pytest.mark.parametrize("page", [64, 128])
+@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2]], ids=[IDS[1], IDS[2]])
+def test_paged_is_bit_identical_to_contiguous(shape, page):
+    dev = _dev()
+    q, k8, v8, kd, vd, refs = _case(*shape)
+    pk, pv, bt = _paged(k8, v8, page, torch.Generator(device="cpu").manual_seed(page))
+    qd, lens = q.to(dev), torch.tensor(LENS, dtype=torch.int32, device=dev)
+    kk, vv, pkd, pvd, btd, kdd, vdd = (t.to(dev) for t in (k8, v8, pk, pv, bt, kd, vd))
+    for ns in SPLITS[1:]:
+        o, lse = _decode_c(qd, kk, vv, lens, ns, kdd, vdd)
+        po, plse = _decode_c(qd, pkd, pvd, lens, ns, kdd, vdd, block_table=btd)
+        assert torch.equal(po.view(torch.int16), o.view(torch.int16)) and torch.equal(plse, lse), (shape[:4], page, ns)
+    po, plse = _decode_c(qd, pkd, pvd, lens, 0, kdd, vdd, block_table=btd)
+    _check(po, plse, refs, shape[4], (shape[:4], "paged", page))
+    oo = flash_attention_decode(qd, pkd, pvd, lens, block_table=btd, k_descale=kdd, v_descale=vdd)
+    assert torch.equal(oo.view(torch.int16), po.view(torch.int16))
+
+
+@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[4]], ids=[IDS[1], IDS[4]])
+def test_strided_views_are_bit_identical(shape):
+    dev = _dev()
+    H, Hkv, Nq, D, dt = shape
+    q, k8, v8, kd, vd, _ = _case(*shape)
+    B = q.shape[0]
+    qd, kk, vv = q.to(dev), k8.to(dev), v8.to(dev)
+    lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
+    qw = torch.full((B, Nq, H + 2, D), float("nan"), dtype=dt, device=dev)
+    qw[:, :, :H] = qd
+    kw = torch.full((B, NMAX + 48, Hkv + 1, D), NAN_BYTE, dtype=torch.uint8, device=dev)       # a padded Nmax stride and a padded head stride
+    kw[:, :NMAX, :Hkv] = kk.view(torch.uint8)
+    kview = kw.view(E4M3)[:, :NMAX, :Hkv]
+    dw = torch.full((B, 2 * Hkv + 1), float("nan"), device=dev)                                # strided descales: every other element of a wider row
+    dk, dv = dw[:, 0:2 * Hkv:2], torch.full((B, 2 * Hkv + 1), float("nan"), device=dev)[:, 0:2 * Hkv:2]
+    dk.copy_(kd)
+    dv.copy_(vd)
+    assert not kview.is_contiguous() and not dk.is_contiguous() and dk.stride() == dv.stride()
+    for ns in (1, 3):
+        o, lse = _decode_c(qd, kk, vv, lens, ns, kd.to(dev), vd.to(dev))
+        ow = torch.full((B, Nq, H + 2, D), float("nan"), dtype=dt, device=dev)
+        so, slse = _decode_c(qw[:, :, :H], kview, vv, lens, ns, dk, dv, o=ow[:, :, :H])
+        assert torch.equal(so.view(torch.int16), o.view(torch.int16)) and torch.equal(slse, lse), (shape[:4], ns)
+        assert torch.isnan(ow[:, :, H:]).all(), "the call wrote outside its view of o"
+        po, pl = flash_attention_decode(qw[:, :, :H], kview, vv, lens, return_lse=True, num_splits=ns, k_descale=dk, v_descale=dv)
+        assert torch.equal(po.view(torch.int16), o.view(torch.int16)), (shape[:4], ns, "flash_attention_decode")
+        assert _same_lse(pl * LOG2E, lse)
+
+
+@pytest.mark.parametrize("ns", [0, 3])
+def test_graph_replay_follows_lengths_and_descales_changed_in_place(ns):
+    """The host reads neither cache_seqlens nor the descales: one captured call, replayed after all three were overwritten in place, gives the eager
+    result for the contents at that time (a fully valid cache here, so that every permutation of the lengths is a legal call)."""
+    dev = _dev()
+    H, Hkv, Nq, D, dt = 8, 2, 3, 128, F16
+    B = len(LENS)
+    g = torch.Generator(device="cpu").manual_seed(78)
+    q = torch.randn((B, Nq, H, D), generator=g).to(dt).to(dev)
+    k8, v8 = (_quant(torch.randn((B, NMAX, Hkv, D), generator=g), 2.0 ** -5).to(dev) for _ in range(2))
+    sets = []
+    for i in range(2):
+        lens_i = torch.tensor(LENS[3 * i:] + LENS[:3 * i], dtype=torch.int32, device=dev)
+        kd_i, vd_i = ((2.0 ** -5 * (1.0 + torch.rand((B, Hkv), generator=g))).to(dev) for _ in range(2))
+        sets.append((lens_i, kd_i, vd_i))
+    want = [tuple(t.clone() for t in flash_attention_decode(q, k8, v8, s[0], return_lse=True, num_splits=ns, k_descale=s[1], v_descale=s[2])) for s in sets]
+    assert not torch.equal(want[0][0], want[1][0])
+    lens, kd, vd = (t.clone() for t in sets[0])
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        flash_attention_decode(q, k8, v8, lens, return_lse=True, num_splits=ns, k_descale=kd, v_descale=vd)           # warm-up outside the capture
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            go, gl = flash_attention_decode(q, k8, v8, lens, return_lse=True, num_splits=ns, k_descale=kd, v_descale=vd)
+    torch.cuda.current_stream().wait_stream(side)
+    for i in (0, 1, 0):
+        lens.copy_(sets[i][0])
+        kd.copy_(sets[i][1])
+        vd.copy_(sets[i][2])
+        go.zero_()
+        gl.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(go.view(torch.int16), want[i][0].view(torch.int16)) and torch.equal(gl, want[i][1])

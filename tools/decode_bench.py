@@ -1,7 +1,7 @@
 """KV-cache decode attention: flash_attention_decode against the routes the library had before it, same box, interleaved rounds, median of
 per-round event times with the spread of the rounds beside it (tools/gqa_bench.py practice).
 
-    python tools/decode_bench.py [--rounds R] [--iters I] [--rows uniform|ragged|all]
+    python tools/decode_bench.py [--rounds R] [--iters I] [--rows uniform|ragged|fp8|all]
 
 Uniform rows (every sequence has the same length, so the older entry points can serve the call at all):
     decode  flash_attention_decode(q, k_cache, v_cache, cache_seqlens) on a [B, Nmax, Hkv, D] cache with Nmax above the length
@@ -12,6 +12,13 @@ Ragged rows (B sequences with lengths drawn from 256 .. 8192):
     varlen        flash_attention_varlen(causal=True, bottom_right=True) on a packed copy of the valid keys made OUTSIDE the timed region
     varlen+copy   ... with the packing (one torch.cat of the per-sequence slices per tensor) inside it: what serving a cache through it costs per step
     padmask       flash_attention(mask = key padding [B, 1, 1, Nmax]) on the padded cache
+FP8 rows (--rows fp8): the e4m3 cache with per (sequence, K / V head) descales beside the 16-bit call on the same shape and the
+same (dequantised) values, in the same interleaved protocol:
+    bf16 / fp16   flash_attention_decode on the 16-bit cache — the route the library had
+    fp8           flash_attention_decode(k_descale=, v_descale=) on the e4m3 cache: half the bytes
+    dequant+call  (one row) the whole e4m3 cache dequantised to the 16-bit dtype inside the timed region, then the 16-bit call: what a holder of
+                  such a cache had to do per step before
+Each route's TB/s is of ITS OWN valid bytes, and the floor is printed for both cache widths.
 Every row prints the K + V bytes that are valid (what a perfect kernel has to read) and the time they take at 6.3 TB/s, the achievable HBM rate.
 Each row first checks the routes against each other on the timed inputs (fp16 1e-3 + 2e-3 |x|, bf16 8e-3 + 1.6e-2 |x|): faster and different is not faster.
 The same K / V are read in every iteration, so caches up to the 256 MB of Infinity Cache are served from it in every route alike.
@@ -101,6 +108,84 @@ def uniform_row(label, B, H, Hkv, Nq, keys, D, dt, rounds, iters):
     report(label, shape, t, 2 * B * Hkv * keys * D * 2, "dense")
 
 
+FP8_UNIFORM = [r for r in UNIFORM if r[0] in ("b32_hkv8_bf16", "b8_hkv8_nq4", "b1_hkv8")]
+FP8_DEQUANT_ROW = "b32_hkv8_bf16"
+
+
+def report_fp8(label, shape, t, bytes16, base):
+    """rows of an fp8 comparison: every route against `base` (the 16-bit call), TB/s of the route's own valid bytes (fp8: half)"""
+    print("%-14s %s  valid K+V %.1f MB = %.1f us (16-bit) / %.1f MB = %.1f us (e4m3) at %.1f TB/s"
+          % (label, shape, bytes16 / 1e6, bytes16 / (HBM_TBS * 1e12) * 1e6, bytes16 / 2e6, bytes16 / 2 / (HBM_TBS * 1e12) * 1e6, HBM_TBS))
+    b_med, b_lo, b_hi = t[base]
+    for n, (med, lo, hi) in t.items():
+        own = bytes16 // 2 if n.startswith("fp8") else bytes16
+        rel = ""
+        if n != base:
+            real = abs(b_med - med) > (hi - lo) + (b_hi - b_lo)          # the project's rule: a difference beyond the sum of the two spreads
+            rel = "  %.2fx %s than %s (%s the sum of the spreads, %.1f us)" % (max(b_med / med, med / b_med), "faster" if med <= b_med else "SLOWER", base,
+                                                                              "beyond" if real else "WITHIN", ((hi - lo) + (b_hi - b_lo)) * 1e3)
+        print("    %-12s %9.1f us  (rounds %.1f .. %.1f, spread %.1f %%)  %5.2f TB/s of its valid K+V%s"
+              % (n, med * 1e3, lo * 1e3, hi * 1e3, 100.0 * (hi - lo) / med, own / (med * 1e-3) / 1e12, rel))
+    sys.stdout.flush()
+
+
+def quantise(x, g):
+    """unit-scale x [B, N, Hkv, D] -> (e4m3 cache, descale [B, Hkv] of powers of two, the dequantised values in x's dtype — exact)"""
+    B, Hkv = x.shape[0], x.shape[2]
+    d = (2.0 ** -torch.randint(5, 8, (B, Hkv), generator=g).float()).to(x.device)
+    x8 = (x.float() / d[:, None, :, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return x8, d, (x8.float() * d[:, None, :, None]).to(x.dtype)
+
+
+def fp8_uniform_row(label, B, H, Hkv, Nq, keys, D, dt, rounds, iters):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(2)
+    nmax = keys + 256
+    name16 = "fp16" if dt == torch.float16 else "bf16"
+    q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
+    (k8, kd, kc), (v8, vd, vc) = (quantise(torch.randn((B, nmax, Hkv, D), device=dev, dtype=dt), g) for _ in range(2))
+    lens = torch.full((B,), keys, dtype=torch.int32, device=dev)
+    fns = {name16: lambda: flash_attention_decode(q, kc, vc, lens),
+           "fp8": lambda: flash_attention_decode(q, k8, v8, lens, k_descale=kd, v_descale=vd)}
+    if label == FP8_DEQUANT_ROW:
+        dq = lambda x8, d: x8.to(dt) * d[:, None, :, None].to(dt)  # noqa: E731
+        fns["dequant+call"] = lambda: flash_attention_decode(q, dq(k8, kd), dq(v8, vd), lens)
+    with torch.no_grad():
+        for n in fns:
+            close(fns[n](), fns[name16](), dt, label + ": %s and %s" % (n, name16))
+        t = interleaved(fns, rounds, iters)
+    plan = _fa2_lib.decode_fp8_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, nmax)
+    shape = "B%d H%d Hkv%d Nq%d keys %d D%d %s (split %d, key tile %d)" % (B, H, Hkv, Nq, keys, D, name16, plan.nsplit, plan.key_tile)
+    report_fp8(label + "_fp8", shape, t, 2 * B * Hkv * keys * D * 2, name16)
+
+
+def fp8_ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    lens_h = torch.randint(lo, hi + 1, (B,), generator=g).tolist()
+    name16 = "fp16" if dt == torch.float16 else "bf16"
+    q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
+    (k8, kd, kc), (v8, vd, vc) = (quantise(torch.randn((B, hi, Hkv, D), device=dev, dtype=dt), g) for _ in range(2))
+    lens = torch.tensor(lens_h, dtype=torch.int32, device=dev)
+    p16 = paged(kc, vc, lens_h, 64, torch.Generator(device="cpu").manual_seed(3))
+    p8 = paged(k8.view(torch.uint8), v8.view(torch.uint8), lens_h, 64, torch.Generator(device="cpu").manual_seed(3))
+    pk8, pv8 = p8[0].view(torch.float8_e4m3fn), p8[1].view(torch.float8_e4m3fn)
+    fns = {name16: lambda: flash_attention_decode(q, kc, vc, lens),
+           "fp8": lambda: flash_attention_decode(q, k8, v8, lens, k_descale=kd, v_descale=vd),
+           name16 + "_pg64": lambda: flash_attention_decode(q, p16[0], p16[1], lens, block_table=p16[2]),
+           "fp8_pg64": lambda: flash_attention_decode(q, pk8, pv8, lens, block_table=p8[2], k_descale=kd, v_descale=vd)}
+    with torch.no_grad():
+        for n in fns:
+            close(fns[n](), fns[name16](), dt, label + ": %s and %s" % (n, name16))
+        t = interleaved(fns, rounds, max(1, iters // 2))
+    plan = _fa2_lib.decode_fp8_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, hi)
+    shape = "B%d H%d Hkv%d Nq%d keys %d .. %d (mean %d) D%d %s (split %d, key tile %d)" % (B, H, Hkv, Nq, min(lens_h), max(lens_h), sum(lens_h) // B, D, name16,
+                                                                                          plan.nsplit, plan.key_tile)
+    bytes16 = 2 * Hkv * sum(lens_h) * D * 2
+    report_fp8(label + "_fp8", shape, {n: t[n] for n in (name16, "fp8")}, bytes16, name16)
+    report_fp8(label + "_fp8_pg64", shape, {n: t[n] for n in (name16 + "_pg64", "fp8_pg64")}, bytes16, name16 + "_pg64")
+
+
 def paged(kc, vc, lens, page, g):
     B, nmax = kc.shape[0], kc.shape[1]
     used = [-(-n // page) for n in lens]
@@ -159,7 +244,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--rows", default="all", choices=("uniform", "ragged", "all"))
+    ap.add_argument("--rows", default="all", choices=("uniform", "ragged", "fp8", "all"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
@@ -169,6 +254,10 @@ def main():
             uniform_row(*r, a.rounds, a.iters)
     if a.rows in ("ragged", "all"):
         ragged_row(*RAGGED, a.rounds, a.iters)
+    if a.rows in ("fp8", "all"):
+        for r in FP8_UNIFORM:
+            fp8_uniform_row(*r, a.rounds, a.iters)
+        fp8_ragged_row(*RAGGED, a.rounds, a.iters)
 
 
 if __name__ == "__main__":
