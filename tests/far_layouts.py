@@ -6,7 +6,11 @@ slices past byte offsets 2^31 and 2^32, run the call, copy the views out, poison
 and quads of 0xFF bytes are NaN in fp16, bf16 and f32: a read outside the views poisons its result, a write outside them stays in the arena.
 
 This module is plain geometry and comparisons, independent of the device: the CPU test builds the same layouts on device "meta" to prove that they
-cross what they claim, and feeds the checker mutants on small tensors."""
+cross what they claim, and feeds the checker mutants on small tensors.
+
+Case tables: DENSE_CASES, SPAN_CASES, BIAS_SPAN_CASES, PACKED_CASES, F32_CASES (dense, windowed, dropout, biased, packed calls), SCOREMOD_CASES
+(score modifiers: slopes with a far batch stride), LSE_CASES (a dlse slot with strides of its own), MERGE_CASES (parts of one far stride set),
+DECODE_CASES (16-bit and e4m3 caches: far batches, far heads, a wide key row pitch, paged pools)."""
 import numpy as np
 import torch
 
@@ -253,13 +257,13 @@ ASM_DEFAULT = 1987                                                            # 
 
 
 def _case(id, fam="dense", dt="f16", B=None, H=None, Hkv=None, Nq=320, Nkv=None, D=64, causal=False, far="batch", bwd=False, opts=None, expect=None,
-          ws=None, window=None, p=0.0, bias=None, layout="far", expect_bwd=None, form=None):
+          ws=None, window=None, p=0.0, bias=None, layout="far", expect_bwd=None, form=None, softcap=0.0, slopes=False, dlse=None):
     if B is None:
         B = 3 if far == "batch" else 1
     if H is None:
         H = 2 if far == "batch" else 3
     return dict(id="%s-%s" % (id, far or layout), fam=fam, dt=dt, B=B, H=H, Hkv=Hkv or H, Nq=Nq, Nkv=Nkv or Nq, D=D, causal=causal, far=far, bwd=bwd,
-                opts=opts or {}, expect=expect, ws=ws, window=window, p=p, seed=0x5EED0000 + D, bias=bias, layout=layout, expect_bwd=expect_bwd, form=form)
+                opts=opts or {}, expect=expect, ws=ws, window=window, p=p, seed=0x5EED0000 + D, bias=bias, layout=layout, expect_bwd=expect_bwd, form=form, softcap=softcap, slopes=slopes, dlse=dlse)
 
 
 def _both(*a, **kw):
@@ -317,10 +321,13 @@ def dense_specs(case):
     if case["bias"]:
         kind, shape = case["bias"]
         specs.append(("bias", BIAS_DTYPES[kind] or dt, shape, shape[3], "batch"))
+    if case.get("dlse"):                                             # the gradient of the LSE: strides of its own — far like the rest, or compact
+        specs.append(("dlse", torch.float32, (B, H, Nq), None) + ((None,) if case["dlse"] == "compact" else ()))
     return specs
 
 
 WS_FAR_OFFSET = 2 * FAR_STEP + 128 * MIB        # a workspace past 4 GiB
+SLOPES_OFFSET = 48 * MIB + 5 * 4096 + 16        # ALiBi slopes: behind the first slices too
 WS_NEAR_OFFSET = 192 * MIB                      # ... and one behind the first slices (validate() proves that nothing else is there)
 
 
@@ -328,6 +335,9 @@ def dense_slots(case, ws_bytes=0, step=FAR_STEP):
     """-> (far slots, twin slots, bytes of the twin's buffer).  The workspace of a split call is a flat slot of the far layout (scratch: poisoned
     again like every view); the twin gets one of its own."""
     slots = place(dense_specs(case), case["far"], step=step, gap=32768)
+    if case.get("slopes"):                                           # ALiBi slopes: [B, H] with a far batch stride, or one shared [H] vector (B = 1: stride 0)
+        B, H = case["B"], case["H"]
+        slots["slopes"] = Slot("slopes", torch.float32, (B, H), (step // 4 if B > 1 else H, 1), SLOPES_OFFSET)
     twin, tbytes = twin_of(slots)
     if ws_bytes:
         at = WS_FAR_OFFSET if case["ws"] == "far" else WS_NEAR_OFFSET
@@ -350,10 +360,17 @@ PACKED_CASES = [
     dict(id="varlen_topleft", H=2, Hkv=2, D=128, dt="f16", causal=True, bottom_right=False, p=0.0, bwd=True),
     dict(id="varlen_dropout_gqa", H=4, Hkv=2, D=64, dt="f16", causal=True, bottom_right=True, p=0.25, bwd=False),
     dict(id="varlen_dropout", H=2, Hkv=2, D=64, dt="f16", causal=False, bottom_right=False, p=0.25, bwd=True),
+    # score modifiers (fa2_fwd_varlen_scoremod / fa2_bwd_varlen_scoremod): slopes [num_sequences, H], the last sequences' vectors past byte 2^31
+    dict(id="varlen_smod_gqa_topleft", H=4, Hkv=2, D=64, dt="f16", causal=True, bottom_right=False, p=0.0, bwd=False, softcap=30.0, slopes=True),
+    dict(id="varlen_smod_bottomright", H=2, Hkv=2, D=64, dt="bf16", causal=True, bottom_right=True, p=0.0, bwd=True, softcap=30.0, slopes=True),
+    # a gradient for the LSE (fa2_bwd_varlen_lse): dlse [H, total] far like the LSE; bottom-right rows without a visible key carry a NaN in it
+    dict(id="varlen_lse", H=2, Hkv=2, D=64, dt="f16", causal=True, bottom_right=True, p=0.0, bwd=True, dlse=True),
 ]
 for _c in PACKED_CASES:
     _c["seed"] = 0x5EED1000 + _c["D"]
 PACKED_LSE_OFFSET = (1 << 32) + 3 * 4096 + 512 * 1024      # LSE and delta [H, total] far too, in the gap between two rows' columns
+PACKED_SLOPES_OFFSET = 576 * 1024                          # ALiBi slopes [num_sequences, H]: in the gaps as well, ...
+PACKED_SLOPES_STEP = 384 * MIB + 3 * 4096                  # ... the sequences' vectors this many bytes apart: the last two lie past 2^31
 
 
 def packed_slots(case):
@@ -363,11 +380,15 @@ def packed_slots(case):
     if case["bwd"]:
         specs += [("do", dt, (T, H, D)), ("dq", dt, (T, H, D)), ("dk", dt, (T, Hkv, D)), ("dv", dt, (T, Hkv, D))]
         flat.append("delta")
+    if case.get("dlse"):
+        flat.append("dlse")
     slots = place_rows(specs, PACKED_PITCH_BYTES)
     at = PACKED_LSE_OFFSET
     for name in flat:
         slots[name] = Slot(name, torch.float32, (H, T), (T, 1), at)
         at += _up(H * T * 4, 4096) + 4096
+    if case.get("slopes"):
+        slots["slopes"] = Slot("slopes", torch.float32, (len(PACKED_LENS), H), (PACKED_SLOPES_STEP // 4, 1), PACKED_SLOPES_OFFSET)
     twin, tbytes = twin_of(slots, keep_pitch=False)
     return slots, twin, tbytes
 
@@ -486,4 +507,316 @@ F32_STEP = (1 << 32) + 3 * 4096                  # bytes: batch 1 sits at float 
 F32_CASES = [
     _case("f32_lse_delta", D=128, Nq=320, bwd=True, far="batch", expect_bwd=("asm", "asm")),
     _case("f32_bias", fam="bias", B=3, H=2, D=64, Nq=256, bwd=True, bias=("f32", (3, 1, 256, 256)), far="batch", expect="bias", form="tile"),
+    # dlse and the ALiBi slopes at a float index past 2^31 (the slopes' batch stride is the step too); dead rows carry a NaN in dlse
+    _case("f32_dlse_slopes", fam="scoremod", D=64, Nq=320, Nkv=256, causal=True, window=W100, softcap=30.0, slopes=True, bwd=True, far="batch", dlse="far"),
 ]
+
+# ---- score modifiers (fa2_fwd_scoremod / fa2_bwd_scoremod): soft-capping at 30 and ALiBi slopes on the causal window W100.  Batch-far cases: slopes
+# [B, H] whose batch stride is FAR_STEP bytes (b * alibi_batch_stride + h); head-far cases: one shared [H] vector, stride 0.
+SCOREMOD_CASES = (
+    [c for D in (64, 128) for c in _both("smod_d%d" % D, fam="scoremod", D=D, Nq=320, causal=True, window=W100, softcap=30.0, slopes=True, bwd=True)] +
+    [_case("smod_gqa", fam="scoremod", B=1, H=6, Hkv=3, D=64, Nq=320, causal=True, far="head", window=W100, softcap=30.0, slopes=True)]
+)
+# ---- a gradient for the LSE (fa2_bwd_lse, fa2_bwd_window_lse): a dlse slot with strides of its own, far like lse, or compact beside far tensors.
+# The windowed cases have 256 keys for 320 rows at q_offset 64: rows 292 .. 319 see no key, carry a NaN in dlse and must get zero gradients.
+LSE_CASES = (
+    [_case("lse_d64", D=64, Nq=320, bwd=True, far="batch", dlse="far", expect_bwd=("hip", "hip")),
+     _case("lse_d64", D=64, Nq=320, bwd=True, far="head", dlse="compact", expect_bwd=("hip", "hip"))] +
+    # head dim 128 with a dlse leaves the hand-scheduled passes (fa2_bwd_lse_plan)
+    _both("lse_d128", dt="bf16", D=128, Nq=320, causal=True, bwd=True, dlse="far", expect_bwd=("hip", "hip")) +
+    [_case("lse_bias", fam="bias", B=3, H=2, D=64, Nq=256, bwd=True, bias=("f32", (3, 1, 256, 256)), far="batch", dlse="far", expect="bias", form="tile"),
+     # fa2_bwd_window_lse on each of its routes: the windowed, the dropout and the score-modifier backward
+     _case("lse_window", fam="window", D=64, Nq=320, Nkv=256, causal=True, window=W100, bwd=True, far="batch", dlse="far", expect="window"),
+     _case("lse_dropout", fam="dropout", dt="bf16", D=128, Nq=320, Nkv=256, causal=True, window=W100, p=0.25, bwd=True, far="head", dlse="far"),
+     _case("lse_smod", fam="scoremod", D=128, Nq=320, Nkv=256, causal=True, window=W100, softcap=30.0, slopes=True, bwd=True, far="batch", dlse="compact")]
+)
+
+
+# ---- KV-cache decode (fa2_fwd_decode, fa2_fwd_decode_fp8): the header states no span limit, so every product of the kernel must be 64-bit — page id
+# times page stride, batch times batch stride, key row times row pitch, the block table's and the descales' batch strides.  Tensors are the
+# operator's: q / o [B, Nq, H, D], caches [B, Nmax, Hkv, D] or [num_pages, page, Hkv, D], lse [B, H, Nq].  fmt "16": caches of the I/O dtype;
+# "fp8": e4m3 bytes in the SAME byte layout, so that an element index is a byte offset and passes 2^31 and 2^32 where the bytes do.
+# Cache rows at or beyond a length, unused pages and the workspace stay poison: 0xFFFF is NaN in fp16 and bf16, 0xFF an e4m3 NaN, 0xFFFFFFFF a f32 NaN.
+E4M3 = torch.float8_e4m3fn
+DECODE_NMAX = 1024
+DECODE_WIDE_NMAX = 1008
+DECODE_WIDE_PITCH = 4 * MIB + 77 * 4096           # bytes of a key row: 1000 valid keys span 4.2 GiB, the 1008 rows of the capacity fit the arena
+DECODE_PAGE_STRIDE = 64 * MIB + 5 * 4096          # bytes from page to page
+DECODE_POOL_BASE = 8 * MIB                        # page 0 (the compact tensors of the case lie in front of it)
+DECODE_NUM_PAGES = 68                             # pages 0 .. 31 end below 2^31, 32 .. 63 lie between 2^31 and 2^32, 64 .. 67 past 2^32
+
+
+def _dcase(id, layout, dt, D, H, Hkv, Nq, lens, rt, page=0, bt=None, descale="kv"):
+    """descale: which of k_descale / v_descale the FP8 call is given ("kv", "k", "v")."""
+    return dict(id=id, layout=layout, dt=dt, D=D, H=H, Hkv=Hkv, Nq=Nq, lens=tuple(lens), B=len(lens), rt=rt, page=page, bt=bt, descale=descale,
+                nmax=DECODE_WIDE_NMAX if layout == "wide" else DECODE_NMAX, seed=0x5EED5000 + 131 * D + 17 * H + Nq + page)
+
+
+DECODE_CASES = [
+    # batches FAR_STEP bytes apart: q, o, lse, both caches, the descales.  Rows per K / V head 1, 20 and 64: the kernels of 1, 2 and 4 row tiles
+    _dcase("decode_batch_rt1", "batch", "f16", 128, 8, 8, 1, (129, 65, 1000), 1),
+    _dcase("decode_batch_rt2", "batch", "bf16", 64, 10, 2, 4, (2, 1000, 65), 2, descale="v"),
+    _dcase("decode_batch_rt4", "batch", "bf16", 128, 16, 1, 4, (1000, 0, 129), 4),
+    # three K / V heads FAR_STEP bytes apart, the query heads of q, o and lse far too (six of them: the last lies past 2^32)
+    _dcase("decode_head_rt1", "head", "bf16", 128, 3, 3, 1, (129,), 1),
+    _dcase("decode_head_rt2", "head", "f16", 64, 6, 3, 10, (1000,), 2, descale="k"),
+    # one sequence whose key rows are 4.3 MiB apart, K and V interleaved inside the pitch
+    _dcase("decode_wide_row", "wide", "f16", 128, 16, 1, 4, (1000,), 4),
+    # paged: pages 64 MiB + 20 KiB apart, every sequence with keys takes pages of all three regions; the block table's rows far / compact
+    _dcase("decode_paged64", "paged", "f16", 128, 10, 2, 4, (1000, 0, 129), 2, page=64, bt="far"),
+    _dcase("decode_paged128", "paged", "bf16", 64, 16, 1, 4, (300, 1000, 0), 4, page=128, bt="compact", descale="k"),
+]
+DECODE_FORMATS = ("16", "fp8")
+DECODE_F32_CASE = DECODE_CASES[6]                 # runs in the f32 arena too, batch stride F32_STEP: b * stride of lse, descales and block table past element 2^31
+
+
+def _bslot(name, dtype, shape, byte_strides, offset):
+    """A slot from BYTE strides of the leading dimensions (the last one is contiguous)."""
+    es = torch.empty((), dtype=dtype).element_size()
+    assert all(s % es == 0 for s in byte_strides)
+    return Slot(name, dtype, shape, tuple(s // es for s in byte_strides) + (1,), offset)
+
+
+def decode_page_regions(case, fmt):
+    """Page ids whose K and V blocks end below byte 2^31, lie between 2^31 and 2^32, start past 2^32."""
+    block = 2 * (_up(case["page"] * case["Hkv"] * case["D"] * (1 if fmt == "fp8" else 2), 4096) + 4096)
+    at = [DECODE_POOL_BASE + p * DECODE_PAGE_STRIDE for p in range(DECODE_NUM_PAGES)]
+    low = [p for p, a in enumerate(at) if a + block <= 1 << 31]
+    mid = [p for p, a in enumerate(at) if a > 1 << 31 and a + block <= 1 << 32]
+    high = [p for p, a in enumerate(at) if a > 1 << 32]
+    assert len(low) + len(mid) + len(high) == DECODE_NUM_PAGES
+    return low, mid, high
+
+
+def decode_block_tables(case, fmt):
+    """-> (far block table [B, max_pages], twin block table, far poison page, twin page count): every sequence with keys takes one page of each region
+    and the rest from below 2^32, in an order shuffled with the case's seed; entries beyond a sequence's pages name a page nobody wrote (a valid id,
+    past 2^32).  The twin numbers its own small pool, in another shuffled order."""
+    rng = np.random.RandomState(case["seed"] & 0xFFFF)
+    page, per = case["page"], DECODE_NMAX // case["page"]
+    low, mid, high = (list(rng.permutation(r)) for r in decode_page_regions(case, fmt))
+    used = [-(-n // page) for n in case["lens"]]
+    poison = int(high.pop())
+    total_t = sum(used) + 1
+    order_t = list(rng.permutation(total_t))
+    bt, bt_t = np.full((case["B"], per), poison, dtype=np.int32), np.full((case["B"], per), int(order_t.pop()), dtype=np.int32)
+    for b, n in enumerate(used):
+        if n == 0:
+            continue
+        assert n >= 3, "a sequence with keys needs a page of each region"
+        mine = [high.pop(), mid.pop(), low.pop()]
+        rest = low + mid
+        take = list(rng.permutation(len(rest))[:n - 3])
+        mine += [rest[i] for i in take]
+        low, mid = [p for p in low if p not in mine], [p for p in mid if p not in mine]
+        bt[b, :n] = rng.permutation(mine)
+        bt_t[b, :n] = [order_t.pop() for _ in range(n)]
+    return bt, bt_t, poison, total_t
+
+
+def decode_slots(case, fmt, ws_bytes=0, ws="near", step=FAR_STEP):
+    """-> (far slots, twin slots, bytes of the twin's buffer).  Slots: q k v o lse lens, bt (paged), kd / vd (fp8, as the case's `descale` says), ws
+    (a split call).  The twin: the same shapes, compact, in a buffer of its own; a paged twin is a small pool of its own numbering.
+    step: the batch stride in bytes of the batch-far tensors (F32_STEP in the f32 arena: lse, the descales and the block table at ELEMENT indices past 2^31)."""
+    io, fp8 = DTYPES[case["dt"]], fmt == "fp8"
+    cdt, ces = (E4M3, 1) if fp8 else (io, 2)
+    B, H, Hkv, Nq, D, N, lay = case["B"], case["H"], case["Hkv"], case["Nq"], case["D"], case["nmax"], case["layout"]
+    i32, f32 = torch.int32, torch.float32
+    names = ["q", "k", "v", "o", "lse", "lens"] + (["bt"] if lay == "paged" else []) + (["kd", "vd"] if fp8 else [])
+    if fp8:
+        names = [n for n in names if n not in {"kv": (), "k": ("vd",), "v": ("kd",)}[case["descale"]]]
+    # compact shapes and byte strides (the twin's, and the inner dimensions of the far layouts)
+    cshape = (DECODE_NUM_PAGES, case["page"], Hkv, D) if lay == "paged" else (B, N, Hkv, D)
+    shapes = dict(q=(B, Nq, H, D), o=(B, Nq, H, D), k=cshape, v=cshape, lse=(B, H, Nq), lens=(B,), kd=(B, Hkv), vd=(B, Hkv), bt=(B, DECODE_NMAX // max(case["page"], 1)))
+    dts = dict(q=io, o=io, k=cdt, v=cdt, lse=f32, lens=i32, kd=f32, vd=f32, bt=i32)
+
+    def compact(shape, es):
+        st = [es]
+        for n in reversed(shape[1:]):
+            st.insert(0, st[0] * n)
+        return st[:-1]
+
+    slots, cur = {}, 0 if lay != "wide" else 65536
+    hs_q = head_step(H)
+    for n in names:
+        shape, dt = shapes[n], dts[n]
+        es = torch.empty((), dtype=dt).element_size()
+        st = compact(shape, es)
+        if n in ("k", "v") and lay in ("wide", "paged"):
+            continue
+        if lay in ("batch", "paged") and n != "lens" and not (n == "bt" and case["bt"] == "compact"):
+            st[0] = step
+            used = int(np.prod(shape[1:])) * es
+        elif lay == "head" and n in ("q", "o"):
+            st, used = [H * hs_q, D * es, hs_q], Nq * D * es                      # [B, Nq, H, D]: each head a block of Nq rows
+        elif lay == "head" and n in ("k", "v"):
+            st, used = [Hkv * FAR_STEP, D * es, head_step(Hkv)], N * D * es
+        elif lay == "head" and n == "lse":
+            st, used = [H * hs_q, hs_q], Nq * es
+        else:
+            used = int(np.prod(shape)) * es
+        slots[n] = _bslot(n, dt, shape, st, cur)
+        cur += _up(used, 4096) + 32768 + 1040
+    if lay == "wide":                                                             # K and V interleave inside the row pitch
+        P, width = DECODE_WIDE_PITCH, _up(Hkv * D * ces, 16) + 64
+        for i, n in enumerate(("k", "v")):
+            slots[n] = _bslot(n, cdt, cshape, [N * P, P, D * ces], i * width)
+        assert cur <= P and 2 * width <= 65536
+    if lay == "paged":                                                            # ... and inside the page stride
+        assert cur <= DECODE_POOL_BASE
+        block = _up(case["page"] * Hkv * D * ces, 4096) + 4096
+        for i, n in enumerate(("k", "v")):
+            slots[n] = _bslot(n, cdt, cshape, [DECODE_PAGE_STRIDE, Hkv * D * ces, D * ces], DECODE_POOL_BASE + i * block)
+    twin, tcur = {}, 0
+    for n in names:
+        shape = shapes[n]
+        if lay == "paged" and n in ("k", "v"):
+            shape = (decode_block_tables(case, fmt)[3],) + shape[1:]
+        es = torch.empty((), dtype=dts[n]).element_size()
+        twin[n] = _bslot(n, dts[n], shape, compact(shape, es), tcur)
+        tcur += _up(int(np.prod(shape)) * es, 4096) + 4096
+    if ws_bytes:
+        slots["ws"] = Slot("ws", torch.uint8, (ws_bytes,), (1,), WS_FAR_OFFSET if ws == "far" else WS_NEAR_OFFSET)
+        twin["ws"] = Slot("ws", torch.uint8, (ws_bytes,), (1,), tcur)
+        tcur += _up(ws_bytes, 4096) + 4096
+    return slots, twin, tcur
+
+
+def decode_inputs(case, fmt):
+    """CPU data of a case (one generator, the case's seed): q, the LOGICAL caches k / v [B, Nmax, Hkv, D] (e4m3 for fmt "fp8": clamp(randn / d, +-448)
+    with power-of-two descales d per (sequence, K / V head), 1 where the case leaves the descale out), kd / vd (None: left out)."""
+    g = torch.Generator(device="cpu").manual_seed(case["seed"])
+    io, B, H, Hkv, Nq, D, N = DTYPES[case["dt"]], case["B"], case["H"], case["Hkv"], case["Nq"], case["D"], case["nmax"]
+    data = {"q": torch.randn((B, Nq, H, D), generator=g).to(io), "lens": torch.tensor(case["lens"], dtype=torch.int32)}
+    xk, xv = (torch.randn((B, N, Hkv, D), generator=g) for _ in range(2))
+    if fmt != "fp8":
+        data.update(k=xk.to(io), v=xv.to(io), kd=None, vd=None)
+        return data
+    kd, vd = (2.0 ** -torch.randint(5, 8, (B, Hkv), generator=g).float() for _ in range(2))
+    kd, vd = (kd if "k" in case["descale"] else None), (vd if "v" in case["descale"] else None)
+    one = torch.ones(B, 1, Hkv, 1)
+    data.update(k=(xk / (one if kd is None else kd[:, None, :, None])).clamp(-448.0, 448.0).to(E4M3),
+                v=(xv / (one if vd is None else vd[:, None, :, None])).clamp(-448.0, 448.0).to(E4M3), kd=kd, vd=vd)
+    return data
+
+
+def _poison_like(slot):
+    return torch.full(slot.shape[:-1] + (slot.shape[-1] * slot.esize,), POISON, dtype=torch.uint8)
+
+
+def decode_images(case, fmt, slots, data, block_table=None):
+    """What each INPUT slot must hold before and after the call, as uint8 tensors of the slot's shape (last dimension in bytes): the valid rows of the
+    caches — scattered into their pages for a paged case — and poison everywhere else in them."""
+    img = {}
+    for n, s in slots.items():
+        if n in ("o", "lse", "ws"):
+            continue
+        im = _poison_like(s)
+        if n in ("k", "v"):
+            raw = data[n].contiguous().view(torch.uint8)
+            for b, ln in enumerate(case["lens"]):
+                if case["layout"] != "paged":
+                    im[b, :ln] = raw[b, :ln]
+                    continue
+                page = case["page"]
+                for j in range(-(-ln // page)):
+                    rows = min(page, ln - j * page)
+                    im[int(block_table[b, j]), :rows] = raw[b, j * page:j * page + rows]
+        elif n == "bt":
+            im = torch.from_numpy(np.ascontiguousarray(block_table)).view(torch.uint8)
+        else:
+            im = data[n].contiguous().view(torch.uint8)
+        assert tuple(im.shape) == tuple(_poison_like(s).shape), (n, im.shape)
+        img[n] = im
+    return img
+
+
+def image_failures(got, images, who=""):
+    """The harvested input slots against the images they were written from, byte for byte.  -> list of failures."""
+    return ["%s input %s was written, or a row beyond a length is no longer poison" % (who, n) for n, im in images.items()
+            if not torch.equal(got[n].cpu().contiguous().view(torch.uint8).reshape(im.shape), im)]
+
+
+# ---- merge of partial results (fa2_merge_fwd, fa2_merge_bwd): three parts that share one far stride set, as the C-ABI demands; o, lse, dout, dlse and
+# the parts' gradients are far as well.  Part 1 has rows of weight exactly 0 (lse -inf) whose O stays poison: the contract says they are never read.
+# A far stride leaves no room for a base past 4 GiB inside the arena, so the batch- and head-far parts start as far apart as their slices allow
+# and one compact case puts part 0 at the arena's start, part 1 past 2^31 and part 2 past 2^32.
+MERGE_PARTS = 3
+MERGE_CASES = [
+    dict(id="merge_batch", layout="batch", dt="f16", B=3, H=2, Nq=203, D=128, natural=False),
+    dict(id="merge_head_d40", layout="head", dt="bf16", B=1, H=3, Nq=203, D=40, natural=True),          # D / 8 = 5: the backward's idle group lanes
+    dict(id="merge_packed", layout="packed", dt="f16", B=1, H=2, Nq=PACKED_TOTAL, D=64, natural=False),  # B = 1, Nq = total, rows 1 MiB apart
+    dict(id="merge_bases", layout="bases", dt="bf16", B=2, H=2, Nq=203, D=128, natural=False),
+]
+for _i, _c in enumerate(MERGE_CASES):
+    _c["seed"] = 0x5EED6000 + _i
+MERGE_O_NAMES = ["o%d" % k for k in range(MERGE_PARTS)] + ["o", "dout"] + ["do%d" % k for k in range(MERGE_PARTS)]
+MERGE_L_NAMES = ["l%d" % k for k in range(MERGE_PARTS)] + ["lse", "dlse"] + ["dl%d" % k for k in range(MERGE_PARTS)]
+MERGE_INPUTS = ["o%d" % k for k in range(MERGE_PARTS)] + ["l%d" % k for k in range(MERGE_PARTS)] + ["dout", "dlse"]
+MERGE_PART_GAP = 20 * MIB           # batch- and head-far: bytes between the parts' bases
+
+
+def merge_slots(case):
+    """-> (far slots, twin slots, bytes of the twin's buffer).  Dense slots are [B, H, Nq, D] / [B, H, Nq]; packed ones [total, H, D] / [H, total]."""
+    dt, B, H, Nq, D, lay = DTYPES[case["dt"]], case["B"], case["H"], case["Nq"], case["D"], case["layout"]
+    if lay == "packed":
+        slots = place_rows([(n, dt, (Nq, H, D)) for n in MERGE_O_NAMES], PACKED_PITCH_BYTES)
+        at = PACKED_LSE_OFFSET
+        for n in MERGE_L_NAMES:
+            slots[n] = Slot(n, torch.float32, (H, Nq), (Nq, 1), at)
+            at += _up(H * Nq * 4, 4096) + 4096
+        twin, tbytes = twin_of(slots, keep_pitch=False)
+        return slots, twin, tbytes
+    slots = {}
+    groups = [["o%d" % k, "l%d" % k, "do%d" % k, "dl%d" % k] for k in range(MERGE_PARTS)]      # a part and its gradients start MERGE_PART_GAP after the last
+    groups.append(["o", "lse", "dout", "dlse"])
+    for gi, names in enumerate(groups):
+        specs = [(n, dt, (B, H, Nq, D), D) if n in MERGE_O_NAMES else (n, torch.float32, (B, H, Nq), None) for n in names]
+        if lay == "bases":                                           # compact tensors: group 0 at the start, 1 past 2^31, 2 past 2^32, the rest between
+            start = (0, FAR_STEP + 5 * 4096, 2 * FAR_STEP + 7 * 4096, FAR_STEP // 2)[gi]
+            slots.update(place(specs, None, start=start, gap=4096))
+        else:
+            slots.update(place(specs, lay, start=gi * MERGE_PART_GAP, gap=32768))
+    slots = {n: slots[n] for n in MERGE_O_NAMES + MERGE_L_NAMES}
+    twin, tbytes = twin_of(slots)
+    return slots, twin, tbytes
+
+
+def merge_inputs(case):
+    """CPU data of a merge case as [B, H, Nq, D] / [B, H, Nq]: the parts' O and LSE (the case's unit; spread over ~40 log2 units), dout, dlse.  Row 0
+    is -inf in every part (nobody saw a key), part 1 has further -inf rows; `unwritten`: the rows of o1 that stay poison."""
+    g = torch.Generator(device="cpu").manual_seed(case["seed"])
+    dt, B, H, Nq, D = DTYPES[case["dt"]], case["B"], case["H"], case["Nq"], case["D"]
+    data = {}
+    for k in range(MERGE_PARTS):
+        o, l = torch.randn((B, H, Nq, D), generator=g).to(dt), torch.randn((B, H, Nq), generator=g) * 6.0
+        if k == 1:
+            l[torch.rand((B, H, Nq), generator=g) < 0.3] = float("-inf")
+        l[:, :, 0] = float("-inf")
+        data["o%d" % k], data["l%d" % k] = o, l
+    data["dout"], data["dlse"] = torch.randn((B, H, Nq, D), generator=g).to(dt), torch.randn((B, H, Nq), generator=g)
+    data["unwritten"] = torch.isneginf(data["l1"])
+    return data
+
+
+def merge_as_slot(case, t):
+    """A [B, H, Nq, D] / [B, H, Nq] tensor in the slot's own shape (packed: [total, H, D] / [H, total]), and back (the same call: B = 1)."""
+    if case["layout"] != "packed":
+        return t
+    if t.dim() in (4, 3) and t.shape[0] == 1 and t.shape[1] == case["H"]:
+        return t[0].transpose(0, 1) if t.dim() == 4 else t[0]
+    return t.transpose(0, 1).unsqueeze(0) if t.dim() == 3 else t.unsqueeze(0)
+
+
+def merge_images(case, slots, data):
+    """What each input slot holds before and after the calls (uint8, the slot's shape, last dimension in bytes); the unwritten rows of o1 are poison."""
+    img = {}
+    for n in MERGE_INPUTS:
+        t = merge_as_slot(case, data[n]).contiguous()
+        im = t.view(torch.uint8).clone()
+        if n == "o1":
+            im[merge_as_slot(case, data["unwritten"].unsqueeze(-1).expand(-1, -1, -1, 1))[..., 0]] = POISON
+        assert tuple(im.shape) == tuple(_poison_like(slots[n]).shape), (n, im.shape)
+        img[n] = im
+    return img
+

@@ -135,3 +135,43 @@ def merge64(outs, lses):
     w = w / torch.where(dead, torch.ones_like(s), s)
     O = torch.where(w.unsqueeze(-1) > 0, O, torch.zeros_like(O))          # a part of weight 0 may hold anything
     return (w.unsqueeze(-1) * O).sum(0), torch.where(dead, m, m + torch.log(torch.where(dead, torch.ones_like(s), s)))
+
+
+MERGE_EPS = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}          # half an ulp at 1: one round-to-nearest of the I/O dtype
+
+
+def merge_check(tag, dt, natural, outs, lses, dout, dlse, out, lse, dos, dls):
+    """fa2_merge_fwd / fa2_merge_bwd against the float64 merge and its autograd.  Everything as [B, H, N, D] / [B, H, N] views: the parts, dO, dlse
+    (the LSEs' unit, natural-log or log2), the merged out / lse and the parts' gradients.  Bars: one rounding of the I/O dtype at the largest
+    magnitude for out and dO_k, LSE_TOL in log2 units for the LSE, 1e-4 relative for dlse_k (f32 dot products over D against float64).  Rows whose
+    LSE is -inf in a part have weight 0 there: whatever that part's O holds is replaced by zeros on the way in (the kernel does not read it)."""
+    nq, nparts = outs[0].shape[2], len(outs)
+    unit = 1.0 if natural else LN2                                         # the LSEs' unit in natural-log units
+    lin = [(l.double() * unit).requires_grad_(True) for l in lses]
+    oin = [torch.where(torch.isneginf(l).unsqueeze(-1), torch.zeros_like(o), o).double().requires_grad_(True) for o, l in zip(outs, lses)]
+    O64, L64 = merge64(oin, lin)
+    dead = torch.isneginf(L64.detach())
+    ((O64 * dout.double()).sum() + (L64.masked_fill(dead, 0.0) * (dlse.double() / unit)).masked_fill(dead, 0.0).sum()).backward()
+    O64, L64 = O64.detach(), L64.detach()
+    # forward: f32 accumulation of <= 16 weighted 16-bit values, rounded once
+    lse2 = lse.double() * unit / LN2
+    bar_o = 2 * MERGE_EPS[dt] * max(1.0, O64.abs().max().item())
+    err_o = (out.double() - O64).abs().max().item()
+    assert nq == 1 or dead[:, :, 0].all(), "row 0 of the case is dead"
+    assert torch.isneginf(lse2[dead]).all() and (out[dead] == 0).all(), (tag, "dead rows: O = 0, lse = -inf")
+    err_l = (lse2[~dead] - L64[~dead] / LN2).abs().max().item() if (~dead).any() else 0.0
+    print("%s: O err %.3g (bar %.3g), lse err %.3g log2 units (bar %.3g)" % (tag, err_o, bar_o, err_l, LSE_TOL))
+    assert err_o <= bar_o and err_l <= LSE_TOL, (tag, err_o, bar_o, err_l)
+    if nparts == 1:
+        assert torch.equal(out[~dead], outs[0][~dead]), "one part: its rows come back bit for bit"
+    # backward: dO_k = w_k dO rounded once; dlse_k in the LSEs' unit
+    for kx in range(nparts):
+        want, wl = oin[kx].grad, lin[kx].grad * unit
+        bar = 2 * MERGE_EPS[dt] * max(1.0, want.abs().max().item())
+        err = (dos[kx].double() - want).abs().max().item()
+        bar_l = 1e-4 * max(1.0, wl.abs().max().item())
+        err_lk = (dls[kx].double() - wl).abs().max().item()
+        assert torch.isfinite(dos[kx].float()).all() and torch.isfinite(dls[kx]).all(), (tag, kx, "non-finite gradient")
+        assert err <= bar and err_lk <= bar_l, (tag, kx, err, bar, err_lk, bar_l)
+        zero_w = torch.isneginf(lses[kx])
+        assert (dls[kx][zero_w] == 0).all() and (dos[kx][zero_w] == 0).all(), (tag, kx, "zero-weight parts get zeros")

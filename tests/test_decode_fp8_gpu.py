@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ATOL, FLOOR, LSE_TOL, RTOL
+import decode_refs as dr
 from oracle import fa2_oracle as fo
 from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode
@@ -44,10 +44,6 @@ def _dev():
 
 def _code(dt):
     return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 def _s3(t):
@@ -92,17 +88,7 @@ def _poison(cache8):
     return cache8
 
 
-def _seq_inputs(q, k8, v8, kd, vd, b, n, Nq, G):
-    """sequence b: q [1, H, Nq, D]; f32 K * k_descale and V (no descale), V * v_descale, [1, H, n, D], heads repeated; the causal band as a bias"""
-    keep = np.arange(n)[None, :] <= (n - Nq + np.arange(Nq))[:, None]
-    bias = np.where(keep, 0.0, -np.inf).astype(np.float32)
-    qs = q[b].transpose(0, 1).unsqueeze(0).contiguous()
-    rep = lambda t: t.transpose(0, 1).repeat_interleave(G, dim=0).unsqueeze(0).contiguous()
-    one = torch.ones(k8.shape[2])
-    ks = rep(k8[b, :n].float() * (one if kd is None else kd[b])[None, :, None])
-    vraw = rep(v8[b, :n].float())
-    vs = rep(v8[b, :n].float() * (one if vd is None else vd[b])[None, :, None])
-    return qs, ks, vraw, vs, keep, bias
+_seq_inputs = dr.seq_inputs_fp8
 
 
 @functools.lru_cache(maxsize=None)
@@ -114,54 +100,16 @@ def _case(H, Hkv, Nq, D, dt):
     kd, vd = (2.0 ** -torch.randint(5, 8, (B, Hkv), generator=g).float() for _ in range(2))
     k8 = _poison(_quant(torch.randn((B, NMAX, Hkv, D), generator=g), kd[:, None, :, None]))
     v8 = _poison(_quant(torch.randn((B, NMAX, Hkv, D), generator=g), vd[:, None, :, None]))
-    code, G = _code(dt), H // Hkv
-    refs = []
-    for b, n in enumerate(LENS):
-        if n == 0:
-            refs.append(None)
-            continue
-        qs, ks, vraw, vs, keep, bias = _seq_inputs(q, k8, v8, kd, vd, b, n, Nq, G)
-        assert torch.equal(ks.to(dt).float(), ks) and torch.equal(vraw.to(dt).float(), vraw), "the upcast, descaled cache is exact in q's dtype"
-        o_bits, lse_ref = fo.fwd_c(_bits(qs), _bits(ks.to(dt)), _bits(vraw.to(dt)), code, False, bias=bias)
-        vdh = vd[b].repeat_interleave(G).numpy()[None, :, None, None]
-        o_ref = fo.bits_to_f32(o_bits, code) * vdh                                        # a power of two: exact, commutes with the oracle's rounding
-        o_true, lse_true = fo.fwd_numpy(qs.float().numpy(), ks.numpy(), vs.numpy(), False, bias=bias)
-        live = keep.any(1)
-        assert np.abs(o_ref - o_true)[:, :, live].max() <= FLOOR[code], "the oracle itself against float64 (CPU, before any GPU run)"
-        assert np.abs(lse_ref[..., live] - lse_true[..., live]).max() <= LSE_TOL
-        refs.append((o_ref, lse_ref, o_true, lse_true, ~live))
+    refs = dr.refs_fp8(q, k8, v8, kd, vd, LENS, _code(dt))
     return q, k8, v8, kd, vd, refs
 
 
 def _check(o, lse2, refs, dt, tag, oracle=True):
     """o [B, Nq, H, D] and the log2 lse [B, H, Nq] (device) against the shared references; dead rows exactly 0 / -inf, every element written."""
-    code = _code(dt)
-    got_o, got_l = o.float().cpu(), lse2.cpu()
-    assert torch.isfinite(got_o).all(), (tag, "O not finite: an element was not written, or a NaN byte beyond a length leaked")
-    assert not torch.isnan(got_l).any(), (tag, "LSE not written")
-    for b, ref in enumerate(refs):
-        go = got_o[b].transpose(0, 1).unsqueeze(0).numpy()
-        gl = got_l[b].unsqueeze(0).numpy()
-        if ref is None:
-            assert np.all(go == 0.0) and np.all(np.isneginf(gl)), (tag, b, "a sequence without keys")
-            continue
-        o_ref, lse_ref, o_true, lse_true, dead = ref
-        assert np.all(go[:, :, dead] == 0.0) and np.all(np.isneginf(gl[:, :, dead])), (tag, b, "rows at a negative position")
-        err_t = np.abs(go - o_true)
-        print(tag, "len", LENS[b], "float64 O err %.3g" % err_t.max(), "" if not oracle else "oracle O err %.3g" % np.abs(go - o_ref).max())
-        if oracle:
-            err_o = np.abs(go - o_ref)
-            assert np.all(err_o <= ATOL[code] + RTOL[code] * np.abs(o_ref)), (tag, b, LENS[b], "oracle O", float(err_o.max()))
-        assert err_t.max() <= 2 * FLOOR[code], (tag, b, LENS[b], "float64 O", float(err_t.max()))
-        if (~dead).any():
-            if oracle:
-                assert np.abs(gl[..., ~dead] - lse_ref[..., ~dead]).max() <= LSE_TOL, (tag, b, LENS[b], "oracle LSE")
-            assert np.abs(gl[..., ~dead] - lse_true[..., ~dead]).max() <= LSE_TOL, (tag, b, LENS[b], "float64 LSE")
+    dr.check(o, lse2, refs, LENS, _code(dt), tag, oracle=oracle, verbose=True)
 
 
-def _same_lse(a, b):
-    fa, fb = torch.isfinite(a), torch.isfinite(b)
-    return torch.equal(fa, fb) and torch.equal(a[~fa], b[~fb]) and (not fa.any() or float((a[fa] - b[fb]).abs().max()) <= LSE_TOL)
+_same_lse = dr.same_lse
 
 
 def _all_codes():

@@ -14,8 +14,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ATOL, FLOOR, LSE_TOL, RTOL
-from oracle import fa2_oracle as fo
+import decode_refs as dr
+from conftest import ATOL, LSE_TOL, RTOL
 from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode, flash_attention_varlen, merge_attention
 
@@ -40,10 +40,6 @@ def _dev():
 
 def _code(dt):
     return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 def _s3(t):
@@ -84,48 +80,16 @@ def _case(H, Hkv, Nq, D, dt):
     for b, n in enumerate(LENS):
         k[b, n:] = float("nan")
         v[b, n:] = float("nan")
-    code, G = _code(dt), H // Hkv
-    refs = []
-    for b, n in enumerate(LENS):
-        if n == 0:
-            refs.append(None)
-            continue
-        keep = np.arange(n)[None, :] <= (n - Nq + np.arange(Nq))[:, None]                 # row i at position n - Nq + i sees keys j <= it
-        bias = np.where(keep, 0.0, -np.inf).astype(np.float32)
-        qs = q[b].transpose(0, 1).unsqueeze(0).contiguous()                               # [1, H, Nq, D]
-        ks, vs = (t[b, :n].transpose(0, 1).repeat_interleave(G, dim=0).unsqueeze(0).contiguous() for t in (k, v))
-        o_bits, lse_ref = fo.fwd_c(_bits(qs), _bits(ks), _bits(vs), code, False, bias=bias)
-        o_true, lse_true = fo.fwd_numpy(qs.float().numpy(), ks.float().numpy(), vs.float().numpy(), False, bias=bias)
-        refs.append((fo.bits_to_f32(o_bits, code), lse_ref, o_true, lse_true, ~keep.any(1)))
+    refs = dr.refs16(q, k, v, LENS, _code(dt))
     return q, k, v, refs
 
 
 def _check(o, lse2, refs, dt, tag):
     """o [B, Nq, H, D] and the log2 lse [B, H, Nq] (device) against the shared references; dead rows exactly 0 / -inf, every element written."""
-    code = _code(dt)
-    got_o, got_l = o.float().cpu(), lse2.cpu()
-    assert torch.isfinite(got_o).all(), (tag, "O not finite: an element was not written, or a NaN beyond a length leaked")
-    assert not torch.isnan(got_l).any(), (tag, "LSE not written")
-    for b, ref in enumerate(refs):
-        go = got_o[b].transpose(0, 1).unsqueeze(0).numpy()
-        gl = got_l[b].unsqueeze(0).numpy()
-        if ref is None:
-            assert np.all(go == 0.0) and np.all(np.isneginf(gl)), (tag, b, "a sequence without keys")
-            continue
-        o_ref, lse_ref, o_true, lse_true, dead = ref
-        assert np.all(go[:, :, dead] == 0.0) and np.all(np.isneginf(gl[:, :, dead])), (tag, b, "rows at a negative position")
-        err_o, err_t = np.abs(go - o_ref), np.abs(go - o_true)
-        assert np.all(err_o <= ATOL[code] + RTOL[code] * np.abs(o_ref)), (tag, b, LENS[b], "oracle O", float(err_o.max()))
-        assert err_t.max() <= 2 * FLOOR[code], (tag, b, LENS[b], "float64 O", float(err_t.max()))
-        if (~dead).any():
-            assert np.abs(gl[..., ~dead] - lse_ref[..., ~dead]).max() <= LSE_TOL, (tag, b, LENS[b], "oracle LSE")
-            assert np.abs(gl[..., ~dead] - lse_true[..., ~dead]).max() <= LSE_TOL, (tag, b, LENS[b], "float64 LSE")
+    dr.check(o, lse2, refs, LENS, _code(dt), tag)
 
 
-def _same_lse(a, b):
-    """two log2 LSE tensors agree within LSE_TOL, -inf in the same places"""
-    fa, fb = torch.isfinite(a), torch.isfinite(b)
-    return torch.equal(fa, fb) and torch.equal(a[~fa], b[~fb]) and (not fa.any() or float((a[fa] - b[fb]).abs().max()) <= LSE_TOL)
+_same_lse = dr.same_lse
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)

@@ -5,7 +5,13 @@ the documented span limits ("addressing limits"; include/fa2_gfx950.h
 The dense launching entry points report a null tensor before they look at a span (the order of the checks is part of the C-ABI, tests/test_abi_golden.py),
 so their edges are pinned through the plan queries, which run the same validation on the same call description (fa2_fwd_plan and its grouped and
 windowed twins; fa2_bwd_plan); the packed entry points check their tensors last and show the edge themselves.  tests/test_far_offsets_gpu.py
-repeats the refusals through the launching entry points, on real tensors."""
+repeats the refusals through the launching entry points, on real tensors.
+
+The decode, merge, score-modifier and LSE-gradient layouts are proved here too (what crosses byte 2^31 and 2^32, which e4m3 caches pass element
+index 2^31, that a wide-row cache's invalid keys stay inside the arena, that every paged sequence takes a page of each region), their checkers are
+fed mutants — an output built from the neighbouring page id, the key at index len included, a write into a poison page, a row merged from the wrong
+part's base, a gradient that ignored dlse —, and the packed score-modifier and LSE entry points and fa2_bwd_lse_plan sit on the span edges of the
+calls they extend.  The decode call documents no span limit; its plan and workspace queries take sizes only and are asserted per case."""
 import ctypes
 import re
 
@@ -325,6 +331,11 @@ def test_backward_plan_query_sits_on_the_span_edge_of_every_bounded_tensor():
             good = fl.last_pitch(n, D)
             assert _bwd_plan(lib, dt, 1, H, Hkv, Nq, Nkv, D, {which: _s3(good, n)})[0] == 0, (which, D)
             assert _bwd_plan(lib, dt, 1, H, Hkv, Nq, Nkv, D, {which: _s3(good + 8, n)})[0] == shape, (which, D)
+            for has_dlse in (0, 1):                                     # fa2_bwd_lse's own query: the same validation, with and without a dlse
+                plan = _fa2_lib.BwdPlan()
+                st = lambda p: [{which: _s3(p, n)}.get(t) for t in ("q", "k", "v", "o", "do")]      # noqa: E731
+                assert lib.fa2_bwd_lse_plan(dt, 1, H, Hkv, Nq, Nkv, D, *st(good), D ** -0.5, 0, 0, None, has_dlse, ctypes.byref(plan)) == 0
+                assert lib.fa2_bwd_lse_plan(dt, 1, H, Hkv, Nq, Nkv, D, *st(good + 8), D ** -0.5, 0, 0, None, has_dlse, ctypes.byref(plan)) == shape
             if Hkv == H and D <= 256:        # the masked backward: the same tensors, and its own slice rule
                 assert _bwd_plan(lib, dt, 1, H, Hkv, Nq, Nkv, D, {which: _s3(good + 8, n)}, bias_kind=_fa2_lib.FA2_BIAS_BOOL)[0] == shape
         assert _bwd_plan(lib, dt, 1, H, Hkv, Nq, Nkv, D, {"o": _s3(1 << 24, Nq)})[0] == 0
@@ -380,6 +391,7 @@ def test_packed_entry_points_sit_on_the_span_edge_of_every_bounded_tensor():
             args = (3, H, H, mq, mk, D, None, None, st["q"], st["k"], st["v"], st["o"], 0, 0.125, 1, -1, -1, None)
             assert lib.fa2_fwd_varlen(0, *[None] * 5, *args) == want, (which, step)
             assert lib.fa2_fwd_varlen_dropout(0, *[None] * 5, *args, 0.25, 7) == want
+            assert lib.fa2_fwd_varlen_scoremod(0, *[None] * 5, *args, 30.0, None, 0) == want          # the score-modifier call inherits the packed rule
             if which == "k":
                 assert lib.fa2_fwd_varlen_plan(0, 3, H, H, mq, mk, D, small, st["k"], 0.125, 1, -1, -1, ctypes.byref(plan)) == (0 if want == null else shape)
     for which in ("q", "do", "k", "v"):
@@ -390,6 +402,9 @@ def test_packed_entry_points_sit_on_the_span_edge_of_every_bounded_tensor():
             args = (3, H, mq, mk, D, None, None) + tuple(st[t] for t in ("q", "k", "v", "o", "do", "dq", "dk", "dv")) + (0, 0.125, 1, -1, -1, None)
             assert lib.fa2_bwd_varlen(1, *[None] * 10, *args) == want, (which, step)
             assert lib.fa2_bwd_varlen_dropout(1, *[None] * 10, *args, 0.25, 7) == want
+            assert lib.fa2_bwd_varlen_scoremod(1, *[None] * 10, *args, 30.0, None, 0) == want
+            for drop, cap in ((0.0, 0.0), (0.25, 0.0), (0.0, 30.0)):      # fa2_bwd_varlen_lse on each of its routes: the edge sits at the same pitch
+                assert lib.fa2_bwd_varlen_lse(1, *[None] * 10, *args, drop, 7, cap, None, 0, None, 0) == want, (which, step, drop, cap)
     # O, dQ, dK, dV are not bounded: 1 MiB rows for 1500-row sequences reach the null tensors
     st = {t: small for t in ("q", "k", "v", "o", "do", "dq", "dk", "dv")}
     for t in ("o", "dq", "dk", "dv"):
@@ -447,7 +462,8 @@ def test_forward_bias_takes_the_lds_dma_form_exactly_inside_the_slice_rule():
     assert form(1, 1, 1, 64, 64, 60, 64) == c["FA2_ERR_HEAD_DIM"] and form(1, 0, 1, 64, 64, 64, 64) == c["FA2_ERR_BAD_SHAPE"]
 
 
-@pytest.mark.parametrize("case", list(fl.DENSE_CASES) + fl.SPAN_CASES + fl.BIAS_SPAN_CASES + fl.F32_CASES, ids=lambda c: c["id"])
+@pytest.mark.parametrize("case", list(fl.DENSE_CASES) + fl.SPAN_CASES + fl.BIAS_SPAN_CASES + fl.F32_CASES + list(fl.SCOREMOD_CASES) + list(fl.LSE_CASES),
+                         ids=lambda c: c["id"])
 def test_every_case_is_planned_on_the_kernel_it_names(case):
     """The case table says which kernel a shape is there for (`expect`, `expect_bwd`, under the case's options): the plan queries, asked with the
     layout's own strides, agree — for the far layout and for its twin.  (The GPU module asserts the same before it launches; here the table cannot
@@ -473,3 +489,352 @@ def test_every_case_is_planned_on_the_kernel_it_names(case):
         if case["bwd"] and case["fam"] in ("dense", "bias"):
             got, got_t = tg._bwd_plan(case, T), tg._bwd_plan(case, Tt)
             assert got == got_t and (not case.get("expect_bwd") or got == tuple(tg.BWD_KERNELS[k] for k in case["expect_bwd"])), (got, got_t, case["expect_bwd"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- KV-cache decode
+def _decode_ids(v):
+    return v["id"] if isinstance(v, dict) else v
+
+
+def test_decode_table_reaches_every_kernel_length_and_format():
+    cases = fl.DECODE_CASES
+    lens = {n for c in cases for n in c["lens"]}
+    assert {0, 65, 129, 1000} <= lens and any(0 < n < c["Nq"] for c in cases for n in c["lens"])
+    assert {c["rt"] for c in cases} == {1, 2, 4} and {c["D"] for c in cases} == {64, 128} and {c["dt"] for c in cases} == {"f16", "bf16"}
+    assert {c["layout"] for c in cases} == {"batch", "head", "wide", "paged"} and {c["page"] for c in cases} == {0, 64, 128}
+    assert {c["bt"] for c in cases if c["layout"] == "paged"} == {"far", "compact"} and {c["descale"] for c in cases} == {"kv", "k", "v"}
+    assert all(n <= c["nmax"] for c in cases for n in c["lens"]) and all(c["Nq"] * (c["H"] // c["Hkv"]) <= 64 for c in cases)
+
+
+@pytest.mark.parametrize("fmt", fl.DECODE_FORMATS)
+@pytest.mark.parametrize("case", fl.DECODE_CASES, ids=_decode_ids)
+def test_decode_layouts_cross_what_they_claim(case, fmt):
+    """Every decode layout, with a split's workspace near and far: inside the arena, no two rows share a byte, and the slices named by the layout cross
+    byte 2^31 and byte 2^32 — for the e4m3 caches that is element index 2^31 and 2^32 of the cache, for the 16-bit wide-row cache element index 2^31.
+    The plan and workspace queries take sizes only, so the far call and its twin get one answer; it names the row tiles the case is there for."""
+    import test_far_offsets_gpu as tg
+    need = [tg._decode_plan(case, fmt, ns)[1] for ns in tg.DECODE_SPLITS]
+    assert need[0] == 0 and need[1] > 0 and need[2] > 0
+    for where in ("near", "far"):
+        slots, twin, tbytes = fl.decode_slots(case, fmt, max(need), where)
+        fl.validate(list(slots.values()), fl.ARENA_BYTES)
+        fl.validate(list(twin.values()), tbytes)
+        _meta_views(slots, fl.ARENA_BYTES)
+        _meta_views(twin, tbytes)
+        assert (slots["ws"].offset > P32) == (where == "far") and (slots["ws"].offset < P31) == (where == "near")
+    assert ("kd" in slots, "vd" in slots) == ((fmt == "fp8" and "k" in case["descale"]), (fmt == "fp8" and "v" in case["descale"]))
+    assert all(t.shape == slots[n].shape or (case["layout"] == "paged" and n in ("k", "v")) for n, t in twin.items())
+    lay, k, v = case["layout"], slots["k"], slots["v"]
+    ces = 1 if fmt == "fp8" else 2
+    assert k.esize == ces and k.dtype == v.dtype and k.strides == v.strides
+    if lay in ("batch", "paged"):
+        far = ["q", "o", "lse"] + [n for n in ("kd", "vd") if n in slots] + (["k", "v"] if lay == "batch" else []) + (["bt"] if case["bt"] == "far" else [])
+        for n in far:
+            assert _crosses(slots[n], 0, P31) and _crosses(slots[n], 0, P32) and slots[n].strides[0] * slots[n].esize == fl.FAR_STEP, n
+        assert slots["lens"].strides == (1,)                                          # cache_seqlens stays contiguous: the operator requires it
+        if fmt == "fp8" and lay == "batch":                                           # the cache's ELEMENT index: batch 1 past 2^31, batch 2 past 2^32
+            assert P31 < k.strides[0] < P32 < 2 * k.strides[0]
+    if lay == "head":
+        for n, dim in (("k", 2), ("v", 2), ("q", 2), ("o", 2), ("lse", 1)):
+            starts = [slots[n].slice_range(dim, i)[0] for i in range(slots[n].shape[dim])]
+            assert min(starts) < P31 and any(P31 < a < P32 for a in starts) and max(starts) > P32, (n, starts)
+        assert k.strides[2] * ces == fl.FAR_STEP and (fmt != "fp8" or P31 < k.strides[2] < P32 < 2 * k.strides[2])
+    if lay == "wide":
+        n, rows = case["lens"][0], k.row_starts()[0, :, 0]
+        assert k.strides[1] * ces == fl.DECODE_WIDE_PITCH == v.strides[1] * ces and 0 < v.offset - k.offset < 65536      # K and V interleave inside the pitch
+        for s in (k, v):
+            at = s.row_starts()[0, :, 0]
+            assert at[0] < P31 and ((at[:n] > P31) & (at[:n] < P32)).any() and at[n - 1] > P32 and at[n - 32] > P32      # the whole last key tile lies past 2^32
+            assert at[n:].min() > P32 and at[-1] + s.row_bytes() <= fl.ARENA_BYTES and len(at) > n                      # the invalid keys stay inside the arena
+        elem = (rows[n - 1] - k.offset) // ces                                                                          # the last key's element index in the cache
+        assert elem > (P32 if fmt == "fp8" else P31) and elem == (n - 1) * k.strides[1]
+    if lay == "paged":
+        bt, bt_t, poison, pages_t = fl.decode_block_tables(case, fmt)
+        low, mid, high = fl.decode_page_regions(case, fmt)
+        assert low and mid and len(high) >= 3 and k.strides[0] * ces == fl.DECODE_PAGE_STRIDE == v.strides[0] * ces and fl.DECODE_PAGE_STRIDE // 4096 % 2 == 1
+        assert 0 < v.offset - k.offset < fl.DECODE_PAGE_STRIDE and k.shape[0] == fl.DECODE_NUM_PAGES and twin["k"].shape[0] == pages_t
+        for s in (k, v):                                                                                                # the regions are what the slots say
+            assert all(s.slice_range(0, p)[1] <= P31 for p in low) and all(P31 < s.slice_range(0, p)[0] and s.slice_range(0, p)[1] <= P32 for p in mid)
+            assert all(s.slice_range(0, p)[0] > P32 for p in high)
+        taken = []
+        for b, n in enumerate(case["lens"]):
+            used = -(-n // case["page"])
+            mine = [int(p) for p in bt[b, :used]]
+            taken += mine
+            if n:
+                assert all(any(p in r for p in mine) for r in (low, mid, high)), (b, mine)
+                assert mine != sorted(mine)                                                                             # shuffled
+            assert all(int(p) == poison for p in bt[b, used:])
+        assert len(set(taken)) == len(taken) and poison not in taken and poison in high and 0 <= bt.min() and bt.max() < fl.DECODE_NUM_PAGES
+        tw = [int(p) for b, n in enumerate(case["lens"]) for p in bt_t[b, :-(-n // case["page"])]]
+        assert len(set(tw)) == len(tw) == pages_t - 1 and 0 <= bt_t.min() and bt_t.max() < pages_t and tw != [int(p) for p in taken]
+        spare_t = (set(range(pages_t)) - set(tw)).pop()                                                                 # the twin's page nobody writes
+        assert all(int(p) == spare_t for b, n in enumerate(case["lens"]) for p in bt_t[b, -(-n // case["page"]):])
+        if fmt == "fp8":                                                                                                # page id * page stride as an element index
+            assert max(taken) * k.strides[0] > P32 and any(P31 < p * k.strides[0] < P32 for p in taken)
+        if case["bt"] == "compact":
+            assert slots["bt"].strides == (bt.shape[1], 1)
+    # the images: valid rows hold data, every other cache byte is poison; a paged twin holds the same logical rows under its own numbering
+    data = fl.decode_inputs(case, fmt)
+    tables = fl.decode_block_tables(case, fmt) if lay == "paged" else (None, None)
+    img, img_t = fl.decode_images(case, fmt, slots, data, tables[0]), fl.decode_images(case, fmt, twin, data, tables[1])
+    valid = sum(case["lens"]) * case["Hkv"] * case["D"] * ces
+    for im in (img, img_t):
+        assert set(im) == set(slots) - {"o", "lse", "ws"}
+        for n in ("k", "v"):
+            raw = data[n].contiguous().view(torch.uint8)
+            assert int((im[n] != fl.POISON).sum()) <= valid and int((im[n] != fl.POISON).sum()) >= valid * 0.98         # (a data byte may equal 0xFF by chance: fp16 only)
+            for b, ln in enumerate(case["lens"]):
+                if lay != "paged":
+                    assert torch.equal(im[n][b, :ln], raw[b, :ln]) and (im[n][b, ln:] == fl.POISON).all()
+    if lay == "paged":
+        page = case["page"]
+        for b, ln in enumerate(case["lens"]):
+            for j in range(-(-ln // page)):
+                rows = min(page, ln - j * page)
+                assert torch.equal(img["k"][int(tables[0][b, j]), :rows], img_t["k"][int(tables[1][b, j]), :rows])
+                assert (img["k"][int(tables[0][b, j]), rows:] == fl.POISON).all()
+
+
+def _toy_paged_case():
+    """A paged decode in miniature, on the CPU: six pages of 64 keys 40 KiB apart in a 1 MiB arena, two sequences (70 and 100 keys) whose pages are
+    neighbours in memory, page 5 for the block table's unused entries, page 0 unused.  The 'kernel' is dense float64 attention through the block
+    table, reading the arena's own views — what it reads past a length or in a page nobody wrote is poison, as on the GPU."""
+    import decode_refs as dr
+    case = dict(id="toy", layout="paged", dt="f16", D=64, H=2, Hkv=1, Nq=2, lens=(70, 100), B=2, page=64)
+    f16, f32, i32 = torch.float16, torch.float32, torch.int32
+    slots = {"q": fl._bslot("q", f16, (2, 2, 2, 64), [512, 256, 128], 0), "o": fl._bslot("o", f16, (2, 2, 2, 64), [512, 256, 128], 4096 + 16),
+             "lse": fl._bslot("lse", f32, (2, 2, 2), [16, 8], 8192 + 32), "lens": fl._bslot("lens", i32, (2,), [], 12288), "bt": fl._bslot("bt", i32, (2, 2), [8], 12288 + 64),
+             "k": fl._bslot("k", f16, (6, 64, 1, 64), [40960, 128, 128], 65536), "v": fl._bslot("v", f16, (6, 64, 1, 64), [40960, 128, 128], 65536 + 16384)}
+    fl.validate(list(slots.values()), 1 << 20)
+    g = torch.Generator().manual_seed(11)
+    data = {"q": torch.randn((2, 2, 2, 64), generator=g).half(), "k": torch.randn((2, 128, 1, 64), generator=g).half(),
+            "v": torch.randn((2, 128, 1, 64), generator=g).half(), "lens": torch.tensor(case["lens"], dtype=i32)}
+    bt = np.array([[4, 1], [2, 3]], dtype=np.int32)
+    images = fl.decode_images(case, "16", slots, data, bt)
+    refs = dr.refs16(data["q"], data["k"], data["v"], case["lens"], 0)
+    return case, slots, images, refs
+
+
+def _toy_decode(arena, slots, case, mutant=None):
+    T = {n: s.view(arena) for n, s in slots.items()}
+    page, Nq, D = case["page"], case["Nq"], case["D"]
+    for b in range(case["B"]):
+        n = int(T["lens"][b]) + (1 if mutant == "key_at_len" and b == 0 else 0)
+        pids = [int(T["bt"][b, j // page]) + (1 if mutant == "neighbour_page" and (b, j // page) == (0, 1) else 0) for j in range(n)]
+        kk = torch.stack([T["k"][p, j % page, 0] for j, p in enumerate(pids)]).double()
+        vv = torch.stack([T["v"][p, j % page, 0] for j, p in enumerate(pids)]).double()
+        s = torch.einsum("ihd,jd->hij", T["q"][b].double(), kk) * D ** -0.5
+        keep = torch.arange(n)[None, :] <= (n - Nq + torch.arange(Nq))[:, None]
+        s = s.masked_fill(~keep, float("-inf"))
+        dead = ~keep.any(1)
+        lse = torch.logsumexp(s.masked_fill(dead[None, :, None], 0.0), -1)
+        p = torch.exp(s - lse.unsqueeze(-1)).masked_fill(dead[None, :, None], 0.0)
+        T["o"][b] = torch.einsum("hij,jd->ihd", p, vv).half()
+        T["lse"][b] = (lse / np.log(2.0)).masked_fill(dead[None, :], float("-inf")).float()
+    if mutant == "write_into_poison_page":
+        T["k"][5, 3, 0, 7] = 1.0
+
+
+def _toy_check(arena, slots, case, images, refs, twin_out):
+    """What tests/test_far_offsets_gpu.py's _decode_run checks, in its order -> list of failures."""
+    import decode_refs as dr
+    got = fl.harvest(arena, slots)
+    fails = fl.image_failures(got, images) + fl.compare_exact(got, twin_out, ["o", "lse"])
+    try:
+        dr.check(got["o"], got["lse"], refs, case["lens"], 0, "toy")
+    except AssertionError as e:
+        fails.append("truth: %s" % (e,))
+    return fails
+
+
+def test_decode_checker_flags_its_mutants():
+    case, slots, images, refs = _toy_paged_case()
+    runs = {}
+    for mutant in (None, "neighbour_page", "key_at_len", "write_into_poison_page"):
+        arena = fl.new_arena(1 << 20, "cpu")
+        for n, im in images.items():
+            slots[n].bytes_view(arena).copy_(im)
+        _toy_decode(arena, slots, case, mutant)
+        if mutant is None:
+            clean = {n: slots[n].view(arena).clone() for n in ("o", "lse")}
+        runs[mutant] = _toy_check(arena, slots, case, images, refs, clean)
+        assert fl.arena_is_poison(arena)
+    assert runs[None] == []
+    # an output built from the neighbouring page id — real keys of the other sequence, nothing non-finite: the twin and the truth both object
+    assert any(f.startswith("o:") for f in runs["neighbour_page"]) and any("oracle O" in f or "float64 O" in f for f in runs["neighbour_page"])
+    assert not any("input" in f for f in runs["neighbour_page"])
+    # the key at index len is poison: it reaches O as NaN
+    assert any("O not finite" in f for f in runs["key_at_len"]) and any(f.startswith("o:") for f in runs["key_at_len"])
+    # a write into a page nobody uses: the outputs are right, the page's image is not
+    assert runs["write_into_poison_page"] == [" input k was written, or a row beyond a length is no longer poison"]
+
+
+# ---------------------------------------------------------------------------------------------------------------- merge, score modifiers, a gradient for the LSE
+@pytest.mark.parametrize("case", fl.MERGE_CASES, ids=_decode_ids)
+def test_merge_layouts_cross_both_thresholds_with_one_stride_set(case):
+    slots, twin, tbytes = fl.merge_slots(case)
+    fl.validate(list(slots.values()), fl.ARENA_BYTES)
+    fl.validate(list(twin.values()), tbytes)
+    _meta_views(slots, fl.ARENA_BYTES)
+    _meta_views(twin, tbytes)
+    assert set(slots) == set(fl.MERGE_O_NAMES + fl.MERGE_L_NAMES) and set(fl.MERGE_INPUTS) < set(slots)
+    for group in (["o%d" % k for k in range(fl.MERGE_PARTS)], ["l%d" % k for k in range(fl.MERGE_PARTS)], ["do%d" % k for k in range(fl.MERGE_PARTS)],
+                  ["dl%d" % k for k in range(fl.MERGE_PARTS)]):
+        assert len({slots[n].strides for n in group}) == 1 and len({slots[n].offset for n in group}) == fl.MERGE_PARTS      # one stride set, bases of their own
+    lay = case["layout"]
+    if lay in ("batch", "head"):
+        dim = 0 if lay == "batch" else 1
+        for n, s in slots.items():
+            assert _crosses(s, dim, P31) and _crosses(s, dim, P32), n
+        assert slots["o2"].offset - slots["o0"].offset == 2 * fl.MERGE_PART_GAP
+    elif lay == "packed":
+        assert case["B"] == 1 and case["Nq"] == fl.PACKED_TOTAL
+        for n in fl.MERGE_O_NAMES:
+            s = slots[n]
+            at = s.row_starts()[:, 0]
+            assert s.kind == "packed" and s.strides[0] * s.esize == fl.PACKED_PITCH_BYTES and at[0] < P31 and ((at > P31) & (at < P32)).any() and at[-1] > P32
+        assert all(slots[n].offset > P32 and slots[n].shape == (case["H"], case["Nq"]) for n in fl.MERGE_L_NAMES)
+    else:                                                                 # the parts' bases: the arena's start, past 2^31, past 2^32
+        for names in (("o0", "o1", "o2"), ("l0", "l1", "l2"), ("do0", "do1", "do2"), ("dl0", "dl1", "dl2")):
+            a, b, c = (slots[n].offset for n in names)
+            assert a < 16 * fl.MIB and P31 < b < P32 < c
+    assert {c["D"] for c in fl.MERGE_CASES} >= {128, 40} and {c["dt"] for c in fl.MERGE_CASES} == {"f16", "bf16"} and any(c["natural"] for c in fl.MERGE_CASES)
+    # the data: part 1 has rows of weight 0 whose O stays poison; every other input byte is data
+    data = fl.merge_inputs(case)
+    img = fl.merge_images(case, slots, data)
+    un = data["unwritten"]
+    assert un.any() and not un.all() and un[:, :, 0].all() and all(torch.isneginf(data["l%d" % k][:, :, 0]).all() for k in range(fl.MERGE_PARTS))
+    assert int((img["o1"] == fl.POISON).all(-1).sum()) == int(un.sum())
+    assert not torch.isneginf(data["l0"][:, :, 1:]).any() and not torch.isneginf(data["l2"][:, :, 1:]).any()
+
+
+def test_merge_checker_flags_a_row_merged_from_the_wrong_parts_base():
+    import lse_refs as R
+    case = dict(fl.MERGE_CASES[0], B=2, H=2, Nq=9, D=16)
+    data = fl.merge_inputs(case)
+    parts = range(fl.MERGE_PARTS)
+    outs, lses = [data["o%d" % k] for k in parts], [data["l%d" % k] for k in parts]
+    clean = [torch.where(torch.isneginf(l).unsqueeze(-1), torch.zeros_like(o), o) for o, l in zip(outs, lses)]
+
+    def result(os_):
+        oin, lin = [o.double().requires_grad_(True) for o in os_], [(l.double() * R.LN2).requires_grad_(True) for l in lses]
+        O, L = R.merge64(oin, lin)
+        dead = torch.isneginf(L.detach())
+        ((O * data["dout"].double()).sum() + (L.masked_fill(dead, 0.0) * (data["dlse"].double() / R.LN2)).masked_fill(dead, 0.0).sum()).backward()
+        return (O.detach().half(), (L.detach() / R.LN2).float(), [t.grad.half() for t in oin], [(t.grad * R.LN2).float() for t in lin])
+
+    good = result(clean)
+    R.merge_check("clean", torch.float16, False, outs, lses, data["dout"], data["dlse"], *good)
+    # row (1, 0, 5) of the merged O taken with every part's pointer rotated by one: the weights of parts k meet the rows of parts k + 1
+    wrong = result([clean[1], clean[2], clean[0]])
+    bad_o = good[0].clone()
+    bad_o[1, 0, 5] = wrong[0][1, 0, 5]
+    assert (bad_o != good[0]).any()
+    with pytest.raises(AssertionError):
+        R.merge_check("mutant", torch.float16, False, outs, lses, data["dout"], data["dlse"], bad_o, *good[1:])
+    # ... and a part's gradient that went to another part's base
+    with pytest.raises(AssertionError):
+        R.merge_check("mutant", torch.float16, False, outs, lses, data["dout"], data["dlse"], good[0], good[1], [good[2][1], good[2][0], good[2][2]], good[3])
+
+
+@pytest.mark.parametrize("case", list(fl.SCOREMOD_CASES) + list(fl.LSE_CASES), ids=_decode_ids)
+def test_scoremod_and_lse_layouts_place_slopes_and_dlse_where_they_claim(case):
+    import lse_refs as R
+    slots, twin, tbytes = fl.dense_slots(case)
+    fl.validate(list(slots.values()), fl.ARENA_BYTES)
+    fl.validate(list(twin.values()), tbytes)
+    _meta_views(slots, fl.ARENA_BYTES)
+    dim = 0 if case["far"] == "batch" else 1
+    for n in ("q", "k", "v", "o", "lse"):
+        starts = [slots[n].slice_range(dim, i)[0] for i in range(slots[n].shape[dim])]
+        assert min(starts) < P31 and any(P31 < a < P32 for a in starts) and max(starts) > P32, n
+    if case["slopes"]:
+        s = slots["slopes"]
+        assert case["softcap"] == 30.0 and s.dtype == torch.float32 and s.shape == (case["B"], case["H"])
+        if case["far"] == "batch":                                        # b * alibi_batch_stride + h past byte 2^31 and 2^32
+            assert _crosses(s, 0, P31) and _crosses(s, 0, P32) and s.strides[0] * 4 == fl.FAR_STEP
+        else:
+            assert case["B"] == 1                                         # one shared [H] vector: the call passes stride 0
+    if case["dlse"]:
+        s = slots["dlse"]
+        assert case["bwd"] and s.shape == slots["lse"].shape
+        if case["dlse"] == "far":
+            assert s.strides == slots["lse"].strides and _crosses(s, dim, P31) and _crosses(s, dim, P32)
+        else:                                                             # compact beside far tensors: strides of its own
+            assert s.strides == (case["H"] * case["Nq"], case["Nq"], 1) != slots["lse"].strides and s.extent()[1] < P31
+        dead = ~R.ff.band(case["Nq"], case["Nkv"], *(case["window"] or (-1, -1, 0)), case["causal"], "cpu").any(-1)
+        assert bool(dead.any()) == (case["window"] is not None) and not dead.all()
+    tabs = list(fl.SCOREMOD_CASES) + list(fl.LSE_CASES)
+    assert {c["dlse"] for c in tabs} == {None, "far", "compact"} and any(c["dlse"] == "compact" and c["far"] for c in tabs)
+    assert {(c["fam"], bool(c["dlse"])) for c in tabs} >= {("scoremod", False), ("dense", True), ("bias", True), ("window", True), ("dropout", True), ("scoremod", True)}
+
+
+def test_f32_decode_case_puts_lse_descales_and_block_table_past_element_index_two_to_the_31():
+    import test_far_offsets_gpu as tg
+    case = fl.DECODE_F32_CASE
+    assert case["layout"] == "paged" and case["bt"] == "far" and case["descale"] == "kv" and case["B"] == 3 and case["lens"][2] > 0
+    for where in ("near", "far"):
+        slots, twin, tbytes = fl.decode_slots(case, "fp8", tg._decode_plan(case, "fp8", 3)[1], where, step=fl.F32_STEP)
+        fl.validate(list(slots.values()), fl.ARENA_F32_BYTES)
+        fl.validate(list(twin.values()), tbytes)
+        _meta_views(slots, fl.ARENA_F32_BYTES)
+    for n in ("lse", "kd", "vd", "bt"):                                  # 4-byte elements: b * stride[0] leaves 31 bits for the last sequence, which has keys
+        s = slots[n]
+        first = [s.slice_range(0, b)[0] // 4 for b in range(3)]
+        assert s.esize == 4 and first[0] < P31 // 4 and P31 // 2 < first[1] < P31 < first[2] and 2 * s.strides[0] > P31, (n, first)
+    assert max(s.extent()[1] for s in (slots["k"], slots["v"])) < fl.ARENA_BYTES      # the pool itself stays where the other arena has it
+
+
+def test_f32_case_puts_dlse_and_slopes_past_float_index_two_to_the_31():
+    case = fl.F32_CASES[-1]
+    slots, _, _ = fl.dense_slots(case, step=fl.F32_STEP)
+    assert case["dlse"] == "far" and case["slopes"] and case["fam"] == "scoremod"
+    for n in ("dlse", "slopes"):
+        first = [slots[n].slice_range(0, b)[0] // 4 for b in range(3)]
+        assert first[0] < P31 // 4 and P31 // 2 < first[1] < P31 < first[2] and 2 * slots[n].strides[0] > P31, (n, first)
+
+
+def test_lse_checker_flags_a_gradient_that_ignored_dlse():
+    """tests/test_far_offsets_gpu.py's _truth_lse on the CPU: given the emulation's own outputs it passes, given gradients computed without the dlse
+    term it objects to dQ (dV does not depend on dlse), and its dead rows — a NaN in dlse — are there."""
+    import lse_refs as R
+    import test_far_offsets_gpu as tg
+    case = dict(fl.LSE_CASES[5], B=2, H=2, Hkv=2, Nq=96, Nkv=48, far=None)
+    assert case["fam"] == "window" and case["dlse"]
+    slots, _, _ = fl.dense_slots(case)
+    data = tg._inputs(case, slots, "cpu")
+    dead = torch.isnan(data["dlse"])
+    assert dead[:, :, 84:].all() and not dead[:, :, :84].any()
+
+    def outputs(with_u):
+        out = {n: [] for n in ("o", "lse", "dq", "dk", "dv")}
+        allow = R.ff.band(96, 48, *case["window"], True, "cpu")
+        for b in range(2):
+            u = torch.nan_to_num(data["dlse"][b], nan=0.0) / R.LN2 if with_u else None
+            e = R.emulate(data["q"][b], data["k"][b], data["v"][b], data["do"][b], u, allow, tg._scale(case), torch.float16)
+            for n, m in (("o", "O"), ("lse", "lse"), ("dq", "dQ"), ("dk", "dK"), ("dv", "dV")):
+                out[n].append(e[m].float() if n == "lse" else e[m].half())
+        return {n: torch.stack(v) for n, v in out.items()}
+
+    fails, live = tg._truth_lse(case, outputs(True), data)
+    assert fails == [] and not live[:, :, 84:].any() and live[:, :, :84].all()
+    fails, _ = tg._truth_lse(case, outputs(False), data)
+    assert len(fails) == 2 and all("dQ" in f for f in fails), fails
+
+
+def test_packed_scoremod_and_lse_cases_place_slopes_and_dlse_far():
+    cases = {c["id"]: c for c in fl.PACKED_CASES}
+    assert {"varlen_smod_gqa_topleft", "varlen_smod_bottomright", "varlen_lse"} <= set(cases)
+    top, bottom, lse = cases["varlen_smod_gqa_topleft"], cases["varlen_smod_bottomright"], cases["varlen_lse"]
+    assert top["Hkv"] < top["H"] and not top["bwd"] and not top["bottom_right"] and bottom["bwd"] and bottom["bottom_right"] and lse["bwd"] and lse["bottom_right"]
+    for c in (top, bottom):
+        s = fl.packed_slots(c)[0]["slopes"]                              # [num_sequences, H]: s * alibi_batch_stride + h
+        starts = [s.slice_range(0, i)[0] for i in range(s.shape[0])]
+        assert c["softcap"] == 30.0 and s.shape == (len(fl.PACKED_LENS), c["H"]) and s.strides[0] * 4 == fl.PACKED_SLOPES_STEP
+        assert starts[0] < P31 and sum(a > P31 for a in starts) >= 2 and starts[-1] % (1 << 16) != 0
+        assert [n for n, a in zip(fl.PACKED_LENS, starts) if a > P31 and n > 0], "a sequence with rows reads its slopes past 2^31"
+    slots = fl.packed_slots(lse)[0]
+    assert slots["dlse"].offset > P32 and slots["dlse"].strides == slots["lse"].strides and slots["dlse"].offset != slots["lse"].offset
+    # bottom-right: sequences with fewer keys than rows have rows that see no key (they carry a NaN in dlse)
+    assert any(nk < n for n, nk in zip(fl.PACKED_LENS, fl.PACKED_LENS_K))

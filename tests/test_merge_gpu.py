@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 F16, BF16 = torch.float16, torch.bfloat16
 DTYPES = [F16, BF16]
 LN2 = R.LN2
-EPS = {F16: 2.0 ** -11, BF16: 2.0 ** -8}          # half an ulp at 1: one round-to-nearest of the I/O dtype
+EPS = R.MERGE_EPS                                # half an ulp at 1: one round-to-nearest of the I/O dtype
 
 
 def _dev():
@@ -161,37 +161,8 @@ def test_merge_kernels_match_the_float64_contract(nparts, D, nq, layout, dt, nat
     dlse = torch.randn(lses[0].shape, generator=g).to(dev)
     out, lse, dos, dls = _raw_merge(outs, lses, layout, natural, dout, dlse)
     vo, vl = _views(layout)
-    unit = 1.0 if natural else LN2                                         # the LSEs' unit in natural-log units
-    # float64 truth and its autograd in [B, H, N, D]; the garbage under weight 0 is replaced by zeros on the way in (the kernel does not read it)
-    lin = [(vl(l).double() * unit).requires_grad_(True) for l in lses]
-    oin = [torch.where(torch.isneginf(vl(l)).unsqueeze(-1), torch.zeros_like(vo(o)), vo(o)).double().requires_grad_(True) for o, l in zip(outs, lses)]
-    O64, L64 = R.merge64(oin, lin)
-    dead = torch.isneginf(L64.detach())
-    ((O64 * vo(dout).double()).sum() + (L64.masked_fill(dead, 0.0) * (vl(dlse).double() / unit)).masked_fill(dead, 0.0).sum()).backward()
-    O64, L64 = O64.detach(), L64.detach()
     tag = "merge %s n%d D%d Nq%d %s %s" % (str(dt)[6:], nparts, D, nq, layout, "natural" if natural else "log2")
-    # forward: f32 accumulation of <= 16 weighted 16-bit values, rounded once
-    out_v, lse2 = vo(out), vl(lse).double() * unit / LN2
-    bar_o = 2 * EPS[dt] * max(1.0, O64.abs().max().item())
-    err_o = (out_v.double() - O64).abs().max().item()
-    assert nq == 1 or dead[:, :, 0].all(), "row 0 of the case is dead"
-    assert torch.isneginf(lse2[dead]).all() and (out_v[dead] == 0).all(), (tag, "dead rows: O = 0, lse = -inf")
-    err_l = (lse2[~dead] - L64[~dead] / LN2).abs().max().item() if (~dead).any() else 0.0
-    print("%s: O err %.3g (bar %.3g), lse err %.3g log2 units (bar %.3g)" % (tag, err_o, bar_o, err_l, LSE_TOL))
-    assert err_o <= bar_o and err_l <= LSE_TOL, (tag, err_o, bar_o, err_l)
-    if nparts == 1:
-        assert torch.equal(out_v[~dead], vo(outs[0])[~dead]), "one part: its rows come back bit for bit"
-    # backward: dO_k = w_k dO rounded once; dlse_k in the LSEs' unit (f32 dot products over D against float64: 1e-4 relative is a wide margin over 2^-24)
-    for kx in range(nparts):
-        want, wl = oin[kx].grad, lin[kx].grad * unit
-        bar = 2 * EPS[dt] * max(1.0, want.abs().max().item())
-        err = (vo(dos[kx]).double() - want).abs().max().item()
-        bar_l = 1e-4 * max(1.0, wl.abs().max().item())
-        err_lk = (vl(dls[kx]).double() - wl).abs().max().item()
-        assert torch.isfinite(dos[kx].float()).all() and torch.isfinite(dls[kx]).all(), (tag, kx, "non-finite gradient")
-        assert err <= bar and err_lk <= bar_l, (tag, kx, err, bar, err_lk, bar_l)
-        zero_w = torch.isneginf(vl(lses[kx]))
-        assert (vl(dls[kx])[zero_w] == 0).all() and (vo(dos[kx])[zero_w] == 0).all(), (tag, kx, "zero-weight parts get zeros")
+    R.merge_check(tag, dt, natural, [vo(o) for o in outs], [vl(l) for l in lses], vo(dout), vl(dlse), vo(out), vl(lse), [vo(t) for t in dos], [vl(t) for t in dls])
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["f16", "bf16"])
