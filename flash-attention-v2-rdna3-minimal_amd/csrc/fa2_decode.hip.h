@@ -64,6 +64,14 @@ FA2_DEC_HD inline void decode_part_range(int64_t len, int64_t capacity_keys, int
     *n = lo < hi ? (int)(hi - lo) : 0;
 }
 
+// The key position new token `i` of `Nnew` is appended at (fa2_kvcache_append; csrc/fa2_kvappend.hip.h), host and device: `len` counts the valid keys
+// INCLUDING the new tokens, so token i sits at len - Nnew + i — the position decode's query row i has.  -1 = skipped: a position outside
+// [0, capacity_keys) is never clamped onto a valid row, because a clamped write would destroy a live key.
+FA2_DEC_HD inline int64_t kvappend_slot(int64_t len, int64_t capacity_keys, int Nnew, int i) {
+    const int64_t p = len - Nnew + i;
+    return p < 0 || p >= capacity_keys ? -1 : p;
+}
+
 struct DecodeParams {
     const void *q, *k, *v;
     void* o;

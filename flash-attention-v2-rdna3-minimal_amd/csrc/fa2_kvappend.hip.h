@@ -1,0 +1,216 @@
+// fa2_kvappend.hip.h — KV-cache append with rotary embedding and e4m3 quantisation (fa2_kvcache_append; include/fa2_gfx950.h has the contract, DESIGN.md
+// section 22 the reasons): the write side of the decode path.  One launch moves the new tokens' K rows and V rows into the cache — contiguous or paged,
+// 16-bit or e4m3 — at the key position only the device knows, and, when q is given, writes the rotated q rows to q_out.
+//
+// Work is (sequence, token) groups of R = 2 Hkv (+ H) rows: blockIdx.x is the group, so the length, the position, the page id and the table row are
+// uniform over the workgroup (scalar loads: read once per group, not per lane); blockIdx.y * blockDim.x + threadIdx.x is the lane's unit inside the
+// group (64, 128 or 256 lanes per workgroup: the smallest that holds the group's units, so that a K / V-only append of few heads idles no wave).
+// A unit is TWO 16-byte chunks of one row (8 columns of the 16-bit source each): chunks (2u, 2u + 1) — 16 consecutive columns, one 16-byte store into
+// an e4m3 cache — except in the rotated span of a non-interleaved (GPT-NeoX) row, where unit u < rotary_dim / 16 takes chunk u and its partner chunk
+// u + rotary_dim / 16: both halves of every pair are in one lane, and no value crosses lanes.  (rotary_dim is a multiple of 16, so the rotated span is
+// an even number of chunks and the units behind it are again the pairs (2u, 2u + 1).)
+//
+// Safety (the lengths and the block table are device data nobody validated): kvappend_slot (fa2_decode.hip.h, host and device) gives the key position
+// or "skip"; a page id outside [0, num_pages) skips too; the table row is clamped into [0, seqlen_ro - 1].  Nothing is clamped onto a valid cache row.
+// Every address is a 64-bit product of validated sizes and a value inside its range, so no device value can move a write outside the two caches.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include "fa2_fwd_kernel.hip.h"      // the vector types, pack2
+#endif
+#include "fa2_decode.hip.h"          // kvappend_slot
+#include "fa2_rotary.h"
+
+namespace fa2 {
+
+constexpr int kAppendThreads = 256;      // the largest workgroup; a group of fewer units runs 64 or 128 lanes (append_threads)
+inline int append_threads(int units) { return units <= 64 ? 64 : units <= 128 ? 128 : kAppendThreads; }
+
+struct KvAppendParams {
+    const void *k_new, *v_new;      // B x Hkv x Nnew x D, the I/O dtype
+    void *k_cache, *v_cache;        // decode's layouts; the I/O dtype or e4m3 bytes
+    const void* q;                  // B x H x Nnew x D or null
+    void* q_out;
+    const void *cos, *sin;          // [seqlen_ro, rot / 2], f32 or the I/O dtype (tab16); null: no rotary
+    const int* lens;                // cache_seqlens [B], device: the lengths AFTER the append
+    const int* bt;                  // block_table (paged) or null
+    const float *kd, *vd;           // e4m3 caches: descales [B, Hkv], device, null = 1.0
+    int B, Hkv, H, Nnew, D;
+    int rot, interleaved, tab16;
+    int page_size, num_pages;
+    int R, UR;                      // rows per (sequence, token) group; units per row = ceil(D / 16)
+    int64_t capacity_keys, seqlen_ro;
+    int64_t kns[3], vns[3], ks[3], vs[3], qs[3], qos[3];      // element strides {batch | page, head, row}
+    int64_t bts, ros, ds[2];        // block-table row stride, table row stride, descale strides {batch, K / V head}
+};
+
+#if defined(__HIPCC__)
+
+// one 32-bit word of two I/O dtype values -> f32
+template <bool BF16>
+__device__ __forceinline__ void append_unpack2(uint32_t w, float* lo, float* hi) {
+    if constexpr (BF16) {
+        *lo = __builtin_bit_cast(float, w << 16);
+        *hi = __builtin_bit_cast(float, w & 0xffff0000u);
+    } else {
+        const f16x2 h = __builtin_bit_cast(f16x2, w);
+        *lo = (float)h[0];
+        *hi = (float)h[1];
+    }
+}
+template <bool BF16>
+__device__ __forceinline__ void append_unpack8(u32x4 w, float (&x)[8]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) append_unpack2<BF16>(w[k], &x[2 * k], &x[2 * k + 1]);
+}
+
+// N (4 or 8) entries of a table row from entry j0 (a multiple of N) on: f32 or the I/O dtype
+template <bool BF16, int N>
+__device__ __forceinline__ void append_table(const void* tab, int64_t row_ofs, int j0, bool tab16, float (&c)[8]) {
+    if (tab16) {
+        const uint16_t* r = static_cast<const uint16_t*>(tab) + row_ofs + j0;
+        if constexpr (N == 8) {
+            append_unpack8<BF16>(*reinterpret_cast<const u32x4*>(r), c);
+        } else {
+            const u32x2 w = *reinterpret_cast<const u32x2*>(r);
+            append_unpack2<BF16>(w[0], &c[0], &c[1]);
+            append_unpack2<BF16>(w[1], &c[2], &c[3]);
+        }
+    } else {
+        const float* r = static_cast<const float*>(tab) + row_ofs + j0;
+#pragma unroll
+        for (int k = 0; k < N / 4; ++k) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(r + 4 * k);
+            c[4 * k] = v[0]; c[4 * k + 1] = v[1]; c[4 * k + 2] = v[2]; c[4 * k + 3] = v[3];
+        }
+    }
+}
+
+// eight f32 values -> eight e4m3 bytes: code = rne_e4m3(clamp(y / descale, +-448)).  The division is the correctly rounded one; the clamp is two
+// selects that a NaN falls through (this unit is compiled with NaNs honoured), so the convert never sees a value beyond the format's range and its
+// overflow mode does not matter; a NaN converts to a NaN code.
+__device__ __forceinline__ u32x2 append_quant8(const float (&y)[8], float d) {
+    float t[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float v = y[k] / d;
+        v = v > 448.0f ? 448.0f : v;
+        v = v < -448.0f ? -448.0f : v;
+        t[k] = v;
+    }
+    int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
+    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], w0, true);
+    int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], 0, false);
+    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], w1, true);
+    return (u32x2){(uint32_t)w0, (uint32_t)w1};
+}
+
+template <bool BF16>
+__device__ __forceinline__ u32x4 append_pack8(const float (&y)[8]) {
+    return (u32x4){pack2<BF16>(y[0], y[1]), pack2<BF16>(y[2], y[3]), pack2<BF16>(y[4], y[5]), pack2<BF16>(y[6], y[7])};
+}
+
+// FP8: the caches hold OCP e4m3 bytes; k_new, v_new, q, q_out stay in the I/O dtype.
+template <bool BF16, bool FP8>
+__global__ __launch_bounds__(kAppendThreads) void kvappend_kernel(const KvAppendParams p) {
+    const int tok = blockIdx.x;                                  // uniform: the (sequence, token) group
+    const int b = tok / p.Nnew, i = tok - b * p.Nnew;
+    const int unit = blockIdx.y * blockDim.x + threadIdx.x;
+    if (unit >= p.R * p.UR) return;
+    const int row = unit / p.UR, u = unit - row * p.UR;
+    const bool isq = row >= 2 * p.Hkv, isv = !isq && row >= p.Hkv;
+    const int h = isq ? row - 2 * p.Hkv : isv ? row - p.Hkv : row;
+
+    const int64_t len = p.lens[b];
+    const int64_t pos = len - p.Nnew + i;                        // the position q row i and new key i share
+    const int64_t slot = kvappend_slot(len, p.capacity_keys, p.Nnew, i);
+    if (!isq && slot < 0) return;                                // a skipped token: nothing is written
+
+    // the row's source and destination
+    const uint16_t* src;
+    char* dst;
+    if (isq) {
+        src = static_cast<const uint16_t*>(p.q) + b * p.qs[0] + h * p.qs[1] + i * p.qs[2];
+        dst = reinterpret_cast<char*>(static_cast<uint16_t*>(p.q_out) + b * p.qos[0] + h * p.qos[1] + i * p.qos[2]);
+    } else {
+        const int64_t* ns = isv ? p.vns : p.kns;
+        const int64_t* cs = isv ? p.vs : p.ks;
+        src = static_cast<const uint16_t*>(isv ? p.v_new : p.k_new) + b * ns[0] + h * ns[1] + i * ns[2];
+        int64_t base = b, r = slot;
+        if (p.page_size) {
+            const int64_t pg = slot / p.page_size;               // < the block-table entries per sequence: slot < capacity * page_size
+            const int pid = p.bt[b * p.bts + pg];
+            if (pid < 0 || pid >= p.num_pages) return;           // a page id outside the pool: skipped, never clamped onto a live page
+            base = pid;
+            r = slot - pg * p.page_size;
+        }
+        dst = static_cast<char*>(isv ? p.v_cache : p.k_cache) + (base * cs[0] + h * cs[1] + r * cs[2]) * (FP8 ? 1 : 2);
+    }
+
+    const int CH = p.D >> 3, rh = p.rot >> 4;
+    const bool rotate = p.cos != nullptr && !isv;
+    const bool halves = rotate && !p.interleaved && u < rh;     // chunk u and its partner chunk u + rh
+    const int ca = halves ? u : 2 * u, cb = halves ? u + rh : 2 * u + 1;
+    const bool hasb = cb < CH;
+    const u32x4 wa = *reinterpret_cast<const u32x4*>(src + 8 * ca);
+    const u32x4 wb = hasb ? *reinterpret_cast<const u32x4*>(src + 8 * cb) : (u32x4){0u, 0u, 0u, 0u};
+    const bool to8 = FP8 && !isq;
+
+    float xa[8], xb[8];
+    bool rota = false, rotb = false;
+    if (rotate || to8) {
+        append_unpack8<BF16>(wa, xa);
+        append_unpack8<BF16>(wb, xb);
+    }
+    if (rotate) {
+        const int64_t tr = rotary_table_row(pos, p.seqlen_ro) * p.ros;
+        float c[8], s[8];
+        if (halves) {
+            append_table<BF16, 8>(p.cos, tr, 8 * u, p.tab16 != 0, c);
+            append_table<BF16, 8>(p.sin, tr, 8 * u, p.tab16 != 0, s);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) rotary_pair(xa[e], xb[e], c[e], s[e], &xa[e], &xb[e]);
+            rota = rotb = true;
+        } else if (p.interleaved) {
+            if (8 * ca < p.rot) {
+                append_table<BF16, 4>(p.cos, tr, 4 * ca, p.tab16 != 0, c);
+                append_table<BF16, 4>(p.sin, tr, 4 * ca, p.tab16 != 0, s);
+#pragma unroll
+                for (int m = 0; m < 4; ++m) rotary_pair(xa[2 * m], xa[2 * m + 1], c[m], s[m], &xa[2 * m], &xa[2 * m + 1]);
+                rota = true;
+            }
+            if (hasb && 8 * cb < p.rot) {
+                append_table<BF16, 4>(p.cos, tr, 4 * cb, p.tab16 != 0, c);
+                append_table<BF16, 4>(p.sin, tr, 4 * cb, p.tab16 != 0, s);
+#pragma unroll
+                for (int m = 0; m < 4; ++m) rotary_pair(xb[2 * m], xb[2 * m + 1], c[m], s[m], &xb[2 * m], &xb[2 * m + 1]);
+                rotb = true;
+            }
+        }
+    }
+
+    if (to8) {
+        const float* dp = isv ? p.vd : p.kd;
+        const float d = dp ? dp[b * p.ds[0] + h * p.ds[1]] : 1.0f;
+        const u32x2 qa = append_quant8(xa, d);
+        if (hasb) {
+            const u32x2 qb = append_quant8(xb, d);
+            if (!halves) {                                       // 16 consecutive columns: one 16-byte store
+                *reinterpret_cast<u32x4*>(dst + 8 * ca) = (u32x4){qa[0], qa[1], qb[0], qb[1]};
+            } else {
+                *reinterpret_cast<u32x2*>(dst + 8 * ca) = qa;
+                *reinterpret_cast<u32x2*>(dst + 8 * cb) = qb;
+            }
+        } else {
+            *reinterpret_cast<u32x2*>(dst + 8 * ca) = qa;
+        }
+    } else {                                                     // a 16-bit row: what was not rotated lands bit for bit
+        *reinterpret_cast<u32x4*>(dst + 16 * ca) = rota ? append_pack8<BF16>(xa) : wa;
+        if (hasb) *reinterpret_cast<u32x4*>(dst + 16 * cb) = rotb ? append_pack8<BF16>(xb) : wb;
+    }
+}
+
+#endif  // __HIPCC__
+
+}  // namespace fa2

@@ -14,6 +14,7 @@
 #include "fa2_scoremod.h"
 #include "fa2_bwd_kernel.hip.h"      // FwdParams / BwdParams (templates are only instantiated where a launcher names them)
 #include "fa2_decode.hip.h"          // DecodeParams, decode_part_range
+#include "fa2_kvappend.hip.h"        // KvAppendParams, kvappend_slot, the rotary arithmetic
 
 #define FA2_HIDDEN __attribute__((visibility("hidden")))
 
@@ -261,7 +262,10 @@ FA2_LAUNCHER(launch_decode, (int HD, const DecodeParams& p, int row_tiles, hipSt
 // ... the same kernel over e4m3 caches (fa2_fwd_decode_fp8; decode_hip.cpp compiled with -DFA2_TU_FP8=1), and the one combine both end with
 FA2_LAUNCHER(launch_decode_fp8, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
 FA2_LAUNCHER(launch_decode_combine, (int HD, const DecodeParams& p, hipStream_t stream), (HD, p, stream))
+// KV-cache append (kvappend_hip.cpp; fa2_kvcache_append): the kernel of csrc/fa2_kvappend.hip.h into 16-bit caches, and (-DFA2_TU_FP8=1) into e4m3 caches
+FA2_LAUNCHER(launch_kvappend, (const KvAppendParams& p, hipStream_t stream), (p, stream))
+FA2_LAUNCHER(launch_kvappend_fp8, (const KvAppendParams& p, hipStream_t stream), (p, stream))
 
-constexpr int kBwdAsmParts = 3;      // passes the hand-scheduled backward covers: bit 0 = dQ, bit 1 = dK / dV
+constexpr int kBwdAsmParts = 3;     // passes the hand-scheduled backward covers: bit 0 = dQ, bit 1 = dK / dV
 
 }  // namespace fa2

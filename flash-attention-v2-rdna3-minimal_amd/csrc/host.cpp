@@ -1610,6 +1610,90 @@ size_t fa2_fwd_decode_fp8_workspace_bytes(int dtype, int B, int H, int Hkv, int 
     return fa2_fwd_decode_workspace_bytes(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits);
 }
 
+// ---- KV-cache append with rotary embedding and e4m3 quantisation: include/fa2_gfx950.h has the contract, csrc/fa2_kvappend.hip.h the kernel,
+// kvappend_hip.cpp its launch.  The checks run in the documented order.
+int fa2_kvappend_slot(int64_t len, int64_t capacity_keys, int Nnew, int i, int64_t* pos) {
+    if (!pos) return FA2_ERR_NULL_POINTER;
+    if (capacity_keys < 0 || Nnew < 1 || i < 0 || i >= Nnew) return FA2_ERR_BAD_SHAPE;
+    *pos = fa2::kvappend_slot(len, capacity_keys, Nnew, i);
+    return FA2_OK;
+}
+
+static int rotary_dim_check(int D, int rotary_dim) { return (rotary_dim < 16 || rotary_dim % 16 != 0 || rotary_dim > D) ? FA2_ERR_HEAD_DIM : FA2_OK; }
+
+int fa2_rotary_eval(int dtype, const void* x, const float* cos_row, const float* sin_row, int D, int rotary_dim, int interleaved, void* y) {
+    if (!x || !cos_row || !sin_row || !y) return FA2_ERR_NULL_POINTER;
+    if (D < 1) return FA2_ERR_BAD_SHAPE;
+    if ((D & 7) || D > kMaxBwdHeadDim) return FA2_ERR_HEAD_DIM;
+    if (int rc = rotary_dim_check(D, rotary_dim)) return rc;
+    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    const bool bf16 = dtype == FA2_DTYPE_BF16;
+    const uint16_t* in = static_cast<const uint16_t*>(x);
+    uint16_t* out = static_cast<uint16_t*>(y);
+    for (int j = rotary_dim; j < D; ++j) out[j] = in[j];                       // bit for bit
+    for (int j = 0; j < rotary_dim / 2; ++j) {
+        const int c1 = fa2::rotary_col1(j, rotary_dim, interleaved != 0), c2 = fa2::rotary_col2(j, rotary_dim, interleaved != 0);
+        float y1, y2;
+        fa2::rotary_pair(fa2::rot_io_to_f32(in[c1], bf16), fa2::rot_io_to_f32(in[c2], bf16), cos_row[j], sin_row[j], &y1, &y2);
+        out[c1] = fa2::rot_f32_to_io(y1, bf16);
+        out[c2] = fa2::rot_f32_to_io(y2, bf16);
+    }
+    return FA2_OK;
+}
+
+int fa2_kvcache_append(int dtype, int cache_format, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens,
+                       const int* block_table, int B, int Hkv, int Nnew, int D, int capacity, int page_size, int num_pages, const int64_t k_new_strides[3],
+                       const int64_t v_new_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], int64_t block_table_stride, const void* q,
+                       void* q_out, int H, int Nq, const int64_t q_strides[3], const int64_t q_out_strides[3], const void* rotary_cos,
+                       const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride, int rotary_interleaved,
+                       const float* k_descale, const float* v_descale, const int64_t descale_strides[2], void* hip_stream) {
+    const bool has_q = q || q_out, rotary = rotary_cos || rotary_sin, descaled = k_descale || v_descale;
+    if (any_null({k_new, v_new, k_cache, v_cache, cache_seqlens, k_new_strides, v_new_strides, k_strides, v_strides}) || (page_size > 0 && !block_table) ||
+        (has_q && any_null({q, q_out, q_strides, q_out_strides})) || (rotary && (!rotary_cos || !rotary_sin)) || (descaled && !descale_strides))
+        return FA2_ERR_NULL_POINTER;
+    if (B < 1 || Hkv < 1 || Nnew < 1 || D < 1 || capacity < 1 || page_size < 0 || page_size % 64 != 0 || (page_size > 0 && num_pages < 1))
+        return FA2_ERR_BAD_SHAPE;
+    if (page_size > 0 && (int64_t)capacity * page_size > 0x7fffffffLL - 64) return FA2_ERR_BAD_SHAPE;      // key positions are ints, as in decode
+    if (has_q && (!rotary || H < 1 || H % Hkv != 0 || Nq != Nnew)) return FA2_ERR_BAD_SHAPE;               // q rows exist to be rotated
+    if (rotary && (seqlen_ro < 1 || rotary_row_stride < 0)) return FA2_ERR_BAD_SHAPE;
+    if (descaled && (descale_strides[0] < 0 || descale_strides[1] < 0)) return FA2_ERR_BAD_SHAPE;
+    const bool fp8 = cache_format == FA2_CACHE_E4M3;
+    if ((D & (fp8 ? 15 : 7)) || D > kMaxBwdHeadDim) return FA2_ERR_HEAD_DIM;
+    if (rotary)
+        if (int rc = rotary_dim_check(D, rotary_dim)) return rc;
+    const bool tab32 = rotary_dtype == FA2_DTYPE_F32;
+    const auto cache_strides_ok = [fp8](const int64_t* st) { return strides3_ok(st) && (!fp8 || ((st[0] | st[1] | st[2]) & 15) == 0); };
+    if (!all_aligned16({k_new, v_new, k_cache, v_cache, q, q_out, rotary_cos, rotary_sin}) ||
+        ((reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(k_descale) |
+          reinterpret_cast<uintptr_t>(v_descale)) & 3u) ||
+        !strides3_ok(k_new_strides) || !strides3_ok(v_new_strides) || !cache_strides_ok(k_strides) || !cache_strides_ok(v_strides) ||
+        (has_q && (!strides3_ok(q_strides) || !strides3_ok(q_out_strides))) || block_table_stride < 0 ||
+        (rotary && rotary_row_stride % (tab32 ? 4 : 8) != 0))      // a table row starts on a 16-byte boundary
+        return FA2_ERR_ALIGNMENT;
+    if ((dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) || (cache_format != FA2_CACHE_16BIT && cache_format != FA2_CACHE_E4M3) ||
+        (rotary && !tab32 && rotary_dtype != dtype) || (descaled && !fp8))
+        return FA2_ERR_DTYPE;
+    fa2::KvAppendParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.k_new = k_new; p.v_new = v_new; p.k_cache = k_cache; p.v_cache = v_cache; p.q = q; p.q_out = q_out;
+    p.cos = rotary_cos; p.sin = rotary_sin; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr; p.kd = k_descale; p.vd = v_descale;
+    p.B = B; p.Hkv = Hkv; p.H = has_q ? H : 0; p.Nnew = Nnew; p.D = D;
+    p.rot = rotary ? rotary_dim : 0; p.interleaved = rotary_interleaved != 0; p.tab16 = !tab32;
+    p.page_size = page_size; p.num_pages = num_pages;
+    p.R = 2 * Hkv + p.H; p.UR = (D + 15) / 16;
+    p.capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
+    p.seqlen_ro = rotary ? seqlen_ro : 1;
+    for (int i = 0; i < 3; ++i) {
+        p.kns[i] = k_new_strides[i]; p.vns[i] = v_new_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i];
+        if (has_q) { p.qs[i] = q_strides[i]; p.qos[i] = q_out_strides[i]; }
+    }
+    p.bts = block_table_stride; p.ros = rotary_row_stride;
+    if (descaled) { p.ds[0] = descale_strides[0]; p.ds[1] = descale_strides[1]; }
+    if ((int64_t)B * Nnew > 0x7fffffffLL || ((int64_t)p.R * p.UR + fa2::kAppendThreads - 1) / fa2::kAppendThreads > 65535) return FA2_ERR_GRID;
+    return fp8 ? fa2::launch_kvappend_fp8(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream)
+               : fa2::launch_kvappend(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
+}
+
 int fa2_fwd_f16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_F16, FA2_FWD_PASS, hip_stream); }
 int fa2_fwd_bf16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_BF16, FA2_FWD_PASS, hip_stream); }
 int fa2_bwd_f16(FA2_BWD_ARGS(), void* hip_stream) { return fa2_bwd(FA2_DTYPE_F16, FA2_BWD_PASS, hip_stream); }

@@ -1101,58 +1101,31 @@ _FP8_CACHE = getattr(torch, "float8_e4m3fn", None)
 _FP8_OTHERS = tuple(d for d in (getattr(torch, n, None) for n in ("float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz")) if d is not None)
 
 
-def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None, scale=None, return_lse=False, num_splits=0, k_descale=None,
-                           v_descale=None):
-    """KV-cache decode attention (the flash_attn_with_kvcache shape): a few new query tokens per sequence against a preallocated cache.
-    q [B, Nq, H, D] fp16 / bf16.  Contiguous cache: k_cache / v_cache [B, Nmax, Hkv, D].  Paged cache: k_cache / v_cache [num_pages, page_size, Hkv, D]
-    with block_table int32 [B, max_pages] on q's device, page_size a multiple of 64.  Strided views are fine (D contiguous, strides multiples of 8
-    elements); a q that is not is copied, a cache that is not raises — copying the cache is what this call exists to avoid.
-    cache_seqlens: int32 [B] on q's device, the valid keys of each sequence INCLUDING the Nq new tokens (the caller has written their K / V).  The host
-    never reads it or the block table: no synchronisation, the call can be captured in a graph, and replaying the graph after either tensor changed in
-    place gives the result for the new contents.
-    Masking is bottom-right causal per sequence: query row i of sequence b sits at position len_b - Nq + i and sees the keys j <= that position (Nq = 1:
-    every valid key).  Rows at a negative position return zeros (lse -inf).  Keys at or beyond len_b and unused pages contribute nothing whatever
-    they hold; lengths and page ids are clamped into the cache in-kernel, so wrong ones give a wrong answer, never an out-of-bounds read.
-    Hkv divides H; D is 64 or 128; Nq * (H / Hkv) <= 64.  Anything else raises ValueError (longer chunks: flash_attention_varlen).
-    Returns o [B, Nq, H, D]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention combines such pairs).
-    num_splits: 0 = the library's plan, 1 .. 16 = that many parts per (sequence, K / V head).  Inference only: no backward.
-    FP8 caches: k_cache and v_cache may both be torch.float8_e4m3fn (OCP e4m3, gfx950's FP8; not e5m2, not fnuz) in the same two layouts, q staying
-    fp16 / bf16.  k_descale / v_descale: float32 [B, Hkv] on q's device (any strides), each optional, None = 1.0; K = float(k_cache) * k_descale[b, hkv],
-    V = float(v_cache) * v_descale[b, hkv].  They are device data the host never reads, like cache_seqlens: a captured graph replays correctly after
-    they changed in place.  An fp8 cache needs a contiguous head dim, 16-byte aligned storage and strides that are multiples of 16 elements.  A descale
-    with a 16-bit cache raises ValueError.  C-ABI fa2_fwd_decode_fp8; o and lse as for a 16-bit cache.
-    C-ABI fa2_fwd_decode: K and V are read once per K / V head group (the group's rows are the M rows of the MFMA), no atomics."""
-    if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cache_seqlens)) or q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
-        raise ValueError("fa2: flash_attention_decode takes q [B, Nq, H, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
-                         "with a block_table)")
-    if torch.is_grad_enabled() and (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad):
-        raise ValueError("fa2: flash_attention_decode is inference only (an input requires grad); " + _DECODE_ROUTE)
+def _cache_format(who, q, k_cache, v_cache, k_descale, v_descale):
+    """The cache-format checks flash_attention_decode and kvcache_append share (q: the 16-bit tensor whose dtype is the call's I/O dtype).  -> fp8"""
     if k_cache.dtype in _FP8_OTHERS or v_cache.dtype in _FP8_OTHERS:
-        raise ValueError("fa2: flash_attention_decode takes FP8 caches as torch.float8_e4m3fn (OCP e4m3) only: e5m2 and the fnuz formats are not "
-                         "served, got %s %s" % (k_cache.dtype, v_cache.dtype))
+        raise ValueError("fa2: %s takes FP8 caches as torch.float8_e4m3fn (OCP e4m3) only: e5m2 and the fnuz formats are not "
+                         "served, got %s %s" % (who, k_cache.dtype, v_cache.dtype))
     fp8 = _FP8_CACHE is not None and (k_cache.dtype == _FP8_CACHE or v_cache.dtype == _FP8_CACHE)
     if fp8 and k_cache.dtype != v_cache.dtype:
-        raise ValueError("fa2: flash_attention_decode takes k_cache and v_cache of one dtype (both float8_e4m3fn, or both q's dtype), got %s %s"
-                         % (k_cache.dtype, v_cache.dtype))
+        raise ValueError("fa2: %s takes k_cache and v_cache of one dtype (both float8_e4m3fn, or both q's dtype), got %s %s"
+                         % (who, k_cache.dtype, v_cache.dtype))
     if q.dtype not in (torch.float16, torch.bfloat16) or (not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype)):
-        raise ValueError("fa2: flash_attention_decode takes fp16 or bf16 q, k_cache, v_cache of one dtype (or float8_e4m3fn caches), got %s %s %s"
-                         % (q.dtype, k_cache.dtype, v_cache.dtype))
+        raise ValueError("fa2: %s takes fp16 or bf16 q, k_cache, v_cache of one dtype (or float8_e4m3fn caches), got %s %s %s"
+                         % (who, q.dtype, k_cache.dtype, v_cache.dtype))
     if not fp8 and (k_descale is not None or v_descale is not None):
         raise ValueError("fa2: k_descale / v_descale belong to float8_e4m3fn caches; this cache is %s" % k_cache.dtype)
-    B, Nq, H, D = q.shape
-    Hkv = k_cache.shape[2]
-    if v_cache.shape != k_cache.shape or k_cache.shape[3] != D:
-        raise ValueError("fa2: inconsistent q / k_cache / v_cache shapes %s %s %s" % (tuple(q.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
-    if B < 1 or Nq < 1 or Hkv < 1 or H % Hkv:
-        raise ValueError("fa2: the head count of the cache (%d) must divide the head count of q (%d), and B, Nq >= 1; %s" % (Hkv, H, _DECODE_ROUTE))
-    if D not in (64, 128):
-        raise ValueError("fa2: flash_attention_decode serves head dims 64 and 128, got %d; %s" % (D, _DECODE_ROUTE))
-    if Nq * (H // Hkv) > _DECODE_MAX_ROWS:
-        raise ValueError("fa2: flash_attention_decode serves Nq * (H / Hkv) <= %d query rows per K / V head, got %d * %d; %s"
-                         % (_DECODE_MAX_ROWS, Nq, H // Hkv, _DECODE_ROUTE))
+    return fp8
+
+
+def _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8, num_splits=None):
+    """The checks of the lengths, the block table, the descales, the devices and the cache strides that flash_attention_decode and kvcache_append share
+    (q: the tensor that sets the batch size and the device; num_splits: decode's, checked in its place).
+    -> capacity, page_size, num_pages, k_descale, v_descale (the descales made to share one stride pair)"""
+    B, Hkv = q.shape[0], k_cache.shape[2]
     if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous():
         raise ValueError("fa2: cache_seqlens must be a contiguous int32 tensor of shape [B] = [%d], got %s %s" % (B, cache_seqlens.dtype, tuple(cache_seqlens.shape)))
-    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _DECODE_MAX_SPLITS:
+    if num_splits is not None and (isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _DECODE_MAX_SPLITS):
         raise ValueError("fa2: num_splits is 0 (the library chooses) or 1 .. %d, got %r" % (_DECODE_MAX_SPLITS, num_splits))
     if block_table is None:
         if k_cache.shape[0] != B:
@@ -1189,6 +1162,160 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
             k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
     elif not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
         raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
+    return capacity, page_size, num_pages, k_descale, v_descale
+
+
+def _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8):
+    """The argument checks of kvcache_append that concern the new tokens, the rotary tables and q (the caches' own: _cache_format / _cache_layout).
+    -> rotary_dim (0: no rotary)"""
+    if not all(torch.is_tensor(t) and t.dim() == 4 for t in (k, v)) or k.shape != v.shape or k.dtype != v.dtype:
+        raise ValueError("fa2: kvcache_append takes k and v [B, Nnew, Hkv, D] of one shape and dtype")
+    B, Nnew, Hkv, D = k.shape
+    if k_cache.shape != v_cache.shape or k_cache.shape[2] != Hkv or k_cache.shape[3] != D:
+        raise ValueError("fa2: inconsistent k / k_cache / v_cache shapes %s %s %s" % (tuple(k.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
+    if B < 1 or Nnew < 1 or Hkv < 1:
+        raise ValueError("fa2: kvcache_append needs B, Nnew, Hkv >= 1, got k %s" % (tuple(k.shape),))
+    if D % (16 if fp8 else 8) or D > 512:
+        raise ValueError("fa2: kvcache_append serves head dims that are multiples of 8 (float8_e4m3fn caches: of 16) up to 512, got %d" % D)
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError("fa2: rotary_cos and rotary_sin come together")
+    rotary_dim = 0
+    if rotary_cos is not None:
+        if not all(torch.is_tensor(t) and t.dim() == 2 for t in (rotary_cos, rotary_sin)) or rotary_cos.shape != rotary_sin.shape or rotary_cos.shape[0] < 1:
+            raise ValueError("fa2: rotary_cos / rotary_sin must be 2-D tensors [seqlen_ro, rotary_dim / 2] of one shape")
+        if rotary_cos.dtype != rotary_sin.dtype or rotary_cos.dtype not in (torch.float32, k.dtype):
+            raise ValueError("fa2: rotary_cos / rotary_sin must share one dtype, float32 or the dtype of k (%s), got %s %s"
+                             % (k.dtype, rotary_cos.dtype, rotary_sin.dtype))
+        rotary_dim = 2 * rotary_cos.shape[1]
+        if rotary_dim < 16 or rotary_dim % 16 or rotary_dim > D:
+            raise ValueError("fa2: rotary_dim (2 * rotary_cos.shape[1]) must be a multiple of 16 between 16 and the head dim %d, got %d" % (D, rotary_dim))
+    if q is not None:
+        if rotary_dim == 0:
+            raise ValueError("fa2: kvcache_append takes q to rotate it: q without rotary_cos / rotary_sin has nothing to do")
+        if not torch.is_tensor(q) or q.dim() != 4 or q.dtype != k.dtype or q.shape[0] != B or q.shape[1] != Nnew or q.shape[3] != D or q.shape[2] < 1 or \
+                q.shape[2] % Hkv:
+            raise ValueError("fa2: kvcache_append takes q [B, Nnew, H, D] in k's dtype with Hkv dividing H, got %s for k %s"
+                             % ("%s %s" % (q.dtype, tuple(q.shape)) if torch.is_tensor(q) else repr(q), tuple(k.shape)))
+    return rotary_dim
+
+
+def kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, k_descale=None,
+                   v_descale=None, q=None):
+    """Append new tokens to a KV cache, in place: the write side of flash_attention_decode (the append and rotary parts of flash_attn_with_kvcache).
+    k / v [B, Nnew, Hkv, D] fp16 / bf16; the caches, cache_seqlens, block_table and the descales follow flash_attention_decode's rules (contiguous or
+    paged, 16-bit or float8_e4m3fn).  cache_seqlens[b] counts the valid keys INCLUDING the new tokens — the length after the append — so new token i
+    is written at key position len_b - Nnew + i, the position decode's query row i has.  A token whose position lies outside the cache, or whose page
+    id lies outside the pool, is skipped: nothing is written, nothing is clamped onto a live key, and no content of cache_seqlens / block_table can
+    move a write outside the caches.
+    rotary_cos / rotary_sin [seqlen_ro, rotary_dim / 2], float32 or k's dtype, rotary_dim a multiple of 16 up to D: new token i of k — and row i of q,
+    when q [B, Nnew, H, D] is given — is rotated by table row len_b - Nnew + i (clamped into the table).  rotary_interleaved=True pairs the columns
+    (2j, 2j + 1) (GPT-J), False pairs (j, j + rotary_dim / 2) (GPT-NeoX); columns at or beyond rotary_dim and all of v pass through bit for bit.
+    float8_e4m3fn caches store rne_e4m3(clamp(y / descale[b, hkv], +-448)) of the f32 value y (NaN -> a NaN code, +-Inf -> +-448, None = 1.0).
+    Returns the rotated q (a new tensor; q is not touched) when q and the tables are given, else None.  D: a multiple of 8 (e4m3: of 16) up to 512;
+    Nnew has no upper bound (a prefill chunk is a legitimate append).  The host reads no device value: the call can be captured in a graph.
+    Not served: cache_batch_idx, cache_leftpad, rotary without an append.  C-ABI fa2_kvcache_append."""
+    if not all(torch.is_tensor(t) for t in (k_cache, v_cache, k, v, cache_seqlens)) or k_cache.dim() != 4 or v_cache.dim() != 4 or k.dim() != 4:
+        raise ValueError("fa2: kvcache_append takes k / v [B, Nnew, Hkv, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
+                         "with a block_table)")
+    fp8 = _cache_format("kvcache_append", k, k_cache, v_cache, k_descale, v_descale)
+    rotary_dim = _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8)
+    capacity, page_size, num_pages, k_descale, v_descale = _cache_layout(k, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8)
+    B, Nnew, Hkv, D = k.shape
+    extra = tuple(t for t in (v, q, rotary_cos, rotary_sin) if t is not None)
+    if not all(t.is_cuda for t in extra) or any(t.device != k.device for t in extra):
+        raise RuntimeError("fa2: k, v, q and the rotary tables must be on the ROCm device of the caches")
+    k, v = (t if _decode_strides_ok(t) else t.contiguous() for t in (k, v))
+    H, q_out = 0, None
+    if q is not None:
+        H = q.shape[2]
+        q = q if _decode_strides_ok(q) else q.contiguous()
+        q_out = torch.empty((B, Nnew, H, D), dtype=q.dtype, device=q.device)
+    tab_code, seqlen_ro, ros = 0, 0, 0
+    if rotary_dim:
+        per16 = 16 // rotary_cos.element_size()
+        rotary_cos, rotary_sin = (t if t.stride(1) == 1 and t.stride(0) % per16 == 0 and not (t.data_ptr() & 15) else t.contiguous() for t in (rotary_cos, rotary_sin))
+        if rotary_cos.stride(0) != rotary_sin.stride(0):                   # the C-ABI takes one row stride
+            rotary_cos, rotary_sin = rotary_cos.contiguous(), rotary_sin.contiguous()
+        seqlen_ro, ros = rotary_cos.shape[0], rotary_cos.stride(0)
+    lib = _fa2_lib.load()
+    code = _fa2_lib.FA2_DTYPE_F16 if k.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+    if rotary_dim:
+        tab_code = _fa2_lib.FA2_DTYPE_F32 if rotary_cos.dtype == torch.float32 else code
+    dev = k.device.index if k.device.index is not None else _current_device()
+    s3 = _fa2_lib.strides3
+    bnhd = lambda t: s3(t.stride(0), t.stride(2), t.stride(1))      # noqa: E731
+    d0 = k_descale if k_descale is not None else v_descale
+    with torch.cuda.device(dev):
+        rc = lib.fa2_kvcache_append(code, _fa2_lib.FA2_CACHE_E4M3 if fp8 else _fa2_lib.FA2_CACHE_16BIT, k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
+                                    v_cache.data_ptr(), cache_seqlens.data_ptr(), None if block_table is None else block_table.data_ptr(), B, Hkv, Nnew, D,
+                                    capacity, page_size, num_pages, bnhd(k), bnhd(v), bnhd(k_cache), bnhd(v_cache),
+                                    0 if block_table is None else block_table.stride(0), None if q is None else q.data_ptr(),
+                                    None if q is None else q_out.data_ptr(), H, Nnew if q is not None else 0, None if q is None else bnhd(q),
+                                    None if q is None else bnhd(q_out), rotary_cos.data_ptr() if rotary_dim else None,
+                                    rotary_sin.data_ptr() if rotary_dim else None, tab_code, rotary_dim, seqlen_ro, ros, 1 if rotary_interleaved else 0,
+                                    None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
+                                    None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return q_out
+
+
+def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None, scale=None, return_lse=False, num_splits=0, k_descale=None,
+                           v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
+    """KV-cache decode attention (the flash_attn_with_kvcache shape): a few new query tokens per sequence against a preallocated cache.
+    q [B, Nq, H, D] fp16 / bf16.  Contiguous cache: k_cache / v_cache [B, Nmax, Hkv, D].  Paged cache: k_cache / v_cache [num_pages, page_size, Hkv, D]
+    with block_table int32 [B, max_pages] on q's device, page_size a multiple of 64.  Strided views are fine (D contiguous, strides multiples of 8
+    elements); a q that is not is copied, a cache that is not raises — copying the cache is what this call exists to avoid.
+    cache_seqlens: int32 [B] on q's device, the valid keys of each sequence INCLUDING the Nq new tokens (the caller has written their K / V).  The host
+    never reads it or the block table: no synchronisation, the call can be captured in a graph, and replaying the graph after either tensor changed in
+    place gives the result for the new contents.
+    Masking is bottom-right causal per sequence: query row i of sequence b sits at position len_b - Nq + i and sees the keys j <= that position (Nq = 1:
+    every valid key).  Rows at a negative position return zeros (lse -inf).  Keys at or beyond len_b and unused pages contribute nothing whatever
+    they hold; lengths and page ids are clamped into the cache in-kernel, so wrong ones give a wrong answer, never an out-of-bounds read.
+    Hkv divides H; D is 64 or 128; Nq * (H / Hkv) <= 64.  Anything else raises ValueError (longer chunks: flash_attention_varlen).
+    Returns o [B, Nq, H, D]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention combines such pairs).
+    num_splits: 0 = the library's plan, 1 .. 16 = that many parts per (sequence, K / V head).  Inference only: no backward.
+    FP8 caches: k_cache and v_cache may both be torch.float8_e4m3fn (OCP e4m3, gfx950's FP8; not e5m2, not fnuz) in the same two layouts, q staying
+    fp16 / bf16.  k_descale / v_descale: float32 [B, Hkv] on q's device (any strides), each optional, None = 1.0; K = float(k_cache) * k_descale[b, hkv],
+    V = float(v_cache) * v_descale[b, hkv].  They are device data the host never reads, like cache_seqlens: a captured graph replays correctly after
+    they changed in place.  An fp8 cache needs a contiguous head dim, 16-byte aligned storage and strides that are multiples of 16 elements.  A descale
+    with a 16-bit cache raises ValueError.  C-ABI fa2_fwd_decode_fp8; o and lse as for a 16-bit cache.
+    Append and rotary: with k / v [B, Nq, Hkv, D] given (both, k.shape[1] == Nq) the call first runs kvcache_append — the new tokens' K / V written
+    at positions len_b - Nq + i (cache_seqlens already counts them), k and q rotated by rotary_cos / rotary_sin when given, quantised for an e4m3
+    cache — and then the decode below on the rotated q, on one stream.  rotary_* without k / v raises ValueError.  With none of the five keywords
+    the call makes exactly the launches it made before they existed.
+    C-ABI fa2_fwd_decode: K and V are read once per K / V head group (the group's rows are the M rows of the MFMA), no atomics."""
+    if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cache_seqlens)) or q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("fa2: flash_attention_decode takes q [B, Nq, H, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
+                         "with a block_table)")
+    if torch.is_grad_enabled() and (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad):
+        raise ValueError("fa2: flash_attention_decode is inference only (an input requires grad); " + _DECODE_ROUTE)
+    fp8 = _cache_format("flash_attention_decode", q, k_cache, v_cache, k_descale, v_descale)
+    fused = k is not None or v is not None
+    if not fused and (rotary_cos is not None or rotary_sin is not None):
+        raise ValueError("fa2: rotary_cos / rotary_sin rotate the appended tokens: flash_attention_decode takes them together with k and v (rotary without "
+                         "an append is not served)")
+    B, Nq, H, D = q.shape
+    Hkv = k_cache.shape[2]
+    if v_cache.shape != k_cache.shape or k_cache.shape[3] != D:
+        raise ValueError("fa2: inconsistent q / k_cache / v_cache shapes %s %s %s" % (tuple(q.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
+    if B < 1 or Nq < 1 or Hkv < 1 or H % Hkv:
+        raise ValueError("fa2: the head count of the cache (%d) must divide the head count of q (%d), and B, Nq >= 1; %s" % (Hkv, H, _DECODE_ROUTE))
+    if D not in (64, 128):
+        raise ValueError("fa2: flash_attention_decode serves head dims 64 and 128, got %d; %s" % (D, _DECODE_ROUTE))
+    if Nq * (H // Hkv) > _DECODE_MAX_ROWS:
+        raise ValueError("fa2: flash_attention_decode serves Nq * (H / Hkv) <= %d query rows per K / V head, got %d * %d; %s"
+                         % (_DECODE_MAX_ROWS, Nq, H // Hkv, _DECODE_ROUTE))
+    if fused:
+        if not all(torch.is_tensor(t) and t.dim() == 4 for t in (k, v)) or k.dtype != q.dtype or k.shape[0] != B or k.shape[1] != Nq:
+            raise ValueError("fa2: flash_attention_decode takes k and v together, [B, Nq, Hkv, D] = [%d, %d, %d, %d] in q's dtype: the new tokens are the "
+                             "query rows' own (k.shape[1] == Nq); got %s %s" % (B, Nq, Hkv, D, tuple(getattr(k, "shape", ())), tuple(getattr(v, "shape", ()))))
+        _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q if rotary_cos is not None else None, fp8)
+    capacity, page_size, num_pages, k_descale, v_descale = _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8,
+                                                                        num_splits)
+    if fused:               # the append launch, then today's call on the rotated q: one stream, so the decode kernel reads what the append wrote
+        q_rot = kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, k_descale, v_descale,
+                               q=q if rotary_cos is not None else None)
+        q = q if q_rot is None else q_rot
     if not _decode_strides_ok(q):
         q = q.contiguous()
     if scale is None:

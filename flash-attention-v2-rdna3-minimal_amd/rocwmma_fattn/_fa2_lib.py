@@ -19,6 +19,8 @@ _OVERRIDE = os.environ.get("FA2_GFX950_LIB")      # developer A/B: load this bui
 
 FA2_DTYPE_F16 = 0
 FA2_DTYPE_BF16 = 1
+FA2_DTYPE_F32 = 2                                  # the rotary tables of fa2_kvcache_append only
+FA2_CACHE_16BIT, FA2_CACHE_E4M3 = 0, 1             # cache_format of fa2_kvcache_append
 FA2_BIAS_NONE, FA2_BIAS_IO_DTYPE, FA2_BIAS_F32, FA2_BIAS_BOOL = 0, 1, 2, 3     # bias_kind of fa2_fwd_bias
 
 FA2_KERNEL_HIP_256, FA2_KERNEL_HIP_128, FA2_KERNEL_ASM, FA2_KERNEL_HIP_BIAS = 1, 2, 3, 4              # fa2_fwd_plan_t.kernel
@@ -154,6 +156,15 @@ SYMBOLS = {
                             ctypes.c_void_p]),
     "fa2_fwd_decode_fp8_plan": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(DecodePlan)]),
     "fa2_fwd_decode_fp8_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
+    # KV-cache append: dtype cache_format, k_new v_new k_cache v_cache cache_seqlens block_table, B Hkv Nnew D capacity page_size num_pages, four stride
+    # triples, the block-table row stride, q q_out H Nq and their stride triples, cos sin rotary_dtype rotary_dim seqlen_ro row-stride interleaved,
+    # k_descale v_descale descale_strides, stream
+    "fa2_kvcache_append": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 7 + [_i64p] * 4 + [ctypes.c_int64] +
+                           [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [_i64p] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_int64, ctypes.c_int] +
+                           [ctypes.c_void_p] * 2 + [_i64p, ctypes.c_void_p]),
+    "fa2_kvappend_slot": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "fa2_rotary_eval": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 3 +
+                        [ctypes.c_void_p]),
     "fa2_scoremod_eval": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 2),
     "fa2_dropout_keep_mask": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 4 + [ctypes.c_void_p]),
     "fa2_dropout_threshold": (ctypes.c_int, [ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
@@ -366,6 +377,13 @@ def decode_part_range(length, capacity_keys, Nq, tile, nsplit, part):
     first, n = ctypes.c_int(), ctypes.c_int()
     check(load().fa2_decode_part_range(int(length), int(capacity_keys), int(Nq), int(tile), int(nsplit), int(part), ctypes.byref(first), ctypes.byref(n)))
     return first.value, n.value
+
+
+def kvappend_slot(length, capacity_keys, Nnew, i):
+    """fa2_kvappend_slot -> the key position new token `i` of `Nnew` is written at for a sequence of `length` keys after the append, or -1 (skipped)."""
+    pos = ctypes.c_int64()
+    check(load().fa2_kvappend_slot(int(length), int(capacity_keys), int(Nnew), int(i), ctypes.byref(pos)))
+    return pos.value
 
 
 def strides3(a, b, c):

@@ -640,7 +640,8 @@ int fa2_merge_bwd(int dtype, int nparts, const void* const* o_parts, const float
  * v_mfma_f32_16x16x32 in `row_tiles` tiles of 16, so K and V are fetched once per group.  With a split of 1 the kernel writes o / lse itself;
  * otherwise the parts leave normalised f32 rows and log2 LSEs of the live rows in the workspace (an empty part: lse = -inf, no O) and a second
  * kernel merges them and rounds once (all parts empty: zeros and -inf).  No atomics.
- * Not here: appending new K / V or rotary embedding inside the call, windows, soft-capping, ALiBi, a backward. */
+ * Writing the new tokens' K / V into the cache, rotating q and k and quantising to e4m3 is fa2_kvcache_append (its own section, below): one launch
+ * in front of this call, on the same stream.  Not here: windows, soft-capping, ALiBi, a backward. */
 enum { FA2_KERNEL_HIP_DECODE = 7 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
 typedef struct fa2_decode_plan_t {
     int kernel;        /* FA2_KERNEL_HIP_DECODE */
@@ -691,6 +692,60 @@ int fa2_fwd_decode_fp8(int dtype, const void* q, const void* k_cache, const void
                        int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
 int fa2_fwd_decode_fp8_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan);
 size_t fa2_fwd_decode_fp8_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits);
+
+/* ---- KV-cache append: the write side of the decode calls.  One launch writes the K and V rows of Nnew new tokens per sequence into the cache at the
+ * key position only the device knows, optionally rotates k (and q) by that position and optionally quantises to e4m3.
+ * Layout (element strides {batch, head, row}, D contiguous)
+ *   k_new, v_new  : B x Hkv x Nnew x D, the I/O dtype.
+ *   k_cache, v_cache, cache_seqlens, block_table, capacity, page_size, num_pages, block_table_stride : as in fa2_fwd_decode; cache_format says what the
+ *                   caches hold: FA2_CACHE_16BIT (the I/O dtype) or FA2_CACHE_E4M3 (OCP e4m3 bytes; element strides are bytes, as in fa2_fwd_decode_fp8).
+ *   q, q_out      : optional, both or neither: B x H x Nq x D with Nq == Nnew and Hkv dividing H.  q is NOT rotated in place: the rotated rows go to
+ *                   q_out, which the decode call then reads.  Refused without rotary tables (FA2_ERR_BAD_SHAPE): there would be nothing to do.
+ *   rotary_cos, rotary_sin : optional, both or neither: [seqlen_ro, rotary_dim / 2], rows rotary_row_stride elements apart, f32 (rotary_dtype
+ *                   FA2_DTYPE_F32) or the I/O dtype (rotary_dtype == dtype).  rotary_dim is a multiple of 16, 16 <= rotary_dim <= D.
+ *   k_descale, v_descale, descale_strides : as in fa2_fwd_decode_fp8; e4m3 caches only (FA2_ERR_DTYPE with a 16-bit cache).
+ * Semantics.  len = cache_seqlens[b] counts the valid keys INCLUDING the new tokens: it is the length after the append (a serving step increments the
+ * lengths in place, appends, decodes).  New token i sits at key position p = len - Nnew + i, the position query row i of the decode call has.  A token
+ * with p < 0 or p >= capacity_keys is SKIPPED, and so is a paged token whose page id lies outside [0, num_pages): nothing is written.  A position is
+ * never clamped onto a valid row — a clamped write would destroy a live key.  No content of cache_seqlens or block_table can make the kernel write
+ * outside the two cache allocations: a wrong value loses a token, it never faults.  fa2_kvappend_slot is the host side of that one mapping.
+ * Rotary: new token i of k and row i of q are rotated by table row clamp(p, 0, seqlen_ro - 1) (a table that is too short gives a wrong answer, not a
+ * fault).  rotary_interleaved != 0 pairs the columns (2j, 2j + 1) (GPT-J), 0 pairs (j, j + rotary_dim / 2) (GPT-NeoX); in f32
+ * y1 = fma(x1, c, -(x2 s)), y2 = fma(x1, s, x2 c), each rounded once to the destination format.  Columns at or beyond rotary_dim pass through bit for
+ * bit.  V is never rotated.  fa2_rotary_eval is the host side of that arithmetic (csrc/fa2_rotary.h).
+ * 16-bit cache: V, and K without rotary, land bit for bit; rotated K is rounded once (RNE).  e4m3 cache: code = rne_e4m3(clamp(y / descale[b, hkv],
+ * +-448)) with y the f32 value (rotated or not; never rounded to 16 bits first), a correctly rounded f32 division and the clamp in f32 BEFORE the
+ * convert.  NaN in gives an e4m3 NaN code, +-Inf saturates to +-448, a null descale is 1.0; a NaN, zero or negative descale spoils its own (sequence,
+ * K / V head) only and moves no address.
+ * The host reads no device value: the call can be captured in a graph and replays for the lengths, block table and descales of that time.
+ * Shapes: D a multiple of 8 (e4m3 caches: of 16) up to 512; Nnew >= 1 without an upper bound (a prefill chunk is a legitimate append); page_size a
+ * multiple of 64.  Checked in this order: null pointers (block_table only when paged; q, q_out and their strides together; cos and sin together;
+ * descale_strides when a descale is given), sizes (FA2_ERR_BAD_SHAPE: a size < 1, page_size, H % Hkv, Nq != Nnew, q without rotary, seqlen_ro < 1, a
+ * negative table or descale stride), head dim and rotary_dim (FA2_ERR_HEAD_DIM), alignment (16-byte tensors and tables, 4-byte cache_seqlens /
+ * block_table / descales, strides multiples of 8 — cache strides of an e4m3 cache multiples of 16 — with a positive row stride, a table row stride
+ * that keeps rows 16-byte aligned, a non-negative block-table stride), dtype (dtype, cache_format, rotary_dtype, a descale with a 16-bit cache),
+ * FA2_ERR_GRID (B * Nnew above 2^31 - 1).
+ * Kernel (csrc/fa2_kvappend.hip.h): one workgroup slice per (sequence, token); a lane moves two 16-byte chunks of one row — 16 consecutive columns,
+ * or, in the rotated span of a non-interleaved row, a chunk and its partner half a rotary span away, so that no value crosses lanes. */
+#define FA2_DTYPE_F32 2          /* the rotary tables of fa2_kvcache_append only */
+enum { FA2_CACHE_16BIT = 0, FA2_CACHE_E4M3 = 1 };
+int fa2_kvcache_append(int dtype, int cache_format, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                       const int* cache_seqlens, const int* block_table,
+                       int B, int Hkv, int Nnew, int D, int capacity, int page_size, int num_pages,
+                       const int64_t k_new_strides[3], const int64_t v_new_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                       int64_t block_table_stride,
+                       const void* q, void* q_out, int H, int Nq, const int64_t q_strides[3], const int64_t q_out_strides[3],
+                       const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride,
+                       int rotary_interleaved,
+                       const float* k_descale, const float* v_descale, const int64_t descale_strides[2], void* hip_stream);
+/* The key position new token i of Nnew is written at — the host side of the one function the kernel calls (csrc/fa2_decode.hip.h: kvappend_slot):
+ * *pos = len - Nnew + i when that lies in [0, capacity_keys), else -1 (skipped).  FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for capacity_keys < 0,
+ * Nnew < 1 or i outside [0, Nnew). */
+int fa2_kvappend_slot(int64_t len, int64_t capacity_keys, int Nnew, int i, int64_t* pos);
+/* One row of D 16-bit values x rotated into y with the arithmetic the kernel calls (csrc/fa2_rotary.h): cos_row / sin_row hold rotary_dim / 2 floats;
+ * columns at or beyond rotary_dim are copied bit for bit.  FA2_ERR_NULL_POINTER, FA2_ERR_BAD_SHAPE (D < 1), FA2_ERR_HEAD_DIM (D, rotary_dim),
+ * FA2_ERR_DTYPE, in this order. */
+int fa2_rotary_eval(int dtype, const void* x, const float* cos_row, const float* sin_row, int D, int rotary_dim, int interleaved, void* y);
 
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D
