@@ -33,6 +33,8 @@
 
 #include <type_traits>
 
+#include "fa2_scoremod.h"            // smod_cap, smod_alibi: the one copy of the score modifiers' arithmetic
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #include "fa2_fwd_kernel.hip.h"      // the vector types, pack2
 #define FA2_DEC_HD __host__ __device__
@@ -64,6 +66,26 @@ FA2_DEC_HD inline void decode_part_range(int64_t len, int64_t capacity_keys, int
     *n = lo < hi ? (int)(hi - lo) : 0;
 }
 
+// The lowest key any query row of a sequence sees under a window of `window_left` keys (-1: no window): row 0 sits at len - Nq and keeps the keys
+// j >= len - Nq - window_left.  len: already clamped.
+FA2_DEC_HD inline int decode_window_lo(int len, int Nq, int window_left) {
+    const int64_t lo = window_left < 0 ? 0 : (int64_t)len - Nq - window_left;
+    return lo < 0 ? 0 : (int)lo;
+}
+
+// ... and the key tiles of a part under that window (fa2_fwd_decode_window): the sweep starts at the tile that holds `lo`,
+// t0 = lo / tile, t1 = ceil(len / tile), per = ceil((t1 - t0) / nsplit), part s takes [t0 + s * per, min(t0 + (s + 1) * per, t1)).  A tile that lies
+// wholly below lo is in no part: its page is never addressed.  window_left = -1 gives exactly decode_part_range's answer.
+FA2_DEC_HD inline void decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int window_left, int tile, int nsplit, int part, int* first,
+                                                int* n) {
+    const int l = decode_clamp_len(len, capacity_keys);
+    const int t0 = decode_window_lo(l, Nq, window_left) / tile, t1 = (int)(((int64_t)l + tile - 1) / tile);
+    const int per = (t1 - t0 + nsplit - 1) / nsplit;
+    const int64_t lo = t0 + (int64_t)part * per, hi = lo + per < t1 ? lo + per : t1;
+    *first = lo < hi ? (int)lo : 0;
+    *n = lo < hi ? (int)(hi - lo) : 0;
+}
+
 // The key position new token `i` of `Nnew` is appended at (fa2_kvcache_append; csrc/fa2_kvappend.hip.h), host and device: `len` counts the valid keys
 // INCLUDING the new tokens, so token i sits at len - Nnew + i — the position decode's query row i has.  -1 = skipped: a position outside
 // [0, capacity_keys) is never clamped onto a valid row, because a clamped write would destroy a live key.
@@ -87,6 +109,12 @@ struct DecodeParams {
     float c;                    // scale * log2(e)
     const float *kd, *vd;       // FP8 caches: k_descale / v_descale [B, Hkv], device, null = 1.0
     int64_t ds[2];              // their element strides {batch, K / V head}
+    // the BAND kernels alone (fa2_fwd_decode_window), behind everything the plain kernels read:
+    int window_left;            // row i also needs j >= pos_i - window_left; -1 = no window
+    float softcap, inv_softcap; // 0 = no capping (make_scoremod's pair)
+    float scale;                // the scale in natural units (c = scale * log2(e) serves the plain kernels)
+    const float* slopes;        // ALiBi slopes f32 [.., H], device, null = none
+    int64_t slope_stride;       // elements between the slope vectors of two sequences (0: one vector for all)
 };
 
 // workspace bytes of a split call (live rows only)
@@ -136,7 +164,10 @@ __device__ __forceinline__ u32x4 decode_cvt8(uint32_t lo, uint32_t hi) {
 }
 
 // FP8: the caches hold OCP e4m3 bytes (KV = bytes per cache element); q, o and the arithmetic stay in the I/O dtype.
-template <int HD, bool BF16, int RT, bool FP8 = false>
+// BAND (fa2_fwd_decode_window): a sliding window, logit soft-capping and ALiBi slopes.  The part sweeps decode_window_part_range's
+// tiles; a score is formed in natural units, capped (csrc/fa2_scoremod.h), biased by -slope * (pos - key) and brought to log2 units, and only then
+// the position select — now with a lower bound — replaces it; V rows below the window's lowest key are zero bits like the rows at or beyond len.
+template <int HD, bool BF16, int RT, bool FP8 = false, bool BAND = false>
 __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeParams p) {
     constexpr int KV = FP8 ? 1 : 2;
     using cache_t = typename std::conditional<FP8, uint8_t, uint16_t>::type;
@@ -159,7 +190,8 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
     const int g = lane >> 4, qi = lane & 15;
     const int len = decode_clamp_len(p.lens[b], p.capacity_keys);
     int first, nt;
-    decode_part_range(len, p.capacity_keys, p.Nq, T, p.nsplit, part, &first, &nt);
+    if constexpr (BAND) decode_window_part_range(len, p.capacity_keys, p.Nq, p.window_left, T, p.nsplit, part, &first, &nt);
+    else decode_part_range(len, p.capacity_keys, p.Nq, T, p.nsplit, part, &first, &nt);
     const int64_t item = (int64_t)b * p.Hkv + hkv;
     float* const ws_o = p.ws + ((item * p.nsplit + part) * p.rows) * HD;
     float* const ws_l = p.ws + (int64_t)p.B * p.Hkv * p.nsplit * p.rows * HD + (item * p.nsplit + part) * p.rows;
@@ -173,6 +205,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
     const uint16_t* const qbase = static_cast<const uint16_t*>(p.q) + b * p.qs[0];
     u32x4 qf[RT][DC];
     int pos[RT];
+    float slope[BAND ? RT : 1];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int r = rt * 16 + qi;
@@ -183,9 +216,15 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
 #pragma unroll
         for (int dc = 0; dc < DC; ++dc)                // FP8: the column order of K's 16-byte loads
             qf[rt][dc] = live ? *reinterpret_cast<const u32x4*>(row + (FP8 ? 64 * (dc >> 1) + 8 * (dc & 1) : dc * 32)) : (u32x4){0u, 0u, 0u, 0u};
+        if constexpr (BAND) slope[rt] = live && p.slopes ? p.slopes[b * p.slope_stride + h] : 0.f;      // the QUERY head's, through the map that loads q
     }
-    // the score scale and the output scale of the item (FP8: the descales are device data, like the lengths)
-    float c = p.c, vd = 1.f;
+    // BAND: the widest distance pos - key a row keeps (no window: every distance a key at or below pos has; a key above pos has a negative one, which
+    // the unsigned comparison refuses), and the lowest key any row of the item keeps
+    const uint32_t reach = BAND ? (p.window_left < 0 ? 0x7fffffffu : (uint32_t)p.window_left) : 0u;
+    const int lo = BAND ? decode_window_lo(len, p.Nq, p.window_left) : 0;
+    (void)slope; (void)reach; (void)lo;
+    // the score scale and the output scale of the item (FP8: the descales are device data, like the lengths); BAND: the scale in natural units
+    float c = BAND ? p.scale : p.c, vd = 1.f;
     if constexpr (FP8) {
         const int64_t di = b * p.ds[0] + hkv * p.ds[1];
         if (p.kd) c *= p.kd[di];
@@ -223,7 +262,8 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
         for (int i = 0; i < VL; ++i) {
             const int ch = i * 64 + lane, kk = ch / VGR, col = ch % VGR;
             const u32x4 x = *reinterpret_cast<const u32x4*>(vb + (int64_t)(row0 + (kk < last ? kk : last)) * p.vs[2] + col * E16);
-            vr[i] = kk <= last ? x : (u32x4){0u, 0u, 0u, 0u};
+            if constexpr (BAND) vr[i] = kk <= last && key0 + kk >= lo ? x : (u32x4){0u, 0u, 0u, 0u};
+            else vr[i] = kk <= last ? x : (u32x4){0u, 0u, 0u, 0u};
         }
     };
 
@@ -290,7 +330,18 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int key = key0 + 16 * (j >> 2) + 4 * g + (j & 3);
-                x[j] = key <= pos[rt] ? s[rt][j >> 2][j & 3] * c : ninf;
+                if constexpr (BAND) {
+                    const int dist = pos[rt] - key;
+                    float y = s[rt][j >> 2][j & 3] * c;
+                    if (p.softcap > 0.f) {             // wave-uniform
+                        float th;
+                        y = smod_cap(y, p.softcap, p.inv_softcap, &th);
+                    }
+                    y = smod_alibi(y, slope[rt], (float)dist) * kSmodLog2e;
+                    x[j] = (uint32_t)dist <= reach ? y : ninf;      // the masks come last: 0 <= pos - key <= window_left
+                } else {
+                    x[j] = key <= pos[rt] ? s[rt][j >> 2][j & 3] * c : ninf;
+                }
                 mt = __builtin_fmaxf(mt, x[j]);
             }
             mt = decode_group_max(mt);

@@ -262,6 +262,9 @@ FA2_LAUNCHER(launch_decode, (int HD, const DecodeParams& p, int row_tiles, hipSt
 // ... the same kernel over e4m3 caches (fa2_fwd_decode_fp8; decode_hip.cpp compiled with -DFA2_TU_FP8=1), and the one combine both end with
 FA2_LAUNCHER(launch_decode_fp8, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
 FA2_LAUNCHER(launch_decode_combine, (int HD, const DecodeParams& p, hipStream_t stream), (HD, p, stream))
+// ... and the BAND instantiations of both (fa2_fwd_decode_window: a sliding window, soft-capping, ALiBi slopes), in the same units
+FA2_LAUNCHER(launch_decode_band, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
+FA2_LAUNCHER(launch_decode_band_fp8, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
 // KV-cache append (kvappend_hip.cpp; fa2_kvcache_append): the kernel of csrc/fa2_kvappend.hip.h into 16-bit caches, and (-DFA2_TU_FP8=1) into e4m3 caches
 FA2_LAUNCHER(launch_kvappend, (const KvAppendParams& p, hipStream_t stream), (p, stream))
 FA2_LAUNCHER(launch_kvappend_fp8, (const KvAppendParams& p, hipStream_t stream), (p, stream))

@@ -1503,27 +1503,50 @@ static int decode_split(int B, int Hkv, int row_tiles, int capacity_tiles, int n
     return S < 1 ? 1 : (int)S;
 }
 
-static int decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
+// window_left >= 0 (fa2_fwd_decode_window): "8 key tiles of the capacity" becomes "... of the span a sequence can sweep" — a window of window_left keys
+// under Nq rows touches at most ceil((window_left + Nq) / 32) + 1 tiles wherever it starts, so a short window in a long cache is not cut into parts
+// of a tile or two.  A window that reaches across the whole cache changes nothing.
+static int decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left,
+                       fa2_decode_plan_t* plan) {
+    if (window_left < -1) return FA2_ERR_BAD_SHAPE;
     int row_tiles = 0;
     if (int rc = decode_check_shape(B, H, Hkv, Nq, D, capacity, page_size, num_splits, &row_tiles)) return rc;
     if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
     const int64_t capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
+    int64_t span_tiles = (capacity_keys + fa2::kDecodeTile - 1) / fa2::kDecodeTile;
+    if (window_left >= 0) {
+        const int64_t w = ((int64_t)window_left + Nq + fa2::kDecodeTile - 1) / fa2::kDecodeTile + 1;
+        if (w < span_tiles) span_tiles = w;
+    }
     plan->kernel = FA2_KERNEL_HIP_DECODE;
     plan->row_tiles = row_tiles;
     plan->key_tile = fa2::kDecodeTile;
-    plan->nsplit = decode_split(B, Hkv, row_tiles, (int)((capacity_keys + fa2::kDecodeTile - 1) / fa2::kDecodeTile), num_splits);
+    plan->nsplit = decode_split(B, Hkv, row_tiles, (int)span_tiles, num_splits);
     return FA2_OK;
 }
 
 int fa2_fwd_decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
     if (!plan) return FA2_ERR_NULL_POINTER;
     std::memset(plan, 0, sizeof(*plan));
-    return decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, plan);
+    return decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, -1, plan);
 }
 
 size_t fa2_fwd_decode_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits) {
     fa2_decode_plan_t plan;
-    if (decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, &plan)) return 0;
+    if (decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, -1, &plan)) return 0;
+    return (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, Nq * (H / Hkv), D);
+}
+
+int fa2_fwd_decode_window_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left,
+                               fa2_decode_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    std::memset(plan, 0, sizeof(*plan));
+    return decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left, plan);
+}
+
+size_t fa2_fwd_decode_window_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left) {
+    fa2_decode_plan_t plan;
+    if (decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left, &plan)) return 0;
     return (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, Nq * (H / Hkv), D);
 }
 
@@ -1535,9 +1558,29 @@ int fa2_decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, 
     return FA2_OK;
 }
 
-// One body for fa2_fwd_decode and fa2_fwd_decode_fp8 (fp8: e4m3 caches, whose element strides are bytes; the descales and their strides are the fp8
-// entry's alone).  The checks run in the documented order.
-static int decode_run(bool fp8, int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens,
+int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int window_left, int tile, int nsplit, int part, int* first_tile, int* ntiles) {
+    if (!first_tile || !ntiles) return FA2_ERR_NULL_POINTER;
+    if (capacity_keys < 0 || capacity_keys > 0x7fffffffLL || Nq < 1 || tile < 1 || nsplit < 1 || nsplit > fa2::kDecodeMaxSplit || part < 0 || part >= nsplit ||
+        window_left < -1)
+        return FA2_ERR_BAD_SHAPE;
+    fa2::decode_window_part_range(len, capacity_keys, Nq, window_left, tile, nsplit, part, first_tile, ntiles);
+    return FA2_OK;
+}
+
+// What fa2_fwd_decode_window adds to a decode call.  The older entries pass none of it.
+struct DecodeBand {
+    bool checked = false;        // the new entry: cache_format is an argument to be validated
+    int cache_format = FA2_CACHE_16BIT;
+    int window_left = -1;
+    float softcap = 0.f;
+    const float* slopes = nullptr;
+    int64_t slope_stride = 0;
+};
+
+// One body for fa2_fwd_decode, fa2_fwd_decode_fp8 and fa2_fwd_decode_window (fp8: e4m3 caches, whose element strides are bytes; the descales and their
+// strides belong to e4m3 caches alone).  The checks run in the documented order; the window entry's arguments are checked where their kind is.
+// A call whose window reaches across the whole cache, without a cap and without slopes, runs the plain kernels: the same bits as the older entries.
+static int decode_run(const DecodeBand& band, int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens,
                       const int* block_table, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
                       const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
                       int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
@@ -1545,6 +1588,8 @@ static int decode_run(bool fp8, int dtype, const void* q, const void* k_cache, c
     if (any_null({q, k_cache, v_cache, o, lse, cache_seqlens, q_strides, k_strides, v_strides, o_strides, lse_strides}) || (page_size > 0 && !block_table) ||
         ((k_descale || v_descale) && !descale_strides))
         return FA2_ERR_NULL_POINTER;
+    const bool fp8 = band.cache_format == FA2_CACHE_E4M3;
+    if (band.window_left < -1 || band.slope_stride < 0) return FA2_ERR_BAD_SHAPE;
     int row_tiles = 0;
     if (int rc = decode_check_shape(B, H, Hkv, Nq, D, capacity, page_size, num_splits, &row_tiles)) return rc;
     if ((page_size > 0 && num_pages < 1) || lse_strides[0] < 0 || lse_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
@@ -1553,23 +1598,33 @@ static int decode_run(bool fp8, int dtype, const void* q, const void* k_cache, c
     const auto cache_strides_ok = [fp8](const int64_t* st) { return strides3_ok(st) && (!fp8 || ((st[0] | st[1] | st[2]) & 15) == 0); };
     if (!all_aligned16({q, k_cache, v_cache, o}) ||
         ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(block_table) |
-          reinterpret_cast<uintptr_t>(k_descale) | reinterpret_cast<uintptr_t>(v_descale)) & 3u) ||
+          reinterpret_cast<uintptr_t>(k_descale) | reinterpret_cast<uintptr_t>(v_descale) | reinterpret_cast<uintptr_t>(band.slopes)) & 3u) ||
         !strides3_ok(q_strides) || !cache_strides_ok(k_strides) || !cache_strides_ok(v_strides) || !strides3_ok(o_strides) || block_table_stride < 0)
         return FA2_ERR_ALIGNMENT;
+    const int64_t capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
+    // window_left >= capacity_keys - 1: EVERY row (the last one sits at len - 1 <= capacity_keys - 1) sees every key at or below it
+    const int window_left = (int64_t)band.window_left + 1 >= capacity_keys ? -1 : band.window_left;
     fa2_decode_plan_t plan;
-    if (int rc = decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, &plan)) return rc;       // (the dtype: after the alignment)
+    if (int rc = decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left, &plan)) return rc;       // (the dtype: after the alignment)
+    if (band.checked && ((band.cache_format != FA2_CACHE_16BIT && !fp8) || ((k_descale || v_descale) && !fp8))) return FA2_ERR_DTYPE;
     if (!std::isfinite(scale)) return FA2_ERR_SCALE;
+    if (!fa2::softcap_ok(band.softcap)) return FA2_ERR_SOFTCAP;
     if (B > 65535 || Hkv > 65535) return FA2_ERR_GRID;
     fa2::DecodeParams p;
     std::memset(&p, 0, sizeof(p));
     p.q = q; p.k = k_cache; p.v = v_cache; p.o = o; p.lse = lse; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr;
     p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.G = H / Hkv; p.rows = Nq * p.G;
     p.page_size = page_size; p.num_pages = num_pages; p.nsplit = plan.nsplit;
-    p.capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
+    p.capacity_keys = capacity_keys;
     for (int i = 0; i < 3; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; p.os[i] = o_strides[i]; }
     p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
     p.bts = block_table_stride;
     p.c = scale * 1.4426950408889634f;
+    const bool banded = window_left >= 0 || band.softcap > 0.f || band.slopes;
+    p.window_left = window_left;
+    p.softcap = band.softcap; p.inv_softcap = band.softcap > 0.f ? 1.0f / band.softcap : 0.f;
+    p.scale = scale;
+    p.slopes = band.slopes; p.slope_stride = band.slopes ? band.slope_stride : 0;
     p.kd = k_descale; p.vd = v_descale;
     if (k_descale || v_descale) { p.ds[0] = descale_strides[0]; p.ds[1] = descale_strides[1]; }
     if (plan.nsplit > 1) {
@@ -1578,15 +1633,18 @@ static int decode_run(bool fp8, int dtype, const void* q, const void* k_cache, c
         if (workspace_bytes < (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, p.rows, D)) return FA2_ERR_BAD_SHAPE;
         p.ws = static_cast<float*>(workspace);
     }
-    return fp8 ? fa2::launch_decode_fp8(dtype == FA2_DTYPE_BF16, D, p, plan.row_tiles, (hipStream_t)hip_stream)
-               : fa2::launch_decode(dtype == FA2_DTYPE_BF16, D, p, plan.row_tiles, (hipStream_t)hip_stream);
+    const bool bf16 = dtype == FA2_DTYPE_BF16;
+    hipStream_t const stream = (hipStream_t)hip_stream;
+    if (banded)
+        return fp8 ? fa2::launch_decode_band_fp8(bf16, D, p, plan.row_tiles, stream) : fa2::launch_decode_band(bf16, D, p, plan.row_tiles, stream);
+    return fp8 ? fa2::launch_decode_fp8(bf16, D, p, plan.row_tiles, stream) : fa2::launch_decode(bf16, D, p, plan.row_tiles, stream);
 }
 
 int fa2_fwd_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table,
                    int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3], const int64_t k_strides[3],
                    const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale,
                    int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    return decode_run(false, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
+    return decode_run(DecodeBand(), dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
                       v_strides, o_strides, lse_strides, block_table_stride, scale, nullptr, nullptr, nullptr, num_splits, workspace, workspace_bytes, hip_stream);
 }
 
@@ -1597,7 +1655,28 @@ int fa2_fwd_decode_fp8(int dtype, const void* q, const void* k_cache, const void
                        const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
                        int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
                        int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    return decode_run(true, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
+    DecodeBand band;
+    band.cache_format = FA2_CACHE_E4M3;
+    return decode_run(band, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
+                      v_strides, o_strides, lse_strides, block_table_stride, scale, k_descale, v_descale, descale_strides, num_splits, workspace, workspace_bytes,
+                      hip_stream);
+}
+
+// ---- ... with a sliding window, logit soft-capping and ALiBi slopes, on either cache format: the superset entry
+int fa2_fwd_decode_window(int dtype, int cache_format, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens,
+                          const int* block_table, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
+                          const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
+                          int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                          int window_left, float softcap, const float* alibi_slopes, int64_t alibi_stride, int num_splits, void* workspace,
+                          size_t workspace_bytes, void* hip_stream) {
+    DecodeBand band;
+    band.checked = true;
+    band.cache_format = cache_format;
+    band.window_left = window_left;
+    band.softcap = softcap;
+    band.slopes = alibi_slopes;
+    band.slope_stride = alibi_stride;
+    return decode_run(band, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
                       v_strides, o_strides, lse_strides, block_table_stride, scale, k_descale, v_descale, descale_strides, num_splits, workspace, workspace_bytes,
                       hip_stream);
 }

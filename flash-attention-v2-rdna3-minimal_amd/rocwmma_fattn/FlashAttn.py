@@ -1260,7 +1260,8 @@ def kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rota
 
 
 def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None, scale=None, return_lse=False, num_splits=0, k_descale=None,
-                           v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
+                           v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, window=None, softcap=0.0,
+                           alibi_slopes=None):
     """KV-cache decode attention (the flash_attn_with_kvcache shape): a few new query tokens per sequence against a preallocated cache.
     q [B, Nq, H, D] fp16 / bf16.  Contiguous cache: k_cache / v_cache [B, Nmax, Hkv, D].  Paged cache: k_cache / v_cache [num_pages, page_size, Hkv, D]
     with block_table int32 [B, max_pages] on q's device, page_size a multiple of 64.  Strided views are fine (D contiguous, strides multiples of 8
@@ -1283,6 +1284,15 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     at positions len_b - Nq + i (cache_seqlens already counts them), k and q rotated by rotary_cos / rotary_sin when given, quantised for an e4m3
     cache — and then the decode below on the rotated q, on one stream.  rotary_* without k / v raises ValueError.  With none of the five keywords
     the call makes exactly the launches it made before they existed.
+    Window, soft-capping, ALiBi: window = None, an int W or (left, right) as in flash_attention; only `left` is used — row i also needs
+    j >= pos_i - left — and a legal `right` has no effect, decode being causal.  A part sweeps only the key tiles that hold a key some row sees:
+    keys below len_b - Nq - left contribute nothing whatever they hold (like keys at or beyond len_b), and a page that holds only such keys is never
+    addressed, nor its block-table entry read — a server may have freed it.  softcap > 0: s = softcap * tanh(x / softcap) on the descaled, scaled
+    score x.  alibi_slopes: float32 [H] or [B, H] on q's device, s -= slope[b, h] * (pos_i - j) with h the QUERY head.  The masks come last; o and
+    lse are those of s.  The slopes are device data the host never reads: a captured graph follows slopes changed in place — CONTIGUOUS
+    slopes: a non-contiguous tensor is copied once per call, as in flash_attention, and a capture would follow the copy.  window and softcap are
+    host values, baked into a capture.  The three combine with each other and with everything above (the append runs first and is unaffected); with
+    none of them the call goes to the entries below with the launches it made before.  C-ABI fa2_fwd_decode_window.
     C-ABI fa2_fwd_decode: K and V are read once per K / V head group (the group's rows are the M rows of the MFMA), no atomics."""
     if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cache_seqlens)) or q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("fa2: flash_attention_decode takes q [B, Nq, H, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
@@ -1305,6 +1315,8 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     if Nq * (H // Hkv) > _DECODE_MAX_ROWS:
         raise ValueError("fa2: flash_attention_decode serves Nq * (H / Hkv) <= %d query rows per K / V head, got %d * %d; %s"
                          % (_DECODE_MAX_ROWS, Nq, H // Hkv, _DECODE_ROUTE))
+    window_left = _fa2_lib.parse_window(window)[0]
+    scoremod = _parse_scoremod(softcap, alibi_slopes, q, H, B)
     if fused:
         if not all(torch.is_tensor(t) and t.dim() == 4 for t in (k, v)) or k.dtype != q.dtype or k.shape[0] != B or k.shape[1] != Nq:
             raise ValueError("fa2: flash_attention_decode takes k and v together, [B, Nq, Hkv, D] = [%d, %d, %d, %d] in q's dtype: the new tokens are the "
@@ -1327,7 +1339,11 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     dev = q.device.index if q.device.index is not None else _current_device()
     with torch.cuda.device(dev):
         stream = _raw_stream(dev)
-        need = (lib.fa2_fwd_decode_fp8_workspace_bytes if fp8 else lib.fa2_fwd_decode_workspace_bytes)(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits)
+        banded = window_left >= 0 or scoremod is not None
+        if banded:
+            need = lib.fa2_fwd_decode_window_workspace_bytes(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left)
+        else:
+            need = (lib.fa2_fwd_decode_fp8_workspace_bytes if fp8 else lib.fa2_fwd_decode_workspace_bytes)(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits)
         ws = _workspace(need, q.device, dev, stream) if need else None
         if ws is None and _WS_POOL:
             _workspace_unused(dev, stream)
@@ -1338,10 +1354,14 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
                 s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)), s3(o.stride(0), o.stride(2), o.stride(1)),
                 _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0), float(scale))
         tail = (num_splits, None if ws is None else ws.data_ptr(), need, stream)
-        if fp8:
-            d0 = k_descale if k_descale is not None else v_descale
-            rc = lib.fa2_fwd_decode_fp8(*head, None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
-                                        None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), *tail)
+        d0 = k_descale if k_descale is not None else v_descale
+        descales = (None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
+                    None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)))
+        if banded:
+            rc = lib.fa2_fwd_decode_window(code, _fa2_lib.FA2_CACHE_E4M3 if fp8 else _fa2_lib.FA2_CACHE_16BIT, *head[1:], *descales, window_left,
+                                           *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), *tail)
+        elif fp8:
+            rc = lib.fa2_fwd_decode_fp8(*head, *descales, *tail)
         else:
             rc = lib.fa2_fwd_decode(*head, *tail)
     _fa2_lib.check(rc)

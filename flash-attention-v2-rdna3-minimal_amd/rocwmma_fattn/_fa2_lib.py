@@ -156,6 +156,14 @@ SYMBOLS = {
                             ctypes.c_void_p]),
     "fa2_fwd_decode_fp8_plan": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(DecodePlan)]),
     "fa2_fwd_decode_fp8_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
+    # ... with a sliding window, soft-capping and ALiBi slopes: cache_format after dtype, fa2_fwd_decode_fp8's list up to descale_strides, then
+    # window_left softcap alibi_slopes alibi_stride, then num_splits workspace bytes stream; the queries take window_left last (before the plan)
+    "fa2_fwd_decode_window": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 8 + [_i64p] * 5 +
+                              [ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, _i64p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
+                               ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fa2_fwd_decode_window_plan": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(DecodePlan)]),
+    "fa2_fwd_decode_window_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
+    "fa2_decode_window_part_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 2),
     # KV-cache append: dtype cache_format, k_new v_new k_cache v_cache cache_seqlens block_table, B Hkv Nnew D capacity page_size num_pages, four stride
     # triples, the block-table row stride, q q_out H Nq and their stride triples, cos sin rotary_dtype rotary_dim seqlen_ro row-stride interleaved,
     # k_descale v_descale descale_strides, stream
@@ -376,6 +384,22 @@ def decode_part_range(length, capacity_keys, Nq, tile, nsplit, part):
     """fa2_decode_part_range -> (first_tile, ntiles): the key tiles part `part` of `nsplit` sweeps for a sequence of `length` keys."""
     first, n = ctypes.c_int(), ctypes.c_int()
     check(load().fa2_decode_part_range(int(length), int(capacity_keys), int(Nq), int(tile), int(nsplit), int(part), ctypes.byref(first), ctypes.byref(n)))
+    return first.value, n.value
+
+
+def decode_window_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size=0, num_splits=0, window_left=-1):
+    """fa2_fwd_decode_window_plan: the plan of a decode call with a sliding window of `window_left` keys (-1: none; the 16-bit and e4m3 caches share it)."""
+    plan = DecodePlan()
+    check(load().fa2_fwd_decode_window_plan(int(dtype), int(B), int(H), int(Hkv), int(Nq), int(D), int(capacity), int(page_size), int(num_splits),
+                                            int(window_left), ctypes.byref(plan)))
+    return plan
+
+
+def decode_window_part_range(length, capacity_keys, Nq, window_left, tile, nsplit, part):
+    """fa2_decode_window_part_range -> (first_tile, ntiles): the key tiles part `part` of `nsplit` sweeps under a window of `window_left` keys."""
+    first, n = ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_decode_window_part_range(int(length), int(capacity_keys), int(Nq), int(window_left), int(tile), int(nsplit), int(part),
+                                              ctypes.byref(first), ctypes.byref(n)))
     return first.value, n.value
 
 

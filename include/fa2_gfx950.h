@@ -641,7 +641,7 @@ int fa2_merge_bwd(int dtype, int nparts, const void* const* o_parts, const float
  * otherwise the parts leave normalised f32 rows and log2 LSEs of the live rows in the workspace (an empty part: lse = -inf, no O) and a second
  * kernel merges them and rounds once (all parts empty: zeros and -inf).  No atomics.
  * Writing the new tokens' K / V into the cache, rotating q and k and quantising to e4m3 is fa2_kvcache_append (its own section, below): one launch
- * in front of this call, on the same stream.  Not here: windows, soft-capping, ALiBi, a backward. */
+ * in front of this call, on the same stream.  A sliding window, soft-capping and ALiBi slopes are fa2_fwd_decode_window (below).  Not here: a backward. */
 enum { FA2_KERNEL_HIP_DECODE = 7 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
 typedef struct fa2_decode_plan_t {
     int kernel;        /* FA2_KERNEL_HIP_DECODE */
@@ -692,6 +692,49 @@ int fa2_fwd_decode_fp8(int dtype, const void* q, const void* k_cache, const void
                        int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
 int fa2_fwd_decode_fp8_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan);
 size_t fa2_fwd_decode_fp8_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits);
+
+/* ---- ... with a sliding window, logit soft-capping and ALiBi slopes: the superset of the two entries above (cache_format: FA2_CACHE_16BIT or
+ * FA2_CACHE_E4M3, the constants of fa2_kvcache_append; descales belong to e4m3 caches).  Everything not named here is fa2_fwd_decode's / _fp8's.
+ * With len = clamp(cache_seqlens[b], 0, capacity_keys), query row i at pos = len - Nq + i, query head h and key j:
+ *     x  = (q_i . K_j) * scale                     f32; e4m3 cache: K_j is the descaled key, i.e. the factor is scale * k_descale[b, hkv]
+ *     s  = softcap > 0 ? softcap * tanh(x / softcap) : x
+ *     s -= slope[b, h] * (pos - j)                 alibi_slopes f32, DEVICE memory, slope[b, h] = alibi_slopes[b * alibi_stride + h] (alibi_stride 0:
+ *                                                  one [H] vector for every sequence); null = no ALiBi.  h is the QUERY head.
+ *     keep(j) = 0 <= j <= pos  and  (window_left < 0 or j >= pos - window_left)
+ * The masks come last; the softmax, P, O and the LSE are those of s.  The arithmetic is csrc/fa2_scoremod.h's (smod_cap, smod_alibi: the tanh and the
+ * float distance of the score-modifier entries).  Decode is causal, so the window has a left edge only.  window_left = -1, softcap = 0 and null
+ * slopes is fa2_fwd_decode / fa2_fwd_decode_fp8 bit for bit, and so is a window that reaches across the whole cache for EVERY row
+ * (window_left >= capacity_keys - 1: the last row sits at len - 1) without a cap and slopes: such calls run the plain kernels.  The slopes are device data the host never reads (a captured call
+ * follows slopes changed in place); window_left and softcap are host values.
+ * Keys below the window: lo = window_left < 0 ? 0 : max(0, len - Nq - window_left) is the lowest key any row of the sequence sees.  Keys below lo
+ * contribute nothing WHATEVER they hold, NaN and Inf in K and in V included — the guarantee keys at or beyond len have, kept the same way (scores
+ * replaced by -inf through a select on the position, V rows replaced by zero bits before they reach LDS).  A key tile that lies wholly below lo is
+ * never swept: its block-table entry is never read and its page never addressed, so a server may free the pages that fell out of the window.  The
+ * clamps of lengths, page ids and key indices apply to everything that is read; no device value, slopes included, can move an address.
+ * Parts: fa2_decode_window_part_range — t0 = lo / tile, t1 = ceil(len / tile), per = ceil((t1 - t0) / nsplit), part s sweeps
+ * [t0 + s * per, min(t0 + (s + 1) * per, t1)); with window_left = -1 it is fa2_decode_part_range.  Its argument checks are that function's, plus
+ * window_left < -1: FA2_ERR_BAD_SHAPE.
+ * Plan: fa2_fwd_decode_plan's rule with "at most one part per 8 key tiles of the capacity" read as "... of the span a sequence can sweep",
+ * min(capacity tiles, ceil((window_left + Nq) / 32) + 1) when window_left >= 0 — still a pure host function of shape, capacity, CU count and
+ * window_left, never of the lengths.  The workspace formula is unchanged.
+ * Checked in fa2_fwd_decode_fp8's order with the new arguments where their kind is: null pointers; sizes (also window_left < -1, alibi_stride < 0);
+ * head dim; alignment (also 4-byte alibi_slopes); dtype (also a cache_format that is neither constant, and descales with a 16-bit cache:
+ * FA2_ERR_DTYPE, fa2_kvcache_append's answer); scale; softcap (FA2_ERR_SOFTCAP, the rule of fa2_fwd_scoremod); FA2_ERR_GRID; the workspace.
+ * Every combination of D, row tiles, dtype and cache format is served; no instantiation uses scratch. */
+int fa2_fwd_decode_window(int dtype, int cache_format, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse,
+                          const int* cache_seqlens, const int* block_table,
+                          int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages,
+                          const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                          const int64_t lse_strides[2], int64_t block_table_stride, float scale,
+                          const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                          int window_left, float softcap, const float* alibi_slopes, int64_t alibi_stride,
+                          int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fa2_fwd_decode_window_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left,
+                               fa2_decode_plan_t* plan);
+size_t fa2_fwd_decode_window_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits,
+                                             int window_left);
+int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int window_left, int tile, int nsplit, int part, int* first_tile,
+                                 int* ntiles);
 
 /* ---- KV-cache append: the write side of the decode calls.  One launch writes the K and V rows of Nnew new tokens per sequence into the cache at the
  * key position only the device knows, optionally rotates k (and q) by that position and optionally quantises to e4m3.
