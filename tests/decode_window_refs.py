@@ -67,15 +67,20 @@ def keep_mask(n, Nq, window_left):
     return keep
 
 
-def _scores(q, k, scale, softcap, slopes, f):
-    """q [H, Nq, D], k [H, n, D] -> S [H, Nq, n] in dtype f, before the masks"""
+def _scores(q, k, scale, softcap, slopes, f, pos=None, cap_last=False):
+    """q [H, Nq, D], k [H, n, D] -> S [H, Nq, n] in dtype f, before the masks.  scale: a float, or a tensor that broadcasts over [H, Nq, n] (an e4m3
+    cache: scale * k_descale per head).  pos / cap_last exist for the mutants of tests/test_fuzz_decode.py: other row positions than len - Nq + i, and
+    the cap applied after the ALiBi term."""
     Nq, n = q.shape[1], k.shape[1]
-    S = (q.to(f) @ k.to(f).transpose(-1, -2)) * scale
-    if softcap > 0:
+    S = (q.to(f) @ k.to(f).transpose(-1, -2)) * (scale.to(f) if torch.is_tensor(scale) else scale)
+    if softcap > 0 and not cap_last:
         S = softcap * torch.tanh(S / softcap)
     if slopes is not None:
-        dist = ((n - Nq + torch.arange(Nq)).unsqueeze(1) - torch.arange(n).unsqueeze(0)).to(f)
+        pos = n - Nq + torch.arange(Nq) if pos is None else pos
+        dist = (pos.unsqueeze(1) - torch.arange(n).unsqueeze(0)).to(f)
         S = S - slopes.to(f)[:, None, None] * dist
+    if softcap > 0 and cap_last:
+        S = softcap * torch.tanh(S / softcap)
     return S
 
 
@@ -91,19 +96,24 @@ def _softmax_parts(S, keep):
     return E, l1, lse
 
 
-def truth64(q, k, v, scale, window_left, softcap, slopes):
-    """float64 of the contract for [H, Nq, D] q and [H, n, D] k / v (grouped heads already expanded), n >= 1 -> O [H, Nq, D], lse [H, Nq] (log2 units)."""
-    keep = keep_mask(k.shape[1], q.shape[1], window_left)
-    E, l1, lse = _softmax_parts(_scores(q, k, scale, softcap, slopes, torch.float64), keep)
+def truth64(q, k, v, scale, window_left, softcap, slopes, keep=None, pos=None, cap_last=False):
+    """float64 of the contract for [H, Nq, D] q and [H, n, D] k / v (grouped heads already expanded), n >= 1 -> O [H, Nq, D], lse [H, Nq] (log2 units).
+    keep (bool [Nq, n]), pos and cap_last replace the contract's own mask, row positions and order: the mutants of tests/test_fuzz_decode.py."""
+    keep = keep_mask(k.shape[1], q.shape[1], window_left) if keep is None else keep
+    E, l1, lse = _softmax_parts(_scores(q, k, scale, softcap, slopes, torch.float64, pos, cap_last), keep)
     return (E / l1) @ v.double(), lse
 
 
-def emulate(q, k, v, scale, window_left, softcap, slopes, dt):
-    """The kernel's contract in torch: f32 scores, transform and sums; P rounded to the I/O dtype; O rounded once."""
+def emulate(q, k, v, scale, window_left, softcap, slopes, dt, v_descale=None):
+    """The kernel's contract in torch: f32 scores, transform and sums; P rounded to the I/O dtype; O rounded once.  An e4m3 cache with general descales
+    (tests/test_decode_fp8_gpu.py: test_general_descales_against_float64): k and v are the upcast codes, k_descale is folded into `scale` (a tensor
+    [H, 1, 1]) and v_descale [H, 1, 1] multiplies the normalised f32 row before its one rounding."""
     keep = keep_mask(k.shape[1], q.shape[1], window_left)
     E, l1, lse = _softmax_parts(_scores(q, k, scale, softcap, slopes, torch.float32), keep)
-    O = ((E.to(dt).float() @ v.float()) / l1).to(dt)
-    return O.double(), lse.double()
+    O = (E.to(dt).float() @ v.float()) / l1
+    if v_descale is not None:
+        O = O * v_descale.float()
+    return O.to(dt).double(), lse.double()
 
 
 def bars_of(true, emu, code):
