@@ -926,7 +926,7 @@ const char* fa2_error_string(int code) {
     return "fa2: unknown error code";
 }
 
-const char* fa2_version(void) { return "fa2_gfx950 0.9 (D=128 forward (sum-check fast bodies) + backward and D=64 forward: hand-scheduled 4-wave asm bodies; other head dims up to 512: HIP kernels; mfma32x32x16, lds-dma; KV-split tail rounds; attention bias / mask, forward + backward)"; }
+const char* fa2_version(void) { return "fa2_gfx950 0.9 (D=128 forward (sum-check fast bodies) + backward and D=64 forward: hand-scheduled 4-wave asm bodies, head dims 136 to 256 forward too; short KV sweeps and the other head dims up to 512: HIP kernels; lds-dma; KV-split tail rounds; attention bias / mask, forward + backward; KV-cache decode and append)"; }
 
 // The parameters every dense forward / backward entry point takes, after `dtype` and up to the flag word (HKV: FA2_HKV where the entry point has an Hkv;
 // include/fa2_gfx950.h spells every list out), the same as arguments, and a call description filled from them by field name (the MHA entry points' Hkv is H).
@@ -1478,13 +1478,62 @@ int fa2_merge_bwd(int dtype, int nparts, const void* const* o_parts, const float
 }
 
 // ---- KV-cache decode attention: include/fa2_gfx950.h has the contract, csrc/fa2_decode.hip.h the kernel, decode_hip.cpp its launches
+// A KV cache as the decode and the append calls are handed it, and its checks, each inside one error class (the callers keep the classes' order).
+struct CacheDesc {
+    const void *k = nullptr, *v = nullptr;                  // [B, capacity, Hkv, D], or a pool [num_pages, page_size, Hkv, D] under a block table
+    const int* block_table = nullptr;
+    int capacity = 0, page_size = 0, num_pages = 0;         // capacity: key slots (page_size == 0) or block-table entries per sequence
+    const int64_t *ks = nullptr, *vs = nullptr;             // {batch | page, head, row} in elements, which are bytes in an e4m3 cache
+    int64_t bts = 0;
+    int format = FA2_CACHE_16BIT;
+    const float *kd = nullptr, *vd = nullptr;               // per (sequence, K / V head) descales: e4m3 caches alone
+    const int64_t* ds = nullptr;
+    bool fp8() const { return format == FA2_CACHE_E4M3; }
+    bool descaled() const { return kd || vd; }
+    int64_t capacity_keys() const { return page_size ? (int64_t)capacity * page_size : capacity; }
+};
+// null pointers: a paged call needs its block table, a descale its stride pair
+static bool cache_null(const CacheDesc& c) { return any_null({c.k, c.v, c.ks, c.vs}) || (c.page_size > 0 && !c.block_table) || (c.descaled() && !c.ds); }
+// sizes: pages of a multiple of 64 keys, and key positions are ints
+static bool cache_paging_ok(const CacheDesc& c) {
+    return c.capacity >= 1 && c.page_size >= 0 && c.page_size % 64 == 0 && (c.page_size == 0 || (int64_t)c.capacity * c.page_size <= 0x7fffffffLL - 64);
+}
+// sizes again, apart from the above: the decode call looks at these two after the head dim, the append before it
+static bool cache_extent_ok(const CacheDesc& c) { return !(c.page_size > 0 && c.num_pages < 1) && !(c.descaled() && (c.ds[0] < 0 || c.ds[1] < 0)); }
+// alignment: a 16-byte load covers 8 columns of a 16-bit cache and 16 of an e4m3 one
+static bool cache_aligned(const CacheDesc& c) {
+    const auto strides_ok = [&c](const int64_t* st) { return strides3_ok(st) && (!c.fp8() || ((st[0] | st[1] | st[2]) & 15) == 0); };
+    return all_aligned16({c.k, c.v}) && strides_ok(c.ks) && strides_ok(c.vs) && c.bts >= 0 &&
+           !((reinterpret_cast<uintptr_t>(c.block_table) | reinterpret_cast<uintptr_t>(c.kd) | reinterpret_cast<uintptr_t>(c.vd)) & 3u);
+}
+// dtype: one of the two formats, descales with e4m3 alone (fa2_fwd_decode and fa2_fwd_decode_fp8 state a format that passes)
+static bool cache_format_ok(const CacheDesc& c) { return (c.format == FA2_CACHE_16BIT || c.fp8()) && (!c.descaled() || c.fp8()); }
+
+// One decode call, described: the three entries fill it by field name; a plan or size query fills the sizes alone.
+struct DecodeCall : CacheDesc {
+    int dtype = 0, B = 0, H = 0, Hkv = 0, Nq = 0, D = 0;
+    const void* q = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    const int* lens = nullptr;
+    const int64_t *qs = nullptr, *os = nullptr, *ls = nullptr;      // {batch, head, row}; ls: {batch, head}
+    float scale = 0.f;
+    int window_left = -1;                                           // what fa2_fwd_decode_window adds: the older entries leave these four as they are
+    float softcap = 0.f;
+    const float* slopes = nullptr;
+    int64_t slope_stride = 0;
+    int num_splits = 0;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    void* stream = nullptr;
+};
+
 // The sizes of a decode call, in the documented order (shape, then head dim); *row_tiles: the row tiles the kernel runs (1, 2 or 4).
-static int decode_check_shape(int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int* row_tiles) {
-    if (B < 1 || H < 1 || Hkv < 1 || Nq < 1 || D < 1 || capacity < 1 || Hkv > H || H % Hkv != 0) return FA2_ERR_BAD_SHAPE;
-    const int64_t rows = (int64_t)Nq * (H / Hkv);
-    if (rows > fa2::kDecodeMaxRows || page_size < 0 || page_size % 64 != 0 || num_splits < 0 || num_splits > fa2::kDecodeMaxSplit) return FA2_ERR_BAD_SHAPE;
-    if (page_size > 0 && (int64_t)capacity * page_size > 0x7fffffffLL - 64) return FA2_ERR_BAD_SHAPE;      // key positions are ints
-    if (D != 64 && D != 128) return FA2_ERR_HEAD_DIM;
+static int decode_check_shape(const DecodeCall& c, int* row_tiles) {
+    if (c.B < 1 || c.H < 1 || c.Hkv < 1 || c.Nq < 1 || c.D < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return FA2_ERR_BAD_SHAPE;
+    const int64_t rows = (int64_t)c.Nq * (c.H / c.Hkv);
+    if (rows > fa2::kDecodeMaxRows || !cache_paging_ok(c) || c.num_splits < 0 || c.num_splits > fa2::kDecodeMaxSplit) return FA2_ERR_BAD_SHAPE;
+    if (c.D != 64 && c.D != 128) return FA2_ERR_HEAD_DIM;
     const int rt = (int)((rows + 15) / 16);
     *row_tiles = rt == 3 ? 4 : rt;
     return FA2_OK;
@@ -1506,48 +1555,53 @@ static int decode_split(int B, int Hkv, int row_tiles, int capacity_tiles, int n
 // window_left >= 0 (fa2_fwd_decode_window): "8 key tiles of the capacity" becomes "... of the span a sequence can sweep" — a window of window_left keys
 // under Nq rows touches at most ceil((window_left + Nq) / 32) + 1 tiles wherever it starts, so a short window in a long cache is not cut into parts
 // of a tile or two.  A window that reaches across the whole cache changes nothing.
-static int decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left,
-                       fa2_decode_plan_t* plan) {
+static int decode_plan(const DecodeCall& c, int window_left, fa2_decode_plan_t* plan) {
     if (window_left < -1) return FA2_ERR_BAD_SHAPE;
     int row_tiles = 0;
-    if (int rc = decode_check_shape(B, H, Hkv, Nq, D, capacity, page_size, num_splits, &row_tiles)) return rc;
-    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
-    const int64_t capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
-    int64_t span_tiles = (capacity_keys + fa2::kDecodeTile - 1) / fa2::kDecodeTile;
+    if (int rc = decode_check_shape(c, &row_tiles)) return rc;
+    if (c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    int64_t span_tiles = (c.capacity_keys() + fa2::kDecodeTile - 1) / fa2::kDecodeTile;
     if (window_left >= 0) {
-        const int64_t w = ((int64_t)window_left + Nq + fa2::kDecodeTile - 1) / fa2::kDecodeTile + 1;
+        const int64_t w = ((int64_t)window_left + c.Nq + fa2::kDecodeTile - 1) / fa2::kDecodeTile + 1;
         if (w < span_tiles) span_tiles = w;
     }
     plan->kernel = FA2_KERNEL_HIP_DECODE;
     plan->row_tiles = row_tiles;
     plan->key_tile = fa2::kDecodeTile;
-    plan->nsplit = decode_split(B, Hkv, row_tiles, (int)span_tiles, num_splits);
+    plan->nsplit = decode_split(c.B, c.Hkv, row_tiles, (int)span_tiles, c.num_splits);
     return FA2_OK;
 }
 
-int fa2_fwd_decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
-    if (!plan) return FA2_ERR_NULL_POINTER;
-    std::memset(plan, 0, sizeof(*plan));
-    return decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, -1, plan);
+// The f32 parts a split call leaves between its two launches.
+static size_t decode_ws_need(const DecodeCall& c, const fa2_decode_plan_t& plan) {
+    return (size_t)fa2::decode_ws_bytes((int64_t)c.B * c.Hkv, plan.nsplit, c.Nq * (c.H / c.Hkv), c.D);
 }
 
-size_t fa2_fwd_decode_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits) {
-    fa2_decode_plan_t plan;
-    if (decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, -1, &plan)) return 0;
-    return (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, Nq * (H / Hkv), D);
-}
+// The sizes every decode query and entry takes, filled by field name.
+#define FA2_DECODE_SIZES(c) \
+    DecodeCall c;           \
+    c.dtype = dtype; c.B = B; c.H = H; c.Hkv = Hkv; c.Nq = Nq; c.D = D; c.capacity = capacity; c.page_size = page_size; c.num_splits = num_splits
 
 int fa2_fwd_decode_window_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left,
                                fa2_decode_plan_t* plan) {
     if (!plan) return FA2_ERR_NULL_POINTER;
     std::memset(plan, 0, sizeof(*plan));
-    return decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left, plan);
+    FA2_DECODE_SIZES(c);
+    return decode_plan(c, window_left, plan);
 }
 
 size_t fa2_fwd_decode_window_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left) {
     fa2_decode_plan_t plan;
-    if (decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left, &plan)) return 0;
-    return (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, Nq * (H / Hkv), D);
+    FA2_DECODE_SIZES(c);
+    return decode_plan(c, window_left, &plan) ? 0 : decode_ws_need(c, plan);
+}
+
+int fa2_fwd_decode_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
+    return fa2_fwd_decode_window_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, -1, plan);
+}
+
+size_t fa2_fwd_decode_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits) {
+    return fa2_fwd_decode_window_workspace_bytes(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, -1);
 }
 
 int fa2_decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, int nsplit, int part, int* first_tile, int* ntiles) {
@@ -1567,85 +1621,71 @@ int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int
     return FA2_OK;
 }
 
-// What fa2_fwd_decode_window adds to a decode call.  The older entries pass none of it.
-struct DecodeBand {
-    bool checked = false;        // the new entry: cache_format is an argument to be validated
-    int cache_format = FA2_CACHE_16BIT;
-    int window_left = -1;
-    float softcap = 0.f;
-    const float* slopes = nullptr;
-    int64_t slope_stride = 0;
-};
-
 // One body for fa2_fwd_decode, fa2_fwd_decode_fp8 and fa2_fwd_decode_window (fp8: e4m3 caches, whose element strides are bytes; the descales and their
 // strides belong to e4m3 caches alone).  The checks run in the documented order; the window entry's arguments are checked where their kind is.
 // A call whose window reaches across the whole cache, without a cap and without slopes, runs the plain kernels: the same bits as the older entries.
-static int decode_run(const DecodeBand& band, int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens,
-                      const int* block_table, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
-                      const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
-                      int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
-                      int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    if (any_null({q, k_cache, v_cache, o, lse, cache_seqlens, q_strides, k_strides, v_strides, o_strides, lse_strides}) || (page_size > 0 && !block_table) ||
-        ((k_descale || v_descale) && !descale_strides))
-        return FA2_ERR_NULL_POINTER;
-    const bool fp8 = band.cache_format == FA2_CACHE_E4M3;
-    if (band.window_left < -1 || band.slope_stride < 0) return FA2_ERR_BAD_SHAPE;
+static int decode_run(const DecodeCall& c) {
+    if (any_null({c.q, c.o, c.lse, c.lens, c.qs, c.os, c.ls}) || cache_null(c)) return FA2_ERR_NULL_POINTER;
+    if (c.window_left < -1 || c.slope_stride < 0) return FA2_ERR_BAD_SHAPE;
     int row_tiles = 0;
-    if (int rc = decode_check_shape(B, H, Hkv, Nq, D, capacity, page_size, num_splits, &row_tiles)) return rc;
-    if ((page_size > 0 && num_pages < 1) || lse_strides[0] < 0 || lse_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
-    if ((k_descale || v_descale) && (descale_strides[0] < 0 || descale_strides[1] < 0)) return FA2_ERR_BAD_SHAPE;
-    // a 16-byte load covers 8 columns of a 16-bit cache and 16 of an e4m3 one
-    const auto cache_strides_ok = [fp8](const int64_t* st) { return strides3_ok(st) && (!fp8 || ((st[0] | st[1] | st[2]) & 15) == 0); };
-    if (!all_aligned16({q, k_cache, v_cache, o}) ||
-        ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(block_table) |
-          reinterpret_cast<uintptr_t>(k_descale) | reinterpret_cast<uintptr_t>(v_descale) | reinterpret_cast<uintptr_t>(band.slopes)) & 3u) ||
-        !strides3_ok(q_strides) || !cache_strides_ok(k_strides) || !cache_strides_ok(v_strides) || !strides3_ok(o_strides) || block_table_stride < 0)
+    if (int rc = decode_check_shape(c, &row_tiles)) return rc;
+    if (!cache_extent_ok(c) || c.ls[0] < 0 || c.ls[1] < 0) return FA2_ERR_BAD_SHAPE;
+    if (!all_aligned16({c.q, c.o}) || !cache_aligned(c) ||
+        ((reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.lens) | reinterpret_cast<uintptr_t>(c.slopes)) & 3u) || !strides3_ok(c.qs) ||
+        !strides3_ok(c.os))
         return FA2_ERR_ALIGNMENT;
-    const int64_t capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
     // window_left >= capacity_keys - 1: EVERY row (the last one sits at len - 1 <= capacity_keys - 1) sees every key at or below it
-    const int window_left = (int64_t)band.window_left + 1 >= capacity_keys ? -1 : band.window_left;
+    const int window_left = (int64_t)c.window_left + 1 >= c.capacity_keys() ? -1 : c.window_left;
     fa2_decode_plan_t plan;
-    if (int rc = decode_plan(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left, &plan)) return rc;       // (the dtype: after the alignment)
-    if (band.checked && ((band.cache_format != FA2_CACHE_16BIT && !fp8) || ((k_descale || v_descale) && !fp8))) return FA2_ERR_DTYPE;
-    if (!std::isfinite(scale)) return FA2_ERR_SCALE;
-    if (!fa2::softcap_ok(band.softcap)) return FA2_ERR_SOFTCAP;
-    if (B > 65535 || Hkv > 65535) return FA2_ERR_GRID;
+    if (int rc = decode_plan(c, window_left, &plan)) return rc;       // (the dtype: after the alignment)
+    if (!cache_format_ok(c)) return FA2_ERR_DTYPE;
+    if (!std::isfinite(c.scale)) return FA2_ERR_SCALE;
+    if (!fa2::softcap_ok(c.softcap)) return FA2_ERR_SOFTCAP;
+    if (c.B > 65535 || c.Hkv > 65535) return FA2_ERR_GRID;
     fa2::DecodeParams p;
     std::memset(&p, 0, sizeof(p));
-    p.q = q; p.k = k_cache; p.v = v_cache; p.o = o; p.lse = lse; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr;
-    p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.G = H / Hkv; p.rows = Nq * p.G;
-    p.page_size = page_size; p.num_pages = num_pages; p.nsplit = plan.nsplit;
-    p.capacity_keys = capacity_keys;
-    for (int i = 0; i < 3; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; p.os[i] = o_strides[i]; }
-    p.ls[0] = lse_strides[0]; p.ls[1] = lse_strides[1];
-    p.bts = block_table_stride;
-    p.c = scale * 1.4426950408889634f;
-    const bool banded = window_left >= 0 || band.softcap > 0.f || band.slopes;
+    p.q = c.q; p.k = c.k; p.v = c.v; p.o = c.o; p.lse = c.lse; p.lens = c.lens; p.bt = c.page_size > 0 ? c.block_table : nullptr;
+    p.B = c.B; p.H = c.H; p.Hkv = c.Hkv; p.Nq = c.Nq; p.G = c.H / c.Hkv; p.rows = c.Nq * p.G;
+    p.page_size = c.page_size; p.num_pages = c.num_pages; p.nsplit = plan.nsplit;
+    p.capacity_keys = c.capacity_keys();
+    for (int i = 0; i < 3; ++i) { p.qs[i] = c.qs[i]; p.ks[i] = c.ks[i]; p.vs[i] = c.vs[i]; p.os[i] = c.os[i]; }
+    p.ls[0] = c.ls[0]; p.ls[1] = c.ls[1];
+    p.bts = c.bts;
+    p.c = c.scale * 1.4426950408889634f;
+    const bool banded = window_left >= 0 || c.softcap > 0.f || c.slopes;
     p.window_left = window_left;
-    p.softcap = band.softcap; p.inv_softcap = band.softcap > 0.f ? 1.0f / band.softcap : 0.f;
-    p.scale = scale;
-    p.slopes = band.slopes; p.slope_stride = band.slopes ? band.slope_stride : 0;
-    p.kd = k_descale; p.vd = v_descale;
-    if (k_descale || v_descale) { p.ds[0] = descale_strides[0]; p.ds[1] = descale_strides[1]; }
+    p.softcap = c.softcap; p.inv_softcap = c.softcap > 0.f ? 1.0f / c.softcap : 0.f;
+    p.scale = c.scale;
+    p.slopes = c.slopes; p.slope_stride = c.slopes ? c.slope_stride : 0;
+    p.kd = c.kd; p.vd = c.vd;
+    if (c.descaled()) { p.ds[0] = c.ds[0]; p.ds[1] = c.ds[1]; }
     if (plan.nsplit > 1) {
-        if (!workspace) return FA2_ERR_NULL_POINTER;
-        if (!aligned16(workspace)) return FA2_ERR_ALIGNMENT;
-        if (workspace_bytes < (size_t)fa2::decode_ws_bytes((int64_t)B * Hkv, plan.nsplit, p.rows, D)) return FA2_ERR_BAD_SHAPE;
-        p.ws = static_cast<float*>(workspace);
+        if (!c.ws) return FA2_ERR_NULL_POINTER;
+        if (!aligned16(c.ws)) return FA2_ERR_ALIGNMENT;
+        if (c.ws_bytes < decode_ws_need(c, plan)) return FA2_ERR_BAD_SHAPE;
+        p.ws = static_cast<float*>(c.ws);
     }
-    const bool bf16 = dtype == FA2_DTYPE_BF16;
-    hipStream_t const stream = (hipStream_t)hip_stream;
+    const bool bf16 = c.dtype == FA2_DTYPE_BF16;
+    hipStream_t const stream = (hipStream_t)c.stream;
     if (banded)
-        return fp8 ? fa2::launch_decode_band_fp8(bf16, D, p, plan.row_tiles, stream) : fa2::launch_decode_band(bf16, D, p, plan.row_tiles, stream);
-    return fp8 ? fa2::launch_decode_fp8(bf16, D, p, plan.row_tiles, stream) : fa2::launch_decode(bf16, D, p, plan.row_tiles, stream);
+        return c.fp8() ? fa2::launch_decode_band_fp8(bf16, c.D, p, plan.row_tiles, stream) : fa2::launch_decode_band(bf16, c.D, p, plan.row_tiles, stream);
+    return c.fp8() ? fa2::launch_decode_fp8(bf16, c.D, p, plan.row_tiles, stream) : fa2::launch_decode(bf16, c.D, p, plan.row_tiles, stream);
 }
+
+// ... and the arguments the three entries share, by field name (include/fa2_gfx950.h spells every list out)
+#define FA2_DECODE_CALL(c)                                                                                                          \
+    FA2_DECODE_SIZES(c);                                                                                                            \
+    c.q = q; c.k = k_cache; c.v = v_cache; c.o = o; c.lse = lse; c.lens = cache_seqlens; c.block_table = block_table; c.num_pages = num_pages; \
+    c.qs = q_strides; c.ks = k_strides; c.vs = v_strides; c.os = o_strides; c.ls = lse_strides; c.bts = block_table_stride; c.scale = scale;   \
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = hip_stream
+#define FA2_DECODE_DESCALES(c) c.kd = k_descale; c.vd = v_descale; c.ds = descale_strides
 
 int fa2_fwd_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table,
                    int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3], const int64_t k_strides[3],
                    const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale,
                    int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    return decode_run(DecodeBand(), dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
-                      v_strides, o_strides, lse_strides, block_table_stride, scale, nullptr, nullptr, nullptr, num_splits, workspace, workspace_bytes, hip_stream);
+    FA2_DECODE_CALL(c);
+    return decode_run(c);
 }
 
 // ---- ... on e4m3 caches with per (sequence, K / V head) descales.  The fp8 kernel sweeps the same 32-key tiles under the same split rule, so the plan
@@ -1655,11 +1695,10 @@ int fa2_fwd_decode_fp8(int dtype, const void* q, const void* k_cache, const void
                        const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
                        int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
                        int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    DecodeBand band;
-    band.cache_format = FA2_CACHE_E4M3;
-    return decode_run(band, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
-                      v_strides, o_strides, lse_strides, block_table_stride, scale, k_descale, v_descale, descale_strides, num_splits, workspace, workspace_bytes,
-                      hip_stream);
+    FA2_DECODE_CALL(c);
+    FA2_DECODE_DESCALES(c);
+    c.format = FA2_CACHE_E4M3;
+    return decode_run(c);
 }
 
 // ---- ... with a sliding window, logit soft-capping and ALiBi slopes, on either cache format: the superset entry
@@ -1669,16 +1708,11 @@ int fa2_fwd_decode_window(int dtype, int cache_format, const void* q, const void
                           int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
                           int window_left, float softcap, const float* alibi_slopes, int64_t alibi_stride, int num_splits, void* workspace,
                           size_t workspace_bytes, void* hip_stream) {
-    DecodeBand band;
-    band.checked = true;
-    band.cache_format = cache_format;
-    band.window_left = window_left;
-    band.softcap = softcap;
-    band.slopes = alibi_slopes;
-    band.slope_stride = alibi_stride;
-    return decode_run(band, dtype, q, k_cache, v_cache, o, lse, cache_seqlens, block_table, B, H, Hkv, Nq, D, capacity, page_size, num_pages, q_strides, k_strides,
-                      v_strides, o_strides, lse_strides, block_table_stride, scale, k_descale, v_descale, descale_strides, num_splits, workspace, workspace_bytes,
-                      hip_stream);
+    FA2_DECODE_CALL(c);
+    FA2_DECODE_DESCALES(c);
+    c.format = cache_format;
+    c.window_left = window_left; c.softcap = softcap; c.slopes = alibi_slopes; c.slope_stride = alibi_stride;
+    return decode_run(c);
 }
 
 int fa2_fwd_decode_fp8_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, fa2_decode_plan_t* plan) {
@@ -1726,32 +1760,25 @@ int fa2_kvcache_append(int dtype, int cache_format, const void* k_new, const voi
                        void* q_out, int H, int Nq, const int64_t q_strides[3], const int64_t q_out_strides[3], const void* rotary_cos,
                        const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride, int rotary_interleaved,
                        const float* k_descale, const float* v_descale, const int64_t descale_strides[2], void* hip_stream) {
-    const bool has_q = q || q_out, rotary = rotary_cos || rotary_sin, descaled = k_descale || v_descale;
-    if (any_null({k_new, v_new, k_cache, v_cache, cache_seqlens, k_new_strides, v_new_strides, k_strides, v_strides}) || (page_size > 0 && !block_table) ||
-        (has_q && any_null({q, q_out, q_strides, q_out_strides})) || (rotary && (!rotary_cos || !rotary_sin)) || (descaled && !descale_strides))
+    CacheDesc c;
+    c.k = k_cache; c.v = v_cache; c.block_table = block_table; c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    c.ks = k_strides; c.vs = v_strides; c.bts = block_table_stride; c.format = cache_format; c.kd = k_descale; c.vd = v_descale; c.ds = descale_strides;
+    const bool has_q = q || q_out, rotary = rotary_cos || rotary_sin, fp8 = c.fp8();
+    if (any_null({k_new, v_new, cache_seqlens, k_new_strides, v_new_strides}) || cache_null(c) || (has_q && any_null({q, q_out, q_strides, q_out_strides})) ||
+        (rotary && (!rotary_cos || !rotary_sin)))
         return FA2_ERR_NULL_POINTER;
-    if (B < 1 || Hkv < 1 || Nnew < 1 || D < 1 || capacity < 1 || page_size < 0 || page_size % 64 != 0 || (page_size > 0 && num_pages < 1))
-        return FA2_ERR_BAD_SHAPE;
-    if (page_size > 0 && (int64_t)capacity * page_size > 0x7fffffffLL - 64) return FA2_ERR_BAD_SHAPE;      // key positions are ints, as in decode
+    if (B < 1 || Hkv < 1 || Nnew < 1 || D < 1 || !cache_paging_ok(c) || !cache_extent_ok(c)) return FA2_ERR_BAD_SHAPE;
     if (has_q && (!rotary || H < 1 || H % Hkv != 0 || Nq != Nnew)) return FA2_ERR_BAD_SHAPE;               // q rows exist to be rotated
     if (rotary && (seqlen_ro < 1 || rotary_row_stride < 0)) return FA2_ERR_BAD_SHAPE;
-    if (descaled && (descale_strides[0] < 0 || descale_strides[1] < 0)) return FA2_ERR_BAD_SHAPE;
-    const bool fp8 = cache_format == FA2_CACHE_E4M3;
     if ((D & (fp8 ? 15 : 7)) || D > kMaxBwdHeadDim) return FA2_ERR_HEAD_DIM;
     if (rotary)
         if (int rc = rotary_dim_check(D, rotary_dim)) return rc;
     const bool tab32 = rotary_dtype == FA2_DTYPE_F32;
-    const auto cache_strides_ok = [fp8](const int64_t* st) { return strides3_ok(st) && (!fp8 || ((st[0] | st[1] | st[2]) & 15) == 0); };
-    if (!all_aligned16({k_new, v_new, k_cache, v_cache, q, q_out, rotary_cos, rotary_sin}) ||
-        ((reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(k_descale) |
-          reinterpret_cast<uintptr_t>(v_descale)) & 3u) ||
-        !strides3_ok(k_new_strides) || !strides3_ok(v_new_strides) || !cache_strides_ok(k_strides) || !cache_strides_ok(v_strides) ||
-        (has_q && (!strides3_ok(q_strides) || !strides3_ok(q_out_strides))) || block_table_stride < 0 ||
+    if (!all_aligned16({k_new, v_new, q, q_out, rotary_cos, rotary_sin}) || !cache_aligned(c) || (reinterpret_cast<uintptr_t>(cache_seqlens) & 3u) ||
+        !strides3_ok(k_new_strides) || !strides3_ok(v_new_strides) || (has_q && (!strides3_ok(q_strides) || !strides3_ok(q_out_strides))) ||
         (rotary && rotary_row_stride % (tab32 ? 4 : 8) != 0))      // a table row starts on a 16-byte boundary
         return FA2_ERR_ALIGNMENT;
-    if ((dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) || (cache_format != FA2_CACHE_16BIT && cache_format != FA2_CACHE_E4M3) ||
-        (rotary && !tab32 && rotary_dtype != dtype) || (descaled && !fp8))
-        return FA2_ERR_DTYPE;
+    if ((dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) || !cache_format_ok(c) || (rotary && !tab32 && rotary_dtype != dtype)) return FA2_ERR_DTYPE;
     fa2::KvAppendParams p;
     std::memset(&p, 0, sizeof(p));
     p.k_new = k_new; p.v_new = v_new; p.k_cache = k_cache; p.v_cache = v_cache; p.q = q; p.q_out = q_out;
@@ -1760,14 +1787,14 @@ int fa2_kvcache_append(int dtype, int cache_format, const void* k_new, const voi
     p.rot = rotary ? rotary_dim : 0; p.interleaved = rotary_interleaved != 0; p.tab16 = !tab32;
     p.page_size = page_size; p.num_pages = num_pages;
     p.R = 2 * Hkv + p.H; p.UR = (D + 15) / 16;
-    p.capacity_keys = page_size ? (int64_t)capacity * page_size : capacity;
+    p.capacity_keys = c.capacity_keys();
     p.seqlen_ro = rotary ? seqlen_ro : 1;
     for (int i = 0; i < 3; ++i) {
         p.kns[i] = k_new_strides[i]; p.vns[i] = v_new_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i];
         if (has_q) { p.qs[i] = q_strides[i]; p.qos[i] = q_out_strides[i]; }
     }
     p.bts = block_table_stride; p.ros = rotary_row_stride;
-    if (descaled) { p.ds[0] = descale_strides[0]; p.ds[1] = descale_strides[1]; }
+    if (c.descaled()) { p.ds[0] = descale_strides[0]; p.ds[1] = descale_strides[1]; }
     if ((int64_t)B * Nnew > 0x7fffffffLL || ((int64_t)p.R * p.UR + fa2::kAppendThreads - 1) / fa2::kAppendThreads > 65535) return FA2_ERR_GRID;
     return fp8 ? fa2::launch_kvappend_fp8(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream)
                : fa2::launch_kvappend(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);

@@ -9,6 +9,7 @@ import re
 import pytest
 import torch
 
+import decode_calls as dc
 from conftest import ROOT
 from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode
@@ -116,17 +117,15 @@ def test_plan_does_not_split_a_grid_that_covers_the_chip():
         assert _fa2_lib.decode_plan(F16, 1, 8, 8, 1, 128, cap).nsplit == max(1, min(16, -(-cap // tile) // 8)), cap
 
 
+P = dc.HOST                                  # 16-byte aligned host memory that no call here ever touches
+DEFAULTS = dict(dtype=F16, q=P, k=P, v=P, o=P, lse=P, lens=P, bt=None, B=2, H=8, Hkv=2, Nq=1, D=128, cap=256, page=0, pages=0,
+                qs=_fa2_lib.strides3(1024, 128, 1024), ks=_fa2_lib.strides3(256 * 256, 128, 256), vs=_fa2_lib.strides3(256 * 256, 128, 256),
+                os=_fa2_lib.strides3(1024, 128, 1024), ls=_fa2_lib.strides2(8, 1), bts=0, scale=0.1, ns=1, ws=None, wsb=0)
+
+
 def _call(**kw):
     """fa2_fwd_decode on host memory that is never touched: every call here is refused before the launch."""
-    lib = _fa2_lib.load()
-    buf = ctypes.create_string_buffer(4096 + 16)
-    p = (ctypes.addressof(buf) + 15) & ~15
-    a = dict(dtype=F16, q=p, k=p, v=p, o=p, lse=p, lens=p, bt=None, B=2, H=8, Hkv=2, Nq=1, D=128, cap=256, page=0, pages=0,
-             qs=_fa2_lib.strides3(1024, 128, 1024), ks=_fa2_lib.strides3(256 * 256, 128, 256), vs=_fa2_lib.strides3(256 * 256, 128, 256),
-             os=_fa2_lib.strides3(1024, 128, 1024), ls=_fa2_lib.strides2(8, 1), bts=0, scale=0.1, ns=1, ws=None, wsb=0)
-    a.update(kw)
-    return lib.fa2_fwd_decode(a["dtype"], a["q"], a["k"], a["v"], a["o"], a["lse"], a["lens"], a["bt"], a["B"], a["H"], a["Hkv"], a["Nq"], a["D"], a["cap"],
-                              a["page"], a["pages"], a["qs"], a["ks"], a["vs"], a["os"], a["ls"], a["bts"], a["scale"], a["ns"], a["ws"], a["wsb"], None)
+    return dc.host_call("plain", DEFAULTS, **kw)
 
 
 def test_every_error_code():

@@ -9,8 +9,9 @@ import re
 import pytest
 import torch
 
+import decode_calls as dc
 from conftest import ROOT
-from rocwmma_fattn import FlashAttn, _fa2_lib
+from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode
 
 HEADER = os.path.join(ROOT, "include", "fa2_gfx950.h")
@@ -68,18 +69,15 @@ def test_plan_and_workspace_follow_the_stated_rule():
     assert _ws(F16, 2, 8, 2, 17, 128, 256, 0, 4) == 0 and _ws(7, 2, 8, 2, 1, 128, 256, 0, 4) == 0
 
 
+P = dc.HOST                                  # 16-byte aligned host memory that no call here ever touches
+DEFAULTS = dict(dtype=F16, q=P, k=P, v=P, o=P, lse=P, lens=P, bt=None, B=2, H=8, Hkv=2, Nq=1, D=128, cap=256, page=0, pages=0,
+                qs=_fa2_lib.strides3(1024, 128, 1024), ks=_fa2_lib.strides3(256 * 256, 128, 256), vs=_fa2_lib.strides3(256 * 256, 128, 256),
+                os=_fa2_lib.strides3(1024, 128, 1024), ls=_fa2_lib.strides2(8, 1), bts=0, scale=0.1, kd=P, vd=P, ds=_fa2_lib.strides2(2, 1), ns=1, ws=None, wsb=0)
+
+
 def _call(**kw):
     """fa2_fwd_decode_fp8 on host memory that is never touched: every call here is refused before the launch."""
-    lib = _fa2_lib.load()
-    buf = ctypes.create_string_buffer(4096 + 16)
-    p = (ctypes.addressof(buf) + 15) & ~15
-    a = dict(dtype=F16, q=p, k=p, v=p, o=p, lse=p, lens=p, bt=None, B=2, H=8, Hkv=2, Nq=1, D=128, cap=256, page=0, pages=0,
-             qs=_fa2_lib.strides3(1024, 128, 1024), ks=_fa2_lib.strides3(256 * 256, 128, 256), vs=_fa2_lib.strides3(256 * 256, 128, 256),
-             os=_fa2_lib.strides3(1024, 128, 1024), ls=_fa2_lib.strides2(8, 1), bts=0, scale=0.1, kd=p, vd=p, ds=_fa2_lib.strides2(2, 1), ns=1, ws=None, wsb=0)
-    a.update(kw)
-    return lib.fa2_fwd_decode_fp8(a["dtype"], a["q"], a["k"], a["v"], a["o"], a["lse"], a["lens"], a["bt"], a["B"], a["H"], a["Hkv"], a["Nq"], a["D"], a["cap"],
-                                  a["page"], a["pages"], a["qs"], a["ks"], a["vs"], a["os"], a["ls"], a["bts"], a["scale"], a["kd"], a["vd"], a["ds"], a["ns"],
-                                  a["ws"], a["wsb"], None)
+    return dc.host_call("fp8", DEFAULTS, **kw)
 
 
 def test_every_error_code():
@@ -194,47 +192,25 @@ def test_cache_strides_must_be_multiples_of_16(monkeypatch):
         flash_attention_decode(q, off, off, lens)
 
 
-class _Recorder:
-    """Stands in for the loaded library: records which decode entry the operator reaches and with how many arguments."""
+TAGS = {"fa2_fwd_decode_workspace_bytes": "ws16", "fa2_fwd_decode_fp8_workspace_bytes": "ws8", "fa2_fwd_decode": "decode", "fa2_fwd_decode_fp8": "decode_fp8"}
 
-    def __init__(self):
-        self.calls = []
 
-    def fa2_fwd_decode_workspace_bytes(self, *a):
-        self.calls.append(("ws16", len(a)))
-        return 0
-
-    def fa2_fwd_decode_fp8_workspace_bytes(self, *a):
-        self.calls.append(("ws8", len(a)))
-        return 0
-
-    def fa2_fwd_decode(self, *a):
-        self.calls.append(("decode", len(a)))
-        return 0
-
-    def fa2_fwd_decode_fp8(self, *a):
-        self.calls.append(("decode_fp8", len(a), a[23], a[24], None if a[25] is None else tuple(a[25])))
-        return 0
+def _brief(calls):
+    """Which decode entry the operator reached and with how many arguments; the fp8 entry with its descale pointers and their stride pair.  (Another
+    symbol than these four is a KeyError.)"""
+    out = []
+    for name, a in calls:
+        row = (TAGS[name], len(a))
+        if name == "fa2_fwd_decode_fp8":
+            ds = dc.arg("fp8", a, "ds")
+            row += (dc.arg("fp8", a, "kd"), dc.arg("fp8", a, "vd"), None if ds is None else tuple(ds))
+        out.append(row)
+    return out
 
 
 @pytest.fixture
 def recorder(monkeypatch):
-    rec = _Recorder()
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(_fa2_lib, "load", lambda: rec)
-    monkeypatch.setattr(FlashAttn, "_raw_stream", lambda dev: None)
-    monkeypatch.setattr(FlashAttn, "_current_device", lambda: 0)
-    monkeypatch.setattr(FlashAttn, "_workspace_unused", lambda dev, stream: None)
-
-    class _Ctx:
-        def __enter__(self):
-            return self
-
-        def __exit__(self, *exc):
-            return False
-
-    monkeypatch.setattr(torch.cuda, "device", lambda dev: _Ctx())
-    return rec
+    return dc.recording_lib(monkeypatch)
 
 
 def test_a_16_bit_call_reaches_fa2_fwd_decode_as_before(recorder):
@@ -242,7 +218,7 @@ def test_a_16_bit_call_reaches_fa2_fwd_decode_as_before(recorder):
     q, k, v, lens = _args(cache=torch.float16)
     o = flash_attention_decode(q, k, v, lens, k_descale=None, v_descale=None)
     assert o.shape == q.shape and o.dtype == q.dtype
-    assert recorder.calls == [("ws16", 9), ("decode", len(_fa2_lib.SYMBOLS["fa2_fwd_decode"][1]))]
+    assert _brief(recorder.calls) == [("ws16", 9), ("decode", len(_fa2_lib.SYMBOLS["fa2_fwd_decode"][1]))]
 
 
 def test_an_fp8_call_reaches_the_new_entry_with_the_descales_passed_through(recorder):
@@ -253,5 +229,5 @@ def test_an_fp8_call_reaches_the_new_entry_with_the_descales_passed_through(reco
     flash_attention_decode(q, k, v, lens, v_descale=vd)
     flash_attention_decode(q, k, v, lens)
     n = len(_fa2_lib.SYMBOLS["fa2_fwd_decode_fp8"][1])
-    assert recorder.calls == [("ws8", 9), ("decode_fp8", n, kd.data_ptr(), vd.data_ptr(), (6, 2)), ("ws8", 9), ("decode_fp8", n, None, vd.data_ptr(), (6, 2)),
+    assert _brief(recorder.calls) == [("ws8", 9), ("decode_fp8", n, kd.data_ptr(), vd.data_ptr(), (6, 2)), ("ws8", 9), ("decode_fp8", n, None, vd.data_ptr(), (6, 2)),
                               ("ws8", 9), ("decode_fp8", n, None, None, None)]

@@ -11,16 +11,15 @@ unchanged: fa2_oracle.fwd_c per sequence on the cache upcast to q's dtype and mu
 anything runs on the GPU, _case checks on the CPU that the oracle's own result on these inputs is within FLOOR of float64.
 General (not power-of-two) descales are held to float64 only.  The references of a shape are computed once and shared.
 No test feeds an out-of-range length or page id to the GPU."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import decode_calls as dc
 import decode_refs as dr
 from oracle import fa2_oracle as fo
-from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode
 
 pytestmark = pytest.mark.gpu
@@ -36,48 +35,9 @@ SHAPES = [(8, 8, 1, 128, F16), (8, 2, 1, 64, BF16), (10, 2, 4, 128, BF16), (16, 
 IDS = ["H%d_Hkv%d_Nq%d_D%d_%s" % (s[0], s[1], s[2], s[3], "f16" if s[4] == F16 else "bf16") for s in SHAPES]
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda", 0)
-
-
-def _code(dt):
-    return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
-
-
-def _s3(t):
-    return _fa2_lib.strides3(t.stride(0), t.stride(2), t.stride(1))
-
-
 def _quant(x, d):
     """x / d as e4m3, clamped into the format's range first (torch's cast does not saturate); d broadcasts against x."""
     return (x / d).clamp(-448.0, 448.0).to(E4M3)
-
-
-def _decode_c(q, k, v, lens, num_splits, kd=None, vd=None, block_table=None, o=None, scale=None):
-    """fa2_fwd_decode_fp8 with NaN-filled outputs and a NaN-filled workspace: every element the contract names must be written, nothing unwritten read."""
-    lib = _fa2_lib.load()
-    B, Nq, H, D = q.shape
-    Hkv = k.shape[2]
-    o = torch.full((B, Nq, H, D), float("nan"), dtype=q.dtype, device=q.device) if o is None else o
-    lse = torch.full((B, H, Nq), float("nan"), dtype=torch.float32, device=q.device)
-    if block_table is None:
-        capacity, page, pages = k.shape[1], 0, 0
-    else:
-        capacity, page, pages = block_table.shape[1], k.shape[1], k.shape[0]
-    need = lib.fa2_fwd_decode_fp8_workspace_bytes(_code(q.dtype), B, H, Hkv, Nq, D, capacity, page, num_splits)
-    ws = torch.full((max(need, 16) // 4,), float("nan"), dtype=torch.float32, device=q.device)
-    d0 = kd if kd is not None else vd
-    assert kd is None or vd is None or kd.stride() == vd.stride()
-    _fa2_lib.check(lib.fa2_fwd_decode_fp8(_code(q.dtype), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), lens.data_ptr(),
-                                          None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page, pages, _s3(q), _s3(k),
-                                          _s3(v), _s3(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0),
-                                          D ** -0.5 if scale is None else scale, None if kd is None else kd.data_ptr(), None if vd is None else vd.data_ptr(),
-                                          None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), num_splits, ws.data_ptr() if need else None,
-                                          need, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    return o, lse
 
 
 def _poison(cache8):
@@ -100,13 +60,13 @@ def _case(H, Hkv, Nq, D, dt):
     kd, vd = (2.0 ** -torch.randint(5, 8, (B, Hkv), generator=g).float() for _ in range(2))
     k8 = _poison(_quant(torch.randn((B, NMAX, Hkv, D), generator=g), kd[:, None, :, None]))
     v8 = _poison(_quant(torch.randn((B, NMAX, Hkv, D), generator=g), vd[:, None, :, None]))
-    refs = dr.refs_fp8(q, k8, v8, kd, vd, LENS, _code(dt))
+    refs = dr.refs_fp8(q, k8, v8, kd, vd, LENS, dc.code(dt))
     return q, k8, v8, kd, vd, refs
 
 
 def _check(o, lse2, refs, dt, tag, oracle=True):
     """o [B, Nq, H, D] and the log2 lse [B, H, Nq] (device) against the shared references; dead rows exactly 0 / -inf, every element written."""
-    dr.check(o, lse2, refs, LENS, _code(dt), tag, oracle=oracle, verbose=True)
+    dr.check(o, lse2, refs, LENS, dc.code(dt), tag, oracle=oracle, verbose=True)
 
 
 _same_lse = dr.same_lse
@@ -125,7 +85,7 @@ def test_every_v_code_exactly(dt):
     """B4 Hkv1 H1 D64, one key per sequence whose V row holds 64 of the 256 codes: a single key has weight exactly 1, so o is the V row converted —
     torch's e4m3fn -> q.dtype conversion bit for bit, for every code.  (One code is expected as a different bit pattern than torch's: 0x80, -0.  The
     f32 accumulator starts at +0 and +0 + 1 * (-0) is +0 under round-to-nearest, as in the 16-bit call on a V of -0; the value is the same.)"""
-    dev = _dev()
+    dev = dc.dev()
     nmax = 64
     v8 = torch.full((4, nmax, 1, 64), NAN_BYTE, dtype=torch.uint8)
     v8[:, 0, 0] = _all_codes()
@@ -147,7 +107,7 @@ def test_every_v_code_exactly(dt):
 def test_every_k_code_exactly(dt):
     """The same four rows as K, 64 query heads with q[h] = e_h and scale = 1: the one score of head h is k[h] exactly, so lse[b, h, 0] = float(k[b, 0, 0, h])
     within three f32 roundings (scale * log2e, the product, the operator's ln 2): 3 * 2^-24 = 1.8e-7 < 1e-6 relative."""
-    dev = _dev()
+    dev = dc.dev()
     nmax = 64
     k8 = torch.full((4, nmax, 1, 64), NAN_BYTE, dtype=torch.uint8)
     k8[:, 0, 0] = _all_codes()
@@ -166,14 +126,14 @@ def test_every_k_code_exactly(dt):
 
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_lengths_shapes_and_splits(shape):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k8, v8, kd, vd, refs = _case(*shape)
     qd, kk, vv, kdd, vdd = (t.to(dev) for t in (q, k8, v8, kd, vd))
     lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
     lse1 = None
     for ns in SPLITS:
-        o, lse = _decode_c(qd, kk, vv, lens, ns, kdd, vdd)
+        o, lse = dc.decode_c("fp8", qd, kk, vv, lens, ns, kd=kdd, vd=vdd)
         _check(o, lse, refs, dt, (shape[:4], "splits", ns))
         if ns == 1:
             lse1 = lse
@@ -181,7 +141,7 @@ def test_lengths_shapes_and_splits(shape):
             assert _same_lse(lse, lse1), (shape[:4], ns, "LSE of the split against split 1")
     # the operator: natural-log LSE, the same O bits as the C call with the plan's split
     po, pl = flash_attention_decode(qd, kk, vv, lens, return_lse=True, k_descale=kdd, v_descale=vdd)
-    o0, l0 = _decode_c(qd, kk, vv, lens, 0, kdd, vdd)
+    o0, l0 = dc.decode_c("fp8", qd, kk, vv, lens, 0, kd=kdd, vd=vdd)
     assert torch.equal(po.view(torch.int16), o0.view(torch.int16)) and _same_lse(pl * LOG2E, l0)
 
 
@@ -190,7 +150,7 @@ def test_general_descales_against_float64(which):
     """Descales amax / 448 per (sequence, head) — not powers of two, so no same-contract oracle: float64 of the dequantised values only, 2 * FLOOR and
     LSE_TOL.  Where a descale is left out the cache is quantised at scale 1, so the dequantised values stay unit-scale and the absolute bar means
     what it means elsewhere."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = 8, 2, 3, 64, BF16
     G, B = H // Hkv, len(LENS)
     g = torch.Generator(device="cpu").manual_seed(41)
@@ -224,40 +184,19 @@ def test_general_descales_against_float64(which):
         _check(o, lse * LOG2E, refs, dt, (which, ns), oracle=False)
 
 
-def _paged(k, v, page, g, spare=3):
-    """The [B, NMAX, Hkv, D] caches scattered into pages in shuffled physical order; spare pages and the pages no sequence uses hold 0x7f bytes, and
-    block-table entries beyond a sequence's used pages point at such a page."""
-    B, per = k.shape[0], NMAX // page
-    used = [-(-n // page) for n in LENS]
-    total = sum(used) + spare
-    order = torch.randperm(total, generator=g).tolist()
-    pk = torch.full((total, page) + tuple(k.shape[2:]), NAN_BYTE, dtype=torch.uint8)
-    pv = torch.full_like(pk, NAN_BYTE)
-    bt = torch.full((B, per), order[-1], dtype=torch.int32)
-    nxt = 0
-    for b in range(B):
-        for j in range(used[b]):
-            pid = order[nxt]
-            nxt += 1
-            pk[pid] = k.view(torch.uint8)[b, j * page:(j + 1) * page]
-            pv[pid] = v.view(torch.uint8)[b, j * page:(j + 1) * page]
-            bt[b, j] = pid
-    return pk.view(E4M3), pv.view(E4M3), bt
-
-
 @pytest.mark.parametrize("page", [64, 128])
 @pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2]], ids=[IDS[1], IDS[2]])
 def test_paged_is_bit_identical_to_contiguous(shape, page):
-    dev = _dev()
+    dev = dc.dev()
     q, k8, v8, kd, vd, refs = _case(*shape)
-    pk, pv, bt = _paged(k8, v8, page, torch.Generator(device="cpu").manual_seed(page))
+    pk, pv, bt = dc.paged(k8, v8, LENS, page, torch.Generator(device="cpu").manual_seed(page))
     qd, lens = q.to(dev), torch.tensor(LENS, dtype=torch.int32, device=dev)
     kk, vv, pkd, pvd, btd, kdd, vdd = (t.to(dev) for t in (k8, v8, pk, pv, bt, kd, vd))
     for ns in SPLITS[1:]:
-        o, lse = _decode_c(qd, kk, vv, lens, ns, kdd, vdd)
-        po, plse = _decode_c(qd, pkd, pvd, lens, ns, kdd, vdd, block_table=btd)
+        o, lse = dc.decode_c("fp8", qd, kk, vv, lens, ns, kd=kdd, vd=vdd)
+        po, plse = dc.decode_c("fp8", qd, pkd, pvd, lens, ns, kd=kdd, vd=vdd, block_table=btd)
         assert torch.equal(po.view(torch.int16), o.view(torch.int16)) and torch.equal(plse, lse), (shape[:4], page, ns)
-    po, plse = _decode_c(qd, pkd, pvd, lens, 0, kdd, vdd, block_table=btd)
+    po, plse = dc.decode_c("fp8", qd, pkd, pvd, lens, 0, kd=kdd, vd=vdd, block_table=btd)
     _check(po, plse, refs, shape[4], (shape[:4], "paged", page))
     oo = flash_attention_decode(qd, pkd, pvd, lens, block_table=btd, k_descale=kdd, v_descale=vdd)
     assert torch.equal(oo.view(torch.int16), po.view(torch.int16))
@@ -265,7 +204,7 @@ def test_paged_is_bit_identical_to_contiguous(shape, page):
 
 @pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[4]], ids=[IDS[1], IDS[4]])
 def test_strided_views_are_bit_identical(shape):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k8, v8, kd, vd, _ = _case(*shape)
     B = q.shape[0]
@@ -282,9 +221,9 @@ def test_strided_views_are_bit_identical(shape):
     dv.copy_(vd)
     assert not kview.is_contiguous() and not dk.is_contiguous() and dk.stride() == dv.stride()
     for ns in (1, 3):
-        o, lse = _decode_c(qd, kk, vv, lens, ns, kd.to(dev), vd.to(dev))
+        o, lse = dc.decode_c("fp8", qd, kk, vv, lens, ns, kd=kd.to(dev), vd=vd.to(dev))
         ow = torch.full((B, Nq, H + 2, D), float("nan"), dtype=dt, device=dev)
-        so, slse = _decode_c(qw[:, :, :H], kview, vv, lens, ns, dk, dv, o=ow[:, :, :H])
+        so, slse = dc.decode_c("fp8", qw[:, :, :H], kview, vv, lens, ns, kd=dk, vd=dv, o=ow[:, :, :H])
         assert torch.equal(so.view(torch.int16), o.view(torch.int16)) and torch.equal(slse, lse), (shape[:4], ns)
         assert torch.isnan(ow[:, :, H:]).all(), "the call wrote outside its view of o"
         po, pl = flash_attention_decode(qw[:, :, :H], kview, vv, lens, return_lse=True, num_splits=ns, k_descale=dk, v_descale=dv)
@@ -296,7 +235,7 @@ def test_strided_views_are_bit_identical(shape):
 def test_graph_replay_follows_lengths_and_descales_changed_in_place(ns):
     """The host reads neither cache_seqlens nor the descales: one captured call, replayed after all three were overwritten in place, gives the eager
     result for the contents at that time (a fully valid cache here, so that every permutation of the lengths is a legal call)."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = 8, 2, 3, 128, F16
     B = len(LENS)
     g = torch.Generator(device="cpu").manual_seed(78)

@@ -6,7 +6,6 @@ against the oracle, 2 * FLOOR against float64.  One batch of nine sequences cove
 64-key tile edges and a long one; every cache row at or beyond a sequence's length holds NaN in K and in V, outputs and the workspace are
 pre-filled with NaN.  The references of a shape are computed once and shared by every split, the paged and the strided calls.
 No test feeds an out-of-range length or page id to the GPU: the clamps are checked on the CPU (tests/test_decode.py)."""
-import ctypes
 import functools
 import math
 
@@ -14,9 +13,9 @@ import numpy as np
 import pytest
 import torch
 
+import decode_calls as dc
 import decode_refs as dr
 from conftest import ATOL, LSE_TOL, RTOL
-from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode, flash_attention_varlen, merge_attention
 
 pytestmark = pytest.mark.gpu
@@ -32,43 +31,6 @@ SHAPES = [(8, 8, 1, 128, F16), (8, 8, 4, 64, BF16), (8, 8, 3, 128, F16), (8, 2, 
 IDS = ["H%d_Hkv%d_Nq%d_D%d_%s" % (s[0], s[1], s[2], s[3], "f16" if s[4] == F16 else "bf16") for s in SHAPES]
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda", 0)
-
-
-def _code(dt):
-    return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
-
-
-def _s3(t):
-    """{batch | page, head, row} element strides of a [B, N, heads, D] tensor."""
-    return _fa2_lib.strides3(t.stride(0), t.stride(2), t.stride(1))
-
-
-def _decode_c(q, k, v, lens, num_splits, block_table=None, o=None, lse=None, scale=None):
-    """fa2_fwd_decode with NaN-filled outputs and a NaN-filled workspace: every element the contract names must be written, nothing unwritten read."""
-    lib = _fa2_lib.load()
-    B, Nq, H, D = q.shape
-    Hkv = k.shape[2]
-    o = torch.full((B, Nq, H, D), float("nan"), dtype=q.dtype, device=q.device) if o is None else o
-    lse = torch.full((B, H, Nq), float("nan"), dtype=torch.float32, device=q.device) if lse is None else lse
-    if block_table is None:
-        capacity, page, pages = k.shape[1], 0, 0
-    else:
-        capacity, page, pages = block_table.shape[1], k.shape[1], k.shape[0]
-    need = lib.fa2_fwd_decode_workspace_bytes(_code(q.dtype), B, H, Hkv, Nq, D, capacity, page, num_splits)
-    ws = torch.full((max(need, 16) // 4,), float("nan"), dtype=torch.float32, device=q.device)
-    _fa2_lib.check(lib.fa2_fwd_decode(_code(q.dtype), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), lens.data_ptr(),
-                                      None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page, pages, _s3(q), _s3(k), _s3(v),
-                                      _s3(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0),
-                                      D ** -0.5 if scale is None else scale, num_splits, ws.data_ptr() if need else None, need,
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    return o, lse
-
-
 @functools.lru_cache(maxsize=None)
 def _case(H, Hkv, Nq, D, dt):
     """CPU tensors of one shape (cache rows at or beyond len_b are NaN) and, per sequence, the oracle's and the float64 results.  Computed once."""
@@ -80,13 +42,13 @@ def _case(H, Hkv, Nq, D, dt):
     for b, n in enumerate(LENS):
         k[b, n:] = float("nan")
         v[b, n:] = float("nan")
-    refs = dr.refs16(q, k, v, LENS, _code(dt))
+    refs = dr.refs16(q, k, v, LENS, dc.code(dt))
     return q, k, v, refs
 
 
 def _check(o, lse2, refs, dt, tag):
     """o [B, Nq, H, D] and the log2 lse [B, H, Nq] (device) against the shared references; dead rows exactly 0 / -inf, every element written."""
-    dr.check(o, lse2, refs, LENS, _code(dt), tag)
+    dr.check(o, lse2, refs, LENS, dc.code(dt), tag)
 
 
 _same_lse = dr.same_lse
@@ -94,14 +56,14 @@ _same_lse = dr.same_lse
 
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_lengths_shapes_and_splits(shape):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k, v, refs = _case(*shape)
     qd, kd, vd = q.to(dev), k.to(dev), v.to(dev)
     lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
     lse1 = None
     for ns in SPLITS:
-        o, lse = _decode_c(qd, kd, vd, lens, ns)
+        o, lse = dc.decode_c("plain", qd, kd, vd, lens, ns)
         _check(o, lse, refs, dt, (shape[:4], "splits", ns))
         if ns == 1:
             lse1 = lse
@@ -109,47 +71,25 @@ def test_lengths_shapes_and_splits(shape):
             assert _same_lse(lse, lse1), (shape[:4], ns, "LSE of the split against split 1")
 
 
-def _paged(k, v, page, g, spare=3):
-    """The [B, NMAX, Hkv, D] caches scattered into pages in shuffled physical order; spare pages and the pages no sequence uses hold NaN, and block-table
-    entries beyond a sequence's used pages point at a NaN page."""
-    B, per = k.shape[0], NMAX // page
-    used = [-(-n // page) for n in LENS]
-    total = sum(used) + spare
-    order = torch.randperm(total, generator=g).tolist()
-    pk = torch.full((total, page) + tuple(k.shape[2:]), float("nan"), dtype=k.dtype)
-    pv = torch.full_like(pk, float("nan"))
-    nan_page = order[-1]
-    bt = torch.full((B, per), nan_page, dtype=torch.int32)
-    nxt = 0
-    for b in range(B):
-        for j in range(used[b]):
-            pid = order[nxt]
-            nxt += 1
-            pk[pid] = k[b, j * page:(j + 1) * page]
-            pv[pid] = v[b, j * page:(j + 1) * page]
-            bt[b, j] = pid
-    return pk, pv, bt
-
-
 @pytest.mark.parametrize("page", [64, 128])
 @pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[3], SHAPES[8], SHAPES[11]], ids=[IDS[0], IDS[3], IDS[8], IDS[11]])
 def test_paged_is_bit_identical_to_contiguous(shape, page):
-    dev = _dev()
+    dev = dc.dev()
     q, k, v, refs = _case(*shape)
-    pk, pv, bt = _paged(k, v, page, torch.Generator(device="cpu").manual_seed(page))
+    pk, pv, bt = dc.paged(k, v, LENS, page, torch.Generator(device="cpu").manual_seed(page))
     qd, lens = q.to(dev), torch.tensor(LENS, dtype=torch.int32, device=dev)
     kd, vd, pkd, pvd, btd = k.to(dev), v.to(dev), pk.to(dev), pv.to(dev), bt.to(dev)
     for ns in SPLITS[1:]:
-        o, lse = _decode_c(qd, kd, vd, lens, ns)
-        po, plse = _decode_c(qd, pkd, pvd, lens, ns, block_table=btd)
+        o, lse = dc.decode_c("plain", qd, kd, vd, lens, ns)
+        po, plse = dc.decode_c("plain", qd, pkd, pvd, lens, ns, block_table=btd)
         assert torch.equal(po.view(torch.int16), o.view(torch.int16)) and torch.equal(plse, lse), (shape[:4], page, ns)
-    po, plse = _decode_c(qd, pkd, pvd, lens, 0, block_table=btd)          # the plan's own split of the paged call (its capacity is the block table's)
+    po, plse = dc.decode_c("plain", qd, pkd, pvd, lens, 0, block_table=btd)          # the plan's own split of the paged call (its capacity is the block table's)
     _check(po, plse, refs, shape[4], (shape[:4], "paged", page))
 
 
 @pytest.mark.parametrize("shape", [SHAPES[3], SHAPES[9], SHAPES[10]], ids=[IDS[3], IDS[9], IDS[10]])
 def test_strided_views_are_bit_identical(shape):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k, v, _ = _case(*shape)
     B = q.shape[0]
@@ -160,9 +100,9 @@ def test_strided_views_are_bit_identical(shape):
     kw = torch.full((B, NMAX + 40, Hkv, D), float("nan"), dtype=dt, device=dev)       # a padded Nmax stride
     kw[:, :NMAX] = kd
     for ns in (1, 3):
-        o, lse = _decode_c(qd, kd, vd, lens, ns)
+        o, lse = dc.decode_c("plain", qd, kd, vd, lens, ns)
         ow = torch.full((B, Nq, H + 2, D), float("nan"), dtype=dt, device=dev)
-        so, slse = _decode_c(qw[:, :, :H], kw[:, :NMAX], vd, lens, ns, o=ow[:, :, :H])
+        so, slse = dc.decode_c("plain", qw[:, :, :H], kw[:, :NMAX], vd, lens, ns, o=ow[:, :, :H])
         assert not qw[:, :, :H].is_contiguous() and not kw[:, :NMAX].is_contiguous()
         assert torch.equal(so.view(torch.int16), o.view(torch.int16)) and torch.equal(slse, lse), (shape[:4], ns)
         assert torch.isnan(ow[:, :, H:]).all(), "the call wrote outside its view of o"
@@ -175,10 +115,10 @@ def test_strided_views_are_bit_identical(shape):
 @pytest.mark.parametrize("shape", [SHAPES[3], SHAPES[5], SHAPES[7]], ids=[IDS[3], IDS[5], IDS[7]])
 def test_against_packed_varlen(shape):
     """flash_attention_varlen(causal=True, bottom_right=True) on a packed copy of the valid keys: the route the library had before."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k, v, _ = _case(*shape)
-    code = _code(dt)
+    code = dc.code(dt)
     lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
     o = flash_attention_decode(q.to(dev), k.to(dev), v.to(dev), lens)
     cu_q = torch.arange(0, (len(LENS) + 1) * Nq, Nq, dtype=torch.int32, device=dev)
@@ -195,7 +135,7 @@ def test_against_packed_varlen(shape):
 def test_graph_replay_follows_lengths_changed_in_place(ns):
     """The host never reads cache_seqlens: one captured call, replayed after the lengths were overwritten in place, gives the eager result for the
     contents at that time (a fully valid cache here, so that every permutation of the lengths is a legal call)."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = 8, 2, 3, 128, F16
     g = torch.Generator(device="cpu").manual_seed(77)
     q = torch.randn((len(LENS), Nq, H, D), generator=g).to(dt).to(dev)
@@ -228,9 +168,9 @@ def test_graph_replay_follows_lengths_changed_in_place(ns):
 @pytest.mark.parametrize("dt", [F16, BF16], ids=["f16", "bf16"])
 def test_return_lse_composes_with_merge_attention(dt):
     """A cache of 512 keys as two 256-key halves (Nq = 1: no causal interaction): merge_attention of the two decode results is the one-call result."""
-    dev = _dev()
+    dev = dc.dev()
     B, H, Hkv, D = 3, 8, 2, 128
-    code = _code(dt)
+    code = dc.code(dt)
     g = torch.Generator(device="cpu").manual_seed(5)
     q = torch.randn((B, 1, H, D), generator=g).to(dt).to(dev)
     k, v = (torch.randn((B, 512, Hkv, D), generator=g).to(dt).to(dev) for _ in range(2))

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import decode_window_refs as wr
+import decode_calls as dc
 from conftest import ROOT
 from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode
@@ -159,19 +160,16 @@ def test_plan_part_cap_follows_the_span_of_the_window():
     assert _ws(F16, 2, 8, 2, 1, 128, 256, 0, 4, -2) == 0 and _ws(7, 2, 8, 2, 1, 128, 256, 0, 4, 5) == 0
 
 
+P = dc.HOST                                  # 16-byte aligned host memory that no call here ever touches
+DEFAULTS = dict(dtype=F16, fmt=C16, q=P, k=P, v=P, o=P, lse=P, lens=P, bt=None, B=2, H=8, Hkv=2, Nq=1, D=128, cap=256, page=0, pages=0,
+                qs=_fa2_lib.strides3(1024, 128, 1024), ks=_fa2_lib.strides3(256 * 256, 128, 256), vs=_fa2_lib.strides3(256 * 256, 128, 256),
+                os=_fa2_lib.strides3(1024, 128, 1024), ls=_fa2_lib.strides2(8, 1), bts=0, scale=0.1, kd=None, vd=None, ds=None, wl=31, cap_=8.0, sl=P, st=8,
+                ns=1, ws=None, wsb=0)
+
+
 def _call(**kw):
     """fa2_fwd_decode_window on host memory that is never touched: every call here is refused before the launch."""
-    lib = _fa2_lib.load()
-    buf = ctypes.create_string_buffer(4096 + 16)
-    p = (ctypes.addressof(buf) + 15) & ~15
-    a = dict(dtype=F16, fmt=C16, q=p, k=p, v=p, o=p, lse=p, lens=p, bt=None, B=2, H=8, Hkv=2, Nq=1, D=128, cap=256, page=0, pages=0,
-             qs=_fa2_lib.strides3(1024, 128, 1024), ks=_fa2_lib.strides3(256 * 256, 128, 256), vs=_fa2_lib.strides3(256 * 256, 128, 256),
-             os=_fa2_lib.strides3(1024, 128, 1024), ls=_fa2_lib.strides2(8, 1), bts=0, scale=0.1, kd=None, vd=None, ds=None, wl=31, cap_=8.0, sl=p, st=8,
-             ns=1, ws=None, wsb=0)
-    a.update(kw)
-    return lib.fa2_fwd_decode_window(a["dtype"], a["fmt"], a["q"], a["k"], a["v"], a["o"], a["lse"], a["lens"], a["bt"], a["B"], a["H"], a["Hkv"], a["Nq"],
-                                     a["D"], a["cap"], a["page"], a["pages"], a["qs"], a["ks"], a["vs"], a["os"], a["ls"], a["bts"], a["scale"], a["kd"],
-                                     a["vd"], a["ds"], a["wl"], a["cap_"], a["sl"], a["st"], a["ns"], a["ws"], a["wsb"], None)
+    return dc.host_call("window", DEFAULTS, **kw)
 
 
 def test_every_error_code():
@@ -261,24 +259,7 @@ def test_python_argument_checks():
 def test_plain_call_reaches_the_old_entries(monkeypatch):
     """With none of the three keywords the operator calls fa2_fwd_decode with its old argument list; with one of them the new entry.  (CPU tensors that
     claim a ROCm device and a stand-in for the loaded library, as tests/test_decode_fp8.py does.)"""
-    import contextlib
-
-    from rocwmma_fattn import FlashAttn
-    seen = []
-
-    class Lib:
-        def __getattr__(self, name):
-            def f(*a):
-                seen.append((name, a))
-                return 0
-            return f
-
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(_fa2_lib, "load", lambda: Lib())
-    monkeypatch.setattr(FlashAttn, "_raw_stream", lambda dev: None)
-    monkeypatch.setattr(FlashAttn, "_current_device", lambda: 0)
-    monkeypatch.setattr(FlashAttn, "_workspace_unused", lambda dev, stream: None)
-    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    seen = dc.recording_lib(monkeypatch).calls
     q, k, v, lens = _args()
     flash_attention_decode(q, k, v, lens)
     flash_attention_decode(q, k, v, lens, window=None, softcap=0.0, alibi_slopes=None)

@@ -6,14 +6,12 @@ or beyond every length AND below every sequence's lowest visible key, outputs an
 contract per sequence and a same-contract emulation (tests/decode_window_refs.py), computed once per (shape, case) and shared; the bars are the
 project's rule (tools/fuzz_features.py: error_and_bar).  That every parity case differs from the plain call by at least 5 bars is asserted on the CPU
 (tests/test_decode_window.py).  No test feeds an out-of-range length or page id to the GPU."""
-import ctypes
-
 import pytest
 import torch
 
+import decode_calls as dc
 import decode_refs as dr
 import decode_window_refs as wr
-from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode, kvcache_append
 
 pytestmark = pytest.mark.gpu
@@ -22,74 +20,6 @@ F16, BF16 = wr.F16, wr.BF16
 LENS, NMAX, SPLITS = wr.LENS, wr.NMAX, wr.SPLITS
 LOG2E = 1.4426950408889634
 E4M3 = torch.float8_e4m3fn
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda", 0)
-
-
-def _code(dt):
-    return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
-
-
-def _s3(t):
-    return _fa2_lib.strides3(t.stride(0), t.stride(2), t.stride(1))
-
-
-def _nan_out(q):
-    B, Nq, H, D = q.shape
-    return (torch.full((B, Nq, H, D), float("nan"), dtype=q.dtype, device=q.device), torch.full((B, H, Nq), float("nan"), dtype=torch.float32, device=q.device))
-
-
-def _window_c(q, k, v, lens, num_splits, window_left=-1, softcap=0.0, slopes=None, block_table=None, kd=None, vd=None, scale=None):
-    """fa2_fwd_decode_window with NaN-filled outputs and a NaN-filled workspace (the cache format follows k's dtype)."""
-    lib = _fa2_lib.load()
-    B, Nq, H, D = q.shape
-    Hkv = k.shape[2]
-    o, lse = _nan_out(q)
-    if block_table is None:
-        capacity, page, pages = k.shape[1], 0, 0
-    else:
-        capacity, page, pages = block_table.shape[1], k.shape[1], k.shape[0]
-    need = lib.fa2_fwd_decode_window_workspace_bytes(_code(q.dtype), B, H, Hkv, Nq, D, capacity, page, num_splits, window_left)
-    ws = torch.full((max(need, 16) // 4,), float("nan"), dtype=torch.float32, device=q.device)
-    d0 = kd if kd is not None else vd
-    fmt = _fa2_lib.FA2_CACHE_E4M3 if k.dtype == E4M3 else _fa2_lib.FA2_CACHE_16BIT
-    _fa2_lib.check(lib.fa2_fwd_decode_window(
-        _code(q.dtype), fmt, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), lens.data_ptr(),
-        None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page, pages, _s3(q), _s3(k), _s3(v), _s3(o),
-        _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0), D ** -0.5 if scale is None else scale,
-        None if kd is None else kd.data_ptr(), None if vd is None else vd.data_ptr(), None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)),
-        window_left, softcap, None if slopes is None else slopes.data_ptr(), 0 if slopes is None or slopes.dim() == 1 else slopes.stride(0),
-        num_splits, ws.data_ptr() if need else None, need, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    return o, lse
-
-
-def _plain_c(q, k, v, lens, num_splits, kd=None, vd=None):
-    """fa2_fwd_decode / fa2_fwd_decode_fp8, NaN-filled outputs and workspace"""
-    lib = _fa2_lib.load()
-    B, Nq, H, D = q.shape
-    Hkv = k.shape[2]
-    o, lse = _nan_out(q)
-    fp8 = k.dtype == E4M3
-    need = lib.fa2_fwd_decode_workspace_bytes(_code(q.dtype), B, H, Hkv, Nq, D, k.shape[1], 0, num_splits)
-    ws = torch.full((max(need, 16) // 4,), float("nan"), dtype=torch.float32, device=q.device)
-    head = (_code(q.dtype), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), lens.data_ptr(), None, B, H, Hkv, Nq, D, k.shape[1], 0, 0,
-            _s3(q), _s3(k), _s3(v), _s3(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0, D ** -0.5)
-    tail = (num_splits, ws.data_ptr() if need else None, need, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if fp8:
-        _fa2_lib.check(lib.fa2_fwd_decode_fp8(*head, kd.data_ptr(), vd.data_ptr(), _fa2_lib.strides2(kd.stride(0), kd.stride(1)), *tail))
-    else:
-        _fa2_lib.check(lib.fa2_fwd_decode(*head, *tail))
-    torch.cuda.synchronize()
-    return o, lse
-
-
-def _same_bits(a, b):
-    return torch.equal(a[0].view(torch.int16), b[0].view(torch.int16)) and torch.equal(a[1], b[1])
 
 
 def _device_case(shape, name, dev):
@@ -105,12 +35,12 @@ def _device_case(shape, name, dev):
 @pytest.mark.parametrize("name", list(wr.CASES))
 @pytest.mark.parametrize("shape", wr.SHAPES, ids=wr.IDS)
 def test_parity_with_float64(shape, name):
-    dev = _dev()
+    dev = dc.dev()
     refs = wr.case_refs(shape, name)
     q, k, v, lens, sl, wl, cap = _device_case(shape, name, dev)
     lses = {}
     for ns in SPLITS:
-        o, lses[ns] = _window_c(q, k, v, lens, ns, wl, cap, sl)
+        o, lses[ns] = dc.decode_c("window", q, k, v, lens, ns, wl, cap, sl)
         wr.check(o, lses[ns], refs, (wr.IDS[wr.SHAPES.index(shape)], name, "splits", ns))
     for ns in SPLITS:                                # the plan's own split (0) included
         assert dr.same_lse(lses[ns], lses[1]), (shape[:4], name, ns, "LSE of the split against split 1")
@@ -121,7 +51,7 @@ def test_windows_between_row_0s_reach_and_the_last_rows(shape):
     """window_left in {NMAX - Nq, NMAX - 2} on full sequences: such a window masks nothing for row 0, but row i still drops the keys below
     i + NMAX - Nq - window_left.  Alone and with all-zero slopes beside it (idle, so that the float64 reference and its margin are the window's
     alone): neither the plain kernels nor a windowless launch of the banded ones may serve these calls."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k, v = wr.edge_inputs(*shape)
     lens = torch.tensor(wr.EDGE_LENS, dtype=torch.int32, device=dev)
@@ -131,11 +61,11 @@ def test_windows_between_row_0s_reach_and_the_last_rows(shape):
         args = (q.to(dev), wr.dirty(k, Nq, wl, lens=wr.EDGE_LENS).to(dev), wr.dirty(v, Nq, wl, lens=wr.EDGE_LENS).to(dev), lens)
         outs = {}
         for ns in SPLITS:
-            outs[ns] = _window_c(*args, ns, wl)
+            outs[ns] = dc.decode_c("window", *args, ns, wl)
             wr.check(*outs[ns], refs, (wr.EDGE_IDS[wr.EDGE_SHAPES.index(shape)], name, "splits", ns))
         for ns in SPLITS:
             assert dr.same_lse(outs[ns][1], outs[1][1]), (shape[:4], name, ns, "LSE of the split against split 1")
-        o, lse = _window_c(*args, 3, wl, 0.0, zero)               # zero slopes: the launch that slopes force must carry the window too
+        o, lse = dc.decode_c("window", *args, 3, wl, 0.0, zero)               # zero slopes: the launch that slopes force must carry the window too
         wr.check(o, lse, refs, (shape[:4], name, "zero slopes"))
         po, pl = flash_attention_decode(*args, window=wl, return_lse=True, num_splits=3)
         assert torch.equal(po.view(torch.int16), outs[3][0].view(torch.int16)) and dr.same_lse(pl * LOG2E, outs[3][1]), (shape[:4], name, "operator")
@@ -143,23 +73,23 @@ def test_windows_between_row_0s_reach_and_the_last_rows(shape):
 
 @pytest.mark.parametrize("shape", [wr.SHAPES[0], wr.SHAPES[2], wr.SHAPES[4]], ids=[wr.IDS[0], wr.IDS[2], wr.IDS[4]])
 def test_no_keywords_and_a_window_wider_than_the_cache_are_the_plain_call_bit_for_bit(shape):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k, v = wr.inputs(*shape)
     qd, kd_, vd_ = q.to(dev), wr.dirty(k, Nq, -1).to(dev), wr.dirty(v, Nq, -1).to(dev)
     lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
     for ns in (1, 3):
-        want = _plain_c(qd, kd_, vd_, lens, ns)
+        want = dc.decode_c("plain", qd, kd_, vd_, lens, ns)
         assert torch.isfinite(want[0].float()).all()
-        assert _same_bits(_window_c(qd, kd_, vd_, lens, ns), want), (shape[:4], ns, "window_left -1, softcap 0, null slopes")
-        assert _same_bits(_window_c(qd, kd_, vd_, lens, ns, window_left=5000), want), (shape[:4], ns, "window_left 5000")
+        assert dc.same_bits(dc.decode_c("window", qd, kd_, vd_, lens, ns), want), (shape[:4], ns, "window_left -1, softcap 0, null slopes")
+        assert dc.same_bits(dc.decode_c("window", qd, kd_, vd_, lens, ns, window_left=5000), want), (shape[:4], ns, "window_left 5000")
     # the same pair on an e4m3 cache with power-of-two descales
     k8, v8, kds, vds = _fp8_cache(k, v, Hkv, Nq, -1, dev)
     for ns in (1, 3):
-        want = _plain_c(qd, k8, v8, lens, ns, kds, vds)
+        want = dc.decode_c("fp8", qd, k8, v8, lens, ns, kd=kds, vd=vds)
         assert torch.isfinite(want[0].float()).all()
-        assert _same_bits(_window_c(qd, k8, v8, lens, ns, kd=kds, vd=vds), want), (shape[:4], ns, "e4m3, no keywords")
-        assert _same_bits(_window_c(qd, k8, v8, lens, ns, window_left=5000, kd=kds, vd=vds), want), (shape[:4], ns, "e4m3, window_left 5000")
+        assert dc.same_bits(dc.decode_c("window", qd, k8, v8, lens, ns, kd=kds, vd=vds), want), (shape[:4], ns, "e4m3, no keywords")
+        assert dc.same_bits(dc.decode_c("window", qd, k8, v8, lens, ns, window_left=5000, kd=kds, vd=vds), want), (shape[:4], ns, "e4m3, window_left 5000")
 
 
 def _fp8_parts(k, v, Hkv):
@@ -183,60 +113,38 @@ def _fp8_cache(k, v, Hkv, Nq, wl, dev):
     return _dirty8(k8, Nq, wl).to(dev), _dirty8(v8, Nq, wl).to(dev), kds.to(dev), vds.to(dev)
 
 
-def _paged(k, v, page, Nq, wl, g, spare=3):
-    """The clean [B, NMAX, Hkv, D] caches scattered into pages in shuffled physical order.  Pages no sequence uses, the spare pages AND every page that
-    holds only keys below its sequence's window are NaN; the block-table entries of the latter (and those beyond the used pages) point at a NaN page."""
-    B, per = k.shape[0], NMAX // page
-    kdirty, vdirty = wr.dirty(k, Nq, wl), wr.dirty(v, Nq, wl)
-    used = [-(-n // page) for n in LENS]
-    total = sum(used) + spare
-    order = torch.randperm(total, generator=g).tolist()
-    pk = torch.full((total, page) + tuple(k.shape[2:]), float("nan"), dtype=k.dtype)
-    pv = torch.full_like(pk, float("nan"))
-    nan_page = order[-1]
-    bt = torch.full((B, per), nan_page, dtype=torch.int32)
-    nxt, freed = 0, 0
-    for b in range(B):
-        lo = wr.window_lo(LENS[b], Nq, wl)
-        for j in range(used[b]):
-            pid = order[nxt]
-            nxt += 1
-            if (j + 1) * page <= lo:        # wholly below the window: the server freed it — the page stays NaN and the table names the NaN page
-                freed += 1
-                continue
-            pk[pid] = kdirty[b, j * page:(j + 1) * page]
-            pv[pid] = vdirty[b, j * page:(j + 1) * page]
-            bt[b, j] = pid
-    assert freed > 0
-    return pk, pv, bt
+def _paged(k, v, page, Nq, wl, g):
+    """The clean [B, NMAX, Hkv, D] caches, made dirty, in pages (decode_calls.paged).  A page that holds only keys below its sequence's window is one the
+    server freed: it stays NaN and the table names the NaN page."""
+    return dc.paged(wr.dirty(k, Nq, wl), wr.dirty(v, Nq, wl), LENS, page, g, keep=lambda b, j: (j + 1) * page > wr.window_lo(LENS[b], Nq, wl))
 
 
 @pytest.mark.parametrize("page", [64, 128])
 @pytest.mark.parametrize("shape", [wr.SHAPES[0], wr.SHAPES[3]], ids=[wr.IDS[0], wr.IDS[3]])
 def test_paged_with_freed_pages_is_bit_identical_to_contiguous(shape, page):
-    dev = _dev()
+    dev = dc.dev()
     name = "all"
     q, k, v, lens, sl, wl, cap = _device_case(shape, name, dev)
     cq, ck, cv = wr.inputs(*shape)
     pk, pv, bt = _paged(ck, cv, page, shape[2], wl, torch.Generator(device="cpu").manual_seed(page))
     pk, pv, bt = pk.to(dev), pv.to(dev), bt.to(dev)
     for ns in (1, 3, 16):
-        want = _window_c(q, k, v, lens, ns, wl, cap, sl)
-        got = _window_c(q, pk, pv, lens, ns, wl, cap, sl, block_table=bt)
-        assert _same_bits(got, want), (shape[:4], page, ns)
-    o, lse = _window_c(q, pk, pv, lens, 0, wl, cap, sl, block_table=bt)       # the plan's own split of the paged call
+        want = dc.decode_c("window", q, k, v, lens, ns, wl, cap, sl)
+        got = dc.decode_c("window", q, pk, pv, lens, ns, wl, cap, sl, block_table=bt)
+        assert dc.same_bits(got, want), (shape[:4], page, ns)
+    o, lse = dc.decode_c("window", q, pk, pv, lens, 0, wl, cap, sl, block_table=bt)       # the plan's own split of the paged call
     wr.check(o, lse, wr.case_refs(shape, name), (shape[:4], "paged", page))
     # window only, where nothing but the select keeps the freed pages out
     q, k, v, lens, _, wl, _ = _device_case(shape, "window31", dev)
     pk, pv, bt = (t.to(dev) for t in _paged(ck, cv, page, shape[2], wl, torch.Generator(device="cpu").manual_seed(page + 1)))
     for ns in (1, 3):
-        assert _same_bits(_window_c(q, pk, pv, lens, ns, wl, block_table=bt), _window_c(q, k, v, lens, ns, wl)), (shape[:4], page, ns, "window31")
+        assert dc.same_bits(dc.decode_c("window", q, pk, pv, lens, ns, wl, block_table=bt), dc.decode_c("window", q, k, v, lens, ns, wl)), (shape[:4], page, ns, "window31")
 
 
 @pytest.mark.parametrize("shape", [wr.SHAPES[0], wr.SHAPES[1], wr.SHAPES[3]], ids=[wr.IDS[0], wr.IDS[1], wr.IDS[3]])
 def test_fp8_cache_against_float64_of_the_descaled_cache(shape):
     """window=100, softcap=8.0 and [B, H] slopes on an e4m3 cache with power-of-two descales: the cap acts on the DESCALED score."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     q, k, v = wr.inputs(*shape)
     wl, cap, sl = 100, 8.0, wr.slopes_of("BH", len(LENS), H)
@@ -248,18 +156,18 @@ def test_fp8_cache_against_float64_of_the_descaled_cache(shape):
     lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
     args = (q.to(dev), _dirty8(k8, Nq, wl).to(dev), _dirty8(v8, Nq, wl).to(dev), lens)
     for ns in SPLITS:
-        o, lse = _window_c(*args, ns, wl, cap, sl.to(dev), kd=kds.to(dev), vd=vds.to(dev))
+        o, lse = dc.decode_c("window", *args, ns, wl, cap, sl.to(dev), kd=kds.to(dev), vd=vds.to(dev))
         wr.check(o, lse, refs, (shape[:4], "fp8", ns))
     # the operator reaches the same bits
     po, pl = flash_attention_decode(*args, window=wl, softcap=cap, alibi_slopes=sl.to(dev), k_descale=kds.to(dev), v_descale=vds.to(dev), return_lse=True,
                                     num_splits=3)
-    o, lse = _window_c(*args, 3, wl, cap, sl.to(dev), kd=kds.to(dev), vd=vds.to(dev))
+    o, lse = dc.decode_c("window", *args, 3, wl, cap, sl.to(dev), kd=kds.to(dev), vd=vds.to(dev))
     assert torch.equal(po.view(torch.int16), o.view(torch.int16)) and dr.same_lse(pl * LOG2E, lse)
 
 
 @pytest.mark.parametrize("shape", [wr.SHAPES[0], wr.SHAPES[2]], ids=[wr.IDS[0], wr.IDS[2]])
 def test_operator_gives_the_c_calls_bits(shape):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt = shape
     B = len(LENS)
     for name, window in (("window31", 31), ("window100", (100, 0)), ("softcap30", None), ("slopes_H", None), ("all", (100, None))):
@@ -270,7 +178,7 @@ def test_operator_gives_the_c_calls_bits(shape):
         kw[:, :NMAX] = k
         assert not qw[:, :, :H].is_contiguous() and not kw[:, :NMAX].is_contiguous()
         for ns in (1, 3):
-            o, lse = _window_c(q, k, v, lens, ns, wl, cap, sl)
+            o, lse = dc.decode_c("window", q, k, v, lens, ns, wl, cap, sl)
             po = flash_attention_decode(q, k, v, lens, num_splits=ns, window=window, softcap=cap, alibi_slopes=sl)
             assert torch.equal(po.view(torch.int16), o.view(torch.int16)), (shape[:4], name, ns)
             so, sl2 = flash_attention_decode(qw[:, :, :H], kw[:, :NMAX], v, lens, num_splits=ns, window=window, softcap=cap, alibi_slopes=sl, return_lse=True)
@@ -280,7 +188,7 @@ def test_operator_gives_the_c_calls_bits(shape):
 
 @pytest.mark.parametrize("dt", [F16, BF16], ids=["f16", "bf16"])
 def test_fused_append_under_a_window_is_append_then_the_windowed_call(dt):
-    dev = _dev()
+    dev = dc.dev()
     B, H, Hkv, Nq, D, N, wl = 4, 8, 2, 3, 128, 256, 40
     g = torch.Generator(device="cpu").manual_seed(23)
     q = (2 * torch.randn((B, Nq, H, D), generator=g)).to(dt).to(dev)
@@ -306,7 +214,7 @@ def test_fused_append_under_a_window_is_append_then_the_windowed_call(dt):
 def test_graph_replay_follows_lengths_and_slopes_changed_in_place(ns):
     """The host reads neither cache_seqlens nor the slopes: one captured call with a window and slopes, replayed after both were overwritten in place,
     gives the eager result for the contents at that time (a fully valid cache, so that every permutation of the lengths is a legal call)."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, Nq, D, dt, wl = 8, 2, 3, 128, F16, 100
     g = torch.Generator(device="cpu").manual_seed(78)
     B = len(LENS)

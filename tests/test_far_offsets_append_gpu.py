@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import decode_calls as dc
 import far_layouts as fl
 from rocwmma_fattn.FlashAttn import kvcache_append
 
@@ -23,12 +24,11 @@ NEW_AT = (4 * fl.MIB + 1040, 5 * fl.MIB + 2080)      # k_new / v_new: behind the
 
 @pytest.fixture(scope="module")
 def arena():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
+    dev = dc.dev()
     free, _ = torch.cuda.mem_get_info()
     if free < fl.ARENA_BYTES + 2 * fl.GIB:
         pytest.skip("the far-offset arena needs %.2f GiB + 2 GiB of free device memory, the device reports %.2f GiB" % (fl.ARENA_BYTES / fl.GIB, free / fl.GIB))
-    a = fl.new_arena(fl.ARENA_BYTES, torch.device("cuda", 0))
+    a = fl.new_arena(fl.ARENA_BYTES, dev)
     yield a
     del a
     torch.cuda.empty_cache()

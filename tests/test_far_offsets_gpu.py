@@ -28,6 +28,7 @@ import time
 import pytest
 import torch
 
+import decode_calls as dc
 import decode_refs as dr
 import far_layouts as fl
 import lse_refs as R
@@ -764,11 +765,6 @@ def test_f32_tensors_at_element_indices_past_two_to_the_31(ff, fm):
 DECODE_SPLITS = (1, 3, 0)          # 0: the plan's own choice
 
 
-def _d3(t):
-    """{batch | page, head, row} element strides of a [B, N, heads, D] view."""
-    return _fa2_lib.strides3(t.stride(0), t.stride(2), t.stride(1))
-
-
 def _decode_dims(case):
     paged = case["layout"] == "paged"
     return (_code(case), case["B"], case["H"], case["Hkv"], case["Nq"], case["D"], fl.DECODE_NMAX // case["page"] if paged else case["nmax"], case["page"])
@@ -786,15 +782,10 @@ def _decode_plan(case, fmt, ns):
 
 
 def _decode_call(case, fmt, T, ns, need):
-    lib, paged = _fa2_lib.load(), case["layout"] == "paged"
-    dims = _decode_dims(case)
-    head = (dims[0], *[T[n].data_ptr() for n in ("q", "k", "v", "o", "lse", "lens")], T["bt"].data_ptr() if paged else None, *dims[1:],
-            T["k"].shape[0] if paged else 0, _d3(T["q"]), _d3(T["k"]), _d3(T["v"]), _d3(T["o"]), _s2(T["lse"]), T["bt"].stride(0) if paged else 0, _scale(case))
-    tail = (ns, T["ws"].data_ptr() if need else None, need, _stream())
-    if fmt != "fp8":
-        return lib.fa2_fwd_decode(*head, *tail)
-    d0 = T.get("kd", T.get("vd"))
-    return lib.fa2_fwd_decode_fp8(*head, T["kd"].data_ptr() if "kd" in T else None, T["vd"].data_ptr() if "vd" in T else None, _s2(d0), *tail)
+    """the C entry of the format on the slot views T (decode_calls.py has the argument order) -> its return code"""
+    kw = dc.tensor_kw(T["q"], T["k"], T["v"], T["o"], T["lse"], T["lens"], T.get("bt"), T.get("kd"), T.get("vd"), scale=_scale(case))
+    assert tuple(kw[n] for n in ("dtype", "B", "H", "Hkv", "Nq", "D", "cap", "page")) == _decode_dims(case)
+    return dc.call("fp8" if fmt == "fp8" else "plain", **kw, ns=ns, ws=T["ws"].data_ptr() if need else None, wsb=need, stream=_stream())
 
 
 def _decode_prepare(case, fmt):

@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+import decode_calls as dc
 from conftest import ROOT
-from rocwmma_fattn import FlashAttn, _fa2_lib
+from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode, kvcache_append
 from kvappend_refs import rotary_bar, rotary_ref64
 
@@ -115,19 +116,15 @@ def test_rotary_eval_error_codes():
     assert a(dt=2) == DTYPE and a(dt=2, rot=24) == HEAD_DIM and a(dt=2, D=0) == SHAPE and a(D=0, x=None) == NULLP
 
 
+P = dc.HOST                                  # 16-byte aligned host memory that no call here ever touches
+DEFAULTS = dict(dtype=F16, fmt=C16, kn=P, vn=P, k=P, v=P, lens=P, bt=None, B=2, Hkv=2, N=1, D=128, cap=256, page=0, pages=0, kns=_fa2_lib.strides3(256, 128, 256),
+                vns=_fa2_lib.strides3(256, 128, 256), ks=_fa2_lib.strides3(256 * 256, 128, 256), vs=_fa2_lib.strides3(256 * 256, 128, 256), bts=0, q=None, qo=None,
+                H=0, Nq=0, qs=None, qos=None, cos=None, sin=None, rdt=F32, rot=0, sro=0, ros=0, inter=1, kd=None, vd=None, ds=None)
+
+
 def _call(**kw):
     """fa2_kvcache_append on host memory that is never touched: every call here is refused before the launch."""
-    lib = _fa2_lib.load()
-    buf = ctypes.create_string_buffer(4096 + 16)
-    p = (ctypes.addressof(buf) + 15) & ~15
-    s3, s2 = _fa2_lib.strides3, _fa2_lib.strides2
-    a = dict(dtype=F16, fmt=C16, kn=p, vn=p, k=p, v=p, lens=p, bt=None, B=2, Hkv=2, N=1, D=128, cap=256, page=0, pages=0, kns=s3(256, 128, 256),
-             vns=s3(256, 128, 256), ks=s3(256 * 256, 128, 256), vs=s3(256 * 256, 128, 256), bts=0, q=None, qo=None, H=0, Nq=0, qs=None, qos=None, cos=None,
-             sin=None, rdt=F32, rot=0, sro=0, ros=0, inter=1, kd=None, vd=None, ds=None)
-    a.update(kw)
-    return lib.fa2_kvcache_append(*[a[n] for n in ("dtype", "fmt", "kn", "vn", "k", "v", "lens", "bt", "B", "Hkv", "N", "D", "cap", "page", "pages", "kns", "vns",
-                                                   "ks", "vs", "bts", "q", "qo", "H", "Nq", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter", "kd",
-                                                   "vd", "ds")], None)
+    return dc.host_call("append", DEFAULTS, **kw)
 
 
 def _ptr():
@@ -269,47 +266,30 @@ def test_operator_argument_checks():
         flash_attention_decode(q, kc, vc, lens, k=k, v=v, rotary_cos=cos, rotary_sin=sin, rotary_interleaved=False)
 
 
-class _Recorder:
-    def __init__(self):
-        self.calls = []
-
-    def fa2_fwd_decode_workspace_bytes(self, *a):
-        return 0
-
-    def fa2_fwd_decode(self, *a):
-        self.calls.append(("decode", a[1]))
-        return 0
-
-    def fa2_kvcache_append(self, *a):
-        self.calls.append(("append", len(a), a[20], a[21], a[29]))
-        return 0
+def _brief(calls):
+    """the decode entry with its q, the append with its argument count, q, q_out and rotary_dim; the size queries left out"""
+    out = []
+    for name, a in calls:
+        if name == "fa2_fwd_decode":
+            out.append(("decode", dc.arg("plain", a, "q")))
+        elif name == "fa2_kvcache_append":
+            out.append(("append", len(a)) + tuple(dc.arg("append", a, n) for n in ("q", "qo", "rot")))
+        else:
+            assert name == "fa2_fwd_decode_workspace_bytes", name
+    return out
 
 
 def test_the_fused_call_appends_then_decodes_on_the_rotated_q(monkeypatch):
-    rec = _Recorder()
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
-    monkeypatch.setattr(_fa2_lib, "load", lambda: rec)
-    monkeypatch.setattr(FlashAttn, "_raw_stream", lambda dev: None)
-    monkeypatch.setattr(FlashAttn, "_current_device", lambda: 0)
-    monkeypatch.setattr(FlashAttn, "_workspace_unused", lambda dev, stream: None)
-
-    class _Ctx:
-        def __enter__(self):
-            return self
-
-        def __exit__(self, *exc):
-            return False
-
-    monkeypatch.setattr(torch.cuda, "device", lambda dev: _Ctx())
+    rec = dc.recording_lib(monkeypatch)
     q, kc, vc, k, v, lens = _args()
     cos, sin = torch.ones(16, 32), torch.zeros(16, 32)
     flash_attention_decode(q, kc, vc, lens)                                                  # no new keyword: the one launch it made before
-    assert rec.calls == [("decode", q.data_ptr())]
+    assert _brief(rec.calls) == [("decode", q.data_ptr())]
     del rec.calls[:]
     flash_attention_decode(q, kc, vc, lens, k=k, v=v)                                        # no rotary: q is not touched and not passed
-    assert rec.calls == [("append", 37, None, None, 0), ("decode", q.data_ptr())]
+    assert _brief(rec.calls) == [("append", 37, None, None, 0), ("decode", q.data_ptr())]
     del rec.calls[:]
     flash_attention_decode(q, kc, vc, lens, k=k, v=v, rotary_cos=cos, rotary_sin=sin)
-    (tag, n, qin, qout, rot), (tag2, qdec) = rec.calls
+    (tag, n, qin, qout, rot), (tag2, qdec) = _brief(rec.calls)
     assert (tag, n, qin, rot, tag2) == ("append", 37, q.data_ptr(), 64, "decode") and qout not in (None, q.data_ptr()) and qdec == qout
     assert kvcache_append(kc, vc, k, v, lens) is None

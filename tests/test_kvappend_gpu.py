@@ -14,8 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+import decode_calls as dc
 import decode_refs as dr
-from rocwmma_fattn import _fa2_lib
 from rocwmma_fattn.FlashAttn import flash_attention_decode, kvcache_append
 from kvappend_refs import rotary_bar, rotary_ref64
 
@@ -28,16 +28,6 @@ LOG2E = 1.4426950408889634
 # (H, Hkv, Nq, D, dtype): the decode tests' list — 1, 4, 20, 48 and 64 rows per K / V head
 SHAPES = [(8, 8, 1, 128, F16), (8, 2, 1, 64, BF16), (10, 2, 4, 128, BF16), (16, 1, 3, 64, F16), (16, 1, 4, 128, F16)]
 IDS = ["H%d_Hkv%d_Nq%d_D%d_%s" % (s[0], s[1], s[2], s[3], "f16" if s[4] == F16 else "bf16") for s in SHAPES]
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    return torch.device("cuda", 0)
-
-
-def _code(dt):
-    return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
 
 
 def _pattern(nbytes, salt=0):
@@ -55,21 +45,6 @@ def _pool(shape, dt, salt=0):
 def _bytes(t):
     """the bytes of a contiguous cache tensor, [..., D * element size]"""
     return t.contiguous().view(torch.uint8)
-
-
-def _block_table(lens, page, g, spare=3):
-    """shuffled physical pages for the used logical pages, spare pages, and unused entries that name one of the spare pages (a valid id)"""
-    per = NMAX // page
-    used = [-(-n // page) for n in lens]
-    total = sum(used) + spare
-    order = torch.randperm(total, generator=g).tolist()
-    bt = torch.full((len(lens), per), order[-1], dtype=torch.int32)
-    nxt = 0
-    for b, u in enumerate(used):
-        for j in range(u):
-            bt[b, j] = order[nxt]
-            nxt += 1
-    return bt, total
 
 
 def _targets(lens, nnew, cap):
@@ -101,7 +76,7 @@ LAYOUTS = ["contiguous", "paged64", "paged128", "strided"]
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_image(shape, layout):
     """No rotary, 16-bit cache: V rows and K rows equal the source bit for bit at their targets, every other byte of the pool is unchanged."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, nnew, D, dt = shape
     B = len(LENS)
     _, k, v = _new_tokens(B, nnew, H, Hkv, D, dt, 11 + H)
@@ -109,7 +84,7 @@ def test_image(shape, layout):
     page, bt = 0, None
     if layout.startswith("paged"):
         page = int(layout[5:])
-        bt, total = _block_table(LENS, page, g)
+        bt, total, _ = dc.block_table(LENS, NMAX // page, page, g)
         kc, vc = _pool((total, page, Hkv, D), dt), _pool((total, page, Hkv, D), dt, 5)
         kview, vview = kc.to(dev), vc.to(dev)
     elif layout == "strided":                                  # a padded Nmax stride and a padded head stride
@@ -163,7 +138,7 @@ def _check_rotated(got, x, cos, sin, pos, rot, inter, dt, tag):
 @pytest.mark.parametrize("table", ["f32", "io"])
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_rotary(shape, table):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, nnew, D, dt = shape
     B = len(LENS)
     q, k, v = _new_tokens(B, nnew, H, Hkv, D, dt, 23 + H)
@@ -193,11 +168,11 @@ def test_rotary(shape, table):
 def test_head_dim_96_rotary_dim_32():
     """A head dim decode does not serve (the append alone does): D = 96 is 12 chunks of 8 columns, rotary_dim 32 leaves 8 pass-through chunks behind
     the rotated span; both pairings, paged."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, nnew, D, dt, rot = 4, 2, 3, 96, F16, 32
     B = len(LENS)
     q, k, v = _new_tokens(B, nnew, H, Hkv, D, dt, 96)
-    bt, total = _block_table(LENS, 64, torch.Generator(device="cpu").manual_seed(96))
+    bt, total, _ = dc.block_table(LENS, NMAX // 64, 64, torch.Generator(device="cpu").manual_seed(96))
     cos, sin = _tables(rot, torch.float32)
     lens = torch.tensor(LENS, dtype=torch.int32, device=dev)
     tg = _targets(LENS, nnew, NMAX)
@@ -221,11 +196,11 @@ def test_head_dim_96_rotary_dim_32():
 def test_a_130_token_append():
     """Nnew = 130, more than two pages of 64: a prefill chunk.  Lengths after the append put tokens at negative positions (100), at the start of the
     cache (130), across page edges (200, 1000) and at the cache's last slot (1024)."""
-    dev = _dev()
+    dev = dc.dev()
     lens_t, nnew, H, Hkv, D, dt = (130, 200, 1000, 100, 1024), 130, 4, 2, 64, BF16
     B = len(lens_t)
     q, k, v = _new_tokens(B, nnew, H, Hkv, D, dt, 130)
-    bt, total = _block_table(lens_t, 64, torch.Generator(device="cpu").manual_seed(130))
+    bt, total, _ = dc.block_table(lens_t, NMAX // 64, 64, torch.Generator(device="cpu").manual_seed(130))
     lens = torch.tensor(lens_t, dtype=torch.int32, device=dev)
     kc, vc = _pool((total, 64, Hkv, D), dt), _pool((total, 64, Hkv, D), dt, 5)
     kcd, vcd = kc.to(dev), vc.to(dev)
@@ -255,7 +230,7 @@ def _quant_ref(x, d=None):
 @pytest.mark.parametrize("dt", [F16, BF16], ids=["f16", "bf16"])
 def test_e4m3_every_input_pattern(dt):
     """All 65 536 bit patterns of the I/O dtype as v (and as k), 512 rows of 128, descale 1 (None and an explicit tensor of ones)."""
-    dev = _dev()
+    dev = dc.dev()
     x = torch.arange(65536, dtype=torch.int32).to(torch.int16).view(dt).reshape(1, 512, 1, 128)
     lens = torch.tensor([512], dtype=torch.int32, device=dev)
     ones = torch.ones((1, 1), device=dev)
@@ -275,7 +250,7 @@ def test_e4m3_every_input_pattern(dt):
 @pytest.mark.parametrize("layout", ["contiguous", "paged64"])
 @pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2], SHAPES[3]], ids=[IDS[1], IDS[2], IDS[3]])
 def test_e4m3_power_of_two_descales_are_bit_exact(shape, layout):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, nnew, D, dt = shape
     B = len(LENS)
     _, k, v = _new_tokens(B, nnew, H, Hkv, D, dt, 31 + H)
@@ -284,7 +259,7 @@ def test_e4m3_power_of_two_descales_are_bit_exact(shape, layout):
     page, bt = 0, None
     if layout == "paged64":
         page = 64
-        bt, total = _block_table(LENS, page, g)
+        bt, total, _ = dc.block_table(LENS, NMAX // page, page, g)
     cshape = (total, page, Hkv, D) if page else (B, NMAX, Hkv, D)
     kc, vc = _pool(cshape, E4M3), _pool(cshape, E4M3, 5)
     kcd, vcd = kc.to(dev), vc.to(dev)
@@ -300,7 +275,7 @@ def test_e4m3_power_of_two_descales_are_bit_exact(shape, layout):
 def test_e4m3_general_descale_and_rotated_k(inter):
     """Descales that are no powers of two, K rotated: the dequantised error against float64 is at most half an e4m3 step of the exact value plus f32
     slack, (2^-4 + 2^-20) |exact|, plus half the smallest subnormal step times the descale, d * 2^-10.  (|exact / d| stays below 448: no clamp.)"""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, nnew, D, dt = SHAPES[2]
     B = len(LENS)
     q, k, v = _new_tokens(B, nnew, H, Hkv, D, dt, 57)
@@ -359,7 +334,7 @@ def _fused_case(H, Hkv, nnew, D, dt, fmt):
 @pytest.mark.parametrize("fmt", ["16", "fp8"])
 @pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2], SHAPES[3]], ids=[IDS[1], IDS[2], IDS[3]])
 def test_fused_call_equals_append_then_decode(shape, fmt):
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, nnew, D, dt = shape
     q, k, v, kc, vc, kd, vd, cos, sin = _fused_case(*shape, fmt)
     qd, kn, vn, cosd, sind = (t.to(dev) for t in (q, k, v, cos, sin))
@@ -378,14 +353,14 @@ def test_fused_call_equals_append_then_decode(shape, fmt):
         assert not torch.equal(_bytes(ka.cpu()), _bytes(kc)), "the append wrote"
         if refs is None:                                       # the references: on the cache contents and the rotated q read back from the device
             args = (q_rot.cpu(), ka.cpu(), va.cpu())
-            refs = dr.refs16(*args, LENS, _code(dt)) if fmt == "16" else dr.refs_fp8(*args, kd, vd, LENS, _code(dt))
-        dr.check(o, lse * LOG2E, refs, LENS, _code(dt), (shape[:4], fmt, ns), verbose=True)
+            refs = dr.refs16(*args, LENS, dc.code(dt)) if fmt == "16" else dr.refs_fp8(*args, kd, vd, LENS, dc.code(dt))
+        dr.check(o, lse * LOG2E, refs, LENS, dc.code(dt), (shape[:4], fmt, ns), verbose=True)
 
 
 def test_graph_replay_of_the_fused_paged_call():
     """One captured serving step — lengths incremented in place, new k / v / q copied into the captured inputs — replayed for three steps: each equals
     the eager call on a twin cache."""
-    dev = _dev()
+    dev = dc.dev()
     H, Hkv, D, dt, page = 8, 2, 128, F16, 64
     start = (5, 62, 63, 126, 0)
     B, per = len(start), 4

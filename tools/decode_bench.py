@@ -25,7 +25,6 @@ The same K / V are read in every iteration, so caches up to the 256 MB of Infini
 """
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
@@ -33,6 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
 
 import torch  # noqa: E402
 
+from benchlib import close, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
 from rocwmma_fattn.FlashAttn import flash_attention, flash_attention_decode, flash_attention_varlen  # noqa: E402
 
@@ -46,33 +46,6 @@ UNIFORM = [  # (label, B, H, Hkv, Nq, keys, D, dtype)
     ("b8_hkv8_nq4", 8, 32, 8, 4, 8192, 128, torch.float16),
 ]
 RAGGED = ("ragged_b32", 32, 32, 8, 1, 256, 8192, 128, torch.float16)      # label, B, H, Hkv, Nq, shortest, longest, D, dtype
-
-
-def interleaved(fns, rounds, iters):
-    """{name: (median, min, max) ms per call} of the callables in `fns`, timed round-robin (one event pair per (round, callable))."""
-    for f in fns.values():
-        for _ in range(3):
-            f()
-    torch.cuda.synchronize()
-    times = {n: [] for n in fns}
-    for _ in range(rounds):
-        for n, f in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                f()
-            e1.record()
-            torch.cuda.synchronize()
-            times[n].append(e0.elapsed_time(e1) / iters)
-    return {n: (statistics.median(t), min(t), max(t)) for n, t in times.items()}
-
-
-def close(a, b, dt, what):
-    atol, rtol = (1e-3, 2e-3) if dt == torch.float16 else (8e-3, 1.6e-2)
-    a, b = a.float(), b.float()
-    bad = (a - b).abs() > atol + rtol * b.abs()
-    if bad.any() or not torch.isfinite(a).all():
-        raise SystemExit("decode_bench: %s disagree (max |diff| %.3g)" % (what, float((a - b).abs().max())))
 
 
 def report(label, shape, t, valid_bytes, base):
@@ -100,7 +73,7 @@ def uniform_row(label, B, H, Hkv, Nq, keys, D, dt, rounds, iters):
         dense = lambda: flash_attention(qh, kh[:, :, :keys], vh[:, :, :keys], causal=True, q_offset=keys - Nq)  # noqa: E731
     fns = {"decode": lambda: flash_attention_decode(q, kc, vc, lens), "dense": dense}
     with torch.no_grad():
-        close(fns["decode"]().transpose(1, 2), fns["dense"](), dt, label + ": decode and dense")
+        close("decode_bench", fns["decode"]().transpose(1, 2), fns["dense"](), dt, label + ": decode and dense")
         t = interleaved(fns, rounds, iters)
     plan = _fa2_lib.decode_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, nmax)
     shape = "B%d H%d Hkv%d Nq%d keys %d D%d %s (split %d, %d row tile%s)" % (B, H, Hkv, Nq, keys, D, "fp16" if dt == torch.float16 else "bf16", plan.nsplit,
@@ -152,7 +125,7 @@ def fp8_uniform_row(label, B, H, Hkv, Nq, keys, D, dt, rounds, iters):
         fns["dequant+call"] = lambda: flash_attention_decode(q, dq(k8, kd), dq(v8, vd), lens)
     with torch.no_grad():
         for n in fns:
-            close(fns[n](), fns[name16](), dt, label + ": %s and %s" % (n, name16))
+            close("decode_bench", fns[n](), fns[name16](), dt, label + ": %s and %s" % (n, name16))
         t = interleaved(fns, rounds, iters)
     plan = _fa2_lib.decode_fp8_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, nmax)
     shape = "B%d H%d Hkv%d Nq%d keys %d D%d %s (split %d, key tile %d)" % (B, H, Hkv, Nq, keys, D, name16, plan.nsplit, plan.key_tile)
@@ -167,8 +140,8 @@ def fp8_ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
     q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
     (k8, kd, kc), (v8, vd, vc) = (quantise(torch.randn((B, hi, Hkv, D), device=dev, dtype=dt), g) for _ in range(2))
     lens = torch.tensor(lens_h, dtype=torch.int32, device=dev)
-    p16 = paged(kc, vc, lens_h, 64, torch.Generator(device="cpu").manual_seed(3))
-    p8 = paged(k8.view(torch.uint8), v8.view(torch.uint8), lens_h, 64, torch.Generator(device="cpu").manual_seed(3))
+    p16 = paged_pool(kc, vc, 64, torch.Generator(device="cpu").manual_seed(3), lens=lens_h)
+    p8 = paged_pool(k8.view(torch.uint8), v8.view(torch.uint8), 64, torch.Generator(device="cpu").manual_seed(3), lens=lens_h)
     pk8, pv8 = p8[0].view(torch.float8_e4m3fn), p8[1].view(torch.float8_e4m3fn)
     fns = {name16: lambda: flash_attention_decode(q, kc, vc, lens),
            "fp8": lambda: flash_attention_decode(q, k8, v8, lens, k_descale=kd, v_descale=vd),
@@ -176,7 +149,7 @@ def fp8_ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
            "fp8_pg64": lambda: flash_attention_decode(q, pk8, pv8, lens, block_table=p8[2], k_descale=kd, v_descale=vd)}
     with torch.no_grad():
         for n in fns:
-            close(fns[n](), fns[name16](), dt, label + ": %s and %s" % (n, name16))
+            close("decode_bench", fns[n](), fns[name16](), dt, label + ": %s and %s" % (n, name16))
         t = interleaved(fns, rounds, max(1, iters // 2))
     plan = _fa2_lib.decode_fp8_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, hi)
     shape = "B%d H%d Hkv%d Nq%d keys %d .. %d (mean %d) D%d %s (split %d, key tile %d)" % (B, H, Hkv, Nq, min(lens_h), max(lens_h), sum(lens_h) // B, D, name16,
@@ -184,24 +157,6 @@ def fp8_ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
     bytes16 = 2 * Hkv * sum(lens_h) * D * 2
     report_fp8(label + "_fp8", shape, {n: t[n] for n in (name16, "fp8")}, bytes16, name16)
     report_fp8(label + "_fp8_pg64", shape, {n: t[n] for n in (name16 + "_pg64", "fp8_pg64")}, bytes16, name16 + "_pg64")
-
-
-def paged(kc, vc, lens, page, g):
-    B, nmax = kc.shape[0], kc.shape[1]
-    used = [-(-n // page) for n in lens]
-    total = sum(used) + 4
-    order = torch.randperm(total, generator=g).tolist()
-    pk = torch.zeros((total, page) + tuple(kc.shape[2:]), device=kc.device, dtype=kc.dtype)
-    pv = torch.zeros_like(pk)
-    bt = torch.full((B, nmax // page), order[-1], dtype=torch.int32)
-    nxt = 0
-    for b in range(B):
-        for j in range(used[b]):
-            pk[order[nxt]] = kc[b, j * page:(j + 1) * page]
-            pv[order[nxt]] = vc[b, j * page:(j + 1) * page]
-            bt[b, j] = order[nxt]
-            nxt += 1
-    return pk, pv, bt.to(kc.device)
 
 
 def ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
@@ -219,7 +174,7 @@ def ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
     kp, vp = pack(kc), pack(vc)
     qh, kh, vh = q.transpose(1, 2).contiguous(), kc.transpose(1, 2).contiguous(), vc.transpose(1, 2).contiguous()
     keep = (torch.arange(nmax, device=dev)[None, :] < lens[:, None]).view(B, 1, 1, nmax)
-    p64, p256 = paged(kc, vc, lens_h, 64, g), paged(kc, vc, lens_h, 256, g)
+    p64, p256 = paged_pool(kc, vc, 64, g, lens=lens_h), paged_pool(kc, vc, 256, g, lens=lens_h)
     fns = {
         "decode": lambda: flash_attention_decode(q, kc, vc, lens),
         "paged64": lambda: flash_attention_decode(q, p64[0], p64[1], lens, block_table=p64[2]),
@@ -231,8 +186,8 @@ def ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
     with torch.no_grad():
         want = fns["varlen"]().reshape(B, Nq, H, D)
         for n in ("decode", "paged64", "paged256"):
-            close(fns[n](), want, dt, label + ": %s and varlen" % n)
-        close(fns["padmask"]().transpose(1, 2), want, dt, label + ": padmask and varlen")
+            close("decode_bench", fns[n](), want, dt, label + ": %s and varlen" % n)
+        close("decode_bench", fns["padmask"]().transpose(1, 2), want, dt, label + ": padmask and varlen")
         t = interleaved(fns, rounds, max(1, iters // 2))
     plan = _fa2_lib.decode_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, nmax)
     shape = "B%d H%d Hkv%d Nq%d keys %d .. %d (mean %d) D%d %s (split %d)" % (B, H, Hkv, Nq, min(lens_h), max(lens_h), sum(lens_h) // B, D,

@@ -19,7 +19,6 @@ Each row first checks its routes against each other on the timed inputs."""
 import argparse
 import ctypes
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
@@ -27,6 +26,8 @@ sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
 
 import torch  # noqa: E402
 
+import decode_abi as dc  # noqa: E402 - the one copy of the C argument lists
+from benchlib import close, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
 from rocwmma_fattn.FlashAttn import flash_attention_decode  # noqa: E402
 
@@ -35,32 +36,6 @@ PLAIN = [("b1_hkv8", 1, 32, 8, 1, 8192, 128, torch.float16), ("b1_hkv1_mqa", 1, 
          ("b1_hkv32_mha", 1, 32, 32, 1, 8192, 128, torch.float16), ("b32_hkv8_bf16", 32, 32, 8, 1, 4096, 128, torch.bfloat16),
          ("b4_h8_d64", 4, 8, 8, 1, 16384, 64, torch.float16), ("b8_hkv8_nq4", 8, 32, 8, 4, 8192, 128, torch.float16)]       # tools/decode_bench.py's UNIFORM
 KEYS = 32768
-
-
-def interleaved(fns, rounds, iters):
-    """{name: (median, min, max) ms per call}, timed round-robin (one event pair per (round, callable))."""
-    for f in fns.values():
-        for _ in range(3):
-            f()
-    torch.cuda.synchronize()
-    times = {n: [] for n in fns}
-    for _ in range(rounds):
-        for n, f in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                f()
-            e1.record()
-            torch.cuda.synchronize()
-            times[n].append(e0.elapsed_time(e1) / iters)
-    return {n: (statistics.median(t), min(t), max(t)) for n, t in times.items()}
-
-
-def close(a, b, dt, what):
-    atol, rtol = (1e-3, 2e-3) if dt == torch.float16 else (8e-3, 1.6e-2)
-    a, b = a.float(), b.float()
-    if ((a - b).abs() > atol + rtol * b.abs()).any() or not torch.isfinite(a).all():
-        raise SystemExit("decode_window_bench: %s disagree (max |diff| %.3g)" % (what, float((a - b).abs().max())))
 
 
 def report(label, shape, t, base, compare=()):
@@ -80,23 +55,12 @@ def report(label, shape, t, base, compare=()):
     sys.stdout.flush()
 
 
-def paged64(kc, vc, g):
-    """the whole [B, N, Hkv, D] caches in pages of 64 in shuffled physical order -> pool K, pool V, block table"""
-    B, N = kc.shape[0], kc.shape[1]
-    P = N // 64
-    order = torch.randperm(B * P, generator=g)
-    inv = torch.argsort(order).to(kc.device)
-    pk = kc.reshape(B * P, 64, *kc.shape[2:])[inv]
-    pv = vc.reshape(B * P, 64, *vc.shape[2:])[inv]
-    return pk, pv, order.reshape(B, P).to(torch.int32).to(kc.device)
-
-
 def window_rows(label, B, H, Hkv, Nq, D, dt, rounds, iters):
     dev = torch.device("cuda", 0)
     code = 0 if dt == torch.float16 else 1
     q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
     kc, vc = (torch.randn((B, KEYS, Hkv, D), device=dev, dtype=dt) for _ in range(2))
-    pk, pv, bt = paged64(kc, vc, torch.Generator(device="cpu").manual_seed(5))
+    pk, pv, bt = paged_pool(kc, vc, 64, torch.Generator(device="cpu").manual_seed(5), spare=0)
     full = torch.full((B,), KEYS, dtype=torch.int32, device=dev)
     for layout, (k, v, kw) in (("contiguous", (kc, vc, {})), ("pages of 64", (pk, pv, dict(block_table=bt)))):
         for W in (1023, 4095):
@@ -110,8 +74,9 @@ def window_rows(label, B, H, Hkv, Nq, D, dt, rounds, iters):
                    "full": lambda: flash_attention_decode(q, k, v, full, **kw)}
             with torch.no_grad():
                 lo = KEYS - Nq - W           # the window of a full cache is the plain call on that slice of it
-                close(flash_attention_decode(q, kc, vc, full, window=W), flash_attention_decode(q, kc[:, lo:], vc[:, lo:], short), dt, label + ": window and slice")
-                close(fns["window"](), flash_attention_decode(q, kc, vc, full, window=W), dt, label + ": the layouts")
+                close("decode_window_bench", flash_attention_decode(q, kc, vc, full, window=W), flash_attention_decode(q, kc[:, lo:], vc[:, lo:], short), dt,
+                      label + ": window and slice")
+                close("decode_window_bench", fns["window"](), flash_attention_decode(q, kc, vc, full, window=W), dt, label + ": the layouts")
                 t = interleaved(fns, rounds, iters)
             shape = "B%d H%d Hkv%d Nq%d D%d %s, %d valid keys, %s, window %d (split %d; reference and full: split %d)" % (
                 B, H, Hkv, Nq, D, "fp16" if dt == torch.float16 else "bf16", KEYS, layout, W, ns, ns0)
@@ -133,7 +98,8 @@ def scoremod_rows(label, B, H, Hkv, Nq, D, dt, rounds, iters):
            "cap+alibi_e4m3": lambda: flash_attention_decode(q, k8, v8, lens, k_descale=d, v_descale=d, softcap=30.0, alibi_slopes=sl)}
     with torch.no_grad():
         zero = torch.zeros_like(sl)
-        close(flash_attention_decode(q, kc, vc, lens, alibi_slopes=zero), fns["plain"](), dt, label + ": the banded kernel with zero slopes and plain")
+        close("decode_window_bench", flash_attention_decode(q, kc, vc, lens, alibi_slopes=zero), fns["plain"](), dt,
+              label + ": the banded kernel with zero slopes and plain")
         t = interleaved(fns, rounds, iters)
     shape = "B%d H%d Hkv%d Nq%d D%d %s, %d keys, softcap 30 and [H] slopes" % (B, H, Hkv, Nq, D, "fp16" if dt == torch.float16 else "bf16", keys)
     report(label + "_smod", shape, {n: t[n] for n in ("plain", "cap+alibi")}, "plain")
@@ -147,7 +113,6 @@ def plain_rows(parent_path, rounds, iters):
     names = ("fa2_fwd_decode", "fa2_fwd_decode_fp8", "fa2_fwd_decode_workspace_bytes")
     for n in names:
         getattr(libs["parent"], n).restype, getattr(libs["parent"], n).argtypes = _fa2_lib.SYMBOLS[n]
-    s3 = lambda t: _fa2_lib.strides3(t.stride(0), t.stride(2), t.stride(1))  # noqa: E731
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     for (label, B, H, Hkv, Nq, keys, D, dt) in PLAIN:
         code = 0 if dt == torch.float16 else 1
@@ -166,14 +131,10 @@ def plain_rows(parent_path, rounds, iters):
             o = torch.empty((B, Nq, H, D), device=dev, dtype=dt)
             lse = torch.empty((B, H, Nq), device=dev, dtype=torch.float32)
             outs[key] = (o, lse)
-            k, v = (k8, v8) if fp8 else (kc, vc)
-            head = (code, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), lens.data_ptr(), None, B, H, Hkv, Nq, D, nmax, 0, 0, s3(q), s3(k),
-                    s3(v), s3(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0, D ** -0.5)
-            tail = (0, ws.data_ptr() if need else None, need, stream)
-            if fp8:
-                ds = _fa2_lib.strides2(d.stride(0), d.stride(1))
-                return lambda: _fa2_lib.check(lib.fa2_fwd_decode_fp8(*head, d.data_ptr(), d.data_ptr(), ds, *tail))
-            return lambda: _fa2_lib.check(lib.fa2_fwd_decode(*head, *tail))
+            k, v, dd = (k8, v8, d) if fp8 else (kc, vc, None)
+            entry = "fp8" if fp8 else "plain"
+            args = dc.c_args(entry, **dc.tensor_kw(q, k, v, o, lse, lens, kd=dd, vd=dd), ns=0, ws=ws.data_ptr() if need else None, wsb=need, stream=stream)
+            return lambda: _fa2_lib.check(getattr(lib, dc.ENTRIES[entry][0])(*args))
 
         for fp8 in (False, True):
             fns = {n: make(lib, fp8, (n, fp8)) for n, lib in libs.items()}

@@ -24,7 +24,6 @@ float64 mutants and that the drawn features are not idle, all on the CPU.  No ca
     python tools/fuzz_decode.py --mode decode --cases 1500 --seed 1 [--out FILE]
 """
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -34,9 +33,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
-for _p in (os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"), os.path.join(ROOT, "tests")):
+for _p in (os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
+import decode_abi as dc  # noqa: E402 - decode_c: the one copy of the C argument lists
 import decode_window_refs as wr  # noqa: E402 - truth64, emulate, bars_of, check: the one copy of the decode contract
 import kvappend_refs as kr  # noqa: E402 - append_rows: the one copy of the append contract
 from rocwmma_fattn import _fa2_lib  # noqa: E402
@@ -505,34 +505,6 @@ def _padded2(t, pad, dev):
     return wide.to(dev)[:, :t.shape[1]]
 
 
-def _code(dt):
-    return _fa2_lib.FA2_DTYPE_F16 if dt == F16 else _fa2_lib.FA2_DTYPE_BF16
-
-
-def _s3(t):
-    return _fa2_lib.strides3(t.stride(0), t.stride(2), t.stride(1))
-
-
-def _window_c(desc, q, k, v, lens, bt, kd, vd, sl, scale, need):
-    """fa2_fwd_decode_window as tests/test_decode_window_gpu.py calls it: NaN-filled outputs and workspace -> (rc, o, lse)"""
-    lib = _fa2_lib.load()
-    B, nq, H, D = q.shape
-    o = torch.full((B, nq, H, D), float("nan"), dtype=q.dtype, device=q.device)
-    lse = torch.full((B, H, nq), float("nan"), dtype=torch.float32, device=q.device)
-    ws = torch.full((max(need, 16) // 4,), float("nan"), dtype=torch.float32, device=q.device)
-    d0 = kd if kd is not None else vd
-    rc = lib.fa2_fwd_decode_window(
-        _code(q.dtype), _fa2_lib.FA2_CACHE_E4M3 if desc["fp8"] else _fa2_lib.FA2_CACHE_16BIT, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-        lse.data_ptr(), lens.data_ptr(), None if bt is None else bt.data_ptr(), B, H, desc["Hkv"], nq, D, desc["capacity"], desc["page"],
-        k.shape[0] if desc["page"] else 0, _s3(q), _s3(k), _s3(v), _s3(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)),
-        0 if bt is None else bt.stride(0), scale, None if kd is None else kd.data_ptr(), None if vd is None else vd.data_ptr(),
-        None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), desc["window_left"], desc["softcap"],
-        None if sl is None else sl.data_ptr(), 0 if sl is None or sl.dim() == 1 else sl.stride(0), desc["num_splits"], ws.data_ptr() if need else None, need,
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    return rc, o, lse
-
-
 def figures(o, lse2, refs):
     """(worst O error over its bar, worst LSE error) of outputs [B, Nq, H, D] / [B, H, Nq] against the float64 of refs; non-finite differences count as inf"""
     ratio = lerr = 0.0
@@ -559,10 +531,6 @@ def checked(o, lse2, refs, tag):
     return []
 
 
-def _same_bits(a, b):
-    return torch.equal(a[0].view(torch.int16), b[0].view(torch.int16)) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32))
-
-
 def _run_decode(desc):
     from rocwmma_fattn import FlashAttn
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -583,28 +551,31 @@ def _run_decode(desc):
         sl = sl.to(dev) if sl.dim() == 1 else _padded2(sl, desc["slopes_pad"], dev)
     # the plan and the workspace against their mirrors
     lib = _fa2_lib.load()
-    plan = _fa2_lib.decode_window_plan(_code(dt), B, Hkv * G, Hkv, nq, D, desc["capacity"], desc["page"], desc["num_splits"], wl)
+    plan = _fa2_lib.decode_window_plan(dc.code(dt), B, Hkv * G, Hkv, nq, D, desc["capacity"], desc["page"], desc["num_splits"], wl)
     want = plan_mirror(B, Hkv, nq, G, ck, wl, desc["num_splits"], device_cus())
     if (plan.row_tiles, plan.nsplit) != want or plan.key_tile != TILE:
         fails.append("plan (%d, %d) tile %d, mirror %s" % (plan.row_tiles, plan.nsplit, plan.key_tile, want))
-    need = lib.fa2_fwd_decode_window_workspace_bytes(_code(dt), B, Hkv * G, Hkv, nq, D, desc["capacity"], desc["page"], desc["num_splits"], wl)
+    need = lib.fa2_fwd_decode_window_workspace_bytes(dc.code(dt), B, Hkv * G, Hkv, nq, D, desc["capacity"], desc["page"], desc["num_splits"], wl)
     if need != workspace_mirror(B, Hkv, nq, G, D, plan.nsplit):
         fails.append("workspace %d bytes, the header's formula %d" % (need, workspace_mirror(B, Hkv, nq, G, D, plan.nsplit)))
-    args = (desc, q, k, v, lens, btd, kd, vd, sl, inp["scale"], need)
-    rc, o, lse = _window_c(*args)
+    def window_c():
+        """fa2_fwd_decode_window as tests/test_decode_window_gpu.py calls it: NaN-filled outputs and workspace -> (rc, o, lse)"""
+        return dc.decode_c("window", q, k, v, lens, desc["num_splits"], wl, desc["softcap"], sl, block_table=btd, kd=kd, vd=vd, scale=inp["scale"], check=False)
+
+    rc, o, lse = window_c()
     if rc != 0:
         return dict(desc, fails=fails + ["fa2_fwd_decode_window: %s" % _fa2_lib.error_string(rc)], o_ratio=float("inf"), lse_err=float("inf"))
     fails += checked(o, lse, refs, "case %d" % desc["i"])
     ratio, lerr = figures(o, lse, refs)
     if desc["twice"]:
-        rc2, o2, lse2 = _window_c(*args)
-        if rc2 != 0 or not _same_bits((o, lse), (o2, lse2)):
+        rc2, o2, lse2 = window_c()
+        if rc2 != 0 or not dc.same_bits((o, lse), (o2, lse2)):
             fails.append("a second run differs")
     if desc["operator"]:
         po, pl = FlashAttn.flash_attention_decode(q, k, v, lens, block_table=btd, scale=inp["scale"], return_lse=True, num_splits=desc["num_splits"],
                                                   k_descale=kd, v_descale=vd, window=None if wl < 0 else (wl, 0), softcap=desc["softcap"], alibi_slopes=sl)
         torch.cuda.synchronize()
-        if not _same_bits((o, lse * FlashAttn._LN2), (po, pl)):
+        if not dc.same_bits((o, lse * FlashAttn._LN2), (po, pl)):
             fails.append("flash_attention_decode differs from the C call")
     return dict(desc, fails=fails, o_ratio=ratio, lse_err=lerr, nsplit=plan.nsplit, row_tiles=plan.row_tiles)
 
@@ -933,7 +904,7 @@ def run_trace_with_graph(desc):
     out = _run_trace(desc, keep=eager)
     g = _run_trace(desc, graph=True, keep=replay)
     fails = out["fails"] + ["graph: " + f for f in g["fails"]]
-    if len(eager) != len(replay) or not all(_same_bits(a, b) for a, b in zip(eager, replay)):
+    if len(eager) != len(replay) or not all(dc.same_bits(a, b) for a, b in zip(eager, replay)):
         fails.append("the graph replay differs from the eager trace")
     return dict(out, fails=fails, graph=True, o_ratio=max(out["o_ratio"], g["o_ratio"]), lse_err=max(out["lse_err"], g["lse_err"]))
 

@@ -17,7 +17,6 @@ Chunk rows: a standalone append of B4 x 2 048 tokens (a prefill chunk), 16-bit a
 rows written once) and the time those bytes take at 6.3 TB/s."""
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
@@ -25,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
 
 import torch  # noqa: E402
 
+from benchlib import close, graphed, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
 from rocwmma_fattn.FlashAttn import flash_attention_decode, kvcache_append  # noqa: E402
 
@@ -38,41 +38,6 @@ STEP_ROWS = [  # (label, B, H, Hkv, Nq, keys, D, dtype, page, fp8)
     ("b8_nq4_8k", 8, 32, 8, 4, 8192, 128, torch.bfloat16, 0, False),
 ]
 CHUNK_ROWS = [("chunk_16bit", 4, 2048, 8, 128, torch.bfloat16, False), ("chunk_e4m3", 4, 2048, 8, 128, torch.bfloat16, True)]
-
-
-def interleaved(fns, rounds, iters):
-    """{name: (median, min, max) ms per call} of the callables in `fns`, timed round-robin (one event pair per (round, callable))."""
-    for f in fns.values():
-        for _ in range(3):
-            f()
-    torch.cuda.synchronize()
-    times = {n: [] for n in fns}
-    for _ in range(rounds):
-        for n, f in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                f()
-            e1.record()
-            torch.cuda.synchronize()
-            times[n].append(e0.elapsed_time(e1) / iters)
-    return {n: (statistics.median(t), min(t), max(t)) for n, t in times.items()}
-
-
-def graphed(fn):
-    """fn captured once (after a warm-up on a side stream) -> the replay"""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.current_stream().wait_stream(side)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-            keep = fn()
-    torch.cuda.current_stream().wait_stream(side)
-    graph.keep = keep
-    return graph.replay
 
 
 def rotate(x, cos, sin):
@@ -108,18 +73,6 @@ def torch_append(q, k, v, kc, vc, lens, bt, cos, sin, kd, vd):
     return q_rot
 
 
-def paged_pool(kc, vc, page, g):
-    """the [B, Nmax, Hkv, D] caches scattered into pages in shuffled physical order"""
-    B, nmax = kc.shape[:2]
-    per = nmax // page
-    order = torch.randperm(B * per + 4, generator=g)[:B * per].reshape(B, per)
-    pk = torch.zeros((B * per + 4, page) + tuple(kc.shape[2:]), device=kc.device, dtype=kc.dtype)
-    pv = torch.zeros_like(pk)
-    pk[order.reshape(-1).to(kc.device)] = kc.reshape(B * per, page, *kc.shape[2:])
-    pv[order.reshape(-1).to(kc.device)] = vc.reshape(B * per, page, *vc.shape[2:])
-    return pk, pv, order.to(torch.int32).to(kc.device)
-
-
 def line(name, t, base=None):
     med, lo, hi = t[name]
     rel = ""
@@ -129,13 +82,6 @@ def line(name, t, base=None):
         rel = "  %.2fx %s than %s (%s the sum of the spreads, %.1f us)" % (max(b_med / med, med / b_med), "faster" if med <= b_med else "SLOWER", base,
                                                                           "beyond" if real else "WITHIN", ((hi - lo) + (b_hi - b_lo)) * 1e3)
     return "    %-10s %9.1f us  (rounds %.1f .. %.1f, spread %.1f %%)%s" % (name, med * 1e3, lo * 1e3, hi * 1e3, 100.0 * (hi - lo) / med, rel)
-
-
-def close(a, b, dt, what):
-    atol, rtol = (1e-3, 2e-3) if dt == torch.float16 else (8e-3, 1.6e-2)
-    a, b = a.float(), b.float()
-    if ((a - b).abs() > atol + rtol * b.abs()).any() or not torch.isfinite(a).all():
-        raise SystemExit("kvappend_bench: %s disagree (max |diff| %.3g)" % (what, float((a - b).abs().max())))
 
 
 def step_row(label, B, H, Hkv, Nq, keys, D, dt, page, fp8, rounds, iters):
@@ -171,13 +117,13 @@ def step_row(label, B, H, Hkv, Nq, keys, D, dt, page, fp8, rounds, iters):
         return flash_attention_decode(q, kc, vc, lens, **dec)
 
     with torch.no_grad():
-        close(fused(), torch_route(), dt, label + ": fused and torch outputs")
+        close("kvappend_bench", fused(), torch_route(), dt, label + ": fused and torch outputs")
         a, b = kc.float(), kc2.float()
         if fp8:                                                          # at most one e4m3 step apart where the two f32 rotations round differently
             if bool(((a - b).abs() > 0.126 * b.abs() + 2.0 ** -9).any()):
                 raise SystemExit("kvappend_bench: %s: the K caches of the two routes differ by more than one e4m3 step" % label)
         else:
-            close(a, b, dt, label + ": the K caches")
+            close("kvappend_bench", a, b, dt, label + ": the K caches")
         if not torch.equal(vc.view(torch.uint8), vc2.view(torch.uint8)):
             raise SystemExit("kvappend_bench: %s: the V caches of the two routes differ" % label)
         fns = {"fused": fused, "torch": torch_route, "append": append, "decode": decode}
