@@ -8,9 +8,11 @@
 // and the band's masks come LAST (tanh(-inf) = -1: capping a masked score would un-mask it).  The softmax, the LSE and P are those of s.
 // Backward: dX = dS * (1 - tanh^2(x / softcap)) — smod_score returns that factor beside s; the ALiBi term is a constant of the call.
 //
-// tanh.  t = 1 - 2 / (1 + 2^(2 log2(e) y)): the exponential overflows to +inf or underflows to 0 for |y| beyond ~44, where the quotient is exactly 0 or 2
-// and t exactly +1 or -1 — finite for every finite y (the textbook (e - 1) / (e + 1) gives inf / inf there), and 1 - t^2 is exactly 0 in saturation.
-// The price is cancellation near 0: the absolute error of t is a few 2^-24 everywhere (not relative to t), i.e. a few ulps of `softcap` in s.
+// tanh.  |y| >= 1/8: t = 1 - 2 / (1 + 2^(2 log2(e) y)): the exponential overflows to +inf or underflows to 0 for |y| beyond ~44, where the quotient is
+// exactly 0 or 2 and t exactly +1 or -1 — finite for every finite y (the textbook (e - 1) / (e + 1) gives inf / inf there), and 1 - t^2 is exactly 0 in
+// saturation.  That form cancels near 0: its error in t is a few 2^-24 ABSOLUTE, i.e. a few ulps of `softcap` in s whatever x is — at softcap = 1e4 that
+// was 1e-3 in every score and in the LSE (found by tools/fuzz_lse.py).  So |y| < 1/8 takes the odd series y (1 - y^2/3 + 2 y^4/15 - 17 y^6/315), whose
+// truncation (62 y^9 / 2835) is below 1.4e-9 relative there: the error of t is a few ulps of t itself, and s -> x as softcap grows.
 // The division x / softcap is a multiplication by 1 / softcap, rounded on the host once per call.
 // The distance |pos - j| enters as a float: exact below 2^24, rounded to nearest above.
 // Slopes of either sign are served: nothing in the passes relies on s <= x (the dK / dV passes mask the rows >= Nq of a ragged last Q tile themselves).
@@ -72,10 +74,13 @@ FA2_SMOD_HD inline float smod_rcp(float x) {
     return 1.0f / x;
 #endif
 }
-// tanh(y), exactly +-1 in saturation, finite for every finite y
+// tanh(y), exactly +-1 in saturation, finite for every finite y, a few ulps of the result near 0 (both forms computed, one selected: no branch)
 FA2_SMOD_HD inline float smod_tanh(float y) {
     const float e = smod_exp2(y * 2.8853900817779268f);               // 2^(2 log2(e) y) = e^(2 y): +inf / 0 far out
-    return __builtin_fmaf(-2.0f, smod_rcp(1.0f + e), 1.0f);
+    const float far = __builtin_fmaf(-2.0f, smod_rcp(1.0f + e), 1.0f);
+    const float y2 = y * y;
+    const float near = y * __builtin_fmaf(y2, __builtin_fmaf(y2, __builtin_fmaf(y2, -0.053968254f, 0.13333334f), -0.33333334f), 1.0f);
+    return __builtin_fabsf(y) < 0.125f ? near : far;
 }
 // softcap * tanh(x / softcap) (the caller knows softcap > 0)
 FA2_SMOD_HD inline float smod_cap(float x, float softcap, float inv_softcap, float* t) {

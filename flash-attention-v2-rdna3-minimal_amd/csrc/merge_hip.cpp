@@ -57,13 +57,15 @@ template <bool BF16>
 __global__ __launch_bounds__(kMergeThreads) void merge_fwd_kernel(const MergeParams p) {
     const MergeLane l = merge_lane(p);
     if (!l.active) return;
+    // (the LSEs stay in their own unit until a DIFFERENCE is formed: lse_k - m is exact or nearly so, lse_k * log2(e) - m * log2(e) carries two roundings at
+    //  the LSEs' magnitude — with one part the merged LSE must be that part's, bit for bit, and the backward's weight exactly 1)
     const float in_unit = p.natural ? kLog2e : 1.0f, out_unit = p.natural ? kLn2 : 1.0f;
     const int64_t lo = l.b * p.pls[0] + l.h * p.pls[1] + l.n, po = l.b * p.ps[0] + l.h * p.ps[1] + l.n * p.ps[2] + l.col;
     float ls[kMergeMaxParts];
     float m = -__builtin_inff();
 #pragma unroll
     for (int k = 0; k < kMergeMaxParts; ++k) {
-        ls[k] = k < p.nparts ? p.lse_parts[k][lo] * in_unit : -__builtin_inff();
+        ls[k] = k < p.nparts ? p.lse_parts[k][lo] : -__builtin_inff();
         m = __builtin_fmaxf(m, ls[k]);
     }
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_fwd_kernel(const MergePar
     if (m != -__builtin_inff()) {
 #pragma unroll
         for (int k = 0; k < kMergeMaxParts; ++k) {
-            const float w = __builtin_amdgcn_exp2f(ls[k] - m);
+            const float w = __builtin_amdgcn_exp2f((ls[k] - m) * in_unit);
             if (k < p.nparts && w != 0.f) {
                 float x[8];
                 unpack8<BF16>(*(const u32x4*)((const uint16_t*)p.o_parts[k] + po), x);
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_fwd_kernel(const MergePar
         for (int e = 0; e < 8; ++e) acc[e] *= inv;
     }
     *(u32x4*)((uint16_t*)p.o + l.b * p.os[0] + l.h * p.os[1] + l.n * p.os[2] + l.col) = pack8<BF16>(acc);
-    if (l.first) p.lse[l.b * p.ls[0] + l.h * p.ls[1] + l.n] = m != -__builtin_inff() ? (m + __builtin_amdgcn_logf(sum)) * out_unit : m;
+    if (l.first) p.lse[l.b * p.ls[0] + l.h * p.ls[1] + l.n] = m != -__builtin_inff() ? __builtin_fmaf(__builtin_amdgcn_logf(sum), out_unit, m) : m;
 }
 
 // dO_k = w_k dO;  dlse_k = w_k (dlse + dO.(O_k - O)) with dO.O = sum_k w_k (dO.O_k) — in the LSEs' own unit: the dot term carries ln 2 when they are log2
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_bwd_kernel(const MergePar
     const float in_unit = p.natural ? kLog2e : 1.0f, dot_unit = p.natural ? 1.0f : kLn2;
     const int64_t lo = l.b * p.pls[0] + l.h * p.pls[1] + l.n, po = l.b * p.ps[0] + l.h * p.ps[1] + l.n * p.ps[2] + l.col;
     const int64_t dlo = l.b * p.dpls[0] + l.h * p.dpls[1] + l.n, dpo = l.b * p.dps[0] + l.h * p.dps[1] + l.n * p.dps[2] + l.col;
-    const float lse = l.first || l.active ? p.lse[l.b * p.ls[0] + l.h * p.ls[1] + l.n] * in_unit : -__builtin_inff();
+    const float lse = l.first || l.active ? p.lse[l.b * p.ls[0] + l.h * p.ls[1] + l.n] : -__builtin_inff();      // (its own unit: merge_fwd_kernel)
     const bool live = lse != -__builtin_inff();
     float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (l.active) unpack8<BF16>(*(const u32x4*)((const uint16_t*)p.dout + l.b * p.dos[0] + l.h * p.dos[1] + l.n * p.dos[2] + l.col), g);
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_bwd_kernel(const MergePar
         w[k] = 0.f;
         d[k] = 0.f;
         if (k < p.nparts) {
-            if (live && (l.active || l.first)) w[k] = __builtin_amdgcn_exp2f(p.lse_parts[k][lo] * in_unit - lse);
+            if (live && (l.active || l.first)) w[k] = __builtin_amdgcn_exp2f((p.lse_parts[k][lo] - lse) * in_unit);
             if (l.active) {
                 float y[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 if (w[k] != 0.f) {

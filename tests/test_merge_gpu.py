@@ -165,6 +165,27 @@ def test_merge_kernels_match_the_float64_contract(nparts, D, nq, layout, dt, nat
     R.merge_check(tag, dt, natural, [vo(o) for o in outs], [vl(l) for l in lses], vo(dout), vl(dlse), vo(out), vl(lse), [vo(t) for t in dos], [vl(t) for t in dls])
 
 
+@pytest.mark.parametrize("natural", [True, False], ids=["natural", "log2"])
+@pytest.mark.parametrize("dt", DTYPES, ids=["f16", "bf16"])
+def test_one_part_with_large_lses_is_the_identity(dt, natural):
+    """One part whose LSEs sit near -200: the merged LSE is the part's bit for bit and the backward's weight exactly 1, so dO_0 = dO and dlse_0 = dlse.
+    The reduced form of what tools/fuzz_lse.py's merge runs flagged (seed 203, six one-part cases, D 216 .. 384): the kernels converted every LSE to
+    log2 units BEFORE subtracting, two roundings at the LSEs' magnitude, so the weight came out as 1 +- 4e-5 and dlse_0 carried (dO.O_0) times that —
+    4e-4 against a bar of 1e-4.  They now subtract in the LSEs' own unit and scale the difference."""
+    dev = _dev()
+    outs, lses = _merge_case(dt, 1, 272, 129, "bhnd", natural, dev, seed=4)
+    lses = [l - 200.0 for l in lses]
+    g = torch.Generator().manual_seed(901)
+    dout = torch.randn(outs[0].shape, generator=g).to(dt).to(dev)
+    dlse = torch.randn(lses[0].shape, generator=g).to(dev)
+    out, lse, dos, dls = _raw_merge(outs, lses, "bhnd", natural, dout, dlse)
+    live = ~torch.isneginf(lses[0])
+    assert live.any() and not live.all()
+    assert torch.equal(lse, lses[0]) and torch.equal(out[live], outs[0][live])
+    assert torch.equal(dos[0][live], dout[live]) and torch.equal(dls[0][live], dlse[live]) and (dls[0][~live] == 0).all()
+    R.merge_check("one part %s %s" % (str(dt)[6:], "natural" if natural else "log2"), dt, natural, outs, lses, dout, dlse, out, lse, dos, dls)
+
+
 @pytest.mark.parametrize("dt", DTYPES, ids=["f16", "bf16"])
 def test_seventeen_parts_fold_in_groups(dt):
     dev = _dev()

@@ -49,6 +49,24 @@ def test_softcap_against_float64(softcap):
     assert worst <= 6.0
 
 
+@pytest.mark.parametrize("softcap", [0.5, 30.0, 1e4, 1e6])
+def test_softcap_is_relative_near_zero(softcap):
+    """Below |x / softcap| = 1/8 the tanh is the odd series: |s - s64| is a few ulps of s ITSELF, not of softcap, so that a large softcap leaves the
+    scores alone (the 1 - 2 / (1 + e^2y) form alone was 1e-3 off in every score at softcap = 1e4: tools/fuzz_lse.py's first runs).  Bound: 0.5 ulp for
+    x * (1 / softcap) twice (the reciprocal, the product), 1.5 for the series' Horner steps and truncation (62 y^8 / 2835 <= 1.4e-9), 0.5 each for
+    y * poly and softcap * t: 4 ulps of s.  The derivative factor stays within 8 * 2^-24 of 1 - tanh^2."""
+    cap32 = float(np.float32(softcap))
+    worst = 0.0
+    for y in np.concatenate([np.logspace(-8, math.log10(0.1249), 2001), -np.logspace(-8, math.log10(0.1249), 2001)]):
+        x = float(np.float32(y * cap32))
+        s, f = evaluate(x, cap32)
+        t64 = math.tanh(x / cap32)
+        worst = max(worst, abs(s - cap32 * t64) / ulp_of(cap32 * t64))
+        assert abs(f - (1.0 - t64 * t64)) <= 8 * 2.0 ** -24, (x, f)
+    print("softcap %g: max |s - s64| = %.2f ulps of s below |y| = 1/8 (bound 4)" % (softcap, worst))
+    assert worst <= 4.0
+
+
 def test_softcap_is_safe_at_the_ends_of_float32():
     for x in (3.0e38, -3.0e38, 1e30, -1e30, 0.0, 1e-45, -1e-45):
         for cap in (1e-3, 1.0, 50.0):

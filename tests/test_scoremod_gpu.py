@@ -207,6 +207,15 @@ def test_softcap_alone(D, dt, softcap):
 
 
 @pytest.mark.parametrize("dt", [F16, BF16])
+@pytest.mark.parametrize("nkv", [1, NKV])
+def test_a_large_softcap_leaves_the_scores_alone(nkv, dt):
+    """softcap = 1e4 over scores of a few units: s = x to 1e-7 relative, so every output — the LSE within LSE_TOL — is that of the uncapped call.  The
+    reduced form of what tools/fuzz_lse.py's first runs flagged: the tanh of csrc/fa2_scoremod.h was 1 - 2 / (1 + e^2y) everywhere, a few 2^-24 off in
+    ABSOLUTE terms, which softcap = 1e4 turned into 1e-3 in every score (LSE errors of 1.0e-3 .. 1.6e-3 log2 units; with one key the LSE is that score)."""
+    run_dense(dt, 2, 64, softcap=1e4, inputs=make_inputs(dt, 2, 64, nq=64, nkv=nkv, seed=11), vacuous_ok=True)
+
+
+@pytest.mark.parametrize("dt", [F16, BF16])
 @pytest.mark.parametrize("D", DIMS)
 def test_alibi_alone_keys_on_both_sides(D, dt):
     run_dense(dt, 2 if dt == F16 else 4, D, slopes=alibi_slopes(H))
