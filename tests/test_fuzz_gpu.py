@@ -50,6 +50,9 @@ def test_randomised_parity_sweep_slice():
         n_tail += kernel_tail != 0
         n_padded_wide += d["i"] >= 1000 and "rowpad" in d["layouts"]
     assert not bad, bad[:3]
+    # every case was held to the per-element bars of tests/key_probes.py as well (class C: 2 u sum P|v| for O, 2 u sum P|dO| for dV, where tighter)
+    assert all("o_ratio" in d for d in plan_of) and all("dv_ratio" in d for d in plan_of if d["bwd"])
+    print("worst err / per-element bar: O %.3f, dV %.3f" % (max(d["o_ratio"] for d in plan_of), max(d["dv_ratio"] for d in plan_of if d["bwd"])))
     # the slice must reach what it is here for: the hand-scheduled kernels, the split, a padded row pitch on a wide grid
     assert n_asm >= 5 and n_split >= 1 and n_padded_wide >= 1, (n_asm, n_split, n_padded_wide, n_tail)
 

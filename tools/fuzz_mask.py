@@ -1,7 +1,8 @@
 """Randomised parity sweep of the attention bias / mask path on the GPU (developer tool): flash_attention(q, k, v, mask, causal, scale) — C-ABI
 fa2_fwd_bias / fa2_bwd_bias — against dense float64 attention with the same mask on the device.  Draws shapes, head dims (8..256: the masked
 backward stops there), dtypes, the mask kind (bool keep-mask, additive in the I/O dtype, additive f32), every broadcast pattern over [B, H, Nq, Nkv],
-aligned and unaligned Nkv (the three load forms of the kernels), fully masked rows, causal on top.  Bounds: the test-suite's.
+aligned and unaligned Nkv (the three load forms of the kernels), fully masked rows, causal on top.  Bounds: the test-suite's, and element by element
+the class-C bars of tests/key_probes.py (tools/key_bars.py: 2 u sum_j P_ij |v_jc| for O, 2 u sum_i P_ij |dO_ic| for dV) wherever they are tighter.
     python tools/fuzz_mask.py --cases 300 --seed 1 [--bwd-every 2]"""
 import argparse
 import json
@@ -13,6 +14,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
+if os.path.join(ROOT, "tools") not in sys.path:
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+import key_bars as kp  # noqa: E402 - the per-element bars of O and dV (class C of tests/key_probes.py, which re-exports them)
 from rocwmma_fattn.FlashAttn import flash_attention  # noqa: E402
 
 FLOOR = {torch.float16: 1e-3, torch.bfloat16: 8e-3}
@@ -69,6 +73,7 @@ def one_case(i, rng, gen, want_bwd):
     desc = dict(i=i, B=B, H=H, Nq=Nq, Nkv=Nkv, D=D, dtype=str(dtype)[6:], causal=causal, kind=kind, mask_shape=shape, bwd=want_bwd)
     fails = []
     o_true = dense64(q, k, v, mask, causal, scale)
+    go = None
     if want_bwd:
         qg, kg, vg = (t.clone().requires_grad_(True) for t in (q, k, v))
         o = flash_attention(qg, kg, vg, mask, causal, scale)
@@ -88,14 +93,25 @@ def one_case(i, rng, gen, want_bwd):
     else:
         o = flash_attention(q, k, v, mask, causal, scale)
     torch.cuda.synchronize()
+    ref = kp.dense64(q, k, v, scale, causal=causal, do=go, dv_only=True, **({"keep": mask} if mask.dtype == torch.bool else {"bias": mask}))
     if not torch.isfinite(o.float()).all():
         fails.append("O non-finite")
     else:
-        err = (o.double() - o_true).abs().max().item()
+        diff = (o.double() - o_true).abs()
+        err = diff.max().item()
         lim = 2 * FLOOR[dtype] * max(1.0, v.float().abs().max().item())
+        bar = kp.o_bar(ref, dtype).clamp(max=lim)                             # min(the per-tensor bar, the class-C bar), element by element
         if err > lim:
             fails.append("O err %.3e > %.3e" % (err, lim))
+        elif bool((diff > bar).any()):
+            fails.append("O: %d elements outside 2 u sum P|v|, worst %.2f bars (err %.3e)" % (int((diff > bar).sum()), kp.ratio_max(diff, bar), diff[diff > bar].max().item()))
         desc["o_err"] = err
+        desc["o_ratio"] = kp.ratio_max(diff, bar)
+    if want_bwd and torch.isfinite(vg.grad.float()).all():
+        diff = (vg.grad.double() - ref["dv"]).abs()
+        bar = kp.dv_bar(ref, dtype).clamp(max=2 * GRAD_TOL[dtype] * max(1.0, ref["dv"].abs().max().item()))
+        if bool((diff > bar).any()):
+            fails.append("dv: %d elements outside 2 u sum P|dO|, worst %.2f bars (err %.3e)" % (int((diff > bar).sum()), kp.ratio_max(diff, bar), diff[diff > bar].max().item()))
     desc["fails"] = fails
     return desc
 
@@ -109,7 +125,7 @@ def main():
     a = ap.parse_args()
     rng = random.Random(a.seed)
     gen = torch.Generator(device="cuda").manual_seed(a.seed)
-    bad, worst, n_bwd = [], 0.0, 0
+    bad, worst, n_bwd, worst_ratio = [], 0.0, 0, 0.0
     for i in range(a.cases):
         want_bwd = a.bwd_every > 0 and i % a.bwd_every == 0
         try:
@@ -118,10 +134,11 @@ def main():
             d = dict(i=i, fails=["exception: %r" % (e,)])
         n_bwd += int(want_bwd)
         worst = max(worst, d.get("o_err", 0.0))
+        worst_ratio = max(worst_ratio, d.get("o_ratio", 0.0))
         if d["fails"]:
             bad.append(d)
             print("FAIL", json.dumps(d), flush=True)
-    line = json.dumps(dict(cases=a.cases, backward_cases=n_bwd, seed=a.seed, failures=len(bad), worst_o_err=worst, device=torch.cuda.get_device_name(0), failing=bad))
+    line = json.dumps(dict(cases=a.cases, backward_cases=n_bwd, seed=a.seed, failures=len(bad), worst_o_err=worst, worst_o_ratio=worst_ratio, device=torch.cuda.get_device_name(0), failing=bad))
     print(line)
     if a.out:
         open(a.out, "w").write(line + "\n")

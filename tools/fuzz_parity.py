@@ -3,7 +3,9 @@
 Draws shapes, head dims, dtypes, layouts (BHND / BNHD views, padded row strides, head slices of a larger tensor), scales
 and the causal flag at random, runs the operator (forward and backward) and compares with dense float64
 attention computed by torch on the same device.  Bounds are the test suite's (tests/conftest.py): FLOOR for O, 1e-3 for the
-log2 LSE (scaled by the logit magnitude for large |scale|), GRAD_TOL * max(1, max|g|) for gradients.  Also checks, case by
+log2 LSE (scaled by the logit magnitude for large |scale|), GRAD_TOL * max(1, max|g|) for gradients — and, element by element, the class-C bars of
+tests/key_probes.py (tools/key_bars.py) wherever they are tighter: 2 u sum_j P_ij |v_jc| for O, 2 u sum_i P_ij |dO_ic| for dV (on a sweep of thousands of keys the
+per-tensor bars accept a dropped 64 x 64 tile: tests/test_key_probes.py).  Also checks, case by
 case, that memory around the outputs is untouched (canaries) and that a second run is bit-identical.
 
     python tools/fuzz_parity.py --cases 400 --seed 1 [--bwd-every 2]
@@ -19,6 +21,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
+if os.path.join(ROOT, "tools") not in sys.path:
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+import key_bars as kp  # noqa: E402 - the per-element bars of O and dV (class C of tests/key_probes.py, which re-exports them)
 from rocwmma_fattn import _fa2_lib  # noqa: E402
 from rocwmma_fattn.FlashAttn import FlashAttentionFunction, flash_attn_wmma  # noqa: E402
 
@@ -53,6 +58,17 @@ def folded_heads(plan, B, H, device):
     if pre_tail:
         folded[plan.heads_main:] = True
     return folded.view(B, H)
+
+
+def worst_row(diff, bar, q, k, causal, scale):
+    """Which row decides a case's o_ratio: the (b, h, row, column) of the largest diff / bar, the number of keys the row may see, its two largest P (float64)
+    and the bar's share that is relative (u sum P|v|, against the per-tensor cap): a row that one key dominates is the derivation's own worst case."""
+    r = torch.where(bar > 0, diff / bar, torch.zeros_like(diff))
+    b, h, i, c = (int(x) for x in torch.unravel_index(r.argmax(), r.shape))
+    s = (k[b, h].double() @ q[b, h, i].double()) * scale
+    n = min(i + 1, s.numel()) if causal else s.numel()
+    top = torch.softmax(s[:n], 0).topk(min(2, n)).values.tolist()
+    return dict(at=[b, h, i, c], keys=n, top_p=[round(x, 4) for x in top], ratio=round(float(r[b, h, i, c]), 4))
 
 
 def prescaled_q(q, scale, dtype):
@@ -185,6 +201,7 @@ def one_case(i, rng, gen, want_bwd, force=None):
         o_true = torch.where(folded[:, :, None, None], o_alt, o_true)
         lse_true = torch.where(folded[:, :, None], lse_alt, lse_true)
     fails = []
+    go = None
 
     if want_bwd:
         qg, kg, vg = (t.detach().clone().requires_grad_(True) for t in (q, k, v))   # clone keeps the strides of dense views only
@@ -213,14 +230,31 @@ def one_case(i, rng, gen, want_bwd, force=None):
         if not torch.equal(o, ret[0]):
             fails.append("operator and extension forward differ bit-wise")
     torch.cuda.synchronize()
+    # the per-element bars: float64 again with the sums of absolute terms (the differentiated call's O is the exact-scale one)
+    ref = kp.dense64(q, k, v, scale, causal=causal, do=go, dv_only=True)
+    if folded is not None and not want_bwd:
+        alt = kp.dense64(qs, k, v, s_alt, causal=causal)
+        ref = {n: torch.where(folded[:, :, None, None], alt[n], ref[n]) for n in ("o_abs", "o_sub")}
     if not torch.isfinite(o.float()).all():
         fails.append("O non-finite")
     else:
-        err = (o.double() - o_true).abs().max().item()
+        diff = (o.double() - o_true).abs()
+        err = diff.max().item()
         vmax = max(1.0, v.float().abs().max().item())
+        bar = kp.o_bar(ref, dtype).clamp(max=2 * FLOOR[dtype] * vmax)            # min(the per-tensor bar, the class-C bar), element by element
         if err > 2 * FLOOR[dtype] * vmax:
             fails.append("O err %.3e > %.3e" % (err, 2 * FLOOR[dtype] * vmax))
+        elif bool((diff > bar).any()):
+            fails.append("O: %d elements outside 2 u sum P|v|, worst %.2f bars (err %.3e)" % (int((diff > bar).sum()), kp.ratio_max(diff, bar), diff[diff > bar].max().item()))
         desc["o_err"] = err
+        desc["o_ratio"] = kp.ratio_max(diff, bar)
+        desc["o_worst"] = worst_row(diff, bar, q, k, causal, scale)
+    if want_bwd and torch.isfinite(vg.grad.float()).all():
+        diff = (vg.grad.double() - ref["dv"]).abs()
+        bar = kp.dv_bar(ref, dtype).clamp(max=2 * GRAD_TOL[dtype] * max(1.0, ref["dv"].abs().max().item()))
+        if bool((diff > bar).any()):
+            fails.append("dv: %d elements outside 2 u sum P|dO|, worst %.2f bars (err %.3e)" % (int((diff > bar).sum()), kp.ratio_max(diff, bar), diff[diff > bar].max().item()))
+        desc["dv_ratio"] = kp.ratio_max(diff, bar)
     if lse is not None:
         lim = lse_limit(plan, q, k, D, scale, dtype)
         lerr = (lse.double() - lse_true).abs().max().item()
@@ -241,7 +275,7 @@ def main():
     args = ap.parse_args()
     rng = random.Random(args.seed)
     gen = torch.Generator(device="cuda").manual_seed(args.seed)
-    bad, worst_o, worst_l, n_bwd = [], 0.0, 0.0, 0
+    bad, worst_o, worst_l, n_bwd, worst_or, worst_vr, worst_case = [], 0.0, 0.0, 0, 0.0, 0.0, None
     for i in range(args.cases):
         want_bwd = args.bwd_every > 0 and i % args.bwd_every == 0
         try:
@@ -251,11 +285,14 @@ def main():
         n_bwd += int(want_bwd)
         worst_o = max(worst_o, d.get("o_err", 0.0))
         worst_l = max(worst_l, d.get("lse_err", 0.0))
+        if d.get("o_ratio", 0.0) > worst_or:
+            worst_case = {n: d[n] for n in ("i", "Nq", "Nkv", "D", "dtype", "causal", "scale", "dist", "amp", "plan", "o_worst")}
+        worst_or, worst_vr = max(worst_or, d.get("o_ratio", 0.0)), max(worst_vr, d.get("dv_ratio", 0.0))       # (as shares of the per-element bars)
         if d["fails"]:
             bad.append(d)
             print("FAIL", json.dumps(d), flush=True)
     summary = dict(cases=args.cases, backward_cases=n_bwd, seed=args.seed, failures=len(bad), worst_o_err=worst_o,
-                   worst_lse_err=worst_l, device=torch.cuda.get_device_name(0), failing=bad)
+                   worst_lse_err=worst_l, worst_o_ratio=worst_or, worst_dv_ratio=worst_vr, worst_o_case=worst_case, device=torch.cuda.get_device_name(0), failing=bad)
     line = json.dumps(summary)
     print(line)
     if args.out:
