@@ -1208,6 +1208,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_dkv_kernel(const BwdParam
 
 // Mid-tile barrier of the pair pass: only the LDS hand-over of P has to be complete — unlike __syncthreads() it does not wait for the
 // next tile's staging loads in flight (vmcnt), which have the whole tile to land (the end-of-tile __syncthreads() drains them).
+template <bool BF16> constexpr float kPairSlotGain = BF16 ? 1.0f : 16384.0f;      // what P is multiplied by on its way through the pair's slot
+
 __device__ __forceinline__ void pair_mid_barrier() {
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1219,9 +1221,13 @@ __device__ __forceinline__ void pair_mid_barrier() {
 // A workgroup owns 128 KV rows; waves g and g + 4 (same SIMD) share the 32 KV rows of group g:
 //   wave g     ("P side")   S = Q K^T (K rows as B fragments), P = 2^(S c - L), dV^T += dO^T P
 //   wave g + 4 ("dS side")  dP = dO V^T (V rows as B fragments), dS = P (dP - D), dK^T += Q^T dS
-// P crosses from the first to the second wave once per tile through a 4-KiB LDS slot per pair, as the very 16-bit B
-// fragments the dV product consumes (same lane, same registers: S^T and dP^T have the same layout) — so S and P are formed once
+// P crosses from the first to the second wave once per tile through a 4-KiB LDS slot per pair, as 16-bit B fragments in the layout
+// the dV product consumes (same lane, same registers: S^T and dP^T have the same layout) — so S and P are formed once
 // for both products: 4 GEMMs per (kv, q) pair instead of the 5 of the two separate passes, 7 instead of 8 for the whole backward.
+// bf16 sends the dV fragments themselves.  fp16 sends round16(2^14 P) and the dS side takes the 2^14 out again in f32: a power of two
+// leaves a normal P bit-equal to round16(P), while a P below 2^-14 — an fp16 subnormal, zero below 2^-25 — keeps its 11 bits down to
+// 2^-28 and is quantised to 2^-39 below that.  dS = P (dP - D) of such a pair is then as the separate passes form it (f32 P, dS rounded
+// once), instead of missing the pair.  (P <= 1 up to rounding, 1 on rows past Nq: 2^14 P stays far below fp16's 65504.)
 // Each tile has two phases separated by a barrier: {S, exp | dP} and {dV | dS, dK}; the transcendental / VALU stretch of one wave
 // of a pair runs beside the MFMAs of the other.  Stage: Q row | dO row | Q tr | dO tr | L | D, two stages (129 KiB) + 16 KiB of slots.
 template <int HD, bool BF16, bool CAUSAL, int KSN = HD / 16, int DTN = HD / 32>
@@ -1352,8 +1358,9 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
         for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
     const float c = p.c;
 #if FA2_SMOD
-    // FA2_SMOD: only the P side holds S, so the factor travels with P — the pair's slot carries round16(P (1 - t^2)) while the P side keeps the plain
-    // round16(P) for its dV product; the dS side multiplies what it reads by (dP - D) as ever, which makes it dX / scale.  (kv_group = 1: h is the query head)
+    // FA2_SMOD: only the P side holds S, so the factor travels with P — the pair's slot carries round16(gain P (1 - t^2)), gain = kPairSlotGain, while
+    // the P side keeps the plain round16(P) for its dV product; the dS side multiplies what it reads by (dP - D) as ever, which makes it dX / scale.
+    // (kv_group = 1: h is the query head)
     (void)c;
     const float smod_slope = smod.slopes ? smod.slopes[(int64_t)b * smod.stride + h * G] : 0.f;
 #endif
@@ -1433,8 +1440,8 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                         const float v1 = smod_score(s1[r] * scale, smod.softcap, smod.inv_softcap, smod_slope, __builtin_fabsf(dpos + (float)(qo + 32)), &f1);
                         s0[r] = (qo < lo_rel || qo > hi_rel) ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(v0, kSmodLog2e, -L0[e]));
                         s1[r] = (qo + 32 < lo_rel || qo + 32 > hi_rel) ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(v1, kSmodLog2e, -L1[e]));
-                        pf0[e] = s0[r] * f0;
-                        pf1[e] = s1[r] * f1;
+                        pf0[e] = s0[r] * (f0 * kPairSlotGain<BF16>);
+                        pf1[e] = s1[r] * (f1 * kPairSlotGain<BF16>);
                     }
                     xg[g4 >> 1][2 * (g4 & 1)] = pack2<BF16>(pf0[0], pf0[1]);
                     xg[g4 >> 1][2 * (g4 & 1) + 1] = pack2<BF16>(pf0[2], pf0[3]);
@@ -1483,11 +1490,26 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                 xf[2][i] = pack2<BF16>(s1[2 * i], s1[2 * i + 1]);
                 xf[3][i] = pack2<BF16>(s1[8 + 2 * i], s1[8 + 2 * i + 1]);
             }
-#pragma unroll
 #if FA2_SMOD
+#pragma unroll
             for (int i = 0; i < 4; ++i) *(lds_u32x4_ptr)(xch + 1024 * i) = xg[i];
 #else
-            for (int i = 0; i < 4; ++i) *(lds_u32x4_ptr)(xch + 1024 * i) = xf[i];
+            if constexpr (BF16) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) *(lds_u32x4_ptr)(xch + 1024 * i) = xf[i];
+            } else {                                                  // fp16: the slot's P carries kPairSlotGain (masked entries are 0 either way)
+                constexpr float gain = kPairSlotGain<BF16>;
+                u32x4 xg[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    xg[0][i] = pack2<BF16>(s0[2 * i] * gain, s0[2 * i + 1] * gain);
+                    xg[1][i] = pack2<BF16>(s0[8 + 2 * i] * gain, s0[8 + 2 * i + 1] * gain);
+                    xg[2][i] = pack2<BF16>(s1[2 * i] * gain, s1[2 * i + 1] * gain);
+                    xg[3][i] = pack2<BF16>(s1[8 + 2 * i] * gain, s1[8 + 2 * i + 1] * gain);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) *(lds_u32x4_ptr)(xch + 1024 * i) = xg[i];
+            }
 #endif
             pair_mid_barrier();                                       // P is in the pair's slot
 #if FA2_DROP
@@ -1532,7 +1554,7 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
             u32x4 xf[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) xf[i] = *(lds_u32x4_ptr)(xch + 1024 * i);
-            float pv[32];                                              // P as the dV product sees it (16-bit), in register order
+            float pv[32];                                              // P as the slot carried it (16-bit, gain taken out), in register order
             if constexpr (BF16) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -1546,7 +1568,7 @@ __global__ __launch_bounds__(512, 2) void bwd_dkv_pair_kernel(const BwdParams FA
                 for (int j = 0; j < 4; ++j) {
                     const f16x8 hv = __builtin_bit_cast(f16x8, xf[j]);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) pv[8 * j + e] = (float)hv[e];
+                    for (int e = 0; e < 8; ++e) pv[8 * j + e] = (float)hv[e] * (1.0f / kPairSlotGain<BF16>);
                 }
             }
 #pragma unroll

@@ -1,7 +1,7 @@
 """Inputs whose expected attention output resolves ONE key, however long the sweep: builders, expectations and per-element bars.
 
 The suite's bars are one number per tensor (conftest FLOOR / ATOL / GRAD_TOL, tools/fuzz_parity.py's 2 * FLOOR * max|v|).  On a sweep of 4096 keys one
-(row, key) pair moves O by P * |v| ~ 1 / 1500 — under those bars — and a whole dropped 64 x 64 tile passes the bf16 one.  The three input classes here
+(row, key) pair moves O by P * |v| ~ 1 / 1500 — under those bars — and a whole dropped 64 x 64 tile passes the bf16 one.  The four input classes here
 keep their power at any Nkv.  CPU-only code with a `device` argument; imports neither the library nor the oracle (class C's code is tools/key_bars.py's,
 re-exported here; tests/test_key_probes.py proves the conditions, the oracle inside every bar and ten float64 mutants outside; tests/test_key_probes_gpu.py runs the kernels; tools/fuzz_parity.py and
 tools/fuzz_mask.py apply the class-C O and dV bars).
@@ -50,6 +50,28 @@ C. Random inputs (N(0,1)) against float64 dense attention on the device, with pe
    D 2^-24 in place of u (1.5 % of u at fp16, D = 128).
    KAPPA is measured, not derived: the largest |g_oracle - g_float64| / (u A) of the same-contract oracle backward over the class-C shapes of the GPU
    tests, both dtypes (tests/test_key_probes.py: measure_kappa(), `python tests/test_key_probes.py kappa`), doubled.
+
+D. Two-key pointer inputs.  B's keys and values; Q_i = c (K_a(i) + K_b(i)): entries -2c, 0, 2c, exact in fp16 and bf16.  Both targets score
+   scale c (D + K_a . K_b), the same integer times c: P_a = P_b = 1/2 up to the leak, O_i = (v_a + v_b) / 2, and the backward does NOT cancel on them:
+       dS_a = -dS_b = scale g_i / 4,  g_i = dO_i . (v_a - v_b);   dQ_i = dS_a (k_a - k_b),   dK_a += dS_a q_i,   dV_a += dO_i / 2
+   all O(1) at any sweep length.  dO = N(0,1) + sig (v_a - v_b) / 2 keeps g_i away from 0 (g_i ~ sig D).  two_pointer_maps puts a and b ON the edges of the
+   row's visible interval [lo_i, hi_i) (kind "edge") or one key inside them (kind "inner"): a transposed band that is one key short or long at either
+   end drops or adds exactly such a pair, and the two kinds together tell which side.  Under a keep mask or a dropout mask the targets are the row's
+   first and last kept visible keys.  Rows with a = b (a band one key wide, a sequence of one key) probe O and dV only, rows that see no key get
+   q = 0 and must come back with dQ = 0.
+   The expected values are float64 dense attention under the call's own modifiers (dense64 with keep= / bias= / softcap= / kept= / dlse=), the bars
+   class C's with two more terms (tools/key_bars.py: delta through the rounded O, an absolute floor for bf16) and a KAPPA_D measured as KAPPA is.
+   The builder REFUSES (ValueError) inputs that are not a probe — conditions, checked in float64 from that reference:
+       leak    1 - P_a - P_b <= POINTER_LEAK for every row, under the call's score modifiers (c starts at 4 and doubles, up to 256: D = 64 needs 32);
+       power   for every (row, target) pair, leaving the pair out of the backward moves some element of dV by >= POWER_D = 4 of that element's bars,
+               and for rows with two targets some element of dQ and some element of dK likewise (bars of the dtype in use; a key that many rows
+               point at has a larger bar, which is why this is checked and not assumed).
+   Three things the conditions forced.  A row that can see ONE key (a packed sequence of one key under 700 rows) has P = 1 whatever the scores are, and no
+   element of that key's dV resolves one of 700 summands: such rows are exempt from the dV condition and reported apart (power["dv_lone"]); O holds them.
+   Heads of a group that all point at one key put g summands under one dK / dV bar: where that leaves a pair under POWER_D (bf16, g >= 4) the caller
+   asks for spread_group, one pointing head per row.  And a head in which some row's two targets tie with a third key gets new keys (_tied_heads).
+   ALiBi (P_a != P_b: the nearer target wins by exp(slope * width)) and soft-capping (the capped target must still beat the capped rest) are given as
+   bias= and softcap=; the caller chooses slopes with slope * width of order 1 and a cap above the target's score, and the two conditions decide.
 """
 import importlib.util
 import math
@@ -64,6 +86,8 @@ kb = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(kb)
 LOG2E, U, FP16_MIN_NORMAL, QUANTUM, KAPPA_MEASURED, KAPPA = kb.LOG2E, kb.U, kb.FP16_MIN_NORMAL, kb.QUANTUM, kb.KAPPA_MEASURED, kb.KAPPA
 dense64, o_bar, dv_bar, dq_bar, dk_bar, ratio_max = kb.dense64, kb.o_bar, kb.dv_bar, kb.dq_bar, kb.dk_bar, kb.ratio_max
+FLOOR_D, KAPPA_D_MEASURED, KAPPA_D = kb.FLOOR_D, kb.KAPPA_D_MEASURED, kb.KAPPA_D
+o_bar_d, dv_bar_d, dq_bar_d, dk_bar_d = kb.o_bar_d, kb.dv_bar_d, kb.dq_bar_d, kb.dk_bar_d
 
 _MANT = {torch.float16: 10, torch.bfloat16: 7}
 _EMIN = {torch.float16: -14, torch.bfloat16: -126}
@@ -346,3 +370,239 @@ def check_random(ref, dtype, o=None, dq=None, dk=None, dv=None):
     if dk is not None:
         fails += check_elements("dK", dk, ref["dk"], dk_bar(ref, dtype))
     return fails
+
+
+# ---------------------------------------------------------------------------------------------------------------- D: two-key pointer inputs
+POWER_D = 4.0
+C_MAX_D = 256.0
+DRAWS_D = 8
+
+
+def _uniform_in(lo, width, gen):
+    """One seeded uniform draw per row from [lo, lo + width) (width >= 1)."""
+    return lo + (torch.rand(lo.shape, generator=gen, dtype=torch.float64) * width.double()).long().clamp(max=width - 1)
+
+
+def two_pointer_maps(lo, hi, Nkv, seed, kind="edge", keep=None):
+    """-> (a, b): int64 target keys of every row, -1 for rows that see no key.  lo, hi: row_ranges' output.  a(i) = lo_i where the band bounds the row from
+    the left (lo_i > 0), else a seeded uniform key of [lo_i, hi_i); b(i) = hi_i - 1 where hi_i < Nkv, else uniform, different from a where the row sees two
+    keys.  kind "inner": lo_i + 1 and hi_i - 2 instead (kept inside the interval).  keep (bool [..., Nq, Nkv], already the visible & kept keys): the first
+    and the last True of every row instead, lo / hi unused; the result has keep's leading shape."""
+    if keep is not None:
+        any_ = keep.any(-1)
+        idx = torch.arange(keep.shape[-1], device=keep.device)
+        a = torch.where(keep, idx, torch.full_like(idx, keep.shape[-1])).min(-1).values
+        b = torch.where(keep, idx, torch.full_like(idx, -1)).max(-1).values
+        if kind == "inner":                                             # the second and the second-to-last kept key, where the row has that many
+            k2 = keep.clone()
+            k2.scatter_(-1, a.clamp(max=keep.shape[-1] - 1).unsqueeze(-1), False)
+            a2 = torch.where(k2, idx, torch.full_like(idx, keep.shape[-1])).min(-1).values
+            k2 = keep.clone()
+            k2.scatter_(-1, b.clamp(min=0).unsqueeze(-1), False)
+            b2 = torch.where(k2, idx, torch.full_like(idx, -1)).max(-1).values
+            many = keep.sum(-1) >= 4
+            a, b = torch.where(many, a2, a), torch.where(many, b2, b)
+        return torch.where(any_, a, torch.full_like(a, -1)), torch.where(any_, b, torch.full_like(b, -1))
+    lo, hi = lo.cpu(), hi.cpu()
+    g = _gen(seed)
+    width = (hi - lo).clamp(min=1)
+    inner = 1 if kind == "inner" else 0
+    a_edge, b_edge = lo > 0, hi < Nkv
+    a = torch.where(a_edge, torch.minimum(lo + inner, hi - 1), _uniform_in(lo, width, g))
+    # b: the edge, or a uniform key other than a (a + 1 + r mod width, r uniform in [0, width - 1))
+    r = _uniform_in(torch.zeros_like(lo), (width - 1).clamp(min=1), g)
+    b = torch.where(b_edge, torch.maximum(hi - 1 - inner, lo), torch.where(width > 1, lo + (a - lo + 1 + r) % width, a))
+    r = _uniform_in(torch.zeros_like(lo), (width - 1).clamp(min=1), g)
+    a = torch.where(~a_edge & b_edge & (a == b) & (width > 1), lo + (b - lo + 1 + r) % width, a)
+    dead = hi <= lo
+    return torch.where(dead, torch.full_like(a, -1), a), torch.where(dead, torch.full_like(b, -1), b)
+
+
+def _gather_rows(t, idx):
+    """t [B,H,N,D], idx int64 [B,H,R] (>= 0) -> [B,H,R,D]."""
+    return torch.gather(t, 2, idx.unsqueeze(-1).expand(*idx.shape, t.shape[-1]))
+
+
+def two_pointer_inputs(B, H, Hkv, Nq, Nkv, D, dtype, pa, pb, seed, *args, draws=None, **kw):
+    """two_pointer_draw(..., seed + 1000 t) for t = 0, 1, ... < draws (DRAWS_D): the first draw of keys and values that meets the conditions; the last
+    draw's ValueError where none does.  (Among 3072 keys of 64 signs some third key matches the two targets on every sign they share, once in a few
+    draws: a three-way tie that no c separates.  The conditions are the same for every draw; "draw" in the result says which one was taken.)"""
+    for t in range(DRAWS_D if draws is None else draws):
+        try:
+            out = two_pointer_draw(B, H, Hkv, Nq, Nkv, D, dtype, pa, pb, seed + 1000 * t, *args, **kw)
+            out["draw"] = t
+            return out
+        except ValueError as e:
+            err = e
+    raise err
+
+
+def two_pointer_draw(B, H, Hkv, Nq, Nkv, D, dtype, pa, pb, seed, device=None, scale=None, visible=None, bias=None, softcap=0.0, kept=None, rs=1.0,
+                     dlse=None, sig=1.0, c=None, per_query_head=False, spread_group=False):
+    """-> dict(q, k, v, do, c, scale, pa, pb [B,H,Nq], leak [B,H,Nq], power = dict(dv, dq, dk: the smallest moved-element / bar ratio over the pairs),
+    ref = dense64(...) of the inputs under the given modifiers: the expected values and the sums the bars are made of).
+    pa, pb: int64 [Nq] or [B,Hkv,Nq], -1 for rows that see no key.  visible: None or bool broadcastable to [B,H,Nq,Nkv] (band and / or keep mask);
+    bias: additive, broadcastable likewise (an additive mask, ALiBi as -slope |distance|); softcap; kept / rs: a dropout keep mask and 1 / (1 - p_eff);
+    dlse: a gradient of the natural-log LSE [B,H,Nq].  Raises ValueError where the leak or the power condition fails (module docstring).
+    per_query_head: the backward under test runs on expanded k / v and returns dK / dV per query head (the power condition then uses those bars, not a
+    group's sum).  spread_group: row i points in ONE head of its group, head i mod g, and has q = 0 in the others (same map for all): g heads that
+    point at one key put g summands under one dK / dV bar and each pair keeps 1 / g of its power — at bf16 and g = 16, 1.3 bars."""
+    scale = D ** -0.5 if scale is None else scale
+    g = _gen(seed)
+    k = (torch.randint(0, 2, (B, Hkv, Nkv, D), generator=g) * 2 - 1).to(dtype)
+    v = torch.randn((B, Hkv, Nkv, D), generator=g).to(dtype)
+    noise = torch.randn((B, H, Nq, D), generator=g)
+    dev = torch.device("cpu") if device is None else device
+    k, v, noise = k.to(dev), v.to(dev), noise.to(dev)
+    pa, pb = (_expand(t.to(dev).expand(B, Hkv, Nq) if t.dim() == 3 else t.to(dev).view(1, 1, Nq).expand(B, Hkv, Nq), H) for t in (pa, pb))
+    live = pa >= 0
+    if not bool(((pb >= 0) == live).all()):
+        raise ValueError("two-pointer inputs: a row has one target and not the other")
+    if spread_group and H != Hkv:
+        g_ = H // Hkv
+        mine = (torch.arange(Nq, device=dev)[None, :] % g_) == (torch.arange(H, device=dev)[:, None] % g_)
+        pa, pb = (torch.where(mine[None], t, torch.full_like(t, -1)) for t in (pa, pb))
+        live = pa >= 0
+    ia, ib = pa.clamp(min=0), pb.clamp(min=0)
+    for t in range(1, DRAWS_D + 1):                                     # k / v heads with a tie get new keys (the other heads keep theirs)
+        tied = _tied_heads(k, ia, ib, live, visible, H)
+        if not tied:
+            break
+        for (b_, h_) in tied:
+            k[b_, h_] = (torch.randint(0, 2, (Nkv, D), generator=_gen(seed + 7919 * t + b_ * Hkv + h_)) * 2 - 1).to(dtype).to(dev)
+    ke, ve = _expand(k, H), _expand(v, H)
+    ka, kb_ = _gather_rows(ke, ia).float(), _gather_rows(ke, ib).float()
+    va, vb = _gather_rows(ve, ia).float(), _gather_rows(ve, ib).float()
+    do = (noise + (0.5 * sig) * (va - vb) * live.unsqueeze(-1)).to(dtype)
+    mods = dict(keep=visible, bias=bias, softcap=softcap)
+    cc = 4.0 if c is None else float(c)
+    while True:
+        assert math.log2(cc) == int(math.log2(cc)), "c must be a power of two"
+        q = ((ka + kb_) * cc * live.unsqueeze(-1)).to(dtype)
+        fwd = dense64(q, ke, ve, scale, **mods)
+        p_a, p_b, _ = _target_p(q, ke, scale, fwd["lse"], ia, ib, bias, softcap, visible)
+        leak = torch.where(live, 1.0 - p_a - torch.where(ia == ib, torch.zeros_like(p_b), p_b), torch.zeros_like(p_a))
+        if bool(torch.isfinite(leak).all()) and float(leak.max()) <= POINTER_LEAK:
+            break
+        if c is not None or cc >= C_MAX_D or not float(leak.max()) < 0.2:       # (a fifth and more: a tie, the same at every c)
+            raise ValueError("two-pointer inputs: 1 - P_a - P_b = %.3e > 2^-16 at c = %g (D = %d, Nkv = %d)" % (float(leak.max()), cc, D, Nkv))
+        cc *= 2
+    del fwd
+    ref = dense64(q, ke, ve, scale, do=do, kept=kept, rs=rs, dlse=dlse, **mods)
+    out = dict(q=q, k=k, v=v, do=do, c=cc, scale=scale, pa=pa, pb=pb, leak=leak, ref=ref, Hkv=Hkv, softcap=softcap, bias=bias, visible=visible, kept=kept, rs=rs, dlse=dlse,
+               per_query_head=per_query_head)
+    out["power"] = two_pointer_power(out, dtype)
+    bad = [n for n, x in out["power"].items() if n != "dv_lone" and not x >= POWER_D]
+    if bad:
+        raise ValueError("two-pointer inputs: a dropped (row, target) pair moves %s by only %s bars (< %g)" % (bad, [round(out["power"][n], 2) for n in bad], POWER_D))
+    return out
+
+
+def _tied_heads(k, ia, ib, live, visible, H):
+    """The k / v heads [(b, h)] in which some row sees a THIRD key that scores exactly what its two targets score: (k_a + k_b) . k_j = D + k_a . k_b, in
+    integers (exact in f32).  No c separates such a key (P = 1/3 each): among 3072 keys of 64 signs it happens to one head in some fifteen."""
+    B, Hkv, Nkv, D = k.shape
+    g = H // Hkv
+    out = []
+    for b in range(B):
+        for h in range(Hkv):
+            kf = k[b, h].float()
+            tie = False
+            for hq in range(h * g, (h + 1) * g):                        # (a group's heads point the same way; their visible keys may differ)
+                a, bb = ia[b, hq], ib[b, hq]
+                gram = torch.matmul(kf[a] + kf[bb], kf.t())
+                hit = gram >= (D + (kf[a] * kf[bb]).sum(-1))[:, None]
+                rows = torch.arange(a.numel(), device=k.device)
+                hit[rows, a] = False
+                hit[rows, bb] = False
+                if visible is not None:
+                    hit &= visible.to(k.device).expand(B, H, a.numel(), Nkv)[b, hq]
+                tie = tie or bool((hit & live[b, hq][:, None]).any())
+            if tie:
+                out.append((b, h))
+    return out
+
+
+def _target_p(q, ke, scale, lse2, ia, ib, bias, softcap, visible):
+    """P of the two targets of every row [B,H,Nq] each and the soft-capping's d s / d x at them, in float64, from the reference's LSE (log2)."""
+    res = []
+    B, H, Nq, _ = q.shape
+    for idx in (ia, ib):
+        s = (q.double() * _gather_rows(ke, idx).double()).sum(-1) * scale
+        fac = torch.ones_like(s)
+        if softcap > 0:
+            t = torch.tanh(s / softcap)
+            s, fac = softcap * t, 1.0 - t * t
+        if bias is not None:
+            s = s + torch.gather(bias.to(q.device).expand(B, H, Nq, ke.shape[2]), 3, idx.unsqueeze(-1)).squeeze(-1).double()
+        if visible is not None:
+            ok = torch.gather(visible.to(q.device).expand(B, H, Nq, ke.shape[2]), 3, idx.unsqueeze(-1)).squeeze(-1)
+            s = s.masked_fill(~ok, float("-inf"))
+        res.append((torch.exp(s - lse2 / LOG2E), fac))
+    return res[0][0], res[1][0], (res[0][1], res[1][1])
+
+
+def _visible_count(inp, B, H, Nq):
+    Nkv = inp["k"].shape[2]
+    ok = torch.ones((B, H, Nq, Nkv), dtype=torch.bool, device=inp["q"].device)
+    if inp["visible"] is not None:
+        ok = ok & inp["visible"].to(ok.device)
+    if inp["bias"] is not None:
+        ok = ok & ~torch.isneginf(inp["bias"].to(ok.device))
+    return ok.sum(-1)
+
+
+def two_pointer_power(inp, dtype):
+    """The power condition's figures: over every (row, target) pair, the smallest of max_c |what leaving the pair out of the backward moves| / bar, for dV
+    (all pairs) and for dQ and dK (rows with two targets).  float64, from inp["ref"]."""
+    ref, q, do = inp["ref"], inp["q"], inp["do"].double()
+    B, H, Nq, D = q.shape
+    Hkv = inp["Hkv"]
+    ke, ve = _expand(inp["k"], H), _expand(inp["v"], H)
+    live = inp["pa"] >= 0
+    two = live & (inp["pa"] != inp["pb"])
+    # a row that can see ONE key has P = 1 whatever the scores are (a packed sequence of one key under 700 rows: no element of that key's dV can resolve one
+    # of 700 summands); leaving its pair out of the forward gives O = 0 for v, 1 / (2 u) bars.  Such rows are reported apart ("dv_lone"), not refused.
+    lone = live & (_visible_count(inp, B, H, Nq) == 1)
+    ia, ib = inp["pa"].clamp(min=0), inp["pb"].clamp(min=0)
+    p_a, p_b, facs = _target_p(q, ke, inp["scale"], ref["lse"], ia, ib, inp["bias"], inp["softcap"], inp["visible"])
+    delta = (do * ref["o"]).sum(-1)
+    if inp["dlse"] is not None:
+        delta = delta - inp["dlse"].double()
+    # the bars of dK / dV belong to the k / v heads: a group's query heads add up (fold_kv_heads), and so do their bars
+    dvb, dkb = (f(ref, dtype) if inp["per_query_head"] else _expand(fold_kv_heads(f(ref, dtype), Hkv), H) for f in (dv_bar_d, dk_bar_d))
+    dqb = dq_bar_d(ref, dtype)
+    inf = torch.full((B, H, Nq), float("inf"), dtype=torch.float64, device=q.device)
+    worst = dict(dv=inf, dq=inf, dk=inf, dv_lone=inf)
+    for idx, p, fac in ((ia, p_a, facs[0]), (ib, p_b, facs[1])):
+        pd = p * inp["rs"]                                               # (the targets are kept keys)
+        r_dv = ((pd.unsqueeze(-1) * do).abs() / _gather_rows(dvb, idx)).max(-1).values
+        ds = p * ((do * _gather_rows(ve, idx).double()).sum(-1) * inp["rs"] - delta) * fac * inp["scale"]
+        r_dq = ((ds.unsqueeze(-1) * _gather_rows(ke, idx).double()).abs() / dqb).max(-1).values
+        r_dk = ((ds.unsqueeze(-1) * q.double()).abs() / _gather_rows(dkb, idx)).max(-1).values
+        worst["dv"] = torch.minimum(worst["dv"], torch.where(live & ~lone, r_dv, inf))
+        worst["dv_lone"] = torch.minimum(worst["dv_lone"], torch.where(lone, r_dv, inf))
+        worst["dq"] = torch.minimum(worst["dq"], torch.where(two, r_dq, inf))
+        worst["dk"] = torch.minimum(worst["dk"], torch.where(two, r_dk, inf))
+    return {n: float(x.min()) for n, x in worst.items()}
+
+
+def check_two_pointer(inp, dtype, o=None, dq=None, dk=None, dv=None):
+    """-> (failures, {tensor: worst err / bar}) of whichever results are given against inp["ref"] and the class-D bars.  dk, dv: per k / v head
+    [B,Hkv,Nkv,D] (the reference and its bars are summed over each group), or, for inputs built with per_query_head, per query head [B,H,Nkv,D] (a backward
+    run on expanded k / v).  Rows that see no key must have dQ = 0 exactly."""
+    ref, Hkv, per_query_head = inp["ref"], inp["Hkv"], inp["per_query_head"]
+    fold = (lambda t: t) if per_query_head else (lambda t: fold_kv_heads(t, Hkv))
+    items = [("O", o, ref["o"], o_bar_d(ref, dtype)), ("dQ", dq, ref["dq"], dq_bar_d(ref, dtype)),
+             ("dK", dk, fold(ref["dk"]), fold(dk_bar_d(ref, dtype))), ("dV", dv, fold(ref["dv"]), fold(dv_bar_d(ref, dtype)))]
+    fails, worst = [], {}
+    for name, got, want, bar in items:
+        if got is None:
+            continue
+        fails += check_elements(name, got, want, bar)
+        worst[name] = worst_ratio(got, want, bar) if bool(torch.isfinite(got.double()).all()) else float("nan")
+    if dq is not None:
+        dead = torch.isinf(ref["lse"])
+        if bool(dead.any()) and not bool((dq.double()[dead] == 0).all()):
+            fails.append("dQ: rows that see no key are not exactly 0")
+    return fails, worst

@@ -4,8 +4,10 @@ themselves live in tools/fuzz_lse.py, the randomised sweep of the same calls, an
 truth64: dense float64 autograd of the contract with the LSE as a second output — loss = (O * dO).sum() + (lse_live * u).sum(), lse in natural-log
 units, u the caller's weights; every route of flash_attention goes through the same few lines: scaled scores, soft-capping, ALiBi, an additive bias,
 a keep mask (bool mask and band) as -inf, dropout applied to the probabilities (the LSE is that of the undropped ones).
-emulate: the same contract as the kernels run it — f32 scores and sums, P rounded to the I/O dtype, dS (1 - t^2) rounded to the I/O dtype, outputs
-rounded once — with the dQ pass's row term delta - u.
+emulate: the same contract as the kernels run it — f32 scores and sums, P rounded to the I/O dtype where it multiplies V and dO (O, dV), dS = P (dP - delta) (1 - t^2)
+formed from the f32 P and rounded to the I/O dtype once, outputs rounded once — with the dQ pass's row term delta - u.  (The fp16 wave-pair dK / dV pass
+hands P from one wave to the other in 16 bits, one relative rounding more than here; in fp16 as round16(2^14 P), which keeps that rounding relative
+down to P = 2^-28 instead of losing the pair below 2^-25.)
 Bars: the project's rule (tools/fuzz_features.py: error_and_bar; FLOOR / GRAD_TOL / LSE_TOL of conftest.py); the LSE is compared in log2 units."""
 import importlib.util
 import math

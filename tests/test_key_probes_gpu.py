@@ -1,5 +1,6 @@
 """GPU tests (`-m gpu`) of the dense forward and backward on the inputs of tests/key_probes.py: counting inputs (A), pointer inputs (B) and random inputs
-with per-element bars (C).  The bars do not grow with the sweep: one (row, key) pair missed at Nkv = 4096 fails A's LSE (one count) or B's O (the row
+with per-element bars (C); and of every backward — dense, windowed, packed, grouped, masked, dropout, score modifiers, their packed twins and the *_lse
+entries — on two-key pointer inputs (D, the second half of this file).  The bars do not grow with the sweep: one (row, key) pair missed at Nkv = 4096 fails A's LSE (one count) or B's O (the row
 points at it), where the per-tensor bars of the other test modules pass a whole dropped tile (tests/test_key_probes.py proves both on float64 mutants).
 
 Every case asks the library's plan query which kernel serves the call and asserts the route it is named for BEFORE it runs anything — on paper too:
@@ -109,6 +110,18 @@ BACKWARD_CASES = [    # route, B, H, Nq, Nkv, D, dtype, causal, ws, classes, (dq
 ]
 SEED_C_BWD = 123        # the class-C backward inputs: tests/test_key_probes.py measure_kappa() draws the same
 BWD_KERNEL = {"hip": _fa2_lib.FA2_BWD_KERNEL_HIP, "asm": _fa2_lib.FA2_BWD_KERNEL_ASM}
+
+
+SEED_D = 131            # the class-D inputs of the dense backward cases: tests/test_key_probes.py measure_kappa_d() draws the same
+D_KINDS = ("edge", "inner")
+
+
+def dense_d_inputs(b, kind, device=None):
+    """The class-D inputs (tests/key_probes.py) of a BACKWARD_CASES row: targets on ('edge') or one key inside ('inner') the ends of every row's sweep."""
+    route, B, H, Nq, Nkv, D, dtype, causal = b[:8]
+    lo, hi = kp.row_ranges(Nq, Nkv, causal=causal)
+    pa, pb = kp.two_pointer_maps(lo, hi, Nkv, seed=SEED_D, kind=kind)
+    return kp.two_pointer_inputs(B, H, H, Nq, Nkv, D, dtype, pa, pb, seed=SEED_D + 1, device=device, visible=_vis(dict(Nq=Nq, Nkv=Nkv, causal=causal), device))
 
 
 def all_forward_shapes():
@@ -385,4 +398,509 @@ def test_backward_routes_on_key_probes(b):
         print("C: worst err / bar: O %.3f dQ %.3f dK %.3f dV %.3f" % (kp.worst_ratio(o, ref["o"], kp.o_bar(ref, dtype)), kp.worst_ratio(dq, ref["dq"], kp.dq_bar(ref, dtype)),
                                                                       kp.worst_ratio(dk, ref["dk"], kp.dk_bar(ref, dtype)), kp.worst_ratio(dv, ref["dv"], kp.dv_bar(ref, dtype))))
         fails += ["C: " + f for f in kp.check_random(ref, dtype, o=o, dq=dq, dk=dk, dv=dv)]
+    assert fails == [], fails
+
+
+# ---------------------------------------------------------------------------------------------------------------- class D: two-key pointer probes of every backward
+# tests/key_probes.py class D: every row puts half its weight on each of two keys that sit ON the ends of its visible interval ("edge") or one key inside
+# them ("inner"); O, dQ, dK and dV are held element by element to float64 under the call's own modifiers.  The family backwards walk the transposed band,
+# the packed sequences' offsets, the group sum, the regenerated dropout mask and the score modifiers' derivative: a pair dropped or added there moves dQ_i,
+# dK_a and dV_a by tens of bars (tests/test_key_probes.py shows it on float64 mutants).  Outputs are NaN before every call.
+LN2 = 0.6931471805599453
+CAUSAL, BOTTOM_RIGHT = _fa2_lib.FA2_FLAG_CAUSAL, _fa2_lib.FA2_FLAG_BOTTOM_RIGHT
+D_WORST = {}            # case id -> {tensor: worst err / bar}: what the run prints (profiles/ keeps one run's)
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _s2(t):
+    return _fa2_lib.strides2(t.stride(0), t.stride(1))
+
+
+def _nan_like(*ts):
+    return tuple(torch.full_like(t, float("nan")) for t in ts)
+
+
+def _dt(dtype):
+    return "f16" if dtype == F16 else "bf16"
+
+
+def _report(tag, fails, worst):
+    D_WORST[tag] = worst
+    print("D %s: worst err / bar %s" % (tag, " ".join("%s %.3f" % (n, x) for n, x in worst.items())))
+    return ["%s: %s" % (tag, f) for f in fails]
+
+
+def _band_of(Nq, Nkv, causal=False, window=(-1, -1), q_offset=0, bottom_right=False, device=None):
+    lo, hi = kp.row_ranges(Nq, Nkv, causal=causal, bottom_right=bottom_right, window=window, q_offset=q_offset)
+    j = torch.arange(Nkv)[None]
+    vis = (j >= lo[:, None]) & (j < hi[:, None])
+    return lo, hi, (vis.to(device) if device is not None else vis)
+
+
+def alibi_bias(slopes, Nq, Nkv, off):
+    """-slope_h |i + off - j| as an additive [1 or B, H, Nq, Nkv] float64 tensor (slopes [H] or [B, H])."""
+    dist = (torch.arange(Nq, device=slopes.device)[:, None] + off - torch.arange(Nkv, device=slopes.device)[None]).abs().double()
+    s = slopes.double().view(-1, slopes.shape[-1]) if slopes.dim() == 2 else slopes.double().view(1, -1)
+    return -s[:, :, None, None] * dist
+
+
+def bhnd_call(inp, causal=False, window=None, bias=None, dropout=None, smod=None, dlse=None, gqa=False, ws_bytes=0, opts=None):
+    """Forward (flagged FA2_FLAG_EXACT_SCALE, as every differentiated call) and backward of one [B,H,N,D] call through the C-ABI -> (o, dq, dk, dv).
+    window = (left, right, q_offset): the windowed family (fa2_fwd_window / fa2_bwd_window; with dropout = (p, seed) fa2_*_dropout, with smod = (softcap,
+    slopes or None) fa2_*_scoremod); bias: fa2_fwd_bias / fa2_bwd_bias (fa2_bwd_bias_ws with ws_bytes); gqa: fa2_fwd_gqa / fa2_bwd_gqa; else fa2_fwd /
+    fa2_bwd (fa2_bwd_ws).  dlse (natural-log units, [B,H,Nq]): the family's *_lse entry.  The windowed and masked backwards have no grouped form: grouped
+    k / v are expanded for them and dK / dV come back per query head."""
+    from rocwmma_fattn.FlashAttn import _prepare_bias
+    lib = _fa2_lib.load(build_if_missing=False)
+    q, do = inp["q"], inp["do"]
+    k, v = inp["k"], inp["v"]
+    B, H, Nq, D = q.shape
+    Hkv, Nkv = k.shape[1], k.shape[2]
+    dt, scale, flags = _code(q.dtype), float(inp["scale"]), (CAUSAL if causal else 0) | EXACT
+    o, = _nan_like(q)
+    lse = torch.full((B, H, Nq), float("nan"), dtype=torch.float32, device=q.device)
+    fwd = (dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, H)
+    ftail = (Nq, Nkv, D, _s3(q), _s3(k), _s3(v), _s3(o), _s2(lse), scale, flags)
+    bias_args = None
+    if bias is not None:
+        bias_t, kind, bstr = _prepare_bias(bias, B, H, Nq, Nkv, q.dtype, q.device)
+        bias_args = (bias_t.data_ptr(), kind, _fa2_lib.strides3(*bstr))
+    smod_args = None
+    if smod is not None:
+        smod_args = (float(smod[0]), None, 0) if smod[1] is None else (float(smod[0]), smod[1].data_ptr(), smod[1].stride(0) if smod[1].dim() == 2 else 0)
+    with _fa2_lib.options(**(opts or {})):
+        if window is not None:
+            name = "fa2_fwd_scoremod" if smod is not None else "fa2_fwd_dropout" if dropout is not None else "fa2_fwd_window"
+            extra = smod_args if smod is not None else (float(dropout[0]), int(dropout[1])) if dropout is not None else ()
+            rc = getattr(lib, name)(*fwd, Hkv, *ftail, *window, _stream(), *extra)
+        elif bias is not None:
+            rc = lib.fa2_fwd_bias(*fwd, *ftail, *bias_args, _stream())
+        elif gqa:
+            rc = lib.fa2_fwd_gqa(*fwd, Hkv, *ftail, None, 0, _stream())
+        else:
+            rc = lib.fa2_fwd(*fwd, *ftail, _stream())
+        _fa2_lib.check(rc)
+        torch.cuda.synchronize()
+    if not gqa and Hkv != H:
+        k, v = (t.repeat_interleave(H // Hkv, dim=1) for t in (k, v))
+    dq, dk, dv = _nan_like(q, k, v)
+    delta = torch.full_like(lse, float("nan"))
+    ws = torch.full(((ws_bytes + 3) // 4 + 4,), float("nan"), dtype=torch.float32, device=q.device) if ws_bytes else None
+    ws_args = (ws.data_ptr() if ws_bytes else None, ws_bytes)
+    head = (dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), B, H)
+    tail = (Nq, Nkv, D, *(_s3(t) for t in (q, k, v, o, do, dq, dk, dv)), _s2(lse), scale, int(causal))
+    if dlse is not None:
+        g = (dlse.float() * LN2).contiguous()
+        g_args = (g.data_ptr(), _s2(g))
+    if gqa:
+        assert dlse is None
+        rc = lib.fa2_bwd_gqa(*head, Hkv, *tail, *ws_args, _stream())
+    elif window is not None:
+        if dlse is not None:
+            rc = lib.fa2_bwd_window_lse(*head, *tail, *window, _stream(), *((0.0, 0) if dropout is None else (float(dropout[0]), int(dropout[1]))),
+                                        *(smod_args or (0.0, None, 0)), *g_args)
+        elif smod is not None:
+            rc = lib.fa2_bwd_scoremod(*head, *tail, *window, _stream(), *smod_args)
+        elif dropout is not None:
+            rc = lib.fa2_bwd_dropout(*head, *tail, *window, _stream(), float(dropout[0]), int(dropout[1]))
+        else:
+            rc = lib.fa2_bwd_window(*head, *tail, *window, _stream())
+    elif dlse is not None:
+        rc = lib.fa2_bwd_lse(*head, *tail, *(bias_args or (None, _fa2_lib.FA2_BIAS_NONE, None)), *ws_args, _stream(), *g_args)
+    elif bias is not None:
+        rc = lib.fa2_bwd_bias_ws(*head, *tail, *bias_args, *ws_args, _stream()) if ws_bytes else lib.fa2_bwd_bias(*head, *tail, *bias_args, _stream())
+    else:
+        rc = lib.fa2_bwd_ws(*head, *tail, *ws_args, _stream()) if ws_bytes else lib.fa2_bwd(*head, *tail, _stream())
+    _fa2_lib.check(rc)
+    torch.cuda.synchronize()
+    return o, dq, dk, dv
+
+
+def _dlse_of(B, H, Nq, seed, device):
+    return torch.randn((B, H, Nq), generator=torch.Generator().manual_seed(seed)).to(device or "cpu")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("b", [b for b in BACKWARD_CASES if "B" in b[9]], ids=lambda b: "%s-%dx%dx%dx%dx%d-%s%s" % (b[0], b[1], b[2], b[3], b[4], b[5], "f16" if b[6] == F16 else "bf16", "-causal" if b[7] else ""))
+def test_dense_backward_resolves_both_targets_of_every_row(b):
+    """Class D on every dense backward route; the plain fp16 rows also through fa2_bwd_lse with a gradient for the LSE (the reference adds P dlse)."""
+    route, B, H, Nq, Nkv, D, dtype, causal, ws, classes, kernels = b
+    dev = _dev()
+    need = bwd_route_of(b)
+    fails = []
+    for kind in D_KINDS if causal else D_KINDS[:1]:          # (full attention has no band edge: both kinds draw the same uniform targets)
+        inp = dense_d_inputs(b, kind, dev)
+        o, dq, dk, dv = bhnd_call(inp, causal=causal, ws_bytes=need)
+        fails += _report("%s %dx%d %s%s %s" % (route, Nq, Nkv, _dt(dtype), " causal" if causal else "", kind), *kp.check_two_pointer(inp, dtype, o, dq, dk, dv))
+    if route == "plain" and dtype == F16:
+        plan = _fa2_lib.BwdPlan()
+        s = _fa2_lib.strides3(H * Nq * D, Nq * D, D), _fa2_lib.strides3(H * Nkv * D, Nkv * D, D)
+        _fa2_lib.check(_fa2_lib.load().fa2_bwd_lse_plan(_code(dtype), B, H, H, Nq, Nkv, D, s[0], s[1], s[1], s[0], s[0], float(D ** -0.5), int(causal), 0, None, 1,
+                                                        ctypes.byref(plan)))
+        assert (plan.dq_kernel, plan.dkv_kernel) == (BWD_KERNEL["hip"], BWD_KERNEL["hip"]), (plan.dq_kernel, plan.dkv_kernel)      # a dlse: no hand-scheduled pass
+        dlse = _dlse_of(B, H, Nq, 141, dev)
+        lo, hi = kp.row_ranges(Nq, Nkv, causal=causal)
+        pa, pb = kp.two_pointer_maps(lo, hi, Nkv, seed=SEED_D, kind="edge")
+        inp = kp.two_pointer_inputs(B, H, H, Nq, Nkv, D, dtype, pa, pb, seed=SEED_D + 1, device=dev, visible=_vis(dict(Nq=Nq, Nkv=Nkv, causal=causal), dev), dlse=dlse)
+        o, dq, dk, dv = bhnd_call(inp, causal=causal, dlse=dlse)
+        fails += _report("%s %dx%d %s%s lse" % (route, Nq, Nkv, _dt(dtype), " causal" if causal else ""), *kp.check_two_pointer(inp, dtype, o, dq, dk, dv))
+    assert fails == [], fails
+
+
+def window_d_cases():
+    out = []
+    for wi, w in enumerate(WINDOW_CASES):
+        for dtype in (F16, BF16):
+            out.append(dict(w, D=128, dtype=dtype, rows=None, dlse=(wi == 1 and dtype == BF16)))
+    out.append(dict(WINDOW_CASES[0], D=64, dtype=F16, rows=None, dlse=False))
+    out.append(dict(WINDOW_CASES[1], D=64, dtype=BF16, rows=None, dlse=False))
+    out.append(dict(WINDOW_CASES[2], D=256, dtype=BF16, rows=None, dlse=False))
+    out.append(dict(WINDOW_CASES[1], D=128, dtype=F16, rows=128, dlse=False))       # the forward's option "rows"
+    out.append(dict(WINDOW_CASES[1], D=128, dtype=F16, rows=256, dlse=False))
+    return out
+
+
+def _wid(w):
+    return "%dx%dx%d-%s-off%d%s-%s%s%s" % (w["Nq"], w["Nkv"], w["D"], w["window"], w["q_offset"], "-causal" if w["causal"] else "", "f16" if w["dtype"] == F16 else "bf16",
+                                         "-rows%d" % w["rows"] if w["rows"] else "", "-lse" if w["dlse"] else "")
+
+
+def window_d_inputs(w, kind, device=None, B=2, H=4, Hkv=2, dlse=None):
+    lo, hi, vis = _band_of(w["Nq"], w["Nkv"], causal=w["causal"], window=w["window"], q_offset=w["q_offset"], device=device)
+    pa, pb = kp.two_pointer_maps(lo, hi, w["Nkv"], seed=SEED_D + 2, kind=kind)
+    return kp.two_pointer_inputs(B, H, Hkv, w["Nq"], w["Nkv"], w["D"], w["dtype"], pa, pb, seed=SEED_D + 3, device=device, visible=vis, dlse=dlse, per_query_head=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w", window_d_cases(), ids=_wid)
+def test_window_backward_resolves_the_band_edges(w):
+    """fa2_bwd_window (grouped k / v B2 H4 Hkv2 in the forward, expanded for the backward, which has no grouped form: dK / dV per query head)."""
+    dev = _dev()
+    B, H, Hkv = 2, 4, 2
+    win = (w["window"][0], w["window"][1], w["q_offset"])
+    fails = []
+    for kind in D_KINDS:
+        dlse = _dlse_of(B, H, w["Nq"], 143, dev) if w["dlse"] else None
+        inp = window_d_inputs(w, kind, dev, B, H, Hkv, dlse)
+        with _fa2_lib.options(**({"rows": w["rows"]} if w["rows"] else {})):
+            plan = _fa2_lib.window_plan(inp["q"], inp["k"], w["causal"], *win)
+        assert plan.kernel == _fa2_lib.FA2_KERNEL_HIP_WINDOW and plan.heads_main == B * H, plan.as_dict()
+        assert plan.rows == (w["rows"] or 128), plan.as_dict()               # (the option reached the plan; D = 256 has no 256-row form and is not asked for one)
+        o, dq, dk, dv = bhnd_call(inp, causal=w["causal"], window=win, dlse=dlse, opts={"rows": w["rows"]} if w["rows"] else None)
+        fails += _report("window %s %s" % (_wid(w), kind), *kp.check_two_pointer(inp, w["dtype"], o, dq, dk, dv))
+    assert fails == [], fails
+
+
+GROUPED_D = [(32, 8, F16, False), (32, 8, BF16, True), (16, 1, F16, True), (16, 1, BF16, False)]
+
+
+def grouped_d_inputs(g, kind, device=None, H=None, Hkv=None):
+    B, Nq, Nkv, D = 1, 1100, 1984, 128
+    lo, hi, vis = _band_of(Nq, Nkv, causal=g[3], device=device)
+    pa, pb = kp.two_pointer_maps(lo, hi, Nkv, seed=SEED_D + 4, kind=kind)
+    return kp.two_pointer_inputs(B, H or g[0], Hkv or g[1], Nq, Nkv, D, g[2], pa, pb, seed=SEED_D + 5, device=device, visible=vis if g[3] else None,
+                                 spread_group=g[2] == BF16)           # (bf16: one pointing head per row, see the builder)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("g", GROUPED_D, ids=lambda g: "h%d-hkv%d-%s%s" % (g[0], g[1], "f16" if g[2] == F16 else "bf16", "-causal" if g[3] else ""))
+def test_grouped_backward_sums_every_head_of_a_group(g):
+    """fa2_bwd_gqa through the C-ABI at 1100 x 1984 (the in-kernel group sum: every query head of a group points at the same two keys, a head left out of the
+    sum takes 1 / g of dK_a and dV_a with it); H16 / Hkv1 causal also through the operator's expanded path."""
+    H, Hkv, dtype, causal = g
+    dev = _dev()
+    B, Nq, Nkv, D = 1, 1100, 1984, 128
+    lib = _fa2_lib.load()
+    plan = _fa2_lib.BwdPlan()
+    s = lambda h, n: _fa2_lib.strides3(h * n * D, n * D, D)  # noqa: E731
+    _fa2_lib.check(lib.fa2_bwd_plan(_code(dtype), B, H, Hkv, Nq, Nkv, D, s(H, Nq), s(Hkv, Nkv), s(Hkv, Nkv), s(H, Nq), s(H, Nq), float(D ** -0.5), int(causal), 0, None,
+                                    ctypes.byref(plan)))
+    # as the dense "plain" rows of this size: the hand-scheduled dQ pass per query head, the compiler-scheduled dK / dV pass with the in-kernel group sum
+    assert (plan.dq_kernel, plan.dkv_kernel) == (BWD_KERNEL["asm"], BWD_KERNEL["hip"]), (plan.dq_kernel, plan.dkv_kernel)
+    fails = []
+    for kind in D_KINDS if causal else D_KINDS[:1]:
+        inp = grouped_d_inputs(g, kind, dev)
+        o, dq, dk, dv = bhnd_call(inp, causal=causal, gqa=True)
+        fails += _report("gqa h%d/%d %s%s %s" % (H, Hkv, _dt(dtype), " causal" if causal else "", kind), *kp.check_two_pointer(inp, dtype, o, dq, dk, dv))
+        if (H, Hkv, causal) == (16, 1, True) and kind == "edge":
+            ret = flash_attn_wmma.forward_py(inp["q"], inp["k"], inp["v"], 64, 128, CAUSAL | EXACT, inp["scale"], False)
+            dq2, dk2, dv2 = flash_attn_wmma.backward_py(ret[1], ret[2], ret[3], ret[4], inp["do"], ret[5], Nq, Nkv, D, 64, 128, True, inp["scale"], False)
+            torch.cuda.synchronize()
+            fails += _report("gqa h%d/%d %s causal operator" % (H, Hkv, _dt(dtype)), *kp.check_two_pointer(inp, dtype, ret[0], dq2, dk2, dv2))
+    assert fails == [], fails
+
+
+def _packed_d(align, dtype, dev, H=4, Hkv=2, D=128, window=(-1, -1), dropout=None, smod=None, dlse_seed=None):
+    """Per sequence of PACKED_Q / PACKED_K: class-D inputs of its own band -> packed q, k, v, do, the per-sequence inputs (None where a sequence has no row
+    or no key) and the per-sequence modifiers."""
+    g = torch.Generator().manual_seed(151)
+    parts, seqs = dict(q=[], k=[], v=[], do=[]), []
+    kept_all = dropout_keep_mask(dropout[1], dropout[0], len(PACKED_Q), H, max(PACKED_Q), max(PACKED_K)) if dropout else None
+    for s_, (nq, nk) in enumerate(zip(PACKED_Q, PACKED_K)):
+        inp = None
+        if nq and nk:
+            lo, hi, vis = _band_of(nq, nk, causal=align != "full", bottom_right=align == "bottom_right", window=window, device=dev)
+            kw = dict(visible=vis)
+            if dropout:
+                kept = kept_all[s_:s_ + 1, :, :nq, :nk].to(dev)
+                pa, pb = kp.two_pointer_maps(None, None, nk, 0, keep=(vis & kept)[0].view(Hkv, H // Hkv, nq, nk).all(1)[None])
+                kw.update(kept=kept, rs=1.0 / (1.0 - round(dropout[0] * 65536) / 65536.0))
+            else:
+                pa, pb = kp.two_pointer_maps(lo, hi, nk, seed=SEED_D + 6 + s_, kind="edge")
+            if smod:
+                kw["softcap"] = smod[0]
+                if smod[1] is not None:
+                    kw["bias"] = alibi_bias(smod[1], nq, nk, (nk - nq) if align == "bottom_right" else 0)
+            if dlse_seed is not None:
+                kw["dlse"] = _dlse_of(1, H, nq, dlse_seed + s_, dev)
+            inp = kp.two_pointer_inputs(1, H, Hkv, nq, nk, D, dtype, pa, pb, seed=SEED_D + 20 + s_, device=dev, per_query_head=True, **kw)
+        seqs.append(inp)
+        parts["q"].append(inp["q"][0] if inp else torch.zeros((H, nq, D), dtype=dtype, device=dev))
+        parts["do"].append(inp["do"][0] if inp else torch.randn((H, nq, D), generator=g).to(dtype).to(dev))
+        for n in "kv":
+            parts[n].append(inp[n][0] if inp else torch.randn((Hkv, nk, D), generator=g).to(dtype).to(dev))
+    packed = {n: torch.cat(ts, dim=1).transpose(0, 1).contiguous() for n, ts in parts.items()}           # [total, heads, D]
+    return packed, seqs
+
+
+def packed_call(p, H, Hkv, D, flags, window=(-1, -1), dropout=None, smod=None, dlse=None):
+    """fa2_fwd_varlen* / fa2_bwd_varlen* on [total, heads, D] tensors (k / v expanded for the backward) -> (o, dq, dk, dv per query head)."""
+    lib = _fa2_lib.load(build_if_missing=False)
+    dev = p["q"].device
+    cu_q = torch.tensor([0] + PACKED_Q, dtype=torch.int32).cumsum(0).to(torch.int32).to(dev)
+    cu_k = torch.tensor([0] + PACKED_K, dtype=torch.int32).cumsum(0).to(torch.int32).to(dev)
+    q, k, v, do = p["q"], p["k"], p["v"], p["do"]
+    dt, scale, nseq = _code(q.dtype), float(D ** -0.5), len(PACKED_Q)
+    s2 = lambda t: _fa2_lib.strides2(t.stride(1), t.stride(0))  # noqa: E731
+    o, = _nan_like(q)
+    lse = torch.full((H, q.shape[0]), float("nan"), dtype=torch.float32, device=dev)
+    extra = ()
+    if smod is not None:
+        extra = (float(smod[0]), None, 0) if smod[1] is None else (float(smod[0]), smod[1].data_ptr(), 0)
+    elif dropout is not None:
+        extra = (float(dropout[0]), int(dropout[1]))
+    name = "_scoremod" if smod is not None else "_dropout" if dropout is not None else ""
+    _fa2_lib.check(getattr(lib, "fa2_fwd_varlen" + name)(dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), nseq, H, Hkv, max(PACKED_Q), max(PACKED_K), D,
+                                                         cu_q.data_ptr(), cu_k.data_ptr(), s2(q), s2(k), s2(v), s2(o), lse.stride(0), scale, flags | EXACT, window[0], window[1],
+                                                         _stream(), *extra))
+    torch.cuda.synchronize()
+    k, v = (t.repeat_interleave(H // Hkv, dim=1) for t in (k, v))
+    dq, dk, dv = _nan_like(q, k, v)
+    delta = torch.full_like(lse, float("nan"))
+    args = (dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), nseq, H,
+            max(PACKED_Q), max(PACKED_K), D, cu_q.data_ptr(), cu_k.data_ptr(), *(s2(t) for t in (q, k, v, o, do, dq, dk, dv)), lse.stride(0), scale, flags, window[0], window[1], _stream())
+    if dlse is not None:
+        g = (dlse.float() * LN2).contiguous()
+        rc = lib.fa2_bwd_varlen_lse(*args, *((0.0, 0) if dropout is None else extra), *((0.0, None, 0) if smod is None else extra), g.data_ptr(), g.stride(0))
+    else:
+        rc = getattr(lib, "fa2_bwd_varlen" + name)(*args, *extra)
+    _fa2_lib.check(rc)
+    torch.cuda.synchronize()
+    return o, dq, dk, dv
+
+
+def _check_packed(tag, seqs, dtype, o, dq, dk, dv):
+    """Per sequence, as the forward test: class D where the sequence has rows and keys; O = dQ = 0 for rows without keys, dK = dV = 0 for keys without rows."""
+    fails, q0, k0 = [], 0, 0
+    for s_, (nq, nk) in enumerate(zip(PACKED_Q, PACKED_K)):
+        sl = lambda t, a, n: t[a:a + n].transpose(0, 1)[None]  # noqa: E731
+        if seqs[s_] is not None:
+            fails += _report("%s seq %d (%d x %d)" % (tag, s_, nq, nk), *kp.check_two_pointer(seqs[s_], dtype, sl(o, q0, nq), sl(dq, q0, nq), sl(dk, k0, nk), sl(dv, k0, nk)))
+        else:
+            for name, t in (("O", sl(o, q0, nq)), ("dQ", sl(dq, q0, nq)), ("dK", sl(dk, k0, nk)), ("dV", sl(dv, k0, nk))):
+                if not bool((t == 0).all()):
+                    fails.append("%s seq %d (%d x %d): %s is not exactly 0" % (tag, s_, nq, nk, name))
+        q0, k0 = q0 + nq, k0 + nk
+    return fails
+
+
+PACKED_D = [("full", (-1, -1), False), ("top_left", (-1, -1), False), ("bottom_right", (-1, -1), True), ("bottom_right", (40, 0), False)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pc", PACKED_D, ids=lambda pc: "%s%s%s" % (pc[0], "-w%d" % pc[1][0] if pc[1][0] >= 0 else "", "-lse" if pc[2] else ""))
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_packed_backward_resolves_every_sequences_edges(pc, dtype):
+    """fa2_bwd_varlen on the lengths 0, 1, 63, 64, 65, 700 against 65, 0, 64, 63, 700, 1: the targets sit on the first and last key each row of each sequence
+    may see under the alignment, so a sequence read one key early or late, or a row placed under the other alignment, drops a pair."""
+    align, window, with_lse = pc
+    dev = _dev()
+    H, Hkv, D = 4, 2, 128
+    flags = {"full": 0, "top_left": CAUSAL, "bottom_right": CAUSAL | BOTTOM_RIGHT}[align]
+    packed, seqs = _packed_d(align, dtype, dev, H, Hkv, D, window=window, dlse_seed=161 if with_lse else None)
+    plan = _fa2_lib.varlen_plan(packed["q"], packed["k"], max(PACKED_Q), max(PACKED_K), len(PACKED_Q), flags=flags, window_left=window[0], window_right=window[1])
+    assert plan.kernel == _fa2_lib.FA2_KERNEL_HIP_VARLEN, plan.as_dict()
+    dlse = None
+    if with_lse:
+        dlse = torch.cat([s["dlse"][0] if s is not None else torch.zeros((H, nq), device=dev) for s, nq in zip(seqs, PACKED_Q)], dim=1)      # [H, total_q]
+    o, dq, dk, dv = packed_call(packed, H, Hkv, D, flags, window=window, dlse=dlse)
+    fails = _check_packed("packed %s%s%s %s" % (align, " w%d" % window[0] if window[0] >= 0 else "", " lse" if with_lse else "", _dt(dtype)), seqs, dtype, o, dq, dk, dv)
+    assert fails == [], fails
+
+
+MASK_D = [("bool_broadcast", 2, 3, 300, 700, False), ("bool_per_head", 2, 3, 300, 700, False), ("f32_additive", 2, 3, 300, 700, False), ("bool_broadcast", 1, 2, 1100, 1984, True),
+          ("bool_per_head_lse", 2, 3, 300, 700, False)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("m", MASK_D, ids=lambda m: "%s-%dx%dx%dx%d%s" % (m[0], m[1], m[2], m[3], m[4], "-ws" if m[5] else ""))
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_masked_backward_resolves_the_first_and_last_kept_key(m, dtype):
+    """fa2_bwd_bias / fa2_bwd_bias_ws under a bool keep mask (broadcast over the heads, or one per head) and an additive f32 mask (-inf where the same
+    pattern drops a key, N(0, 1/4) elsewhere): the targets are each row's first and last kept key.  The mask is a random half of a band of 101 keys that
+    moves along the rows — of a random half of ALL keys the first kept one is key 0 or 1 for three rows in four, and no element of dK_0 resolves one of
+    150 summands (the builder refuses it: the power condition)."""
+    kind, B, H, Nq, Nkv, ws = m
+    dev = _dev()
+    D = 128
+    inp, mask, bias_kind, dlse = mask_d_inputs(m, dtype, dev)
+    plan = _fa2_lib.fwd_plan(inp["q"], inp["k"], False, bias_kind=bias_kind)
+    assert plan.kernel == _fa2_lib.FA2_KERNEL_HIP_BIAS, plan.as_dict()
+    need = _fa2_lib.load().fa2_bwd_bias_workspace_bytes(_code(dtype), B, H, Nq, Nkv, D, 0) if ws else 0
+    assert (need > 0) == ws
+    o, dq, dk, dv = bhnd_call(inp, bias=mask, ws_bytes=need, dlse=dlse)
+    fails = _report("mask %s%s %s" % (kind, " ws" if ws else "", _dt(dtype)), *kp.check_two_pointer(inp, dtype, o, dq, dk, dv))
+    assert fails == [], fails
+
+
+def mask_d_inputs(m, dtype, dev=None, B=None, H=None):
+    kind, B0, H0, Nq, Nkv, ws = m
+    B, H, D = B or B0, H or H0, 128
+    gen = torch.Generator().manual_seed(171)
+    keep = (torch.rand((B, 1 if kind == "bool_broadcast" else H, Nq, Nkv), generator=gen) < 0.5).to(dev or "cpu") & _band_of(Nq, Nkv, window=(70, 30), q_offset=(Nkv - Nq) // 2, device=dev)[2]
+    pa, pb = kp.two_pointer_maps(None, None, Nkv, 0, keep=keep)
+    if kind == "f32_additive":
+        mask = torch.where(keep, (torch.randn(keep.shape, generator=gen) * 0.5).to(dev), torch.full(keep.shape, float("-inf"), device=dev)).float()
+        kw, bias_kind = dict(bias=mask), _fa2_lib.FA2_BIAS_F32
+    else:
+        mask, kw, bias_kind = keep, dict(visible=keep), _fa2_lib.FA2_BIAS_BOOL
+    dlse = _dlse_of(B, H, Nq, 173, dev) if kind.endswith("_lse") else None
+    return kp.two_pointer_inputs(B, H, H, Nq, Nkv, D, dtype, pa, pb, seed=SEED_D + 40, device=dev, dlse=dlse, **kw), mask, bias_kind, dlse
+
+
+DROP_P, DROP_SEED = 0.25, 1234
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_lse", [False, True], ids=["plain", "lse"])
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_dropout_backward_regenerates_the_forwards_mask(dtype, with_lse):
+    """fa2_bwd_dropout at p = 0.25 (B1 H2 300 x 700, band (70, 30) at offset 200: without a band three rows in four have key 0 as their first kept key,
+    and the builder refuses such a fan-in): the targets are each row's first and last visible key that the library's host keep mask keeps,
+    P kept / (1 - p_eff) multiplies V and dO.  A backward that regenerates another mask (transposed, another head's) drops a target."""
+    dev = _dev()
+    inp, win, dlse = dropout_d_inputs(dtype, with_lse, dev)
+    o, dq, dk, dv = bhnd_call(inp, window=win, dropout=(DROP_P, DROP_SEED), dlse=dlse)
+    fails = _report("dropout%s %s" % (" lse" if with_lse else "", _dt(dtype)), *kp.check_two_pointer(inp, dtype, o, dq, dk, dv))
+    assert fails == [], fails
+
+
+def dropout_d_inputs(dtype, with_lse, dev=None):
+    B, H, Nq, Nkv, D = 1, 2, 300, 700, 128
+    win = (70, 30, 200)
+    vis = _band_of(Nq, Nkv, window=win[:2], q_offset=win[2], device=dev)[2]
+    kept = dropout_keep_mask(DROP_SEED, DROP_P, B, H, Nq, Nkv).to(dev or "cpu")
+    pa, pb = kp.two_pointer_maps(None, None, Nkv, 0, keep=kept & vis)
+    dlse = _dlse_of(B, H, Nq, 175, dev) if with_lse else None
+    inp = kp.two_pointer_inputs(B, H, H, Nq, Nkv, D, dtype, pa, pb, seed=SEED_D + 50, device=dev, visible=vis, kept=kept, rs=1.0 / (1.0 - round(DROP_P * 65536) / 65536.0), dlse=dlse)
+    return inp, win, dlse
+
+
+def _slopes(H, width, device):
+    """Geometric slopes 3 / width, halved from head to head: slope * width of order 1 (ALiBi balance: the nearer target wins by exp(slope * the difference of
+    the two distances), and the farther one must keep its power: the builder checks it)."""
+    return (torch.tensor([2.0 ** -(h % 4) for h in range(H)], dtype=torch.float32) * (3.0 / width)).to(device or "cpu")
+
+
+SCOREMOD_D = [("softcap", (-1, -1), 0, False, False), ("slopes", (70, 30), 5, False, False), ("both", (70, 30), 5, False, False), ("both_lse", (60, 40), 200, False, True)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sm", SCOREMOD_D, ids=lambda sm: sm[0])
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_scoremod_backward_carries_the_cap_and_the_slopes(dtype, sm):
+    """fa2_bwd_scoremod (B2 H4 Hkv2, 700 x 900): soft-capping at 1.5 times the targets' score (tanh' = 0.6 on the targets: a backward without 1 - tanh^2 is
+    1.6 times off on every pair), ALiBi slopes of 1 / width .. 1 / (8 width) under a band (P_a != P_b; a distance off by one moves the ratio by e^slope)."""
+    kind, window, off, causal, with_lse = sm
+    dev = _dev()
+    inp, cap, slopes, dlse = scoremod_d_inputs(sm, dtype, dev)
+    o, dq, dk, dv = bhnd_call(inp, causal=causal, window=(window[0], window[1], off), smod=(cap, slopes), dlse=dlse)
+    fails = _report("scoremod %s %s" % (kind, _dt(dtype)), *kp.check_two_pointer(inp, dtype, o, dq, dk, dv))
+    assert fails == [], fails
+
+
+def scoremod_d_inputs(sm, dtype, dev=None, B=2):
+    kind, window, off, causal, with_lse = sm
+    H, Hkv, Nq, Nkv, D = 4, 2, 700, 900, 128
+    lo, hi, vis = _band_of(Nq, Nkv, causal=causal, window=window, q_offset=off, device=dev)
+    pa, pb = kp.two_pointer_maps(lo, hi, Nkv, seed=SEED_D + 60, kind="edge")
+    width = 101 if window[0] >= 0 else Nkv
+    slopes = _slopes(H, width, dev) if kind != "softcap" else None
+    cap = 0.0 if kind == "slopes" else 1.5 * 4.0 * D * D ** -0.5          # (the targets score about scale c D at c = 4)
+    dlse = _dlse_of(B, H, Nq, 177, dev) if with_lse else None
+    inp = kp.two_pointer_inputs(B, H, Hkv, Nq, Nkv, D, dtype, pa, pb, seed=SEED_D + 61, device=dev, visible=vis, softcap=cap,
+                                bias=alibi_bias(slopes, Nq, Nkv, off) if slopes is not None else None, dlse=dlse, per_query_head=True)
+    return inp, cap, slopes, dlse
+
+
+def tiny_p_inputs(softcap, dtype=F16, device=None, N=192, D=128, i0=148, j0=150, c=4.0):
+    """One (row, key) pair whose P is below half of fp16's smallest subnormal, alone under its key.  Every row points at its own key (q_i = c K_i, K of +-1:
+    P_ii = 1 - 1e-19), row j0 at key j0 - 1; k_j0 is K_i0 with m signs flipped, so row i0 scores it scale c 2 m below its own key: P = 1.0e-8 (2^-26.5) with m = 26, and
+    with m = 33 under a cap of 1.5 times the own score.  dO_i0 = 2 (v_j0 - v_i0) makes dP - delta ~ 500, so dS / scale is 5e-6, some 80 fp16 subnormal
+    steps, and dK_j0 = scale dS q_i0 is 2e-6 per element.  Under the band (3, 3) six other rows see key j0, each with P ~ e^-45: dK_j0 is that one pair."""
+    g = torch.Generator().manual_seed(191)
+    scale = D ** -0.5
+    k = torch.where(torch.rand((1, 1, N, D), generator=g) < 0.5, -1.0, 1.0)
+    m = 33 if softcap else 26
+    k[0, 0, j0] = k[0, 0, i0]
+    k[0, 0, j0, :m] *= -1.0
+    q = c * k
+    q[0, 0, j0] = q[0, 0, j0 - 1]                  # (row j0 points at its neighbour's key: no row puts weight on key j0)
+    v = torch.randn((1, 1, N, D), generator=g)
+    do = torch.randn((1, 1, N, D), generator=g)
+    do[0, 0, i0] = 2.0 * (v[0, 0, j0] - v[0, 0, i0])
+    q, k, v, do = (t.to(dtype).to(device or "cpu") for t in (q, k, v, do))
+    vis = _band_of(N, N, window=(3, 3), device=device)[2]
+    ref = kp.dense64(q, k, v, scale, keep=vis, do=do, softcap=softcap)
+    return dict(q=q, k=k, v=v, do=do, scale=scale, ref=ref, Hkv=1, per_query_head=True, i0=i0, j0=j0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", ["window", "scoremod"])
+def test_pair_pass_keeps_a_pair_whose_p_is_below_fp16(family):
+    """The reduced form of the class-D failure of fa2_bwd_scoremod in fp16: the wave-pair dK / dV pass (head dims 65..128) handed round16(P) from its P
+    wave to its dS wave, so a pair with P below 2^-25 gave dK nothing, and a key resting on one such pair came back 0 against a true 2.2e-7.  The pass now
+    hands over round16(2^14 P).  Here dK of key j0 is one pair of P = 1e-8: the reference alone puts it above 4 of its bars, so a 0 fails; fa2_bwd_window
+    runs the plain form of the pass, fa2_bwd_scoremod (soft-capping) the one that carries P (1 - tanh^2)."""
+    dev = _dev()
+    cap = 1.5 * 4.0 * 128 * 128 ** -0.5 if family == "scoremod" else 0.0
+    inp = tiny_p_inputs(cap, F16, dev)
+    ref, i0, j0 = inp["ref"], inp["i0"], inp["j0"]
+    bar = kp.dk_bar_d(ref, F16)[0, 0, j0]
+    assert float((ref["dk"][0, 0, j0].abs() / bar).min()) >= kp.POWER_D, "the inputs do not resolve the pair"
+    plan = _fa2_lib.window_plan(inp["q"], inp["k"], False, 3, 3, 0)
+    assert plan.kernel == _fa2_lib.FA2_KERNEL_HIP_WINDOW, plan.as_dict()
+    o, dq, dk, dv = bhnd_call(inp, window=(3, 3, 0), smod=(cap, None) if cap else None)
+    fails = _report("tiny P %s f16" % family, *kp.check_two_pointer(inp, F16, o, dq, dk, dv))
+    assert fails == [], fails
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("twin", ["dropout", "scoremod"])
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_packed_twins_of_dropout_and_scoremod(dtype, twin):
+    """fa2_bwd_varlen_dropout (the mask is keyed by the sequence and the positions inside it) and fa2_bwd_varlen_scoremod (soft-capping and slopes [H], the
+    distances counted inside the sequence, bottom-right) on the packed lengths."""
+    dev = _dev()
+    H, Hkv, D = 4, 2, 128
+    align, flags = "bottom_right", CAUSAL | BOTTOM_RIGHT
+    window = (40, 0)          # (a band: of all keys the first kept one is key 0 for most rows, too many for one dK element; slopes 3 / 101 .. 3 / 808 on distances up to 40)
+    dropout = (DROP_P, DROP_SEED) if twin == "dropout" else None
+    smod = (1.5 * 4.0 * D * D ** -0.5, _slopes(H, 101, dev)) if twin == "scoremod" else None
+    packed, seqs = _packed_d(align, dtype, dev, H, Hkv, D, window=window, dropout=dropout, smod=smod)
+    o, dq, dk, dv = packed_call(packed, H, Hkv, D, flags, window=window, dropout=dropout, smod=smod)
+    fails = _check_packed("packed %s %s" % (twin, _dt(dtype)), seqs, dtype, o, dq, dk, dv)
     assert fails == [], fails
