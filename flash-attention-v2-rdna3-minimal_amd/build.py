@@ -58,6 +58,10 @@ UNITS = [
     ("scoremod_hip_bf16", "scoremod_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("varlen_scoremod_hip_f16", "varlen_scoremod_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("varlen_scoremod_hip_bf16", "varlen_scoremod_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("prefill_hip_f16", "prefill_hip.cpp", ["-DFA2_TU_BF16=0"]),                          # chunked prefill against a KV cache: forward only
+    ("prefill_hip_bf16", "prefill_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("prefill_scoremod_hip_f16", "prefill_scoremod_hip.cpp", ["-DFA2_TU_BF16=0"]),
+    ("prefill_scoremod_hip_bf16", "prefill_scoremod_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("merge_hip", "merge_hip.cpp", []),          # both dtypes in one unit
     ("decode_hip_f16", "decode_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("decode_hip_bf16", "decode_hip.cpp", ["-DFA2_TU_BF16=1"]),
@@ -73,7 +77,7 @@ FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")
 GENERATORS = [os.path.join("gen", "fwd_d128_gen.py"), os.path.join("gen", "fwd_m16_gen.py"), os.path.join("gen", "fwd_m16_d256_gen.py"), os.path.join("gen", "bwd_d128_gen.py"),
               os.path.join("gen", "bwd_dq_m16_gen.py"), os.path.join("gen", "bwd_dkv_m16_gen.py")]
-HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_kvappend.hip.h", "fa2_rotary.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
+HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_kvappend.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
            os.path.join(INCLUDE, "fa2_gfx950.h"), os.path.join("gen", "isa.py"), os.path.join("gen", "sched.py"), os.path.join("gen", "gen_driver.py")] + GENERATORS
 
 HIPCC_FLAGS = [

@@ -10,6 +10,7 @@
 // The families' kernels are non-causal instantiations: host.cpp folds the causal flag into the window (right = 0) before it gets here; the packed forms
 // are launched exactly like the dense ones (the host passes the stated maximum lengths as Nq / Nkv, which size the grids).
 // No trimmed instantiations, no KV-split, no hand-scheduled bodies: every head dim runs the full kernel of its padded head dim.
+// FA2_FAMILY_FWD_ONLY = 1 (prefill_hip.cpp, prefill_scoremod_hip.cpp: an inference call has no backward): the unit compiles and exports the forward alone.
 #ifndef FA2_FAMILY
 #error "define FA2_FAMILY (and the family's form macros) before including fa2_family_unit.h"
 #endif
@@ -21,14 +22,28 @@
 #define bwd_dkv_pair_kernel FA2_FAMILY_NAME(bwd_, FA2_FAMILY, _dkv_pair_kernel)
 #include "fa2_pass_launch.h"
 
-// The FA2_SMOD kernels take one further argument, the ScoreMod block (fa2_scoremod.h), which the launchers pass through.  Elsewhere both macros are empty.
-#if FA2_SMOD
-#define FA2_FAMILY_MORE_PARAMS , const fa2::ScoreMod& sm
-#define FA2_FAMILY_MORE_ARGS , sm
-#else
-#define FA2_FAMILY_MORE_PARAMS
-#define FA2_FAMILY_MORE_ARGS
+#ifndef FA2_FAMILY_FWD_ONLY
+#define FA2_FAMILY_FWD_ONLY 0
 #endif
+
+// The FA2_PAGED kernels take one further argument, the PagedKv block (fa2_prefill.h), and the FA2_SMOD kernels the ScoreMod block (fa2_scoremod.h), in this
+// order; the launchers pass them through.  Elsewhere the macros are empty.
+#if FA2_PAGED
+#define FA2_FAMILY_PAGED_PARAMS , const fa2::PagedKv& pg
+#define FA2_FAMILY_PAGED_ARGS , pg
+#else
+#define FA2_FAMILY_PAGED_PARAMS
+#define FA2_FAMILY_PAGED_ARGS
+#endif
+#if FA2_SMOD
+#define FA2_FAMILY_SMOD_PARAMS , const fa2::ScoreMod& sm
+#define FA2_FAMILY_SMOD_ARGS , sm
+#else
+#define FA2_FAMILY_SMOD_PARAMS
+#define FA2_FAMILY_SMOD_ARGS
+#endif
+#define FA2_FAMILY_MORE_PARAMS FA2_FAMILY_PAGED_PARAMS FA2_FAMILY_SMOD_PARAMS
+#define FA2_FAMILY_MORE_ARGS FA2_FAMILY_PAGED_ARGS FA2_FAMILY_SMOD_ARGS
 
 namespace {
 
@@ -36,10 +51,12 @@ template <int HD>
 int launch_fwd_hd(const fa2::FwdParams& p0, int rows, hipStream_t stream FA2_FAMILY_MORE_PARAMS) {
     fa2::FwdParams p = p0;
     p.nsplit = 0;
-    if constexpr (HD > 256) return launch_fwd_shape<HD, false, 4>(p, stream FA2_FAMILY_MORE_ARGS);
+    // (FA2_PAGED: 128-row workgroups at every head dim above 128 — the 256-row instantiation of head dim 256 spills to scratch memory, the 128-row one does not)
+    if constexpr (HD > (FA2_PAGED ? 128 : 256)) return launch_fwd_shape<HD, false, 4>(p, stream FA2_FAMILY_MORE_ARGS);
     else return rows == 128 ? launch_fwd_shape<HD, false, 4>(p, stream FA2_FAMILY_MORE_ARGS) : launch_fwd_shape<HD, false, 8>(p, stream FA2_FAMILY_MORE_ARGS);
 }
 
+#if !FA2_FAMILY_FWD_ONLY
 // The backward: dQ pass, then dK and dV — fused at head dims <= 64, wave pairs at 128, separate sweeps at 256, slabs at 512 (bwd_hip.cpp has the
 // reasons for each shape).  kv_group == 1: the operator expands grouped K / V and sums the gradients per group.
 template <int HD>
@@ -58,6 +75,7 @@ int launch_bwd_hd(const fa2::BwdParams& p0, hipStream_t stream FA2_FAMILY_MORE_P
         else return launch_dv_dk<HD, false, NW>(p, owners, stream FA2_FAMILY_MORE_ARGS);
     }
 }
+#endif
 
 }  // namespace
 
@@ -73,6 +91,7 @@ int FA2_DT(FA2_FAMILY_NAME(launch_fwd_, FA2_FAMILY, ))(int HD, const FwdParams& 
     }
 }
 
+#if !FA2_FAMILY_FWD_ONLY
 int FA2_DT(FA2_FAMILY_NAME(launch_bwd_, FA2_FAMILY, ))(int HD, const BwdParams& p, hipStream_t stream FA2_FAMILY_MORE_PARAMS) {
     switch (HD) {
         case 64: return launch_bwd_hd<64>(p, stream FA2_FAMILY_MORE_ARGS);
@@ -82,5 +101,6 @@ int FA2_DT(FA2_FAMILY_NAME(launch_bwd_, FA2_FAMILY, ))(int HD, const BwdParams& 
         default: return FA2_ERR_HEAD_DIM;
     }
 }
+#endif
 
 }  // namespace fa2

@@ -85,6 +85,21 @@
 #else
 #define FA2_SMOD_PARAM
 #endif
+// FA2_PAGED = 1 (prefill_hip.cpp / prefill_scoremod_hip.cpp only, on top of FA2_VARLEN = 1, forward only): chunked prefill against a KV cache (fa2_fwd_prefill).
+// The queries are packed as in a varlen call; a sequence's keys are the first cache_seqlens[s] slots of its cache, contiguous or paged, and K / V tiles are
+// staged through a buffer descriptor built per tile (paged_enter and PagedCursor below).  The cache's description travels in a further kernel argument.
+#ifndef FA2_PAGED
+#define FA2_PAGED 0
+#endif
+#if FA2_PAGED && (!FA2_VARLEN || FA2_DROP)
+#error "FA2_PAGED builds on the FA2_VARLEN blocks and does not combine with FA2_DROP"
+#endif
+#if FA2_PAGED
+#include "fa2_prefill.h"
+#define FA2_PAGED_PARAM , const PagedKv pg
+#else
+#define FA2_PAGED_PARAM
+#endif
 
 // ---- tuning knobs (A/B-tested on MI355X with tools/kbench.py; numbers at B2 H16 N4096 D128 fp16) ----
 #ifndef FA2_DEFER_THR        // skip the O rescale while the row max grew by <= this (log2 units); <0: always rescale.
@@ -223,7 +238,60 @@ __device__ __forceinline__ bool varlen_enter(FwdParams& p, Window& win, int s, i
 }
 #endif
 
-constexpr int kSplitRows = 256;          // rows of a split item (the 8-wave workgroup shape)
+#if FA2_PAGED
+// Chunked prefill against a KV cache (fa2_fwd_prefill; fa2_prefill.h).  The workgroup of sequence s takes its query rows from cu_seqlens_q as a packed call
+// does, its key count from cache_seqlens[s] clamped into [0, capacity], and the band's offset is always the bottom-right one: row i sits at position
+// Nkv_s - Nq_s + i.  The K / V base pointers stay at the pool: a tile's place is found per tile (PagedCursor).
+__device__ __forceinline__ bool paged_enter(FwdParams& p, const PagedKv& pg, Window& win, int s, int row0) {      // (s is workgroup-uniform: three scalar loads)
+    const int* cq = get_varlen(p).cu_q;
+    const int q_base = cq[s], Nq = cq[s + 1] - q_base;
+    if (row0 >= Nq) return true;
+    const int Nkv = prefill_clamp_len(pg.lens[s], pg.capacity_keys);
+    p.Nq = Nq; p.Nkv = Nkv;
+    win.off = Nkv - Nq;
+    p.q = (const uint16_t*)p.q + (int64_t)q_base * p.qs[2];
+    p.o = (uint16_t*)p.o + (int64_t)q_base * p.os[2];
+    p.lse += q_base;
+    return false;
+}
+// Where the next tile to stage lies.  K and V each walk the workgroup's tiles [t0, t0 + ntiles) once, in order, with a cursor of their own: the tile's
+// page slot, its first row inside the page and its valid rows are running counters (prefill_tile_next: no division per tile), the page id of the current
+// slot is a register and the one of the next slot is loaded when the current slot is entered — a wave-uniform scalar load at least one tile ahead of its
+// use.  Only the slots of [t0, t0 + ntiles) are ever read from the block table: pages below a window or beyond the causal edge of the workgroup's last
+// row are never addressed, and a workgroup that sees no key (ntiles = 0) stages its prologue tile through an empty descriptor (all zeros, all masked).
+struct PagedCursor { PrefillTile at; int key0, pid, pid_next, last_slot; };
+__device__ __forceinline__ PagedCursor paged_cursor(const PagedKv& pg, const int* bt_row, int s, int t0, int ntiles, int len) {
+    PagedCursor c;
+    c.at = prefill_tile(t0, len, pg.page_keys);
+    c.key0 = t0 * kKvTile;
+    c.last_slot = ntiles > 0 ? ((t0 + ntiles - 1) * kKvTile) / pg.page_keys : -1;
+    if (ntiles <= 0) c.at.rows = 0;
+    c.pid = !bt_row ? s : c.at.slot <= c.last_slot ? bt_row[c.at.slot] : 0;
+    c.pid_next = bt_row && c.at.slot + 1 <= c.last_slot ? bt_row[c.at.slot + 1] : 0;
+    return c;
+}
+__device__ __forceinline__ void paged_advance(PagedCursor& c, const PagedKv& pg, const int* bt_row, int len) {
+    const int slot0 = c.at.slot;
+    c.key0 += kKvTile;
+    prefill_tile_next(c.at, c.key0, len, pg.page_keys);
+    if (c.at.slot != slot0) {
+        c.pid = c.pid_next;
+        if (bt_row && c.at.slot + 1 <= c.last_slot) c.pid_next = bt_row[c.at.slot + 1];
+    }
+}
+// The buffer descriptor of the cursor's tile: base = pool + page id * page stride + row in page * pitch (64 bits; `head` already points at the K / V head
+// inside page 0), records = the tile's valid rows — rows at or beyond the sequence's length read zeros whatever the cache holds there.  The page id is
+// clamped into the pool.  Every input is wave-uniform; readfirstlane says so to the compiler, so that the buffer loads take the descriptor from SGPRs.
+__device__ __forceinline__ auto paged_rsrc(const uint16_t* head, const PagedCursor& c, const PagedKv& pg, int64_t page_stride, int64_t pitch, int D) {
+    const int pid = prefill_clamp_page(c.pid, pg.num_pages);
+    const uint64_t a = (uint64_t)(uintptr_t)(head + (int64_t)pid * page_stride + (int64_t)c.at.row * pitch);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    const uint32_t bytes = __builtin_amdgcn_readfirstlane(varlen_bytes(c.at.rows, pitch, D));
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), 0, bytes, 0x00020000);
+}
+#endif
+
+constexpr int kSplitRows = 256;         // rows of a split item (the 8-wave workgroup shape)
 constexpr int kMaxSplit = 8;
 
 // bytes of the KV-split workspace: partial O tiles + partial LSE rows
@@ -382,7 +450,7 @@ constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && 
 // computes only the tiles of its own 32 rows' range [tf_w, ntiles_w), tiles cut by the band's left or right edge are masked per lane (lim_lo, lim_hi)
 // and the tiles in between run the unmasked steady-state loop.  A row that sees no key ends with O = 0, lse = -inf (the BIAS kernels' convention).
 template <int HD, int HDV, bool BF16, bool CAUSAL, int NW, int QB, int BIAS = 0, int KSQ = HD / 16, int DTN = HDV / 32, bool RTD = false>
-__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP FA2_SMOD_PARAM) {
+__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP FA2_PAGED_PARAM FA2_SMOD_PARAM) {
 #if FA2_VARLEN
     FwdParams p = pk;         // (adjusted to the workgroup's sequence below: varlen_enter)
 #endif
@@ -433,7 +501,9 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     block_to_head_qblock<CAUSAL>(p, bid, bh, qblk);
     const int b = bh / p.H, h = bh % p.H;
     const int q0 = qblk * kRowsPerBlock;
-#if FA2_VARLEN
+#if FA2_PAGED
+    if (paged_enter(p, pg, win, b, q0)) return;   // b is the sequence; from here on p describes its queries and its key count (K / V: the whole cache)
+#elif FA2_VARLEN
     if (varlen_enter(p, win, b, q0)) return;      // b is the sequence (the batch strides are 0); from here on p describes that sequence alone
 #endif
     // this workgroup's KV range [kv_first, kv_first + nkv): everything, or a part's whole tiles
@@ -475,10 +545,16 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 
     // ---- K/V staging: buffer descriptors of this head's matrices (out-of-range rows read 0)
     const uint32_t k_rowb = (uint32_t)p.ks[2] * 2u, v_rowb = (uint32_t)p.vs[2] * 2u;
+#if FA2_PAGED
+    // (one descriptor per tile: load_k / load_v below.  p.ks[0] / p.vs[0] are the page strides)
+    const uint16_t* khead = (const uint16_t*)p.k + (h / p.kv_group) * p.ks[1];
+    const uint16_t* vhead = (const uint16_t*)p.v + (h / p.kv_group) * p.vs[1];
+#else
     const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + (h / p.kv_group) * p.ks[1] + (int64_t)kv_first * p.ks[2];
     const uint16_t* vbase = (const uint16_t*)p.v + b * p.vs[0] + (h / p.kv_group) * p.vs[1] + (int64_t)kv_first * p.vs[2];
     const auto krs = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, p.k_bytes - (uint32_t)kv_first * k_rowb, 0x00020000);
     const auto vrs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, p.v_bytes - (uint32_t)kv_first * v_rowb, 0x00020000);
+#endif
     uint32_t kg_off[NPASS], vg_off[VNPASS];  // per-lane byte offsets into the head matrix, tile 0
     int kw_off[NPASS], vw_off[VNPASS];       // per-lane LDS byte offsets inside a tile image
 #pragma unroll
@@ -862,8 +938,20 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         vd_off[i] = gv * 8 + vcol0 < p.D ? row * v_rowb + gv * 16 + vcol0 * 2 : kOobOffset;
     }
     u32x4 kreg[NPASS], vreg[VNPASS];
+#if FA2_PAGED
+    // load_k / load_v are called once per tile of [0, ntiles), in order, K ahead of V: each stages the tile ITS cursor stands on and moves on (`tile` is
+    // implied).  The descriptor is the tile's own, so the tile's byte offset is 0.
+    const int* bt_row = pg.bt ? pg.bt + (int64_t)b * pg.bts : nullptr;
+    PagedCursor kcur = paged_cursor(pg, bt_row, b, kv_first / kKvTile, ntiles, p.Nkv), vcur = kcur;
+#endif
     auto load_k = [&](int tile, int buf) __attribute__((always_inline)) {
+#if FA2_PAGED
+        const uint32_t soff = 0u;
+        const auto krs = paged_rsrc(khead, kcur, pg, p.ks[0], p.ks[2], p.D);
+        paged_advance(kcur, pg, bt_row, p.Nkv);
+#else
         const uint32_t soff = (uint32_t)tile * kKvTile * k_rowb;
+#endif
 #pragma unroll
         for (int i = 0; i < NPASS; ++i) {
             if constexpr (kDma) dma16_to_lds(krs, smem + buf * TILEB + (wave * 64 + kThreads * i) * 16, FA2_TILE_OFF(kd_off[i], soff));
@@ -871,7 +959,13 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         }
     };
     auto load_v = [&](int tile, int buf) __attribute__((always_inline)) {
+#if FA2_PAGED
+        const uint32_t soff = 0u;
+        const auto vrs = paged_rsrc(vhead, vcur, pg, p.vs[0], p.vs[2], p.D);
+        paged_advance(vcur, pg, bt_row, p.Nkv);
+#else
         const uint32_t soff = (uint32_t)tile * kKvTile * v_rowb;
+#endif
 #pragma unroll
         for (int i = 0; i < VNPASS; ++i) {
             if constexpr (kDma) dma16_to_lds(vrs, smem + VBASE + buf * VTILEB + (wave * 64 + kThreads * i) * 16, FA2_TILE_OFF(vd_off[i], soff));

@@ -15,6 +15,7 @@
 #include "fa2_bwd_kernel.hip.h"      // FwdParams / BwdParams (templates are only instantiated where a launcher names them)
 #include "fa2_decode.hip.h"          // DecodeParams, decode_part_range
 #include "fa2_kvappend.hip.h"        // KvAppendParams, kvappend_slot, the rotary arithmetic
+#include "fa2_prefill.h"             // PagedKv, prefill_tile
 
 #define FA2_HIDDEN __attribute__((visibility("hidden")))
 
@@ -228,6 +229,11 @@ FA2_FWD_SMOD_LAUNCHER(launch_fwd_scoremod)
 FA2_BWD_SMOD_LAUNCHER(launch_bwd_scoremod)
 FA2_FWD_SMOD_LAUNCHER(launch_fwd_varlen_scoremod)
 FA2_BWD_SMOD_LAUNCHER(launch_bwd_varlen_scoremod)
+// chunked prefill against a KV cache (prefill_hip.cpp, prefill_scoremod_hip.cpp; fa2_fwd_prefill): the PAGED forms of the packed forward kernels, forward
+// only, with the PagedKv block (fa2_prefill.h) as a further kernel argument; cu_seqlens_q in p.bias (set_varlen), the page strides in p.ks[0] / p.vs[0]
+FA2_LAUNCHER(launch_fwd_prefill, (int HD, const FwdParams& p, int rows, hipStream_t stream, const PagedKv& pg), (HD, p, rows, stream, pg))
+FA2_LAUNCHER(launch_fwd_prefill_scoremod, (int HD, const FwdParams& p, int rows, hipStream_t stream, const PagedKv& pg, const ScoreMod& sm),
+             (HD, p, rows, stream, pg, sm))
 // hand-scheduled backward, head dim exactly 128 (bwd_asm.cpp); same `parts`
 // neg_delta: the dQ pass writes -delta (the hand-scheduled dK/dV pass reads it as such; the HIP dK/dV passes read +delta)
 // kfold: the dK / dV body whose P side folds scale * log2(e) into its K fragments (option "fold"; host.cpp: bwd_folds)

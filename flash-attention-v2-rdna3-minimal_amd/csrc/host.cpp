@@ -1800,6 +1800,139 @@ int fa2_kvcache_append(int dtype, int cache_format, const void* k_new, const voi
                : fa2::launch_kvappend(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
 }
 
+// ---- chunked prefill against a KV cache: include/fa2_gfx950.h has the contract, csrc/fa2_prefill.h the tile arithmetic, prefill_hip.cpp /
+// prefill_scoremod_hip.cpp the kernels (the FA2_PAGED forms of the packed forward).  One call, described: the entry fills it by field name, the plan
+// query the sizes alone.  The checks run in decode's class order.
+struct PrefillCall : CacheDesc {
+    int dtype = 0, B = 0, H = 0, Hkv = 0, max_q = 0, D = 0;
+    const void* q = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    const int *cu_q = nullptr, *lens = nullptr;
+    const int64_t *qs = nullptr, *os = nullptr;      // {head, row}
+    int64_t lse_stride = 0;
+    float scale = 0.f;
+    int window_left = -1;
+    float softcap = 0.f;
+    const float* slopes = nullptr;
+    int64_t slope_stride = 0;
+    void* stream = nullptr;
+};
+
+// The sizes of a prefill call (shape, then head dim); *HD: the kernel head dim.
+static int prefill_check_shape(const PrefillCall& c, int* HD) {
+    if (c.B < 1 || c.H < 1 || c.Hkv < 1 || c.max_q < 1 || c.D < 1 || c.Hkv > c.H || c.H % c.Hkv != 0 || !cache_paging_ok(c)) return FA2_ERR_BAD_SHAPE;
+    if (c.capacity_keys() > 0x7fffffffLL - 64 || c.window_left < -1) return FA2_ERR_BAD_SHAPE;
+    // a sequence's offset len_s - Nq_s lies in [-max_seqlen_q, capacity_keys]
+    const int cap = (int)c.capacity_keys(), n = c.max_q > cap ? c.max_q : cap;
+    if (!fa2::window_args_ok(c.max_q, cap, c.window_left, 0, -n, true)) return FA2_ERR_BAD_SHAPE;
+    *HD = fa2_padded_head_dim(c.D);
+    if (*HD < 0 || (c.D & 7)) return FA2_ERR_HEAD_DIM;
+    return FA2_OK;
+}
+
+// rows per workgroup: the packed call's heuristic on (B, H, max_seqlen_q) and option "rows"; 128 above head dim 128 (fa2_family_unit.h)
+static int prefill_rows(const PrefillCall& c, int HD) {
+    fa2::FwdParams p{};
+    p.nbh = c.B * c.H; p.Nq = c.max_q; p.D = c.D;
+    return HD > 128 ? 128 : pick_rows(p);
+}
+
+int fa2_fwd_prefill_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    std::memset(plan, 0, sizeof(*plan));
+    PrefillCall c;
+    c.dtype = dtype; c.B = B; c.H = H; c.Hkv = Hkv; c.max_q = max_seqlen_q; c.D = D; c.capacity = capacity; c.page_size = page_size;
+    int HD = 0;
+    if (int rc = prefill_check_shape(c, &HD)) return rc;
+    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    if ((int64_t)B * H * ((max_seqlen_q + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
+    plan->kernel = FA2_KERNEL_HIP_PREFILL;
+    plan->contract = 0;
+    plan->rows = prefill_rows(c, HD);
+    plan->heads_main = B * H;
+    return FA2_OK;
+}
+
+int fa2_prefill_tile(int64_t len, int capacity, int page_size, int tile, int* page_slot, int* row_in_page, int* valid_rows) {
+    if (!page_slot || !row_in_page || !valid_rows) return FA2_ERR_NULL_POINTER;
+    CacheDesc c;
+    c.capacity = capacity; c.page_size = page_size;
+    if (!cache_paging_ok(c) || c.capacity_keys() > 0x7fffffffLL - 64) return FA2_ERR_BAD_SHAPE;
+    const int64_t cap = c.capacity_keys();
+    if (tile < 0 || tile >= (cap + fa2::kPrefillTile - 1) / fa2::kPrefillTile) return FA2_ERR_BAD_SHAPE;
+    const fa2::PrefillTile t = fa2::prefill_tile(tile, fa2::prefill_clamp_len(len, cap), fa2::prefill_page_keys(page_size, cap));
+    *page_slot = t.slot; *row_in_page = t.row; *valid_rows = t.rows;
+    return FA2_OK;
+}
+
+static int prefill_run(const PrefillCall& c) {
+    if (any_null({c.q, c.o, c.lse, c.cu_q, c.lens, c.qs, c.os}) || cache_null(c)) return FA2_ERR_NULL_POINTER;
+    int HD = 0;
+    // one tile's rows must stay below the byte offset that stands for "out of range" (kOobOffset), whatever else the pool spans
+    const auto tile_ok = [](const int64_t* s) { return s[2] <= 0 || (int64_t)fa2::kKvTile * s[2] * 2 < (int64_t)fa2::kOobOffset; };
+    if (c.lse_stride < 0 || c.slope_stride < 0 || !cache_extent_ok(c) || !tile_ok(c.ks) || !tile_ok(c.vs)) return FA2_ERR_BAD_SHAPE;
+    if (int rc = prefill_check_shape(c, &HD)) return rc;
+    const auto strides2_ok = [](const int64_t* s) { return s[0] % 8 == 0 && s[1] % 8 == 0 && s[1] > 0; };
+    if (!all_aligned16({c.q, c.o}) || !cache_aligned(c) ||
+        ((reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.cu_q) | reinterpret_cast<uintptr_t>(c.lens) |
+          reinterpret_cast<uintptr_t>(c.slopes)) & 3u) || !strides2_ok(c.qs) || !strides2_ok(c.os))
+        return FA2_ERR_ALIGNMENT;
+    if ((c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) || c.format != FA2_CACHE_16BIT || !cache_format_ok(c)) return FA2_ERR_DTYPE;
+    if (!std::isfinite(c.scale)) return FA2_ERR_SCALE;
+    if (!fa2::softcap_ok(c.softcap)) return FA2_ERR_SOFTCAP;
+    if ((int64_t)c.B * c.H * ((c.max_q + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
+
+    fa2::FwdParams p{};
+    const bool paged = c.page_size > 0;
+    const int64_t cap = c.capacity_keys();
+    p.q = c.q; p.k = c.k; p.v = c.v; p.o = c.o; p.lse = c.lse;
+    p.B = c.B; p.H = c.H; p.Nq = c.max_q; p.Nkv = (int)cap; p.D = c.D;
+    p.qs[0] = 0; p.qs[1] = c.qs[0]; p.qs[2] = c.qs[1];
+    p.os[0] = 0; p.os[1] = c.os[0]; p.os[2] = c.os[1];
+    for (int i = 0; i < 3; ++i) { p.ks[i] = c.ks[i]; p.vs[i] = c.vs[i]; }      // [0]: the page (contiguous: batch) stride, read by the PAGED kernels as such
+    p.ls[0] = 0; p.ls[1] = c.lse_stride;
+    p.c = std::fabs(c.scale) * 1.4426950408889634f;
+    if (p.c < 1e-30f) p.c = 1e-30f;                  // (scale == 0: fwd_validate has the reason)
+    p.negate_q = c.scale < 0.f;
+    p.nqblk = (c.max_q + kFwdRows - 1) / kFwdRows;
+    p.nbh = c.B * c.H;
+    p.exact_scale = 1;
+    p.persist = 1;
+    p.kv_group = c.H / c.Hkv;
+    fa2::Window w;
+    w.left = c.window_left; w.right = 0; w.off = 1;   // decode's mask: causal, bottom-right (the kernels take the offset per sequence)
+    fa2::set_window(p, w);
+    fa2::set_varlen(p, c.cu_q, (const int*)nullptr);
+    fa2::PagedKv pg;
+    pg.lens = c.lens;
+    pg.bt = paged ? c.block_table : nullptr;
+    pg.bts = paged ? c.bts : 0;
+    pg.page_keys = fa2::prefill_page_keys(c.page_size, cap);
+    pg.num_pages = paged ? c.num_pages : c.B;         // contiguous: page id = the sequence
+    pg.capacity_keys = (int)cap;
+    const int rows = prefill_rows(c, HD);
+    const bool bf16 = c.dtype == FA2_DTYPE_BF16;
+    hipStream_t const stream = (hipStream_t)c.stream;
+    if (c.softcap > 0.f || c.slopes)
+        return fa2::launch_fwd_prefill_scoremod(bf16, HD, p, rows, stream, pg, fa2::make_scoremod(c.softcap, c.scale, c.slopes, c.slopes ? c.slope_stride : 0));
+    return fa2::launch_fwd_prefill(bf16, HD, p, rows, stream, pg);
+}
+
+int fa2_fwd_prefill(int dtype, int cache_format, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cu_seqlens_q,
+                    const int* cache_seqlens, const int* block_table, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size,
+                    int num_pages, const int64_t q_strides[2], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[2],
+                    int64_t lse_stride, int64_t block_table_stride, float scale, int window_left, float softcap, const float* alibi_slopes,
+                    int64_t alibi_stride, void* hip_stream) {
+    PrefillCall c;
+    c.dtype = dtype; c.format = cache_format; c.B = B; c.H = H; c.Hkv = Hkv; c.max_q = max_seqlen_q; c.D = D;
+    c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    c.q = q; c.k = k_cache; c.v = v_cache; c.o = o; c.lse = lse; c.cu_q = cu_seqlens_q; c.lens = cache_seqlens; c.block_table = block_table;
+    c.qs = q_strides; c.ks = k_strides; c.vs = v_strides; c.os = o_strides; c.lse_stride = lse_stride; c.bts = block_table_stride;
+    c.scale = scale; c.window_left = window_left; c.softcap = softcap; c.slopes = alibi_slopes; c.slope_stride = alibi_stride; c.stream = hip_stream;
+    return prefill_run(c);
+}
+
 int fa2_fwd_f16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_F16, FA2_FWD_PASS, hip_stream); }
 int fa2_fwd_bf16(FA2_FWD_ARGS(), void* hip_stream) { return fa2_fwd(FA2_DTYPE_BF16, FA2_FWD_PASS, hip_stream); }
 int fa2_bwd_f16(FA2_BWD_ARGS(), void* hip_stream) { return fa2_bwd(FA2_DTYPE_F16, FA2_BWD_PASS, hip_stream); }

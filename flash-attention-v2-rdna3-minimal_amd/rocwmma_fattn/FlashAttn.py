@@ -23,7 +23,7 @@ import torch
 
 from . import _fa2_lib
 
-__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention"]
+__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill"]
 
 
 class _FlashAttnWmma:
@@ -1366,6 +1366,106 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
             rc = lib.fa2_fwd_decode(*head, *tail)
     _fa2_lib.check(rc)
     return (o, lse * _LN2) if return_lse else o
+
+
+def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, max_seqlen_q=None, scale=None, window=None, softcap=0.0,
+                            alibi_slopes=None, return_lse=False, k_descale=None, v_descale=None):
+    """Chunked prefill against a KV cache: many query rows per sequence (packed, as flash_attention_varlen's) against the cache kvcache_append writes and
+    flash_attention_decode reads — a prompt whose prefix sits in cached pages, a prompt processed in chunks, a continuous-batching step that mixes
+    prefill chunks with decode rows (other libraries: flash_attn_varlen_func(..., block_table=), flash_attn_with_kvcache with a long seqlen_q).
+    q [total_q, H, D] fp16 / bf16; cu_seqlens_q int32 [B + 1] on q's device: sequence s owns the rows [cu[s], cu[s+1]), Nq_s may be 0, 1 or thousands.
+    k_cache / v_cache: flash_attention_decode's two 16-bit layouts — [B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] with block_table int32
+    [B, max_pages], page_size a multiple of 64 (a pool may exceed 4 GiB).  Strided views are fine; a cache that is not addressable raises.
+    cache_seqlens: int32 [B] on q's device, the valid keys of each sequence INCLUDING its Nq_s new tokens (the caller has written their K / V, with
+    kvcache_append or otherwise).  The host never reads it or the block table, and no maximum key length is asked for: the call can be captured in
+    a graph and replayed after lengths, table and cache contents changed in place.
+    max_seqlen_q: a host int >= every Nq_s; it sizes the grid.  None computes it from cu_seqlens_q, which is a device-to-host SYNCHRONISATION (and
+    cannot be captured) — pass it in a hot loop.  A sequence longer than the stated maximum is the caller's error: its extra rows are not computed.
+    Masking is decode's, bottom-right causal per sequence: row i of sequence s sits at position len_s - Nq_s + i and sees the keys j <= that position;
+    window = None, an int W or (left, right): only `left` acts (j >= pos - left).  softcap / alibi_slopes (float32 [H] or [B, H]) as in
+    flash_attention_decode, positions as above.  Rows at a negative position (Nq_s > len_s) return zeros and lse = -inf.  Keys at or beyond len_s and
+    unused pages contribute nothing whatever they hold; lengths and page ids are clamped into the cache in-kernel (a wrong one gives a wrong answer,
+    never an out-of-bounds read); a page that holds no key a workgroup's rows see is never addressed, nor its block-table entry read.
+    Returns o [total_q, H, D]; with return_lse=True also lse f32 [H, total_q] in natural-log units (merge_attention combines such pairs).
+    Inference only.  Head dims up to 512; one that is no multiple of 8 is zero-padded — q AND both caches, i.e. copies of the caches.
+    float8_e4m3fn caches and k_descale / v_descale raise ValueError: 16-bit caches only.  C-ABI fa2_fwd_prefill."""
+    who = "flash_attention_prefill"
+    if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cu_seqlens_q, cache_seqlens)) or q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("fa2: %s takes q [total_q, H, D], 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] with a "
+                         "block_table), cu_seqlens_q and cache_seqlens" % who)
+    if torch.is_grad_enabled() and (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad):
+        raise ValueError("fa2: %s is inference only (an input requires grad); flash_attention_varlen on packed keys is differentiable" % who)
+    if _cache_format(who, q, k_cache, v_cache, None, None) or k_descale is not None or v_descale is not None:
+        raise ValueError("fa2: %s serves 16-bit caches only (fp16 / bf16, q's dtype): float8_e4m3fn caches and k_descale / v_descale are "
+                         "flash_attention_decode's" % who)
+    total_q, H, D = q.shape
+    Hkv = k_cache.shape[2]
+    if v_cache.shape != k_cache.shape or k_cache.shape[3] != D:
+        raise ValueError("fa2: inconsistent q / k_cache / v_cache shapes %s %s %s" % (tuple(q.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
+    _check_groups(H, Hkv)
+    if D < 1 or D > _MAX_HEAD_DIM:
+        raise ValueError("fa2: %s serves head dims 1 .. %d, got %d" % (who, _MAX_HEAD_DIM, D))
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous():
+        raise ValueError("fa2: cu_seqlens_q must be a contiguous 1-D int32 tensor of B + 1 >= 2 row offsets, got %s %s" % (cu_seqlens_q.dtype, tuple(cu_seqlens_q.shape)))
+    B = cu_seqlens_q.numel() - 1
+    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous():
+        raise ValueError("fa2: cache_seqlens must be a contiguous int32 tensor of shape [B] = [%d] (cu_seqlens_q has B + 1 entries), got %s %s"
+                         % (B, cache_seqlens.dtype, tuple(cache_seqlens.shape)))
+    if block_table is None:
+        if k_cache.shape[0] != B:
+            raise ValueError("fa2: a contiguous cache is [B, Nmax, Hkv, D] with B = %d sequences, got %s (a paged cache needs its block_table)" % (B, tuple(k_cache.shape)))
+        capacity, page_size, num_pages = k_cache.shape[1], 0, 0
+    else:
+        if not torch.is_tensor(block_table) or block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != B or \
+                block_table.shape[1] < 1 or block_table.stride(1) != 1:
+            raise ValueError("fa2: block_table must be int32 [B, max_pages] with B = %d sequences and contiguous rows, got %s"
+                             % (B, "%s %s" % (block_table.dtype, tuple(block_table.shape)) if torch.is_tensor(block_table) else repr(block_table)))
+        capacity, page_size, num_pages = block_table.shape[1], k_cache.shape[1], k_cache.shape[0]
+        if page_size < 64 or page_size % 64:
+            raise ValueError("fa2: the page size of a paged cache (k_cache.shape[1]) must be a multiple of 64, got %d" % page_size)
+        if num_pages < 1:
+            raise ValueError("fa2: a paged cache needs at least one page")
+    if capacity < 1:
+        raise ValueError("fa2: the cache has no key slots")
+    if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0):
+        raise ValueError("fa2: max_seqlen_q is None or a non-negative int, got %r" % (max_seqlen_q,))
+    window_left = _fa2_lib.parse_window(window)[0]
+    scoremod = _parse_scoremod(softcap, alibi_slopes, q, H, B)
+    aux = (cu_seqlens_q, cache_seqlens) if block_table is None else (cu_seqlens_q, cache_seqlens, block_table)
+    if not all(t.is_cuda for t in (q, k_cache, v_cache) + aux):
+        raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on a ROCm device (no CPU path in this operator)")
+    if any(t.device != q.device for t in (k_cache, v_cache) + aux):
+        raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on the same device")
+    d_pad = -D % 8
+    if d_pad:
+        q, k_cache, v_cache = (torch.nn.functional.pad(t, (0, d_pad)) for t in (q, k_cache, v_cache))
+    if not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
+        raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
+    q = _packed_ready(q)
+    if max_seqlen_q is None:
+        max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max())
+    if scale is None:
+        scale = D ** -0.5
+    o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
+    if total_q and max_seqlen_q > 0:
+        lib = _fa2_lib.load()
+        code = _fa2_lib.FA2_DTYPE_F16 if q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+        dev = q.device.index if q.device.index is not None else _current_device()
+        s3 = _fa2_lib.strides3
+        with torch.cuda.device(dev):
+            rc = lib.fa2_fwd_prefill(code, _fa2_lib.FA2_CACHE_16BIT, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(),
+                                     cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(), None if block_table is None else block_table.data_ptr(),
+                                     B, H, Hkv, int(max_seqlen_q), D + d_pad, capacity, page_size, num_pages, _s2(q),
+                                     s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)), s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)),
+                                     _s2(o), lse.stride(0), 0 if block_table is None else block_table.stride(0), float(scale), window_left,
+                                     *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), _raw_stream(dev))
+        _fa2_lib.check(rc)
+    elif total_q:                  # (a stated maximum of 0: no row is computed)
+        o.zero_()
+        lse.fill_(float("-inf"))
+    out = o[..., :D] if d_pad else o
+    return (out, lse * _LN2) if return_lse else out
 
 
 SOFTCAP_MESSAGE = "fa2: softcap must be 0 (off) or a finite positive number (a normal float32: >= 1.18e-38)"

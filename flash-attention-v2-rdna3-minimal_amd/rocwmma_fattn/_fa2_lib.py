@@ -54,6 +54,7 @@ class DecodePlan(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FA2_KERNEL_HIP_PREFILL = 8                                                                              # fa2_fwd_prefill_plan's kernel (an enumerator in the header)
 FA2_KERNEL_HIP_DECODE = 7                                                                               # fa2_decode_plan_t.kernel (an enumerator in the header)
 FA2_BWD_KERNEL_HIP, FA2_BWD_KERNEL_ASM, FA2_BWD_KERNEL_SHORT = 1, 2, 3                                  # fa2_bwd_plan_t.dq_kernel / .dkv_kernel
 FA2_BIAS_FORM_SCALAR, FA2_BIAS_FORM_VEC4, FA2_BIAS_FORM_TILE, FA2_BIAS_FORM_TILE_DMA, FA2_BIAS_FORM_ROW = 0, 1, 2, 3, 4     # fa2_fwd_bias_form
@@ -170,6 +171,12 @@ SYMBOLS = {
     "fa2_kvcache_append": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 7 + [_i64p] * 4 + [ctypes.c_int64] +
                            [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [_i64p] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_int64, ctypes.c_int] +
                            [ctypes.c_void_p] * 2 + [_i64p, ctypes.c_void_p]),
+    # chunked prefill against a KV cache: dtype cache_format, q k_cache v_cache o lse cu_seqlens_q cache_seqlens block_table, B H Hkv max_seqlen_q D capacity
+    # page_size num_pages, q k v o strides, the lse and block-table row strides, scale, window_left, softcap slopes slope-stride, stream
+    "fa2_fwd_prefill": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8 + [ctypes.c_int] * 8 + [_i64p] * 4 + [ctypes.c_int64] * 2 +
+                        [ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "fa2_fwd_prefill_plan": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(FwdPlan)]),
+    "fa2_prefill_tile": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 3),
     "fa2_kvappend_slot": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "fa2_rotary_eval": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p]),
@@ -408,6 +415,21 @@ def kvappend_slot(length, capacity_keys, Nnew, i):
     pos = ctypes.c_int64()
     check(load().fa2_kvappend_slot(int(length), int(capacity_keys), int(Nnew), int(i), ctypes.byref(pos)))
     return pos.value
+
+
+def prefill_plan(dtype, B, H, Hkv, max_seqlen_q, D, capacity, page_size=0):
+    """fa2_fwd_prefill_plan: the kernel, the contract and the rows per workgroup of a prefill call (dtype: an FA2_DTYPE_* code)."""
+    plan = FwdPlan()
+    check(load().fa2_fwd_prefill_plan(int(dtype), int(B), int(H), int(Hkv), int(max_seqlen_q), int(D), int(capacity), int(page_size), ctypes.byref(plan)))
+    return plan.as_dict()
+
+
+def prefill_tile(length, capacity, page_size, tile):
+    """fa2_prefill_tile -> (page_slot, row_in_page, valid_rows) of 64-key tile `tile` of a sequence of `length` keys (capacity: key slots, or block-table
+    entries per sequence when page_size > 0)."""
+    slot, row, rows = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_prefill_tile(int(length), int(capacity), int(page_size), int(tile), ctypes.byref(slot), ctypes.byref(row), ctypes.byref(rows)))
+    return slot.value, row.value, rows.value
 
 
 def strides3(a, b, c):

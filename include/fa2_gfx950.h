@@ -904,6 +904,57 @@ int fa2_fwd_varlen_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int 
                         const int64_t q_strides[2], const int64_t k_strides[2],
                         float scale, int flags, int window_left, int window_right, fa2_fwd_plan_t* plan);
 
+/* ---- Chunked prefill against a KV cache: packed queries (as fa2_fwd_varlen's) against the cache fa2_kvcache_append writes and fa2_fwd_decode reads,
+ * contiguous or paged, with every length and the block table read on the device — a prompt whose prefix already sits in cached pages, a prompt
+ * processed in chunks, a continuous-batching step that mixes prefill chunks with decode rows.  Inference only: there is no backward.
+ *   q, o            : [total_q, H, D] of `dtype`, element strides {head, row} as in fa2_fwd_varlen; lse f32 [H, total_q] (log2 units) with its head stride
+ *   cu_seqlens_q    : int32 [B + 1], device memory: sequence s owns the query rows [cu[s], cu[s+1]) — Nq_s may be 0, 1 or thousands.  NOT validated
+ *                     (fa2_fwd_varlen's contract: ascending, cu[0] >= 0, cu[B] <= the rows of q / o / lse, Nq_s <= max_seqlen_q).
+ *   max_seqlen_q    : host int >= every Nq_s; it sizes the grid B * H * ceil(max_seqlen_q / rows).  A longer sequence's rows beyond it are not computed.
+ *   cache_seqlens   : int32 [B], device memory: the valid keys of sequence s INCLUDING its Nq_s new tokens, whose K / V the caller has already written
+ *                     (fa2_kvcache_append or otherwise).  Clamped into [0, capacity_keys] by the kernel.
+ *   k_cache, v_cache: 16-bit caches of `dtype` in fa2_fwd_decode's two layouts: [B, capacity, Hkv, D] (page_size = 0, capacity = key slots per sequence)
+ *                     or a pool [num_pages, page_size, Hkv, D] under an int32 block_table [B, capacity] (page_size a multiple of 64, capacity =
+ *                     block-table entries per sequence).  Element strides {batch | page, head, row}.  cache_format must be FA2_CACHE_16BIT: e4m3 caches
+ *                     are FA2_ERR_DTYPE (the kernels stage K / V tiles by LDS-DMA, which cannot convert).
+ *   window_left     : -1 (none) or >= 0.  softcap, alibi_slopes (f32 [H] or [B, H], device memory), alibi_stride: fa2_fwd_decode_window's.
+ * Masking is decode's: bottom-right causal per sequence — row i of sequence s sits at key position len_s - Nq_s + i and attends the keys j with
+ * pos - window_left <= j <= pos.  Rows at a negative position (Nq_s > len_s) return zeros and lse = -inf.  The host reads neither cache_seqlens nor
+ * block_table, and no maximum key length is asked for: the capacity bounds the sweep and the device length ends it, so a call is captured in a graph once
+ * and replayed as lengths, tables and cache contents change in place.
+ * Safety (decode's rules): a length is clamped into [0, capacity_keys], a page id into [0, num_pages); keys at or beyond the length contribute nothing
+ * whatever the cache holds there (a tile's buffer descriptor ends at the sequence's last valid row: such rows read as zeros, and their scores are masked
+ * by position); no content of cache_seqlens or block_table moves a read outside the two cache allocations — a wrong value gives a wrong answer; a page
+ * that holds no key visible to any row of a workgroup (below a window, beyond the causal edge of the workgroup's last row) is never addressed and its
+ * block-table entry never read.
+ * Addressing: every 64-key tile is staged through a descriptor of its own whose base is formed in 64 bits (fa2_prefill_tile below has the arithmetic),
+ * so a pool may exceed 4 GiB and fa2_fwd_varlen's "K / V span below 2 GiB" rule does not apply: only one tile, 64 * row stride * 2 bytes, must stay
+ * below 2^31 (FA2_ERR_BAD_SHAPE).
+ * Checks, in fa2_fwd_decode's class order: null pointers (the block table of a paged call included); sizes (FA2_ERR_BAD_SHAPE: a size < 1, H % Hkv, a
+ * page_size that is negative or no multiple of 64, capacity_keys above 2^31 - 65, num_pages < 1 of a paged call, window_left < -1, a negative lse /
+ * slope stride, position sums that leave 32 bits, the tile rule above); head dim (FA2_ERR_HEAD_DIM: D a multiple of 8 up to 512); alignment (16-byte
+ * tensors, 4-byte lse / cu_seqlens_q / cache_seqlens / block_table / slopes, strides multiples of 8 with a positive row stride, a non-negative
+ * block-table stride); dtype and cache_format (FA2_ERR_DTYPE); scale; softcap (FA2_ERR_SOFTCAP); FA2_ERR_GRID.
+ * Kernels (FA2_KERNEL_HIP_PREFILL, contract 0): the packed kernels (FA2_KERNEL_HIP_VARLEN) with the key count from cache_seqlens and a per-tile
+ * descriptor; everything after the staging is shared, so the results equal fa2_fwd_varlen's (FA2_FLAG_CAUSAL | FA2_FLAG_BOTTOM_RIGHT, the same
+ * window; with softcap > 0 or slopes: fa2_fwd_varlen_scoremod's) on the sequence's keys gathered into a packed buffer BIT FOR BIT.  128- or 256-row
+ * workgroups by the packed call's rule on (B, H, max_seqlen_q) and option "rows" at head dims up to 128, 128-row workgroups above.  No KV-split. */
+enum { FA2_KERNEL_HIP_PREFILL = 8 };    /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+int fa2_fwd_prefill(int dtype, int cache_format, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse,
+                    const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                    int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, int num_pages,
+                    const int64_t q_strides[2], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[2],
+                    int64_t lse_stride, int64_t block_table_stride, float scale, int window_left, float softcap,
+                    const float* alibi_slopes, int64_t alibi_stride, void* hip_stream);
+/* The plan of the call above: kernel = FA2_KERNEL_HIP_PREFILL, contract 0, rows as launched, heads_main = B * H.  Sizes and dtype are checked as above. */
+int fa2_fwd_prefill_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan);
+/* Where 64-key tile `tile` of a sequence lies — the host side of the one function the kernel calls (csrc/fa2_prefill.h: prefill_tile).  len is clamped into
+ * [0, capacity_keys] (capacity_keys = capacity * page_size, or capacity when page_size = 0: the contiguous layout, one page per sequence).
+ * *page_slot: the block-table entry of the tile's page (contiguous: 0); *row_in_page: the tile's first row inside that page; *valid_rows: how many of
+ * its 64 rows hold a key of the sequence (0 .. 64; 0: the tile lies at or beyond the length).  FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for capacity < 1,
+ * a page_size that is negative or no multiple of 64, capacity_keys above 2^31 - 65, or a tile outside [0, ceil(capacity_keys / 64)). */
+int fa2_prefill_tile(int64_t len, int capacity, int page_size, int tile, int* page_slot, int* row_in_page, int* valid_rows);
+
 /* Coarse form of the above (kept for callers of version 0.8): 1 if launches of this head dim MAY fold the scale into Q (head dims exactly 64
  * and 128, 0 < scale*log2(e) <= 1, option "fold" >= 1: the fp16 launches the hand-scheduled bodies take), 0 if none does, -1: D not supported.
  * fa2_fwd_plan is the exact, per-call answer. */
