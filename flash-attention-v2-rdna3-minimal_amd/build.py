@@ -72,6 +72,11 @@ UNITS = [
     ("kvappend_hip_bf16", "kvappend_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans"]),
     ("kvappend_fp8_hip_f16", "kvappend_hip.cpp", ["-DFA2_TU_BF16=0", "-DFA2_TU_FP8=1", "-fhonor-nans"]),
     ("kvappend_fp8_hip_bf16", "kvappend_hip.cpp", ["-DFA2_TU_BF16=1", "-DFA2_TU_FP8=1", "-fhonor-nans"]),
+    # ... and its packed (ragged) form: one packed token per workgroup slice, the sequence found in cu_seqlens on the device
+    ("kvappend_varlen_hip_f16", "kvappend_varlen_hip.cpp", ["-DFA2_TU_BF16=0", "-fhonor-nans"]),
+    ("kvappend_varlen_hip_bf16", "kvappend_varlen_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans"]),
+    ("kvappend_varlen_fp8_hip_f16", "kvappend_varlen_hip.cpp", ["-DFA2_TU_BF16=0", "-DFA2_TU_FP8=1", "-fhonor-nans"]),
+    ("kvappend_varlen_fp8_hip_bf16", "kvappend_varlen_hip.cpp", ["-DFA2_TU_BF16=1", "-DFA2_TU_FP8=1", "-fhonor-nans"]),
 ]
 FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end of the operator (host-only C++, g++)
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")

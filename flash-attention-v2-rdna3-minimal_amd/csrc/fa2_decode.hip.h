@@ -94,6 +94,29 @@ FA2_DEC_HD inline int64_t kvappend_slot(int64_t len, int64_t capacity_keys, int 
     return p < 0 || p >= capacity_keys ? -1 : p;
 }
 
+// The sequence that owns packed token `t` (fa2_kvcache_append_varlen; csrc/fa2_kvappend.hip.h), host and device: cu[0 .. B] are the row offsets of B
+// sequences, sequence s owning the rows [cu[s], cu[s + 1]).  -> true with *s in [0, B), *i = t - cu[s] in [0, *nnew) and *nnew = cu[s + 1] - cu[s];
+// false: no sequence owns t (t < cu[0], t >= cu[B], or an array that is no ascending list of offsets).  cu is device data nobody validated: the search
+// is an upper bound over cu[1 .. B] whose probes lo + half stay inside [1, B] whatever it reads (lo + n <= B is kept by both branches) and whose trip
+// count depends on B alone (n halves, rounding down: ceil(log2(B + 1)) probes); on an ascending array it ends at the last j with cu[j] <= t, which
+// skips every zero-length sequence that shares t's offset.  The explicit check behind it makes the answer consistent on ANY array: a sequence is
+// named only when 0 <= cu[s] <= t < cu[s + 1], so i and nnew are what the caller's arithmetic assumes (and fit an int), or nothing is named.
+FA2_DEC_HD inline bool kvappend_varlen_token(const int* cu, int B, int64_t t, int* s, int* i, int* nnew) {
+    int lo = 0;
+    for (int n = B; n > 0;) {
+        const int half = (n + 1) >> 1;
+        if (cu[lo + half] <= t) lo += half;
+        n -= half;
+    }
+    if (lo >= B) return false;
+    const int64_t c0 = cu[lo], c1 = cu[lo + 1];
+    if (c0 < 0 || t < c0 || t >= c1) return false;
+    *s = lo;
+    *i = (int)(t - c0);
+    *nnew = (int)(c1 - c0);
+    return true;
+}
+
 struct DecodeParams {
     const void *q, *k, *v;
     void* o;

@@ -10,7 +10,12 @@
 // u + rotary_dim / 16: both halves of every pair are in one lane, and no value crosses lanes.  (rotary_dim is a multiple of 16, so the rotated span is
 // an even number of chunks and the units behind it are again the pairs (2u, 2u + 1).)
 //
-// Safety (the lengths and the block table are device data nobody validated): kvappend_slot (fa2_decode.hip.h, host and device) gives the key position
+// The packed (ragged) form, fa2_kvcache_append_varlen: k_new / v_new / q are [total, heads, D], blockIdx.x is the packed token t, and
+// kvappend_varlen_token (fa2_decode.hip.h, host and device) finds the sequence s that owns it in cu_seqlens [B + 1] — a binary search of a fixed trip
+// count whose probes stay inside cu[1 .. B] whatever the array holds, then the explicit check cu[s] <= t < cu[s + 1].  From there on the row is the uniform
+// call's (kvappend_row, the one body of both kernels) with Nnew = cu[s + 1] - cu[s].  A token no sequence owns writes no K / V; its q row is copied.
+//
+// Safety (the lengths, the block table and cu_seqlens are device data nobody validated): kvappend_slot (fa2_decode.hip.h, host and device) gives the key position
 // or "skip"; a page id outside [0, num_pages) skips too; the table row is clamped into [0, seqlen_ro - 1].  Nothing is clamped onto a valid cache row.
 // Every address is a 64-bit product of validated sizes and a value inside its range, so no device value can move a write outside the two caches.
 #pragma once
@@ -43,6 +48,11 @@ struct KvAppendParams {
     int64_t capacity_keys, seqlen_ro;
     int64_t kns[3], vns[3], ks[3], vs[3], qs[3], qos[3];      // element strides {batch | page, head, row}
     int64_t bts, ros, ds[2];        // block-table row stride, table row stride, descale strides {batch, K / V head}
+};
+
+// the packed call's: the shared description (B: sequences; Nnew unused; the source strides' [0] unused) and the row offsets
+struct KvAppendVarlenParams : KvAppendParams {
+    const int* cu;                  // cu_seqlens [B + 1], device: sequence s owns the packed rows [cu[s], cu[s + 1])
 };
 
 #if defined(__HIPCC__)
@@ -111,32 +121,35 @@ __device__ __forceinline__ u32x4 append_pack8(const float (&y)[8]) {
     return (u32x4){pack2<BF16>(y[0], y[1]), pack2<BF16>(y[2], y[3]), pack2<BF16>(y[4], y[5]), pack2<BF16>(y[6], y[7])};
 }
 
+// One row unit of one token: what both kernels run.  (b, i, nnew): the sequence, the token's index among the sequence's nnew new tokens; (sb, sr): the
+// batch and the row of the token's source rows in k_new / v_new / q / q_out (the uniform call: (b, i); the packed call: (0, t)).  owned = false (the
+// packed call alone: a token that belongs to no sequence): K and V rows are skipped and the q row is copied to q_out bit for bit; no length, table
+// entry or descale is read, b being no index then.
 // FP8: the caches hold OCP e4m3 bytes; k_new, v_new, q, q_out stay in the I/O dtype.
 template <bool BF16, bool FP8>
-__global__ __launch_bounds__(kAppendThreads) void kvappend_kernel(const KvAppendParams p) {
-    const int tok = blockIdx.x;                                  // uniform: the (sequence, token) group
-    const int b = tok / p.Nnew, i = tok - b * p.Nnew;
+__device__ __forceinline__ void kvappend_row(const KvAppendParams& p, int b, int i, int nnew, int64_t sb, int64_t sr, bool owned) {
     const int unit = blockIdx.y * blockDim.x + threadIdx.x;
     if (unit >= p.R * p.UR) return;
     const int row = unit / p.UR, u = unit - row * p.UR;
     const bool isq = row >= 2 * p.Hkv, isv = !isq && row >= p.Hkv;
     const int h = isq ? row - 2 * p.Hkv : isv ? row - p.Hkv : row;
+    if (!owned && !isq) return;
 
-    const int64_t len = p.lens[b];
-    const int64_t pos = len - p.Nnew + i;                        // the position q row i and new key i share
-    const int64_t slot = kvappend_slot(len, p.capacity_keys, p.Nnew, i);
+    const int64_t len = owned ? p.lens[b] : 0;
+    const int64_t pos = len - nnew + i;                          // the position q row i and new key i share
+    const int64_t slot = kvappend_slot(len, p.capacity_keys, nnew, i);
     if (!isq && slot < 0) return;                                // a skipped token: nothing is written
 
     // the row's source and destination
     const uint16_t* src;
     char* dst;
     if (isq) {
-        src = static_cast<const uint16_t*>(p.q) + b * p.qs[0] + h * p.qs[1] + i * p.qs[2];
-        dst = reinterpret_cast<char*>(static_cast<uint16_t*>(p.q_out) + b * p.qos[0] + h * p.qos[1] + i * p.qos[2]);
+        src = static_cast<const uint16_t*>(p.q) + sb * p.qs[0] + h * p.qs[1] + sr * p.qs[2];
+        dst = reinterpret_cast<char*>(static_cast<uint16_t*>(p.q_out) + sb * p.qos[0] + h * p.qos[1] + sr * p.qos[2]);
     } else {
         const int64_t* ns = isv ? p.vns : p.kns;
         const int64_t* cs = isv ? p.vs : p.ks;
-        src = static_cast<const uint16_t*>(isv ? p.v_new : p.k_new) + b * ns[0] + h * ns[1] + i * ns[2];
+        src = static_cast<const uint16_t*>(isv ? p.v_new : p.k_new) + sb * ns[0] + h * ns[1] + sr * ns[2];
         int64_t base = b, r = slot;
         if (p.page_size) {
             const int64_t pg = slot / p.page_size;               // < the block-table entries per sequence: slot < capacity * page_size
@@ -149,7 +162,7 @@ __global__ __launch_bounds__(kAppendThreads) void kvappend_kernel(const KvAppend
     }
 
     const int CH = p.D >> 3, rh = p.rot >> 4;
-    const bool rotate = p.cos != nullptr && !isv;
+    const bool rotate = p.cos != nullptr && !isv && owned;
     const bool halves = rotate && !p.interleaved && u < rh;     // chunk u and its partner chunk u + rh
     const int ca = halves ? u : 2 * u, cb = halves ? u + rh : 2 * u + 1;
     const bool hasb = cb < CH;
@@ -209,6 +222,24 @@ __global__ __launch_bounds__(kAppendThreads) void kvappend_kernel(const KvAppend
         *reinterpret_cast<u32x4*>(dst + 16 * ca) = rota ? append_pack8<BF16>(xa) : wa;
         if (hasb) *reinterpret_cast<u32x4*>(dst + 16 * cb) = rotb ? append_pack8<BF16>(xb) : wb;
     }
+}
+
+// the uniform call: blockIdx.x is the (sequence, token) group of Nnew tokens per sequence
+template <bool BF16, bool FP8>
+__global__ __launch_bounds__(kAppendThreads) void kvappend_kernel(const KvAppendParams p) {
+    const int tok = blockIdx.x;                                  // uniform: the (sequence, token) group
+    const int b = tok / p.Nnew, i = tok - b * p.Nnew;
+    kvappend_row<BF16, FP8>(p, b, i, p.Nnew, b, i, true);
+}
+
+// the packed call (fa2_kvcache_append_varlen): blockIdx.x is the packed token t; kvappend_varlen_token (fa2_decode.hip.h, host and device) finds the
+// sequence that owns it in cu_seqlens — device data nobody validated — or none.  Everything it reads is uniform over the workgroup.
+template <bool BF16, bool FP8>
+__global__ __launch_bounds__(kAppendThreads) void kvappend_varlen_kernel(const KvAppendVarlenParams p) {
+    const int t = blockIdx.x;
+    int s, i, nnew;
+    const bool owned = kvappend_varlen_token(p.cu, p.B, t, &s, &i, &nnew);
+    kvappend_row<BF16, FP8>(p, owned ? s : 0, owned ? i : 0, owned ? nnew : 1, 0, t, owned);
 }
 
 #endif  // __HIPCC__

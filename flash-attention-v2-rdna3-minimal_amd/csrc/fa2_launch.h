@@ -274,6 +274,9 @@ FA2_LAUNCHER(launch_decode_band_fp8, (int HD, const DecodeParams& p, int row_til
 // KV-cache append (kvappend_hip.cpp; fa2_kvcache_append): the kernel of csrc/fa2_kvappend.hip.h into 16-bit caches, and (-DFA2_TU_FP8=1) into e4m3 caches
 FA2_LAUNCHER(launch_kvappend, (const KvAppendParams& p, hipStream_t stream), (p, stream))
 FA2_LAUNCHER(launch_kvappend_fp8, (const KvAppendParams& p, hipStream_t stream), (p, stream))
+// ... and its packed (ragged) form (kvappend_varlen_hip.cpp; fa2_kvcache_append_varlen): one workgroup slice per packed token
+FA2_LAUNCHER(launch_kvappend_varlen, (const KvAppendVarlenParams& p, int64_t total, hipStream_t stream), (p, total, stream))
+FA2_LAUNCHER(launch_kvappend_varlen_fp8, (const KvAppendVarlenParams& p, int64_t total, hipStream_t stream), (p, total, stream))
 
 constexpr int kBwdAsmParts = 3;     // passes the hand-scheduled backward covers: bit 0 = dQ, bit 1 = dK / dV
 

@@ -1754,50 +1754,113 @@ int fa2_rotary_eval(int dtype, const void* x, const float* cos_row, const float*
     return FA2_OK;
 }
 
+// One append call, described: the uniform and the packed entry fill it by field name.  The new tokens' strides are {batch, head, row}; the packed call
+// has no batch stride (0) and names its rows by packed token.
+struct AppendCall : CacheDesc {
+    int dtype = 0, B = 0, Hkv = 0, H = 0, D = 0;
+    int Nnew = 0;                                           // the uniform call's; the packed call's sequences take theirs from cu
+    const int* cu = nullptr;                                // the packed call's cu_seqlens [B + 1], device
+    bool packed = false;
+    int64_t groups = 0;                                     // (sequence, token) groups = grid x: B * Nnew, or the packed call's total
+    const void *k_new = nullptr, *v_new = nullptr, *q = nullptr;
+    void* q_out = nullptr;
+    const int* lens = nullptr;
+    const int64_t *kns = nullptr, *vns = nullptr, *qs = nullptr, *qos = nullptr;
+    const void *cos = nullptr, *sin = nullptr;
+    int rotary_dtype = 0, rotary_dim = 0, seqlen_ro = 0, interleaved = 0;
+    int64_t ros = 0;
+    void* stream = nullptr;
+};
+
+static int append_run(const AppendCall& c, bool q_sizes_ok) {
+    const bool has_q = c.q || c.q_out, rotary = c.cos || c.sin, fp8 = c.fp8();
+    if (any_null({c.k_new, c.v_new, c.lens, c.kns, c.vns}) || (c.packed && !c.cu) || cache_null(c) || (has_q && any_null({c.q, c.q_out, c.qs, c.qos})) ||
+        (rotary && (!c.cos || !c.sin)))
+        return FA2_ERR_NULL_POINTER;
+    if (c.B < 1 || c.Hkv < 1 || (c.packed ? c.groups < 0 : c.Nnew < 1) || c.D < 1 || !cache_paging_ok(c) || !cache_extent_ok(c)) return FA2_ERR_BAD_SHAPE;
+    if (has_q && (!rotary || c.H < 1 || c.H % c.Hkv != 0 || !q_sizes_ok)) return FA2_ERR_BAD_SHAPE;          // q rows exist to be rotated
+    if (rotary && (c.seqlen_ro < 1 || c.ros < 0)) return FA2_ERR_BAD_SHAPE;
+    if ((c.D & (fp8 ? 15 : 7)) || c.D > kMaxBwdHeadDim) return FA2_ERR_HEAD_DIM;
+    if (rotary)
+        if (int rc = rotary_dim_check(c.D, c.rotary_dim)) return rc;
+    const bool tab32 = c.rotary_dtype == FA2_DTYPE_F32;
+    if (!all_aligned16({c.k_new, c.v_new, c.q, c.q_out, c.cos, c.sin}) || !cache_aligned(c) ||
+        ((reinterpret_cast<uintptr_t>(c.lens) | reinterpret_cast<uintptr_t>(c.cu)) & 3u) || !strides3_ok(c.kns) || !strides3_ok(c.vns) ||
+        (has_q && (!strides3_ok(c.qs) || !strides3_ok(c.qos))) || (rotary && c.ros % (tab32 ? 4 : 8) != 0))      // a table row starts on a 16-byte boundary
+        return FA2_ERR_ALIGNMENT;
+    if ((c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) || !cache_format_ok(c) || (rotary && !tab32 && c.rotary_dtype != c.dtype)) return FA2_ERR_DTYPE;
+    fa2::KvAppendVarlenParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.k_new = c.k_new; p.v_new = c.v_new; p.k_cache = const_cast<void*>(c.k); p.v_cache = const_cast<void*>(c.v); p.q = c.q; p.q_out = c.q_out;
+    p.cos = c.cos; p.sin = c.sin; p.lens = c.lens; p.bt = c.page_size > 0 ? c.block_table : nullptr; p.kd = c.kd; p.vd = c.vd;
+    p.B = c.B; p.Hkv = c.Hkv; p.H = has_q ? c.H : 0; p.Nnew = c.Nnew; p.D = c.D;
+    p.rot = rotary ? c.rotary_dim : 0; p.interleaved = c.interleaved != 0; p.tab16 = !tab32;
+    p.page_size = c.page_size; p.num_pages = c.num_pages;
+    p.R = 2 * c.Hkv + p.H; p.UR = (c.D + 15) / 16;
+    p.capacity_keys = c.capacity_keys();
+    p.seqlen_ro = rotary ? c.seqlen_ro : 1;
+    for (int i = 0; i < 3; ++i) {
+        p.kns[i] = c.kns[i]; p.vns[i] = c.vns[i]; p.ks[i] = c.ks[i]; p.vs[i] = c.vs[i];
+        if (has_q) { p.qs[i] = c.qs[i]; p.qos[i] = c.qos[i]; }
+    }
+    p.bts = c.bts; p.ros = c.ros;
+    if (c.descaled()) { p.ds[0] = c.ds[0]; p.ds[1] = c.ds[1]; }
+    p.cu = c.cu;
+    if (c.groups > 0x7fffffffLL || ((int64_t)p.R * p.UR + fa2::kAppendThreads - 1) / fa2::kAppendThreads > 65535) return FA2_ERR_GRID;
+    const bool bf16 = c.dtype == FA2_DTYPE_BF16;
+    hipStream_t const stream = (hipStream_t)c.stream;
+    if (c.packed) {
+        if (c.groups == 0) return FA2_OK;                    // an empty token buffer: nothing to launch
+        return fp8 ? fa2::launch_kvappend_varlen_fp8(bf16, p, c.groups, stream) : fa2::launch_kvappend_varlen(bf16, p, c.groups, stream);
+    }
+    return fp8 ? fa2::launch_kvappend_fp8(bf16, p, stream) : fa2::launch_kvappend(bf16, p, stream);
+}
+
 int fa2_kvcache_append(int dtype, int cache_format, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens,
                        const int* block_table, int B, int Hkv, int Nnew, int D, int capacity, int page_size, int num_pages, const int64_t k_new_strides[3],
                        const int64_t v_new_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], int64_t block_table_stride, const void* q,
                        void* q_out, int H, int Nq, const int64_t q_strides[3], const int64_t q_out_strides[3], const void* rotary_cos,
                        const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride, int rotary_interleaved,
                        const float* k_descale, const float* v_descale, const int64_t descale_strides[2], void* hip_stream) {
-    CacheDesc c;
+    AppendCall c;
     c.k = k_cache; c.v = v_cache; c.block_table = block_table; c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
     c.ks = k_strides; c.vs = v_strides; c.bts = block_table_stride; c.format = cache_format; c.kd = k_descale; c.vd = v_descale; c.ds = descale_strides;
-    const bool has_q = q || q_out, rotary = rotary_cos || rotary_sin, fp8 = c.fp8();
-    if (any_null({k_new, v_new, cache_seqlens, k_new_strides, v_new_strides}) || cache_null(c) || (has_q && any_null({q, q_out, q_strides, q_out_strides})) ||
-        (rotary && (!rotary_cos || !rotary_sin)))
-        return FA2_ERR_NULL_POINTER;
-    if (B < 1 || Hkv < 1 || Nnew < 1 || D < 1 || !cache_paging_ok(c) || !cache_extent_ok(c)) return FA2_ERR_BAD_SHAPE;
-    if (has_q && (!rotary || H < 1 || H % Hkv != 0 || Nq != Nnew)) return FA2_ERR_BAD_SHAPE;               // q rows exist to be rotated
-    if (rotary && (seqlen_ro < 1 || rotary_row_stride < 0)) return FA2_ERR_BAD_SHAPE;
-    if ((D & (fp8 ? 15 : 7)) || D > kMaxBwdHeadDim) return FA2_ERR_HEAD_DIM;
-    if (rotary)
-        if (int rc = rotary_dim_check(D, rotary_dim)) return rc;
-    const bool tab32 = rotary_dtype == FA2_DTYPE_F32;
-    if (!all_aligned16({k_new, v_new, q, q_out, rotary_cos, rotary_sin}) || !cache_aligned(c) || (reinterpret_cast<uintptr_t>(cache_seqlens) & 3u) ||
-        !strides3_ok(k_new_strides) || !strides3_ok(v_new_strides) || (has_q && (!strides3_ok(q_strides) || !strides3_ok(q_out_strides))) ||
-        (rotary && rotary_row_stride % (tab32 ? 4 : 8) != 0))      // a table row starts on a 16-byte boundary
-        return FA2_ERR_ALIGNMENT;
-    if ((dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) || !cache_format_ok(c) || (rotary && !tab32 && rotary_dtype != dtype)) return FA2_ERR_DTYPE;
-    fa2::KvAppendParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.k_new = k_new; p.v_new = v_new; p.k_cache = k_cache; p.v_cache = v_cache; p.q = q; p.q_out = q_out;
-    p.cos = rotary_cos; p.sin = rotary_sin; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr; p.kd = k_descale; p.vd = v_descale;
-    p.B = B; p.Hkv = Hkv; p.H = has_q ? H : 0; p.Nnew = Nnew; p.D = D;
-    p.rot = rotary ? rotary_dim : 0; p.interleaved = rotary_interleaved != 0; p.tab16 = !tab32;
-    p.page_size = page_size; p.num_pages = num_pages;
-    p.R = 2 * Hkv + p.H; p.UR = (D + 15) / 16;
-    p.capacity_keys = c.capacity_keys();
-    p.seqlen_ro = rotary ? seqlen_ro : 1;
-    for (int i = 0; i < 3; ++i) {
-        p.kns[i] = k_new_strides[i]; p.vns[i] = v_new_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i];
-        if (has_q) { p.qs[i] = q_strides[i]; p.qos[i] = q_out_strides[i]; }
-    }
-    p.bts = block_table_stride; p.ros = rotary_row_stride;
-    if (c.descaled()) { p.ds[0] = descale_strides[0]; p.ds[1] = descale_strides[1]; }
-    if ((int64_t)B * Nnew > 0x7fffffffLL || ((int64_t)p.R * p.UR + fa2::kAppendThreads - 1) / fa2::kAppendThreads > 65535) return FA2_ERR_GRID;
-    return fp8 ? fa2::launch_kvappend_fp8(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream)
-               : fa2::launch_kvappend(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
+    c.dtype = dtype; c.B = B; c.Hkv = Hkv; c.H = H; c.D = D; c.Nnew = Nnew; c.groups = (int64_t)B * Nnew;
+    c.k_new = k_new; c.v_new = v_new; c.q = q; c.q_out = q_out; c.lens = cache_seqlens;
+    c.kns = k_new_strides; c.vns = v_new_strides; c.qs = q_strides; c.qos = q_out_strides;
+    c.cos = rotary_cos; c.sin = rotary_sin; c.rotary_dtype = rotary_dtype; c.rotary_dim = rotary_dim; c.seqlen_ro = seqlen_ro; c.ros = rotary_row_stride;
+    c.interleaved = rotary_interleaved; c.stream = hip_stream;
+    return append_run(c, Nq == Nnew);
+}
+
+// ... its packed (ragged) form: the new tokens are [total, heads, D], strides {head, row} as the packed attention calls take them
+int fa2_kvappend_varlen_token(const int* cu_seqlens, int B, int64_t t, int* seq, int* i, int* nnew) {
+    if (!cu_seqlens || !seq || !i || !nnew) return FA2_ERR_NULL_POINTER;
+    if (B < 1) return FA2_ERR_BAD_SHAPE;
+    if (!fa2::kvappend_varlen_token(cu_seqlens, B, t, seq, i, nnew)) { *seq = -1; *i = 0; *nnew = 0; }
+    return FA2_OK;
+}
+
+int fa2_kvcache_append_varlen(int dtype, int cache_format, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cu_seqlens,
+                              const int* cache_seqlens, const int* block_table, int B, int64_t total, int Hkv, int D, int capacity, int page_size,
+                              int num_pages, const int64_t k_new_strides[2], const int64_t v_new_strides[2], const int64_t k_strides[3],
+                              const int64_t v_strides[3], int64_t block_table_stride, const void* q, void* q_out, int H, const int64_t q_strides[2],
+                              const int64_t q_out_strides[2], const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
+                              int64_t rotary_row_stride, int rotary_interleaved, const float* k_descale, const float* v_descale,
+                              const int64_t descale_strides[2], void* hip_stream) {
+    AppendCall c;
+    c.k = k_cache; c.v = v_cache; c.block_table = block_table; c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    c.ks = k_strides; c.vs = v_strides; c.bts = block_table_stride; c.format = cache_format; c.kd = k_descale; c.vd = v_descale; c.ds = descale_strides;
+    c.dtype = dtype; c.B = B; c.Hkv = Hkv; c.H = H; c.D = D; c.packed = true; c.cu = cu_seqlens; c.groups = total;
+    c.k_new = k_new; c.v_new = v_new; c.q = q; c.q_out = q_out; c.lens = cache_seqlens;
+    int64_t st[4][3] = {};
+    const int64_t* in[4] = {k_new_strides, v_new_strides, q_strides, q_out_strides};
+    const int64_t** out[4] = {&c.kns, &c.vns, &c.qs, &c.qos};
+    for (int j = 0; j < 4; ++j)
+        if (in[j]) { st[j][1] = in[j][0]; st[j][2] = in[j][1]; *out[j] = st[j]; }
+    c.cos = rotary_cos; c.sin = rotary_sin; c.rotary_dtype = rotary_dtype; c.rotary_dim = rotary_dim; c.seqlen_ro = seqlen_ro; c.ros = rotary_row_stride;
+    c.interleaved = rotary_interleaved; c.stream = hip_stream;
+    return append_run(c, true);
 }
 
 // ---- chunked prefill against a KV cache: include/fa2_gfx950.h has the contract, csrc/fa2_prefill.h the tile arithmetic, prefill_hip.cpp /

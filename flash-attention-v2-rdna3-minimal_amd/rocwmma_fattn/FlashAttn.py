@@ -17,13 +17,15 @@ The host is PyTorch-ROCm for memory and streams only; the compute is the C-ABI l
 (include/fa2_gfx950.h).  There is no CPU path: tensors must live on a ROCm device.
 """
 import ctypes
+import math
 import os
 
 import torch
 
 from . import _fa2_lib
 
-__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill"]
+__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill",
+           "kvcache_append_varlen"]
 
 
 class _FlashAttnWmma:
@@ -1118,11 +1120,11 @@ def _cache_format(who, q, k_cache, v_cache, k_descale, v_descale):
     return fp8
 
 
-def _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8, num_splits=None):
+def _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8, num_splits=None, B=None):
     """The checks of the lengths, the block table, the descales, the devices and the cache strides that flash_attention_decode and kvcache_append share
-    (q: the tensor that sets the batch size and the device; num_splits: decode's, checked in its place).
+    (q: the tensor that sets the batch size and the device — a packed call states its B; num_splits: decode's, checked in its place).
     -> capacity, page_size, num_pages, k_descale, v_descale (the descales made to share one stride pair)"""
-    B, Hkv = q.shape[0], k_cache.shape[2]
+    B, Hkv = q.shape[0] if B is None else B, k_cache.shape[2]
     if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous():
         raise ValueError("fa2: cache_seqlens must be a contiguous int32 tensor of shape [B] = [%d], got %s %s" % (B, cache_seqlens.dtype, tuple(cache_seqlens.shape)))
     if num_splits is not None and (isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _DECODE_MAX_SPLITS):
@@ -1177,6 +1179,13 @@ def _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8):
         raise ValueError("fa2: kvcache_append needs B, Nnew, Hkv >= 1, got k %s" % (tuple(k.shape),))
     if D % (16 if fp8 else 8) or D > 512:
         raise ValueError("fa2: kvcache_append serves head dims that are multiples of 8 (float8_e4m3fn caches: of 16) up to 512, got %d" % D)
+    rotary_dim = _rotary_check(k, D, rotary_cos, rotary_sin)
+    _append_q_check("kvcache_append", "[B, Nnew, H, D]", q, k, rotary_dim)
+    return rotary_dim
+
+
+def _rotary_check(k, D, rotary_cos, rotary_sin):
+    """The rotary tables of an append of new tokens k (uniform or packed) with head dim D -> rotary_dim (0: no rotary)"""
     if (rotary_cos is None) != (rotary_sin is None):
         raise ValueError("fa2: rotary_cos and rotary_sin come together")
     rotary_dim = 0
@@ -1189,14 +1198,28 @@ def _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8):
         rotary_dim = 2 * rotary_cos.shape[1]
         if rotary_dim < 16 or rotary_dim % 16 or rotary_dim > D:
             raise ValueError("fa2: rotary_dim (2 * rotary_cos.shape[1]) must be a multiple of 16 between 16 and the head dim %d, got %d" % (D, rotary_dim))
-    if q is not None:
-        if rotary_dim == 0:
-            raise ValueError("fa2: kvcache_append takes q to rotate it: q without rotary_cos / rotary_sin has nothing to do")
-        if not torch.is_tensor(q) or q.dim() != 4 or q.dtype != k.dtype or q.shape[0] != B or q.shape[1] != Nnew or q.shape[3] != D or q.shape[2] < 1 or \
-                q.shape[2] % Hkv:
-            raise ValueError("fa2: kvcache_append takes q [B, Nnew, H, D] in k's dtype with Hkv dividing H, got %s for k %s"
-                             % ("%s %s" % (q.dtype, tuple(q.shape)) if torch.is_tensor(q) else repr(q), tuple(k.shape)))
     return rotary_dim
+
+
+def _append_q_check(who, layout, q, k, rotary_dim):
+    """q of an append of new tokens k: the leading (token) dims of k, H heads with Hkv dividing H, k's dtype and head dim; tables required"""
+    if q is None:
+        return
+    if rotary_dim == 0:
+        raise ValueError("fa2: %s takes q to rotate it: q without rotary_cos / rotary_sin has nothing to do" % who)
+    if not torch.is_tensor(q) or q.dim() != k.dim() or q.dtype != k.dtype or q.shape[:-2] != k.shape[:-2] or q.shape[-1] != k.shape[-1] or q.shape[-2] < 1 or \
+            q.shape[-2] % k.shape[-2]:
+        raise ValueError("fa2: %s takes q %s in k's dtype with Hkv dividing H, got %s for k %s"
+                         % (who, layout, "%s %s" % (q.dtype, tuple(q.shape)) if torch.is_tensor(q) else repr(q), tuple(k.shape)))
+
+
+def _rotary_tables(rotary_cos, rotary_sin):
+    """The tables as the C-ABI takes them: contiguous rows that start on 16-byte boundaries, one row stride -> cos, sin, seqlen_ro, row stride"""
+    per16 = 16 // rotary_cos.element_size()
+    rotary_cos, rotary_sin = (t if t.stride(1) == 1 and t.stride(0) % per16 == 0 and not (t.data_ptr() & 15) else t.contiguous() for t in (rotary_cos, rotary_sin))
+    if rotary_cos.stride(0) != rotary_sin.stride(0):                   # the C-ABI takes one row stride
+        rotary_cos, rotary_sin = rotary_cos.contiguous(), rotary_sin.contiguous()
+    return rotary_cos, rotary_sin, rotary_cos.shape[0], rotary_cos.stride(0)
 
 
 def kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, k_descale=None,
@@ -1232,11 +1255,7 @@ def kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rota
         q_out = torch.empty((B, Nnew, H, D), dtype=q.dtype, device=q.device)
     tab_code, seqlen_ro, ros = 0, 0, 0
     if rotary_dim:
-        per16 = 16 // rotary_cos.element_size()
-        rotary_cos, rotary_sin = (t if t.stride(1) == 1 and t.stride(0) % per16 == 0 and not (t.data_ptr() & 15) else t.contiguous() for t in (rotary_cos, rotary_sin))
-        if rotary_cos.stride(0) != rotary_sin.stride(0):                   # the C-ABI takes one row stride
-            rotary_cos, rotary_sin = rotary_cos.contiguous(), rotary_sin.contiguous()
-        seqlen_ro, ros = rotary_cos.shape[0], rotary_cos.stride(0)
+        rotary_cos, rotary_sin, seqlen_ro, ros = _rotary_tables(rotary_cos, rotary_sin)
     lib = _fa2_lib.load()
     code = _fa2_lib.FA2_DTYPE_F16 if k.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
     if rotary_dim:
@@ -1255,6 +1274,80 @@ def kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rota
                                     rotary_sin.data_ptr() if rotary_dim else None, tab_code, rotary_dim, seqlen_ro, ros, 1 if rotary_interleaved else 0,
                                     None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
                                     None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return q_out
+
+
+def _check_cu(name, cu):
+    if not torch.is_tensor(cu) or cu.dim() != 1 or cu.dtype != torch.int32 or cu.numel() < 2 or not cu.is_contiguous():
+        raise ValueError("fa2: %s must be a contiguous 1-D int32 tensor of B + 1 >= 2 row offsets, got %s"
+                         % (name, "%s %s" % (cu.dtype, tuple(cu.shape)) if torch.is_tensor(cu) else repr(cu)))
+    return cu.numel() - 1
+
+
+def kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens, cache_seqlens, block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True,
+                          k_descale=None, v_descale=None, q=None):
+    """Packed (ragged) append to a KV cache, in place: kvcache_append for a batch whose sequences bring different numbers of new tokens — the write side
+    of flash_attention_prefill, a continuous-batching step that mixes prefill chunks with decode rows.
+    k / v [total, Hkv, D] fp16 / bf16, packed; cu_seqlens int32 [B + 1] on the device: sequence s owns the rows [cu[s], cu[s+1]), Nnew_s may be 0.
+    The caches, cache_seqlens [B], block_table and the descales [B, Hkv] follow kvcache_append's rules (contiguous or paged, 16-bit or float8_e4m3fn);
+    cache_seqlens[s] counts the valid keys INCLUDING the Nnew_s new tokens, so row cu[s] + i is written at key position len_s - Nnew_s + i, the
+    position flash_attention_prefill gives query row i.  rotary_* and q [total, H, D] as in kvcache_append: k — and q — rotated by that position.
+    cu[B] < total is legitimate (a token buffer of a fixed, captured size that this step fills partly): rows at or beyond cu[B] belong to no sequence,
+    write nothing, and their q rows come back unrotated, bit for bit.  cu_seqlens is device data nobody validated, like the lengths and the block
+    table: an array that is not ascending loses tokens, it moves no write outside the caches.  A token whose position lies outside the cache or whose
+    page id lies outside the pool is skipped, as in kvcache_append.
+    Returns the rotated q (a new tensor) when q and the tables are given, else None.  The host reads no device value: the call can be captured in a
+    graph.  Not served: cache_batch_idx, cache_leftpad, rotary without an append.  C-ABI fa2_kvcache_append_varlen."""
+    who = "kvcache_append_varlen"
+    if not all(torch.is_tensor(t) for t in (k_cache, v_cache, k, v, cache_seqlens)) or k_cache.dim() != 4 or v_cache.dim() != 4 or k.dim() != 3 or v.dim() != 3:
+        raise ValueError("fa2: %s takes k / v [total, Hkv, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
+                         "with a block_table)" % who)
+    fp8 = _cache_format(who, k, k_cache, v_cache, k_descale, v_descale)
+    if k.shape != v.shape or k.dtype != v.dtype:
+        raise ValueError("fa2: %s takes k and v [total, Hkv, D] of one shape and dtype, got %s %s" % (who, tuple(k.shape), tuple(v.shape)))
+    total, Hkv, D = k.shape
+    if k_cache.shape != v_cache.shape or k_cache.shape[2] != Hkv or k_cache.shape[3] != D:
+        raise ValueError("fa2: inconsistent k / k_cache / v_cache shapes %s %s %s" % (tuple(k.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
+    if Hkv < 1:
+        raise ValueError("fa2: %s needs Hkv >= 1, got k %s" % (who, tuple(k.shape)))
+    if D % (16 if fp8 else 8) or D > 512:
+        raise ValueError("fa2: %s serves head dims that are multiples of 8 (float8_e4m3fn caches: of 16) up to 512, got %d" % (who, D))
+    rotary_dim = _rotary_check(k, D, rotary_cos, rotary_sin)
+    _append_q_check(who, "[total, H, D]", q, k, rotary_dim)
+    B = _check_cu("cu_seqlens", cu_seqlens)
+    capacity, page_size, num_pages, k_descale, v_descale = _cache_layout(k, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8, B=B)
+    extra = tuple(t for t in (v, cu_seqlens, q, rotary_cos, rotary_sin) if t is not None)
+    if not all(t.is_cuda for t in extra) or any(t.device != k.device for t in extra):
+        raise RuntimeError("fa2: k, v, cu_seqlens, q and the rotary tables must be on the ROCm device of the caches")
+    k, v = _packed_ready(k), _packed_ready(v)
+    H, q_out = 0, None
+    if q is not None:
+        H = q.shape[1]
+        q = _packed_ready(q)
+        q_out = torch.empty((total, H, D), dtype=q.dtype, device=q.device)
+    if total == 0:                 # an empty token buffer: nothing to launch
+        return q_out
+    code = _fa2_lib.FA2_DTYPE_F16 if k.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+    tab_code, seqlen_ro, ros = 0, 0, 0
+    if rotary_dim:
+        rotary_cos, rotary_sin, seqlen_ro, ros = _rotary_tables(rotary_cos, rotary_sin)
+        tab_code = _fa2_lib.FA2_DTYPE_F32 if rotary_cos.dtype == torch.float32 else code
+    lib = _fa2_lib.load()
+    dev = k.device.index if k.device.index is not None else _current_device()
+    s3 = _fa2_lib.strides3
+    bnhd = lambda t: s3(t.stride(0), t.stride(2), t.stride(1))      # noqa: E731
+    d0 = k_descale if k_descale is not None else v_descale
+    with torch.cuda.device(dev):
+        rc = lib.fa2_kvcache_append_varlen(code, _fa2_lib.FA2_CACHE_E4M3 if fp8 else _fa2_lib.FA2_CACHE_16BIT, k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
+                                           v_cache.data_ptr(), cu_seqlens.data_ptr(), cache_seqlens.data_ptr(),
+                                           None if block_table is None else block_table.data_ptr(), B, total, Hkv, D, capacity, page_size, num_pages,
+                                           _s2(k), _s2(v), bnhd(k_cache), bnhd(v_cache), 0 if block_table is None else block_table.stride(0),
+                                           None if q is None else q.data_ptr(), None if q is None else q_out.data_ptr(), H,
+                                           None if q is None else _s2(q), None if q is None else _s2(q_out), rotary_cos.data_ptr() if rotary_dim else None,
+                                           rotary_sin.data_ptr() if rotary_dim else None, tab_code, rotary_dim, seqlen_ro, ros, 1 if rotary_interleaved else 0,
+                                           None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
+                                           None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), _raw_stream(dev))
     _fa2_lib.check(rc)
     return q_out
 
@@ -1369,7 +1462,8 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
 
 
 def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, max_seqlen_q=None, scale=None, window=None, softcap=0.0,
-                            alibi_slopes=None, return_lse=False, k_descale=None, v_descale=None):
+                            alibi_slopes=None, return_lse=False, k_descale=None, v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None,
+                            rotary_interleaved=True):
     """Chunked prefill against a KV cache: many query rows per sequence (packed, as flash_attention_varlen's) against the cache kvcache_append writes and
     flash_attention_decode reads — a prompt whose prefix sits in cached pages, a prompt processed in chunks, a continuous-batching step that mixes
     prefill chunks with decode rows (other libraries: flash_attn_varlen_func(..., block_table=), flash_attn_with_kvcache with a long seqlen_q).
@@ -1388,7 +1482,15 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
     never an out-of-bounds read); a page that holds no key a workgroup's rows see is never addressed, nor its block-table entry read.
     Returns o [total_q, H, D]; with return_lse=True also lse f32 [H, total_q] in natural-log units (merge_attention combines such pairs).
     Inference only.  Head dims up to 512; one that is no multiple of 8 is zero-padded — q AND both caches, i.e. copies of the caches.
-    float8_e4m3fn caches and k_descale / v_descale raise ValueError: 16-bit caches only.  C-ABI fa2_fwd_prefill."""
+    Append and rotary: with k / v [total_q, Hkv, D] given (both) the call first runs kvcache_append_varlen with cu_seqlens_q as its cu_seqlens — the
+    new tokens' K / V written at positions len_s - Nq_s + i, k and q rotated by rotary_cos / rotary_sin when given — and then the call above on the
+    rotated q, on one stream: with the lengths incremented in place before it, a whole ragged serving step is one capturable sequence.  The append
+    serves head dims that are multiples of 8.  rotary_* without k / v raises ValueError.  Every argument check of this function and of
+    kvcache_append_varlen runs before the append launch, so a call they refuse leaves the caches as they were; what only the C entry refuses after that
+    (a window or a grid beyond its limits) leaves caches that hold the new tokens.  With none of the five keywords the call makes exactly the launches it
+    made before they existed.
+    float8_e4m3fn caches and k_descale / v_descale raise ValueError: 16-bit caches only (kvcache_append_varlen alone writes e4m3 caches, for
+    flash_attention_decode to read).  C-ABI fa2_fwd_prefill."""
     who = "flash_attention_prefill"
     if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cu_seqlens_q, cache_seqlens)) or q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("fa2: %s takes q [total_q, H, D], 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] with a "
@@ -1398,6 +1500,10 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
     if _cache_format(who, q, k_cache, v_cache, None, None) or k_descale is not None or v_descale is not None:
         raise ValueError("fa2: %s serves 16-bit caches only (fp16 / bf16, q's dtype): float8_e4m3fn caches and k_descale / v_descale are "
                          "flash_attention_decode's" % who)
+    fused = k is not None or v is not None
+    if not fused and (rotary_cos is not None or rotary_sin is not None):
+        raise ValueError("fa2: rotary_cos / rotary_sin rotate the appended tokens: %s takes them together with k and v (rotary without an append is "
+                         "not served)" % who)
     total_q, H, D = q.shape
     Hkv = k_cache.shape[2]
     if v_cache.shape != k_cache.shape or k_cache.shape[3] != D:
@@ -1405,6 +1511,13 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
     _check_groups(H, Hkv)
     if D < 1 or D > _MAX_HEAD_DIM:
         raise ValueError("fa2: %s serves head dims 1 .. %d, got %d" % (who, _MAX_HEAD_DIM, D))
+    if fused:
+        if not all(torch.is_tensor(t) and t.dim() == 3 and t.dtype == q.dtype and tuple(t.shape) == (total_q, Hkv, D) for t in (k, v)):
+            raise ValueError("fa2: %s takes k and v together, [total_q, Hkv, D] = [%d, %d, %d] in q's dtype: the new tokens are the query rows' own "
+                             "(k.shape[0] == total_q); got %s %s" % (who, total_q, Hkv, D, tuple(getattr(k, "shape", ())), tuple(getattr(v, "shape", ()))))
+        if D % 8:
+            raise ValueError("fa2: %s appends k / v at head dims that are multiples of 8 (kvcache_append_varlen's), got %d" % (who, D))
+        _rotary_check(k, D, rotary_cos, rotary_sin)
     if cu_seqlens_q.dim() != 1 or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous():
         raise ValueError("fa2: cu_seqlens_q must be a contiguous 1-D int32 tensor of B + 1 >= 2 row offsets, got %s %s" % (cu_seqlens_q.dtype, tuple(cu_seqlens_q.shape)))
     B = cu_seqlens_q.numel() - 1
@@ -1436,16 +1549,22 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
         raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on a ROCm device (no CPU path in this operator)")
     if any(t.device != q.device for t in (k_cache, v_cache) + aux):
         raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on the same device")
-    d_pad = -D % 8
+    d_pad = -D % 8                 # (0 in a fused call: its check above)
     if d_pad:
         q, k_cache, v_cache = (torch.nn.functional.pad(t, (0, d_pad)) for t in (q, k_cache, v_cache))
     if not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
         raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
-    q = _packed_ready(q)
     if max_seqlen_q is None:
         max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max())
     if scale is None:
         scale = D ** -0.5
+    if fused:               # every check of this function lies above: the packed append launch, then today's call on the rotated q, on one stream
+        if not math.isfinite(float(scale)):
+            raise ValueError("fa2: %s needs a finite scale, got %r" % (who, scale))
+        q_rot = kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                                      q=q if rotary_cos is not None else None)
+        q = q if q_rot is None else q_rot
+    q = _packed_ready(q)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
     if total_q and max_seqlen_q > 0:

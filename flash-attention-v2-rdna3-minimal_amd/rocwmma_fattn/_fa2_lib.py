@@ -178,6 +178,12 @@ SYMBOLS = {
     "fa2_fwd_prefill_plan": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(FwdPlan)]),
     "fa2_prefill_tile": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 3),
     "fa2_kvappend_slot": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    # ... packed (ragged): cu_seqlens before cache_seqlens, B total(int64) Hkv D capacity page_size num_pages, stride PAIRS {head, row} for k_new v_new q
+    # q_out, no Nq; the rest as above
+    "fa2_kvcache_append_varlen": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 + [_i64p] * 4 +
+                                  [ctypes.c_int64] + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [_i64p] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 +
+                                  [ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 2 + [_i64p, ctypes.c_void_p]),
+    "fa2_kvappend_varlen_token": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "fa2_rotary_eval": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p]),
     "fa2_scoremod_eval": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 2),
@@ -415,6 +421,14 @@ def kvappend_slot(length, capacity_keys, Nnew, i):
     pos = ctypes.c_int64()
     check(load().fa2_kvappend_slot(int(length), int(capacity_keys), int(Nnew), int(i), ctypes.byref(pos)))
     return pos.value
+
+
+def kvappend_varlen_token(cu_seqlens, t):
+    """fa2_kvappend_varlen_token on a host sequence of B + 1 ints -> (seq, i, nnew) of packed token `t`, or None when no sequence owns it."""
+    cu = (ctypes.c_int * len(cu_seqlens))(*[int(c) for c in cu_seqlens])
+    seq, i, nnew = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_kvappend_varlen_token(cu, len(cu_seqlens) - 1, int(t), ctypes.byref(seq), ctypes.byref(i), ctypes.byref(nnew)))
+    return None if seq.value < 0 else (seq.value, i.value, nnew.value)
 
 
 def prefill_plan(dtype, B, H, Hkv, max_seqlen_q, D, capacity, page_size=0):

@@ -785,6 +785,41 @@ int fa2_kvcache_append(int dtype, int cache_format, const void* k_new, const voi
  * *pos = len - Nnew + i when that lies in [0, capacity_keys), else -1 (skipped).  FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for capacity_keys < 0,
  * Nnew < 1 or i outside [0, Nnew). */
 int fa2_kvappend_slot(int64_t len, int64_t capacity_keys, int Nnew, int i, int64_t* pos);
+/* ---- Packed (ragged) KV-cache append: fa2_kvcache_append for a batch whose sequences bring DIFFERENT numbers of new tokens — the write side of
+ * fa2_fwd_prefill, a continuous-batching step that mixes prefill chunks with decode rows.  One launch; what is not said here is fa2_kvcache_append's.
+ * Layout (element strides {head, row}, as the packed attention calls take them; D contiguous)
+ *   k_new, v_new  : total x Hkv x D, the I/O dtype: the new tokens of all sequences, packed.
+ *   cu_seqlens    : int32 [B + 1], DEVICE: sequence s owns the packed rows [cu[s], cu[s + 1]), Nnew_s = cu[s + 1] - cu[s] may be 0.  cu[B] < total is
+ *                   legitimate — a token buffer of a fixed (captured) size that this step fills only partly: the rows t >= cu[B], like rows
+ *                   t < cu[0], belong to no sequence.
+ *   q, q_out      : optional, both or neither: total x H x D, rotated as in fa2_kvcache_append (tables required).
+ * Semantics.  Packed row t = cu[s] + i is new token i of sequence s and is treated as fa2_kvcache_append treats token i of Nnew_s: position
+ * p = cache_seqlens[s] - Nnew_s + i, skipped when p lies outside [0, capacity_keys) or its page id outside [0, num_pages), rotated by table row
+ * clamp(p, 0, seqlen_ro - 1), descaled by descale[s, hkv].  The q row of a token that belongs to a sequence is rotated whether or not its K / V is
+ * written; the q row of a token that belongs to no sequence is copied to q_out bit for bit (q_out never holds uninitialised memory), and no K / V is
+ * written for it.
+ * cu_seqlens is device data nobody validated, like cache_seqlens and block_table.  The kernel finds s by a binary search whose probes stay inside
+ * cu[1 .. B] whatever the array holds, then checks 0 <= cu[s] <= t < cu[s + 1]: on an array that is not ascending, holds negative entries or ends
+ * above total a token either belongs to no sequence or gets a consistent (s, i, Nnew_s).  No content of cu_seqlens, cache_seqlens or block_table can
+ * move a write outside the two caches and q_out, nor a read outside k_new, v_new, q and the tables: a wrong value loses a token, it never faults.  All
+ * addressing is in 64 bits.  fa2_kvappend_varlen_token is the host side of the search (csrc/fa2_decode.hip.h: kvappend_varlen_token, one function).
+ * The host reads no device value: the call can be captured in a graph and replays for the offsets, lengths, block table and descales of that time.
+ * Checked in fa2_kvcache_append's order: null pointers (cu_seqlens too), sizes (FA2_ERR_BAD_SHAPE: B, Hkv, D < 1, total < 0, and the rest of that
+ * list but Nq), head dim and rotary_dim, alignment (4-byte cu_seqlens too), dtype, FA2_ERR_GRID (total above 2^31 - 1).  total == 0 passes the checks
+ * and returns FA2_OK without a launch. */
+int fa2_kvcache_append_varlen(int dtype, int cache_format, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                              const int* cu_seqlens, const int* cache_seqlens, const int* block_table,
+                              int B, int64_t total, int Hkv, int D, int capacity, int page_size, int num_pages,
+                              const int64_t k_new_strides[2], const int64_t v_new_strides[2], const int64_t k_strides[3], const int64_t v_strides[3],
+                              int64_t block_table_stride,
+                              const void* q, void* q_out, int H, const int64_t q_strides[2], const int64_t q_out_strides[2],
+                              const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride,
+                              int rotary_interleaved,
+                              const float* k_descale, const float* v_descale, const int64_t descale_strides[2], void* hip_stream);
+/* The sequence that owns packed token t — the host side of the one function the kernel calls; cu_seqlens is HOST memory of B + 1 ints here.
+ * *seq in [0, B) with *i = t - cu[*seq] in [0, *nnew) and *nnew = cu[*seq + 1] - cu[*seq]; or *seq = -1 (*i = *nnew = 0): no sequence owns t.  Any
+ * array contents give one of the two.  FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for B < 1. */
+int fa2_kvappend_varlen_token(const int* cu_seqlens, int B, int64_t t, int* seq, int* i, int* nnew);
 /* One row of D 16-bit values x rotated into y with the arithmetic the kernel calls (csrc/fa2_rotary.h): cos_row / sin_row hold rotary_dim / 2 floats;
  * columns at or beyond rotary_dim are copied bit for bit.  FA2_ERR_NULL_POINTER, FA2_ERR_BAD_SHAPE (D < 1), FA2_ERR_HEAD_DIM (D, rotary_dim),
  * FA2_ERR_DTYPE, in this order. */

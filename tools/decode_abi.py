@@ -1,5 +1,5 @@
-"""The C argument order of the decode and append entries, for the tests and the tools alike: fa2_fwd_decode, fa2_fwd_decode_fp8, fa2_fwd_decode_window and
-fa2_kvcache_append by keyword (ENTRIES, c_args: the only copy under tests/ and tools/), what the tensors of a call say (tensor_kw) and the GPU call on
+"""The C argument order of the decode and append entries, for the tests and the tools alike: fa2_fwd_decode, fa2_fwd_decode_fp8, fa2_fwd_decode_window,
+fa2_kvcache_append and fa2_kvcache_append_varlen by keyword (ENTRIES, c_args: the only copy under tests/ and tools/), what the tensors of a call say (tensor_kw) and the GPU call on
 NaN-filled outputs and workspace (decode_c).  tests/decode_calls.py hands these on to the tests beside what only tests need; the tools import them
 here, so that a tool runs with nothing but itself, this file and the package."""
 import ctypes
@@ -44,6 +44,9 @@ ENTRIES = {      # entry -> (symbol, its arguments by keyword, its workspace que
     "window": ("fa2_fwd_decode_window", ("dtype", "fmt") + _HEAD + _DESCALES + ("wl", "cap_", "sl", "st") + _TAIL, "fa2_fwd_decode_window_workspace_bytes"),
     "append": ("fa2_kvcache_append", ("dtype", "fmt", "kn", "vn", "k", "v", "lens", "bt", "B", "Hkv", "N", "D", "cap", "page", "pages", "kns", "vns", "ks", "vs", "bts",
                                       "q", "qo", "H", "Nq", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter") + _DESCALES + ("stream",), None),
+    "append_varlen": ("fa2_kvcache_append_varlen", ("dtype", "fmt", "kn", "vn", "k", "v", "cu", "lens", "bt", "B", "total", "Hkv", "D", "cap", "page", "pages", "kns", "vns",
+                                                    "ks", "vs", "bts", "q", "qo", "H", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter") + _DESCALES +
+                      ("stream",), None),
 }
 _ABSENT = dict(kd=None, vd=None, ds=None, wl=-1, cap_=0.0, sl=None, st=0)      # what an entry without the argument computes with
 _FORMAT = {"plain": _fa2_lib.FA2_CACHE_16BIT, "fp8": _fa2_lib.FA2_CACHE_E4M3}   # ... and the cache format it serves
