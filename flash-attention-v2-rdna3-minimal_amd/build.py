@@ -62,6 +62,10 @@ UNITS = [
     ("prefill_hip_bf16", "prefill_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("prefill_scoremod_hip_f16", "prefill_scoremod_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("prefill_scoremod_hip_bf16", "prefill_scoremod_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("prefill_fp8_hip_f16", "prefill_fp8_hip.cpp", ["-DFA2_TU_BF16=0"]),                  # ... against an e4m3 cache: the FA2_KV8 forms, head dims up to 256
+    ("prefill_fp8_hip_bf16", "prefill_fp8_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("prefill_fp8_scoremod_hip_f16", "prefill_fp8_scoremod_hip.cpp", ["-DFA2_TU_BF16=0"]),
+    ("prefill_fp8_scoremod_hip_bf16", "prefill_fp8_scoremod_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("merge_hip", "merge_hip.cpp", []),          # both dtypes in one unit
     ("decode_hip_f16", "decode_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("decode_hip_bf16", "decode_hip.cpp", ["-DFA2_TU_BF16=1"]),

@@ -36,7 +36,7 @@
 #include "fa2_scoremod.h"            // smod_cap, smod_alibi: the one copy of the score modifiers' arithmetic
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#include "fa2_fwd_kernel.hip.h"      // the vector types, pack2
+#include "fa2_fwd_kernel.hip.h"      // the vector types, pack2, cvt8_e4m3
 #define FA2_DEC_HD __host__ __device__
 #else
 #define FA2_DEC_HD
@@ -168,22 +168,6 @@ __device__ __forceinline__ void decode_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// two e4m3 bytes (the low or the high half of w) -> two I/O dtype values, exact
-template <bool BF16>
-__device__ __forceinline__ uint32_t decode_cvt2(uint32_t w, bool hi) {
-    if constexpr (BF16)
-        return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
-                  : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-    else
-        return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))
-                  : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
-}
-// eight e4m3 bytes -> eight I/O dtype values in memory order
-template <bool BF16>
-__device__ __forceinline__ u32x4 decode_cvt8(uint32_t lo, uint32_t hi) {
-    return (u32x4){decode_cvt2<BF16>(lo, false), decode_cvt2<BF16>(lo, true), decode_cvt2<BF16>(hi, false), decode_cvt2<BF16>(hi, true)};
 }
 
 // FP8: the caches hold OCP e4m3 bytes (KV = bytes per cache element); q, o and the arithmetic stay in the I/O dtype.
@@ -322,7 +306,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
 #pragma unroll
                 for (int dc = 0; dc < DC; ++dc) {
                     u32x4 a;
-                    if constexpr (FP8) a = decode_cvt8<BF16>(kf[blk][dc >> 1][2 * (dc & 1)], kf[blk][dc >> 1][2 * (dc & 1) + 1]);
+                    if constexpr (FP8) a = cvt8_e4m3<BF16>(kf[blk][dc >> 1][2 * (dc & 1)], kf[blk][dc >> 1][2 * (dc & 1) + 1]);
                     else a = kf[blk][dc];
                     s[rt][blk] = decode_mfma<BF16>(a, qf[rt][dc], s[rt][blk]);
                 }
@@ -335,8 +319,8 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_kernel(const DecodeP
             const int ch = i * 64 + lane;
             if constexpr (FP8) {                       // 16 columns of a key: converted here, the slab holds the I/O dtype as ever
                 char* const dst = slab + (ch / VGR) * VROWB + (ch % VGR) * 32;
-                *reinterpret_cast<u32x4*>(dst) = decode_cvt8<BF16>(vr[i][0], vr[i][1]);
-                *reinterpret_cast<u32x4*>(dst + 16) = decode_cvt8<BF16>(vr[i][2], vr[i][3]);
+                *reinterpret_cast<u32x4*>(dst) = cvt8_e4m3<BF16>(vr[i][0], vr[i][1]);
+                *reinterpret_cast<u32x4*>(dst + 16) = cvt8_e4m3<BF16>(vr[i][2], vr[i][3]);
             } else {
                 *reinterpret_cast<u32x4*>(slab + (ch / GR) * VROWB + (ch % GR) * 16) = vr[i];
             }

@@ -11,6 +11,8 @@
 // are launched exactly like the dense ones (the host passes the stated maximum lengths as Nq / Nkv, which size the grids).
 // No trimmed instantiations, no KV-split, no hand-scheduled bodies: every head dim runs the full kernel of its padded head dim.
 // FA2_FAMILY_FWD_ONLY = 1 (prefill_hip.cpp, prefill_scoremod_hip.cpp: an inference call has no backward): the unit compiles and exports the forward alone.
+// FA2_FAMILY_MAX_HD (prefill_fp8_hip.cpp, prefill_fp8_scoremod_hip.cpp): the largest kernel head dim the unit instantiates; above it the launcher answers
+// FA2_ERR_HEAD_DIM (an instantiation that would need scratch memory is not compiled).  Default: all four.
 #ifndef FA2_FAMILY
 #error "define FA2_FAMILY (and the family's form macros) before including fa2_family_unit.h"
 #endif
@@ -25,15 +27,25 @@
 #ifndef FA2_FAMILY_FWD_ONLY
 #define FA2_FAMILY_FWD_ONLY 0
 #endif
+#ifndef FA2_FAMILY_MAX_HD
+#define FA2_FAMILY_MAX_HD 512
+#endif
 
-// The FA2_PAGED kernels take one further argument, the PagedKv block (fa2_prefill.h), and the FA2_SMOD kernels the ScoreMod block (fa2_scoremod.h), in this
-// order; the launchers pass them through.  Elsewhere the macros are empty.
+// The FA2_PAGED kernels take one further argument, the PagedKv block (fa2_prefill.h), the FA2_KV8 kernels the KvDescale block behind it, and the FA2_SMOD
+// kernels the ScoreMod block (fa2_scoremod.h), in this order; the launchers pass them through.  Elsewhere the macros are empty.
 #if FA2_PAGED
 #define FA2_FAMILY_PAGED_PARAMS , const fa2::PagedKv& pg
 #define FA2_FAMILY_PAGED_ARGS , pg
 #else
 #define FA2_FAMILY_PAGED_PARAMS
 #define FA2_FAMILY_PAGED_ARGS
+#endif
+#if FA2_KV8
+#define FA2_FAMILY_KV8_PARAMS , const fa2::KvDescale& kvd
+#define FA2_FAMILY_KV8_ARGS , kvd
+#else
+#define FA2_FAMILY_KV8_PARAMS
+#define FA2_FAMILY_KV8_ARGS
 #endif
 #if FA2_SMOD
 #define FA2_FAMILY_SMOD_PARAMS , const fa2::ScoreMod& sm
@@ -42,8 +54,8 @@
 #define FA2_FAMILY_SMOD_PARAMS
 #define FA2_FAMILY_SMOD_ARGS
 #endif
-#define FA2_FAMILY_MORE_PARAMS FA2_FAMILY_PAGED_PARAMS FA2_FAMILY_SMOD_PARAMS
-#define FA2_FAMILY_MORE_ARGS FA2_FAMILY_PAGED_ARGS FA2_FAMILY_SMOD_ARGS
+#define FA2_FAMILY_MORE_PARAMS FA2_FAMILY_PAGED_PARAMS FA2_FAMILY_KV8_PARAMS FA2_FAMILY_SMOD_PARAMS
+#define FA2_FAMILY_MORE_ARGS FA2_FAMILY_PAGED_ARGS FA2_FAMILY_KV8_ARGS FA2_FAMILY_SMOD_ARGS
 
 namespace {
 
@@ -85,8 +97,12 @@ int FA2_DT(FA2_FAMILY_NAME(launch_fwd_, FA2_FAMILY, ))(int HD, const FwdParams& 
     switch (HD) {
         case 64: return launch_fwd_hd<64>(p, rows, stream FA2_FAMILY_MORE_ARGS);
         case 128: return launch_fwd_hd<128>(p, rows, stream FA2_FAMILY_MORE_ARGS);
+#if FA2_FAMILY_MAX_HD >= 256
         case 256: return launch_fwd_hd<256>(p, rows, stream FA2_FAMILY_MORE_ARGS);
+#endif
+#if FA2_FAMILY_MAX_HD >= 512
         case 512: return launch_fwd_hd<512>(p, rows, stream FA2_FAMILY_MORE_ARGS);
+#endif
         default: return FA2_ERR_HEAD_DIM;
     }
 }

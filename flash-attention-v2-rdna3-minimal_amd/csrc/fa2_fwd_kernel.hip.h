@@ -100,6 +100,22 @@
 #else
 #define FA2_PAGED_PARAM
 #endif
+// FA2_KV8 = 1 (prefill_fp8_hip.cpp / prefill_fp8_scoremod_hip.cpp only, on top of FA2_PAGED = 1): the cache holds OCP e4m3 bytes (fa2_fwd_prefill_fp8).  K / V
+// tiles take the register form of the staging at every head dim — 8 bytes per 16-byte LDS granule, converted to the I/O dtype between the registers and
+// the ds_write (exact: cvt8_e4m3 below), so the LDS image and everything behind it are the 16-bit kernel's.  The cache's strides and every staging
+// address count bytes (kv_elem_t), k_descale[s, hkv] multiplies the score factor, v_descale[s, hkv] the epilogue's row factor; both are device data and
+// travel in a further kernel argument (KvDescale, fa2_prefill.h).
+#ifndef FA2_KV8
+#define FA2_KV8 0
+#endif
+#if FA2_KV8 && !FA2_PAGED
+#error "FA2_KV8 builds on the FA2_PAGED blocks"
+#endif
+#if FA2_KV8
+#define FA2_KV8_PARAM , const KvDescale kvd
+#else
+#define FA2_KV8_PARAM
+#endif
 
 // ---- tuning knobs (A/B-tested on MI355X with tools/kbench.py; numbers at B2 H16 N4096 D128 fp16) ----
 #ifndef FA2_DEFER_THR        // skip the O rescale while the row max grew by <= this (log2 units); <0: always rescale.
@@ -150,6 +166,14 @@ constexpr int kKvTile = 64;       // KV rows per tile
 // Buffer-load byte offset that is out of range for every head matrix (host.cpp keeps them below 2 GiB, and the
 // per-tile scalar offset added to it stays below 2 GiB too): lanes that stage columns >= D use it and receive 0.
 constexpr uint32_t kOobOffset = 0x80000000u;
+// One K / V element as the staging addresses it: 16 bits of the I/O dtype, or (FA2_KV8) one e4m3 byte.  An LDS granule is 8 elements either way.
+#if FA2_KV8
+typedef uint8_t kv_elem_t;
+#else
+typedef uint16_t kv_elem_t;
+#endif
+constexpr int kKvEs = (int)sizeof(kv_elem_t);      // bytes per element
+constexpr int kKvGranB = 8 * kKvEs;                // source bytes of one granule
 
 struct FwdParams {
     const void* q;
@@ -219,8 +243,8 @@ __device__ __forceinline__ VarlenSeq varlen_seq(const P& p, int s) {       // (s
     v.Nq = cq[s + 1] - v.q_base; v.Nkv = ck[s + 1] - v.k_base;
     return v;
 }
-// addressable bytes of n rows of `pitch` elements, D of them used (0 rows: nothing is addressable)
-__device__ __forceinline__ uint32_t varlen_bytes(int n, int64_t pitch, int D) { return n > 0 ? (uint32_t)(((int64_t)(n - 1) * pitch + D) * 2) : 0u; }
+// addressable bytes of n rows of `pitch` elements of `es` bytes, D of them used (0 rows: nothing is addressable)
+__device__ __forceinline__ uint32_t varlen_bytes(int n, int64_t pitch, int D, int es = 2) { return n > 0 ? (uint32_t)(((int64_t)(n - 1) * pitch + D) * es) : 0u; }
 // true: the block of rows from row0 on lies beyond the sequence's queries — the workgroup has nothing to do (uniform; before any barrier or LDS-DMA)
 __device__ __forceinline__ bool varlen_enter(FwdParams& p, Window& win, int s, int row0) {
     const VarlenSeq v = varlen_seq(p, s);
@@ -254,6 +278,15 @@ __device__ __forceinline__ bool paged_enter(FwdParams& p, const PagedKv& pg, Win
     p.lse += q_base;
     return false;
 }
+#if FA2_KV8
+// ... and the two descales of (sequence s, K / V head hkv), read once per workgroup: wave-uniform scalar loads, a null pointer stands for 1.0.  They are
+// device data: a NaN poisons the rows of its own (sequence, K / V head) and nothing else.
+__device__ __forceinline__ void paged_descales(const KvDescale& kvd, int s, int hkv, float& kd, float& vd) {
+    const int64_t at = (int64_t)s * kvd.s[0] + (int64_t)hkv * kvd.s[1];
+    kd = kvd.k ? kvd.k[at] : 1.0f;
+    vd = kvd.v ? kvd.v[at] : 1.0f;
+}
+#endif
 // Where the next tile to stage lies.  K and V each walk the workgroup's tiles [t0, t0 + ntiles) once, in order, with a cursor of their own: the tile's
 // page slot, its first row inside the page and its valid rows are running counters (prefill_tile_next: no division per tile), the page id of the current
 // slot is a register and the one of the next slot is loaded when the current slot is entered — a wave-uniform scalar load at least one tile ahead of its
@@ -279,14 +312,14 @@ __device__ __forceinline__ void paged_advance(PagedCursor& c, const PagedKv& pg,
         if (bt_row && c.at.slot + 1 <= c.last_slot) c.pid_next = bt_row[c.at.slot + 1];
     }
 }
-// The buffer descriptor of the cursor's tile: base = pool + page id * page stride + row in page * pitch (64 bits; `head` already points at the K / V head
-// inside page 0), records = the tile's valid rows — rows at or beyond the sequence's length read zeros whatever the cache holds there.  The page id is
+// The buffer descriptor of the cursor's tile: base = pool + page id * page stride + row in page * pitch (64 bits, in elements of the cache — bytes in
+// an e4m3 one; `head` already points at the K / V head inside page 0), records = the tile's valid rows — rows at or beyond the sequence's length read zeros whatever the cache holds there.  The page id is
 // clamped into the pool.  Every input is wave-uniform; readfirstlane says so to the compiler, so that the buffer loads take the descriptor from SGPRs.
-__device__ __forceinline__ auto paged_rsrc(const uint16_t* head, const PagedCursor& c, const PagedKv& pg, int64_t page_stride, int64_t pitch, int D) {
+__device__ __forceinline__ auto paged_rsrc(const kv_elem_t* head, const PagedCursor& c, const PagedKv& pg, int64_t page_stride, int64_t pitch, int D) {
     const int pid = prefill_clamp_page(c.pid, pg.num_pages);
     const uint64_t a = (uint64_t)(uintptr_t)(head + (int64_t)pid * page_stride + (int64_t)c.at.row * pitch);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    const uint32_t bytes = __builtin_amdgcn_readfirstlane(varlen_bytes(c.at.rows, pitch, D));
+    const uint32_t bytes = __builtin_amdgcn_readfirstlane(varlen_bytes(c.at.rows, pitch, D, kKvEs));
     return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), 0, bytes, 0x00020000);
 }
 #endif
@@ -317,6 +350,23 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
         return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
     else
         return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, f16x2));
+}
+
+// two e4m3 bytes (the low or the high half of w) -> two I/O dtype values, exact (v_cvt_scalef32_pk_{f16,bf16}_fp8 at scale 1: every finite e4m3 value
+// is a f16 and a bf16 value).  Shared by the decode kernels (fa2_decode.hip.h) and the FA2_KV8 staging below.
+template <bool BF16>
+__device__ __forceinline__ uint32_t cvt2_e4m3(uint32_t w, bool hi) {
+    if constexpr (BF16)
+        return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
+                  : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+    else
+        return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))
+                  : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
+}
+// eight e4m3 bytes -> eight I/O dtype values in memory order
+template <bool BF16>
+__device__ __forceinline__ u32x4 cvt8_e4m3(uint32_t lo, uint32_t hi) {
+    return (u32x4){cvt2_e4m3<BF16>(lo, false), cvt2_e4m3<BF16>(lo, true), cvt2_e4m3<BF16>(hi, false), cvt2_e4m3<BF16>(hi, true)};
 }
 
 __device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
@@ -433,8 +483,15 @@ __device__ __forceinline__ void block_to_head_qblock(const FwdParams& p, int bid
 #ifndef FA2_OCC128
 #define FA2_OCC128 2
 #endif
+#if FA2_KV8 && FA2_SMOD
+// (the 128-row score-modifier kernel of head dim 128 on an e4m3 cache: the 16-bit kernel's 245 registers plus the 16 staging registers of this mode do not
+//  fit 256 — 36 bytes of scratch per lane — so this one instantiation is compiled for one wave per SIMD, like the kernels of head dim 256)
+template <int HD, int NW, int QB, int BIAS>
+constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && HD <= 64) ? FA2_OCC64 : (NW + 3) / 4; }
+#else
 template <int HD, int NW, int QB, int BIAS>
 constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && HD <= 128) ? (HD <= 64 ? FA2_OCC64 : FA2_OCC128) : (NW + 3) / 4; }
+#endif
 
 //
 // KSQ / DTN / RTD (round 3, "trimmed" instantiations, fwd_hip.cpp): a head dim D below the kernel's HD keeps the LDS images and
@@ -450,7 +507,7 @@ constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && 
 // computes only the tiles of its own 32 rows' range [tf_w, ntiles_w), tiles cut by the band's left or right edge are masked per lane (lim_lo, lim_hi)
 // and the tiles in between run the unmasked steady-state loop.  A row that sees no key ends with O = 0, lse = -inf (the BIAS kernels' convention).
 template <int HD, int HDV, bool BF16, bool CAUSAL, int NW, int QB, int BIAS = 0, int KSQ = HD / 16, int DTN = HDV / 32, bool RTD = false>
-__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP FA2_PAGED_PARAM FA2_SMOD_PARAM) {
+__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP FA2_PAGED_PARAM FA2_KV8_PARAM FA2_SMOD_PARAM) {
 #if FA2_VARLEN
     FwdParams p = pk;         // (adjusted to the workgroup's sequence below: varlen_enter)
 #endif
@@ -503,6 +560,10 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     const int q0 = qblk * kRowsPerBlock;
 #if FA2_PAGED
     if (paged_enter(p, pg, win, b, q0)) return;   // b is the sequence; from here on p describes its queries and its key count (K / V: the whole cache)
+#if FA2_KV8
+    float kv_kd, kv_vd;
+    paged_descales(kvd, b, h / p.kv_group, kv_kd, kv_vd);
+#endif
 #elif FA2_VARLEN
     if (varlen_enter(p, win, b, q0)) return;      // b is the sequence (the batch strides are 0); from here on p describes that sequence alone
 #endif
@@ -544,11 +605,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     }
 
     // ---- K/V staging: buffer descriptors of this head's matrices (out-of-range rows read 0)
-    const uint32_t k_rowb = (uint32_t)p.ks[2] * 2u, v_rowb = (uint32_t)p.vs[2] * 2u;
+    const uint32_t k_rowb = (uint32_t)p.ks[2] * (uint32_t)kKvEs, v_rowb = (uint32_t)p.vs[2] * (uint32_t)kKvEs;
 #if FA2_PAGED
     // (one descriptor per tile: load_k / load_v below.  p.ks[0] / p.vs[0] are the page strides)
-    const uint16_t* khead = (const uint16_t*)p.k + (h / p.kv_group) * p.ks[1];
-    const uint16_t* vhead = (const uint16_t*)p.v + (h / p.kv_group) * p.vs[1];
+    const kv_elem_t* khead = (const kv_elem_t*)p.k + (h / p.kv_group) * p.ks[1];
+    const kv_elem_t* vhead = (const kv_elem_t*)p.v + (h / p.kv_group) * p.vs[1];
 #else
     const uint16_t* kbase = (const uint16_t*)p.k + b * p.ks[0] + (h / p.kv_group) * p.ks[1] + (int64_t)kv_first * p.ks[2];
     const uint16_t* vbase = (const uint16_t*)p.v + b * p.vs[0] + (h / p.kv_group) * p.vs[1] + (int64_t)kv_first * p.vs[2];
@@ -561,14 +622,14 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     for (int i = 0; i < NPASS; ++i) {
         const int idx = tid + kThreads * i;
         const int row = idx / G_::G, gi = idx % G_::G;
-        kg_off[i] = gi * 8 < p.D ? row * k_rowb + gi * 16 : kOobOffset;
+        kg_off[i] = gi * 8 < p.D ? row * k_rowb + gi * kKvGranB : kOobOffset;
         kw_off[i] = G_::k_off(row, gi);
     }
 #pragma unroll
     for (int i = 0; i < VNPASS; ++i) {
         const int idx = tid + kThreads * i;
         const int row = idx / GV_::G, gi = idx % GV_::G;
-        vg_off[i] = gi * 8 + vcol0 < p.D ? row * v_rowb + gi * 16 + vcol0 * 2 : kOobOffset;
+        vg_off[i] = gi * 8 + vcol0 < p.D ? row * v_rowb + gi * kKvGranB + vcol0 * kKvEs : kOobOffset;
         vw_off[i] = GV_::v_off(row, gi * 16);
     }
 
@@ -629,14 +690,23 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[qb][dt][r] = 0.f;
     }
+#if FA2_KV8
+    const float cs = p.c * kv_kd;        // (k_descale rides in the score factor: the scores, the cap and the LSE are those of the descaled keys)
+#else
     const float cs = p.c;                // factor of the raw Q.K^T product
+#endif
 #if FA2_SMOD
+#if FA2_KV8
+    const float smod_scale = smod.scale * kv_kd;
+#else
+    const float smod_scale = smod.scale;
+#endif
     const float c = kSmodLog2e;          // (the modified scores are scaled already, in natural units)
     // this workgroup's slope (one scalar load; packed calls: b is the sequence) and this lane's row's key position
     const float smod_slope = smod.slopes ? smod.slopes[(int64_t)b * smod.stride + h] : 0.f;
     const int smod_pos = qrow[0] + win.off;
 #else
-    const float c = BIAS ? 1.0f : p.c;   // factor still to be applied to a finished score (BIAS: already in log2 units)
+    const float c = BIAS ? 1.0f : cs;    // factor still to be applied to a finished score (BIAS: already in log2 units)
 #endif
 
     // ---- attention bias (BIAS kernels): the 32 values of this lane's row in one KV tile, as loaded (raw words), in the register
@@ -921,7 +991,8 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     // the granule that belongs at image slot (wave*64 + kThreads*i + l), i.e. the inverse of the k_off /
     // v_off swizzle (the image itself stays lane-linear).  The destination buffer must be free when the
     // load is ISSUED.  Register form: global -> VGPRs at issue, ds_write_b128 at the end of the step.
-    constexpr bool kDma = FA2_LDS_DMA && HD >= FA2_LDS_DMA_MIN_HD;
+    // (FA2_KV8: the register form at every head dim — a granule's 8 e4m3 bytes are two dwords per pass, converted at the write, once per workgroup)
+    constexpr bool kDma = FA2_LDS_DMA && HD >= FA2_LDS_DMA_MIN_HD && !FA2_KV8;
     uint32_t kd_off[NPASS], vd_off[VNPASS];
 #pragma unroll
     for (int i = 0; i < NPASS; ++i) {
@@ -937,7 +1008,22 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         const int gv = ((((slot >> 2) ^ ((row / GV_::RPB) & GV_::VMASK))) << 2) | (slot & 3);
         vd_off[i] = gv * 8 + vcol0 < p.D ? row * v_rowb + gv * 16 + vcol0 * 2 : kOobOffset;
     }
+#if FA2_KV8
+    u32x2 kreg[NPASS], vreg[VNPASS];
+    auto stage_load = [](auto rsrc, uint32_t voff, uint32_t soff) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, soff, 0); };
+    auto stage_image = [](const u32x2& r) __attribute__((always_inline)) { return cvt8_e4m3<BF16>(r[0], r[1]); };
+    // Pass i of a thread lies KRPP (VRPP) rows below its pass 0 in the same granule: the source offset of pass i is pass 0's plus a wave-uniform term,
+    // which rides in the load's soffset (a lane at kOobOffset stays out of range: the tile rule keeps the term below 2^31), and where the rows of a
+    // pass are a multiple of the swizzle's period the LDS offset is pass 0's plus a constant.  One offset register per tile image instead of NPASS:
+    // the staging registers of this mode have to fit beside the 16-bit kernel's working set.
+    constexpr int KRPP = kThreads / G_::G, VRPP = kThreads / GV_::G;
+    constexpr bool kKwLin = KRPP % G_::RPB == 0 && (KRPP / G_::RPB) % (G_::KMASK + 1) == 0;
+    constexpr bool kVwLin = VRPP % GV_::RPB == 0 && (VRPP / GV_::RPB) % (GV_::VMASK + 1) == 0;
+#else
     u32x4 kreg[NPASS], vreg[VNPASS];
+    auto stage_load = [](auto rsrc, uint32_t voff, uint32_t soff) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0); };
+    auto stage_image = [](const u32x4& r) __attribute__((always_inline)) { return r; };
+#endif
 #if FA2_PAGED
     // load_k / load_v are called once per tile of [0, ntiles), in order, K ahead of V: each stages the tile ITS cursor stands on and moves on (`tile` is
     // implied).  The descriptor is the tile's own, so the tile's byte offset is 0.
@@ -955,7 +1041,11 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 #pragma unroll
         for (int i = 0; i < NPASS; ++i) {
             if constexpr (kDma) dma16_to_lds(krs, smem + buf * TILEB + (wave * 64 + kThreads * i) * 16, FA2_TILE_OFF(kd_off[i], soff));
-            else kreg[i] = __builtin_amdgcn_raw_buffer_load_b128(krs, FA2_TILE_OFF(kg_off[i], soff), 0);
+#if FA2_KV8
+            else kreg[i] = stage_load(krs, kg_off[0], (uint32_t)(i * KRPP) * k_rowb);
+#else
+            else kreg[i] = stage_load(krs, FA2_TILE_OFF(kg_off[i], soff));
+#endif
         }
     };
     auto load_v = [&](int tile, int buf) __attribute__((always_inline)) {
@@ -969,19 +1059,31 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 #pragma unroll
         for (int i = 0; i < VNPASS; ++i) {
             if constexpr (kDma) dma16_to_lds(vrs, smem + VBASE + buf * VTILEB + (wave * 64 + kThreads * i) * 16, FA2_TILE_OFF(vd_off[i], soff));
-            else vreg[i] = __builtin_amdgcn_raw_buffer_load_b128(vrs, FA2_TILE_OFF(vg_off[i], soff), 0);
+#if FA2_KV8
+            else vreg[i] = stage_load(vrs, vg_off[0], (uint32_t)(i * VRPP) * v_rowb);
+#else
+            else vreg[i] = stage_load(vrs, FA2_TILE_OFF(vg_off[i], soff));
+#endif
         }
     };
     auto write_k = [&](int buf) __attribute__((always_inline)) {
         if constexpr (!kDma) {
 #pragma unroll
-            for (int i = 0; i < NPASS; ++i) *(u32x4*)(smem + buf * TILEB + kw_off[i]) = kreg[i];
+#if FA2_KV8
+            for (int i = 0; i < NPASS; ++i) *(u32x4*)(smem + buf * TILEB + (kKwLin ? kw_off[0] + i * KRPP * ROWB : kw_off[i])) = stage_image(kreg[i]);
+#else
+            for (int i = 0; i < NPASS; ++i) *(u32x4*)(smem + buf * TILEB + kw_off[i]) = stage_image(kreg[i]);
+#endif
         }
     };
     auto write_v = [&](int buf) __attribute__((always_inline)) {
         if constexpr (!kDma) {
 #pragma unroll
-            for (int i = 0; i < VNPASS; ++i) *(u32x4*)(smem + VBASE + buf * VTILEB + vw_off[i]) = vreg[i];
+#if FA2_KV8
+            for (int i = 0; i < VNPASS; ++i) *(u32x4*)(smem + VBASE + buf * VTILEB + (kVwLin ? vw_off[0] + i * VRPP * VROWB : vw_off[i])) = stage_image(vreg[i]);
+#else
+            for (int i = 0; i < VNPASS; ++i) *(u32x4*)(smem + VBASE + buf * VTILEB + vw_off[i]) = stage_image(vreg[i]);
+#endif
         }
     };
 
@@ -1025,12 +1127,12 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float t;
-                    s0[r] = smod_cap(s0[r] * smod.scale, smod.softcap, smod.inv_softcap, &t);
-                    s1[r] = smod_cap(s1[r] * smod.scale, smod.softcap, smod.inv_softcap, &t);
+                    s0[r] = smod_cap(s0[r] * smod_scale, smod.softcap, smod.inv_softcap, &t);
+                    s1[r] = smod_cap(s1[r] * smod_scale, smod.softcap, smod.inv_softcap, &t);
                 }
             } else {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { s0[r] *= smod.scale; s1[r] *= smod.scale; }
+                for (int r = 0; r < 16; ++r) { s0[r] *= smod_scale; s1[r] *= smod_scale; }
             }
             if (smod.slopes) {
                 // pos - j of register r: d - (r & 3) - 8 (r >> 2) (- 32); |.| is a source modifier of the fma (free, whatever the band)
@@ -1316,6 +1418,8 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         const float l_tot = half_swap_sum(l_run[0]);
 #if FA2_DROP
         const float inv_l = !(l_tot > 0.f) ? 0.f : drop.rs / l_tot;          // ... and the kept probabilities scaled by 1 / (1 - p_eff)
+#elif FA2_KV8
+        const float inv_l = !(l_tot > 0.f) ? 0.f : kv_vd / l_tot;            // ... and v_descale: the f32 row is scaled before its one rounding
 #elif FA2_WIN
         const float inv_l = !(l_tot > 0.f) ? 0.f : 1.0f / l_tot;             // row that sees no key: O = 0 (lse = -inf)
 #else
@@ -1354,6 +1458,8 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         const float l_tot = half_swap_sum(l_run[qb]);
 #if FA2_DROP
         const float inv_l = !(l_tot > 0.f) ? 0.f : drop.rs / l_tot;
+#elif FA2_KV8
+        const float inv_l = !(l_tot > 0.f) ? 0.f : kv_vd / l_tot;
 #elif FA2_WIN
         const float inv_l = !(l_tot > 0.f) ? 0.f : 1.0f / l_tot;
 #else

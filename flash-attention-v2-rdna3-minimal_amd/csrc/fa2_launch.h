@@ -234,6 +234,14 @@ FA2_BWD_SMOD_LAUNCHER(launch_bwd_varlen_scoremod)
 FA2_LAUNCHER(launch_fwd_prefill, (int HD, const FwdParams& p, int rows, hipStream_t stream, const PagedKv& pg), (HD, p, rows, stream, pg))
 FA2_LAUNCHER(launch_fwd_prefill_scoremod, (int HD, const FwdParams& p, int rows, hipStream_t stream, const PagedKv& pg, const ScoreMod& sm),
              (HD, p, rows, stream, pg, sm))
+// ... on e4m3 caches (prefill_fp8_hip.cpp, prefill_fp8_scoremod_hip.cpp; fa2_fwd_prefill_fp8): the KV8 forms of the same kernels, with the KvDescale block
+// (fa2_prefill.h) behind PagedKv; the cache's strides count bytes.  Kernel head dims up to kPrefillFp8MaxHD: above, FA2_ERR_HEAD_DIM
+constexpr int kPrefillFp8MaxHD = 256;
+FA2_LAUNCHER(launch_fwd_prefill_fp8, (int HD, const FwdParams& p, int rows, hipStream_t stream, const PagedKv& pg, const KvDescale& kvd),
+             (HD, p, rows, stream, pg, kvd))
+FA2_LAUNCHER(launch_fwd_prefill_fp8_scoremod,
+             (int HD, const FwdParams& p, int rows, hipStream_t stream, const PagedKv& pg, const KvDescale& kvd, const ScoreMod& sm),
+             (HD, p, rows, stream, pg, kvd, sm))
 // hand-scheduled backward, head dim exactly 128 (bwd_asm.cpp); same `parts`
 // neg_delta: the dQ pass writes -delta (the hand-scheduled dK/dV pass reads it as such; the HIP dK/dV passes read +delta)
 // kfold: the dK / dV body whose P side folds scale * log2(e) into its K fragments (option "fold"; host.cpp: bwd_folds)

@@ -29,6 +29,14 @@ struct PagedKv {
     int capacity_keys = 0;               // key slots of one sequence: every length is clamped into [0, capacity_keys]
 };
 
+// What a prefill call on an e4m3 cache adds to that (fa2_fwd_prefill_fp8; the FA2_KV8 kernels alone take it, as one more kernel argument behind PagedKv,
+// so the 16-bit kernels keep their kernarg segment): the per (sequence, K / V head) descales, device data like the lengths.
+struct KvDescale {
+    const float* k = nullptr;            // k_descale [B, Hkv] f32, device memory; nullptr: 1.0
+    const float* v = nullptr;            // v_descale, likewise
+    int64_t s[2] = {0, 0};               // their element strides {sequence, K / V head}
+};
+
 // keys per page as the kernels count them
 FA2_PREFILL_HD inline int prefill_page_keys(int page_size, int64_t capacity_keys) {
     return page_size > 0 ? page_size : (int)((capacity_keys + kPrefillTile - 1) / kPrefillTile * kPrefillTile);

@@ -1865,8 +1865,12 @@ int fa2_kvcache_append_varlen(int dtype, int cache_format, const void* k_new, co
 
 // ---- chunked prefill against a KV cache: include/fa2_gfx950.h has the contract, csrc/fa2_prefill.h the tile arithmetic, prefill_hip.cpp /
 // prefill_scoremod_hip.cpp the kernels (the FA2_PAGED forms of the packed forward).  One call, described: the entry fills it by field name, the plan
-// query the sizes alone.  The checks run in decode's class order.
+// query the sizes alone.  The checks run in decode's class order.  fa2_fwd_prefill_fp8 (prefill_fp8_hip.cpp, prefill_fp8_scoremod_hip.cpp: the KV8 forms) is
+// the same call with the cache format its entry serves: an e4m3 cache's strides count bytes, its head dims are multiples of 16 up to the largest compiled
+// one, and its descales are checked where decode's are (CacheDesc).
 struct PrefillCall : CacheDesc {
+    int serves = FA2_CACHE_16BIT;                    // the cache format of the entry: any other stated format is FA2_ERR_DTYPE
+    bool kv8() const { return serves == FA2_CACHE_E4M3; }
     int dtype = 0, B = 0, H = 0, Hkv = 0, max_q = 0, D = 0;
     const void* q = nullptr;
     void* o = nullptr;
@@ -1890,7 +1894,7 @@ static int prefill_check_shape(const PrefillCall& c, int* HD) {
     const int cap = (int)c.capacity_keys(), n = c.max_q > cap ? c.max_q : cap;
     if (!fa2::window_args_ok(c.max_q, cap, c.window_left, 0, -n, true)) return FA2_ERR_BAD_SHAPE;
     *HD = fa2_padded_head_dim(c.D);
-    if (*HD < 0 || (c.D & 7)) return FA2_ERR_HEAD_DIM;
+    if (*HD < 0 || (c.D & (c.kv8() ? 15 : 7)) || (c.kv8() && *HD > fa2::kPrefillFp8MaxHD)) return FA2_ERR_HEAD_DIM;
     return FA2_OK;
 }
 
@@ -1901,10 +1905,11 @@ static int prefill_rows(const PrefillCall& c, int HD) {
     return HD > 128 ? 128 : pick_rows(p);
 }
 
-int fa2_fwd_prefill_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan) {
+static int prefill_plan(int serves, int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan) {
     if (!plan) return FA2_ERR_NULL_POINTER;
     std::memset(plan, 0, sizeof(*plan));
     PrefillCall c;
+    c.serves = serves;
     c.dtype = dtype; c.B = B; c.H = H; c.Hkv = Hkv; c.max_q = max_seqlen_q; c.D = D; c.capacity = capacity; c.page_size = page_size;
     int HD = 0;
     if (int rc = prefill_check_shape(c, &HD)) return rc;
@@ -1915,6 +1920,14 @@ int fa2_fwd_prefill_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int
     plan->rows = prefill_rows(c, HD);
     plan->heads_main = B * H;
     return FA2_OK;
+}
+
+int fa2_fwd_prefill_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan) {
+    return prefill_plan(FA2_CACHE_16BIT, dtype, B, H, Hkv, max_seqlen_q, D, capacity, page_size, plan);
+}
+
+int fa2_fwd_prefill_fp8_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan) {
+    return prefill_plan(FA2_CACHE_E4M3, dtype, B, H, Hkv, max_seqlen_q, D, capacity, page_size, plan);
 }
 
 int fa2_prefill_tile(int64_t len, int capacity, int page_size, int tile, int* page_slot, int* row_in_page, int* valid_rows) {
@@ -1933,7 +1946,8 @@ static int prefill_run(const PrefillCall& c) {
     if (any_null({c.q, c.o, c.lse, c.cu_q, c.lens, c.qs, c.os}) || cache_null(c)) return FA2_ERR_NULL_POINTER;
     int HD = 0;
     // one tile's rows must stay below the byte offset that stands for "out of range" (kOobOffset), whatever else the pool spans
-    const auto tile_ok = [](const int64_t* s) { return s[2] <= 0 || (int64_t)fa2::kKvTile * s[2] * 2 < (int64_t)fa2::kOobOffset; };
+    const int64_t es = c.kv8() ? 1 : 2;              // bytes per cache element
+    const auto tile_ok = [es](const int64_t* s) { return s[2] <= 0 || (int64_t)fa2::kKvTile * s[2] * es < (int64_t)fa2::kOobOffset; };
     if (c.lse_stride < 0 || c.slope_stride < 0 || !cache_extent_ok(c) || !tile_ok(c.ks) || !tile_ok(c.vs)) return FA2_ERR_BAD_SHAPE;
     if (int rc = prefill_check_shape(c, &HD)) return rc;
     const auto strides2_ok = [](const int64_t* s) { return s[0] % 8 == 0 && s[1] % 8 == 0 && s[1] > 0; };
@@ -1941,7 +1955,7 @@ static int prefill_run(const PrefillCall& c) {
         ((reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.cu_q) | reinterpret_cast<uintptr_t>(c.lens) |
           reinterpret_cast<uintptr_t>(c.slopes)) & 3u) || !strides2_ok(c.qs) || !strides2_ok(c.os))
         return FA2_ERR_ALIGNMENT;
-    if ((c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) || c.format != FA2_CACHE_16BIT || !cache_format_ok(c)) return FA2_ERR_DTYPE;
+    if ((c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) || c.format != c.serves || !cache_format_ok(c)) return FA2_ERR_DTYPE;
     if (!std::isfinite(c.scale)) return FA2_ERR_SCALE;
     if (!fa2::softcap_ok(c.softcap)) return FA2_ERR_SOFTCAP;
     if ((int64_t)c.B * c.H * ((c.max_q + 127) / 128) > 0x7fffffffLL) return FA2_ERR_GRID;
@@ -1977,6 +1991,15 @@ static int prefill_run(const PrefillCall& c) {
     const int rows = prefill_rows(c, HD);
     const bool bf16 = c.dtype == FA2_DTYPE_BF16;
     hipStream_t const stream = (hipStream_t)c.stream;
+    if (c.kv8()) {
+        fa2::KvDescale kvd;
+        kvd.k = c.kd; kvd.v = c.vd;
+        if (c.descaled()) { kvd.s[0] = c.ds[0]; kvd.s[1] = c.ds[1]; }
+        if (c.softcap > 0.f || c.slopes)
+            return fa2::launch_fwd_prefill_fp8_scoremod(bf16, HD, p, rows, stream, pg, kvd,
+                                                        fa2::make_scoremod(c.softcap, c.scale, c.slopes, c.slopes ? c.slope_stride : 0));
+        return fa2::launch_fwd_prefill_fp8(bf16, HD, p, rows, stream, pg, kvd);
+    }
     if (c.softcap > 0.f || c.slopes)
         return fa2::launch_fwd_prefill_scoremod(bf16, HD, p, rows, stream, pg, fa2::make_scoremod(c.softcap, c.scale, c.slopes, c.slopes ? c.slope_stride : 0));
     return fa2::launch_fwd_prefill(bf16, HD, p, rows, stream, pg);
@@ -1992,6 +2015,23 @@ int fa2_fwd_prefill(int dtype, int cache_format, const void* q, const void* k_ca
     c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
     c.q = q; c.k = k_cache; c.v = v_cache; c.o = o; c.lse = lse; c.cu_q = cu_seqlens_q; c.lens = cache_seqlens; c.block_table = block_table;
     c.qs = q_strides; c.ks = k_strides; c.vs = v_strides; c.os = o_strides; c.lse_stride = lse_stride; c.bts = block_table_stride;
+    c.scale = scale; c.window_left = window_left; c.softcap = softcap; c.slopes = alibi_slopes; c.slope_stride = alibi_stride; c.stream = hip_stream;
+    return prefill_run(c);
+}
+
+int fa2_fwd_prefill_fp8(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cu_seqlens_q,
+                        const int* cache_seqlens, const int* block_table, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size,
+                        int num_pages, const int64_t q_strides[2], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[2],
+                        int64_t lse_stride, int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale,
+                        const int64_t descale_strides[2], int window_left, float softcap, const float* alibi_slopes, int64_t alibi_stride,
+                        void* hip_stream) {
+    PrefillCall c;
+    c.serves = c.format = FA2_CACHE_E4M3;
+    c.dtype = dtype; c.B = B; c.H = H; c.Hkv = Hkv; c.max_q = max_seqlen_q; c.D = D;
+    c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    c.q = q; c.k = k_cache; c.v = v_cache; c.o = o; c.lse = lse; c.cu_q = cu_seqlens_q; c.lens = cache_seqlens; c.block_table = block_table;
+    c.qs = q_strides; c.ks = k_strides; c.vs = v_strides; c.os = o_strides; c.lse_stride = lse_stride; c.bts = block_table_stride;
+    c.kd = k_descale; c.vd = v_descale; c.ds = descale_strides;
     c.scale = scale; c.window_left = window_left; c.softcap = softcap; c.slopes = alibi_slopes; c.slope_stride = alibi_stride; c.stream = hip_stream;
     return prefill_run(c);
 }

@@ -24,7 +24,7 @@ import torch
 
 from . import _fa2_lib
 
-__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill",
+__all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
            "kvcache_append_varlen"]
 
 
@@ -1489,17 +1489,56 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
     kvcache_append_varlen runs before the append launch, so a call they refuse leaves the caches as they were; what only the C entry refuses after that
     (a window or a grid beyond its limits) leaves caches that hold the new tokens.  With none of the five keywords the call makes exactly the launches it
     made before they existed.
-    float8_e4m3fn caches and k_descale / v_descale raise ValueError: 16-bit caches only (kvcache_append_varlen alone writes e4m3 caches, for
-    flash_attention_decode to read).  C-ABI fa2_fwd_prefill."""
+    float8_e4m3fn caches and k_descale / v_descale raise ValueError: 16-bit caches only (flash_attention_prefill_fp8 serves e4m3 caches).
+    C-ABI fa2_fwd_prefill."""
     who = "flash_attention_prefill"
+    _prefill_tensors(who, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens)
+    if _cache_format(who, q, k_cache, v_cache, None, None) or k_descale is not None or v_descale is not None:
+        raise ValueError("fa2: %s serves 16-bit caches only (fp16 / bf16, q's dtype): float8_e4m3fn caches and k_descale / v_descale are "
+                         "flash_attention_decode's" % who)
+    return _prefill(who, False, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, max_seqlen_q, scale, window, softcap, alibi_slopes,
+                    return_lse, None, None, k, v, rotary_cos, rotary_sin, rotary_interleaved)
+
+
+_PREFILL_FP8_MAX_D = 256        # the largest head dim fa2_fwd_prefill_fp8 has a kernel for (the head-dim-512 one would need scratch memory)
+
+
+def flash_attention_prefill_fp8(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, max_seqlen_q=None, scale=None, window=None, softcap=0.0,
+                                alibi_slopes=None, return_lse=False, k_descale=None, v_descale=None, k=None, v=None, rotary_cos=None, rotary_sin=None,
+                                rotary_interleaved=True):
+    """flash_attention_prefill against a float8_e4m3fn KV cache — the cache kvcache_append_varlen quantises into and flash_attention_decode reads — so a
+    server that keeps its cache in e4m3 uses cached prefix pages, chunks a prompt and mixes prefill chunks with decode rows without dequantising a copy.
+    Everything is flash_attention_prefill's, with K = float(k_cache) * k_descale[s, hkv] and V = float(v_cache) * v_descale[s, hkv]; what differs:
+    k_cache / v_cache must both be torch.float8_e4m3fn (OCP e4m3; e5m2, the fnuz formats and 16-bit caches raise ValueError) with a contiguous head dim,
+    16-byte aligned storage and strides that are multiples of 16 elements (flash_attention_decode's rules for e4m3).  q stays fp16 / bf16.
+    k_descale / v_descale: float32 [B, Hkv] on q's device, each optional, None = 1.0.  They are device data the host never reads, like cache_seqlens: a
+    captured graph replays correctly after they changed in place.  softcap caps the descaled, scaled score; o and lse are those of the descaled K / V.
+    D must be a multiple of 16, at most 256: there is no padding path (it would copy the caches), and no kernel above 256.
+    Append: with k / v [total_q, Hkv, D] (fp16 / bf16) the call first runs kvcache_append_varlen with the same descales — which quantises the new tokens
+    into the cache — and then attends, on one stream; every argument check of both runs before the first launch.
+    With descales that are null or powers of two in [1/8, 8] the result equals flash_attention_prefill's on the dequantised 16-bit cache bit for bit.
+    C-ABI fa2_fwd_prefill_fp8."""
+    who = "flash_attention_prefill_fp8"
+    _prefill_tensors(who, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens)
+    if not _cache_format(who, q, k_cache, v_cache, k_descale, v_descale):
+        raise ValueError("fa2: %s serves float8_e4m3fn caches only, got %s %s: 16-bit caches are flash_attention_prefill's" % (who, k_cache.dtype, v_cache.dtype))
+    return _prefill(who, True, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, max_seqlen_q, scale, window, softcap, alibi_slopes,
+                    return_lse, k_descale, v_descale, k, v, rotary_cos, rotary_sin, rotary_interleaved)
+
+
+def _prefill_tensors(who, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens):
+    """The first two checks of the prefill calls: the tensors' ranks, and inference only"""
     if not all(torch.is_tensor(t) for t in (q, k_cache, v_cache, cu_seqlens_q, cache_seqlens)) or q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("fa2: %s takes q [total_q, H, D], 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] with a "
                          "block_table), cu_seqlens_q and cache_seqlens" % who)
     if torch.is_grad_enabled() and (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad):
         raise ValueError("fa2: %s is inference only (an input requires grad); flash_attention_varlen on packed keys is differentiable" % who)
-    if _cache_format(who, q, k_cache, v_cache, None, None) or k_descale is not None or v_descale is not None:
-        raise ValueError("fa2: %s serves 16-bit caches only (fp16 / bf16, q's dtype): float8_e4m3fn caches and k_descale / v_descale are "
-                         "flash_attention_decode's" % who)
+
+
+def _prefill(who, fp8, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, max_seqlen_q, scale, window, softcap, alibi_slopes, return_lse,
+             k_descale, v_descale, k, v, rotary_cos, rotary_sin, rotary_interleaved):
+    """flash_attention_prefill (fp8 = False: 16-bit caches, no descales) and flash_attention_prefill_fp8 (fp8 = True) behind their cache-format checks:
+    the argument checks both share, the fused append, the launch."""
     fused = k is not None or v is not None
     if not fused and (rotary_cos is not None or rotary_sin is not None):
         raise ValueError("fa2: rotary_cos / rotary_sin rotate the appended tokens: %s takes them together with k and v (rotary without an append is "
@@ -1511,6 +1550,9 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
     _check_groups(H, Hkv)
     if D < 1 or D > _MAX_HEAD_DIM:
         raise ValueError("fa2: %s serves head dims 1 .. %d, got %d" % (who, _MAX_HEAD_DIM, D))
+    if fp8 and (D % 16 or D > _PREFILL_FP8_MAX_D):
+        raise ValueError("fa2: %s serves head dims that are multiples of 16 up to %d (no padding path: it would copy the caches), got %d"
+                         % (who, _PREFILL_FP8_MAX_D, D))
     if fused:
         if not all(torch.is_tensor(t) and t.dim() == 3 and t.dtype == q.dtype and tuple(t.shape) == (total_q, Hkv, D) for t in (k, v)):
             raise ValueError("fa2: %s takes k and v together, [total_q, Hkv, D] = [%d, %d, %d] in q's dtype: the new tokens are the query rows' own "
@@ -1544,15 +1586,26 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
         raise ValueError("fa2: max_seqlen_q is None or a non-negative int, got %r" % (max_seqlen_q,))
     window_left = _fa2_lib.parse_window(window)[0]
     scoremod = _parse_scoremod(softcap, alibi_slopes, q, H, B)
-    aux = (cu_seqlens_q, cache_seqlens) if block_table is None else (cu_seqlens_q, cache_seqlens, block_table)
+    descales = tuple(d for d in (k_descale, v_descale) if d is not None)          # (fp8 alone)
+    for d in descales:
+        if not torch.is_tensor(d) or d.dtype != torch.float32 or tuple(d.shape) != (B, Hkv):
+            raise ValueError("fa2: k_descale / v_descale must be float32 tensors of shape [B, Hkv] = [%d, %d], got %s"
+                             % (B, Hkv, "%s %s" % (d.dtype, tuple(d.shape)) if torch.is_tensor(d) else repr(d)))
+    aux = ((cu_seqlens_q, cache_seqlens) if block_table is None else (cu_seqlens_q, cache_seqlens, block_table)) + descales
     if not all(t.is_cuda for t in (q, k_cache, v_cache) + aux):
         raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on a ROCm device (no CPU path in this operator)")
     if any(t.device != q.device for t in (k_cache, v_cache) + aux):
         raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on the same device")
-    d_pad = -D % 8                 # (0 in a fused call: its check above)
+    d_pad = 0 if fp8 else -D % 8   # (0 in a fused call: its check above)
     if d_pad:
         q, k_cache, v_cache = (torch.nn.functional.pad(t, (0, d_pad)) for t in (q, k_cache, v_cache))
-    if not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
+    if fp8:
+        if not _decode_strides_ok(k_cache, 16) or not _decode_strides_ok(v_cache, 16):
+            raise ValueError("fa2: float8_e4m3fn k_cache / v_cache need a contiguous head dim, strides that are multiples of 16 elements and 16-byte "
+                             "aligned storage")
+        if len(descales) == 2 and k_descale.stride() != v_descale.stride():       # the C-ABI takes one stride pair: a device copy, nothing read back
+            k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
+    elif not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
         raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
     if max_seqlen_q is None:
         max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max())
@@ -1562,7 +1615,7 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
         if not math.isfinite(float(scale)):
             raise ValueError("fa2: %s needs a finite scale, got %r" % (who, scale))
         q_rot = kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved,
-                                      q=q if rotary_cos is not None else None)
+                                      k_descale, v_descale, q=q if rotary_cos is not None else None)
         q = q if q_rot is None else q_rot
     q = _packed_ready(q)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
@@ -1572,13 +1625,19 @@ def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, bl
         code = _fa2_lib.FA2_DTYPE_F16 if q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
         dev = q.device.index if q.device.index is not None else _current_device()
         s3 = _fa2_lib.strides3
+        head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(),
+                None if block_table is None else block_table.data_ptr(), B, H, Hkv, int(max_seqlen_q), D + d_pad, capacity, page_size, num_pages, _s2(q),
+                s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)), s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)),
+                _s2(o), lse.stride(0), 0 if block_table is None else block_table.stride(0), float(scale))
         with torch.cuda.device(dev):
-            rc = lib.fa2_fwd_prefill(code, _fa2_lib.FA2_CACHE_16BIT, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(),
-                                     cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(), None if block_table is None else block_table.data_ptr(),
-                                     B, H, Hkv, int(max_seqlen_q), D + d_pad, capacity, page_size, num_pages, _s2(q),
-                                     s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)), s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)),
-                                     _s2(o), lse.stride(0), 0 if block_table is None else block_table.stride(0), float(scale), window_left,
-                                     *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), _raw_stream(dev))
+            tail = (window_left, *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), _raw_stream(dev))
+            if fp8:
+                d0 = k_descale if k_descale is not None else v_descale
+                rc = lib.fa2_fwd_prefill_fp8(code, *head, None if k_descale is None else k_descale.data_ptr(),
+                                             None if v_descale is None else v_descale.data_ptr(),
+                                             None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), *tail)
+            else:
+                rc = lib.fa2_fwd_prefill(code, _fa2_lib.FA2_CACHE_16BIT, *head, *tail)
         _fa2_lib.check(rc)
     elif total_q:                  # (a stated maximum of 0: no row is computed)
         o.zero_()

@@ -176,6 +176,11 @@ SYMBOLS = {
     "fa2_fwd_prefill": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8 + [ctypes.c_int] * 8 + [_i64p] * 4 + [ctypes.c_int64] * 2 +
                         [ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "fa2_fwd_prefill_plan": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(FwdPlan)]),
+    # ... on e4m3 caches: no cache_format, k_descale v_descale descale_strides after scale
+    "fa2_fwd_prefill_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 8 + [ctypes.c_int] * 8 + [_i64p] * 4 + [ctypes.c_int64] * 2 +
+                            [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, _i64p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64,
+                             ctypes.c_void_p]),
+    "fa2_fwd_prefill_fp8_plan": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(FwdPlan)]),
     "fa2_prefill_tile": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 3),
     "fa2_kvappend_slot": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     # ... packed (ragged): cu_seqlens before cache_seqlens, B total(int64) Hkv D capacity page_size num_pages, stride PAIRS {head, row} for k_new v_new q
@@ -435,6 +440,13 @@ def prefill_plan(dtype, B, H, Hkv, max_seqlen_q, D, capacity, page_size=0):
     """fa2_fwd_prefill_plan: the kernel, the contract and the rows per workgroup of a prefill call (dtype: an FA2_DTYPE_* code)."""
     plan = FwdPlan()
     check(load().fa2_fwd_prefill_plan(int(dtype), int(B), int(H), int(Hkv), int(max_seqlen_q), int(D), int(capacity), int(page_size), ctypes.byref(plan)))
+    return plan.as_dict()
+
+
+def prefill_fp8_plan(dtype, B, H, Hkv, max_seqlen_q, D, capacity, page_size=0):
+    """fa2_fwd_prefill_fp8_plan: prefill_plan's answer for the call on an e4m3 cache (head dims: multiples of 16 up to 256)."""
+    plan = FwdPlan()
+    check(load().fa2_fwd_prefill_fp8_plan(int(dtype), int(B), int(H), int(Hkv), int(max_seqlen_q), int(D), int(capacity), int(page_size), ctypes.byref(plan)))
     return plan.as_dict()
 
 

@@ -951,7 +951,7 @@ int fa2_fwd_varlen_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int 
  *   k_cache, v_cache: 16-bit caches of `dtype` in fa2_fwd_decode's two layouts: [B, capacity, Hkv, D] (page_size = 0, capacity = key slots per sequence)
  *                     or a pool [num_pages, page_size, Hkv, D] under an int32 block_table [B, capacity] (page_size a multiple of 64, capacity =
  *                     block-table entries per sequence).  Element strides {batch | page, head, row}.  cache_format must be FA2_CACHE_16BIT: e4m3 caches
- *                     are FA2_ERR_DTYPE (the kernels stage K / V tiles by LDS-DMA, which cannot convert).
+ *                     are FA2_ERR_DTYPE here (fa2_fwd_prefill_fp8 below serves them).
  *   window_left     : -1 (none) or >= 0.  softcap, alibi_slopes (f32 [H] or [B, H], device memory), alibi_stride: fa2_fwd_decode_window's.
  * Masking is decode's: bottom-right causal per sequence — row i of sequence s sits at key position len_s - Nq_s + i and attends the keys j with
  * pos - window_left <= j <= pos.  Rows at a negative position (Nq_s > len_s) return zeros and lse = -inf.  The host reads neither cache_seqlens nor
@@ -983,6 +983,35 @@ int fa2_fwd_prefill(int dtype, int cache_format, const void* q, const void* k_ca
                     const float* alibi_slopes, int64_t alibi_stride, void* hip_stream);
 /* The plan of the call above: kernel = FA2_KERNEL_HIP_PREFILL, contract 0, rows as launched, heads_main = B * H.  Sizes and dtype are checked as above. */
 int fa2_fwd_prefill_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan);
+
+/* ---- ... on e4m3 caches with per (sequence, K / V head) descales: the cache fa2_kvcache_append_varlen writes with FA2_CACHE_E4M3 and fa2_fwd_decode_fp8
+ * reads.  Everything is fa2_fwd_prefill's with K = float(k_cache) * k_descale[s, hkv] and V = float(v_cache) * v_descale[s, hkv]; what differs:
+ *   k_cache, v_cache: OCP e4m3 bytes in the same two layouts; their element strides count bytes, as in fa2_fwd_decode_fp8.
+ *   k_descale, v_descale: f32 [B, Hkv] in device memory with element strides descale_strides = {sequence, K / V head}; either may be null (= 1.0).  They are
+ *                     read on the device, once per workgroup: a captured call is replayed as they change in place.  k_descale multiplies the score
+ *                     factor, so soft-capping sees the descaled score and the LSE is that of the descaled scores; v_descale multiplies the normalised
+ *                     f32 row before its one rounding.  A NaN descale poisons the rows of its own (sequence, K / V head) and nothing else.
+ * Safety: fa2_fwd_prefill's rules.  A tile's descriptor ends at the sequence's last valid row, in bytes: rows at or beyond the length read zero bytes
+ * (= +0.0) whatever the cache holds there, the e4m3 NaN codes 0x7f / 0xff included.
+ * Addressing: fa2_fwd_prefill's, in bytes: one tile, 64 * row stride bytes, must stay below 2^31 (FA2_ERR_BAD_SHAPE).
+ * Checks, in fa2_fwd_prefill's class order, with fa2_fwd_decode_fp8's additions where their kind is: null pointers (+ descale_strides when a descale is
+ * given); sizes (+ a negative descale stride; the tile rule in bytes); head dim (FA2_ERR_HEAD_DIM: D a multiple of 16 up to 256 — the kernel of head dim
+ * 512 would keep its e4m3 staging registers in scratch memory and is not compiled, so 256 < D <= 512 is refused here while fa2_fwd_prefill takes it);
+ * alignment (16-byte caches whose strides are multiples of 16, 4-byte descales); dtype (f16 / bf16); scale; softcap; FA2_ERR_GRID.
+ * Kernels (FA2_KERNEL_HIP_PREFILL, contract 0): fa2_fwd_prefill's with the register form of the K / V staging at every head dim — a 16-byte LDS granule
+ * is fetched as its 8 e4m3 bytes and converted to `dtype` in registers, exactly, before the LDS write; everything after the LDS image is shared.  With
+ * descales that are null or powers of two in [1/8, 8] (every finite e4m3 value times such a factor is a f16 and a bf16 value) the results equal
+ * fa2_fwd_prefill's on the 16-bit cache (float(cache) * descale) BIT FOR BIT.  Rows per workgroup: fa2_fwd_prefill's rule.  No KV-split. */
+int fa2_fwd_prefill_fp8(int dtype, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse,
+                        const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                        int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, int num_pages,
+                        const int64_t q_strides[2], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[2],
+                        int64_t lse_stride, int64_t block_table_stride, float scale,
+                        const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                        int window_left, float softcap, const float* alibi_slopes, int64_t alibi_stride, void* hip_stream);
+/* The plan of the call above: fa2_fwd_prefill_plan's answer on the same shape, with the head-dim rule of the e4m3 call. */
+int fa2_fwd_prefill_fp8_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int D, int capacity, int page_size, fa2_fwd_plan_t* plan);
+
 /* Where 64-key tile `tile` of a sequence lies — the host side of the one function the kernel calls (csrc/fa2_prefill.h: prefill_tile).  len is clamped into
  * [0, capacity_keys] (capacity_keys = capacity * page_size, or capacity when page_size = 0: the contiguous layout, one page per sequence).
  * *page_slot: the block-table entry of the tile's page (contiguous: 0); *row_in_page: the tile's first row inside that page; *valid_rows: how many of
