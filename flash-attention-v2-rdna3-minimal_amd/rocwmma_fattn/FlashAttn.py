@@ -16,6 +16,7 @@ Layers (reference counterpart in brackets):
 The host is PyTorch-ROCm for memory and streams only; the compute is the C-ABI library
 (include/fa2_gfx950.h).  There is no CPU path: tensors must live on a ROCm device.
 """
+import collections
 import ctypes
 import math
 import os
@@ -496,9 +497,13 @@ def _grouped_backward(mha_backward, Q, K, V, O, dO, L, act_n, act_nkv, act_d, Br
     return [dQ, dKe.unflatten(h_ax, (K.size(h_ax), g)).sum(h_ax + 1), dVe.unflatten(h_ax, (V.size(h_ax), g)).sum(h_ax + 1)]
 
 
+_I64x2, _I64x3 = ctypes.c_int64 * 2, ctypes.c_int64 * 3          # (the array types of _fa2_lib.strides2 / strides3)
+
+
 def _s2(t):
     """{head, row} element strides of a packed [total, heads, D] tensor, as the varlen entry points take them."""
-    return _fa2_lib.strides2(t.stride(1), t.stride(0))
+    s = t.stride()
+    return _I64x2(s[1], s[0])
 
 
 def _packed_ready(t):
@@ -1099,6 +1104,11 @@ def _decode_strides_ok(t, mult=8):
     return s3 == 1 and not ((s0 | s1 | s2) & (mult - 1)) and s1 > 0 and not (t.data_ptr() & 15)
 
 
+def _bnhd_ready(t):
+    """A [B, N, heads, D] tensor the serving kernels can address (_packed_ready's rule): itself, or a contiguous copy"""
+    return t if _decode_strides_ok(t) else t.contiguous()
+
+
 _FP8_CACHE = getattr(torch, "float8_e4m3fn", None)
 _FP8_OTHERS = tuple(d for d in (getattr(torch, n, None) for n in ("float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz")) if d is not None)
 
@@ -1120,24 +1130,46 @@ def _cache_format(who, q, k_cache, v_cache, k_descale, v_descale):
     return fp8
 
 
-def _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8, num_splits=None, B=None):
-    """The checks of the lengths, the block table, the descales, the devices and the cache strides that flash_attention_decode and kvcache_append share
-    (q: the tensor that sets the batch size and the device — a packed call states its B; num_splits: decode's, checked in its place).
-    -> capacity, page_size, num_pages, k_descale, v_descale (the descales made to share one stride pair)"""
-    B, Hkv = q.shape[0] if B is None else B, k_cache.shape[2]
+def _dtype_code(t):
+    return _fa2_lib.FA2_DTYPE_F16 if t.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+
+
+def _device_index(t):
+    return t.device.index if t.device.index is not None else _current_device()
+
+
+def _bnhd(t):
+    """{batch | page, head, row} element strides of a [B, N, heads, D] tensor"""
+    s = t.stride()
+    return _I64x3(s[0], s[2], s[1])
+
+
+# A KV cache as the five serving entries of the C-ABI take it (host.cpp's CacheDesc, seen from Python): made by _cache_desc alone, which has checked it.
+# k / v: the caches (the copies, on flash_attention_prefill's pad path), D: their head dim; the descales share one stride pair.  The entries order the
+# cache's arguments differently, so these come in groups and a call puts the groups in its order: fmt (the format code), ptrs (k, v), tables (cache_seqlens,
+# block_table), sizes (capacity, page_size, num_pages), strides (ks, vs), bts (the block table's row stride), descales (kd, vd, their stride pair ds).
+_Cache = collections.namedtuple("_Cache", "fp8 capacity page_size num_pages Hkv D k v lens block_table k_descale v_descale fmt ptrs tables sizes strides bts descales")
+
+
+def _cache_desc(fp8, io, B, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, aux=(), num_splits=None, d_pad=0):
+    """The one place a cache is checked and described, behind _cache_format (-> fp8): the lengths, the block table, the page size, the descales, the
+    devices and the cache strides.  io: the tensor that sets the device (q, or an append's k), B: the batch size (a packed call: its sequences), aux:
+    further tensors that must be on that device (cu_seqlens); num_splits: decode's, checked in its place; d_pad: flash_attention_prefill's pad of the
+    head dim, which copies the caches — the stride checks see the copies.  -> _Cache"""
+    Hkv = k_cache.shape[2]
     if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous():
         raise ValueError("fa2: cache_seqlens must be a contiguous int32 tensor of shape [B] = [%d], got %s %s" % (B, cache_seqlens.dtype, tuple(cache_seqlens.shape)))
     if num_splits is not None and (isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _DECODE_MAX_SPLITS):
         raise ValueError("fa2: num_splits is 0 (the library chooses) or 1 .. %d, got %r" % (_DECODE_MAX_SPLITS, num_splits))
     if block_table is None:
         if k_cache.shape[0] != B:
-            raise ValueError("fa2: a contiguous cache is [B, Nmax, Hkv, D] with q's batch size %d, got %s (a paged cache needs its block_table)"
+            raise ValueError("fa2: a contiguous cache is [B, Nmax, Hkv, D] with B = %d sequences, got %s (a paged cache needs its block_table)"
                              % (B, tuple(k_cache.shape)))
         capacity, page_size, num_pages = k_cache.shape[1], 0, 0
     else:
         if not torch.is_tensor(block_table) or block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != B or \
                 block_table.shape[1] < 1 or block_table.stride(1) != 1:
-            raise ValueError("fa2: block_table must be int32 [B, max_pages] with q's batch size %d and contiguous rows, got %s"
+            raise ValueError("fa2: block_table must be int32 [B, max_pages] with B = %d sequences and contiguous rows, got %s"
                              % (B, "%s %s" % (block_table.dtype, tuple(block_table.shape)) if torch.is_tensor(block_table) else repr(block_table)))
         capacity, page_size, num_pages = block_table.shape[1], k_cache.shape[1], k_cache.shape[0]
         if page_size < 64 or page_size % 64:
@@ -1151,11 +1183,15 @@ def _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_
         if not torch.is_tensor(d) or d.dtype != torch.float32 or tuple(d.shape) != (B, Hkv):
             raise ValueError("fa2: k_descale / v_descale must be float32 tensors of shape [B, Hkv] = [%d, %d], got %s"
                              % (B, Hkv, "%s %s" % (d.dtype, tuple(d.shape)) if torch.is_tensor(d) else repr(d)))
-    aux = ((cache_seqlens,) if block_table is None else (cache_seqlens, block_table)) + descales
-    if not all(t.is_cuda for t in (q, k_cache, v_cache) + aux):
-        raise RuntimeError("fa2: q, the caches, cache_seqlens, block_table and the descales must be on a ROCm device (no CPU path in this operator)")
-    if any(t.device != q.device for t in (k_cache, v_cache) + aux):
-        raise RuntimeError("fa2: q, the caches, cache_seqlens, block_table and the descales must be on the same device")
+    aux = tuple(aux) + ((cache_seqlens,) if block_table is None else (cache_seqlens, block_table)) + descales
+    if not all(t.is_cuda for t in (io, k_cache, v_cache) + aux):
+        raise RuntimeError("fa2: q (an append: k), the caches, cache_seqlens, cu_seqlens, block_table and the descales must be on a ROCm device (no CPU "
+                           "path in this operator)")
+    device = io.device
+    if any(t.device != device for t in (k_cache, v_cache) + aux):
+        raise RuntimeError("fa2: q (an append: k), the caches, cache_seqlens, cu_seqlens, block_table and the descales must be on the same device")
+    if d_pad:
+        k_cache, v_cache = (torch.nn.functional.pad(t, (0, d_pad)) for t in (k_cache, v_cache))
     if fp8:
         if not _decode_strides_ok(k_cache, 16) or not _decode_strides_ok(v_cache, 16):
             raise ValueError("fa2: float8_e4m3fn k_cache / v_cache need a contiguous head dim, strides that are multiples of 16 elements and 16-byte "
@@ -1164,23 +1200,34 @@ def _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_
             k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
     elif not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
         raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
-    return capacity, page_size, num_pages, k_descale, v_descale
+    d0 = k_descale if k_descale is not None else v_descale
+    return _Cache(fp8, capacity, page_size, num_pages, Hkv, k_cache.shape[3], k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale,
+                  _fa2_lib.FA2_CACHE_E4M3 if fp8 else _fa2_lib.FA2_CACHE_16BIT, (k_cache.data_ptr(), v_cache.data_ptr()),
+                  (cache_seqlens.data_ptr(), None if block_table is None else block_table.data_ptr()), (capacity, page_size, num_pages),
+                  (_bnhd(k_cache), _bnhd(v_cache)), 0 if block_table is None else block_table.stride(0),
+                  (None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
+                   None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1))))
 
 
-def _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8):
-    """The argument checks of kvcache_append that concern the new tokens, the rotary tables and q (the caches' own: _cache_format / _cache_layout).
+_APPEND_NAMES = (("kvcache_append", "[B, Nnew, Hkv, D]", "[B, Nnew, H, D]"), ("kvcache_append_varlen", "[total, Hkv, D]", "[total, H, D]"))      # [packed]
+
+
+def _append_check(packed, k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8):
+    """The argument checks of the two appends that concern the new tokens, the rotary tables and q (the caches' own: _cache_format / _cache_desc).
     -> rotary_dim (0: no rotary)"""
-    if not all(torch.is_tensor(t) and t.dim() == 4 for t in (k, v)) or k.shape != v.shape or k.dtype != v.dtype:
-        raise ValueError("fa2: kvcache_append takes k and v [B, Nnew, Hkv, D] of one shape and dtype")
-    B, Nnew, Hkv, D = k.shape
-    if k_cache.shape != v_cache.shape or k_cache.shape[2] != Hkv or k_cache.shape[3] != D:
-        raise ValueError("fa2: inconsistent k / k_cache / v_cache shapes %s %s %s" % (tuple(k.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
-    if B < 1 or Nnew < 1 or Hkv < 1:
-        raise ValueError("fa2: kvcache_append needs B, Nnew, Hkv >= 1, got k %s" % (tuple(k.shape),))
+    who, layout, q_layout = _APPEND_NAMES[packed]
+    if not all(torch.is_tensor(t) and t.dim() == 4 - packed for t in (k, v)) or k.shape != v.shape or k.dtype != v.dtype:
+        raise ValueError("fa2: %s takes k and v %s of one shape and dtype, got %s %s" % (who, layout, tuple(getattr(k, "shape", ())), tuple(getattr(v, "shape", ()))))
+    shape, cshape = k.shape, k_cache.shape
+    Hkv, D = shape[-2], shape[-1]
+    if cshape != v_cache.shape or cshape[2] != Hkv or cshape[3] != D:
+        raise ValueError("fa2: inconsistent k / k_cache / v_cache shapes %s %s %s" % (tuple(shape), tuple(cshape), tuple(v_cache.shape)))
+    if Hkv < 1 or (not packed and (shape[0] < 1 or shape[1] < 1)):                  # (a packed token buffer may be empty)
+        raise ValueError("fa2: %s needs %s >= 1, got k %s" % (who, "Hkv" if packed else "B, Nnew, Hkv", tuple(k.shape)))
     if D % (16 if fp8 else 8) or D > 512:
-        raise ValueError("fa2: kvcache_append serves head dims that are multiples of 8 (float8_e4m3fn caches: of 16) up to 512, got %d" % D)
+        raise ValueError("fa2: %s serves head dims that are multiples of 8 (float8_e4m3fn caches: of 16) up to 512, got %d" % (who, D))
     rotary_dim = _rotary_check(k, D, rotary_cos, rotary_sin)
-    _append_q_check("kvcache_append", "[B, Nnew, H, D]", q, k, rotary_dim)
+    _append_q_check(who, q_layout, q, k, rotary_dim)
     return rotary_dim
 
 
@@ -1214,12 +1261,12 @@ def _append_q_check(who, layout, q, k, rotary_dim):
 
 
 def _rotary_tables(rotary_cos, rotary_sin):
-    """The tables as the C-ABI takes them: contiguous rows that start on 16-byte boundaries, one row stride -> cos, sin, seqlen_ro, row stride"""
+    """The tables as the C-ABI takes them: contiguous rows that start on 16-byte boundaries, one row stride -> cos, sin"""
     per16 = 16 // rotary_cos.element_size()
     rotary_cos, rotary_sin = (t if t.stride(1) == 1 and t.stride(0) % per16 == 0 and not (t.data_ptr() & 15) else t.contiguous() for t in (rotary_cos, rotary_sin))
     if rotary_cos.stride(0) != rotary_sin.stride(0):                   # the C-ABI takes one row stride
         rotary_cos, rotary_sin = rotary_cos.contiguous(), rotary_sin.contiguous()
-    return rotary_cos, rotary_sin, rotary_cos.shape[0], rotary_cos.stride(0)
+    return rotary_cos, rotary_sin
 
 
 def kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, k_descale=None,
@@ -1237,45 +1284,7 @@ def kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table=None, rota
     Returns the rotated q (a new tensor; q is not touched) when q and the tables are given, else None.  D: a multiple of 8 (e4m3: of 16) up to 512;
     Nnew has no upper bound (a prefill chunk is a legitimate append).  The host reads no device value: the call can be captured in a graph.
     Not served: cache_batch_idx, cache_leftpad, rotary without an append.  C-ABI fa2_kvcache_append."""
-    if not all(torch.is_tensor(t) for t in (k_cache, v_cache, k, v, cache_seqlens)) or k_cache.dim() != 4 or v_cache.dim() != 4 or k.dim() != 4:
-        raise ValueError("fa2: kvcache_append takes k / v [B, Nnew, Hkv, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
-                         "with a block_table)")
-    fp8 = _cache_format("kvcache_append", k, k_cache, v_cache, k_descale, v_descale)
-    rotary_dim = _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8)
-    capacity, page_size, num_pages, k_descale, v_descale = _cache_layout(k, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8)
-    B, Nnew, Hkv, D = k.shape
-    extra = tuple(t for t in (v, q, rotary_cos, rotary_sin) if t is not None)
-    if not all(t.is_cuda for t in extra) or any(t.device != k.device for t in extra):
-        raise RuntimeError("fa2: k, v, q and the rotary tables must be on the ROCm device of the caches")
-    k, v = (t if _decode_strides_ok(t) else t.contiguous() for t in (k, v))
-    H, q_out = 0, None
-    if q is not None:
-        H = q.shape[2]
-        q = q if _decode_strides_ok(q) else q.contiguous()
-        q_out = torch.empty((B, Nnew, H, D), dtype=q.dtype, device=q.device)
-    tab_code, seqlen_ro, ros = 0, 0, 0
-    if rotary_dim:
-        rotary_cos, rotary_sin, seqlen_ro, ros = _rotary_tables(rotary_cos, rotary_sin)
-    lib = _fa2_lib.load()
-    code = _fa2_lib.FA2_DTYPE_F16 if k.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
-    if rotary_dim:
-        tab_code = _fa2_lib.FA2_DTYPE_F32 if rotary_cos.dtype == torch.float32 else code
-    dev = k.device.index if k.device.index is not None else _current_device()
-    s3 = _fa2_lib.strides3
-    bnhd = lambda t: s3(t.stride(0), t.stride(2), t.stride(1))      # noqa: E731
-    d0 = k_descale if k_descale is not None else v_descale
-    with torch.cuda.device(dev):
-        rc = lib.fa2_kvcache_append(code, _fa2_lib.FA2_CACHE_E4M3 if fp8 else _fa2_lib.FA2_CACHE_16BIT, k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
-                                    v_cache.data_ptr(), cache_seqlens.data_ptr(), None if block_table is None else block_table.data_ptr(), B, Hkv, Nnew, D,
-                                    capacity, page_size, num_pages, bnhd(k), bnhd(v), bnhd(k_cache), bnhd(v_cache),
-                                    0 if block_table is None else block_table.stride(0), None if q is None else q.data_ptr(),
-                                    None if q is None else q_out.data_ptr(), H, Nnew if q is not None else 0, None if q is None else bnhd(q),
-                                    None if q is None else bnhd(q_out), rotary_cos.data_ptr() if rotary_dim else None,
-                                    rotary_sin.data_ptr() if rotary_dim else None, tab_code, rotary_dim, seqlen_ro, ros, 1 if rotary_interleaved else 0,
-                                    None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
-                                    None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), _raw_stream(dev))
-    _fa2_lib.check(rc)
-    return q_out
+    return _append(False, k_cache, v_cache, k, v, None, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, k_descale, v_descale, q)
 
 
 def _check_cu(name, cu):
@@ -1299,55 +1308,64 @@ def kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens, cache_seqlens, blo
     page id lies outside the pool is skipped, as in kvcache_append.
     Returns the rotated q (a new tensor) when q and the tables are given, else None.  The host reads no device value: the call can be captured in a
     graph.  Not served: cache_batch_idx, cache_leftpad, rotary without an append.  C-ABI fa2_kvcache_append_varlen."""
-    who = "kvcache_append_varlen"
-    if not all(torch.is_tensor(t) for t in (k_cache, v_cache, k, v, cache_seqlens)) or k_cache.dim() != 4 or v_cache.dim() != 4 or k.dim() != 3 or v.dim() != 3:
-        raise ValueError("fa2: %s takes k / v [total, Hkv, D] and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] "
-                         "with a block_table)" % who)
+    return _append(True, k_cache, v_cache, k, v, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, k_descale, v_descale, q)
+
+
+def _append(packed, k_cache, v_cache, k, v, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, k_descale, v_descale, q):
+    """kvcache_append (packed = False) and kvcache_append_varlen (True): the tensors' ranks and the cache format, then check, then launch"""
+    who, layout, _ = _APPEND_NAMES[packed]
+    if not all(torch.is_tensor(t) for t in (k_cache, v_cache, k, v, cache_seqlens)) or k_cache.dim() != 4 or v_cache.dim() != 4 or k.dim() != 4 - packed or \
+            v.dim() != 4 - packed:
+        raise ValueError("fa2: %s takes k / v %s and 4-D k_cache / v_cache ([B, Nmax, Hkv, D], or [num_pages, page_size, Hkv, D] with a block_table)"
+                         % (who, layout))
     fp8 = _cache_format(who, k, k_cache, v_cache, k_descale, v_descale)
-    if k.shape != v.shape or k.dtype != v.dtype:
-        raise ValueError("fa2: %s takes k and v [total, Hkv, D] of one shape and dtype, got %s %s" % (who, tuple(k.shape), tuple(v.shape)))
-    total, Hkv, D = k.shape
-    if k_cache.shape != v_cache.shape or k_cache.shape[2] != Hkv or k_cache.shape[3] != D:
-        raise ValueError("fa2: inconsistent k / k_cache / v_cache shapes %s %s %s" % (tuple(k.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
-    if Hkv < 1:
-        raise ValueError("fa2: %s needs Hkv >= 1, got k %s" % (who, tuple(k.shape)))
-    if D % (16 if fp8 else 8) or D > 512:
-        raise ValueError("fa2: %s serves head dims that are multiples of 8 (float8_e4m3fn caches: of 16) up to 512, got %d" % (who, D))
-    rotary_dim = _rotary_check(k, D, rotary_cos, rotary_sin)
-    _append_q_check(who, "[total, H, D]", q, k, rotary_dim)
-    B = _check_cu("cu_seqlens", cu_seqlens)
-    capacity, page_size, num_pages, k_descale, v_descale = _cache_layout(k, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8, B=B)
-    extra = tuple(t for t in (v, cu_seqlens, q, rotary_cos, rotary_sin) if t is not None)
-    if not all(t.is_cuda for t in extra) or any(t.device != k.device for t in extra):
-        raise RuntimeError("fa2: k, v, cu_seqlens, q and the rotary tables must be on the ROCm device of the caches")
-    k, v = _packed_ready(k), _packed_ready(v)
-    H, q_out = 0, None
+    B = _check_cu("cu_seqlens", cu_seqlens) if packed else k.shape[0]
+    return _append_launch(*_append_prepare(packed, fp8, B, k_cache, v_cache, k, v, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin,
+                                           rotary_interleaved, k_descale, v_descale, q))
+
+
+def _append_prepare(packed, fp8, B, k_cache, v_cache, k, v, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, k_descale,
+                    v_descale, q, lead=None, num_splits=None):
+    """Every argument check of an append, and what its launch needs: the cache description, rotary_dim, the tensors and tables as the kernel can address
+    them (copies where it cannot), q_out.  Nothing is launched here: a fused call (lead: its q, which then sets the device; num_splits: decode's) runs
+    this beside its own checks and _append_launch after all of them, so a call that is refused leaves the caches as they were.
+    -> _append_launch's arguments, the cache description first"""
+    rotary_dim = _append_check(packed, k_cache, v_cache, k, v, rotary_cos, rotary_sin, q, fp8)
+    cache = _cache_desc(fp8, k if lead is None else lead, B, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale,
+                        aux=(cu_seqlens,) if packed else (), num_splits=num_splits)
+    extra = tuple(t for t in (k, v, q, rotary_cos, rotary_sin) if t is not None)
+    device = k_cache.device
+    if not all(t.is_cuda and t.device == device for t in extra):
+        raise RuntimeError("fa2: k, v, q and the rotary tables must be on the ROCm device of the caches")
+    ready = _packed_ready if packed else _bnhd_ready
+    k, v = ready(k), ready(v)
+    q_out = None
     if q is not None:
-        H = q.shape[1]
-        q = _packed_ready(q)
-        q_out = torch.empty((total, H, D), dtype=q.dtype, device=q.device)
-    if total == 0:                 # an empty token buffer: nothing to launch
-        return q_out
-    code = _fa2_lib.FA2_DTYPE_F16 if k.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
-    tab_code, seqlen_ro, ros = 0, 0, 0
+        q = ready(q)
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     if rotary_dim:
-        rotary_cos, rotary_sin, seqlen_ro, ros = _rotary_tables(rotary_cos, rotary_sin)
-        tab_code = _fa2_lib.FA2_DTYPE_F32 if rotary_cos.dtype == torch.float32 else code
+        rotary_cos, rotary_sin = _rotary_tables(rotary_cos, rotary_sin)
+    return cache, packed, B, k, v, cu_seqlens, q, q_out, rotary_dim, rotary_cos, rotary_sin, rotary_interleaved
+
+
+def _append_launch(cache, packed, B, k, v, cu_seqlens, q, q_out, rotary_dim, cos, sin, rotary_interleaved):
+    """The one C call of an append _append_prepare has checked -> q_out (the rotated q, or None)"""
+    if packed and k.shape[0] == 0:                   # an empty token buffer: nothing to launch
+        return q_out
     lib = _fa2_lib.load()
-    dev = k.device.index if k.device.index is not None else _current_device()
-    s3 = _fa2_lib.strides3
-    bnhd = lambda t: s3(t.stride(0), t.stride(2), t.stride(1))      # noqa: E731
-    d0 = k_descale if k_descale is not None else v_descale
+    code = _dtype_code(k)
+    if packed:                                       # ([total, heads, D] and cu_seqlens against [B, Nnew, heads, D]: what the two entries differ in)
+        entry, st, cu, sizes, nq = lib.fa2_kvcache_append_varlen, _s2, (cu_seqlens.data_ptr(),), (B, k.shape[0], cache.Hkv, cache.D), ()
+    else:
+        entry, st, cu, sizes, nq = lib.fa2_kvcache_append, _bnhd, (), (B, cache.Hkv, k.shape[1], cache.D), (k.shape[1] if q is not None else 0,)
+    q_args = (None, None, 0, *nq, None, None) if q is None else (q.data_ptr(), q_out.data_ptr(), q.shape[-2], *nq, st(q), st(q_out))
+    rotary = (None, None, 0, 0, 0, 0)
+    if rotary_dim:
+        rotary = (cos.data_ptr(), sin.data_ptr(), _fa2_lib.FA2_DTYPE_F32 if cos.dtype == torch.float32 else code, rotary_dim, cos.shape[0], cos.stride(0))
+    dev = _device_index(k)
     with torch.cuda.device(dev):
-        rc = lib.fa2_kvcache_append_varlen(code, _fa2_lib.FA2_CACHE_E4M3 if fp8 else _fa2_lib.FA2_CACHE_16BIT, k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
-                                           v_cache.data_ptr(), cu_seqlens.data_ptr(), cache_seqlens.data_ptr(),
-                                           None if block_table is None else block_table.data_ptr(), B, total, Hkv, D, capacity, page_size, num_pages,
-                                           _s2(k), _s2(v), bnhd(k_cache), bnhd(v_cache), 0 if block_table is None else block_table.stride(0),
-                                           None if q is None else q.data_ptr(), None if q is None else q_out.data_ptr(), H,
-                                           None if q is None else _s2(q), None if q is None else _s2(q_out), rotary_cos.data_ptr() if rotary_dim else None,
-                                           rotary_sin.data_ptr() if rotary_dim else None, tab_code, rotary_dim, seqlen_ro, ros, 1 if rotary_interleaved else 0,
-                                           None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
-                                           None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), _raw_stream(dev))
+        rc = entry(code, cache.fmt, k.data_ptr(), v.data_ptr(), *cache.ptrs, *cu, *cache.tables, *sizes, *cache.sizes, st(k), st(v), *cache.strides, cache.bts,
+                   *q_args, *rotary, 1 if rotary_interleaved else 0, *cache.descales, _raw_stream(dev))
     _fa2_lib.check(rc)
     return q_out
 
@@ -1414,49 +1432,43 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
         if not all(torch.is_tensor(t) and t.dim() == 4 for t in (k, v)) or k.dtype != q.dtype or k.shape[0] != B or k.shape[1] != Nq:
             raise ValueError("fa2: flash_attention_decode takes k and v together, [B, Nq, Hkv, D] = [%d, %d, %d, %d] in q's dtype: the new tokens are the "
                              "query rows' own (k.shape[1] == Nq); got %s %s" % (B, Nq, Hkv, D, tuple(getattr(k, "shape", ())), tuple(getattr(v, "shape", ()))))
-        _append_check(k_cache, v_cache, k, v, rotary_cos, rotary_sin, q if rotary_cos is not None else None, fp8)
-    capacity, page_size, num_pages, k_descale, v_descale = _cache_layout(q, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, fp8,
-                                                                        num_splits)
-    if fused:               # the append launch, then today's call on the rotated q: one stream, so the decode kernel reads what the append wrote
-        q_rot = kvcache_append(k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, k_descale, v_descale,
-                               q=q if rotary_cos is not None else None)
+        app = _append_prepare(False, fp8, B, k_cache, v_cache, k, v, None, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, k_descale,
+                              v_descale, q if rotary_cos is not None else None, lead=q, num_splits=num_splits)
+        cache = app[0]
+    else:
+        cache = _cache_desc(fp8, q, B, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, num_splits=num_splits)
+    if fused:               # every check lies above: the append launch, then today's call on the rotated q, on one stream, so that decode reads what it wrote
+        q_rot = _append_launch(*app)
         q = q if q_rot is None else q_rot
-    if not _decode_strides_ok(q):
-        q = q.contiguous()
+    q = _bnhd_ready(q)
     if scale is None:
         scale = D ** -0.5
     lib = _fa2_lib.load()
-    code = _fa2_lib.FA2_DTYPE_F16 if q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+    code = _dtype_code(q)
     o = torch.empty((B, Nq, H, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
-    dev = q.device.index if q.device.index is not None else _current_device()
+    dev = _device_index(q)
     with torch.cuda.device(dev):
         stream = _raw_stream(dev)
         banded = window_left >= 0 or scoremod is not None
         if banded:
-            need = lib.fa2_fwd_decode_window_workspace_bytes(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits, window_left)
+            need = lib.fa2_fwd_decode_window_workspace_bytes(code, B, H, Hkv, Nq, D, cache.capacity, cache.page_size, num_splits, window_left)
         else:
-            need = (lib.fa2_fwd_decode_fp8_workspace_bytes if fp8 else lib.fa2_fwd_decode_workspace_bytes)(code, B, H, Hkv, Nq, D, capacity, page_size, num_splits)
+            need = (lib.fa2_fwd_decode_fp8_workspace_bytes if fp8 else lib.fa2_fwd_decode_workspace_bytes)(code, B, H, Hkv, Nq, D, cache.capacity, cache.page_size,
+                                                                                                           num_splits)
         ws = _workspace(need, q.device, dev, stream) if need else None
         if ws is None and _WS_POOL:
             _workspace_unused(dev, stream)
-        s3 = _fa2_lib.strides3
-        head = (code, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), cache_seqlens.data_ptr(),
-                None if block_table is None else block_table.data_ptr(), B, H, Hkv, Nq, D, capacity, page_size, num_pages,
-                s3(q.stride(0), q.stride(2), q.stride(1)), s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)),
-                s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)), s3(o.stride(0), o.stride(2), o.stride(1)),
-                _fa2_lib.strides2(lse.stride(0), lse.stride(1)), 0 if block_table is None else block_table.stride(0), float(scale))
+        head = (q.data_ptr(), *cache.ptrs, o.data_ptr(), lse.data_ptr(), *cache.tables, B, H, Hkv, Nq, D, *cache.sizes, _bnhd(q), *cache.strides, _bnhd(o),
+                _fa2_lib.strides2(lse.stride(0), lse.stride(1)), cache.bts, float(scale))
         tail = (num_splits, None if ws is None else ws.data_ptr(), need, stream)
-        d0 = k_descale if k_descale is not None else v_descale
-        descales = (None if k_descale is None else k_descale.data_ptr(), None if v_descale is None else v_descale.data_ptr(),
-                    None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)))
         if banded:
-            rc = lib.fa2_fwd_decode_window(code, _fa2_lib.FA2_CACHE_E4M3 if fp8 else _fa2_lib.FA2_CACHE_16BIT, *head[1:], *descales, window_left,
+            rc = lib.fa2_fwd_decode_window(code, cache.fmt, *head, *cache.descales, window_left,
                                            *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), *tail)
         elif fp8:
-            rc = lib.fa2_fwd_decode_fp8(*head, *descales, *tail)
+            rc = lib.fa2_fwd_decode_fp8(code, *head, *cache.descales, *tail)
         else:
-            rc = lib.fa2_fwd_decode(*head, *tail)
+            rc = lib.fa2_fwd_decode(code, *head, *tail)
     _fa2_lib.check(rc)
     return (o, lse * _LN2) if return_lse else o
 
@@ -1559,85 +1571,44 @@ def _prefill(who, fp8, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_t
                              "(k.shape[0] == total_q); got %s %s" % (who, total_q, Hkv, D, tuple(getattr(k, "shape", ())), tuple(getattr(v, "shape", ()))))
         if D % 8:
             raise ValueError("fa2: %s appends k / v at head dims that are multiples of 8 (kvcache_append_varlen's), got %d" % (who, D))
-        _rotary_check(k, D, rotary_cos, rotary_sin)
-    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.numel() < 2 or not cu_seqlens_q.is_contiguous():
-        raise ValueError("fa2: cu_seqlens_q must be a contiguous 1-D int32 tensor of B + 1 >= 2 row offsets, got %s %s" % (cu_seqlens_q.dtype, tuple(cu_seqlens_q.shape)))
-    B = cu_seqlens_q.numel() - 1
-    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous():
-        raise ValueError("fa2: cache_seqlens must be a contiguous int32 tensor of shape [B] = [%d] (cu_seqlens_q has B + 1 entries), got %s %s"
-                         % (B, cache_seqlens.dtype, tuple(cache_seqlens.shape)))
-    if block_table is None:
-        if k_cache.shape[0] != B:
-            raise ValueError("fa2: a contiguous cache is [B, Nmax, Hkv, D] with B = %d sequences, got %s (a paged cache needs its block_table)" % (B, tuple(k_cache.shape)))
-        capacity, page_size, num_pages = k_cache.shape[1], 0, 0
-    else:
-        if not torch.is_tensor(block_table) or block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != B or \
-                block_table.shape[1] < 1 or block_table.stride(1) != 1:
-            raise ValueError("fa2: block_table must be int32 [B, max_pages] with B = %d sequences and contiguous rows, got %s"
-                             % (B, "%s %s" % (block_table.dtype, tuple(block_table.shape)) if torch.is_tensor(block_table) else repr(block_table)))
-        capacity, page_size, num_pages = block_table.shape[1], k_cache.shape[1], k_cache.shape[0]
-        if page_size < 64 or page_size % 64:
-            raise ValueError("fa2: the page size of a paged cache (k_cache.shape[1]) must be a multiple of 64, got %d" % page_size)
-        if num_pages < 1:
-            raise ValueError("fa2: a paged cache needs at least one page")
-    if capacity < 1:
-        raise ValueError("fa2: the cache has no key slots")
+    B = _check_cu("cu_seqlens_q", cu_seqlens_q)
     if max_seqlen_q is not None and (isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0):
         raise ValueError("fa2: max_seqlen_q is None or a non-negative int, got %r" % (max_seqlen_q,))
     window_left = _fa2_lib.parse_window(window)[0]
     scoremod = _parse_scoremod(softcap, alibi_slopes, q, H, B)
-    descales = tuple(d for d in (k_descale, v_descale) if d is not None)          # (fp8 alone)
-    for d in descales:
-        if not torch.is_tensor(d) or d.dtype != torch.float32 or tuple(d.shape) != (B, Hkv):
-            raise ValueError("fa2: k_descale / v_descale must be float32 tensors of shape [B, Hkv] = [%d, %d], got %s"
-                             % (B, Hkv, "%s %s" % (d.dtype, tuple(d.shape)) if torch.is_tensor(d) else repr(d)))
-    aux = ((cu_seqlens_q, cache_seqlens) if block_table is None else (cu_seqlens_q, cache_seqlens, block_table)) + descales
-    if not all(t.is_cuda for t in (q, k_cache, v_cache) + aux):
-        raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on a ROCm device (no CPU path in this operator)")
-    if any(t.device != q.device for t in (k_cache, v_cache) + aux):
-        raise RuntimeError("fa2: q, the caches, cu_seqlens_q, cache_seqlens and block_table must be on the same device")
     d_pad = 0 if fp8 else -D % 8   # (0 in a fused call: its check above)
+    if fused:
+        app = _append_prepare(True, fp8, B, k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                              k_descale, v_descale, q if rotary_cos is not None else None, lead=q)
+        cache = app[0]
+    else:
+        cache = _cache_desc(fp8, q, B, k_cache, v_cache, cache_seqlens, block_table, k_descale, v_descale, aux=(cu_seqlens_q,), d_pad=d_pad)
     if d_pad:
-        q, k_cache, v_cache = (torch.nn.functional.pad(t, (0, d_pad)) for t in (q, k_cache, v_cache))
-    if fp8:
-        if not _decode_strides_ok(k_cache, 16) or not _decode_strides_ok(v_cache, 16):
-            raise ValueError("fa2: float8_e4m3fn k_cache / v_cache need a contiguous head dim, strides that are multiples of 16 elements and 16-byte "
-                             "aligned storage")
-        if len(descales) == 2 and k_descale.stride() != v_descale.stride():       # the C-ABI takes one stride pair: a device copy, nothing read back
-            k_descale, v_descale = k_descale.contiguous(), v_descale.contiguous()
-    elif not _decode_strides_ok(k_cache) or not _decode_strides_ok(v_cache):
-        raise ValueError("fa2: k_cache / v_cache need a contiguous head dim, strides that are multiples of 8 elements and 16-byte aligned storage")
+        q = torch.nn.functional.pad(q, (0, d_pad))
     if max_seqlen_q is None:
         max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max())
     if scale is None:
         scale = D ** -0.5
-    if fused:               # every check of this function lies above: the packed append launch, then today's call on the rotated q, on one stream
+    if fused:               # every check lies above: the packed append launch, then today's call on the rotated q, on one stream
         if not math.isfinite(float(scale)):
             raise ValueError("fa2: %s needs a finite scale, got %r" % (who, scale))
-        q_rot = kvcache_append_varlen(k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved,
-                                      k_descale, v_descale, q=q if rotary_cos is not None else None)
+        q_rot = _append_launch(*app)
         q = q if q_rot is None else q_rot
     q = _packed_ready(q)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
     if total_q and max_seqlen_q > 0:
         lib = _fa2_lib.load()
-        code = _fa2_lib.FA2_DTYPE_F16 if q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
-        dev = q.device.index if q.device.index is not None else _current_device()
-        s3 = _fa2_lib.strides3
-        head = (q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), o.data_ptr(), lse.data_ptr(), cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(),
-                None if block_table is None else block_table.data_ptr(), B, H, Hkv, int(max_seqlen_q), D + d_pad, capacity, page_size, num_pages, _s2(q),
-                s3(k_cache.stride(0), k_cache.stride(2), k_cache.stride(1)), s3(v_cache.stride(0), v_cache.stride(2), v_cache.stride(1)),
-                _s2(o), lse.stride(0), 0 if block_table is None else block_table.stride(0), float(scale))
+        code = _dtype_code(q)
+        dev = _device_index(q)
+        head = (q.data_ptr(), *cache.ptrs, o.data_ptr(), lse.data_ptr(), cu_seqlens_q.data_ptr(), *cache.tables, B, H, Hkv, int(max_seqlen_q), cache.D,
+                *cache.sizes, _s2(q), *cache.strides, _s2(o), lse.stride(0), cache.bts, float(scale))
         with torch.cuda.device(dev):
             tail = (window_left, *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), _raw_stream(dev))
             if fp8:
-                d0 = k_descale if k_descale is not None else v_descale
-                rc = lib.fa2_fwd_prefill_fp8(code, *head, None if k_descale is None else k_descale.data_ptr(),
-                                             None if v_descale is None else v_descale.data_ptr(),
-                                             None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), *tail)
+                rc = lib.fa2_fwd_prefill_fp8(code, *head, *cache.descales, *tail)
             else:
-                rc = lib.fa2_fwd_prefill(code, _fa2_lib.FA2_CACHE_16BIT, *head, *tail)
+                rc = lib.fa2_fwd_prefill(code, cache.fmt, *head, *tail)
         _fa2_lib.check(rc)
     elif total_q:                  # (a stated maximum of 0: no row is computed)
         o.zero_()

@@ -12,6 +12,7 @@ from rocwmma_fattn import _fa2_lib
 
 if os.path.join(ROOT, "tools") not in sys.path:
     sys.path.append(os.path.join(ROOT, "tools"))
+import decode_abi  # noqa: E402
 import key_bars  # noqa: E402
 
 LOG2E = 1.4426950408889634
@@ -46,15 +47,20 @@ def nan_out(q):
     return o, lse
 
 
+def prefill_kw(q, kc, vc, o, lse, cu, lens, bt, max_q, scale, window_left=-1, softcap=0.0, slopes=None):
+    """What the tensors of a prefill call say, by decode_abi's keywords (16-bit or e4m3 caches; the descales are the caller's to add)."""
+    paged = bt is not None
+    return dict(dtype=code(q.dtype), fmt=_fa2_lib.FA2_CACHE_16BIT if kc.element_size() == 2 else _fa2_lib.FA2_CACHE_E4M3, q=ptr(q), k=ptr(kc), v=ptr(vc), o=ptr(o),
+                lse=ptr(lse), cu=ptr(cu), lens=ptr(lens), bt=ptr(bt), B=lens.numel(), H=q.shape[1], Hkv=kc.shape[2], max_q=int(max_q), D=q.shape[2],
+                cap=bt.shape[1] if paged else kc.shape[1], page=kc.shape[1] if paged else 0, pages=kc.shape[0] if paged else 0, qs=s2(q), ks=s3(kc), vs=s3(vc),
+                os=s2(o), lss=lse.stride(0), bts=bt.stride(0) if paged else 0, scale=float(scale), wl=int(window_left), cap_=float(softcap), sl=ptr(slopes),
+                st=0 if slopes is None or slopes.dim() == 1 else slopes.stride(0), stream=stream())
+
+
 def prefill_c(q, kc, vc, cu, lens, bt, max_q, scale, window_left=-1, softcap=0.0, slopes=None, out=None, check=True):
     """fa2_fwd_prefill on NaN-filled o / lse (or `out`) -> o [total_q, H, D], lse f32 [H, total_q] in log2 units."""
     o, lse = out if out is not None else nan_out(q)
-    paged = bt is not None
-    rc = _fa2_lib.load().fa2_fwd_prefill(
-        code(q.dtype), _fa2_lib.FA2_CACHE_16BIT, ptr(q), ptr(kc), ptr(vc), ptr(o), ptr(lse), ptr(cu), ptr(lens), ptr(bt),
-        lens.numel(), q.shape[1], kc.shape[2], int(max_q), q.shape[2], bt.shape[1] if paged else kc.shape[1], kc.shape[1] if paged else 0,
-        kc.shape[0] if paged else 0, s2(q), s3(kc), s3(vc), s2(o), lse.stride(0), bt.stride(0) if paged else 0, float(scale), int(window_left),
-        float(softcap), ptr(slopes), 0 if slopes is None or slopes.dim() == 1 else slopes.stride(0), stream())
+    rc = decode_abi.call("prefill", **prefill_kw(q, kc, vc, o, lse, cu, lens, bt, max_q, scale, window_left, softcap, slopes))
     if check:
         _fa2_lib.check(rc)
         return o, lse

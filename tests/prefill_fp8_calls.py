@@ -15,14 +15,9 @@ POW2 = tuple(2.0 ** e for e in range(-3, 4))         # 1/8 .. 8: every finite e4
 def prefill_fp8_c(q, kc, vc, cu, lens, bt, max_q, scale, kd=None, vd=None, window_left=-1, softcap=0.0, slopes=None, out=None, check=True):
     """fa2_fwd_prefill_fp8 on NaN-filled o / lse (or `out`) -> o [total_q, H, D], lse f32 [H, total_q] in log2 units.  kc / vc: e4m3 (strides = bytes)."""
     o, lse = out if out is not None else pc.nan_out(q)
-    paged = bt is not None
     d0 = kd if kd is not None else vd
-    rc = _fa2_lib.load().fa2_fwd_prefill_fp8(
-        pc.code(q.dtype), pc.ptr(q), pc.ptr(kc), pc.ptr(vc), pc.ptr(o), pc.ptr(lse), pc.ptr(cu), pc.ptr(lens), pc.ptr(bt),
-        lens.numel(), q.shape[1], kc.shape[2], int(max_q), q.shape[2], bt.shape[1] if paged else kc.shape[1], kc.shape[1] if paged else 0,
-        kc.shape[0] if paged else 0, pc.s2(q), pc.s3(kc), pc.s3(vc), pc.s2(o), lse.stride(0), bt.stride(0) if paged else 0, float(scale),
-        pc.ptr(kd), pc.ptr(vd), None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)), int(window_left),
-        float(softcap), pc.ptr(slopes), 0 if slopes is None or slopes.dim() == 1 else slopes.stride(0), pc.stream())
+    rc = pc.decode_abi.call("prefill_fp8", **pc.prefill_kw(q, kc, vc, o, lse, cu, lens, bt, max_q, scale, window_left, softcap, slopes), kd=pc.ptr(kd), vd=pc.ptr(vd),
+                            ds=None if d0 is None else _fa2_lib.strides2(d0.stride(0), d0.stride(1)))
     if check:
         _fa2_lib.check(rc)
         return o, lse

@@ -301,8 +301,9 @@ def _prefill_args_of_the_parent(q, kc, vc, cu, lens, bt, max_q, o_ptr, lse_ptr):
     total, H, D = q.shape
     hr = lambda t: (t.stride(1), t.stride(0))                   # noqa: E731
     bnhd = lambda t: (t.stride(0), t.stride(2), t.stride(1))    # noqa: E731
-    return (F16, C16, q.data_ptr(), kc.data_ptr(), vc.data_ptr(), o_ptr, lse_ptr, cu.data_ptr(), lens.data_ptr(), bt.data_ptr(), 2, H, kc.shape[2], max_q, D,
-            bt.shape[1], kc.shape[1], kc.shape[0], hr(q), bnhd(kc), bnhd(vc), (D, H * D), total, bt.stride(0), float(D ** -0.5), -1, 0.0, None, 0, None)
+    return dc.c_args("prefill", dtype=F16, fmt=C16, q=q.data_ptr(), k=kc.data_ptr(), v=vc.data_ptr(), o=o_ptr, lse=lse_ptr, cu=cu.data_ptr(), lens=lens.data_ptr(),
+                     bt=bt.data_ptr(), B=2, H=H, Hkv=kc.shape[2], max_q=max_q, D=D, cap=bt.shape[1], page=kc.shape[1], pages=kc.shape[0], qs=hr(q), ks=bnhd(kc),
+                     vs=bnhd(vc), os=(D, H * D), lss=total, bts=bt.stride(0), scale=float(D ** -0.5), wl=-1, cap_=0.0, sl=None, st=0, stream=None)
 
 
 def _plain(a):
@@ -315,7 +316,8 @@ def test_the_prefill_call_without_the_keywords_is_the_parents(monkeypatch):
     o = flash_attention_prefill(q, kc, vc, cu, lens, bt, max_seqlen_q=6)
     assert [name for name, _ in rec.calls] == ["fa2_fwd_prefill"]
     a = rec.calls[0][1]
-    assert _plain(a) == _prefill_args_of_the_parent(q, kc, vc, cu, lens, bt, 6, o.data_ptr(), a[6]) and a[6] not in (None, 0)
+    lse_ptr = dc.arg("prefill", a, "lse")
+    assert _plain(a) == _prefill_args_of_the_parent(q, kc, vc, cu, lens, bt, 6, o.data_ptr(), lse_ptr) and lse_ptr not in (None, 0)
 
 
 def test_the_fused_prefill_appends_then_attends_on_the_rotated_q(monkeypatch):
@@ -325,7 +327,7 @@ def test_the_fused_prefill_appends_then_attends_on_the_rotated_q(monkeypatch):
     arg = lambda a, n: dc.arg("append_varlen", a, n)            # noqa: E731
     flash_attention_prefill(q, kc, vc, cu, lens, bt, max_seqlen_q=6, k=k, v=v)          # no rotary: q is not touched and not passed
     (n1, a1), (n2, a2) = rec.calls
-    assert (n1, n2, len(a1)) == ("fa2_kvcache_append_varlen", "fa2_fwd_prefill", 37) and a2[2] == q.data_ptr()
+    assert (n1, n2, len(a1)) == ("fa2_kvcache_append_varlen", "fa2_fwd_prefill", 37) and dc.arg("prefill", a2, "q") == q.data_ptr()
     assert [arg(a1, n) for n in ("q", "qo", "rot", "H")] == [None, None, 0, 0]
     assert [arg(a1, n) for n in ("kn", "vn", "k", "v", "cu", "lens", "bt", "B", "total", "Hkv", "D", "cap", "page", "pages")] == \
         [k.data_ptr(), v.data_ptr(), kc.data_ptr(), vc.data_ptr(), cu.data_ptr(), lens.data_ptr(), bt.data_ptr(), 2, 10, 2, 64, 3, 64, 6]
@@ -334,7 +336,7 @@ def test_the_fused_prefill_appends_then_attends_on_the_rotated_q(monkeypatch):
     flash_attention_prefill(q, kc, vc, cu, lens, bt, max_seqlen_q=6, k=k, v=v, rotary_cos=cos, rotary_sin=sin, rotary_interleaved=False)
     (n1, a1), (n2, a2) = rec.calls
     assert (n1, n2) == ("fa2_kvcache_append_varlen", "fa2_fwd_prefill")
-    assert arg(a1, "q") == q.data_ptr() and arg(a1, "qo") not in (None, q.data_ptr()) and a2[2] == arg(a1, "qo"), "prefill reads the rotated q"
+    assert arg(a1, "q") == q.data_ptr() and arg(a1, "qo") not in (None, q.data_ptr()) and dc.arg("prefill", a2, "q") == arg(a1, "qo"), "prefill reads the rotated q"
     assert [arg(a1, n) for n in ("rot", "H", "sro", "ros", "inter", "rdt")] == [32, 4, 16, 16, 0, F32] and tuple(arg(a1, "qs")) == (64, 256)
     del rec.calls[:]
     assert kvcache_append_varlen(kc, vc, k, v, cu, lens, bt) is None and [n for n, _ in rec.calls] == ["fa2_kvcache_append_varlen"]

@@ -5,6 +5,7 @@ import ctypes
 import pytest
 import torch
 
+import decode_calls as dc
 from rocwmma_fattn import FlashAttn, _fa2_lib
 
 TILE = 64
@@ -83,30 +84,27 @@ def test_plan_reports_the_prefill_kernel_and_follows_option_rows():
 # ---------------------------------------------------------------------------------------------------------------- error codes on host memory
 _HOST = ctypes.create_string_buffer(4096 + 16)
 HOST = (ctypes.addressof(_HOST) + 15) & ~15          # 16-byte aligned host memory that no call here ever touches
-ORDER = ("dtype", "format", "q", "k", "v", "o", "lse", "cu", "lens", "bt", "B", "H", "Hkv", "max_q", "D", "capacity", "page", "num_pages", "qs", "ks", "vs", "os",
-         "lse_stride", "bts", "scale", "window_left", "softcap", "slopes", "slope_stride", "stream")
 NULL, BAD_SHAPE, HEAD_DIM, ALIGN, DTYPE, SCALE, GRID, SOFTCAP = -1, -2, -3, -4, -5, -6, -7, -10
 
 
 def _call(**kw):
     s2, s3 = _fa2_lib.strides2, _fa2_lib.strides3
-    a = dict(dtype=_fa2_lib.FA2_DTYPE_F16, format=_fa2_lib.FA2_CACHE_16BIT, q=HOST, k=HOST, v=HOST, o=HOST, lse=HOST, cu=HOST, lens=HOST, bt=HOST, B=2, H=4, Hkv=2,
-             max_q=300, D=128, capacity=8, page=64, num_pages=20, qs=s2(128, 512), ks=s3(64 * 256, 128, 256), vs=s3(64 * 256, 128, 256), os=s2(128, 512),
-             lse_stride=1024, bts=8, scale=0.125, window_left=-1, softcap=0.0, slopes=None, slope_stride=0, stream=None)
-    a.update(kw)
-    return _fa2_lib.load().fa2_fwd_prefill(*[a[n] for n in ORDER])
+    a = dict(dtype=_fa2_lib.FA2_DTYPE_F16, fmt=_fa2_lib.FA2_CACHE_16BIT, q=HOST, k=HOST, v=HOST, o=HOST, lse=HOST, cu=HOST, lens=HOST, bt=HOST, B=2, H=4, Hkv=2,
+             max_q=300, D=128, cap=8, page=64, pages=20, qs=s2(128, 512), ks=s3(64 * 256, 128, 256), vs=s3(64 * 256, 128, 256), os=s2(128, 512),
+             lss=1024, bts=8, scale=0.125, wl=-1, cap_=0.0, sl=None, st=0, stream=None)
+    return dc.host_call("prefill", a, **kw)
 
 
 BAD = {      # one defect per class, in the order the classes are checked
     NULL: [dict(q=None), dict(k=None), dict(o=None), dict(lse=None), dict(cu=None), dict(lens=None), dict(bt=None), dict(qs=None), dict(ks=None), dict(os=None)],
-    BAD_SHAPE: [dict(B=0), dict(H=0), dict(Hkv=3), dict(max_q=0), dict(page=96), dict(page=-64), dict(capacity=0), dict(num_pages=0), dict(window_left=-2),
-                dict(lse_stride=-1), dict(slope_stride=-1), dict(capacity=2 ** 25), dict(ks=_fa2_lib.strides3(8, 8, 2 ** 24))],
+    BAD_SHAPE: [dict(B=0), dict(H=0), dict(Hkv=3), dict(max_q=0), dict(page=96), dict(page=-64), dict(cap=0), dict(pages=0), dict(wl=-2),
+                dict(lss=-1), dict(st=-1), dict(cap=2 ** 25), dict(ks=_fa2_lib.strides3(8, 8, 2 ** 24))],
     HEAD_DIM: [dict(D=12), dict(D=520)],
     ALIGN: [dict(q=HOST + 8), dict(k=HOST + 2), dict(o=HOST + 4), dict(lse=HOST + 2), dict(cu=HOST + 2), dict(lens=HOST + 1), dict(bt=HOST + 2),
-            dict(slopes=HOST + 2), dict(qs=_fa2_lib.strides2(4, 512)), dict(ks=_fa2_lib.strides3(64 * 256, 128, 4)), dict(os=_fa2_lib.strides2(128, 0)), dict(bts=-8)],
-    DTYPE: [dict(dtype=5), dict(format=_fa2_lib.FA2_CACHE_E4M3), dict(format=9)],
+            dict(sl=HOST + 2), dict(qs=_fa2_lib.strides2(4, 512)), dict(ks=_fa2_lib.strides3(64 * 256, 128, 4)), dict(os=_fa2_lib.strides2(128, 0)), dict(bts=-8)],
+    DTYPE: [dict(dtype=5), dict(fmt=_fa2_lib.FA2_CACHE_E4M3), dict(fmt=9)],
     SCALE: [dict(scale=float("nan")), dict(scale=float("inf"))],
-    SOFTCAP: [dict(softcap=-1.0), dict(softcap=float("nan"))],
+    SOFTCAP: [dict(cap_=-1.0), dict(cap_=float("nan"))],
     GRID: [dict(B=2 ** 15, H=2 ** 15, Hkv=2 ** 15, max_q=2 ** 20)],
 }
 CLASSES = (NULL, BAD_SHAPE, HEAD_DIM, ALIGN, DTYPE, SCALE, SOFTCAP, GRID)
@@ -117,8 +115,8 @@ def test_every_error_code_is_returned():
         for kw in cases:
             assert _call(**kw) == rc, kw
     # the contiguous layout takes no block table and no pool size
-    assert _call(bt=None, page=0, capacity=717, num_pages=0, q=None) == NULL
-    assert _call(bt=None, page=0, capacity=717, num_pages=0, D=12) == HEAD_DIM
+    assert _call(bt=None, page=0, cap=717, pages=0, q=None) == NULL
+    assert _call(bt=None, page=0, cap=717, pages=0, D=12) == HEAD_DIM
 
 
 def test_error_classes_are_checked_in_decode_order():

@@ -7,6 +7,7 @@ import os
 import pytest
 import torch
 
+import decode_calls as dc
 import prefill_calls as pc
 import prefill_fp8_calls as p8
 from conftest import ROOT
@@ -56,33 +57,32 @@ def test_plan_answers_as_the_16_bit_plan_up_to_head_dim_256():
 # ---------------------------------------------------------------------------------------------------------------- error codes on host memory
 _HOST = ctypes.create_string_buffer(4096 + 16)
 HOST = (ctypes.addressof(_HOST) + 15) & ~15          # 16-byte aligned host memory that no call here ever touches
-ORDER = ("dtype", "q", "k", "v", "o", "lse", "cu", "lens", "bt", "B", "H", "Hkv", "max_q", "D", "capacity", "page", "num_pages", "qs", "ks", "vs", "os",
-         "lse_stride", "bts", "scale", "kd", "vd", "ds", "window_left", "softcap", "slopes", "slope_stride", "stream")
 NULL, BAD_SHAPE, HEAD_DIM, ALIGN, DTYPE, SCALE, GRID, SOFTCAP = -1, -2, -3, -4, -5, -6, -7, -10
 S2, S3 = _fa2_lib.strides2, _fa2_lib.strides3
 
 
+DEFAULTS = dict(dtype=_fa2_lib.FA2_DTYPE_F16, q=HOST, k=HOST, v=HOST, o=HOST, lse=HOST, cu=HOST, lens=HOST, bt=HOST, B=2, H=4, Hkv=2,
+                max_q=300, D=128, cap=8, page=64, pages=20, qs=S2(128, 512), ks=S3(64 * 256, 128, 256), vs=S3(64 * 256, 128, 256), os=S2(128, 512),
+                lss=1024, bts=8, scale=0.125, kd=HOST, vd=HOST + 64, ds=S2(2, 1), wl=-1, cap_=0.0, sl=None, st=0, stream=None)
+
+
 def _call(**kw):
-    a = dict(dtype=_fa2_lib.FA2_DTYPE_F16, q=HOST, k=HOST, v=HOST, o=HOST, lse=HOST, cu=HOST, lens=HOST, bt=HOST, B=2, H=4, Hkv=2,
-             max_q=300, D=128, capacity=8, page=64, num_pages=20, qs=S2(128, 512), ks=S3(64 * 256, 128, 256), vs=S3(64 * 256, 128, 256), os=S2(128, 512),
-             lse_stride=1024, bts=8, scale=0.125, kd=HOST, vd=HOST + 64, ds=S2(2, 1), window_left=-1, softcap=0.0, slopes=None, slope_stride=0, stream=None)
-    a.update(kw)
-    return _fa2_lib.load().fa2_fwd_prefill_fp8(*[a[n] for n in ORDER])
+    return dc.host_call("prefill_fp8", DEFAULTS, **kw)
 
 
 BAD = {      # one defect per class, in the order the classes are checked
     NULL: [dict(q=None), dict(k=None), dict(v=None), dict(o=None), dict(lse=None), dict(cu=None), dict(lens=None), dict(bt=None), dict(qs=None), dict(ks=None),
            dict(os=None), dict(ds=None), dict(ds=None, vd=None), dict(ds=None, kd=None)],
-    BAD_SHAPE: [dict(B=0), dict(H=0), dict(Hkv=3), dict(max_q=0), dict(page=96), dict(page=-64), dict(capacity=0), dict(num_pages=0), dict(window_left=-2),
-                dict(lse_stride=-1), dict(slope_stride=-1), dict(capacity=2 ** 25), dict(ds=S2(-2, 1)), dict(ds=S2(2, -1)),
+    BAD_SHAPE: [dict(B=0), dict(H=0), dict(Hkv=3), dict(max_q=0), dict(page=96), dict(page=-64), dict(cap=0), dict(pages=0), dict(wl=-2),
+                dict(lss=-1), dict(st=-1), dict(cap=2 ** 25), dict(ds=S2(-2, 1)), dict(ds=S2(2, -1)),
                 dict(ks=S3(16, 16, 2 ** 25)), dict(vs=S3(16, 16, 2 ** 25))],                  # one tile: 64 rows of 2^25 BYTES = 2^31
     HEAD_DIM: [dict(D=12), dict(D=72), dict(D=264), dict(D=512), dict(D=520)],
     ALIGN: [dict(q=HOST + 8), dict(k=HOST + 8), dict(v=HOST + 2), dict(o=HOST + 4), dict(lse=HOST + 2), dict(cu=HOST + 2), dict(lens=HOST + 1),
-            dict(bt=HOST + 2), dict(slopes=HOST + 2), dict(kd=HOST + 2), dict(vd=HOST + 1), dict(qs=S2(4, 512)), dict(ks=S3(64 * 256, 128, 8)),
+            dict(bt=HOST + 2), dict(sl=HOST + 2), dict(kd=HOST + 2), dict(vd=HOST + 1), dict(qs=S2(4, 512)), dict(ks=S3(64 * 256, 128, 8)),
             dict(vs=S3(64 * 256, 8, 256)), dict(ks=S3(64 * 256 + 8, 128, 256)), dict(os=S2(128, 0)), dict(bts=-8)],
     DTYPE: [dict(dtype=5), dict(dtype=_fa2_lib.FA2_DTYPE_F32)],
     SCALE: [dict(scale=float("nan")), dict(scale=float("inf"))],
-    SOFTCAP: [dict(softcap=-1.0), dict(softcap=float("nan"))],
+    SOFTCAP: [dict(cap_=-1.0), dict(cap_=float("nan"))],
     GRID: [dict(B=2 ** 15, H=2 ** 15, Hkv=2 ** 15, max_q=2 ** 20)],
 }
 CLASSES = (NULL, BAD_SHAPE, HEAD_DIM, ALIGN, DTYPE, SCALE, SOFTCAP, GRID)
@@ -93,8 +93,8 @@ def test_every_error_code_is_returned():
         for kw in cases:
             assert _call(**kw) == rc, kw
     # the contiguous layout takes no block table and no pool size; null descales need no stride pair
-    assert _call(bt=None, page=0, capacity=717, num_pages=0, q=None) == NULL
-    assert _call(bt=None, page=0, capacity=717, num_pages=0, D=72) == HEAD_DIM
+    assert _call(bt=None, page=0, cap=717, pages=0, q=None) == NULL
+    assert _call(bt=None, page=0, cap=717, pages=0, D=72) == HEAD_DIM
     assert _call(kd=None, vd=None, ds=None, scale=float("nan")) == SCALE
     # the tile rule counts bytes: a row stride of 2^24 elements is 2^30 bytes per tile here (the 16-bit call refuses it), 2^25 is 2^31
     assert _call(ks=S3(16, 16, 2 ** 24), scale=float("nan")) == SCALE
@@ -116,10 +116,7 @@ def test_error_classes_are_checked_in_the_16_bit_calls_order():
 
 
 def test_the_16_bit_entry_still_refuses_an_e4m3_cache():
-    lib = _fa2_lib.load()
-    a = [_fa2_lib.FA2_DTYPE_F16, _fa2_lib.FA2_CACHE_E4M3] + [HOST] * 8 + [2, 4, 2, 300, 128, 8, 64, 20, S2(128, 512), S3(64 * 256, 128, 256), S3(64 * 256, 128, 256),
-                                                                  S2(128, 512), 1024, 8, 0.125, -1, 0.0, None, 0, None]
-    assert lib.fa2_fwd_prefill(*a) == DTYPE
+    assert dc.host_call("prefill", DEFAULTS, fmt=_fa2_lib.FA2_CACHE_E4M3, kd=None, vd=None, ds=None) == DTYPE
 
 
 # ---------------------------------------------------------------------------------------------------------------- the operator

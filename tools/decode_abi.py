@@ -1,7 +1,7 @@
-"""The C argument order of the decode and append entries, for the tests and the tools alike: fa2_fwd_decode, fa2_fwd_decode_fp8, fa2_fwd_decode_window,
-fa2_kvcache_append and fa2_kvcache_append_varlen by keyword (ENTRIES, c_args: the only copy under tests/ and tools/), what the tensors of a call say (tensor_kw) and the GPU call on
-NaN-filled outputs and workspace (decode_c).  tests/decode_calls.py hands these on to the tests beside what only tests need; the tools import them
-here, so that a tool runs with nothing but itself, this file and the package."""
+"""The C argument order of the serving entries, for the tests and the tools alike: fa2_fwd_decode, fa2_fwd_decode_fp8, fa2_fwd_decode_window,
+fa2_kvcache_append, fa2_kvcache_append_varlen, fa2_fwd_prefill and fa2_fwd_prefill_fp8 by keyword (ENTRIES, c_args: the only copy under tests/ and
+tools/), what the tensors of a decode call say (tensor_kw) and the GPU call on NaN-filled outputs and workspace (decode_c).  tests/decode_calls.py hands
+these on to the tests beside what only tests need; the tools import them here, so that a tool runs with nothing but itself, this file and the package."""
 import ctypes
 
 import torch
@@ -38,18 +38,23 @@ def same_bits(a, b):
 _HEAD = ("q", "k", "v", "o", "lse", "lens", "bt", "B", "H", "Hkv", "Nq", "D", "cap", "page", "pages", "qs", "ks", "vs", "os", "ls", "bts", "scale")
 _DESCALES = ("kd", "vd", "ds")
 _TAIL = ("ns", "ws", "wsb", "stream")
+_SCOREMOD = ("wl", "cap_", "sl", "st")
+_PREFILL_HEAD = ("q", "k", "v", "o", "lse", "cu", "lens", "bt", "B", "H", "Hkv", "max_q", "D", "cap", "page", "pages", "qs", "ks", "vs", "os", "lss", "bts",
+                 "scale")         # (qs, os: {head, row} pairs of packed tensors; lss: the one head stride of lse [H, total_q])
 ENTRIES = {      # entry -> (symbol, its arguments by keyword, its workspace query)
     "plain": ("fa2_fwd_decode", ("dtype",) + _HEAD + _TAIL, "fa2_fwd_decode_workspace_bytes"),
     "fp8": ("fa2_fwd_decode_fp8", ("dtype",) + _HEAD + _DESCALES + _TAIL, "fa2_fwd_decode_fp8_workspace_bytes"),
-    "window": ("fa2_fwd_decode_window", ("dtype", "fmt") + _HEAD + _DESCALES + ("wl", "cap_", "sl", "st") + _TAIL, "fa2_fwd_decode_window_workspace_bytes"),
+    "window": ("fa2_fwd_decode_window", ("dtype", "fmt") + _HEAD + _DESCALES + _SCOREMOD + _TAIL, "fa2_fwd_decode_window_workspace_bytes"),
     "append": ("fa2_kvcache_append", ("dtype", "fmt", "kn", "vn", "k", "v", "lens", "bt", "B", "Hkv", "N", "D", "cap", "page", "pages", "kns", "vns", "ks", "vs", "bts",
                                       "q", "qo", "H", "Nq", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter") + _DESCALES + ("stream",), None),
     "append_varlen": ("fa2_kvcache_append_varlen", ("dtype", "fmt", "kn", "vn", "k", "v", "cu", "lens", "bt", "B", "total", "Hkv", "D", "cap", "page", "pages", "kns", "vns",
                                                     "ks", "vs", "bts", "q", "qo", "H", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter") + _DESCALES +
                       ("stream",), None),
+    "prefill": ("fa2_fwd_prefill", ("dtype", "fmt") + _PREFILL_HEAD + _SCOREMOD + ("stream",), None),
+    "prefill_fp8": ("fa2_fwd_prefill_fp8", ("dtype",) + _PREFILL_HEAD + _DESCALES + _SCOREMOD + ("stream",), None),
 }
 _ABSENT = dict(kd=None, vd=None, ds=None, wl=-1, cap_=0.0, sl=None, st=0)      # what an entry without the argument computes with
-_FORMAT = {"plain": _fa2_lib.FA2_CACHE_16BIT, "fp8": _fa2_lib.FA2_CACHE_E4M3}   # ... and the cache format it serves
+_FORMAT = {"plain": _fa2_lib.FA2_CACHE_16BIT, "fp8": _fa2_lib.FA2_CACHE_E4M3, "prefill_fp8": _fa2_lib.FA2_CACHE_E4M3}   # ... and the cache format it serves
 
 
 def c_args(entry, **kw):
