@@ -71,6 +71,8 @@ UNITS = [
     ("decode_hip_bf16", "decode_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("decode_fp8_hip_f16", "decode_hip.cpp", ["-DFA2_TU_BF16=0", "-DFA2_TU_FP8=1"]),      # e4m3 caches, f16 / bf16 q and o
     ("decode_fp8_hip_bf16", "decode_hip.cpp", ["-DFA2_TU_BF16=1", "-DFA2_TU_FP8=1"]),
+    ("decode_mla_hip_f16", "decode_mla_hip.cpp", ["-DFA2_TU_BF16=0"]),                    # decode on a latent (MLA) cache, and the 512-wide combine
+    ("decode_mla_hip_bf16", "decode_mla_hip.cpp", ["-DFA2_TU_BF16=1"]),
     # KV-cache append (rotary, e4m3 quantisation): NaNs honoured, so that the e4m3 clamp lets a NaN through to the convert
     ("kvappend_hip_f16", "kvappend_hip.cpp", ["-DFA2_TU_BF16=0", "-fhonor-nans"]),
     ("kvappend_hip_bf16", "kvappend_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans"]),
@@ -86,7 +88,7 @@ FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")
 GENERATORS = [os.path.join("gen", "fwd_d128_gen.py"), os.path.join("gen", "fwd_m16_gen.py"), os.path.join("gen", "fwd_m16_d256_gen.py"), os.path.join("gen", "bwd_d128_gen.py"),
               os.path.join("gen", "bwd_dq_m16_gen.py"), os.path.join("gen", "bwd_dkv_m16_gen.py")]
-HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_kvappend.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
+HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_kvappend.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
            os.path.join(INCLUDE, "fa2_gfx950.h"), os.path.join("gen", "isa.py"), os.path.join("gen", "sched.py"), os.path.join("gen", "gen_driver.py")] + GENERATORS
 
 HIPCC_FLAGS = [

@@ -18,6 +18,7 @@
 // (reference: kernel_fp16.cu:854-863).
 #include "fa2_launch.h"
 #include "fa2_dropout.h"
+#include "fa2_decode_mla.hip.h"      // the latent-cache decode: its constants, the arithmetic the plan shares with the kernel, its launcher
 
 #include <algorithm>
 #include <cmath>
@@ -1721,6 +1722,138 @@ int fa2_fwd_decode_fp8_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int
 
 size_t fa2_fwd_decode_fp8_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits) {
     return fa2_fwd_decode_workspace_bytes(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits);
+}
+
+// ---- decode attention on a latent (MLA) KV cache: include/fa2_gfx950.h has the contract, csrc/fa2_decode_mla.hip.h the kernel and the arithmetic the
+// plan shares with it, decode_mla_hip.cpp the launches.  The cache is a CacheDesc whose k and v are the one latent tensor (Hkv = 1).
+struct DecodeMlaCall : CacheDesc {
+    int dtype = 0, B = 0, H = 0, Nq = 0, D = 0, Dv = 0;
+    const void* q = nullptr;
+    void* o = nullptr;
+    float* lse = nullptr;
+    const int* lens = nullptr;
+    const int64_t *qs = nullptr, *os = nullptr, *ls = nullptr;      // {batch, head, row}; ls: {batch, head}
+    float scale = 0.f;
+    int num_splits = 0;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    void* stream = nullptr;
+};
+
+// The sizes of the call, in the documented order (shape, then head dim)
+static int decode_mla_check_shape(const DecodeMlaCall& c) {
+    if (c.B < 1 || c.H < 1 || c.Nq < 1 || c.D < 1 || c.Dv < 1 || c.H > fa2::kMlaMaxHeads) return FA2_ERR_BAD_SHAPE;
+    if ((int64_t)c.Nq * c.H > fa2::kMlaMaxRows || !cache_paging_ok(c) || c.num_splits < 0 || c.num_splits > fa2::kMlaMaxSplit) return FA2_ERR_BAD_SHAPE;
+    if (c.D != fa2::kMlaD || c.Dv != fa2::kMlaDv) return FA2_ERR_HEAD_DIM;
+    return FA2_OK;
+}
+
+// The split: decode_split's reasoning for a workgroup that fills a CU on its own (one per CU: 73 KiB of LDS, more than 256 registers per lane).
+// B * row blocks >= CUs: the chip is covered, no split.  Otherwise one workgroup per CU's worth of parts, at most kMlaMaxSplit, and no part shorter
+// than kMlaMinPartTiles key tiles of the capacity (csrc/fa2_decode_mla.hip.h has the arithmetic behind both constants).
+static int decode_mla_split(int B, int row_blocks, int64_t capacity_tiles, int num_splits) {
+    if (num_splits > 0) return num_splits;
+    const int64_t work = (int64_t)B * row_blocks, cus = fa2::device_cus();
+    if (work >= cus) return 1;
+    int64_t S = cus / work;
+    if (S > fa2::kMlaMaxSplit) S = fa2::kMlaMaxSplit;
+    if (S > capacity_tiles / fa2::kMlaMinPartTiles) S = capacity_tiles / fa2::kMlaMinPartTiles;
+    return S < 1 ? 1 : (int)S;
+}
+
+static int decode_mla_plan(const DecodeMlaCall& c, fa2_decode_mla_plan_t* plan) {
+    if (int rc = decode_mla_check_shape(c)) return rc;
+    if (c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    plan->kernel = FA2_KERNEL_HIP_DECODE_MLA;
+    plan->row_blocks = fa2::mla_row_blocks(c.Nq * c.H);
+    plan->key_tile = fa2::kMlaTile;
+    plan->max_split = fa2::kMlaMaxSplit;
+    plan->nsplit = decode_mla_split(c.B, plan->row_blocks, (c.capacity_keys() + fa2::kMlaTile - 1) / fa2::kMlaTile, c.num_splits);
+    return FA2_OK;
+}
+
+// The f32 parts a split call leaves between its two launches: decode's layout with one K / V head
+static size_t decode_mla_ws_need(const DecodeMlaCall& c, const fa2_decode_mla_plan_t& plan) {
+    return (size_t)fa2::decode_ws_bytes(c.B, plan.nsplit, c.Nq * c.H, fa2::kMlaDv);
+}
+
+#define FA2_DECODE_MLA_SIZES(c) \
+    DecodeMlaCall c;            \
+    c.dtype = dtype; c.B = B; c.H = H; c.Nq = Nq; c.D = D; c.Dv = Dv; c.capacity = capacity; c.page_size = page_size; c.num_splits = num_splits
+
+int fa2_fwd_decode_mla_plan(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, fa2_decode_mla_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    std::memset(plan, 0, sizeof(*plan));
+    FA2_DECODE_MLA_SIZES(c);
+    return decode_mla_plan(c, plan);
+}
+
+size_t fa2_fwd_decode_mla_workspace_bytes(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits) {
+    fa2_decode_mla_plan_t plan;
+    FA2_DECODE_MLA_SIZES(c);
+    return decode_mla_plan(c, &plan) ? 0 : decode_mla_ws_need(c, plan);
+}
+
+int fa2_decode_mla_part_range(int64_t len, int64_t capacity_keys, int nsplit, int part, int* first_tile, int* ntiles) {
+    if (!first_tile || !ntiles) return FA2_ERR_NULL_POINTER;
+    if (capacity_keys < 0 || capacity_keys > 0x7fffffffLL - 64 || nsplit < 1 || nsplit > fa2::kMlaMaxSplit || part < 0 || part >= nsplit) return FA2_ERR_BAD_SHAPE;
+    fa2::mla_part_range(len, capacity_keys, nsplit, part, first_tile, ntiles);
+    return FA2_OK;
+}
+
+int fa2_decode_mla_tile(int64_t len, int capacity, int page_size, int tile, int* page_slot, int* row_in_page, int* valid_rows) {
+    if (!page_slot || !row_in_page || !valid_rows) return FA2_ERR_NULL_POINTER;
+    CacheDesc c;
+    c.capacity = capacity; c.page_size = page_size;
+    if (!cache_paging_ok(c) || c.capacity_keys() > 0x7fffffffLL - 64) return FA2_ERR_BAD_SHAPE;
+    const int64_t cap = c.capacity_keys();
+    if (tile < 0 || tile >= (cap + fa2::kMlaTile - 1) / fa2::kMlaTile) return FA2_ERR_BAD_SHAPE;
+    const fa2::MlaTile t = fa2::mla_tile(tile, fa2::decode_clamp_len(len, cap), fa2::mla_page_keys(page_size, cap));
+    *page_slot = t.slot; *row_in_page = t.row; *valid_rows = t.rows;
+    return FA2_OK;
+}
+
+static int decode_mla_run(const DecodeMlaCall& c) {
+    if (any_null({c.q, c.o, c.lse, c.lens, c.qs, c.os, c.ls}) || cache_null(c)) return FA2_ERR_NULL_POINTER;
+    if (int rc = decode_mla_check_shape(c)) return rc;
+    if (!cache_extent_ok(c) || c.ls[0] < 0 || c.ls[1] < 0) return FA2_ERR_BAD_SHAPE;
+    if (!all_aligned16({c.q, c.o}) || !cache_aligned(c) || ((reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.lens)) & 3u) ||
+        !strides3_ok(c.qs) || !strides3_ok(c.os))
+        return FA2_ERR_ALIGNMENT;
+    fa2_decode_mla_plan_t plan;
+    if (int rc = decode_mla_plan(c, &plan)) return rc;                // (the dtype: after the alignment)
+    if (!std::isfinite(c.scale)) return FA2_ERR_SCALE;
+    if (c.B > 65535) return FA2_ERR_GRID;
+    fa2::DecodeParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = c.q; p.k = c.k; p.v = c.k; p.o = c.o; p.lse = c.lse; p.lens = c.lens; p.bt = c.page_size > 0 ? c.block_table : nullptr;
+    p.B = c.B; p.H = c.H; p.Hkv = 1; p.Nq = c.Nq; p.G = c.H; p.rows = c.Nq * c.H;
+    p.page_size = c.page_size; p.num_pages = c.num_pages; p.nsplit = plan.nsplit;
+    p.capacity_keys = c.capacity_keys();
+    for (int i = 0; i < 3; ++i) { p.qs[i] = c.qs[i]; p.ks[i] = c.ks[i]; p.vs[i] = c.ks[i]; p.os[i] = c.os[i]; }
+    p.ls[0] = c.ls[0]; p.ls[1] = c.ls[1];
+    p.bts = c.bts;
+    p.c = c.scale * 1.4426950408889634f;
+    p.window_left = -1;
+    p.scale = c.scale;
+    if (plan.nsplit > 1) {
+        if (!c.ws) return FA2_ERR_NULL_POINTER;
+        if (!aligned16(c.ws)) return FA2_ERR_ALIGNMENT;
+        if (c.ws_bytes < decode_mla_ws_need(c, plan)) return FA2_ERR_BAD_SHAPE;
+        p.ws = static_cast<float*>(c.ws);
+    }
+    return fa2::launch_decode_mla(c.dtype == FA2_DTYPE_BF16, p, (hipStream_t)c.stream);
+}
+
+int fa2_fwd_decode_mla(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table, int B, int H,
+                       int Nq, int D, int Dv, int capacity, int page_size, int num_pages, const int64_t q_strides[3], const int64_t kv_strides[3],
+                       const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale, int num_splits, void* workspace,
+                       size_t workspace_bytes, void* hip_stream) {
+    FA2_DECODE_MLA_SIZES(c);
+    c.q = q; c.k = kv_cache; c.v = kv_cache; c.o = o; c.lse = lse; c.lens = cache_seqlens; c.block_table = block_table; c.num_pages = num_pages;
+    c.qs = q_strides; c.ks = kv_strides; c.vs = kv_strides; c.os = o_strides; c.ls = lse_strides; c.bts = block_table_stride; c.scale = scale;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = hip_stream;
+    return decode_mla_run(c);
 }
 
 // ---- KV-cache append with rotary embedding and e4m3 quantisation: include/fa2_gfx950.h has the contract, csrc/fa2_kvappend.hip.h the kernel,

@@ -26,7 +26,7 @@ import torch
 from . import _fa2_lib
 
 __all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
-           "kvcache_append_varlen"]
+           "kvcache_append_varlen", "flash_attention_decode_mla"]
 
 
 class _FlashAttnWmma:
@@ -1469,6 +1469,71 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
             rc = lib.fa2_fwd_decode_fp8(code, *head, *cache.descales, *tail)
         else:
             rc = lib.fa2_fwd_decode(code, *head, *tail)
+    _fa2_lib.check(rc)
+    return (o, lse * _LN2) if return_lse else o
+
+
+_MLA_D, _MLA_DV, _MLA_MAX_HEADS, _MLA_MAX_ROWS, _MLA_MAX_SPLITS = 576, 512, 128, 512, 128      # csrc/fa2_decode_mla.hip.h (the split cap: the plan reports it)
+
+
+def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, head_dim_v=512, scale=None, return_lse=False, num_splits=0):
+    """Decode attention on a multi-head-latent (MLA) KV cache — the decode step of DeepSeek-V2 / V3 / R1 and Kimi K2 with the up-projections absorbed
+    into the query and the output (the flash_mla_with_kvcache shape).
+    q [B, Nq, H, 576] fp16 / bf16: the absorbed query, q_nope . W_UK in columns 0 .. 511 and the rotated q_pe in columns 512 .. 575.  A q the kernel
+    cannot address (last dim not contiguous, strides no multiples of 8 elements, storage not 16-byte aligned) is copied, as in flash_attention_decode.
+    kv_cache, in q's dtype: one latent row of 576 columns per token, shared by all heads — 512 of compressed KV, then 64 of rotary key; its first 512
+    columns are also the value.  Contiguous: [B, Nmax, 576].  Paged: [num_pages, page_size, 576] with block_table int32 [B, max_pages] on q's device,
+    page_size a multiple of 64.  A 4-D cache with a head axis of size 1 ([.., .., 1, 576]) is accepted in both forms.  Strided views are fine; a cache
+    the kernel cannot address raises — it is never copied.
+    cache_seqlens: int32 [B] on q's device, the valid keys of each sequence INCLUDING the Nq new tokens.  The host reads neither it nor the block
+    table: the call can be captured in a graph and replayed as they change in place.
+    o[b, i, h] = softmax_j(scale * q[b, i, h, :] . kv[b, j, :]) . kv[b, j, :512] under decode's mask, bottom-right causal: row i sits at position
+    len_b - Nq + i.  Rows at a negative position return zeros (lse -inf).  Keys at or beyond len_b and unused pages contribute nothing whatever they
+    hold, NaN included; lengths and page ids are clamped in-kernel: a wrong one gives a wrong answer, never an out-of-bounds access.
+    scale: None = 576 ** -0.5 (FlashMLA's default).  DeepSeek callers pass their own: the softmax scale of the NON-absorbed head dim (192 ** -0.5, times
+    the YaRN mscale factor where the model has one).
+    head_dim_v must be 512 and q.shape[-1] 576; H is 1 .. 128 and Nq * H <= 512 (TP8's 16 heads up to all 128, with a few speculative tokens).
+    Anything else raises ValueError.  Returns o [B, Nq, H, 512]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention
+    composes with it).  num_splits: 0 = the library's plan, 1 .. 128 = that many parts per (sequence, block of 64 rows).  Inference only.
+    Writing new tokens into a latent cache is the caller's: kvcache_append serves head dims up to 512 and rotates the leading columns.
+    C-ABI fa2_fwd_decode_mla: each cache row is fetched once per workgroup and used as K and as V for up to 64 (token, head) rows; no atomics."""
+    who = "flash_attention_decode_mla"
+    if not all(torch.is_tensor(t) for t in (q, kv_cache, cache_seqlens)) or q.dim() != 4 or kv_cache.dim() not in (3, 4) or \
+            (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):
+        raise ValueError("fa2: %s takes q [B, Nq, H, 576] and a latent kv_cache [B, Nmax, 576] ([num_pages, page_size, 576] with a block_table); a 4-D "
+                         "cache has a head axis of size 1" % who)
+    if torch.is_grad_enabled() and (q.requires_grad or kv_cache.requires_grad):
+        raise ValueError("fa2: %s is inference only (an input requires grad)" % who)
+    if isinstance(head_dim_v, bool) or head_dim_v != _MLA_DV or q.shape[3] != _MLA_D or kv_cache.shape[-1] != _MLA_D:
+        raise ValueError("fa2: %s serves latent rows of %d columns whose first %d are the value (head_dim_v), got q %s kv_cache %s head_dim_v=%r"
+                         % (who, _MLA_D, _MLA_DV, tuple(q.shape), tuple(kv_cache.shape), head_dim_v))
+    if q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
+        raise ValueError("fa2: %s takes fp16 or bf16 q and kv_cache of one dtype, got %s %s" % (who, q.dtype, kv_cache.dtype))
+    B, Nq, H, D = q.shape
+    if B < 1 or Nq < 1 or not 1 <= H <= _MLA_MAX_HEADS or Nq * H > _MLA_MAX_ROWS:
+        raise ValueError("fa2: %s serves 1 .. %d heads and Nq * H <= %d query rows (B, Nq >= 1), got q %s" % (who, _MLA_MAX_HEADS, _MLA_MAX_ROWS, tuple(q.shape)))
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _MLA_MAX_SPLITS:
+        raise ValueError("fa2: num_splits is 0 (the library chooses) or 1 .. %d, got %r" % (_MLA_MAX_SPLITS, num_splits))
+    # the latent as a cache of ONE head, K and V at once: _cache_desc checks it as it checks every cache (a head stride of one row keeps its rule quiet)
+    kv4 = (kv_cache if kv_cache.dim() == 3 else kv_cache[:, :, 0]).unsqueeze(2)
+    cache = _cache_desc(False, q, B, kv4, kv4, cache_seqlens, block_table, None, None)
+    q = _bnhd_ready(q)
+    if scale is None:
+        scale = _MLA_D ** -0.5
+    lib = _fa2_lib.load()
+    code = _dtype_code(q)
+    o = torch.empty((B, Nq, H, _MLA_DV), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    dev = _device_index(q)
+    with torch.cuda.device(dev):
+        stream = _raw_stream(dev)
+        need = lib.fa2_fwd_decode_mla_workspace_bytes(code, B, H, Nq, _MLA_D, _MLA_DV, cache.capacity, cache.page_size, num_splits)
+        ws = _workspace(need, q.device, dev, stream) if need else None
+        if ws is None and _WS_POOL:
+            _workspace_unused(dev, stream)
+        rc = lib.fa2_fwd_decode_mla(code, q.data_ptr(), cache.ptrs[0], o.data_ptr(), lse.data_ptr(), *cache.tables, B, H, Nq, _MLA_D, _MLA_DV, *cache.sizes,
+                                    _bnhd(q), cache.strides[0], _bnhd(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), cache.bts, float(scale),
+                                    num_splits, None if ws is None else ws.data_ptr(), need, stream)
     _fa2_lib.check(rc)
     return (o, lse * _LN2) if return_lse else o
 

@@ -54,6 +54,15 @@ class DecodePlan(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DecodeMlaPlan(ctypes.Structure):
+    """fa2_decode_mla_plan_t (include/fa2_gfx950.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kernel", "nsplit", "row_blocks", "key_tile", "max_split")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+FA2_KERNEL_HIP_DECODE_MLA = 9                                                                           # fa2_decode_mla_plan_t.kernel (an enumerator in the header)
 FA2_KERNEL_HIP_PREFILL = 8                                                                              # fa2_fwd_prefill_plan's kernel (an enumerator in the header)
 FA2_KERNEL_HIP_DECODE = 7                                                                               # fa2_decode_plan_t.kernel (an enumerator in the header)
 FA2_BWD_KERNEL_HIP, FA2_BWD_KERNEL_ASM, FA2_BWD_KERNEL_SHORT = 1, 2, 3                                  # fa2_bwd_plan_t.dq_kernel / .dkv_kernel
@@ -165,6 +174,14 @@ SYMBOLS = {
     "fa2_fwd_decode_window_plan": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(DecodePlan)]),
     "fa2_fwd_decode_window_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
     "fa2_decode_window_part_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    # decode on a latent (MLA) cache: q kv_cache o lse cache_seqlens block_table, B H Nq D Dv capacity page_size num_pages, the q kv o stride triples, the
+    # lse pair, the block-table row stride, scale, num_splits, workspace, bytes, stream
+    "fa2_fwd_decode_mla": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +
+                           [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fa2_fwd_decode_mla_plan": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(DecodeMlaPlan)]),
+    "fa2_fwd_decode_mla_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
+    "fa2_decode_mla_part_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "fa2_decode_mla_tile": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 3),
     # KV-cache append: dtype cache_format, k_new v_new k_cache v_cache cache_seqlens block_table, B Hkv Nnew D capacity page_size num_pages, four stride
     # triples, the block-table row stride, q q_out H Nq and their stride triples, cos sin rotary_dtype rotary_dim seqlen_ro row-stride interleaved,
     # k_descale v_descale descale_strides, stream
@@ -419,6 +436,28 @@ def decode_window_part_range(length, capacity_keys, Nq, window_left, tile, nspli
     check(load().fa2_decode_window_part_range(int(length), int(capacity_keys), int(Nq), int(window_left), int(tile), int(nsplit), int(part),
                                               ctypes.byref(first), ctypes.byref(n)))
     return first.value, n.value
+
+
+def decode_mla_plan(dtype, B, H, Nq, capacity, page_size=0, num_splits=0, D=576, Dv=512):
+    """fa2_fwd_decode_mla_plan: the split, the row blocks, the key tile, the split cap and the kernel of a latent-cache decode call."""
+    plan = DecodeMlaPlan()
+    check(load().fa2_fwd_decode_mla_plan(int(dtype), int(B), int(H), int(Nq), int(D), int(Dv), int(capacity), int(page_size), int(num_splits), ctypes.byref(plan)))
+    return plan
+
+
+def decode_mla_part_range(length, capacity_keys, nsplit, part):
+    """fa2_decode_mla_part_range -> (first_tile, ntiles): the 32-key tiles part `part` of `nsplit` sweeps for a sequence of `length` keys."""
+    first, n = ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_decode_mla_part_range(int(length), int(capacity_keys), int(nsplit), int(part), ctypes.byref(first), ctypes.byref(n)))
+    return first.value, n.value
+
+
+def decode_mla_tile(length, capacity, page_size, tile):
+    """fa2_decode_mla_tile -> (page_slot, row_in_page, valid_rows) of 32-key tile `tile` of a sequence of `length` keys (capacity: key slots, or
+    block-table entries per sequence when page_size > 0)."""
+    slot, row, rows = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_decode_mla_tile(int(length), int(capacity), int(page_size), int(tile), ctypes.byref(slot), ctypes.byref(row), ctypes.byref(rows)))
+    return slot.value, row.value, rows.value
 
 
 def kvappend_slot(length, capacity_keys, Nnew, i):

@@ -736,6 +736,55 @@ size_t fa2_fwd_decode_window_workspace_bytes(int dtype, int B, int H, int Hkv, i
 int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int window_left, int tile, int nsplit, int part, int* first_tile,
                                  int* ntiles);
 
+/* ---- Decode attention on a multi-head-latent (MLA) KV cache: the decode step of DeepSeek-V2 / V3 / R1 style models with the up-projections absorbed
+ * into the query and the output.  The cache holds ONE row of D = 576 columns per token, shared by all heads (512 of compressed KV, then 64 of rotary
+ * key); its first Dv = 512 columns are also the value.  With len and the positions as in fa2_fwd_decode,
+ *   o[b, h, i, :] = softmax_j(scale * q[b, h, i, :] . kv[b, j, :]) . kv[b, j, :512]      over the keys j <= len - Nq + i.
+ *   q             : B x H x Nq x 576 (the absorbed query), o : B x H x Nq x 512; element strides {batch, head, row}, last dim contiguous.
+ *   kv_cache      : page_size == 0: B x capacity x 576; page_size > 0: num_pages x page_size x 576 under block_table, page_size a multiple of 64.
+ *                   kv_strides {batch | page, head, row}: the head stride is not used (there is one latent head) but is checked like the others.
+ *   cache_seqlens, block_table, lse, capacity, num_pages, block_table_stride : fa2_fwd_decode's, device data the host never reads (graph replay).
+ * Masking, dead rows (O = 0, lse = -inf), keys at or beyond len (nothing, whatever they hold) and the clamps of lengths and page ids are
+ * fa2_fwd_decode's.  Addresses are formed in 64 bits: a pool may exceed 4 GiB.
+ * Shapes: H 1 .. 128 and Nq * H <= 512 packed rows r = i * H + h; num_splits 0 (the plan chooses) or 1 .. 128 (fa2_decode_mla_plan_t.max_split);
+ * page_size as above: FA2_ERR_BAD_SHAPE otherwise.  D != 576 or Dv != 512: FA2_ERR_HEAD_DIM, looked at after those.
+ * Checked in fa2_fwd_decode's order: null pointers (block_table only when paged), sizes, head dim, alignment, dtype, scale, FA2_ERR_GRID (B above
+ * 65535), and last the workspace (null, alignment, size) when the split is above 1.
+ * Kernel (FA2_KERNEL_HIP_DECODE_MLA, csrc/fa2_decode_mla.hip.h; contract 0 as fa2_fwd_decode): one workgroup of four waves per (sequence, block of
+ * up to 64 packed rows, part); each 32-key tile of the cache is loaded once per workgroup into LDS and serves both products; each wave owns 16 rows.
+ * A split call leaves normalised f32 rows and log2 LSEs of the live rows in the workspace (an empty part: lse = -inf alone) and the combine kernel of
+ * fa2_fwd_decode, at head dim 512, merges them.  No atomics.
+ * Not here: an append for the 576-wide cache (fa2_kvcache_append stops at head dim 512 and rotates the LEADING columns), e4m3 latents, a window,
+ * soft-capping, slopes, a backward. */
+enum { FA2_KERNEL_HIP_DECODE_MLA = 9 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+typedef struct fa2_decode_mla_plan_t {
+    int kernel;        /* FA2_KERNEL_HIP_DECODE_MLA */
+    int nsplit;        /* parts per (sequence, row block); 1: no workspace, no combine kernel */
+    int row_blocks;    /* blocks of up to 64 packed rows: ceil(Nq * H / 64) */
+    int key_tile;      /* keys per tile (32) */
+    int max_split;     /* the largest num_splits the call takes (128) */
+} fa2_decode_mla_plan_t;
+int fa2_fwd_decode_mla(int dtype, const void* q, const void* kv_cache, void* o, float* lse,
+                       const int* cache_seqlens, const int* block_table,
+                       int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages,
+                       const int64_t q_strides[3], const int64_t kv_strides[3], const int64_t o_strides[3],
+                       const int64_t lse_strides[2], int64_t block_table_stride,
+                       float scale, int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* The plan of that call and its workspace: pure host functions of the shape, the capacity and the device's CU count, never of the lengths.
+ * Split rule: 1 when B * row_blocks workgroups cover the CUs (a workgroup fills a CU), else floor(CUs / (B * row_blocks)), at most 128 and at most one
+ * part per 8 key tiles of the capacity (a shorter part moves more workspace than cache).  Workspace: B * nsplit * Nq * H * (512 + 1) * 4 bytes, 0 for
+ * a split of 1 and for arguments the call would refuse. */
+int fa2_fwd_decode_mla_plan(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, fa2_decode_mla_plan_t* plan);
+size_t fa2_fwd_decode_mla_workspace_bytes(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits);
+/* The host side of the functions the kernel calls (csrc/fa2_decode_mla.hip.h: mla_part_range, mla_tile).
+ * fa2_decode_mla_part_range: fa2_decode_part_range's rule on 32-key tiles with nsplit in 1 .. 128.
+ * fa2_decode_mla_tile: where 32-key tile `tile` of a sequence lies — len is clamped into [0, capacity_keys] (capacity_keys = capacity, paged:
+ * capacity * page_size); *page_slot = the block-table slot of its page (contiguous: 0), *row_in_page its first row there, *valid_rows how many of its 32
+ * rows hold a key of the sequence (0: the tile lies at or beyond the length).  FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for capacity < 1, a page size
+ * that is no multiple of 64, or a tile outside [0, ceil(capacity_keys / 32)). */
+int fa2_decode_mla_part_range(int64_t len, int64_t capacity_keys, int nsplit, int part, int* first_tile, int* ntiles);
+int fa2_decode_mla_tile(int64_t len, int capacity, int page_size, int tile, int* page_slot, int* row_in_page, int* valid_rows);
+
 /* ---- KV-cache append: the write side of the decode calls.  One launch writes the K and V rows of Nnew new tokens per sequence into the cache at the
  * key position only the device knows, optionally rotates k (and q) by that position and optionally quantises to e4m3.
  * Layout (element strides {batch, head, row}, D contiguous)
