@@ -83,12 +83,17 @@ UNITS = [
     ("kvappend_varlen_hip_bf16", "kvappend_varlen_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans"]),
     ("kvappend_varlen_fp8_hip_f16", "kvappend_varlen_hip.cpp", ["-DFA2_TU_BF16=0", "-DFA2_TU_FP8=1", "-fhonor-nans"]),
     ("kvappend_varlen_fp8_hip_bf16", "kvappend_varlen_hip.cpp", ["-DFA2_TU_BF16=1", "-DFA2_TU_FP8=1", "-fhonor-nans"]),
+    # ... and the append for a latent (MLA) cache: kv_c and k_pe into one 576-wide row, the trailing 64 columns rotated; the uniform and the packed kernel.
+    # No SLP vectorisation: packed f32 math wants the 16 rotated pairs in aligned register pairs, which costs the bf16 kernels an occupancy step
+    # (72 registers against 56).
+    ("kvappend_mla_hip_f16", "kvappend_mla_hip.cpp", ["-DFA2_TU_BF16=0", "-fhonor-nans", "-fno-slp-vectorize"]),
+    ("kvappend_mla_hip_bf16", "kvappend_mla_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans", "-fno-slp-vectorize"]),
 ]
 FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end of the operator (host-only C++, g++)
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")
 GENERATORS = [os.path.join("gen", "fwd_d128_gen.py"), os.path.join("gen", "fwd_m16_gen.py"), os.path.join("gen", "fwd_m16_d256_gen.py"), os.path.join("gen", "bwd_d128_gen.py"),
               os.path.join("gen", "bwd_dq_m16_gen.py"), os.path.join("gen", "bwd_dkv_m16_gen.py")]
-HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_kvappend.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
+HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_kvappend.hip.h", "fa2_kvappend_mla.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
            os.path.join(INCLUDE, "fa2_gfx950.h"), os.path.join("gen", "isa.py"), os.path.join("gen", "sched.py"), os.path.join("gen", "gen_driver.py")] + GENERATORS
 
 HIPCC_FLAGS = [

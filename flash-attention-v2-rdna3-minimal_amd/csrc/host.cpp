@@ -19,6 +19,7 @@
 #include "fa2_launch.h"
 #include "fa2_dropout.h"
 #include "fa2_decode_mla.hip.h"      // the latent-cache decode: its constants, the arithmetic the plan shares with the kernel, its launcher
+#include "fa2_kvappend_mla.hip.h"    // ... and its append: the parameter block, the unit -> chunks map, its launcher
 
 #include <algorithm>
 #include <cmath>
@@ -1994,6 +1995,91 @@ int fa2_kvcache_append_varlen(int dtype, int cache_format, const void* k_new, co
     c.cos = rotary_cos; c.sin = rotary_sin; c.rotary_dtype = rotary_dtype; c.rotary_dim = rotary_dim; c.seqlen_ro = seqlen_ro; c.ros = rotary_row_stride;
     c.interleaved = rotary_interleaved; c.stream = hip_stream;
     return append_run(c, true);
+}
+
+// ---- the append for a latent (MLA) cache: include/fa2_gfx950.h has the contract, csrc/fa2_kvappend_mla.hip.h the kernels, kvappend_mla_hip.cpp their
+// launch.  The call is an AppendCall whose "K" source is kv_c and whose "V" source is k_pe (Hkv = 1, no head stride), both caches the one latent tensor,
+// in the 16-bit format; the checks run in append_run's order and classes.
+int fa2_kvappend_mla_chunks(int unit, int halves, int* chunk_a, int* chunk_b) {
+    if (!chunk_a || !chunk_b) return FA2_ERR_NULL_POINTER;
+    if (unit < 0 || unit >= fa2::kMlaUnits) return FA2_ERR_BAD_SHAPE;
+    fa2::mla_append_chunks(unit, halves != 0, chunk_a, chunk_b);
+    return FA2_OK;
+}
+
+static int append_mla_run(const AppendCall& c, int Dv, bool q_sizes_ok) {
+    const bool has_q = c.q || c.q_out, rotary = c.cos || c.sin;
+    if (any_null({c.k_new, c.v_new, c.lens, c.kns, c.vns}) || (c.packed && !c.cu) || cache_null(c) || (has_q && any_null({c.q, c.q_out, c.qs, c.qos})) ||
+        (rotary && (!c.cos || !c.sin)))
+        return FA2_ERR_NULL_POINTER;
+    if (c.B < 1 || (c.packed ? c.groups < 0 : c.Nnew < 1) || c.D < 1 || Dv < 1 || !cache_paging_ok(c) || !cache_extent_ok(c)) return FA2_ERR_BAD_SHAPE;
+    if (has_q && (!rotary || c.H < 1 || c.H > fa2::kMlaMaxHeads || !q_sizes_ok)) return FA2_ERR_BAD_SHAPE;      // q rows exist to be rotated
+    if (rotary && (c.seqlen_ro < 1 || c.ros < 0)) return FA2_ERR_BAD_SHAPE;
+    if (c.D != fa2::kMlaD || Dv != fa2::kMlaDv || (rotary && c.rotary_dim != fa2::kMlaRot)) return FA2_ERR_HEAD_DIM;
+    const bool tab32 = c.rotary_dtype == FA2_DTYPE_F32;
+    if (!all_aligned16({c.k_new, c.v_new, c.q, c.q_out, c.cos, c.sin}) || !cache_aligned(c) ||
+        ((reinterpret_cast<uintptr_t>(c.lens) | reinterpret_cast<uintptr_t>(c.cu)) & 3u) || !strides3_ok(c.kns) || !strides3_ok(c.vns) ||
+        (has_q && (!strides3_ok(c.qs) || !strides3_ok(c.qos))) || (rotary && c.ros % (tab32 ? 4 : 8) != 0))
+        return FA2_ERR_ALIGNMENT;
+    if ((c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) || (rotary && !tab32 && c.rotary_dtype != c.dtype)) return FA2_ERR_DTYPE;
+    if (c.groups > 0x7fffffffLL) return FA2_ERR_GRID;               // (blockIdx.y: at most 129 rows of 36 units)
+    if (c.packed && c.groups == 0) return FA2_OK;                   // an empty token buffer: nothing to launch
+    fa2::KvAppendMlaParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.kv_c = c.k_new; p.k_pe = c.v_new; p.kv_cache = const_cast<void*>(c.k); p.q = c.q; p.q_out = c.q_out;
+    p.cos = c.cos; p.sin = c.sin; p.lens = c.lens; p.bt = c.page_size > 0 ? c.block_table : nullptr; p.cu = c.cu;
+    p.B = c.B; p.H = has_q ? c.H : 0; p.Nnew = c.Nnew;
+    p.interleaved = c.interleaved != 0; p.tab16 = !tab32;
+    p.page_size = c.page_size; p.num_pages = c.num_pages;
+    p.R = 1 + p.H;
+    p.capacity_keys = c.capacity_keys();
+    p.seqlen_ro = rotary ? c.seqlen_ro : 1;
+    p.cs[0] = c.kns[0]; p.cs[1] = c.kns[2]; p.ps[0] = c.vns[0]; p.ps[1] = c.vns[2];
+    for (int i = 0; i < 3; ++i) {
+        p.ks[i] = c.ks[i];
+        if (has_q) { p.qs[i] = c.qs[i]; p.qos[i] = c.qos[i]; }
+    }
+    p.bts = c.bts; p.ros = c.ros;
+    return fa2::launch_kvappend_mla(c.dtype == FA2_DTYPE_BF16, p, c.groups, c.packed, (hipStream_t)c.stream);
+}
+
+// what the two entries fill alike: the cache (K and V the one latent tensor), the tables, the lengths
+#define FA2_APPEND_MLA_COMMON(c)                                                                                                              \
+    AppendCall c;                                                                                                                             \
+    c.k = kv_cache; c.v = kv_cache; c.block_table = block_table; c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;     \
+    c.ks = kv_strides; c.vs = kv_strides; c.bts = block_table_stride; c.dtype = dtype; c.B = B; c.Hkv = 1; c.H = H; c.D = D;                  \
+    c.k_new = kv_c; c.v_new = k_pe; c.q = q; c.q_out = q_out; c.lens = cache_seqlens;                                                         \
+    c.cos = rotary_cos; c.sin = rotary_sin; c.rotary_dtype = rotary_dtype; c.rotary_dim = rotary_dim; c.seqlen_ro = seqlen_ro;                \
+    c.ros = rotary_row_stride; c.interleaved = rotary_interleaved; c.stream = hip_stream
+
+int fa2_kvcache_append_mla(int dtype, const void* kv_c, const void* k_pe, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nnew,
+                           int D, int Dv, int capacity, int page_size, int num_pages, const int64_t kv_c_strides[2], const int64_t k_pe_strides[2],
+                           const int64_t kv_strides[3], int64_t block_table_stride, const void* q, void* q_out, int H, int Nq, const int64_t q_strides[3],
+                           const int64_t q_out_strides[3], const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
+                           int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream) {
+    FA2_APPEND_MLA_COMMON(c);
+    c.Nnew = Nnew; c.groups = (int64_t)B * Nnew; c.qs = q_strides; c.qos = q_out_strides;
+    int64_t st[2][3] = {};                                   // {batch, row} -> {batch, head (none), row}
+    if (kv_c_strides) { st[0][0] = kv_c_strides[0]; st[0][2] = kv_c_strides[1]; c.kns = st[0]; }
+    if (k_pe_strides) { st[1][0] = k_pe_strides[0]; st[1][2] = k_pe_strides[1]; c.vns = st[1]; }
+    return append_mla_run(c, Dv, Nq == Nnew);
+}
+
+// ... its packed (ragged) form: kv_c / k_pe are [total, 512] / [total, 64] with a row stride each, q and q_out [total, H, 576] with {head, row}
+int fa2_kvcache_append_mla_varlen(int dtype, const void* kv_c, const void* k_pe, void* kv_cache, const int* cu_seqlens, const int* cache_seqlens,
+                                  const int* block_table, int B, int64_t total, int D, int Dv, int capacity, int page_size, int num_pages,
+                                  const int64_t kv_c_strides[1], const int64_t k_pe_strides[1], const int64_t kv_strides[3], int64_t block_table_stride,
+                                  const void* q, void* q_out, int H, const int64_t q_strides[2], const int64_t q_out_strides[2], const void* rotary_cos,
+                                  const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride, int rotary_interleaved,
+                                  void* hip_stream) {
+    FA2_APPEND_MLA_COMMON(c);
+    c.packed = true; c.cu = cu_seqlens; c.groups = total;
+    int64_t st[4][3] = {};
+    if (kv_c_strides) { st[0][2] = kv_c_strides[0]; c.kns = st[0]; }
+    if (k_pe_strides) { st[1][2] = k_pe_strides[0]; c.vns = st[1]; }
+    if (q_strides) { st[2][1] = q_strides[0]; st[2][2] = q_strides[1]; c.qs = st[2]; }
+    if (q_out_strides) { st[3][1] = q_out_strides[0]; st[3][2] = q_out_strides[1]; c.qos = st[3]; }
+    return append_mla_run(c, Dv, true);
 }
 
 // ---- chunked prefill against a KV cache: include/fa2_gfx950.h has the contract, csrc/fa2_prefill.h the tile arithmetic, prefill_hip.cpp /

@@ -26,7 +26,7 @@ import torch
 from . import _fa2_lib
 
 __all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
-           "kvcache_append_varlen", "flash_attention_decode_mla"]
+           "kvcache_append_varlen", "flash_attention_decode_mla", "kvcache_append_mla", "kvcache_append_mla_varlen"]
 
 
 class _FlashAttnWmma:
@@ -1473,10 +1473,132 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     return (o, lse * _LN2) if return_lse else o
 
 
+def _mla_kv4(kv_cache):
+    """The latent as a cache of ONE head, K and V at once: _cache_desc checks it as it checks every cache (a head stride of one row keeps its rule quiet)"""
+    return (kv_cache if kv_cache.dim() == 3 else kv_cache[:, :, 0]).unsqueeze(2)
+
+
+_MLA_APPEND_NAMES = (("kvcache_append_mla", "[B, Nnew, 512]", "[B, Nnew, 64]", "[B, Nnew, H, 576]"),
+                     ("kvcache_append_mla_varlen", "[total, 512]", "[total, 64]", "[total, H, 576]"))      # [packed]
+
+
+def _mla_rows_ready(t):
+    """New-token rows [.., width] the append can address (last dim contiguous, strides multiples of 8 elements with a positive row stride, 16-byte
+    aligned storage — the two slices of one [.., 576] projection output are): themselves, or a contiguous copy"""
+    st = t.stride()
+    ok = st[-1] == 1 and not any(x & 7 for x in st[:-1]) and st[-2] > 0 and all(x >= 0 for x in st) and not (t.data_ptr() & 15)
+    return t if ok else t.contiguous()
+
+
+def _mla_append_prepare(packed, B, kv_cache, kv_c, k_pe, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, q, lead=None):
+    """Every argument check of a latent-cache append and what its launch needs (_append_prepare's split: nothing is launched here, so that the fused
+    decode call checks everything before it launches anything).  lead: the fused call's q, which then sets the device.
+    -> _mla_append_launch's arguments, the cache description first"""
+    who, c_layout, pe_layout, q_layout = _MLA_APPEND_NAMES[packed]
+    rank = 3 - packed
+    if not all(torch.is_tensor(t) for t in (kv_cache, kv_c, k_pe, cache_seqlens)):
+        raise ValueError("fa2: %s takes tensors kv_cache, kv_c %s, k_pe %s and cache_seqlens" % (who, c_layout, pe_layout))
+    kv_c, k_pe = (t[..., 0, :] if t.dim() == rank + 1 and t.shape[-2] == 1 else t for t in (kv_c, k_pe))        # a head axis of size 1
+    if kv_c.dim() != rank or k_pe.dim() != rank or kv_cache.dim() not in (3, 4) or (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):
+        raise ValueError("fa2: %s takes kv_c %s, k_pe %s and a latent kv_cache [B, Nmax, 576] ([num_pages, page_size, 576] with a block_table); a head "
+                         "axis, where there is one, has size 1" % (who, c_layout, pe_layout))
+    if kv_c.shape[-1] != _MLA_DV or k_pe.shape[-1] != _MLA_D - _MLA_DV or kv_cache.shape[-1] != _MLA_D or kv_c.shape[:-1] != k_pe.shape[:-1]:
+        raise ValueError("fa2: %s writes rows of %d columns: %d of kv_c, then %d of k_pe, one row of each per token; got kv_c %s k_pe %s kv_cache %s"
+                         % (who, _MLA_D, _MLA_DV, _MLA_D - _MLA_DV, tuple(kv_c.shape), tuple(k_pe.shape), tuple(kv_cache.shape)))
+    if kv_c.dtype not in (torch.float16, torch.bfloat16) or k_pe.dtype != kv_c.dtype or kv_cache.dtype != kv_c.dtype:
+        raise ValueError("fa2: %s takes fp16 or bf16 kv_c, k_pe and kv_cache of one dtype (e4m3 latents are not served), got %s %s %s"
+                         % (who, kv_c.dtype, k_pe.dtype, kv_cache.dtype))
+    if not packed and (kv_c.shape[0] < 1 or kv_c.shape[1] < 1):                       # (a packed token buffer may be empty)
+        raise ValueError("fa2: %s needs B, Nnew >= 1, got kv_c %s" % (who, tuple(kv_c.shape)))
+    rotary_dim = _rotary_check(k_pe, _MLA_D - _MLA_DV, rotary_cos, rotary_sin)
+    if rotary_dim not in (0, _MLA_D - _MLA_DV):
+        raise ValueError("fa2: %s rotates the whole 64-wide k_pe: rotary_cos / rotary_sin must be [seqlen_ro, 32], got rotary_dim %d" % (who, rotary_dim))
+    if q is not None:
+        if rotary_dim == 0:
+            raise ValueError("fa2: %s takes q to rotate it: q without rotary_cos / rotary_sin has nothing to do" % who)
+        if not torch.is_tensor(q) or q.dim() != rank + 1 or q.dtype != kv_c.dtype or q.shape[:-2] != kv_c.shape[:-1] or q.shape[-1] != _MLA_D or \
+                not 1 <= q.shape[-2] <= _MLA_MAX_HEADS:
+            raise ValueError("fa2: %s takes q %s in kv_c's dtype with 1 .. %d heads, got %s for kv_c %s"
+                             % (who, q_layout, _MLA_MAX_HEADS, "%s %s" % (q.dtype, tuple(q.shape)) if torch.is_tensor(q) else repr(q), tuple(kv_c.shape)))
+    kv4 = _mla_kv4(kv_cache)
+    cache = _cache_desc(False, kv_c if lead is None else lead, B, kv4, kv4, cache_seqlens, block_table, None, None, aux=(cu_seqlens,) if packed else ())
+    extra = tuple(t for t in (kv_c, k_pe, q, rotary_cos, rotary_sin) if t is not None)
+    device = kv_cache.device
+    if not all(t.is_cuda and t.device == device for t in extra):
+        raise RuntimeError("fa2: kv_c, k_pe, q and the rotary tables must be on the ROCm device of the cache")
+    kv_c, k_pe = _mla_rows_ready(kv_c), _mla_rows_ready(k_pe)
+    q_out = None
+    if q is not None:
+        q = (_packed_ready if packed else _bnhd_ready)(q)
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    if rotary_dim:
+        rotary_cos, rotary_sin = _rotary_tables(rotary_cos, rotary_sin)
+    return cache, packed, B, kv_c, k_pe, cu_seqlens, q, q_out, rotary_dim, rotary_cos, rotary_sin, rotary_interleaved
+
+
+def _mla_append_launch(cache, packed, B, kv_c, k_pe, cu_seqlens, q, q_out, rotary_dim, cos, sin, rotary_interleaved):
+    """The one C call of a latent-cache append _mla_append_prepare has checked -> q_out (the rotated q, or None)"""
+    if packed and kv_c.shape[0] == 0:                # an empty token buffer: nothing to launch
+        return q_out
+    lib = _fa2_lib.load()
+    code = _dtype_code(kv_c)
+    if packed:
+        entry, cu, sizes, nq = lib.fa2_kvcache_append_mla_varlen, (cu_seqlens.data_ptr(),), (B, kv_c.shape[0]), ()
+        rows, st = (lambda t: (ctypes.c_int64 * 1)(t.stride(0))), _s2
+    else:
+        entry, cu, sizes, nq = lib.fa2_kvcache_append_mla, (), (B, kv_c.shape[1]), (kv_c.shape[1] if q is not None else 0,)
+        rows, st = (lambda t: _I64x2(t.stride(0), t.stride(1))), _bnhd
+    q_args = (None, None, 0, *nq, None, None) if q is None else (q.data_ptr(), q_out.data_ptr(), q.shape[-2], *nq, st(q), st(q_out))
+    rotary = (None, None, 0, 0, 0, 0)
+    if rotary_dim:
+        rotary = (cos.data_ptr(), sin.data_ptr(), _fa2_lib.FA2_DTYPE_F32 if cos.dtype == torch.float32 else code, rotary_dim, cos.shape[0], cos.stride(0))
+    dev = _device_index(kv_c)
+    with torch.cuda.device(dev):
+        rc = entry(code, kv_c.data_ptr(), k_pe.data_ptr(), cache.ptrs[0], *cu, *cache.tables, *sizes, _MLA_D, _MLA_DV, *cache.sizes, rows(kv_c), rows(k_pe),
+                   cache.strides[0], cache.bts, *q_args, *rotary, 1 if rotary_interleaved else 0, _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return q_out
+
+
+def kvcache_append_mla(kv_cache, kv_c, k_pe, cache_seqlens, block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, q=None):
+    """Append new tokens to a latent (MLA) KV cache, in place: the write side of flash_attention_decode_mla.
+    kv_c [B, Nnew, 512] (the compressed KV) and k_pe [B, Nnew, 64] (the rotary key), fp16 / bf16, become ONE cache row of 576 columns per token:
+    kv_c bit for bit in columns 0 .. 511, k_pe in columns 512 .. 575.  kv_cache, cache_seqlens and block_table follow flash_attention_decode_mla's
+    rules (contiguous [B, Nmax, 576] or paged [num_pages, page_size, 576]); a head axis of size 1 is accepted on kv_c, k_pe and the cache.
+    cache_seqlens[b] counts the valid keys INCLUDING the new tokens, so new token i is written at key position len_b - Nnew + i, the position the
+    decode call's query row i has.  A token whose position lies outside the cache, or whose page id lies outside the pool, is skipped: nothing is
+    written, nothing is clamped onto a live key, and no content of cache_seqlens / block_table can move a write outside the cache.
+    rotary_cos / rotary_sin [seqlen_ro, 32], float32 or kv_c's dtype (rotary_dim is exactly 64): k_pe of token i — and the trailing 64 columns of
+    row i of q [B, Nnew, H, 576], when q is given — are rotated by table row len_b - Nnew + i (clamped into the table), in f32 with one rounding.
+    rotary_interleaved=True pairs the columns (512 + 2j, 512 + 2j + 1), False pairs (512 + j, 512 + 32 + j).  Without tables k_pe is copied bit for
+    bit (a caller who rotated it already).  Strided views are fine when the last dim is contiguous, the strides are multiples of 8 elements and the
+    storage is 16-byte aligned — the two slices of one [.., 576] projection output go in without a copy; another source is copied, another cache
+    raises.  Returns the rotated q (a new tensor; q is not touched; its columns 0 .. 511 bit for bit) when q and the tables are given, else None.
+    The host reads no device value: the call can be captured in a graph.  Not served: e4m3 latents, cache_batch_idx, cache_leftpad, rotary without
+    an append.  C-ABI fa2_kvcache_append_mla."""
+    B = kv_c.shape[0] if torch.is_tensor(kv_c) and kv_c.dim() >= 1 else 0
+    return _mla_append_launch(*_mla_append_prepare(False, B, kv_cache, kv_c, k_pe, None, cache_seqlens, block_table, rotary_cos, rotary_sin,
+                                                   rotary_interleaved, q))
+
+
+def kvcache_append_mla_varlen(kv_cache, kv_c, k_pe, cu_seqlens, cache_seqlens, block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True,
+                              q=None):
+    """Packed (ragged) append to a latent (MLA) KV cache, in place: kvcache_append_mla for a batch whose sequences bring different numbers of new tokens.
+    kv_c [total, 512], k_pe [total, 64] and q [total, H, 576], packed; cu_seqlens int32 [B + 1] on the device: sequence s owns the rows
+    [cu[s], cu[s + 1]), Nnew_s may be 0; row cu[s] + i is written at key position len_s - Nnew_s + i.  cu[B] < total is legitimate (a token buffer of a
+    fixed, captured size that this step fills partly): rows at or beyond cu[B] belong to no sequence, write nothing, and their q rows come back
+    unrotated, bit for bit.  cu_seqlens is device data nobody validated, like the lengths and the block table: an array that is not ascending loses
+    tokens, it moves no write outside the cache.  Everything else is kvcache_append_mla's.  C-ABI fa2_kvcache_append_mla_varlen."""
+    B = _check_cu("cu_seqlens", cu_seqlens)
+    return _mla_append_launch(*_mla_append_prepare(True, B, kv_cache, kv_c, k_pe, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin,
+                                                   rotary_interleaved, q))
+
+
 _MLA_D, _MLA_DV, _MLA_MAX_HEADS, _MLA_MAX_ROWS, _MLA_MAX_SPLITS = 576, 512, 128, 512, 128      # csrc/fa2_decode_mla.hip.h (the split cap: the plan reports it)
 
 
-def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, head_dim_v=512, scale=None, return_lse=False, num_splits=0):
+def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, head_dim_v=512, scale=None, return_lse=False, num_splits=0, kv_c=None, k_pe=None,
+                               rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
     """Decode attention on a multi-head-latent (MLA) KV cache — the decode step of DeepSeek-V2 / V3 / R1 and Kimi K2 with the up-projections absorbed
     into the query and the output (the flash_mla_with_kvcache shape).
     q [B, Nq, H, 576] fp16 / bf16: the absorbed query, q_nope . W_UK in columns 0 .. 511 and the rotated q_pe in columns 512 .. 575.  A q the kernel
@@ -1495,7 +1617,11 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
     head_dim_v must be 512 and q.shape[-1] 576; H is 1 .. 128 and Nq * H <= 512 (TP8's 16 heads up to all 128, with a few speculative tokens).
     Anything else raises ValueError.  Returns o [B, Nq, H, 512]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention
     composes with it).  num_splits: 0 = the library's plan, 1 .. 128 = that many parts per (sequence, block of 64 rows).  Inference only.
-    Writing new tokens into a latent cache is the caller's: kvcache_append serves head dims up to 512 and rotates the leading columns.
+    kv_c [B, Nq, 512] and k_pe [B, Nq, 64] (both or neither): the query rows' own new tokens, appended first by kvcache_append_mla's rules —
+    cache_seqlens counts them already — with rotary_cos / rotary_sin [seqlen_ro, 32] rotating k_pe and the trailing 64 columns of q by each row's
+    position; the attention then reads the rotated q.  Every check of both halves runs before the first launch, so a call that is refused leaves the
+    cache as it was; the two launches share q's stream.  rotary_* without kv_c / k_pe raises (rotary without an append is not served).  With none of
+    the five the call makes exactly the launches it made before.  Standalone: kvcache_append_mla, kvcache_append_mla_varlen.
     C-ABI fa2_fwd_decode_mla: each cache row is fetched once per workgroup and used as K and as V for up to 64 (token, head) rows; no atomics."""
     who = "flash_attention_decode_mla"
     if not all(torch.is_tensor(t) for t in (q, kv_cache, cache_seqlens)) or q.dim() != 4 or kv_cache.dim() not in (3, 4) or \
@@ -1514,9 +1640,21 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
         raise ValueError("fa2: %s serves 1 .. %d heads and Nq * H <= %d query rows (B, Nq >= 1), got q %s" % (who, _MLA_MAX_HEADS, _MLA_MAX_ROWS, tuple(q.shape)))
     if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _MLA_MAX_SPLITS:
         raise ValueError("fa2: num_splits is 0 (the library chooses) or 1 .. %d, got %r" % (_MLA_MAX_SPLITS, num_splits))
-    # the latent as a cache of ONE head, K and V at once: _cache_desc checks it as it checks every cache (a head stride of one row keeps its rule quiet)
-    kv4 = (kv_cache if kv_cache.dim() == 3 else kv_cache[:, :, 0]).unsqueeze(2)
-    cache = _cache_desc(False, q, B, kv4, kv4, cache_seqlens, block_table, None, None)
+    fused = kv_c is not None or k_pe is not None
+    if not fused and (rotary_cos is not None or rotary_sin is not None):
+        raise ValueError("fa2: rotary_cos / rotary_sin rotate the appended tokens: %s takes them together with kv_c and k_pe (rotary without an append is "
+                         "not served)" % who)
+    if fused:
+        if not all(torch.is_tensor(t) and t.dim() in (3, 4) for t in (kv_c, k_pe)) or tuple(kv_c.shape[:2]) != (B, Nq) or tuple(k_pe.shape[:2]) != (B, Nq):
+            raise ValueError("fa2: %s takes kv_c and k_pe together, [B, Nq, 512] and [B, Nq, 64] = [%d, %d, ..] in q's dtype: the new tokens are the query "
+                             "rows' own (shape[1] == Nq); got %s %s" % (who, B, Nq, tuple(getattr(kv_c, "shape", ())), tuple(getattr(k_pe, "shape", ()))))
+        app = _mla_append_prepare(False, B, kv_cache, kv_c, k_pe, None, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                                  q if rotary_cos is not None else None, lead=q)
+        cache = app[0]
+        q_rot = _mla_append_launch(*app)      # every check lies above: the append launch, then today's call on the rotated q, on one stream
+        q = q if q_rot is None else q_rot
+    else:
+        cache = _cache_desc(False, q, B, _mla_kv4(kv_cache), _mla_kv4(kv_cache), cache_seqlens, block_table, None, None)
     q = _bnhd_ready(q)
     if scale is None:
         scale = _MLA_D ** -0.5

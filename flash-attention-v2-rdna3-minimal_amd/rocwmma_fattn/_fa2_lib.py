@@ -206,6 +206,17 @@ SYMBOLS = {
                                   [ctypes.c_int64] + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [_i64p] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 +
                                   [ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 2 + [_i64p, ctypes.c_void_p]),
     "fa2_kvappend_varlen_token": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int)] * 3),
+    # the append for a latent (MLA) cache: dtype, kv_c k_pe kv_cache cache_seqlens block_table, B Nnew D Dv capacity page_size num_pages, the kv_c / k_pe
+    # stride pairs and the cache's triple, the block-table row stride, q q_out H Nq and their triples, cos sin rotary_dtype rotary_dim seqlen_ro row-stride
+    # interleaved, stream
+    "fa2_kvcache_append_mla": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 + [_i64p] * 3 + [ctypes.c_int64] +
+                               [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [_i64p] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 +
+                               [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # ... packed: cu_seqlens before cache_seqlens, B total(int64) D Dv ..., one row stride each for kv_c / k_pe, {head, row} pairs for q / q_out, no Nq
+    "fa2_kvcache_append_mla_varlen": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 + [_i64p] * 3 +
+                                      [ctypes.c_int64] + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [_i64p] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 +
+                                      [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "fa2_kvappend_mla_chunks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_rotary_eval": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)] + [ctypes.c_int] * 3 +
                         [ctypes.c_void_p]),
     "fa2_scoremod_eval": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 2),
@@ -495,6 +506,13 @@ def prefill_tile(length, capacity, page_size, tile):
     slot, row, rows = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     check(load().fa2_prefill_tile(int(length), int(capacity), int(page_size), int(tile), ctypes.byref(slot), ctypes.byref(row), ctypes.byref(rows)))
     return slot.value, row.value, rows.value
+
+
+def kvappend_mla_chunks(unit, halves):
+    """fa2_kvappend_mla_chunks -> (chunk a, chunk b): the two 16-byte chunks unit `unit` (0 .. 35) of a 576-wide row moves in the latent-cache append."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_kvappend_mla_chunks(int(unit), int(bool(halves)), ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
 
 
 def strides3(a, b, c):

@@ -754,8 +754,8 @@ int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int
  * up to 64 packed rows, part); each 32-key tile of the cache is loaded once per workgroup into LDS and serves both products; each wave owns 16 rows.
  * A split call leaves normalised f32 rows and log2 LSEs of the live rows in the workspace (an empty part: lse = -inf alone) and the combine kernel of
  * fa2_fwd_decode, at head dim 512, merges them.  No atomics.
- * Not here: an append for the 576-wide cache (fa2_kvcache_append stops at head dim 512 and rotates the LEADING columns), e4m3 latents, a window,
- * soft-capping, slopes, a backward. */
+ * Writing new tokens into the 576-wide cache is fa2_kvcache_append_mla (its own section, below; fa2_kvcache_append stops at head dim 512 and rotates
+ * the LEADING columns).  Not here: e4m3 latents, a window, soft-capping, slopes, a backward. */
 enum { FA2_KERNEL_HIP_DECODE_MLA = 9 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
 typedef struct fa2_decode_mla_plan_t {
     int kernel;        /* FA2_KERNEL_HIP_DECODE_MLA */
@@ -873,6 +873,50 @@ int fa2_kvappend_varlen_token(const int* cu_seqlens, int B, int64_t t, int* seq,
  * columns at or beyond rotary_dim are copied bit for bit.  FA2_ERR_NULL_POINTER, FA2_ERR_BAD_SHAPE (D < 1), FA2_ERR_HEAD_DIM (D, rotary_dim),
  * FA2_ERR_DTYPE, in this order. */
 int fa2_rotary_eval(int dtype, const void* x, const float* cos_row, const float* sin_row, int D, int rotary_dim, int interleaved, void* y);
+
+/* ---- Append for a latent (MLA) KV cache: the write side of fa2_fwd_decode_mla.  One launch writes the rows of Nnew new tokens per sequence into the
+ * 576-wide cache at the key position only the device knows, rotating the TRAILING 64 columns by that position, and optionally writes the rotated q.
+ * Everything not said here is fa2_kvcache_append's contract, word for word: the lengths AFTER the append, p = len - Nnew + i, tokens with p outside
+ * [0, capacity_keys) or a page id outside [0, num_pages) SKIPPED and never clamped onto a live row, device data nobody validated moving no write
+ * outside kv_cache and q_out and no read outside kv_c, k_pe, q and the tables, 64-bit addressing, no host read of a device value (graph replay).
+ * Layout (last dim contiguous)
+ *   kv_c          : B x Nnew x 512, the compressed KV; k_pe : B x Nnew x 64, the rotary key; element strides {batch, row} each.  The two may be
+ *                   slices of one projection output.
+ *   kv_cache, cache_seqlens, block_table, capacity, page_size, num_pages, kv_strides, block_table_stride : as in fa2_fwd_decode_mla (D = 576, Dv = 512).
+ *   q, q_out      : optional, both or neither: B x H x Nq x 576 with Nq == Nnew and H 1 .. 128, strides {batch, head, row}.  Needs the tables.
+ *   rotary_cos, rotary_sin : optional, both or neither: [seqlen_ro, 32], f32 or the I/O dtype; rotary_dim is exactly 64.
+ * The cache row at p receives kv_c[b, i, :] bit for bit in columns 0 .. 511 and k_pe[b, i, :] in columns 512 .. 575: rotated by table row
+ * clamp(p, 0, seqlen_ro - 1) with tables (csrc/fa2_rotary.h's arithmetic in f32, one RNE rounding; fa2_rotary_eval on the 64-wide sub-row is its host
+ * side), copied bit for bit without (a caller who rotated it already).  rotary_interleaved != 0 pairs the columns (512 + 2j, 512 + 2j + 1), 0 pairs
+ * (512 + j, 512 + 32 + j).  q_out row i of every head: columns 0 .. 511 of q bit for bit, columns 512 .. 575 rotated by the table row of token i,
+ * whether or not that token's latent row was written.  q itself is not touched.
+ * Checked in fa2_kvcache_append's order: null pointers, sizes (FA2_ERR_BAD_SHAPE: B, Nnew, D, Dv < 1, page_size, H outside 1 .. 128, Nq != Nnew, q
+ * without tables, seqlen_ro < 1, a negative table stride), head dim (FA2_ERR_HEAD_DIM: D != 576, Dv != 512, rotary_dim != 64), alignment, dtype,
+ * FA2_ERR_GRID (B * Nnew above 2^31 - 1).  There is no cache_format and there are no descales: e4m3 latents are not served.
+ * Kernel (csrc/fa2_kvappend_mla.hip.h): fa2_kvcache_append's decomposition with R = 1 + H rows of 36 units; a unit is two 16-byte chunks of a row's
+ * 72 — fa2_kvappend_mla_chunks is the host side of that one map: (2u, 2u + 1), or with halves != 0 (a rotated GPT-NeoX tail) (64 + c, 68 + c) for
+ * unit 32 + c.  FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for a unit outside [0, 36). */
+int fa2_kvcache_append_mla(int dtype, const void* kv_c, const void* k_pe, void* kv_cache,
+                           const int* cache_seqlens, const int* block_table,
+                           int B, int Nnew, int D, int Dv, int capacity, int page_size, int num_pages,
+                           const int64_t kv_c_strides[2], const int64_t k_pe_strides[2],
+                           const int64_t kv_strides[3], int64_t block_table_stride,
+                           const void* q, void* q_out, int H, int Nq, const int64_t q_strides[3], const int64_t q_out_strides[3],
+                           const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
+                           int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream);
+/* ... its packed (ragged) form, as fa2_kvcache_append_varlen is fa2_kvcache_append's: kv_c total x 512 and k_pe total x 64 with one row stride each
+ * (kv_c_strides[1], k_pe_strides[1]), q and q_out total x H x 576 with {head, row}; cu_seqlens int32 [B + 1] on the device, cu[B] < total legitimate.
+ * A token no sequence owns writes no latent row and its q row is copied to q_out bit for bit.  total == 0 passes the checks and returns FA2_OK
+ * without a launch; FA2_ERR_GRID for total above 2^31 - 1. */
+int fa2_kvcache_append_mla_varlen(int dtype, const void* kv_c, const void* k_pe, void* kv_cache,
+                                  const int* cu_seqlens, const int* cache_seqlens, const int* block_table,
+                                  int B, int64_t total, int D, int Dv, int capacity, int page_size, int num_pages,
+                                  const int64_t kv_c_strides[1], const int64_t k_pe_strides[1],
+                                  const int64_t kv_strides[3], int64_t block_table_stride,
+                                  const void* q, void* q_out, int H, const int64_t q_strides[2], const int64_t q_out_strides[2],
+                                  const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
+                                  int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream);
+int fa2_kvappend_mla_chunks(int unit, int halves, int* chunk_a, int* chunk_b);
 
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D

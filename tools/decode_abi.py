@@ -1,5 +1,6 @@
 """The C argument order of the serving entries, for the tests and the tools alike: fa2_fwd_decode, fa2_fwd_decode_fp8, fa2_fwd_decode_window,
-fa2_fwd_decode_mla, fa2_kvcache_append, fa2_kvcache_append_varlen, fa2_fwd_prefill and fa2_fwd_prefill_fp8 by keyword (ENTRIES, c_args: the only copy under tests/ and
+fa2_fwd_decode_mla, fa2_kvcache_append, fa2_kvcache_append_varlen, fa2_kvcache_append_mla, fa2_kvcache_append_mla_varlen, fa2_fwd_prefill and
+fa2_fwd_prefill_fp8 by keyword (ENTRIES, c_args: the only copy under tests/ and
 tools/), what the tensors of a decode call say (tensor_kw) and the GPU call on NaN-filled outputs and workspace (decode_c).  tests/decode_calls.py hands
 these on to the tests beside what only tests need; the tools import them here, so that a tool runs with nothing but itself, this file and the package."""
 import ctypes
@@ -53,6 +54,11 @@ ENTRIES = {      # entry -> (symbol, its arguments by keyword, its workspace que
     # decode on a latent (MLA) cache: k is the one latent tensor, D / Dv the 576 / 512 columns; no Hkv, no v, no vs
     "mla": ("fa2_fwd_decode_mla", ("dtype", "q", "k", "o", "lse", "lens", "bt", "B", "H", "Nq", "D", "Dv", "cap", "page", "pages", "qs", "ks", "os", "ls", "bts",
                                    "scale") + _TAIL, "fa2_fwd_decode_mla_workspace_bytes"),
+    # ... and its append: kn / vn are kv_c / k_pe (kns / vns: their {batch, row} pairs; packed: one row stride each), k the one latent tensor
+    "append_mla": ("fa2_kvcache_append_mla", ("dtype", "kn", "vn", "k", "lens", "bt", "B", "N", "D", "Dv", "cap", "page", "pages", "kns", "vns", "ks", "bts", "q", "qo",
+                                              "H", "Nq", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter", "stream"), None),
+    "append_mla_varlen": ("fa2_kvcache_append_mla_varlen", ("dtype", "kn", "vn", "k", "cu", "lens", "bt", "B", "total", "D", "Dv", "cap", "page", "pages", "kns", "vns",
+                                                            "ks", "bts", "q", "qo", "H", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter", "stream"), None),
     "prefill": ("fa2_fwd_prefill", ("dtype", "fmt") + _PREFILL_HEAD + _SCOREMOD + ("stream",), None),
     "prefill_fp8": ("fa2_fwd_prefill_fp8", ("dtype",) + _PREFILL_HEAD + _DESCALES + _SCOREMOD + ("stream",), None),
 }
