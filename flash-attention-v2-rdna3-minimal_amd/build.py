@@ -50,6 +50,8 @@ UNITS = [
     ("window_hip_bf16", "window_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("varlen_hip_f16", "varlen_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("varlen_hip_bf16", "varlen_hip.cpp", ["-DFA2_TU_BF16=1"]),
+    ("varlen_dv_hip_f16", "varlen_dv_hip.cpp", ["-DFA2_TU_BF16=0"]),                      # packed forward with V narrower than K (MLA prefill, 192 / 128)
+    ("varlen_dv_hip_bf16", "varlen_dv_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("dropout_hip_f16", "dropout_hip.cpp", ["-DFA2_TU_BF16=0"]),
     ("dropout_hip_bf16", "dropout_hip.cpp", ["-DFA2_TU_BF16=1"]),
     ("varlen_dropout_hip_f16", "varlen_dropout_hip.cpp", ["-DFA2_TU_BF16=0"]),

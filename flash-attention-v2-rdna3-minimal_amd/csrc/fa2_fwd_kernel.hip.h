@@ -116,6 +116,23 @@
 #else
 #define FA2_KV8_PARAM
 #endif
+// FA2_DV = 1 (varlen_dv_hip.cpp only, on top of FA2_VARLEN = 1, forward only): V and O are narrower than Q and K (fa2_fwd_varlen_dv: the non-absorbed MLA
+// prefill, head dims 192 / 128).  The V / O side — V's descriptor, the staging guards, the count of O column blocks, the O stores — takes the value head dim
+// Dv, which travels in a further kernel argument (the parameter block keeps its layout); Q, K and the Q.K^T k-steps keep p.D.  FA2_VD names that width:
+// everywhere else it is the `p.D` it always was.  The unit instantiates <HD 256, HDV 128, RTD> and launches ONE column slab (vcol0 = 0).
+#ifndef FA2_DV
+#define FA2_DV 0
+#endif
+#if FA2_DV && (!FA2_VARLEN || FA2_PAGED || FA2_DROP || FA2_SMOD)
+#error "FA2_DV builds on the plain FA2_VARLEN blocks"
+#endif
+#if FA2_DV
+#define FA2_DV_PARAM , const int dv
+#define FA2_VD dv
+#else
+#define FA2_DV_PARAM
+#define FA2_VD p.D
+#endif
 
 // ---- tuning knobs (A/B-tested on MI355X with tools/kbench.py; numbers at B2 H16 N4096 D128 fp16) ----
 #ifndef FA2_DEFER_THR        // skip the O rescale while the row max grew by <= this (log2 units); <0: always rescale.
@@ -507,7 +524,7 @@ constexpr int fwd_min_waves_per_simd() { return (NW == 4 && !BIAS && QB == 1 && 
 // computes only the tiles of its own 32 rows' range [tf_w, ntiles_w), tiles cut by the band's left or right edge are masked per lane (lim_lo, lim_hi)
 // and the tiles in between run the unmasked steady-state loop.  A row that sees no key ends with O = 0, lse = -inf (the BIAS kernels' convention).
 template <int HD, int HDV, bool BF16, bool CAUSAL, int NW, int QB, int BIAS = 0, int KSQ = HD / 16, int DTN = HDV / 32, bool RTD = false>
-__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP FA2_PAGED_PARAM FA2_KV8_PARAM FA2_SMOD_PARAM) {
+__global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>())) void fwd_kernel(const FwdParams FA2_KP FA2_PAGED_PARAM FA2_KV8_PARAM FA2_SMOD_PARAM FA2_DV_PARAM) {
 #if FA2_VARLEN
     FwdParams p = pk;         // (adjusted to the workgroup's sequence below: varlen_enter)
 #endif
@@ -520,7 +537,7 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     static_assert(KSQ <= G_::KS_QK && DTN <= GV_::DT, "trimmed loop bounds");
     constexpr int VBASE = 2 * TILEB;   // LDS: K buf0 | K buf1 | V buf0 | V buf1
     const int vcol0 = blockIdx.y * HDV;   // first V / O column of this workgroup
-    const int ndt = RTD ? (p.D - vcol0 + 31) / 32 : DT;   // O column blocks of this half that hold real columns (uniform)
+    const int ndt = RTD ? (FA2_VD - vcol0 + 31) / 32 : DT;   // O column blocks of this half that hold real columns (uniform)
     constexpr int kThreads = NW * 64, kRowsPerWave = 32 * QB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -566,6 +583,9 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
 #endif
 #elif FA2_VARLEN
     if (varlen_enter(p, win, b, q0)) return;      // b is the sequence (the batch strides are 0); from here on p describes that sequence alone
+#if FA2_DV
+    p.v_bytes = varlen_bytes(p.Nkv, p.vs[2], dv);   // (V's last row ends after Dv columns: what lies beyond them in the caller's buffer is never addressable)
+#endif
 #endif
     // this workgroup's KV range [kv_first, kv_first + nkv): everything, or a part's whole tiles
     int kv_first = 0, nkv = p.Nkv;
@@ -629,7 +649,7 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
     for (int i = 0; i < VNPASS; ++i) {
         const int idx = tid + kThreads * i;
         const int row = idx / GV_::G, gi = idx % GV_::G;
-        vg_off[i] = gi * 8 + vcol0 < p.D ? row * v_rowb + gi * kKvGranB + vcol0 * kKvEs : kOobOffset;
+        vg_off[i] = gi * 8 + vcol0 < FA2_VD ? row * v_rowb + gi * kKvGranB + vcol0 * kKvEs : kOobOffset;
         vw_off[i] = GV_::v_off(row, gi * 16);
     }
 
@@ -1006,7 +1026,7 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         const int idx = tid + kThreads * i;
         const int row = idx / GV_::G, slot = idx % GV_::G;
         const int gv = ((((slot >> 2) ^ ((row / GV_::RPB) & GV_::VMASK))) << 2) | (slot & 3);
-        vd_off[i] = gv * 8 + vcol0 < p.D ? row * v_rowb + gv * 16 + vcol0 * 2 : kOobOffset;
+        vd_off[i] = gv * 8 + vcol0 < FA2_VD ? row * v_rowb + gv * 16 + vcol0 * 2 : kOobOffset;
     }
 #if FA2_KV8
     u32x2 kreg[NPASS], vreg[VNPASS];
@@ -1448,7 +1468,7 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
         for (int i = 0; i < 32 / RPI; ++i) {
             const int r = i * RPI + rl;
             const u32x4 w = *(const u32x4*)(img + r * EROW + cl * 16);
-            if (qw0 + r < p.Nq && vcol0 + cl * 8 < p.D) *(u32x4*)(obase + (int64_t)(qw0 + r) * p.os[2] + cl * 8) = w;
+            if (qw0 + r < p.Nq && vcol0 + cl * 8 < FA2_VD) *(u32x4*)(obase + (int64_t)(qw0 + r) * p.os[2] + cl * 8) = w;
         }
         return;
     }
@@ -1481,7 +1501,7 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves_per_simd<HD, NW, QB, BIAS>(
                     auto x0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
                     auto x1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
                     const u32x4 w = {x0[0], x1[0], x0[1], x1[1]};
-                    if (vcol0 + 32 * dt + 8 * (r4 + hi) < p.D) *(u32x4*)(op + 32 * dt + 8 * (r4 + hi)) = w;
+                    if (vcol0 + 32 * dt + 8 * (r4 + hi) < FA2_VD) *(u32x4*)(op + 32 * dt + 8 * (r4 + hi)) = w;
                 }
             }
             if (hi == 0 && vcol0 == 0)

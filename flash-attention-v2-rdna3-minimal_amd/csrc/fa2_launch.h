@@ -217,6 +217,9 @@ FA2_BWD_FAMILY_LAUNCHER(launch_bwd_window)
 // of sequences, batch strides 0, cu_seqlens_q / cu_seqlens_k in p.bias / p.ws (set_varlen / get_varlen), the window's offset field = the bottom-right flag
 FA2_FWD_FAMILY_LAUNCHER(launch_fwd_varlen)
 FA2_BWD_FAMILY_LAUNCHER(launch_bwd_varlen)
+// ... with V / O narrower than Q / K (varlen_dv_hip.cpp; fa2_fwd_varlen_dv): the DV form of the packed forward, forward only.  p as for launch_fwd_varlen,
+// p.D in 136 .. 256 and Dv in 8 .. 128 (multiples of 8; the value head dim is a further kernel argument); always the kernel of head dim 256, one column slab
+FA2_LAUNCHER(launch_fwd_varlen_dv, (const FwdParams& p, int Dv, int rows, hipStream_t stream), (p, Dv, rows, stream))
 // attention dropout (dropout_hip.cpp, varlen_dropout_hip.cpp): the same launchers over the DROP forms of the windowed and packed kernels; the seed and
 // the threshold travel in p.full_items / p.split_items / p.bias_kind (set_dropout, fa2_dropout.h)
 FA2_FWD_FAMILY_LAUNCHER(launch_fwd_dropout)

@@ -470,6 +470,7 @@ struct FwdCall : Call {
     float* lse = nullptr;
     const int64_t *qs = nullptr, *ks = nullptr, *vs = nullptr, *os = nullptr, *ls = nullptr;      // {batch, head, row}; ls: {batch, head}
     fa2_fwd_plan_t* plan = nullptr;          // Ask::Plan
+    int Dv = 0;                              // fa2_fwd_varlen_dv: the head dim of v and o, narrower than D (packed calls only); 0 = as D
 };
 struct BwdCall : Call {
     const void *q = nullptr, *k = nullptr, *v = nullptr, *o = nullptr, *dout = nullptr;
@@ -556,6 +557,18 @@ void set_family(P& p, const Call& c) {
     if (c.dropout) fa2::set_dropout(p, c.seed, c.drop_t);
 }
 
+// fa2_fwd_varlen_dv serves D in 136 .. 256 with Dv in 8 .. 128, multiples of 8: one column slab of the kernel of head dim 256 (varlen_dv_hip.cpp)
+bool dv_pair_ok(int D, int Dv) { return D % 8 == 0 && D >= 136 && D <= 256 && Dv % 8 == 0 && Dv >= 8 && Dv <= 128; }
+// ... in 256-row workgroups, one per CU (96 KiB of LDS), unless that grid covers at most half of the CUs: 128-row workgroups then double the busy CUs.
+// Measured (tools/mla_prefill_bench.py, profiles/r51_mla_prefill_bench.txt, bf16 192 / 128): 128 workgroups of 256 rows (H16, 2 048 new tokens on 8 192
+// context keys, both passes and the merge) 349.7 -> 291.6 us; everywhere above, 128-row workgroups are 1.34 .. 1.61x SLOWER (B4 H16 x 4 096: 453 -> 606 us),
+// so the family's 3/8 rule (pick_rows) gives way to this one.  Option "rows" overrides it.
+int dv_rows(const fa2::FwdParams& p) {
+    const int f = forced_rows();
+    if (f == 128 || f == 256) return f;
+    return (int64_t)p.nbh * ((p.Nq + 255) / 256) <= fa2::device_cus() / 2 ? 128 : 256;
+}
+
 int fwd_validate(const FwdCall& c, fa2::FwdParams& p, int& HD) {
     // Until round 5 any non-zero value of the flag word meant "causal"; a caller that still passes another truthy int would silently get a non-causal
     // forward: refuse it
@@ -563,9 +576,13 @@ int fwd_validate(const FwdCall& c, fa2::FwdParams& p, int& HD) {
     const bool tensors = c.ask == Ask::Launch && !c.packed;
     if (tensors && tensors_null(c)) return FA2_ERR_NULL_POINTER;
     if (int rc = check_bias(c)) return rc;
-    if (int rc = check_shape(c, &HD)) return rc;
+    int shape_rc = check_shape(c, &HD);
+    // (fa2_fwd_varlen_dv: the served (D, Dv) pairs are a head-dim matter, so they are looked at where the head dim is: ahead of the scale)
+    if (c.Dv && (shape_rc == FA2_OK || shape_rc == FA2_ERR_SCALE) && !dv_pair_ok(c.D, c.Dv)) shape_rc = FA2_ERR_HEAD_DIM;
+    if (shape_rc) return shape_rc;
+    const int Dv = c.Dv ? c.Dv : c.D;        // columns of V
     if ((tensors && !tensors_aligned(c)) || !strides_ok(c.qs) || !strides_ok(c.ks) || !strides_ok(c.vs) || !strides_ok(c.os)) return FA2_ERR_ALIGNMENT;
-    if (!span_ok(c.Nkv, c.ks, c.D) || !span_ok(c.Nkv, c.vs, c.D)) return FA2_ERR_BAD_SHAPE;
+    if (!span_ok(c.Nkv, c.ks, c.D) || !span_ok(c.Nkv, c.vs, Dv)) return FA2_ERR_BAD_SHAPE;
 
     const int B = c.B, H = c.H, Nq = c.Nq, Nkv = c.Nkv, bias_kind = c.bias.kind;
     p.q = c.q; p.k = c.k; p.v = c.v; p.o = c.o; p.lse = c.lse;
@@ -588,7 +605,7 @@ int fwd_validate(const FwdCall& c, fa2::FwdParams& p, int& HD) {
     p.full_items = p.split_items = p.nsplit = p.blk0 = p.item_cap = 0;
     p.ws = nullptr;
     p.k_bytes = (uint32_t)span_bytes(Nkv, c.ks, c.D);
-    p.v_bytes = (uint32_t)span_bytes(Nkv, c.vs, c.D);
+    p.v_bytes = (uint32_t)span_bytes(Nkv, c.vs, Dv);
     p.kv_group = H / c.Hkv;
     p.bias = c.bias.ptr;
     p.bias_kind = bias_kind;
@@ -637,7 +654,7 @@ void fwd_report(const FwdCall& c, const fa2::FwdParams& p, int HD, int family_ro
     std::memset(out, 0, sizeof(*out));
     out->heads_main = c.B * c.H;
     if (c.windowed) {
-        out->kernel = c.packed ? FA2_KERNEL_HIP_VARLEN : FA2_KERNEL_HIP_WINDOW;
+        out->kernel = c.Dv ? FA2_KERNEL_HIP_VARLEN_DV : c.packed ? FA2_KERNEL_HIP_VARLEN : FA2_KERNEL_HIP_WINDOW;
         out->rows = family_rows;
     } else if (c.bias.kind != FA2_BIAS_NONE) {
         out->kernel = FA2_KERNEL_HIP_BIAS;
@@ -659,12 +676,13 @@ int fwd_run(const FwdCall& c) {
     if (int rc = fwd_validate(c, p, HD)) return rc;
     const bool bf16 = c.dtype == FA2_DTYPE_BF16, causal = (c.flags & FA2_FLAG_CAUSAL) != 0;
     // rows per workgroup of the windowed / packed kernels (packed: the grid of the stated maximum lengths)
-    const int family_rows = !c.windowed ? 0 : HD > 256 ? 128 : pick_rows(p);
+    const int family_rows = !c.windowed ? 0 : c.Dv ? dv_rows(p) : HD > 256 ? 128 : pick_rows(p);
     if (c.ask == Ask::Size) { *c.ws_need = fwd_workspace_need(p, HD, bf16, causal); return FA2_OK; }
     if (c.ask == Ask::Plan) { fwd_report(c, p, HD, family_rows, c.plan); return FA2_OK; }
     if (c.packed)
         if (int rc = check_packed_tensors(c)) return rc;
     hipStream_t stream = (hipStream_t)c.stream;
+    if (c.Dv) return fa2::launch_fwd_varlen_dv(bf16, p, c.Dv, family_rows, stream);      // (a packed call without dropout or score modifiers: its entry point sets nothing else)
     if (c.scoremod) return kFwdSmod[c.packed](bf16, HD, p, family_rows, stream, scoremod_of(c));
     if (c.windowed) return kFwdFamily[c.packed][c.dropout](bf16, HD, p, family_rows, stream);
     if (c.bias.kind != FA2_BIAS_NONE) return fa2::launch_fwd_hip(bf16, HD, p, causal, 128, true, stream);
@@ -1172,6 +1190,38 @@ int fa2_fwd_varlen_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int 
     FA2_PACKED_FILL(c, Hkv);
     if (int rc = packed_call(c, ps, {qs, ks, ks, qs}, 0, flags, window_left, window_right)) return rc;
     c.qs = ps.s[0]; c.ks = ps.s[1]; c.vs = ps.s[2]; c.os = ps.s[3]; c.ls = ps.ls;
+    c.ask = Ask::Plan; c.plan = plan;
+    return fwd_run(c);
+}
+
+// ... with V and O of head dim Dv < D (the non-absorbed MLA prefill, 192 / 128; varlen_dv_hip.cpp).  Dv < 1 is a bad size like the others; the pair is
+// checked with the head dim (fwd_validate); V's span rule and descriptor use Dv.
+int fa2_fwd_varlen_dv(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Hkv,
+                      int max_seqlen_q, int max_seqlen_k, int D, int Dv, const int* cu_seqlens_q, const int* cu_seqlens_k,
+                      const int64_t q_strides[2], const int64_t k_strides[2], const int64_t v_strides[2], const int64_t o_strides[2],
+                      int64_t lse_stride, float scale, int flags, int window_left, int window_right, void* hip_stream) {
+    FwdCall c;
+    PackedStrides ps;
+    FA2_PACKED_FILL(c, Hkv);
+    if (Dv < 1) return FA2_ERR_BAD_SHAPE;
+    if (int rc = packed_call(c, ps, {q_strides, k_strides, v_strides, o_strides}, lse_stride, flags, window_left, window_right)) return rc;
+    FA2_PACKED_FWD_FILL(c, ps);
+    c.Dv = Dv;
+    return fwd_run(c);
+}
+
+int fa2_fwd_varlen_dv_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D, int Dv, const int64_t q_strides[2],
+                           const int64_t k_strides[2], float scale, int flags, int window_left, int window_right, fa2_fwd_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    const int64_t cq[2] = {D, (int64_t)H * D}, ck[2] = {D, (int64_t)Hkv * D};          // a contiguous [total, heads, D]; V and O take K's and Q's
+    const int64_t *qs = q_strides ? q_strides : cq, *ks = k_strides ? k_strides : ck;
+    FwdCall c;
+    PackedStrides ps;
+    FA2_PACKED_FILL(c, Hkv);
+    if (Dv < 1) return FA2_ERR_BAD_SHAPE;
+    if (int rc = packed_call(c, ps, {qs, ks, ks, qs}, 0, flags, window_left, window_right)) return rc;
+    c.qs = ps.s[0]; c.ks = ps.s[1]; c.vs = ps.s[2]; c.os = ps.s[3]; c.ls = ps.ls;
+    c.Dv = Dv;
     c.ask = Ask::Plan; c.plan = plan;
     return fwd_run(c);
 }

@@ -118,6 +118,33 @@ class _FlashAttnWmma:
         return [O[..., :d] if d_pad else O, q, k, v, O, L]
 
     @staticmethod
+    def forward_varlen_dv(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, flags, scale, window):
+        """forward_varlen with v [total_k, Hkv, Dv] narrower than k (C-ABI fa2_fwd_varlen_dv; forward only).  v keeps its strides — a column slice of a
+        wider buffer is addressed in place.  Returns (O [total_q, H, Dv], L f32 [H, total_q] in log2 units)."""
+        lib = _fa2_lib.load()
+        h, h_kv, d = _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, dv=True)
+        if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+            raise RuntimeError("fa2: q, k, v of a call with v narrower than k must share one dtype, float16 or bfloat16")
+        dtype_code = _fa2_lib.FA2_DTYPE_F16 if q.dtype == torch.float16 else _fa2_lib.FA2_DTYPE_BF16
+        q, k, v = (_packed_ready(t) for t in (q, k, v))
+        total_q, d_v = q.shape[0], v.shape[2]
+        O = torch.empty((total_q, h, d_v), dtype=q.dtype, device=q.device)
+        L = torch.empty((h, total_q), dtype=torch.float32, device=q.device)
+        if total_q and k.shape[0] == 0:            # no keys at all: every row is dead (and the library wants non-null pointers)
+            O.zero_()
+            L.fill_(float("-inf"))
+        elif total_q:
+            dev = q.device.index
+            with torch.cuda.device(dev):
+                rc = lib.fa2_fwd_varlen_dv(dtype_code, q.data_ptr(), k.data_ptr(), v.data_ptr(), O.data_ptr(), L.data_ptr(), cu_seqlens_q.numel() - 1, h,
+                                           h_kv, max(int(max_seqlen_q), 1), max(int(max_seqlen_k), 1), d, d_v, cu_seqlens_q.data_ptr(),
+                                           cu_seqlens_k.data_ptr(), _s2(q), _s2(k), _s2(v), _s2(O), L.stride(0), float(scale), int(flags), int(window[0]),
+                                           int(window[1]), _raw_stream(dev))
+            if rc:
+                _fa2_lib.check(rc)
+        return O, L
+
+    @staticmethod
     def backward_varlen(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, act_d, flags, scale, window, dropout=None, scoremod=None,
                         dlse=None):
         """backward() of forward_varlen (C-ABI fa2_bwd_varlen; grouped K / V: expanded, dK / dV summed per group in f32).  Returns [dQ, dK, dV].
@@ -512,8 +539,9 @@ def _packed_ready(t):
     return t if s2 == 1 and not ((s0 | s1) & 7) and not (t.data_ptr() & 15) else t.contiguous()
 
 
-def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k):
-    """The argument checks of the packed calls, before any device work -> (H, Hkv, D)."""
+def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, dv=False):
+    """The argument checks of the packed calls, before any device work -> (H, Hkv, D).  dv: v may be narrower than k (flash_attention_varlen's
+    Dv route, which has checked the pair of widths already); everywhere else v has k's shape."""
     if not all(torch.is_tensor(t) for t in (q, k, v)) or q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
         raise ValueError("fa2: q, k, v of a packed (varlen) call must be 3-D: [total_q, H, D] and [total_k, Hkv, D]")
     if not torch.is_tensor(cu_seqlens_q) or not torch.is_tensor(cu_seqlens_k) or cu_seqlens_q.dim() != 1 or cu_seqlens_k.dim() != 1:
@@ -524,7 +552,7 @@ def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k):
         raise ValueError("fa2: cu_seqlens_q / cu_seqlens_k must be int32, got %s and %s" % (cu_seqlens_q.dtype, cu_seqlens_k.dtype))
     if cu_seqlens_q.device != q.device or cu_seqlens_k.device != q.device:
         raise ValueError("fa2: cu_seqlens_q / cu_seqlens_k must be on the device of q")
-    if k.shape[2] != q.shape[2] or v.shape != k.shape:
+    if k.shape[2] != q.shape[2] or (v.shape[:2] != k.shape[:2] if dv else v.shape != k.shape):
         raise RuntimeError("fa2: inconsistent q/k/v shapes %s %s %s" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
     _check_groups(q.shape[1], k.shape[1])
     if q.shape[2] > _MAX_HEAD_DIM:
@@ -1909,7 +1937,14 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     softcap / alibi_slopes: as flash_attention's; the slopes are [H] or [num_sequences, H], the positions count inside the sequence (row i at i, or at
     i + Nkv_s - Nq_s with bottom_right=True).  Not together with dropout_p > 0 (ValueError).
     return_lse=True returns (out, lse), lse f32 [H, total_q] in natural-log units, -inf for rows that see no key, differentiable like out (see
-    flash_attention); merge_attention combines such pairs.  False takes exactly the path taken without the argument."""
+    flash_attention); merge_attention combines such pairs.  False takes exactly the path taken without the argument.
+    v narrower than k — v [total_k, Hkv, Dv] with Dv != D, the non-absorbed prefill of multi-head-latent attention (D 192, Dv 128) — returns
+    [total_q, H, Dv] (C-ABI fa2_fwd_varlen_dv).  Served: D a multiple of 8 in 136 .. 256 with Dv a multiple of 8 in 8 .. 128; forward only (no input may
+    require grad under grad mode), no dropout, softcap or alibi_slopes: ValueError otherwise.  scale=None stays D ** -0.5.  v is read in place whatever
+    its row pitch (a column slice of the up-projection's output); return_lse and merge_attention work as above."""
+    if _varlen_dv(k, v):
+        return _flash_attention_varlen_dv(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window, bottom_right, dropout_p,
+                                          softcap, alibi_slopes, return_lse)
     dropout = None if dropout_p.__class__ is float and dropout_p == 0.0 else _parse_dropout(dropout_p, dropout_seed)      # (the default: no work)
     left, right, _ = _fa2_lib.parse_window(window, 0)
     smod = None
@@ -1948,6 +1983,35 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=Non
     if dropout is not None:
         return flash_attn_wmma.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right), dropout)[0]
     return flash_attn_wmma.forward_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right))[0]
+
+
+def _varlen_dv(k, v):
+    """Is this packed call one with v narrower (or wider) than k — same tokens, same heads, another head dim?  Anything else is _check_varlen's to judge."""
+    return torch.is_tensor(k) and torch.is_tensor(v) and k.dim() == 3 and v.dim() == 3 and v.shape[2] != k.shape[2] and v.shape[:2] == k.shape[:2]
+
+
+def _flash_attention_varlen_dv(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window, bottom_right, dropout_p, softcap,
+                               alibi_slopes, return_lse):
+    """flash_attention_varlen with v narrower than k: the refusals (before any device work), then fa2_fwd_varlen_dv."""
+    D, Dv = k.shape[2], v.shape[2]
+    if D % 8 or not 136 <= D <= 256 or Dv % 8 or not 8 <= Dv <= 128:
+        raise ValueError("fa2: flash_attention_varlen serves v narrower than k for head dims D in 136 .. 256 and Dv in 8 .. 128, multiples of 8 "
+                         "(192 / 128: the MLA prefill); got D = %d, Dv = %d" % (D, Dv))
+    if not (dropout_p == 0 and softcap == 0 and alibi_slopes is None):
+        raise ValueError("fa2: flash_attention_varlen with v narrower than k takes no dropout_p > 0, softcap or alibi_slopes")
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v)):
+        raise ValueError("fa2: flash_attention_varlen with v narrower than k is forward only (an input requires grad): call it under torch.no_grad()")
+    left, right, _ = _fa2_lib.parse_window(window, 0)
+    _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, dv=True)
+    if max_seqlen_q is None:
+        max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max())
+    if max_seqlen_k is None:
+        max_seqlen_k = int((cu_seqlens_k[1:] - cu_seqlens_k[:-1]).max())
+    if scale is None:
+        scale = D ** -0.5
+    flags = (_fa2_lib.FA2_FLAG_CAUSAL if causal else 0) | (_fa2_lib.FA2_FLAG_BOTTOM_RIGHT if bottom_right else 0)
+    out, L = flash_attn_wmma.forward_varlen_dv(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), flags, scale, (left, right))
+    return (out, L * _LN2) if return_lse else out
 
 
 def _band_mask(nq, nkv, window, causal, device):

@@ -26,7 +26,8 @@ FA2_BIAS_NONE, FA2_BIAS_IO_DTYPE, FA2_BIAS_F32, FA2_BIAS_BOOL = 0, 1, 2, 3     #
 FA2_KERNEL_HIP_256, FA2_KERNEL_HIP_128, FA2_KERNEL_ASM, FA2_KERNEL_HIP_BIAS = 1, 2, 3, 4              # fa2_fwd_plan_t.kernel
 FA2_KERNEL_HIP_WINDOW = 5                                                                               # ... of fa2_fwd_window_plan (an enumerator in the header)
 FA2_KERNEL_HIP_VARLEN = 6                                                                               # ... of fa2_fwd_varlen_plan (an enumerator, too)
-FA2_CONTRACT_PRESCALE_Q, FA2_CONTRACT_LSUM_P16 = 1, 2                                                   # fa2_fwd_plan_t.contract bits
+FA2_KERNEL_HIP_VARLEN_DV = 10                                                                           # ... of fa2_fwd_varlen_dv_plan (an enumerator, too)
+FA2_CONTRACT_PRESCALE_Q, FA2_CONTRACT_LSUM_P16 = 1, 2                                                 # fa2_fwd_plan_t.contract bits
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _vpp = ctypes.POINTER(ctypes.c_void_p)      # a host array of device pointers (fa2_merge_*)
@@ -121,6 +122,10 @@ SYMBOLS = {
     "fa2_bwd_varlen": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 10 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [_i64p] * 8 +
                        [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
     "fa2_fwd_varlen_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_i64p, _i64p, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.POINTER(FwdPlan)]),
+    # ... with v / o of head dim Dv < D (the non-absorbed MLA prefill): fa2_fwd_varlen's / fa2_fwd_varlen_plan's lists with Dv after D
+    "fa2_fwd_varlen_dv": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p] * 2 + [_i64p] * 4 +
+                          [ctypes.c_int64, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "fa2_fwd_varlen_dv_plan": (ctypes.c_int, [ctypes.c_int] * 8 + [_i64p, _i64p, ctypes.c_float] + [ctypes.c_int] * 3 + [ctypes.POINTER(FwdPlan)]),
     "fa2_varlen_tile_range": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_varlen_row_range": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int)] * 2),
     # attention dropout: the windowed / packed argument lists, then (float dropout_p, uint64_t seed); and the host side of the mask contract

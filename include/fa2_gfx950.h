@@ -408,6 +408,29 @@ int fa2_bwd_varlen(int dtype, const void* q, const void* k, const void* v, const
                    const int64_t o_strides[2], const int64_t do_strides[2], const int64_t dq_strides[2],
                    const int64_t dk_strides[2], const int64_t dv_strides[2], int64_t lse_stride,
                    float scale, int flags, int window_left, int window_right, void* hip_stream);
+/*
+ * Packed attention with V narrower than K: the non-absorbed prefill of multi-head-latent attention (q and k 192 wide — 128 "nope" plus 64 rotary
+ * columns —, v 128 wide).  Forward only, packed layout only.  fa2_fwd_varlen's argument list with Dv after D:
+ *   q              : [total_q, H, D]      k : [total_k, Hkv, D]      v : [total_k, Hkv, Dv]      o : [total_q, H, Dv]
+ * Served pairs: D a multiple of 8 in 136 .. 256 and Dv a multiple of 8 in 8 .. 128; (192, 128) is the pair the call exists for.
+ * v's strides are its own and independent of Dv — typically the slice [..., 128:256] of the up-projection's output: columns of that buffer at or beyond
+ * Dv are never fetched, and nothing of o beyond column Dv is written.  Everything else is fa2_fwd_varlen's: device cu_seqlens, zero-length sequences,
+ * grouped K / V not expanded, the flags and the window, rows that see no key (O = 0, lse = -inf), one owner per element of o[:, :, :Dv] and lse below
+ * cu[B], contract 0, lse in log2 units.  scale is the caller's (D ** -0.5 for the plain softmax scale, not Dv ** -0.5).
+ * Validation: fa2_fwd_varlen's order and codes; in addition Dv < 1 is FA2_ERR_BAD_SHAPE (with the other sizes), a pair outside the served set
+ * FA2_ERR_HEAD_DIM (where the head dim is checked), and v's span rule counts Dv columns in its last row.
+ * Kernel (FA2_KERNEL_HIP_VARLEN_DV, csrc/varlen_dv_hip.cpp): the packed kernel of head dim 256 run as ONE 128-column slab, with ceil(D / 16) Q.K^T
+ * k-steps rounded up to 12 (D <= 192) or 16 and ceil(Dv / 32) O column blocks.  With the same "rows" the result equals fa2_fwd_varlen on v zero-padded
+ * to D, sliced to Dv, bit for bit: the skipped k-steps and the skipped slab only ever multiplied zeros.  Option "rows" picks 128- or 256-row workgroups.
+ */
+int fa2_fwd_varlen_dv(int dtype,
+                      const void* q, const void* k, const void* v, void* o, float* lse,
+                      int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D, int Dv,
+                      const int* cu_seqlens_q, const int* cu_seqlens_k,
+                      const int64_t q_strides[2], const int64_t k_strides[2],
+                      const int64_t v_strides[2], const int64_t o_strides[2],
+                      int64_t lse_stride,
+                      float scale, int flags, int window_left, int window_right, void* hip_stream);
 /* The per-sequence range arithmetic of the packed kernels: fa2_window_tile_range / fa2_window_row_range for one sequence of Nq_s queries and Nkv_s
  * keys (>= 0), the offset derived from `flags` (FA2_FLAG_BOTTOM_RIGHT: Nkv_s - Nq_s, which may be negative — the windowed queries above keep
  * refusing negative offsets; FA2_FLAG_CAUSAL: window_right = 0).  Pure host arithmetic. */
@@ -1031,6 +1054,13 @@ enum { FA2_KERNEL_HIP_VARLEN = 6 };     /* (an enumerator, like FA2_KERNEL_HIP_W
 int fa2_fwd_varlen_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D,
                         const int64_t q_strides[2], const int64_t k_strides[2],
                         float scale, int flags, int window_left, int window_right, fa2_fwd_plan_t* plan);
+
+/* The plan of fa2_fwd_varlen_dv above: kernel = FA2_KERNEL_HIP_VARLEN_DV, contract 0, rows as launched, heads_main = B*H.  The strides may be NULL
+ * (contiguous tensors); v takes k's, o takes q's.  Sizes, flags, window, dtype, the (D, Dv) pair and the scale are checked as by the call. */
+enum { FA2_KERNEL_HIP_VARLEN_DV = 10 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+int fa2_fwd_varlen_dv_plan(int dtype, int B, int H, int Hkv, int max_seqlen_q, int max_seqlen_k, int D, int Dv,
+                           const int64_t q_strides[2], const int64_t k_strides[2],
+                           float scale, int flags, int window_left, int window_right, fa2_fwd_plan_t* plan);
 
 /* ---- Chunked prefill against a KV cache: packed queries (as fa2_fwd_varlen's) against the cache fa2_kvcache_append writes and fa2_fwd_decode reads,
  * contiguous or paged, with every length and the block table read on the device — a prompt whose prefix already sits in cached pages, a prompt
