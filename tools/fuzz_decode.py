@@ -758,14 +758,18 @@ class Trace:
                 for pool, rows in zip(self.pool, (rows_k, rows_v)):
                     _raw(pool)[self.owned[b][p // page], p % page] = _raw(rows)[i]
 
-    def start(self, b, n):
-        """slot b's sequence ends (its pages return to the free list as they are) and a prompt of n tokens takes the slot: one append chunk"""
-        from rocwmma_fattn import FlashAttn
+    def release(self, b):
+        """slot b's sequence ends: its pages return to the free list as they are"""
         if self.owned[b]:
             self.recycled.add(b)
         for j in sorted(self.owned[b]):
             self.free.append(self.owned[b][j])
         self.owned[b] = {}
+
+    def start(self, b, n):
+        """slot b's sequence ends (release) and a prompt of n tokens takes the slot: one append chunk"""
+        from rocwmma_fattn import FlashAttn
+        self.release(b)
         self.lens[b] = n
         self._hand_out(b, whole=True)                  # (pages of a long prompt that lie below the window are freed at the next step)
         k, v = (_randn((1, n, self.d["Hkv"], self.d["D"]), self.g).to(self.dt) for _ in range(2))
