@@ -19,6 +19,7 @@
 #include "fa2_launch.h"
 #include "fa2_dropout.h"
 #include "fa2_decode_mla.hip.h"      // the latent-cache decode: its constants, the arithmetic the plan shares with the kernel, its launcher
+#include "fa2_decode_mla_sparse.hip.h"      // ... and its sparse (top-k indexed) form
 #include "fa2_kvappend_mla.hip.h"    // ... and its append: the parameter block, the unit -> chunks map, its launcher
 
 #include <algorithm>
@@ -1789,12 +1790,18 @@ struct DecodeMlaCall : CacheDesc {
     void* ws = nullptr;
     size_t ws_bytes = 0;
     void* stream = nullptr;
+    // what fa2_fwd_decode_mla_sparse adds: the dense entry leaves these as they are
+    bool sparse = false;
+    const int* indices = nullptr;
+    int topk = 0;
+    const int64_t* is = nullptr;                                    // {batch, row}
 };
 
 // The sizes of the call, in the documented order (shape, then head dim)
 static int decode_mla_check_shape(const DecodeMlaCall& c) {
     if (c.B < 1 || c.H < 1 || c.Nq < 1 || c.D < 1 || c.Dv < 1 || c.H > fa2::kMlaMaxHeads) return FA2_ERR_BAD_SHAPE;
     if ((int64_t)c.Nq * c.H > fa2::kMlaMaxRows || !cache_paging_ok(c) || c.num_splits < 0 || c.num_splits > fa2::kMlaMaxSplit) return FA2_ERR_BAD_SHAPE;
+    if (c.sparse && (c.topk < 1 || c.topk > 0x7fffffff - 64)) return FA2_ERR_BAD_SHAPE;
     if (c.D != fa2::kMlaD || c.Dv != fa2::kMlaDv) return FA2_ERR_HEAD_DIM;
     return FA2_OK;
 }
@@ -1815,11 +1822,13 @@ static int decode_mla_split(int B, int row_blocks, int64_t capacity_tiles, int n
 static int decode_mla_plan(const DecodeMlaCall& c, fa2_decode_mla_plan_t* plan) {
     if (int rc = decode_mla_check_shape(c)) return rc;
     if (c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
-    plan->kernel = FA2_KERNEL_HIP_DECODE_MLA;
-    plan->row_blocks = fa2::mla_row_blocks(c.Nq * c.H);
+    plan->kernel = c.sparse ? FA2_KERNEL_HIP_DECODE_MLA_SPARSE : FA2_KERNEL_HIP_DECODE_MLA;
+    plan->row_blocks = c.sparse ? fa2::mla_sparse_row_blocks(c.Nq, c.H) : fa2::mla_row_blocks(c.Nq * c.H);
     plan->key_tile = fa2::kMlaTile;
     plan->max_split = fa2::kMlaMaxSplit;
-    plan->nsplit = decode_mla_split(c.B, plan->row_blocks, (c.capacity_keys() + fa2::kMlaTile - 1) / fa2::kMlaTile, c.num_splits);
+    // the sparse call sweeps its list, not the cache: the tiles a part can be given are those of topk
+    const int64_t span = c.sparse ? c.topk : c.capacity_keys();
+    plan->nsplit = decode_mla_split(c.B, plan->row_blocks, (span + fa2::kMlaTile - 1) / fa2::kMlaTile, c.num_splits);
     return FA2_OK;
 }
 
@@ -1864,12 +1873,16 @@ int fa2_decode_mla_tile(int64_t len, int capacity, int page_size, int tile, int*
     return FA2_OK;
 }
 
+// One body for fa2_fwd_decode_mla and fa2_fwd_decode_mla_sparse: the sparse entry's arguments are checked where their kind is.
 static int decode_mla_run(const DecodeMlaCall& c) {
     if (any_null({c.q, c.o, c.lse, c.lens, c.qs, c.os, c.ls}) || cache_null(c)) return FA2_ERR_NULL_POINTER;
+    if (c.sparse && any_null({c.indices, c.is})) return FA2_ERR_NULL_POINTER;
     if (int rc = decode_mla_check_shape(c)) return rc;
     if (!cache_extent_ok(c) || c.ls[0] < 0 || c.ls[1] < 0) return FA2_ERR_BAD_SHAPE;
-    if (!all_aligned16({c.q, c.o}) || !cache_aligned(c) || ((reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.lens)) & 3u) ||
-        !strides3_ok(c.qs) || !strides3_ok(c.os))
+    if (c.sparse && (c.is[0] < 0 || c.is[1] < 0)) return FA2_ERR_BAD_SHAPE;
+    if (!all_aligned16({c.q, c.o}) || !cache_aligned(c) ||
+        ((reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.lens) | reinterpret_cast<uintptr_t>(c.indices)) & 3u) || !strides3_ok(c.qs) ||
+        !strides3_ok(c.os))
         return FA2_ERR_ALIGNMENT;
     fa2_decode_mla_plan_t plan;
     if (int rc = decode_mla_plan(c, &plan)) return rc;                // (the dtype: after the alignment)
@@ -1893,6 +1906,12 @@ static int decode_mla_run(const DecodeMlaCall& c) {
         if (c.ws_bytes < decode_mla_ws_need(c, plan)) return FA2_ERR_BAD_SHAPE;
         p.ws = static_cast<float*>(c.ws);
     }
+    if (c.sparse) {
+        fa2::MlaSparse sp;
+        std::memset(&sp, 0, sizeof(sp));
+        sp.idx = c.indices; sp.topk = c.topk; sp.is[0] = c.is[0]; sp.is[1] = c.is[1];
+        return fa2::launch_decode_mla_sparse(c.dtype == FA2_DTYPE_BF16, p, sp, (hipStream_t)c.stream);
+    }
     return fa2::launch_decode_mla(c.dtype == FA2_DTYPE_BF16, p, (hipStream_t)c.stream);
 }
 
@@ -1905,6 +1924,47 @@ int fa2_fwd_decode_mla(int dtype, const void* q, const void* kv_cache, void* o, 
     c.qs = q_strides; c.ks = kv_strides; c.vs = kv_strides; c.os = o_strides; c.ls = lse_strides; c.bts = block_table_stride; c.scale = scale;
     c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = hip_stream;
     return decode_mla_run(c);
+}
+
+// ---- ... on the rows a per-token list names (sparse, top-k indexed): csrc/fa2_decode_mla_sparse.hip.h has the kernel
+int fa2_fwd_decode_mla_sparse(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table, int B,
+                              int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
+                              const int64_t kv_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale,
+                              int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream, const int* indices, int topk,
+                              const int64_t indices_strides[2]) {
+    FA2_DECODE_MLA_SIZES(c);
+    c.q = q; c.k = kv_cache; c.v = kv_cache; c.o = o; c.lse = lse; c.lens = cache_seqlens; c.block_table = block_table; c.num_pages = num_pages;
+    c.qs = q_strides; c.ks = kv_strides; c.vs = kv_strides; c.os = o_strides; c.ls = lse_strides; c.bts = block_table_stride; c.scale = scale;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = hip_stream;
+    c.sparse = true; c.indices = indices; c.topk = topk; c.is = indices_strides;
+    return decode_mla_run(c);
+}
+
+int fa2_fwd_decode_mla_sparse_plan(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, int topk,
+                                   fa2_decode_mla_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    std::memset(plan, 0, sizeof(*plan));
+    FA2_DECODE_MLA_SIZES(c);
+    c.sparse = true; c.topk = topk;
+    return decode_mla_plan(c, plan);
+}
+
+size_t fa2_fwd_decode_mla_sparse_workspace_bytes(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, int topk) {
+    fa2_decode_mla_plan_t plan;
+    FA2_DECODE_MLA_SIZES(c);
+    c.sparse = true; c.topk = topk;
+    return decode_mla_plan(c, &plan) ? 0 : decode_mla_ws_need(c, plan);
+}
+
+int fa2_decode_mla_sparse_entry(int entry, int64_t len, int Nq, int i, int capacity, int page_size, int* valid, int* page_slot, int* row_in_page) {
+    if (!valid || !page_slot || !row_in_page) return FA2_ERR_NULL_POINTER;
+    CacheDesc c;
+    c.capacity = capacity; c.page_size = page_size;
+    if (!cache_paging_ok(c) || c.capacity_keys() > 0x7fffffffLL - 64 || Nq < 1 || i < 0 || i >= Nq) return FA2_ERR_BAD_SHAPE;
+    const int64_t cap = c.capacity_keys();
+    const fa2::MlaSparseEntry e = fa2::mla_sparse_entry(entry, (int64_t)fa2::decode_clamp_len(len, cap) - Nq + i, fa2::mla_page_keys(page_size, cap));
+    *valid = e.valid; *page_slot = e.slot; *row_in_page = e.row;
+    return FA2_OK;
 }
 
 // ---- KV-cache append with rotary embedding and e4m3 quantisation: include/fa2_gfx950.h has the contract, csrc/fa2_kvappend.hip.h the kernel,

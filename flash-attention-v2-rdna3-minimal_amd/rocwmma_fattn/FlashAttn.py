@@ -1626,7 +1626,7 @@ _MLA_D, _MLA_DV, _MLA_MAX_HEADS, _MLA_MAX_ROWS, _MLA_MAX_SPLITS = 576, 512, 128,
 
 
 def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, head_dim_v=512, scale=None, return_lse=False, num_splits=0, kv_c=None, k_pe=None,
-                               rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
+                               rotary_cos=None, rotary_sin=None, rotary_interleaved=True, indices=None):
     """Decode attention on a multi-head-latent (MLA) KV cache — the decode step of DeepSeek-V2 / V3 / R1 and Kimi K2 with the up-projections absorbed
     into the query and the output (the flash_mla_with_kvcache shape).
     q [B, Nq, H, 576] fp16 / bf16: the absorbed query, q_nope . W_UK in columns 0 .. 511 and the rotated q_pe in columns 512 .. 575.  A q the kernel
@@ -1650,7 +1650,14 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
     position; the attention then reads the rotated q.  Every check of both halves runs before the first launch, so a call that is refused leaves the
     cache as it was; the two launches share q's stream.  rotary_* without kv_c / k_pe raises (rotary without an append is not served).  With none of
     the five the call makes exactly the launches it made before.  Standalone: kvcache_append_mla, kvcache_append_mla_varlen.
-    C-ABI fa2_fwd_decode_mla: each cache row is fetched once per workgroup and used as K and as V for up to 64 (token, head) rows; no atomics."""
+    C-ABI fa2_fwd_decode_mla: each cache row is fetched once per workgroup and used as K and as V for up to 64 (token, head) rows; no atomics.
+    indices: None, or int32 [B, Nq, topk] on q's device with stride(2) == 1 and topk >= 1 — the sparse (top-k indexed) decode step of DeepSeek-V3.2
+    (flash_mla_with_kvcache(..., indices=)): query token (b, i), with all its heads, attends the cache positions its list names and no others.
+    An entry j is a LOGICAL key position of sequence b, resolved through block_table in-kernel; it counts iff 0 <= j <= len_b - Nq + i, and a position
+    named twice counts twice.  -1 padding and every other entry outside that range contribute nothing and are never addressed; a row without a
+    valid entry returns zeros (lse -inf); cache rows no valid entry names are never read.  The rows are read in place — no gathered copy — and the
+    work per row is topk whatever the lengths.  Every other argument keeps its meaning (num_splits then splits the list), the fused append
+    included; the host reads nothing of the list, so a captured call follows indices changed in place.  C-ABI fa2_fwd_decode_mla_sparse."""
     who = "flash_attention_decode_mla"
     if not all(torch.is_tensor(t) for t in (q, kv_cache, cache_seqlens)) or q.dim() != 4 or kv_cache.dim() not in (3, 4) or \
             (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):
@@ -1668,6 +1675,12 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
         raise ValueError("fa2: %s serves 1 .. %d heads and Nq * H <= %d query rows (B, Nq >= 1), got q %s" % (who, _MLA_MAX_HEADS, _MLA_MAX_ROWS, tuple(q.shape)))
     if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _MLA_MAX_SPLITS:
         raise ValueError("fa2: num_splits is 0 (the library chooses) or 1 .. %d, got %r" % (_MLA_MAX_SPLITS, num_splits))
+    if indices is not None:
+        if not torch.is_tensor(indices) or indices.dtype != torch.int32 or indices.dim() != 3 or tuple(indices.shape[:2]) != (B, Nq) or indices.shape[2] < 1 or \
+                indices.stride(2) != 1 or indices.device != q.device:
+            raise ValueError("fa2: %s takes indices as an int32 tensor [B, Nq, topk] = [%d, %d, >= 1] on q's device whose last dim is contiguous, got %s"
+                             % (who, B, Nq, "%s %s strides %s on %s" % (indices.dtype, tuple(indices.shape), indices.stride(), indices.device)
+                                if torch.is_tensor(indices) else repr(indices)))
     fused = kv_c is not None or k_pe is not None
     if not fused and (rotary_cos is not None or rotary_sin is not None):
         raise ValueError("fa2: rotary_cos / rotary_sin rotate the appended tokens: %s takes them together with kv_c and k_pe (rotary without an append is "
@@ -1693,13 +1706,21 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
     dev = _device_index(q)
     with torch.cuda.device(dev):
         stream = _raw_stream(dev)
-        need = lib.fa2_fwd_decode_mla_workspace_bytes(code, B, H, Nq, _MLA_D, _MLA_DV, cache.capacity, cache.page_size, num_splits)
+        sizes = (code, B, H, Nq, _MLA_D, _MLA_DV, cache.capacity, cache.page_size, num_splits)
+        if indices is None:
+            need = lib.fa2_fwd_decode_mla_workspace_bytes(*sizes)
+        else:
+            need = lib.fa2_fwd_decode_mla_sparse_workspace_bytes(*sizes, indices.shape[2])
         ws = _workspace(need, q.device, dev, stream) if need else None
         if ws is None and _WS_POOL:
             _workspace_unused(dev, stream)
-        rc = lib.fa2_fwd_decode_mla(code, q.data_ptr(), cache.ptrs[0], o.data_ptr(), lse.data_ptr(), *cache.tables, B, H, Nq, _MLA_D, _MLA_DV, *cache.sizes,
-                                    _bnhd(q), cache.strides[0], _bnhd(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), cache.bts, float(scale),
-                                    num_splits, None if ws is None else ws.data_ptr(), need, stream)
+        args = (code, q.data_ptr(), cache.ptrs[0], o.data_ptr(), lse.data_ptr(), *cache.tables, B, H, Nq, _MLA_D, _MLA_DV, *cache.sizes, _bnhd(q),
+                cache.strides[0], _bnhd(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), cache.bts, float(scale), num_splits,
+                None if ws is None else ws.data_ptr(), need, stream)
+        if indices is None:
+            rc = lib.fa2_fwd_decode_mla(*args)
+        else:
+            rc = lib.fa2_fwd_decode_mla_sparse(*args, indices.data_ptr(), indices.shape[2], _fa2_lib.strides2(indices.stride(0), indices.stride(1)))
     _fa2_lib.check(rc)
     return (o, lse * _LN2) if return_lse else o
 

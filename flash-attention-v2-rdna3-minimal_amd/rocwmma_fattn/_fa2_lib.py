@@ -63,6 +63,7 @@ class DecodeMlaPlan(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FA2_KERNEL_HIP_DECODE_MLA_SPARSE = 11                                                                   # ... of fa2_fwd_decode_mla_sparse_plan
 FA2_KERNEL_HIP_DECODE_MLA = 9                                                                           # fa2_decode_mla_plan_t.kernel (an enumerator in the header)
 FA2_KERNEL_HIP_PREFILL = 8                                                                              # fa2_fwd_prefill_plan's kernel (an enumerator in the header)
 FA2_KERNEL_HIP_DECODE = 7                                                                               # fa2_decode_plan_t.kernel (an enumerator in the header)
@@ -187,6 +188,13 @@ SYMBOLS = {
     "fa2_fwd_decode_mla_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
     "fa2_decode_mla_part_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 2),
     "fa2_decode_mla_tile": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 3),
+    # ... sparse (top-k indexed): fa2_fwd_decode_mla's list, then indices, topk, the indices' {batch, row} stride pair; the queries gain topk
+    "fa2_fwd_decode_mla_sparse": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +
+                                  [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_int, _i64p]),
+    "fa2_fwd_decode_mla_sparse_plan": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(DecodeMlaPlan)]),
+    "fa2_fwd_decode_mla_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
+    "fa2_decode_mla_sparse_entry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)] * 3),
     # KV-cache append: dtype cache_format, k_new v_new k_cache v_cache cache_seqlens block_table, B Hkv Nnew D capacity page_size num_pages, four stride
     # triples, the block-table row stride, q q_out H Nq and their stride triples, cos sin rotary_dtype rotary_dim seqlen_ro row-stride interleaved,
     # k_descale v_descale descale_strides, stream
@@ -459,6 +467,22 @@ def decode_mla_plan(dtype, B, H, Nq, capacity, page_size=0, num_splits=0, D=576,
     plan = DecodeMlaPlan()
     check(load().fa2_fwd_decode_mla_plan(int(dtype), int(B), int(H), int(Nq), int(D), int(Dv), int(capacity), int(page_size), int(num_splits), ctypes.byref(plan)))
     return plan
+
+
+def decode_mla_sparse_plan(dtype, B, H, Nq, capacity, topk, page_size=0, num_splits=0, D=576, Dv=512):
+    """fa2_fwd_decode_mla_sparse_plan: the plan of a sparse (top-k indexed) latent-cache decode call; its parts split the list of topk entries."""
+    plan = DecodeMlaPlan()
+    check(load().fa2_fwd_decode_mla_sparse_plan(int(dtype), int(B), int(H), int(Nq), int(D), int(Dv), int(capacity), int(page_size), int(num_splits), int(topk),
+                                                ctypes.byref(plan)))
+    return plan
+
+
+def decode_mla_sparse_entry(entry, length, Nq, i, capacity, page_size=0):
+    """fa2_decode_mla_sparse_entry -> (valid, page_slot, row_in_page) of list entry `entry` for query row i of Nq of a sequence of `length` keys."""
+    v, slot, row = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(load().fa2_decode_mla_sparse_entry(int(entry), int(length), int(Nq), int(i), int(capacity), int(page_size), ctypes.byref(v), ctypes.byref(slot),
+                                             ctypes.byref(row)))
+    return v.value, slot.value, row.value
 
 
 def decode_mla_part_range(length, capacity_keys, nsplit, part):

@@ -808,6 +808,39 @@ size_t fa2_fwd_decode_mla_workspace_bytes(int dtype, int B, int H, int Nq, int D
 int fa2_decode_mla_part_range(int64_t len, int64_t capacity_keys, int nsplit, int part, int* first_tile, int* ntiles);
 int fa2_decode_mla_tile(int64_t len, int capacity, int page_size, int tile, int* page_slot, int* row_in_page, int* valid_rows);
 
+/* ---- ... sparse (top-k indexed): the decode step of DeepSeek-V3.2 style models, whose indexer names, per query token, the topk cache positions the
+ * token attends (all heads of the token share the list).  fa2_fwd_decode_mla's argument list, then
+ *   indices         : B x Nq x topk int32, device data the host never reads; element strides indices_strides {batch, row}, last dim contiguous.
+ *                     indices[b, i, t] = j is a LOGICAL key position of sequence b — resolved through block_table in-kernel like every other
+ *                     position, never a physical slot.
+ * With pos = len_b - Nq + i (len clamped as in fa2_fwd_decode_mla), entry t is VALID iff 0 <= j <= pos, and
+ *   o[b, h, i, :] = sum over the valid t of softmax_t(scale * q[b, h, i, :] . kv[b, j_t, :]) . kv[b, j_t, :512],  lse = logsumexp over the valid t.
+ * A position named twice counts twice.  Invalid entries (-1 padding, negative, above pos, INT32_MIN / INT32_MAX) contribute nothing and never become
+ * part of an address: neither their block-table entry nor their row is read.  A row without a valid entry, or at a negative position, returns zeros
+ * and lse = -inf.  Cache rows no valid entry names are never read, whatever they hold; a page that holds only such rows is never addressed and its
+ * block-table entry never read.  Lengths and page ids are clamped as in fa2_fwd_decode_mla; addresses are formed in 64 bits.
+ * Checked in fa2_fwd_decode_mla's order with the new arguments where their kind is: null pointers (also indices, indices_strides); sizes (also
+ * topk < 1 or topk > 2^31 - 1 - 64: FA2_ERR_BAD_SHAPE); head dim; the strides' signs (a negative indices stride, like a negative lse stride:
+ * FA2_ERR_BAD_SHAPE); alignment (also indices, 4 bytes); dtype; scale; FA2_ERR_GRID; the workspace.
+ * Kernel (FA2_KERNEL_HIP_DECODE_MLA_SPARSE, csrc/fa2_decode_mla_sparse.hip.h): one workgroup of four waves per (part, token x block of up to 64
+ * heads, sequence) — a block never spans two tokens — over tiles of 32 consecutive ENTRIES of the list; the per-tile arithmetic is
+ * FA2_KERNEL_HIP_DECODE_MLA's.  Parts split the list: the plan is fa2_fwd_decode_mla_plan's rule with row_blocks = Nq * ceil(H / 64) and the tiles of
+ * topk in the place of the capacity's, so work per row is topk whatever the lengths.  The workspace has fa2_fwd_decode_mla's layout and formula.
+ * fa2_decode_mla_sparse_entry: the host side of the function the kernel resolves an entry with — for `entry` in the list of query row i of Nq of a
+ * sequence of len keys: *valid, and for a valid entry the block-table slot of its page and its row there (an invalid one: 0, 0). */
+enum { FA2_KERNEL_HIP_DECODE_MLA_SPARSE = 11 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+int fa2_fwd_decode_mla_sparse(int dtype, const void* q, const void* kv_cache, void* o, float* lse,
+                              const int* cache_seqlens, const int* block_table,
+                              int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages,
+                              const int64_t q_strides[3], const int64_t kv_strides[3], const int64_t o_strides[3],
+                              const int64_t lse_strides[2], int64_t block_table_stride,
+                              float scale, int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream,
+                              const int* indices, int topk, const int64_t indices_strides[2]);
+int fa2_fwd_decode_mla_sparse_plan(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, int topk,
+                                   fa2_decode_mla_plan_t* plan);
+size_t fa2_fwd_decode_mla_sparse_workspace_bytes(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, int topk);
+int fa2_decode_mla_sparse_entry(int entry, int64_t len, int Nq, int i, int capacity, int page_size, int* valid, int* page_slot, int* row_in_page);
+
 /* ---- KV-cache append: the write side of the decode calls.  One launch writes the K and V rows of Nnew new tokens per sequence into the cache at the
  * key position only the device knows, optionally rotates k (and q) by that position and optionally quantises to e4m3.
  * Layout (element strides {batch, head, row}, D contiguous)

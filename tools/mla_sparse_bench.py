@@ -1,0 +1,109 @@
+"""Sparse (top-k indexed) decode attention on a latent (MLA) KV cache: flash_attention_decode_mla(indices=) against the routes a holder of such a cache
+had before, same box, interleaved rounds, median of per-round event times with the spread of the rounds beside it (tools/mla_decode_bench.py's method).
+
+    python tools/mla_sparse_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX]
+
+Routes
+    sparse        flash_attention_decode_mla(q, cache, lens, indices=idx): the selected rows read in place
+    gather+dense  (a) index_select of the selected rows into a contiguous [B * Nq, topk, 576] copy (through the block table where the cache is paged),
+                  then the dense call on the copy, the copy INSIDE the timed region: the same computation
+    dense-all     (b) the dense call over the whole cache: a DIFFERENT computation (it attends every key), shown for scale only
+Every row prints (c) the floor: B * Nq * topk * 1 152 bytes at 6.3 TB/s.  A route is called faster only where the gap exceeds the sum of the two
+spreads.  Each row first checks sparse against gather+dense on the timed inputs.  The lists hold topk distinct positions of each sequence, drawn
+uniformly and sorted, as an indexer's top-k is."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "flash-attention-v2-rdna3-minimal_amd"))
+
+import torch  # noqa: E402
+
+from benchlib import close, interleaved, paged_pool  # noqa: E402
+from rocwmma_fattn import _fa2_lib  # noqa: E402
+from rocwmma_fattn.FlashAttn import flash_attention_decode_mla  # noqa: E402
+
+HBM_TBS = 6.3
+D, TOPK, BF16 = 576, 2048, torch.bfloat16
+ROWS = [(("%d_b%d_h%d_%dk%s" % (n, B, H, keys // 1024, "_pg64" if paged else "")), B, H, keys, paged)      # (label, B, H, keys or (shortest, longest), paged)
+        for n, (B, H) in enumerate(((32, 128), (32, 16)), 1) for keys in (4096, 32768, 65536) for paged in (False, True)]
+ROWS.append(("3_ragged_b32_h128_pg64", 32, 128, (2048, 65536), True))
+
+
+def row(out, label, B, H, keys, paged, rounds, iters):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    lens_h = torch.randint(keys[0], keys[1] + 1, (B,), generator=g).tolist() if isinstance(keys, tuple) else [keys] * B
+    nmax = -(-max(lens_h) // 64) * 64
+    q = torch.randn((B, 1, H, D), device=dev, dtype=BF16)
+    kv = torch.randn((B, nmax, D), device=dev, dtype=BF16)
+    lens = torch.tensor(lens_h, dtype=torch.int32, device=dev)
+    idx = torch.stack([torch.randperm(n, generator=g)[:TOPK].sort().values for n in lens_h]).to(torch.int32).view(B, 1, TOPK).to(dev)
+    full = torch.full((B,), TOPK, dtype=torch.int32, device=dev)
+    if paged:
+        pool, _, bt = paged_pool(kv.unsqueeze(2), kv.unsqueeze(2), 64, g, lens=lens_h)
+        pool = pool[:, :, 0]
+        flat = pool.view(-1, D)
+
+        def rows_of():                                 # logical -> physical rows, then the copy
+            j = idx.view(B, TOPK).long()
+            return flat.index_select(0, (bt.long().gather(1, j // 64) * 64 + j % 64).view(-1)).view(B, TOPK, D)
+        fns = {"sparse": lambda: flash_attention_decode_mla(q, pool, lens, block_table=bt, indices=idx),
+               "gather+dense": lambda: flash_attention_decode_mla(q, rows_of(), full),
+               "dense-all": lambda: flash_attention_decode_mla(q, pool, lens, block_table=bt)}
+    else:
+        flat = kv.view(-1, D)
+        base = (torch.arange(B, device=dev) * nmax).view(B, 1)
+        fns = {"sparse": lambda: flash_attention_decode_mla(q, kv, lens, indices=idx),
+               "gather+dense": lambda: flash_attention_decode_mla(q, flat.index_select(0, (base + idx.view(B, TOPK)).view(-1)).view(B, TOPK, D), full),
+               "dense-all": lambda: flash_attention_decode_mla(q, kv, lens)}
+    with torch.no_grad():
+        close("mla_sparse_bench", fns["sparse"](), fns["gather+dense"](), BF16, label + ": sparse and gather+dense")
+        t = interleaved(fns, rounds, iters)
+    plan = _fa2_lib.decode_mla_sparse_plan(1, B, H, 1, bt.shape[1] if paged else nmax, TOPK, 64 if paged else 0)
+    floor_us = B * TOPK * D * 2 / (HBM_TBS * 1e12) * 1e6
+    shape = "B%d H%d Nq1 topk %d of %s keys bf16%s (split %d)" % (
+        B, H, TOPK, keys if not isinstance(keys, tuple) else "%d .. %d (mean %d)" % (min(lens_h), max(lens_h), sum(lens_h) // B), " pages of 64" if paged else "",
+        plan.nsplit)
+    lines = ["%-24s %s  floor %.1f us at %.1f TB/s" % (label, shape, floor_us, HBM_TBS)]
+    s_med, s_lo, s_hi = t["sparse"]
+    for n, (med, lo, hi) in t.items():
+        rel = ""
+        if n != "sparse":
+            real = abs(med - s_med) > (hi - lo) + (s_hi - s_lo)
+            rel = "  sparse %.2fx %s (%s the sum of the spreads, %.1f us)%s" % (
+                max(med / s_med, s_med / med), "faster" if s_med <= med else "SLOWER", "beyond" if real else "WITHIN", ((hi - lo) + (s_hi - s_lo)) * 1e3,
+                "  [a different computation: every key]" if n == "dense-all" else "")
+        lines.append("    %-13s %9.1f us  (rounds %.1f .. %.1f, spread %.1f %%)  %.1f x the floor%s" % (n, med * 1e3, lo * 1e3, hi * 1e3, 100.0 * (hi - lo) / med,
+                                                                                                   med * 1e3 / floor_us, rel))
+    for line in lines:
+        print(line)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+    sys.stdout.flush()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--only", default="", help="rows whose label starts with this")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mla_sparse_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
+    out = open(a.out, "w") if a.out else None
+    head = "%s (%d CUs) rounds %d iters %d | %s" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).multi_processor_count, a.rounds, a.iters,
+                                                   _fa2_lib.load().fa2_version().decode())
+    print(head)
+    if out:
+        out.write(head + "\n")
+    for r in ROWS:
+        if r[0].startswith(a.only):
+            row(out, *r, a.rounds, a.iters)
+
+
+if __name__ == "__main__":
+    main()
