@@ -20,6 +20,9 @@
 // Safety (fa2_decode.hip.h's rules): len is clamped into [0, capacity_keys], every page id into [0, num_pages), every row index of a tile into its
 // live rows before it becomes an address; addresses are formed in 64 bits.  Keys at or beyond len: their rows in the image are zero bits (a select on
 // the staged registers; 0 * NaN is NaN) and their scores -inf (a select on the position).
+//
+// e4m3 latents (fa2_fwd_decode_mla_fp8): rows of 656 bytes — 512 codes, four f32 scales, 64 rotary columns in the I/O dtype —
+// staged through 24 registers and converted on the way into the same LDS image (decode_mla_fp8_kernel, below); everything that reads the image is shared.
 #pragma once
 #include <stdint.h>
 
@@ -65,158 +68,69 @@ FA2_DEC_HD inline MlaTile mla_tile(int t, int len, int page_keys) {
 // row blocks of a call
 FA2_DEC_HD inline int mla_row_blocks(int rows) { return (rows + kMlaBlockRows - 1) / kMlaBlockRows; }
 
+// ---- the e4m3 latent row (fa2_fwd_decode_mla_fp8): 512 OCP e4m3 codes, four f32 scales (scale g: columns 128 g .. 128 g + 127),
+// then the 64 rotary columns in the I/O dtype — 656 bytes, 41 chunks of 16.  The cache's strides count BYTES.
+constexpr int kMlaFp8ScaleOff = kMlaDv;                        // 512
+constexpr int kMlaFp8RopeOff = kMlaFp8ScaleOff + 16;           // 528
+constexpr int kMlaFp8RowBytes = kMlaFp8RopeOff + (kMlaD - kMlaDv) * 2;      // 656
+constexpr int kMlaFp8Group = 128;                              // columns per scale
+// a row stride the kernel can address: whole rows that do not overlap, every chunk 16-byte aligned
+FA2_DEC_HD inline bool mla_fp8_row_stride_ok(int64_t bytes) { return bytes >= kMlaFp8RowBytes && (bytes & 15) == 0; }
+// The staging map of a 32-key tile onto 256 threads: thread t serves ONE row, t / 8, and the column eighth e = t % 8 of it.  Its load i (0 .. 3) is
+// code chunk 8 i + e — the eight threads of a row read 128 consecutive bytes, a whole cache line, per load, and the chunk's scale group is i, the
+// same for all threads, so the row's four scales are ONE 16-byte load — and its one rotary chunk is chunk e of the row's eight.
+struct MlaFp8Stage { int row, eighth; };
+FA2_DEC_HD inline MlaFp8Stage mla_fp8_stage(int t) { return MlaFp8Stage{t >> 3, t & 7}; }
+FA2_DEC_HD inline int mla_fp8_code_chunk(int i, int eighth) { return 8 * i + eighth; }              // its byte offset in the row: 16 x; its scale group: i
+FA2_DEC_HD inline int mla_fp8_scale_group(int chunk) { return chunk * 16 / kMlaFp8Group; }
+
 #if defined(__HIPCC__)
 
-// DecodeParams as fa2_fwd_decode_mla fills it: k = the latent cache (v unused), Hkv = 1, G = H, rows = Nq * H, ks = {batch | page, -, row}
+// One thread's share of a staged e4m3 tile, as it lies in memory: 24 registers where the 16-bit kernel holds 36
+struct MlaFp8Regs { u32x4 code[4], scale, rope; };
+constexpr int kMlaFp8Pieces = 9;       // LDS writes of 16 bytes a thread owes a tile: eight half chunks of codes, one rotary chunk
+// The staged registers as values made HERE (no instruction): what is computed from them stays behind this point.  Without it the compiler hoists the
+// conversion above the S MFMAs, next to the loads, where it waits for them at once and holds 36 converted registers through the first product.
+__device__ __forceinline__ void mla_fp8_pin(MlaFp8Regs& s) {
+    asm volatile("" : "+v"(s.code[0]), "+v"(s.code[1]), "+v"(s.code[2]), "+v"(s.code[3]), "+v"(s.scale), "+v"(s.rope));
+}
+
+// Piece j of a thread's share -> the LDS image of the 16-bit kernel.  j < 8: codes 8 (j & 1) .. + 7 of code chunk j / 2, each
+// rne_io(float(code) * scale) — the packed e4m3 -> f32 conversion (exact), ONE f32 multiply by the group's scale, one rounding (pack2).
+// v_cvt_scalef32_pk_{f16,bf16}_fp8's scale operand serves powers of two alone, and cvt2_e4m3 followed by a 16-bit multiply would round twice.
 template <bool BF16>
-__global__ __launch_bounds__(kDecodeWaves * 64) void decode_mla_kernel(const DecodeParams p) {
-    constexpr int T = kMlaTile, DC = kMlaD / 32, DB = kMlaDv / 16, ROWB = kMlaRowBytes, BUF = T * ROWB;
-    constexpr int CH = kMlaD / 8;                      // 16-byte chunks of a row: 72
-    constexpr int NL = T * CH / (kDecodeWaves * 64);   // staged chunks per thread: 9
-    static_assert(NL * kDecodeWaves * 64 == T * CH && T == 32, "tile geometry");
-    extern __shared__ __attribute__((aligned(16))) char mla_lds[];
-    const float ninf = -__builtin_inff();
-
-    const int part = blockIdx.x, rb = blockIdx.y, b = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4, qi = lane & 15;
-    const int len = decode_clamp_len(p.lens[b], p.capacity_keys);
-    int first, nt;
-    mla_part_range(len, p.capacity_keys, p.nsplit, part, &first, &nt);
-    float* const ws_o = p.ws + (((int64_t)b * p.nsplit + part) * p.rows) * kMlaDv;
-    float* const ws_l = p.ws + (int64_t)p.B * p.nsplit * p.rows * kMlaDv + ((int64_t)b * p.nsplit + part) * p.rows;
-
-    if (p.nsplit > 1 && nt == 0) {                     // an empty part: lse = -inf, no O (the combine never reads a part of weight 0)
-        const int r = rb * kMlaBlockRows + tid;
-        if (tid < kMlaBlockRows && r < p.rows) ws_l[r] = ninf;
+__device__ __forceinline__ void mla_fp8_store_piece(char* row_img, int eighth, const MlaFp8Regs& st, int j) {
+    if (j == kMlaFp8Pieces - 1) {
+        *reinterpret_cast<u32x4*>(row_img + kMlaDv * 2 + eighth * 16) = st.rope;
         return;
     }
+    const int i = j >> 1, h = j & 1;
+    const uint32_t sbits = st.scale[i];                // (a copy first: __builtin_bit_cast on the vector element itself reads element 0)
+    const float sc = __builtin_bit_cast(float, sbits);
+    const uint32_t w0 = st.code[i][2 * h], w1 = st.code[i][2 * h + 1];
+    const f32x2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w0, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w0, 1.0f, true);
+    const f32x2 c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w1, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w1, 1.0f, true);
+    *reinterpret_cast<u32x4*>(row_img + mla_fp8_code_chunk(i, eighth) * 32 + h * 16) =
+        (u32x4){pack2<BF16>(a[0] * sc, a[1] * sc), pack2<BF16>(b[0] * sc, b[1] * sc), pack2<BF16>(c[0] * sc, c[1] * sc), pack2<BF16>(d[0] * sc, d[1] * sc)};
+}
 
-    // the lane's query row: packed row r = i * H + h -> query i, head h, at key position len - Nq + i
-    const int r = rb * kMlaBlockRows + w * 16 + qi;
-    const bool live = r < p.rows;
-    const bool wave_live = rb * kMlaBlockRows + w * 16 < p.rows;      // (wave-uniform) a wave without rows stages and waits, no more
-    const int qrow_i = live ? r / p.G : 0, qrow_h = live ? r % p.G : 0;
-    const int pos = live ? len - p.Nq + qrow_i : -1;
-    u32x4 qf[DC];
-    {
-        const uint16_t* row = static_cast<const uint16_t*>(p.q) + b * p.qs[0] + qrow_h * p.qs[1] + qrow_i * p.qs[2] + 8 * g;
-#pragma unroll
-        for (int dc = 0; dc < DC; ++dc) qf[dc] = live ? *reinterpret_cast<const u32x4*>(row + dc * 32) : (u32x4){0u, 0u, 0u, 0u};
-    }
-
-    const int page_keys = mla_page_keys(p.page_size, p.capacity_keys);
-    // one tile into registers as it lies in memory: chunk c = i * 256 + tid of its 32 x 72 chunks; rows at or beyond len as zero bits
-    auto load_tile = [&](int t, u32x4 (&st)[NL]) {
-        const MlaTile mt = mla_tile(t, len, page_keys);
-        int64_t base;
-        if (p.page_size) base = (int64_t)prefill_clamp_page(p.bt[b * p.bts + mt.slot], p.num_pages) * p.ks[0];
-        else base = b * p.ks[0];
-        const int last = mt.rows - 1;                  // >= 0: every tile of a part holds a valid key; a row index is clamped to it
-        const uint16_t* const kb = static_cast<const uint16_t*>(p.k) + base;
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int ch = i * (kDecodeWaves * 64) + tid, kk = ch / CH, col = ch % CH;
-            const u32x4 x = *reinterpret_cast<const u32x4*>(kb + (int64_t)(mt.row + (kk < last ? kk : last)) * p.ks[2] + col * 8);
-            st[i] = kk <= last ? x : (u32x4){0u, 0u, 0u, 0u};
-        }
-    };
-    auto store_tile = [&](char* buf, const u32x4 (&st)[NL]) {
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int ch = i * (kDecodeWaves * 64) + tid;
-            *reinterpret_cast<u32x4*>(buf + (ch / CH) * ROWB + (ch % CH) * 16) = st[i];
-        }
-    };
-
-    float m = ninf, l = 0.f;
-    f32x4 acc[DB];
-#pragma unroll
-    for (int db = 0; db < DB; ++db) acc[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    const int tend = first + nt;
-    u32x4 st[NL];
-    if (nt > 0) {
-        load_tile(first, st);
-        store_tile(mla_lds, st);
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int t = first; t < tend; ++t) {
-        const bool more = t + 1 < tend;
-        if (more) load_tile(t + 1, st);                // in flight while this tile is computed on
-        const char* const img = mla_lds + cur * BUF;
-        if (wave_live) {
-            // S^T = K Q^T: one 16 x 16 block per 16-key block
-            f32x4 s[2];
-            const char* const ka = img + qi * ROWB + g * 16;
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                s[blk] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int dc = 0; dc < DC; ++dc)
-                    s[blk] = decode_mfma<BF16>(*reinterpret_cast<const u32x4*>(ka + blk * 16 * ROWB + dc * 64), qf[dc], s[blk]);
-            }
-            // online softmax: scores scaled in f32, f32 maxima and row sums of the unrounded P, P rounded to the I/O dtype for P . V
-            const int key0 = t * T;
-            float x[8];
-            float mt = ninf;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int key = key0 + 16 * (j >> 2) + 4 * g + (j & 3);
-                x[j] = key <= pos ? s[j >> 2][j & 3] * p.c : ninf;
-                mt = __builtin_fmaxf(mt, x[j]);
-            }
-            mt = decode_group_max(mt);
-            const float mn = __builtin_fmaxf(m, mt), mu = mn == ninf ? 0.f : mn;
-            const float alpha = __builtin_amdgcn_exp2f(m - mu);
-            float sum = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                x[j] = __builtin_amdgcn_exp2f(x[j] - mu);
-                sum += x[j];
-            }
-            l = l * alpha + decode_group_sum(sum);
-            m = mn;
-            const u32x4 pf = {pack2<BF16>(x[0], x[1]), pack2<BF16>(x[2], x[3]), pack2<BF16>(x[4], x[5]), pack2<BF16>(x[6], x[7])};
-            // O^T = alpha O^T + V^T P^T: the transposed reads deliver keys 4 g .. 4 g + 3 and the same 16 rows further down — P's k order
-            const char* const tr_addr = img + (4 * g + (qi >> 2)) * ROWB + 8 * (qi & 3);      // lane 4 q + p of a group supplies row q, columns 4 p ..
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const u32x2 lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tr_addr + db * 32)));
-                const u32x2 hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tr_addr + db * 32 + 16 * ROWB)));
-                const u32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
-                acc[db] = decode_mfma<BF16>(vf, pf, acc[db] * alpha);
-            }
-        }
-        if (more) store_tile(mla_lds + (cur ^ 1) * BUF, st);
-        __syncthreads();                               // tile t + 1 is visible, and tile t's buffer is free for t + 2
-        cur ^= 1;
-    }
-
-    // each wave owns its rows: acc[db][e] = O^T[d = 16 db + 4 g + e][row qi], normalised once, rounded once
-    if (!live) return;
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    // log2(l) with one Newton step on v_log_f32's answer y: y += (l 2^-y - 1) log2(e).  v_log_f32 is good to an ulp of its RESULT, and at a few hundred
-    // keys per part that ulp is 2^-20: the parts' errors reach the merged LSE one to one
-    const float l1 = l > 0.f ? l : 1.0f;
-    float lg = __builtin_amdgcn_logf(l1);
-    lg = __builtin_fmaf(__builtin_fmaf(l1, __builtin_amdgcn_exp2f(-lg), -1.0f), 1.4426950408889634f, lg);
-    const float lse2 = l > 0.f ? m + lg : ninf;
-    if (p.nsplit > 1) {
-        float* dst = ws_o + (int64_t)r * kMlaDv + 4 * g;
-#pragma unroll
-        for (int db = 0; db < DB; ++db) *reinterpret_cast<f32x4*>(dst + db * 16) = acc[db] * inv;
-        if (g == 0) ws_l[r] = lse2;
-    } else {
-        uint16_t* dst = static_cast<uint16_t*>(p.o) + b * p.os[0] + qrow_h * p.os[1] + qrow_i * p.os[2] + 4 * g;
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-            const f32x4 a = acc[db] * inv;
-            *reinterpret_cast<u32x2*>(dst + db * 16) = (u32x2){pack2<BF16>(a[0], a[1]), pack2<BF16>(a[2], a[3])};
-        }
-        if (g == 0) p.lse[b * p.ls[0] + qrow_h * p.ls[1] + qrow_i] = lse2;
-    }
+// DecodeParams as fa2_fwd_decode_mla fills it: k = the latent cache (v unused), Hkv = 1, G = H, rows = Nq * H, ks = {batch | page, -, row}.
+// FP8: the cache holds e4m3 rows (above; ks in bytes).  Only the staging differs: global -> 24 registers as the bytes lie in memory -> converted on the
+// way into the SAME LDS image, so every read of the image, the softmax and the epilogue are the 16-bit kernel's statements.  The conversion of tile
+// t + 1 is spread over tile t's 32 P . V MFMAs, nine pieces three MFMAs apart: its ~150 VALU instructions issue in the MFMAs' shadow (a workgroup owns
+// its CU, one wave per SIMD: nothing else would fill it), and it sits in the SECOND product so that the loads, issued before the first, have had the
+// 72 S MFMAs to land.  The barrier stays where it was: behind the last write of tile t + 1, which frees tile t's buffer.
+// The cache format is the compile-time constant FP8 of the one body, csrc/fa2_decode_mla_sweep.h, which both kernels include.
+template <bool BF16>
+__global__ __launch_bounds__(kDecodeWaves * 64) void decode_mla_kernel(const DecodeParams p) {
+    constexpr bool FP8 = false;
+#include "fa2_decode_mla_sweep.h"
+}
+// ... on an e4m3 latent cache (decode_mla_fp8_hip.cpp)
+template <bool BF16>
+__global__ __launch_bounds__(kDecodeWaves * 64) void decode_mla_fp8_kernel(const DecodeParams p) {
+    constexpr bool FP8 = true;
+#include "fa2_decode_mla_sweep.h"
 }
 
 #endif  // __HIPCC__
@@ -228,5 +142,7 @@ __global__ __launch_bounds__(kDecodeWaves * 64) void decode_mla_kernel(const Dec
 namespace fa2 {
 // decode_mla_hip.cpp: the kernel above on a grid of (p.nsplit, row blocks, B) workgroups, then — p.nsplit > 1 — decode_combine_kernel at head dim 512
 FA2_LAUNCHER(launch_decode_mla, (const DecodeParams& p, hipStream_t stream), (p, stream))
+// decode_mla_fp8_hip.cpp: the same grid and combine on decode_mla_fp8_kernel
+FA2_LAUNCHER(launch_decode_mla_fp8, (const DecodeParams& p, hipStream_t stream), (p, stream))
 }  // namespace fa2
 #endif

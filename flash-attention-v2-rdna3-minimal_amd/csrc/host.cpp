@@ -1880,6 +1880,7 @@ static int decode_mla_run(const DecodeMlaCall& c) {
     if (int rc = decode_mla_check_shape(c)) return rc;
     if (!cache_extent_ok(c) || c.ls[0] < 0 || c.ls[1] < 0) return FA2_ERR_BAD_SHAPE;
     if (c.sparse && (c.is[0] < 0 || c.is[1] < 0)) return FA2_ERR_BAD_SHAPE;
+    if (c.fp8() && !fa2::mla_fp8_row_stride_ok(c.ks[2])) return FA2_ERR_BAD_SHAPE;      // e4m3 rows: whole 656-byte rows, every chunk of 16 bytes aligned
     if (!all_aligned16({c.q, c.o}) || !cache_aligned(c) ||
         ((reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.lens) | reinterpret_cast<uintptr_t>(c.indices)) & 3u) || !strides3_ok(c.qs) ||
         !strides3_ok(c.os))
@@ -1910,8 +1911,10 @@ static int decode_mla_run(const DecodeMlaCall& c) {
         fa2::MlaSparse sp;
         std::memset(&sp, 0, sizeof(sp));
         sp.idx = c.indices; sp.topk = c.topk; sp.is[0] = c.is[0]; sp.is[1] = c.is[1];
+        if (c.fp8()) return fa2::launch_decode_mla_sparse_fp8(c.dtype == FA2_DTYPE_BF16, p, sp, (hipStream_t)c.stream);
         return fa2::launch_decode_mla_sparse(c.dtype == FA2_DTYPE_BF16, p, sp, (hipStream_t)c.stream);
     }
+    if (c.fp8()) return fa2::launch_decode_mla_fp8(c.dtype == FA2_DTYPE_BF16, p, (hipStream_t)c.stream);
     return fa2::launch_decode_mla(c.dtype == FA2_DTYPE_BF16, p, (hipStream_t)c.stream);
 }
 
@@ -1926,6 +1929,20 @@ int fa2_fwd_decode_mla(int dtype, const void* q, const void* kv_cache, void* o, 
     return decode_mla_run(c);
 }
 
+// ---- ... on an e4m3 latent cache of 656-byte rows: the twin's arguments with kv_cache the byte cache and kv_strides in bytes.
+// The kernel sweeps the same tiles under the same split rule, so the plan and the workspace are the twin's.
+int fa2_fwd_decode_mla_fp8(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table, int B,
+                           int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
+                           const int64_t kv_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride, float scale,
+                           int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    FA2_DECODE_MLA_SIZES(c);
+    c.q = q; c.k = kv_cache; c.v = kv_cache; c.o = o; c.lse = lse; c.lens = cache_seqlens; c.block_table = block_table; c.num_pages = num_pages;
+    c.qs = q_strides; c.ks = kv_strides; c.vs = kv_strides; c.os = o_strides; c.ls = lse_strides; c.bts = block_table_stride; c.scale = scale;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = hip_stream;
+    c.format = FA2_CACHE_E4M3;
+    return decode_mla_run(c);
+}
+
 // ---- ... on the rows a per-token list names (sparse, top-k indexed): csrc/fa2_decode_mla_sparse.hip.h has the kernel
 int fa2_fwd_decode_mla_sparse(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table, int B,
                               int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
@@ -1937,6 +1954,20 @@ int fa2_fwd_decode_mla_sparse(int dtype, const void* q, const void* kv_cache, vo
     c.qs = q_strides; c.ks = kv_strides; c.vs = kv_strides; c.os = o_strides; c.ls = lse_strides; c.bts = block_table_stride; c.scale = scale;
     c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = hip_stream;
     c.sparse = true; c.indices = indices; c.topk = topk; c.is = indices_strides;
+    return decode_mla_run(c);
+}
+
+int fa2_fwd_decode_mla_sparse_fp8(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* cache_seqlens, const int* block_table,
+                                  int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
+                                  const int64_t kv_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2], int64_t block_table_stride,
+                                  float scale, int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream, const int* indices, int topk,
+                                  const int64_t indices_strides[2]) {
+    FA2_DECODE_MLA_SIZES(c);
+    c.q = q; c.k = kv_cache; c.v = kv_cache; c.o = o; c.lse = lse; c.lens = cache_seqlens; c.block_table = block_table; c.num_pages = num_pages;
+    c.qs = q_strides; c.ks = kv_strides; c.vs = kv_strides; c.os = o_strides; c.ls = lse_strides; c.bts = block_table_stride; c.scale = scale;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = hip_stream;
+    c.sparse = true; c.indices = indices; c.topk = topk; c.is = indices_strides;
+    c.format = FA2_CACHE_E4M3;
     return decode_mla_run(c);
 }
 

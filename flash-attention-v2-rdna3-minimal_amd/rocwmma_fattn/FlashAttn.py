@@ -26,7 +26,8 @@ import torch
 from . import _fa2_lib
 
 __all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
-           "kvcache_append_varlen", "flash_attention_decode_mla", "kvcache_append_mla", "kvcache_append_mla_varlen"]
+           "kvcache_append_varlen", "flash_attention_decode_mla", "kvcache_append_mla", "kvcache_append_mla_varlen", "mla_cache_to_fp8",
+           "mla_cache_from_fp8"]
 
 
 class _FlashAttnWmma:
@@ -1623,6 +1624,42 @@ def kvcache_append_mla_varlen(kv_cache, kv_c, k_pe, cu_seqlens, cache_seqlens, b
 
 
 _MLA_D, _MLA_DV, _MLA_MAX_HEADS, _MLA_MAX_ROWS, _MLA_MAX_SPLITS = 576, 512, 128, 512, 128      # csrc/fa2_decode_mla.hip.h (the split cap: the plan reports it)
+_MLA_FP8_ROW, _MLA_FP8_GROUP, _E4M3_MAX = 656, 128, 448.0      # bytes of an e4m3 latent row (512 codes, 4 f32 scales, 64 rotary columns), columns per scale
+
+
+def mla_cache_to_fp8(kv_cache):
+    """A 16-bit latent cache [.., 576] -> the e4m3 cache flash_attention_decode_mla reads, uint8 [.., 656] (include/fa2_gfx950.h has the row).  Per row
+    and group of 128 columns: scale = amax / 448 in float32 (an all-zero group: 1), code = e4m3(clamp(x / scale, -448, 448)); the 64 rotary columns are
+    copied bit for bit.  Plain torch on the tensor's device: an OFFLINE and TEST utility, not a serving path (the quantising append is not served yet)."""
+    if not torch.is_tensor(kv_cache) or kv_cache.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dim() < 1 or kv_cache.shape[-1] != _MLA_D:
+        raise ValueError("fa2: mla_cache_to_fp8 takes an fp16 or bf16 latent cache [.., %d]" % _MLA_D)
+    lead = tuple(kv_cache.shape[:-1])
+    x = kv_cache[..., :_MLA_DV].float().reshape(lead + (_MLA_DV // _MLA_FP8_GROUP, _MLA_FP8_GROUP))
+    amax = x.abs().amax(-1, keepdim=True)
+    scale = torch.where(amax > 0, amax / _E4M3_MAX, torch.ones_like(amax))
+    codes = (x / scale).clamp(-_E4M3_MAX, _E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8).reshape(lead + (_MLA_DV,))
+    out = torch.empty(lead + (_MLA_FP8_ROW,), dtype=torch.uint8, device=kv_cache.device)
+    out[..., :_MLA_DV] = codes
+    out[..., _MLA_DV:_MLA_DV + 16] = scale.reshape(lead + (4,)).contiguous().view(torch.uint8)
+    out[..., _MLA_DV + 16:] = kv_cache[..., _MLA_DV:].contiguous().view(torch.uint8)
+    return out
+
+
+def mla_cache_from_fp8(cache, dtype):
+    """An e4m3 latent cache, uint8 / float8_e4m3fn [.., 656] -> the 16-bit cache [.., 576] in `dtype` the kernels compute with, by exactly the contract's
+    arithmetic: K[.., c] = (float32(code) * scale[c / 128]) rounded once to `dtype`, the rotary columns bit for bit (`dtype` is the dtype they were
+    stored in).  Plain torch: an OFFLINE and TEST utility — calling it before every decode step is what the e4m3 path of flash_attention_decode_mla saves."""
+    if not torch.is_tensor(cache) or cache.dim() < 1 or cache.shape[-1] != _MLA_FP8_ROW or dtype not in (torch.float16, torch.bfloat16) or \
+            not (cache.dtype == torch.uint8 or (_FP8_CACHE is not None and cache.dtype == _FP8_CACHE)):
+        raise ValueError("fa2: mla_cache_from_fp8 takes a uint8 / float8_e4m3fn latent cache [.., %d] and torch.float16 or torch.bfloat16" % _MLA_FP8_ROW)
+    raw = cache.view(torch.uint8)
+    lead = tuple(raw.shape[:-1])
+    codes = raw[..., :_MLA_DV].contiguous().view(torch.float8_e4m3fn).float().reshape(lead + (_MLA_DV // _MLA_FP8_GROUP, _MLA_FP8_GROUP))
+    scale = raw[..., _MLA_DV:_MLA_DV + 16].contiguous().view(torch.float32).reshape(lead + (4, 1))
+    out = torch.empty(lead + (_MLA_D,), dtype=dtype, device=raw.device)
+    out[..., :_MLA_DV] = (codes * scale).to(dtype).reshape(lead + (_MLA_DV,))
+    out[..., _MLA_DV:] = raw[..., _MLA_DV + 16:].contiguous().view(dtype)
+    return out
 
 
 def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, head_dim_v=512, scale=None, return_lse=False, num_splits=0, kv_c=None, k_pe=None,
@@ -1657,7 +1694,13 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
     named twice counts twice.  -1 padding and every other entry outside that range contribute nothing and are never addressed; a row without a
     valid entry returns zeros (lse -inf); cache rows no valid entry names are never read.  The rows are read in place — no gathered copy — and the
     work per row is topk whatever the lengths.  Every other argument keeps its meaning (num_splits then splits the list), the fused append
-    included; the host reads nothing of the list, so a captured call follows indices changed in place.  C-ABI fa2_fwd_decode_mla_sparse."""
+    included; the host reads nothing of the list, so a captured call follows indices changed in place.  C-ABI fa2_fwd_decode_mla_sparse.
+    An e4m3 latent cache (DeepSeek-V3.2 servers' FP8 KV cache): kv_cache of dtype torch.uint8 or torch.float8_e4m3fn whose last dim is 656 bytes — 512
+    OCP e4m3 codes, four float32 scales (one per 128 columns), the 64 rotary columns in q's dtype (mla_cache_to_fp8 makes one) — in every layout above
+    (3-D or a head axis of 1, contiguous or paged, with or without indices; strides in bytes, multiples of 16; never copied).  The kernels convert
+    each row on its way into LDS, K[j, c] = (float32(code) * scale) rounded once to q's dtype, and compute as on a 16-bit cache: the result equals the
+    call on mla_cache_from_fp8(kv_cache, q.dtype) bit for bit under the same num_splits, and dead rows contribute nothing whatever their bytes hold.
+    kv_c / k_pe / rotary_* with such a cache raise: the quantising append is not served yet.  C-ABI fa2_fwd_decode_mla_fp8, fa2_fwd_decode_mla_sparse_fp8."""
     who = "flash_attention_decode_mla"
     if not all(torch.is_tensor(t) for t in (q, kv_cache, cache_seqlens)) or q.dim() != 4 or kv_cache.dim() not in (3, 4) or \
             (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):
@@ -1665,10 +1708,17 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
                          "cache has a head axis of size 1" % who)
     if torch.is_grad_enabled() and (q.requires_grad or kv_cache.requires_grad):
         raise ValueError("fa2: %s is inference only (an input requires grad)" % who)
-    if isinstance(head_dim_v, bool) or head_dim_v != _MLA_DV or q.shape[3] != _MLA_D or kv_cache.shape[-1] != _MLA_D:
+    if kv_cache.dtype in _FP8_OTHERS:
+        raise ValueError("fa2: %s takes an FP8 latent cache as torch.uint8 or torch.float8_e4m3fn rows of %d bytes (OCP e4m3 codes): e5m2 and the fnuz "
+                         "formats are not served, got %s" % (who, _MLA_FP8_ROW, kv_cache.dtype))
+    fp8 = kv_cache.dtype == torch.uint8 or (_FP8_CACHE is not None and kv_cache.dtype == _FP8_CACHE)
+    if fp8 and kv_cache.shape[-1] != _MLA_FP8_ROW:
+        raise ValueError("fa2: %s takes a uint8 / float8_e4m3fn latent cache as rows of %d bytes (512 e4m3 codes, four float32 scales, 64 rotary columns "
+                         "in q's dtype), got kv_cache %s" % (who, _MLA_FP8_ROW, tuple(kv_cache.shape)))
+    if isinstance(head_dim_v, bool) or head_dim_v != _MLA_DV or q.shape[3] != _MLA_D or (not fp8 and kv_cache.shape[-1] != _MLA_D):
         raise ValueError("fa2: %s serves latent rows of %d columns whose first %d are the value (head_dim_v), got q %s kv_cache %s head_dim_v=%r"
                          % (who, _MLA_D, _MLA_DV, tuple(q.shape), tuple(kv_cache.shape), head_dim_v))
-    if q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
+    if q.dtype not in (torch.float16, torch.bfloat16) or (not fp8 and kv_cache.dtype != q.dtype):
         raise ValueError("fa2: %s takes fp16 or bf16 q and kv_cache of one dtype, got %s %s" % (who, q.dtype, kv_cache.dtype))
     B, Nq, H, D = q.shape
     if B < 1 or Nq < 1 or not 1 <= H <= _MLA_MAX_HEADS or Nq * H > _MLA_MAX_ROWS:
@@ -1682,6 +1732,8 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
                              % (who, B, Nq, "%s %s strides %s on %s" % (indices.dtype, tuple(indices.shape), indices.stride(), indices.device)
                                 if torch.is_tensor(indices) else repr(indices)))
     fused = kv_c is not None or k_pe is not None
+    if fp8 and (fused or rotary_cos is not None or rotary_sin is not None):
+        raise ValueError("fa2: %s on a uint8 / float8_e4m3fn latent cache takes no kv_c / k_pe / rotary_*: the quantising append is not served yet" % who)
     if not fused and (rotary_cos is not None or rotary_sin is not None):
         raise ValueError("fa2: rotary_cos / rotary_sin rotate the appended tokens: %s takes them together with kv_c and k_pe (rotary without an append is "
                          "not served)" % who)
@@ -1694,6 +1746,9 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
         cache = app[0]
         q_rot = _mla_append_launch(*app)      # every check lies above: the append launch, then today's call on the rotated q, on one stream
         q = q if q_rot is None else q_rot
+    elif fp8:                                         # the byte view: strides in bytes, multiples of 16 (_cache_desc's e4m3 rule); never copied
+        kv4 = _mla_kv4(kv_cache.view(torch.uint8))
+        cache = _cache_desc(True, q, B, kv4, kv4, cache_seqlens, block_table, None, None)
     else:
         cache = _cache_desc(False, q, B, _mla_kv4(kv_cache), _mla_kv4(kv_cache), cache_seqlens, block_table, None, None)
     q = _bnhd_ready(q)
@@ -1718,9 +1773,10 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
                 cache.strides[0], _bnhd(o), _fa2_lib.strides2(lse.stride(0), lse.stride(1)), cache.bts, float(scale), num_splits,
                 None if ws is None else ws.data_ptr(), need, stream)
         if indices is None:
-            rc = lib.fa2_fwd_decode_mla(*args)
+            rc = (lib.fa2_fwd_decode_mla_fp8 if fp8 else lib.fa2_fwd_decode_mla)(*args)
         else:
-            rc = lib.fa2_fwd_decode_mla_sparse(*args, indices.data_ptr(), indices.shape[2], _fa2_lib.strides2(indices.stride(0), indices.stride(1)))
+            rc = (lib.fa2_fwd_decode_mla_sparse_fp8 if fp8 else lib.fa2_fwd_decode_mla_sparse)(
+                *args, indices.data_ptr(), indices.shape[2], _fa2_lib.strides2(indices.stride(0), indices.stride(1)))
     _fa2_lib.check(rc)
     return (o, lse * _LN2) if return_lse else o
 

@@ -1,6 +1,6 @@
 """MI355X (gfx950) drop-in for the reference package `rocwmma_fattn` (forward attention path)."""
 
-_LAZY = ("kvcache_append_varlen", "kvcache_append_mla", "kvcache_append_mla_varlen")
+_LAZY = ("kvcache_append_varlen", "kvcache_append_mla", "kvcache_append_mla_varlen", "mla_cache_to_fp8", "mla_cache_from_fp8")
 
 
 def __getattr__(name):

@@ -195,6 +195,12 @@ SYMBOLS = {
     "fa2_fwd_decode_mla_sparse_plan": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(DecodeMlaPlan)]),
     "fa2_fwd_decode_mla_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
     "fa2_decode_mla_sparse_entry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)] * 3),
+    # ... on an e4m3 latent cache of 656-byte rows: the twins' lists (kv_cache the byte cache, kv_strides in bytes); the twins' plan and workspace queries
+    "fa2_fwd_decode_mla_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +
+                               [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fa2_fwd_decode_mla_sparse_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +
+                                      [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_int, _i64p]),
     # KV-cache append: dtype cache_format, k_new v_new k_cache v_cache cache_seqlens block_table, B Hkv Nnew D capacity page_size num_pages, four stride
     # triples, the block-table row stride, q q_out H Nq and their stride triples, cos sin rotary_dtype rotary_dim seqlen_ro row-stride interleaved,
     # k_descale v_descale descale_strides, stream

@@ -778,7 +778,7 @@ int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int
  * A split call leaves normalised f32 rows and log2 LSEs of the live rows in the workspace (an empty part: lse = -inf alone) and the combine kernel of
  * fa2_fwd_decode, at head dim 512, merges them.  No atomics.
  * Writing new tokens into the 576-wide cache is fa2_kvcache_append_mla (its own section, below; fa2_kvcache_append stops at head dim 512 and rotates
- * the LEADING columns).  Not here: e4m3 latents, a window, soft-capping, slopes, a backward. */
+ * the LEADING columns).  e4m3 latents: fa2_fwd_decode_mla_fp8, below.  Not here: a window, soft-capping, slopes, a backward. */
 enum { FA2_KERNEL_HIP_DECODE_MLA = 9 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
 typedef struct fa2_decode_mla_plan_t {
     int kernel;        /* FA2_KERNEL_HIP_DECODE_MLA */
@@ -840,6 +840,37 @@ int fa2_fwd_decode_mla_sparse_plan(int dtype, int B, int H, int Nq, int D, int D
                                    fa2_decode_mla_plan_t* plan);
 size_t fa2_fwd_decode_mla_sparse_workspace_bytes(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, int topk);
 int fa2_decode_mla_sparse_entry(int entry, int64_t len, int Nq, int i, int capacity, int page_size, int* valid, int* page_slot, int* row_in_page);
+
+/* ---- ... on an e4m3 latent cache (the FP8 KV cache of DeepSeek-V3.2 servers: FlashMLA's, vLLM's fp8_ds_mla), dense and sparse.  One row per token,
+ * 656 bytes instead of 1 152:
+ *   bytes   0 .. 511   OCP e4m3 codes of latent columns 0 .. 511 (the part that is also the value)
+ *   bytes 512 .. 527   four little-endian float32 scales; scale g belongs to columns 128 g .. 128 g + 127
+ *   bytes 528 .. 655   the 64 rotary-key columns in the I/O dtype (`dtype`: that of q and o)
+ * The row the kernels compute with is  K[j, c] = rne_io(float(code[j, c]) * scale[j, c / 128])  for c < 512 — one f32 multiply, one round-to-nearest-
+ * even to the I/O dtype —, K[j, 512 + c] = rope[j, c] bit for bit, V[j] = K[j, :512].  Behind that the contracts are fa2_fwd_decode_mla's and
+ * fa2_fwd_decode_mla_sparse's, unchanged, and the arithmetic is theirs (q, o and the MFMAs 16-bit, f32 accumulation): the result equals the twin's on
+ * the dequantised cache BIT FOR BIT under the same num_splits.  A dead row — at or beyond the length; sparse: one no valid entry names — contributes
+ * nothing whatever its 656 bytes hold, 0xFF everywhere (a NaN code, a NaN scale and NaN rotary columns at once) included.
+ * Arguments: the twins' lists.  kv_cache is the byte cache; kv_strides {batch | page, head, row} count BYTES: multiples of 16, the row stride at least
+ * 656; the base 16-byte aligned.  Checked in the twins' order; a row stride below 656 or no multiple of 16: FA2_ERR_BAD_SHAPE (with the strides'
+ * signs, after the head dim); a misaligned base or a batch | page stride that is no multiple of 16: FA2_ERR_ALIGNMENT.
+ * Plan and workspace: fa2_fwd_decode_mla_plan / _workspace_bytes and fa2_fwd_decode_mla_sparse_plan / _workspace_bytes serve BOTH formats (the kernels
+ * sweep the same tiles under the same split rule and leave the same f32 parts), so the bit-for-bit property holds at num_splits = 0 too.
+ * Kernels: the FP8 instantiations of csrc/fa2_decode_mla.hip.h and csrc/fa2_decode_mla_sparse.hip.h — only the staging differs (global -> 24 registers
+ * -> converted into the 16-bit kernels' LDS image).  Writing this cache (the quantising append) is not served yet. */
+int fa2_fwd_decode_mla_fp8(int dtype, const void* q, const void* kv_cache, void* o, float* lse,
+                           const int* cache_seqlens, const int* block_table,
+                           int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages,
+                           const int64_t q_strides[3], const int64_t kv_strides[3], const int64_t o_strides[3],
+                           const int64_t lse_strides[2], int64_t block_table_stride,
+                           float scale, int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fa2_fwd_decode_mla_sparse_fp8(int dtype, const void* q, const void* kv_cache, void* o, float* lse,
+                                  const int* cache_seqlens, const int* block_table,
+                                  int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages,
+                                  const int64_t q_strides[3], const int64_t kv_strides[3], const int64_t o_strides[3],
+                                  const int64_t lse_strides[2], int64_t block_table_stride,
+                                  float scale, int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream,
+                                  const int* indices, int topk, const int64_t indices_strides[2]);
 
 /* ---- KV-cache append: the write side of the decode calls.  One launch writes the K and V rows of Nnew new tokens per sequence into the cache at the
  * key position only the device knows, optionally rotates k (and q) by that position and optionally quantises to e4m3.

@@ -1,7 +1,7 @@
 """Decode attention on a latent (MLA) KV cache: flash_attention_decode_mla against what a holder of such a cache ran before the library had the call,
 same box, interleaved rounds, median of per-round event times with the spread of the rounds beside it (tools/decode_bench.py's method).
 
-    python tools/mla_decode_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX] [--routes mla,torch]
+    python tools/mla_decode_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX] [--routes mla,torch] [--fp8]
 
 Routes
     mla          flash_attention_decode_mla(q, kv_cache, cache_seqlens) on a [B, Nmax, 576] cache (paged rows: [num_pages, 64, 576] under a block table)
@@ -12,7 +12,12 @@ Routes
 Every row prints the valid cache bytes (1 152 per key, once: what a perfect kernel has to read), the time they take at 6.3 TB/s (the achievable HBM rate
 DESIGN section 20 uses) and each route's achieved bytes/s.  A route is called faster only where the gap exceeds the sum of the two spreads.  Each row
 first checks the routes against each other on the timed inputs (fp16 1e-3 + 2e-3 |x|, bf16 8e-3 + 1.6e-2 |x|).  The same cache is read in every
-iteration, so caches up to the 256 MB of Infinity Cache are served from it in every route alike."""
+iteration, so caches up to the 256 MB of Infinity Cache are served from it in every route alike.
+--fp8: rows 2, 3, 5 and 6a on an e4m3 latent cache of 656-byte rows instead, three routes interleaved in one process:
+    mla          (a) the 16-bit call on the 16-bit cache of the same shape
+    deq+mla      (b) mla_cache_from_fp8 over the rows up to the longest length, then the 16-bit call: what a holder of an e4m3 cache ran before
+    mla_fp8      (c) flash_attention_decode_mla on the e4m3 cache itself
+with the floor from the valid bytes at 656 per key; (c) is checked bit for bit against the 16-bit call on the dequantised cache first."""
 import argparse
 import os
 import sys
@@ -24,7 +29,7 @@ import torch  # noqa: E402
 
 from benchlib import close, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
-from rocwmma_fattn.FlashAttn import flash_attention_decode_mla  # noqa: E402
+from rocwmma_fattn.FlashAttn import flash_attention_decode_mla, mla_cache_from_fp8, mla_cache_to_fp8  # noqa: E402
 
 HBM_TBS = 6.3
 D, DV, SCALE = 576, 512, 576 ** -0.5
@@ -118,6 +123,52 @@ def row(out, label, B, H, Nq, keys, dt, paged, rounds, iters, routes):
     sys.stdout.flush()
 
 
+FP8_ROWS = ("2_", "3_", "5_", "6a_")
+
+
+def row_fp8(out, label, B, H, Nq, keys, dt, paged, rounds, iters):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    if isinstance(keys, tuple):
+        lens_h, nmax = torch.randint(keys[0], keys[1] + 1, (B,), generator=g).tolist(), keys[1]
+    else:
+        lens_h, nmax = [keys] * B, keys + 256
+    q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
+    kv = torch.randn((B, nmax, D), device=dev, dtype=dt)
+    lens = torch.tensor(lens_h, dtype=torch.int32, device=dev)
+    used, c8 = max(lens_h), mla_cache_to_fp8(kv)
+    kw = {}
+    if paged:                                          # the same shuffled pages for both caches
+        pool, _, bt = paged_pool(kv.unsqueeze(2), kv.unsqueeze(2), 64, g, lens=lens_h)
+        kv, kw = pool[:, :, 0], dict(block_table=bt)
+        c8 = mla_cache_to_fp8(torch.nan_to_num(kv))
+        used = kv.shape[1]                             # (b) converts whole pages: the pool's live pages are not contiguous
+    fns = {"mla": lambda: flash_attention_decode_mla(q, kv, lens, **kw),
+           "deq+mla": lambda: flash_attention_decode_mla(q, mla_cache_from_fp8(c8[:, :used], dt), lens, **kw),
+           "mla_fp8": lambda: flash_attention_decode_mla(q, c8, lens, **kw)}
+    with torch.no_grad():
+        assert torch.equal(fns["mla_fp8"]().view(torch.int16), fns["deq+mla"]().view(torch.int16)), label + ": the e4m3 call against the dequantised cache"
+        t = interleaved(fns, rounds, iters)
+    valid = sum(lens_h) * 656
+    floor_us = valid / (HBM_TBS * 1e12) * 1e6
+    lines = ["%-20s B%d H%d Nq%d keys %s %s%s  valid e4m3 cache %.1f MB = %.1f us at %.1f TB/s (16-bit: %.1f MB)"
+             % (label, B, H, Nq, keys, "fp16" if dt == F16 else "bf16", " pages of 64" if paged else "", valid / 1e6, floor_us, HBM_TBS, sum(lens_h) * D * 2 / 1e6)]
+    c_med, c_lo, c_hi = t["mla_fp8"]
+    for n, (med, lo, hi) in t.items():
+        rel = ""
+        if n != "mla_fp8":
+            real = abs(med - c_med) > (hi - lo) + (c_hi - c_lo)
+            rel = "  mla_fp8 %.2fx %s (%s the sum of the spreads, %.1f us)" % (max(med / c_med, c_med / med), "faster" if c_med <= med else "SLOWER",
+                                                                              "beyond" if real else "WITHIN", ((hi - lo) + (c_hi - c_lo)) * 1e3)
+        lines.append("    %-12s %9.1f us  (rounds %.1f .. %.1f, spread %.1f us)%s" % (n, med * 1e3, lo * 1e3, hi * 1e3, (hi - lo) * 1e3, rel))
+    for line in lines:
+        print(line)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+    sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -125,6 +176,7 @@ def main():
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--only", default="", help="rows whose label starts with this")
     ap.add_argument("--routes", default="", help="comma-separated routes to time alone (no comparison, no table)")
+    ap.add_argument("--fp8", action="store_true", help="rows 2, 3, 5, 6a on an e4m3 cache: the 16-bit call, dequantise-then-call and the e4m3 call")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mla_decode_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
@@ -135,7 +187,10 @@ def main():
     if out:
         out.write(head + "\n")
     for r in ROWS:
-        if r[0].startswith(a.only):
+        if a.fp8:
+            if r[0].startswith(FP8_ROWS) and r[0].startswith(a.only):
+                row_fp8(out, *r, a.rounds, a.iters)
+        elif r[0].startswith(a.only):
             row(out, *r, a.rounds, a.iters, [n for n in a.routes.split(",") if n])
 
 

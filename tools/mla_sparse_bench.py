@@ -1,7 +1,7 @@
 """Sparse (top-k indexed) decode attention on a latent (MLA) KV cache: flash_attention_decode_mla(indices=) against the routes a holder of such a cache
 had before, same box, interleaved rounds, median of per-round event times with the spread of the rounds beside it (tools/mla_decode_bench.py's method).
 
-    python tools/mla_sparse_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX]
+    python tools/mla_sparse_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX] [--fp8]
 
 Routes
     sparse        flash_attention_decode_mla(q, cache, lens, indices=idx): the selected rows read in place
@@ -10,7 +10,12 @@ Routes
     dense-all     (b) the dense call over the whole cache: a DIFFERENT computation (it attends every key), shown for scale only
 Every row prints (c) the floor: B * Nq * topk * 1 152 bytes at 6.3 TB/s.  A route is called faster only where the gap exceeds the sum of the two
 spreads.  Each row first checks sparse against gather+dense on the timed inputs.  The lists hold topk distinct positions of each sequence, drawn
-uniformly and sorted, as an indexer's top-k is."""
+uniformly and sorted, as an indexer's top-k is.
+--fp8: the contiguous H128 / H16 rows at 4 K and 64 K keys on an e4m3 latent cache of 656-byte rows instead, three routes:
+    sparse        (a) the 16-bit sparse call on the 16-bit cache of the same shape
+    deq+sparse    (b) mla_cache_from_fp8 over the live rows, then the 16-bit sparse call: what a holder of an e4m3 cache ran before
+    sparse_fp8    (c) the sparse call on the e4m3 cache itself (checked bit for bit against (b) first)
+and the floor B * topk * 656 bytes at 6.3 TB/s."""
 import argparse
 import os
 import sys
@@ -22,7 +27,7 @@ import torch  # noqa: E402
 
 from benchlib import close, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
-from rocwmma_fattn.FlashAttn import flash_attention_decode_mla  # noqa: E402
+from rocwmma_fattn.FlashAttn import flash_attention_decode_mla, mla_cache_from_fp8, mla_cache_to_fp8  # noqa: E402
 
 HBM_TBS = 6.3
 D, TOPK, BF16 = 576, 2048, torch.bfloat16
@@ -85,12 +90,45 @@ def row(out, label, B, H, keys, paged, rounds, iters):
     sys.stdout.flush()
 
 
+def row_fp8(out, label, B, H, keys, rounds, iters):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    q = torch.randn((B, 1, H, D), device=dev, dtype=BF16)
+    kv = torch.randn((B, keys, D), device=dev, dtype=BF16)
+    lens = torch.full((B,), keys, dtype=torch.int32, device=dev)
+    idx = torch.stack([torch.randperm(keys, generator=g)[:TOPK].sort().values for _ in range(B)]).to(torch.int32).view(B, 1, TOPK).to(dev)
+    c8 = mla_cache_to_fp8(kv)
+    fns = {"sparse": lambda: flash_attention_decode_mla(q, kv, lens, indices=idx),
+           "deq+sparse": lambda: flash_attention_decode_mla(q, mla_cache_from_fp8(c8, BF16), lens, indices=idx),
+           "sparse_fp8": lambda: flash_attention_decode_mla(q, c8, lens, indices=idx)}
+    with torch.no_grad():
+        assert torch.equal(fns["sparse_fp8"]().view(torch.int16), fns["deq+sparse"]().view(torch.int16)), label + ": the e4m3 call against the dequantised cache"
+        t = interleaved(fns, rounds, iters)
+    floor_us = B * TOPK * 656 / (HBM_TBS * 1e12) * 1e6
+    lines = ["%-24s B%d H%d Nq1 topk %d of %d keys bf16, e4m3 cache  floor %.1f us at %.1f TB/s" % (label, B, H, TOPK, keys, floor_us, HBM_TBS)]
+    c_med, c_lo, c_hi = t["sparse_fp8"]
+    for n, (med, lo, hi) in t.items():
+        rel = ""
+        if n != "sparse_fp8":
+            real = abs(med - c_med) > (hi - lo) + (c_hi - c_lo)
+            rel = "  sparse_fp8 %.2fx %s (%s the sum of the spreads, %.1f us)" % (max(med / c_med, c_med / med), "faster" if c_med <= med else "SLOWER",
+                                                                                 "beyond" if real else "WITHIN", ((hi - lo) + (c_hi - c_lo)) * 1e3)
+        lines.append("    %-13s %9.1f us  (rounds %.1f .. %.1f, spread %.1f us)%s" % (n, med * 1e3, lo * 1e3, hi * 1e3, (hi - lo) * 1e3, rel))
+    for line in lines:
+        print(line)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+    sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--only", default="", help="rows whose label starts with this")
+    ap.add_argument("--fp8", action="store_true", help="H128 / H16 at 4 K and 64 K keys on an e4m3 cache: 16-bit, dequantise-then-call and the e4m3 call")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mla_sparse_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
@@ -101,7 +139,10 @@ def main():
     if out:
         out.write(head + "\n")
     for r in ROWS:
-        if r[0].startswith(a.only):
+        if a.fp8:
+            if not r[4] and r[3] in (4096, 65536) and r[0].startswith(a.only):
+                row_fp8(out, *r[:4], a.rounds, a.iters)
+        elif r[0].startswith(a.only):
             row(out, *r, a.rounds, a.iters)
 
 
