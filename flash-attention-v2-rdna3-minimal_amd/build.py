@@ -105,12 +105,16 @@ UNITS = [
     # (72 registers against 56).
     ("kvappend_mla_hip_f16", "kvappend_mla_hip.cpp", ["-DFA2_TU_BF16=0", "-fhonor-nans", "-fno-slp-vectorize"]),
     ("kvappend_mla_hip_bf16", "kvappend_mla_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans", "-fno-slp-vectorize"]),
+    # ... and the quantising append for an e4m3 latent cache of 656-byte rows: one wave quantises the latent row (a DPP row per scale group), the q rows
+    # are the 16-bit kernel's code (so: its flags)
+    ("kvappend_mla_fp8_hip_f16", "kvappend_mla_fp8_hip.cpp", ["-DFA2_TU_BF16=0", "-fhonor-nans", "-fno-slp-vectorize"]),
+    ("kvappend_mla_fp8_hip_bf16", "kvappend_mla_fp8_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans", "-fno-slp-vectorize"]),
 ]
 FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end of the operator (host-only C++, g++)
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")
 GENERATORS = [os.path.join("gen", "fwd_d128_gen.py"), os.path.join("gen", "fwd_m16_gen.py"), os.path.join("gen", "fwd_m16_d256_gen.py"), os.path.join("gen", "bwd_d128_gen.py"),
               os.path.join("gen", "bwd_dq_m16_gen.py"), os.path.join("gen", "bwd_dkv_m16_gen.py")]
-HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_decode_mla_sweep.h", "fa2_decode_mla_sparse.hip.h", "fa2_decode_mla_sparse_sweep.h", "fa2_kvappend.hip.h", "fa2_kvappend_mla.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
+HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_decode_mla_sweep.h", "fa2_decode_mla_sparse.hip.h", "fa2_decode_mla_sparse_sweep.h", "fa2_kvappend.hip.h", "fa2_kvappend_mla.hip.h", "fa2_kvappend_mla_fp8.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
            os.path.join(INCLUDE, "fa2_gfx950.h"), os.path.join("gen", "isa.py"), os.path.join("gen", "sched.py"), os.path.join("gen", "gen_driver.py")] + GENERATORS
 
 HIPCC_FLAGS = [

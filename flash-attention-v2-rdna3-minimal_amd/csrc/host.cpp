@@ -21,6 +21,7 @@
 #include "fa2_decode_mla.hip.h"      // the latent-cache decode: its constants, the arithmetic the plan shares with the kernel, its launcher
 #include "fa2_decode_mla_sparse.hip.h"      // ... and its sparse (top-k indexed) form
 #include "fa2_kvappend_mla.hip.h"    // ... and its append: the parameter block, the unit -> chunks map, its launcher
+#include "fa2_kvappend_mla_fp8.hip.h"      // ... and the quantising append of its e4m3 form: the launcher
 
 #include <algorithm>
 #include <cmath>
@@ -2140,7 +2141,8 @@ int fa2_kvcache_append_varlen(int dtype, int cache_format, const void* k_new, co
 
 // ---- the append for a latent (MLA) cache: include/fa2_gfx950.h has the contract, csrc/fa2_kvappend_mla.hip.h the kernels, kvappend_mla_hip.cpp their
 // launch.  The call is an AppendCall whose "K" source is kv_c and whose "V" source is k_pe (Hkv = 1, no head stride), both caches the one latent tensor,
-// in the 16-bit format; the checks run in append_run's order and classes.
+// in the 16-bit format or as e4m3 rows of 656 bytes (the _fp8 entries: csrc/fa2_kvappend_mla_fp8.hip.h, strides in bytes); the checks run in append_run's
+// order and classes.
 int fa2_kvappend_mla_chunks(int unit, int halves, int* chunk_a, int* chunk_b) {
     if (!chunk_a || !chunk_b) return FA2_ERR_NULL_POINTER;
     if (unit < 0 || unit >= fa2::kMlaUnits) return FA2_ERR_BAD_SHAPE;
@@ -2157,6 +2159,7 @@ static int append_mla_run(const AppendCall& c, int Dv, bool q_sizes_ok) {
     if (has_q && (!rotary || c.H < 1 || c.H > fa2::kMlaMaxHeads || !q_sizes_ok)) return FA2_ERR_BAD_SHAPE;      // q rows exist to be rotated
     if (rotary && (c.seqlen_ro < 1 || c.ros < 0)) return FA2_ERR_BAD_SHAPE;
     if (c.D != fa2::kMlaD || Dv != fa2::kMlaDv || (rotary && c.rotary_dim != fa2::kMlaRot)) return FA2_ERR_HEAD_DIM;
+    if (c.fp8() && !fa2::mla_fp8_row_stride_ok(c.ks[2])) return FA2_ERR_BAD_SHAPE;      // e4m3 rows: fa2_fwd_decode_mla_fp8's refusal, in its place
     const bool tab32 = c.rotary_dtype == FA2_DTYPE_F32;
     if (!all_aligned16({c.k_new, c.v_new, c.q, c.q_out, c.cos, c.sin}) || !cache_aligned(c) ||
         ((reinterpret_cast<uintptr_t>(c.lens) | reinterpret_cast<uintptr_t>(c.cu)) & 3u) || !strides3_ok(c.kns) || !strides3_ok(c.vns) ||
@@ -2181,6 +2184,7 @@ static int append_mla_run(const AppendCall& c, int Dv, bool q_sizes_ok) {
         if (has_q) { p.qs[i] = c.qs[i]; p.qos[i] = c.qos[i]; }
     }
     p.bts = c.bts; p.ros = c.ros;
+    if (c.fp8()) return fa2::launch_kvappend_mla_fp8(c.dtype == FA2_DTYPE_BF16, p, c.groups, c.packed, (hipStream_t)c.stream);      // (p.ks: bytes)
     return fa2::launch_kvappend_mla(c.dtype == FA2_DTYPE_BF16, p, c.groups, c.packed, (hipStream_t)c.stream);
 }
 
@@ -2193,12 +2197,15 @@ static int append_mla_run(const AppendCall& c, int Dv, bool q_sizes_ok) {
     c.cos = rotary_cos; c.sin = rotary_sin; c.rotary_dtype = rotary_dtype; c.rotary_dim = rotary_dim; c.seqlen_ro = seqlen_ro;                \
     c.ros = rotary_row_stride; c.interleaved = rotary_interleaved; c.stream = hip_stream
 
-int fa2_kvcache_append_mla(int dtype, const void* kv_c, const void* k_pe, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nnew,
-                           int D, int Dv, int capacity, int page_size, int num_pages, const int64_t kv_c_strides[2], const int64_t k_pe_strides[2],
-                           const int64_t kv_strides[3], int64_t block_table_stride, const void* q, void* q_out, int H, int Nq, const int64_t q_strides[3],
-                           const int64_t q_out_strides[3], const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
-                           int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream) {
+// The uniform entry for a cache of `format`: fa2_kvcache_append_mla (16-bit rows of 576 values) and fa2_kvcache_append_mla_fp8 (e4m3 rows of 656 bytes,
+// strides in bytes) are this one body
+static int append_mla_uniform(int format, int dtype, const void* kv_c, const void* k_pe, void* kv_cache, const int* cache_seqlens, const int* block_table, int B,
+                              int Nnew, int D, int Dv, int capacity, int page_size, int num_pages, const int64_t kv_c_strides[2],
+                              const int64_t k_pe_strides[2], const int64_t kv_strides[3], int64_t block_table_stride, const void* q, void* q_out, int H, int Nq,
+                              const int64_t q_strides[3], const int64_t q_out_strides[3], const void* rotary_cos, const void* rotary_sin, int rotary_dtype,
+                              int rotary_dim, int seqlen_ro, int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream) {
     FA2_APPEND_MLA_COMMON(c);
+    c.format = format;
     c.Nnew = Nnew; c.groups = (int64_t)B * Nnew; c.qs = q_strides; c.qos = q_out_strides;
     int64_t st[2][3] = {};                                   // {batch, row} -> {batch, head (none), row}
     if (kv_c_strides) { st[0][0] = kv_c_strides[0]; st[0][2] = kv_c_strides[1]; c.kns = st[0]; }
@@ -2207,13 +2214,14 @@ int fa2_kvcache_append_mla(int dtype, const void* kv_c, const void* k_pe, void* 
 }
 
 // ... its packed (ragged) form: kv_c / k_pe are [total, 512] / [total, 64] with a row stride each, q and q_out [total, H, 576] with {head, row}
-int fa2_kvcache_append_mla_varlen(int dtype, const void* kv_c, const void* k_pe, void* kv_cache, const int* cu_seqlens, const int* cache_seqlens,
-                                  const int* block_table, int B, int64_t total, int D, int Dv, int capacity, int page_size, int num_pages,
-                                  const int64_t kv_c_strides[1], const int64_t k_pe_strides[1], const int64_t kv_strides[3], int64_t block_table_stride,
-                                  const void* q, void* q_out, int H, const int64_t q_strides[2], const int64_t q_out_strides[2], const void* rotary_cos,
-                                  const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride, int rotary_interleaved,
-                                  void* hip_stream) {
+static int append_mla_packed(int format, int dtype, const void* kv_c, const void* k_pe, void* kv_cache, const int* cu_seqlens, const int* cache_seqlens,
+                             const int* block_table, int B, int64_t total, int D, int Dv, int capacity, int page_size, int num_pages,
+                             const int64_t kv_c_strides[1], const int64_t k_pe_strides[1], const int64_t kv_strides[3], int64_t block_table_stride,
+                             const void* q, void* q_out, int H, const int64_t q_strides[2], const int64_t q_out_strides[2], const void* rotary_cos,
+                             const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride, int rotary_interleaved,
+                             void* hip_stream) {
     FA2_APPEND_MLA_COMMON(c);
+    c.format = format;
     c.packed = true; c.cu = cu_seqlens; c.groups = total;
     int64_t st[4][3] = {};
     if (kv_c_strides) { st[0][2] = kv_c_strides[0]; c.kns = st[0]; }
@@ -2222,6 +2230,32 @@ int fa2_kvcache_append_mla_varlen(int dtype, const void* kv_c, const void* k_pe,
     if (q_out_strides) { st[3][1] = q_out_strides[0]; st[3][2] = q_out_strides[1]; c.qos = st[3]; }
     return append_mla_run(c, Dv, true);
 }
+
+#define FA2_APPEND_MLA_UNIFORM_PARAMS                                                                                                              \
+    int dtype, const void *kv_c, const void *k_pe, void *kv_cache, const int *cache_seqlens, const int *block_table, int B, int Nnew, int D, int Dv, \
+        int capacity, int page_size, int num_pages, const int64_t kv_c_strides[2], const int64_t k_pe_strides[2], const int64_t kv_strides[3],     \
+        int64_t block_table_stride, const void *q, void *q_out, int H, int Nq, const int64_t q_strides[3], const int64_t q_out_strides[3],         \
+        const void *rotary_cos, const void *rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro, int64_t rotary_row_stride,                \
+        int rotary_interleaved, void *hip_stream
+#define FA2_APPEND_MLA_UNIFORM_ARGS                                                                                                                \
+    dtype, kv_c, k_pe, kv_cache, cache_seqlens, block_table, B, Nnew, D, Dv, capacity, page_size, num_pages, kv_c_strides, k_pe_strides, kv_strides, \
+        block_table_stride, q, q_out, H, Nq, q_strides, q_out_strides, rotary_cos, rotary_sin, rotary_dtype, rotary_dim, seqlen_ro, rotary_row_stride, \
+        rotary_interleaved, hip_stream
+#define FA2_APPEND_MLA_PACKED_PARAMS                                                                                                               \
+    int dtype, const void *kv_c, const void *k_pe, void *kv_cache, const int *cu_seqlens, const int *cache_seqlens, const int *block_table, int B,  \
+        int64_t total, int D, int Dv, int capacity, int page_size, int num_pages, const int64_t kv_c_strides[1], const int64_t k_pe_strides[1],    \
+        const int64_t kv_strides[3], int64_t block_table_stride, const void *q, void *q_out, int H, const int64_t q_strides[2],                    \
+        const int64_t q_out_strides[2], const void *rotary_cos, const void *rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,           \
+        int64_t rotary_row_stride, int rotary_interleaved, void *hip_stream
+#define FA2_APPEND_MLA_PACKED_ARGS                                                                                                                 \
+    dtype, kv_c, k_pe, kv_cache, cu_seqlens, cache_seqlens, block_table, B, total, D, Dv, capacity, page_size, num_pages, kv_c_strides, k_pe_strides, \
+        kv_strides, block_table_stride, q, q_out, H, q_strides, q_out_strides, rotary_cos, rotary_sin, rotary_dtype, rotary_dim, seqlen_ro,        \
+        rotary_row_stride, rotary_interleaved, hip_stream
+int fa2_kvcache_append_mla(FA2_APPEND_MLA_UNIFORM_PARAMS) { return append_mla_uniform(FA2_CACHE_16BIT, FA2_APPEND_MLA_UNIFORM_ARGS); }
+int fa2_kvcache_append_mla_varlen(FA2_APPEND_MLA_PACKED_PARAMS) { return append_mla_packed(FA2_CACHE_16BIT, FA2_APPEND_MLA_PACKED_ARGS); }
+// ... into an e4m3 latent cache of 656-byte rows: kv_cache the byte cache, kv_strides in bytes (multiples of 16; the row stride: mla_fp8_row_stride_ok)
+int fa2_kvcache_append_mla_fp8(FA2_APPEND_MLA_UNIFORM_PARAMS) { return append_mla_uniform(FA2_CACHE_E4M3, FA2_APPEND_MLA_UNIFORM_ARGS); }
+int fa2_kvcache_append_mla_varlen_fp8(FA2_APPEND_MLA_PACKED_PARAMS) { return append_mla_packed(FA2_CACHE_E4M3, FA2_APPEND_MLA_PACKED_ARGS); }
 
 // ---- chunked prefill against a KV cache: include/fa2_gfx950.h has the contract, csrc/fa2_prefill.h the tile arithmetic, prefill_hip.cpp /
 // prefill_scoremod_hip.cpp the kernels (the FA2_PAGED forms of the packed forward).  One call, described: the entry fills it by field name, the plan

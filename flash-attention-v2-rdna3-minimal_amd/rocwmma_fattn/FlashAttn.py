@@ -1531,12 +1531,19 @@ def _mla_append_prepare(packed, B, kv_cache, kv_c, k_pe, cu_seqlens, cache_seqle
     if kv_c.dim() != rank or k_pe.dim() != rank or kv_cache.dim() not in (3, 4) or (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):
         raise ValueError("fa2: %s takes kv_c %s, k_pe %s and a latent kv_cache [B, Nmax, 576] ([num_pages, page_size, 576] with a block_table); a head "
                          "axis, where there is one, has size 1" % (who, c_layout, pe_layout))
-    if kv_c.shape[-1] != _MLA_DV or k_pe.shape[-1] != _MLA_D - _MLA_DV or kv_cache.shape[-1] != _MLA_D or kv_c.shape[:-1] != k_pe.shape[:-1]:
+    if kv_cache.dtype in _FP8_OTHERS:
+        raise ValueError("fa2: %s takes an FP8 latent cache as torch.uint8 or torch.float8_e4m3fn rows of %d bytes (OCP e4m3 codes): e5m2 and the fnuz "
+                         "formats are not served, got %s" % (who, _MLA_FP8_ROW, kv_cache.dtype))
+    fp8 = kv_cache.dtype == torch.uint8 or (_FP8_CACHE is not None and kv_cache.dtype == _FP8_CACHE)
+    if fp8 and kv_cache.shape[-1] != _MLA_FP8_ROW:
+        raise ValueError("fa2: %s takes a uint8 / float8_e4m3fn latent cache as rows of %d bytes (512 e4m3 codes, four float32 scales, 64 rotary columns "
+                         "in kv_c's dtype), got kv_cache %s" % (who, _MLA_FP8_ROW, tuple(kv_cache.shape)))
+    if kv_c.shape[-1] != _MLA_DV or k_pe.shape[-1] != _MLA_D - _MLA_DV or (not fp8 and kv_cache.shape[-1] != _MLA_D) or kv_c.shape[:-1] != k_pe.shape[:-1]:
         raise ValueError("fa2: %s writes rows of %d columns: %d of kv_c, then %d of k_pe, one row of each per token; got kv_c %s k_pe %s kv_cache %s"
                          % (who, _MLA_D, _MLA_DV, _MLA_D - _MLA_DV, tuple(kv_c.shape), tuple(k_pe.shape), tuple(kv_cache.shape)))
-    if kv_c.dtype not in (torch.float16, torch.bfloat16) or k_pe.dtype != kv_c.dtype or kv_cache.dtype != kv_c.dtype:
-        raise ValueError("fa2: %s takes fp16 or bf16 kv_c, k_pe and kv_cache of one dtype (e4m3 latents are not served), got %s %s %s"
-                         % (who, kv_c.dtype, k_pe.dtype, kv_cache.dtype))
+    if kv_c.dtype not in (torch.float16, torch.bfloat16) or k_pe.dtype != kv_c.dtype or (not fp8 and kv_cache.dtype != kv_c.dtype):
+        raise ValueError("fa2: %s takes fp16 or bf16 kv_c and k_pe of one dtype and a kv_cache of that dtype (or an e4m3 latent cache: uint8 / "
+                         "float8_e4m3fn rows of %d bytes), got %s %s %s" % (who, _MLA_FP8_ROW, kv_c.dtype, k_pe.dtype, kv_cache.dtype))
     if not packed and (kv_c.shape[0] < 1 or kv_c.shape[1] < 1):                       # (a packed token buffer may be empty)
         raise ValueError("fa2: %s needs B, Nnew >= 1, got kv_c %s" % (who, tuple(kv_c.shape)))
     rotary_dim = _rotary_check(k_pe, _MLA_D - _MLA_DV, rotary_cos, rotary_sin)
@@ -1549,8 +1556,8 @@ def _mla_append_prepare(packed, B, kv_cache, kv_c, k_pe, cu_seqlens, cache_seqle
                 not 1 <= q.shape[-2] <= _MLA_MAX_HEADS:
             raise ValueError("fa2: %s takes q %s in kv_c's dtype with 1 .. %d heads, got %s for kv_c %s"
                              % (who, q_layout, _MLA_MAX_HEADS, "%s %s" % (q.dtype, tuple(q.shape)) if torch.is_tensor(q) else repr(q), tuple(kv_c.shape)))
-    kv4 = _mla_kv4(kv_cache)
-    cache = _cache_desc(False, kv_c if lead is None else lead, B, kv4, kv4, cache_seqlens, block_table, None, None, aux=(cu_seqlens,) if packed else ())
+    kv4 = _mla_kv4(kv_cache.view(torch.uint8) if fp8 else kv_cache)        # e4m3: the byte view, strides in bytes (_cache_desc's e4m3 rule); never copied
+    cache = _cache_desc(fp8, kv_c if lead is None else lead, B, kv4, kv4, cache_seqlens, block_table, None, None, aux=(cu_seqlens,) if packed else ())
     extra = tuple(t for t in (kv_c, k_pe, q, rotary_cos, rotary_sin) if t is not None)
     device = kv_cache.device
     if not all(t.is_cuda and t.device == device for t in extra):
@@ -1572,10 +1579,10 @@ def _mla_append_launch(cache, packed, B, kv_c, k_pe, cu_seqlens, q, q_out, rotar
     lib = _fa2_lib.load()
     code = _dtype_code(kv_c)
     if packed:
-        entry, cu, sizes, nq = lib.fa2_kvcache_append_mla_varlen, (cu_seqlens.data_ptr(),), (B, kv_c.shape[0]), ()
+        entry, cu, sizes, nq = (lib.fa2_kvcache_append_mla_varlen_fp8 if cache.fp8 else lib.fa2_kvcache_append_mla_varlen), (cu_seqlens.data_ptr(),), (B, kv_c.shape[0]), ()
         rows, st = (lambda t: (ctypes.c_int64 * 1)(t.stride(0))), _s2
     else:
-        entry, cu, sizes, nq = lib.fa2_kvcache_append_mla, (), (B, kv_c.shape[1]), (kv_c.shape[1] if q is not None else 0,)
+        entry, cu, sizes, nq = (lib.fa2_kvcache_append_mla_fp8 if cache.fp8 else lib.fa2_kvcache_append_mla), (), (B, kv_c.shape[1]), (kv_c.shape[1] if q is not None else 0,)
         rows, st = (lambda t: _I64x2(t.stride(0), t.stride(1))), _bnhd
     q_args = (None, None, 0, *nq, None, None) if q is None else (q.data_ptr(), q_out.data_ptr(), q.shape[-2], *nq, st(q), st(q_out))
     rotary = (None, None, 0, 0, 0, 0)
@@ -1603,8 +1610,16 @@ def kvcache_append_mla(kv_cache, kv_c, k_pe, cache_seqlens, block_table=None, ro
     bit (a caller who rotated it already).  Strided views are fine when the last dim is contiguous, the strides are multiples of 8 elements and the
     storage is 16-byte aligned — the two slices of one [.., 576] projection output go in without a copy; another source is copied, another cache
     raises.  Returns the rotated q (a new tensor; q is not touched; its columns 0 .. 511 bit for bit) when q and the tables are given, else None.
-    The host reads no device value: the call can be captured in a graph.  Not served: e4m3 latents, cache_batch_idx, cache_leftpad, rotary without
-    an append.  C-ABI fa2_kvcache_append_mla."""
+    The host reads no device value: the call can be captured in a graph.  Not served: cache_batch_idx, cache_leftpad, rotary without an append.
+    C-ABI fa2_kvcache_append_mla.
+    An e4m3 latent cache — kv_cache of dtype torch.uint8 or torch.float8_e4m3fn whose last dim is 656 bytes, in every layout above (3-D or a head axis
+    of 1, contiguous or paged; strides in bytes, multiples of 16; never copied) — gets the QUANTISING append: the row at p receives exactly the bytes
+    mla_cache_to_fp8 gives for the 576-column row the 16-bit append would have written there (per 128 columns of kv_c: scale = amax / 448 in float32,
+    an all-zero group 1.0; code = e4m3(clamp(x / scale, -448, 448)); then the four scales; then the 64 rotary columns in kv_c's dtype, rotated as
+    above), and the returned q is the 16-bit append's bit for bit.  A NaN in kv_c is stored as a NaN code.  kv_c, k_pe and q stay fp16 / bf16.  A
+    serving step on such a cache is two calls on one stream — the same two launches the fused form of flash_attention_decode_mla would make:
+        q_rot = kvcache_append_mla(cache8, kv_c, k_pe, lens, ..., q=q);  flash_attention_decode_mla(q_rot, cache8, lens, ...)
+    C-ABI fa2_kvcache_append_mla_fp8."""
     B = kv_c.shape[0] if torch.is_tensor(kv_c) and kv_c.dim() >= 1 else 0
     return _mla_append_launch(*_mla_append_prepare(False, B, kv_cache, kv_c, k_pe, None, cache_seqlens, block_table, rotary_cos, rotary_sin,
                                                    rotary_interleaved, q))
@@ -1617,7 +1632,9 @@ def kvcache_append_mla_varlen(kv_cache, kv_c, k_pe, cu_seqlens, cache_seqlens, b
     [cu[s], cu[s + 1]), Nnew_s may be 0; row cu[s] + i is written at key position len_s - Nnew_s + i.  cu[B] < total is legitimate (a token buffer of a
     fixed, captured size that this step fills partly): rows at or beyond cu[B] belong to no sequence, write nothing, and their q rows come back
     unrotated, bit for bit.  cu_seqlens is device data nobody validated, like the lengths and the block table: an array that is not ascending loses
-    tokens, it moves no write outside the cache.  Everything else is kvcache_append_mla's.  C-ABI fa2_kvcache_append_mla_varlen."""
+    tokens, it moves no write outside the cache.  Everything else is kvcache_append_mla's, its e4m3 latent caches of 656-byte rows included (the
+    quantising append; the packed step is then kvcache_append_mla_varlen followed by the attention call, two launches on one stream).
+    C-ABI fa2_kvcache_append_mla_varlen, fa2_kvcache_append_mla_varlen_fp8."""
     B = _check_cu("cu_seqlens", cu_seqlens)
     return _mla_append_launch(*_mla_append_prepare(True, B, kv_cache, kv_c, k_pe, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin,
                                                    rotary_interleaved, q))
@@ -1630,7 +1647,8 @@ _MLA_FP8_ROW, _MLA_FP8_GROUP, _E4M3_MAX = 656, 128, 448.0      # bytes of an e4m
 def mla_cache_to_fp8(kv_cache):
     """A 16-bit latent cache [.., 576] -> the e4m3 cache flash_attention_decode_mla reads, uint8 [.., 656] (include/fa2_gfx950.h has the row).  Per row
     and group of 128 columns: scale = amax / 448 in float32 (an all-zero group: 1), code = e4m3(clamp(x / scale, -448, 448)); the 64 rotary columns are
-    copied bit for bit.  Plain torch on the tensor's device: an OFFLINE and TEST utility, not a serving path (the quantising append is not served yet)."""
+    copied bit for bit.  Plain torch on the tensor's device: an OFFLINE and TEST utility, not a serving path (that is kvcache_append_mla on the e4m3
+    cache, which writes these bytes)."""
     if not torch.is_tensor(kv_cache) or kv_cache.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dim() < 1 or kv_cache.shape[-1] != _MLA_D:
         raise ValueError("fa2: mla_cache_to_fp8 takes an fp16 or bf16 latent cache [.., %d]" % _MLA_D)
     lead = tuple(kv_cache.shape[:-1])
@@ -1700,7 +1718,9 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
     (3-D or a head axis of 1, contiguous or paged, with or without indices; strides in bytes, multiples of 16; never copied).  The kernels convert
     each row on its way into LDS, K[j, c] = (float32(code) * scale) rounded once to q's dtype, and compute as on a 16-bit cache: the result equals the
     call on mla_cache_from_fp8(kv_cache, q.dtype) bit for bit under the same num_splits, and dead rows contribute nothing whatever their bytes hold.
-    kv_c / k_pe / rotary_* with such a cache raise: the quantising append is not served yet.  C-ABI fa2_fwd_decode_mla_fp8, fa2_fwd_decode_mla_sparse_fp8."""
+    kv_c / k_pe / rotary_* with such a cache raise (the fused form is not served there): a step is two calls on one stream, the same two launches the
+    fused form would make — q_rot = kvcache_append_mla(kv_cache, kv_c, k_pe, cache_seqlens, ..., q=q), the quantising append, then this call on
+    q_rot.  C-ABI fa2_fwd_decode_mla_fp8, fa2_fwd_decode_mla_sparse_fp8."""
     who = "flash_attention_decode_mla"
     if not all(torch.is_tensor(t) for t in (q, kv_cache, cache_seqlens)) or q.dim() != 4 or kv_cache.dim() not in (3, 4) or \
             (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):

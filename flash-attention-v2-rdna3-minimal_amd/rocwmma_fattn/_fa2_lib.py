@@ -247,6 +247,9 @@ SYMBOLS = {
     "fa2_error_string": (ctypes.c_char_p, [ctypes.c_int]),
     "fa2_version": (ctypes.c_char_p, []),
 }
+# the quantising appends for an e4m3 latent cache of 656-byte rows: their twins' argument lists (the cache pointer: bytes, its strides: bytes)
+SYMBOLS["fa2_kvcache_append_mla_fp8"] = SYMBOLS["fa2_kvcache_append_mla"]
+SYMBOLS["fa2_kvcache_append_mla_varlen_fp8"] = SYMBOLS["fa2_kvcache_append_mla_varlen"]
 
 _lib = None
 WS_CACHE = {}        # FlashAttn.py: shape -> workspace bytes, valid for the current option values (dropped whenever an option is set here)

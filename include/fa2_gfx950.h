@@ -857,7 +857,7 @@ int fa2_decode_mla_sparse_entry(int entry, int64_t len, int Nq, int i, int capac
  * Plan and workspace: fa2_fwd_decode_mla_plan / _workspace_bytes and fa2_fwd_decode_mla_sparse_plan / _workspace_bytes serve BOTH formats (the kernels
  * sweep the same tiles under the same split rule and leave the same f32 parts), so the bit-for-bit property holds at num_splits = 0 too.
  * Kernels: the FP8 instantiations of csrc/fa2_decode_mla.hip.h and csrc/fa2_decode_mla_sparse.hip.h — only the staging differs (global -> 24 registers
- * -> converted into the 16-bit kernels' LDS image).  Writing this cache (the quantising append) is not served yet. */
+ * -> converted into the 16-bit kernels' LDS image).  Writing this cache: fa2_kvcache_append_mla_fp8 (the quantising append, below). */
 int fa2_fwd_decode_mla_fp8(int dtype, const void* q, const void* kv_cache, void* o, float* lse,
                            const int* cache_seqlens, const int* block_table,
                            int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_pages,
@@ -979,7 +979,8 @@ int fa2_rotary_eval(int dtype, const void* x, const float* cos_row, const float*
  * whether or not that token's latent row was written.  q itself is not touched.
  * Checked in fa2_kvcache_append's order: null pointers, sizes (FA2_ERR_BAD_SHAPE: B, Nnew, D, Dv < 1, page_size, H outside 1 .. 128, Nq != Nnew, q
  * without tables, seqlen_ro < 1, a negative table stride), head dim (FA2_ERR_HEAD_DIM: D != 576, Dv != 512, rotary_dim != 64), alignment, dtype,
- * FA2_ERR_GRID (B * Nnew above 2^31 - 1).  There is no cache_format and there are no descales: e4m3 latents are not served.
+ * FA2_ERR_GRID (B * Nnew above 2^31 - 1).  There is no cache_format and there are no descales: e4m3 latents have entries of their own
+ * (fa2_kvcache_append_mla_fp8, below).
  * Kernel (csrc/fa2_kvappend_mla.hip.h): fa2_kvcache_append's decomposition with R = 1 + H rows of 36 units; a unit is two 16-byte chunks of a row's
  * 72 — fa2_kvappend_mla_chunks is the host side of that one map: (2u, 2u + 1), or with halves != 0 (a rotated GPT-NeoX tail) (64 + c, 68 + c) for
  * unit 32 + c.  FA2_ERR_NULL_POINTER; FA2_ERR_BAD_SHAPE for a unit outside [0, 36). */
@@ -1004,6 +1005,43 @@ int fa2_kvcache_append_mla_varlen(int dtype, const void* kv_c, const void* k_pe,
                                   const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
                                   int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream);
 int fa2_kvappend_mla_chunks(int unit, int halves, int* chunk_a, int* chunk_b);
+
+/* ---- ... into an e4m3 latent cache of 656-byte rows (fa2_fwd_decode_mla_fp8's, above): the QUANTISING append, uniform and packed.  New token (b, i)
+ * sits at key position p = len_b - Nnew + i, and its cache row receives exactly the bytes the 16-bit append's 576-column row would quantise to:
+ *   bytes   0 .. 511   for each group g of 128 columns of kv_c[b, i, :]: amax_g = max |x|, scale_g = amax_g / 448 in float32 (the correctly rounded
+ *                      division; an all-zero group: 1.0f), code = rne_e4m3(clamp(float(x) / scale_g, -448, 448)) — again the correctly rounded
+ *                      division, no reciprocal multiply;
+ *   bytes 512 .. 527   the four scales, little-endian float32;
+ *   bytes 528 .. 655   k_pe[b, i, :] in the I/O dtype: rotated by table row clamp(p, 0, seqlen_ro - 1) exactly as fa2_kvcache_append_mla rotates it
+ *                      (csrc/fa2_rotary.h's f32 arithmetic, one rounding, either pairing), copied bit for bit without tables.
+ * q_out is fa2_kvcache_append_mla's, bit for bit, whether or not the latent row was written.  Everything else is that call's contract, word for word:
+ * skipped tokens (p outside the cache, a page id outside [0, num_pages)) are never clamped onto a live row, a packed token no sequence owns writes no
+ * row and its q row is copied, no device value moves an access outside its tensors, addressing is 64-bit, the host reads nothing from the device (graph
+ * capture).  A NaN in kv_c is stored as an e4m3 NaN code (0x7F / 0xFF); the group's other codes and its scale are those of the group without it.
+ * +-Inf is not specified (the kernel: a scale of Inf, zeros for the group's finite elements, a NaN code for the Inf).
+ * Arguments: the twins' lists.  kv_cache is the byte cache; kv_strides {batch | page, head, row} count BYTES: multiples of 16 (FA2_ERR_ALIGNMENT), the
+ * row stride at least 656 (FA2_ERR_BAD_SHAPE where fa2_fwd_decode_mla_fp8 gives it: after the head dim, before the alignment); the base 16-byte
+ * aligned.  dtype is the I/O dtype of kv_c, k_pe, q, q_out and the rotary columns.  Checked in the twins' order; total == 0 returns FA2_OK without a
+ * launch.
+ * Kernel (csrc/fa2_kvappend_mla_fp8.hip.h): the twins' grid.  The first wave of a token's workgroup quantises the latent row — lane l one 16-byte chunk
+ * of kv_c, the 16 lanes of a scale group one DPP row whose four-step all-reduce gives the amax, 8 code bytes per lane, the four scales by readlane —
+ * and four of its lanes move the rotary tail; the q rows are the 16-bit kernel's units, lanes and code. */
+int fa2_kvcache_append_mla_fp8(int dtype, const void* kv_c, const void* k_pe, void* kv_cache,
+                               const int* cache_seqlens, const int* block_table,
+                               int B, int Nnew, int D, int Dv, int capacity, int page_size, int num_pages,
+                               const int64_t kv_c_strides[2], const int64_t k_pe_strides[2],
+                               const int64_t kv_strides[3], int64_t block_table_stride,
+                               const void* q, void* q_out, int H, int Nq, const int64_t q_strides[3], const int64_t q_out_strides[3],
+                               const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
+                               int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream);
+int fa2_kvcache_append_mla_varlen_fp8(int dtype, const void* kv_c, const void* k_pe, void* kv_cache,
+                                      const int* cu_seqlens, const int* cache_seqlens, const int* block_table,
+                                      int B, int64_t total, int D, int Dv, int capacity, int page_size, int num_pages,
+                                      const int64_t kv_c_strides[1], const int64_t k_pe_strides[1],
+                                      const int64_t kv_strides[3], int64_t block_table_stride,
+                                      const void* q, void* q_out, int H, const int64_t q_strides[2], const int64_t q_out_strides[2],
+                                      const void* rotary_cos, const void* rotary_sin, int rotary_dtype, int rotary_dim, int seqlen_ro,
+                                      int64_t rotary_row_stride, int rotary_interleaved, void* hip_stream);
 
 /* Head dims the forward kernels are instantiated for (ascending).  Writes up to `cap` entries into `dims`, returns
  * the total count.  Any D that is a multiple of 8 runs on the next of these with its tail columns masked; only a D

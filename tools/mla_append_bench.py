@@ -3,7 +3,7 @@ library's append launch against the route a caller had before it, same box, inte
 rounds beside it (tools/kvappend_bench.py's protocol: 9 rounds of 20 calls, spread = (max - min) / median; a gap counts only beyond the sum of the
 two spreads).
 
-    python tools/mla_append_bench.py [--rounds R] [--iters I] [--rows step|packed|all]
+    python tools/mla_append_bench.py [--rounds R] [--iters I] [--rows step|packed|all] [--fp8]
 
 Step rows (cache_seqlens counts the new tokens; every sequence has `keys` keys after the append):
     fused        flash_attention_decode_mla(q, ..., kv_c=, k_pe=, rotary_cos=, rotary_sin=): the append launch, then the decode call on the rotated q
@@ -15,7 +15,15 @@ Each of the four is timed eagerly and, with a "/g" suffix, as a replayed graph. 
 inputs (caches and outputs within fp16 1e-3 + 2e-3 |x|, bf16 8e-3 + 1.6e-2 |x|).  The append lines carry the GB/s of the valid bytes: the latent rows
 read and written, the q rows both ways, the table rows (1 GB/s is 1 000 bytes per microsecond).
 Packed row: a continuous-batching step of 24 single-token rows and 4 chunks of 384 tokens: kvcache_append_mla_varlen (one launch) against a loop of
-per-sequence kvcache_append_mla calls (28 launches), eager and replayed."""
+per-sequence kvcache_append_mla calls (28 launches), eager and replayed.
+--fp8: the same rows on an e4m3 latent cache of 656-byte rows, three routes interleaved per step row:
+    step16       kvcache_append_mla then flash_attention_decode_mla on a 16-bit cache (the launches of `fused`)
+    torch8       what a holder of an e4m3 cache ran before the quantising append: torch positions and rotation, mla_cache_to_fp8 of the new rows,
+                 index_put_ into the byte cache, then the e4m3 decode
+    step8        kvcache_append_mla on the e4m3 cache (the quantising append), then the e4m3 decode — its output first checked against torch8's within
+                 the tool's tolerance (torch on the device divides by the scalar 448 as a multiply by a reciprocal and rotates without an fma: its
+                 bytes are not the contract's; the cache bytes that differ are counted and printed)
+and the packed append alone on both caches, with the bytes per microsecond of its valid bytes (1 152 read and 656 or 1 152 written per token, plus q)."""
 import argparse
 import os
 import sys
@@ -27,7 +35,7 @@ import torch  # noqa: E402
 
 from benchlib import close, graphed, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
-from rocwmma_fattn.FlashAttn import flash_attention_decode_mla, kvcache_append_mla, kvcache_append_mla_varlen  # noqa: E402
+from rocwmma_fattn.FlashAttn import flash_attention_decode_mla, kvcache_append_mla, kvcache_append_mla_varlen, mla_cache_from_fp8, mla_cache_to_fp8  # noqa: E402
 
 D, DV, ROT = 576, 512, 64
 STEP_ROWS = [  # (label, B, H, Nq, keys, page)
@@ -52,8 +60,9 @@ def rotate(x, cos, sin):
     return torch.stack((x1 * cos - x2 * sin, x1 * sin + x2 * cos), dim=-1).flatten(-2)
 
 
-def torch_append(q, kv_c, k_pe, cache, lens, bt, cos, sin):
-    """The route before the append launch: positions, page slots, rotation, cat and the cache write as torch ops on device tensors -> the rotated q"""
+def torch_append(q, kv_c, k_pe, cache, lens, bt, cos, sin, quantise=False):
+    """The route before the append launch: positions, page slots, rotation, cat and the cache write as torch ops on device tensors -> the rotated q.
+    quantise: the cache holds 656-byte e4m3 rows, and the new rows go through mla_cache_to_fp8 on their way"""
     B, N = kv_c.shape[:2]
     pos = lens.long()[:, None] - N + torch.arange(N, device=kv_c.device)[None, :]
     rows = pos.clamp(0, cos.shape[0] - 1)
@@ -65,7 +74,7 @@ def torch_append(q, kv_c, k_pe, cache, lens, bt, cos, sin):
     else:
         page = cache.shape[1]
         idx = (bt.gather(1, pos // page).long(), pos % page)
-    cache.index_put_(idx, row)
+    cache.index_put_(idx, mla_cache_to_fp8(row) if quantise else row)
     return q_rot
 
 
@@ -127,6 +136,96 @@ def step_row(label, B, H, Nq, keys, page, rounds, iters):
     sys.stdout.flush()
 
 
+def fp8_step_row(label, B, H, Nq, keys, page, rounds, iters):
+    dev, dt = torch.device("cuda", 0), torch.bfloat16
+    g = torch.Generator(device="cpu").manual_seed(4)
+    nmax = keys + 256
+    q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
+    proj = torch.randn((B, Nq, D), device=dev, dtype=dt)
+    kv_c, k_pe = proj[..., :DV], proj[..., DV:]
+    cache = torch.randn((B, nmax, D), device=dev, dtype=dt)
+    bt = None
+    if page:
+        pool, _, bt = paged_pool(cache.unsqueeze(2), cache.unsqueeze(2), page, g)
+        cache = pool[:, :, 0].contiguous()
+    lens = torch.full((B,), keys, dtype=torch.int32, device=dev)
+    cos, sin = tables(nmax, dev)
+    c8 = mla_cache_to_fp8(cache)
+    c8t = c8.clone()
+
+    def step16():
+        return flash_attention_decode_mla(kvcache_append_mla(cache, kv_c, k_pe, lens, block_table=bt, rotary_cos=cos, rotary_sin=sin, q=q), cache, lens, block_table=bt)
+
+    def torch8():
+        return flash_attention_decode_mla(torch_append(q, kv_c, k_pe, c8t, lens, bt, cos, sin, quantise=True), c8t, lens, block_table=bt)
+
+    def step8():
+        return flash_attention_decode_mla(kvcache_append_mla(c8, kv_c, k_pe, lens, block_table=bt, rotary_cos=cos, rotary_sin=sin, q=q), c8, lens, block_table=bt)
+
+    def append8():
+        return kvcache_append_mla(c8, kv_c, k_pe, lens, block_table=bt, rotary_cos=cos, rotary_sin=sin, q=q)
+
+    def append16():
+        return kvcache_append_mla(cache, kv_c, k_pe, lens, block_table=bt, rotary_cos=cos, rotary_sin=sin, q=q)
+
+    with torch.no_grad():
+        close("mla_append_bench", step8(), torch8(), dt, label + ": step8 and torch8 outputs")
+        # not bit for bit: torch on the device divides by the scalar 448 as a multiply by its reciprocal, so its scales may sit one ulp off the contract's
+        # and a code on a rounding boundary then lands one e4m3 step away (the library's bytes are held to the CPU's mla_cache_to_fp8 in
+        # tests/test_kvappend_mla_fp8_gpu.py).  The outputs agree (above); the differing cache bytes are counted and printed.
+        diff = int((c8 != c8t).sum())
+        fns = {"step16": step16, "torch8": torch8, "step8": step8, "append16": append16, "append8": append8}
+        fns.update({n + "/g": graphed(f) for n, f in list(fns.items())})
+        t = interleaved(fns, rounds, iters)
+    q_bytes = 2 * H * D * 2 + 2 * (ROT // 2) * 4
+    own8, own16 = B * Nq * (D * 2 + 656 + q_bytes), B * Nq * (2 * D * 2 + q_bytes)
+    print("%-14s B%d H%d Nq%d keys %d bf16 %s, e4m3 cache of 656-byte rows; %d bytes of the cache differ from the torch route's"
+          % (label, B, H, Nq, keys, "pages of %d" % page if page else "contiguous", diff))
+    for sfx in ("", "/g"):
+        print(line("step8" + sfx, t, "torch8" + sfx))
+        print(line("step8" + sfx, t, "step16" + sfx))
+        print(line("torch8" + sfx, t))
+        print(line("step16" + sfx, t))
+        print(line("append8" + sfx, t, "append16" + sfx, "  %.0f bytes/us of its valid bytes" % (own8 / (t["append8" + sfx][0] * 1e3))))
+        print(line("append16" + sfx, t, None, "  %.0f bytes/us of its valid bytes" % (own16 / (t["append16" + sfx][0] * 1e3))))
+    sys.stdout.flush()
+
+
+def fp8_packed_row(rounds, iters):
+    dev, dt, H, keys = torch.device("cuda", 0), torch.bfloat16, 16, 4096
+    counts = PACKED_COUNTS
+    B, total, nmax = len(counts), sum(counts), keys + 256
+    cu = torch.tensor([sum(counts[:s]) for s in range(B + 1)], dtype=torch.int32, device=dev)
+    proj = torch.randn((total, D), device=dev, dtype=dt)
+    kv_c, k_pe = proj[:, :DV], proj[:, DV:]
+    q = torch.randn((total, H, D), device=dev, dtype=dt)
+    cache = torch.zeros((B, nmax, D), device=dev, dtype=dt)
+    c8 = mla_cache_to_fp8(cache)
+    lens = torch.tensor([keys if c == 1 else 2048 for c in counts], dtype=torch.int32, device=dev)
+    cos, sin = tables(nmax, dev)
+
+    def packed16():
+        return kvcache_append_mla_varlen(cache, kv_c, k_pe, cu, lens, rotary_cos=cos, rotary_sin=sin, q=q)
+
+    def packed8():
+        return kvcache_append_mla_varlen(c8, kv_c, k_pe, cu, lens, rotary_cos=cos, rotary_sin=sin, q=q)
+
+    with torch.no_grad():
+        qa, qb = packed16(), packed8()
+        if not torch.equal(qa.view(torch.int16), qb.view(torch.int16)) or not torch.equal(c8.cpu(), mla_cache_to_fp8(cache.cpu())):
+            raise SystemExit("mla_append_bench: the quantising packed append is not mla_cache_to_fp8 (on the CPU) of the 16-bit one")
+        fns = {"packed16": packed16, "packed8": packed8}
+        fns.update({n + "/g": graphed(f) for n, f in list(fns.items())})
+        t = interleaved(fns, rounds, iters)
+    q_bytes = 2 * H * D * 2 + 2 * (ROT // 2) * 4
+    own8, own16 = total * (D * 2 + 656 + q_bytes), total * (2 * D * 2 + q_bytes)
+    print("%-14s 24 single-token rows + 4 chunks of 384 (%d tokens, %d sequences) H%d bf16 contiguous, the append alone" % ("packed_step", total, B, H))
+    for sfx in ("", "/g"):
+        print(line("packed8" + sfx, t, "packed16" + sfx, "  %.0f bytes/us of its valid bytes" % (own8 / (t["packed8" + sfx][0] * 1e3))))
+        print(line("packed16" + sfx, t, None, "  %.0f bytes/us of its valid bytes" % (own16 / (t["packed16" + sfx][0] * 1e3))))
+    sys.stdout.flush()
+
+
 def packed_row(rounds, iters):
     dev, dt, H, keys = torch.device("cuda", 0), torch.bfloat16, 16, 4096
     counts = PACKED_COUNTS
@@ -170,15 +269,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rows", default="all", choices=("step", "packed", "all"))
+    ap.add_argument("--fp8", action="store_true", help="the rows on an e4m3 latent cache of 656-byte rows: the quantising append against the routes before it")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mla_append_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
     print(torch.cuda.get_device_name(0), "rounds", a.rounds, "iters", a.iters, "|", _fa2_lib.load().fa2_version().decode())
     if a.rows in ("step", "all"):
         for r in STEP_ROWS:
-            step_row(*r, a.rounds, a.iters)
+            (fp8_step_row if a.fp8 else step_row)(*r, a.rounds, a.iters)
     if a.rows in ("packed", "all"):
-        packed_row(a.rounds, a.iters)
+        (fp8_packed_row if a.fp8 else packed_row)(a.rounds, a.iters)
 
 
 if __name__ == "__main__":
