@@ -20,6 +20,8 @@
 #include "fa2_dropout.h"
 #include "fa2_decode_mla.hip.h"      // the latent-cache decode: its constants, the arithmetic the plan shares with the kernel, its launcher
 #include "fa2_decode_mla_sparse.hip.h"      // ... and its sparse (top-k indexed) form
+#include "fa2_mla_indexer.hip.h"     // ... the indexer that names the sparse form's lists: the logits kernel's parameter block and launcher
+#include "fa2_topk_select.hip.h"     // ... and the selection behind it
 #include "fa2_kvappend_mla.hip.h"    // ... and its append: the parameter block, the unit -> chunks map, its launcher
 #include "fa2_kvappend_mla_fp8.hip.h"      // ... and the quantising append of its e4m3 form: the launcher
 
@@ -1997,6 +1999,49 @@ int fa2_decode_mla_sparse_entry(int entry, int64_t len, int Nq, int i, int capac
     const fa2::MlaSparseEntry e = fa2::mla_sparse_entry(entry, (int64_t)fa2::decode_clamp_len(len, cap) - Nq + i, fa2::mla_page_keys(page_size, cap));
     *valid = e.valid; *page_slot = e.slot; *row_in_page = e.row;
     return FA2_OK;
+}
+
+// ---- the lightning indexer of sparse MLA decode: the logits over an index-key cache (csrc/fa2_mla_indexer.hip.h), then the
+// top-k selection that writes fa2_fwd_decode_mla_sparse's indices (csrc/fa2_topk_select.hip.h).  The checks run in the documented order.
+int fa2_mla_indexer_logits(int dtype, const void* q_idx, const void* k_idx_cache, const float* weights, float* logits, const int* cache_seqlens,
+                           const int* block_table, int B, int H_idx, int Nq, int D_idx, int capacity, int page_size, int num_pages,
+                           const int64_t q_strides[3], const int64_t k_strides[2], const int64_t w_strides[2], const int64_t logits_strides[2],
+                           int64_t block_table_stride, void* hip_stream) {
+    if (any_null({q_idx, k_idx_cache, weights, logits, cache_seqlens, q_strides, k_strides, w_strides, logits_strides}) || (page_size > 0 && !block_table))
+        return FA2_ERR_NULL_POINTER;
+    CacheDesc c;
+    c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    if (B < 1 || H_idx < 1 || Nq < 1 || D_idx < 1 || !cache_paging_ok(c) || c.capacity_keys() > 0x7fffffffLL - 64 || !cache_extent_ok(c)) return FA2_ERR_BAD_SHAPE;
+    if (w_strides[0] < 0 || w_strides[1] < 0 || logits_strides[0] < 0 || logits_strides[1] < 0 || block_table_stride < 0) return FA2_ERR_BAD_SHAPE;
+    if (!fa2::mla_indexer_heads_ok(H_idx) || D_idx != fa2::kIdxD) return FA2_ERR_HEAD_DIM;
+    if (!all_aligned16({q_idx, k_idx_cache}) || !strides3_ok(q_strides) || k_strides[0] < 0 || k_strides[0] % 8 != 0 || k_strides[1] < 1 || k_strides[1] % 8 != 0 ||
+        ((reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(cache_seqlens) |
+          reinterpret_cast<uintptr_t>(block_table)) & 3u))
+        return FA2_ERR_ALIGNMENT;
+    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    if (B > 65535 || Nq > 65535) return FA2_ERR_GRID;
+    fa2::MlaIndexerParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = q_idx; p.k = k_idx_cache; p.w = weights; p.logits = logits; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr;
+    p.B = B; p.H = H_idx; p.Nq = Nq; p.page_size = page_size; p.num_pages = num_pages; p.capacity_keys = c.capacity_keys();
+    for (int i = 0; i < 3; ++i) p.qs[i] = q_strides[i];
+    for (int i = 0; i < 2; ++i) { p.ks[i] = k_strides[i]; p.ws[i] = w_strides[i]; p.ls[i] = logits_strides[i]; }
+    p.bts = block_table_stride;
+    return fa2::launch_mla_indexer_logits(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
+}
+
+int fa2_topk_indices(const float* logits, int* indices, const int* cache_seqlens, int B, int Nq, int capacity, int topk, const int64_t logits_strides[2],
+                     const int64_t indices_strides[2], void* hip_stream) {
+    if (any_null({logits, indices, cache_seqlens, logits_strides, indices_strides})) return FA2_ERR_NULL_POINTER;
+    if (B < 1 || Nq < 1 || capacity < 1 || capacity > 0x7fffffff - 64 || topk < 1 || topk > 0x7fffffff - 64) return FA2_ERR_BAD_SHAPE;
+    if (logits_strides[0] < 0 || logits_strides[1] < 0 || indices_strides[0] < 0 || indices_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(indices) | reinterpret_cast<uintptr_t>(cache_seqlens)) & 3u) return FA2_ERR_ALIGNMENT;
+    if ((int64_t)B * Nq > 0x7fffffffLL) return FA2_ERR_GRID;
+    fa2::TopkParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.logits = logits; p.idx = indices; p.lens = cache_seqlens; p.B = B; p.Nq = Nq; p.topk = topk; p.capacity_keys = capacity;
+    for (int i = 0; i < 2; ++i) { p.ls[i] = logits_strides[i]; p.is[i] = indices_strides[i]; }
+    return fa2::launch_topk_select(p, (hipStream_t)hip_stream);
 }
 
 // ---- KV-cache append with rotary embedding and e4m3 quantisation: include/fa2_gfx950.h has the contract, csrc/fa2_kvappend.hip.h the kernel,

@@ -27,7 +27,7 @@ from . import _fa2_lib
 
 __all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
            "kvcache_append_varlen", "flash_attention_decode_mla", "kvcache_append_mla", "kvcache_append_mla_varlen", "mla_cache_to_fp8",
-           "mla_cache_from_fp8"]
+           "mla_cache_from_fp8", "mla_indexer_logits", "topk_indices", "mla_indexer_topk"]
 
 
 class _FlashAttnWmma:
@@ -1799,6 +1799,140 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
                 *args, indices.data_ptr(), indices.shape[2], _fa2_lib.strides2(indices.stride(0), indices.stride(1)))
     _fa2_lib.check(rc)
     return (o, lse * _LN2) if return_lse else o
+
+
+_IDX_D = 128                       # the index head dim
+_IDX_HEADS = (16, 32, 48, 64)      # indexer head counts with a kernel (DeepSeek-V3.2: 64)
+_TOPK_MAX = 2 ** 31 - 1 - 64
+
+
+def _no_grad_inputs(who, *tensors):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise ValueError("fa2: %s is inference only (an input requires grad)" % who)
+
+
+def _check_lens(who, cache_seqlens, B, device):
+    if not torch.is_tensor(cache_seqlens) or cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous() or \
+            cache_seqlens.device != device:
+        raise ValueError("fa2: %s takes cache_seqlens as a contiguous int32 tensor [B] = [%d] on the inputs' device" % (who, B))
+
+
+def _check_topk(who, topk):
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= _TOPK_MAX:
+        raise ValueError("fa2: %s takes topk as an int in 1 .. 2^31 - 65, got %r" % (who, topk))
+
+
+def _indexer_prepare(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table):
+    """Every argument check of mla_indexer_logits; nothing is launched here.  -> (q_idx, k [.., .., 128], weights, capacity, page_size, num_pages)"""
+    if not all(torch.is_tensor(t) for t in (q_idx, k_idx_cache, weights, cache_seqlens)) or q_idx.dim() != 4 or k_idx_cache.dim() not in (3, 4) or \
+            (k_idx_cache.dim() == 4 and k_idx_cache.shape[2] != 1) or weights.dim() != 3:
+        raise ValueError("fa2: %s takes q_idx [B, Nq, H_idx, 128], an index-key cache [B, Nmax, 128] ([num_pages, page_size, 128] with a block_table; a 4-D "
+                         "cache has a head axis of size 1), weights [B, Nq, H_idx] and cache_seqlens [B]" % who)
+    _no_grad_inputs(who, q_idx, k_idx_cache, weights)
+    if q_idx.dtype not in (torch.float16, torch.bfloat16) or k_idx_cache.dtype != q_idx.dtype or weights.dtype != torch.float32:
+        raise ValueError("fa2: %s takes fp16 or bf16 q_idx and k_idx_cache of one dtype and float32 weights, got %s %s %s"
+                         % (who, q_idx.dtype, k_idx_cache.dtype, weights.dtype))
+    B, Nq, H, D = q_idx.shape
+    if D != _IDX_D or k_idx_cache.shape[-1] != _IDX_D:
+        raise ValueError("fa2: %s serves index rows of %d columns, got q_idx %s k_idx_cache %s" % (who, _IDX_D, tuple(q_idx.shape), tuple(k_idx_cache.shape)))
+    if H not in _IDX_HEADS or B < 1 or not 1 <= Nq <= 65535 or tuple(weights.shape) != (B, Nq, H):
+        raise ValueError("fa2: %s serves H_idx in %s with weights [B, Nq, H_idx] (B >= 1, Nq in 1 .. 65535), got q_idx %s weights %s"
+                         % (who, _IDX_HEADS, tuple(q_idx.shape), tuple(weights.shape)))
+    k = k_idx_cache if k_idx_cache.dim() == 3 else k_idx_cache[:, :, 0]
+    if block_table is None:
+        if k.shape[0] != B:
+            raise ValueError("fa2: a contiguous index-key cache is [B, Nmax, 128] with B = %d sequences, got %s (a paged cache needs its block_table)"
+                             % (B, tuple(k_idx_cache.shape)))
+        capacity, page_size, num_pages = k.shape[1], 0, 0
+    else:
+        if not torch.is_tensor(block_table) or block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != B or \
+                block_table.shape[1] < 1 or block_table.stride(1) != 1 or block_table.device != q_idx.device:
+            raise ValueError("fa2: block_table must be int32 [B, max_pages] with B = %d sequences and contiguous rows on q_idx's device" % B)
+        capacity, page_size, num_pages = block_table.shape[1], k.shape[1], k.shape[0]
+        if page_size < 64 or page_size % 64 or num_pages < 1:
+            raise ValueError("fa2: the page size of a paged cache (k_idx_cache.shape[1]) must be a multiple of 64 and the pool must hold a page, got %s"
+                             % (tuple(k_idx_cache.shape),))
+    if capacity < 1 or capacity * max(page_size, 1) > _TOPK_MAX:
+        raise ValueError("fa2: %s serves 1 .. 2^31 - 65 key slots per sequence" % who)
+    _check_lens(who, cache_seqlens, B, q_idx.device)
+    if not q_idx.is_cuda or any(t.device != q_idx.device for t in (k, weights)):
+        raise ValueError("fa2: %s takes q_idx, k_idx_cache, weights, cache_seqlens and block_table on one ROCm device (no CPU path in this operator)" % who)
+    if k.stride(2) != 1 or k.stride(0) % 8 or k.stride(1) % 8 or k.stride(1) < 1 or k.data_ptr() & 15:
+        raise ValueError("fa2: k_idx_cache needs a contiguous last dim, strides that are multiples of 8 elements and 16-byte aligned storage (it is never copied)")
+    return _bnhd_ready(q_idx), k, weights if weights.stride(2) == 1 else weights.contiguous(), capacity, page_size, num_pages
+
+
+def _indexer_logits_launch(q, k, w, cache_seqlens, block_table, capacity, page_size, num_pages):
+    B, Nq, H, _ = q.shape
+    logits = torch.empty((B, Nq, capacity * max(page_size, 1)), dtype=torch.float32, device=q.device)
+    dev = _device_index(q)
+    with torch.cuda.device(dev):
+        rc = _fa2_lib.load().fa2_mla_indexer_logits(
+            _dtype_code(q), q.data_ptr(), k.data_ptr(), w.data_ptr(), logits.data_ptr(), cache_seqlens.data_ptr(),
+            None if block_table is None else block_table.data_ptr(), B, H, Nq, _IDX_D, capacity, page_size, num_pages, _bnhd(q),
+            _fa2_lib.strides2(k.stride(0), k.stride(1)), _fa2_lib.strides2(w.stride(0), w.stride(1)), _fa2_lib.strides2(logits.stride(0), logits.stride(1)),
+            0 if block_table is None else block_table.stride(0), _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return logits
+
+
+def _topk_prepare(who, logits, cache_seqlens, topk):
+    if not torch.is_tensor(logits) or logits.dim() != 3 or logits.dtype != torch.float32 or logits.shape[0] < 1 or logits.shape[1] < 1 or \
+            not 1 <= logits.shape[2] <= _TOPK_MAX:
+        raise ValueError("fa2: %s takes logits as a float32 tensor [B, Nq, capacity]" % who)
+    _no_grad_inputs(who, logits)
+    _check_topk(who, topk)
+    _check_lens(who, cache_seqlens, logits.shape[0], logits.device)
+    if not logits.is_cuda:
+        raise ValueError("fa2: %s takes logits and cache_seqlens on one ROCm device (no CPU path in this operator)" % who)
+    return logits if logits.stride(2) == 1 else logits.contiguous()
+
+
+def _topk_launch(logits, cache_seqlens, topk):
+    B, Nq, capacity = logits.shape
+    idx = torch.empty((B, Nq, topk), dtype=torch.int32, device=logits.device)
+    dev = _device_index(logits)
+    with torch.cuda.device(dev):
+        rc = _fa2_lib.load().fa2_topk_indices(logits.data_ptr(), idx.data_ptr(), cache_seqlens.data_ptr(), B, Nq, capacity, topk,
+                                              _fa2_lib.strides2(logits.stride(0), logits.stride(1)), _fa2_lib.strides2(idx.stride(0), idx.stride(1)),
+                                              _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return idx
+
+
+def mla_indexer_logits(q_idx, k_idx_cache, weights, cache_seqlens, block_table=None):
+    """The logits of DeepSeek-V3.2's lightning indexer over an index-key cache (DeepGEMM's fp8_paged_mqa_logits shape, in 16 bits).
+    q_idx [B, Nq, H_idx, 128] fp16 / bf16, H_idx in 16, 32, 48, 64 (a q the kernel cannot address is copied).  k_idx_cache in q_idx's dtype: ONE row of
+    128 columns per token shared by all indexer heads — [B, Nmax, 128], or [num_pages, page_size, 128] under block_table int32 [B, max_pages] with the
+    page sizes and semantics of flash_attention_decode_mla (a server shares one table between the latent cache and this one; a head axis of 1 is
+    accepted; the cache is never copied).  weights float32 [B, Nq, H_idx] on the device: the caller folds the softmax scale, H_idx ** -0.5 and any q
+    scale into it.  cache_seqlens int32 [B] counts the valid keys INCLUDING the Nq new tokens; the host reads no device value, so the call can be captured.
+    -> float32 [B, Nq, capacity], capacity = Nmax or max_pages * page_size: with pos = len_b - Nq + i,
+    logits[b, i, s] = sum_h weights[b, i, h] * relu(q_idx[b, i, h] . k_idx[b, s]) for s <= pos and -inf beyond; every element is written.  Key rows
+    beyond pos and unused pages contribute nothing whatever they hold and are never read.  f32 accumulation in one fixed order: paged equals contiguous
+    bit for bit.  kvcache_append with one K / V head of 128 columns writes the cache.  Inference only.  C-ABI fa2_mla_indexer_logits."""
+    q, k, w, capacity, page_size, num_pages = _indexer_prepare("mla_indexer_logits", q_idx, k_idx_cache, weights, cache_seqlens, block_table)
+    return _indexer_logits_launch(q, k, w, cache_seqlens, block_table, capacity, page_size, num_pages)
+
+
+def topk_indices(logits, cache_seqlens, topk):
+    """Deterministic top-k selection over indexer logits.  logits float32 [B, Nq, capacity] on the device, cache_seqlens int32 [B], topk a positive int.
+    -> int32 [B, Nq, topk], the indices tensor flash_attention_decode_mla(..., indices=) consumes: per row (b, i), over s in [0, pos] only
+    (pos = len_b - Nq + i), the min(topk, pos + 1) positions of the largest logits in ASCENDING position order, then -1.  Among equal logits the
+    lowest positions win; a NaN ranks as -inf; pos + 1 <= topk selects every position without reading a logit; pos < 0 gives all -1.  A pure function
+    of the row: two runs give the same bits.  The host reads no device value.  Inference only.  C-ABI fa2_topk_indices."""
+    return _topk_launch(_topk_prepare("topk_indices", logits, cache_seqlens, topk), cache_seqlens, topk)
+
+
+def mla_indexer_topk(q_idx, k_idx_cache, weights, cache_seqlens, block_table=None, topk=2048, return_logits=False):
+    """mla_indexer_logits, then topk_indices, on the current stream: the call a server makes in front of flash_attention_decode_mla(..., indices=).
+    Every check of both halves runs before the first launch.  -> indices int32 [B, Nq, topk], with return_logits=True also the float32 logits."""
+    who = "mla_indexer_topk"
+    _check_topk(who, topk)
+    q, k, w, capacity, page_size, num_pages = _indexer_prepare(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table)
+    logits = _indexer_logits_launch(q, k, w, cache_seqlens, block_table, capacity, page_size, num_pages)
+    idx = _topk_launch(logits, cache_seqlens, topk)
+    return (idx, logits) if return_logits else idx
 
 
 def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, max_seqlen_q=None, scale=None, window=None, softcap=0.0,

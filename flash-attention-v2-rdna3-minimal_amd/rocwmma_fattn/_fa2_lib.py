@@ -63,7 +63,8 @@ class DecodeMlaPlan(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-FA2_KERNEL_HIP_DECODE_MLA_SPARSE = 11                                                                   # ... of fa2_fwd_decode_mla_sparse_plan
+FA2_KERNEL_HIP_MLA_INDEXER = 12                                                                         # the logits kernel of fa2_mla_indexer_logits
+FA2_KERNEL_HIP_DECODE_MLA_SPARSE = 11                                                                 # ... of fa2_fwd_decode_mla_sparse_plan
 FA2_KERNEL_HIP_DECODE_MLA = 9                                                                           # fa2_decode_mla_plan_t.kernel (an enumerator in the header)
 FA2_KERNEL_HIP_PREFILL = 8                                                                              # fa2_fwd_prefill_plan's kernel (an enumerator in the header)
 FA2_KERNEL_HIP_DECODE = 7                                                                               # fa2_decode_plan_t.kernel (an enumerator in the header)
@@ -195,6 +196,11 @@ SYMBOLS = {
     "fa2_fwd_decode_mla_sparse_plan": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(DecodeMlaPlan)]),
     "fa2_fwd_decode_mla_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
     "fa2_decode_mla_sparse_entry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)] * 3),
+    # the lightning indexer that makes those lists.  logits: dtype, q_idx k_idx_cache weights logits cache_seqlens block_table, B H_idx Nq D_idx capacity
+    # page_size num_pages, the q stride triple, the k / weights / logits pairs, the block-table row stride, stream.  top-k: logits indices cache_seqlens,
+    # B Nq capacity topk, the logits / indices pairs, stream
+    "fa2_mla_indexer_logits": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 7 + [_i64p] * 4 + [ctypes.c_int64, ctypes.c_void_p]),
+    "fa2_topk_indices": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [_i64p] * 2 + [ctypes.c_void_p]),
     # ... on an e4m3 latent cache of 656-byte rows: the twins' lists (kv_cache the byte cache, kv_strides in bytes); the twins' plan and workspace queries
     "fa2_fwd_decode_mla_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +
                                [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

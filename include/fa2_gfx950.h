@@ -841,6 +841,44 @@ int fa2_fwd_decode_mla_sparse_plan(int dtype, int B, int H, int Nq, int D, int D
 size_t fa2_fwd_decode_mla_sparse_workspace_bytes(int dtype, int B, int H, int Nq, int D, int Dv, int capacity, int page_size, int num_splits, int topk);
 int fa2_decode_mla_sparse_entry(int entry, int64_t len, int Nq, int i, int capacity, int page_size, int* valid, int* page_slot, int* row_in_page);
 
+/* ---- ... and the lightning indexer that makes those lists (DeepSeek-V3.2): two calls on one stream, the host reads no device
+ * value in either.  With pos = len_b - Nq + i (len clamped as in fa2_fwd_decode_mla):
+ *   logits[b, i, s] = sum_h weights[b, i, h] * max(0, sum_d q_idx[b, i, h, d] * k_idx[b, s, d])   for 0 <= s <= pos,   -inf for pos < s < capacity_keys
+ * fa2_mla_indexer_logits
+ *   q_idx           : B x Nq x H_idx x 128, f16 / bf16 (dtype); element strides q_strides {batch, head, row}, the last dim contiguous.
+ *                     H_idx is 16, 32, 48 or 64; D_idx is 128.
+ *   k_idx_cache     : same dtype, ONE row of 128 columns per token shared by all indexer heads: B x capacity x 128 (page_size == 0), or a pool
+ *                     num_pages x page_size x 128 under block_table B x capacity (capacity then counts block-table entries and capacity_keys =
+ *                     capacity * page_size); element strides k_strides {batch | page, row}.  page_size, num_pages, block_table and its stride mean
+ *                     what they mean in fa2_fwd_decode_mla: a server shares one table between the latent cache and this one.
+ *   weights         : B x Nq x H_idx f32, device; element strides w_strides {batch, row}, the head dim contiguous.  The caller folds the softmax scale,
+ *                     H_idx ** -0.5 and any q scale into it: there is no separate scale.
+ *   logits          : B x Nq x capacity_keys f32, element strides logits_strides {batch, row}; EVERY element is written.
+ * f32 accumulation (the products of 16-bit values are exact in f32) and an f32 head sum in one fixed order: a row's bits depend on its own q, weights
+ * and key row alone, and a paged call equals the contiguous call bit for bit.  A key row beyond pos contributes nothing whatever it holds and is never
+ * read; a page that holds only keys beyond len_b is never addressed and its block-table entry never read; page ids are clamped into the pool; a
+ * contiguous capacity that is no multiple of the 16-key tile is never read past its end.
+ * Checked in this order: null pointers (block_table only when paged); sizes (FA2_ERR_BAD_SHAPE: B, H_idx, Nq, D_idx, capacity < 1, the page-size rule,
+ * num_pages < 1 when paged, capacity_keys above 2^31 - 1 - 64, a negative weights / logits / block-table stride); H_idx outside the served set or
+ * D_idx != 128 (FA2_ERR_HEAD_DIM); alignment (q_idx and k_idx_cache 16 bytes with strides that are multiples of 8 and a positive row stride; weights,
+ * logits, cache_seqlens, block_table 4 bytes); dtype; FA2_ERR_GRID (B or Nq above 65535).
+ * Kernel (FA2_KERNEL_HIP_MLA_INDEXER, csrc/fa2_mla_indexer.hip.h): v_mfma_f32_16x16x32 with the heads on the M rows, K straight from memory into the
+ * operand registers, no LDS, no barrier; a grid of (ceil(capacity_keys / 512), Nq, B) workgroups of four waves.
+ * fa2_topk_indices: per row (b, i), over s in [0, pos] only, indices[b, i, :] = the min(topk, pos + 1) positions of the largest logits IN ASCENDING
+ * POSITION ORDER, then -1.  Among equal logits the lowest positions win; a NaN ranks as -inf; pos + 1 <= topk selects 0 .. pos without reading a logit;
+ * pos < 0 gives all -1.  logits B x Nq x capacity f32 (strides {batch, row}), indices B x Nq x topk int32 (strides {batch, row}), both with a
+ * contiguous last dim; capacity here counts keys.  A pure function of the row (a radix select in LDS, no global atomics: csrc/fa2_topk_select.hip.h).
+ * Checked in this order: null pointers; sizes (FA2_ERR_BAD_SHAPE: B, Nq, capacity, topk < 1, capacity or topk above 2^31 - 1 - 64, a negative stride);
+ * alignment (4 bytes); FA2_ERR_GRID (B * Nq above 2^31 - 1). */
+enum { FA2_KERNEL_HIP_MLA_INDEXER = 12 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+int fa2_mla_indexer_logits(int dtype, const void* q_idx, const void* k_idx_cache, const float* weights, float* logits,
+                           const int* cache_seqlens, const int* block_table,
+                           int B, int H_idx, int Nq, int D_idx, int capacity, int page_size, int num_pages,
+                           const int64_t q_strides[3], const int64_t k_strides[2], const int64_t w_strides[2],
+                           const int64_t logits_strides[2], int64_t block_table_stride, void* hip_stream);
+int fa2_topk_indices(const float* logits, int* indices, const int* cache_seqlens, int B, int Nq, int capacity, int topk,
+                     const int64_t logits_strides[2], const int64_t indices_strides[2], void* hip_stream);
+
 /* ---- ... on an e4m3 latent cache (the FP8 KV cache of DeepSeek-V3.2 servers: FlashMLA's, vLLM's fp8_ds_mla), dense and sparse.  One row per token,
  * 656 bytes instead of 1 152:
  *   bytes   0 .. 511   OCP e4m3 codes of latent columns 0 .. 511 (the part that is also the value)
