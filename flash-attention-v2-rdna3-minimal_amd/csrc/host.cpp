@@ -24,6 +24,8 @@
 #include "fa2_topk_select.hip.h"     // ... and the selection behind it
 #include "fa2_kvappend_mla.hip.h"    // ... and its append: the parameter block, the unit -> chunks map, its launcher
 #include "fa2_kvappend_mla_fp8.hip.h"      // ... and the quantising append of its e4m3 form: the launcher
+#include "fa2_mla_indexer_fp8.hip.h"       // the indexer on an e4m3 index-key cache: the logits kernel's parameter block and launcher
+#include "fa2_kvappend_mla_index_fp8.hip.h"      // ... and that cache's quantising append
 
 #include <algorithm>
 #include <cmath>
@@ -2042,6 +2044,94 @@ int fa2_topk_indices(const float* logits, int* indices, const int* cache_seqlens
     p.logits = logits; p.idx = indices; p.lens = cache_seqlens; p.B = B; p.Nq = Nq; p.topk = topk; p.capacity_keys = capacity;
     for (int i = 0; i < 2; ++i) { p.ls[i] = logits_strides[i]; p.is[i] = indices_strides[i]; }
     return fa2::launch_topk_select(p, (hipStream_t)hip_stream);
+}
+
+// ---- ... on an e4m3 index-key cache: 128 codes and one float32 scale per token, addressed separately, so rows of 132 bytes and
+// vLLM's blocks are both views of it (csrc/fa2_mla_indexer_fp8.hip.h), and the quantising append that writes it
+// (csrc/fa2_kvappend_mla_index_fp8.hip.h).  The 16-bit call's checks in its order, the new arguments' appended inside each class.
+static bool index_cache_aligned(const void* codes, const float* scales, const int64_t* cs) {
+    return !((reinterpret_cast<uintptr_t>(codes) | reinterpret_cast<uintptr_t>(scales)) & 3u) && cs[0] >= 0 && cs[0] % 4 == 0 && cs[1] >= 1 && cs[1] % 4 == 0;
+}
+
+int fa2_mla_indexer_logits_fp8(int q_dtype, const void* q_idx, const void* k_codes, const float* k_scales, const float* weights, float* logits,
+                               const int* cache_seqlens, const int* block_table, int B, int H_idx, int Nq, int D_idx, int capacity, int page_size,
+                               int num_pages, const int64_t q_strides[3], const int64_t code_strides[2], const int64_t scale_strides[2],
+                               const int64_t w_strides[2], const int64_t logits_strides[2], int64_t block_table_stride, void* hip_stream) {
+    if (any_null({q_idx, k_codes, weights, logits, cache_seqlens, q_strides, code_strides, w_strides, logits_strides, k_scales, scale_strides}) ||
+        (page_size > 0 && !block_table))
+        return FA2_ERR_NULL_POINTER;
+    CacheDesc c;
+    c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    if (B < 1 || H_idx < 1 || Nq < 1 || D_idx < 1 || !cache_paging_ok(c) || c.capacity_keys() > 0x7fffffffLL - 64 || !cache_extent_ok(c)) return FA2_ERR_BAD_SHAPE;
+    if (w_strides[0] < 0 || w_strides[1] < 0 || logits_strides[0] < 0 || logits_strides[1] < 0 || block_table_stride < 0 || scale_strides[0] < 0 ||
+        scale_strides[1] < 0)
+        return FA2_ERR_BAD_SHAPE;
+    if (!fa2::mla_indexer_heads_ok(H_idx) || D_idx != fa2::kIdxD) return FA2_ERR_HEAD_DIM;
+    const int q_mult = q_dtype == FA2_DTYPE_E4M3 ? 16 : 8;       // a 16-byte load: 16 codes or 8 values
+    if (!aligned16(q_idx) || !strides3_ok(q_strides) || (q_strides[0] | q_strides[1] | q_strides[2]) % q_mult != 0 ||
+        ((reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(cache_seqlens) |
+          reinterpret_cast<uintptr_t>(block_table)) & 3u) || !index_cache_aligned(k_codes, k_scales, code_strides))
+        return FA2_ERR_ALIGNMENT;
+    if (q_dtype != FA2_DTYPE_F16 && q_dtype != FA2_DTYPE_BF16 && q_dtype != FA2_DTYPE_E4M3) return FA2_ERR_DTYPE;
+    if (B > 65535 || Nq > 65535) return FA2_ERR_GRID;
+    fa2::MlaIndexerFp8Params p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = q_idx; p.k = static_cast<const uint8_t*>(k_codes); p.ksc = k_scales; p.w = weights; p.logits = logits; p.lens = cache_seqlens;
+    p.bt = page_size > 0 ? block_table : nullptr;
+    p.B = B; p.H = H_idx; p.Nq = Nq; p.page_size = page_size; p.num_pages = num_pages; p.capacity_keys = c.capacity_keys();
+    for (int i = 0; i < 3; ++i) p.qs[i] = q_strides[i];
+    for (int i = 0; i < 2; ++i) { p.ks[i] = code_strides[i]; p.ss[i] = scale_strides[i]; p.ws[i] = w_strides[i]; p.ls[i] = logits_strides[i]; }
+    p.bts = block_table_stride;
+    const int form = q_dtype == FA2_DTYPE_E4M3 ? fa2::kIdxQE4M3 : q_dtype == FA2_DTYPE_BF16 ? fa2::kIdxQBF16 : fa2::kIdxQF16;
+    return fa2::launch_mla_indexer_logits_fp8(form, p, (hipStream_t)hip_stream);
+}
+
+// cu_seqlens null: the uniform call (tokens = B * Nnew); else the packed one (tokens = total, k_idx_strides[0] unused)
+static int append_mla_index_run(bool packed, int dtype, const void* k_idx, void* k_codes, float* k_scales, const int* cu_seqlens, const int* cache_seqlens,
+                                const int* block_table, int B, int Nnew, int64_t tokens, int D_idx, int capacity, int page_size, int num_pages,
+                                const int64_t k_idx_strides[2], const int64_t code_strides[2], const int64_t scale_strides[2], int64_t block_table_stride,
+                                int scale_pow2, void* hip_stream) {
+    if (any_null({k_idx, k_codes, k_scales, cache_seqlens, k_idx_strides, code_strides, scale_strides}) || (packed && !cu_seqlens) ||
+        (page_size > 0 && !block_table))
+        return FA2_ERR_NULL_POINTER;
+    CacheDesc c;
+    c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    if (B < 1 || (packed ? tokens < 0 : Nnew < 1) || D_idx < 1 || !cache_paging_ok(c) || c.capacity_keys() > 0x7fffffffLL - 64 || !cache_extent_ok(c) ||
+        block_table_stride < 0 || scale_strides[0] < 0 || scale_strides[1] < 0 || k_idx_strides[0] < 0)
+        return FA2_ERR_BAD_SHAPE;
+    if (D_idx != fa2::kIdxD) return FA2_ERR_HEAD_DIM;
+    if (!aligned16(k_idx) || k_idx_strides[0] % 8 != 0 || k_idx_strides[1] < 1 || k_idx_strides[1] % 8 != 0 || !index_cache_aligned(k_codes, k_scales, code_strides) ||
+        ((reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(cu_seqlens) | reinterpret_cast<uintptr_t>(block_table)) & 3u))
+        return FA2_ERR_ALIGNMENT;
+    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    if (tokens > 0x7fffffffLL) return FA2_ERR_GRID;
+    if (tokens == 0) return FA2_OK;                                  // an empty token buffer: nothing to launch
+    fa2::KvAppendMlaIndexParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.x = k_idx; p.k = static_cast<uint8_t*>(k_codes); p.ksc = k_scales; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr;
+    p.cu = packed ? cu_seqlens : nullptr;
+    p.B = B; p.Nnew = packed ? 1 : Nnew; p.page_size = page_size; p.num_pages = num_pages; p.pow2 = scale_pow2 != 0;
+    p.tokens = tokens; p.capacity_keys = c.capacity_keys();
+    p.xs[0] = packed ? 0 : k_idx_strides[0]; p.xs[1] = k_idx_strides[1];
+    p.ks[0] = code_strides[0]; p.ks[2] = code_strides[1]; p.ss[0] = scale_strides[0]; p.ss[2] = scale_strides[1];
+    p.bts = block_table_stride;
+    return fa2::launch_kvappend_mla_index_fp8(dtype == FA2_DTYPE_BF16, p, (hipStream_t)hip_stream);
+}
+
+int fa2_kvcache_append_mla_index_fp8(int dtype, const void* k_idx, void* k_codes, float* k_scales, const int* cache_seqlens, const int* block_table, int B,
+                                     int Nnew, int D_idx, int capacity, int page_size, int num_pages, const int64_t k_idx_strides[2],
+                                     const int64_t code_strides[2], const int64_t scale_strides[2], int64_t block_table_stride, int scale_pow2,
+                                     void* hip_stream) {
+    return append_mla_index_run(false, dtype, k_idx, k_codes, k_scales, nullptr, cache_seqlens, block_table, B, Nnew, (int64_t)B * Nnew, D_idx, capacity,
+                                page_size, num_pages, k_idx_strides, code_strides, scale_strides, block_table_stride, scale_pow2, hip_stream);
+}
+
+int fa2_kvcache_append_mla_index_varlen_fp8(int dtype, const void* k_idx, void* k_codes, float* k_scales, const int* cu_seqlens, const int* cache_seqlens,
+                                            const int* block_table, int B, int64_t total, int D_idx, int capacity, int page_size, int num_pages,
+                                            const int64_t k_idx_strides[2], const int64_t code_strides[2], const int64_t scale_strides[2],
+                                            int64_t block_table_stride, int scale_pow2, void* hip_stream) {
+    return append_mla_index_run(true, dtype, k_idx, k_codes, k_scales, cu_seqlens, cache_seqlens, block_table, B, 1, total, D_idx, capacity, page_size,
+                                num_pages, k_idx_strides, code_strides, scale_strides, block_table_stride, scale_pow2, hip_stream);
 }
 
 // ---- KV-cache append with rotary embedding and e4m3 quantisation: include/fa2_gfx950.h has the contract, csrc/fa2_kvappend.hip.h the kernel,

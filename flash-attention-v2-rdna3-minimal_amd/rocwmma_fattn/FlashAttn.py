@@ -27,7 +27,8 @@ from . import _fa2_lib
 
 __all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
            "kvcache_append_varlen", "flash_attention_decode_mla", "kvcache_append_mla", "kvcache_append_mla_varlen", "mla_cache_to_fp8",
-           "mla_cache_from_fp8", "mla_indexer_logits", "topk_indices", "mla_indexer_topk"]
+           "mla_cache_from_fp8", "mla_indexer_logits", "topk_indices", "mla_indexer_topk", "mla_indexer_q_to_fp8", "mla_index_cache_to_fp8",
+           "mla_index_cache_from_fp8", "kvcache_append_mla_index"]
 
 
 class _FlashAttnWmma:
@@ -1822,6 +1823,27 @@ def _check_topk(who, topk):
         raise ValueError("fa2: %s takes topk as an int in 1 .. 2^31 - 65, got %r" % (who, topk))
 
 
+def _indexer_geometry(who, B, kshape, shown, block_table, cache_seqlens, device, width=_IDX_D):
+    """The paging checks of an index-key cache [B | num_pages, rows, ..] -> capacity, page_size, num_pages (the 16-bit and the e4m3 form alike)"""
+    if block_table is None:
+        if kshape[0] != B:
+            raise ValueError("fa2: a contiguous index-key cache is [B, Nmax, %d] with B = %d sequences, got %s (a paged cache needs its block_table)"
+                             % (width, B, shown))
+        capacity, page_size, num_pages = kshape[1], 0, 0
+    else:
+        if not torch.is_tensor(block_table) or block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != B or \
+                block_table.shape[1] < 1 or block_table.stride(1) != 1 or block_table.device != device:
+            raise ValueError("fa2: block_table must be int32 [B, max_pages] with B = %d sequences and contiguous rows on q_idx's device" % B)
+        capacity, page_size, num_pages = block_table.shape[1], kshape[1], kshape[0]
+        if page_size < 64 or page_size % 64 or num_pages < 1:
+            raise ValueError("fa2: the page size of a paged cache (k_idx_cache.shape[1]) must be a multiple of 64 and the pool must hold a page, got %s"
+                             % (shown,))
+    if capacity < 1 or capacity * max(page_size, 1) > _TOPK_MAX:
+        raise ValueError("fa2: %s serves 1 .. 2^31 - 65 key slots per sequence" % who)
+    _check_lens(who, cache_seqlens, B, device)
+    return capacity, page_size, num_pages
+
+
 def _indexer_prepare(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table):
     """Every argument check of mla_indexer_logits; nothing is launched here.  -> (q_idx, k [.., .., 128], weights, capacity, page_size, num_pages)"""
     if not all(torch.is_tensor(t) for t in (q_idx, k_idx_cache, weights, cache_seqlens)) or q_idx.dim() != 4 or k_idx_cache.dim() not in (3, 4) or \
@@ -1839,22 +1861,7 @@ def _indexer_prepare(who, q_idx, k_idx_cache, weights, cache_seqlens, block_tabl
         raise ValueError("fa2: %s serves H_idx in %s with weights [B, Nq, H_idx] (B >= 1, Nq in 1 .. 65535), got q_idx %s weights %s"
                          % (who, _IDX_HEADS, tuple(q_idx.shape), tuple(weights.shape)))
     k = k_idx_cache if k_idx_cache.dim() == 3 else k_idx_cache[:, :, 0]
-    if block_table is None:
-        if k.shape[0] != B:
-            raise ValueError("fa2: a contiguous index-key cache is [B, Nmax, 128] with B = %d sequences, got %s (a paged cache needs its block_table)"
-                             % (B, tuple(k_idx_cache.shape)))
-        capacity, page_size, num_pages = k.shape[1], 0, 0
-    else:
-        if not torch.is_tensor(block_table) or block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != B or \
-                block_table.shape[1] < 1 or block_table.stride(1) != 1 or block_table.device != q_idx.device:
-            raise ValueError("fa2: block_table must be int32 [B, max_pages] with B = %d sequences and contiguous rows on q_idx's device" % B)
-        capacity, page_size, num_pages = block_table.shape[1], k.shape[1], k.shape[0]
-        if page_size < 64 or page_size % 64 or num_pages < 1:
-            raise ValueError("fa2: the page size of a paged cache (k_idx_cache.shape[1]) must be a multiple of 64 and the pool must hold a page, got %s"
-                             % (tuple(k_idx_cache.shape),))
-    if capacity < 1 or capacity * max(page_size, 1) > _TOPK_MAX:
-        raise ValueError("fa2: %s serves 1 .. 2^31 - 65 key slots per sequence" % who)
-    _check_lens(who, cache_seqlens, B, q_idx.device)
+    capacity, page_size, num_pages = _indexer_geometry(who, B, k.shape, tuple(k_idx_cache.shape), block_table, cache_seqlens, q_idx.device)
     if not q_idx.is_cuda or any(t.device != q_idx.device for t in (k, weights)):
         raise ValueError("fa2: %s takes q_idx, k_idx_cache, weights, cache_seqlens and block_table on one ROCm device (no CPU path in this operator)" % who)
     if k.stride(2) != 1 or k.stride(0) % 8 or k.stride(1) % 8 or k.stride(1) < 1 or k.data_ptr() & 15:
@@ -1874,6 +1881,192 @@ def _indexer_logits_launch(q, k, w, cache_seqlens, block_table, capacity, page_s
             0 if block_table is None else block_table.stride(0), _raw_stream(dev))
     _fa2_lib.check(rc)
     return logits
+
+
+_IDX_ROW8 = _IDX_D + 4             # bytes of an e4m3 index-key row: 128 codes, then the float32 scale
+_IndexCache8 = collections.namedtuple("_IndexCache8", "codes scales shape device code_ptr scale_ptr code_strides scale_strides")
+
+
+def _is_8bit(t):
+    return torch.is_tensor(t) and (t.dtype == torch.uint8 or t.dtype in _FP8_OTHERS or (_FP8_CACHE is not None and t.dtype == _FP8_CACHE))
+
+
+def _index_cache8(who, k_idx_cache):
+    """An e4m3 index-key cache as the C-ABI takes it — codes (byte strides) and scales (float32 element strides) addressed separately — or None for a
+    16-bit cache.  Two forms: ROWS, a uint8 / float8_e4m3fn tensor [.., .., 132] (128 codes, then the scale), and BLOCKS, a pair (codes [.., .., 128]
+    8-bit, scales [.., ..] float32) of views of one storage (vLLM's pages: a page's codes, then its scales).  Never copied."""
+    pair = isinstance(k_idx_cache, (tuple, list))
+    if not pair and not _is_8bit(k_idx_cache):
+        return None
+    codes, scales = k_idx_cache if pair and len(k_idx_cache) == 2 else (k_idx_cache, None)
+    if not _is_8bit(codes) or (pair and not (torch.is_tensor(scales) and scales.dtype == torch.float32)):
+        raise ValueError("fa2: %s takes an e4m3 index-key cache as uint8 / float8_e4m3fn rows of %d bytes, or as a pair (codes [.., .., 128] uint8 / "
+                         "float8_e4m3fn, scales [.., ..] float32)" % (who, _IDX_ROW8))
+    if codes.dtype in _FP8_OTHERS:
+        raise ValueError("fa2: %s takes OCP e4m3 codes (torch.uint8 or torch.float8_e4m3fn): e5m2 and the fnuz formats are not served, got %s" % (who, codes.dtype))
+    if codes.dim() not in (3, 4) or (codes.dim() == 4 and codes.shape[2] != 1):
+        raise ValueError("fa2: %s takes an index-key cache [B, Nmax, %d] ([num_pages, page_size, %d] with a block_table; a 4-D cache has a head axis of size "
+                         "1), got %s" % (who, _IDX_D if pair else _IDX_ROW8, _IDX_D if pair else _IDX_ROW8, tuple(codes.shape)))
+    raw = codes.view(torch.uint8)
+    raw = raw if raw.dim() == 3 else raw[:, :, 0]
+    if raw.shape[-1] != (_IDX_D if pair else _IDX_ROW8):
+        raise ValueError("fa2: %s takes e4m3 index-key rows of %d bytes (128 codes and one float32 scale), or codes of 128 bytes beside their scales, got %s"
+                         % (who, _IDX_ROW8, tuple(codes.shape)))
+    if pair:
+        if scales.dim() == 3 and scales.shape[2] == 1:
+            scales = scales[:, :, 0]
+        if tuple(scales.shape) != tuple(raw.shape[:2]) or scales.device != raw.device:
+            raise ValueError("fa2: %s takes (codes, scales) with one float32 scale per code row on one device, got codes %s scales %s"
+                             % (who, tuple(codes.shape), tuple(scales.shape)))
+        scale_ptr, scale_strides = scales.data_ptr(), (scales.stride(0), scales.stride(1))
+    else:
+        scale_ptr, scale_strides = raw.data_ptr() + _IDX_D, (raw.stride(0) // 4, raw.stride(1) // 4)
+    if raw.stride(2) != 1 or raw.stride(0) % 4 or raw.stride(1) % 4 or raw.stride(1) < 1 or raw.data_ptr() & 3:
+        raise ValueError("fa2: %s needs the codes' last dim contiguous and their storage and strides 4-byte aligned (the cache is never copied)" % who)
+    if scale_ptr & 3 or scale_strides[0] < 0 or scale_strides[1] < 0:
+        raise ValueError("fa2: %s needs 4-byte aligned scales with non-negative strides (the cache is never copied)" % who)
+    return _IndexCache8(raw, scales, tuple(raw.shape), raw.device, raw.data_ptr(), scale_ptr, _fa2_lib.strides2(raw.stride(0), raw.stride(1)),
+                        _fa2_lib.strides2(*scale_strides))
+
+
+def _indexer_prepare_fp8(who, q_idx, k8, weights, cache_seqlens, block_table):
+    """_indexer_prepare for an e4m3 index-key cache (k8: _index_cache8's); q_idx is fp16 / bf16 (quantised in the kernel) or float8_e4m3fn"""
+    if not all(torch.is_tensor(t) for t in (q_idx, weights, cache_seqlens)) or q_idx.dim() != 4 or weights.dim() != 3:
+        raise ValueError("fa2: %s takes q_idx [B, Nq, H_idx, 128], weights [B, Nq, H_idx] and cache_seqlens [B]" % who)
+    _no_grad_inputs(who, q_idx, weights)
+    q8 = _FP8_CACHE is not None and q_idx.dtype == _FP8_CACHE
+    if (q_idx.dtype not in (torch.float16, torch.bfloat16) and not q8) or weights.dtype != torch.float32:
+        raise ValueError("fa2: %s on an e4m3 index-key cache takes fp16, bf16 or float8_e4m3fn q_idx and float32 weights, got %s %s" % (who, q_idx.dtype, weights.dtype))
+    B, Nq, H, D = q_idx.shape
+    if D != _IDX_D:
+        raise ValueError("fa2: %s serves index rows of %d columns, got q_idx %s" % (who, _IDX_D, tuple(q_idx.shape)))
+    if H not in _IDX_HEADS or B < 1 or not 1 <= Nq <= 65535 or tuple(weights.shape) != (B, Nq, H):
+        raise ValueError("fa2: %s serves H_idx in %s with weights [B, Nq, H_idx] (B >= 1, Nq in 1 .. 65535), got q_idx %s weights %s"
+                         % (who, _IDX_HEADS, tuple(q_idx.shape), tuple(weights.shape)))
+    capacity, page_size, num_pages = _indexer_geometry(who, B, k8.shape, k8.shape, block_table, cache_seqlens, q_idx.device, k8.shape[2])
+    if not q_idx.is_cuda or any(d != q_idx.device for d in (k8.device, weights.device)):
+        raise ValueError("fa2: %s takes q_idx, k_idx_cache, weights, cache_seqlens and block_table on one ROCm device (no CPU path in this operator)" % who)
+    q = q_idx if _decode_strides_ok(q_idx, 16 if q8 else 8) else q_idx.contiguous()
+    return q, weights if weights.stride(2) == 1 else weights.contiguous(), capacity, page_size, num_pages
+
+
+def _indexer_logits_launch_fp8(q, k8, w, cache_seqlens, block_table, capacity, page_size, num_pages):
+    B, Nq, H, _ = q.shape
+    logits = torch.empty((B, Nq, capacity * max(page_size, 1)), dtype=torch.float32, device=q.device)
+    dev = _device_index(q)
+    code = _fa2_lib.FA2_DTYPE_E4M3 if q.dtype == _FP8_CACHE else _dtype_code(q)
+    with torch.cuda.device(dev):
+        rc = _fa2_lib.load().fa2_mla_indexer_logits_fp8(
+            code, q.data_ptr(), k8.code_ptr, k8.scale_ptr, w.data_ptr(), logits.data_ptr(), cache_seqlens.data_ptr(),
+            None if block_table is None else block_table.data_ptr(), B, H, Nq, _IDX_D, capacity, page_size, num_pages, _bnhd(q), k8.code_strides,
+            k8.scale_strides, _fa2_lib.strides2(w.stride(0), w.stride(1)), _fa2_lib.strides2(logits.stride(0), logits.stride(1)),
+            0 if block_table is None else block_table.stride(0), _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return logits
+
+
+def _indexer_logits(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table):
+    """Checks, then the launch, of the logits for either cache format: the e4m3 cache dispatches to its own kernel, the 16-bit call is what it was"""
+    k8 = _index_cache8(who, k_idx_cache)
+    if k8 is not None:
+        q, w, capacity, page_size, num_pages = _indexer_prepare_fp8(who, q_idx, k8, weights, cache_seqlens, block_table)
+        return _indexer_logits_launch_fp8(q, k8, w, cache_seqlens, block_table, capacity, page_size, num_pages)
+    q, k, w, capacity, page_size, num_pages = _indexer_prepare(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table)
+    return _indexer_logits_launch(q, k, w, cache_seqlens, block_table, capacity, page_size, num_pages)
+
+
+def _index_scale(x, scale_pow2):
+    """Per row of float32 x [.., 128]: amax / 448 (an all-zero row: 1; a NaN does not count, as v_max_f32 drops it), or the smallest power of two at or
+    above that, from the exponent bits — the kernels' arithmetic"""
+    amax = torch.where(x.isnan(), torch.zeros_like(x), x.abs()).amax(-1, keepdim=True)
+    scale = torch.where(amax > 0, amax / _E4M3_MAX, torch.ones_like(amax))
+    if scale_pow2:
+        scale = ((scale.view(torch.int32) + 0x7FFFFF) & 0x7F800000).view(torch.float32)
+    return scale
+
+
+def _to_e4m3(x, scale):
+    return (x / scale).clamp(-_E4M3_MAX, _E4M3_MAX).to(torch.float8_e4m3fn)
+
+
+def mla_indexer_q_to_fp8(q_idx, weights):
+    """What mla_indexer_logits does to a 16-bit q_idx in front of an e4m3 index-key cache, in plain torch: per (token, head) s = amax / 448 in float32
+    (an all-zero head: 1), q8 = e4m3(clamp(q / s, -448, 448)), w' = weights * s (one float32 rounding).  -> (q8 float8_e4m3fn [B, Nq, H_idx, 128], w'
+    float32 [B, Nq, H_idx]): the pair the call takes in DeepGEMM's form, with the same bits out.  The reference of the kernel's prologue, and a utility
+    for callers who cache it."""
+    if not torch.is_tensor(q_idx) or q_idx.dtype not in (torch.float16, torch.bfloat16) or q_idx.dim() != 4 or q_idx.shape[-1] != _IDX_D or \
+            not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(q_idx.shape[:3]):
+        raise ValueError("fa2: mla_indexer_q_to_fp8 takes fp16 or bf16 q_idx [B, Nq, H_idx, %d] and float32 weights [B, Nq, H_idx]" % _IDX_D)
+    x = q_idx.float()
+    scale = _index_scale(x, False)
+    return _to_e4m3(x, scale), weights * scale[..., 0]
+
+
+def mla_index_cache_to_fp8(k16, scale_pow2=False):
+    """A 16-bit index-key cache [.., 128] -> the e4m3 cache in ROWS form, uint8 [.., 132]: per row scale = amax / 448 in float32 (an all-zero row: 1;
+    scale_pow2=True: the smallest power of two at or above it, DeepSeek's ue8m0 choice), 128 codes e4m3(clamp(x / scale, -448, 448)), then the scale's
+    four bytes.  Plain torch: an OFFLINE and TEST utility (kvcache_append_mla_index writes these bytes while serving)."""
+    if not torch.is_tensor(k16) or k16.dtype not in (torch.float16, torch.bfloat16) or k16.dim() < 1 or k16.shape[-1] != _IDX_D:
+        raise ValueError("fa2: mla_index_cache_to_fp8 takes an fp16 or bf16 index-key cache [.., %d]" % _IDX_D)
+    x = k16.float()
+    scale = _index_scale(x, scale_pow2)
+    out = torch.empty(tuple(k16.shape[:-1]) + (_IDX_ROW8,), dtype=torch.uint8, device=k16.device)
+    out[..., :_IDX_D] = _to_e4m3(x, scale).view(torch.uint8)
+    out[..., _IDX_D:] = scale.contiguous().view(torch.uint8)
+    return out
+
+
+def mla_index_cache_from_fp8(cache, dtype):
+    """An e4m3 index-key cache in ROWS form, uint8 / float8_e4m3fn [.., 132] -> [.., 128] in `dtype`: float32(code) * scale rounded once.  Plain torch:
+    an OFFLINE and TEST utility — calling it before every step is what the e4m3 path of mla_indexer_logits saves."""
+    if not _is_8bit(cache) or cache.dtype in _FP8_OTHERS or cache.dim() < 1 or cache.shape[-1] != _IDX_ROW8 or \
+            dtype not in (torch.float16, torch.bfloat16, torch.float32, torch.float64):
+        raise ValueError("fa2: mla_index_cache_from_fp8 takes a uint8 / float8_e4m3fn index-key cache [.., %d] and a floating dtype" % _IDX_ROW8)
+    raw = cache.view(torch.uint8)
+    codes = raw[..., :_IDX_D].contiguous().view(torch.float8_e4m3fn).float()
+    scale = raw[..., _IDX_D:].contiguous().view(torch.float32)
+    return (codes.double() * scale.double()).to(dtype) if dtype == torch.float64 else (codes * scale).to(dtype)
+
+
+def kvcache_append_mla_index(k_idx_cache, k_idx, cache_seqlens, block_table=None, cu_seqlens=None, scale_pow2=False):
+    """The quantising append for an e4m3 index-key cache, in place: the write side of mla_indexer_logits on such a cache.  k_idx fp16 / bf16
+    [B, Nnew, 128] — or packed [total, 128] with cu_seqlens int32 [B + 1] on the device (sequence s owns the rows [cu[s], cu[s + 1]), Nnew_s may be 0,
+    cu[B] < total is legitimate) — becomes 128 e4m3 codes and one float32 scale per token at key position len_b - Nnew + i, exactly the bytes
+    mla_index_cache_to_fp8(k_idx, scale_pow2) gives.  k_idx_cache in either form mla_indexer_logits takes (rows of 132 bytes, or (codes, scales)),
+    contiguous or paged under block_table; cache_seqlens[b] counts the valid keys INCLUDING the new tokens.  A token whose position lies outside the
+    cache, or whose page id lies outside the pool, is skipped: nothing is written, nothing is clamped onto a live key, no device value can move a
+    write outside the buffers.  A NaN in k_idx is stored as a NaN code.  The host reads no device value: the call can be captured in a graph.
+    C-ABI fa2_kvcache_append_mla_index_fp8, fa2_kvcache_append_mla_index_varlen_fp8."""
+    who = "kvcache_append_mla_index"
+    k8 = _index_cache8(who, k_idx_cache)
+    packed = cu_seqlens is not None
+    rank = 2 if packed else 3
+    if k8 is None or not torch.is_tensor(k_idx) or k_idx.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("fa2: %s takes an e4m3 index-key cache (uint8 / float8_e4m3fn rows of %d bytes, or (codes, scales)) and fp16 or bf16 k_idx"
+                         % (who, _IDX_ROW8))
+    if k_idx.dim() == rank + 1 and k_idx.shape[-2] == 1:
+        k_idx = k_idx[..., 0, :]                     # a head axis of size 1
+    if k_idx.dim() != rank or k_idx.shape[-1] != _IDX_D or (not packed and (k_idx.shape[0] < 1 or k_idx.shape[1] < 1)):
+        raise ValueError("fa2: %s takes k_idx %s, got %s" % (who, "[total, 128] with cu_seqlens" if packed else "[B, Nnew, 128] (B, Nnew >= 1)", tuple(k_idx.shape)))
+    _no_grad_inputs(who, k_idx)
+    B = _check_cu("cu_seqlens", cu_seqlens) if packed else k_idx.shape[0]
+    capacity, page_size, num_pages = _indexer_geometry(who, B, k8.shape, k8.shape, block_table, cache_seqlens, k_idx.device, k8.shape[2])
+    if not k_idx.is_cuda or k8.device != k_idx.device or (packed and cu_seqlens.device != k_idx.device):
+        raise ValueError("fa2: %s takes k_idx_cache, k_idx, cache_seqlens, cu_seqlens and block_table on one ROCm device (no CPU path in this operator)" % who)
+    k_idx = _mla_rows_ready(k_idx)
+    if packed and k_idx.shape[0] == 0:               # an empty token buffer: nothing to launch
+        return
+    lib, dev = _fa2_lib.load(), _device_index(k_idx)
+    tables = (cache_seqlens.data_ptr(), None if block_table is None else block_table.data_ptr())
+    tail = (_IDX_D, capacity, page_size, num_pages, _fa2_lib.strides2(0, k_idx.stride(0)) if packed else _fa2_lib.strides2(k_idx.stride(0), k_idx.stride(1)),
+            k8.code_strides, k8.scale_strides, 0 if block_table is None else block_table.stride(0), 1 if scale_pow2 else 0, _raw_stream(dev))
+    with torch.cuda.device(dev):
+        if packed:
+            rc = lib.fa2_kvcache_append_mla_index_varlen_fp8(_dtype_code(k_idx), k_idx.data_ptr(), k8.code_ptr, k8.scale_ptr, cu_seqlens.data_ptr(), *tables, B,
+                                                             k_idx.shape[0], *tail)
+        else:
+            rc = lib.fa2_kvcache_append_mla_index_fp8(_dtype_code(k_idx), k_idx.data_ptr(), k8.code_ptr, k8.scale_ptr, *tables, B, k_idx.shape[1], *tail)
+    _fa2_lib.check(rc)
 
 
 def _topk_prepare(who, logits, cache_seqlens, topk):
@@ -1910,9 +2103,15 @@ def mla_indexer_logits(q_idx, k_idx_cache, weights, cache_seqlens, block_table=N
     -> float32 [B, Nq, capacity], capacity = Nmax or max_pages * page_size: with pos = len_b - Nq + i,
     logits[b, i, s] = sum_h weights[b, i, h] * relu(q_idx[b, i, h] . k_idx[b, s]) for s <= pos and -inf beyond; every element is written.  Key rows
     beyond pos and unused pages contribute nothing whatever they hold and are never read.  f32 accumulation in one fixed order: paged equals contiguous
-    bit for bit.  kvcache_append with one K / V head of 128 columns writes the cache.  Inference only.  C-ABI fa2_mla_indexer_logits."""
-    q, k, w, capacity, page_size, num_pages = _indexer_prepare("mla_indexer_logits", q_idx, k_idx_cache, weights, cache_seqlens, block_table)
-    return _indexer_logits_launch(q, k, w, cache_seqlens, block_table, capacity, page_size, num_pages)
+    bit for bit.  kvcache_append with one K / V head of 128 columns writes the cache.  Inference only.  C-ABI fa2_mla_indexer_logits.
+    An E4M3 index-key cache (DeepGEMM's fp8_paged_mqa_logits, vLLM's indexer cache: 128 OCP e4m3 codes and ONE float32 scale per token) is taken in two
+    forms, never copied: ROWS, a torch.uint8 / torch.float8_e4m3fn tensor [B, Nmax, 132] or [num_pages, page_size, 132] (bytes 0 .. 127 the codes, bytes
+    128 .. 131 the scale; a head axis of 1 is accepted), and BLOCKS, a pair (codes [num_pages, page_size, 128] 8-bit, scales [num_pages, page_size]
+    float32) of views of one storage.  Then logits[b, i, s] = k_scale[b, s] * sum_h w'[b, i, h] * relu(q8[b, i, h] . k8[b, s]) on the FP8 matrix pipe
+    (f32 accumulation; the key scale multiplies once, after the head sum): q_idx float8_e4m3fn is taken as it is (the caller folded its scales into
+    weights, w' = weights); q_idx fp16 / bf16 is quantised in the kernel per (token, head) by mla_indexer_q_to_fp8's arithmetic, and the call equals
+    the call on that function's pair bit for bit.  kvcache_append_mla_index writes the cache.  C-ABI fa2_mla_indexer_logits_fp8."""
+    return _indexer_logits("mla_indexer_logits", q_idx, k_idx_cache, weights, cache_seqlens, block_table)
 
 
 def topk_indices(logits, cache_seqlens, topk):
@@ -1929,8 +2128,7 @@ def mla_indexer_topk(q_idx, k_idx_cache, weights, cache_seqlens, block_table=Non
     Every check of both halves runs before the first launch.  -> indices int32 [B, Nq, topk], with return_logits=True also the float32 logits."""
     who = "mla_indexer_topk"
     _check_topk(who, topk)
-    q, k, w, capacity, page_size, num_pages = _indexer_prepare(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table)
-    logits = _indexer_logits_launch(q, k, w, cache_seqlens, block_table, capacity, page_size, num_pages)
+    logits = _indexer_logits(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table)
     idx = _topk_launch(logits, cache_seqlens, topk)
     return (idx, logits) if return_logits else idx
 

@@ -20,6 +20,7 @@ _OVERRIDE = os.environ.get("FA2_GFX950_LIB")      # developer A/B: load this bui
 FA2_DTYPE_F16 = 0
 FA2_DTYPE_BF16 = 1
 FA2_DTYPE_F32 = 2                                  # the rotary tables of fa2_kvcache_append only
+FA2_DTYPE_E4M3 = 3                                 # q_idx of fa2_mla_indexer_logits_fp8 only
 FA2_CACHE_16BIT, FA2_CACHE_E4M3 = 0, 1             # cache_format of fa2_kvcache_append
 FA2_BIAS_NONE, FA2_BIAS_IO_DTYPE, FA2_BIAS_F32, FA2_BIAS_BOOL = 0, 1, 2, 3     # bias_kind of fa2_fwd_bias
 
@@ -63,6 +64,7 @@ class DecodeMlaPlan(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FA2_KERNEL_HIP_MLA_INDEXER_FP8 = 13                                                                     # ... of fa2_mla_indexer_logits_fp8
 FA2_KERNEL_HIP_MLA_INDEXER = 12                                                                         # the logits kernel of fa2_mla_indexer_logits
 FA2_KERNEL_HIP_DECODE_MLA_SPARSE = 11                                                                 # ... of fa2_fwd_decode_mla_sparse_plan
 FA2_KERNEL_HIP_DECODE_MLA = 9                                                                           # fa2_decode_mla_plan_t.kernel (an enumerator in the header)
@@ -201,6 +203,15 @@ SYMBOLS = {
     # B Nq capacity topk, the logits / indices pairs, stream
     "fa2_mla_indexer_logits": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 7 + [_i64p] * 4 + [ctypes.c_int64, ctypes.c_void_p]),
     "fa2_topk_indices": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [_i64p] * 2 + [ctypes.c_void_p]),
+    # ... on an e4m3 index-key cache: q_dtype (FA2_DTYPE_E4M3: q_idx in codes), q_idx k_codes k_scales weights logits cache_seqlens block_table, the seven
+    # sizes, the q triple, the code (bytes) / scale (elements) / weights / logits pairs, the block-table row stride, stream.  Its quantising append,
+    # uniform and packed: dtype, k_idx k_codes k_scales [cu_seqlens] cache_seqlens block_table, B Nnew | total, D_idx capacity page_size num_pages, the
+    # k_idx / code / scale pairs, the block-table row stride, scale_pow2, stream
+    "fa2_mla_indexer_logits_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 7 + [_i64p] * 5 + [ctypes.c_int64, ctypes.c_void_p]),
+    "fa2_kvcache_append_mla_index_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [_i64p] * 3 +
+                                         [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "fa2_kvcache_append_mla_index_varlen_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 4 +
+                                                [_i64p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     # ... on an e4m3 latent cache of 656-byte rows: the twins' lists (kv_cache the byte cache, kv_strides in bytes); the twins' plan and workspace queries
     "fa2_fwd_decode_mla_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +
                                [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

@@ -879,6 +879,54 @@ int fa2_mla_indexer_logits(int dtype, const void* q_idx, const void* k_idx_cache
 int fa2_topk_indices(const float* logits, int* indices, const int* cache_seqlens, int B, int Nq, int capacity, int topk,
                      const int64_t logits_strides[2], const int64_t indices_strides[2], void* hip_stream);
 
+/* ---- ... on an E4M3 index-key cache (DeepGEMM's fp8_mqa_logits / fp8_paged_mqa_logits, vLLM's indexer cache): per token 128
+ * OCP e4m3 codes and ONE float32 scale, 132 bytes instead of 256.  Codes and scales are addressed separately —
+ *   k_codes   : 128 bytes per token; BYTE strides code_strides {batch | page, row}; pointer and strides 4-byte aligned, the row stride positive
+ *   k_scales  : one float32 per token; ELEMENT strides scale_strides {batch | page, row}, non-negative; pointer 4-byte aligned
+ * — so both arrangements in use are views of one buffer: ROWS of 132 bytes (bytes 0 .. 127 the codes, 128 .. 131 the scale: k_scales = k_codes + 128,
+ * code_strides {.., 132}, scale_strides {.., 33}; a row's codes are then only 4-byte aligned) and BLOCKS (inside a page the page_size x 128 code bytes,
+ * then the page_size scales: code_strides {132 page_size, 128}, scale_strides {33 page_size, 1}).  capacity, page_size, num_pages, block_table and the
+ * lengths mean what they mean in fa2_mla_indexer_logits.
+ * fa2_mla_indexer_logits_fp8: with pos = len_b - Nq + i,
+ *   logits[b, i, s] = k_scales[b, s] * sum_h w'[b, i, h] * max(0, sum_d q8[b, i, h, d] * k8[b, s, d])   for 0 <= s <= pos,   -inf beyond; every element
+ * is written.  q8 and k8 are the codes as real numbers; the dot product accumulates in f32 on the matrix pipe (v_mfma_f32_16x16x128_f8f6f4, one per 16
+ * heads x 16 keys); the key scale multiplies once, after the head sum (for the positive scales the append writes this equals descaling the key; a NaN
+ * or negative scale gives what the formula gives).  q_dtype FA2_DTYPE_E4M3: q_idx holds codes (q_strides in bytes, multiples of 16), w' = weights — the
+ * caller folded the q scales into them.  q_dtype FA2_DTYPE_F16 / _BF16: the kernel quantises q_idx per (token, head) in f32 with correctly rounded
+ * divisions — s = amax / 448 (an all-zero head: 1), code = e4m3_rne(clamp(x / s, +-448)), w' = weights * s — and the result equals the call on those
+ * codes and weights bit for bit.  One fixed summation order: paged equals contiguous bit for bit, rows equal blocks.  Dead rows, dead scales and dead
+ * pages are never addressed; page ids are clamped into the pool.
+ * Checked in fa2_mla_indexer_logits' order, the new arguments after the existing ones inside each class: null pointers (.., k_scales, scale_strides);
+ * sizes (.., a negative scale stride); head dims; alignment (q_idx 16 bytes with strides that are multiples of 8 elements / 16 codes; weights, logits,
+ * cache_seqlens, block_table 4 bytes; then k_codes, k_scales and code_strides as above); q_dtype; FA2_ERR_GRID.
+ * Kernel (FA2_KERNEL_HIP_MLA_INDEXER_FP8, csrc/fa2_mla_indexer_fp8.hip.h): the 16-bit kernel's grid and work split, no LDS, no barrier.
+ * fa2_kvcache_append_mla_index_fp8 / _varlen_fp8: the quantising append that writes this cache.  k_idx (f16 / bf16) B x Nnew x 128 with element
+ * strides k_idx_strides {batch, row} — the packed call: total x 128 with {unused, row} under cu_seqlens [B + 1] as in fa2_kvcache_append_mla_varlen —
+ * becomes codes and a scale at key position len_b - Nnew + i: scale = amax / 448 in f32 (an all-zero row: 1; scale_pow2 != 0: the smallest power of
+ * two at or above it, from the exponent bits — ue8m0), code = e4m3_rne(clamp(x / scale, +-448)); a NaN input gives a NaN code and does not count in
+ * amax.  fa2_kvcache_append_mla's guarantees hold: a token outside the cache, behind a page id outside the pool or owned by no sequence writes
+ * nothing and is never clamped onto a live row; no device value moves a write outside the buffers; the host reads none.
+ * Checked in this order: null pointers (cu_seqlens when packed, block_table when paged); sizes (B, Nnew, D_idx < 1, total < 0, the paging rules, a
+ * negative block-table / scale / batch stride); D_idx != 128 (FA2_ERR_HEAD_DIM); alignment (k_idx 16 bytes, strides multiples of 8, a positive row
+ * stride; the cache as above; cache_seqlens, cu_seqlens, block_table 4 bytes); dtype; FA2_ERR_GRID (more than 2^31 - 1 tokens).  total == 0 returns
+ * FA2_OK without a launch.  Kernel: csrc/fa2_kvappend_mla_index_fp8.hip.h (sixteen lanes per token, vector stores only). */
+#define FA2_DTYPE_E4M3 3         /* q_idx of fa2_mla_indexer_logits_fp8 only */
+enum { FA2_KERNEL_HIP_MLA_INDEXER_FP8 = 13 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+int fa2_mla_indexer_logits_fp8(int q_dtype, const void* q_idx, const void* k_codes, const float* k_scales, const float* weights, float* logits,
+                               const int* cache_seqlens, const int* block_table,
+                               int B, int H_idx, int Nq, int D_idx, int capacity, int page_size, int num_pages,
+                               const int64_t q_strides[3], const int64_t code_strides[2], const int64_t scale_strides[2],
+                               const int64_t w_strides[2], const int64_t logits_strides[2], int64_t block_table_stride, void* hip_stream);
+int fa2_kvcache_append_mla_index_fp8(int dtype, const void* k_idx, void* k_codes, float* k_scales, const int* cache_seqlens, const int* block_table,
+                                     int B, int Nnew, int D_idx, int capacity, int page_size, int num_pages,
+                                     const int64_t k_idx_strides[2], const int64_t code_strides[2], const int64_t scale_strides[2],
+                                     int64_t block_table_stride, int scale_pow2, void* hip_stream);
+int fa2_kvcache_append_mla_index_varlen_fp8(int dtype, const void* k_idx, void* k_codes, float* k_scales, const int* cu_seqlens,
+                                            const int* cache_seqlens, const int* block_table,
+                                            int B, int64_t total, int D_idx, int capacity, int page_size, int num_pages,
+                                            const int64_t k_idx_strides[2], const int64_t code_strides[2], const int64_t scale_strides[2],
+                                            int64_t block_table_stride, int scale_pow2, void* hip_stream);
+
 /* ---- ... on an e4m3 latent cache (the FP8 KV cache of DeepSeek-V3.2 servers: FlashMLA's, vLLM's fp8_ds_mla), dense and sparse.  One row per token,
  * 656 bytes instead of 1 152:
  *   bytes   0 .. 511   OCP e4m3 codes of latent columns 0 .. 511 (the part that is also the value)

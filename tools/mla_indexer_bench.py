@@ -1,7 +1,7 @@
 """The lightning indexer of sparse MLA decode: mla_indexer_topk against what a user of flash_attention_decode_mla(indices=) wrote before it existed, same
 box, interleaved rounds, median of per-round event times with the spread of the rounds beside it (tools/mla_sparse_bench.py's method).
 
-    python tools/mla_indexer_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX]
+    python tools/mla_indexer_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX] [--fp8]
 
 Routes
     indexer       mla_indexer_topk(q_idx, k_idx_cache, weights, lens, topk=2048): two launches
@@ -24,7 +24,8 @@ import torch  # noqa: E402
 
 from benchlib import graphed, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
-from rocwmma_fattn.FlashAttn import mla_indexer_logits, mla_indexer_topk, topk_indices  # noqa: E402
+from rocwmma_fattn.FlashAttn import (kvcache_append_mla_index, mla_index_cache_from_fp8, mla_index_cache_to_fp8, mla_indexer_logits,  # noqa: E402
+                                     mla_indexer_topk, topk_indices)
 
 H, D, TOPK, BF16 = 64, 128, 2048, torch.bfloat16
 ROWS = [("%d_b%d_%dk%s" % (n, B, keys // 1024, "_pg64" if paged else ""), B, keys, paged)
@@ -88,12 +89,62 @@ def row(out, label, B, keys, paged, rounds, iters):
     sys.stdout.flush()
 
 
+def row8(out, label, B, keys, paged, rounds, iters):
+    if paged:                                          # (the three layouts are one row here)
+        return
+    dev = torch.device("cuda", 0)
+    q = torch.randn((B, 1, H, D), device=dev, dtype=BF16)
+    k = torch.randn((B, keys, D), device=dev, dtype=BF16)
+    w = torch.randn((B, 1, H), device=dev) * H ** -0.5
+    lens = torch.full((B,), keys, dtype=torch.int32, device=dev)
+    rows = mla_index_cache_to_fp8(k)
+    pages = B * keys // 64
+    perm = torch.randperm(pages, device=dev)
+    pool = torch.empty((pages, 64, 132), dtype=torch.uint8, device=dev)
+    pool[perm] = rows.view(pages, 64, 132)
+    bt = perm.view(B, keys // 64).int()
+    buf = torch.cat([pool[:, :, :128].reshape(pages, -1), pool[:, :, 128:].reshape(pages, -1)], 1).contiguous()
+    blocks = (buf[:, :64 * 128].view(pages, 64, 128), buf[:, 64 * 128:].view(torch.float32))
+    new, at = torch.randn((B, 1, D), device=dev, dtype=BF16), (torch.arange(B, device=dev), lens.long() - 1)
+    caches = {"16-bit": (k, None), "e4m3 rows": (rows, None), "e4m3 rows pg64": (pool, bt), "e4m3 blocks pg64": (blocks, bt)}
+    fns = {}
+    for n, (c, t) in caches.items():
+        fns[n] = lambda c=c, t=t: mla_indexer_topk(q, c, w, lens, block_table=t, topk=TOPK)
+        fns[n + " logits"] = lambda c=c, t=t: mla_indexer_logits(q, c, w, lens, block_table=t)
+    fns["dequant + 16-bit"] = lambda: mla_indexer_topk(q, mla_index_cache_from_fp8(rows, BF16), w, lens, topk=TOPK)
+    fns["append"] = lambda: kvcache_append_mla_index(rows, new, lens)
+    fns["append torch"] = lambda: rows.index_put_(at, mla_index_cache_to_fp8(new[:, 0]))
+    with torch.no_grad():
+        a = fns["e4m3 rows logits"]()
+        if not all(torch.equal(a, fns[n + " logits"]()) for n in ("e4m3 rows pg64", "e4m3 blocks pg64")):
+            raise SystemExit("mla_indexer_bench: %s: the e4m3 layouts disagree" % label)
+        t = interleaved(fns, rounds, iters)
+    lines = ["%-12s B%d Nq1 H_idx %d topk %d of %d keys, bf16 q" % (label, B, H, TOPK, keys)]
+    for n, (med, lo, hi) in t.items():
+        rel = ""
+        base = t.get("16-bit logits" if n.endswith("logits") else "16-bit")
+        if n.endswith("logits"):
+            per = 256 if n.startswith("16") else 132
+            rel = "  %.2f TB/s of valid key bytes (%d MB)" % (B * keys * per / (med * 1e-3) / 1e12, B * keys * per >> 20)
+        if n.startswith("e4m3") or n.startswith("dequant"):
+            real = abs(med - base[0]) > (hi - lo) + (base[2] - base[1])
+            rel += "  %.2fx the 16-bit time (%s the sum of the spreads)" % (med / base[0], "beyond" if real else "WITHIN")
+        lines.append("    %-24s %9.1f us  (rounds %.1f .. %.1f, spread %.1f %%)%s" % (n, med * 1e3, lo * 1e3, hi * 1e3, 100.0 * (hi - lo) / med, rel))
+    for line in lines:
+        print(line)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+    sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--only", default="", help="rows whose label starts with this")
+    ap.add_argument("--fp8", action="store_true", help="the e4m3 index-key cache rows (section 35) instead of the 16-bit ones")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mla_indexer_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
@@ -105,7 +156,7 @@ def main():
         out.write(head + "\n")
     for r in ROWS:
         if r[0].startswith(a.only):
-            row(out, *r, a.rounds, a.iters)
+            (row8 if a.fp8 else row)(out, *r, a.rounds, a.iters)
 
 
 if __name__ == "__main__":
