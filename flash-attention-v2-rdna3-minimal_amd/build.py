@@ -98,6 +98,9 @@ UNITS = [
     # ... on an e4m3 index-key cache: the FP8-MFMA logits for the three q forms and that cache's quantising append (no I/O dtype in the cache: one unit;
     # NaNs honoured for the e4m3 clamp, as in the appends below)
     ("mla_indexer_fp8_hip", "mla_indexer_fp8_hip.cpp", ["-fhonor-nans"] + NO_PACKED_F32),
+    # ... and its packed (prefill) form: the keys stationary in registers, the tokens streaming past them through LDS; the same flags, so that the
+    # quantisation and the epilogue are the same instructions
+    ("mla_indexer_prefill_fp8_hip", "mla_indexer_prefill_fp8_hip.cpp", ["-fhonor-nans"] + NO_PACKED_F32),
     # KV-cache append (rotary, e4m3 quantisation): NaNs honoured, so that the e4m3 clamp lets a NaN through to the convert
     ("kvappend_hip_f16", "kvappend_hip.cpp", ["-DFA2_TU_BF16=0", "-fhonor-nans"]),
     ("kvappend_hip_bf16", "kvappend_hip.cpp", ["-DFA2_TU_BF16=1", "-fhonor-nans"]),
@@ -122,7 +125,7 @@ FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")
 GENERATORS = [os.path.join("gen", "fwd_d128_gen.py"), os.path.join("gen", "fwd_m16_gen.py"), os.path.join("gen", "fwd_m16_d256_gen.py"), os.path.join("gen", "bwd_d128_gen.py"),
               os.path.join("gen", "bwd_dq_m16_gen.py"), os.path.join("gen", "bwd_dkv_m16_gen.py")]
-HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_decode_mla_sweep.h", "fa2_decode_mla_sparse.hip.h", "fa2_decode_mla_sparse_sweep.h", "fa2_mla_indexer.hip.h", "fa2_topk_select.hip.h", "fa2_mla_indexer_fp8.hip.h", "fa2_kvappend_mla_index_fp8.hip.h", "fa2_kvappend.hip.h", "fa2_kvappend_mla.hip.h", "fa2_kvappend_mla_fp8.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
+HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_decode_mla_sweep.h", "fa2_decode_mla_sparse.hip.h", "fa2_decode_mla_sparse_sweep.h", "fa2_mla_indexer.hip.h", "fa2_topk_select.hip.h", "fa2_mla_indexer_fp8.hip.h", "fa2_mla_indexer_prefill_fp8.hip.h", "fa2_kvappend_mla_index_fp8.hip.h", "fa2_kvappend.hip.h", "fa2_kvappend_mla.hip.h", "fa2_kvappend_mla_fp8.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
            os.path.join(INCLUDE, "fa2_gfx950.h"), os.path.join("gen", "isa.py"), os.path.join("gen", "sched.py"), os.path.join("gen", "gen_driver.py")] + GENERATORS
 
 HIPCC_FLAGS = [

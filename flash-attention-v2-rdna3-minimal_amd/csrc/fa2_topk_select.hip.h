@@ -36,6 +36,7 @@ struct TopkParams {
     int B, Nq, topk;
     int64_t capacity_keys;
     int64_t ls[2], is[2];       // element strides {batch, row}
+    const int* cu;              // the packed geometry alone: cu_seqlens_q [B + 1], device; the row is packed token t and Nq counts all of them
 };
 
 // The order-preserving image of a float32's bits: a < b as floats <=> topk_key(a) < topk_key(b), with every NaN at -inf's place and -0 at +0's.
@@ -48,15 +49,28 @@ FA2_DEC_HD inline uint32_t topk_key(uint32_t bits) {
 #if defined(__HIPCC__)
 
 // (a template so that the header can be included by more than one unit: topk_select_hip.cpp alone instantiates it)
-template <int THREADS>
+// PACKED (fa2_topk_indices_varlen): the row is packed token t of [total_q, capacity]; kvappend_varlen_token names its sequence s,
+// i = t - cu[s] and Nq_s, pos = clamp_len(len_s) - Nq_s + i, and a row no sequence owns is all -1 (as is one at a negative position, by n <= 0).
+template <int THREADS, bool PACKED = false>
 __global__ __launch_bounds__(THREADS) void topk_select_kernel(const TopkParams p) {
     static_assert(THREADS == kTopkThreads, "one workgroup shape");
     __shared__ uint32_t hist[256 * kTopkCopies];
     __shared__ uint32_t wsum[2][kTopkWaves];
     __shared__ uint32_t found[2];
-    const int row = blockIdx.x, b = row / p.Nq, i = row - b * p.Nq;
+    int b, i, pos;
+    if constexpr (PACKED) {
+        int s, si, nq;
+        const bool owned = kvappend_varlen_token(p.cu, p.B, blockIdx.x, &s, &si, &nq);
+        pos = owned ? decode_clamp_len(p.lens[s], p.capacity_keys) - nq + si : -1;
+        b = 0;                                                            // (the row strides alone address a packed row)
+        i = blockIdx.x;
+    } else {
+        const int row = blockIdx.x;
+        b = row / p.Nq;
+        i = row - b * p.Nq;
+        pos = decode_clamp_len(p.lens[b], p.capacity_keys) - p.Nq + i;
+    }
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int pos = decode_clamp_len(p.lens[b], p.capacity_keys) - p.Nq + i;
     const int n = pos + 1, topk = p.topk;
     int* const out = p.idx + b * p.is[0] + i * p.is[1];
     if (n <= topk) {                                                      // every position is selected (n <= 0: none): no logit is read
@@ -133,5 +147,7 @@ __global__ __launch_bounds__(THREADS) void topk_select_kernel(const TopkParams p
 namespace fa2 {
 // topk_select_hip.cpp: the kernel above, one workgroup per row (b, i)
 FA2_HIDDEN int launch_topk_select(const TopkParams& p, hipStream_t stream);
+// ... and its packed form, one workgroup per packed token (p.Nq = total_q, p.cu set)
+FA2_HIDDEN int launch_topk_select_varlen(const TopkParams& p, hipStream_t stream);
 }  // namespace fa2
 #endif

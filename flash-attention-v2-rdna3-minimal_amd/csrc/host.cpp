@@ -26,6 +26,7 @@
 #include "fa2_kvappend_mla_fp8.hip.h"      // ... and the quantising append of its e4m3 form: the launcher
 #include "fa2_mla_indexer_fp8.hip.h"       // the indexer on an e4m3 index-key cache: the logits kernel's parameter block and launcher
 #include "fa2_kvappend_mla_index_fp8.hip.h"      // ... and that cache's quantising append
+#include "fa2_mla_indexer_prefill_fp8.hip.h"     // ... and the packed (prefill) logits on it
 
 #include <algorithm>
 #include <cmath>
@@ -2084,6 +2085,57 @@ int fa2_mla_indexer_logits_fp8(int q_dtype, const void* q_idx, const void* k_cod
     p.bts = block_table_stride;
     const int form = q_dtype == FA2_DTYPE_E4M3 ? fa2::kIdxQE4M3 : q_dtype == FA2_DTYPE_BF16 ? fa2::kIdxQBF16 : fa2::kIdxQF16;
     return fa2::launch_mla_indexer_logits_fp8(form, p, (hipStream_t)hip_stream);
+}
+
+// ---- ... for packed query tokens (csrc/fa2_mla_indexer_prefill_fp8.hip.h) and the packed row geometry of the selection.  The
+// uniform calls' checks in their order, the new arguments' appended inside each class.
+int fa2_mla_indexer_logits_varlen_fp8(int q_dtype, const void* q_idx, const void* k_codes, const float* k_scales, const float* weights, float* logits,
+                                      const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, int B, int H_idx, int64_t total_q, int D_idx,
+                                      int capacity, int page_size, int num_pages, const int64_t q_strides[2], const int64_t code_strides[2],
+                                      const int64_t scale_strides[2], int64_t w_stride, int64_t logits_stride, int64_t block_table_stride, void* hip_stream) {
+    if (any_null({q_idx, k_codes, weights, logits, cache_seqlens, q_strides, code_strides, k_scales, scale_strides, cu_seqlens_q}) ||
+        (page_size > 0 && !block_table))
+        return FA2_ERR_NULL_POINTER;
+    CacheDesc c;
+    c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    if (B < 1 || H_idx < 1 || total_q < 0 || D_idx < 1 || !cache_paging_ok(c) || c.capacity_keys() > 0x7fffffffLL - 64 || !cache_extent_ok(c)) return FA2_ERR_BAD_SHAPE;
+    if (w_stride < 0 || logits_stride < 0 || block_table_stride < 0 || scale_strides[0] < 0 || scale_strides[1] < 0) return FA2_ERR_BAD_SHAPE;
+    if (!fa2::mla_indexer_heads_ok(H_idx) || D_idx != fa2::kIdxD) return FA2_ERR_HEAD_DIM;
+    const int q_mult = q_dtype == FA2_DTYPE_E4M3 ? 16 : 8;       // a 16-byte load: 16 codes or 8 values
+    if (!aligned16(q_idx) || q_strides[0] < 0 || q_strides[1] < 0 || (q_strides[0] | q_strides[1]) % q_mult != 0 ||
+        ((reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(cache_seqlens) |
+          reinterpret_cast<uintptr_t>(block_table)) & 3u) || !index_cache_aligned(k_codes, k_scales, code_strides) ||
+        (reinterpret_cast<uintptr_t>(cu_seqlens_q) & 3u))
+        return FA2_ERR_ALIGNMENT;
+    if (q_dtype != FA2_DTYPE_F16 && q_dtype != FA2_DTYPE_BF16 && q_dtype != FA2_DTYPE_E4M3) return FA2_ERR_DTYPE;
+    if (fa2::mla_indexer_prefill_blocks(total_q) > 65535) return FA2_ERR_GRID;
+    if (total_q == 0) return FA2_OK;                                 // an empty token buffer: nothing to launch
+    fa2::MlaIndexerPrefillParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = q_idx; p.k = static_cast<const uint8_t*>(k_codes); p.ksc = k_scales; p.w = weights; p.logits = logits; p.cu = cu_seqlens_q; p.lens = cache_seqlens;
+    p.bt = page_size > 0 ? block_table : nullptr;
+    p.B = B; p.H = H_idx; p.total_q = (int)total_q; p.page_size = page_size; p.num_pages = num_pages; p.capacity_keys = c.capacity_keys();
+    for (int i = 0; i < 2; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = code_strides[i]; p.ss[i] = scale_strides[i]; }
+    p.ws = w_stride; p.ls = logits_stride; p.bts = block_table_stride;
+    const int form = q_dtype == FA2_DTYPE_E4M3 ? fa2::kIdxQE4M3 : q_dtype == FA2_DTYPE_BF16 ? fa2::kIdxQBF16 : fa2::kIdxQF16;
+    return fa2::launch_mla_indexer_prefill_fp8(form, p, (hipStream_t)hip_stream);
+}
+
+int fa2_topk_indices_varlen(const float* logits, int* indices, const int* cu_seqlens_q, const int* cache_seqlens, int B, int64_t total_q, int capacity, int topk,
+                            int64_t logits_stride, int64_t indices_stride, void* hip_stream) {
+    if (any_null({logits, indices, cache_seqlens, cu_seqlens_q})) return FA2_ERR_NULL_POINTER;
+    if (B < 1 || total_q < 0 || capacity < 1 || capacity > 0x7fffffff - 64 || topk < 1 || topk > 0x7fffffff - 64) return FA2_ERR_BAD_SHAPE;
+    if (logits_stride < 0 || indices_stride < 0) return FA2_ERR_BAD_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(indices) | reinterpret_cast<uintptr_t>(cache_seqlens) |
+         reinterpret_cast<uintptr_t>(cu_seqlens_q)) & 3u)
+        return FA2_ERR_ALIGNMENT;
+    if (total_q > 0x7fffffffLL) return FA2_ERR_GRID;
+    if (total_q == 0) return FA2_OK;
+    fa2::TopkParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.logits = logits; p.idx = indices; p.lens = cache_seqlens; p.cu = cu_seqlens_q; p.B = B; p.Nq = (int)total_q; p.topk = topk; p.capacity_keys = capacity;
+    p.ls[1] = logits_stride; p.is[1] = indices_stride;
+    return fa2::launch_topk_select_varlen(p, (hipStream_t)hip_stream);
 }
 
 // cu_seqlens null: the uniform call (tokens = B * Nnew); else the packed one (tokens = total, k_idx_strides[0] unused)

@@ -28,7 +28,7 @@ from . import _fa2_lib
 __all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
            "kvcache_append_varlen", "flash_attention_decode_mla", "kvcache_append_mla", "kvcache_append_mla_varlen", "mla_cache_to_fp8",
            "mla_cache_from_fp8", "mla_indexer_logits", "topk_indices", "mla_indexer_topk", "mla_indexer_q_to_fp8", "mla_index_cache_to_fp8",
-           "mla_index_cache_from_fp8", "kvcache_append_mla_index"]
+           "mla_index_cache_from_fp8", "kvcache_append_mla_index", "mla_indexer_logits_varlen", "topk_indices_varlen", "mla_indexer_topk_varlen"]
 
 
 class _FlashAttnWmma:
@@ -2130,6 +2130,110 @@ def mla_indexer_topk(q_idx, k_idx_cache, weights, cache_seqlens, block_table=Non
     _check_topk(who, topk)
     logits = _indexer_logits(who, q_idx, k_idx_cache, weights, cache_seqlens, block_table)
     idx = _topk_launch(logits, cache_seqlens, topk)
+    return (idx, logits) if return_logits else idx
+
+
+def _indexer_prepare_varlen(who, q_idx, k_idx_cache, weights, cu_seqlens_q, cache_seqlens, block_table):
+    """Every argument check of mla_indexer_logits_varlen; nothing is launched here.  -> (q, k8, weights, B, capacity, page_size, num_pages)"""
+    k8 = _index_cache8(who, k_idx_cache)
+    if k8 is None:
+        raise ValueError("fa2: %s serves the e4m3 index-key cache (rows of %d bytes, or (codes, scales)); on a 16-bit index-key cache call the uniform "
+                         "mla_indexer_logits per sequence" % (who, _IDX_ROW8))
+    if not all(torch.is_tensor(t) for t in (q_idx, weights, cache_seqlens)) or q_idx.dim() != 3 or weights.dim() != 2:
+        raise ValueError("fa2: %s takes packed q_idx [total_q, H_idx, 128], weights [total_q, H_idx], cu_seqlens_q [B + 1] and cache_seqlens [B]" % who)
+    _no_grad_inputs(who, q_idx, weights)
+    q8 = _FP8_CACHE is not None and q_idx.dtype == _FP8_CACHE
+    if (q_idx.dtype not in (torch.float16, torch.bfloat16) and not q8) or weights.dtype != torch.float32:
+        raise ValueError("fa2: %s takes fp16, bf16 or float8_e4m3fn q_idx and float32 weights, got %s %s" % (who, q_idx.dtype, weights.dtype))
+    total, H, D = q_idx.shape
+    if D != _IDX_D:
+        raise ValueError("fa2: %s serves index rows of %d columns, got q_idx %s" % (who, _IDX_D, tuple(q_idx.shape)))
+    if H not in _IDX_HEADS or total > 65535 * 128 or tuple(weights.shape) != (total, H):
+        raise ValueError("fa2: %s serves H_idx in %s with weights [total_q, H_idx] and at most 65535 * 128 packed tokens, got q_idx %s weights %s"
+                         % (who, _IDX_HEADS, tuple(q_idx.shape), tuple(weights.shape)))
+    B = _check_cu("cu_seqlens_q", cu_seqlens_q)
+    capacity, page_size, num_pages = _indexer_geometry(who, B, k8.shape, k8.shape, block_table, cache_seqlens, q_idx.device, k8.shape[2])
+    if not q_idx.is_cuda or any(d != q_idx.device for d in (k8.device, weights.device, cu_seqlens_q.device)):
+        raise ValueError("fa2: %s takes q_idx, k_idx_cache, weights, cu_seqlens_q, cache_seqlens and block_table on one ROCm device (no CPU path in this "
+                         "operator)" % who)
+    mult = 16 if q8 else 8
+    ok = q_idx.stride(2) == 1 and q_idx.stride(0) % mult == 0 and q_idx.stride(1) % mult == 0 and q_idx.data_ptr() % 16 == 0
+    return q_idx if ok else q_idx.contiguous(), k8, weights if weights.stride(1) == 1 else weights.contiguous(), B, capacity, page_size, num_pages
+
+
+def _indexer_logits_launch_varlen(q, k8, w, cu_seqlens_q, cache_seqlens, block_table, B, capacity, page_size, num_pages):
+    total, H, _ = q.shape
+    logits = torch.empty((total, capacity * max(page_size, 1)), dtype=torch.float32, device=q.device)
+    if total == 0:                                   # an empty token buffer: nothing to launch
+        return logits
+    dev = _device_index(q)
+    code = _fa2_lib.FA2_DTYPE_E4M3 if q.dtype == _FP8_CACHE else _dtype_code(q)
+    with torch.cuda.device(dev):
+        rc = _fa2_lib.load().fa2_mla_indexer_logits_varlen_fp8(
+            code, q.data_ptr(), k8.code_ptr, k8.scale_ptr, w.data_ptr(), logits.data_ptr(), cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(),
+            None if block_table is None else block_table.data_ptr(), B, H, total, _IDX_D, capacity, page_size, num_pages,
+            _fa2_lib.strides2(q.stride(0), q.stride(1)), k8.code_strides, k8.scale_strides, w.stride(0), logits.stride(0),
+            0 if block_table is None else block_table.stride(0), _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return logits
+
+
+def _topk_prepare_varlen(who, logits, cu_seqlens_q, cache_seqlens, topk):
+    if not torch.is_tensor(logits) or logits.dim() != 2 or logits.dtype != torch.float32 or not 1 <= logits.shape[1] <= _TOPK_MAX:
+        raise ValueError("fa2: %s takes logits as a float32 tensor [total_q, capacity]" % who)
+    _no_grad_inputs(who, logits)
+    _check_topk(who, topk)
+    B = _check_cu("cu_seqlens_q", cu_seqlens_q)
+    _check_lens(who, cache_seqlens, B, logits.device)
+    if not logits.is_cuda or cu_seqlens_q.device != logits.device:
+        raise ValueError("fa2: %s takes logits, cu_seqlens_q and cache_seqlens on one ROCm device (no CPU path in this operator)" % who)
+    return logits if logits.stride(1) == 1 else logits.contiguous()
+
+
+def _topk_launch_varlen(logits, cu_seqlens_q, cache_seqlens, topk):
+    total, capacity = logits.shape
+    idx = torch.empty((total, topk), dtype=torch.int32, device=logits.device)
+    if total == 0:
+        return idx
+    dev = _device_index(logits)
+    with torch.cuda.device(dev):
+        rc = _fa2_lib.load().fa2_topk_indices_varlen(logits.data_ptr(), idx.data_ptr(), cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(),
+                                                     cu_seqlens_q.numel() - 1, total, capacity, topk, logits.stride(0), idx.stride(0), _raw_stream(dev))
+    _fa2_lib.check(rc)
+    return idx
+
+
+def mla_indexer_logits_varlen(q_idx, k_idx_cache, weights, cu_seqlens_q, cache_seqlens, block_table=None):
+    """mla_indexer_logits for PACKED query tokens on an e4m3 index-key cache: the indexer of a continuous-batching step that mixes decode rows and
+    prefill chunks of different lengths.  q_idx [total_q, H_idx, 128] float8_e4m3fn, fp16 or bf16 (H_idx in 16, 32, 48, 64), weights float32
+    [total_q, H_idx], cu_seqlens_q int32 [B + 1] on the device: sequence s owns the rows [cu[s], cu[s + 1]) — Nq_s may be 0 and rows beyond cu[B]
+    belong to nobody, as in kvcache_append_mla_index(cu_seqlens=).  k_idx_cache in either e4m3 form mla_indexer_logits takes (rows of 132 bytes, or
+    (codes, scales)), contiguous or paged under block_table; never copied.  cache_seqlens int32 [B] counts the valid keys INCLUDING the sequence's
+    new tokens.  -> float32 [total_q, capacity]: for row t of sequence s with i = t - cu[s], pos = len_s - Nq_s + i, the uniform call's value for
+    j <= pos and -inf beyond; a row nobody owns, or one at a negative position, is all -inf; every element is written.  The rows of sequence s equal
+    mla_indexer_logits on that sequence alone bit for bit.  No value of cu_seqlens_q, cache_seqlens or block_table moves an access outside the
+    buffers; the host reads none and takes no maximum length, so the call can be captured.  A 16-bit index-key cache is refused (call the uniform
+    operator per sequence).  Inference only.  C-ABI fa2_mla_indexer_logits_varlen_fp8."""
+    args = _indexer_prepare_varlen("mla_indexer_logits_varlen", q_idx, k_idx_cache, weights, cu_seqlens_q, cache_seqlens, block_table)
+    return _indexer_logits_launch_varlen(*args[:3], cu_seqlens_q, cache_seqlens, block_table, *args[3:])
+
+
+def topk_indices_varlen(logits, cu_seqlens_q, cache_seqlens, topk):
+    """topk_indices for packed rows: logits float32 [total_q, capacity], cu_seqlens_q int32 [B + 1], cache_seqlens int32 [B] -> int32 [total_q, topk].
+    Row t of sequence s selects over [0, pos], pos = len_s - Nq_s + (t - cu[s]), by topk_indices' rules (ascending positions, ties to the lowest
+    positions, NaN as -inf, pos + 1 <= topk reads no logit); a row nobody owns, or one at a negative position, is all -1.  The rows [cu[s], cu[s + 1])
+    viewed as [1, Nq_s, topk] are the indices flash_attention_decode_mla(..., indices=) takes for sequence s.  C-ABI fa2_topk_indices_varlen."""
+    return _topk_launch_varlen(_topk_prepare_varlen("topk_indices_varlen", logits, cu_seqlens_q, cache_seqlens, topk), cu_seqlens_q, cache_seqlens, topk)
+
+
+def mla_indexer_topk_varlen(q_idx, k_idx_cache, weights, cu_seqlens_q, cache_seqlens, block_table=None, topk=2048, return_logits=False):
+    """mla_indexer_logits_varlen, then topk_indices_varlen, on the current stream: the indexer of a packed step.  Every check of both halves runs
+    before the first launch.  -> indices int32 [total_q, topk], with return_logits=True also the float32 logits [total_q, capacity]."""
+    who = "mla_indexer_topk_varlen"
+    _check_topk(who, topk)
+    args = _indexer_prepare_varlen(who, q_idx, k_idx_cache, weights, cu_seqlens_q, cache_seqlens, block_table)
+    logits = _indexer_logits_launch_varlen(*args[:3], cu_seqlens_q, cache_seqlens, block_table, *args[3:])
+    idx = _topk_launch_varlen(logits, cu_seqlens_q, cache_seqlens, topk)
     return (idx, logits) if return_logits else idx
 
 

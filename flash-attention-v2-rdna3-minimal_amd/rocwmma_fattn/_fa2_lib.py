@@ -64,6 +64,7 @@ class DecodeMlaPlan(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+FA2_KERNEL_HIP_MLA_INDEXER_PREFILL = 14                                                                 # ... of fa2_mla_indexer_logits_varlen_fp8
 FA2_KERNEL_HIP_MLA_INDEXER_FP8 = 13                                                                     # ... of fa2_mla_indexer_logits_fp8
 FA2_KERNEL_HIP_MLA_INDEXER = 12                                                                         # the logits kernel of fa2_mla_indexer_logits
 FA2_KERNEL_HIP_DECODE_MLA_SPARSE = 11                                                                 # ... of fa2_fwd_decode_mla_sparse_plan
@@ -208,6 +209,9 @@ SYMBOLS = {
     # uniform and packed: dtype, k_idx k_codes k_scales [cu_seqlens] cache_seqlens block_table, B Nnew | total, D_idx capacity page_size num_pages, the
     # k_idx / code / scale pairs, the block-table row stride, scale_pow2, stream
     "fa2_mla_indexer_logits_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 7 + [_i64p] * 5 + [ctypes.c_int64, ctypes.c_void_p]),
+    "fa2_mla_indexer_logits_varlen_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 8 + [ctypes.c_int] * 2 + [ctypes.c_int64] + [ctypes.c_int] * 4 +
+                                          [_i64p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p]),
+    "fa2_topk_indices_varlen": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_int64] * 2 + [ctypes.c_void_p]),
     "fa2_kvcache_append_mla_index_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [_i64p] * 3 +
                                          [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "fa2_kvcache_append_mla_index_varlen_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 4 +

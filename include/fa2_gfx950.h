@@ -927,6 +927,36 @@ int fa2_kvcache_append_mla_index_varlen_fp8(int dtype, const void* k_idx, void* 
                                             const int64_t k_idx_strides[2], const int64_t code_strides[2], const int64_t scale_strides[2],
                                             int64_t block_table_stride, int scale_pow2, void* hip_stream);
 
+/* ---- ... for PACKED query tokens (the prefill side of the indexer): one token buffer for a continuous-batching step that mixes
+ * decode rows and prefill chunks of different lengths, on the e4m3 index-key cache above (its two views, contiguous or paged).
+ *   cu_seqlens_q : int32 [B + 1], device: sequence s owns the packed tokens [cu[s], cu[s + 1]) — fa2_kvappend_varlen_token's rule, zero-length sequences
+ *                  and total_q > cu[B] included.  Unvalidated device data: no value in it moves an access outside the buffers.
+ *   q_idx        : total_q x H_idx x 128, q_strides {token, head} (bytes for FA2_DTYPE_E4M3, multiples of 16; elements for 16 bits, multiples of 8)
+ *   weights      : total_q x H_idx f32, row stride w_stride, the head dim contiguous;  logits : total_q x capacity_keys f32, row stride logits_stride
+ * fa2_mla_indexer_logits_varlen_fp8: for token t of sequence s, i = t - cu[s], Nq_s = cu[s + 1] - cu[s], pos = clamp(len_s, 0, capacity_keys) - Nq_s + i,
+ *   logits[t, j] = k_scales[s, j] * sum_h w'[t, h] * max(0, sum_d q8[t, h, d] * k8[s, j, d])   for 0 <= j <= pos,   -inf beyond; every element of
+ * total_q x capacity_keys is written; a token no sequence owns, or one at a negative position (Nq_s > len_s), is all -inf.  q8, w' and the summation
+ * order are fa2_mla_indexer_logits_fp8's: the rows of sequence s equal that call on the sequence (B = 1, Nq = Nq_s) bit for bit.  Dead rows, dead
+ * scales and dead pages are never addressed, nor the block-table entries of pages beyond the largest position a workgroup serves.  The host reads no
+ * device value and takes no maximum length: the call can be captured.
+ * Checked in fa2_mla_indexer_logits_fp8's order, the new arguments after the existing ones inside each class: null pointers (.., cu_seqlens_q); sizes
+ * (B < 1, total_q < 0, ..); head dims; alignment (.., cu_seqlens_q 4 bytes); q_dtype; FA2_ERR_GRID (more than 65535 x 128 tokens).  total_q == 0 passes
+ * every check and launches nothing.
+ * Kernel (FA2_KERNEL_HIP_MLA_INDEXER_PREFILL, csrc/fa2_mla_indexer_prefill_fp8.hip.h): a grid of (ceil(capacity_keys / 1024), ceil(total_q / 128))
+ * workgroups of eight waves; a wave holds 128 keys as MFMA B operands while the tokens stream past through a double-buffered, XOR-swizzled LDS image.
+ * fa2_topk_indices_varlen: fa2_topk_indices with the packed row geometry: row t of logits total_q x capacity (row stride) and indices total_q x topk
+ * (row stride), pos as above; a row no sequence owns, or one at a negative position, is all -1.  The rows [cu[s], cu[s + 1]) are sequence s's lists.
+ * Checked in fa2_topk_indices' order: null pointers (.., cu_seqlens_q); sizes (B < 1, total_q < 0, ..); alignment; FA2_ERR_GRID (total_q above
+ * 2^31 - 1: unreachable through an int).  total_q == 0 launches nothing. */
+enum { FA2_KERNEL_HIP_MLA_INDEXER_PREFILL = 14 };     /* (an enumerator, like FA2_KERNEL_HIP_WINDOW) */
+int fa2_mla_indexer_logits_varlen_fp8(int q_dtype, const void* q_idx, const void* k_codes, const float* k_scales, const float* weights, float* logits,
+                                      const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                                      int B, int H_idx, int64_t total_q, int D_idx, int capacity, int page_size, int num_pages,
+                                      const int64_t q_strides[2], const int64_t code_strides[2], const int64_t scale_strides[2],
+                                      int64_t w_stride, int64_t logits_stride, int64_t block_table_stride, void* hip_stream);
+int fa2_topk_indices_varlen(const float* logits, int* indices, const int* cu_seqlens_q, const int* cache_seqlens, int B, int64_t total_q, int capacity,
+                            int topk, int64_t logits_stride, int64_t indices_stride, void* hip_stream);
+
 /* ---- ... on an e4m3 latent cache (the FP8 KV cache of DeepSeek-V3.2 servers: FlashMLA's, vLLM's fp8_ds_mla), dense and sparse.  One row per token,
  * 656 bytes instead of 1 152:
  *   bytes   0 .. 511   OCP e4m3 codes of latent columns 0 .. 511 (the part that is also the value)

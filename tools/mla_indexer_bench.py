@@ -1,7 +1,7 @@
 """The lightning indexer of sparse MLA decode: mla_indexer_topk against what a user of flash_attention_decode_mla(indices=) wrote before it existed, same
 box, interleaved rounds, median of per-round event times with the spread of the rounds beside it (tools/mla_sparse_bench.py's method).
 
-    python tools/mla_indexer_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX] [--fp8]
+    python tools/mla_indexer_bench.py [--rounds R] [--iters I] [--out FILE] [--only LABEL-PREFIX] [--fp8 | --prefill]
 
 Routes
     indexer       mla_indexer_topk(q_idx, k_idx_cache, weights, lens, topk=2048): two launches
@@ -25,7 +25,7 @@ import torch  # noqa: E402
 from benchlib import graphed, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
 from rocwmma_fattn.FlashAttn import (kvcache_append_mla_index, mla_index_cache_from_fp8, mla_index_cache_to_fp8, mla_indexer_logits,  # noqa: E402
-                                     mla_indexer_topk, topk_indices)
+                                     mla_indexer_logits_varlen, mla_indexer_q_to_fp8, mla_indexer_topk, mla_indexer_topk_varlen, topk_indices)
 
 H, D, TOPK, BF16 = 64, 128, 2048, torch.bfloat16
 ROWS = [("%d_b%d_%dk%s" % (n, B, keys // 1024, "_pg64" if paged else ""), B, keys, paged)
@@ -138,6 +138,68 @@ def row8(out, label, B, keys, paged, rounds, iters):
     sys.stdout.flush()
 
 
+# --prefill (section 36): (label, token counts per sequence, keys per sequence).  The packed operators against what a caller does without them: one
+# uniform call with Nq = the chunk where the batch is uniform, the host loop over sequences where it is ragged.
+PREFILL = [("1_b1_2048_8k", (2048,), 8192), ("2_b1_2048_32k", (2048,), 32768), ("3_b1_2048_64k", (2048,), 65536), ("4_b4_512_32k", (512,) * 4, 32768),
+           ("5_ragged_24x1_4x384_32k", (1,) * 24 + (384,) * 4, 32768)]
+CLOCK_GHZ, MFMA_CYCLES, HBM_TBS = 2.4, 32, 8.0      # the floors' assumptions: peak clock, 8 passes of 4 cycles per 16x16x128 FP8 MFMA, peak HBM rate
+
+
+def row_prefill(out, label, counts, keys, rounds, iters):
+    dev, B, total = torch.device("cuda", 0), len(counts), sum(counts)
+    uniform = len(set(counts)) == 1
+    q = torch.randn((total, H, D), device=dev, dtype=BF16)
+    w = torch.randn((total, H), device=dev) * H ** -0.5
+    q8, w8 = (t[0] for t in mla_indexer_q_to_fp8(q[None], w[None]))
+    rows = mla_index_cache_to_fp8(torch.randn((B, keys, D), device=dev, dtype=BF16))
+    lens = torch.full((B,), keys, dtype=torch.int32, device=dev)
+    cu_host = [0]
+    for c in counts:
+        cu_host.append(cu_host[-1] + c)
+    cu = torch.tensor(cu_host, dtype=torch.int32, device=dev)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def parent(qq, ww, f):
+        if uniform:
+            return [f(qq.view(B, counts[0], H, D), rows, ww.view(B, counts[0], H), lens)]
+        return [f(qq[a:b][None], rows[s:s + 1], ww[a:b][None], lens[s:s + 1]) for s, (a, b) in enumerate(zip(cu_host, cu_host[1:]))]
+
+    fns = {}
+    for n, (qq, ww) in (("bf16 q", (q, w)), ("e4m3 q", (q8, w8))):
+        fns[n + " logits packed"] = lambda qq=qq, ww=ww: mla_indexer_logits_varlen(qq, rows, ww, cu, lens)
+        fns[n + " logits parent"] = lambda qq=qq, ww=ww: parent(qq, ww, mla_indexer_logits)
+        fns[n + " step packed"] = lambda qq=qq, ww=ww: mla_indexer_topk_varlen(qq, rows, ww, cu, lens, topk=TOPK)
+        fns[n + " step parent"] = lambda qq=qq, ww=ww: parent(qq, ww, lambda *a: mla_indexer_topk(*a, topk=TOPK))
+    with torch.no_grad():
+        for n in ("bf16 q", "e4m3 q"):
+            a, b = fns[n + " logits packed"](), torch.cat([t.flatten(0, 1) for t in fns[n + " logits parent"]()])
+            c, d = fns[n + " step packed"](), torch.cat([t.flatten(0, 1) for t in fns[n + " step parent"]()])
+            if not torch.equal(a.view(torch.int32), b.view(torch.int32)) or not torch.equal(c, d):
+                raise SystemExit("mla_indexer_bench: %s: %s: the packed call disagrees with the parent's calls" % (label, n))
+        t = interleaved(fns, rounds, iters)
+    # the causal triangle: token i of a chunk of c sees keys - c + i + 1 keys; an MFMA serves 16 heads x 16 keys
+    mfmas = sum(sum(-(-(keys - c + i + 1) // 16) for i in range(c)) for c in counts) * (H // 16)
+    f_mfma, f_write = mfmas * MFMA_CYCLES / (cus * 4) / (CLOCK_GHZ * 1e3), total * keys * 4 / (HBM_TBS * 1e6)      # us
+    lines = ["%-24s B%d, %d packed tokens, %d keys per sequence, H_idx %d topk %d, e4m3 rows; packed == parent bit for bit" % (label, B, total, keys, H, TOPK),
+             "    floors for the logits: MFMA issue %.1f us (%d MFMAs, %d cycles each, %d SIMDs, %.1f GHz), output write %.1f us (%d MB at %.0f TB/s)"
+             % (f_mfma, mfmas, MFMA_CYCLES, cus * 4, CLOCK_GHZ, f_write, total * keys * 4 >> 20, HBM_TBS)]
+    for n, (med, lo, hi) in t.items():
+        rel = ""
+        if n.endswith("packed"):
+            base = t[n[:-6] + "parent"]
+            real = abs(med - base[0]) > (hi - lo) + (base[2] - base[1])
+            rel = "  %.2fx the parent's time (%s the sum of the spreads)" % (med / base[0], "beyond" if real else "WITHIN")
+            if "logits" in n:
+                rel += "; %.2f of the MFMA floor's rate, %.2f of the write floor's" % (f_mfma / (med * 1e3), f_write / (med * 1e3))
+        lines.append("    %-22s %10.1f us  (rounds %.1f .. %.1f, spread %.1f %%)%s" % (n, med * 1e3, lo * 1e3, hi * 1e3, 100.0 * (hi - lo) / med, rel))
+    for line in lines:
+        print(line)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+    sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -145,6 +207,7 @@ def main():
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--only", default="", help="rows whose label starts with this")
     ap.add_argument("--fp8", action="store_true", help="the e4m3 index-key cache rows (section 35) instead of the 16-bit ones")
+    ap.add_argument("--prefill", action="store_true", help="the packed (prefill) indexer against the parent's calls (section 36)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mla_indexer_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
@@ -154,9 +217,9 @@ def main():
     print(head)
     if out:
         out.write(head + "\n")
-    for r in ROWS:
+    for r in PREFILL if a.prefill else ROWS:
         if r[0].startswith(a.only):
-            (row8 if a.fp8 else row)(out, *r, a.rounds, a.iters)
+            (row_prefill if a.prefill else row8 if a.fp8 else row)(out, *r, a.rounds, a.iters)
 
 
 if __name__ == "__main__":
