@@ -90,6 +90,12 @@ UNITS = [
     ("decode_mla_fp8_hip_bf16", "decode_mla_fp8_hip.cpp", ["-DFA2_TU_BF16=1"] + NO_PACKED_F32),
     ("decode_mla_sparse_fp8_hip_f16", "decode_mla_sparse_fp8_hip.cpp", ["-DFA2_TU_BF16=0"] + NO_PACKED_F32),
     ("decode_mla_sparse_fp8_hip_bf16", "decode_mla_sparse_fp8_hip.cpp", ["-DFA2_TU_BF16=1"] + NO_PACKED_F32),
+    # ... and the sparse form for packed tokens (the prefill step): one kernel per format on a one-dimensional grid; the decode units' flags, so that the
+    # per-tile arithmetic is the same instructions
+    ("prefill_mla_sparse_hip_f16", "prefill_mla_sparse_hip.cpp", ["-DFA2_TU_BF16=0"] + NO_PACKED_F32),
+    ("prefill_mla_sparse_hip_bf16", "prefill_mla_sparse_hip.cpp", ["-DFA2_TU_BF16=1"] + NO_PACKED_F32),
+    ("prefill_mla_sparse_fp8_hip_f16", "prefill_mla_sparse_fp8_hip.cpp", ["-DFA2_TU_BF16=0"] + NO_PACKED_F32),
+    ("prefill_mla_sparse_fp8_hip_bf16", "prefill_mla_sparse_fp8_hip.cpp", ["-DFA2_TU_BF16=1"] + NO_PACKED_F32),
     # the lightning indexer that names the sparse form's lists: the MFMA logits over an index-key cache (an f32 ReLU / weight / head-sum epilogue: no
     # packed f32), and the dtype-free radix select behind it
     ("mla_indexer_hip_f16", "mla_indexer_hip.cpp", ["-DFA2_TU_BF16=0"] + NO_PACKED_F32),
@@ -125,7 +131,7 @@ FRONTEND_SRC = "frontend.cpp"                      # optional compiled front end
 FRONTEND_PATH = os.path.join(PKG_DIR, "rocwmma_fattn", "_fa2_frontend.so")
 GENERATORS = [os.path.join("gen", "fwd_d128_gen.py"), os.path.join("gen", "fwd_m16_gen.py"), os.path.join("gen", "fwd_m16_d256_gen.py"), os.path.join("gen", "bwd_d128_gen.py"),
               os.path.join("gen", "bwd_dq_m16_gen.py"), os.path.join("gen", "bwd_dkv_m16_gen.py")]
-HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_decode_mla_sweep.h", "fa2_decode_mla_sparse.hip.h", "fa2_decode_mla_sparse_sweep.h", "fa2_mla_indexer.hip.h", "fa2_topk_select.hip.h", "fa2_mla_indexer_fp8.hip.h", "fa2_mla_indexer_prefill_fp8.hip.h", "fa2_kvappend_mla_index_fp8.hip.h", "fa2_kvappend.hip.h", "fa2_kvappend_mla.hip.h", "fa2_kvappend_mla_fp8.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
+HEADERS = ["fa2_launch.h", "fa2_pass_launch.h", "fa2_family_unit.h", "fa2_window.h", "fa2_dropout.h", "fa2_scoremod.h", "fa2_decode.hip.h", "fa2_decode_mla.hip.h", "fa2_decode_mla_sweep.h", "fa2_decode_mla_sparse.hip.h", "fa2_decode_mla_sparse_sweep.h", "fa2_prefill_mla_sparse.hip.h", "fa2_prefill_mla_sparse_sweep.h", "fa2_mla_indexer.hip.h", "fa2_topk_select.hip.h", "fa2_mla_indexer_fp8.hip.h", "fa2_mla_indexer_prefill_fp8.hip.h", "fa2_kvappend_mla_index_fp8.hip.h", "fa2_kvappend.hip.h", "fa2_kvappend_mla.hip.h", "fa2_kvappend_mla_fp8.hip.h", "fa2_rotary.h", "fa2_prefill.h", "fa2_fwd_kernel.hip.h", "fa2_fwd_short.hip.h", "fa2_fwd_d128.hip.h", "fa2_fwd_d256.hip.h", "fa2_bwd_kernel.hip.h", "fa2_bwd_short.hip.h", "fa2_bwd_d128.hip.h",
            os.path.join(INCLUDE, "fa2_gfx950.h"), os.path.join("gen", "isa.py"), os.path.join("gen", "sched.py"), os.path.join("gen", "gen_driver.py")] + GENERATORS
 
 HIPCC_FLAGS = [

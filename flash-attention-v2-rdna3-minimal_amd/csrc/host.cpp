@@ -20,6 +20,7 @@
 #include "fa2_dropout.h"
 #include "fa2_decode_mla.hip.h"      // the latent-cache decode: its constants, the arithmetic the plan shares with the kernel, its launcher
 #include "fa2_decode_mla_sparse.hip.h"      // ... and its sparse (top-k indexed) form
+#include "fa2_prefill_mla_sparse.hip.h"     // ... and that form for packed tokens
 #include "fa2_mla_indexer.hip.h"     // ... the indexer that names the sparse form's lists: the logits kernel's parameter block and launcher
 #include "fa2_topk_select.hip.h"     // ... and the selection behind it
 #include "fa2_kvappend_mla.hip.h"    // ... and its append: the parameter block, the unit -> chunks map, its launcher
@@ -2002,6 +2003,61 @@ int fa2_decode_mla_sparse_entry(int entry, int64_t len, int Nq, int i, int capac
     const fa2::MlaSparseEntry e = fa2::mla_sparse_entry(entry, (int64_t)fa2::decode_clamp_len(len, cap) - Nq + i, fa2::mla_page_keys(page_size, cap));
     *valid = e.valid; *page_slot = e.slot; *row_in_page = e.row;
     return FA2_OK;
+}
+
+// ---- ... for PACKED query tokens (the prefill step): csrc/fa2_prefill_mla_sparse.hip.h has the kernel.  One body for both cache
+// formats; the checks run in decode_mla_run's order, the new arguments after the existing ones inside each class.
+static int prefill_mla_sparse_run(int format, int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* indices, const int* cu_seqlens_q,
+                                  const int* cache_seqlens, const int* block_table, int B, int H, int64_t total_q, int D, int Dv, int topk, int capacity,
+                                  int page_size, int num_pages, const int64_t* qs, const int64_t* ks, const int64_t* os, int64_t lse_stride,
+                                  int64_t indices_stride, int64_t block_table_stride, float scale, void* hip_stream) {
+    CacheDesc c;
+    c.k = kv_cache; c.v = kv_cache; c.block_table = block_table; c.capacity = capacity; c.page_size = page_size; c.num_pages = num_pages;
+    c.ks = ks; c.vs = ks; c.bts = block_table_stride; c.format = format;
+    if (any_null({q, o, lse, cache_seqlens, qs, os}) || cache_null(c) || any_null({indices, cu_seqlens_q})) return FA2_ERR_NULL_POINTER;
+    if (B < 1 || H < 1 || D < 1 || Dv < 1 || H > fa2::kMlaMaxHeads || !cache_paging_ok(c) || total_q < 0) return FA2_ERR_BAD_SHAPE;
+    if (topk < 1 || topk > 0x7fffffff - 64) return FA2_ERR_BAD_SHAPE;
+    if (D != fa2::kMlaD || Dv != fa2::kMlaDv) return FA2_ERR_HEAD_DIM;
+    if (!cache_extent_ok(c) || lse_stride < 0 || indices_stride < 0) return FA2_ERR_BAD_SHAPE;
+    if (c.fp8() && !fa2::mla_fp8_row_stride_ok(ks[2])) return FA2_ERR_BAD_SHAPE;
+    const auto rows_ok = [](const int64_t* st) { return st[0] >= 0 && st[1] >= 0 && ((st[0] | st[1]) & 7) == 0; };
+    if (!all_aligned16({q, o}) || !cache_aligned(c) ||
+        ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(cache_seqlens) | reinterpret_cast<uintptr_t>(indices) |
+          reinterpret_cast<uintptr_t>(cu_seqlens_q)) & 3u) || !rows_ok(qs) || !rows_ok(os))
+        return FA2_ERR_ALIGNMENT;
+    if (dtype != FA2_DTYPE_F16 && dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
+    if (!std::isfinite(scale)) return FA2_ERR_SCALE;
+    const int64_t items = total_q * fa2::mla_sparse_head_blocks(H);
+    if (total_q > 0x7fffffffLL || items > 0x7fffffffLL) return FA2_ERR_GRID;          // a one-dimensional grid
+    if (total_q == 0) return FA2_OK;                                                 // an empty token buffer: nothing to launch
+    fa2::PrefillMlaSparseParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = q; p.k = kv_cache; p.o = o; p.lse = lse; p.idx = indices; p.cu = cu_seqlens_q; p.lens = cache_seqlens; p.bt = page_size > 0 ? block_table : nullptr;
+    p.B = B; p.H = H; p.topk = topk; p.page_size = page_size; p.num_pages = num_pages; p.capacity_keys = c.capacity_keys();
+    for (int i = 0; i < 2; ++i) { p.qs[i] = qs[i]; p.os[i] = os[i]; }
+    for (int i = 0; i < 3; ++i) p.ks[i] = ks[i];
+    p.ls = lse_stride; p.is = indices_stride; p.bts = block_table_stride;
+    p.c = scale * 1.4426950408889634f;
+    if (c.fp8()) return fa2::launch_prefill_mla_sparse_fp8(dtype == FA2_DTYPE_BF16, p, (uint32_t)items, (hipStream_t)hip_stream);
+    return fa2::launch_prefill_mla_sparse(dtype == FA2_DTYPE_BF16, p, (uint32_t)items, (hipStream_t)hip_stream);
+}
+
+int fa2_fwd_prefill_mla_sparse(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* indices, const int* cu_seqlens_q,
+                               const int* cache_seqlens, const int* block_table, int B, int H, int64_t total_q, int D, int Dv, int topk, int capacity,
+                               int page_size, int num_pages, const int64_t q_strides[2], const int64_t kv_strides[3], const int64_t o_strides[2],
+                               int64_t lse_stride, int64_t indices_stride, int64_t block_table_stride, float scale, void* hip_stream) {
+    return prefill_mla_sparse_run(FA2_CACHE_16BIT, dtype, q, kv_cache, o, lse, indices, cu_seqlens_q, cache_seqlens, block_table, B, H, total_q, D, Dv, topk,
+                                  capacity, page_size, num_pages, q_strides, kv_strides, o_strides, lse_stride, indices_stride, block_table_stride, scale,
+                                  hip_stream);
+}
+
+int fa2_fwd_prefill_mla_sparse_fp8(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* indices, const int* cu_seqlens_q,
+                                   const int* cache_seqlens, const int* block_table, int B, int H, int64_t total_q, int D, int Dv, int topk, int capacity,
+                                   int page_size, int num_pages, const int64_t q_strides[2], const int64_t kv_strides[3], const int64_t o_strides[2],
+                                   int64_t lse_stride, int64_t indices_stride, int64_t block_table_stride, float scale, void* hip_stream) {
+    return prefill_mla_sparse_run(FA2_CACHE_E4M3, dtype, q, kv_cache, o, lse, indices, cu_seqlens_q, cache_seqlens, block_table, B, H, total_q, D, Dv, topk,
+                                  capacity, page_size, num_pages, q_strides, kv_strides, o_strides, lse_stride, indices_stride, block_table_stride, scale,
+                                  hip_stream);
 }
 
 // ---- the lightning indexer of sparse MLA decode: the logits over an index-key cache (csrc/fa2_mla_indexer.hip.h), then the

@@ -28,7 +28,7 @@ from . import _fa2_lib
 __all__ = ["FlashAttentionFunction", "flash_attn_wmma", "flash_attention", "flash_attention_varlen", "merge_attention", "flash_attention_prefill", "flash_attention_prefill_fp8",
            "kvcache_append_varlen", "flash_attention_decode_mla", "kvcache_append_mla", "kvcache_append_mla_varlen", "mla_cache_to_fp8",
            "mla_cache_from_fp8", "mla_indexer_logits", "topk_indices", "mla_indexer_topk", "mla_indexer_q_to_fp8", "mla_index_cache_to_fp8",
-           "mla_index_cache_from_fp8", "kvcache_append_mla_index", "mla_indexer_logits_varlen", "topk_indices_varlen", "mla_indexer_topk_varlen"]
+           "mla_index_cache_from_fp8", "kvcache_append_mla_index", "mla_indexer_logits_varlen", "topk_indices_varlen", "mla_indexer_topk_varlen", "flash_attention_prefill_mla"]
 
 
 class _FlashAttnWmma:
@@ -1681,6 +1681,18 @@ def mla_cache_from_fp8(cache, dtype):
     return out
 
 
+def _mla_cache_is_fp8(who, kv_cache):
+    """The format checks of a latent cache an attention call reads -> True for rows of 656 bytes (uint8 / float8_e4m3fn), False for a 16-bit cache"""
+    if kv_cache.dtype in _FP8_OTHERS:
+        raise ValueError("fa2: %s takes an FP8 latent cache as torch.uint8 or torch.float8_e4m3fn rows of %d bytes (OCP e4m3 codes): e5m2 and the fnuz "
+                         "formats are not served, got %s" % (who, _MLA_FP8_ROW, kv_cache.dtype))
+    fp8 = kv_cache.dtype == torch.uint8 or (_FP8_CACHE is not None and kv_cache.dtype == _FP8_CACHE)
+    if fp8 and kv_cache.shape[-1] != _MLA_FP8_ROW:
+        raise ValueError("fa2: %s takes a uint8 / float8_e4m3fn latent cache as rows of %d bytes (512 e4m3 codes, four float32 scales, 64 rotary columns "
+                         "in q's dtype), got kv_cache %s" % (who, _MLA_FP8_ROW, tuple(kv_cache.shape)))
+    return fp8
+
+
 def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, head_dim_v=512, scale=None, return_lse=False, num_splits=0, kv_c=None, k_pe=None,
                                rotary_cos=None, rotary_sin=None, rotary_interleaved=True, indices=None):
     """Decode attention on a multi-head-latent (MLA) KV cache — the decode step of DeepSeek-V2 / V3 / R1 and Kimi K2 with the up-projections absorbed
@@ -1699,8 +1711,9 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
     scale: None = 576 ** -0.5 (FlashMLA's default).  DeepSeek callers pass their own: the softmax scale of the NON-absorbed head dim (192 ** -0.5, times
     the YaRN mscale factor where the model has one).
     head_dim_v must be 512 and q.shape[-1] 576; H is 1 .. 128 and Nq * H <= 512 (TP8's 16 heads up to all 128, with a few speculative tokens).
-    Anything else raises ValueError.  Returns o [B, Nq, H, 512]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention
-    composes with it).  num_splits: 0 = the library's plan, 1 .. 128 = that many parts per (sequence, block of 64 rows).  Inference only.
+    Anything else raises ValueError — this is the call for decode-only batches; a packed step with prefill chunks is flash_attention_prefill_mla, which
+    has no row limit.  Returns o [B, Nq, H, 512]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention composes with it).
+    num_splits: 0 = the library's plan, 1 .. 128 = that many parts per (sequence, block of 64 rows).  Inference only.
     kv_c [B, Nq, 512] and k_pe [B, Nq, 64] (both or neither): the query rows' own new tokens, appended first by kvcache_append_mla's rules —
     cache_seqlens counts them already — with rotary_cos / rotary_sin [seqlen_ro, 32] rotating k_pe and the trailing 64 columns of q by each row's
     position; the attention then reads the rotated q.  Every check of both halves runs before the first launch, so a call that is refused leaves the
@@ -1729,13 +1742,7 @@ def flash_attention_decode_mla(q, kv_cache, cache_seqlens, block_table=None, hea
                          "cache has a head axis of size 1" % who)
     if torch.is_grad_enabled() and (q.requires_grad or kv_cache.requires_grad):
         raise ValueError("fa2: %s is inference only (an input requires grad)" % who)
-    if kv_cache.dtype in _FP8_OTHERS:
-        raise ValueError("fa2: %s takes an FP8 latent cache as torch.uint8 or torch.float8_e4m3fn rows of %d bytes (OCP e4m3 codes): e5m2 and the fnuz "
-                         "formats are not served, got %s" % (who, _MLA_FP8_ROW, kv_cache.dtype))
-    fp8 = kv_cache.dtype == torch.uint8 or (_FP8_CACHE is not None and kv_cache.dtype == _FP8_CACHE)
-    if fp8 and kv_cache.shape[-1] != _MLA_FP8_ROW:
-        raise ValueError("fa2: %s takes a uint8 / float8_e4m3fn latent cache as rows of %d bytes (512 e4m3 codes, four float32 scales, 64 rotary columns "
-                         "in q's dtype), got kv_cache %s" % (who, _MLA_FP8_ROW, tuple(kv_cache.shape)))
+    fp8 = _mla_cache_is_fp8(who, kv_cache)
     if isinstance(head_dim_v, bool) or head_dim_v != _MLA_DV or q.shape[3] != _MLA_D or (not fp8 and kv_cache.shape[-1] != _MLA_D):
         raise ValueError("fa2: %s serves latent rows of %d columns whose first %d are the value (head_dim_v), got q %s kv_cache %s head_dim_v=%r"
                          % (who, _MLA_D, _MLA_DV, tuple(q.shape), tuple(kv_cache.shape), head_dim_v))
@@ -2222,7 +2229,8 @@ def topk_indices_varlen(logits, cu_seqlens_q, cache_seqlens, topk):
     """topk_indices for packed rows: logits float32 [total_q, capacity], cu_seqlens_q int32 [B + 1], cache_seqlens int32 [B] -> int32 [total_q, topk].
     Row t of sequence s selects over [0, pos], pos = len_s - Nq_s + (t - cu[s]), by topk_indices' rules (ascending positions, ties to the lowest
     positions, NaN as -inf, pos + 1 <= topk reads no logit); a row nobody owns, or one at a negative position, is all -1.  The rows [cu[s], cu[s + 1])
-    viewed as [1, Nq_s, topk] are the indices flash_attention_decode_mla(..., indices=) takes for sequence s.  C-ABI fa2_topk_indices_varlen."""
+    viewed as [1, Nq_s, topk] are the indices flash_attention_decode_mla(..., indices=) takes for sequence s; the whole tensor is what
+    flash_attention_prefill_mla takes.  C-ABI fa2_topk_indices_varlen."""
     return _topk_launch_varlen(_topk_prepare_varlen("topk_indices_varlen", logits, cu_seqlens_q, cache_seqlens, topk), cu_seqlens_q, cache_seqlens, topk)
 
 
@@ -2235,6 +2243,66 @@ def mla_indexer_topk_varlen(q_idx, k_idx_cache, weights, cu_seqlens_q, cache_seq
     logits = _indexer_logits_launch_varlen(*args[:3], cu_seqlens_q, cache_seqlens, block_table, *args[3:])
     idx = _topk_launch_varlen(logits, cu_seqlens_q, cache_seqlens, topk)
     return (idx, logits) if return_logits else idx
+
+
+def flash_attention_prefill_mla(q, kv_cache, cu_seqlens_q, cache_seqlens, indices, block_table=None, head_dim_v=512, scale=None, return_lse=False):
+    """Sparse (top-k indexed) attention for PACKED query tokens on a latent (MLA) KV cache: the prefill step of DeepSeek-V3.2, and the consumer of
+    mla_indexer_topk_varlen's lists — one call for a continuous-batching step that mixes decode rows and prefill chunks of any length.
+    q [total_q, H, 576] fp16 / bf16, H in 1 .. 128: the absorbed queries (flash_attention_decode_mla's columns), copied only if the kernel cannot address
+    them.  cu_seqlens_q int32 [B + 1] on the device: sequence s owns the rows [cu[s], cu[s + 1]) — Nq_s may be 0 and rows beyond cu[B] belong to nobody.
+    kv_cache: every latent layout flash_attention_decode_mla takes — 16-bit rows of 576 columns, or uint8 / float8_e4m3fn rows of 656 bytes; 3-D or
+    with a head axis of 1; contiguous [B, Nmax, ..] or paged [num_pages, page_size, ..] under block_table int32 [B, max_pages] — never copied.
+    cache_seqlens int32 [B] counts each sequence's valid keys INCLUDING its new tokens.  indices int32 [total_q, topk] with stride(1) == 1: entry j of
+    row t of sequence s is a LOGICAL key position of s, resolved through block_table in-kernel; it counts iff 0 <= j <= len_s - Nq_s + (t - cu[s]), and
+    a position named twice counts twice.  Every other entry (-1 padding included) contributes nothing and is never addressed; cache rows no valid
+    entry names are never read.  Returns o [total_q, H, 512]; with return_lse=True also lse f32 [H, total_q] in natural-log units
+    (flash_attention_prefill's layout).  A row nobody owns, one at a negative position or one without a valid entry is zeros (lse -inf); every element
+    is written.  scale: None = 576 ** -0.5.  The rows of sequence s equal flash_attention_decode_mla(q_s, ..., indices=idx_s, num_splits=1) bit for
+    bit wherever that call is allowed, and an e4m3 cache gives the 16-bit call's result on mla_cache_from_fp8(kv_cache, q.dtype) bit for bit.
+    The host reads no device tensor and takes no maximum length: the call can be captured in a graph and replayed as cu_seqlens_q, the lengths, the
+    lists and the block table change in place.  Inference only.  A step is kvcache_append_mla_varlen, then mla_indexer_topk_varlen, then this call,
+    on one stream; flash_attention_decode_mla stays the call for decode-only batches (it splits the list over idle CUs).
+    C-ABI fa2_fwd_prefill_mla_sparse, fa2_fwd_prefill_mla_sparse_fp8."""
+    who = "flash_attention_prefill_mla"
+    if not all(torch.is_tensor(t) for t in (q, kv_cache, cache_seqlens)) or q.dim() != 3 or kv_cache.dim() not in (3, 4) or \
+            (kv_cache.dim() == 4 and kv_cache.shape[2] != 1):
+        raise ValueError("fa2: %s takes packed q [total_q, H, 576] and a latent kv_cache [B, Nmax, 576] ([num_pages, page_size, 576] with a block_table); a "
+                         "4-D cache has a head axis of size 1" % who)
+    _no_grad_inputs(who, q, kv_cache)
+    fp8 = _mla_cache_is_fp8(who, kv_cache)
+    if isinstance(head_dim_v, bool) or head_dim_v != _MLA_DV or q.shape[2] != _MLA_D or (not fp8 and kv_cache.shape[-1] != _MLA_D):
+        raise ValueError("fa2: %s serves latent rows of %d columns whose first %d are the value (head_dim_v), got q %s kv_cache %s head_dim_v=%r"
+                         % (who, _MLA_D, _MLA_DV, tuple(q.shape), tuple(kv_cache.shape), head_dim_v))
+    if q.dtype not in (torch.float16, torch.bfloat16) or (not fp8 and kv_cache.dtype != q.dtype):
+        raise ValueError("fa2: %s takes fp16 or bf16 q and kv_cache of one dtype (or rows of %d bytes), got %s %s" % (who, _MLA_FP8_ROW, q.dtype, kv_cache.dtype))
+    total, H, _ = q.shape
+    if not 1 <= H <= _MLA_MAX_HEADS:
+        raise ValueError("fa2: %s serves 1 .. %d heads, got q %s" % (who, _MLA_MAX_HEADS, tuple(q.shape)))
+    if not torch.is_tensor(indices) or indices.dtype != torch.int32 or indices.dim() != 2 or indices.shape[0] != total or \
+            not 1 <= indices.shape[1] <= _TOPK_MAX or indices.stride(1) != 1 or indices.stride(0) < 0 or indices.device != q.device:
+        raise ValueError("fa2: %s takes indices as an int32 tensor [total_q, topk] = [%d, >= 1] on q's device whose last dim is contiguous, got %s"
+                         % (who, total, "%s %s strides %s on %s" % (indices.dtype, tuple(indices.shape), indices.stride(), indices.device)
+                            if torch.is_tensor(indices) else repr(indices)))
+    B = _check_cu("cu_seqlens_q", cu_seqlens_q)
+    _check_lens(who, cache_seqlens, B, q.device)
+    kv4 = _mla_kv4(kv_cache.view(torch.uint8) if fp8 else kv_cache)
+    cache = _cache_desc(fp8, q, B, kv4, kv4, cache_seqlens, block_table, None, None, aux=(cu_seqlens_q,))
+    ok = q.stride(2) == 1 and not ((q.stride(0) | q.stride(1)) & 7) and q.stride(0) >= 0 and q.stride(1) >= 0 and not (q.data_ptr() & 15)
+    q = q if ok else q.contiguous()
+    if scale is None:
+        scale = _MLA_D ** -0.5
+    o = torch.empty((total, H, _MLA_DV), dtype=q.dtype, device=q.device)
+    lse = torch.empty((H, total), dtype=torch.float32, device=q.device)
+    if total:
+        lib = _fa2_lib.load()
+        dev = _device_index(q)
+        with torch.cuda.device(dev):
+            rc = (lib.fa2_fwd_prefill_mla_sparse_fp8 if fp8 else lib.fa2_fwd_prefill_mla_sparse)(
+                _dtype_code(q), q.data_ptr(), cache.ptrs[0], o.data_ptr(), lse.data_ptr(), indices.data_ptr(), cu_seqlens_q.data_ptr(), *cache.tables, B, H,
+                total, _MLA_D, _MLA_DV, indices.shape[1], *cache.sizes, _fa2_lib.strides2(q.stride(0), q.stride(1)), cache.strides[0],
+                _fa2_lib.strides2(o.stride(0), o.stride(1)), lse.stride(0), indices.stride(0), cache.bts, float(scale), _raw_stream(dev))
+        _fa2_lib.check(rc)
+    return (o, lse * _LN2) if return_lse else o
 
 
 def flash_attention_prefill(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table=None, max_seqlen_q=None, scale=None, window=None, softcap=0.0,

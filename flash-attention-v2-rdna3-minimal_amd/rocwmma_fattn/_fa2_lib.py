@@ -222,6 +222,12 @@ SYMBOLS = {
     "fa2_fwd_decode_mla_sparse_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +
                                       [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_int, _i64p]),
+    # ... and the sparse form for packed tokens, both cache formats: dtype, q kv_cache o lse indices cu_seqlens_q cache_seqlens block_table, B H total_q,
+    # D Dv topk capacity page_size num_pages, the q pair, the cache triple, the o pair, the lse / indices / block-table strides, scale, stream
+    "fa2_fwd_prefill_mla_sparse": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 8 + [ctypes.c_int] * 2 + [ctypes.c_int64] + [ctypes.c_int] * 6 +
+                                   [_i64p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_float, ctypes.c_void_p]),
+    "fa2_fwd_prefill_mla_sparse_fp8": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 8 + [ctypes.c_int] * 2 + [ctypes.c_int64] + [ctypes.c_int] * 6 +
+                                       [_i64p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_float, ctypes.c_void_p]),
     # KV-cache append: dtype cache_format, k_new v_new k_cache v_cache cache_seqlens block_table, B Hkv Nnew D capacity page_size num_pages, four stride
     # triples, the block-table row stride, q q_out H Nq and their stride triples, cos sin rotary_dtype rotary_dim seqlen_ro row-stride interleaved,
     # k_descale v_descale descale_strides, stream

@@ -988,6 +988,44 @@ int fa2_fwd_decode_mla_sparse_fp8(int dtype, const void* q, const void* kv_cache
                                   float scale, int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream,
                                   const int* indices, int topk, const int64_t indices_strides[2]);
 
+/* ---- ... sparse (top-k indexed) for PACKED query tokens: the prefill step of DeepSeek-V3.2 style models, and the call that
+ * consumes fa2_topk_indices_varlen's lists.  One token buffer for a continuous-batching step that mixes decode rows and prefill chunks:
+ *   q            : total_q x H x 576 (dtype), element strides q_strides {token, head}, multiples of 8, the last dim contiguous; H 1 .. 128
+ *   o            : total_q x H x 512 (dtype), element strides o_strides {token, head};  lse : H x total_q f32 (log2 units), head stride lse_stride
+ *   indices      : total_q x topk int32, row stride indices_stride, the last dim contiguous: LOGICAL key positions of the token's sequence
+ *   cu_seqlens_q : int32 [B + 1], device: sequence s owns the packed tokens [cu[s], cu[s + 1]) — fa2_kvappend_varlen_token's rule, zero-length sequences
+ *                  and total_q > cu[B] included
+ *   kv_cache, cache_seqlens, block_table, capacity, page_size, num_pages, kv_strides {batch | page, head, row}, block_table_stride : as in
+ *                  fa2_fwd_decode_mla (fa2_fwd_prefill_mla_sparse) or fa2_fwd_decode_mla_fp8 (.._fp8: e4m3 rows of 656 bytes, strides in bytes)
+ * For token t of sequence s, i = t - cu[s], Nq_s = cu[s + 1] - cu[s], pos = clamp(len_s, 0, capacity_keys) - Nq_s + i: entry e is VALID iff
+ * 0 <= indices[t, e] <= pos, and
+ *   o[t, h, :] = sum over the valid e of softmax_e(scale * q[t, h, :] . kv[s, j_e, :]) . kv[s, j_e, :512],   lse[h, t] = logsumexp over the valid e.
+ * A position named twice counts twice.  A token nobody owns, a token at a negative position and a list without a valid entry give zeros and
+ * lse = -inf; every element of o and lse is written.  No invalid entry becomes part of an address, and no cache row or block-table entry is addressed
+ * other than ones a valid entry of that token names; lengths and page ids are clamped as in fa2_fwd_decode_mla; addresses are formed in 64 bits.  The
+ * host reads no device value and takes no maximum length: the call can be captured.
+ * The summation order is fa2_fwd_decode_mla_sparse's under num_splits = 1: the rows of sequence s equal that call on the sequence (B = 1, Nq = Nq_s)
+ * bit for bit wherever it is allowed, and the e4m3 call equals the 16-bit call on the dequantised cache bit for bit.
+ * Checked in fa2_fwd_decode_mla_sparse's order, the new arguments after the existing ones inside each class: null pointers (.., indices,
+ * cu_seqlens_q); sizes (B, H < 1, H > 128, the paging rules, total_q < 0, topk < 1 or above 2^31 - 1 - 64: FA2_ERR_BAD_SHAPE); head dim; the strides'
+ * signs and num_pages (a negative lse or indices stride, an e4m3 row stride below 656 or no multiple of 16: FA2_ERR_BAD_SHAPE); alignment (q, o, the
+ * cache 16 bytes, strides multiples of 8 elements / 16 bytes; lse, cache_seqlens, block_table, indices, cu_seqlens_q 4 bytes); dtype; scale;
+ * FA2_ERR_GRID (total_q * ceil(H / 64) above 2^31 - 1).  total_q == 0 passes every check and launches nothing.
+ * Kernel (csrc/fa2_prefill_mla_sparse.hip.h; the call has no plan, so no kernel id): one workgroup of four waves per (token, block of up to 64 heads) on
+ * a one-dimensional grid; no list split, no workspace, no combine.  The owner of a token is found once per workgroup.  Every load of the gather is
+ * unconditional (a lane whose entry is invalid loads the row of the tile's first valid entry and zero-selects when it writes LDS), so the rows of
+ * tile t + 1 stay in flight across tile t's MFMAs. */
+int fa2_fwd_prefill_mla_sparse(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* indices,
+                               const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                               int B, int H, int64_t total_q, int D, int Dv, int topk, int capacity, int page_size, int num_pages,
+                               const int64_t q_strides[2], const int64_t kv_strides[3], const int64_t o_strides[2],
+                               int64_t lse_stride, int64_t indices_stride, int64_t block_table_stride, float scale, void* hip_stream);
+int fa2_fwd_prefill_mla_sparse_fp8(int dtype, const void* q, const void* kv_cache, void* o, float* lse, const int* indices,
+                                   const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                                   int B, int H, int64_t total_q, int D, int Dv, int topk, int capacity, int page_size, int num_pages,
+                                   const int64_t q_strides[2], const int64_t kv_strides[3], const int64_t o_strides[2],
+                                   int64_t lse_stride, int64_t indices_stride, int64_t block_table_stride, float scale, void* hip_stream);
+
 /* ---- KV-cache append: the write side of the decode calls.  One launch writes the K and V rows of Nnew new tokens per sequence into the cache at the
  * key position only the device knows, optionally rotates k (and q) by that position and optionally quantises to e4m3.
  * Layout (element strides {batch, head, row}, D contiguous)

@@ -15,7 +15,14 @@ uniformly and sorted, as an indexer's top-k is.
     sparse        (a) the 16-bit sparse call on the 16-bit cache of the same shape
     deq+sparse    (b) mla_cache_from_fp8 over the live rows, then the 16-bit sparse call: what a holder of an e4m3 cache ran before
     sparse_fp8    (c) the sparse call on the e4m3 cache itself (checked bit for bit against (b) first)
-and the floor B * topk * 656 bytes at 6.3 TB/s."""
+and the floor B * topk * 656 bytes at 6.3 TB/s.
+--packed: the packed (prefill) call, flash_attention_prefill_mla, at topk 2 048 over 32 K keys, H128 / H16, bf16 and e4m3 caches:
+    chunk         one sequence's chunk of 2 048 tokens;  ragged: 28 decode rows and 4 chunks of 505 tokens in one buffer of 2 048
+    per-token     32 sequences of one token each: the shape of section 31's B32 row, for the time per (token, head block)
+    packed        the one call;  host-loop: flash_attention_decode_mla(indices=, num_splits=0) per sequence in calls of Nq * H <= 512 rows, which
+                  is what a caller had before (checked bit for bit against packed under num_splits=1 first)
+A token's list is its sequence's 2 048 sorted random positions with the last min(i, 256) of them replaced by the newest positions below its own:
+neighbouring tokens share most of their rows, as an indexer's lists do."""
 import argparse
 import os
 import sys
@@ -27,7 +34,7 @@ import torch  # noqa: E402
 
 from benchlib import close, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
-from rocwmma_fattn.FlashAttn import flash_attention_decode_mla, mla_cache_from_fp8, mla_cache_to_fp8  # noqa: E402
+from rocwmma_fattn.FlashAttn import flash_attention_decode_mla, flash_attention_prefill_mla, mla_cache_from_fp8, mla_cache_to_fp8  # noqa: E402
 
 HBM_TBS = 6.3
 D, TOPK, BF16 = 576, 2048, torch.bfloat16
@@ -122,6 +129,61 @@ def row_fp8(out, label, B, H, keys, rounds, iters):
     sys.stdout.flush()
 
 
+PACKED = [("%s_h%d_%s" % (kind, H, "e4m3" if fp8 else "bf16"), kind, H, fp8) for kind in ("chunk", "ragged", "per-token") for H in (128, 16) for fp8 in (False, True)]
+
+
+def row_packed(out, label, kind, H, fp8, rounds, iters):
+    dev, keys = torch.device("cuda", 0), 32768
+    g = torch.Generator(device="cpu").manual_seed(1)
+    counts = {"chunk": [2048], "ragged": [1] * 28 + [505] * 4, "per-token": [1] * 32}[kind]
+    B, total = len(counts), sum(counts)
+    q = torch.randn((total, H, D), device=dev, dtype=BF16)
+    kv = torch.randn((B, keys, D), device=dev, dtype=BF16)
+    cache = mla_cache_to_fp8(kv) if fp8 else kv
+    lens = torch.full((B,), keys, dtype=torch.int32, device=dev)
+    cu_h = [sum(counts[:s]) for s in range(B + 1)]
+    cu = torch.tensor(cu_h, dtype=torch.int32, device=dev)
+    idx = torch.empty((total, TOPK), dtype=torch.int32)
+    for s, n in enumerate(counts):
+        base = torch.randperm(keys - n, generator=g)[:TOPK].sort().values
+        for i in range(n):
+            r, pos = min(i, 256), keys - n + i
+            idx[cu_h[s] + i] = torch.cat([base[:TOPK - r], torch.arange(pos - r + 1, pos + 1)])
+    idx = idx.to(dev)
+
+    def host_loop(num_splits=0):
+        outs = []
+        for s, n in enumerate(counts):
+            for a in range(0, n, 512 // H):
+                b = min(n, a + 512 // H)
+                outs.append(flash_attention_decode_mla(q[None, cu_h[s] + a:cu_h[s] + b], cache[s:s + 1], lens[s:s + 1] - (n - b), num_splits=num_splits,
+                                                       indices=idx[None, cu_h[s] + a:cu_h[s] + b])[0])
+        return torch.cat(outs)
+    fns = {"packed": lambda: flash_attention_prefill_mla(q, cache, cu, lens, idx), "host-loop": host_loop}
+    if kind == "per-token":                            # the decode call on the same 32 rows, under its own plan (it splits the list over idle CUs)
+        fns["decode-b32"] = lambda: flash_attention_decode_mla(q.view(B, 1, H, D), cache, lens, indices=idx.view(B, 1, TOPK))
+    with torch.no_grad():
+        assert torch.equal(fns["packed"]().view(torch.int16), host_loop(1).view(torch.int16)), label + ": packed against the host loop, bit for bit"
+        t = interleaved(fns, rounds, iters)
+    blocks = total * -(-H // 64)
+    lines = ["%-22s %d tokens in %d sequences, H%d, topk %d of %d keys, %s cache: %d (token, head block) items, %d calls in the host loop"
+             % (label, total, B, H, TOPK, keys, "e4m3" if fp8 else "bf16", blocks, sum(-(-n // (512 // H)) for n in counts))]
+    p_med, p_lo, p_hi = t["packed"]
+    for n, (med, lo, hi) in t.items():
+        rel = "  %.2f us per item" % (med * 1e3 / blocks)
+        if n != "packed":
+            rel += "  packed %.2fx %s (%s the sum of the spreads, %.1f us)" % (max(med / p_med, p_med / med), "faster" if p_med <= med else "SLOWER",
+                                                                            "beyond" if abs(med - p_med) > (hi - lo) + (p_hi - p_lo) else "WITHIN",
+                                                                            ((hi - lo) + (p_hi - p_lo)) * 1e3)
+        lines.append("    %-13s %10.1f us  (rounds %.1f .. %.1f, spread %.1f us)%s" % (n, med * 1e3, lo * 1e3, hi * 1e3, (hi - lo) * 1e3, rel))
+    for line in lines:
+        print(line)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+    sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -129,6 +191,7 @@ def main():
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--only", default="", help="rows whose label starts with this")
     ap.add_argument("--fp8", action="store_true", help="H128 / H16 at 4 K and 64 K keys on an e4m3 cache: 16-bit, dequantise-then-call and the e4m3 call")
+    ap.add_argument("--packed", action="store_true", help="flash_attention_prefill_mla against the host loop of sparse decode calls: chunk, ragged, per-token")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mla_sparse_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
@@ -138,7 +201,10 @@ def main():
     print(head)
     if out:
         out.write(head + "\n")
-    for r in ROWS:
+    for r in PACKED if a.packed else ():
+        if r[0].startswith(a.only):
+            row_packed(out, *r, a.rounds, a.iters)
+    for r in () if a.packed else ROWS:
         if a.fp8:
             if not r[4] and r[3] in (4096, 65536) and r[0].startswith(a.only):
                 row_fp8(out, *r[:4], a.rounds, a.iters)
