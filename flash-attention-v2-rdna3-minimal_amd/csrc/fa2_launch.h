@@ -282,6 +282,11 @@ FA2_LAUNCHER(launch_decode_combine, (int HD, const DecodeParams& p, hipStream_t 
 // ... and the BAND instantiations of both (fa2_fwd_decode_window: a sliding window, soft-capping, ALiBi slopes), in the same units
 FA2_LAUNCHER(launch_decode_band, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
 FA2_LAUNCHER(launch_decode_band_fp8, (int HD, const DecodeParams& p, int row_tiles, hipStream_t stream), (HD, p, row_tiles, stream))
+// ... at head dim 256 (decode_wide_hip.cpp; fa2_fwd_decode_wide): the kernel of csrc/fa2_decode_wide.hip.h with `row_tiles` (1 or 2) row tiles per workgroup
+// on a grid of (row blocks * p.nsplit, Hkv, B), plain or banded, over 16-bit or e4m3 caches, then the same combine kernel at 256 columns
+FA2_LAUNCHER(launch_decode_wide, (const DecodeParams& p, int row_tiles, bool band, hipStream_t stream), (p, row_tiles, band, stream))
+FA2_LAUNCHER(launch_decode_wide_fp8, (const DecodeParams& p, int row_tiles, bool band, hipStream_t stream), (p, row_tiles, band, stream))
+FA2_LAUNCHER(launch_decode_wide_combine, (const DecodeParams& p, hipStream_t stream), (p, stream))
 // KV-cache append (kvappend_hip.cpp; fa2_kvcache_append): the kernel of csrc/fa2_kvappend.hip.h into 16-bit caches, and (-DFA2_TU_FP8=1) into e4m3 caches
 FA2_LAUNCHER(launch_kvappend, (const KvAppendParams& p, hipStream_t stream), (p, stream))
 FA2_LAUNCHER(launch_kvappend_fp8, (const KvAppendParams& p, hipStream_t stream), (p, stream))

@@ -18,6 +18,7 @@
 // (reference: kernel_fp16.cu:854-863).
 #include "fa2_launch.h"
 #include "fa2_dropout.h"
+#include "fa2_decode_wide.hip.h"     // decode at head dim 256: the rows a workgroup serves (the plan shares them with the launcher)
 #include "fa2_decode_mla.hip.h"      // the latent-cache decode: its constants, the arithmetic the plan shares with the kernel, its launcher
 #include "fa2_decode_mla_sparse.hip.h"      // ... and its sparse (top-k indexed) form
 #include "fa2_prefill_mla_sparse.hip.h"     // ... and that form for packed tokens
@@ -1569,8 +1570,9 @@ static bool cache_aligned(const CacheDesc& c) {
 // dtype: one of the two formats, descales with e4m3 alone (fa2_fwd_decode and fa2_fwd_decode_fp8 state a format that passes)
 static bool cache_format_ok(const CacheDesc& c) { return (c.format == FA2_CACHE_16BIT || c.fp8()) && (!c.descaled() || c.fp8()); }
 
-// One decode call, described: the three entries fill it by field name; a plan or size query fills the sizes alone.
+// One decode call, described: the four entries fill it by field name; a plan or size query fills the sizes alone.
 struct DecodeCall : CacheDesc {
+    bool wide = false;                                              // fa2_fwd_decode_wide: head dim 256 on csrc/fa2_decode_wide.hip.h's kernel
     int dtype = 0, B = 0, H = 0, Hkv = 0, Nq = 0, D = 0;
     const void* q = nullptr;
     void* o = nullptr;
@@ -1588,25 +1590,28 @@ struct DecodeCall : CacheDesc {
     void* stream = nullptr;
 };
 
-// The sizes of a decode call, in the documented order (shape, then head dim); *row_tiles: the row tiles the kernel runs (1, 2 or 4).
-static int decode_check_shape(const DecodeCall& c, int* row_tiles) {
+// The sizes of a decode call, in the documented order (shape, then head dim); *row_tiles: the row tiles the kernel runs (1, 2 or 4; the wide kernel: 1 or
+// 2 per workgroup, in *row_blocks workgroups).
+static int decode_check_shape(const DecodeCall& c, int* row_tiles, int* row_blocks = nullptr) {
     if (c.B < 1 || c.H < 1 || c.Hkv < 1 || c.Nq < 1 || c.D < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return FA2_ERR_BAD_SHAPE;
     const int64_t rows = (int64_t)c.Nq * (c.H / c.Hkv);
     if (rows > fa2::kDecodeMaxRows || !cache_paging_ok(c) || c.num_splits < 0 || c.num_splits > fa2::kDecodeMaxSplit) return FA2_ERR_BAD_SHAPE;
-    if (c.D != 64 && c.D != 128) return FA2_ERR_HEAD_DIM;
+    if (c.wide ? c.D != fa2::kDecodeWideHD : c.D != 64 && c.D != 128) return FA2_ERR_HEAD_DIM;
     const int rt = (int)((rows + 15) / 16);
-    *row_tiles = rt == 3 ? 4 : rt;
+    *row_tiles = c.wide ? fa2::decode_wide_row_tiles((int)rows) : rt == 3 ? 4 : rt;
+    if (row_blocks) *row_blocks = c.wide ? fa2::decode_wide_row_blocks((int)rows) : 1;
     return FA2_OK;
 }
 
 // The split: a pure function of the shape, the capacity and the CU count (the lengths live on the device).  One workgroup per (sequence, K / V head,
 // part) streams its share of K and V once; B * Hkv * row_tiles >= CUs: the chip is covered, no split.  Otherwise two workgroups per CU's worth of
 // parts (a workgroup is 4 waves and 36 KiB of LDS: two fit), at most 16, and no part shorter than 8 key tiles of the capacity (two per wave).
-static int decode_split(int B, int Hkv, int row_tiles, int capacity_tiles, int num_splits) {
+// The wide kernel (per_cu = 1, row_tiles = its row blocks): a workgroup fills a CU on its own (67 or 84 KiB of LDS, 512 registers per lane).
+static int decode_split(int B, int Hkv, int row_tiles, int capacity_tiles, int num_splits, int per_cu = 2) {
     if (num_splits > 0) return num_splits;
     const int64_t work = (int64_t)B * Hkv * row_tiles, cus = fa2::device_cus();
     if (work >= cus) return 1;
-    int64_t S = 2 * cus / work;
+    int64_t S = per_cu * cus / work;
     if (S > fa2::kDecodeMaxSplit) S = fa2::kDecodeMaxSplit;
     if (S > capacity_tiles / 8) S = capacity_tiles / 8;
     return S < 1 ? 1 : (int)S;
@@ -1617,8 +1622,8 @@ static int decode_split(int B, int Hkv, int row_tiles, int capacity_tiles, int n
 // of a tile or two.  A window that reaches across the whole cache changes nothing.
 static int decode_plan(const DecodeCall& c, int window_left, fa2_decode_plan_t* plan) {
     if (window_left < -1) return FA2_ERR_BAD_SHAPE;
-    int row_tiles = 0;
-    if (int rc = decode_check_shape(c, &row_tiles)) return rc;
+    int row_tiles = 0, row_blocks = 1;
+    if (int rc = decode_check_shape(c, &row_tiles, &row_blocks)) return rc;
     if (c.dtype != FA2_DTYPE_F16 && c.dtype != FA2_DTYPE_BF16) return FA2_ERR_DTYPE;
     int64_t span_tiles = (c.capacity_keys() + fa2::kDecodeTile - 1) / fa2::kDecodeTile;
     if (window_left >= 0) {
@@ -1628,7 +1633,7 @@ static int decode_plan(const DecodeCall& c, int window_left, fa2_decode_plan_t* 
     plan->kernel = FA2_KERNEL_HIP_DECODE;
     plan->row_tiles = row_tiles;
     plan->key_tile = fa2::kDecodeTile;
-    plan->nsplit = decode_split(c.B, c.Hkv, row_tiles, (int)span_tiles, c.num_splits);
+    plan->nsplit = c.wide ? decode_split(c.B, c.Hkv, row_blocks, (int)span_tiles, c.num_splits, 1) : decode_split(c.B, c.Hkv, row_tiles, (int)span_tiles, c.num_splits);
     return FA2_OK;
 }
 
@@ -1664,6 +1669,23 @@ size_t fa2_fwd_decode_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, 
     return fa2_fwd_decode_window_workspace_bytes(dtype, B, H, Hkv, Nq, D, capacity, page_size, num_splits, -1);
 }
 
+// ---- ... at head dim 256: the same queries for the wide kernel, whose workgroups serve at most 32 rows and fill a CU each
+int fa2_fwd_decode_wide_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left,
+                             fa2_decode_plan_t* plan) {
+    if (!plan) return FA2_ERR_NULL_POINTER;
+    std::memset(plan, 0, sizeof(*plan));
+    FA2_DECODE_SIZES(c);
+    c.wide = true;
+    return decode_plan(c, window_left, plan);
+}
+
+size_t fa2_fwd_decode_wide_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left) {
+    fa2_decode_plan_t plan;
+    FA2_DECODE_SIZES(c);
+    c.wide = true;
+    return decode_plan(c, window_left, &plan) ? 0 : decode_ws_need(c, plan);
+}
+
 int fa2_decode_part_range(int64_t len, int64_t capacity_keys, int Nq, int tile, int nsplit, int part, int* first_tile, int* ntiles) {
     if (!first_tile || !ntiles) return FA2_ERR_NULL_POINTER;
     if (capacity_keys < 0 || capacity_keys > 0x7fffffffLL || Nq < 1 || tile < 1 || nsplit < 1 || nsplit > fa2::kDecodeMaxSplit || part < 0 || part >= nsplit)
@@ -1681,7 +1703,7 @@ int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int
     return FA2_OK;
 }
 
-// One body for fa2_fwd_decode, fa2_fwd_decode_fp8 and fa2_fwd_decode_window (fp8: e4m3 caches, whose element strides are bytes; the descales and their
+// One body for fa2_fwd_decode, fa2_fwd_decode_fp8, fa2_fwd_decode_window and fa2_fwd_decode_wide (fp8: e4m3 caches, whose element strides are bytes; the descales and their
 // strides belong to e4m3 caches alone).  The checks run in the documented order; the window entry's arguments are checked where their kind is.
 // A call whose window reaches across the whole cache, without a cap and without slopes, runs the plain kernels: the same bits as the older entries.
 static int decode_run(const DecodeCall& c) {
@@ -1727,6 +1749,8 @@ static int decode_run(const DecodeCall& c) {
     }
     const bool bf16 = c.dtype == FA2_DTYPE_BF16;
     hipStream_t const stream = (hipStream_t)c.stream;
+    if (c.wide)
+        return c.fp8() ? fa2::launch_decode_wide_fp8(bf16, p, plan.row_tiles, banded, stream) : fa2::launch_decode_wide(bf16, p, plan.row_tiles, banded, stream);
     if (banded)
         return c.fp8() ? fa2::launch_decode_band_fp8(bf16, c.D, p, plan.row_tiles, stream) : fa2::launch_decode_band(bf16, c.D, p, plan.row_tiles, stream);
     return c.fp8() ? fa2::launch_decode_fp8(bf16, c.D, p, plan.row_tiles, stream) : fa2::launch_decode(bf16, c.D, p, plan.row_tiles, stream);
@@ -1770,6 +1794,21 @@ int fa2_fwd_decode_window(int dtype, int cache_format, const void* q, const void
                           size_t workspace_bytes, void* hip_stream) {
     FA2_DECODE_CALL(c);
     FA2_DECODE_DESCALES(c);
+    c.format = cache_format;
+    c.window_left = window_left; c.softcap = softcap; c.slopes = alibi_slopes; c.slope_stride = alibi_stride;
+    return decode_run(c);
+}
+
+// ---- ... and fa2_fwd_decode_window's call at head dim 256, on the wide-head kernel (csrc/fa2_decode_wide.hip.h)
+int fa2_fwd_decode_wide(int dtype, int cache_format, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse, const int* cache_seqlens,
+                        const int* block_table, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages, const int64_t q_strides[3],
+                        const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[2],
+                        int64_t block_table_stride, float scale, const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                        int window_left, float softcap, const float* alibi_slopes, int64_t alibi_stride, int num_splits, void* workspace,
+                        size_t workspace_bytes, void* hip_stream) {
+    FA2_DECODE_CALL(c);
+    FA2_DECODE_DESCALES(c);
+    c.wide = true;
     c.format = cache_format;
     c.window_left = window_left; c.softcap = softcap; c.slopes = alibi_slopes; c.slope_stride = alibi_stride;
     return decode_run(c);

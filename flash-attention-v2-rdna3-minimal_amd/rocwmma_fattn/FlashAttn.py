@@ -1413,7 +1413,9 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     Masking is bottom-right causal per sequence: query row i of sequence b sits at position len_b - Nq + i and sees the keys j <= that position (Nq = 1:
     every valid key).  Rows at a negative position return zeros (lse -inf).  Keys at or beyond len_b and unused pages contribute nothing whatever
     they hold; lengths and page ids are clamped into the cache in-kernel, so wrong ones give a wrong answer, never an out-of-bounds read.
-    Hkv divides H; D is 64 or 128; Nq * (H / Hkv) <= 64.  Anything else raises ValueError (longer chunks: flash_attention_varlen).
+    Hkv divides H; D is 64, 128 or 256; Nq * (H / Hkv) <= 64.  Anything else raises ValueError (longer chunks: flash_attention_varlen).  D = 256
+    (Gemma-2 / Gemma-3) runs the wide-head kernel with every keyword below (C-ABI fa2_fwd_decode_wide): a workgroup serves at most 32 rows there, so
+    33 .. 64 rows per K / V head stream K and V twice.
     Returns o [B, Nq, H, D]; with return_lse=True also lse f32 [B, H, Nq] in natural-log units (merge_attention combines such pairs).
     num_splits: 0 = the library's plan, 1 .. 16 = that many parts per (sequence, K / V head).  Inference only: no backward.
     FP8 caches: k_cache and v_cache may both be torch.float8_e4m3fn (OCP e4m3, gfx950's FP8; not e5m2, not fnuz) in the same two layouts, q staying
@@ -1451,8 +1453,8 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
         raise ValueError("fa2: inconsistent q / k_cache / v_cache shapes %s %s %s" % (tuple(q.shape), tuple(k_cache.shape), tuple(v_cache.shape)))
     if B < 1 or Nq < 1 or Hkv < 1 or H % Hkv:
         raise ValueError("fa2: the head count of the cache (%d) must divide the head count of q (%d), and B, Nq >= 1; %s" % (Hkv, H, _DECODE_ROUTE))
-    if D not in (64, 128):
-        raise ValueError("fa2: flash_attention_decode serves head dims 64 and 128, got %d; %s" % (D, _DECODE_ROUTE))
+    if D not in (64, 128, 256):
+        raise ValueError("fa2: flash_attention_decode serves head dims 64 and 128, and 256 on the wide-head kernel, got %d; %s" % (D, _DECODE_ROUTE))
     if Nq * (H // Hkv) > _DECODE_MAX_ROWS:
         raise ValueError("fa2: flash_attention_decode serves Nq * (H / Hkv) <= %d query rows per K / V head, got %d * %d; %s"
                          % (_DECODE_MAX_ROWS, Nq, H // Hkv, _DECODE_ROUTE))
@@ -1481,7 +1483,10 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
     with torch.cuda.device(dev):
         stream = _raw_stream(dev)
         banded = window_left >= 0 or scoremod is not None
-        if banded:
+        wide = D == 256                                # the superset entry of the wide-head kernel, banded or not
+        if wide:
+            need = lib.fa2_fwd_decode_wide_workspace_bytes(code, B, H, Hkv, Nq, D, cache.capacity, cache.page_size, num_splits, window_left)
+        elif banded:
             need = lib.fa2_fwd_decode_window_workspace_bytes(code, B, H, Hkv, Nq, D, cache.capacity, cache.page_size, num_splits, window_left)
         else:
             need = (lib.fa2_fwd_decode_fp8_workspace_bytes if fp8 else lib.fa2_fwd_decode_workspace_bytes)(code, B, H, Hkv, Nq, D, cache.capacity, cache.page_size,
@@ -1492,9 +1497,9 @@ def flash_attention_decode(q, k_cache, v_cache, cache_seqlens, block_table=None,
         head = (q.data_ptr(), *cache.ptrs, o.data_ptr(), lse.data_ptr(), *cache.tables, B, H, Hkv, Nq, D, *cache.sizes, _bnhd(q), *cache.strides, _bnhd(o),
                 _fa2_lib.strides2(lse.stride(0), lse.stride(1)), cache.bts, float(scale))
         tail = (num_splits, None if ws is None else ws.data_ptr(), need, stream)
-        if banded:
-            rc = lib.fa2_fwd_decode_window(code, cache.fmt, *head, *cache.descales, window_left,
-                                           *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), *tail)
+        if wide or banded:
+            rc = (lib.fa2_fwd_decode_wide if wide else lib.fa2_fwd_decode_window)(code, cache.fmt, *head, *cache.descales, window_left,
+                                                                                  *_scoremod_args(scoremod if scoremod is not None else (0.0, None)), *tail)
         elif fp8:
             rc = lib.fa2_fwd_decode_fp8(code, *head, *cache.descales, *tail)
         else:

@@ -184,6 +184,12 @@ SYMBOLS = {
     "fa2_fwd_decode_window_plan": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(DecodePlan)]),
     "fa2_fwd_decode_window_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
     "fa2_decode_window_part_range": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    # ... at head dim 256 (the wide-head kernel): fa2_fwd_decode_window's three lists
+    "fa2_fwd_decode_wide": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 7 + [ctypes.c_int] * 8 + [_i64p] * 5 +
+                            [ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, _i64p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
+                             ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fa2_fwd_decode_wide_plan": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(DecodePlan)]),
+    "fa2_fwd_decode_wide_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
     # decode on a latent (MLA) cache: q kv_cache o lse cache_seqlens block_table, B H Nq D Dv capacity page_size num_pages, the q kv o stride triples, the
     # lse pair, the block-table row stride, scale, num_splits, workspace, bytes, stream
     "fa2_fwd_decode_mla": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_int] * 8 + [_i64p] * 4 +

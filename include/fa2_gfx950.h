@@ -759,6 +759,32 @@ size_t fa2_fwd_decode_window_workspace_bytes(int dtype, int B, int H, int Hkv, i
 int fa2_decode_window_part_range(int64_t len, int64_t capacity_keys, int Nq, int window_left, int tile, int nsplit, int part, int* first_tile,
                                  int* ntiles);
 
+/* ---- ... at head dim 256 (Gemma-2 2B / 9B, Gemma-3 1B / 4B / 12B): fa2_fwd_decode_window's call, argument for argument, on a kernel whose register
+ * and LDS plan is made for 256 columns (csrc/fa2_decode_wide.hip.h).  Everything fa2_fwd_decode_window documents holds here —
+ * both cache formats and layouts, device-side lengths and block table with their clamps, bottom-right causal masking, window_left, softcap and
+ * alibi_slopes, Nq * H / Hkv <= 64 rows per K / V head, 1 .. 16 parts and the same combine, the log2 LSE, dead rows exactly 0 / -inf, keys at or beyond
+ * len and keys below the window contributing nothing whatever they hold, a tile wholly below the window never addressed, numerical contract 0, the
+ * part ranges of fa2_decode_part_range / fa2_decode_window_part_range — with these differences:
+ *   D      : exactly 256; every other head dim, 64 and 128 included, is FA2_ERR_HEAD_DIM (those belong to the entries above).
+ *   rows   : a workgroup serves at most 32 rows (two row tiles); 33 .. 64 rows run as two row blocks that each stream K and V.  plan.row_tiles is the
+ *            tiles per workgroup (1 or 2); the row blocks are ceil(Nq * (H / Hkv) / 32).
+ *   plan   : ONE workgroup per CU — no split when B * Hkv * row_blocks >= CUs, else floor(CUs / (B * Hkv * row_blocks)) parts, at most 16 and at most
+ *            one per 8 key tiles of the span a sequence can sweep (fa2_fwd_decode_window_plan's span).  A pure host function of the shape, the
+ *            capacity, the CU count and window_left.  The workspace formula is fa2_fwd_decode's: each row block writes its own rows of a part.
+ * The checks, their codes and their order are fa2_fwd_decode_window's.  No instantiation uses scratch. */
+int fa2_fwd_decode_wide(int dtype, int cache_format, const void* q, const void* k_cache, const void* v_cache, void* o, float* lse,
+                        const int* cache_seqlens, const int* block_table,
+                        int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_pages,
+                        const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                        const int64_t lse_strides[2], int64_t block_table_stride, float scale,
+                        const float* k_descale, const float* v_descale, const int64_t descale_strides[2],
+                        int window_left, float softcap, const float* alibi_slopes, int64_t alibi_stride,
+                        int num_splits, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fa2_fwd_decode_wide_plan(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits, int window_left,
+                             fa2_decode_plan_t* plan);
+size_t fa2_fwd_decode_wide_workspace_bytes(int dtype, int B, int H, int Hkv, int Nq, int D, int capacity, int page_size, int num_splits,
+                                           int window_left);
+
 /* ---- Decode attention on a multi-head-latent (MLA) KV cache: the decode step of DeepSeek-V2 / V3 / R1 style models with the up-projections absorbed
  * into the query and the output.  The cache holds ONE row of D = 576 columns per token, shared by all heads (512 of compressed KV, then 64 of rotary
  * key); its first Dv = 512 columns are also the value.  With len and the positions as in fa2_fwd_decode,

@@ -1,5 +1,5 @@
 """The C argument order of the serving entries, for the tests and the tools alike: fa2_fwd_decode, fa2_fwd_decode_fp8, fa2_fwd_decode_window,
-fa2_fwd_decode_mla, fa2_kvcache_append, fa2_kvcache_append_varlen, fa2_kvcache_append_mla, fa2_kvcache_append_mla_varlen, fa2_fwd_prefill and
+fa2_fwd_decode_wide, fa2_fwd_decode_mla, fa2_kvcache_append, fa2_kvcache_append_varlen, fa2_kvcache_append_mla, fa2_kvcache_append_mla_varlen, fa2_fwd_prefill and
 fa2_fwd_prefill_fp8 by keyword (ENTRIES, c_args: the only copy under tests/ and
 tools/), what the tensors of a decode call say (tensor_kw) and the GPU call on NaN-filled outputs and workspace (decode_c).  tests/decode_calls.py hands
 these on to the tests beside what only tests need; the tools import them here, so that a tool runs with nothing but itself, this file and the package."""
@@ -46,6 +46,7 @@ ENTRIES = {      # entry -> (symbol, its arguments by keyword, its workspace que
     "plain": ("fa2_fwd_decode", ("dtype",) + _HEAD + _TAIL, "fa2_fwd_decode_workspace_bytes"),
     "fp8": ("fa2_fwd_decode_fp8", ("dtype",) + _HEAD + _DESCALES + _TAIL, "fa2_fwd_decode_fp8_workspace_bytes"),
     "window": ("fa2_fwd_decode_window", ("dtype", "fmt") + _HEAD + _DESCALES + _SCOREMOD + _TAIL, "fa2_fwd_decode_window_workspace_bytes"),
+    "wide": ("fa2_fwd_decode_wide", ("dtype", "fmt") + _HEAD + _DESCALES + _SCOREMOD + _TAIL, "fa2_fwd_decode_wide_workspace_bytes"),      # head dim 256
     "append": ("fa2_kvcache_append", ("dtype", "fmt", "kn", "vn", "k", "v", "lens", "bt", "B", "Hkv", "N", "D", "cap", "page", "pages", "kns", "vns", "ks", "vs", "bts",
                                       "q", "qo", "H", "Nq", "qs", "qos", "cos", "sin", "rdt", "rot", "sro", "ros", "inter") + _DESCALES + ("stream",), None),
     "append_varlen": ("fa2_kvcache_append_varlen", ("dtype", "fmt", "kn", "vn", "k", "v", "cu", "lens", "bt", "B", "total", "Hkv", "D", "cap", "page", "pages", "kns", "vns",
@@ -107,7 +108,7 @@ def decode_c(entry, q, k, v, lens, num_splits, window_left=-1, softcap=0.0, slop
     no, nl = nan_out(q)
     o, lse = no if o is None else o, nl if lse is None else lse
     kw = tensor_kw(q, k, v, o, lse, lens, block_table, kd, vd, scale)
-    sizes = [kw[n] for n in ("dtype", "B", "H", "Hkv", "Nq", "D", "cap", "page")] + [num_splits] + ([window_left] if entry == "window" else [])
+    sizes = [kw[n] for n in ("dtype", "B", "H", "Hkv", "Nq", "D", "cap", "page")] + [num_splits] + ([window_left] if entry in ("window", "wide") else [])
     need = getattr(_fa2_lib.load(), ENTRIES[entry][2])(*sizes)
     ws = torch.full((max(need, 16) // 4,), float("nan"), dtype=torch.float32, device=q.device)
     rc = call(entry, **kw, wl=window_left, cap_=softcap, sl=_ptr(slopes), st=0 if slopes is None or slopes.dim() == 1 else slopes.stride(0), ns=num_splits,

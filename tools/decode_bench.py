@@ -24,6 +24,7 @@ Each row first checks the routes against each other on the timed inputs (fp16 1e
 The same K / V are read in every iteration, so caches up to the 256 MB of Infinity Cache are served from it in every route alike.
 """
 import argparse
+import ctypes
 import os
 import sys
 
@@ -34,7 +35,8 @@ import torch  # noqa: E402
 
 from benchlib import close, interleaved, paged_pool  # noqa: E402
 from rocwmma_fattn import _fa2_lib  # noqa: E402
-from rocwmma_fattn.FlashAttn import flash_attention, flash_attention_decode, flash_attention_varlen  # noqa: E402
+from rocwmma_fattn.FlashAttn import (flash_attention, flash_attention_decode, flash_attention_prefill, flash_attention_prefill_fp8,  # noqa: E402
+                                     flash_attention_varlen)
 
 HBM_TBS = 6.3
 UNIFORM = [  # (label, B, H, Hkv, Nq, keys, D, dtype)
@@ -195,11 +197,58 @@ def ragged_row(label, B, H, Hkv, Nq, lo, hi, D, dt, rounds, iters):
     report(label, shape, t, 2 * Hkv * sum(lens_h) * D * 2, "varlen")
 
 
+WIDE = [  # (label, B, H, Hkv, Nq, lengths: keys or (shortest, longest), dtype, e4m3 cache, flash_attention_decode's keywords); D = 256
+    ("w_b32", 32, 16, 8, 1, 4096, torch.bfloat16, False, {}),
+    ("w_b1", 1, 16, 8, 1, 8192, torch.bfloat16, False, {}),
+    ("w_b8_nq4", 8, 16, 8, 4, 8192, torch.bfloat16, False, {}),
+    ("w_ragged_b32", 32, 16, 8, 1, (256, 8192), torch.bfloat16, False, {}),
+    ("w_b32_win1023", 32, 16, 8, 1, 4096, torch.bfloat16, False, dict(window=1023)),
+    ("w_b32_cap50", 32, 16, 8, 1, 4096, torch.bfloat16, False, dict(softcap=50.0, window=4095)),
+    ("w_b32_e4m3", 32, 16, 8, 1, 4096, torch.bfloat16, True, {}),
+    ("w_b8_h64_mqa", 8, 64, 1, 1, 8192, torch.bfloat16, False, {}),      # 64 rows per K / V head: two row blocks
+]
+
+
+def wide_row(label, B, H, Hkv, Nq, keys, dt, fp8, kw, rounds, iters):
+    """--rows wide: head dim 256.  decode is flash_attention_decode on the wide-head kernel; prefill — the BASELINE — is the one
+    in-place route these shapes had before it, flash_attention_prefill (e4m3: _fp8) on the same cache with Nq packed rows per sequence."""
+    dev, D = torch.device("cuda", 0), 256
+    g = torch.Generator(device="cpu").manual_seed(1)
+    lens_h = [keys] * B if isinstance(keys, int) else torch.randint(keys[0], keys[1] + 1, (B,), generator=g).tolist()
+    nmax = max(lens_h) + (256 if isinstance(keys, int) else 0)
+    q = torch.randn((B, Nq, H, D), device=dev, dtype=dt)
+    kc, vc = (torch.randn((B, nmax, Hkv, D), device=dev, dtype=dt) for _ in range(2))
+    desc = {}
+    if fp8:
+        (kc, kd, _), (vc, vd, _) = (quantise(t, g) for t in (kc, vc))
+        desc = dict(k_descale=kd, v_descale=vd)
+    lens = torch.tensor(lens_h, dtype=torch.int32, device=dev)
+    cu_q = torch.arange(0, (B + 1) * Nq, Nq, dtype=torch.int32, device=dev)
+    qp = q.reshape(B * Nq, H, D)
+    prefill = flash_attention_prefill_fp8 if fp8 else flash_attention_prefill
+    fns = {"decode": lambda: flash_attention_decode(q, kc, vc, lens, **desc, **kw),
+           "prefill": lambda: prefill(qp, kc, vc, cu_q, lens, max_seqlen_q=Nq, **desc, **kw)}
+    with torch.no_grad():
+        close("decode_bench", fns["decode"]().reshape(B * Nq, H, D), fns["prefill"](), dt, label + ": decode and prefill")
+        t = interleaved(fns, rounds, iters)
+    plan = _fa2_lib.DecodePlan()
+    _fa2_lib.check(_fa2_lib.load().fa2_fwd_decode_wide_plan(0 if dt == torch.float16 else 1, B, H, Hkv, Nq, D, nmax, 0, 0, kw.get("window", -1), ctypes.byref(plan)))
+    lo = [max(0, n - Nq - kw["window"]) if "window" in kw else 0 for n in lens_h]                  # keys below a window are not valid bytes
+    shape = "B%d H%d Hkv%d Nq%d keys %d .. %d D%d %s%s %s (split %d, %d row tile%s x %d row block%s)" % (
+        B, H, Hkv, Nq, min(lens_h), max(lens_h), D, "fp16" if dt == torch.float16 else "bf16", " e4m3 cache" if fp8 else "", kw or "", plan.nsplit, plan.row_tiles,
+        "" if plan.row_tiles == 1 else "s", -(-Nq * (H // Hkv) // 32), "" if Nq * (H // Hkv) <= 32 else "s")
+    valid = 2 * Hkv * sum(n - l for n, l in zip(lens_h, lo)) * D * (1 if fp8 else 2)
+    report(label, shape, t, valid, "prefill")
+    (bm, bl, bh), (dm, dl, dh) = t["prefill"], t["decode"]
+    print("    gap %.1f us against the sum of the spreads %.1f us: %s" % ((bm - dm) * 1e3, ((bh - bl) + (dh - dl)) * 1e3,
+                                                                        "a win" if bm - dm > (bh - bl) + (dh - dl) else "NO win"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--rows", default="all", choices=("uniform", "ragged", "fp8", "all"))
+    ap.add_argument("--rows", default="all", choices=("uniform", "ragged", "fp8", "wide", "all"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench: needs a ROCm GPU (a timing taken anywhere else says nothing)")
@@ -213,6 +262,9 @@ def main():
         for r in FP8_UNIFORM:
             fp8_uniform_row(*r, a.rounds, a.iters)
         fp8_ragged_row(*RAGGED, a.rounds, a.iters)
+    if a.rows == "wide":                         # behind the flag: "all" stays the rows it was
+        for r in WIDE:
+            wide_row(*r, a.rounds, a.iters)
 
 
 if __name__ == "__main__":
